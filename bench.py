@@ -22,6 +22,12 @@ HBM bytes come from the rocprofv3 PMC passes committed under profiles/ WHEN they
 kernel sources of this checkout (source hash), otherwise from the traffic model evaluated on this run's
 own path counts (mi_last_pipeline_counts); `traffic_source` says which.  `roofline.valu` is the
 second bound of this VALU-heavy path (issue utilisation and live lanes, committed PMC only).
+
+A plain run prints the headline (`value`, `ms_per_step` = wall time of one timed step) and the workload's description
+only.  `--full` adds what takes more than the timed steps: `roofline` (and its consistency check) and `cpu_baseline`
+(the CPU oracle built and timed on this host, N = 1 only; `--no-cpu-baseline` leaves it out).  `--dump-outputs DIR`
+writes what rank 0's timed path returned in its LAST timed step (the f32 image and the tone-mapped u8 image, both as
+float32) to DIR/<name>.npy after the timed steps; the scene and the seeds (1 + step) depend on the arguments only.
 """
 import argparse
 import hashlib
@@ -158,29 +164,10 @@ def cpu_model():
     return "unknown CPU"
 
 
-def report(args, sc, flat, world, backend, route, dt, kernel_ms, pipe, counts, extra_config=None):
-    """Rank 0's ONE JSON line.  `kernel_ms` = pipeline pass of the slowest device (HIP events on its launch stream), `pipe` the
-    per-kernel sums and `counts` the path counts of ONE device (device 0) over the timed steps."""
-    cam = sc.camera
-    samples_per_frame = cam.screen_width * cam.screen_height * cam.aa_sample_count
-    ms_per_step = dt / args.steps * 1e3
-    value = samples_per_frame * args.steps / dt / 1e6
-    b_sample, segs_oracle = algorithmic_bytes_per_sample(args.config, cam.aa_sample_count)
-    wavefront = args.variant in (0, 7)
-    # What the headline counts.  `value` divides ALL W*H*spp samples by the time, as the metric is defined; the samples of dead
-    # tiles (32x32 tiles from which no camera ray can reach anything: black by tracing.rs:306, no ray is generated) cost nothing,
-    # so the rate over the pixels that see something is printed beside it, and the segment rate comes from the device's own count of
-    # Scene::intersect_ray evaluations of the timed steps — not from the oracle's per-sample mean, which counts one segment for
-    # every void sample.  `counts` are device 0's: with N > 1 ranks the segment figures are left out.
-    dead_frac = live_rate = segs = mseg = None
-    if counts and wavefront and world == 1:
-        dead_frac = counts["dead_tile_samples"] / float(samples_per_frame)
-        live_rate = (samples_per_frame - counts["dead_tile_samples"]) * args.steps / dt / 1e6
-        if counts.get("segments"):
-            segs = counts["segments"] / float(samples_per_frame)
-            mseg = counts["segments"] * args.steps / dt / 1e6
+def roofline(args, flat, world, wavefront, kernel_ms, pipe, counts, b_sample):
+    """--full only: the HBM roofline of the dominant kernel group (the pipeline pass of ONE device) and the VALU figures beside it,
+    from the timed steps' per-kernel times and path counts and the committed PMC of the same kernel sources."""
     per_step = {k: (v / args.steps) for k, v in pipe.items()}
-    # ---- HBM roofline of the dominant kernel group (the pipeline pass of ONE device) ----
     pmc, why_not = (committed_pmc(args.config) if world == 1 and not args.spp and wavefront and not args.flags and not args.max_state_gb
                     else (None, "not the profiled configuration"))
     model_bytes = traffic_model(counts, flat.desc.n_meshes) if (wavefront and counts and counts["passes"]) else None
@@ -211,6 +198,58 @@ def report(args, sc, flat, world, backend, route, dt, kernel_ms, pipe, counts, e
         if valu:
             dom = max(valu, key=lambda k: valu[k]["ms"])
             valu_issue, valu_lane = valu[dom]["issue_frac"], valu[dom]["lane_frac"]
+    # Two resources bound this path and NEITHER is saturated: `frac` is the HBM fraction of the
+    # pipeline pass (the key the bench contract names), `valu_lane_frac` the VALU lane-throughput fraction of the
+    # dominant kernel.  "bound" names the roofline `achieved`/`peak`/`frac` are quoted on, not a claim that it binds.
+    return {"bound": "hbm",
+            "kernel": "K1w pipeline pass (wf_main + wf_prefix + wf_trav per segment, wf_reduce)" if wavefront else "single-launch kernel",
+            "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": frac,
+            "frac_x2_corrected": (frac if pmc is not None else None), "frac_raw_counters": frac_raw,
+            "valu_issue_frac": valu_issue, "valu_lane_frac": valu_lane, "valu_kernel": dom,
+            "binding": "VALU instruction issue on partly filled waves. Measured ceiling on gfx950 (tools/microbench/valu_rates.hip): one wave64 "
+                       "VALU instruction per ~2.5 cycles per SIMD; the walkers run at 2.4-2.6 cycles per instruction and wf_main's class-A form at "
+                       "2.7 (valu.*.cycles_per_inst, from SQ_INSTS_VALU and GRBM_GUI_ACTIVE of the committed PMC) with 37-52 of 64 lanes live, so "
+                       "kernel time follows the instruction count (walkers: -4.6 % instructions = -4.4 % time, paired-layout A/B); wf_main's "
+                       "class-B form adds the latency of its per-lane gathers (3.4 cycles per instruction); HBM carries the path state at "
+                       "0.21-0.28 of its peak. valu_issue_frac keeps the nominal 2 cycles / 2.4 GHz of earlier rounds for comparison",
+            "traffic": traffic, "traffic_source": traffic_source,
+            "traffic_model_bytes": model_bytes, "path_counts": counts,
+            "kernel_ms": kernel_ms,
+            "per_step_ms": ({"wf_main": per_step["wf_main_ms"], "wf_trav": per_step["wf_trav_ms"],
+                             "wf_reduce": per_step["wf_reduce_ms"], "launches": per_step["launches"],
+                             "wf_trav_f": per_step["wf_trav_f_ms"], "wf_replay": per_step["wf_replay_ms"],
+                             "wf_main_class_a_beside_walkers": per_step["wf_main_a_ms"]}
+                            if per_step.get("launches") else None),
+            "valu": valu,
+            "algorithmic_bytes_per_sample": b_sample,
+            "note": "achieved = HBM bytes of one device's pipeline pass / its duration (HIP events on the launch stream). "
+                    "The path state streamed between the phase kernels IS the traffic; the scene (object list, BVH) is "
+                    "SGPR/LDS/L2-resident, so SURVEY 8(d)'s logical bytes are informational only. valu_issue_frac = "
+                    "SQ_INSTS_VALU x 2 cycles / (1024 SIMDs x 2.4 GHz x kernel time); valu_lane_frac = valu_issue_frac x "
+                    "active lanes / 64 (committed PMC of the same kernel sources only)"}
+
+
+def report(args, sc, flat, world, backend, route, dt, kernel_ms, pipe, counts, extra_config=None):
+    """Rank 0's ONE JSON line.  `kernel_ms` = pipeline pass of the slowest device (HIP events on its launch stream), `pipe` the
+    per-kernel sums and `counts` the path counts of ONE device (device 0) over the timed steps."""
+    cam = sc.camera
+    samples_per_frame = cam.screen_width * cam.screen_height * cam.aa_sample_count
+    ms_per_step = dt / args.steps * 1e3
+    value = samples_per_frame * args.steps / dt / 1e6
+    b_sample, segs_oracle = algorithmic_bytes_per_sample(args.config, cam.aa_sample_count)
+    wavefront = args.variant in (0, 7)
+    # What the headline counts.  `value` divides ALL W*H*spp samples by the time, as the metric is defined; the samples of dead
+    # tiles (32x32 tiles from which no camera ray can reach anything: black by tracing.rs:306, no ray is generated) cost nothing,
+    # so the rate over the pixels that see something is printed beside it, and the segment rate comes from the device's own count of
+    # Scene::intersect_ray evaluations of the timed steps — not from the oracle's per-sample mean, which counts one segment for
+    # every void sample.  `counts` are device 0's: with N > 1 ranks the segment figures are left out.
+    dead_frac = live_rate = segs = mseg = None
+    if counts and wavefront and world == 1:
+        dead_frac = counts["dead_tile_samples"] / float(samples_per_frame)
+        live_rate = (samples_per_frame - counts["dead_tile_samples"]) * args.steps / dt / 1e6
+        if counts.get("segments"):
+            segs = counts["segments"] / float(samples_per_frame)
+            mseg = counts["segments"] * args.steps / dt / 1e6
     out = {
         "metric": "Msamples/sec (=rays/sec) at 1080p Cornell+teapot, 256 spp; 1/2/4/8 GPU",
         "value": value, "unit": "Msamples/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -226,41 +265,32 @@ def report(args, sc, flat, world, backend, route, dt, kernel_ms, pipe, counts, e
                    "segments_per_sample_oracle": segs_oracle,
                    "multi_gpu_note": "N>1 numbers exist only where this script ran on a multi-GPU node; "
                                      "the builder's own N>1 figures are single-GPU rehearsals (DESIGN.md section 6)"},
-        # Two resources bound this path and NEITHER is saturated: `frac` is the HBM fraction of the
-        # pipeline pass (the key the bench contract names), `valu_lane_frac` the VALU lane-throughput fraction of the
-        # dominant kernel.  "bound" names the roofline `achieved`/`peak`/`frac` are quoted on, not a claim that it binds.
-        "roofline": {"bound": "hbm",
-                     "kernel": "K1w pipeline pass (wf_main + wf_prefix + wf_trav per segment, wf_reduce)" if wavefront else "single-launch kernel",
-                     "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": frac,
-                     "frac_x2_corrected": (frac if pmc is not None else None), "frac_raw_counters": frac_raw,
-                     "valu_issue_frac": valu_issue, "valu_lane_frac": valu_lane, "valu_kernel": dom,
-                     "binding": "VALU instruction issue on partly filled waves. Measured ceiling on gfx950 (tools/microbench/valu_rates.hip): one wave64 "
-                                "VALU instruction per ~2.5 cycles per SIMD; the walkers run at 2.4-2.6 cycles per instruction and wf_main's class-A form at "
-                                "2.7 (valu.*.cycles_per_inst, from SQ_INSTS_VALU and GRBM_GUI_ACTIVE of the committed PMC) with 37-52 of 64 lanes live, so "
-                                "kernel time follows the instruction count (walkers: -4.6 % instructions = -4.4 % time, paired-layout A/B); wf_main's "
-                                "class-B form adds the latency of its per-lane gathers (3.4 cycles per instruction); HBM carries the path state at "
-                                "0.21-0.28 of its peak. valu_issue_frac keeps the nominal 2 cycles / 2.4 GHz of earlier rounds for comparison",
-                     "traffic": traffic, "traffic_source": traffic_source,
-                     "traffic_model_bytes": model_bytes, "path_counts": counts,
-                     "kernel_ms": kernel_ms,
-                     "per_step_ms": ({"wf_main": per_step["wf_main_ms"], "wf_trav": per_step["wf_trav_ms"],
-                                      "wf_reduce": per_step["wf_reduce_ms"], "launches": per_step["launches"],
-                                      "wf_trav_f": per_step["wf_trav_f_ms"], "wf_replay": per_step["wf_replay_ms"],
-                                      "wf_main_class_a_beside_walkers": per_step["wf_main_a_ms"]}
-                                     if per_step.get("launches") else None),
-                     "valu": valu,
-                     "algorithmic_bytes_per_sample": b_sample,
-                     "note": "achieved = HBM bytes of one device's pipeline pass / its duration (HIP events on the launch stream). "
-                             "The path state streamed between the phase kernels IS the traffic; the scene (object list, BVH) is "
-                             "SGPR/LDS/L2-resident, so SURVEY 8(d)'s logical bytes are informational only. valu_issue_frac = "
-                             "SQ_INSTS_VALU x 2 cycles / (1024 SIMDs x 2.4 GHz x kernel time); valu_lane_frac = valu_issue_frac x "
-                             "active lanes / 64 (committed PMC of the same kernel sources only)"},
     }
     if extra_config:
         out["config"].update(extra_config)
-    if world == 1 and not args.no_cpu_baseline:
-        out["cpu_baseline"] = cpu_baseline(sc, flat)
+    if args.full:
+        out["roofline"] = roofline(args, flat, world, wavefront, kernel_ms, pipe, counts, b_sample)
+        if world == 1 and not args.no_cpu_baseline:
+            out["cpu_baseline"] = cpu_baseline(sc, flat)
     print(json.dumps(out), flush=True)
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(dirname, arrays, limit=DUMP_LIMIT_BYTES):
+    """--dump-outputs: every array as DIR/<name>.npy in float32.  Past `limit` bytes in all, each array is replaced by the same
+    seeded sample of its elements in every run (flattened, in index order), so that two builds stay comparable."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float32) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    budget = limit - 4096 * len(arrays)                 # room for the .npy headers
+    for name, a in arrays.items():
+        if total > budget:
+            keep = a.size * budget // total
+            a = a.reshape(-1)[np.sort(np.random.default_rng(0).choice(a.size, size=keep, replace=False))]
+        np.save(os.path.join(dirname, name + ".npy"), a)
 
 
 def run_in_process(args):
@@ -291,13 +321,16 @@ def run_in_process(args):
         # contract are inside the call, on both sides of every step)
         t0 = time.perf_counter()
         for s in range(args.steps):
-            _, _, _, st = m.render(cam, seed=1 + s, want_f32=False, want_u8=False, variant=args.variant, flags=args.flags, max_state_bytes=msb)
+            want = bool(args.dump_outputs) and s == args.steps - 1       # the images cross PCIe in the last step only when they are dumped
+            f32, u8, _, st = m.render(cam, seed=1 + s, want_f32=want, want_u8=want, variant=args.variant, flags=args.flags, max_state_bytes=msb)
             kms.append(st.kernel_ms)       # the slowest device's pipeline pass
             wall.append(st.total_ms)
             for k, v in dev0.last_pipeline_ms().items():
                 pipe[k] += v
             counts = dev0.last_pipeline_counts()
         dt = time.perf_counter() - t0
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, {"image_f32": f32, "image_u8": u8})
         report(args, sc, flat, args.gpus, "loopback test transport (all ranks on device 0: NOT a scaling figure)" if args.loopback else "rccl (mi_multi, in-process)",
                "mi_multi_* in one process (loopback test transport)" if args.loopback else "mi_multi_* in one process (native RCCL fan-in, include/mi_rt.h)",
                dt, sum(kms) / max(1, len(kms)), pipe, counts,
@@ -316,7 +349,10 @@ def main():
     ap.add_argument("--variant", type=int, default=0)
     ap.add_argument("--flags", type=int, default=0, help="mi_render_opts.flags (MI_OPT_*), developer A/B")
     ap.add_argument("--max-state-gb", type=float, default=0.0, help="mi_render_opts.max_state_bytes in GB (0 = the library's default budget)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out cpu_baseline")
+    ap.add_argument("--full", action="store_true", help="besides the headline: the roofline block (and its check) and cpu_baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's f32 and u8 images as DIR/image_f32.npy and DIR/image_u8.npy (float32)")
     ap.add_argument("--loopback", action="store_true", help="N ranks on device 0 through mi_multi_create_loopback (test transport; exercises the N >= 2 code, measures no scaling)")
     ap.add_argument("--via-multi", action="store_true", help="N = 1 through mi_multi_* as well (the route every N > 1 run without a launcher takes)")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend (nccl = RCCL; gloo only to rehearse N>1 on one GPU)")
@@ -324,6 +360,8 @@ def main():
     args = ap.parse_args()
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
 
     # Two ways to N GPUs.  Under torch.distributed.run (WORLD_SIZE set): one process per GPU, dist.py + torch's RCCL gather.
     # Without a launcher: N > 1 (or --via-multi) runs in THIS process through mi_multi_* (native RCCL inside the library).
@@ -390,6 +428,8 @@ def main():
     else:
         kernel_ms = sum(r.kernel_ms) / max(1, len(r.kernel_ms))
 
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"image_f32": r.image.cpu().numpy(), "image_u8": r.u8.cpu().numpy()})
     if rank == 0:
         report(args, sc, flat, world, (args.backend if world > 1 else None),
                "one process per GPU (torch.distributed.run), dist.py + torch.distributed.gather" if world > 1 else "one process, one GPU (mi_ctx_*)",

@@ -293,17 +293,63 @@ def test_rust_patch_set_is_complete_and_well_formed():
                 assert sorted(names) == sorted(want), (name, sname, sorted(names), sorted(want))
 
 
-def test_reference_patch_applies(tmp_path):
-    """rust/reference.patch (five one-line edits + four include! lines) applies to the reference's sources as they are."""
-    ref = "/root/reference/src"
-    if not os.path.isdir(ref):
-        pytest.skip("the reference is not on this box")
-    import shutil
-    shutil.copytree(ref, tmp_path / "src")
-    out = subprocess.run(["patch", "-p1", "--dry-run", "-i", os.path.join(ROOT, "rust", "reference.patch")], cwd=tmp_path,
-                         capture_output=True, text=True)
+def _patch_sides(patch_text):
+    """{path: (old lines, new lines, old ends without newline, new ends without newline)} of a unified diff, every line at the
+    1-based position its hunk header gives; the hunk headers' line counts are checked against the hunk bodies."""
+    files, cur, hunk = {}, None, None
+    for line in patch_text.splitlines():
+        if line.startswith("diff ") or line.startswith("--- "):
+            continue
+        if line.startswith("+++ "):
+            cur = files.setdefault(line[4:].split("/", 1)[1], ({}, {}, [False], [False]))
+            continue
+        m = re.match(r"@@ -(\d+)(?:,(\d+))? \+(\d+)(?:,(\d+))? @@", line)
+        if m:
+            if hunk:
+                assert hunk[0] == hunk[1] == 0 and hunk[2] == hunk[3] == 0, f"hunk line counts disagree with its body: {hunk}"
+            o, oc, n, nc = int(m[1]), int(m[2] or 1), int(m[3]), int(m[4] or 1)
+            hunk = [oc, 0, nc, 0, o, n, None]       # old lines left, 0, new lines left, 0, next old position, next new position, last side
+            continue
+        assert hunk is not None and cur is not None, line
+        tag, text = line[:1], line[1:]
+        if tag == "\\":
+            for side in hunk[6]:
+                cur[2 + side][0] = True
+            continue
+        sides = {" ": (0, 1), "-": (0,), "+": (1,)}[tag]
+        for side in sides:
+            cur[side][hunk[4 + side]] = text
+            hunk[4 + side] += 1
+            hunk[2 * side] -= 1
+        hunk[6] = sides
+    assert hunk and hunk[0] == 0 and hunk[2] == 0, f"last hunk's line counts disagree with its body: {hunk}"
+    return files
+
+
+def test_reference_patch_is_well_formed(tmp_path):
+    """rust/reference.patch (five one-line edits + four include! lines) is a well-formed unified diff that `patch` applies,
+    without fuzz, to files holding its context and removed lines where its hunk headers put them, and yields its added lines
+    there; the four include!d fragments and the two traits it names exist in rust/src/util."""
+    patch_path = os.path.join(ROOT, "rust", "reference.patch")
+    patch = open(patch_path).read()
+    sides = _patch_sides(patch)
+    assert sorted(sides) == ["src/util.rs", "src/util/geometry.rs", "src/util/materials.rs", "src/util/texture.rs", "src/util/tracing.rs"]
+    for path, (old, _, old_nonl, _) in sides.items():
+        lines = [old.get(i, f"// line {i}") for i in range(1, max(old) + 1)]
+        f = tmp_path / path
+        f.parent.mkdir(parents=True, exist_ok=True)
+        f.write_text("\n".join(lines) + ("" if old_nonl[0] else "\n"))
+    out = subprocess.run(["patch", "-p1", "-F0", "--no-backup-if-mismatch", "-i", patch_path], cwd=tmp_path, capture_output=True, text=True)
     assert out.returncode == 0, out.stdout + out.stderr
-    patch = open(os.path.join(ROOT, "rust", "reference.patch")).read()
+    for path, (_, new, _, new_nonl) in sides.items():
+        got = (tmp_path / path).read_text()
+        assert got.endswith("\n") != new_nonl[0], path
+        got = got.split("\n")
+        for i, text in new.items():
+            assert got[i - 1] == text, (path, i, got[i - 1], text)
+    util = os.path.join(ROOT, "rust", "src", "util")
     for frag in ("geometry_flatten.rs", "materials_flatten.rs", "texture_flatten.rs", "tracing_flatten.rs"):
-        assert f'include!("{frag}");' in patch
+        assert f'include!("{frag}");' in patch and os.path.exists(os.path.join(util, frag))
     assert "pub mod mi_rt;" in patch and "FlattenObject" in patch and "FlattenMaterial" in patch and "render_to_image_cpu" in patch
+    mi_rt = open(os.path.join(util, "mi_rt.rs")).read()
+    assert "pub trait FlattenObject" in mi_rt and "pub trait FlattenMaterial" in mi_rt

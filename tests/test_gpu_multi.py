@@ -121,9 +121,9 @@ def _run_bench(*extra, timeout=900):
 
 
 def test_bench_in_process_route_one_device():
-    """`python bench.py --gpus 1 --via-multi`: the route every N > 1 run without a launcher takes (mi_multi_* in this process,
-    no torch), on the one device this box has.  (Bit-identity of that route with mi_render: the first test of this file.)"""
-    out, rec = _run_bench("--gpus", "1", "--via-multi", "--steps", "2", "--warmup", "1", "--spp", "16", "--no-cpu-baseline")
+    """`python bench.py --gpus 1 --via-multi --full`: the route every N > 1 run without a launcher takes (mi_multi_* in this process,
+    no torch), on the one device this box has, with the roofline block.  (Bit-identity of that route with mi_render: the first test of this file.)"""
+    out, rec = _run_bench("--gpus", "1", "--via-multi", "--steps", "2", "--warmup", "1", "--spp", "16", "--full", "--no-cpu-baseline")
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-2000:]
     assert rec["n_gpus"] == 1 and rec["backend"].startswith("rccl (mi_multi") and rec["config"]["ranks"] == 1
     assert rec["value"] > 0 and rec["roofline"]["frac"] is not None and 0 < rec["roofline"]["frac"] <= 1

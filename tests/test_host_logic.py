@@ -1,5 +1,6 @@
 """Host-side logic above the C ABI (CPU only): OBJ reader (tobj semantics), cgmath helpers,
 scene flattening order, tile partition arithmetic and the N>1 gather path on gloo."""
+import gzip
 import os
 import subprocess
 import sys
@@ -12,7 +13,7 @@ from cs397raytracingsp22_amd import (Camera, ConvexVolume, Dielectric, Isotropic
                                      Triangle, abi, cgmath, dist, objload, scenes)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF_OBJ = "/root/reference/obj"
+REF_OBJ = os.path.join(ROOT, "tests", "golden", "obj")         # the reference's obj/ meshes, gzipped (sphere.obj is 2.3 MB)
 
 
 def test_obj_reader_fan_triangulation_and_single_index():
@@ -47,10 +48,12 @@ def test_obj_reader_keeps_first_model_only():
     assert [m.n_triangles for m in models] == [1, 2]            # the reference uses models.remove(0) (geometry.rs:157)
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_OBJ), reason="reference assets not present (GPU box)")
 @pytest.mark.parametrize("name,tris", [("teapot", 240), ("cube", 12), ("drone", 1736), ("sphere", 32512)])
-def test_committed_assets_equal_reader_output(name, tris):
-    m = objload.load_obj(os.path.join(REF_OBJ, name + ".obj"))[0]
+def test_committed_assets_equal_reader_output(name, tris, tmp_path):
+    obj = tmp_path / (name + ".obj")
+    with gzip.open(os.path.join(REF_OBJ, name + ".obj.gz"), "rb") as fh:
+        obj.write_bytes(fh.read())
+    m = objload.load_obj(str(obj))[0]
     a = scenes.load_asset_mesh(name)
     assert m.n_triangles == tris == a.n_triangles
     assert np.array_equal(m.positions, a.positions) and np.array_equal(m.indices, a.indices)
@@ -186,8 +189,8 @@ def test_bench_without_a_launcher_takes_the_in_process_route_and_fails_loudly_wi
 
 def test_bench_line_says_what_the_headline_counts(capsys):
     """bench.report() on fixed numbers (no GPU): the ONE JSON line carries the contract's keys, the dead-tile share, the rate over the
-    pixels that see something, the segment rate from the device's own count, and the HBM fraction as a range when a committed PMC
-    profile of the same kernel sources exists."""
+    pixels that see something, the segment rate from the device's own count, and (--full) the HBM fraction as a range when a committed
+    PMC profile of the same kernel sources exists."""
     import importlib.util
     import json
     import types
@@ -197,7 +200,7 @@ def test_bench_line_says_what_the_headline_counts(capsys):
     from cs397raytracingsp22_amd import scenes
     sc = scenes.config2()
     flat = sc.flatten()
-    args = types.SimpleNamespace(steps=5, config="cfg2", variant=0, spp=0, flags=0, max_state_gb=0.0, no_cpu_baseline=True, warmup=1)
+    args = types.SimpleNamespace(steps=5, config="cfg2", variant=0, spp=0, flags=0, max_state_gb=0.0, no_cpu_baseline=True, warmup=1, full=True)
     samples = 1920 * 1080 * 256
     counts = {"passes": 11, "paths_a": 494431863, "paths_b": 338823571, "queue_entries": 338823571, "sample_slots": 534773760,
               "pixels": 2088960, "segments": 1674413948, "dead_tile_samples": 212336640}
@@ -223,3 +226,9 @@ def test_bench_line_says_what_the_headline_counts(capsys):
     bench.report(args, sc, flat, 8, "nccl", "one process per GPU", 0.385, 76.8, pipe, counts)
     rec8 = json.loads(capsys.readouterr().out.strip().splitlines()[-1])
     assert rec8["n_gpus"] == 8 and rec8["config"]["dead_tile_frac"] is None and rec8["config"]["msegments_per_s"] is None and "cpu_baseline" not in rec8
+    # a plain run (no --full): the same headline and workload description, without the roofline block
+    args.full = False
+    bench.report(args, sc, flat, 1, None, "one process, one GPU (mi_ctx_*)", 0.385, 76.8, pipe, counts)
+    plain = json.loads(capsys.readouterr().out.strip().splitlines()[-1])
+    assert "roofline" not in plain and "cpu_baseline" not in plain
+    assert {k: v for k, v in rec.items() if k != "roofline"} == plain
