@@ -1027,9 +1027,12 @@ static int wf_prepare(mi_ctx* c, const mi_camera_desc* cam, uint32_t padded, uin
 
 // Primary-ray culling for the wavefront pipeline.  For every 32x32 tile: which Triangle / Sphere entries of
 // the kind-grouped list can a camera ray of that tile reach?  A perspective camera with lens_radius 0
-// sends every ray of a tile from the eye through the tile's pixel footprints — pixel centre +- 1 px
-// (tracing.rs:171-181: both jitter terms span +-0.5 px) — so the rays lie inside the pyramid spanned by
-// the four corner directions of the footprint, here widened by one more pixel (>= 5e-4 rad at any
+// sends every ray of a tile from the eye through the tile's pixel footprints.  The jitter (tracing.rs:166-173,
+// n = aa_sample_count, r = (u32)sqrt(n)) is (floor(i / r) - sqrt(n)/2) / sqrt(n) + (rand - n/2) / n px in x and
+// ((i % r) - sqrt(n)/2) / sqrt(n) + (rand - n/2) / n in y: from -1 px up to floor((n-1)/r) / sqrt(n) - 1/n px in x,
+// which exceeds +1 px when n is not a square (n = 3: +0.82, 8: +0.94, 31: +1.05, never +1.16 or more), and
+// below +1 px in y.  The 2 px margin below covers all of it: the rays lie inside the pyramid spanned by
+// the four corner directions of the footprint widened by 2 px (>= 5e-4 rad of slack beyond the jitter at any
 // resolution up to 2k rows, against f32 rounding of ~1e-7 in the generated directions).  An object that is
 // entirely on the outer side of one of the pyramid's four planes through the eye cannot be hit; it is
 // dropped from the tile's mask and its test — which would have missed — is not run.  f64 on the host,

@@ -53,3 +53,6 @@ def test_plain_run_dumps_the_last_timed_step(tmp_path, gpu_ctx, route):
     gpu_ctx.upload(sc.flatten())
     ref32, ref8, _, _ = gpu_ctx.render(sc.camera, seed=3)
     assert np.array_equal(f32, ref32, equal_nan=True) and np.array_equal(u8, ref8.astype(np.float32))
+    # the timed form (no signatures: dead tiles skipped) against the form the oracle tests pin (signatures: every sample traced)
+    sig32, sig8, _, _ = gpu_ctx.render(sc.camera, seed=3, want_sig=True)
+    assert np.array_equal(f32, sig32) and np.array_equal(u8, sig8.astype(np.float32))

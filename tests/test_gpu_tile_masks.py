@@ -42,17 +42,31 @@ def scatter_scene(seed, n_tri=40, n_sph=12, skew=True):
     return Scene(cam, [objs[i] for i in order])
 
 
+def _signature_free_equals(ctx, cam, seed, f32, u8, r32, r8, cnt):
+    """want_sig=False (the dead-tile shortcut live) against the signature render, bit for bit, and against the oracle directly;
+    every sample is either traced or a dead tile's (one camera ray that hits nothing in the oracle).  Returns the counts."""
+    fast, fast8, _, _ = ctx.render(cam, seed=seed, want_sig=False)
+    c = ctx.last_pipeline_counts()
+    assert np.array_equal(fast, f32) and np.array_equal(fast8, u8)
+    assert np.array_equal(np.signbit(fast), np.signbit(r32))                  # black is +0.0, dead tiles included
+    assert float((np.abs(fast.astype(np.float64) - r32) / np.maximum(1.0, np.abs(r32))).max()) <= 2e-5
+    assert int(np.abs(fast8.astype(int) - r8.astype(int)).max()) <= 1
+    assert c["segments"] + c["dead_tile_samples"] == cnt["segments"]
+    return c
+
+
 @pytest.mark.parametrize("seed", list(range(16)))
 def test_masked_primary_rays_take_the_oracles_paths(gpu_ctx, orc, seed):
     sc = scatter_scene(500 + seed, skew=(seed % 2 == 0))
     flat = sc.flatten()
     gpu_ctx.upload(flat)
-    f32, _, sig, _ = gpu_ctx.render(sc.camera, seed=seed, want_u8=False, want_sig=True)
-    r32, _, rsig, _ = orc.OracleScene(flat).render(sc.camera, seed=seed, want_u8=False)
+    f32, u8, sig, _ = gpu_ctx.render(sc.camera, seed=seed, want_sig=True)
+    r32, r8, rsig, cnt = orc.OracleScene(flat).render(sc.camera, seed=seed, want_counters=True)
     assert int((sig != rsig).sum()) == 0
     assert float((np.abs(f32.astype(np.float64) - r32) / np.maximum(1.0, np.abs(r32))).max()) <= 2e-5
     g32, _, gsig, _ = gpu_ctx.render(sc.camera, seed=seed, want_u8=False, want_sig=True, flags=abi.MI_OPT_NO_TILE_MASKS)
     assert np.array_equal(gsig, sig) and np.array_equal(g32, f32)          # masking changes nothing, bit for bit
+    _signature_free_equals(gpu_ctx, sc.camera, seed, f32, u8, r32, r8, cnt)
 
 
 def test_more_than_64_entries_disables_masking(gpu_ctx, orc):
@@ -113,9 +127,10 @@ def test_eye_in_the_plane_of_a_large_triangle(gpu_ctx, orc, height):
     sc = Scene(cam, objs)
     flat = sc.flatten()
     gpu_ctx.upload(flat)
-    _, _, sig, _ = gpu_ctx.render(cam, seed=5, want_u8=False, want_sig=True)
-    _, _, rsig, _ = orc.OracleScene(flat).render(cam, seed=5, want_u8=False)
+    f32, u8, sig, _ = gpu_ctx.render(cam, seed=5, want_sig=True)
+    r32, r8, rsig, cnt = orc.OracleScene(flat).render(cam, seed=5, want_counters=True)
     assert np.array_equal(sig, rsig)
+    _signature_free_equals(gpu_ctx, cam, 5, f32, u8, r32, r8, cnt)
 
 
 @pytest.mark.parametrize("name", ["config2", "config4", "config5"])

@@ -14,7 +14,7 @@ from cs397raytracingsp22_amd import Context, Lambertian, StaticMesh, abi, cgmath
 pytestmark = pytest.mark.gpu
 
 
-def render_with_env(env, flat, cam, seed, flags=0):
+def render_with_env(env, flat, cam, seed, flags=0, want_sig=True):
     """A context of its own created under the given developer knobs (read once in mi_ctx_create)."""
     old = {k: os.environ.get(k) for k in env}
     os.environ.update({k: str(v) for k, v in env.items()})
@@ -28,7 +28,7 @@ def render_with_env(env, flat, cam, seed, flags=0):
                 os.environ[k] = v
     try:
         ctx.upload(flat)
-        f32, _, sig, _ = ctx.render(cam, seed=seed, want_sig=True, flags=flags)
+        f32, _, sig, _ = ctx.render(cam, seed=seed, want_sig=want_sig, flags=flags)
         return f32, sig
     finally:
         ctx.close()
