@@ -1,4 +1,4 @@
-// bvh_build.hpp — host-side tree builders of the scene compiler (mi_rt.cpp); header-only so that the CPU test of the
+// bvh_build.hpp — host-side tree builders of the scene compiler (scene_compile.cpp); header-only so that the CPU test of the
 // two-stage traversal (tests/cpp/two_stage_check.cpp) builds the very same trees.
 //
 //   RefTree   the REFERENCE's BVH of a StaticMesh (geometry.rs:175-217): median split of the triangle INDEX range,

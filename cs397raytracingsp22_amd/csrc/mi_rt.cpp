@@ -1,10 +1,6 @@
 // mi_rt.cpp — host runtime behind the C ABI of include/mi_rt.h (libmi_rt.so).
 //
-//   * scene compiler: flattens the POD description of the reference's Scene.objects
-//     into the device layout of pt_device.h, including the BVH of every StaticMesh with
-//     the REFERENCE's topology (geometry.rs:190-217: median split of the triangle index
-//     range, leaf i = triangle i, exact union boxes), emitted in DFS pre-order with skip
-//     links for the stackless traversal of pt_kernels.hip.
+//   * scene upload: the scene compiler's output (scene_compile.cpp) committed to the device.
 //   * render entry points: whole image on one GPU (mi_render) and the device-pointer
 //     building blocks used with one process per GPU (tiles, un-permute, tone-map).
 //
@@ -28,7 +24,7 @@
 
 #include "../../include/mi_rt.h"
 #include "pt_device.h"
-#include "bvh_build.hpp"
+#include "scene_compile.hpp"
 
 #pragma clang fp contract(off)
 
@@ -39,9 +35,7 @@ hipError_t launch_megakernel_voted(const K1Args& args, uint32_t n_blocks, bool l
 hipError_t launch_wf_main(const WfArgs& a, uint32_t n_blocks, bool sig, bool gv, bool tex, hipStream_t stream);
 hipError_t launch_phong(const K1Args& a, uint32_t n_blocks, bool sig, hipStream_t stream);
 hipError_t launch_branch(const K1Args& a, uint32_t n_blocks, uint32_t path_samples, bool sig, hipStream_t stream);
-hipError_t launch_wf_trav(const WfArgs& a, uint32_t n_blocks, int lds_mode, size_t lds_bytes, bool* big_lds_enabled, hipStream_t stream);
-hipError_t launch_wf_trav_i(const WfArgs& a, uint32_t n_blocks, size_t lds_bytes, bool leaf_lds, bool* big_lds_enabled, hipStream_t stream);
-hipError_t launch_wf_trav_p(const WfArgs& a, uint32_t n_blocks, size_t lds_bytes, hipStream_t stream);
+hipError_t launch_walker(const WfArgs& a, const WalkerPlan& p, uint32_t n_blocks, bool* big_lds_enabled, hipStream_t stream);
 hipError_t launch_wf_filter_f(const WfArgs& a, uint32_t blocks_per_shard, hipStream_t stream);
 hipError_t launch_wf_trav_f(const WfArgs& a, uint32_t n_blocks, hipStream_t stream);
 hipError_t launch_wf_replay(const WfArgs& a, uint32_t n_blocks, hipStream_t stream);
@@ -60,7 +54,7 @@ using namespace pt;
 
 // ------------------------------------------------------------------ errors
 static thread_local std::string g_err;
-static int fail(int code, const char* fmt, ...) {
+int pt::fail(int code, const char* fmt, ...) {
     char buf[512];
     va_list ap; va_start(ap, fmt); vsnprintf(buf, sizeof buf, fmt, ap); va_end(ap);
     g_err = buf;
@@ -72,17 +66,7 @@ static int fail(int code, const char* fmt, ...) {
         if (e_ != hipSuccess) return fail(MI_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(e_)); \
     } while (0)
 
-// ------------------------------------------------------------------ host f32 math (reference order)
 namespace {
-struct h3 { float x, y, z; };
-inline h3 H3(float x, float y, float z) { h3 r = { x, y, z }; return r; }
-inline h3 H3p(const float* p) { return H3(p[0], p[1], p[2]); }
-inline h3 sub(h3 a, h3 b) { return H3(a.x - b.x, a.y - b.y, a.z - b.z); }
-inline h3 add(h3 a, h3 b) { return H3(a.x + b.x, a.y + b.y, a.z + b.z); }
-inline h3 scale(h3 a, float s) { return H3(a.x * s, a.y * s, a.z * s); }
-inline float dot(h3 a, h3 b) { return (a.x * b.x + a.y * b.y) + a.z * b.z; }
-inline h3 cross(h3 a, h3 b) { return H3(a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x); }
-inline h3 normalize(h3 a) { return scale(a, 1.0f / sqrtf(dot(a, a))); }
 inline uint32_t lowbias32(uint32_t x) {
     x ^= x >> 16; x *= 0x7feb352du; x ^= x >> 15; x *= 0x846ca68bu; x ^= x >> 16; return x;
 }
@@ -98,17 +82,11 @@ struct mi_ctx {
     hipEvent_t ev_start = nullptr, ev_stop = nullptr;
     bool ev_recorded = false;
 
-    // device scene
+    // device scene: the blob, its pools (S), and the compiler's tables for the host side of a render (scene.image is emptied once copied)
     void* blob = nullptr; size_t blob_bytes = 0;
     DScene S{};
+    CompiledScene scene;
     bool have_scene = false;
-    bool mesh_maps = false;                  // some mesh takes its material from maps or has a normal map: wf_main's MESH = 2 form
-    bool gen_volumes = false;                // a ConvexVolume whose boundary is not the inline sphere: the kernels' GV forms
-    bool list_tree = false;                  // the list's Triangles sit in a top-level tree (long lists): wf_main's TOP forms
-    uint32_t lds_bytes = 0;                  // bytes needed to stage nodes + tris, 0 = no meshes
-    // per live mesh (Scene.objects order): end of its nodes in the node pool, does the two-stage bound apply to it at all,
-    // is it walked two-stage by default (qualifies and large enough for the F-tree to pay)
-    std::vector<int> mesh_node_end, mesh_e2_end, mesh_inode_end; std::vector<uint8_t> mesh_qualifies, mesh_default_ts;
     void* d_cand = nullptr; size_t cand_bytes = 0;           // two-stage candidates [cap][kCandMax] {t, key}
     void* d_cand_hdr = nullptr; size_t cand_hdr_bytes = 0;   // [cap] {pos, count | flags}
 
@@ -119,10 +97,8 @@ struct mi_ctx {
     uint32_t* d_sigc = nullptr; size_t sigc_bytes = 0;
     uint32_t* d_sigi = nullptr; size_t sigi_bytes = 0;
     unsigned long long* d_diag = nullptr;    // 16 counters of the diagnostic variant
-    float point_light_pos[3] = {0.0f, 1.0f, 5.0f}, ambient[3] = {0.1f, 0.1f, 0.1f};   // Scene fields read by Phong
     hipEvent_t ev_t0 = nullptr, ev_t1 = nullptr;     // mi_render's whole-call timer
-    bool big_lds_enabled = false;                    // wf_trav<2,1024>'s > 64 KB dynamic-LDS opt-in, set on THIS context's device
-    bool big_lds_enabled_i = false;                  // the same for wf_trav_i<1024>
+    bool big_lds_enabled = false;                    // wf_trav_i<1024>'s > 64 KB dynamic-LDS opt-in, set on THIS context's device
     // wavefront pipeline buffers
     void* d_wf_a = nullptr; size_t wf_a_bytes = 0;   // path state ping
     void* d_wf_b = nullptr; size_t wf_b_bytes = 0;   // path state pong
@@ -133,10 +109,7 @@ struct mi_ctx {
     uint64_t wf_counts[8] = { 0, 0, 0, 0, 0, 0, 0, 0 };   // last frame: passes, class-A paths streamed, class-B paths, queue entries, samples, pixels
     uint32_t* h_hdr_dev = nullptr;                   // its device-side address
     uint32_t hdr_seq = 0;
-    // per-tile primary-ray masks over the kind-grouped list (see tile_masks)
-    std::vector<DObject> h_list; int h_n_tri = 0, h_n_sphere = 0, h_n_unmasked = 0;   // planes + volumes: never masked
-    struct MeshBox { bool cullable; double corner[8][3]; };
-    std::vector<MeshBox> h_mesh_box;                 // world-space corners of every live mesh's root box
+    // per-tile primary-ray masks over the kind-grouped list and the meshes' root boxes (see tile_masks)
     std::vector<unsigned long long> h_tile_mask; void* d_tile_mask = nullptr; size_t tile_mask_bytes = 0;
     mi_camera_desc mask_cam{}; uint32_t mask_stride = 0; bool mask_valid = false;
     std::vector<hipEvent_t> wf_ev;                   // event pool for per-kernel timing of the pipeline
@@ -149,8 +122,8 @@ struct mi_ctx {
         uint32_t lds_pad = 0;                           // occupancy experiments
         uint32_t refill_min = 16;                       // wf_trav: refill idle lanes when at least this many are idle (A/B round 2: 32 / 16 / 8 -> 36.9 / 35.8 / 38.6 ms on cfg2)
         uint32_t fuse_max = 0, fuse_min = 32;           // wf_main: in-launch continuation (rounds: 0 = automatic; lanes needed)
-        int trav_lds = -1;                              // wf_trav LDS mode override (-1 = automatic)
-        int trav_bpc = 0;                               // wf_trav blocks per CU override (0 = automatic)
+        int trav_lds = -1;                              // reference-tree walker override, a WalkerPlan form (-1 = automatic)
+        int trav_bpc = 0;                               // its blocks per CU override (0 = automatic)
         int travf_bpc = 0;                              // wf_trav_f blocks per CU override (0 = default)
         int kernel_timing = -1;                         // per-launch HIP events: -1 = single-rank renders only
         bool global_bvh = false;                        // never stage a BVH in LDS
@@ -280,589 +253,27 @@ extern "C" void mi_ctx_destroy(mi_ctx* c) {
     delete c;
 }
 
-// ------------------------------------------------------------------ scene compiler
-namespace {
-
-bool finite16(const float* m) { for (int i = 0; i < 16; i++) if (!std::isfinite(m[i])) return false; return true; }
-
-}  // namespace
-
+// ------------------------------------------------------------------ scene upload
+// Validate and compile on the host (no device state is touched: a failure there leaves the previous scene as it was), then commit.
+// The commit frees the old blob first, so that the peak HBM is one scene; a failure from there on leaves the context with no scene.
 extern "C" int mi_scene_upload(mi_ctx* c, const mi_scene_desc* d) {
     if (!c || !d) return fail(MI_ERR_INVALID, "mi_scene_upload: NULL argument");
-    if (d->n_objects < 0 || d->n_materials < 0 || d->n_meshes < 0 || d->n_textures < 0)
-        return fail(MI_ERR_INVALID, "negative count");
-    if (d->n_objects > 0 && !d->objects) return fail(MI_ERR_INVALID, "objects is NULL");
+    CompiledScene sc;
+    const int rc = compile_scene(d, &sc);
+    if (rc != MI_OK) return rc;
     HIP_TRY(hipSetDevice(c->device));
-
-    std::vector<DObject> objs((size_t)d->n_objects);
-    std::vector<DMaterial> mats((size_t)d->n_materials);
-    std::vector<DMesh> meshes((size_t)d->n_meshes);
-    std::vector<DMeshF> meshf((size_t)d->n_meshes);
-    struct MeshBuild { std::vector<float> nodes, fnodes, ftris; std::vector<uint32_t> fq; bool qualifies = false, default_ts = false; int inode_end = 0; };
-    std::vector<MeshBuild> mb((size_t)d->n_meshes);
-    std::vector<float> nodes, tris, ftris, e2s, inodes, lnodes;
-    std::vector<uint32_t> fnodes;              // the F-trees as the device walks them: 4 words per node (bvh_build.hpp fq_encode)
-    std::vector<DTriAttr> attrs;
-    std::vector<DTexture> texs((size_t)d->n_textures);
-    std::vector<uint8_t> texels;
-
-    const float PI = 3.14159265358979323846f;
-    for (int i = 0; i < d->n_materials; i++) {
-        const mi_material& s = d->materials[i];
-        if (s.kind < MI_MAT_LAMBERTIAN || s.kind > MI_MAT_ISOTROPIC) return fail(MI_ERR_INVALID, "material %d: bad kind %d", i, s.kind);
-        DMaterial& m = mats[(size_t)i];
-        memset(&m, 0, sizeof m);
-        m.kind = s.kind;
-        for (int k = 0; k < 3; k++) { m.albedo[k] = s.albedo[k]; m.emission[k] = s.emission[k]; m.albedo_over_pi[k] = s.albedo[k] / PI; }
-        if (s.kind == MI_MAT_DIELECTRIC) for (int k = 0; k < 3; k++) m.emission[k] = 0.0f;      // materials.rs:102
-        m.roughness = s.roughness; m.metallic = s.metallic; m.ior = s.idx_of_refraction;
-    }
-    auto mat_ok = [&](int id) { return id >= 0 && id < d->n_materials; };
-
-    for (int i = 0; i < d->n_textures; i++) {
-        const mi_texture& t = d->textures[i];
-        if (t.width <= 0 || t.height <= 0 || !t.rgb) return fail(MI_ERR_INVALID, "texture %d: bad size or NULL texels", i);
-        while (texels.size() % 16) texels.push_back(0);
-        texs[(size_t)i].offset = (uint32_t)texels.size();
-        texs[(size_t)i].width = t.width; texs[(size_t)i].height = t.height; texs[(size_t)i].pad = 0;
-        // texels are padded to RGBA8 on the device: one aligned 4-byte load per fetch instead of three byte loads
-        const size_t np = (size_t)t.width * t.height, at = texels.size();
-        texels.resize(at + np * 4);
-        for (size_t k = 0; k < np; k++) {
-            texels[at + 4 * k] = t.rgb[3 * k]; texels[at + 4 * k + 1] = t.rgb[3 * k + 1]; texels[at + 4 * k + 2] = t.rgb[3 * k + 2];
-            texels[at + 4 * k + 3] = 255;
-        }
-    }
-
-    // meshes: BVH + de-indexed triangle pools
-    for (int mi = 0; mi < d->n_meshes; mi++) {
-        const mi_mesh& s = d->meshes[mi];
-        if (!s.positions || !s.normals || !s.texcoords || !s.indices || s.n_triangles < 1 || s.n_vertices < 1)
-            return fail(MI_ERR_INVALID, "mesh %d: positions, normals, texcoords and indices are all required (geometry.rs:350,355)", mi);
-        for (size_t k = 0; k < 3 * (size_t)s.n_triangles; k++)
-            if (s.indices[k] >= (uint32_t)s.n_vertices) return fail(MI_ERR_INVALID, "mesh %d: index %u out of range", mi, s.indices[k]);
-        if (!finite16(s.transform) || !finite16(s.inv_transform)) return fail(MI_ERR_INVALID, "mesh %d: non-finite transform", mi);
-        if (s.material >= d->n_materials) return fail(MI_ERR_INVALID, "mesh %d: bad material", mi);
-        DMesh& M = meshes[(size_t)mi];
-        memset(&M, 0, sizeof M);
-        memcpy(M.transform, s.transform, sizeof M.transform);
-        memcpy(M.inv_transform, s.inv_transform, sizeof M.inv_transform);
-        M.material = s.material < 0 ? -1 : s.material;
-        for (int k = 0; k < 5; k++) {
-            if (s.textures[k] >= d->n_textures) return fail(MI_ERR_INVALID, "mesh %d: bad texture index", mi);
-            M.tex[k] = s.textures[k] < 0 ? -1 : s.textures[k];
-        }
-        M.object_index = -1;
-        M.tex_comb = -1;
-        if (s.material < 0) {
-            // interleaved copy of this mesh's maps (pt_device.h DMesh.tex_comb) when every bound map has the same size
-            int w = 0, h = 0, bound = 0; bool same = true;
-            for (int k = 0; k < 5; k++) if (s.textures[k] >= 0) {
-                const mi_texture& t = d->textures[s.textures[k]];
-                if (bound == 0) { w = t.width; h = t.height; } else if (t.width != w || t.height != h) same = false;
-                bound++;
-            }
-            if (bound >= 2 && same && (uint64_t)w * (uint64_t)h * 16u < (1ull << 30)) {
-                while (texels.size() % 16) texels.push_back(0);
-                DTexture T; T.offset = (uint32_t)texels.size(); T.width = w; T.height = h; T.pad = 0;
-                const size_t np = (size_t)w * h, at = texels.size();
-                texels.resize(at + np * 16, 0);
-                const uint8_t* src[5];
-                for (int k = 0; k < 5; k++) src[k] = s.textures[k] >= 0 ? d->textures[s.textures[k]].rgb : nullptr;
-                for (size_t px = 0; px < np; px++) {
-                    uint8_t* o = &texels[at + px * 16];
-                    // absent maps: albedo 0, emission 0, metallic 0, roughness 1.0 = 255 / 255 (geometry.rs:260-263)
-                    for (int ch = 0; ch < 3; ch++) { o[ch] = src[0] ? src[0][px * 3 + ch] : 0; o[4 + ch] = src[1] ? src[1][px * 3 + ch] : 0; o[8 + ch] = src[4] ? src[4][px * 3 + ch] : 0; }
-                    o[3] = src[2] ? src[2][px * 3] : 0;
-                    o[7] = src[3] ? src[3][px * 3] : 255;
-                }
-                M.tex_comb = (int)texs.size();
-                texs.push_back(T);
-            }
-        }
-        M.tri_begin = (int)(tris.size() / 12);
-        M.n_tris = s.n_triangles;
-        MeshBuild& B = mb[(size_t)mi];
-        build::RefTree rt{ s.positions, s.indices, &B.nodes };           // mesh-local node indices; relocated into the pool below
-        rt.build(0, s.n_triangles);                                      // geometry.rs:185
-        for (int t = 0; t < s.n_triangles; t++) {
-            uint32_t ia = s.indices[3 * (size_t)t], ib = s.indices[3 * (size_t)t + 1], ic = s.indices[3 * (size_t)t + 2];
-            h3 a = H3p(&s.positions[3 * (size_t)ia]), b = H3p(&s.positions[3 * (size_t)ib]), cc = H3p(&s.positions[3 * (size_t)ic]);
-            h3 e1 = sub(b, a), e2 = sub(cc, a);                         // geometry.rs:336-337
-            float rec[12] = { a.x, a.y, a.z, 0.0f, e1.x, e1.y, e1.z, 0.0f, e2.x, e2.y, e2.z, 0.0f };
-            tris.insert(tris.end(), rec, rec + 12);
-            DTriAttr A; memset(&A, 0, sizeof A);
-            memcpy(A.na, &s.normals[3 * (size_t)ia], 12); memcpy(A.nb, &s.normals[3 * (size_t)ib], 12); memcpy(A.nc, &s.normals[3 * (size_t)ic], 12);
-            memcpy(A.ta, &s.texcoords[2 * (size_t)ia], 8); memcpy(A.tb, &s.texcoords[2 * (size_t)ib], 8); memcpy(A.tc, &s.texcoords[2 * (size_t)ic], 8);
-            // StaticMesh::get_tangent geometry.rs:245-250
-            float u1 = A.ta[0], u2 = A.tb[0], u3 = A.tc[0], v1 = A.ta[1], v2 = A.tb[1], v3 = A.tc[1];
-            h3 num = sub(scale(sub(b, a), (v3 - v1)), scale(sub(cc, a), (v2 - v1)));
-            float den = (u2 - u1) * (v3 - v1) - (v2 - v1) * (u3 - u1);
-            A.tan[0] = num.x / den; A.tan[1] = num.y / den; A.tan[2] = num.z / den;
-            attrs.push_back(A);
-        }
-        // Two-stage traversal (bvh_build.hpp): does the padding bound apply to this mesh?  B = 7 eps E2 |d_obj| / 1e-4 must
-        // stay <= 1/2 for every ray; |d_obj| <= |inv_transform's 3x3|_F |d_world|, and world directions of up to 8 units are
-        // covered with a factor 10 to spare (a longer one takes the reference walk for that ray, decided on the device).
-        DMeshF& F = meshf[(size_t)mi];
-        memset(&F, 0, sizeof F);
-        {
-            build::FTree ft{ tris.data() + (size_t)M.tri_begin * 12, s.n_triangles, &B.fnodes, &B.ftris, 0, 2, {}, {}, {} };
-            const build::FConst fc = ft.run();
-            double fro = 0.0;
-            for (int cc = 0; cc < 3; cc++) for (int r = 0; r < 3; r++) fro += (double)s.inv_transform[cc * 4 + r] * (double)s.inv_transform[cc * 4 + r];
-            const double b_ref = 7.0 * 5.9604645e-08 * (double)fc.E2 * (std::sqrt(fro) * 8.0) * 1.0e4;
-            const bool affine = s.inv_transform[3] == 0.0f && s.inv_transform[7] == 0.0f && s.inv_transform[11] == 0.0f && s.inv_transform[15] == 1.0f;
-            B.qualifies = affine && std::isfinite(b_ref) && b_ref <= 0.05 && s.n_triangles < (1 << 24) && std::isfinite(fc.R) && std::isfinite(fc.L);
-            build::FQuant fq{ 1.0f, 0.0f, 0.0f, 0.0f };
-            if (B.qualifies) B.qualifies = build::fq_encode(B.fnodes.data(), B.fnodes.size() / 8, &fq, &B.fq);
-            F.qs = fq.s; F.qbx = fq.bx; F.qby = fq.by; F.qbz = fq.bz;
-            B.fnodes.clear(); B.fnodes.shrink_to_fit();
-            B.default_ts = B.qualifies && s.n_triangles >= 1024;        // below that the reference's tree sits in LDS and the F-tree does not pay
-            F.qualifies = B.qualifies ? 1 : 0;
-            F.E2 = fc.E2; F.L = fc.L; F.cx = fc.cx; F.cy = fc.cy; F.cz = fc.cz; F.R = fc.R;
-            if (!B.qualifies) { B.fq.clear(); B.ftris.clear(); }
-        }
-    }
-    // Pool placement: meshes walked through the reference's tree first, so that one LDS window over the head of the node
-    // pool covers exactly the trees wf_trav needs.  (The order of Scene.objects — ties, RNG draws — is not touched.)
-    // Who references which mesh: Scene.objects entries, and ConvexVolume boundaries (a StaticMesh, or a nested Scene's entries).
-    // Trees nobody references are not placed at all; boundary-only trees go last (they are walked from global memory).
-    std::vector<uint8_t> obj_ref((size_t)d->n_meshes, 0), bnd_ref((size_t)d->n_meshes, 0);
-    if (d->n_boundary_objects < 0 || (d->n_boundary_objects > 0 && !d->boundary_objects)) return fail(MI_ERR_INVALID, "bad boundary_objects");
-    for (int i = 0; i < d->n_objects; i++)
-        if (d->objects[i].kind == MI_OBJ_MESH) {
-            if (d->objects[i].index < 0 || d->objects[i].index >= d->n_meshes) return fail(MI_ERR_INVALID, "object %d: bad mesh index", i);
-            obj_ref[(size_t)d->objects[i].index] = 1;
-        }
-    for (int v = 0; v < d->n_volumes && d->volumes; v++) {
-        const mi_volume& vo = d->volumes[v];
-        auto mark = [&](int kind, int index) -> int {
-            if (kind == MI_OBJ_MESH) {
-                if (index < 0 || index >= d->n_meshes) return fail(MI_ERR_INVALID, "volume %d: bad boundary mesh index", v);
-                bnd_ref[(size_t)index] = 1;
-            }
-            return MI_OK;
-        };
-        if (vo.boundary_kind == MI_OBJ_SCENE) {
-            if (vo.boundary_index < 0 || vo.boundary_count < 0 || (int64_t)vo.boundary_index + vo.boundary_count > d->n_boundary_objects)
-                return fail(MI_ERR_INVALID, "volume %d: boundary entries out of range", v);
-            for (int k = 0; k < vo.boundary_count; k++) {
-                const mi_object& e = d->boundary_objects[vo.boundary_index + k];
-                const int rcm = mark(e.kind, e.index);
-                if (rcm != MI_OK) return rcm;
-            }
-        } else {
-            const int rcm = mark(vo.boundary_kind, vo.boundary_index);
-            if (rcm != MI_OK) return rcm;
-        }
-    }
-    {
-        std::vector<int> order;
-        for (int pass = 0; pass < 3; pass++)
-            for (int mi = 0; mi < d->n_meshes; mi++) {
-                const int cls = obj_ref[(size_t)mi] ? (mb[(size_t)mi].default_ts ? 1 : 0) : (bnd_ref[(size_t)mi] ? 2 : 3);
-                if (cls == pass) order.push_back(mi);
-            }
-        for (int mi : order) {
-            MeshBuild& B = mb[(size_t)mi];
-            DMesh& M = meshes[(size_t)mi];
-            DMeshF& F = meshf[(size_t)mi];
-            const int nbase = (int)(nodes.size() / 8), fbase = (int)(fnodes.size() / 4);
-            M.node_begin = nbase;
-            for (size_t k = 0; k < B.nodes.size(); k += 8) { int sk; memcpy(&sk, &B.nodes[k + 3], 4); sk += nbase; memcpy(&B.nodes[k + 3], &sk, 4); }
-            // leaf nodes carry {a, skip}{e1, tri} instead of their (never tested) box; e2 goes to its own small pool
-            M.e2_begin = (int)(e2s.size() / 4);
-            for (size_t k = 0; k < B.nodes.size(); k += 8) {
-                int tri; memcpy(&tri, &B.nodes[k + 7], 4);
-                if (tri < 0) continue;
-                const float* T = &tris[((size_t)M.tri_begin + (size_t)tri) * 12];
-                B.nodes[k + 0] = T[0]; B.nodes[k + 1] = T[1]; B.nodes[k + 2] = T[2];
-                B.nodes[k + 4] = T[4]; B.nodes[k + 5] = T[5]; B.nodes[k + 6] = T[6];
-            }
-            for (int t = 0; t < M.n_tris; t++) {
-                const float* T = &tris[((size_t)M.tri_begin + (size_t)t) * 12];
-                const float rec[4] = { T[8], T[9], T[10], 0.0f };
-                e2s.insert(e2s.end(), rec, rec + 4);
-            }
-            // the same tree with interior nodes and leaves in separate pools and explicit links (pt_device.h DScene.inodes)
-            {
-                const int n_local = (int)(B.nodes.size() / 8);
-                const int ibase = (int)(inodes.size() / 8), lbase = (int)(lnodes.size() / 12);
-                std::vector<int32_t> id((size_t)n_local);
-                int ni = 0, nl = 0;
-                for (int j = 0; j < n_local; j++) {
-                    int tri; memcpy(&tri, &B.nodes[(size_t)j * 8 + 7], 4);
-                    id[(size_t)j] = tri < 0 ? ibase + ni++ : ~(lbase + nl++);
-                }
-                auto id_of = [&](int j) -> int32_t { return j >= n_local ? kIdEnd : id[(size_t)j]; };
-                for (int j = 0; j < n_local; j++) {
-                    const float* N = &B.nodes[(size_t)j * 8];
-                    int sk, tri; memcpy(&sk, &N[3], 4); memcpy(&tri, &N[7], 4);
-                    if (tri < 0) {
-                        float rec[8] = { N[0], N[1], N[2], 0.0f, N[4], N[5], N[6], 0.0f };
-                        const int32_t miss = id_of(sk - nbase), hit = id_of(j + 1);
-                        memcpy(&rec[3], &miss, 4); memcpy(&rec[7], &hit, 4);
-                        inodes.insert(inodes.end(), rec, rec + 8);
-                    } else {
-                        const float* T = &tris[((size_t)M.tri_begin + (size_t)tri) * 12];
-                        float rec[12] = { T[0], T[1], T[2], 0.0f, T[4], T[5], T[6], 0.0f, T[8], T[9], T[10], 0.0f };
-                        const int32_t next = id_of(j + 1);
-                        memcpy(&rec[3], &next, 4); memcpy(&rec[7], &tri, 4);
-                        lnodes.insert(lnodes.end(), rec, rec + 12);
-                    }
-                }
-                M.i_root = id_of(0);
-                B.inode_end = (int)(inodes.size() / 8);
-            }
-            nodes.insert(nodes.end(), B.nodes.begin(), B.nodes.end());
-            M.node_end = (int)(nodes.size() / 8);
-            for (size_t k = 0; k < B.fq.size(); k += 4) if (!(B.fq[k + 3] & 0x80000000u)) B.fq[k + 3] += (uint32_t)fbase;      // interior nodes: skip links into the pool
-            F.fnode_begin = fbase; F.ftri_begin = (int)(ftris.size() / 12);
-            fnodes.insert(fnodes.end(), B.fq.begin(), B.fq.end());
-            ftris.insert(ftris.end(), B.ftris.begin(), B.ftris.end());
-            F.fnode_end = (int)(fnodes.size() / 4);
-            B.nodes.clear(); B.nodes.shrink_to_fit(); B.fq.clear(); B.ftris.clear();
-        }
-    }
-
-    // one Sphere / Triangle / Plane record (Scene.objects entry or boundary entry), derived constants hoisted
-    auto fill_primitive = [&](int kind, int index, const char* what, int i, DObject& D) -> int {
-        switch (kind) {
-        case MI_OBJ_SPHERE: {
-            if (index < 0 || index >= d->n_spheres || !d->spheres) return fail(MI_ERR_INVALID, "%s %d: bad sphere index", what, i);
-            const mi_sphere& s = d->spheres[index];
-            if (!mat_ok(s.material)) return fail(MI_ERR_INVALID, "%s %d: bad material", what, i);
-            D.material = s.material;
-            D.f[0] = s.center[0]; D.f[1] = s.center[1]; D.f[2] = s.center[2]; D.f[3] = s.radius;
-            D.f[4] = s.radius * s.radius;                               // geometry.rs:400
-            return MI_OK;
-        }
-        case MI_OBJ_TRIANGLE: {
-            if (index < 0 || index >= d->n_triangles || !d->triangles) return fail(MI_ERR_INVALID, "%s %d: bad triangle index", what, i);
-            const mi_triangle& t = d->triangles[index];
-            if (!mat_ok(t.material)) return fail(MI_ERR_INVALID, "%s %d: bad material", what, i);
-            D.material = t.material;
-            h3 a = H3p(t.a), e1 = sub(H3p(t.b), a), e2 = sub(H3p(t.c), a);      // geometry.rs:434-435
-            h3 n = normalize(cross(e1, e2));                                    // geometry.rs:449
-            D.f[0] = a.x; D.f[1] = a.y; D.f[2] = a.z;
-            D.f[3] = e1.x; D.f[4] = e1.y; D.f[5] = e1.z;
-            D.f[6] = e2.x; D.f[7] = e2.y; D.f[8] = e2.z;
-            D.f[9] = n.x; D.f[10] = n.y; D.f[11] = n.z;
-            return MI_OK;
-        }
-        case MI_OBJ_PLANE: {
-            if (index < 0 || index >= d->n_planes || !d->planes) return fail(MI_ERR_INVALID, "%s %d: bad plane index", what, i);
-            const mi_plane& p = d->planes[index];
-            if (!mat_ok(p.material)) return fail(MI_ERR_INVALID, "%s %d: bad material", what, i);
-            D.material = p.material;
-            for (int k = 0; k < 3; k++) { D.f[k] = p.point[k]; D.f[3 + k] = p.normal[k]; }
-            return MI_OK;
-        }
-        default: return fail(MI_ERR_INVALID, "%s %d: unknown kind %d", what, i, kind);
-        }
-    };
-    // boundary records of the ConvexVolumes that are not plain spheres; boundary meshes get entries of the device's mesh table
-    // BEHIND the Scene.objects meshes (bmesh_of: mesh index -> entry, filled below once the live table exists)
-    std::vector<DObject> bobjs;
-    std::vector<std::pair<size_t, int>> bmesh_fix;        // (record in bobjs, mi_mesh index) to be pointed at its table entry
-
-    // Scene.objects in order
-    for (int i = 0; i < d->n_objects; i++) {
-        const mi_object& o = d->objects[i];
-        DObject& D = objs[(size_t)i];
-        memset(&D, 0, sizeof D);
-        D.kind = o.kind;
-        D.index = i;
-        D.ref = -1;
-        switch (o.kind) {
-        case MI_OBJ_SPHERE: case MI_OBJ_TRIANGLE: case MI_OBJ_PLANE: {
-            const int rcp = fill_primitive(o.kind, o.index, "object", i, D);
-            if (rcp != MI_OK) return rcp;
-            break;
-        }
-        case MI_OBJ_VOLUME: {
-            if (o.index < 0 || o.index >= d->n_volumes || !d->volumes) return fail(MI_ERR_INVALID, "object %d: bad volume index", i);
-            const mi_volume& v = d->volumes[o.index];
-            if (!mat_ok(v.phase_material)) return fail(MI_ERR_INVALID, "object %d: bad phase material", i);
-            D.material = v.phase_material;
-            D.f[5] = -1.0f / v.density;                                 // geometry.rs:517
-            if (v.boundary_kind == MI_OBJ_SPHERE) {                     // the inline sphere: what every use in the reference is
-                for (int k = 0; k < 3; k++) D.f[k] = v.boundary_center[k];
-                D.f[3] = v.boundary_radius;
-                D.f[4] = v.boundary_radius * v.boundary_radius;         // geometry.rs:400 via :505
-                break;
-            }
-            // any other `Arc<dyn Intersectable>` (geometry.rs:496): its records, tested twice per ray by the kernels (:505,508)
-            std::vector<mi_object> entries;
-            if (v.boundary_kind == MI_OBJ_SCENE) for (int k = 0; k < v.boundary_count; k++) entries.push_back(d->boundary_objects[v.boundary_index + k]);
-            else { mi_object e; e.kind = v.boundary_kind; e.index = v.boundary_index; entries.push_back(e); }
-            D.ref = (int)bobjs.size();
-            { const int n = (int)entries.size(); memcpy(&D.f[6], &n, 4); }
-            for (size_t k = 0; k < entries.size(); k++) {
-                DObject R; memset(&R, 0, sizeof R);
-                R.kind = entries[k].kind; R.index = (int)k; R.ref = -1;
-                if (entries[k].kind == MI_OBJ_MESH) { R.material = -1; bmesh_fix.emplace_back(bobjs.size(), entries[k].index); }
-                else if (entries[k].kind == MI_OBJ_VOLUME || entries[k].kind == MI_OBJ_SCENE)
-                    return fail(MI_ERR_UNSUPPORTED, "object %d: a ConvexVolume or a Scene inside a ConvexVolume boundary", i);
-                else { const int rcp = fill_primitive(entries[k].kind, entries[k].index, "boundary entry of object", i, R); if (rcp != MI_OK) return rcp; }
-                bobjs.push_back(R);
-            }
-            break;
-        }
-        case MI_OBJ_MESH: {
-            // the same StaticMesh may appear several times (Arc sharing, tracing.rs:215): every appearance is an entry of its own
-            // in the device's mesh table — sharing the nodes, triangles and attributes in the pools — with its own object index
-            D.ref = o.index; D.material = -1;
-            break;
-        }
-        default: return fail(MI_ERR_INVALID, "object %d: unknown kind %d", i, o.kind);
-        }
-    }
-    // The device's mesh table: one entry per MESH entry of Scene.objects, in that order (S.n_meshes of them: what the hit loop
-    // walks), then one per boundary mesh (reached only through a ConvexVolume's boundary record).
-    std::vector<DMesh> live;
-    std::vector<DMeshF> livef;
-    c->mesh_node_end.clear(); c->mesh_e2_end.clear(); c->mesh_inode_end.clear(); c->mesh_qualifies.clear(); c->mesh_default_ts.clear();
-    for (int i = 0; i < d->n_objects; i++)
-        if (objs[(size_t)i].kind == OBJ_MESH) {
-            int r = objs[(size_t)i].ref; objs[(size_t)i].ref = (int)live.size();
-            live.push_back(meshes[(size_t)r]); livef.push_back(meshf[(size_t)r]);
-            live.back().object_index = i;
-            c->mesh_node_end.push_back(meshes[(size_t)r].node_end);
-            c->mesh_e2_end.push_back(meshes[(size_t)r].e2_begin + meshes[(size_t)r].n_tris);
-            c->mesh_inode_end.push_back(mb[(size_t)r].inode_end);
-            c->mesh_qualifies.push_back(mb[(size_t)r].qualifies ? 1 : 0); c->mesh_default_ts.push_back(mb[(size_t)r].default_ts ? 1 : 0);
-        }
-    const size_t n_scene_meshes = live.size();
-    for (auto& fx : bmesh_fix) {
-        bobjs[fx.first].ref = (int)live.size();
-        live.push_back(meshes[(size_t)fx.second]); livef.push_back(meshf[(size_t)fx.second]);
-        live.back().object_index = -1;
-    }
-
-    // kind-grouped copy of the non-mesh objects (stable within a kind)
-    std::vector<DObject> list;
-    int n_list[4] = { 0, 0, 0, 0 };
-    {
-        const int order[4] = { OBJ_TRIANGLE, OBJ_SPHERE, OBJ_PLANE, OBJ_VOLUME };
-        for (int g = 0; g < 4; g++)
-            for (size_t i = 0; i < objs.size(); i++)
-                if (objs[i].kind == order[g]) { list.push_back(objs[i]); n_list[g]++; }
-    }
-    // ---- top-level tree over the list's Triangles ("top-level BVH over Scene.objects"; long lists only) ----
-    // A list of hundreds of Triangles is hundreds of Moller-Trumbore tests per path segment.  The exact two-stage machinery of the
-    // meshes applies to them unchanged, in world space: a SAH tree over the triangles' boxes, walked per ray with the boxes padded by the
-    // proven bound on what the reference's f32 test can accept (bvh_build.hpp), and the reference's own test on the triangles of the leaves
-    // reached — a triangle whose padded box the ray misses would have failed that test, and the closest hit over the rest is
-    // order-independent (ties: the lower Scene.objects index).  The bound scales with E2 = max |e1||e2| over the tree, so the LARGE
-    // triangles (walls: 32 x the median product and more) stay in front of the list and are tested one by one; the tree needs >= 96 of
-    // the others.  A ray the bound does not cover (B > 1/2, non-finite) makes its wave test the whole list one by one.
-    int n_list_lin = n_list[0], top_meshf = -1;
-    {
-        constexpr int kTopMinTris = 96;       // measured (tools/probe_list_tree.py): 40 small triangles 0.85 x, 105: 1.1 x, 400: 1.6 x, 2000: 1.9 x of the plain loop
-        const int nt = n_list[0];
-        if (nt >= kTopMinTris) {
-            std::vector<double> prod((size_t)nt);
-            for (int k = 0; k < nt; k++) {
-                const float* f = list[(size_t)k].f;
-                prod[(size_t)k] = std::sqrt((double)f[3] * f[3] + (double)f[4] * f[4] + (double)f[5] * f[5]) * std::sqrt((double)f[6] * f[6] + (double)f[7] * f[7] + (double)f[8] * f[8]);
-            }
-            std::vector<double> sorted = prod;
-            std::nth_element(sorted.begin(), sorted.begin() + nt / 2, sorted.end());
-            const double big = 32.0 * sorted[(size_t)nt / 2];
-            // large triangles (and anything non-finite) to the front, order kept within each part (stable: ties between equal hits are decided by index anyway)
-            std::vector<DObject> front, rest;
-            for (int k = 0; k < nt; k++) ((!(prod[(size_t)k] <= big) || !std::isfinite(prod[(size_t)k])) ? front : rest).push_back(list[(size_t)k]);
-            if ((int)rest.size() >= kTopMinTris) {
-                std::vector<float> lt(rest.size() * 12, 0.0f), tn, tt;
-                for (size_t k = 0; k < rest.size(); k++) {
-                    const float* f = rest[k].f; float* T = &lt[k * 12];
-                    for (int q = 0; q < 3; q++) { T[q] = f[q]; T[4 + q] = f[3 + q]; T[8 + q] = f[6 + q]; }
-                }
-                build::FTree ft{ lt.data(), (int)rest.size(), &tn, &tt, 0, 2, {}, {}, {} };
-                const build::FConst fc = ft.run();
-                build::FQuant fq{ 1.0f, 0.0f, 0.0f, 0.0f };
-                std::vector<uint32_t> tq;
-                // (the bound's B = 7 eps E2 |d| / 1e-4 is checked per ray on the device; here only: is it finite, and below 1/2 for a unit direction at all)
-                const double b_unit = 7.0 * 5.9604645e-08 * (double)fc.E2 * 1.0e4;
-                if (std::isfinite(b_unit) && b_unit <= 0.25 && std::isfinite(fc.R) && std::isfinite(fc.L) && rest.size() < (1u << 24) &&
-                    build::fq_encode(tn.data(), tn.size() / 8, &fq, &tq)) {
-                    const int fbase = (int)(fnodes.size() / 4);
-                    for (size_t k = 0; k < tq.size(); k += 4) if (!(tq[k + 3] & 0x80000000u)) tq[k + 3] += (uint32_t)fbase;      // interior nodes: skip links into the pool
-                    for (size_t e = 0; e < tt.size() / 12; e++) {          // a leaf triangle carries its Scene.objects index where a mesh triangle carries its number
-                        int t; memcpy(&t, &tt[e * 12 + 3], 4);
-                        const int32_t idx = rest[(size_t)t].index;
-                        memcpy(&tt[e * 12 + 3], &idx, 4);
-                    }
-                    DMeshF F; memset(&F, 0, sizeof F);
-                    F.fnode_begin = fbase; F.ftri_begin = (int)(ftris.size() / 12);
-                    fnodes.insert(fnodes.end(), tq.begin(), tq.end());
-                    ftris.insert(ftris.end(), tt.begin(), tt.end());
-                    F.fnode_end = (int)(fnodes.size() / 4);
-                    F.qualifies = 1; F.E2 = fc.E2; F.L = fc.L; F.cx = fc.cx; F.cy = fc.cy; F.cz = fc.cz; F.R = fc.R;
-                    F.qs = fq.s; F.qbx = fq.bx; F.qby = fq.by; F.qbz = fq.bz;
-                    top_meshf = (int)livef.size();
-                    livef.push_back(F);
-                    n_list_lin = (int)front.size();
-                    for (size_t k = 0; k < front.size(); k++) list[k] = front[k];
-                    for (size_t k = 0; k < rest.size(); k++) list[front.size() + k] = rest[k];
-                }
-            }
-        }
-    }
-    // world-space corners of the root boxes (tile masks).  The rays reach object space through inv_transform
-    // (geometry.rs:304), so the corners come from ITS inverse (f64), not from `transform`; a projective
-    // inv_transform or a single-triangle mesh (no root box) is never culled.
-    c->h_mesh_box.assign(n_scene_meshes, mi_ctx::MeshBox{ false, {} });
-    for (size_t m = 0; m < n_scene_meshes; m++) {
-        const DMesh& M = live[m];
-        const float* it = M.inv_transform;
-        if (!(it[3] == 0.0f && it[7] == 0.0f && it[11] == 0.0f && it[15] == 1.0f)) continue;
-        const float* n0 = &nodes[(size_t)M.node_begin * 8];
-        int32_t tri_id; memcpy(&tri_id, &n0[7], 4);
-        if (tri_id >= 0) continue;
-        double a[4][8];                                   // [inv | I], Gauss-Jordan with partial pivoting
-        for (int r = 0; r < 4; r++) for (int q = 0; q < 4; q++) { a[r][q] = (double)it[q * 4 + r]; a[r][4 + q] = r == q ? 1.0 : 0.0; }
-        bool ok = true;
-        for (int col = 0; col < 4 && ok; col++) {
-            int piv = col;
-            for (int r = col + 1; r < 4; r++) if (fabs(a[r][col]) > fabs(a[piv][col])) piv = r;
-            if (!(fabs(a[piv][col]) > 1e-12)) { ok = false; break; }
-            if (piv != col) for (int q = 0; q < 8; q++) std::swap(a[piv][q], a[col][q]);
-            const double inv = 1.0 / a[col][col];
-            for (int q = 0; q < 8; q++) a[col][q] *= inv;
-            for (int r = 0; r < 4; r++) if (r != col) { const double f = a[r][col]; for (int q = 0; q < 8; q++) a[r][q] -= f * a[col][q]; }
-        }
-        if (!ok) continue;
-        mi_ctx::MeshBox& B = c->h_mesh_box[m];
-        B.cullable = true;
-        for (int k = 0; k < 8; k++) {
-            const double q[3] = { (double)((k & 1) ? n0[4] : n0[0]), (double)((k & 2) ? n0[5] : n0[1]), (double)((k & 4) ? n0[6] : n0[2]) };
-            for (int r = 0; r < 3; r++) {
-                B.corner[k][r] = a[r][4] * q[0] + a[r][5] * q[1] + a[r][6] * q[2] + a[r][7];
-                if (!std::isfinite(B.corner[k][r])) B.cullable = false;
-            }
-        }
-    }
-    // sample_hemisphere's rotation Basis3::between_vectors(unit_y, n) (materials.rs:176) as a matrix, for the two normals a list Triangle or Plane can
-    // present to a ray (its stored normal and the negation: RayHit::new, tracing.rs:118-123; Plane: geometry.rs:476-478): the same f32 operations in the same order as
-    // pt_kernels.hip rotate_from_unit_y performs per scatter (this file is compiled with -ffp-contract=off; sqrtf and the divisions are
-    // correctly rounded on both sides, rcp_exact IS 1.0f / x), so reading the table is exact.  12 floats per entry:
-    // {c0.xyz, c1.x}{c1.yz, c2.xy}{c2.z, 1 = identity (the function returns `dir` untouched), 0, 0}; entry 2 i + (frontface ? 0 : 1) of object i.
-    std::vector<float> obj_rot(objs.size() * 24, 0.0f);
-    {
-        auto ulps_eq = [](float a, float b) {                       // approx::ulps_eq!, f32 defaults (pt_kernels.hip ulps_eq)
-            if (fabsf(a - b) <= 1.1920929e-07f) return true;
-            if ((a < 0.0f) != (b < 0.0f)) return false;
-            int32_t ia, ib; memcpy(&ia, &a, 4); memcpy(&ib, &b, 4);
-            int32_t d = (int32_t)((uint32_t)ia - (uint32_t)ib);
-            if (d < 0) d = (int32_t)(0u - (uint32_t)d);
-            return d <= 4;
-        };
-        auto rot = [&](float nx, float ny, float nz, float* out) {
-            const float k_cos_theta = ny;
-            if (ulps_eq(k_cos_theta, 1.0f)) { out[9] = 1.0f; return; }
-            const float k = sqrtf(1.0f * ((nx * nx + ny * ny) + nz * nz));
-            float qs, qx, qz;
-            if (ulps_eq(k_cos_theta / k, -1.0f)) { qs = 0.0f; qx = 0.0f; qz = -1.0f; }
-            else {
-                const float sq = k + k_cos_theta;
-                const float cx = nz, cz = -nx;
-                const float mag = sqrtf(sq * sq + ((cx * cx + 0.0f) + cz * cz));
-                const float inv = 1.0f / mag;
-                qs = sq * inv; qx = cx * inv; qz = cz * inv;
-            }
-            const float x2 = qx + qx, z2 = qz + qz;
-            const float xx2 = x2 * qx, xz2 = x2 * qz, zz2 = z2 * qz;
-            const float sz2 = z2 * qs, sx2 = x2 * qs;
-            out[0] = 1.0f - zz2; out[1] = sz2; out[2] = xz2;                       // c0
-            out[3] = -sz2; out[4] = (1.0f - xx2) - zz2; out[5] = sx2;            // c1
-            out[6] = xz2; out[7] = -sx2; out[8] = 1.0f - xx2;                     // c2
-        };
-        for (size_t i = 0; i < objs.size(); i++) if (objs[i].kind == OBJ_TRIANGLE || objs[i].kind == OBJ_PLANE) {
-            const float* n = objs[i].f + (objs[i].kind == OBJ_TRIANGLE ? 9 : 3);       // the Triangle's stored normal / the Plane's
-            rot(n[0], n[1], n[2], &obj_rot[i * 24]);
-            rot(-n[0], -n[1], -n[2], &obj_rot[i * 24 + 12]);
-        }
-    }
-    // one blob: objects | list | materials | meshes | nodes | tris | attrs | textures | texels
-    auto align = [](size_t x) { return (x + 255) & ~(size_t)255; };
-    size_t off_obj = 0;
-    size_t off_list = align(off_obj + objs.size() * sizeof(DObject));
-    size_t off_bobj = align(off_list + (list.size() + 1) * sizeof(DObject));     // +1: the loop prefetches one record ahead
-    size_t off_rot = align(off_bobj + (bobjs.size() + 1) * sizeof(DObject));
-    size_t off_mat = align(off_rot + obj_rot.size() * 4 + 16);
-    size_t off_mesh = align(off_mat + mats.size() * sizeof(DMaterial));
-    size_t off_meshf = align(off_mesh + live.size() * sizeof(DMesh));
-    size_t off_fnodes = align(off_meshf + livef.size() * sizeof(DMeshF));
-    size_t off_ftris = align(off_fnodes + fnodes.size() * 4 + 32);
-    size_t off_nodes = align(off_ftris + ftris.size() * 4 + 48);
-    size_t off_e2 = align(off_nodes + nodes.size() * 4);
-    size_t off_inodes = align(off_e2 + e2s.size() * 4 + 16);
-    size_t off_lnodes = align(off_inodes + inodes.size() * 4 + 32);
-    size_t off_tris = align(off_lnodes + lnodes.size() * 4 + 48);
-    size_t off_attr = align(off_tris + tris.size() * 4);
-    size_t off_tex = align(off_attr + attrs.size() * sizeof(DTriAttr));
-    size_t off_texel = align(off_tex + texs.size() * sizeof(DTexture));
-    size_t total = align(off_texel + texels.size() + 16);
-    if (total > 0xffffffffull) return fail(MI_ERR_UNSUPPORTED, "scene larger than 4 GiB");
-    std::vector<uint8_t> host(total, 0);
-    auto put = [&](size_t off, const void* p, size_t n) { if (n) memcpy(host.data() + off, p, n); };
-    put(off_obj, objs.data(), objs.size() * sizeof(DObject));
-    put(off_list, list.data(), list.size() * sizeof(DObject));
-    put(off_bobj, bobjs.data(), bobjs.size() * sizeof(DObject));
-    put(off_rot, obj_rot.data(), obj_rot.size() * 4);
-    put(off_mat, mats.data(), mats.size() * sizeof(DMaterial));
-    put(off_mesh, live.data(), live.size() * sizeof(DMesh));
-    put(off_meshf, livef.data(), livef.size() * sizeof(DMeshF));
-    put(off_fnodes, fnodes.data(), fnodes.size() * 4);
-    put(off_ftris, ftris.data(), ftris.size() * 4);
-    put(off_nodes, nodes.data(), nodes.size() * 4);
-    put(off_e2, e2s.data(), e2s.size() * 4);
-    put(off_inodes, inodes.data(), inodes.size() * 4);
-    put(off_lnodes, lnodes.data(), lnodes.size() * 4);
-    put(off_tris, tris.data(), tris.size() * 4);
-    put(off_attr, attrs.data(), attrs.size() * sizeof(DTriAttr));
-    put(off_tex, texs.data(), texs.size() * sizeof(DTexture));
-    put(off_texel, texels.data(), texels.size());
-
-    if (c->blob) { (void)hipFree(c->blob); c->blob = nullptr; c->blob_bytes = 0; c->have_scene = false; }
-    hipError_t e = hipMalloc(&c->blob, total);
+    if (c->blob) (void)hipFree(c->blob);
+    c->blob = nullptr; c->blob_bytes = 0; c->S = DScene{}; c->scene = CompiledScene(); c->have_scene = false;
+    c->mask_valid = false;
+    const size_t total = sc.image.size();
+    void* blob = nullptr;
+    hipError_t e = hipMalloc(&blob, total);
     if (e != hipSuccess) return fail(MI_ERR_OOM, "hipMalloc(%zu) for the scene failed: %s", total, hipGetErrorString(e));
-    c->blob_bytes = total;
-    HIP_TRY(hipMemcpy(c->blob, host.data(), total, hipMemcpyHostToDevice));
-    uint8_t* b = (uint8_t*)c->blob;
-    c->S.objects = (const DObject*)(b + off_obj);
-    c->S.list = (const DObject*)(b + off_list);
-    c->S.bobjs = (const DObject*)(b + off_bobj);
-    c->S.obj_rot = (const float*)(b + off_rot);
-    c->gen_volumes = !bobjs.empty();
-    c->mesh_maps = false;
-    for (const DMesh& M : live) if (M.material < 0 || M.tex[4] >= 0) c->mesh_maps = true;
-    c->h_list = list; c->h_n_tri = n_list[0]; c->h_n_sphere = n_list[1]; c->h_n_unmasked = n_list[2] + n_list[3]; c->mask_valid = false;
-    c->S.n_list_tri = n_list[0]; c->S.n_list_sphere = n_list[1]; c->S.n_list_plane = n_list[2]; c->S.n_list_volume = n_list[3];
-    c->S.n_list_lin = n_list_lin; c->S.top_meshf = top_meshf; c->list_tree = top_meshf >= 0;
-    c->S.materials = (const DMaterial*)(b + off_mat);
-    c->S.meshes = (const DMesh*)(b + off_mesh);
-    c->S.meshf = (const DMeshF*)(b + off_meshf);
-    c->S.fnodes = (const float*)(b + off_fnodes);
-    c->S.ftris = (const float*)(b + off_ftris);
-    c->S.n_fnodes = (int)(fnodes.size() / 4);
-    c->S.nodes = (const float*)(b + off_nodes);
-    c->S.e2s = (const float*)(b + off_e2);
-    c->S.inodes = (const float*)(b + off_inodes);
-    c->S.lnodes = (const float*)(b + off_lnodes);
-    c->S.tris = (const float*)(b + off_tris);
-    c->S.triattr = (const DTriAttr*)(b + off_attr);
-    c->S.textures = (const DTexture*)(b + off_tex);
-    c->S.texels = (const uint8_t*)(b + off_texel);
-    c->S.n_objects = (int)objs.size();
-    c->S.n_meshes = (int)n_scene_meshes;
-    c->S.n_nodes = (int)(nodes.size() / 8);
-    c->S.n_tris = (int)(tris.size() / 12);
-    c->lds_bytes = (uint32_t)((nodes.size() + tris.size()) * 4);
-    for (int k = 0; k < 3; k++) { c->point_light_pos[k] = d->point_light_pos[k]; c->ambient[k] = d->ambient[k]; }
+    c->blob = blob; c->blob_bytes = total;
+    HIP_TRY(hipMemcpy(c->blob, sc.image.data(), total, hipMemcpyHostToDevice));
+    sc.image = std::vector<uint8_t>();
+    c->S = sc.device_scene(c->blob);
+    c->scene = std::move(sc);
     c->have_scene = true;
     return MI_OK;
 }
@@ -969,8 +380,8 @@ static const size_t kWfBytesPerPathTwoStage = (size_t)kCandMax * sizeof(uint2) +
 static uint32_t two_stage_mask(const mi_ctx* c, uint32_t flags) {
     if (flags & MI_OPT_REFERENCE_WALK) return 0u;
     uint32_t m = 0;
-    for (size_t i = 0; i < c->mesh_qualifies.size() && i < (size_t)kTwoStageMaxMeshes; i++)
-        if (c->mesh_qualifies[i] && ((flags & MI_OPT_TWO_STAGE) || c->mesh_default_ts[i])) m |= 1u << i;
+    for (size_t i = 0; i < c->scene.meshes.size() && i < (size_t)kTwoStageMaxMeshes; i++)
+        if (c->scene.meshes[i].qualifies && ((flags & MI_OPT_TWO_STAGE) || c->scene.meshes[i].default_ts)) m |= 1u << i;
     return m;
 }
 
@@ -1039,8 +450,9 @@ static int wf_prepare(mi_ctx* c, const mi_camera_desc* cam, uint32_t padded, uin
 // a further 1e-4 scene-unit slack; any non-finite value or a singular camera basis keeps everything.
 // Planes and ConvexVolumes are never masked.  Returns false when masking does not apply.
 static bool tile_masks(mi_ctx* c, const mi_camera_desc* cam, uint32_t flags, uint32_t stride) {
-    const int n_ts = c->h_n_tri + c->h_n_sphere;
-    const int n_mesh = (int)c->h_mesh_box.size();
+    const CompiledScene& sc = c->scene;
+    const int n_ts = sc.n_list_tri + sc.n_list_sphere;
+    const int n_mesh = (int)sc.meshes.size();
     if ((n_ts == 0 && n_mesh == 0) || n_ts > 64 || n_mesh > 32) return false;
     // rays must leave the eye itself (no lens) towards the image plane (focus_dist > 0 keeps the direction's sign)
     if (cam->projection_mode != MI_PROJ_PERSPECTIVE || cam->lens_radius != 0.0f || !(cam->focus_dist > 0.0f) || (flags & MI_OPT_NO_TILE_MASKS)) return false;
@@ -1088,10 +500,10 @@ static bool tile_masks(mi_ctx* c, const mi_camera_desc* cam, uint32_t flags, uin
           colmax = 1.0 + lu + lv; }                            // |R d| <= (|c0| + |up| + |view|) |d|, |c0| = 1
         const double t_reach = (double)cam->max_trace_dist * colmax;
         for (int e = 0; e < n_ts; e++) {
-            const DObject& ob = c->h_list[(size_t)e];
+            const DObject& ob = sc.list[(size_t)e];
             Shape& sh = shapes[(size_t)e];
             sh.cullable = false; sh.r = 0.0;
-            if (e < c->h_n_tri) {
+            if (e < sc.n_list_tri) {
                 double P[3][3], cen[3] = { 0, 0, 0 };
                 for (int vtx = 0; vtx < 3; vtx++) for (int q = 0; q < 3; q++) {
                     P[vtx][q] = (double)ob.f[q] + (vtx == 1 ? (double)ob.f[3 + q] : vtx == 2 ? (double)ob.f[6 + q] : 0.0);
@@ -1148,7 +560,7 @@ static bool tile_masks(mi_ctx* c, const mi_camera_desc* cam, uint32_t flags, uin
             if (!sh.cullable) continue;
             bool cull = false;
             for (int k = 0; k < 4 && !cull; k++) {
-                if (e < c->h_n_tri) {                       // the three (scaled) vertices all outside plane k
+                if (e < sc.n_list_tri) {                    // the three (scaled) vertices all outside plane k
                     bool all_out = true;
                     for (int vtx = 0; vtx < 3 && all_out; vtx++) {
                         double d = 0.0;
@@ -1167,7 +579,7 @@ static bool tile_masks(mi_ctx* c, const mi_camera_desc* cam, uint32_t flags, uin
         c->h_tile_mask[(size_t)j * tx + i] = mask;
         unsigned long long mm = 0xffffffffull;
         for (int m = 0; m < n_mesh && m < 32; m++) {          // the mesh word has 32 bits: meshes 32, 33, ... are never culled
-            const mi_ctx::MeshBox& B = c->h_mesh_box[(size_t)m];
+            const CompiledScene::Mesh& B = sc.meshes[(size_t)m];
             if (!B.cullable) continue;
             bool cull = false;
             for (int k = 0; k < 4 && !cull; k++) {
@@ -1183,7 +595,7 @@ static bool tile_masks(mi_ctx* c, const mi_camera_desc* cam, uint32_t flags, uin
         }
         const unsigned long long ts_bits = (n_ts >= 64) ? ~0ull : ((1ull << n_ts) - 1ull);
         const unsigned long long mesh_bits = (n_mesh >= 32) ? 0xffffffffull : ((1ull << n_mesh) - 1ull);
-        if ((mask & ts_bits) == 0ull && (mm & mesh_bits) == 0ull && c->h_n_unmasked == 0 && n_mesh <= 32) mm |= 1ull << 63;
+        if ((mask & ts_bits) == 0ull && (mm & mesh_bits) == 0ull && sc.n_unmasked == 0 && n_mesh <= 32) mm |= 1ull << 63;
         c->h_tile_mask[n_tiles + (size_t)j * tx + i] = mm;
     }
     c->mask_cam = *cam; c->mask_stride = stride; c->mask_valid = false;              // valid once uploaded
@@ -1247,57 +659,11 @@ static int render_tiles_wavefront(mi_ctx* c, const K1Args& k, const mi_camera_de
     const uint32_t all_meshes = c->S.n_meshes >= 32 ? 0xffffffffu : ((1u << c->S.n_meshes) - 1u);
     const uint32_t ts_mask = two_stage_mask(c, flags) & all_meshes;
     const uint32_t ref_mask = all_meshes & ~ts_mask;
-    // wf_trav LDS mode: 2 = BVH nodes in LDS, triangles through L1 (default when the nodes fit 64 KB:
-    // teapot 15 KB -> 8 blocks per CU; 122.6 ms vs 126.0 ms for mode 1 on cfg2 1080p/256), 1 = nodes +
-    // triangles (what the megakernels stage), 0 = everything from global memory.  The LDS window is the head of the node
-    // pool up to the last tree wf_trav walks (the scene compiler places those trees first).
-    int ref_nodes = 0, ref_e2 = 0, ref_inodes = 0;
-    for (size_t m = 0; m < c->mesh_node_end.size(); m++) if (m >= 32 || ((ref_mask >> m) & 1u)) {     // meshes 32, 33, ... have no mask bit: always walked here
-        ref_nodes = std::max(ref_nodes, c->mesh_node_end[m]); ref_e2 = std::max(ref_e2, c->mesh_e2_end[m]);
-        ref_inodes = std::max(ref_inodes, c->mesh_inode_end[m]);
-    }
-    // LDS image of a walker block: the nodes (leaves carry a and e1 of their triangle) + the triangles' e2 vectors
-    const size_t node_bytes = (size_t)ref_nodes * 32 + (size_t)ref_e2 * 16;
-    const size_t inode_bytes = (size_t)ref_inodes * 32;               // wf_trav_i: the interior nodes only
-    const int ref_lnodes = ref_nodes - ref_inodes;                    // the split pools hold every tree in the node pool's order: leaves = nodes - interior nodes
-    const size_t split_bytes = inode_bytes + (size_t)ref_lnodes * 48; // wf_trav_i<.., LEAF_LDS>: interior and leaf records
-    const size_t pair_bytes = (((size_t)ref_inodes * (size_t)kPairStride + 15) & ~(size_t)15) + (size_t)ref_lnodes * 48;   // wf_trav_i<.., PAIR>: 56-byte interior records
-    // 3 = the image needs most of a CU's 160 KB: ONE 1024-thread block per CU (16 waves).  4 = wf_trav_i: interior nodes in LDS, leaves
-    // from global memory — chosen over 3 whenever two of its blocks fit a CU (8 waves per SIMD instead of 4), and the only LDS mode
-    // left for images beyond 156 KB whose interior nodes still fit
-    int trav_lds_mode = 0;
-    if (ref_nodes > 0 && !c->tune.global_bvh) {
-        // one mesh to walk: the single-mesh forms over 32-byte records test boxes with the clamped form (slab_med3), 22 VALU per step like the
-        // paired layout's, on half the LDS and eight 256-thread blocks per CU (cfg2 walker 22.4 against 22.8 ms); several small meshes: the
-        // paired layout (the MULTI forms have no register left for the clamped form's class test)
-        const bool one_mesh = ref_mask == 1u && c->S.n_meshes <= 32;
-        if (one_mesh && split_bytes <= 64u * 1024u) trav_lds_mode = 5;
-        else if (pair_bytes <= 40u * 1024u) trav_lds_mode = 6;      // four 512-thread blocks per CU = 8 waves per SIMD
-        else if (split_bytes <= 64u * 1024u) trav_lds_mode = 5;     // (= node_bytes: both images hold every node once and every triangle once)
-        else if (node_bytes <= 64u * 1024u) trav_lds_mode = 2;
-        else if (inode_bytes <= 78u * 1024u) trav_lds_mode = 4;
-        else if (node_bytes <= 156u * 1024u) trav_lds_mode = 3;
-        else if (inode_bytes <= 156u * 1024u) trav_lds_mode = 4;
-    }
-    // 5 = wf_trav_i with the leaf records in LDS too (the whole split image within 64 KB): the explicit links make its interior step shorter than wf_trav's
-    // 6 = the same with the interior records in the paired layout (near / far plane per axis behind one 8-byte read: no selects in the box test)
-    if (c->tune.trav_lds >= 0) {
-        const int m = c->tune.trav_lds;
-        if (m == 0 || (m == 2 && node_bytes <= 64u * 1024u) || (m == 3 && node_bytes <= 156u * 1024u) || (m == 4 && inode_bytes <= 156u * 1024u && ref_nodes > 0) ||
-            (m == 5 && split_bytes <= 64u * 1024u && ref_nodes > 0) || (m == 6 && pair_bytes <= 40u * 1024u && ref_nodes > 0)) trav_lds_mode = m;
-    }
-    const size_t trav_lds_bytes = trav_lds_mode == 6 ? pair_bytes : trav_lds_mode == 5 ? split_bytes : (trav_lds_mode == 4 ? inode_bytes : (trav_lds_mode >= 2 ? node_bytes : 0));
-    a.R.lds_nodes = trav_lds_mode >= 4 ? (uint32_t)ref_inodes : (trav_lds_mode ? (uint32_t)ref_nodes : 0);
-    a.R.lds_tris = (trav_lds_mode == 2 || trav_lds_mode == 3) ? (uint32_t)ref_e2 : (trav_lds_mode >= 5 ? (uint32_t)ref_lnodes : 0);   // e2 entries / leaf records staged behind the nodes
+    const WalkerPlan walker = plan_walker(c->scene, ref_mask, c->tune.trav_lds, c->tune.trav_bpc, c->tune.global_bvh);
+    a.R.lds_nodes = walker.lds_nodes; a.R.lds_tris = walker.lds_tris;
     a.cand = (uint2*)c->d_cand; a.cand_hdr = (uint2*)c->d_cand_hdr;
     float4* bufs[2] = { (float4*)c->d_wf_a, (float4*)c->d_wf_b };
-    uint32_t trav_bpc = 6;                  // resident blocks per CU: bounded by LDS (160 KB) and by 8 waves/SIMD
-    if (trav_lds_mode == 2) { trav_bpc = (uint32_t)((160u * 1024u) / (node_bytes ? node_bytes : 1)); if (trav_bpc > 8) trav_bpc = 8; if (trav_bpc < 2) trav_bpc = 2; }
-    if (trav_lds_mode == 3) trav_bpc = 1;
-    if (trav_lds_mode == 4) trav_bpc = inode_bytes <= 78u * 1024u ? 2 : 1;
-    if (trav_lds_mode == 5) { trav_bpc = (uint32_t)((160u * 1024u) / (split_bytes ? split_bytes : 1)); if (trav_bpc > 8) trav_bpc = 8; if (trav_bpc < 2) trav_bpc = 2; }
-    if (trav_lds_mode == 6) { trav_bpc = (uint32_t)((160u * 1024u) / (pair_bytes ? pair_bytes : 1)); if (trav_bpc > 4) trav_bpc = 4; if (trav_bpc < 1) trav_bpc = 1; }
-    if (c->tune.trav_bpc > 0) trav_bpc = (uint32_t)c->tune.trav_bpc;
+    const uint32_t trav_bpc = walker.blocks_per_cu;
     const uint32_t trav_blocks = (uint32_t)c->n_cus * trav_bpc;
     const uint32_t travf_blocks = (uint32_t)c->n_cus * (c->tune.travf_bpc > 0 ? (uint32_t)c->tune.travf_bpc : 6u), replay_blocks = (uint32_t)c->n_cus * 8u;
     const uint32_t conc_trav_bpc = c->tune.conc_trav_bpc > 0 ? (uint32_t)c->tune.conc_trav_bpc : trav_bpc;
@@ -1432,14 +798,14 @@ static int render_tiles_wavefront(mi_ctx* c, const K1Args& k, const mi_camera_de
             if (split) {
                 HIP_TRY(hipStreamWaitEvent(c->aux_stream, c->ev_pfx, 0));
                 a.part = 1;
-                WF_TIMED_ON(5, c->aux_stream, launch_wf_main(a, grid_a, d_sig != nullptr, c->gen_volumes, c->mesh_maps, c->aux_stream));     // kind 5: its span includes waiting for CUs
+                WF_TIMED_ON(5, c->aux_stream, launch_wf_main(a, grid_a, d_sig != nullptr, c->scene.gen_volumes, c->scene.mesh_maps, c->aux_stream));     // kind 5: its span includes waiting for CUs
                 HIP_TRY(hipEventRecord(c->ev_part, c->aux_stream));
                 a.part = 2;
-                WF_TIMED(0, launch_wf_main(a, exact ? grid_all - grid_a : grid_all, d_sig != nullptr, c->gen_volumes, c->mesh_maps, stream));
+                WF_TIMED(0, launch_wf_main(a, exact ? grid_all - grid_a : grid_all, d_sig != nullptr, c->scene.gen_volumes, c->scene.mesh_maps, stream));
                 HIP_TRY(hipStreamWaitEvent(stream, c->ev_part, 0));
             } else {
                 a.part = 0;
-                WF_TIMED(0, launch_wf_main(a, grid_all, d_sig != nullptr, c->gen_volumes, c->mesh_maps, stream));
+                WF_TIMED(0, launch_wf_main(a, grid_all, d_sig != nullptr, c->scene.gen_volumes, c->scene.mesh_maps, stream));
             }
             // device-side bookkeeping: tables for the next pass and for wf_trav, and the header the host needs (grid of the
             // next pass, anything alive?), which wf_prefix stores straight into pinned host memory: the compute stream never
@@ -1463,9 +829,7 @@ static int render_tiles_wavefront(mi_ctx* c, const K1Args& k, const mi_camera_de
             if (ref_walk) {
                 a.trav_mask = ref_mask;
                 const uint32_t blocks = side_by_side ? (uint32_t)c->n_cus * conc_trav_bpc : trav_blocks;
-                if (trav_lds_mode == 6) WF_TIMED(1, launch_wf_trav_p(a, blocks, trav_lds_bytes, stream));
-                else if (trav_lds_mode >= 4) WF_TIMED(1, launch_wf_trav_i(a, blocks, trav_lds_bytes, trav_lds_mode == 5, &c->big_lds_enabled_i, stream));
-                else WF_TIMED(1, launch_wf_trav(a, blocks, trav_lds_mode, trav_lds_bytes, &c->big_lds_enabled, stream));
+                WF_TIMED(1, launch_walker(a, walker, blocks, &c->big_lds_enabled, stream));
             }
             if (ts_mask) {
                 a.trav_mask = ts_mask;
@@ -1528,7 +892,7 @@ static int render_tiles(mi_ctx* c, const mi_camera_desc* cam, const mi_render_op
     a.S = c->S;
     if (o->flags & MI_OPT_NO_LIST_TREE) { a.S.top_meshf = -1; a.S.n_list_lin = a.S.n_list_tri; }      // every list Triangle one by one (cross-check)
     make_camera(cam, &a.C);
-    for (int k = 0; k < 3; k++) { a.C.light[k] = c->point_light_pos[k]; a.C.ambient[k] = c->ambient[k]; }
+    for (int k = 0; k < 3; k++) { a.C.light[k] = c->scene.point_light_pos[k]; a.C.ambient[k] = c->scene.ambient[k]; }
     const bool phong = cam->shading_mode == MI_SHADE_PHONG;      // debug shader: own kernel, `variant` is ignored
     // path_samples != 1 (tracing.rs:310) branches at every hit: the literal, recursive estimator (pt_branch)
     const bool recursive = !phong && (cam->path_samples != 1 || o->variant == MI_VARIANT_RECURSIVE);
@@ -1538,7 +902,7 @@ static int render_tiles(mi_ctx* c, const mi_camera_desc* cam, const mi_render_op
     a.R.seed = o->seed; a.R.rank = o->rank; a.R.world = o->world;
     a.R.tiles_x = tx; a.R.tiles_y = ty; a.R.tiles_total = total;
     a.R.my_tiles = (total > (uint32_t)o->rank) ? (total - (uint32_t)o->rank + (uint32_t)o->world - 1) / (uint32_t)o->world : 0;
-    bool lds = c->S.n_meshes > 0 && c->lds_bytes <= 64u * 1024u && !c->tune.global_bvh;
+    bool lds = c->S.n_meshes > 0 && c->scene.lds_bytes <= 64u * 1024u && !c->tune.global_bvh;
     a.R.lds_nodes = lds ? (uint32_t)c->S.n_nodes : 0;
     a.R.lds_tris = lds ? (uint32_t)c->S.n_tris : 0;
     a.seed_key = lowbias32(o->seed ^ 0x68e31da4u);
@@ -1570,9 +934,9 @@ static int render_tiles(mi_ctx* c, const mi_camera_desc* cam, const mi_render_op
         int rcw = render_tiles_wavefront(c, a, cam, wa, wf_batch, lds, o->flags, d_compact, a.sig, range, stream);
         if (rcw != MI_OK) return rcw;
     } else if (variant == MI_VARIANT_VOTED || variant == MI_VARIANT_VOTED_DIAG)
-        HIP_TRY(launch_megakernel_voted(a, n_blocks, lds, a.sig != nullptr, diag, c->gen_volumes, c->lds_bytes + c->tune.lds_pad, stream));
+        HIP_TRY(launch_megakernel_voted(a, n_blocks, lds, a.sig != nullptr, diag, c->scene.gen_volumes, c->scene.lds_bytes + c->tune.lds_pad, stream));
     else
-        HIP_TRY(launch_megakernel(a, n_blocks, lds, a.sig != nullptr, c->lds_bytes, stream));
+        HIP_TRY(launch_megakernel(a, n_blocks, lds, a.sig != nullptr, c->scene.lds_bytes, stream));
     HIP_TRY(hipEventRecord(c->ev_stop, stream));
     c->ev_recorded = true;
     if (st) {

@@ -1,5 +1,5 @@
 // pt_device.h — device-resident scene layout shared by the host scene compiler
-// (mi_rt.cpp) and the HIP kernels (pt_kernels.hip).  gfx950 only.
+// (scene_compile.cpp) and the HIP kernels (pt_kernels.hip).  gfx950 only.
 //
 // Layout rules (DESIGN.md "Data layout in HBM"):
 //  * The linear object list of Scene.objects (tracing.rs:215,330) is an array of
@@ -150,7 +150,7 @@ struct DScene {
     // boundary records of ConvexVolumes whose boundary is not the inline sphere (same record format; MESH: ref = entry of `meshes`
     // at or behind n_meshes — the table holds the Scene.objects meshes first, then the boundary-only ones)
     const PT_CONST_AS DObject*   bobjs;
-    // sample_hemisphere's rotation for the two normals of every list Triangle, hoisted to the host (mi_rt.cpp): 3 float4 per entry,
+    // sample_hemisphere's rotation for the two normals of every list Triangle, hoisted to the host (scene_compile.cpp): 3 float4 per entry,
     // entry 2 i + (frontface ? 0 : 1) of Scene.objects entry i
     const PT_CONST_AS float*     obj_rot;
     // two-stage traversal (meshes that qualify): F-tree nodes (same 2 x float4 node format; leaf word = (first << 3) | (count - 1)
@@ -284,6 +284,22 @@ struct WfArgs {
     uint2* cand;
     uint2* cand_hdr;
     unsigned long long* diag;   // developer builds with -DPT_WF_STAMPS: [16] summed s_memtime deltas of sampled wf_main waves
+};
+
+// How a render walks the meshes that take the reference's tree (scene_compile.cpp plan_walker -> pt_kernels.hip launch_walker).
+// The form values are those of MI_RT_WF_TRAV_LDS.
+enum : int {
+    kWalkGlobal = 0,      // wf_trav: the tree in global memory
+    kWalkInterior = 4,    // wf_trav_i<1024>: interior records in LDS, leaf records from global memory
+    kWalkSplit = 5,       // wf_trav_i<256, .., LEAF_LDS>: interior and leaf records in LDS
+    kWalkPaired = 6,      // wf_trav_i<512, .., LEAF_LDS, PAIR>: the same with 56-byte paired interior records
+};
+struct WalkerPlan {
+    int form;
+    uint32_t lds_bytes;       // dynamic LDS per block
+    uint32_t lds_nodes;       // DRender.lds_nodes: interior records staged
+    uint32_t lds_tris;        // DRender.lds_tris: leaf records staged behind them
+    uint32_t blocks_per_cu;
 };
 
 }  // namespace pt

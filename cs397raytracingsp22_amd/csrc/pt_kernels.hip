@@ -14,7 +14,7 @@
 //                 compile-time forms per scene content (mesh branch, maps, rare kinds, generic volume boundaries); survivors
 //                 appended per shard in two classes (A: plain Triangle / Plane hit, nothing left to walk; B: the rest)
 //   wf_prefix     shard counters -> block tables of the next pass (also the walkers' work list) + the header for the host
-//   wf_trav       persistent walkers over the class-B blocks, the reference's tree as a skip-link image (in LDS, or in global memory), voted steps
+//   wf_trav       persistent walkers over the class-B blocks, the reference's tree as a skip-link image in global memory, voted steps
 //   wf_trav_i     the same walk over split pools with explicit links: interior records in LDS; the leaf records in LDS too for trees whose image
 //                 fits 64 KB (the default small-tree walker since round 4: 8 x 256 threads per CU), from global memory for 64 .. 150 KB (2 x 1024)
 //   wf_filter_f / wf_trav_f / wf_replay   exact two-stage traversal of large meshes: root-box filter -> padded SAH tree of
@@ -377,13 +377,11 @@ __device__ __forceinline__ bool sphere_t(f3 o, f3 d, f3 center, float r2, float 
 }
 
 // Triangle / IndexedTriangle Moller-Trumbore geometry.rs:331-349, 431-447
-// FAST = false: the IEEE division for 1/g (the 1024-thread walker is LDS-bound, the short reciprocal's range check only costs there)
-template <bool FAST = true>
 __device__ __forceinline__ bool tri_t(f3 o, f3 d, f3 a, f3 e1, f3 e2, float t_min, float t_max,
                                       float& t_out, float& u_out, float& v_out) {
     f3 q = cross(d, e2);
     float g = dot(e1, q);
-    float f = FAST ? rcp_exact(g) : 1.0f / g;
+    float f = rcp_exact(g);
     f3 s = o - a;
     float u = f * dot(s, q);
     f3 r = cross(s, e1);
@@ -498,17 +496,6 @@ template <bool LDS>
 struct Bvh {
     typename BvhPtr<LDS>::type nodes;      // LDS, or constant-AS global
     typename BvhPtr<LDS>::type tris;
-    __device__ __forceinline__ void node(int i, float4& n0, float4& n1) const { n0 = nodes[2 * i]; n1 = nodes[2 * i + 1]; }
-    __device__ __forceinline__ void tri(int i, f3& a, f3& e1, f3& e2) const {
-        float4 t0 = tris[3 * i], t1 = tris[3 * i + 1], t2 = tris[3 * i + 2];
-        a = mk3(t0.x, t0.y, t0.z); e1 = mk3(t1.x, t1.y, t1.z); e2 = mk3(t2.x, t2.y, t2.z);
-    }
-};
-
-// nodes in LDS, triangles through L1/L2 (wf_trav: halves the LDS footprint -> more resident waves)
-struct BvhNodesLds {
-    const float4* nodes;
-    cf4_ptr tris;
     __device__ __forceinline__ void node(int i, float4& n0, float4& n1) const { n0 = nodes[2 * i]; n1 = nodes[2 * i + 1]; }
     __device__ __forceinline__ void tri(int i, f3& a, f3& e1, f3& e2) const {
         float4 t0 = tris[3 * i], t1 = tris[3 * i + 1], t2 = tris[3 * i + 2];
@@ -893,7 +880,7 @@ __device__ __forceinline__ void sphere_stage1(REC ob, f3 o, f3 d, float a, float
 
 // RARE = false compiles the Plane / ConvexVolume loop out (a scene without either: the Cornell configurations)
 // TOP = true (long lists; the scene compiler decides): only the first n_list_lin Triangles — the large ones — are tested one by one; the others
-// sit in a top-level tree (mi_rt.cpp, bvh_build.hpp FTree: SAH over the triangles' boxes, 16-byte quantised nodes) that every lane walks
+// sit in a top-level tree (scene_compile.cpp, bvh_build.hpp FTree: SAH over the triangles' boxes, 16-byte quantised nodes) that every lane walks
 // with the boxes padded by the proven bound on what the reference's f32 test can accept, running the reference's own test on the triangles of
 // the leaves it reaches.  A triangle whose padded box the ray misses would have failed that test; the closest hit over the rest does not
 // depend on the order of evaluation (ties: the lower Scene.objects index, which the leaf triangles carry).  A ray the bound does not cover
@@ -1088,7 +1075,7 @@ __device__ __forceinline__ void scatter_raw(const DScene& S, const Surf& s, f3 d
             v.y = fabsf(v.y);
             if (s.rot >= 0) {
                 // the rotation depends on the normal alone, and a list Triangle presents one of two: its matrix was computed at upload by the
-                // same f32 operations (mi_rt.cpp obj_rot) — 3 loads from a table of a few cache lines instead of ~85 VALU instructions (two
+                // same f32 operations (scene_compile.cpp rotations) — 3 loads from a table of a few cache lines instead of ~85 VALU instructions (two
                 // sqrt, a division, a reciprocal, two ulps_eq) in a kernel that is bound by instruction issue
                 cf4_ptr R = (cf4_ptr)S.obj_rot + 3 * s.rot;
                 const float4 r0 = R[0], r1 = R[1], r2 = R[2];
@@ -2073,26 +2060,19 @@ __device__ __forceinline__ bool wf_slot(const WfArgs& A, uint32_t blocks_a, uint
     return local < count;
 }
 
-// persistent BVH walker with per-lane dynamic refill from the sharded queues
-// LDS: 0 = BVH in global memory, 2 = nodes (leaves carry a and e1 of their triangle) + the e2 vectors in LDS
-template <int LDS> struct TravBvh { typedef Bvh<false> type; };
-template <> struct TravBvh<2> { typedef BvhNodesLds type; };
-__device__ __forceinline__ void bvh_bind(BvhNodesLds& B, const DScene& S, int) { B.nodes = k1_lds; B.tris = (cf4_ptr)S.tris; }
-
-// BS: threads per block.  256 for the small-LDS modes; 1024 (one block per CU) when the node array needs most of a
-// CU's 160 KB of LDS.  (Round 3: trees of that size — the drone's 3471 nodes = 140 KB with their leaves — now take wf_trav_i below,
-// which keeps only the interior nodes in LDS and runs TWO 1024-thread blocks per CU; this form remains for trees whose interior
-// nodes alone exceed 78 KB while the whole image still fits 156 KB, and as a cross-check: tests/test_gpu_walkers.py.)
-// (Negative result, round 2: TWO RAYS PER LANE in the 1024-thread form — it runs 4 waves per SIMD whatever its register count,
-// PMC shows 43 % of a wave's life parked at s_waitcnt, so two interleaved walks per lane looked free.  Built as a template
+// persistent BVH walker with per-lane dynamic refill from the sharded queues, over the reference's tree as a skip-link image in
+// global memory (leaves carry a and e1 of their triangle, e2 comes from its own pool).  Trees whose interior nodes fit LDS take
+// wf_trav_i below.
+// (Negative result, round 2: TWO RAYS PER LANE in a 1024-thread form with the tree in LDS — it ran 4 waves per SIMD whatever its register
+// count, PMC showed 43 % of a wave's life parked at s_waitcnt, so two interleaved walks per lane looked free.  Built as a template
 // parameter with the per-ray state slimmed to fit 128 VGPRs without spills (o, d re-read for a further mesh, the hit record
 // merged in memory at the end of a walk, u and v recomputed by one more triangle test): bit-exact, but cfg4 wf_trav
 // 270 -> 321 ms, HEAD 54 -> 67 ms; the slimmed state alone, one ray per lane: 310 / 63 ms and cfg2 28.4 -> 34 ms.  The
 // walker is bound by VALU issue and LDS bank conflicts of its random 32-byte node reads, not by uncovered latency.)
 // MULTI = false: this launch walks ONE mesh (bit 0 of trav_mask alone): the step to a further mesh is compiled out and the world-space
 // ray is dead once it has been taken to object space (6 VGPRs of a 64-register budget)
-template <int LDS, int BS, bool MULTI>
-__global__ __launch_bounds__(BS, (BS == 256 ? PT_TRAV_WAVES : 4)) void wf_trav(WfArgs A) {
+template <bool MULTI>
+__global__ __launch_bounds__(kBlock, PT_TRAV_WAVES) void wf_trav(WfArgs A) {
     const DScene& S = A.S;
     // Work distribution over the slots of the class-B blocks (wf_slot above):
     // wave w owns chunk w outright, later chunks come from one shared cursor.  The static first chunk
@@ -2101,34 +2081,23 @@ __global__ __launch_bounds__(BS, (BS == 256 ? PT_TRAV_WAVES : 4)) void wf_trav(W
     // the static chunks cover never touches the cursor at all.
     const uint32_t blocks_a = A.in_blkpfx[kWfShards];
     const uint32_t n_q = (A.in_blkpfx[2 * kWfShards] - blocks_a) * (uint32_t)kBlock;      // slots
-    const uint32_t n_waves = gridDim.x * ((uint32_t)BS / 64u);
+    const uint32_t n_waves = gridDim.x * ((uint32_t)kBlock / 64u);
     // 256 rays per grab (128: the cursor's round trip shows, trav x3; 1024: long tails, +5 %).  A queue too short to give every
     // wave 256 rays is dealt out evenly instead, in whole waves' worth of 64: 200 k rays are then one walk's time on 3 k waves,
     // not four walks in a row on 800 (the late passes of a frame, and every pass of a small tile share)
     uint32_t chunk = 256u;
     if (n_q < n_waves * 256u) chunk = max(64u, ((n_q + n_waves - 1u) / n_waves + 63u) & ~63u);
     const bool shared_part = n_waves * chunk < n_q;                  // anything beyond the static chunks?
-    if (blockIdx.x * ((uint32_t)BS / 64u) * chunk >= n_q) return;       // nothing for this block (then nothing is left over either)
-    typename TravBvh<LDS>::type B;
-    const int lds_nn = (int)A.R.lds_nodes * 2;                       // float4 slots of the staged nodes; the e2 vectors follow
-    if (LDS != 0) {
-        cf4_ptr gn = (cf4_ptr)S.nodes;
-        cf4_ptr ge = (cf4_ptr)S.e2s;
-        const int ne = (int)A.R.lds_tris;
-        for (int k = threadIdx.x; k < lds_nn; k += BS) k1_lds[k] = gn[k];
-        for (int k = threadIdx.x; k < ne; k += BS) k1_lds[lds_nn + k] = ge[k];
-        __syncthreads();
-    }
-    bvh_bind(B, S, lds_nn);
+    if (blockIdx.x * ((uint32_t)kBlock / 64u) * chunk >= n_q) return;   // nothing for this block (then nothing is left over either)
+    Bvh<false> B;
+    bvh_bind(B, S, 0);
     const float t_min = 0.001f, t_max = A.C.max_trace_dist;
     const uint32_t cap = A.cap;
-    // clamp of the prefetch that follows the last node of a tree: inside the LDS image when there is one (it holds the head of
-    // the node pool only: a clamp to the pool's last node would read behind the staged nodes), else inside the pool
-    const int last_node = (LDS != 0 ? (int)A.R.lds_nodes : S.n_nodes) - 1;
+    const int last_node = S.n_nodes - 1;                             // clamp of the prefetch that follows the last node of a tree
     const uint32_t lane = threadIdx.x & 63;
 
     // wave-uniform work cursor: a chunk [wnext, wend) of the queue
-    const uint32_t wave_id = blockIdx.x * ((uint32_t)BS / 64u) + (threadIdx.x >> 6);
+    const uint32_t wave_id = blockIdx.x * ((uint32_t)kBlock / 64u) + (threadIdx.x >> 6);
     uint32_t wnext = wave_id * chunk, wend = min(wnext + chunk, n_q);
     bool drained = false;
     if (wnext >= n_q) { wnext = wend = 0; drained = true; }
@@ -2225,9 +2194,9 @@ __global__ __launch_bounds__(BS, (BS == 256 ? PT_TRAV_WAVES : 4)) void wf_trav(W
         const int n_leaf = __popcll(__builtin_amdgcn_ballot_w64(at_leaf));
         const int n_inner = __popcll(__builtin_amdgcn_ballot_w64(at_inner));
         if (n_inner >= n_leaf * PT_TRAV_LEAF_W) {
-            // burst of interior steps, no vote in between.  At 6 waves/SIMD the LDS latency of the
-            // dependent node fetch is covered by the other waves, and this form is 20 instructions
-            // per step shorter than prefetching both successors and selecting (used in K1).
+            // burst of interior steps, no vote in between.  The latency of the dependent node fetch is
+            // covered by the other waves, and this form is 20 instructions per step shorter than
+            // prefetching both successors and selecting (used in K1).
 #pragma unroll
             for (int j = 0; j < PT_TRAV_BURST; j++) {
                 const bool act = have & (ti < tend) & (__float_as_int(c1.w) < 0);
@@ -2243,16 +2212,15 @@ __global__ __launch_bounds__(BS, (BS == 256 ? PT_TRAV_WAVES : 4)) void wf_trav(W
             }
         } else {
             // the leaf node just fetched IS the triangle's a and e1 (pt_device.h DScene.e2s); e2 is one more 16-byte read
-            // from the LDS image (or from the e2 pool when the tree is walked from global memory)
+            // from the e2 pool
             for (int k = 0; k < (PT_TRAV_LEAF2 > 0 ? 2 : 1); k++) {
                 const int ltri = __float_as_int(c1.w);
                 const bool lf = have & (ti < tend) & (ltri >= 0);
                 if (k > 0 && __popcll(__builtin_amdgcn_ballot_w64(lf)) < PT_TRAV_LEAF2) break;
                 if (lf) {
-                    float4 ev;
-                    if (LDS != 0) ev = k1_lds[lds_nn + te2 + ltri]; else ev = ((cf4_ptr)S.e2s)[te2 + ltri];
+                    const float4 ev = ((cf4_ptr)S.e2s)[te2 + ltri];
                     float t, u, v;
-                    bool ok = tri_t<BS == 256>(too, tod, mk3(c0.x, c0.y, c0.z), mk3(c1.x, c1.y, c1.z), mk3(ev.x, ev.y, ev.z), t_min, tbt, t, u, v);
+                    bool ok = tri_t(too, tod, mk3(c0.x, c0.y, c0.z), mk3(c1.x, c1.y, c1.z), mk3(ev.x, ev.y, ev.z), t_min, tbt, t, u, v);
                     tbt = ok ? t : tbt; tbtri = ok ? ltri : tbtri; tbu = ok ? u : tbu; tbv = ok ? v : tbv;
                     ti = ti + 1;
                     B.node(min(ti, last_node), c0, c1);
@@ -2299,13 +2267,13 @@ __global__ __launch_bounds__(BS, (BS == 256 ? PT_TRAV_WAVES : 4)) void wf_trav(W
 
 // ---------------------------------------------------------------- wf_trav_i: the walker for trees of 64 .. 150 KB
 // Same walk, same arithmetic, same results as wf_trav; different storage.  A tree whose whole image (nodes with their leaves'
-// triangles) exceeds 64 KB forces wf_trav into ONE 1024-thread block per CU: 4 waves per SIMD, which cannot cover the latency of
+// triangles) exceeds 64 KB needed ONE 1024-thread block per CU in wf_trav's former LDS form: 4 waves per SIMD, which cannot cover the latency of
 // the conflicted LDS node reads (16 waves queue behind one LDS pipe) AND the dependent VALU chain of the slab test — PMC showed the
 // LDS-busy time and the VALU-issue time of that kernel ADDING up to its duration instead of overlapping.  Here only the INTERIOR
 // nodes live in LDS (pt_device.h DScene.inodes: half the bytes, every link explicit), so two such blocks fit a CU — 8 waves per
 // SIMD — and a leaf is three 16-byte reads from the leaf pool in global memory (L2-resident: 11 of the ~96 steps of a drone ray).
 // LEAF_LDS = true (round 4): the leaf records staged in LDS as well, behind the interior ones — for trees whose WHOLE split image fits 64 KB
-// (the teapot: 7.6 + 11.5 KB, eight 256-thread blocks per CU as wf_trav<2, 256>).  Same storage cost as wf_trav's image, but the explicit
+// (the teapot: 7.6 + 11.5 KB, eight 256-thread blocks per CU).  Same storage cost as a whole skip-link image, but the explicit
 // links make an interior step four VALU instructions shorter (no `ti < tend`, no `ti + 1`, no clamp of the prefetch behind the last node).
 // PAIR = true (round 4; needs LEAF_LDS): the interior records are re-laid while they are staged, 56 bytes each —
 //   {bmin.x, bmax.x, bmax.x, bmin.x}{.y ...}{.z ...}{link on a miss, link on a hit}, links to interior records as LDS byte offsets —
@@ -3199,45 +3167,36 @@ hipError_t launch_wf_main(const WfArgs& a, uint32_t n_blocks, bool sig, bool gv,
 #undef PT_WF_MAIN2
     return hipGetLastError();
 }
-// big_lds_enabled: the calling context's record of the > 64 KB dynamic-LDS opt-in.  The attribute belongs to the
-// function ON THE CURRENT DEVICE, so it is kept per context (one context = one device), not per process.
-hipError_t launch_wf_trav(const WfArgs& a, uint32_t n_blocks, int lds_mode, size_t lds_bytes, bool* big_lds_enabled, hipStream_t stream) {
-    dim3 grid(n_blocks), block(kBlock);
+// The walker of the reference's tree that `p` names (scene_compile.cpp plan_walker).  big_lds_enabled: the calling context's record of
+// wf_trav_i<1024>'s > 64 KB dynamic-LDS opt-in.  The attribute belongs to the function ON THE CURRENT DEVICE, so it is kept per
+// context (one context = one device), not per process.
+hipError_t launch_walker(const WfArgs& a, const WalkerPlan& p, uint32_t n_blocks, bool* big_lds_enabled, hipStream_t stream) {
     const bool multi = a.trav_mask != 1u || a.S.n_meshes > 32;      // more than mesh 0 to walk in this launch
-    if (lds_mode == 3) {           // nodes in LDS, one 1024-thread block per CU
+    const dim3 grid(n_blocks);
+    const size_t lds = p.lds_bytes;
+    switch (p.form) {
+    case kWalkPaired:              // the paired layout: 512-thread blocks
+        if (multi) hipLaunchKernelGGL((wf_trav_i<512, true, true, true>), grid, dim3(512), lds, stream, a);
+        else hipLaunchKernelGGL((wf_trav_i<512, false, true, true>), grid, dim3(512), lds, stream, a);
+        break;
+    case kWalkSplit:               // the whole split image (interior + leaf records) fits 64 KB: 256-thread blocks, several per CU
+        if (multi) hipLaunchKernelGGL((wf_trav_i<256, true, true>), grid, dim3(256), lds, stream, a);
+        else hipLaunchKernelGGL((wf_trav_i<256, false, true>), grid, dim3(256), lds, stream, a);
+        break;
+    case kWalkInterior:            // interior records only: 1024-thread blocks, one or two per CU
         if (!*big_lds_enabled) {
-            hipError_t e = hipFuncSetAttribute((const void*)wf_trav<2, 1024, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            if (e == hipSuccess) e = hipFuncSetAttribute((const void*)wf_trav<2, 1024, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+            hipError_t e = hipFuncSetAttribute((const void*)wf_trav_i<1024, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+            if (e == hipSuccess) e = hipFuncSetAttribute((const void*)wf_trav_i<1024, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
             if (e != hipSuccess) return e;
             *big_lds_enabled = true;
         }
-        if (multi) hipLaunchKernelGGL((wf_trav<2, 1024, true>), grid, dim3(1024), lds_bytes, stream, a);
-        else hipLaunchKernelGGL((wf_trav<2, 1024, false>), grid, dim3(1024), lds_bytes, stream, a);
+        if (multi) hipLaunchKernelGGL((wf_trav_i<1024, true>), grid, dim3(1024), lds, stream, a);
+        else hipLaunchKernelGGL((wf_trav_i<1024, false>), grid, dim3(1024), lds, stream, a);
+        break;
+    default:                       // the tree in global memory
+        if (multi) hipLaunchKernelGGL((wf_trav<true>), grid, dim3(kBlock), 0, stream, a);
+        else hipLaunchKernelGGL((wf_trav<false>), grid, dim3(kBlock), 0, stream, a);
     }
-    else if (lds_mode == 2) { if (multi) hipLaunchKernelGGL((wf_trav<2, 256, true>), grid, block, lds_bytes, stream, a); else hipLaunchKernelGGL((wf_trav<2, 256, false>), grid, block, lds_bytes, stream, a); }
-    else { if (multi) hipLaunchKernelGGL((wf_trav<0, 256, true>), grid, block, 0, stream, a); else hipLaunchKernelGGL((wf_trav<0, 256, false>), grid, block, 0, stream, a); }
-    return hipGetLastError();
-}
-hipError_t launch_wf_trav_p(const WfArgs& a, uint32_t n_blocks, size_t lds_bytes, hipStream_t stream) {      // the paired layout: 512-thread blocks
-    if (a.trav_mask != 1u || a.S.n_meshes > 32) hipLaunchKernelGGL((wf_trav_i<512, true, true, true>), dim3(n_blocks), dim3(512), lds_bytes, stream, a);
-    else hipLaunchKernelGGL((wf_trav_i<512, false, true, true>), dim3(n_blocks), dim3(512), lds_bytes, stream, a);
-    return hipGetLastError();
-}
-hipError_t launch_wf_trav_i(const WfArgs& a, uint32_t n_blocks, size_t lds_bytes, bool leaf_lds, bool* big_lds_enabled, hipStream_t stream) {
-    if (leaf_lds) {                // the whole split image (interior + leaf records) fits 64 KB: 256-thread blocks, several per CU
-        if (a.trav_mask != 1u || a.S.n_meshes > 32) hipLaunchKernelGGL((wf_trav_i<256, true, true>), dim3(n_blocks), dim3(256), lds_bytes, stream, a);
-        else hipLaunchKernelGGL((wf_trav_i<256, false, true>), dim3(n_blocks), dim3(256), lds_bytes, stream, a);
-        return hipGetLastError();
-    }
-    if (!*big_lds_enabled) {       // the attribute belongs to the function on the current device: kept per context
-        hipError_t e = hipFuncSetAttribute((const void*)wf_trav_i<1024, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e == hipSuccess) e = hipFuncSetAttribute((const void*)wf_trav_i<1024, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) return e;
-        *big_lds_enabled = true;
-    }
-    const bool multi = a.trav_mask != 1u || a.S.n_meshes > 32;
-    if (multi) hipLaunchKernelGGL((wf_trav_i<1024, true>), dim3(n_blocks), dim3(1024), lds_bytes, stream, a);
-    else hipLaunchKernelGGL((wf_trav_i<1024, false>), dim3(n_blocks), dim3(1024), lds_bytes, stream, a);
     return hipGetLastError();
 }
 hipError_t launch_wf_filter_f(const WfArgs& a, uint32_t blocks_per_shard, hipStream_t stream) {

@@ -199,6 +199,41 @@ def test_cameras_that_make_every_ray_non_finite_are_refused(gpu_ctx, field, valu
     assert np.isfinite(f32).all()
 
 
+def test_a_failed_upload_leaves_the_previous_scene(gpu_ctx):
+    """An upload that the scene compiler refuses (here at the 4 GiB check of the blob) leaves the context as it was: the next
+    render of the previous scene, with a camera whose tile masks it has not computed yet, equals a fresh context's.  The refused
+    scene has the teapot far outside the view, so masks computed from its root box would drop the visible teapot."""
+    import ctypes as C
+    from cs397raytracingsp22_amd import Context
+    sc = scenes.config2(96, 64, 4, 6)
+    flat = sc.flatten()
+    gpu_ctx.upload(flat)
+    gpu_ctx.render(sc.camera, seed=5, want_u8=False)
+    teapot = sc.objects[-1]
+    other = Scene(sc.camera, sc.objects[:-1] + [StaticMesh(teapot.mesh, teapot.material, teapot.textures,
+                                                           cgmath.from_translation((50.0, 0.0, 0.0)))]).flatten()
+    # one unreferenced 32768^2 texture: its RGBA8 copy alone is 2^32 bytes.  The compiler only reads the zeros it is given
+    big = np.zeros(32768 * 32768 * 3, np.uint8)
+    texs = [other.desc.textures[i] for i in range(other.desc.n_textures)]
+    texs.append(abi.mi_texture(32768, 32768, big.ctypes.data_as(C.POINTER(C.c_uint8))))
+    desc = abi.mi_scene_desc.from_buffer_copy(other.desc)
+    desc.textures, desc.n_textures = (abi.mi_texture * len(texs))(*texs), len(texs)
+    lib = abi.load()
+    assert lib.mi_scene_upload(gpu_ctx._h, C.byref(desc)) == abi.MI_ERR_UNSUPPORTED
+    assert b"4 GiB" in lib.mi_last_error()
+    del big
+    cam = sc.camera
+    cam.eyepoint = (0.3, 3.2, 6.4)
+    f32, _, _, _ = gpu_ctx.render(cam, seed=5, want_u8=False)
+    fresh = Context(0)
+    try:
+        fresh.upload(flat)
+        ref, _, _, _ = fresh.render(cam, seed=5, want_u8=False)
+    finally:
+        fresh.close()
+    assert np.array_equal(f32, ref)
+
+
 def test_more_ranks_than_tiles(gpu_ctx):
     """A 40x20 image is two tiles: with world 5, ranks 2, 3, 4 own nothing.  Every variant must cope with an empty share
     (and still write its padding slot as zeros), and the assembly equals the one-rank image bit for bit."""
