@@ -13,8 +13,9 @@ FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -fno-fast-ma
 "$HIPCC" $FLAGS -c "$HERE/pt_kernels.hip" -o "$OUT/pt_kernels.o"
 "$HIPCC" $FLAGS -x hip --cuda-host-only -c "$HERE/mi_rt.cpp" -o "$OUT/mi_rt.o"
 "$HIPCC" $FLAGS -x hip --cuda-host-only -c "$HERE/scene_compile.cpp" -o "$OUT/scene_compile.o"
-"$HIPCC" --offload-arch=gfx950 -shared -fPIC -o "$OUT/libmi_rt.so" "$OUT/pt_kernels.o" "$OUT/mi_rt.o" "$OUT/scene_compile.o" -ldl -lpthread
-rm -f "$OUT/pt_kernels.o" "$OUT/mi_rt.o" "$OUT/scene_compile.o"
+"$HIPCC" $FLAGS -x hip --cuda-host-only -c "$HERE/render_plan.cpp" -o "$OUT/render_plan.o"
+"$HIPCC" --offload-arch=gfx950 -shared -fPIC -o "$OUT/libmi_rt.so" "$OUT/pt_kernels.o" "$OUT/mi_rt.o" "$OUT/scene_compile.o" "$OUT/render_plan.o" -ldl -lpthread
+rm -f "$OUT/pt_kernels.o" "$OUT/mi_rt.o" "$OUT/scene_compile.o" "$OUT/render_plan.o"
 # C++ caller of the C ABI through the host mirror of the reference interface (host/*.hpp)
 g++ -std=c++17 -O2 -ffp-contract=off -Wall -I"$HERE/../../include" "$HERE/../host/mi_rt_cli.cpp" -o "$OUT/mi_rt_cli" -L"$OUT" -lmi_rt -lz -Wl,-rpath,'$ORIGIN'
 echo "built $OUT/libmi_rt.so and $OUT/mi_rt_cli"

@@ -24,7 +24,7 @@
 
 #include "../../include/mi_rt.h"
 #include "pt_device.h"
-#include "scene_compile.hpp"
+#include "render_plan.hpp"
 
 #pragma clang fp contract(off)
 
@@ -64,6 +64,11 @@ int pt::fail(int code, const char* fmt, ...) {
     do {                                                                                       \
         hipError_t e_ = (expr);                                                                \
         if (e_ != hipSuccess) return fail(MI_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(e_)); \
+    } while (0)
+#define MI_TRY(expr)                                                                           \
+    do {                                                                                       \
+        const int rc_ = (expr);                                                                \
+        if (rc_ != MI_OK) return rc_;                                                          \
     } while (0)
 
 namespace {
@@ -105,13 +110,17 @@ struct mi_ctx {
     void* d_wf_samp = nullptr; size_t wf_samp_bytes = 0;
     void* d_wf_acc = nullptr; size_t wf_acc_bytes = 0;
     uint32_t* d_wf_cnt = nullptr;
-    uint32_t* h_hdr = nullptr;                       // pinned + device-mapped ring of 8-word slots: wf_prefix writes {blocks, live, queue, seq, live class B, class-A blocks}
+    uint32_t* h_hdr = nullptr;                       // pinned + device-mapped ring of kHdrRing header slots (pt_device.h kHdr*), written by wf_prefix
     uint64_t wf_counts[8] = { 0, 0, 0, 0, 0, 0, 0, 0 };   // last frame: passes, class-A paths streamed, class-B paths, queue entries, samples, pixels
     uint32_t* h_hdr_dev = nullptr;                   // its device-side address
     uint32_t hdr_seq = 0;
-    // per-tile primary-ray masks over the kind-grouped list and the meshes' root boxes (see tile_masks)
-    std::vector<unsigned long long> h_tile_mask; void* d_tile_mask = nullptr; size_t tile_mask_bytes = 0;
-    mi_camera_desc mask_cam{}; uint32_t mask_stride = 0; bool mask_valid = false;
+    // the primary-ray tile masks (render_plan.cpp tile_masks) of the last camera and their device copy; an upload invalidates them
+    struct MaskCache {
+        bool valid = false, applies = false;
+        mi_camera_desc cam{}; uint32_t stride = 0, flags = 0;
+        std::vector<uint64_t> words;
+        void* d_words = nullptr; size_t d_bytes = 0;
+    } masks;
     std::vector<hipEvent_t> wf_ev;                   // event pool for per-kernel timing of the pipeline
     float wf_ms[8] = { 0, 0, 0, 0, 0, 0, 0, 0 };     // last frame: wf_main, wf_trav, wf_reduce totals (ms), launches, wf_trav_f, wf_replay
     int n_cus = 256;
@@ -152,6 +161,18 @@ extern "C" const char* mi_last_error(void) { return g_err.c_str(); }
 
 extern "C" void mi_ctx_destroy(mi_ctx* c);
 
+// The wavefront pipeline's counter buffer (d_wf_cnt), in words.  wf_main appends per (class, shard) into out_count (class A
+// shards, then class B shards) and counts path segments in trav_count; trav_head holds the walkers' cursors.  wf_prefix turns
+// them into the tables of the next pass (in_count, in_blkpfx, trav_pfx) and the device copy of the header, and re-zeroes the
+// head [0, zeroed) after every pass; each table has 8 words of slack.
+namespace wfcnt {
+constexpr size_t S = (size_t)kWfShards;
+constexpr size_t out_count = 0, trav_count = 2 * S, trav_head = 3 * S, zeroed = 3 * S + 8;
+constexpr size_t in_count = zeroed, in_blkpfx = in_count + 2 * S, trav_pfx = in_blkpfx + 2 * S + 8, hdr = trav_pfx + S + 8;
+constexpr size_t words = hdr + 8;
+}  // namespace wfcnt
+static const int kHdrRing = 16;        // pinned header slots (wf_prefix -> host), one per pass in flight
+
 static int ctx_init(mi_ctx* c, const hipDeviceProp_t& prop) {
     HIP_TRY(hipStreamCreate(&c->stream));
     HIP_TRY(hipStreamCreateWithFlags(&c->aux_stream, hipStreamNonBlocking));
@@ -165,9 +186,9 @@ static int ctx_init(mi_ctx* c, const hipDeviceProp_t& prop) {
     HIP_TRY(hipEventCreate(&c->ev_t1));
     HIP_TRY(hipMalloc((void**)&c->d_diag, 16 * sizeof(unsigned long long)));
     c->n_cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-    HIP_TRY(hipMalloc((void**)&c->d_wf_cnt, (9 * 256 + 64) * sizeof(uint32_t)));
-    HIP_TRY(hipHostMalloc((void**)&c->h_hdr, 16 * 8 * sizeof(uint32_t), hipHostMallocMapped | hipHostMallocCoherent));     // kHdrRing slots of 8 words
-    memset(c->h_hdr, 0, 16 * 8 * sizeof(uint32_t));
+    HIP_TRY(hipMalloc((void**)&c->d_wf_cnt, wfcnt::words * sizeof(uint32_t)));
+    HIP_TRY(hipHostMalloc((void**)&c->h_hdr, kHdrRing * kHdrSlotWords * sizeof(uint32_t), hipHostMallocMapped | hipHostMallocCoherent));
+    memset(c->h_hdr, 0, kHdrRing * kHdrSlotWords * sizeof(uint32_t));
     HIP_TRY(hipHostGetDevicePointer((void**)&c->h_hdr_dev, c->h_hdr, 0));
     // developer knobs: read here, once (never on the render path)
     mi_ctx::Tuning& t = c->tune;
@@ -236,7 +257,7 @@ extern "C" void mi_ctx_destroy(mi_ctx* c) {
     if (c->d_wf_acc) (void)hipFree(c->d_wf_acc);
     if (c->d_cand) (void)hipFree(c->d_cand);
     if (c->d_cand_hdr) (void)hipFree(c->d_cand_hdr);
-    if (c->d_tile_mask) (void)hipFree(c->d_tile_mask);
+    if (c->masks.d_words) (void)hipFree(c->masks.d_words);
     if (c->d_wf_cnt) (void)hipFree(c->d_wf_cnt);
     if (c->h_hdr) (void)hipHostFree(c->h_hdr);
     for (hipEvent_t e : c->wf_ev) (void)hipEventDestroy(e);
@@ -264,7 +285,7 @@ extern "C" int mi_scene_upload(mi_ctx* c, const mi_scene_desc* d) {
     HIP_TRY(hipSetDevice(c->device));
     if (c->blob) (void)hipFree(c->blob);
     c->blob = nullptr; c->blob_bytes = 0; c->S = DScene{}; c->scene = CompiledScene(); c->have_scene = false;
-    c->mask_valid = false;
+    c->masks.valid = false;
     const size_t total = sc.image.size();
     void* blob = nullptr;
     hipError_t e = hipMalloc(&blob, total);
@@ -279,447 +300,111 @@ extern "C" int mi_scene_upload(mi_ctx* c, const mi_scene_desc* d) {
 }
 
 // ------------------------------------------------------------------ render
-static int check_camera(const mi_camera_desc* cam) {
-    if (!cam) return fail(MI_ERR_INVALID, "camera is NULL");
-    if (cam->projection_mode != MI_PROJ_PERSPECTIVE && cam->projection_mode != MI_PROJ_ORTHOGRAPHIC)
-        return fail(MI_ERR_INVALID, "unknown projection_mode %d", cam->projection_mode);
-    if (cam->shading_mode != MI_SHADE_PATHTRACE && cam->shading_mode != MI_SHADE_PHONG)
-        return fail(MI_ERR_INVALID, "unknown shading_mode %d", cam->shading_mode);
-    if (cam->path_samples == 0) return fail(MI_ERR_INVALID, "path_samples must be >= 1 (tracing.rs:318 divides by it)");
-    if (cam->screen_width == 0 || cam->screen_height == 0 || cam->screen_width > 32768 || cam->screen_height > 32768)
-        return fail(MI_ERR_INVALID, "bad image size %ux%u", cam->screen_width, cam->screen_height);
-    if (cam->aa_sample_count == 0) return fail(MI_ERR_INVALID, "aa_sample_count must be >= 1");
-    if ((uint32_t)sqrtf((float)cam->aa_sample_count) == 0) return fail(MI_ERR_INVALID, "aa_sample_count too small");
-    if (!(cam->gamma > 0.0f) || !std::isfinite(cam->gamma)) return fail(MI_ERR_INVALID, "gamma must be finite and > 0 (tracing.rs:254 raises to 1/gamma)");
-    // A camera that makes every ray non-finite is refused, not rendered.  The reference would render it: its tests then "hit"
-    // with a NaN distance wherever every reject comparison is false (geometry.rs:338-349, 401-410) and Scene keeps the FIRST
-    // such hit in Scene.objects order (tracing.rs:335, NaN < x is false) — a result that depends on the evaluation order
-    // of unordered comparisons, which the kind-grouped object list of the kernels does not keep.
-    for (int k = 0; k < 3; k++)
-        if (!std::isfinite(cam->eyepoint[k]) || !std::isfinite(cam->view_dir[k]) || !std::isfinite(cam->up[k]))
-            return fail(MI_ERR_INVALID, "camera eyepoint / view_dir / up must be finite");
-    if (!std::isfinite(cam->focal_length) || !std::isfinite(cam->focus_dist) || !std::isfinite(cam->lens_radius) || std::isnan(cam->max_trace_dist))
-        return fail(MI_ERR_INVALID, "camera focal_length / focus_dist / lens_radius must be finite, max_trace_dist not NaN");
-    {
-        // tracing.rs:188: rotation.x = view_dir.cross(up).normalize(), in f32 as the kernels evaluate it
-        const float* v = cam->view_dir; const float* u = cam->up;
-        const float cx = v[1] * u[2] - v[2] * u[1], cy = v[2] * u[0] - v[0] * u[2], cz = v[0] * u[1] - v[1] * u[0];
-        const float m2 = (cx * cx + cy * cy) + cz * cz;
-        if (!(m2 > 0.0f) || !std::isfinite(1.0f / sqrtf(m2)))
-            return fail(MI_ERR_INVALID, "view_dir x up is zero or not finite: the camera basis is singular and every ray would be NaN (tracing.rs:188)");
-    }
-    return MI_OK;
-}
-
-// The tile grid of the partition.  Tiles are numbered row-major over a grid whose ROW LENGTH `tx` is the image's tile columns
-// rounded up to the next integer coprime with `world` (tile t -> rank t % world, slot t / world): a row length that shares a factor
-// with the rank count repeats the same few column classes for a rank in every row (60 columns over 8 ranks: two classes, and the
-// ranks whose classes cross the expensive middle of the frame took 7 % longer than the others); a coprime one walks every rank
-// through all classes.  The extra columns hold no pixel: their tiles are rendered as "outside the image" (zeros) and never
-// copied anywhere.  world = 1 (mi_render) keeps the plain grid.
-static void tile_counts(const mi_camera_desc* cam, int world, uint32_t* tx, uint32_t* ty, uint32_t* total, uint32_t* padded) {
-    uint32_t stride = (cam->screen_width + MI_TILE - 1) / MI_TILE;
-    auto gcd = [](uint32_t a, uint32_t b) { while (b) { const uint32_t r = a % b; a = b; b = r; } return a; };
-    while (gcd(stride, (uint32_t)world) != 1u) stride++;
-    *tx = stride;
-    *ty = (cam->screen_height + MI_TILE - 1) / MI_TILE;
-    *total = *tx * *ty;
-    *padded = (*total + (uint32_t)world - 1) / (uint32_t)world;
-}
-
 extern "C" int mi_compact_size(const mi_camera_desc* cam, int32_t world, uint32_t* tiles_total, uint32_t* tiles_padded) {
     if (!cam || world < 1 || !tiles_total || !tiles_padded) return fail(MI_ERR_INVALID, "mi_compact_size: bad argument");
-    uint32_t tx, ty;
-    tile_counts(cam, world, &tx, &ty, tiles_total, tiles_padded);
+    const TileGrid g = tile_grid(cam, world);
+    *tiles_total = g.total; *tiles_padded = g.padded;
     return MI_OK;
-}
-
-static void make_camera(const mi_camera_desc* cam, DCamera* C) {
-    memset(C, 0, sizeof *C);
-    h3 view = H3p(cam->view_dir), up = H3p(cam->up);
-    h3 c0 = normalize(cross(view, up));                                 // tracing.rs:188
-    C->eye[0] = cam->eyepoint[0]; C->eye[1] = cam->eyepoint[1]; C->eye[2] = cam->eyepoint[2];
-    C->rot[0] = c0.x; C->rot[1] = c0.y; C->rot[2] = c0.z;
-    C->rot[3] = up.x; C->rot[4] = up.y; C->rot[5] = up.z;               // :189
-    C->rot[6] = -view.x; C->rot[7] = -view.y; C->rot[8] = -view.z;      // :190
-    C->pixel_size = 1.0f / (float)cam->screen_height;                   // :160
-    C->n = (float)cam->aa_sample_count;                                 // :162
-    C->rootn = sqrtf(C->n);                                             // :163
-    C->half_rootn = 0.5f * C->rootn;
-    C->half_n = 0.5f * C->n;
-    C->cx_base = -(0.5f * (float)cam->screen_width);                    // :178
-    C->cy_base = 0.5f + 0.5f * (float)cam->screen_height;               // :179
-    C->focal_length = cam->focal_length; C->focus_dist = cam->focus_dist; C->lens_radius = cam->lens_radius;
-    C->max_trace_dist = cam->max_trace_dist;
-    C->rootn_u = (uint32_t)C->rootn;                                    // :169 `rootn as u32`
-    C->spp = cam->aa_sample_count;
-    C->zone = (C->spp << __builtin_clz(C->spp)) - 1u;                   // rand 0.8.4 UniformInt::sample_single
-    C->path_depth = cam->path_depth;
-    C->width = cam->screen_width; C->height = cam->screen_height;
-    C->ortho = cam->projection_mode == MI_PROJ_ORTHOGRAPHIC ? 1u : 0u;
-    // :200,204  rotation * view_dir with cgmath's Matrix3 * Vector3 order: (c0*v.x + c1*v.y) + c2*v.z
-    h3 c2 = H3(-view.x, -view.y, -view.z);
-    h3 od = add(add(scale(c0, view.x), scale(up, view.y)), scale(c2, view.z));
-    C->ortho_dir[0] = od.x; C->ortho_dir[1] = od.y; C->ortho_dir[2] = od.z;
 }
 
 // K1w: the wavefront pipeline (pt_kernels.hip).  The host enqueues one iteration per path segment:
 // wf_main, wf_prefix (device-side bookkeeping of the shard counters), wf_trav.  It needs one number back
 // per iteration — the grid of the next wf_main — which arrives on a second stream while wf_trav runs, so
 // the compute stream never waits for the host; the call still returns only when the frame is done.
-//
-// Memory: path state is streamed through HBM — 2 x 96 B (ping/pong) + 16 B sample slot per path
-// (kWfBytesPerPath; the walkers read the class-B lists, there is no traversal queue).  The batch is sized to the free HBM (288 GB on MI355X: the whole 1080p/256 spp
-// frame, 531 M paths = 112 GB, is ONE batch), halved on allocation failure.
-static const int kHdrRing = 16;        // pinned header slots (wf_prefix -> host), one per pass in flight
+// Memory and batch size: render_plan.cpp (wf_first_batch, wf_batch).
 static const int kRunAhead = 3;        // passes the host may launch before it has read the header of an earlier one
-static const size_t kWfBytesPerPath = 2 * (size_t)kWfPlanes * sizeof(float4) + sizeof(float4);      // ping / pong state, sample slot
-static const size_t kWfBytesPerPathTwoStage = (size_t)kCandMax * sizeof(uint2) + sizeof(uint2);     // candidates + header per queue slot
 
-// which meshes this render walks two-stage (bit m = live mesh m)
-static uint32_t two_stage_mask(const mi_ctx* c, uint32_t flags) {
-    if (flags & MI_OPT_REFERENCE_WALK) return 0u;
-    uint32_t m = 0;
-    for (size_t i = 0; i < c->scene.meshes.size() && i < (size_t)kTwoStageMaxMeshes; i++)
-        if (c->scene.meshes[i].qualifies && ((flags & MI_OPT_TWO_STAGE) || c->scene.meshes[i].default_ts)) m |= 1u << i;
-    return m;
-}
-
-static int wf_alloc(mi_ctx* c, WfArgs& a, uint32_t spp, uint64_t max_state_bytes, bool two_stage, uint32_t& s_batch) {
-    uint64_t max_paths;
-    const size_t per_path = kWfBytesPerPath + (two_stage ? kWfBytesPerPathTwoStage : 0);
-    if (max_state_bytes != 0) max_paths = max_state_bytes / per_path;        // the caller's budget (mi_render_opts)
-    else {
-        size_t free_b = 0, total_b = 0;
-        if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) free_b = (size_t)8 << 30;
-        // what this context already holds for the pipeline can be reused
-        free_b += c->wf_a_bytes + c->wf_b_bytes + c->wf_samp_bytes + c->cand_bytes + c->cand_hdr_bytes;
-        max_paths = (uint64_t)((double)free_b * 0.6 / (double)per_path);
-    }
-    if (max_paths > (1ull << 31)) max_paths = 1ull << 31;           // 32-bit path indices
-    uint64_t sb = max_paths / a.npix;
-    // the smallest batch is one sample of every (padded) pixel of this rank: a caller's budget below that cannot be honoured
-    if (sb < 1 && max_state_bytes != 0)
-        return fail(MI_ERR_INVALID, "max_state_bytes = %llu is below the pipeline's minimum for this image: one sample per pixel = %llu bytes",
-                    (unsigned long long)max_state_bytes, (unsigned long long)((uint64_t)a.npix * per_path));
-    if (sb < 1) sb = 1;
-    if (sb > spp) sb = spp;
+// Allocates the buffers of a batch of s_batch samples (a.npix set), halving the batch while an allocation fails.
+static int wf_alloc(mi_ctx* c, WfArgs& a, bool two_stage, uint32_t& s_batch) {
     for (;;) {
-        s_batch = (uint32_t)sb;
-        const uint32_t paths = a.npix * s_batch;
-        const uint32_t max_blocks = (paths + kBlock - 1) / kBlock;
-        // a shard receives at most the paths of its own input blocks: ceil(n_blocks / shards) blocks, where
-        // n_blocks <= max_blocks + 2 * shards (one partial block per (class, shard) range)
-        a.region = ((max_blocks + kWfShards - 1) / kWfShards + 3) * kBlock;
-        a.cap = a.region * (uint32_t)kWfShards;
-        const size_t st_bytes = (size_t)kWfPlanes * sizeof(float4) * a.cap;
-        int rc = ensure(&c->d_wf_a, &c->wf_a_bytes, st_bytes);
-        if (rc == MI_OK) rc = ensure(&c->d_wf_b, &c->wf_b_bytes, st_bytes);
-        if (rc == MI_OK) rc = ensure(&c->d_wf_samp, &c->wf_samp_bytes, (size_t)paths * sizeof(float4));
-        if (rc == MI_OK) rc = ensure(&c->d_wf_acc, &c->wf_acc_bytes, (size_t)a.npix * sizeof(float4));
-        if (rc == MI_OK && two_stage) rc = ensure(&c->d_cand, &c->cand_bytes, (size_t)a.cap * kCandMax * sizeof(uint2));
-        if (rc == MI_OK && two_stage) rc = ensure(&c->d_cand_hdr, &c->cand_hdr_bytes, (size_t)a.cap * sizeof(uint2));
+        const WfBatch b = wf_batch(a.npix, s_batch);
+        a.region = b.region; a.cap = b.cap;
+        int rc = ensure(&c->d_wf_a, &c->wf_a_bytes, b.state_bytes);
+        if (rc == MI_OK) rc = ensure(&c->d_wf_b, &c->wf_b_bytes, b.state_bytes);
+        if (rc == MI_OK) rc = ensure(&c->d_wf_samp, &c->wf_samp_bytes, b.samp_bytes);
+        if (rc == MI_OK) rc = ensure(&c->d_wf_acc, &c->wf_acc_bytes, b.acc_bytes);
+        if (rc == MI_OK && two_stage) rc = ensure(&c->d_cand, &c->cand_bytes, b.cand_bytes);
+        if (rc == MI_OK && two_stage) rc = ensure(&c->d_cand_hdr, &c->cand_hdr_bytes, b.cand_hdr_bytes);
         if (rc == MI_OK) return MI_OK;
-        if (rc != MI_ERR_OOM || sb == 1) return rc;
+        if (rc != MI_ERR_OOM || s_batch == 1) return rc;
         (void)hipGetLastError();
-        sb = (sb + 1) / 2;                                           // back off and retry with half the batch
+        s_batch = (s_batch + 1) / 2;                                 // back off and retry with half the batch
     }
 }
 
-// sizes and allocates (host-side work: must happen BEFORE the timing start event is recorded)
-static int wf_prepare(mi_ctx* c, const mi_camera_desc* cam, uint32_t padded, uint64_t max_state_bytes, bool two_stage, WfArgs& a, uint32_t& s_batch) {
+// Sizes and allocates the pipeline for `padded` tiles of this rank (host-side work: must happen BEFORE the timing start event is
+// recorded).  The free HBM is asked for only when the caller gives no budget; what this context already holds for the pipeline
+// can be reused.
+static int wf_prepare(mi_ctx* c, uint32_t padded, uint32_t spp, uint64_t max_state_bytes, bool two_stage, WfArgs& a, uint32_t& s_batch) {
     memset(&a, 0, sizeof a);
     a.npix = padded * (uint32_t)kTilePixels;
-    const uint32_t spp = cam->aa_sample_count;
-    if (spp > 0xffffu) return fail(MI_ERR_UNSUPPORTED, "wavefront variant: aa_sample_count must be <= 65535");
-    if (cam->path_depth > 0xffffu) return fail(MI_ERR_UNSUPPORTED, "wavefront variant: path_depth must be <= 65535");
-    return wf_alloc(c, a, spp, max_state_bytes, two_stage, s_batch);
+    uint64_t free_bytes = 0;
+    if (max_state_bytes == 0) {
+        size_t free_b = 0, total_b = 0;
+        if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) free_b = (size_t)8 << 30;
+        free_bytes = free_b + c->wf_a_bytes + c->wf_b_bytes + c->wf_samp_bytes + c->cand_bytes + c->cand_hdr_bytes;
+    }
+    const int rc = wf_first_batch(a.npix, spp, max_state_bytes, free_bytes, two_stage, &s_batch);
+    if (rc != MI_OK) return rc;
+    return wf_alloc(c, a, two_stage, s_batch);
 }
 
-// Primary-ray culling for the wavefront pipeline.  For every 32x32 tile: which Triangle / Sphere entries of
-// the kind-grouped list can a camera ray of that tile reach?  A perspective camera with lens_radius 0
-// sends every ray of a tile from the eye through the tile's pixel footprints.  The jitter (tracing.rs:166-173,
-// n = aa_sample_count, r = (u32)sqrt(n)) is (floor(i / r) - sqrt(n)/2) / sqrt(n) + (rand - n/2) / n px in x and
-// ((i % r) - sqrt(n)/2) / sqrt(n) + (rand - n/2) / n in y: from -1 px up to floor((n-1)/r) / sqrt(n) - 1/n px in x,
-// which exceeds +1 px when n is not a square (n = 3: +0.82, 8: +0.94, 31: +1.05, never +1.16 or more), and
-// below +1 px in y.  The 2 px margin below covers all of it: the rays lie inside the pyramid spanned by
-// the four corner directions of the footprint widened by 2 px (>= 5e-4 rad of slack beyond the jitter at any
-// resolution up to 2k rows, against f32 rounding of ~1e-7 in the generated directions).  An object that is
-// entirely on the outer side of one of the pyramid's four planes through the eye cannot be hit; it is
-// dropped from the tile's mask and its test — which would have missed — is not run.  f64 on the host,
-// a further 1e-4 scene-unit slack; any non-finite value or a singular camera basis keeps everything.
-// Planes and ConvexVolumes are never masked.  Returns false when masking does not apply.
-static bool tile_masks(mi_ctx* c, const mi_camera_desc* cam, uint32_t flags, uint32_t stride) {
-    const CompiledScene& sc = c->scene;
-    const int n_ts = sc.n_list_tri + sc.n_list_sphere;
-    const int n_mesh = (int)sc.meshes.size();
-    if ((n_ts == 0 && n_mesh == 0) || n_ts > 64 || n_mesh > 32) return false;
-    // rays must leave the eye itself (no lens) towards the image plane (focus_dist > 0 keeps the direction's sign)
-    if (cam->projection_mode != MI_PROJ_PERSPECTIVE || cam->lens_radius != 0.0f || !(cam->focus_dist > 0.0f) || (flags & MI_OPT_NO_TILE_MASKS)) return false;
-    if (c->mask_valid && c->mask_stride == stride && memcmp(&c->mask_cam, cam, sizeof *cam) == 0) return true;
-    const double W = cam->screen_width, H = cam->screen_height, p = 1.0 / H;
-    const double view[3] = { cam->view_dir[0], cam->view_dir[1], cam->view_dir[2] };
-    const double up[3] = { cam->up[0], cam->up[1], cam->up[2] };
-    double c0[3] = { view[1] * up[2] - view[2] * up[1], view[2] * up[0] - view[0] * up[2], view[0] * up[1] - view[1] * up[0] };
-    const double l0 = sqrt(c0[0] * c0[0] + c0[1] * c0[1] + c0[2] * c0[2]);
-    if (!(l0 > 1e-12) || !std::isfinite(l0)) return false;
-    for (double& v : c0) v /= l0;
-    // det of R = [c0 up -view]: a (near-)singular basis flattens the pyramid
-    const double det = c0[0] * (up[1] * -view[2] - up[2] * -view[1]) - up[0] * (c0[1] * -view[2] - c0[2] * -view[1])
-                     + -view[0] * (c0[1] * up[2] - c0[2] * up[1]);
-    if (!(fabs(det) > 1e-6) || !std::isfinite(det)) return false;
-    auto dir = [&](double px, double py, double* o) {           // R * (camera-space point on the image plane)
-        const double x = p * (px - 0.5 * W + 0.5), y = p * (0.5 + 0.5 * H - py), z = -(double)cam->focal_length;
-        for (int k = 0; k < 3; k++) o[k] = c0[k] * x + up[k] * y + -view[k] * z;
-    };
-    // `stride` >= the image's tile columns: the row length of the tile numbering (tile_counts); the surplus columns hold no pixel
-    const uint32_t tx = stride, tx_image = (cam->screen_width + MI_TILE - 1) / MI_TILE, ty = (cam->screen_height + MI_TILE - 1) / MI_TILE;
-    // [0, tiles): list masks; [tiles, 2*tiles): low 32 bits = mesh mask, bit 63 = DEAD tile (nothing reachable:
-    // every camera ray of the tile leaves the scene at once)
-    const size_t n_tiles = (size_t)tx * ty;
-    c->h_tile_mask.assign(2 * n_tiles, ~0ull);
-    for (size_t t = 0; t < n_tiles; t++) c->h_tile_mask[n_tiles + t] = 0xffffffffull;
-    const double margin_px = 2.0, slack = 1e-4;
-    const double eye[3] = { cam->eyepoint[0], cam->eyepoint[1], cam->eyepoint[2] };
-    // Test shapes.  The geometric argument needs the f32 intersection tests to be WELL CONDITIONED for every
-    // camera ray, or a test could "hit" a triangle it passes far from.  Moller-Trumbore (geometry.rs:434-446)
-    // computes u = (s.h)/a with a = -d.n: the rounding error of u is ~2^-22 |s||h| / |a|, and a test that passes
-    // t <= t_max has |a| >= |n| h_E / t_max (t's numerator s.n = h_E |n| does not depend on d; h_E = distance
-    // of the eye from the triangle's plane).  So with  G = 2^-22 S t_reach / (h_E alt_min)  (S = eye to
-    // farthest vertex, alt_min = smallest altitude, t_reach = max_trace_dist x the column norms of the camera
-    // basis) small enough (below) every accepted ray passes inside the triangle scaled by 1.01 about its
-    // centroid — which is the shape tested against the pyramid.  Triangles that fail the
-    // guard (eye almost in their plane, slivers, huge max_trace_dist) are simply never masked.
-    // Spheres (geometry.rs:395-408): the discriminant's rounding moves the silhouette by ~1e-6 relative;
-    // the radius is padded by 0.1 % plus 1e-5 of the centre distance.
-    struct Shape { bool cullable; double v[3][3]; double r; };
-    std::vector<Shape> shapes((size_t)n_ts);
-    {
-        double colmax = 0.0;
-        { const double lu = sqrt(up[0] * up[0] + up[1] * up[1] + up[2] * up[2]), lv = sqrt(view[0] * view[0] + view[1] * view[1] + view[2] * view[2]);
-          colmax = 1.0 + lu + lv; }                            // |R d| <= (|c0| + |up| + |view|) |d|, |c0| = 1
-        const double t_reach = (double)cam->max_trace_dist * colmax;
-        for (int e = 0; e < n_ts; e++) {
-            const DObject& ob = sc.list[(size_t)e];
-            Shape& sh = shapes[(size_t)e];
-            sh.cullable = false; sh.r = 0.0;
-            if (e < sc.n_list_tri) {
-                double P[3][3], cen[3] = { 0, 0, 0 };
-                for (int vtx = 0; vtx < 3; vtx++) for (int q = 0; q < 3; q++) {
-                    P[vtx][q] = (double)ob.f[q] + (vtx == 1 ? (double)ob.f[3 + q] : vtx == 2 ? (double)ob.f[6 + q] : 0.0);
-                    cen[q] += P[vtx][q] / 3.0;
+// The device copy of the tile masks for `cam` (nullptr: masking does not apply), computed and uploaded when the camera, the
+// grid's row length or the flags differ from the cached ones.
+static int device_tile_masks(mi_ctx* c, const mi_camera_desc* cam, uint32_t flags, uint32_t stride, hipStream_t stream,
+                             const unsigned long long** out) {
+    mi_ctx::MaskCache& m = c->masks;
+    if (!m.valid || m.stride != stride || m.flags != flags || memcmp(&m.cam, cam, sizeof *cam) != 0) {
+        m.valid = false;
+        m.applies = tile_masks(c->scene, *cam, flags, stride, m.words);
+        if (m.applies) {
+            if (c->tune.debug_mask) {
+                const int n_ts = c->scene.n_list_tri + c->scene.n_list_sphere, n_mesh = (int)c->scene.meshes.size();
+                const size_t n_tiles = m.words.size() / 2;
+                size_t bits = 0, mbits = 0, dead = 0;
+                for (size_t t = 0; t < n_tiles; t++) {
+                    bits += (size_t)__builtin_popcountll(m.words[t] & ((n_ts >= 64) ? ~0ull : ((1ull << n_ts) - 1ull)));
+                    mbits += (size_t)__builtin_popcountll(m.words[n_tiles + t] & ((n_mesh >= 32) ? 0xffffffffull : ((1ull << n_mesh) - 1ull)));
+                    dead += (size_t)(m.words[n_tiles + t] >> 63);
                 }
-                const double e1[3] = { P[1][0] - P[0][0], P[1][1] - P[0][1], P[1][2] - P[0][2] };
-                const double e2[3] = { P[2][0] - P[0][0], P[2][1] - P[0][1], P[2][2] - P[0][2] };
-                const double e3[3] = { P[2][0] - P[1][0], P[2][1] - P[1][1], P[2][2] - P[1][2] };
-                const double nn[3] = { e1[1] * e2[2] - e1[2] * e2[1], e1[2] * e2[0] - e1[0] * e2[2], e1[0] * e2[1] - e1[1] * e2[0] };
-                const double area2 = sqrt(nn[0] * nn[0] + nn[1] * nn[1] + nn[2] * nn[2]);
-                auto len = [](const double* w) { return sqrt(w[0] * w[0] + w[1] * w[1] + w[2] * w[2]); };
-                const double emax = std::max(len(e1), std::max(len(e2), len(e3)));
-                double S = 0.0, hE = 0.0;
-                for (int vtx = 0; vtx < 3; vtx++) { const double w[3] = { P[vtx][0] - eye[0], P[vtx][1] - eye[1], P[vtx][2] - eye[2] }; S = std::max(S, len(w)); }
-                for (int q = 0; q < 3; q++) hE += (eye[q] - P[0][q]) * nn[q];
-                hE = fabs(hE) / area2;
-                const double alt_min = area2 / emax;
-                const double G = ldexp(1.0, -22) * S * t_reach / (hE * alt_min);
-                // (u, v) off by G moves the point by <= 2 G emax in the plane; scaling by 1.01 about the centroid moves
-                // every edge out by >= 0.0033 alt_min: G <= 1e-3 alt_min / emax keeps the ray inside the scaled triangle
-                sh.cullable = std::isfinite(G) && area2 > 0.0 && G <= 1e-3 * alt_min / emax;
-                for (int vtx = 0; vtx < 3; vtx++) for (int q = 0; q < 3; q++) sh.v[vtx][q] = cen[q] + (P[vtx][q] - cen[q]) * 1.01;
-            } else {
-                double dist = 0.0;
-                for (int q = 0; q < 3; q++) { sh.v[0][q] = (double)ob.f[q]; dist += (sh.v[0][q] - eye[q]) * (sh.v[0][q] - eye[q]); }
-                sh.r = fabs((double)ob.f[3]) * 1.001 + 1e-5 * sqrt(dist);
-                sh.cullable = std::isfinite(sh.r) && std::isfinite(dist);
+                fprintf(stderr, "[mi_rt] tile masks: %zu tiles, %.2f of %d list entries and %.2f of %d meshes kept per tile, %zu dead tiles\n",
+                        n_tiles, (double)bits / (double)n_tiles, n_ts, (double)mbits / (double)n_tiles, n_mesh, dead);
             }
+            const size_t bytes = m.words.size() * sizeof(uint64_t);
+            const int rc = ensure(&m.d_words, &m.d_bytes, bytes);
+            if (rc != MI_OK) return rc;
+            HIP_TRY(hipMemcpyAsync(m.d_words, m.words.data(), bytes, hipMemcpyHostToDevice, stream));
         }
+        m.cam = *cam; m.stride = stride; m.flags = flags; m.valid = true;
     }
-    for (uint32_t j = 0; j < ty; j++) for (uint32_t i = 0; i < tx; i++) {
-        if (i >= tx_image) {                     // a column beyond the image: nothing to render, whatever the scene holds
-            c->h_tile_mask[(size_t)j * tx + i] = 0ull; c->h_tile_mask[n_tiles + (size_t)j * tx + i] = 1ull << 63;
-            continue;
-        }
-        const double x0 = (double)i * MI_TILE - margin_px, x1 = std::min<double>(W, (i + 1.0) * MI_TILE) - 1.0 + margin_px;
-        const double y0 = (double)j * MI_TILE - margin_px, y1 = std::min<double>(H, (j + 1.0) * MI_TILE) - 1.0 + margin_px;
-        double cs[4][3], ctr[3], n[4][3];
-        dir(x0, y0, cs[0]); dir(x1, y0, cs[1]); dir(x1, y1, cs[2]); dir(x0, y1, cs[3]);
-        dir(0.5 * (x0 + x1), 0.5 * (y0 + y1), ctr);
-        bool ok = true;
-        for (int k = 0; k < 4 && ok; k++) {
-            const double* a = cs[k]; const double* b = cs[(k + 1) & 3];
-            double v[3] = { a[1] * b[2] - a[2] * b[1], a[2] * b[0] - a[0] * b[2], a[0] * b[1] - a[1] * b[0] };
-            const double l = sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]);
-            if (!(l > 0.0) || !std::isfinite(l)) { ok = false; break; }
-            const double sgn = (v[0] * ctr[0] + v[1] * ctr[1] + v[2] * ctr[2]) < 0.0 ? -1.0 : 1.0;      // inward
-            for (int q = 0; q < 3; q++) n[k][q] = sgn * v[q] / l;
-        }
-        if (!ok) continue;
-        unsigned long long mask = ~0ull;
-        for (int e = 0; e < n_ts; e++) {
-            const Shape& sh = shapes[(size_t)e];
-            if (!sh.cullable) continue;
-            bool cull = false;
-            for (int k = 0; k < 4 && !cull; k++) {
-                if (e < sc.n_list_tri) {                    // the three (scaled) vertices all outside plane k
-                    bool all_out = true;
-                    for (int vtx = 0; vtx < 3 && all_out; vtx++) {
-                        double d = 0.0;
-                        for (int q = 0; q < 3; q++) d += (sh.v[vtx][q] - eye[q]) * n[k][q];
-                        all_out = d < -slack;              // false for NaN
-                    }
-                    cull = all_out;
-                } else {
-                    double d = 0.0;
-                    for (int q = 0; q < 3; q++) d += (sh.v[0][q] - eye[q]) * n[k][q];
-                    cull = d < -(sh.r + slack);
-                }
-            }
-            if (cull) mask &= ~(1ull << e);
-        }
-        c->h_tile_mask[(size_t)j * tx + i] = mask;
-        unsigned long long mm = 0xffffffffull;
-        for (int m = 0; m < n_mesh && m < 32; m++) {          // the mesh word has 32 bits: meshes 32, 33, ... are never culled
-            const CompiledScene::Mesh& B = sc.meshes[(size_t)m];
-            if (!B.cullable) continue;
-            bool cull = false;
-            for (int k = 0; k < 4 && !cull; k++) {
-                bool all_out = true;
-                for (int v = 0; v < 8 && all_out; v++) {
-                    double d = 0.0, len = 0.0;
-                    for (int q = 0; q < 3; q++) { const double w = B.corner[v][q] - eye[q]; d += w * n[k][q]; len += fabs(B.corner[v][q]) + fabs(eye[q]); }
-                    all_out = d < -(slack + 1e-5 * len);       // f32 rounding of the object-space ray and slabs
-                }
-                cull = all_out;
-            }
-            if (cull) mm &= ~(1ull << m);
-        }
-        const unsigned long long ts_bits = (n_ts >= 64) ? ~0ull : ((1ull << n_ts) - 1ull);
-        const unsigned long long mesh_bits = (n_mesh >= 32) ? 0xffffffffull : ((1ull << n_mesh) - 1ull);
-        if ((mask & ts_bits) == 0ull && (mm & mesh_bits) == 0ull && sc.n_unmasked == 0 && n_mesh <= 32) mm |= 1ull << 63;
-        c->h_tile_mask[n_tiles + (size_t)j * tx + i] = mm;
-    }
-    c->mask_cam = *cam; c->mask_stride = stride; c->mask_valid = false;              // valid once uploaded
-    if (c->tune.debug_mask) {
-        size_t bits = 0, mbits = 0, dead = 0;
-        for (size_t t = 0; t < n_tiles; t++) {
-            bits += (size_t)__builtin_popcountll(c->h_tile_mask[t] & ((n_ts >= 64) ? ~0ull : ((1ull << n_ts) - 1ull)));
-            mbits += (size_t)__builtin_popcountll(c->h_tile_mask[n_tiles + t] & ((n_mesh >= 32) ? 0xffffffffull : ((1ull << n_mesh) - 1ull)));
-            dead += (size_t)(c->h_tile_mask[n_tiles + t] >> 63);
-        }
-        fprintf(stderr, "[mi_rt] tile masks: %zu tiles, %.2f of %d list entries and %.2f of %d meshes kept per tile, %zu dead tiles\n",
-                n_tiles, (double)bits / (double)n_tiles, n_ts, (double)mbits / (double)n_tiles, n_mesh, dead);
-    }
-    return true;
+    *out = m.applies ? (const unsigned long long*)m.d_words : nullptr;
+    return MI_OK;
 }
 
-// Samples [begin, end) of every pixel, added in order to `accum` (nullptr = the context's own buffer).
-// begin == 0 starts the sums from zero; end == aa_sample_count also writes the per-pixel means.
-struct SampleRange { uint32_t begin, end; float4* accum; };
-
-static int render_tiles_wavefront(mi_ctx* c, const K1Args& k, const mi_camera_desc* cam, WfArgs a, uint32_t s_batch, bool lds, uint32_t flags,
-                                  float* d_compact, uint32_t* d_sig, SampleRange range, hipStream_t stream) {
-    a.S = k.S; a.C = k.C; a.R = k.R; a.seed_key = k.seed_key;
-    const uint32_t spp = cam->aa_sample_count;
-    int rc = MI_OK;
-    (void)rc;
-    // counters: [0..2S) out_count (class A shards, class B shards), [2S..3S) trav_count, [3S] trav_head,
-    // then in_count [2S], in_blkpfx [2S+1], trav_pfx [S+1]
-    const size_t S_ = (size_t)kWfShards;
-    uint32_t* cnt = c->d_wf_cnt;
-    a.out_count = cnt; a.trav_count = cnt + 2 * S_; a.trav_head = cnt + 3 * S_;
-    uint32_t* d_in_count = cnt + 3 * S_ + 8;
-    uint32_t* d_in_pfx = d_in_count + 2 * S_;
-    a.in_count = d_in_count; a.in_blkpfx = d_in_pfx;
-    uint32_t* d_trav_pfx = d_in_pfx + 2 * S_ + 8;
-    a.trav_pfx = d_trav_pfx;
-    uint32_t* d_hdr = d_trav_pfx + S_ + 8;
-    a.hdr = d_hdr;
-    a.samp = (float4*)c->d_wf_samp; a.accum = range.accum ? range.accum : (float4*)c->d_wf_acc;
-    a.out = d_compact; a.sig = d_sig;
-    a.tile_mask = nullptr;
-    if (tile_masks(c, cam, flags, a.R.tiles_x)) {
-        if (!c->mask_valid) {
-            int rcm = ensure(&c->d_tile_mask, &c->tile_mask_bytes, c->h_tile_mask.size() * sizeof(unsigned long long));
-            if (rcm != MI_OK) return rcm;
-            HIP_TRY(hipMemcpyAsync(c->d_tile_mask, c->h_tile_mask.data(), c->h_tile_mask.size() * sizeof(unsigned long long), hipMemcpyHostToDevice, stream));
-            c->mask_valid = true;
-        }
-        a.tile_mask = (const unsigned long long*)c->d_tile_mask;
-    }
-    a.diag = nullptr;           // developer builds (-DPT_WF_STAMPS): phase stamps of wf_main
-    if (c->tune.wf_stamps) { a.diag = c->d_diag; HIP_TRY(hipMemsetAsync(c->d_diag, 0, 16 * sizeof(unsigned long long), stream)); }
-    a.refill_min = c->tune.refill_min;
-    // further shade + intersect rounds inside one wf_main launch: one when meshes park part of every wave's rays for the walker
-    // (cfg2: 1 / 2 / 3 rounds -> 99 / 101 / 103 ms), two in a scene without meshes, where every live lane can go on
-    // (cfg5 at 512 spp: 1 / 2 / 3 / 5 rounds -> 281.6 / 271.8 / 278.4 / 287.7 ms; the cfg1 scene at 1080p: 46.6 / 42.9 / 47.4 / 48.1 ms)
-    a.fuse_max = c->tune.fuse_max ? c->tune.fuse_max : (c->S.n_meshes == 0 ? 2u : 1u);
-    a.fuse_min = c->tune.fuse_min < 1 ? 1 : c->tune.fuse_min;
-    const uint32_t fuse_max_normal = a.fuse_max, fuse_min_normal = a.fuse_min;
-    // Which meshes are walked how: the two-stage meshes (wf_trav_f + wf_replay), the rest through the reference's tree (wf_trav).
-    const uint32_t all_meshes = c->S.n_meshes >= 32 ? 0xffffffffu : ((1u << c->S.n_meshes) - 1u);
-    const uint32_t ts_mask = two_stage_mask(c, flags) & all_meshes;
-    const uint32_t ref_mask = all_meshes & ~ts_mask;
-    const WalkerPlan walker = plan_walker(c->scene, ref_mask, c->tune.trav_lds, c->tune.trav_bpc, c->tune.global_bvh);
-    a.R.lds_nodes = walker.lds_nodes; a.R.lds_tris = walker.lds_tris;
-    a.cand = (uint2*)c->d_cand; a.cand_hdr = (uint2*)c->d_cand_hdr;
-    float4* bufs[2] = { (float4*)c->d_wf_a, (float4*)c->d_wf_b };
-    const uint32_t trav_bpc = walker.blocks_per_cu;
-    const uint32_t trav_blocks = (uint32_t)c->n_cus * trav_bpc;
-    const uint32_t travf_blocks = (uint32_t)c->n_cus * (c->tune.travf_bpc > 0 ? (uint32_t)c->tune.travf_bpc : 6u), replay_blocks = (uint32_t)c->n_cus * 8u;
-    const uint32_t conc_trav_bpc = c->tune.conc_trav_bpc > 0 ? (uint32_t)c->tune.conc_trav_bpc : trav_bpc;
-    const uint32_t conc_travf_bpc = c->tune.conc_travf_bpc > 0 ? (uint32_t)c->tune.conc_travf_bpc : travf_blocks / (uint32_t)c->n_cus;
-
-    // per-kernel timing: one event pair per launch, summed after the frame
-    size_t ev_used = 0;
-    std::vector<int> ev_kind;
-    // one event pair per launch is ~0.4 ms per frame of extra barriers: nothing on a whole frame (109 ms), 3 %
-    // of a 1/8 share, so multi-rank renders skip it unless asked (MI_RT_WF_KERNEL_TIMING=0/1 overrides)
-    bool per_kernel_timing = a.R.world == 1;
-    if (c->tune.kernel_timing >= 0) per_kernel_timing = c->tune.kernel_timing != 0;
-    auto stamp = [&](int kind, hipStream_t on) -> int {      // kind: 0 wf_main, 1 wf_trav, 2 wf_reduce, 3 wf_trav_f, 4 wf_replay, 5 wf_main's class-A part on the second stream; call before AND after the launch
-        if (!per_kernel_timing) return MI_OK;
-        if (ev_used == c->wf_ev.size()) { hipEvent_t e; if (hipEventCreate(&e) != hipSuccess) return MI_ERR_HIP; c->wf_ev.push_back(e); }
-        if (hipEventRecord(c->wf_ev[ev_used++], on) != hipSuccess) return MI_ERR_HIP;
-        ev_kind.push_back(kind);
-        return MI_OK;
-    };
-#define WF_TIMED_ON(kind, on, call) do { if (stamp(kind, on) != MI_OK) return fail(MI_ERR_HIP, "event"); HIP_TRY(call); if (stamp(kind, on) != MI_OK) return fail(MI_ERR_HIP, "event"); } while (0)
-#define WF_TIMED(kind, call) WF_TIMED_ON(kind, stream, call)
-
-    uint64_t counts[8] = { 0, 0, 0, 0, 0, 0, 0, 0 };
-    counts[4] = (uint64_t)a.npix * (range.end - range.begin); counts[5] = a.npix;
-    // samples of dead tiles (nothing reachable from the tile: no ray is generated, no slot written or read) — only without signatures
-    if (a.tile_mask && !d_sig) {
-        uint64_t dead_px = 0;
-        for (uint32_t t = (uint32_t)a.R.rank; t < a.R.tiles_total; t += (uint32_t)a.R.world) {
-            if (!(c->h_tile_mask[(size_t)a.R.tiles_total + t] >> 63)) continue;
-            const uint32_t x0 = (t % a.R.tiles_x) * MI_TILE, y0 = (t / a.R.tiles_x) * MI_TILE;
-            if (x0 >= cam->screen_width || y0 >= cam->screen_height) continue;
-            dead_px += (uint64_t)std::min<uint32_t>(MI_TILE, cam->screen_width - x0) * std::min<uint32_t>(MI_TILE, cam->screen_height - y0);
-        }
-        counts[7] = dead_px * (range.end - range.begin);
-    }
-    const bool have_walkers = ref_mask || ts_mask || c->S.n_meshes > 32;
-    // Headers: wf_prefix stores {blocks, live paths, queue length, seq, class-B paths, class-A blocks} of every pass into a RING of
-    // pinned host slots (slot = seq % kHdrRing), so the host may run a few passes ahead of the device and still read every header.
-    struct PassHdr { uint32_t blocks, live, queue, live_b, blocks_a, segments; };
-    auto header_ready = [&](uint32_t seq) { return ((volatile uint32_t*)c->h_hdr)[(size_t)(seq % kHdrRing) * 8 + 3] == seq; };
-    auto read_header = [&](uint32_t seq) {
+// Headers: wf_prefix stores the header of every pass (pt_device.h kHdr*) into a RING of pinned host slots (slot = seq % kHdrRing),
+// so the host may run a few passes ahead of the device and still read every header.
+struct PassHdr { uint32_t blocks, live, queue, live_b, blocks_a, segments; };
+class HeaderRing {
+public:
+    HeaderRing(const mi_ctx* c, hipStream_t stream) : h_((const volatile uint32_t*)c->h_hdr), stream_(stream), timeout_ms_(c->tune.spin_timeout_ms) {}
+    static size_t slot(uint32_t seq) { return (size_t)(seq % kHdrRing) * kHdrSlotWords; }
+    bool ready(uint32_t seq) const { return h_[slot(seq) + kHdrSeq] == seq; }
+    PassHdr read(uint32_t seq) const {          // (it has arrived)
         __atomic_thread_fence(__ATOMIC_ACQUIRE);
-        const volatile uint32_t* h = (volatile uint32_t*)c->h_hdr + (size_t)(seq % kHdrRing) * 8;
-        PassHdr r = { h[0], h[1], h[2], h[4], h[5], h[6] };
+        const volatile uint32_t* h = h_ + slot(seq);
+        PassHdr r = { h[kHdrBlocks], h[kHdrLive], h[kHdrQueue], h[kHdrLiveB], h[kHdrBlocksA], h[kHdrSegments] };
         return r;
-    };
-    auto wait_header = [&](uint32_t seq) -> int {
+    }
+    int wait(uint32_t seq) const {
         const auto t_wait = std::chrono::steady_clock::now();
-        for (uint32_t spin = 1; !header_ready(seq); spin++) {
+        for (uint32_t spin = 1; !ready(seq); spin++) {
             if ((spin & 63u) == 0) {
-                hipError_t q = hipStreamQuery(stream);
-                if (q == hipSuccess) { if (header_ready(seq)) break; return fail(MI_ERR_HIP, "wavefront pipeline: stream drained without a header"); }
+                hipError_t q = hipStreamQuery(stream_);
+                if (q == hipSuccess) { if (ready(seq)) break; return fail(MI_ERR_HIP, "wavefront pipeline: stream drained without a header"); }
                 if (q != hipErrorNotReady) return fail(MI_ERR_HIP, "wavefront pipeline: %s", hipGetErrorString(q));
                 // a wedged stream neither drains nor errors: bound the wait by wall clock (one pass is milliseconds)
                 const auto waited = std::chrono::duration_cast<std::chrono::milliseconds>(std::chrono::steady_clock::now() - t_wait).count();
-                if (waited > (long long)c->tune.spin_timeout_ms)
+                if (waited > (long long)timeout_ms_)
                     return fail(MI_ERR_HIP, "wavefront pipeline: no header from the device after %lld ms (stream wedged?)", (long long)waited);
             }
             // the header of a small pass is there within tens of microseconds: poll without sleeping at first (a sleep
@@ -733,19 +418,110 @@ static int render_tiles_wavefront(mi_ctx* c, const K1Args& k, const mi_camera_de
             } else std::this_thread::sleep_for(std::chrono::microseconds(20));
         }
         return MI_OK;
-    };
+    }
+private:
+    const volatile uint32_t* h_;
+    hipStream_t stream_;
+    uint32_t timeout_ms_;
+};
+
+// Per-launch timing of the pipeline: one event pair per launch from the context's pool, summed per kind into wf_ms after the
+// frame.  One pair is ~0.4 ms per frame of extra barriers: nothing on a whole frame (109 ms), 3 % of a 1/8 share, so multi-rank
+// renders skip it unless asked (MI_RT_WF_KERNEL_TIMING=0/1 overrides).
+enum LaunchKind { kMain, kTrav, kReduce, kTravF, kReplay, kMainA };      // kTravF: wf_filter_f too; kMainA: wf_main's class-A part on the second stream
+class LaunchTimer {
+public:
+    LaunchTimer(mi_ctx* c, bool on) : c_(c), on_(on) {}
+    template <class Launch> int run(LaunchKind kind, hipStream_t on, Launch launch) {
+        if (stamp(kind, on) != MI_OK) return fail(MI_ERR_HIP, "event");
+        const hipError_t e = launch();
+        if (e != hipSuccess) return fail(MI_ERR_HIP, "%s launch failed: %s", kNames[kind], hipGetErrorString(e));
+        if (stamp(kind, on) != MI_OK) return fail(MI_ERR_HIP, "event");
+        return MI_OK;
+    }
+    // after the frame (the streams have drained): wf_ms = {wf_main, wf_trav, wf_reduce} ms, launches, {wf_trav_f, wf_replay, class A} ms
+    void finish() {
+        for (int k = 0; k < 8; k++) c_->wf_ms[k] = 0.0f;
+        c_->wf_ms[3] = (float)(used_ / 2);
+        for (size_t e = 0; e + 1 < used_; e += 2) {
+            float ms = 0.0f;
+            if (hipEventElapsedTime(&ms, c_->wf_ev[e], c_->wf_ev[e + 1]) == hipSuccess) c_->wf_ms[kinds_[e] < 3 ? kinds_[e] : kinds_[e] + 1] += ms;
+            if (c_->tune.dump_launches) fprintf(stderr, "[mi_rt] launch %zu %s %.4f ms\n", e / 2, kNames[kinds_[e]], ms);
+        }
+    }
+private:
+    static constexpr const char* kNames[6] = { "wf_main", "wf_trav", "wf_reduce", "wf_trav_f", "wf_replay", "wf_main (class A, beside the walkers)" };
+    int stamp(LaunchKind kind, hipStream_t on) {          // before AND after the launch
+        if (!on_) return MI_OK;
+        if (used_ == c_->wf_ev.size()) { hipEvent_t e; if (hipEventCreate(&e) != hipSuccess) return MI_ERR_HIP; c_->wf_ev.push_back(e); }
+        if (hipEventRecord(c_->wf_ev[used_++], on) != hipSuccess) return MI_ERR_HIP;
+        kinds_.push_back(kind);
+        return MI_OK;
+    }
+    mi_ctx* c_;
+    bool on_;
+    size_t used_ = 0;
+    std::vector<int> kinds_;
+};
+
+// Samples [begin, end) of every pixel, added in order to `accum` (nullptr = the context's own buffer).
+// begin == 0 starts the sums from zero; end == aa_sample_count also writes the per-pixel means.
+struct SampleRange { uint32_t begin, end; float4* accum; };
+
+static int render_tiles_wavefront(mi_ctx* c, const K1Args& k, const mi_camera_desc* cam, WfArgs a, uint32_t s_batch, uint32_t flags,
+                                  float* d_compact, uint32_t* d_sig, SampleRange range, hipStream_t stream) {
+    a.S = k.S; a.C = k.C; a.R = k.R; a.seed_key = k.seed_key;
+    const uint32_t spp = cam->aa_sample_count;
+    uint32_t* cnt = c->d_wf_cnt;
+    a.out_count = cnt + wfcnt::out_count; a.trav_count = cnt + wfcnt::trav_count; a.trav_head = cnt + wfcnt::trav_head;
+    a.in_count = cnt + wfcnt::in_count; a.in_blkpfx = cnt + wfcnt::in_blkpfx; a.trav_pfx = cnt + wfcnt::trav_pfx; a.hdr = cnt + wfcnt::hdr;
+    a.samp = (float4*)c->d_wf_samp; a.accum = range.accum ? range.accum : (float4*)c->d_wf_acc;
+    a.out = d_compact; a.sig = d_sig;
+    MI_TRY(device_tile_masks(c, cam, flags, a.R.tiles_x, stream, &a.tile_mask));
+    a.diag = nullptr;           // developer builds (-DPT_WF_STAMPS): phase stamps of wf_main
+    if (c->tune.wf_stamps) { a.diag = c->d_diag; HIP_TRY(hipMemsetAsync(c->d_diag, 0, 16 * sizeof(unsigned long long), stream)); }
+    a.refill_min = c->tune.refill_min;
+    // further shade + intersect rounds inside one wf_main launch: one when meshes park part of every wave's rays for the walker
+    // (cfg2: 1 / 2 / 3 rounds -> 99 / 101 / 103 ms), two in a scene without meshes, where every live lane can go on
+    // (cfg5 at 512 spp: 1 / 2 / 3 / 5 rounds -> 281.6 / 271.8 / 278.4 / 287.7 ms; the cfg1 scene at 1080p: 46.6 / 42.9 / 47.4 / 48.1 ms)
+    a.fuse_max = c->tune.fuse_max ? c->tune.fuse_max : (c->S.n_meshes == 0 ? 2u : 1u);
+    a.fuse_min = c->tune.fuse_min < 1 ? 1 : c->tune.fuse_min;
+    const uint32_t fuse_max_normal = a.fuse_max, fuse_min_normal = a.fuse_min;
+    // Which meshes are walked how: the two-stage meshes (wf_trav_f + wf_replay), the rest through the reference's tree (wf_trav).
+    const uint32_t all_meshes = c->S.n_meshes >= 32 ? 0xffffffffu : ((1u << c->S.n_meshes) - 1u);
+    const uint32_t ts_mask = two_stage_mask(c->scene, flags) & all_meshes;
+    const uint32_t ref_mask = all_meshes & ~ts_mask;
+    const WalkerPlan walker = plan_walker(c->scene, ref_mask, c->tune.trav_lds, c->tune.trav_bpc, c->tune.global_bvh);
+    a.R.lds_nodes = walker.lds_nodes; a.R.lds_tris = walker.lds_tris;
+    a.cand = (uint2*)c->d_cand; a.cand_hdr = (uint2*)c->d_cand_hdr;
+    float4* bufs[2] = { (float4*)c->d_wf_a, (float4*)c->d_wf_b };
+    const uint32_t trav_bpc = walker.blocks_per_cu;
+    const uint32_t trav_blocks = (uint32_t)c->n_cus * trav_bpc;
+    const uint32_t travf_blocks = (uint32_t)c->n_cus * (c->tune.travf_bpc > 0 ? (uint32_t)c->tune.travf_bpc : 6u), replay_blocks = (uint32_t)c->n_cus * 8u;
+    const uint32_t conc_trav_bpc = c->tune.conc_trav_bpc > 0 ? (uint32_t)c->tune.conc_trav_bpc : trav_bpc;
+    const uint32_t conc_travf_bpc = c->tune.conc_travf_bpc > 0 ? (uint32_t)c->tune.conc_travf_bpc : travf_blocks / (uint32_t)c->n_cus;
+
+    // one event pair per launch (LaunchTimer): single-rank renders only, unless asked
+    LaunchTimer timer(c, c->tune.kernel_timing >= 0 ? c->tune.kernel_timing != 0 : a.R.world == 1);
+    const HeaderRing ring(c, stream);
+
+    uint64_t counts[8] = { 0, 0, 0, 0, 0, 0, 0, 0 };
+    counts[4] = (uint64_t)a.npix * (range.end - range.begin); counts[5] = a.npix;
+    // samples of dead tiles (nothing reachable from the tile: no ray is generated, no slot written or read) — only without signatures
+    if (a.tile_mask && !d_sig) counts[7] = dead_pixels(tile_grid(cam, a.R.world), cam, a.R.rank, a.R.world, c->masks.words) * (range.end - range.begin);
+    const bool have_walkers = ref_mask || ts_mask || c->S.n_meshes > 32;
     for (uint32_t s0 = range.begin; s0 < range.end; s0 += s_batch) {
         a.s_base = s0; a.s_count = (s0 + s_batch <= range.end) ? s_batch : (range.end - s0);
         int cur = 0;
         a.iter0 = 1;
         a.n_in = a.npix * a.s_count;
-        HIP_TRY(hipMemsetAsync(cnt, 0, (3 * S_ + 8) * sizeof(uint32_t), stream));   // wf_prefix re-zeroes them after every pass
+        HIP_TRY(hipMemsetAsync(cnt, 0, wfcnt::zeroed * sizeof(uint32_t), stream));   // wf_prefix re-zeroes them after every pass
         const uint32_t seq0 = c->hdr_seq + 1u;          // seq of this batch's pass 0
         uint32_t seen = 0;                              // headers of passes [0, seen) have been read
         PassHdr last = { (a.n_in + kBlock - 1) / kBlock, a.n_in, 0u, 0u, 0u, 0u };      // "header of pass -1": the camera rays
         bool all_dead = false;
         auto consume = [&](bool count_it) {             // read header `seen` (it has arrived)
-            last = read_header(seq0 + seen);
+            last = ring.read(seq0 + seen);
             seen++;
             if (count_it) { counts[0] += 1; counts[1] += last.live - last.live_b; counts[2] += last.live_b; counts[3] += last.queue; }
             counts[6] += last.segments;                 // every launched pass counts: a pass behind the one that ended every path ran no segment
@@ -753,7 +529,7 @@ static int render_tiles_wavefront(mi_ctx* c, const K1Args& k, const mi_camera_de
         };
         uint32_t it = 0;
         for (; it <= cam->path_depth + 1u; it++) {
-            while (seen < it && !all_dead && header_ready(seq0 + seen)) consume(true);
+            while (seen < it && !all_dead && ring.ready(seq0 + seen)) consume(true);
             if (all_dead) break;
             // The grid of pass `it` comes from the header of pass it - 1.  While that pass is still running the host would
             // have to wait for it (the header is on its way while the walkers run, so for a big pass the wait is hidden); a SMALL
@@ -764,7 +540,7 @@ static int render_tiles_wavefront(mi_ctx* c, const K1Args& k, const mi_camera_de
             if (!exact) {
                 const uint64_t bound = (uint64_t)last.live / kBlock + 2u * (uint64_t)kWfShards;
                 if (c->tune.nowait_blocks == 0 || bound > (uint64_t)c->tune.nowait_blocks || it - seen > (uint32_t)kRunAhead) {
-                    while (seen < it && !all_dead) { int rcw = wait_header(seq0 + seen); if (rcw != MI_OK) return rcw; consume(true); }
+                    while (seen < it && !all_dead) { MI_TRY(ring.wait(seq0 + seen)); consume(true); }
                     if (all_dead) break;
                     exact = true;
                 }
@@ -798,20 +574,21 @@ static int render_tiles_wavefront(mi_ctx* c, const K1Args& k, const mi_camera_de
             if (split) {
                 HIP_TRY(hipStreamWaitEvent(c->aux_stream, c->ev_pfx, 0));
                 a.part = 1;
-                WF_TIMED_ON(5, c->aux_stream, launch_wf_main(a, grid_a, d_sig != nullptr, c->scene.gen_volumes, c->scene.mesh_maps, c->aux_stream));     // kind 5: its span includes waiting for CUs
+                MI_TRY(timer.run(kMainA, c->aux_stream, [&] { return launch_wf_main(a, grid_a, d_sig != nullptr, c->scene.gen_volumes, c->scene.mesh_maps, c->aux_stream); }));     // its span includes waiting for CUs
                 HIP_TRY(hipEventRecord(c->ev_part, c->aux_stream));
                 a.part = 2;
-                WF_TIMED(0, launch_wf_main(a, exact ? grid_all - grid_a : grid_all, d_sig != nullptr, c->scene.gen_volumes, c->scene.mesh_maps, stream));
+                MI_TRY(timer.run(kMain, stream, [&] { return launch_wf_main(a, exact ? grid_all - grid_a : grid_all, d_sig != nullptr, c->scene.gen_volumes, c->scene.mesh_maps, stream); }));
                 HIP_TRY(hipStreamWaitEvent(stream, c->ev_part, 0));
             } else {
                 a.part = 0;
-                WF_TIMED(0, launch_wf_main(a, grid_all, d_sig != nullptr, c->scene.gen_volumes, c->scene.mesh_maps, stream));
+                MI_TRY(timer.run(kMain, stream, [&] { return launch_wf_main(a, grid_all, d_sig != nullptr, c->scene.gen_volumes, c->scene.mesh_maps, stream); }));
             }
             // device-side bookkeeping: tables for the next pass and for wf_trav, and the header the host needs (grid of the
             // next pass, anything alive?), which wf_prefix stores straight into pinned host memory: the compute stream never
             // waits for the host
             const uint32_t seq = ++c->hdr_seq;
-            HIP_TRY(launch_wf_prefix(cnt, cnt + 2 * S_, d_in_count, d_in_pfx, d_trav_pfx, d_hdr, c->h_hdr_dev + (size_t)(seq % kHdrRing) * 8, seq, stream));
+            HIP_TRY(launch_wf_prefix(cnt + wfcnt::out_count, cnt + wfcnt::trav_count, cnt + wfcnt::in_count, cnt + wfcnt::in_blkpfx, cnt + wfcnt::trav_pfx,
+                                     cnt + wfcnt::hdr, c->h_hdr_dev + HeaderRing::slot(seq), seq, stream));
             if (have_walkers && c->tune.split != 0) HIP_TRY(hipEventRecord(c->ev_pfx, stream));
             // persistent walkers; they leave at once when the queue is empty.  Successive launches merge their meshes' hits
             // into the hit record (strictly closer wins, ties go to the lower Scene.objects index: order-independent)
@@ -829,45 +606,34 @@ static int render_tiles_wavefront(mi_ctx* c, const K1Args& k, const mi_camera_de
             if (ref_walk) {
                 a.trav_mask = ref_mask;
                 const uint32_t blocks = side_by_side ? (uint32_t)c->n_cus * conc_trav_bpc : trav_blocks;
-                WF_TIMED(1, launch_walker(a, walker, blocks, &c->big_lds_enabled, stream));
+                MI_TRY(timer.run(kTrav, stream, [&] { return launch_walker(a, walker, blocks, &c->big_lds_enabled, stream); }));
             }
             if (ts_mask) {
                 a.trav_mask = ts_mask;
                 // wf_filter_f keeps the class-B paths whose ray enters a two-stage mesh's root box; wf_trav_f and wf_replay work on that list
                 if (side_by_side) {
-                    WF_TIMED_ON(3, c->aux2_stream, launch_wf_filter_f(a, 8u, c->aux2_stream));
-                    WF_TIMED_ON(3, c->aux2_stream, launch_wf_trav_f(a, (uint32_t)c->n_cus * conc_travf_bpc, c->aux2_stream));
+                    MI_TRY(timer.run(kTravF, c->aux2_stream, [&] { return launch_wf_filter_f(a, 8u, c->aux2_stream); }));
+                    MI_TRY(timer.run(kTravF, c->aux2_stream, [&] { return launch_wf_trav_f(a, (uint32_t)c->n_cus * conc_travf_bpc, c->aux2_stream); }));
                     HIP_TRY(hipEventRecord(c->ev_travf, c->aux2_stream));
                     HIP_TRY(hipStreamWaitEvent(stream, c->ev_travf, 0));
                 } else {
-                    WF_TIMED(3, launch_wf_filter_f(a, 8u, stream));
-                    WF_TIMED(3, launch_wf_trav_f(a, travf_blocks, stream));
+                    MI_TRY(timer.run(kTravF, stream, [&] { return launch_wf_filter_f(a, 8u, stream); }));
+                    MI_TRY(timer.run(kTravF, stream, [&] { return launch_wf_trav_f(a, travf_blocks, stream); }));
                 }
-                WF_TIMED(4, launch_wf_replay(a, replay_blocks, stream));
+                MI_TRY(timer.run(kReplay, stream, [&] { return launch_wf_replay(a, replay_blocks, stream); }));
             }
             cur ^= 1;
             a.iter0 = 0;
             if (tail && !have_walkers) { it++; break; }
         }
-        WF_TIMED(2, launch_wf_reduce(a, s0 == 0, s0 + a.s_count >= spp, stream));
+        MI_TRY(timer.run(kReduce, stream, [&] { return launch_wf_reduce(a, s0 == 0, s0 + a.s_count >= spp, stream); }));
         // the headers not read yet (statistics; passes launched behind the one that ended every path are not counted)
         const uint32_t launched = c->hdr_seq + 1u - seq0;
-        while (seen < launched) { int rcw = wait_header(seq0 + seen); if (rcw != MI_OK) return rcw; consume(!all_dead); }
+        while (seen < launched) { MI_TRY(ring.wait(seq0 + seen)); consume(!all_dead); }
     }
-#undef WF_TIMED
-#undef WF_TIMED_ON
     HIP_TRY(hipStreamSynchronize(stream));
     for (int k = 0; k < 8; k++) c->wf_counts[k] = counts[k];
-    for (int k = 0; k < 8; k++) c->wf_ms[k] = 0.0f;
-    c->wf_ms[3] = (float)(ev_used / 2);
-    for (size_t e = 0; e + 1 < ev_used; e += 2) {
-        float ms = 0.0f;
-        if (hipEventElapsedTime(&ms, c->wf_ev[e], c->wf_ev[e + 1]) == hipSuccess) c->wf_ms[ev_kind[e] < 3 ? ev_kind[e] : ev_kind[e] + 1] += ms;
-        if (c->tune.dump_launches) {
-            static const char* const names[6] = { "wf_main", "wf_trav", "wf_reduce", "wf_trav_f", "wf_replay", "wf_main (class A, beside the walkers)" };
-            fprintf(stderr, "[mi_rt] launch %zu %s %.4f ms\n", e / 2, names[ev_kind[e]], ms);
-        }
-    }
+    timer.finish();
     return MI_OK;
 }
 
@@ -891,17 +657,16 @@ static int render_tiles(mi_ctx* c, const mi_camera_desc* cam, const mi_render_op
     K1Args a;
     a.S = c->S;
     if (o->flags & MI_OPT_NO_LIST_TREE) { a.S.top_meshf = -1; a.S.n_list_lin = a.S.n_list_tri; }      // every list Triangle one by one (cross-check)
-    make_camera(cam, &a.C);
+    a.C = make_camera(cam);
     for (int k = 0; k < 3; k++) { a.C.light[k] = c->scene.point_light_pos[k]; a.C.ambient[k] = c->scene.ambient[k]; }
     const bool phong = cam->shading_mode == MI_SHADE_PHONG;      // debug shader: own kernel, `variant` is ignored
     // path_samples != 1 (tracing.rs:310) branches at every hit: the literal, recursive estimator (pt_branch)
     const bool recursive = !phong && (cam->path_samples != 1 || o->variant == MI_VARIANT_RECURSIVE);
     if (recursive && cam->path_depth > 64) return fail(MI_ERR_UNSUPPORTED, "recursive estimator: path_depth must be <= 64");
-    uint32_t tx, ty, total, padded;
-    tile_counts(cam, o->world, &tx, &ty, &total, &padded);
+    const TileGrid g = tile_grid(cam, o->world);
     a.R.seed = o->seed; a.R.rank = o->rank; a.R.world = o->world;
-    a.R.tiles_x = tx; a.R.tiles_y = ty; a.R.tiles_total = total;
-    a.R.my_tiles = (total > (uint32_t)o->rank) ? (total - (uint32_t)o->rank + (uint32_t)o->world - 1) / (uint32_t)o->world : 0;
+    a.R.tiles_x = g.tx; a.R.tiles_y = g.ty; a.R.tiles_total = g.total;
+    a.R.my_tiles = rank_tiles(g, o->rank, o->world);
     bool lds = c->S.n_meshes > 0 && c->scene.lds_bytes <= 64u * 1024u && !c->tune.global_bvh;
     a.R.lds_nodes = lds ? (uint32_t)c->S.n_nodes : 0;
     a.R.lds_tris = lds ? (uint32_t)c->S.n_tris : 0;
@@ -915,15 +680,16 @@ static int render_tiles(mi_ctx* c, const mi_camera_desc* cam, const mi_render_op
     const bool diag = variant == MI_VARIANT_VOTED_DIAG;
     a.R.vote_t = c->tune.vote_t; a.R.vote_a = c->tune.vote_a; a.R.k_steps = c->tune.k_steps;
     a.diag = nullptr;
-    uint32_t n_blocks = padded * (uint32_t)kBlocksPerTile;
+    uint32_t n_blocks = g.padded * (uint32_t)kBlocksPerTile;
     if (diag) {
         a.diag = c->d_diag;
         HIP_TRY(hipMemsetAsync(c->d_diag, 0, 16 * sizeof(unsigned long long), stream));
     }
     WfArgs wa; uint32_t wf_batch = 1;
     if (variant == MI_VARIANT_WAVEFRONT && !phong && !recursive) {
-        int rcp = wf_prepare(c, cam, padded, o->max_state_bytes, two_stage_mask(c, o->flags) != 0u, wa, wf_batch);
-        if (rcp != MI_OK) return rcp;
+        if (cam->aa_sample_count > 0xffffu) return fail(MI_ERR_UNSUPPORTED, "wavefront variant: aa_sample_count must be <= 65535");
+        if (cam->path_depth > 0xffffu) return fail(MI_ERR_UNSUPPORTED, "wavefront variant: path_depth must be <= 65535");
+        MI_TRY(wf_prepare(c, g.padded, cam->aa_sample_count, o->max_state_bytes, two_stage_mask(c->scene, o->flags) != 0u, wa, wf_batch));
     }
     HIP_TRY(hipEventRecord(c->ev_start, stream));
     if (phong)
@@ -931,8 +697,7 @@ static int render_tiles(mi_ctx* c, const mi_camera_desc* cam, const mi_render_op
     else if (recursive)
         HIP_TRY(launch_branch(a, n_blocks, cam->path_samples, a.sig != nullptr, stream));
     else if (variant == MI_VARIANT_WAVEFRONT) {
-        int rcw = render_tiles_wavefront(c, a, cam, wa, wf_batch, lds, o->flags, d_compact, a.sig, range, stream);
-        if (rcw != MI_OK) return rcw;
+        MI_TRY(render_tiles_wavefront(c, a, cam, wa, wf_batch, o->flags, d_compact, a.sig, range, stream));
     } else if (variant == MI_VARIANT_VOTED || variant == MI_VARIANT_VOTED_DIAG)
         HIP_TRY(launch_megakernel_voted(a, n_blocks, lds, a.sig != nullptr, diag, c->scene.gen_volumes, c->scene.lds_bytes + c->tune.lds_pad, stream));
     else
@@ -941,17 +706,9 @@ static int render_tiles(mi_ctx* c, const mi_camera_desc* cam, const mi_render_op
     c->ev_recorded = true;
     if (st) {
         memset(st, 0, sizeof *st);
-        uint64_t pixels = 0;
-        for (uint32_t t = (uint32_t)o->rank; t < total; t += (uint32_t)o->world) {
-            uint32_t x0 = (t % tx) * MI_TILE, y0 = (t / tx) * MI_TILE;
-            if (x0 >= cam->screen_width) continue;               // a column of the numbering beyond the image (tile_counts)
-            uint32_t w = cam->screen_width - x0 < MI_TILE ? cam->screen_width - x0 : MI_TILE;
-            uint32_t h = cam->screen_height - y0 < MI_TILE ? cam->screen_height - y0 : MI_TILE;
-            pixels += (uint64_t)w * h;
-        }
-        st->pixels = pixels;
-        st->samples = pixels * (range.end - range.begin);
-        st->tiles = a.R.my_tiles; st->tiles_padded = padded;
+        st->pixels = rank_pixels(g, cam, o->rank, o->world);
+        st->samples = st->pixels * (range.end - range.begin);
+        st->tiles = a.R.my_tiles; st->tiles_padded = g.padded;
         st->scene_bytes = (uint32_t)c->blob_bytes; st->scene_in_lds = lds ? 1u : 0u;
     }
     return MI_OK;
@@ -977,10 +734,9 @@ extern "C" int mi_unpermute_device(mi_ctx* c, const mi_camera_desc* cam, int32_t
                                    void* d_image_f32, void* stream) {
     if (!c || !cam || world < 1 || !d_gathered_f32 || !d_image_f32) return fail(MI_ERR_INVALID, "mi_unpermute_device: bad argument");
     HIP_TRY(hipSetDevice(c->device));
-    uint32_t tx, ty, total, padded;
-    tile_counts(cam, world, &tx, &ty, &total, &padded);
-    HIP_TRY(launch_unpermute((const float*)d_gathered_f32, (float*)d_image_f32, cam->screen_width, cam->screen_height, tx,
-                             (uint32_t)world, padded, (hipStream_t)stream));
+    const TileGrid g = tile_grid(cam, world);
+    HIP_TRY(launch_unpermute((const float*)d_gathered_f32, (float*)d_image_f32, cam->screen_width, cam->screen_height, g.tx,
+                             (uint32_t)world, g.padded, (hipStream_t)stream));
     return MI_OK;
 }
 
@@ -1007,13 +763,9 @@ extern "C" int mi_reserve(mi_ctx* c, const mi_camera_desc* cam, int32_t world, u
     if (rc != MI_OK) return rc;
     if (world < 1) return fail(MI_ERR_INVALID, "bad world");
     HIP_TRY(hipSetDevice(c->device));
-    uint32_t tx, ty, total, padded;
-    tile_counts(cam, world, &tx, &ty, &total, &padded);
     WfArgs a;
-    memset(&a, 0, sizeof a);
-    a.npix = padded * (uint32_t)kTilePixels;
     uint32_t s_batch = 1;
-    return wf_alloc(c, a, cam->aa_sample_count, max_state_bytes, two_stage_mask(c, 0u) != 0u, s_batch);
+    return wf_prepare(c, tile_grid(cam, world).padded, cam->aa_sample_count, max_state_bytes, two_stage_mask(c->scene, 0u) != 0u, a, s_batch);
 }
 
 extern "C" int mi_last_pipeline_ms(mi_ctx* c, float* out8) {
@@ -1058,15 +810,14 @@ extern "C" int mi_render(mi_ctx* c, const mi_camera_desc* cam, const mi_render_o
     if (rc != MI_OK) return rc;
     HIP_TRY(hipSetDevice(c->device));
     const hipEvent_t t0 = c->ev_t0, t1 = c->ev_t1;      // owned by the context: no early return can leak them
-    uint32_t tx, ty, total, padded;
-    tile_counts(cam, 1, &tx, &ty, &total, &padded);
+    const TileGrid g = tile_grid(cam, 1);
     size_t npix = (size_t)cam->screen_width * cam->screen_height;
-    size_t cbytes = (size_t)padded * kTilePixels * 3 * sizeof(float);
+    size_t cbytes = (size_t)g.padded * kTilePixels * 3 * sizeof(float);
     if ((rc = ensure((void**)&c->d_compact, &c->compact_bytes, cbytes)) != MI_OK) return rc;
     if ((rc = ensure((void**)&c->d_image, &c->image_bytes, npix * 3 * sizeof(float))) != MI_OK) return rc;
     bool want_sig = opts->want_signature && out_sig;
     if (want_sig) {
-        if ((rc = ensure((void**)&c->d_sigc, &c->sigc_bytes, (size_t)padded * kTilePixels * 4)) != MI_OK) return rc;
+        if ((rc = ensure((void**)&c->d_sigc, &c->sigc_bytes, (size_t)g.padded * kTilePixels * 4)) != MI_OK) return rc;
         if ((rc = ensure((void**)&c->d_sigi, &c->sigi_bytes, npix * 4)) != MI_OK) return rc;
     }
     mi_render_opts o = *opts;
@@ -1074,7 +825,7 @@ extern "C" int mi_render(mi_ctx* c, const mi_camera_desc* cam, const mi_render_o
     HIP_TRY(hipEventRecord(t0, c->stream));
     rc = render_tiles(c, cam, &o, c->d_compact, want_sig ? c->d_sigc : nullptr, c->stream, stats);
     if (rc != MI_OK) return rc;
-    HIP_TRY(launch_unpermute(c->d_compact, c->d_image, cam->screen_width, cam->screen_height, tx, 1, padded, c->stream));
+    HIP_TRY(launch_unpermute(c->d_compact, c->d_image, cam->screen_width, cam->screen_height, g.tx, 1, g.padded, c->stream));
     if (out_rgb_f32) HIP_TRY(hipMemcpyAsync(out_rgb_f32, c->d_image, npix * 3 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
     if (out_rgb_u8) {
         if ((rc = ensure((void**)&c->d_u8, &c->u8_bytes, npix * 3)) != MI_OK) return rc;
@@ -1082,7 +833,7 @@ extern "C" int mi_render(mi_ctx* c, const mi_camera_desc* cam, const mi_render_o
         HIP_TRY(hipMemcpyAsync(out_rgb_u8, c->d_u8, npix * 3, hipMemcpyDeviceToHost, c->stream));
     }
     if (want_sig) {
-        HIP_TRY(launch_sig_unpermute(c->d_sigc, c->d_sigi, cam->screen_width, cam->screen_height, tx, 1, padded, c->stream));
+        HIP_TRY(launch_sig_unpermute(c->d_sigc, c->d_sigi, cam->screen_width, cam->screen_height, g.tx, 1, g.padded, c->stream));
         HIP_TRY(hipMemcpyAsync(out_sig, c->d_sigi, npix * 4, hipMemcpyDeviceToHost, c->stream));
     }
     HIP_TRY(hipEventRecord(t1, c->stream));
@@ -1267,9 +1018,8 @@ extern "C" int mi_multi_render(mi_multi* m, const mi_camera_desc* cam, const mi_
     int rc = check_camera(cam);
     if (rc != MI_OK) return rc;
     const int world = (int)m->ctx.size();
-    uint32_t tx, ty, total, padded;
-    tile_counts(cam, world, &tx, &ty, &total, &padded);
-    const size_t slice_f = (size_t)padded * kTilePixels * 3, slice_s = (size_t)padded * kTilePixels;     // elements per rank
+    const TileGrid g = tile_grid(cam, world);
+    const size_t slice_f = (size_t)g.padded * kTilePixels * 3, slice_s = (size_t)g.padded * kTilePixels;     // elements per rank
     const size_t npix = (size_t)cam->screen_width * cam->screen_height;
     const bool want_sig = opts->want_signature && out_sig;
     const auto t_begin = std::chrono::steady_clock::now();
@@ -1337,12 +1087,12 @@ extern "C" int mi_multi_render(mi_multi* m, const mi_camera_desc* cam, const mi_
     }
     // ---- K3 + K4 on device 0, in stream order behind the receives ----
     HIP_TRY(hipSetDevice(m->devices[0]));
-    HIP_TRY(launch_unpermute((const float*)m->d_compact[0], c0->d_image, cam->screen_width, cam->screen_height, tx, (uint32_t)world, padded, c0->stream));
+    HIP_TRY(launch_unpermute((const float*)m->d_compact[0], c0->d_image, cam->screen_width, cam->screen_height, g.tx, (uint32_t)world, g.padded, c0->stream));
     if (out_rgb_f32) HIP_TRY(hipMemcpyAsync(out_rgb_f32, c0->d_image, npix * 3 * sizeof(float), hipMemcpyDeviceToHost, c0->stream));
     HIP_TRY(launch_tonemap(c0->d_image, c0->d_u8, (uint32_t)npix, 1.0f / cam->gamma, c0->stream));
     if (out_rgb_u8) HIP_TRY(hipMemcpyAsync(out_rgb_u8, c0->d_u8, npix * 3, hipMemcpyDeviceToHost, c0->stream));
     if (want_sig) {
-        HIP_TRY(launch_sig_unpermute((const uint32_t*)m->d_sig[0], (uint32_t*)m->d_sig_image, cam->screen_width, cam->screen_height, tx, (uint32_t)world, padded, c0->stream));
+        HIP_TRY(launch_sig_unpermute((const uint32_t*)m->d_sig[0], (uint32_t*)m->d_sig_image, cam->screen_width, cam->screen_height, g.tx, (uint32_t)world, g.padded, c0->stream));
         HIP_TRY(hipMemcpyAsync(out_sig, m->d_sig_image, npix * 4, hipMemcpyDeviceToHost, c0->stream));
     }
     for (int r = world - 1; r >= 0; r--) {          // the peers' sends, then device 0
@@ -1355,7 +1105,7 @@ extern "C" int mi_multi_render(mi_multi* m, const mi_camera_desc* cam, const mi_
             stats->samples += st[(size_t)r].samples; stats->pixels += st[(size_t)r].pixels; stats->tiles += st[(size_t)r].tiles;
             stats->kernel_ms = std::max(stats->kernel_ms, st[(size_t)r].kernel_ms);             // the slowest device's pipeline pass
         }
-        stats->tiles_padded = padded; stats->scene_bytes = st[0].scene_bytes; stats->scene_in_lds = st[0].scene_in_lds;
+        stats->tiles_padded = g.padded; stats->scene_bytes = st[0].scene_bytes; stats->scene_in_lds = st[0].scene_in_lds;
         stats->total_ms = (float)std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - t_begin).count() * 1e-3f;
     }
     return MI_OK;

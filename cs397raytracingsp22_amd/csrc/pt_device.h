@@ -234,6 +234,16 @@ constexpr int kWfPlanes = 6;
 constexpr int kWfShards = 256;
 constexpr int kCandMax = 8;          // two-stage: candidate slots per queued ray (more passing triangles -> reference walk for that mesh)
 constexpr int kTwoStageMaxMeshes = 24;   // mesh index bits in cand_hdr
+// The header of a pass as wf_prefix stores it into the host's pinned ring slot (kHdrSlotWords words; kHdrSeq is written last,
+// behind a system-scope fence, and is what the host polls)
+constexpr int kHdrBlocks = 0;        // blocks of the next pass
+constexpr int kHdrLive = 1;          // live paths
+constexpr int kHdrQueue = 2;         // queue length (the class-B paths: the walkers' work list)
+constexpr int kHdrSeq = 3;           // sequence number of the pass
+constexpr int kHdrLiveB = 4;         // class-B paths (statistics only)
+constexpr int kHdrBlocksA = 5;       // the class-A blocks, which come first
+constexpr int kHdrSegments = 6;      // Scene::intersect_ray evaluations of the pass (statistics only)
+constexpr int kHdrSlotWords = 8;
 constexpr int32_t kIdEnd = (int32_t)0x80000000;   // split pools: "no further node"
 constexpr int kPairStride = 56;                    // wf_trav_i<.., PAIR>: bytes of an interior record in the paired LDS layout (pt_kernels.hip)
 struct WfArgs {

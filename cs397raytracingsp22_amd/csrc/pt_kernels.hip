@@ -1016,7 +1016,7 @@ __device__ __forceinline__ void intersect_list(const DScene& S, f3 o, f3 d, floa
 }
 
 // Same walk for CAMERA rays of one tile: entries whose bit in `mask` is clear cannot be reached by any
-// ray of that tile (host-side conservative frustum test, mi_rt.cpp tile_masks), so skipping them
+// ray of that tile (host-side conservative frustum test, render_plan.cpp tile_masks), so skipping them
 // skips tests that would have missed.  `mask` is wave-uniform (SGPRs); planes and volumes are never
 // masked (a volume draws its random number for the whole ray LINE, geometry.rs:505).
 template <bool GV = true, bool RARE = true>
@@ -3005,11 +3005,11 @@ __global__ __launch_bounds__(256) void wf_prefix(uint32_t* __restrict__ out_coun
         hdr[0] = blocks_a + x1; hdr[1] = x3; hdr[2] = x2; hdr[3] = 0;
         // the host's copy goes straight into pinned host memory (no copy kernel that would queue behind the
         // persistent walkers): data, system-scope fence, then the sequence number the host polls
-        host_hdr[0] = blocks_a + x1; host_hdr[1] = x3; host_hdr[2] = x2; host_hdr[4] = tot_b;     // [4]: class-B paths (statistics only)
-        host_hdr[6] = tot_seg;                                                                     // [6]: Scene::intersect_ray evaluations of this pass (statistics only)
-        host_hdr[5] = blocks_a;                                                                    // [5]: the class-A blocks come first
+        host_hdr[kHdrBlocks] = blocks_a + x1; host_hdr[kHdrLive] = x3; host_hdr[kHdrQueue] = x2; host_hdr[kHdrLiveB] = tot_b;
+        host_hdr[kHdrSegments] = tot_seg;
+        host_hdr[kHdrBlocksA] = blocks_a;
         __threadfence_system();
-        host_hdr[3] = seq;
+        host_hdr[kHdrSeq] = seq;
     }
 }
 

@@ -25,7 +25,7 @@ TILE_PIXELS = TILE * TILE
 
 def tile_grid(width: int, height: int, world: int = 1):
     """(row length, rows, tiles) of the partition's tile numbering.  The row length is the image's tile columns rounded up to the
-    next integer coprime with `world` (mi_rt.cpp tile_counts): a rank then walks through every column class instead of the same
+    next integer coprime with `world` (render_plan.cpp tile_grid): a rank then walks through every column class instead of the same
     few in every row.  The surplus columns hold no pixel."""
     import math
     tx = (width + TILE - 1) // TILE

@@ -1,7 +1,7 @@
 """The signature-free render paths (want_sig=False) — the forms bench.py times — against the CPU oracle.
 
 With signatures off, the wavefront pipeline takes the DEAD-TILE shortcut: a 32x32 tile from which the host's f64 frustum
-argument (mi_rt.cpp tile_masks) proves nothing reachable generates no camera ray, and wf_reduce writes +0.0 for its pixels
+argument (render_plan.cpp tile_masks) proves nothing reachable generates no camera ray, and wf_reduce writes +0.0 for its pixels
 without reading a sample slot.  With signatures on the shortcut is off (the signature folds in the RNG state of every
 sample), so every parity test that renders with want_sig=True leaves the shortcut, and the SIG = false instantiations of
 every kernel, unchecked.  Here each case goes through `check_signature_free`:
@@ -390,7 +390,7 @@ def beyond_one_pixel_scene(offset=1.035):
 
 
 def test_jitter_past_one_pixel(gpu_ctx, orc):
-    """Non-square n reaches further than +1 px (mi_rt.cpp tile_masks); the 2 px margin must keep column 0 alive."""
+    """Non-square n reaches further than +1 px (render_plan.cpp tile_masks); the 2 px margin must keep column 0 alive."""
     sc = beyond_one_pixel_scene()
     counts = check_signature_free(gpu_ctx, orc, sc, seed=41, dead=True)
     r32, _, _, _ = orc.OracleScene(sc.flatten()).render(sc.camera, seed=41, want_u8=False, want_sig=False)

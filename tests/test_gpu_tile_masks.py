@@ -1,4 +1,4 @@
-"""Primary-ray tile masks (mi_rt.cpp tile_masks): the wavefront pipeline skips, for the camera rays of a
+"""Primary-ray tile masks (render_plan.cpp tile_masks): the wavefront pipeline skips, for the camera rays of a
 32x32 tile, the list entries a conservative host-side frustum test proves unreachable.  Skipping must
 never change a path: random scenes of many small objects under random (also skewed, non-unit) camera
 bases, checked bit for bit against the oracle and against the same render with masking switched off."""
@@ -116,7 +116,7 @@ def test_masked_mesh_roots_and_dead_tiles(gpu_ctx, orc, seed, extras):
 @pytest.mark.parametrize("height", [0.0, 1e-6, 1e-4, 1e-2])
 def test_eye_in_the_plane_of_a_large_triangle(gpu_ctx, orc, height):
     """Grazing camera rays make Moller-Trumbore ill-conditioned (u, v of rays nearly in the triangle's plane are
-    rounding noise); such triangles must stay in every tile's mask (mi_rt.cpp tile_masks, guard G)."""
+    rounding noise); such triangles must stay in every tile's mask (render_plan.cpp tile_masks, guard G)."""
     grey = Lambertian(albedo=(0.7, 0.7, 0.7), emission=(0.3, 0.3, 0.3))
     objs = [Triangle(a=(-40.0, 0.0, -60.0), b=(40.0, 0.0, -60.0), c=(0.0, 0.0, 5.0), material=grey),
             Triangle(a=(3.0, 0.0, -20.0), b=(9.0, 0.0, -20.0), c=(6.0, 0.0, -2.0), material=grey),       # off to the side

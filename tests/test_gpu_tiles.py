@@ -44,7 +44,7 @@ def test_virtual_ranks_assemble_bit_identical_image(gpu_ctx):
 
 @pytest.mark.parametrize("width", [192, 250, 224])
 def test_virtual_ranks_where_the_tile_columns_share_a_factor_with_the_world(gpu_ctx, width):
-    """The coprime row length of the tile numbering (mi_rt.cpp tile_counts) changes the partition whenever the image's tile
+    """The coprime row length of the tile numbering (render_plan.cpp tile_grid) changes the partition whenever the image's tile
     columns share a factor with the rank count: 192 px = 6 columns (7 for 2 / 3 / 4 / 8 ranks), 250 px = 8 columns with a
     partial last one (9 for 2 / 4 / 8 ranks, 8 for 3), 224 px = 7 columns (already coprime with all four).  The surplus
     columns hold no pixel; the assembled image is mi_render's bit for bit and dist.compact_index is K3's mapping."""
@@ -156,7 +156,7 @@ def test_wavefront_batching_is_exact(gpu_ctx):
     gpu_ctx.upload(flat)
     ref32, ref8, refsig, _ = gpu_ctx.render(sc.camera, seed=11, want_sig=True)
     npix = pdist.tiles_padded(160, 96, 1) * pdist.TILE_PIXELS
-    bytes_per_path = 2 * 6 * 16 + 16       # mi_rt.cpp kWfBytesPerPath: ping + pong state (6 float4 planes each), sample slot; no queue
+    bytes_per_path = 2 * 6 * 16 + 16       # render_plan.hpp kWfBytesPerPath: ping + pong state (6 float4 planes each), sample slot; no queue
     small = Context(0)
     try:
         small.upload(flat)

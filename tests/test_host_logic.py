@@ -105,7 +105,7 @@ def test_tile_partition_arithmetic():
 
 
 def test_library_partition_equals_the_python_mirror_without_a_gpu():
-    """mi_compact_size (mi_rt.cpp tile_counts, what mi_multi_render and the RCCL slice sizes use) against dist.tile_grid for
+    """mi_compact_size (render_plan.cpp tile_grid, what mi_multi_render and the RCCL slice sizes use) against dist.tile_grid for
     widths whose tile-column count is / is not coprime with the world and whose last column is / is not partial.  No GPU."""
     from cs397raytracingsp22_amd import Camera, compact_size
     for W in (32, 75, 192, 203, 224, 250, 256, 1920, 3840):
