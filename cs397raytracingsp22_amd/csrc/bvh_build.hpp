@@ -44,16 +44,32 @@ namespace build {
 struct V3 { float x, y, z; };
 struct Box { V3 mn, mx; };
 
+// The box faces' min / max.  fminf / fmaxf (like the reference's f32::min / max) may return EITHER zero of {+0, -0}, and
+// compilers choose differently, so the blob's bytes would depend on who compiled this file.  These fix it: the minimum of
+// the two zeros is -0, the maximum +0 (IEEE 754-2019 minimum / maximum); a NaN operand yields the other one, as fminf and
+// f32::min do.  Every other pair gives what fminf / fmaxf give; the slab tests compare values, so no decision depends on it.
+inline float box_min(float a, float b) {
+    if (a != a) return b;
+    if (b != b) return a;
+    if (a == b) return std::signbit(a) ? a : b;
+    return a < b ? a : b;
+}
+inline float box_max(float a, float b) {
+    if (a != a) return b;
+    if (b != b) return a;
+    if (a == b) return std::signbit(a) ? b : a;
+    return a > b ? a : b;
+}
 inline Box tri_box(V3 a, V3 b, V3 c) {                 // IndexedTriangle::bounding_box geometry.rs:367-381
     Box r;
-    r.mn = V3{ fminf(a.x, fminf(b.x, c.x)), fminf(a.y, fminf(b.y, c.y)), fminf(a.z, fminf(b.z, c.z)) };
-    r.mx = V3{ fmaxf(a.x, fmaxf(b.x, c.x)), fmaxf(a.y, fmaxf(b.y, c.y)), fmaxf(a.z, fmaxf(b.z, c.z)) };
+    r.mn = V3{ box_min(a.x, box_min(b.x, c.x)), box_min(a.y, box_min(b.y, c.y)), box_min(a.z, box_min(b.z, c.z)) };
+    r.mx = V3{ box_max(a.x, box_max(b.x, c.x)), box_max(a.y, box_max(b.y, c.y)), box_max(a.z, box_max(b.z, c.z)) };
     return r;
 }
 inline Box surround(const Box& a, const Box& b) {      // AABB::aabb_surrounding geometry.rs:28-41
     Box r;
-    r.mn = V3{ fminf(a.mn.x, b.mn.x), fminf(a.mn.y, b.mn.y), fminf(a.mn.z, b.mn.z) };
-    r.mx = V3{ fmaxf(a.mx.x, b.mx.x), fmaxf(a.mx.y, b.mx.y), fmaxf(a.mx.z, b.mx.z) };
+    r.mn = V3{ box_min(a.mn.x, b.mn.x), box_min(a.mn.y, b.mn.y), box_min(a.mn.z, b.mn.z) };
+    r.mx = V3{ box_max(a.mx.x, b.mx.x), box_max(a.mx.y, b.mx.y), box_max(a.mx.z, b.mx.z) };
     return r;
 }
 inline void put_node(float* n, const Box& b, int w0, int w1) {

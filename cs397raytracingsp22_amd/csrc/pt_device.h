@@ -153,8 +153,9 @@ struct DScene {
     // sample_hemisphere's rotation for the two normals of every list Triangle, hoisted to the host (scene_compile.cpp): 3 float4 per entry,
     // entry 2 i + (frontface ? 0 : 1) of Scene.objects entry i
     const PT_CONST_AS float*     obj_rot;
-    // two-stage traversal (meshes that qualify): F-tree nodes (same 2 x float4 node format; leaf word = (first << 3) | (count - 1)
-    // into ftris), the F-ordered triangles {a.xyz, tri index}{e1.xyz, 0}{e2.xyz, 0}, and the per-mesh constants
+    // two-stage traversal (meshes that qualify): F-tree nodes QUANTISED to 16 bytes (bvh_build.hpp fq_encode: three words of 16-bit box
+    // faces on the mesh's grid DMeshF.qs / qb, then the link: the skip index of an interior node, 0x80000000 | (first << 3) | (count - 1)
+    // into ftris for a leaf), the F-ordered triangles {a.xyz, tri index}{e1.xyz, 0}{e2.xyz, 0}, and the per-mesh constants
     const PT_CONST_AS float*     fnodes;
     const PT_CONST_AS float*     ftris;
     const PT_CONST_AS DMeshF*    meshf;

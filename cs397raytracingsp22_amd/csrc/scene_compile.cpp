@@ -528,6 +528,16 @@ void rotations(Build& b) {
         out[0] = 1.0f - zz2; out[1] = sz2; out[2] = xz2;                       // c0
         out[3] = -sz2; out[4] = (1.0f - xx2) - zz2; out[5] = sx2;            // c1
         out[6] = xz2; out[7] = -sx2; out[8] = 1.0f - xx2;                     // c2
+        // A matrix that IS the identity as values (a normal along +y of any length: the early return above takes only n.y within
+        // ulps_eq of 1, i.e. f32 epsilon or 4 ulp) is stored as one: the reference multiplies by it, which returns `dir` up to the sign
+        // of a zero component (its x * 1 + y * 0 + z * 0 can turn a -0 into +0; the flag keeps -0: DESIGN.md section 2 (vi)).  A NaN (the normal of a zero-area Triangle) is stored as THE quiet NaN:
+        // which NaN an operation on NaNs returns — sign, payload — depends on the operand order the compiler chose, and the blob's
+        // bytes must not depend on who compiled this file.
+        bool ident = true;
+        for (int k = 0; k < 9; k++) ident = ident && out[k] == ((k % 4 == 0) ? 1.0f : 0.0f);
+        if (ident) { for (int k = 0; k < 9; k++) out[k] = 0.0f; out[9] = 1.0f; return; }
+        const uint32_t qnan = 0x7fc00000u;
+        for (int k = 0; k < 9; k++) if (out[k] != out[k]) memcpy(&out[k], &qnan, 4);
     };
     b.obj_rot.assign(b.objs.size() * 24, 0.0f);
     for (size_t i = 0; i < b.objs.size(); i++) if (b.objs[i].kind == OBJ_TRIANGLE || b.objs[i].kind == OBJ_PLANE) {

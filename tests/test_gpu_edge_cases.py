@@ -57,14 +57,23 @@ def test_tiny_images_and_odd_sample_counts(gpu_ctx, orc, variant, w, h, spp, dep
     compare(gpu_ctx, orc, scenes.config2(w, h, spp, depth), variant=variant, seed=w * 131 + h)
 
 
+def tiny_mesh_object(n_tris):
+    xf = cgmath.mul(cgmath.from_translation((0.0, 1.5, 0.0)), cgmath.from_angle_x(35.0), cgmath.from_scale(2.0))
+    return StaticMesh(tiny_mesh(n_tris), Lambertian(albedo=(0.8, 0.3, 0.2), emission=(0.1, 0.1, 0.1)), [None] * 5, xf)
+
+
+def tiny_mesh_scene(n_tris):
+    return Scene(camera(80, 60, 4, 4), scenes.cornell_walls() + [tiny_mesh_object(n_tris)])
+
+
+TINY_MESH_SIZES = [1, 2, 3]
+
+
 @pytest.mark.parametrize("variant", VARIANTS)
-@pytest.mark.parametrize("n_tris", [1, 2, 3])
+@pytest.mark.parametrize("n_tris", TINY_MESH_SIZES)
 def test_mesh_of_one_two_three_triangles(gpu_ctx, orc, variant, n_tris):
     """One triangle: the root IS a leaf and is never box-tested (geometry.rs:95); two: the smallest interior node."""
-    xf = cgmath.mul(cgmath.from_translation((0.0, 1.5, 0.0)), cgmath.from_angle_x(35.0), cgmath.from_scale(2.0))
-    mesh = StaticMesh(tiny_mesh(n_tris), Lambertian(albedo=(0.8, 0.3, 0.2), emission=(0.1, 0.1, 0.1)), [None] * 5, xf)
-    sc = Scene(camera(80, 60, 4, 4), scenes.cornell_walls() + [mesh])
-    compare(gpu_ctx, orc, sc, variant=variant)
+    compare(gpu_ctx, orc, tiny_mesh_scene(n_tris), variant=variant)
 
 
 @pytest.mark.parametrize("variant", VARIANTS)
@@ -292,18 +301,24 @@ def test_sheared_mirrored_non_uniform_mesh_transforms(gpu_ctx, orc, name, flags)
         assert int(np.abs(u8.astype(int) - r8.astype(int)).max()) <= 1
 
 
-@pytest.mark.parametrize("variant", [abi.MI_VARIANT_DEFAULT, abi.MI_VARIANT_VOTED, abi.MI_VARIANT_RECURSIVE])
-def test_textures_of_odd_sizes(gpu_ctx, orc, variant):
-    """Texture::sample (texture.rs:26-32) on 1x1, 1xN, Nx1 and mutually different map sizes (the per-mesh interleaved texel
-    record needs equal sizes; these take the five-fetch path), and on equal non-square sizes (interleaved)."""
+def odd_texture_scenes():
     from cs397raytracingsp22_amd import Texture
     rng = np.random.default_rng(3)
     tex = lambda w, h: Texture(rng.integers(0, 256, (h, w, 3), dtype=np.uint8))
     mesh = scenes.load_asset_mesh("sphere")           # texcoords beyond [0, 1]: clamped, not wrapped
+    out = []
     for maps in ([tex(1, 1), tex(1, 7), tex(5, 1), tex(3, 2), tex(16, 9)], [tex(7, 3)] * 5, [tex(1, 1), None, None, None, None],
                  [tex(4, 4), None, tex(2, 8), None, tex(4, 4)]):
         xf = cgmath.mul(cgmath.from_translation((0.0, 2.0, 0.0)), cgmath.from_scale(1.6))
-        sc = Scene(camera(56, 44, 4, 4), scenes.cornell_walls() + [StaticMesh(mesh, None, maps, xf)])
+        out.append(Scene(camera(56, 44, 4, 4), scenes.cornell_walls() + [StaticMesh(mesh, None, maps, xf)]))
+    return out
+
+
+@pytest.mark.parametrize("variant", [abi.MI_VARIANT_DEFAULT, abi.MI_VARIANT_VOTED, abi.MI_VARIANT_RECURSIVE])
+def test_textures_of_odd_sizes(gpu_ctx, orc, variant):
+    """Texture::sample (texture.rs:26-32) on 1x1, 1xN, Nx1 and mutually different map sizes (the per-mesh interleaved texel
+    record needs equal sizes; these take the five-fetch path), and on equal non-square sizes (interleaved)."""
+    for sc in odd_texture_scenes():
         compare(gpu_ctx, orc, sc, variant=variant, seed=6)
 
 
@@ -318,12 +333,7 @@ def _many_triangles(rng, n, lo=(-2.6, 0.2, -2.6), hi=(2.6, 5.6, 2.6), size=0.35)
     return objs
 
 
-@pytest.mark.parametrize("variant", [abi.MI_VARIANT_DEFAULT, abi.MI_VARIANT_VOTED])
-def test_long_triangle_lists_walk_a_top_level_tree(gpu_ctx, orc, variant):
-    """96 or more small Triangles in Scene.objects: the scene compiler puts them into a top-level tree (the walls — 32 x the median
-    |e1||e2| and more — stay in front and are tested one by one) and the wavefront pipeline's object list walks it with padded boxes,
-    running the reference's own test on the leaves it reaches.  Same paths as the oracle's linear loop, and as the library's own with
-    MI_OPT_NO_LIST_TREE; a glass sphere and a metal one keep the bounce directions off unit length."""
+def long_triangle_list_scene():
     rng = np.random.default_rng(77)
     objs = scenes.cornell_walls() + _many_triangles(rng, 150) + scenes.cornell_spheres()
     # degenerate and awkward members of the tree: a zero-area triangle, a sliver, two identical triangles with different materials
@@ -333,7 +343,16 @@ def test_long_triangle_lists_walk_a_top_level_tree(gpu_ctx, orc, variant):
     objs.append(Triangle(*twin, Lambertian(albedo=(0.9, 0.1, 0.1))))
     objs.append(Triangle(*twin, Lambertian(albedo=(0.1, 0.9, 0.1), emission=(2.0, 2.0, 2.0))))     # never seen: the first entry wins the tie
     objs = [objs[i] for i in rng.permutation(len(objs))]
-    sc = Scene(camera(110, 80, 4, 7), objs)
+    return Scene(camera(110, 80, 4, 7), objs)
+
+
+@pytest.mark.parametrize("variant", [abi.MI_VARIANT_DEFAULT, abi.MI_VARIANT_VOTED])
+def test_long_triangle_lists_walk_a_top_level_tree(gpu_ctx, orc, variant):
+    """96 or more small Triangles in Scene.objects: the scene compiler puts them into a top-level tree (the walls — 32 x the median
+    |e1||e2| and more — stay in front and are tested one by one) and the wavefront pipeline's object list walks it with padded boxes,
+    running the reference's own test on the leaves it reaches.  Same paths as the oracle's linear loop, and as the library's own with
+    MI_OPT_NO_LIST_TREE; a glass sphere and a metal one keep the bounce directions off unit length."""
+    sc = long_triangle_list_scene()
     compare(gpu_ctx, orc, sc, variant=variant)
     if variant == abi.MI_VARIANT_DEFAULT:
         flat = sc.flatten()
@@ -363,10 +382,141 @@ def test_top_level_tree_rays_the_bound_does_not_cover(gpu_ctx, orc):
     compare(gpu_ctx, orc, Scene(cam, objs))
 
 
+ONE_SIZE_LISTS = (96, 95, 300)
+
+
+def one_size_list_scene(n):
+    rng = np.random.default_rng(100 + n)
+    objs = _many_triangles(rng, n, size=0.5) + [Sphere((0.0, 2.5, 0.0), 0.8, Dielectric(1.5))]
+    return Scene(camera(80, 60, 4, 6), objs)
+
+
 def test_long_lists_with_triangles_of_one_size_everywhere(gpu_ctx, orc):
     """No outliers: every triangle goes into the tree (nothing stays in front), lists of exactly the minimum length, and a list one short
     of it (no tree at all)."""
-    for n in (96, 95, 300):
-        rng = np.random.default_rng(100 + n)
-        objs = _many_triangles(rng, n, size=0.5) + [Sphere((0.0, 2.5, 0.0), 0.8, Dielectric(1.5))]
-        compare(gpu_ctx, orc, Scene(camera(80, 60, 4, 6), objs), seed=n)
+    for n in ONE_SIZE_LISTS:
+        compare(gpu_ctx, orc, one_size_list_scene(n), seed=n)
+
+
+# ---- scenes that reach branches of the scene compiler no scene above does (tests/test_scene_compile_host.py, the feature census)
+def non_affine_scene():
+    """A StaticMesh under a projective transform (last row not 0 0 0 1): transform_point divides by w (geometry.rs:304,307).
+    Such a mesh never takes the two-stage traversal and its root box is never culled."""
+    xf = cgmath.mul(cgmath.from_translation((0.0, 1.2, 0.0)), cgmath.from_angle_y(20.0), cgmath.from_scale(1.3))
+    xf = np.array(xf, np.float32)
+    xf[3, :] = (0.03, 0.02, -0.04, 1.0)
+    mesh = StaticMesh(scenes.load_asset_mesh("teapot"), Lambertian(albedo=(0.7, 0.4, 0.3), emission=(0.1, 0.1, 0.1)), [None] * 5, xf)
+    return Scene(camera(72, 54, 4, 5), scenes.cornell_walls() + [mesh])
+
+
+def fq_refused_scene():
+    """A mesh the bound admits but the 16-bit grid of the F-nodes cannot hold: small triangles near the origin and zero-area
+    ones 1e36 away (extent / 65534 > 2^100).  It is walked through the reference's tree; a second, ordinary mesh keeps company."""
+    m = tiny_mesh(3)
+    far = np.array([[1e36, 0.0, 0.0]] * 3 + [[0.0, -1e36, 1e36]] * 3, np.float32)
+    pos = np.concatenate([0.4 * m.positions.reshape(-1, 3), far]).astype(np.float32)
+    nrm = np.concatenate([m.normals.reshape(-1, 3), np.tile(np.array([[0.0, 1.0, 0.0]], np.float32), (6, 1))]).astype(np.float32)
+    uv = np.concatenate([m.texcoords.reshape(-1, 2), np.zeros((6, 2), np.float32)]).astype(np.float32)
+    idx = np.arange(len(pos), dtype=np.uint32)
+    wide = Mesh(pos, nrm, uv, idx, "fan3-and-far-points")
+    xf = cgmath.mul(cgmath.from_translation((0.0, 1.5, 0.0)), cgmath.from_angle_x(35.0), cgmath.from_scale(4.0))
+    grey = Lambertian(albedo=(0.8, 0.3, 0.2), emission=(0.1, 0.1, 0.1))
+    return Scene(camera(72, 54, 4, 4), scenes.cornell_walls() + [tiny_mesh_object(2), StaticMesh(wide, grey, [None] * 5, xf)])
+
+
+def declined_list_tree_scene():
+    """100 Triangles of which 5 are large (32 x the median |e1||e2| and more): with those in front, 95 small ones remain — one
+    short of a top-level tree, so the list stays as it is."""
+    rng = np.random.default_rng(31)
+    objs = _many_triangles(rng, 95, size=0.3)
+    grey = Lambertian(albedo=(0.6, 0.6, 0.6), emission=(0.4, 0.4, 0.4))
+    for k in range(5):
+        objs.insert(7 * k, Triangle((-30.0, -1.0 - k, -30.0), (30.0, -1.0 - k, -30.0), (0.0, -1.0 - k, 40.0), grey))
+    return Scene(camera(64, 48, 4, 4), objs + [Sphere((0.0, 2.5, 0.0), 0.8, Dielectric(1.5))])
+
+
+def placement_scene():
+    """Every class of the compiler's pool placement, more than one mesh in each: small object meshes (reference walk), large
+    qualifying ones (two-stage by default), boundary-only meshes, a mesh that is both an object and a boundary, a shared mesh,
+    and one-triangle meshes in the middle of the pools."""
+    from test_gpu_two_stage import stack_mesh
+    from test_oracle_kat import cube_mesh
+    from cs397raytracingsp22_amd import Camera
+    grey = Lambertian(albedo=(0.6, 0.6, 0.6))
+    at = lambda x, s=1.0: cgmath.mul(cgmath.from_translation((x, 1.5, 0.0)), cgmath.from_scale(s))      # noqa: E731
+    sphere = StaticMesh(scenes.load_asset_mesh("sphere"), grey, [None] * 5, at(-2.0, 0.5))
+    stack = StaticMesh(stack_mesh(), grey, [None] * 5, at(2.0, 0.3))
+    cube = StaticMesh(scenes.load_asset_mesh("cube"), Dielectric(1.5), [None] * 5, at(0.0, 0.4))
+    one = StaticMesh(tiny_mesh(1), grey, [None] * 5, at(1.0, 0.4))
+    teapot = StaticMesh(scenes.load_asset_mesh("teapot"), grey, [None] * 5, at(-1.0, 0.3))
+    fog_cube = StaticMesh(cube_mesh(-0.3, 0.3), grey, [None] * 5, at(0.5))
+    fog_one = StaticMesh(tiny_mesh(1), grey, [None] * 5, at(-0.5))
+    fog = Isotropic(albedo=(0.8, 0.8, 0.8))
+    inner = Scene(Camera(), [StaticMesh(tiny_mesh(2), grey, [None] * 5, at(1.5)), Sphere((1.5, 1.5, 0.0), 0.3, grey), fog_one])
+    objs = [ConvexVolume(fog_cube, fog, 1.0), sphere, one, cube, ConvexVolume(cube, fog, 2.0), stack, teapot, cube,
+            StaticMesh(tiny_mesh(1), grey, [None] * 5, at(1.2, 0.2)), ConvexVolume(inner, fog, 1.5), sphere]
+    return Scene(camera(64, 48, 4, 4), scenes.cornell_walls() + objs)
+
+
+class FlatOnly:
+    """Stands in for a Scene where a descriptor was edited by hand: what `compare` needs of one."""
+
+    def __init__(self, flat, cam):
+        self._flat, self.camera = flat, cam
+
+    def flatten(self):
+        return self._flat
+
+
+def unreferenced_mesh_scene():
+    """placement_scene with two more mi_mesh entries that nothing references (the Python front end never produces one):
+    they must take no room in the tree pools and shift nothing."""
+    sc = placement_scene()
+    flat = sc.flatten()
+    d = flat.desc
+    extra = [d.meshes[i] for i in range(d.n_meshes)]
+    extra.insert(1, d.meshes[0])
+    extra.append(d.meshes[2])
+    shift = lambda i: i + 1 if i >= 1 else i      # noqa: E731
+    meshes = (abi.mi_mesh * len(extra))(*extra)
+    objs = (abi.mi_object * d.n_objects)(*[d.objects[i] for i in range(d.n_objects)])
+    bobjs = (abi.mi_object * max(1, d.n_boundary_objects))(*[d.boundary_objects[i] for i in range(d.n_boundary_objects)])
+    for o in list(objs) + list(bobjs)[:d.n_boundary_objects]:
+        if o.kind == abi.MI_OBJ_MESH:
+            o.index = shift(o.index)
+    vols = (abi.mi_volume * d.n_volumes)(*[d.volumes[i] for i in range(d.n_volumes)])
+    for v in vols:
+        if v.boundary_kind == abi.MI_OBJ_MESH:
+            v.boundary_index = shift(v.boundary_index)
+    flat._edited = (meshes, objs, bobjs, vols)
+    d.meshes, d.n_meshes, d.objects, d.boundary_objects, d.volumes = meshes, len(extra), objs, bobjs, vols
+    return FlatOnly(flat, sc.camera)
+
+
+def absent_albedo_scene():
+    """Interleaved maps without an albedo map (it reads as black, geometry.rs:260): emission and roughness only."""
+    from cs397raytracingsp22_amd import Texture
+    rng = np.random.default_rng(41)
+    tex = lambda: Texture(rng.integers(0, 256, (5, 9, 3), dtype=np.uint8))      # noqa: E731
+    xf = cgmath.mul(cgmath.from_translation((0.0, 2.0, 0.0)), cgmath.from_scale(1.6))
+    mesh = StaticMesh(scenes.load_asset_mesh("sphere"), None, [None, tex(), None, tex(), None], xf)
+    return Scene(camera(56, 44, 4, 4), scenes.cornell_walls() + [mesh])
+
+
+def global_walk_scene():
+    """A large mesh that never takes the two-stage traversal (a projective transform): its 65 023 nodes fit no LDS form, so the
+    walker reads the reference's tree from global memory."""
+    xf = np.array(cgmath.mul(cgmath.from_translation((0.0, 2.0, 0.0)), cgmath.from_scale(1.5)), np.float32)
+    xf[3, :] = (0.02, 0.01, -0.03, 1.0)
+    mesh = StaticMesh(scenes.load_asset_mesh("sphere"), Lambertian(albedo=(0.7, 0.6, 0.2), emission=(0.2, 0.2, 0.2)), [None] * 5, xf)
+    return Scene(camera(72, 54, 4, 4), scenes.cornell_walls() + [mesh])
+
+
+COMPILER_BRANCH_SCENES = {"absent_albedo": absent_albedo_scene, "global_walk": global_walk_scene,
+                          "non_affine": non_affine_scene, "fq_refused": fq_refused_scene, "declined_list_tree": declined_list_tree_scene,
+                          "placement": placement_scene, "unreferenced_mesh": unreferenced_mesh_scene}
+
+
+@pytest.mark.parametrize("name", sorted(COMPILER_BRANCH_SCENES))
+def test_scenes_that_reach_rare_compiler_branches(gpu_ctx, orc, name):
+    compare(gpu_ctx, orc, COMPILER_BRANCH_SCENES[name](), seed=12)

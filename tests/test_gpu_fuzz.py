@@ -87,9 +87,16 @@ def random_scene(seed):
     return Scene(cam, objs)
 
 
-@pytest.mark.parametrize("seed", list(range(32)))
+PARITY_SEEDS = list(range(32))
+
+
+def parity_scene(seed):
+    return random_scene(1000 + seed)
+
+
+@pytest.mark.parametrize("seed", PARITY_SEEDS)
 def test_random_scene_parity(gpu_ctx, orc, seed):
-    sc = random_scene(1000 + seed)
+    sc = parity_scene(seed)
     flat = sc.flatten()
     gpu_ctx.upload(flat)
     r32, r8, rsig, _ = orc.OracleScene(flat).render(sc.camera, seed=seed)

@@ -43,9 +43,13 @@ def test_config1_cornell(gpu_ctx, orc, variant):
     compare(gpu_ctx, orc, scenes.config1(128, 128, 16, 8), variant=variant)
 
 
+def config2_teapot_scene():
+    return scenes.config2(160, 96, 16, 10)
+
+
 @pytest.mark.parametrize("variant", [abi.MI_VARIANT_SIMPLE, abi.MI_VARIANT_VOTED, abi.MI_VARIANT_WAVEFRONT])
 def test_config2_teapot(gpu_ctx, orc, variant):
-    compare(gpu_ctx, orc, scenes.config2(160, 96, 16, 10), variant=variant)
+    compare(gpu_ctx, orc, config2_teapot_scene(), variant=variant)
 
 
 def test_config2_ragged_edges_and_seed(gpu_ctx, orc):

@@ -24,10 +24,14 @@ def three_ways(ctx, sc, seed=1):
     return out
 
 
+def head_scene_320():
+    return scenes.head_scene(320, 320, 16, 10, textures=scenes.load_asset_textures())
+
+
 def test_head_scene_two_stage_equals_reference_walk_and_oracle(gpu_ctx, orc):
     """The reference's own run() scene: the 32512-triangle sphere.obj goes two-stage by default, drone and cube walk the
     reference's trees (the drone's object-space scale voids the bound, the cube is too small to qualify)."""
-    sc = scenes.head_scene(320, 320, 16, 10, textures=scenes.load_asset_textures())
+    sc = head_scene_320()
     out = three_ways(gpu_ctx, sc, seed=2)
     assert out["default"][3]["wf_trav_f_ms"] > 0.0 and out["default"][3]["wf_replay_ms"] > 0.0       # the new kernels ran
     assert out["reference"][3]["wf_trav_f_ms"] == 0.0
@@ -54,9 +58,7 @@ def _sphere_mesh():
     return scenes.load_asset_mesh("sphere")
 
 
-def test_several_meshes_mixed_walks(gpu_ctx, orc):
-    """Three sphere.obj instances (different scales: two qualify, the hugely scaled-down one has |d_obj| so large that the
-    bound never covers it), the teapot and the drone in one scene, metal everywhere so that |d| grows along paths."""
+def several_meshes_scene():
     metal = Metal(albedo=(0.9, 0.9, 0.9), emission=(0.0, 0.0, 0.0), roughness=0.6)
     objs = scenes.cornell_walls()
     objs.append(StaticMesh(_sphere_mesh(), metal, [None] * 5, cgmath.mul(cgmath.from_translation((-1.5, 1.0, 0.0)), cgmath.from_scale(0.9))))
@@ -65,7 +67,13 @@ def test_several_meshes_mixed_walks(gpu_ctx, orc):
     objs.append(StaticMesh(_sphere_mesh(), metal, [None] * 5, cgmath.mul(cgmath.from_translation((0.0, 3.5, -1.0)), cgmath.from_scale(1e-4 * 6000))))
     objs.append(scenes.teapot_mesh())
     objs.append(Sphere((0.0, 0.6, 1.8), 0.5, metal))
-    sc = Scene(scenes.cornell_camera(256, 192, 9, 12), objs)
+    return Scene(scenes.cornell_camera(256, 192, 9, 12), objs)
+
+
+def test_several_meshes_mixed_walks(gpu_ctx, orc):
+    """Three sphere.obj instances (different scales: two qualify, the hugely scaled-down one has |d_obj| so large that the
+    bound never covers it), the teapot and the drone in one scene, metal everywhere so that |d| grows along paths."""
+    sc = several_meshes_scene()
     out = three_ways(gpu_ctx, sc, seed=9)
     win = (96, 64, 48, 32)
     x0, y0, w, h = win
@@ -73,9 +81,7 @@ def test_several_meshes_mixed_walks(gpu_ctx, orc):
     assert np.array_equal(out["default"][1][y0:y0 + h, x0:x0 + w], rsig)
 
 
-def test_candidate_overflow_takes_the_reference_walk(gpu_ctx, orc):
-    """Twelve coincident copies of one triangle plus a fan around a vertex: a ray through them passes more triangles than a
-    queue entry has candidate slots, so that mesh is walked through the reference's tree for that ray — same result."""
+def stack_mesh():
     P, N, T, I = [], [], [], []
     for k in range(12):                                   # coincident stack
         b = len(P)
@@ -90,7 +96,13 @@ def test_candidate_overflow_takes_the_reference_walk(gpu_ctx, orc):
     P = np.array(P, np.float32)
     N = np.tile(np.array([[0.0, 0.0, 1.0]], np.float32), (len(P), 1))
     T = np.zeros((len(P), 2), np.float32)
-    mesh = objload.Mesh(P, N, T, np.array(I, np.uint32), "stack")
+    return objload.Mesh(P, N, T, np.array(I, np.uint32), "stack")
+
+
+def test_candidate_overflow_takes_the_reference_walk(gpu_ctx, orc):
+    """Twelve coincident copies of one triangle plus a fan around a vertex: a ray through them passes more triangles than a
+    queue entry has candidate slots, so that mesh is walked through the reference's tree for that ray — same result."""
+    mesh = stack_mesh()
     cam = Camera(eyepoint=(0.0, 0.0, 4.0), view_dir=(0.0, 0.0, -1.0), up=(0.0, 1.0, 0.0), path_depth=4, path_samples=1,
                  screen_width=96, screen_height=96, focal_length=0.6, focus_dist=5.0, lens_radius=0.0, aa_sample_count=4,
                  max_trace_dist=100.0, gamma=2.0)

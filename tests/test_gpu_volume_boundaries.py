@@ -25,13 +25,24 @@ def room(cam_kw=None):
     return sc
 
 
-@pytest.mark.parametrize("variant", VARIANTS)
-def test_volume_in_a_cube_mesh(gpu_ctx, orc, variant):
+def cube_volume_scene():
     sc = room()
     fog = Isotropic(albedo=(0.9, 0.7, 0.5))
     cube = StaticMesh(cube_mesh(-0.9, 0.9), GREY, [None] * 5, cgmath.from_translation((0.3, 1.4, 0.2)))
     sc.objects += [ConvexVolume(cube, fog, 1.5), Sphere((-1.5, 1.0, 0.5), 0.8, Metal((0.8, 0.8, 0.8), (0, 0, 0), 0.1))]
-    compare(gpu_ctx, orc, sc, variant=variant, seed=5)
+    return sc
+
+
+def glass_cube_scene():
+    sc = room()
+    cube = StaticMesh(cube_mesh(-0.7, 0.7), Dielectric(1.5), [None] * 5, cgmath.from_translation((0.0, 1.2, 0.0)))
+    sc.objects += [cube, ConvexVolume(cube, Isotropic(albedo=(0.9, 0.6, 0.5)), 4.0), cube]
+    return sc
+
+
+@pytest.mark.parametrize("variant", VARIANTS)
+def test_volume_in_a_cube_mesh(gpu_ctx, orc, variant):
+    compare(gpu_ctx, orc, cube_volume_scene(), variant=variant, seed=5)
 
 
 @pytest.mark.parametrize("variant", VARIANTS)
@@ -49,9 +60,7 @@ def test_volume_in_a_nested_scene_of_triangles_and_spheres(gpu_ctx, orc, variant
 def test_glass_cube_around_a_cube_volume_and_the_mesh_also_listed(gpu_ctx, orc):
     """The reference's 'subsurface' construction (tracing.rs:499-516) with a mesh: the SAME StaticMesh is the boundary of the
     medium and, with a Dielectric, an entry of Scene.objects — and it is listed twice (the first entry keeps the ties)."""
-    sc = room()
-    cube = StaticMesh(cube_mesh(-0.7, 0.7), Dielectric(1.5), [None] * 5, cgmath.from_translation((0.0, 1.2, 0.0)))
-    sc.objects += [cube, ConvexVolume(cube, Isotropic(albedo=(0.9, 0.6, 0.5)), 4.0), cube]
+    sc = glass_cube_scene()
     flat = sc.flatten()
     assert flat.desc.n_meshes == 1 and sum(1 for k in range(flat.desc.n_objects) if flat.desc.objects[k].kind == abi.MI_OBJ_MESH) == 2
     for variant in (abi.MI_VARIANT_DEFAULT, abi.MI_VARIANT_VOTED):
