@@ -35,6 +35,8 @@ hipError_t launch_megakernel_voted(const K1Args& args, uint32_t n_blocks, bool l
 hipError_t launch_wf_main(const WfArgs& a, uint32_t n_blocks, bool sig, bool gv, bool tex, hipStream_t stream);
 hipError_t launch_phong(const K1Args& a, uint32_t n_blocks, bool sig, hipStream_t stream);
 hipError_t launch_branch(const K1Args& a, uint32_t n_blocks, uint32_t path_samples, bool sig, hipStream_t stream);
+hipError_t launch_rq_intersect(const RqArgs& a, bool lds, bool gv, bool resolve, size_t lds_bytes, int n_cus, hipStream_t stream);
+hipError_t launch_rq_shade(const RqShadeArgs& a, hipStream_t stream);
 hipError_t launch_walker(const WfArgs& a, const WalkerPlan& p, uint32_t n_blocks, bool* big_lds_enabled, hipStream_t stream);
 hipError_t launch_wf_filter_f(const WfArgs& a, uint32_t blocks_per_shard, hipStream_t stream);
 hipError_t launch_wf_trav_f(const WfArgs& a, uint32_t n_blocks, hipStream_t stream);
@@ -86,6 +88,7 @@ struct mi_ctx {
     hipEvent_t ev_pfx = nullptr, ev_part = nullptr, ev_travf = nullptr;
     hipEvent_t ev_start = nullptr, ev_stop = nullptr;
     bool ev_recorded = false;
+    bool ms_summed = false; float ms_sum = 0.0f;             // the host-pointer ray queries run one kernel per chunk: mi_last_kernel_ms reports their sum
 
     // device scene: the blob, its pools (S), and the compiler's tables for the host side of a render (scene.image is emptied once copied)
     void* blob = nullptr; size_t blob_bytes = 0;
@@ -102,6 +105,7 @@ struct mi_ctx {
     uint32_t* d_sigc = nullptr; size_t sigc_bytes = 0;
     uint32_t* d_sigi = nullptr; size_t sigi_bytes = 0;
     unsigned long long* d_diag = nullptr;    // 16 counters of the diagnostic variant
+    void* d_rq = nullptr; size_t rq_bytes = 0;               // ray queries, host-pointer forms: rays and results of one chunk (its own buffer: never the pipeline's)
     hipEvent_t ev_t0 = nullptr, ev_t1 = nullptr;     // mi_render's whole-call timer
     bool big_lds_enabled = false;                    // wf_trav_i<1024>'s > 64 KB dynamic-LDS opt-in, set on THIS context's device
     // wavefront pipeline buffers
@@ -251,6 +255,7 @@ extern "C" void mi_ctx_destroy(mi_ctx* c) {
     if (c->d_sigc) (void)hipFree(c->d_sigc);
     if (c->d_sigi) (void)hipFree(c->d_sigi);
     if (c->d_diag) (void)hipFree(c->d_diag);
+    if (c->d_rq) (void)hipFree(c->d_rq);
     if (c->d_wf_a) (void)hipFree(c->d_wf_a);
     if (c->d_wf_b) (void)hipFree(c->d_wf_b);
     if (c->d_wf_samp) (void)hipFree(c->d_wf_samp);
@@ -703,7 +708,7 @@ static int render_tiles(mi_ctx* c, const mi_camera_desc* cam, const mi_render_op
     else
         HIP_TRY(launch_megakernel(a, n_blocks, lds, a.sig != nullptr, c->scene.lds_bytes, stream));
     HIP_TRY(hipEventRecord(c->ev_stop, stream));
-    c->ev_recorded = true;
+    c->ev_recorded = true; c->ms_summed = false;
     if (st) {
         memset(st, 0, sizeof *st);
         st->pixels = rank_pixels(g, cam, o->rank, o->world);
@@ -751,9 +756,155 @@ extern "C" int mi_tonemap_device(mi_ctx* c, const mi_camera_desc* cam, const voi
 extern "C" int mi_last_kernel_ms(mi_ctx* c, float* ms) {
     if (!c || !ms) return fail(MI_ERR_INVALID, "mi_last_kernel_ms: bad argument");
     if (!c->ev_recorded) return fail(MI_ERR_INVALID, "no kernel has been launched on this context");
+    if (c->ms_summed) { *ms = c->ms_sum; return MI_OK; }
     HIP_TRY(hipSetDevice(c->device));
     HIP_TRY(hipEventSynchronize(c->ev_stop));
     HIP_TRY(hipEventElapsedTime(ms, c->ev_start, c->ev_stop));
+    return MI_OK;
+}
+
+// ------------------------------------------------------------------ ray queries (caller-supplied rays)
+// Scene::intersect_ray / Scene::shade_ray for rays the caller made.  The device forms queue ONE kernel on `stream` between the context's
+// timing events and return; they own no device memory.  The host forms move one chunk of rays at a time through a buffer of their own
+// (never the wavefront pipeline's reserved ones) and advance first_key per chunk — the same answers as one call, by the keying.
+static const uint32_t kRqChunk = 1u << 18;      // rays per chunk of the host-pointer forms: 27 MB of device scratch for a full intersect query
+
+static int intersect_rays_device(mi_ctx* c, uint32_t n_rays, const float* origins, const float* dirs, float t_min, float t_max,
+                                 uint32_t seed, uint32_t first_key, int32_t* out_object, float* out_distance, float* out_hitpoint,
+                                 float* out_normal, int32_t* out_flags, float* out_uv, mi_material* out_material, hipStream_t stream) {
+    RqArgs a;
+    a.S = c->S;
+    const bool lds = c->S.n_meshes > 0 && c->scene.lds_bytes <= 64u * 1024u && !c->tune.global_bvh;
+    a.lds_nodes = lds ? (uint32_t)c->S.n_nodes : 0u;
+    a.lds_tris = lds ? (uint32_t)c->S.n_tris : 0u;
+    a.seed_key = lowbias32(seed ^ 0x68e31da4u);
+    a.first_key = first_key; a.n_rays = n_rays; a.t_min = t_min; a.t_max = t_max;
+    a.origins = origins; a.dirs = dirs;
+    a.out_object = out_object; a.out_distance = out_distance; a.out_hitpoint = out_hitpoint; a.out_normal = out_normal;
+    a.out_flags = out_flags; a.out_uv = out_uv; a.out_material = (uint32_t*)out_material;
+    const bool resolve = out_hitpoint || out_normal || out_flags || out_uv || out_material;     // else the visibility form
+    HIP_TRY(hipEventRecord(c->ev_start, stream));
+    HIP_TRY(launch_rq_intersect(a, lds, c->scene.gen_volumes, resolve, c->scene.lds_bytes, c->n_cus, stream));
+    HIP_TRY(hipEventRecord(c->ev_stop, stream));
+    c->ev_recorded = true; c->ms_summed = false;
+    return MI_OK;
+}
+
+static int check_intersect_args(mi_ctx* c, uint32_t n_rays, const float* origins, const float* dirs, float t_min, float t_max,
+                                const int32_t* out_object) {
+    if (!c) return fail(MI_ERR_INVALID, "ctx is NULL");
+    if (!origins || !dirs || !out_object) return fail(MI_ERR_INVALID, "mi_intersect_rays: origins, dirs and out_object are required");
+    if (t_min != t_min || t_max != t_max) return fail(MI_ERR_INVALID, "mi_intersect_rays: t_min / t_max is NaN");
+    if (!c->have_scene) return fail(MI_ERR_NO_SCENE, "no scene uploaded");
+    (void)n_rays;
+    return MI_OK;
+}
+
+extern "C" int mi_intersect_rays_device(mi_ctx* c, uint32_t n_rays, const float* origins, const float* dirs, float t_min, float t_max,
+                                        uint32_t seed, uint32_t first_key, int32_t* out_object, float* out_distance,
+                                        float* out_hitpoint, float* out_normal, int32_t* out_flags, float* out_uv,
+                                        mi_material* out_material, void* stream) {
+    MI_TRY(check_intersect_args(c, n_rays, origins, dirs, t_min, t_max, out_object));
+    if (n_rays == 0) return MI_OK;
+    HIP_TRY(hipSetDevice(c->device));
+    return intersect_rays_device(c, n_rays, origins, dirs, t_min, t_max, seed, first_key, out_object, out_distance, out_hitpoint,
+                                 out_normal, out_flags, out_uv, out_material, (hipStream_t)stream);
+}
+
+extern "C" int mi_intersect_rays(mi_ctx* c, uint32_t n_rays, const float* origins, const float* dirs, float t_min, float t_max,
+                                 uint32_t seed, uint32_t first_key, int32_t* out_object, float* out_distance, float* out_hitpoint,
+                                 float* out_normal, int32_t* out_flags, float* out_uv, mi_material* out_material) {
+    MI_TRY(check_intersect_args(c, n_rays, origins, dirs, t_min, t_max, out_object));
+    if (n_rays == 0) return MI_OK;
+    HIP_TRY(hipSetDevice(c->device));
+    const size_t chunk = std::min<size_t>(n_rays, kRqChunk);
+    // one buffer, carved in 16-byte-friendly order: origins, dirs, hitpoint, normal (12 B each), material (40 B), uv (8 B), object, distance, flags
+    const size_t off_o = 0, off_d = off_o + chunk * 12, off_hp = off_d + chunk * 12, off_n = off_hp + chunk * 12, off_m = off_n + chunk * 12,
+                 off_uv = off_m + chunk * sizeof(mi_material), off_obj = off_uv + chunk * 8, off_t = off_obj + chunk * 4, off_f = off_t + chunk * 4,
+                 total = off_f + chunk * 4;
+    MI_TRY(ensure(&c->d_rq, &c->rq_bytes, total));
+    char* base = (char*)c->d_rq;
+    float ms_sum = 0.0f;
+    for (size_t first = 0; first < n_rays; first += chunk) {
+        const size_t n = std::min<size_t>(chunk, (size_t)n_rays - first);
+        HIP_TRY(hipMemcpyAsync(base + off_o, origins + 3 * first, n * 12, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipMemcpyAsync(base + off_d, dirs + 3 * first, n * 12, hipMemcpyHostToDevice, c->stream));
+        MI_TRY(intersect_rays_device(c, (uint32_t)n, (const float*)(base + off_o), (const float*)(base + off_d), t_min, t_max, seed,
+                                     first_key + (uint32_t)first, (int32_t*)(base + off_obj), out_distance ? (float*)(base + off_t) : nullptr,
+                                     out_hitpoint ? (float*)(base + off_hp) : nullptr, out_normal ? (float*)(base + off_n) : nullptr,
+                                     out_flags ? (int32_t*)(base + off_f) : nullptr, out_uv ? (float*)(base + off_uv) : nullptr,
+                                     out_material ? (mi_material*)(base + off_m) : nullptr, c->stream));
+        HIP_TRY(hipMemcpyAsync(out_object + first, base + off_obj, n * 4, hipMemcpyDeviceToHost, c->stream));
+        if (out_distance) HIP_TRY(hipMemcpyAsync(out_distance + first, base + off_t, n * 4, hipMemcpyDeviceToHost, c->stream));
+        if (out_hitpoint) HIP_TRY(hipMemcpyAsync(out_hitpoint + 3 * first, base + off_hp, n * 12, hipMemcpyDeviceToHost, c->stream));
+        if (out_normal) HIP_TRY(hipMemcpyAsync(out_normal + 3 * first, base + off_n, n * 12, hipMemcpyDeviceToHost, c->stream));
+        if (out_flags) HIP_TRY(hipMemcpyAsync(out_flags + first, base + off_f, n * 4, hipMemcpyDeviceToHost, c->stream));
+        if (out_uv) HIP_TRY(hipMemcpyAsync(out_uv + 2 * first, base + off_uv, n * 8, hipMemcpyDeviceToHost, c->stream));
+        if (out_material) HIP_TRY(hipMemcpyAsync(out_material + first, base + off_m, n * sizeof(mi_material), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));          // the next chunk reuses the buffer
+        float ms = 0.0f;
+        HIP_TRY(hipEventElapsedTime(&ms, c->ev_start, c->ev_stop));
+        ms_sum += ms;
+    }
+    c->ms_summed = true; c->ms_sum = ms_sum;
+    return MI_OK;
+}
+
+static int shade_rays_device(mi_ctx* c, const mi_camera_desc* cam, uint32_t n_rays, const float* origins, const float* dirs,
+                             uint32_t seed, uint32_t first_key, float* out_rgb, hipStream_t stream) {
+    RqShadeArgs a;
+    a.S = c->S;
+    a.seed_key = lowbias32(seed ^ 0x68e31da4u);
+    a.first_key = first_key; a.n_rays = n_rays;
+    a.path_depth = cam->path_depth; a.path_samples = cam->path_samples; a.max_trace_dist = cam->max_trace_dist;
+    a.origins = origins; a.dirs = dirs; a.out_rgb = out_rgb;
+    HIP_TRY(hipEventRecord(c->ev_start, stream));
+    HIP_TRY(launch_rq_shade(a, stream));
+    HIP_TRY(hipEventRecord(c->ev_stop, stream));
+    c->ev_recorded = true; c->ms_summed = false;
+    return MI_OK;
+}
+
+static int check_shade_args(mi_ctx* c, const mi_camera_desc* cam, const float* origins, const float* dirs, const float* out_rgb) {
+    if (!c) return fail(MI_ERR_INVALID, "ctx is NULL");
+    if (!cam || !origins || !dirs || !out_rgb) return fail(MI_ERR_INVALID, "mi_shade_rays: cam, origins, dirs and out_rgb are required");
+    if (cam->shading_mode == MI_SHADE_PHONG) return fail(MI_ERR_UNSUPPORTED, "mi_shade_rays: ShadingMode::Phong is not available for caller-supplied rays");
+    if (cam->shading_mode != MI_SHADE_PATHTRACE) return fail(MI_ERR_INVALID, "mi_shade_rays: unknown shading_mode %d", cam->shading_mode);
+    if (cam->path_depth > 64) return fail(MI_ERR_UNSUPPORTED, "recursive estimator: path_depth must be <= 64");
+    if (!c->have_scene) return fail(MI_ERR_NO_SCENE, "no scene uploaded");
+    return MI_OK;
+}
+
+extern "C" int mi_shade_rays_device(mi_ctx* c, const mi_camera_desc* cam, uint32_t n_rays, const float* origins, const float* dirs,
+                                    uint32_t seed, uint32_t first_key, float* out_rgb, void* stream) {
+    MI_TRY(check_shade_args(c, cam, origins, dirs, out_rgb));
+    if (n_rays == 0) return MI_OK;
+    HIP_TRY(hipSetDevice(c->device));
+    return shade_rays_device(c, cam, n_rays, origins, dirs, seed, first_key, out_rgb, (hipStream_t)stream);
+}
+
+extern "C" int mi_shade_rays(mi_ctx* c, const mi_camera_desc* cam, uint32_t n_rays, const float* origins, const float* dirs,
+                             uint32_t seed, uint32_t first_key, float* out_rgb) {
+    MI_TRY(check_shade_args(c, cam, origins, dirs, out_rgb));
+    if (n_rays == 0) return MI_OK;
+    HIP_TRY(hipSetDevice(c->device));
+    const size_t chunk = std::min<size_t>(n_rays, kRqChunk);
+    MI_TRY(ensure(&c->d_rq, &c->rq_bytes, chunk * 36));
+    char* base = (char*)c->d_rq;
+    float ms_sum = 0.0f;
+    for (size_t first = 0; first < n_rays; first += chunk) {
+        const size_t n = std::min<size_t>(chunk, (size_t)n_rays - first);
+        HIP_TRY(hipMemcpyAsync(base, origins + 3 * first, n * 12, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipMemcpyAsync(base + chunk * 12, dirs + 3 * first, n * 12, hipMemcpyHostToDevice, c->stream));
+        MI_TRY(shade_rays_device(c, cam, (uint32_t)n, (const float*)base, (const float*)(base + chunk * 12), seed, first_key + (uint32_t)first,
+                                 (float*)(base + chunk * 24), c->stream));
+        HIP_TRY(hipMemcpyAsync(out_rgb + 3 * first, base + chunk * 24, n * 12, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        float ms = 0.0f;
+        HIP_TRY(hipEventElapsedTime(&ms, c->ev_start, c->ev_stop));
+        ms_sum += ms;
+    }
+    c->ms_summed = true; c->ms_sum = ms_sum;
     return MI_OK;
 }
 

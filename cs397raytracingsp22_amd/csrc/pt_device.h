@@ -223,6 +223,35 @@ struct K1Args {
     unsigned long long* diag;   // 16 counters (diagnostic build only) or nullptr
 };
 
+// ---- ray queries (pt_kernels.hip rq_intersect / rq_shade): caller-supplied rays, one lane per ray ----
+// Ray i of the batch draws from the stream (seed, first_key + i, 0).  Every out_* of RqArgs except out_object may be nullptr.
+struct RqArgs {
+    DScene  S;
+    uint32_t lds_nodes, lds_tris;    // as DRender: BVH nodes / triangles staged into LDS (0 = read from global memory)
+    uint32_t seed_key;               // lowbias32(seed ^ 0x68e31da4)
+    uint32_t first_key;
+    uint32_t n_rays;
+    float    t_min, t_max;
+    const float* origins;            // [n][3]
+    const float* dirs;               // [n][3], used as given (not normalised)
+    int32_t*  out_object;            // [n] index into Scene.objects, -1 = no hit
+    float*    out_distance;          // [n]
+    float*    out_hitpoint;          // [n][3]
+    float*    out_normal;            // [n][3]
+    int32_t*  out_flags;             // [n] bit 0 frontface, bit 1 has_tex_coords
+    float*    out_uv;                // [n][2]
+    uint32_t* out_material;          // [n][10] words of mi_material
+};
+struct RqShadeArgs {
+    DScene  S;
+    uint32_t seed_key, first_key, n_rays;
+    uint32_t path_depth, path_samples;
+    float    max_trace_dist;
+    const float* origins;
+    const float* dirs;
+    float*   out_rgb;                // [n][3]
+};
+
 // ---- wavefront pipeline (pt_kernels.hip "K1w") ----
 // Path state streamed through HBM as 6 float4 planes [6][cap] (coalesced 16-byte accesses):
 //   q0 o.xyz d.x | q1 d.yz T.xy | q2 T.z L.xyz | q3 rng.s0 rng.s1 pix sample|depth<<16

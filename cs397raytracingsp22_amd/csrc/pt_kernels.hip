@@ -1370,6 +1370,62 @@ struct BranchFrame {
     uint32_t i;         // samples done at this level
 };
 
+// Scene::shade_ray(ray, 0) (tracing.rs:300-324) for ONE ray whose random stream is `rng`: the per-sample body of pt_branch, shared with
+// rq_shade (caller-supplied rays).  F: the lane's frame stack, kMaxRecursion entries.
+template <bool SIG, class BVH>
+__device__ __forceinline__ f3 shade_ray_recursive(const DScene& S, const BVH& B, f3 o, f3 d, float t_min, float t_max, uint32_t depth_cap,
+                                                  uint32_t path_samples, Rng& rng, BranchFrame* F, uint32_t& sig) {
+    const float PI = 3.14159265358979323846f;
+    uint32_t level = 0;
+    f3 ret = mk3(0.0f, 0.0f, 0.0f);
+    bool entering = true;                          // true: shade_ray(o, d, level) is being called; false: it returned `ret`
+    for (;;) {
+        if (entering) {
+            bool have_hit = false;
+            if (level >= depth_cap) {              // :301
+                if (SIG) sig = sig_end_depth(sig);
+            } else {
+                Best best;
+                intersect_scene(S, B, o, d, t_min, t_max, rng, best);       // :305
+                if (best.obj < 0) { if (SIG) sig = sig_end_miss(sig, rng); }
+                else {
+                    if (SIG) sig = sig_hit(sig, best.t, best.obj);
+                    BranchFrame& f = F[level];
+                    resolve_hit(S, best, o, d, f.s);
+                    f.d = d; f.integral = mk3(0.0f, 0.0f, 0.0f); f.i = 0;
+                    have_hit = true;
+                }
+            }
+            if (!have_hit) { ret = mk3(0.0f, 0.0f, 0.0f); entering = false; }   // background :302,306
+        } else {
+            if (level == 0) break;                 // shade_ray(camera ray, 0) returned
+            level--;
+            BranchFrame& f = F[level];             // :316  integral += (dot_term*(brdf (.) incoming)) / pdf
+            f.integral = mk3(f.integral.x + ((f.brdf.x * ret.x) * f.dot_term) / f.pdf,
+                             f.integral.y + ((f.brdf.y * ret.y) * f.dot_term) / f.pdf,
+                             f.integral.z + ((f.brdf.z * ret.z) * f.dot_term) / f.pdf);
+            f.i++;
+            entering = true;                       // fall into the sample loop of this level
+        }
+        if (entering) {
+            // here F[level] holds a hit; run the sample loop :310 from f.i
+            BranchFrame& f = F[level];
+            if (f.i < path_samples) {
+                f3 nd; float inv_pdf;
+                scatter_raw(S, f.s, f.d, rng, nd, f.brdf, inv_pdf);         // :312
+                f.pdf = (inv_pdf != 1.0f) ? 1.0f / (2.0f * PI) : 1.0f;      // sample_hemisphere's pdf (materials.rs:178)
+                f.dot_term = (mag2(f.s.n) > 0.0f) ? clampf(fabsf(dot(nd, f.s.n)), 0.0f, 1.0f) : 1.0f;   // :313
+                o = f.s.p; d = nd; level++;        // :314 shade_ray(&new_ray, depth + 1)
+            } else {
+                const float n = (float)path_samples;                        // :318, :321
+                ret = mk3(f.s.emission.x + f.integral.x / n, f.s.emission.y + f.integral.y / n, f.s.emission.z + f.integral.z / n);
+                entering = false;
+            }
+        }
+    }
+    return ret;
+}
+
 template <bool SIG>
 __global__ __launch_bounds__(kBlock) void pt_branch(K1Args A, uint32_t path_samples) {
     const DScene& S = A.S;
@@ -1390,7 +1446,6 @@ __global__ __launch_bounds__(kBlock) void pt_branch(K1Args A, uint32_t path_samp
     }
     const uint32_t pixel = py * C.width + px;
     const float t_min = 0.001f, t_max = C.max_trace_dist;
-    const float PI = 3.14159265358979323846f;
     const uint32_t depth_cap = C.path_depth < (uint32_t)kMaxRecursion ? C.path_depth : (uint32_t)kMaxRecursion;   // host checks <= 64
     BranchFrame F[kMaxRecursion];
     f3 accum = mk3(0.0f, 0.0f, 0.0f);
@@ -1401,53 +1456,7 @@ __global__ __launch_bounds__(kBlock) void pt_branch(K1Args A, uint32_t path_samp
         rng_init(rng, A.seed_key, pixel, sample);
         generate_ray(C, px, py, sample, rng, o, d);
         uint32_t sig = 0;
-        uint32_t level = 0;
-        f3 ret = mk3(0.0f, 0.0f, 0.0f);
-        bool entering = true;                          // true: shade_ray(o, d, level) is being called; false: it returned `ret`
-        for (;;) {
-            if (entering) {
-                bool have_hit = false;
-                if (level >= depth_cap) {              // :301
-                    if (SIG) sig = sig_end_depth(sig);
-                } else {
-                    Best best;
-                    intersect_scene(S, B, o, d, t_min, t_max, rng, best);       // :305
-                    if (best.obj < 0) { if (SIG) sig = sig_end_miss(sig, rng); }
-                    else {
-                        if (SIG) sig = sig_hit(sig, best.t, best.obj);
-                        BranchFrame& f = F[level];
-                        resolve_hit(S, best, o, d, f.s);
-                        f.d = d; f.integral = mk3(0.0f, 0.0f, 0.0f); f.i = 0;
-                        have_hit = true;
-                    }
-                }
-                if (!have_hit) { ret = mk3(0.0f, 0.0f, 0.0f); entering = false; }   // background :302,306
-            } else {
-                if (level == 0) break;                 // shade_ray(camera ray, 0) returned
-                level--;
-                BranchFrame& f = F[level];             // :316  integral += (dot_term*(brdf (.) incoming)) / pdf
-                f.integral = mk3(f.integral.x + ((f.brdf.x * ret.x) * f.dot_term) / f.pdf,
-                                 f.integral.y + ((f.brdf.y * ret.y) * f.dot_term) / f.pdf,
-                                 f.integral.z + ((f.brdf.z * ret.z) * f.dot_term) / f.pdf);
-                f.i++;
-                entering = true;                       // fall into the sample loop of this level
-            }
-            if (entering) {
-                // here F[level] holds a hit; run the sample loop :310 from f.i
-                BranchFrame& f = F[level];
-                if (f.i < path_samples) {
-                    f3 nd; float inv_pdf;
-                    scatter_raw(S, f.s, f.d, rng, nd, f.brdf, inv_pdf);         // :312
-                    f.pdf = (inv_pdf != 1.0f) ? 1.0f / (2.0f * PI) : 1.0f;      // sample_hemisphere's pdf (materials.rs:178)
-                    f.dot_term = (mag2(f.s.n) > 0.0f) ? clampf(fabsf(dot(nd, f.s.n)), 0.0f, 1.0f) : 1.0f;   // :313
-                    o = f.s.p; d = nd; level++;        // :314 shade_ray(&new_ray, depth + 1)
-                } else {
-                    const float n = (float)path_samples;                        // :318, :321
-                    ret = mk3(f.s.emission.x + f.integral.x / n, f.s.emission.y + f.integral.y / n, f.s.emission.z + f.integral.z / n);
-                    entering = false;
-                }
-            }
-        }
+        const f3 ret = shade_ray_recursive<SIG>(S, B, o, d, t_min, t_max, depth_cap, path_samples, rng, F, sig);
         accum = accum + ret;                                                    // :238
         if (SIG) sigsum += sig;
     }
@@ -1456,6 +1465,103 @@ __global__ __launch_bounds__(kBlock) void pt_branch(K1Args A, uint32_t path_samp
     if (in_image) { o3[0] = accum.x / n; o3[1] = accum.y / n; o3[2] = accum.z / n; }
     else { o3[0] = 0.0f; o3[1] = 0.0f; o3[2] = 0.0f; }
     if (SIG && A.sig) A.sig[out_idx] = in_image ? sigsum : 0u;
+}
+
+// ---------------------------------------------------------------- ray queries: caller-supplied rays (mi_intersect_rays / mi_shade_rays)
+// rq_intersect: `impl Intersectable for Scene` (tracing.rs:326-346) for a batch of rays the CALLER made — picking, visibility and occlusion
+// probes, cameras the reference does not have.  One lane per ray, a grid-stride loop over 256-ray chunks on a grid of at most what is
+// resident, so that the LDS form stages the meshes' node and triangle pools once per block and not once per chunk.  Per ray: intersect_list
+// over the kind-grouped list (wave-uniform records, the staged Sphere test, the top-level tree when the scene has one), then every mesh of
+// Scene.objects through the reference's own tree (traverse_mesh; exact for every mesh — the two-stage machinery is not wired in here), as
+// intersect_scene does.  Ray i draws from the stream (seed, first_key + i, 0), fresh: only a ConvexVolume reads it.
+// RESOLVE = false is the visibility form: object and distance only, resolve_hit and its attribute / texel gathers compiled out.
+template <bool LDS, bool GV, bool TOP, bool RESOLVE>
+__global__ __launch_bounds__(kBlock) void rq_intersect(RqArgs A) {
+    const DScene& S = A.S;
+    Bvh<LDS> B;
+    if (LDS) {
+        cf4_ptr gn = (cf4_ptr)S.nodes;
+        cf4_ptr gt = (cf4_ptr)S.tris;
+        const int nn = (int)A.lds_nodes * 2, nt = (int)A.lds_tris * 3;
+        for (int k = threadIdx.x; k < nn; k += kBlock) k1_lds[k] = gn[k];
+        for (int k = threadIdx.x; k < nt; k += kBlock) k1_lds[nn + k] = gt[k];
+        __syncthreads();
+    }
+    bvh_bind(B, S, (int)A.lds_nodes * 2);
+    const float t_min = A.t_min, t_max = A.t_max;
+    const uint32_t n_chunks = (A.n_rays + (uint32_t)kBlock - 1u) / (uint32_t)kBlock;
+    for (uint32_t chunk = blockIdx.x; chunk < n_chunks; chunk += gridDim.x) {
+        const uint32_t i = chunk * (uint32_t)kBlock + threadIdx.x;
+        const bool live = i < A.n_rays;
+        const size_t r = live ? (size_t)i : 0;                              // idle lanes of the last chunk trace ray 0 and store nothing
+        const f3 o = mk3(A.origins[3 * r], A.origins[3 * r + 1], A.origins[3 * r + 2]);
+        const f3 d = mk3(A.dirs[3 * r], A.dirs[3 * r + 1], A.dirs[3 * r + 2]);
+        Rng rng;
+        rng_init(rng, A.seed_key, A.first_key + (uint32_t)r, 0u);
+        Best best; best.obj = -1; best.t = 0.0f; best.tri = -1; best.u = best.v = 0.0f;
+        intersect_list<GV, true, TOP>(S, o, d, t_min, t_max, rng, best);    // tracing.rs:330-344
+        for (int m = 0; m < S.n_meshes; m++) {                              // geometry.rs:301-314
+            auto M = &S.meshes[m];
+            const f3 oo = xform_point(M->inv_transform, o), od = xform_vector(M->inv_transform, d);
+            float bt, bu, bv; int btri;
+            traverse_mesh(B, M->node_begin, M->node_end, M->tri_begin, oo, od, t_min, t_max, bt, btri, bu, bv);
+            if (btri >= 0) consider(best, bt, M->object_index, btri, bu, bv);
+        }
+        if (!live) continue;
+        const bool hit = best.obj >= 0;
+        A.out_object[i] = best.obj;
+        if (A.out_distance) A.out_distance[i] = hit ? best.t : 0.0f;
+        if (RESOLVE) {
+            Surf s;
+            s.p = s.n = s.albedo = s.emission = mk3(0.0f, 0.0f, 0.0f);
+            s.frontface = false; s.kind = 0; s.roughness = s.metallic = s.ior = 0.0f;
+            float tu = 0.0f, tv = 0.0f;
+            int flags = 0;
+            if (hit) {
+                resolve_hit<2>(S, best, o, d, s);
+                if (best.tri >= 0) {                                        // a mesh hit: RayHit.tex_coords, geometry.rs:356
+                    auto T = &S.triattr[S.meshes[S.objects[best.obj].ref].tri_begin + best.tri];
+                    const float u = best.u, v = best.v, w = (1.0f - u - v);
+                    tu = (u * T->tb[0] + v * T->tc[0]) + w * T->ta[0];
+                    tv = (u * T->tb[1] + v * T->tc[1]) + w * T->ta[1];
+                    flags = 2;
+                }
+                flags |= s.frontface ? 1 : 0;
+            }
+            if (A.out_hitpoint) { float* p = A.out_hitpoint + 3 * (size_t)i; p[0] = s.p.x; p[1] = s.p.y; p[2] = s.p.z; }
+            if (A.out_normal) { float* p = A.out_normal + 3 * (size_t)i; p[0] = s.n.x; p[1] = s.n.y; p[2] = s.n.z; }
+            if (A.out_flags) A.out_flags[i] = flags;
+            if (A.out_uv) { A.out_uv[2 * (size_t)i] = tu; A.out_uv[2 * (size_t)i + 1] = tv; }
+            if (A.out_material) {                                           // mi_material: kind, albedo, emission, roughness, metallic, ior
+                uint32_t* p = A.out_material + 10 * (size_t)i;
+                const float w[9] = { s.albedo.x, s.albedo.y, s.albedo.z, s.emission.x, s.emission.y, s.emission.z, s.roughness, s.metallic, s.ior };
+                p[0] = (uint32_t)s.kind;
+#pragma unroll
+                for (int k = 0; k < 9; k++) p[1 + k] = __float_as_uint(w[k]);
+            }
+        }
+    }
+}
+
+// rq_shade: Scene::shade_ray(ray, 0) (tracing.rs:300-324) as written for caller-supplied rays: pt_branch's per-sample body on ray i with
+// the stream (seed, first_key + i, 0).  A completeness path like pt_branch (per-lane frame stack in scratch, BVH from global memory),
+// bit-identical to the CPU restatement for every path_samples; not tuned.
+__global__ __launch_bounds__(kBlock) void rq_shade(RqShadeArgs A) {
+    const DScene& S = A.S;
+    Bvh<false> B;
+    bvh_bind(B, S, 0);
+    const uint32_t i = blockIdx.x * (uint32_t)kBlock + threadIdx.x;
+    if (i >= A.n_rays) return;
+    const f3 o = mk3(A.origins[3 * (size_t)i], A.origins[3 * (size_t)i + 1], A.origins[3 * (size_t)i + 2]);
+    const f3 d = mk3(A.dirs[3 * (size_t)i], A.dirs[3 * (size_t)i + 1], A.dirs[3 * (size_t)i + 2]);
+    const uint32_t depth_cap = A.path_depth < (uint32_t)kMaxRecursion ? A.path_depth : (uint32_t)kMaxRecursion;   // host checks <= 64
+    BranchFrame F[kMaxRecursion];
+    Rng rng;
+    rng_init(rng, A.seed_key, A.first_key + i, 0u);
+    uint32_t sig = 0;
+    const f3 c = shade_ray_recursive<false>(S, B, o, d, 0.001f, A.max_trace_dist, depth_cap, A.path_samples, rng, F, sig);   // t_min: tracing.rs:305
+    float* p = A.out_rgb + 3 * (size_t)i;
+    p[0] = c.x; p[1] = c.y; p[2] = c.z;
 }
 
 // ---------------------------------------------------------------- K1, voted state machine
@@ -3144,6 +3250,33 @@ hipError_t launch_branch(const K1Args& a, uint32_t n_blocks, uint32_t path_sampl
     dim3 grid(n_blocks), block(kBlock);
     if (sig) hipLaunchKernelGGL((pt_branch<true>), grid, block, 0, stream, a, path_samples);
     else hipLaunchKernelGGL((pt_branch<false>), grid, block, 0, stream, a, path_samples);
+    return hipGetLastError();
+}
+// Ray queries.  The grid is what the device holds at once (the kernel strides over the 256-ray chunks), at most one block per chunk.
+hipError_t launch_rq_intersect(const RqArgs& a, bool lds, bool gv, bool resolve, size_t lds_bytes, int n_cus, hipStream_t stream) {
+    const bool top = a.S.top_meshf >= 0;
+    const size_t dyn = lds ? lds_bytes : 0;
+    const uint32_t n_chunks = (a.n_rays + (uint32_t)kBlock - 1u) / (uint32_t)kBlock;
+    const void* fn = nullptr;
+#define PT_RQ_PICK(L, G, T, R) fn = (const void*)&rq_intersect<L, G, T, R>
+#define PT_RQ_PICK3(L, G, T) do { if (resolve) PT_RQ_PICK(L, G, T, true); else PT_RQ_PICK(L, G, T, false); } while (0)
+#define PT_RQ_PICK2(L, G) do { if (top) PT_RQ_PICK3(L, G, true); else PT_RQ_PICK3(L, G, false); } while (0)
+    if (lds) { if (gv) PT_RQ_PICK2(true, true); else PT_RQ_PICK2(true, false); }
+    else     { if (gv) PT_RQ_PICK2(false, true); else PT_RQ_PICK2(false, false); }
+#undef PT_RQ_PICK2
+#undef PT_RQ_PICK3
+#undef PT_RQ_PICK
+    int per_cu = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, kBlock, dyn) != hipSuccess || per_cu < 1) { (void)hipGetLastError(); per_cu = 1; }
+    const uint64_t resident = (uint64_t)per_cu * (uint64_t)(n_cus > 0 ? n_cus : 1);
+    const uint32_t n_blocks = (uint32_t)(resident < (uint64_t)n_chunks ? resident : (uint64_t)n_chunks);
+    RqArgs args = a;
+    void* params[] = { (void*)&args };
+    return hipLaunchKernel(fn, dim3(n_blocks), dim3(kBlock), params, dyn, stream);
+}
+hipError_t launch_rq_shade(const RqShadeArgs& a, hipStream_t stream) {
+    const uint32_t n_blocks = (a.n_rays + (uint32_t)kBlock - 1u) / (uint32_t)kBlock;
+    hipLaunchKernelGGL(rq_shade, dim3(n_blocks), dim3(kBlock), 0, stream, a);
     return hipGetLastError();
 }
 hipError_t launch_wf_main(const WfArgs& a, uint32_t n_blocks, bool sig, bool gv, bool tex, hipStream_t stream) {

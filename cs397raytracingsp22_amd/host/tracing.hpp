@@ -3,6 +3,7 @@
 // flatten -> mi_scene_upload -> mi_render through the C ABI of include/mi_rt.h.  Errors that the
 // reference raises as panics surface as std::runtime_error carrying mi_last_error().
 #pragma once
+#include <cmath>
 #include <stdexcept>
 #include <string>
 #include <vector>
@@ -34,6 +35,14 @@ struct Camera {                                        // tracing.rs:138-155, sa
 };
 
 struct RgbImage { uint32_t width = 0, height = 0; std::vector<uint8_t> data; };   // image::RgbImage byte layout
+
+// Closest hits of a batch of caller-supplied rays (Scene::intersect_rays): one entry per ray, object = index into Scene.objects, -1 = None
+struct RayHits {
+    std::vector<int32_t> object; std::vector<float> distance;
+    std::vector<float> hitpoint, normal, uv;           // [n][3], [n][3], [n][2]; empty with resolve = false, like flags and material
+    std::vector<int32_t> flags;                        // bit 0 frontface, bit 1 has_tex_coords
+    std::vector<mi_material> material;
+};
 
 inline void mi_check(int rc) { if (rc != MI_OK) throw std::runtime_error(std::string("mi_rt: ") + mi_last_error()); }
 
@@ -77,6 +86,52 @@ struct Scene : Intersectable {                         // tracing.rs:213-218; `i
         }
         if (rc != MI_OK) throw std::runtime_error("mi_rt: " + err);
         return img;
+    }
+
+    // `impl Intersectable for Scene`, Scene::intersect_ray (tracing.rs:326-346), for n rays of the caller's making through mi_intersect_rays:
+    // origins / dirs are [n][3], directions are used as given.  Ray i draws from the stream (seed, first_key + i, 0).  resolve = false asks
+    // for object and distance only (the visibility form).
+    RayHits intersect_rays(const std::vector<float>& origins, const std::vector<float>& dirs, float t_min = 0.001f, float t_max = INFINITY,
+                           uint32_t seed = 1, uint32_t first_key = 0, bool resolve = true, int device = 0) const {
+        if (origins.size() != dirs.size() || origins.size() % 3 != 0) throw std::runtime_error("mi_rt: origins and dirs must both be [n][3]");
+        const size_t n = origins.size() / 3;
+        RayHits h; h.object.resize(n); h.distance.resize(n);
+        if (resolve) { h.hitpoint.resize(3 * n); h.normal.resize(3 * n); h.uv.resize(2 * n); h.flags.resize(n); h.material.resize(n); }
+        with_context(device, [&](mi_ctx* ctx) {
+            return mi_intersect_rays(ctx, (uint32_t)n, origins.data(), dirs.data(), t_min, t_max, seed, first_key, h.object.data(), h.distance.data(),
+                                     resolve ? h.hitpoint.data() : nullptr, resolve ? h.normal.data() : nullptr, resolve ? h.flags.data() : nullptr,
+                                     resolve ? h.uv.data() : nullptr, resolve ? h.material.data() : nullptr);
+        });
+        return h;
+    }
+
+    // Scene::shade_ray (tracing.rs:300-324) at level 0 for n rays through mi_shade_rays -> [n][3] radiance; the camera supplies path_depth,
+    // path_samples and max_trace_dist.
+    std::vector<float> shade_rays(const std::vector<float>& origins, const std::vector<float>& dirs, uint32_t seed = 1, uint32_t first_key = 0,
+                                  int device = 0) const {
+        if (origins.size() != dirs.size() || origins.size() % 3 != 0) throw std::runtime_error("mi_rt: origins and dirs must both be [n][3]");
+        std::vector<float> rgb(origins.size());
+        const mi_camera_desc cam = camera.flatten();
+        with_context(device, [&](mi_ctx* ctx) {
+            return mi_shade_rays(ctx, &cam, (uint32_t)(origins.size() / 3), origins.data(), dirs.data(), seed, first_key, rgb.data());
+        });
+        return rgb;
+    }
+
+private:
+    // flatten -> context -> upload -> `call(ctx)` -> destroy; a failure surfaces as std::runtime_error carrying mi_last_error()
+    template <class F> void with_context(int device, F call) const {
+        SceneBuilder sb;
+        for (auto& o : objects) o->flatten(sb);
+        mi_scene_desc d = sb.desc();
+        for (int k = 0; k < 3; k++) { d.point_light_pos[k] = point_light_pos[k]; d.ambient[k] = ambient[k]; }
+        mi_ctx* ctx = nullptr;
+        mi_check(mi_ctx_create(device, &ctx));
+        int rc = mi_scene_upload(ctx, &d);
+        if (rc == MI_OK) rc = call(ctx);
+        const std::string err = rc == MI_OK ? "" : mi_last_error();
+        mi_ctx_destroy(ctx);
+        if (rc != MI_OK) throw std::runtime_error("mi_rt: " + err);
     }
 };
 

@@ -59,6 +59,46 @@ class Camera:                        # tracing.rs:138-155, same fields
         return c
 
 
+@dataclass
+class RayHits:
+    """Result of Context.intersect_rays: one entry per ray, numpy arrays.  `object` is the index into Scene.objects (-1 = no hit;
+    every other array then holds zeros).  With resolve=False only `object` and `distance` are filled, the rest is None."""
+    object: np.ndarray                       # [n] int32
+    distance: np.ndarray                     # [n] f32, RayHit.distance (object-space t for a StaticMesh)
+    hitpoint: Optional[np.ndarray] = None    # [n, 3] f32
+    normal: Optional[np.ndarray] = None      # [n, 3] f32, facing the ray (zero inside a ConvexVolume)
+    frontface: Optional[np.ndarray] = None   # [n] bool
+    has_uv: Optional[np.ndarray] = None      # [n] bool
+    uv: Optional[np.ndarray] = None          # [n, 2] f32
+    material: Optional[np.ndarray] = None    # [n] structured: kind, albedo, emission, roughness, metallic, idx_of_refraction
+
+    def __len__(self):
+        return len(self.object)
+
+
+# numpy view of abi.mi_material (40 bytes)
+MATERIAL_DTYPE = np.dtype([("kind", np.int32), ("albedo", np.float32, 3), ("emission", np.float32, 3), ("roughness", np.float32),
+                           ("metallic", np.float32), ("idx_of_refraction", np.float32)])
+
+
+def check_rays(origins, dirs, t_min: float = 0.001, t_max: float = float("inf")):
+    """Input checking of the ray queries (no GPU needed): `origins` and `dirs` as C-contiguous float32 arrays of shape (n, 3) and
+    equal length, t_min / t_max as floats that are not NaN.  Directions are NOT normalised (the reference does not either)."""
+    o = np.ascontiguousarray(np.asarray(origins, dtype=np.float32))
+    d = np.ascontiguousarray(np.asarray(dirs, dtype=np.float32))
+    for name, a in (("origins", o), ("dirs", d)):
+        if a.ndim != 2 or a.shape[1] != 3:
+            raise ValueError(f"{name} must have shape (n, 3), got {a.shape}")
+    if len(o) != len(d):
+        raise ValueError(f"origins and dirs differ in length: {len(o)} and {len(d)}")
+    if len(o) >= 1 << 32:
+        raise ValueError("at most 2^32 - 1 rays per call")
+    t_min, t_max = float(t_min), float(t_max)
+    if t_min != t_min or t_max != t_max:
+        raise ValueError("t_min / t_max must not be NaN")
+    return o, d, t_min, t_max
+
+
 class Context:
     """One mi_ctx = one GPU (one process per GPU: pass LOCAL_RANK)."""
 
@@ -178,6 +218,54 @@ class Context:
         abi.check(self._lib.mi_last_kernel_ms(self._h, C.byref(ms)))
         return float(ms.value)
 
+    # ---- ray queries: Scene::intersect_ray / Scene::shade_ray for rays of the caller's making ----
+    def intersect_rays(self, origins, dirs, t_min: float = 0.001, t_max: float = float("inf"), seed: int = 1,
+                       first_key: int = 0, resolve: bool = True) -> RayHits:
+        """mi_intersect_rays: the closest hit of every ray over Scene.objects.  Ray i draws from the stream (seed, first_key + i, 0).
+        resolve=False is the visibility form: object and distance only."""
+        o, d, t_min, t_max = check_rays(origins, dirs, t_min, t_max)
+        n = len(o)
+        r = RayHits(object=np.zeros(n, np.int32), distance=np.zeros(n, np.float32))
+        flags = None
+        if resolve:
+            r.hitpoint, r.normal = np.zeros((n, 3), np.float32), np.zeros((n, 3), np.float32)
+            r.uv, r.material = np.zeros((n, 2), np.float32), np.zeros(n, MATERIAL_DTYPE)
+            flags = np.zeros(n, np.int32)
+        ptr = lambda a: a.ctypes.data if a is not None else None
+        abi.check(self._lib.mi_intersect_rays(self._h, n, o.ctypes.data, d.ctypes.data, t_min, t_max, seed, first_key & 0xffffffff,
+                                              ptr(r.object), ptr(r.distance), ptr(r.hitpoint), ptr(r.normal), ptr(flags), ptr(r.uv),
+                                              ptr(r.material)))
+        if resolve:
+            r.frontface, r.has_uv = (flags & 1) != 0, (flags & 2) != 0
+        return r
+
+    def intersect_rays_device(self, n_rays: int, d_origins: int, d_dirs: int, d_object: int, d_distance: Optional[int] = None,
+                              d_hitpoint: Optional[int] = None, d_normal: Optional[int] = None, d_flags: Optional[int] = None,
+                              d_uv: Optional[int] = None, d_material: Optional[int] = None, t_min: float = 0.001,
+                              t_max: float = float("inf"), seed: int = 1, first_key: int = 0, stream: Optional[int] = None):
+        """mi_intersect_rays_device: raw device pointers (ints), one kernel queued on `stream`, no synchronisation."""
+        t_min, t_max = float(t_min), float(t_max)
+        if t_min != t_min or t_max != t_max:
+            raise ValueError("t_min / t_max must not be NaN")
+        abi.check(self._lib.mi_intersect_rays_device(self._h, n_rays, d_origins, d_dirs, t_min, t_max, seed, first_key & 0xffffffff,
+                                                     d_object, d_distance, d_hitpoint, d_normal, d_flags, d_uv, d_material, stream))
+
+    def shade_rays(self, cam: Camera, origins, dirs, seed: int = 1, first_key: int = 0) -> np.ndarray:
+        """mi_shade_rays: Scene::shade_ray at level 0 for every ray -> [n, 3] f32 radiance.  `cam` supplies path_depth,
+        path_samples and max_trace_dist."""
+        o, d, _, _ = check_rays(origins, dirs)
+        pod = cam.to_pod()
+        out = np.zeros((len(o), 3), np.float32)
+        abi.check(self._lib.mi_shade_rays(self._h, C.byref(pod), len(o), o.ctypes.data, d.ctypes.data, seed, first_key & 0xffffffff,
+                                          out.ctypes.data))
+        return out
+
+    def shade_rays_device(self, cam: Camera, n_rays: int, d_origins: int, d_dirs: int, d_rgb: int, seed: int = 1,
+                          first_key: int = 0, stream: Optional[int] = None):
+        pod = cam.to_pod()
+        abi.check(self._lib.mi_shade_rays_device(self._h, C.byref(pod), n_rays, d_origins, d_dirs, seed, first_key & 0xffffffff,
+                                                 d_rgb, stream))
+
 
 class MultiContext:
     """mi_multi: N GPUs of one node behind ONE handle (one context, stream and host thread per device inside the
@@ -275,5 +363,26 @@ class Scene:                         # tracing.rs:213-218
             ctx.upload(self.flatten())
             _, u8, _, _ = ctx.render(self.camera, seed=seed, want_f32=False, want_u8=True)
             return u8
+        finally:
+            ctx.close()
+
+    def intersect_rays(self, origins, dirs, t_min: float = 0.001, t_max: float = float("inf"), seed: int = 1, first_key: int = 0,
+                       resolve: bool = True, device: int = 0) -> RayHits:
+        """`impl Intersectable for Scene` (tracing.rs:326-346) for a batch of rays: flatten -> upload -> one query."""
+        o, d, t_min, t_max = check_rays(origins, dirs, t_min, t_max)
+        ctx = Context(device)
+        try:
+            ctx.upload(self.flatten())
+            return ctx.intersect_rays(o, d, t_min, t_max, seed=seed, first_key=first_key, resolve=resolve)
+        finally:
+            ctx.close()
+
+    def shade_rays(self, origins, dirs, seed: int = 1, first_key: int = 0, device: int = 0) -> np.ndarray:
+        """Scene::shade_ray (tracing.rs:300-324) at level 0 for a batch of rays, with this scene's camera settings."""
+        o, d, _, _ = check_rays(origins, dirs)
+        ctx = Context(device)
+        try:
+            ctx.upload(self.flatten())
+            return ctx.shade_rays(self.camera, o, d, seed=seed, first_key=first_key)
         finally:
             ctx.close()

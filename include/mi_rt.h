@@ -200,7 +200,7 @@ typedef struct mi_render_opts {
                                      * exact two-stage traversal would be used: same image, slower on large meshes */
 #define MI_OPT_TWO_STAGE       4u   /* meshes: use the two-stage traversal for every mesh, whatever its size: same image */
 #define MI_OPT_NO_LIST_TREE    8u   /* long lists: test every Triangle of Scene.objects one by one instead of walking the top-level tree the scene
-                                     * compiler builds over them (>= 32 small triangles): same image */
+                                     * compiler builds over them (>= 96 small triangles): same image */
 
 typedef enum mi_variant {
     MI_VARIANT_DEFAULT    = 0,  /* library picks (currently MI_VARIANT_WAVEFRONT)                  */
@@ -279,9 +279,48 @@ int  mi_unpermute_device(mi_ctx* ctx, const mi_camera_desc* cam, int32_t world,
 int  mi_tonemap_device(mi_ctx* ctx, const mi_camera_desc* cam,
                        const void* d_image_f32, void* d_image_u8, void* stream);
 
-/* Elapsed time of the most recent path-tracing kernel of this ctx (HIP events on its
+/* Elapsed time of the most recent path-tracing or ray-query kernel of this ctx (HIP events on its
  * launch stream); synchronises on the stop event. */
 int  mi_last_kernel_ms(mi_ctx* ctx, float* ms);
+
+/* ---- ray queries: the reference's two calls that take a ray of the CALLER's making (added within ABI version 5: the version number
+ * is unchanged, a caller that may meet an older library detects these four by symbol lookup) ----
+ * mi_intersect_rays: `impl Intersectable for Scene`, Scene::intersect_ray (tracing.rs:326-346), for n_rays rays: the closest hit over
+ *   Scene.objects in [t_min, t_max], the first object winning a tie.  Picking, visibility and occlusion probes, light baking, cameras
+ *   the reference does not have.  t_max = +infinity is legal; a NaN t_min or t_max is MI_ERR_INVALID.
+ * mi_shade_rays: Scene::shade_ray (tracing.rs:300-324) at level 0 for n_rays rays, as written (the recursive estimator of
+ *   MI_VARIANT_RECURSIVE, bit-identical to the CPU restatement for every path_samples; not a tuned path).  `cam` supplies path_depth,
+ *   path_samples and max_trace_dist; its screen_* fields and aa_sample_count are ignored.  shading_mode Phong and path_depth > 64 are
+ *   MI_ERR_UNSUPPORTED.
+ * Directions are used as given, NOT normalised (the reference does not normalise them either: distances are in units of |dir|).
+ * Ray i draws from the RNG stream (seed, pixel = first_key + i, sample = 0), fresh: no Camera::generate_rays draws come first.  Only
+ * ConvexVolume::intersect_ray and the scatters read it.  A batch split over several calls with first_key advanced by the rays already
+ * done gives the answers of one call.  Non-finite origins or directions are not rejected: a "hit" at a NaN distance is kept
+ * in the kernels' kind-grouped order, not in Scene.objects order (the deviation DESIGN.md section 2 (v) records; finite rays are exact).
+ * The plain forms take HOST pointers and block: they upload, run and download in chunks through a buffer of their own, so device
+ * scratch stays bounded whatever n_rays is.  The _device forms take DEVICE pointers on ctx's device and queue one kernel on `stream`
+ * (a hipStream_t, NULL = default stream) without synchronising.  Neither touches the buffers mi_reserve sized.
+ * n_rays == 0 is MI_OK and launches nothing.  mi_last_kernel_ms afterwards gives the query kernel's time (the sum over the chunks of a
+ * host-pointer call).
+ * Outputs of mi_intersect_rays (each [n_rays] records; every one except out_object may be NULL, and when all of out_hitpoint ..
+ * out_material are NULL the visibility form of the kernel runs, which never fetches shading data):
+ *   out_object   int32            index into Scene.objects, -1 = None (REQUIRED); for a miss every other output holds zeros
+ *   out_distance float            RayHit.distance (object-space t for a StaticMesh, geometry.rs:304-305)
+ *   out_hitpoint float[3]         RayHit.hitpoint (world space)
+ *   out_normal   float[3]         RayHit.normal, facing the ray (zero inside a ConvexVolume, geometry.rs:520)
+ *   out_flags    int32            bit 0 = frontface, bit 1 = has_tex_coords (StaticMesh hits)
+ *   out_uv       float[2]         RayHit.tex_coords (geometry.rs:356)
+ *   out_material mi_material      the material at the hit (StaticMesh::get_material_at_uv for meshes, the phase function for a volume) */
+int  mi_intersect_rays(mi_ctx* ctx, uint32_t n_rays, const float* origins, const float* dirs, float t_min, float t_max,
+                       uint32_t seed, uint32_t first_key, int32_t* out_object, float* out_distance, float* out_hitpoint,
+                       float* out_normal, int32_t* out_flags, float* out_uv, mi_material* out_material);
+int  mi_intersect_rays_device(mi_ctx* ctx, uint32_t n_rays, const float* origins, const float* dirs, float t_min, float t_max,
+                              uint32_t seed, uint32_t first_key, int32_t* out_object, float* out_distance, float* out_hitpoint,
+                              float* out_normal, int32_t* out_flags, float* out_uv, mi_material* out_material, void* stream);
+int  mi_shade_rays(mi_ctx* ctx, const mi_camera_desc* cam, uint32_t n_rays, const float* origins, const float* dirs,
+                   uint32_t seed, uint32_t first_key, float* out_rgb);
+int  mi_shade_rays_device(mi_ctx* ctx, const mi_camera_desc* cam, uint32_t n_rays, const float* origins, const float* dirs,
+                          uint32_t seed, uint32_t first_key, float* out_rgb, void* stream);
 
 /* Size and allocate the wavefront pipeline's HBM buffers (path state, sample slots) for
  * this camera with the image shared by `world` ranks, so that the first render does not pay the

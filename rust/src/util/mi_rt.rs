@@ -67,6 +67,18 @@ extern "C" {
                                d_gathered_f32: *const c_void, d_image_f32: *mut c_void, stream: *mut c_void) -> c_int;
     pub fn mi_tonemap_device(ctx: *mut mi_ctx, cam: *const mi_camera_desc, d_image_f32: *const c_void, d_image_u8: *mut c_void, stream: *mut c_void) -> c_int;
     pub fn mi_last_kernel_ms(ctx: *mut mi_ctx, ms: *mut f32) -> c_int;
+    // ray queries (added within ABI 5; a caller that may meet an older library looks the symbols up)
+    pub fn mi_intersect_rays(ctx: *mut mi_ctx, n_rays: u32, origins: *const f32, dirs: *const f32, t_min: f32, t_max: f32,
+                             seed: u32, first_key: u32, out_object: *mut i32, out_distance: *mut f32, out_hitpoint: *mut f32,
+                             out_normal: *mut f32, out_flags: *mut i32, out_uv: *mut f32, out_material: *mut mi_material) -> c_int;
+    pub fn mi_intersect_rays_device(ctx: *mut mi_ctx, n_rays: u32, origins: *const f32, dirs: *const f32, t_min: f32, t_max: f32,
+                                    seed: u32, first_key: u32, out_object: *mut i32, out_distance: *mut f32, out_hitpoint: *mut f32,
+                                    out_normal: *mut f32, out_flags: *mut i32, out_uv: *mut f32, out_material: *mut mi_material,
+                                    stream: *mut c_void) -> c_int;
+    pub fn mi_shade_rays(ctx: *mut mi_ctx, cam: *const mi_camera_desc, n_rays: u32, origins: *const f32, dirs: *const f32,
+                         seed: u32, first_key: u32, out_rgb: *mut f32) -> c_int;
+    pub fn mi_shade_rays_device(ctx: *mut mi_ctx, cam: *const mi_camera_desc, n_rays: u32, origins: *const f32, dirs: *const f32,
+                                seed: u32, first_key: u32, out_rgb: *mut f32, stream: *mut c_void) -> c_int;
     pub fn mi_reserve(ctx: *mut mi_ctx, cam: *const mi_camera_desc, world: i32, max_state_bytes: u64) -> c_int;
     pub fn mi_last_pipeline_ms(ctx: *mut mi_ctx, out8: *mut f32) -> c_int;
     pub fn mi_last_pipeline_counts(ctx: *mut mi_ctx, out8: *mut u64) -> c_int;

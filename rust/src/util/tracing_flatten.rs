@@ -91,4 +91,51 @@ impl Scene {
         }
         img
     }
+
+    /// `impl Intersectable for Scene` (tracing.rs:326-346) for a batch of rays on the GPU (mi_intersect_rays): per ray the index into
+    /// `self.objects` of the closest hit in [t_min, t_max] (-1 = None) and RayHit.distance.  `origins` / `dirs` are [x, y, z] per ray;
+    /// directions are used as given.  Ray i draws from the stream (seed, first_key + i, 0), which only a ConvexVolume reads.
+    pub fn intersect_rays(&self, origins: &[[f32; 3]], dirs: &[[f32; 3]], t_min: f32, t_max: f32, seed: u32, first_key: u32) -> (Vec<i32>, Vec<f32>) {
+        assert_eq!(origins.len(), dirs.len(), "mi_rt: origins and dirs differ in length");
+        let n = origins.len();
+        let mut object = vec![-1i32; n];
+        let mut distance = vec![0.0f32; n];
+        let (po, pd) = (origins.as_ptr() as *const f32, dirs.as_ptr() as *const f32);
+        let (pobj, pt) = (object.as_mut_ptr(), distance.as_mut_ptr());
+        self.with_gpu_scene(|ctx| unsafe {
+            mi_rt::mi_intersect_rays(ctx, n as u32, po, pd, t_min, t_max, seed, first_key, pobj, pt, std::ptr::null_mut(), std::ptr::null_mut(),
+                                     std::ptr::null_mut(), std::ptr::null_mut(), std::ptr::null_mut())
+        });
+        (object, distance)
+    }
+
+    /// Scene::shade_ray (tracing.rs:300-324) at level 0 for a batch of rays on the GPU (mi_shade_rays): the radiance per ray; the camera
+    /// supplies path_depth, path_samples and max_trace_dist.
+    pub fn shade_rays(&self, origins: &[[f32; 3]], dirs: &[[f32; 3]], seed: u32, first_key: u32) -> Vec<[f32; 3]> {
+        assert_eq!(origins.len(), dirs.len(), "mi_rt: origins and dirs differ in length");
+        let n = origins.len();
+        let cam = self.camera.flatten();
+        let mut rgb = vec![[0.0f32; 3]; n];
+        let (po, pd, pout) = (origins.as_ptr() as *const f32, dirs.as_ptr() as *const f32, rgb.as_mut_ptr() as *mut f32);
+        self.with_gpu_scene(|ctx| unsafe { mi_rt::mi_shade_rays(ctx, &cam, n as u32, po, pd, seed, first_key, pout) });
+        rgb
+    }
+
+    /// flatten -> context on device 0 -> upload -> `call` -> destroy; panics with the library's message on failure.
+    fn with_gpu_scene<F: FnOnce(*mut mi_rt::mi_ctx) -> i32>(&self, call: F) {
+        let sb = self.flatten_scene();
+        if let Some(why) = &sb.unsupported { panic!("mi_rt: this scene cannot run on the GPU path: {}", why); }
+        let mut desc = sb.desc();
+        desc.point_light_pos = self.point_light_pos.into();
+        desc.ambient = self.ambient.into();
+        unsafe {
+            let mut ctx = std::ptr::null_mut();
+            assert_eq!(mi_rt::mi_ctx_create(0, &mut ctx), 0, "{}", mi_rt::last_error());
+            let up = mi_rt::mi_scene_upload(ctx, &desc);
+            let rc = if up != 0 { up } else { call(ctx) };
+            let msg = mi_rt::last_error();
+            mi_rt::mi_ctx_destroy(ctx);
+            assert_eq!(rc, 0, "{}", msg);
+        }
+    }
 }

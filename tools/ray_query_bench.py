@@ -1,0 +1,111 @@
+#!/usr/bin/env python
+"""Throughput of the ray queries (mi_intersect_rays_device) on one MI355X.
+
+For cfg2 (Cornell box + teapot) and cfg4 (textured drone) at 1920x1080 two ray sets are measured, each with `resolve` on (every
+output array) and off (the visibility form: object and distance only):
+  camera   one ray per pixel of the frame's camera: the pinhole ray through the pixel centre (built here in numpy; a measuring tool,
+           not a parity surface, so the thin lens and the jitter of Camera::generate_rays are left out)
+  bounce   the first-bounce rays of those: origin = the hitpoint the library returned for the camera ray, direction = a seeded random
+           unit vector (one per camera hit; the misses are dropped)
+Per set: 5 warm-up calls, then --calls timed calls (default 20) through the device entry point on device-resident arrays.  Two rates
+are printed per row, from the median call: Mrays/s from mi_last_kernel_ms (HIP events around the kernel) and from the wall clock around
+call + synchronise.  One JSON line per row; no pass / fail bar.  Needs a GPU: there is no CPU fallback."""
+import argparse
+import json
+import os
+import sys
+import time
+
+import torch  # first HIP runtime in the process (see cs397raytracingsp22_amd/abi.py)
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)
+
+from cs397raytracingsp22_amd import Context, scenes  # noqa: E402
+
+
+def pinhole_rays(cam):
+    """Rays through the pixel centres of `cam` (tracing.rs:160-163,187-191 without jitter and lens), row-major."""
+    W, H = cam.screen_width, cam.screen_height
+    eye, view, up = (np.asarray(v, np.float64) for v in (cam.eyepoint, cam.view_dir, cam.up))
+    right = np.cross(view, up)
+    right /= np.linalg.norm(right)
+    x, y = np.meshgrid(np.arange(W, dtype=np.float64), np.arange(H, dtype=np.float64))
+    cx, cy = (x + 0.5 - 0.5 * W) / H, (0.5 * H - y - 0.5) / H
+    d = cx[..., None] * right + cy[..., None] * up + cam.focal_length * view
+    d /= np.linalg.norm(d, axis=-1, keepdims=True)
+    o = np.broadcast_to(eye, d.shape)
+    return np.ascontiguousarray(o.reshape(-1, 3), np.float32), np.ascontiguousarray(d.reshape(-1, 3), np.float32)
+
+
+def measure(ctx, o, d, t_max, resolve, calls, warmup):
+    dev = torch.device("cuda:0")
+    n = len(o)
+    t_o, t_d = torch.from_numpy(o).to(dev), torch.from_numpy(d).to(dev)
+    t_obj, t_t = torch.empty(n, dtype=torch.int32, device=dev), torch.empty(n, dtype=torch.float32, device=dev)
+    extra = [None] * 5
+    keep = []
+    if resolve:
+        keep = [torch.empty((n, 3), dtype=torch.float32, device=dev), torch.empty((n, 3), dtype=torch.float32, device=dev),
+                torch.empty(n, dtype=torch.int32, device=dev), torch.empty((n, 2), dtype=torch.float32, device=dev),
+                torch.empty((n, 10), dtype=torch.int32, device=dev)]
+        extra = [t.data_ptr() for t in keep]
+    torch.cuda.synchronize()
+    kernel_ms, wall_ms = [], []
+    for k in range(warmup + calls):
+        t0 = time.perf_counter()
+        ctx.intersect_rays_device(n, t_o.data_ptr(), t_d.data_ptr(), t_obj.data_ptr(), t_t.data_ptr(), *extra, t_min=0.001, t_max=t_max, seed=1)
+        torch.cuda.synchronize()
+        t1 = time.perf_counter()
+        if k >= warmup:
+            kernel_ms.append(ctx.last_kernel_ms())
+            wall_ms.append((t1 - t0) * 1e3)
+    hits = int((t_obj >= 0).sum().item())
+    return float(np.median(kernel_ms)), float(np.median(wall_ms)), float(np.min(kernel_ms)), float(np.max(kernel_ms)), hits
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--calls", type=int, default=20, help="timed calls per row (at least 20)")
+    ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--width", type=int, default=1920)
+    ap.add_argument("--height", type=int, default=1080)
+    ap.add_argument("--configs", default="2,4")
+    ap.add_argument("--out", default=None, help="also append the JSON lines to this file")
+    a = ap.parse_args()
+    if a.calls < 20:
+        ap.error("--calls must be at least 20")
+    if not torch.cuda.is_available():
+        raise SystemExit("ray_query_bench: no GPU; there is no CPU fallback")
+    ctx = Context(0)
+    rows = []
+    for cfg in [int(c) for c in a.configs.split(",")]:
+        sc = {2: scenes.config2, 4: scenes.config4}[cfg](a.width, a.height, 1, 10)
+        ctx.upload(sc.flatten())
+        co, cd = pinhole_rays(sc.camera)
+        first = ctx.intersect_rays(co, cd, t_max=sc.camera.max_trace_dist)
+        hit = first.object >= 0
+        rng = np.random.default_rng(1)
+        bd = rng.standard_normal((int(hit.sum()), 3))
+        bd = np.ascontiguousarray(bd / np.linalg.norm(bd, axis=1, keepdims=True), np.float32)
+        bo = np.ascontiguousarray(first.hitpoint[hit])
+        for set_name, o, d, t_max in (("camera", co, cd, sc.camera.max_trace_dist), ("bounce", bo, bd, float("inf"))):
+            for resolve in (True, False):
+                med, wall, lo, hi, hits = measure(ctx, o, d, t_max, resolve, a.calls, a.warmup)
+                row = {"config": cfg, "rays": set_name, "resolve": resolve, "n_rays": len(o), "hits": hits, "calls": a.calls,
+                       "kernel_ms_median": round(med, 4), "kernel_ms_min": round(lo, 4), "kernel_ms_max": round(hi, 4),
+                       "wall_ms_median": round(wall, 4), "mrays_per_s_kernel": round(len(o) / med / 1e3, 1),
+                       "mrays_per_s_wall": round(len(o) / wall / 1e3, 1)}
+                rows.append(row)
+                print(json.dumps(row), flush=True)
+    ctx.close()
+    if a.out:
+        with open(a.out, "a") as fh:
+            for row in rows:
+                fh.write(json.dumps(row) + "\n")
+
+
+if __name__ == "__main__":
+    main()
