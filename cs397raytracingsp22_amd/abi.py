@@ -111,6 +111,7 @@ EXPORTS = [
     "mi_render_tiles_device", "mi_unpermute_device", "mi_tonemap_device", "mi_last_kernel_ms",
     "mi_reserve", "mi_render_samples_device", "mi_last_pipeline_ms", "mi_last_pipeline_counts", "mi_last_diag", "mi_selftest", "mi_last_error", "mi_abi_version",
     "mi_intersect_rays", "mi_intersect_rays_device", "mi_shade_rays", "mi_shade_rays_device",
+    "mi_occluded_rays", "mi_occluded_rays_device",
     "mi_multi_create", "mi_multi_create_loopback", "mi_multi_destroy", "mi_multi_device_count", "mi_multi_context", "mi_multi_scene_upload", "mi_multi_reserve", "mi_multi_render",
 ]
 
@@ -184,6 +185,10 @@ def load() -> C.CDLL:
     lib.mi_shade_rays.restype = C.c_int
     lib.mi_shade_rays_device.argtypes = lib.mi_shade_rays.argtypes + [vp]
     lib.mi_shade_rays_device.restype = C.c_int
+    lib.mi_occluded_rays.argtypes = [vp, C.c_uint32, vp, vp, C.c_float, C.c_float, vp, C.c_uint32, C.c_uint32, vp]
+    lib.mi_occluded_rays.restype = C.c_int
+    lib.mi_occluded_rays_device.argtypes = lib.mi_occluded_rays.argtypes + [vp]
+    lib.mi_occluded_rays_device.restype = C.c_int
     lib.mi_multi_create.argtypes = [C.c_int, C.POINTER(C.c_int), C.POINTER(vp)]
     lib.mi_multi_create.restype = C.c_int
     lib.mi_multi_create_loopback.argtypes = [C.c_int, C.c_int, C.POINTER(vp)]

@@ -36,6 +36,7 @@ hipError_t launch_wf_main(const WfArgs& a, uint32_t n_blocks, bool sig, bool gv,
 hipError_t launch_phong(const K1Args& a, uint32_t n_blocks, bool sig, hipStream_t stream);
 hipError_t launch_branch(const K1Args& a, uint32_t n_blocks, uint32_t path_samples, bool sig, hipStream_t stream);
 hipError_t launch_rq_intersect(const RqArgs& a, bool lds, bool gv, bool resolve, size_t lds_bytes, int n_cus, hipStream_t stream);
+hipError_t launch_rq_occluded(const RqOccArgs& a, bool lds, bool gv, size_t lds_bytes, int n_cus, hipStream_t stream);
 hipError_t launch_rq_shade(const RqShadeArgs& a, hipStream_t stream);
 hipError_t launch_walker(const WfArgs& a, const WalkerPlan& p, uint32_t n_blocks, bool* big_lds_enabled, hipStream_t stream);
 hipError_t launch_wf_filter_f(const WfArgs& a, uint32_t blocks_per_shard, hipStream_t stream);
@@ -841,6 +842,71 @@ extern "C" int mi_intersect_rays(mi_ctx* c, uint32_t n_rays, const float* origin
         if (out_flags) HIP_TRY(hipMemcpyAsync(out_flags + first, base + off_f, n * 4, hipMemcpyDeviceToHost, c->stream));
         if (out_uv) HIP_TRY(hipMemcpyAsync(out_uv + 2 * first, base + off_uv, n * 8, hipMemcpyDeviceToHost, c->stream));
         if (out_material) HIP_TRY(hipMemcpyAsync(out_material + first, base + off_m, n * sizeof(mi_material), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));          // the next chunk reuses the buffer
+        float ms = 0.0f;
+        HIP_TRY(hipEventElapsedTime(&ms, c->ev_start, c->ev_stop));
+        ms_sum += ms;
+    }
+    c->ms_summed = true; c->ms_sum = ms_sum;
+    return MI_OK;
+}
+
+// mi_occluded_rays: the any-hit query (rq_occluded).  Same shape as the intersect pair; ray_t_max (may be NULL) replaces t_max per ray.
+static int occluded_rays_device(mi_ctx* c, uint32_t n_rays, const float* origins, const float* dirs, float t_min, float t_max,
+                                const float* ray_t_max, uint32_t seed, uint32_t first_key, uint8_t* out_occluded, hipStream_t stream) {
+    RqOccArgs a;
+    a.S = c->S;
+    const bool lds = c->S.n_meshes > 0 && c->scene.lds_bytes <= 64u * 1024u && !c->tune.global_bvh;
+    a.lds_nodes = lds ? (uint32_t)c->S.n_nodes : 0u;
+    a.lds_tris = lds ? (uint32_t)c->S.n_tris : 0u;
+    a.seed_key = lowbias32(seed ^ 0x68e31da4u);
+    a.first_key = first_key; a.n_rays = n_rays; a.t_min = t_min; a.t_max = t_max;
+    a.origins = origins; a.dirs = dirs; a.ray_t_max = ray_t_max; a.out_occluded = out_occluded;
+    HIP_TRY(hipEventRecord(c->ev_start, stream));
+    HIP_TRY(launch_rq_occluded(a, lds, c->scene.gen_volumes, c->scene.lds_bytes, c->n_cus, stream));
+    HIP_TRY(hipEventRecord(c->ev_stop, stream));
+    c->ev_recorded = true; c->ms_summed = false;
+    return MI_OK;
+}
+
+static int check_occluded_args(mi_ctx* c, const float* origins, const float* dirs, float t_min, float t_max, const uint8_t* out_occluded) {
+    if (!c) return fail(MI_ERR_INVALID, "ctx is NULL");
+    if (!origins || !dirs || !out_occluded) return fail(MI_ERR_INVALID, "mi_occluded_rays: origins, dirs and out_occluded are required");
+    if (t_min != t_min || t_max != t_max) return fail(MI_ERR_INVALID, "mi_occluded_rays: t_min / t_max is NaN");
+    if (!c->have_scene) return fail(MI_ERR_NO_SCENE, "no scene uploaded");
+    return MI_OK;
+}
+
+extern "C" int mi_occluded_rays_device(mi_ctx* c, uint32_t n_rays, const float* origins, const float* dirs, float t_min, float t_max,
+                                       const float* ray_t_max, uint32_t seed, uint32_t first_key, uint8_t* out_occluded, void* stream) {
+    MI_TRY(check_occluded_args(c, origins, dirs, t_min, t_max, out_occluded));
+    if (n_rays == 0) return MI_OK;
+    HIP_TRY(hipSetDevice(c->device));
+    return occluded_rays_device(c, n_rays, origins, dirs, t_min, t_max, ray_t_max, seed, first_key, out_occluded, (hipStream_t)stream);
+}
+
+extern "C" int mi_occluded_rays(mi_ctx* c, uint32_t n_rays, const float* origins, const float* dirs, float t_min, float t_max,
+                                const float* ray_t_max, uint32_t seed, uint32_t first_key, uint8_t* out_occluded) {
+    MI_TRY(check_occluded_args(c, origins, dirs, t_min, t_max, out_occluded));
+    if (ray_t_max)
+        for (size_t i = 0; i < n_rays; i++)
+            if (ray_t_max[i] != ray_t_max[i]) return fail(MI_ERR_INVALID, "mi_occluded_rays: ray_t_max[%zu] is NaN", i);
+    if (n_rays == 0) return MI_OK;
+    HIP_TRY(hipSetDevice(c->device));
+    const size_t chunk = std::min<size_t>(n_rays, kRqChunk);
+    const size_t off_o = 0, off_d = off_o + chunk * 12, off_t = off_d + chunk * 12, off_out = off_t + chunk * 4, total = off_out + chunk;
+    MI_TRY(ensure(&c->d_rq, &c->rq_bytes, total));
+    char* base = (char*)c->d_rq;
+    float ms_sum = 0.0f;
+    for (size_t first = 0; first < n_rays; first += chunk) {
+        const size_t n = std::min<size_t>(chunk, (size_t)n_rays - first);
+        HIP_TRY(hipMemcpyAsync(base + off_o, origins + 3 * first, n * 12, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipMemcpyAsync(base + off_d, dirs + 3 * first, n * 12, hipMemcpyHostToDevice, c->stream));
+        if (ray_t_max) HIP_TRY(hipMemcpyAsync(base + off_t, ray_t_max + first, n * 4, hipMemcpyHostToDevice, c->stream));
+        MI_TRY(occluded_rays_device(c, (uint32_t)n, (const float*)(base + off_o), (const float*)(base + off_d), t_min, t_max,
+                                    ray_t_max ? (const float*)(base + off_t) : nullptr, seed, first_key + (uint32_t)first,
+                                    (uint8_t*)(base + off_out), c->stream));
+        HIP_TRY(hipMemcpyAsync(out_occluded + first, base + off_out, n, hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(hipStreamSynchronize(c->stream));          // the next chunk reuses the buffer
         float ms = 0.0f;
         HIP_TRY(hipEventElapsedTime(&ms, c->ev_start, c->ev_stop));

@@ -242,6 +242,17 @@ struct RqArgs {
     float*    out_uv;                // [n][2]
     uint32_t* out_material;          // [n][10] words of mi_material
 };
+// rq_occluded (mi_occluded_rays): the any-hit query.  ray_t_max, when given, replaces t_max ray by ray.
+struct RqOccArgs {
+    DScene  S;
+    uint32_t lds_nodes, lds_tris;
+    uint32_t seed_key, first_key, n_rays;
+    float    t_min, t_max;
+    const float* origins;            // [n][3]
+    const float* dirs;               // [n][3], used as given (not normalised)
+    const float* ray_t_max;          // [n] or nullptr
+    uint8_t* out_occluded;           // [n] 0 / 1
+};
 struct RqShadeArgs {
     DScene  S;
     uint32_t seed_key, first_key, n_rays;

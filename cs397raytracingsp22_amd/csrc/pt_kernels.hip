@@ -1543,6 +1543,238 @@ __global__ __launch_bounds__(kBlock) void rq_intersect(RqArgs A) {
     }
 }
 
+// ---- rq_occluded: the any-hit query (mi_occluded_rays).  occluded[i] <=> Scene::intersect_ray(ray_i, t_min, t_max_i) (tracing.rs:326-346)
+// is Some, i.e. some entry of Scene.objects returns Some from its own intersect_ray over that interval.  Exact, for three reasons:
+//   1. tracing.rs:333-336 only ever replaces `best_hit` by another Some: it never goes back to None.  The answer is the OR over the objects
+//      whatever the order they are evaluated in — NaN distances included, so the kind-grouped order is no deviation for this query.
+//   2. BVHNode::intersect_ray (geometry.rs:94-119; traverse_mesh above restates it) keeps its running bound `best_t` AT t_max until the
+//      first accepted leaf hit.  A walk that stops at that leaf has made exactly the reference's box and triangle decisions up to there;
+//      if the reference accepts no leaf, neither does this walk.
+//   3. Only ConvexVolume::intersect_ray reads the RNG (geometry.rs:517), one draw per volume whose boundary the ray's line crosses inside
+//      the interval.  The volumes are evaluated in Scene.objects order among themselves (the list keeps that order within a kind), so every
+//      volume sees the draw the reference gives it; a lane that is already occluded may skip the volumes left, because nothing observable
+//      depends on their draws.  Ray i draws from (seed, first_key + i, 0), as in rq_intersect.
+// Order tried: list Triangles, Spheres, Planes, ConvexVolumes, then the meshes — the cheap tests first, so that a wave whose rays are all
+// stopped by the list never enters a tree.  Each lane carries `done`; the wave leaves when ballot(!done) == 0, voted between the kind groups,
+// per pair of Triangles, per Sphere / Plane / Volume and per mesh.  No refill of idle lanes, no compaction.
+
+// any-hit form of traverse_mesh: same node order, the interval's own t_max as the bound of every box and triangle test (fact 2), and the
+// lane leaves at its first accepted triangle.  `active` = false: the lane walks nothing.
+template <class BVH>
+__device__ __forceinline__ bool occluded_mesh(const BVH& B, int node_begin, int node_end, int tri_begin, bool active,
+                                              f3 o, f3 d, float t_min, float t_max) {
+    f3 inv_d; rcp3_exact(d.x, d.y, d.z, inv_d.x, inv_d.y, inv_d.z);      // geometry.rs:57
+    bool found = false;
+    int i = active ? node_begin : node_end;
+    while (i < node_end) {
+        int leaf_tri = -1;
+        while (i < node_end) {
+            float4 n0, n1;
+            B.node(i, n0, n1);
+            int tri = __float_as_int(n1.w);
+            if (tri >= 0) { leaf_tri = tri; break; }                       // geometry.rs:95
+            bool hit = slab(mk3(n0.x, n0.y, n0.z), mk3(n1.x, n1.y, n1.z), o, inv_d, t_min, t_max);    // :103, best_t == t_max so far
+            i = hit ? i + 1 : __float_as_int(n0.w);
+        }
+        if (leaf_tri >= 0) {
+            f3 a, e1, e2;
+            B.tri(tri_begin + leaf_tri, a, e1, e2);
+            float t, u, v;
+            found = tri_t(o, d, a, e1, e2, t_min, t_max, t, u, v);         // :97
+            i = found ? node_end : i + 1;
+        }
+    }
+    return found;
+}
+
+// `boundary.intersect_ray(..)` of a ConvexVolume is a closest-hit question (its distance is used): boundary_hit as it stands.
+// ConvexVolume::intersect_ray geometry.rs:502-526 -> Some / None, one draw where the reference draws one.
+template <bool GV, class OP>
+__device__ __forceinline__ bool occluded_volume(const DScene& S, OP ob, f3 o, f3 d, float t_min, float t_max, Rng& rng) {
+    const float F32_MIN = -3.40282347e+38f, F32_MAX = 3.40282347e+38f;
+    float t_entr, t_exit;
+    bool hit = false;
+    if (boundary_hit<GV>(S, ob, o, d, F32_MIN, F32_MAX, t_entr) &&
+        boundary_hit<GV>(S, ob, o, d, t_entr + 0.0001f, F32_MAX, t_exit)) {
+        if (!(t_exit < t_min || t_entr > t_max)) {
+            const float t_start = fmaxf(t_entr, t_min);
+            const float t_end = fminf(t_exit, t_max);
+            const float dist_in_volume = t_end - t_start;
+            const float dist_before_scatter = ob->f[5] * pt_logf(gen01(rng));       // :517, f[5] = -1/density
+            hit = dist_before_scatter < dist_in_volume;
+        }
+    }
+    return hit;
+}
+
+// The kind-grouped list, any-hit.  Returns with `done` set for every lane some list entry stops; returns early (wave-uniform) once no lane
+// of the wave is left.  TOP: the top-level tree over the small Triangles of a long list (intersect_list<.., TOP> above) with the same
+// padded-box bound and the same fallback to the plain loop for a wave that holds an uncovered ray; the window is not shrunk (there is no
+// closest hit to shrink it to) and a lane stops at its first accepted leaf triangle.
+template <bool GV, bool TOP>
+__device__ __forceinline__ void occluded_list(const DScene& S, f3 o, f3 d, float t_min, float t_max, Rng& rng, bool& done) {
+    auto L = S.list;
+    int k = 0;
+    {   // Triangle::intersect_ray geometry.rs:431-450, two per trip as in intersect_list
+        const int end = TOP ? S.n_list_lin : S.n_list_tri;
+        for (; k + 1 < end; k += 2) {
+            if (__builtin_amdgcn_ballot_w64(!done) == 0ull) return;
+            auto r0 = &L[k]; auto r1 = &L[k + 1];
+            const f3 a0 = ld3(r0->f), p0 = ld3(r0->f + 3), q0 = ld3(r0->f + 6), a1 = ld3(r1->f), p1 = ld3(r1->f + 3), q1 = ld3(r1->f + 6);
+            float t0, u0, v0, t1, u1, v1;
+            const bool ok0 = tri_t(o, d, a0, p0, q0, t_min, t_max, t0, u0, v0);
+            const bool ok1 = tri_t(o, d, a1, p1, q1, t_min, t_max, t1, u1, v1);
+            done = done | ok0 | ok1;
+        }
+        for (; k < end; k++) {
+            auto r0 = &L[k];
+            float t0, u0, v0;
+            done = done | tri_t(o, d, ld3(r0->f), ld3(r0->f + 3), ld3(r0->f + 6), t_min, t_max, t0, u0, v0);
+        }
+    }
+    if (__builtin_amdgcn_ballot_w64(!done) == 0ull) return;
+    if (TOP) {
+        auto F = &S.meshf[S.top_meshf];
+        float rho, dt;
+        const bool covered = two_stage_pad(F, o, d, t_max, rho, dt);
+        if (__builtin_amdgcn_ballot_w64(!covered & !done) != 0ull) {
+            for (k = S.n_list_lin; k < S.n_list_tri; k++) {               // the plain loop for this wave
+                if ((k & 3) == 0 && __builtin_amdgcn_ballot_w64(!done) == 0ull) return;
+                auto r0 = &L[k];
+                float t0, u0, v0;
+                done = done | tri_t(o, d, ld3(r0->f), ld3(r0->f + 3), ld3(r0->f + 6), t_min, t_max, t0, u0, v0);
+            }
+        } else {
+            cf4_ptr FN = (cf4_ptr)S.fnodes;
+            cf4_ptr FT = (cf4_ptr)S.ftris;
+            f3 inv;
+            rcp3_exact(d.x, d.y, d.z, inv.x, inv.y, inv.z);
+            const float t_lo = t_min - dt, t_hi = t_max + dt;
+            const float4 grid = make_float4(F->qs, F->qbx, F->qby, F->qbz);
+            const int fend = F->fnode_end, ftb = F->ftri_begin;
+            int fi = done ? fend : F->fnode_begin;
+            bool atleaf = false;
+            float4 c = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+            if (fi < fend) c = FN[fi];
+            while (__builtin_amdgcn_ballot_w64(fi < fend) != 0ull) {
+#pragma unroll
+                for (int j = 0; j < 6; j++) {
+                    const bool act = (fi < fend) & !atleaf;
+                    f3 bmin, bmax;
+                    fq_box(c, grid, bmin, bmax);
+                    const bool hit = slab_padded(bmin, bmax, o, rho, inv, t_lo, t_hi);
+                    const int link = __float_as_int(c.w);
+                    const bool leaf = link < 0;
+                    const bool stop = act & hit & leaf;
+                    const int nxt = (hit | leaf) ? fi + 1 : link;            // a leaf's successor is the next node either way
+                    atleaf = atleaf | stop;
+                    const bool move = act & !stop;
+                    fi = move ? nxt : fi;
+                    if (move & (fi < fend)) c = FN[fi];
+                }
+                const int n_leaf = __popcll(__builtin_amdgcn_ballot_w64(atleaf));
+                const int n_walk = __popcll(__builtin_amdgcn_ballot_w64((fi < fend) & !atleaf));
+                if (n_leaf * 3 >= n_walk) {
+                    if (atleaf) {
+                        const int payload = __float_as_int(c.w) & 0x7fffffff;
+                        const int first = ftb + (payload >> 3), count = (payload & 7) + 1;
+                        bool ok = false;
+                        for (int j = 0; j < count && !ok; j++) {
+                            const float4 t0 = FT[3 * (first + j)], t1 = FT[3 * (first + j) + 1], t2 = FT[3 * (first + j) + 2];
+                            float t, u, v;
+                            ok = tri_t(o, d, mk3(t0.x, t0.y, t0.z), mk3(t1.x, t1.y, t1.z), mk3(t2.x, t2.y, t2.z), t_min, t_max, t, u, v);
+                        }
+                        done = done | ok;
+                        fi = ok ? fend : fi + 1;
+                        atleaf = false;
+                        if (fi < fend) c = FN[fi];
+                    }
+                }
+            }
+        }
+        k = S.n_list_tri;
+        if (__builtin_amdgcn_ballot_w64(!done) == 0ull) return;
+    }
+    {   // Sphere::intersect_ray geometry.rs:395-413: the whole test — discriminant, root choice (:407) and window (:409) — staged as in
+        // intersect_list: the discriminant for every sphere, the tail once some lane needs its one-entry stash again and once at the end.
+        // An occluded lane is no candidate any more.
+        const int end = k + S.n_list_sphere;
+        if (k < end) {
+            const float a = mag2(d), two_a = 2.0f * a;                    // :398, and the divisor of :405-406
+            float sb = 0.0f, sdisc = 0.0f;
+            bool full = false;
+            auto finish = [&]() {
+                const float sq = sqrtf(sdisc);
+                const float t1 = (-sb - sq) / two_a, t2 = (-sb + sq) / two_a;     // :405-406
+                const float t = (t1 >= t_min) ? t1 : t2;                          // :407
+                done = done | (full & !((t < t_min) | (t > t_max)));              // :409
+                full = false;
+            };
+            for (; k < end; k++) {
+                if (__builtin_amdgcn_ballot_w64(!done) == 0ull) return;
+                auto ob = &L[k];
+                const f3 f = o - ld3(ob->f);                                      // :397
+                const float b = 2.0f * dot(f, d);                                 // :399
+                const float c = mag2(f) - ob->f[4];                               // :400, f[4] = radius * radius
+                const float disc = b * b - 4.0f * a * c;                          // :401
+                const bool cand = !(disc < 0.0f) & !done;                         // :402
+                if (__builtin_amdgcn_ballot_w64(cand & full) != 0ull) finish();
+                sb = cand ? b : sb; sdisc = cand ? disc : sdisc; full = full | cand;
+            }
+            if (__builtin_amdgcn_ballot_w64(full) != 0ull) finish();
+        }
+    }
+    {   // Plane (geometry.rs:474-489), then ConvexVolume (geometry.rs:502-526) in Scene.objects order among themselves (fact 3)
+        const int pend = k + S.n_list_plane;
+        for (; k < pend; k++) {
+            if (__builtin_amdgcn_ballot_w64(!done) == 0ull) return;
+            float t;
+            done = done | plane_t(&L[k], o, d, t_min, t_max, t);
+        }
+        const int vend = k + S.n_list_volume;
+        for (; k < vend; k++) {
+            if (__builtin_amdgcn_ballot_w64(!done) == 0ull) return;
+            if (!done) done = occluded_volume<GV>(S, &L[k], o, d, t_min, t_max, rng);
+        }
+    }
+}
+
+template <bool LDS, bool GV, bool TOP>
+__global__ __launch_bounds__(kBlock) void rq_occluded(RqOccArgs A) {
+    const DScene& S = A.S;
+    Bvh<LDS> B;
+    if (LDS) {
+        cf4_ptr gn = (cf4_ptr)S.nodes;
+        cf4_ptr gt = (cf4_ptr)S.tris;
+        const int nn = (int)A.lds_nodes * 2, nt = (int)A.lds_tris * 3;
+        for (int k = threadIdx.x; k < nn; k += kBlock) k1_lds[k] = gn[k];
+        for (int k = threadIdx.x; k < nt; k += kBlock) k1_lds[nn + k] = gt[k];
+        __syncthreads();
+    }
+    bvh_bind(B, S, (int)A.lds_nodes * 2);
+    const float t_min = A.t_min;
+    const uint32_t n_chunks = (A.n_rays + (uint32_t)kBlock - 1u) / (uint32_t)kBlock;
+    for (uint32_t chunk = blockIdx.x; chunk < n_chunks; chunk += gridDim.x) {
+        const uint32_t i = chunk * (uint32_t)kBlock + threadIdx.x;
+        const bool live = i < A.n_rays;
+        const size_t r = live ? (size_t)i : 0;
+        const f3 o = mk3(A.origins[3 * r], A.origins[3 * r + 1], A.origins[3 * r + 2]);
+        const f3 d = mk3(A.dirs[3 * r], A.dirs[3 * r + 1], A.dirs[3 * r + 2]);
+        const float t_max = A.ray_t_max ? A.ray_t_max[r] : A.t_max;
+        Rng rng;
+        rng_init(rng, A.seed_key, A.first_key + (uint32_t)r, 0u);
+        bool done = !live;                                                  // idle lanes of the last chunk ask nothing
+        occluded_list<GV, TOP>(S, o, d, t_min, t_max, rng, done);
+        for (int m = 0; m < S.n_meshes; m++) {                              // geometry.rs:301-314
+            if (__builtin_amdgcn_ballot_w64(!done) == 0ull) break;         // a mesh no lane of the wave needs
+            auto M = &S.meshes[m];
+            const f3 oo = xform_point(M->inv_transform, o), od = xform_vector(M->inv_transform, d);
+            done = done | occluded_mesh(B, M->node_begin, M->node_end, M->tri_begin, !done, oo, od, t_min, t_max);
+        }
+        if (live) A.out_occluded[i] = done ? (uint8_t)1 : (uint8_t)0;
+    }
+}
+
 // rq_shade: Scene::shade_ray(ray, 0) (tracing.rs:300-324) as written for caller-supplied rays: pt_branch's per-sample body on ray i with
 // the stream (seed, first_key + i, 0).  A completeness path like pt_branch (per-lane frame stack in scratch, BVH from global memory),
 // bit-identical to the CPU restatement for every path_samples; not tuned.
@@ -3271,6 +3503,25 @@ hipError_t launch_rq_intersect(const RqArgs& a, bool lds, bool gv, bool resolve,
     const uint64_t resident = (uint64_t)per_cu * (uint64_t)(n_cus > 0 ? n_cus : 1);
     const uint32_t n_blocks = (uint32_t)(resident < (uint64_t)n_chunks ? resident : (uint64_t)n_chunks);
     RqArgs args = a;
+    void* params[] = { (void*)&args };
+    return hipLaunchKernel(fn, dim3(n_blocks), dim3(kBlock), params, dyn, stream);
+}
+hipError_t launch_rq_occluded(const RqOccArgs& a, bool lds, bool gv, size_t lds_bytes, int n_cus, hipStream_t stream) {
+    const bool top = a.S.top_meshf >= 0;
+    const size_t dyn = lds ? lds_bytes : 0;
+    const uint32_t n_chunks = (a.n_rays + (uint32_t)kBlock - 1u) / (uint32_t)kBlock;
+    const void* fn = nullptr;
+#define PT_RQ_PICK(L, G, T) fn = (const void*)&rq_occluded<L, G, T>
+#define PT_RQ_PICK2(L, G) do { if (top) PT_RQ_PICK(L, G, true); else PT_RQ_PICK(L, G, false); } while (0)
+    if (lds) { if (gv) PT_RQ_PICK2(true, true); else PT_RQ_PICK2(true, false); }
+    else     { if (gv) PT_RQ_PICK2(false, true); else PT_RQ_PICK2(false, false); }
+#undef PT_RQ_PICK2
+#undef PT_RQ_PICK
+    int per_cu = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, kBlock, dyn) != hipSuccess || per_cu < 1) { (void)hipGetLastError(); per_cu = 1; }
+    const uint64_t resident = (uint64_t)per_cu * (uint64_t)(n_cus > 0 ? n_cus : 1);
+    const uint32_t n_blocks = (uint32_t)(resident < (uint64_t)n_chunks ? resident : (uint64_t)n_chunks);
+    RqOccArgs args = a;
     void* params[] = { (void*)&args };
     return hipLaunchKernel(fn, dim3(n_blocks), dim3(kBlock), params, dyn, stream);
 }

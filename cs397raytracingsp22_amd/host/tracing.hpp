@@ -105,6 +105,23 @@ struct Scene : Intersectable {                         // tracing.rs:213-218; `i
         return h;
     }
 
+    // Is Scene::intersect_ray(ray_i, t_min, t_max_i) (tracing.rs:326-346) Some?  The any-hit query through mi_occluded_rays -> [n] bytes, 0 / 1.
+    // ray_t_max: empty, or one t_max per ray (replaces t_max).  Directions are used as given: the segment a -> b is origin a, dir b - a,
+    // [eps, 1 - eps].  Ray i draws from the stream (seed, first_key + i, 0).
+    std::vector<uint8_t> occluded_rays(const std::vector<float>& origins, const std::vector<float>& dirs, float t_min = 0.001f,
+                                       float t_max = INFINITY, const std::vector<float>& ray_t_max = {}, uint32_t seed = 1,
+                                       uint32_t first_key = 0, int device = 0) const {
+        if (origins.size() != dirs.size() || origins.size() % 3 != 0) throw std::runtime_error("mi_rt: origins and dirs must both be [n][3]");
+        const size_t n = origins.size() / 3;
+        if (!ray_t_max.empty() && ray_t_max.size() != n) throw std::runtime_error("mi_rt: ray_t_max must hold one value per ray");
+        std::vector<uint8_t> occluded(n);
+        with_context(device, [&](mi_ctx* ctx) {
+            return mi_occluded_rays(ctx, (uint32_t)n, origins.data(), dirs.data(), t_min, t_max, ray_t_max.empty() ? nullptr : ray_t_max.data(),
+                                    seed, first_key, occluded.data());
+        });
+        return occluded;
+    }
+
     // Scene::shade_ray (tracing.rs:300-324) at level 0 for n rays through mi_shade_rays -> [n][3] radiance; the camera supplies path_depth,
     // path_samples and max_trace_dist.
     std::vector<float> shade_rays(const std::vector<float>& origins, const std::vector<float>& dirs, uint32_t seed = 1, uint32_t first_key = 0,

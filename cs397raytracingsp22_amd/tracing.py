@@ -99,6 +99,26 @@ def check_rays(origins, dirs, t_min: float = 0.001, t_max: float = float("inf"))
     return o, d, t_min, t_max
 
 
+def check_ray_t_max(ray_t_max, n_rays: int):
+    """Input checking of mi_occluded_rays' per-ray interval ends (no GPU needed): None stays None; otherwise a C-contiguous float32
+    array of shape (n_rays,) without NaN (+inf is legal).  Anything that is not already a real floating-point array or sequence of
+    numbers is refused rather than converted."""
+    if ray_t_max is None:
+        return None
+    a = np.asarray(ray_t_max)
+    if a.dtype.kind not in "fiu":
+        raise ValueError(f"ray_t_max must hold real numbers, got dtype {a.dtype}")
+    if a.ndim != 1:
+        raise ValueError(f"ray_t_max must have shape (n,), got {a.shape}")
+    if len(a) != n_rays:
+        raise ValueError(f"ray_t_max holds {len(a)} values for {n_rays} rays")
+    with np.errstate(over="ignore"):                     # a float64 beyond f32's range becomes +-inf, which is legal
+        a = np.ascontiguousarray(a, dtype=np.float32)
+    if np.isnan(a).any():
+        raise ValueError("ray_t_max must not hold NaN")
+    return a
+
+
 class Context:
     """One mi_ctx = one GPU (one process per GPU: pass LOCAL_RANK)."""
 
@@ -250,6 +270,29 @@ class Context:
         abi.check(self._lib.mi_intersect_rays_device(self._h, n_rays, d_origins, d_dirs, t_min, t_max, seed, first_key & 0xffffffff,
                                                      d_object, d_distance, d_hitpoint, d_normal, d_flags, d_uv, d_material, stream))
 
+    def occluded_rays(self, origins, dirs, t_min: float = 0.001, t_max: float = float("inf"), ray_t_max=None, seed: int = 1,
+                      first_key: int = 0) -> np.ndarray:
+        """mi_occluded_rays: for every ray, is Scene::intersect_ray(ray, t_min, t_max) Some?  -> [n] bool.  The any-hit query: a ray is
+        done at its first accepted hit.  `ray_t_max` ([n] floats) replaces `t_max` ray by ray.  Directions are used as given, so the
+        segment a -> b is origins = a, dirs = b - a, t_min = eps, t_max = 1 - eps.  Ray i draws from the stream (seed, first_key + i, 0)."""
+        o, d, t_min, t_max = check_rays(origins, dirs, t_min, t_max)
+        tm = check_ray_t_max(ray_t_max, len(o))
+        out = np.zeros(len(o), np.uint8)
+        abi.check(self._lib.mi_occluded_rays(self._h, len(o), o.ctypes.data, d.ctypes.data, t_min, t_max,
+                                             tm.ctypes.data if tm is not None else None, seed, first_key & 0xffffffff, out.ctypes.data))
+        return out != 0
+
+    def occluded_rays_device(self, n_rays: int, d_origins: int, d_dirs: int, d_occluded: int, d_ray_t_max: Optional[int] = None,
+                             t_min: float = 0.001, t_max: float = float("inf"), seed: int = 1, first_key: int = 0,
+                             stream: Optional[int] = None):
+        """mi_occluded_rays_device: raw device pointers (ints; d_occluded [n] bytes, d_ray_t_max [n] f32 or None), one kernel queued on
+        `stream`, no synchronisation.  Only the scalars are checked: a NaN in a device ray_t_max gives an unspecified answer for that ray."""
+        t_min, t_max = float(t_min), float(t_max)
+        if t_min != t_min or t_max != t_max:
+            raise ValueError("t_min / t_max must not be NaN")
+        abi.check(self._lib.mi_occluded_rays_device(self._h, n_rays, d_origins, d_dirs, t_min, t_max, d_ray_t_max, seed,
+                                                    first_key & 0xffffffff, d_occluded, stream))
+
     def shade_rays(self, cam: Camera, origins, dirs, seed: int = 1, first_key: int = 0) -> np.ndarray:
         """mi_shade_rays: Scene::shade_ray at level 0 for every ray -> [n, 3] f32 radiance.  `cam` supplies path_depth,
         path_samples and max_trace_dist."""
@@ -374,6 +417,18 @@ class Scene:                         # tracing.rs:213-218
         try:
             ctx.upload(self.flatten())
             return ctx.intersect_rays(o, d, t_min, t_max, seed=seed, first_key=first_key, resolve=resolve)
+        finally:
+            ctx.close()
+
+    def occluded_rays(self, origins, dirs, t_min: float = 0.001, t_max: float = float("inf"), ray_t_max=None, seed: int = 1,
+                      first_key: int = 0, device: int = 0) -> np.ndarray:
+        """Is `Scene::intersect_ray(ray, t_min, t_max)` (tracing.rs:326-346) Some, for a batch of rays: flatten -> upload -> one query."""
+        o, d, t_min, t_max = check_rays(origins, dirs, t_min, t_max)
+        tm = check_ray_t_max(ray_t_max, len(o))
+        ctx = Context(device)
+        try:
+            ctx.upload(self.flatten())
+            return ctx.occluded_rays(o, d, t_min, t_max, ray_t_max=tm, seed=seed, first_key=first_key)
         finally:
             ctx.close()
 

@@ -322,6 +322,27 @@ int  mi_shade_rays(mi_ctx* ctx, const mi_camera_desc* cam, uint32_t n_rays, cons
 int  mi_shade_rays_device(mi_ctx* ctx, const mi_camera_desc* cam, uint32_t n_rays, const float* origins, const float* dirs,
                           uint32_t seed, uint32_t first_key, float* out_rgb, void* stream);
 
+/* ---- occlusion queries: "is anything in the way?" (added within ABI version 5 like the four above: detect by symbol lookup) ----
+ * mi_occluded_rays: out_occluded[i] = 1 exactly when Scene::intersect_ray(ray_i, t_min, t_max_i) (tracing.rs:326-346) returns Some,
+ *   that is when some entry of Scene.objects returns Some from its own intersect_ray over that interval; 0 otherwise.  The same answer
+ *   as `mi_intersect_rays(...).out_object >= 0`, but a ray is done at its first accepted hit (any-hit: shadow rays, visibility between
+ *   points, ambient occlusion, baking).  Exact, not approximate: `best_hit` never goes back to None, so the answer is the OR over the
+ *   objects in any order — also for non-finite rays.
+ * ray_t_max: NULL, then every ray uses t_max; or [n_rays] floats that REPLACE t_max ray by ray (t_max is then ignored apart from its
+ *   NaN check).  +infinity is legal.  The host form refuses a NaN t_min / t_max and a NaN anywhere in ray_t_max with MI_ERR_INVALID.
+ *   The _device form checks only the scalars: a NaN entry of a device ray_t_max gives an UNSPECIFIED answer for that ray (0 or 1) and
+ *   never faults or disturbs another ray.
+ * Directions are used as given, NOT normalised, and the interval is in units of |dir|: the segment from a to b is
+ *   origin = a, dir = b - a, [t_min, t_max] = [eps, 1 - eps]; a unit direction towards a light at distance L takes ray_t_max = L - eps.
+ * Ray i draws from the RNG stream (seed, first_key + i, 0) as in mi_intersect_rays (only a ConvexVolume reads it), so a batch may be
+ *   split over calls with first_key advanced.  out_occluded: [n_rays] bytes, 0 or 1 (REQUIRED).
+ * Host / _device forms, chunking, n_rays == 0, the buffers of mi_reserve and mi_last_kernel_ms: as for mi_intersect_rays.  NULL origins,
+ *   dirs or out_occluded are MI_ERR_INVALID, a context without a scene is MI_ERR_NO_SCENE. */
+int  mi_occluded_rays(mi_ctx* ctx, uint32_t n_rays, const float* origins, const float* dirs, float t_min, float t_max,
+                      const float* ray_t_max, uint32_t seed, uint32_t first_key, uint8_t* out_occluded);
+int  mi_occluded_rays_device(mi_ctx* ctx, uint32_t n_rays, const float* origins, const float* dirs, float t_min, float t_max,
+                             const float* ray_t_max, uint32_t seed, uint32_t first_key, uint8_t* out_occluded, void* stream);
+
 /* Size and allocate the wavefront pipeline's HBM buffers (path state, sample slots) for
  * this camera with the image shared by `world` ranks, so that the first render does not pay the
  * allocation (about 110 GB for a whole 1080p / 256 spp frame on one GPU).  `max_state_bytes` as in

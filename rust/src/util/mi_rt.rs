@@ -79,6 +79,11 @@ extern "C" {
                          seed: u32, first_key: u32, out_rgb: *mut f32) -> c_int;
     pub fn mi_shade_rays_device(ctx: *mut mi_ctx, cam: *const mi_camera_desc, n_rays: u32, origins: *const f32, dirs: *const f32,
                                 seed: u32, first_key: u32, out_rgb: *mut f32, stream: *mut c_void) -> c_int;
+    // occlusion queries (any-hit; added within ABI 5 like the ray queries).  ray_t_max: null, or one t_max per ray
+    pub fn mi_occluded_rays(ctx: *mut mi_ctx, n_rays: u32, origins: *const f32, dirs: *const f32, t_min: f32, t_max: f32,
+                            ray_t_max: *const f32, seed: u32, first_key: u32, out_occluded: *mut u8) -> c_int;
+    pub fn mi_occluded_rays_device(ctx: *mut mi_ctx, n_rays: u32, origins: *const f32, dirs: *const f32, t_min: f32, t_max: f32,
+                                   ray_t_max: *const f32, seed: u32, first_key: u32, out_occluded: *mut u8, stream: *mut c_void) -> c_int;
     pub fn mi_reserve(ctx: *mut mi_ctx, cam: *const mi_camera_desc, world: i32, max_state_bytes: u64) -> c_int;
     pub fn mi_last_pipeline_ms(ctx: *mut mi_ctx, out8: *mut f32) -> c_int;
     pub fn mi_last_pipeline_counts(ctx: *mut mi_ctx, out8: *mut u64) -> c_int;

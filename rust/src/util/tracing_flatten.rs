@@ -109,6 +109,22 @@ impl Scene {
         (object, distance)
     }
 
+    /// Is `Scene::intersect_ray(ray_i, t_min, t_max_i)` (tracing.rs:326-346) Some?  The any-hit query on the GPU (mi_occluded_rays): a ray
+    /// is done at its first accepted hit.  `ray_t_max`, when given, holds one t_max per ray and replaces `t_max`.  Directions are used as
+    /// given: the segment a -> b is origin a, dir b - a, [eps, 1 - eps].  Ray i draws from the stream (seed, first_key + i, 0).
+    pub fn occluded_rays(&self, origins: &[[f32; 3]], dirs: &[[f32; 3]], t_min: f32, t_max: f32, ray_t_max: Option<&[f32]>, seed: u32,
+                         first_key: u32) -> Vec<bool> {
+        assert_eq!(origins.len(), dirs.len(), "mi_rt: origins and dirs differ in length");
+        let n = origins.len();
+        if let Some(t) = ray_t_max { assert_eq!(t.len(), n, "mi_rt: ray_t_max must hold one value per ray"); }
+        let mut occluded = vec![0u8; n];
+        let (po, pd) = (origins.as_ptr() as *const f32, dirs.as_ptr() as *const f32);
+        let pt = ray_t_max.map_or(std::ptr::null(), |t| t.as_ptr());
+        let pout = occluded.as_mut_ptr();
+        self.with_gpu_scene(|ctx| unsafe { mi_rt::mi_occluded_rays(ctx, n as u32, po, pd, t_min, t_max, pt, seed, first_key, pout) });
+        occluded.into_iter().map(|b| b != 0).collect()
+    }
+
     /// Scene::shade_ray (tracing.rs:300-324) at level 0 for a batch of rays on the GPU (mi_shade_rays): the radiance per ray; the camera
     /// supplies path_depth, path_samples and max_trace_dist.
     pub fn shade_rays(&self, origins: &[[f32; 3]], dirs: &[[f32; 3]], seed: u32, first_key: u32) -> Vec<[f32; 3]> {

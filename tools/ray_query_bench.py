@@ -9,7 +9,16 @@ output array) and off (the visibility form: object and distance only):
            unit vector (one per camera hit; the misses are dropped)
 Per set: 5 warm-up calls, then --calls timed calls (default 20) through the device entry point on device-resident arrays.  Two rates
 are printed per row, from the median call: Mrays/s from mi_last_kernel_ms (HIP events around the kernel) and from the wall clock around
-call + synchronise.  One JSON line per row; no pass / fail bar.  Needs a GPU: there is no CPU fallback."""
+call + synchronise.  One JSON line per row; no pass / fail bar.  Needs a GPU: there is no CPU fallback.
+
+--mode occlusion compares the any-hit query (mi_occluded_rays_device) with the visibility form of mi_intersect_rays_device on the same
+rays, in the same process and context, the two ALTERNATING call by call (5 warm-up pairs, then --calls timed pairs; median / min / max of
+mi_last_kernel_ms for each).  Ray sets: `camera` and `bounce` as above, and
+  shadow   origin = the library's camera hitpoint, direction = the unit vector towards the fixed point (0, 5.9, 0) just under the ceiling
+           light, per-ray ray_t_max = the distance to that point - 1e-3.  The visibility form has one scalar interval per call and would
+           need one call per distinct distance (about as many as rays), so it runs ONCE with t_max = +inf.  A longer interval can only
+           add box and triangle work to a closest-hit walk, so on this row the comparison is generous to the any-hit query, and the two
+           do not answer the same question; the visibility row says so ("t_max": "inf (scalar)")."""
 import argparse
 import json
 import os
@@ -66,6 +75,57 @@ def measure(ctx, o, d, t_max, resolve, calls, warmup):
     return float(np.median(kernel_ms)), float(np.median(wall_ms)), float(np.min(kernel_ms)), float(np.max(kernel_ms)), hits
 
 
+def measure_pair(ctx, o, d, t_max, ray_t_max, calls, warmup):
+    """The any-hit query and the visibility form on the same device-resident rays, alternating.  Returns two dicts of kernel times."""
+    dev = torch.device("cuda:0")
+    n = len(o)
+    t_o, t_d = torch.from_numpy(o).to(dev), torch.from_numpy(d).to(dev)
+    t_tm = torch.from_numpy(ray_t_max).to(dev) if ray_t_max is not None else None
+    t_occ = torch.empty(n, dtype=torch.uint8, device=dev)
+    t_obj, t_t = torch.empty(n, dtype=torch.int32, device=dev), torch.empty(n, dtype=torch.float32, device=dev)
+    vis_t_max = float("inf") if ray_t_max is not None else t_max
+    torch.cuda.synchronize()
+    occ_ms, vis_ms = [], []
+    for k in range(warmup + calls):
+        ctx.occluded_rays_device(n, t_o.data_ptr(), t_d.data_ptr(), t_occ.data_ptr(), t_tm.data_ptr() if t_tm is not None else None,
+                                 t_min=0.001, t_max=t_max, seed=1)
+        torch.cuda.synchronize()
+        a = ctx.last_kernel_ms()
+        ctx.intersect_rays_device(n, t_o.data_ptr(), t_d.data_ptr(), t_obj.data_ptr(), t_t.data_ptr(), t_min=0.001, t_max=vis_t_max, seed=1)
+        torch.cuda.synchronize()
+        b = ctx.last_kernel_ms()
+        if k >= warmup:
+            occ_ms.append(a)
+            vis_ms.append(b)
+    stat = lambda v: {"kernel_ms_median": round(float(np.median(v)), 4), "kernel_ms_min": round(float(np.min(v)), 4),
+                      "kernel_ms_max": round(float(np.max(v)), 4), "mrays_per_s_kernel": round(n / float(np.median(v)) / 1e3, 1)}
+    occ = dict(stat(occ_ms), query="occluded", true=int((t_occ != 0).sum().item()),
+               t_max="per ray" if ray_t_max is not None else t_max)
+    vis = dict(stat(vis_ms), query="visibility", true=int((t_obj >= 0).sum().item()),
+               t_max="inf (scalar)" if ray_t_max is not None else t_max)
+    return occ, vis
+
+
+SHADOW_POINT = (0.0, 5.9, 0.0)          # just under the Cornell box's ceiling light (y = 6)
+
+
+def occlusion_rows(ctx, cfg, sc, co, cd, bo, bd, hitpoints, calls, warmup):
+    to = (np.array(SHADOW_POINT, np.float32) - hitpoints).astype(np.float32)
+    dist = np.sqrt((to.astype(np.float64) ** 2).sum(axis=1))
+    ok = dist > 2e-3
+    so = np.ascontiguousarray(hitpoints[ok])
+    sd = np.ascontiguousarray((to[ok] / dist[ok, None]).astype(np.float32))
+    stm = np.ascontiguousarray((dist[ok] - 1e-3).astype(np.float32))
+    rows = []
+    for set_name, o, d, t_max, tm in (("camera", co, cd, sc.camera.max_trace_dist, None), ("bounce", bo, bd, float("inf"), None),
+                                      ("shadow", so, sd, float("inf"), stm)):
+        for r in measure_pair(ctx, o, d, t_max, tm, calls, warmup):
+            row = dict({"config": cfg, "rays": set_name, "n_rays": len(o), "calls": calls}, **r)
+            rows.append(row)
+            print(json.dumps(row), flush=True)
+    return rows
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--calls", type=int, default=20, help="timed calls per row (at least 20)")
@@ -73,6 +133,8 @@ def main():
     ap.add_argument("--width", type=int, default=1920)
     ap.add_argument("--height", type=int, default=1080)
     ap.add_argument("--configs", default="2,4")
+    ap.add_argument("--mode", choices=("intersect", "occlusion"), default="intersect",
+                    help="intersect: the closest-hit rows; occlusion: the any-hit query against the visibility form")
     ap.add_argument("--out", default=None, help="also append the JSON lines to this file")
     a = ap.parse_args()
     if a.calls < 20:
@@ -91,6 +153,9 @@ def main():
         bd = rng.standard_normal((int(hit.sum()), 3))
         bd = np.ascontiguousarray(bd / np.linalg.norm(bd, axis=1, keepdims=True), np.float32)
         bo = np.ascontiguousarray(first.hitpoint[hit])
+        if a.mode == "occlusion":
+            rows += occlusion_rows(ctx, cfg, sc, co, cd, bo, bd, np.ascontiguousarray(first.hitpoint[hit]), a.calls, a.warmup)
+            continue
         for set_name, o, d, t_max in (("camera", co, cd, sc.camera.max_trace_dist), ("bounce", bo, bd, float("inf"))):
             for resolve in (True, False):
                 med, wall, lo, hi, hits = measure(ctx, o, d, t_max, resolve, a.calls, a.warmup)
