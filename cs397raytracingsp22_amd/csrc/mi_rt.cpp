@@ -937,6 +937,8 @@ static int check_shade_args(mi_ctx* c, const mi_camera_desc* cam, const float* o
     if (cam->shading_mode == MI_SHADE_PHONG) return fail(MI_ERR_UNSUPPORTED, "mi_shade_rays: ShadingMode::Phong is not available for caller-supplied rays");
     if (cam->shading_mode != MI_SHADE_PATHTRACE) return fail(MI_ERR_INVALID, "mi_shade_rays: unknown shading_mode %d", cam->shading_mode);
     if (cam->path_depth > 64) return fail(MI_ERR_UNSUPPORTED, "recursive estimator: path_depth must be <= 64");
+    if (cam->path_samples == 0) return fail(MI_ERR_INVALID, "path_samples must be >= 1 (tracing.rs:318 divides by it)");
+    if (std::isnan(cam->max_trace_dist)) return fail(MI_ERR_INVALID, "mi_shade_rays: max_trace_dist must not be NaN");
     if (!c->have_scene) return fail(MI_ERR_NO_SCENE, "no scene uploaded");
     return MI_OK;
 }

@@ -127,6 +127,8 @@ struct Scene : Intersectable {                         // tracing.rs:213-218; `i
     std::vector<float> shade_rays(const std::vector<float>& origins, const std::vector<float>& dirs, uint32_t seed = 1, uint32_t first_key = 0,
                                   int device = 0) const {
         if (origins.size() != dirs.size() || origins.size() % 3 != 0) throw std::runtime_error("mi_rt: origins and dirs must both be [n][3]");
+        if (camera.path_samples == 0) throw std::runtime_error("mi_rt: path_samples must be >= 1 (tracing.rs:318 divides by it)");
+        if (camera.max_trace_dist != camera.max_trace_dist) throw std::runtime_error("mi_rt: max_trace_dist must not be NaN");
         std::vector<float> rgb(origins.size());
         const mi_camera_desc cam = camera.flatten();
         with_context(device, [&](mi_ctx* ctx) {

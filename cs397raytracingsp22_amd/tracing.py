@@ -119,6 +119,16 @@ def check_ray_t_max(ray_t_max, n_rays: int):
     return a
 
 
+def check_shade_camera(cam: "Camera"):
+    """Input checking of mi_shade_rays' camera (no GPU needed), the refusals of the library's check_shade_args that concern values:
+    path_samples >= 1 (tracing.rs:318 divides by it) and a max_trace_dist that is not NaN (+inf is legal)."""
+    if int(cam.path_samples) < 1:
+        raise ValueError("path_samples must be >= 1 (tracing.rs:318 divides by it)")
+    if float(cam.max_trace_dist) != float(cam.max_trace_dist):
+        raise ValueError("max_trace_dist must not be NaN")
+    return cam
+
+
 class Context:
     """One mi_ctx = one GPU (one process per GPU: pass LOCAL_RANK)."""
 
@@ -297,7 +307,7 @@ class Context:
         """mi_shade_rays: Scene::shade_ray at level 0 for every ray -> [n, 3] f32 radiance.  `cam` supplies path_depth,
         path_samples and max_trace_dist."""
         o, d, _, _ = check_rays(origins, dirs)
-        pod = cam.to_pod()
+        pod = check_shade_camera(cam).to_pod()
         out = np.zeros((len(o), 3), np.float32)
         abi.check(self._lib.mi_shade_rays(self._h, C.byref(pod), len(o), o.ctypes.data, d.ctypes.data, seed, first_key & 0xffffffff,
                                           out.ctypes.data))
@@ -305,7 +315,7 @@ class Context:
 
     def shade_rays_device(self, cam: Camera, n_rays: int, d_origins: int, d_dirs: int, d_rgb: int, seed: int = 1,
                           first_key: int = 0, stream: Optional[int] = None):
-        pod = cam.to_pod()
+        pod = check_shade_camera(cam).to_pod()
         abi.check(self._lib.mi_shade_rays_device(self._h, C.byref(pod), n_rays, d_origins, d_dirs, seed, first_key & 0xffffffff,
                                                  d_rgb, stream))
 
@@ -435,6 +445,7 @@ class Scene:                         # tracing.rs:213-218
     def shade_rays(self, origins, dirs, seed: int = 1, first_key: int = 0, device: int = 0) -> np.ndarray:
         """Scene::shade_ray (tracing.rs:300-324) at level 0 for a batch of rays, with this scene's camera settings."""
         o, d, _, _ = check_rays(origins, dirs)
+        check_shade_camera(self.camera)
         ctx = Context(device)
         try:
             ctx.upload(self.flatten())

@@ -291,7 +291,7 @@ int  mi_last_kernel_ms(mi_ctx* ctx, float* ms);
  * mi_shade_rays: Scene::shade_ray (tracing.rs:300-324) at level 0 for n_rays rays, as written (the recursive estimator of
  *   MI_VARIANT_RECURSIVE, bit-identical to the CPU restatement for every path_samples; not a tuned path).  `cam` supplies path_depth,
  *   path_samples and max_trace_dist; its screen_* fields and aa_sample_count are ignored.  shading_mode Phong and path_depth > 64 are
- *   MI_ERR_UNSUPPORTED.
+ *   MI_ERR_UNSUPPORTED.  path_samples == 0 (tracing.rs:318 divides by it) and a NaN max_trace_dist are MI_ERR_INVALID, as in mi_render.
  * Directions are used as given, NOT normalised (the reference does not normalise them either: distances are in units of |dir|).
  * Ray i draws from the RNG stream (seed, pixel = first_key + i, sample = 0), fresh: no Camera::generate_rays draws come first.  Only
  * ConvexVolume::intersect_ray and the scatters read it.  A batch split over several calls with first_key advanced by the rays already
