@@ -17,6 +17,7 @@ from .materials import Dielectric, Isotropic, Lambertian, Material, Metal, Param
 from .geometry import ConvexVolume, Intersectable, Plane, Sphere, StaticMesh, Triangle  # noqa: F401
 from .texture import Texture  # noqa: F401
 from .tracing import Camera, CameraProjectionMode, Context, MultiContext, Scene, ShadingMode, compact_size  # noqa: F401
+from .tracing import check_ray_table, equirect_dirs, equirect_ray_table  # noqa: F401
 
 __all__ = [
     "abi", "Camera", "CameraProjectionMode", "ShadingMode", "Scene", "Context", "MultiContext", "compact_size",

@@ -112,6 +112,7 @@ EXPORTS = [
     "mi_reserve", "mi_render_samples_device", "mi_last_pipeline_ms", "mi_last_pipeline_counts", "mi_last_diag", "mi_selftest", "mi_last_error", "mi_abi_version",
     "mi_intersect_rays", "mi_intersect_rays_device", "mi_shade_rays", "mi_shade_rays_device",
     "mi_occluded_rays", "mi_occluded_rays_device",
+    "mi_render_rays", "mi_render_rays_device",
     "mi_multi_create", "mi_multi_create_loopback", "mi_multi_destroy", "mi_multi_device_count", "mi_multi_context", "mi_multi_scene_upload", "mi_multi_reserve", "mi_multi_render",
 ]
 
@@ -189,6 +190,14 @@ def load() -> C.CDLL:
     lib.mi_occluded_rays.restype = C.c_int
     lib.mi_occluded_rays_device.argtypes = lib.mi_occluded_rays.argtypes + [vp]
     lib.mi_occluded_rays_device.restype = C.c_int
+    # ray-table rendering (added within ABI 5): cam, opts, origins, dirs, rays_per_pixel, then mi_render's outputs / the device form's
+    # sample range, accumulator, compact buffer, signatures and stream
+    lib.mi_render_rays.argtypes = [vp, C.POINTER(mi_camera_desc), C.POINTER(mi_render_opts), vp, vp, C.c_uint32,
+                                   vp, vp, vp, C.POINTER(mi_stats)]
+    lib.mi_render_rays.restype = C.c_int
+    lib.mi_render_rays_device.argtypes = [vp, C.POINTER(mi_camera_desc), C.POINTER(mi_render_opts), vp, vp, C.c_uint32,
+                                          C.c_uint32, C.c_uint32, vp, vp, vp, vp, C.POINTER(mi_stats)]
+    lib.mi_render_rays_device.restype = C.c_int
     lib.mi_multi_create.argtypes = [C.c_int, C.POINTER(C.c_int), C.POINTER(vp)]
     lib.mi_multi_create.restype = C.c_int
     lib.mi_multi_create_loopback.argtypes = [C.c_int, C.c_int, C.POINTER(vp)]

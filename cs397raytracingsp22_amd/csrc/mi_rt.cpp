@@ -107,6 +107,7 @@ struct mi_ctx {
     uint32_t* d_sigi = nullptr; size_t sigi_bytes = 0;
     unsigned long long* d_diag = nullptr;    // 16 counters of the diagnostic variant
     void* d_rq = nullptr; size_t rq_bytes = 0;               // ray queries, host-pointer forms: rays and results of one chunk (its own buffer: never the pipeline's)
+    void* d_rays = nullptr; size_t rays_bytes = 0;           // mi_render_rays: the uploaded ray table, origins then dirs (its own buffer too)
     hipEvent_t ev_t0 = nullptr, ev_t1 = nullptr;     // mi_render's whole-call timer
     bool big_lds_enabled = false;                    // wf_trav_i<1024>'s > 64 KB dynamic-LDS opt-in, set on THIS context's device
     // wavefront pipeline buffers
@@ -257,6 +258,7 @@ extern "C" void mi_ctx_destroy(mi_ctx* c) {
     if (c->d_sigi) (void)hipFree(c->d_sigi);
     if (c->d_diag) (void)hipFree(c->d_diag);
     if (c->d_rq) (void)hipFree(c->d_rq);
+    if (c->d_rays) (void)hipFree(c->d_rays);
     if (c->d_wf_a) (void)hipFree(c->d_wf_a);
     if (c->d_wf_b) (void)hipFree(c->d_wf_b);
     if (c->d_wf_samp) (void)hipFree(c->d_wf_samp);
@@ -473,6 +475,8 @@ private:
 // Samples [begin, end) of every pixel, added in order to `accum` (nullptr = the context's own buffer).
 // begin == 0 starts the sums from zero; end == aa_sample_count also writes the per-pixel means.
 struct SampleRange { uint32_t begin, end; float4* accum; };
+// Ray-table rendering: DEVICE arrays [rows][H][W][3] that replace Camera::generate_rays, rows = 1 or aa_sample_count
+struct RayTable { const float* origins; const float* dirs; uint32_t rows; };
 
 static int render_tiles_wavefront(mi_ctx* c, const K1Args& k, const mi_camera_desc* cam, WfArgs a, uint32_t s_batch, uint32_t flags,
                                   float* d_compact, uint32_t* d_sig, SampleRange range, hipStream_t stream) {
@@ -483,7 +487,9 @@ static int render_tiles_wavefront(mi_ctx* c, const K1Args& k, const mi_camera_de
     a.in_count = cnt + wfcnt::in_count; a.in_blkpfx = cnt + wfcnt::in_blkpfx; a.trav_pfx = cnt + wfcnt::trav_pfx; a.hdr = cnt + wfcnt::hdr;
     a.samp = (float4*)c->d_wf_samp; a.accum = range.accum ? range.accum : (float4*)c->d_wf_acc;
     a.out = d_compact; a.sig = d_sig;
-    MI_TRY(device_tile_masks(c, cam, flags, a.R.tiles_x, stream, &a.tile_mask));
+    // the tile masks are derived from the camera: a ray table renders without them, whatever the flags say
+    if (a.ray_o) a.tile_mask = nullptr;
+    else MI_TRY(device_tile_masks(c, cam, flags, a.R.tiles_x, stream, &a.tile_mask));
     a.diag = nullptr;           // developer builds (-DPT_WF_STAMPS): phase stamps of wf_main
     if (c->tune.wf_stamps) { a.diag = c->d_diag; HIP_TRY(hipMemsetAsync(c->d_diag, 0, 16 * sizeof(unsigned long long), stream)); }
     a.refill_min = c->tune.refill_min;
@@ -643,12 +649,15 @@ static int render_tiles_wavefront(mi_ctx* c, const K1Args& k, const mi_camera_de
     return MI_OK;
 }
 
+// `table` (ray-table rendering): the caller's rays instead of Camera::generate_rays; `cam` then went through table_camera
 static int render_tiles(mi_ctx* c, const mi_camera_desc* cam, const mi_render_opts* o, float* d_compact,
-                        uint32_t* d_sig, hipStream_t stream, mi_stats* st, const SampleRange* partial = nullptr) {
-    int rc = check_camera(cam);
+                        uint32_t* d_sig, hipStream_t stream, mi_stats* st, const SampleRange* partial = nullptr, const RayTable* table = nullptr) {
+    int rc = table ? check_table_camera(cam, table->rows) : check_camera(cam);
     if (rc != MI_OK) return rc;
     if (!c->have_scene) return fail(MI_ERR_NO_SCENE, "no scene uploaded");
     if (!o || o->world < 1 || o->rank < 0 || o->rank >= o->world) return fail(MI_ERR_INVALID, "bad rank/world");
+    if (table && o->variant != MI_VARIANT_DEFAULT && o->variant != MI_VARIANT_WAVEFRONT)
+        return fail(MI_ERR_UNSUPPORTED, "ray-table rendering runs on the default (wavefront) variant only, not variant %d: use mi_shade_rays for the recursive estimator", o->variant);
     SampleRange range = { 0u, cam->aa_sample_count, nullptr };
     if (partial) {
         range = *partial;
@@ -696,6 +705,7 @@ static int render_tiles(mi_ctx* c, const mi_camera_desc* cam, const mi_render_op
         if (cam->aa_sample_count > 0xffffu) return fail(MI_ERR_UNSUPPORTED, "wavefront variant: aa_sample_count must be <= 65535");
         if (cam->path_depth > 0xffffu) return fail(MI_ERR_UNSUPPORTED, "wavefront variant: path_depth must be <= 65535");
         MI_TRY(wf_prepare(c, g.padded, cam->aa_sample_count, o->max_state_bytes, two_stage_mask(c->scene, o->flags) != 0u, wa, wf_batch));
+        if (table) { wa.ray_o = table->origins; wa.ray_d = table->dirs; wa.rays_per_pixel = table->rows; }
     }
     HIP_TRY(hipEventRecord(c->ev_start, stream));
     if (phong)
@@ -1020,14 +1030,10 @@ extern "C" int mi_selftest(mi_ctx* c, uint64_t* out4) {
     return MI_OK;
 }
 
-extern "C" int mi_render(mi_ctx* c, const mi_camera_desc* cam, const mi_render_opts* opts, float* out_rgb_f32,
-                         uint8_t* out_rgb_u8, uint32_t* out_sig, mi_stats* stats) {
-    if (!c) return fail(MI_ERR_INVALID, "ctx is NULL");
-    if (!opts) return fail(MI_ERR_INVALID, "opts is NULL");
-    if (opts->rank != 0 || opts->world != 1) return fail(MI_ERR_INVALID, "mi_render renders a whole image: rank/world must be 0/1");
-    int rc = check_camera(cam);
-    if (rc != MI_OK) return rc;
-    HIP_TRY(hipSetDevice(c->device));
+// The whole image on this GPU into host buffers: render, un-permute, tone-map, download (mi_render; with `table`, mi_render_rays).
+static int render_image(mi_ctx* c, const mi_camera_desc* cam, const mi_render_opts* opts, const RayTable* table, float* out_rgb_f32,
+                        uint8_t* out_rgb_u8, uint32_t* out_sig, mi_stats* stats) {
+    int rc;
     const hipEvent_t t0 = c->ev_t0, t1 = c->ev_t1;      // owned by the context: no early return can leak them
     const TileGrid g = tile_grid(cam, 1);
     size_t npix = (size_t)cam->screen_width * cam->screen_height;
@@ -1042,7 +1048,7 @@ extern "C" int mi_render(mi_ctx* c, const mi_camera_desc* cam, const mi_render_o
     mi_render_opts o = *opts;
     o.want_signature = want_sig ? 1 : 0;
     HIP_TRY(hipEventRecord(t0, c->stream));
-    rc = render_tiles(c, cam, &o, c->d_compact, want_sig ? c->d_sigc : nullptr, c->stream, stats);
+    rc = render_tiles(c, cam, &o, c->d_compact, want_sig ? c->d_sigc : nullptr, c->stream, stats, nullptr, table);
     if (rc != MI_OK) return rc;
     HIP_TRY(launch_unpermute(c->d_compact, c->d_image, cam->screen_width, cam->screen_height, g.tx, 1, g.padded, c->stream));
     if (out_rgb_f32) HIP_TRY(hipMemcpyAsync(out_rgb_f32, c->d_image, npix * 3 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
@@ -1063,6 +1069,62 @@ extern "C" int mi_render(mi_ctx* c, const mi_camera_desc* cam, const mi_render_o
         HIP_TRY(hipEventElapsedTime(&ms, t0, t1)); stats->total_ms = ms;
     }
     return MI_OK;
+}
+
+extern "C" int mi_render(mi_ctx* c, const mi_camera_desc* cam, const mi_render_opts* opts, float* out_rgb_f32,
+                         uint8_t* out_rgb_u8, uint32_t* out_sig, mi_stats* stats) {
+    if (!c) return fail(MI_ERR_INVALID, "ctx is NULL");
+    if (!opts) return fail(MI_ERR_INVALID, "opts is NULL");
+    if (opts->rank != 0 || opts->world != 1) return fail(MI_ERR_INVALID, "mi_render renders a whole image: rank/world must be 0/1");
+    int rc = check_camera(cam);
+    if (rc != MI_OK) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    return render_image(c, cam, opts, nullptr, out_rgb_f32, out_rgb_u8, out_sig, stats);
+}
+
+// ------------------------------------------------------------------ ray-table rendering (caller-made rays through the wavefront pipeline)
+// A table [rows][H][W][3] of origins and one of directions replaces Camera::generate_rays for one render; everything behind the camera
+// pass of the pipeline is mi_render's.  Every refusal happens here, before anything is allocated, copied or launched.
+static int check_table_args(mi_ctx* c, const mi_camera_desc* cam, const mi_render_opts* opts, const float* origins, const float* dirs,
+                            uint32_t rays_per_pixel) {
+    if (!c) return fail(MI_ERR_INVALID, "ctx is NULL");
+    if (!opts) return fail(MI_ERR_INVALID, "opts is NULL");
+    if (!origins || !dirs) return fail(MI_ERR_INVALID, "mi_render_rays: the origins and dirs tables are required");
+    MI_TRY(check_table_camera(cam, rays_per_pixel));
+    if (opts->variant != MI_VARIANT_DEFAULT && opts->variant != MI_VARIANT_WAVEFRONT)
+        return fail(MI_ERR_UNSUPPORTED, "ray-table rendering runs on the default (wavefront) variant only, not variant %d: use mi_shade_rays for the recursive estimator", opts->variant);
+    if (cam->aa_sample_count > 0xffffu) return fail(MI_ERR_UNSUPPORTED, "wavefront variant: aa_sample_count must be <= 65535");
+    if (cam->path_depth > 0xffffu) return fail(MI_ERR_UNSUPPORTED, "wavefront variant: path_depth must be <= 65535");
+    if (opts->world < 1 || opts->rank < 0 || opts->rank >= opts->world) return fail(MI_ERR_INVALID, "bad rank/world");
+    if (!c->have_scene) return fail(MI_ERR_NO_SCENE, "no scene uploaded");
+    return MI_OK;
+}
+
+extern "C" int mi_render_rays(mi_ctx* c, const mi_camera_desc* cam, const mi_render_opts* opts, const float* origins, const float* dirs,
+                              uint32_t rays_per_pixel, float* out_rgb_f32, uint8_t* out_rgb_u8, uint32_t* out_sig, mi_stats* stats) {
+    MI_TRY(check_table_args(c, cam, opts, origins, dirs, rays_per_pixel));
+    if (opts->rank != 0 || opts->world != 1) return fail(MI_ERR_INVALID, "mi_render_rays renders a whole image: rank/world must be 0/1");
+    HIP_TRY(hipSetDevice(c->device));
+    const size_t bytes = (size_t)rays_per_pixel * cam->screen_height * cam->screen_width * 3 * sizeof(float);     // of each table
+    MI_TRY(ensure(&c->d_rays, &c->rays_bytes, 2 * bytes));
+    HIP_TRY(hipMemcpyAsync(c->d_rays, origins, bytes, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync((char*)c->d_rays + bytes, dirs, bytes, hipMemcpyHostToDevice, c->stream));
+    const RayTable table = { (const float*)c->d_rays, (const float*)((const char*)c->d_rays + bytes), rays_per_pixel };
+    const mi_camera_desc tc = table_camera(cam);
+    return render_image(c, &tc, opts, &table, out_rgb_f32, out_rgb_u8, out_sig, stats);
+}
+
+extern "C" int mi_render_rays_device(mi_ctx* c, const mi_camera_desc* cam, const mi_render_opts* opts, const float* d_origins,
+                                     const float* d_dirs, uint32_t rays_per_pixel, uint32_t sample_begin, uint32_t sample_end,
+                                     void* d_accum_f32x4, void* d_compact_f32, void* d_sig_u32, void* stream, mi_stats* stats) {
+    MI_TRY(check_table_args(c, cam, opts, d_origins, d_dirs, rays_per_pixel));
+    HIP_TRY(hipSetDevice(c->device));
+    const RayTable table = { d_origins, d_dirs, rays_per_pixel };
+    const mi_camera_desc tc = table_camera(cam);
+    // [0, aa_sample_count) without an accumulator is a whole render (mi_render_tiles_device); anything else a progressive call
+    const bool whole = sample_begin == 0 && sample_end == cam->aa_sample_count && !d_accum_f32x4;
+    SampleRange r = { sample_begin, sample_end, (float4*)d_accum_f32x4 };
+    return render_tiles(c, &tc, opts, (float*)d_compact_f32, (uint32_t*)d_sig_u32, (hipStream_t)stream, stats, whole ? nullptr : &r, &table);
 }
 
 // ------------------------------------------------------------------ multi-GPU behind the ABI

@@ -335,6 +335,11 @@ struct WfArgs {
     uint2* cand;
     uint2* cand_hdr;
     unsigned long long* diag;   // developer builds with -DPT_WF_STAMPS: [16] summed s_memtime deltas of sampled wf_main waves
+    // Ray-table rendering (mi_render_rays): the camera pass takes sample s of pixel (x, y) from ray_o / ray_d at
+    // ((row * height + y) * width + x) * 3, row = s when rays_per_pixel == aa_sample_count, 0 when it is 1.  nullptr = Camera::generate_rays.
+    const float* ray_o;
+    const float* ray_d;
+    uint32_t rays_per_pixel;
 };
 
 // How a render walks the meshes that take the reference's tree (scene_compile.cpp plan_walker -> pt_kernels.hip launch_walker).

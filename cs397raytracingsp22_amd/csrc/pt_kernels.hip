@@ -2084,6 +2084,7 @@ __device__ __forceinline__ uint32_t wf_append(uint32_t* counter, bool want) {
     return base + (uint32_t)__popcll(m & lt);
 }
 
+struct Ray3 { float x, y, z; };       // one 12-byte record of a ray table (dword-aligned)
 __device__ __forceinline__ void wf_pixel_of(const WfArgs& A, uint32_t pix, uint32_t& px, uint32_t& py, bool& in_image) {
     const uint32_t slot = pix / kTilePixels, in = pix % kTilePixels;
     const uint32_t tile = slot * (uint32_t)A.R.world + (uint32_t)A.R.rank;
@@ -2099,8 +2100,10 @@ __device__ __forceinline__ void wf_pixel_of(const WfArgs& A, uint32_t pix, uint3
 // RARE = false: the scene holds no Plane and no ConvexVolume (their loop and the free-flight code are compiled out)
 // ITER0 = true: the camera-ray pass (Camera::generate_rays instead of a state load; always the lean form)
 // TOP = true: the list's Triangles sit in a top-level tree (intersect_list<.., TOP>; scenes with long lists only)
-template <bool LDS, bool SIG, bool GV, int MESH, bool RARE, bool ITER0, bool TOP = false>
+// RAYS = true (with ITER0 only): ray-table rendering — the lane takes (o, d) from the caller's table instead of Camera::generate_rays
+template <bool LDS, bool SIG, bool GV, int MESH, bool RARE, bool ITER0, bool TOP = false, bool RAYS = false>
 __global__ __launch_bounds__(kBlock, (MESH == 2 ? PT_MAIN_WAVES : (MESH == 1 ? PT_MAIN_WAVES_NOTEX : PT_MAIN_WAVES_LEAN))) void wf_main(WfArgs A) {
+    static_assert(ITER0 || !RAYS, "the ray table replaces Camera::generate_rays: the camera-ray pass only");
     const DScene& S = A.S;
     const DCamera& C = A.C;
     Bvh<LDS> B;            // only the mesh ROOT nodes are read here
@@ -2160,7 +2163,14 @@ __global__ __launch_bounds__(kBlock, (MESH == 2 ? PT_MAIN_WAVES : (MESH == 1 ? P
         }
         if (alive) {
             rng_init(P.rng, A.seed_key, py * C.width + px, sample);
-            generate_ray(C, px, py, sample, P.rng, P.o, P.d);
+            if (RAYS) {
+                // the caller's ray (s, y, x) at ((s H + y) W + x) * 3, s = 0 for a one-row table; 64-bit index (S W H 3 passes 2^32 at 4K).
+                // Used as given: no draw from the stream, no normalisation.  A lane outside the image never comes here (the table has no
+                // entry for it).  Consecutive lanes of a tile row read consecutive 12-byte records: 32 lanes, 384 contiguous bytes.
+                const size_t r = (((size_t)(A.rays_per_pixel == 1u ? 0u : sample) * C.height + py) * C.width + px) * 3;
+                const Ray3 ro = *(const Ray3*)(A.ray_o + r), rd = *(const Ray3*)(A.ray_d + r);
+                P.o = mk3(ro.x, ro.y, ro.z); P.d = mk3(rd.x, rd.y, rd.z);
+            } else generate_ray(C, px, py, sample, P.rng, P.o, P.d);
             if (C.path_depth == 0u) {                                     // tracing.rs:301 at level 0: the background, before any intersection
                 if (SIG) P.sig = sig_end_depth(P.sig);
                 A.samp[(size_t)(sample - A.s_base) * A.npix + pix] = make_float4(0.0f, 0.0f, 0.0f, __uint_as_float(P.sig));
@@ -3541,12 +3551,17 @@ hipError_t launch_wf_main(const WfArgs& a, uint32_t n_blocks, bool sig, bool gv,
 #define PT_WF_MAIN2(G, V, M, R, I) do { if (top) hipLaunchKernelGGL((wf_main<false, G, V, M, R, I, true>), grid, block, 0, stream, a); \
                                         else hipLaunchKernelGGL((wf_main<false, G, V, M, R, I, false>), grid, block, 0, stream, a); } while (0)
 #define PT_WF_SIG(V, M, R, I) do { if (sig) PT_WF_MAIN2(true, V, M, R, I); else PT_WF_MAIN2(false, V, M, R, I); } while (0)
-#define PT_WF_MESH(V, R) do { if (a.iter0) PT_WF_SIG(V, 0, R, true); else if (lean) PT_WF_SIG(V, 0, R, false); \
+    // ray-table rendering: the camera pass reads the caller's table (the RAYS form of ITER0); every later pass is the usual one
+#define PT_WF_RAYS(G, V, R) do { if (top) hipLaunchKernelGGL((wf_main<false, G, V, 0, R, true, true, true>), grid, block, 0, stream, a); \
+                                 else hipLaunchKernelGGL((wf_main<false, G, V, 0, R, true, false, true>), grid, block, 0, stream, a); } while (0)
+#define PT_WF_MESH(V, R) do { if (a.iter0 && a.ray_o) { if (sig) PT_WF_RAYS(true, V, R); else PT_WF_RAYS(false, V, R); } \
+                              else if (a.iter0) PT_WF_SIG(V, 0, R, true); else if (lean) PT_WF_SIG(V, 0, R, false); \
                               else if (tex) PT_WF_SIG(V, 2, R, false); else PT_WF_SIG(V, 1, R, false); } while (0)
     if (!rare) PT_WF_MESH(false, false);
     else if (gv) PT_WF_MESH(true, true);
     else PT_WF_MESH(false, true);
 #undef PT_WF_MESH
+#undef PT_WF_RAYS
 #undef PT_WF_SIG
 #undef PT_WF_MAIN2
     return hipGetLastError();

@@ -41,6 +41,34 @@ int check_camera(const mi_camera_desc* cam) {
     return MI_OK;
 }
 
+int check_table_camera(const mi_camera_desc* cam, uint32_t rays_per_pixel) {
+    if (!cam) return fail(MI_ERR_INVALID, "camera is NULL");
+    if (cam->shading_mode != MI_SHADE_PATHTRACE && cam->shading_mode != MI_SHADE_PHONG)
+        return fail(MI_ERR_INVALID, "unknown shading_mode %d", cam->shading_mode);
+    if (cam->path_samples == 0) return fail(MI_ERR_INVALID, "path_samples must be >= 1 (tracing.rs:318 divides by it)");
+    if (cam->screen_width == 0 || cam->screen_height == 0 || cam->screen_width > 32768 || cam->screen_height > 32768)
+        return fail(MI_ERR_INVALID, "bad image size %ux%u", cam->screen_width, cam->screen_height);
+    if (cam->aa_sample_count == 0) return fail(MI_ERR_INVALID, "aa_sample_count must be >= 1");
+    if (!(cam->gamma > 0.0f) || !std::isfinite(cam->gamma)) return fail(MI_ERR_INVALID, "gamma must be finite and > 0 (tracing.rs:254 raises to 1/gamma)");
+    if (std::isnan(cam->max_trace_dist)) return fail(MI_ERR_INVALID, "max_trace_dist must not be NaN");
+    if (rays_per_pixel != 1u && rays_per_pixel != cam->aa_sample_count)
+        return fail(MI_ERR_INVALID, "rays_per_pixel is %u: a ray table holds 1 row or aa_sample_count = %u rows", rays_per_pixel, cam->aa_sample_count);
+    if (cam->shading_mode == MI_SHADE_PHONG)
+        return fail(MI_ERR_UNSUPPORTED, "ray-table rendering: ShadingMode::Phong is not available for caller-supplied rays (mi_shade_rays has no Phong either)");
+    if (cam->path_samples != 1)
+        return fail(MI_ERR_UNSUPPORTED, "ray-table rendering runs the wavefront pipeline, path_samples == 1 only: use mi_shade_rays for path_samples = %u", cam->path_samples);
+    return MI_OK;
+}
+
+mi_camera_desc table_camera(const mi_camera_desc* cam) {
+    mi_camera_desc t = *cam;
+    const float eye[3] = { 0.0f, 0.0f, 0.0f }, view[3] = { 0.0f, 0.0f, -1.0f }, up[3] = { 0.0f, 1.0f, 0.0f };
+    for (int k = 0; k < 3; k++) { t.eyepoint[k] = eye[k]; t.view_dir[k] = view[k]; t.up[k] = up[k]; }
+    t.projection_mode = MI_PROJ_PERSPECTIVE;
+    t.focal_length = 1.0f; t.focus_dist = 1.0f; t.lens_radius = 0.0f;
+    return t;
+}
+
 // The tile grid of the partition.  Tiles are numbered row-major over a grid whose ROW LENGTH `tx` is the image's tile columns
 // rounded up to the next integer coprime with `world` (tile t -> rank t % world, slot t / world): a row length that shares a factor
 // with the rank count repeats the same few column classes for a rank in every row (60 columns over 8 ranks: two classes, and the

@@ -13,6 +13,13 @@ namespace pt {
 
 // MI_OK, or MI_ERR_INVALID with the reason recorded (fail)
 int check_camera(const mi_camera_desc* cam);
+// Ray-table rendering (mi_render_rays): the rays are the caller's, so only the fields that call reads are checked — the image size,
+// aa_sample_count (any value >= 1: the square exists for generate_rays' jitter grid only), path_samples, shading_mode, max_trace_dist
+// and gamma — and rays_per_pixel, which is 1 or aa_sample_count.  eyepoint .. lens_radius may hold anything, non-finite values included.
+// MI_OK, MI_ERR_INVALID or MI_ERR_UNSUPPORTED (path_samples != 1, Phong) with the reason recorded.
+int check_table_camera(const mi_camera_desc* cam, uint32_t rays_per_pixel);
+// `cam` with the fields a ray-table render ignores replaced by fixed finite values (what make_camera and tile_grid may then read)
+mi_camera_desc table_camera(const mi_camera_desc* cam);
 
 // The tile grid of the partition for `world` ranks (tile t -> rank t % world, slot t / world): tx tiles per row (the image's tile
 // columns, rounded up to the next integer coprime with world), ty rows, total = tx * ty, padded = tiles per rank, rounded up.

@@ -137,6 +137,25 @@ struct Scene : Intersectable {                         // tracing.rs:213-218; `i
         return rgb;
     }
 
+    // Scene::render_to_image (tracing.rs:221-263) with a ray table in place of Camera::generate_rays, through mi_render_rays: origins / dirs
+    // are [rays_per_pixel][H][W][3], rays_per_pixel = 1 or camera.aa_sample_count (any value, not only squares).  Sample s of pixel (x, y)
+    // draws from the stream (seed, y * W + x, s); directions are used as given; the camera's pose, projection and lens fields are ignored.
+    RgbImage render_rays(const std::vector<float>& origins, const std::vector<float>& dirs, uint32_t rays_per_pixel, uint32_t seed = 1,
+                         int device = 0, mi_stats* stats = nullptr, std::vector<float>* linear = nullptr) const {
+        const size_t n = (size_t)rays_per_pixel * camera.screen_height * camera.screen_width * 3;
+        if (origins.size() != n || dirs.size() != n) throw std::runtime_error("mi_rt: origins and dirs must both be [rays_per_pixel][H][W][3]");
+        const mi_camera_desc cam = camera.flatten();
+        RgbImage img; img.width = camera.screen_width; img.height = camera.screen_height;
+        img.data.resize((size_t)img.width * img.height * 3);
+        if (linear) linear->resize(img.data.size());
+        mi_render_opts opts{}; opts.seed = seed; opts.rank = 0; opts.world = 1;
+        with_context(device, [&](mi_ctx* ctx) {
+            return mi_render_rays(ctx, &cam, &opts, origins.data(), dirs.data(), rays_per_pixel, linear ? linear->data() : nullptr,
+                                  img.data.data(), nullptr, stats);
+        });
+        return img;
+    }
+
 private:
     // flatten -> context -> upload -> `call(ctx)` -> destroy; a failure surfaces as std::runtime_error carrying mi_last_error()
     template <class F> void with_context(int device, F call) const {

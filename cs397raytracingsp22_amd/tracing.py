@@ -129,6 +129,86 @@ def check_shade_camera(cam: "Camera"):
     return cam
 
 
+def check_ray_table(cam: "Camera", origins, dirs):
+    """Input checking of ray-table rendering (mi_render_rays), no GPU needed.  `origins` and `dirs` are float32 arrays of shape
+    [S, H, W, 3] or [H, W, 3] (= one row) with H, W = cam.screen_height, cam.screen_width and S = 1 (every sample of a pixel uses the
+    same ray) or cam.aa_sample_count (sample s uses row s).  Other dtypes are refused, not converted: a table is large.  The camera is
+    checked for what the call reads — image size, aa_sample_count in 1..65535 (any value, not only squares), path_depth, path_samples
+    (1: the wavefront pipeline), shading_mode (PathTrace), max_trace_dist (not NaN), gamma (finite, > 0); eyepoint .. lens_radius are
+    ignored and may hold anything.  Returns (origins, dirs, rays_per_pixel) as C-contiguous [S, H, W, 3] arrays; raises ValueError."""
+    W, H, aa = int(cam.screen_width), int(cam.screen_height), int(cam.aa_sample_count)
+    if not (1 <= W <= 32768 and 1 <= H <= 32768):
+        raise ValueError(f"bad image size {W}x{H}")
+    if not 1 <= aa <= 0xffff:
+        raise ValueError(f"aa_sample_count must be in 1..65535, got {aa}")
+    if not 0 <= int(cam.path_depth) <= 0xffff:
+        raise ValueError("path_depth must be in 0..65535")
+    if int(cam.path_samples) < 1:
+        raise ValueError("path_samples must be >= 1 (tracing.rs:318 divides by it)")
+    if int(cam.path_samples) != 1:
+        raise ValueError("ray-table rendering runs the wavefront pipeline, path_samples == 1 only: use shade_rays (mi_shade_rays)")
+    if cam.shading_mode == ShadingMode.Phong:
+        raise ValueError("ray-table rendering: ShadingMode.Phong is not available for caller-supplied rays (shade_rays has none either)")
+    if cam.shading_mode != ShadingMode.PathTrace:
+        raise ValueError(f"unknown shading_mode {cam.shading_mode}")
+    if float(cam.max_trace_dist) != float(cam.max_trace_dist):
+        raise ValueError("max_trace_dist must not be NaN")
+    g = float(cam.gamma)
+    if not (g > 0.0) or g == float("inf"):
+        raise ValueError("gamma must be finite and > 0 (tracing.rs:254 raises to 1/gamma)")
+    out = []
+    for name, a in (("origins", origins), ("dirs", dirs)):
+        a = np.asarray(a)
+        if a.dtype != np.float32:
+            raise ValueError(f"{name} must be float32, got {a.dtype}")
+        if a.ndim == 3:
+            a = a[None]
+        if a.ndim != 4 or a.shape[1:] != (H, W, 3):
+            raise ValueError(f"{name} must have shape [S, {H}, {W}, 3] or [{H}, {W}, 3], got {tuple(np.shape(a))}")
+        if a.shape[0] not in (1, aa):
+            raise ValueError(f"{name} holds {a.shape[0]} rays per pixel: a ray table holds 1 row or aa_sample_count = {aa} rows")
+        out.append(np.ascontiguousarray(a))
+    if out[0].shape != out[1].shape:
+        raise ValueError(f"origins and dirs differ in shape: {out[0].shape} and {out[1].shape}")
+    return out[0], out[1], int(out[0].shape[0])
+
+
+def equirect_dirs(lon, lat) -> np.ndarray:
+    """Unit directions [..., 3] float32 of a latitude-longitude panorama for arrays of longitudes / latitudes in radians:
+    (sin lon cos lat, sin lat, -cos lon cos lat) — longitude 0 looks down -z, +pi/2 down +x, +-pi (the seam) down +z; latitude +pi/2 is
+    +y.  Multiples of pi/2 go through exact sines and cosines, so the poles, the seam and +-x / -z are axis-aligned to the last bit."""
+    lon, lat = np.broadcast_arrays(np.asarray(lon, np.float64), np.asarray(lat, np.float64))
+
+    def exact(table, f, a):
+        q = a / (0.5 * np.pi)
+        r = np.rint(q)
+        return np.where(np.abs(q - r) < 1e-12, np.take(np.array(table), r.astype(np.int64) % 4), f(a))
+    sl, cl = exact((0.0, 1.0, 0.0, -1.0), np.sin, lon), exact((1.0, 0.0, -1.0, 0.0), np.cos, lon)
+    sp, cp = exact((0.0, 1.0, 0.0, -1.0), np.sin, lat), exact((1.0, 0.0, -1.0, 0.0), np.cos, lat)
+    d = np.stack([sl * cp, sp, -cl * cp], axis=-1) + 0.0              # + 0.0: no negative zeros
+    return np.ascontiguousarray(d, dtype=np.float32)
+
+
+def equirect_ray_table(width: int, height: int, eye, samples: int = 1, seed: int = 0):
+    """A latitude-longitude panorama seen from `eye` as a ray table for render_rays: (origins, dirs), each [samples, height, width, 3]
+    float32, unit directions (equirect_dirs).  Columns span the longitudes [-pi, pi) from left to right, rows the latitudes from +pi/2
+    at the top edge to -pi/2 at the bottom edge.  Sample s of pixel (x, y) looks through the image point (x + jx, y + jy): the pixel
+    centre for samples == 1, otherwise a jitter in [0, 1)^2 drawn from numpy's default_rng(seed) — the same seed gives the same table."""
+    W, H, S = int(width), int(height), int(samples)
+    if W < 1 or H < 1 or S < 1:
+        raise ValueError("width, height and samples must be >= 1")
+    if S == 1:
+        jx = jy = np.full((1, H, W), 0.5)
+    else:
+        j = np.random.default_rng(seed).random((2, S, H, W))
+        jx, jy = j[0], j[1]
+    lon = ((np.arange(W)[None, None, :] + jx) / W - 0.5) * (2.0 * np.pi)
+    lat = (0.5 - (np.arange(H)[None, :, None] + jy) / H) * np.pi
+    dirs = equirect_dirs(lon, lat)
+    origins = np.ascontiguousarray(np.broadcast_to(np.asarray(eye, np.float32).reshape(3), dirs.shape))
+    return origins, dirs
+
+
 class Context:
     """One mi_ctx = one GPU (one process per GPU: pass LOCAL_RANK)."""
 
@@ -175,7 +255,44 @@ class Context:
             sig.ctypes.data if sig is not None else None, C.byref(st)))
         return f32, u8, sig, st
 
+    def render_rays(self, cam: Camera, origins, dirs, seed: int = 1, want_f32=True, want_u8=True, want_sig=False,
+                    flags: int = 0, max_state_bytes: int = 0):
+        """mi_render_rays: the whole image from a ray table (check_ray_table: [S, H, W, 3] or [H, W, 3] float32, S = 1 or
+        aa_sample_count) instead of Camera::generate_rays, through the wavefront pipeline.  Sample s of pixel (x, y) draws from the stream
+        (seed, y*W + x, s).  Returns what render returns."""
+        o, d, rows = check_ray_table(cam, origins, dirs)
+        pod = cam.to_pod()
+        opts = abi.mi_render_opts(seed=seed, rank=0, world=1, variant=abi.MI_VARIANT_DEFAULT, want_signature=int(want_sig),
+                                  flags=flags, max_state_bytes=max_state_bytes)
+        H, W = cam.screen_height, cam.screen_width
+        f32 = np.empty((H, W, 3), np.float32) if want_f32 else None
+        u8 = np.empty((H, W, 3), np.uint8) if want_u8 else None
+        sig = np.empty((H, W), np.uint32) if want_sig else None
+        st = abi.mi_stats()
+        abi.check(self._lib.mi_render_rays(
+            self._h, C.byref(pod), C.byref(opts), o.ctypes.data, d.ctypes.data, rows,
+            f32.ctypes.data if f32 is not None else None,
+            u8.ctypes.data if u8 is not None else None,
+            sig.ctypes.data if sig is not None else None, C.byref(st)))
+        return f32, u8, sig, st
+
     # ---- device-pointer building blocks (multi-GPU; pointers are ints, e.g. tensor.data_ptr()) ----
+    def render_rays_device(self, cam: Camera, d_origins: int, d_dirs: int, rays_per_pixel: int, d_compact: Optional[int] = None,
+                           d_sig: Optional[int] = None, sample_begin: int = 0, sample_end: Optional[int] = None,
+                           d_accum: Optional[int] = None, seed: int = 1, rank: int = 0, world: int = 1, stream: Optional[int] = None,
+                           flags: int = 0, max_state_bytes: int = 0):
+        """mi_render_rays_device: render_tiles_device and render_samples_device for a ray table held on the device (raw pointers,
+        [rays_per_pixel, H, W, 3] float32 each).  The default range with d_accum None is a whole render of this rank's tiles; any other
+        range adds samples [sample_begin, sample_end) to the accumulator, and the call that reaches aa_sample_count writes d_compact."""
+        pod = cam.to_pod()
+        opts = abi.mi_render_opts(seed=seed, rank=rank, world=world, variant=abi.MI_VARIANT_DEFAULT,
+                                  want_signature=int(d_sig is not None), flags=flags, max_state_bytes=max_state_bytes)
+        st = abi.mi_stats()
+        end = cam.aa_sample_count if sample_end is None else sample_end
+        abi.check(self._lib.mi_render_rays_device(self._h, C.byref(pod), C.byref(opts), d_origins, d_dirs, rays_per_pixel,
+                                                  sample_begin, end, d_accum, d_compact, d_sig, stream, C.byref(st)))
+        return st
+
     def render_tiles_device(self, cam: Camera, d_compact: int, d_sig: Optional[int] = None, seed: int = 1,
                             rank: int = 0, world: int = 1, stream: Optional[int] = None,
                             variant: int = abi.MI_VARIANT_DEFAULT, flags: int = 0, max_state_bytes: int = 0):
@@ -439,6 +556,18 @@ class Scene:                         # tracing.rs:213-218
         try:
             ctx.upload(self.flatten())
             return ctx.occluded_rays(o, d, t_min, t_max, ray_t_max=tm, seed=seed, first_key=first_key)
+        finally:
+            ctx.close()
+
+    def render_rays(self, origins, dirs, seed: int = 1, device: int = 0) -> np.ndarray:
+        """Scene::render_to_image (tracing.rs:221-263) with a ray table in place of Camera::generate_rays (mi_render_rays): the RgbImage
+        bytes [H,W,3] u8.  This scene's camera supplies the image size, aa_sample_count, path_depth, max_trace_dist and gamma."""
+        o, d, _ = check_ray_table(self.camera, origins, dirs)
+        ctx = Context(device)
+        try:
+            ctx.upload(self.flatten())
+            _, u8, _, _ = ctx.render_rays(self.camera, o, d, seed=seed, want_f32=False, want_u8=True)
+            return u8
         finally:
             ctx.close()
 

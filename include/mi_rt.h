@@ -343,6 +343,45 @@ int  mi_occluded_rays(mi_ctx* ctx, uint32_t n_rays, const float* origins, const 
 int  mi_occluded_rays_device(mi_ctx* ctx, uint32_t n_rays, const float* origins, const float* dirs, float t_min, float t_max,
                              const float* ray_t_max, uint32_t seed, uint32_t first_key, uint8_t* out_occluded, void* stream);
 
+/* ---- ray-table rendering: a whole render from rays of the CALLER's making, through the wavefront pipeline (added within ABI version 5
+ * like the queries above: detect by symbol lookup) ----
+ * A ray table replaces Camera::generate_rays (tracing.rs:159-209) for one render; the rest of Scene::render_to_image (tracing.rs:221-263)
+ *   stays: per-pixel sums in sample order, the mean, saturation / gamma / bytes.  Fisheye, panoramic and stereo cameras, light probes,
+ *   lightmap baking at any sample count: the tuned path of mi_render (classes, LDS walkers, two-stage traversal, batches), not the
+ *   recursive kernel of mi_shade_rays.
+ * Layout: the image is cam->screen_width x screen_height (W x H) with cam->aa_sample_count samples per pixel.  `origins` and `dirs` are
+ *   two arrays [rays_per_pixel][H][W][3] f32: ray (s, y, x) sits at ((s*H + y)*W + x)*3 (indexed in 64 bits).  rays_per_pixel is
+ *   aa_sample_count (sample s of a pixel uses row s) or 1 (every sample of a pixel uses the same ray); anything else is MI_ERR_INVALID.
+ * RNG: sample s of pixel (x, y) draws from the stream (seed, y*W + x, s), fresh: no Camera::generate_rays draws come first.  That is
+ *   mi_shade_rays with first_key = 0 for s = 0.  Only ConvexVolume::intersect_ray and the scatters read the stream.
+ * Rays: directions are used as given, NOT normalised; t_min = 0.001, t_max = cam->max_trace_dist, as in mi_render.  Non-finite rays are
+ *   not rejected and never fault; their results follow DESIGN.md section 2 (v), as for mi_intersect_rays (finite rays are exact).
+ * Camera fields read: screen_width, screen_height, aa_sample_count (any value in 1 .. 65535: it need NOT be a perfect square, the
+ *   square exists for generate_rays' jitter grid only), path_depth, path_samples, shading_mode, max_trace_dist, gamma.  eyepoint,
+ *   view_dir, up, projection_mode, focal_length, focus_dist and lens_radius are IGNORED and may hold anything, non-finite values included.
+ * Refusals (each with a message, nothing is launched): path_samples != 1 or MI_SHADE_PHONG, and a variant other than DEFAULT /
+ *   WAVEFRONT, are MI_ERR_UNSUPPORTED (mi_shade_rays is the call for path_samples != 1); path_samples == 0, a NaN max_trace_dist, a bad
+ *   gamma, a bad image size, aa_sample_count == 0 and NULL tables are MI_ERR_INVALID; a context without a scene is MI_ERR_NO_SCENE.
+ * Masks: the primary-ray tile masks and dead-tile culling are derived from the camera, so they are OFF for these calls whatever
+ *   opts->flags says (the effect of MI_OPT_NO_TILE_MASKS; entry 7 of mi_last_pipeline_counts is 0).  The other MI_OPT_* keep their meaning.
+ * Output: sample order, the mean, the f32 / u8 / signature outputs and the compact tile-major layout are those of mi_render /
+ *   mi_render_tiles_device.  mi_reserve, max_state_bytes, mi_last_kernel_ms and mi_last_pipeline_ms / _counts behave as for mi_render.
+ * mi_render_rays: HOST pointers, blocking, opts->rank / world must be 0 / 1.  The table is uploaded into a buffer the context owns
+ *   (grown on demand, freed with the context; never the buffers mi_reserve sized nor the queries' chunk buffer; MI_ERR_OOM if it cannot
+ *   be allocated), then: render, un-permute, tone-map, download, as mi_render.
+ * mi_render_rays_device: DEVICE pointers on ctx's device; mi_render_tiles_device and mi_render_samples_device in one call.  Rank
+ *   opts->rank of opts->world renders its tiles into the compact buffer.  [sample_begin, sample_end) = [0, aa_sample_count) with
+ *   d_accum_f32x4 == NULL is a whole render; any other range follows mi_render_samples_device's rules (accumulator required, calls
+ *   cover the range in order, outputs written by the call that ends at aa_sample_count).  The table must stay valid until the call
+ *   returns (it synchronises `stream`).  mi_multi_* takes no table. */
+int  mi_render_rays(mi_ctx* ctx, const mi_camera_desc* cam, const mi_render_opts* opts,
+                    const float* origins, const float* dirs, uint32_t rays_per_pixel,
+                    float* out_rgb_f32, uint8_t* out_rgb_u8, uint32_t* out_sig, mi_stats* stats);
+int  mi_render_rays_device(mi_ctx* ctx, const mi_camera_desc* cam, const mi_render_opts* opts,
+                           const float* d_origins, const float* d_dirs, uint32_t rays_per_pixel,
+                           uint32_t sample_begin, uint32_t sample_end, void* d_accum_f32x4,
+                           void* d_compact_f32, void* d_sig_u32, void* stream, mi_stats* stats);
+
 /* Size and allocate the wavefront pipeline's HBM buffers (path state, sample slots) for
  * this camera with the image shared by `world` ranks, so that the first render does not pay the
  * allocation (about 110 GB for a whole 1080p / 256 spp frame on one GPU).  `max_state_bytes` as in

@@ -137,6 +137,24 @@ impl Scene {
         rgb
     }
 
+    /// Scene::render_to_image (tracing.rs:221-263) with a ray table in place of Camera::generate_rays (mi_render_rays): `origins` and
+    /// `dirs` hold `rays_per_pixel` x height x width rays, row-major ([s][y][x]), rays_per_pixel = 1 or camera.aa_sample_count (which
+    /// need not be a square here).  Sample s of pixel (x, y) draws from the stream (seed, y * width + x, s); directions are used as
+    /// given.  The camera's eyepoint, view_dir, up, projection and lens fields are ignored.
+    pub fn render_rays(&self, origins: &[[f32; 3]], dirs: &[[f32; 3]], rays_per_pixel: u32, seed: u32) -> RgbImage {
+        let n = rays_per_pixel as usize * self.camera.screen_height as usize * self.camera.screen_width as usize;
+        assert_eq!(origins.len(), n, "mi_rt: the origins table must hold rays_per_pixel * height * width rays");
+        assert_eq!(dirs.len(), n, "mi_rt: the dirs table must hold rays_per_pixel * height * width rays");
+        let cam = self.camera.flatten();
+        let opts = mi_rt::mi_render_opts { seed: seed, rank: 0, world: 1, ..Default::default() };
+        let mut img = RgbImage::new(self.camera.screen_width, self.camera.screen_height);
+        let (po, pd, pimg) = (origins.as_ptr() as *const f32, dirs.as_ptr() as *const f32, img.as_mut_ptr());
+        self.with_gpu_scene(|ctx| unsafe {
+            mi_rt::mi_render_rays(ctx, &cam, &opts, po, pd, rays_per_pixel, std::ptr::null_mut(), pimg, std::ptr::null_mut(), std::ptr::null_mut())
+        });
+        img
+    }
+
     /// flatten -> context on device 0 -> upload -> `call` -> destroy; panics with the library's message on failure.
     fn with_gpu_scene<F: FnOnce(*mut mi_rt::mi_ctx) -> i32>(&self, call: F) {
         let sb = self.flatten_scene();

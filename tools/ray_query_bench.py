@@ -18,7 +18,13 @@ mi_last_kernel_ms for each).  Ray sets: `camera` and `bounce` as above, and
            light, per-ray ray_t_max = the distance to that point - 1e-3.  The visibility form has one scalar interval per call and would
            need one call per distinct distance (about as many as rays), so it runs ONCE with t_max = +inf.  A longer interval can only
            add box and triangle work to a closest-hit walk, so on this row the comparison is generous to the any-hit query, and the two
-           do not answer the same question; the visibility row says so ("t_max": "inf (scalar)")."""
+           do not answer the same question; the visibility row says so ("t_max": "inf (scalar)").
+
+--mode render compares ray-table rendering (mi_render_rays_device: the wavefront pipeline fed from a table) with mi_shade_rays_device (the
+recursive kernel) on the same rays: one table per scene built from the `camera` rays above, rays_per_pixel = 1.  In one context: the
+shade query on the table's rays, then the table render with aa_sample_count = 1 and with 16; for each 5 warm-up calls, then --calls
+timed calls, median / min / max of mi_last_kernel_ms and Msamples/s (rays x aa_sample_count) from the median.  Context for users, not
+a pass bar."""
 import argparse
 import json
 import os
@@ -126,6 +132,49 @@ def occlusion_rows(ctx, cfg, sc, co, cd, bo, bd, hitpoints, calls, warmup):
     return rows
 
 
+def render_rows(ctx, cfg, sc, co, cd, calls, warmup):
+    """mi_shade_rays_device on the pixel-centre rays, then mi_render_rays_device on the same rays as a one-row table, at 1 and 16 spp."""
+    from cs397raytracingsp22_amd import dist as pdist
+    dev = torch.device("cuda:0")
+    cam = sc.camera
+    W, H = cam.screen_width, cam.screen_height
+    n = len(co)
+    assert n == W * H
+    t_o, t_d = torch.from_numpy(co).to(dev), torch.from_numpy(cd).to(dev)          # [H*W, 3] row-major = a table [1][H][W][3]
+    t_rgb = torch.empty((n, 3), dtype=torch.float32, device=dev)
+    t_compact = torch.empty((pdist.tiles_padded(W, H, 1) * pdist.TILE_PIXELS, 3), dtype=torch.float32, device=dev)
+    torch.cuda.synchronize()
+
+    def timed(call):
+        ms = []
+        for k in range(warmup + calls):
+            call()
+            torch.cuda.synchronize()
+            if k >= warmup:
+                ms.append(ctx.last_kernel_ms())
+        return ms
+
+    rows = []
+
+    def report(query, aa, ms, extra):
+        med = float(np.median(ms))
+        row = dict({"config": cfg, "mode": "render", "query": query, "n_rays": n, "aa_sample_count": aa, "path_depth": cam.path_depth,
+                    "calls": calls, "kernel_ms_median": round(med, 4), "kernel_ms_min": round(float(np.min(ms)), 4),
+                    "kernel_ms_max": round(float(np.max(ms)), 4), "msamples_per_s_kernel": round(n * aa / med / 1e3, 1)}, **extra)
+        rows.append(row)
+        print(json.dumps(row), flush=True)
+
+    cam.aa_sample_count = 1
+    ms = timed(lambda: ctx.shade_rays_device(cam, n, t_o.data_ptr(), t_d.data_ptr(), t_rgb.data_ptr(), seed=1, first_key=0))
+    report("shade_rays", 1, ms, {"mean_radiance": round(float(t_rgb.mean().item()), 6)})
+    for aa in (1, 16):
+        cam.aa_sample_count = aa
+        ms = timed(lambda: ctx.render_rays_device(cam, t_o.data_ptr(), t_d.data_ptr(), 1, t_compact.data_ptr(), seed=1))
+        report("render_rays", aa, ms, {"mean_radiance_compact": round(float(t_compact.mean().item()), 6),
+                                       "segments": ctx.last_pipeline_counts()["segments"]})
+    return rows
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--calls", type=int, default=20, help="timed calls per row (at least 20)")
@@ -133,8 +182,9 @@ def main():
     ap.add_argument("--width", type=int, default=1920)
     ap.add_argument("--height", type=int, default=1080)
     ap.add_argument("--configs", default="2,4")
-    ap.add_argument("--mode", choices=("intersect", "occlusion"), default="intersect",
-                    help="intersect: the closest-hit rows; occlusion: the any-hit query against the visibility form")
+    ap.add_argument("--mode", choices=("intersect", "occlusion", "render"), default="intersect",
+                    help="intersect: the closest-hit rows; occlusion: the any-hit query against the visibility form; "
+                         "render: ray-table rendering against mi_shade_rays_device")
     ap.add_argument("--out", default=None, help="also append the JSON lines to this file")
     a = ap.parse_args()
     if a.calls < 20:
@@ -147,6 +197,9 @@ def main():
         sc = {2: scenes.config2, 4: scenes.config4}[cfg](a.width, a.height, 1, 10)
         ctx.upload(sc.flatten())
         co, cd = pinhole_rays(sc.camera)
+        if a.mode == "render":
+            rows += render_rows(ctx, cfg, sc, co, cd, a.calls, a.warmup)
+            continue
         first = ctx.intersect_rays(co, cd, t_max=sc.camera.max_trace_dist)
         hit = first.object >= 0
         rng = np.random.default_rng(1)
