@@ -74,11 +74,10 @@ int pt::fail(int code, const char* fmt, ...) {
         if (rc_ != MI_OK) return rc_;                                                          \
     } while (0)
 
-namespace {
-inline uint32_t lowbias32(uint32_t x) {
-    x ^= x >> 16; x *= 0x7feb352du; x ^= x >> 15; x *= 0x846ca68bu; x ^= x >> 16; return x;
+// the kernels' seed_key of a caller's seed: lowbias32(seed ^ 0x68e31da4)
+static uint32_t seed_key(uint32_t x) {
+    x ^= 0x68e31da4u; x ^= x >> 16; x *= 0x7feb352du; x ^= x >> 15; x *= 0x846ca68bu; x ^= x >> 16; return x;
 }
-}  // namespace
 
 // ------------------------------------------------------------------ context
 struct mi_ctx {
@@ -136,19 +135,14 @@ struct mi_ctx {
         uint32_t vote_t = 2, vote_a = 1, k_steps = 8;   // voted megakernel
         uint32_t lds_pad = 0;                           // occupancy experiments
         uint32_t refill_min = 16;                       // wf_trav: refill idle lanes when at least this many are idle (A/B round 2: 32 / 16 / 8 -> 36.9 / 35.8 / 38.6 ms on cfg2)
-        uint32_t fuse_max = 0, fuse_min = 32;           // wf_main: in-launch continuation (rounds: 0 = automatic; lanes needed)
         int trav_lds = -1;                              // reference-tree walker override, a WalkerPlan form (-1 = automatic)
         int trav_bpc = 0;                               // its blocks per CU override (0 = automatic)
-        int travf_bpc = 0;                              // wf_trav_f blocks per CU override (0 = default)
         int kernel_timing = -1;                         // per-launch HIP events: -1 = single-rank renders only
         bool global_bvh = false;                        // never stage a BVH in LDS
         bool wf_stamps = false;                         // -DPT_WF_STAMPS builds: collect wf_main phase stamps
         bool debug_mask = false;                        // print tile-mask statistics
         bool dump_launches = false;                     // print every pipeline launch's duration (needs per-launch events)
-        int split = 1;                                  // wf_main in two parts, class A beside the previous pass' walkers (0 = one launch per pass)
-        int conc = 1, conc_trav_bpc = 0, conc_travf_bpc = 0;   // wf_trav and wf_trav_f on two streams (0 = one after the other); their blocks per CU then (0 = the usual)
-        uint32_t tail_paths = 0xffffffffu;              // a pass that starts with at most this many live paths runs every path as far as it can inside the launch (0 = never; default: automatic)
-        uint32_t nowait_blocks = 16384;                 // passes whose grid bound is at most this many blocks are launched without waiting for the previous header (0 = always wait)
+        ScheduleKnobs sched;                            // the pass schedule's knobs (render_plan.hpp)
         uint32_t spin_timeout_ms = 120000;              // header wait: give up after this long without progress
     } tune;
 };
@@ -160,6 +154,13 @@ static int ensure(void** p, size_t* have, size_t want) {
     if (e != hipSuccess) return fail(MI_ERR_OOM, "hipMalloc(%zu) failed: %s", want, hipGetErrorString(e));
     *have = want;
     return MI_OK;
+}
+
+// Is the whole BVH (nodes + triangles) staged in LDS (the K1 megakernels, the ray queries)?  Sets the counts `a` carries (0: walk global memory).
+template <class A> static bool stage_in_lds(const mi_ctx* c, A& a) {
+    const bool lds = c->S.n_meshes > 0 && c->scene.lds_bytes <= 64u * 1024u && !c->tune.global_bvh;
+    a.lds_nodes = lds ? (uint32_t)c->S.n_nodes : 0u; a.lds_tris = lds ? (uint32_t)c->S.n_tris : 0u;
+    return lds;
 }
 
 extern "C" int mi_abi_version(void) { return MI_RT_ABI_VERSION; }
@@ -203,10 +204,10 @@ static int ctx_init(mi_ctx* c, const hipDeviceProp_t& prop) {
     env_u("MI_RT_VOTE_T", t.vote_t); env_u("MI_RT_VOTE_A", t.vote_a); env_u("MI_RT_KSTEPS", t.k_steps);
     if (const char* e = getenv("MI_RT_LDS_PAD_KB")) t.lds_pad = (uint32_t)atoi(e) * 1024u;
     env_u("MI_RT_WF_REFILL", t.refill_min);
-    env_u("MI_RT_WF_FUSE_MAX", t.fuse_max); env_u("MI_RT_WF_FUSE_MIN", t.fuse_min);
-    env_i("MI_RT_WF_SPLIT", t.split); env_u("MI_RT_WF_NOWAIT_BLOCKS", t.nowait_blocks); env_u("MI_RT_WF_TAIL_PATHS", t.tail_paths);
-    env_i("MI_RT_WF_CONC", t.conc); env_i("MI_RT_WF_CONC_TRAV_BPC", t.conc_trav_bpc); env_i("MI_RT_WF_CONC_TRAVF_BPC", t.conc_travf_bpc);
-    env_i("MI_RT_WF_TRAV_LDS", t.trav_lds); env_i("MI_RT_WF_TRAV_BPC", t.trav_bpc); env_i("MI_RT_WF_TRAVF_BPC", t.travf_bpc); env_i("MI_RT_WF_KERNEL_TIMING", t.kernel_timing);
+    env_u("MI_RT_WF_FUSE_MAX", t.sched.fuse_max); env_u("MI_RT_WF_FUSE_MIN", t.sched.fuse_min);
+    env_i("MI_RT_WF_SPLIT", t.sched.split); env_u("MI_RT_WF_NOWAIT_BLOCKS", t.sched.nowait_blocks); env_u("MI_RT_WF_TAIL_PATHS", t.sched.tail_paths);
+    env_i("MI_RT_WF_CONC", t.sched.conc); env_i("MI_RT_WF_CONC_TRAV_BPC", t.sched.conc_trav_bpc); env_i("MI_RT_WF_CONC_TRAVF_BPC", t.sched.conc_travf_bpc);
+    env_i("MI_RT_WF_TRAV_LDS", t.trav_lds); env_i("MI_RT_WF_TRAV_BPC", t.trav_bpc); env_i("MI_RT_WF_TRAVF_BPC", t.sched.travf_bpc); env_i("MI_RT_WF_KERNEL_TIMING", t.kernel_timing);
     t.global_bvh = getenv("MI_RT_GLOBAL_BVH") != nullptr;
     t.wf_stamps = getenv("MI_RT_WF_STAMPS") != nullptr;
     t.debug_mask = getenv("MI_RT_DEBUG_MASK") != nullptr;
@@ -319,8 +320,7 @@ extern "C" int mi_compact_size(const mi_camera_desc* cam, int32_t world, uint32_
 // wf_main, wf_prefix (device-side bookkeeping of the shard counters), wf_trav.  It needs one number back
 // per iteration — the grid of the next wf_main — which arrives on a second stream while wf_trav runs, so
 // the compute stream never waits for the host; the call still returns only when the frame is done.
-// Memory and batch size: render_plan.cpp (wf_first_batch, wf_batch).
-static const int kRunAhead = 3;        // passes the host may launch before it has read the header of an earlier one
+// Memory and batch size (wf_first_batch, wf_batch) and every scheduling decision (pass_schedule, pass_gate, plan_pass): render_plan.cpp.
 
 // Allocates the buffers of a batch of s_batch samples (a.npix set), halving the batch while an allocation fails.
 static int wf_alloc(mi_ctx* c, WfArgs& a, bool two_stage, uint32_t& s_batch) {
@@ -391,7 +391,6 @@ static int device_tile_masks(mi_ctx* c, const mi_camera_desc* cam, uint32_t flag
 
 // Headers: wf_prefix stores the header of every pass (pt_device.h kHdr*) into a RING of pinned host slots (slot = seq % kHdrRing),
 // so the host may run a few passes ahead of the device and still read every header.
-struct PassHdr { uint32_t blocks, live, queue, live_b, blocks_a, segments; };
 class HeaderRing {
 public:
     HeaderRing(const mi_ctx* c, hipStream_t stream) : h_((const volatile uint32_t*)c->h_hdr), stream_(stream), timeout_ms_(c->tune.spin_timeout_ms) {}
@@ -493,25 +492,14 @@ static int render_tiles_wavefront(mi_ctx* c, const K1Args& k, const mi_camera_de
     a.diag = nullptr;           // developer builds (-DPT_WF_STAMPS): phase stamps of wf_main
     if (c->tune.wf_stamps) { a.diag = c->d_diag; HIP_TRY(hipMemsetAsync(c->d_diag, 0, 16 * sizeof(unsigned long long), stream)); }
     a.refill_min = c->tune.refill_min;
-    // further shade + intersect rounds inside one wf_main launch: one when meshes park part of every wave's rays for the walker
-    // (cfg2: 1 / 2 / 3 rounds -> 99 / 101 / 103 ms), two in a scene without meshes, where every live lane can go on
-    // (cfg5 at 512 spp: 1 / 2 / 3 / 5 rounds -> 281.6 / 271.8 / 278.4 / 287.7 ms; the cfg1 scene at 1080p: 46.6 / 42.9 / 47.4 / 48.1 ms)
-    a.fuse_max = c->tune.fuse_max ? c->tune.fuse_max : (c->S.n_meshes == 0 ? 2u : 1u);
-    a.fuse_min = c->tune.fuse_min < 1 ? 1 : c->tune.fuse_min;
-    const uint32_t fuse_max_normal = a.fuse_max, fuse_min_normal = a.fuse_min;
-    // Which meshes are walked how: the two-stage meshes (wf_trav_f + wf_replay), the rest through the reference's tree (wf_trav).
-    const uint32_t all_meshes = c->S.n_meshes >= 32 ? 0xffffffffu : ((1u << c->S.n_meshes) - 1u);
-    const uint32_t ts_mask = two_stage_mask(c->scene, flags) & all_meshes;
-    const uint32_t ref_mask = all_meshes & ~ts_mask;
-    const WalkerPlan walker = plan_walker(c->scene, ref_mask, c->tune.trav_lds, c->tune.trav_bpc, c->tune.global_bvh);
+    const WalkMasks masks = walk_masks(c->scene, flags);
+    const WalkerPlan walker = plan_walker(c->scene, masks.ref, c->tune.trav_lds, c->tune.trav_bpc, c->tune.global_bvh);
+    const PassSchedule sched = pass_schedule(c->scene, masks, walker, c->n_cus, cam->path_depth, c->tune.sched);
     a.R.lds_nodes = walker.lds_nodes; a.R.lds_tris = walker.lds_tris;
     a.cand = (uint2*)c->d_cand; a.cand_hdr = (uint2*)c->d_cand_hdr;
     float4* bufs[2] = { (float4*)c->d_wf_a, (float4*)c->d_wf_b };
-    const uint32_t trav_bpc = walker.blocks_per_cu;
-    const uint32_t trav_blocks = (uint32_t)c->n_cus * trav_bpc;
-    const uint32_t travf_blocks = (uint32_t)c->n_cus * (c->tune.travf_bpc > 0 ? (uint32_t)c->tune.travf_bpc : 6u), replay_blocks = (uint32_t)c->n_cus * 8u;
-    const uint32_t conc_trav_bpc = c->tune.conc_trav_bpc > 0 ? (uint32_t)c->tune.conc_trav_bpc : trav_bpc;
-    const uint32_t conc_travf_bpc = c->tune.conc_travf_bpc > 0 ? (uint32_t)c->tune.conc_travf_bpc : travf_blocks / (uint32_t)c->n_cus;
+    const bool sig = d_sig != nullptr, gv = c->scene.gen_volumes, tex = c->scene.mesh_maps;
+    const hipStream_t aux = c->aux_stream, travf_stream = sched.side_by_side ? c->aux2_stream : stream;
 
     // one event pair per launch (LaunchTimer): single-rank renders only, unless asked
     LaunchTimer timer(c, c->tune.kernel_timing >= 0 ? c->tune.kernel_timing != 0 : a.R.world == 1);
@@ -521,7 +509,6 @@ static int render_tiles_wavefront(mi_ctx* c, const K1Args& k, const mi_camera_de
     counts[4] = (uint64_t)a.npix * (range.end - range.begin); counts[5] = a.npix;
     // samples of dead tiles (nothing reachable from the tile: no ray is generated, no slot written or read) — only without signatures
     if (a.tile_mask && !d_sig) counts[7] = dead_pixels(tile_grid(cam, a.R.world), cam, a.R.rank, a.R.world, c->masks.words) * (range.end - range.begin);
-    const bool have_walkers = ref_mask || ts_mask || c->S.n_meshes > 32;
     for (uint32_t s0 = range.begin; s0 < range.end; s0 += s_batch) {
         a.s_base = s0; a.s_count = (s0 + s_batch <= range.end) ? s_batch : (range.end - s0);
         int cur = 0;
@@ -530,7 +517,7 @@ static int render_tiles_wavefront(mi_ctx* c, const K1Args& k, const mi_camera_de
         HIP_TRY(hipMemsetAsync(cnt, 0, wfcnt::zeroed * sizeof(uint32_t), stream));   // wf_prefix re-zeroes them after every pass
         const uint32_t seq0 = c->hdr_seq + 1u;          // seq of this batch's pass 0
         uint32_t seen = 0;                              // headers of passes [0, seen) have been read
-        PassHdr last = { (a.n_in + kBlock - 1) / kBlock, a.n_in, 0u, 0u, 0u, 0u };      // "header of pass -1": the camera rays
+        PassHdr last = camera_pass_header(a.n_in);
         bool all_dead = false;
         auto consume = [&](bool count_it) {             // read header `seen` (it has arrived)
             last = ring.read(seq0 + seen);
@@ -543,57 +530,27 @@ static int render_tiles_wavefront(mi_ctx* c, const K1Args& k, const mi_camera_de
         for (; it <= cam->path_depth + 1u; it++) {
             while (seen < it && !all_dead && ring.ready(seq0 + seen)) consume(true);
             if (all_dead) break;
-            // The grid of pass `it` comes from the header of pass it - 1.  While that pass is still running the host would
-            // have to wait for it (the header is on its way while the walkers run, so for a big pass the wait is hidden); a SMALL
-            // pass is launched at once instead, on a grid that is an upper bound — live paths only decrease, and every (class,
-            // shard) list may end in a partial block — whose surplus blocks leave at their first instruction (wf_main compares
-            // its block number with the device-side table).  The host runs at most kRunAhead passes ahead of the headers.
-            bool exact = seen == it;
-            if (!exact) {
-                const uint64_t bound = (uint64_t)last.live / kBlock + 2u * (uint64_t)kWfShards;
-                if (c->tune.nowait_blocks == 0 || bound > (uint64_t)c->tune.nowait_blocks || it - seen > (uint32_t)kRunAhead) {
-                    while (seen < it && !all_dead) { MI_TRY(ring.wait(seq0 + seen)); consume(true); }
-                    if (all_dead) break;
-                    exact = true;
-                }
+            const PassGate gate = pass_gate(sched, it, seen, last.live);
+            if (gate == PassGate::kWait) {
+                while (seen < it && !all_dead) { MI_TRY(ring.wait(seq0 + seen)); consume(true); }
+                if (all_dead) break;
             }
-            uint32_t grid_all, grid_a;
-            if (exact) { grid_all = last.blocks; grid_a = last.blocks_a; }
-            else { grid_all = grid_a = (uint32_t)((uint64_t)last.live / kBlock) + 2u * (uint32_t)kWfShards; }
-            if (it == 0) { grid_all = last.blocks; grid_a = 0; }
-            if (grid_all == 0) break;
-            // THE TAIL.  Once the live paths no longer fill the chip (last.live bounds this pass' input: paths only end), thin waves
-            // cost nothing — there is nobody to give their lanes to — while every further pass costs two launches and a header.
-            // So each wave keeps shading as long as ANY of its lanes can go on (a path that enters a mesh root still parks for
-            // the walker).  Per path the operations and their order are those of the pass-by-pass schedule.  Without meshes
-            // nothing ever parks: this launch ends every path and is the last one.
-            // Threshold (MI_RT_WF_TAIL_PATHS): without meshes 4 Mi paths, the size below which passes are launched without waiting
-            // (cfg1 as BASELINE states it, 400x400 / 16 spp: 0.64 ms at 0, 0.55 at 64 Ki ... 2 Mi, 0.49 from 3 Mi on; cfg1 / cfg5 at
-            // 1080p unchanged up to 8 Mi); with meshes 1 Mi (a 1/8 share of cfg2: 11.0 ms up to 2 Mi, 11.1 at 4 Mi, 11.3 at 8 Mi).
-            const uint32_t tail_paths = c->tune.tail_paths != 0xffffffffu ? c->tune.tail_paths : (have_walkers ? (1u << 20) : (4u << 20));
-            const bool tail = it > 0 && tail_paths != 0 && last.live <= tail_paths;      // (the camera pass in this form too: 0.49 -> 0.58 ms on cfg1 as stated)
-            a.fuse_max = tail ? cam->path_depth + 2u : fuse_max_normal;
-            a.fuse_min = tail ? 1u : fuse_min_normal;
-            a.st_in = a.iter0 ? nullptr : bufs[cur];
-            a.st_out = bufs[cur ^ 1];
-            a.n_blocks_in = grid_all;
-            // A pass after the first is launched in TWO PARTS.  Its class-A blocks (paths whose pending hit is a plain Triangle /
-            // Plane: nothing a walker could still change) go to a second stream, ordered only behind the previous pass' wf_prefix:
-            // they fill the CUs the persistent walkers of that pass leave idle as their queue runs out (a walker launch ends
-            // with ~0.1 ms of tail whatever its queue size, eleven times per frame and per rank).  The class-B blocks follow the
-            // walkers on the main stream; wf_prefix waits for both parts.  Same blocks, same work, another schedule.
-            const bool split = !a.iter0 && have_walkers && c->tune.split != 0 && (exact ? (grid_a >= 64u && grid_a < grid_all) : true);
-            if (split) {
-                HIP_TRY(hipStreamWaitEvent(c->aux_stream, c->ev_pfx, 0));
+            const PassPlan p = plan_pass(sched, it, gate != PassGate::kBound, last);
+            if (p.stop) break;
+            a.fuse_max = p.fuse_max; a.fuse_min = p.fuse_min;
+            a.st_in = a.iter0 ? nullptr : bufs[cur]; a.st_out = bufs[cur ^ 1];
+            a.n_blocks_in = p.grid_all;
+            if (p.split) {                      // class A beside the previous pass' walkers, class B behind them
+                HIP_TRY(hipStreamWaitEvent(aux, c->ev_pfx, 0));
                 a.part = 1;
-                MI_TRY(timer.run(kMainA, c->aux_stream, [&] { return launch_wf_main(a, grid_a, d_sig != nullptr, c->scene.gen_volumes, c->scene.mesh_maps, c->aux_stream); }));     // its span includes waiting for CUs
-                HIP_TRY(hipEventRecord(c->ev_part, c->aux_stream));
+                MI_TRY(timer.run(kMainA, aux, [&] { return launch_wf_main(a, p.grid_a, sig, gv, tex, aux); }));     // its span includes waiting for CUs
+                HIP_TRY(hipEventRecord(c->ev_part, aux));
                 a.part = 2;
-                MI_TRY(timer.run(kMain, stream, [&] { return launch_wf_main(a, exact ? grid_all - grid_a : grid_all, d_sig != nullptr, c->scene.gen_volumes, c->scene.mesh_maps, stream); }));
+                MI_TRY(timer.run(kMain, stream, [&] { return launch_wf_main(a, p.grid_b, sig, gv, tex, stream); }));
                 HIP_TRY(hipStreamWaitEvent(stream, c->ev_part, 0));
             } else {
                 a.part = 0;
-                MI_TRY(timer.run(kMain, stream, [&] { return launch_wf_main(a, grid_all, d_sig != nullptr, c->scene.gen_volumes, c->scene.mesh_maps, stream); }));
+                MI_TRY(timer.run(kMain, stream, [&] { return launch_wf_main(a, p.grid_all, sig, gv, tex, stream); }));
             }
             // device-side bookkeeping: tables for the next pass and for wf_trav, and the header the host needs (grid of the
             // next pass, anything alive?), which wf_prefix stores straight into pinned host memory: the compute stream never
@@ -601,42 +558,31 @@ static int render_tiles_wavefront(mi_ctx* c, const K1Args& k, const mi_camera_de
             const uint32_t seq = ++c->hdr_seq;
             HIP_TRY(launch_wf_prefix(cnt + wfcnt::out_count, cnt + wfcnt::trav_count, cnt + wfcnt::in_count, cnt + wfcnt::in_blkpfx, cnt + wfcnt::trav_pfx,
                                      cnt + wfcnt::hdr, c->h_hdr_dev + HeaderRing::slot(seq), seq, stream));
-            if (have_walkers && c->tune.split != 0) HIP_TRY(hipEventRecord(c->ev_pfx, stream));
+            if (sched.split_enabled) HIP_TRY(hipEventRecord(c->ev_pfx, stream));
             // persistent walkers; they leave at once when the queue is empty.  Successive launches merge their meshes' hits
             // into the hit record (strictly closer wins, ties go to the lower Scene.objects index: order-independent)
-            const bool ref_walk = ref_mask || c->S.n_meshes > 32;      // meshes 32, 33, ... have no mask bit: they always take the reference walk
-            // Meshes of both kinds: wf_trav and wf_trav_f read the same work list and write different things (the hit record / the
-            // candidate lists; each has its own cursor), so they go to two streams and wf_replay, which merges into the hit
-            // record, follows both.  With full grids the F-tree walkers move in as the reference walkers run out of queue and leave
-            // (HEAD 98.5 -> 96.5 ms).  Sharing every CU from the start — half the wave slots each — gains nothing: 68 ms for the
-            // pair, exactly the 43 + 25 ms they take one after the other (VALU issue 0.71 + 0.34: together they saturate it).
-            const bool side_by_side = ref_walk && ts_mask && c->tune.conc != 0;
-            if (side_by_side) {
+            if (sched.side_by_side) {           // wf_trav_f on its own stream, beside wf_trav
                 HIP_TRY(hipEventRecord(c->ev_pfx, stream));
-                HIP_TRY(hipStreamWaitEvent(c->aux2_stream, c->ev_pfx, 0));
+                HIP_TRY(hipStreamWaitEvent(travf_stream, c->ev_pfx, 0));
             }
-            if (ref_walk) {
-                a.trav_mask = ref_mask;
-                const uint32_t blocks = side_by_side ? (uint32_t)c->n_cus * conc_trav_bpc : trav_blocks;
-                MI_TRY(timer.run(kTrav, stream, [&] { return launch_walker(a, walker, blocks, &c->big_lds_enabled, stream); }));
+            if (sched.ref_walk) {
+                a.trav_mask = sched.ref_mask;
+                MI_TRY(timer.run(kTrav, stream, [&] { return launch_walker(a, walker, sched.walker_blocks, &c->big_lds_enabled, stream); }));
             }
-            if (ts_mask) {
-                a.trav_mask = ts_mask;
+            if (sched.ts_mask) {
+                a.trav_mask = sched.ts_mask;
                 // wf_filter_f keeps the class-B paths whose ray enters a two-stage mesh's root box; wf_trav_f and wf_replay work on that list
-                if (side_by_side) {
-                    MI_TRY(timer.run(kTravF, c->aux2_stream, [&] { return launch_wf_filter_f(a, 8u, c->aux2_stream); }));
-                    MI_TRY(timer.run(kTravF, c->aux2_stream, [&] { return launch_wf_trav_f(a, (uint32_t)c->n_cus * conc_travf_bpc, c->aux2_stream); }));
-                    HIP_TRY(hipEventRecord(c->ev_travf, c->aux2_stream));
+                MI_TRY(timer.run(kTravF, travf_stream, [&] { return launch_wf_filter_f(a, sched.filter_blocks_per_shard, travf_stream); }));
+                MI_TRY(timer.run(kTravF, travf_stream, [&] { return launch_wf_trav_f(a, sched.travf_blocks, travf_stream); }));
+                if (sched.side_by_side) {
+                    HIP_TRY(hipEventRecord(c->ev_travf, travf_stream));
                     HIP_TRY(hipStreamWaitEvent(stream, c->ev_travf, 0));
-                } else {
-                    MI_TRY(timer.run(kTravF, stream, [&] { return launch_wf_filter_f(a, 8u, stream); }));
-                    MI_TRY(timer.run(kTravF, stream, [&] { return launch_wf_trav_f(a, travf_blocks, stream); }));
                 }
-                MI_TRY(timer.run(kReplay, stream, [&] { return launch_wf_replay(a, replay_blocks, stream); }));
+                MI_TRY(timer.run(kReplay, stream, [&] { return launch_wf_replay(a, sched.replay_blocks, stream); }));
             }
             cur ^= 1;
             a.iter0 = 0;
-            if (tail && !have_walkers) { it++; break; }
+            if (p.last) { it++; break; }
         }
         MI_TRY(timer.run(kReduce, stream, [&] { return launch_wf_reduce(a, s0 == 0, s0 + a.s_count >= spp, stream); }));
         // the headers not read yet (statistics; passes launched behind the one that ended every path are not counted)
@@ -682,10 +628,8 @@ static int render_tiles(mi_ctx* c, const mi_camera_desc* cam, const mi_render_op
     a.R.seed = o->seed; a.R.rank = o->rank; a.R.world = o->world;
     a.R.tiles_x = g.tx; a.R.tiles_y = g.ty; a.R.tiles_total = g.total;
     a.R.my_tiles = rank_tiles(g, o->rank, o->world);
-    bool lds = c->S.n_meshes > 0 && c->scene.lds_bytes <= 64u * 1024u && !c->tune.global_bvh;
-    a.R.lds_nodes = lds ? (uint32_t)c->S.n_nodes : 0;
-    a.R.lds_tris = lds ? (uint32_t)c->S.n_tris : 0;
-    a.seed_key = lowbias32(o->seed ^ 0x68e31da4u);
+    const bool lds = stage_in_lds(c, a.R);
+    a.seed_key = seed_key(o->seed);
     a.out = d_compact;
     a.sig = (o->want_signature && d_sig) ? d_sig : nullptr;
     int variant = o->variant == MI_VARIANT_DEFAULT ? MI_VARIANT_WAVEFRONT : o->variant;
@@ -779,35 +723,64 @@ extern "C" int mi_last_kernel_ms(mi_ctx* c, float* ms) {
 // timing events and return; they own no device memory.  The host forms move one chunk of rays at a time through a buffer of their own
 // (never the wavefront pipeline's reserved ones) and advance first_key per chunk — the same answers as one call, by the keying.
 static const uint32_t kRqChunk = 1u << 18;      // rays per chunk of the host-pointer forms: 27 MB of device scratch for a full intersect query
+// The device forms: one kernel on `stream` between the context's timing events
+#define RQ_LAUNCH_TIMED(c, stream, launch)                                                     \
+    do {                                                                                       \
+        HIP_TRY(hipEventRecord(c->ev_start, stream));                                          \
+        HIP_TRY(launch);                                                                       \
+        HIP_TRY(hipEventRecord(c->ev_stop, stream));                                           \
+        c->ev_recorded = true; c->ms_summed = false;                                           \
+    } while (0)
+// The host forms.  A per-ray column of the caller's: `bytes` per ray at `host` (nullptr: an optional column that is absent), uploaded before
+// the launch or (`out`) downloaded after it.  rq_chunked carves d_rq into one array of a chunk per column, in the order given, and for every
+// chunk uploads, calls launch(first, n, dev) — dev[i] = column i's device array, nullptr when absent — downloads and synchronises.
+struct RqColumn { const void* host; size_t bytes; bool out; };
+template <size_t N, class Launch> static int rq_chunked(mi_ctx* c, uint32_t n_rays, const RqColumn (&cols)[N], Launch launch) {
+    if (n_rays == 0) return MI_OK;
+    HIP_TRY(hipSetDevice(c->device));
+    const size_t chunk = std::min<size_t>(n_rays, kRqChunk);
+    size_t off[N + 1] = { 0 };
+    for (size_t i = 0; i < N; i++) off[i + 1] = off[i] + chunk * cols[i].bytes;
+    MI_TRY(ensure(&c->d_rq, &c->rq_bytes, off[N]));
+    void* dev[N];
+    for (size_t i = 0; i < N; i++) dev[i] = cols[i].host ? (char*)c->d_rq + off[i] : nullptr;
+    float ms_sum = 0.0f, ms = 0.0f;
+    for (size_t first = 0; first < n_rays; first += chunk) {
+        const size_t n = std::min<size_t>(chunk, (size_t)n_rays - first);
+        for (size_t i = 0; i < N; i++) if (dev[i] && !cols[i].out)
+            HIP_TRY(hipMemcpyAsync(dev[i], (const char*)cols[i].host + first * cols[i].bytes, n * cols[i].bytes, hipMemcpyHostToDevice, c->stream));
+        MI_TRY(launch((uint32_t)first, (uint32_t)n, dev));
+        for (size_t i = 0; i < N; i++) if (dev[i] && cols[i].out)
+            HIP_TRY(hipMemcpyAsync((char*)cols[i].host + first * cols[i].bytes, dev[i], n * cols[i].bytes, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));          // the next chunk reuses the buffer
+        HIP_TRY(hipEventElapsedTime(&ms, c->ev_start, c->ev_stop));
+        ms_sum += ms;
+    }
+    c->ms_summed = true; c->ms_sum = ms_sum;              // mi_last_kernel_ms: the sum over the chunks
+    return MI_OK;
+}
 
 static int intersect_rays_device(mi_ctx* c, uint32_t n_rays, const float* origins, const float* dirs, float t_min, float t_max,
                                  uint32_t seed, uint32_t first_key, int32_t* out_object, float* out_distance, float* out_hitpoint,
                                  float* out_normal, int32_t* out_flags, float* out_uv, mi_material* out_material, hipStream_t stream) {
     RqArgs a;
     a.S = c->S;
-    const bool lds = c->S.n_meshes > 0 && c->scene.lds_bytes <= 64u * 1024u && !c->tune.global_bvh;
-    a.lds_nodes = lds ? (uint32_t)c->S.n_nodes : 0u;
-    a.lds_tris = lds ? (uint32_t)c->S.n_tris : 0u;
-    a.seed_key = lowbias32(seed ^ 0x68e31da4u);
+    const bool lds = stage_in_lds(c, a);
+    a.seed_key = seed_key(seed);
     a.first_key = first_key; a.n_rays = n_rays; a.t_min = t_min; a.t_max = t_max;
     a.origins = origins; a.dirs = dirs;
     a.out_object = out_object; a.out_distance = out_distance; a.out_hitpoint = out_hitpoint; a.out_normal = out_normal;
     a.out_flags = out_flags; a.out_uv = out_uv; a.out_material = (uint32_t*)out_material;
     const bool resolve = out_hitpoint || out_normal || out_flags || out_uv || out_material;     // else the visibility form
-    HIP_TRY(hipEventRecord(c->ev_start, stream));
-    HIP_TRY(launch_rq_intersect(a, lds, c->scene.gen_volumes, resolve, c->scene.lds_bytes, c->n_cus, stream));
-    HIP_TRY(hipEventRecord(c->ev_stop, stream));
-    c->ev_recorded = true; c->ms_summed = false;
+    RQ_LAUNCH_TIMED(c, stream, launch_rq_intersect(a, lds, c->scene.gen_volumes, resolve, c->scene.lds_bytes, c->n_cus, stream));
     return MI_OK;
 }
 
-static int check_intersect_args(mi_ctx* c, uint32_t n_rays, const float* origins, const float* dirs, float t_min, float t_max,
-                                const int32_t* out_object) {
-    if (!c) return fail(MI_ERR_INVALID, "ctx is NULL");
-    if (!origins || !dirs || !out_object) return fail(MI_ERR_INVALID, "mi_intersect_rays: origins, dirs and out_object are required");
-    if (t_min != t_min || t_max != t_max) return fail(MI_ERR_INVALID, "mi_intersect_rays: t_min / t_max is NaN");
+static int check_interval_args(const char* who, const char* out_name, mi_ctx* c, const float* origins, const float* dirs, float t_min, float t_max, const void* out) {
+    if (!c) return fail(MI_ERR_INVALID, "ctx is NULL");      // (the intersect and the occluded query check the same things)
+    if (!origins || !dirs || !out) return fail(MI_ERR_INVALID, "%s: origins, dirs and %s are required", who, out_name);
+    if (t_min != t_min || t_max != t_max) return fail(MI_ERR_INVALID, "%s: t_min / t_max is NaN", who);
     if (!c->have_scene) return fail(MI_ERR_NO_SCENE, "no scene uploaded");
-    (void)n_rays;
     return MI_OK;
 }
 
@@ -815,7 +788,7 @@ extern "C" int mi_intersect_rays_device(mi_ctx* c, uint32_t n_rays, const float*
                                         uint32_t seed, uint32_t first_key, int32_t* out_object, float* out_distance,
                                         float* out_hitpoint, float* out_normal, int32_t* out_flags, float* out_uv,
                                         mi_material* out_material, void* stream) {
-    MI_TRY(check_intersect_args(c, n_rays, origins, dirs, t_min, t_max, out_object));
+    MI_TRY(check_interval_args("mi_intersect_rays", "out_object", c, origins, dirs, t_min, t_max, out_object));
     if (n_rays == 0) return MI_OK;
     HIP_TRY(hipSetDevice(c->device));
     return intersect_rays_device(c, n_rays, origins, dirs, t_min, t_max, seed, first_key, out_object, out_distance, out_hitpoint,
@@ -825,40 +798,17 @@ extern "C" int mi_intersect_rays_device(mi_ctx* c, uint32_t n_rays, const float*
 extern "C" int mi_intersect_rays(mi_ctx* c, uint32_t n_rays, const float* origins, const float* dirs, float t_min, float t_max,
                                  uint32_t seed, uint32_t first_key, int32_t* out_object, float* out_distance, float* out_hitpoint,
                                  float* out_normal, int32_t* out_flags, float* out_uv, mi_material* out_material) {
-    MI_TRY(check_intersect_args(c, n_rays, origins, dirs, t_min, t_max, out_object));
-    if (n_rays == 0) return MI_OK;
-    HIP_TRY(hipSetDevice(c->device));
-    const size_t chunk = std::min<size_t>(n_rays, kRqChunk);
-    // one buffer, carved in 16-byte-friendly order: origins, dirs, hitpoint, normal (12 B each), material (40 B), uv (8 B), object, distance, flags
-    const size_t off_o = 0, off_d = off_o + chunk * 12, off_hp = off_d + chunk * 12, off_n = off_hp + chunk * 12, off_m = off_n + chunk * 12,
-                 off_uv = off_m + chunk * sizeof(mi_material), off_obj = off_uv + chunk * 8, off_t = off_obj + chunk * 4, off_f = off_t + chunk * 4,
-                 total = off_f + chunk * 4;
-    MI_TRY(ensure(&c->d_rq, &c->rq_bytes, total));
-    char* base = (char*)c->d_rq;
-    float ms_sum = 0.0f;
-    for (size_t first = 0; first < n_rays; first += chunk) {
-        const size_t n = std::min<size_t>(chunk, (size_t)n_rays - first);
-        HIP_TRY(hipMemcpyAsync(base + off_o, origins + 3 * first, n * 12, hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(hipMemcpyAsync(base + off_d, dirs + 3 * first, n * 12, hipMemcpyHostToDevice, c->stream));
-        MI_TRY(intersect_rays_device(c, (uint32_t)n, (const float*)(base + off_o), (const float*)(base + off_d), t_min, t_max, seed,
-                                     first_key + (uint32_t)first, (int32_t*)(base + off_obj), out_distance ? (float*)(base + off_t) : nullptr,
-                                     out_hitpoint ? (float*)(base + off_hp) : nullptr, out_normal ? (float*)(base + off_n) : nullptr,
-                                     out_flags ? (int32_t*)(base + off_f) : nullptr, out_uv ? (float*)(base + off_uv) : nullptr,
-                                     out_material ? (mi_material*)(base + off_m) : nullptr, c->stream));
-        HIP_TRY(hipMemcpyAsync(out_object + first, base + off_obj, n * 4, hipMemcpyDeviceToHost, c->stream));
-        if (out_distance) HIP_TRY(hipMemcpyAsync(out_distance + first, base + off_t, n * 4, hipMemcpyDeviceToHost, c->stream));
-        if (out_hitpoint) HIP_TRY(hipMemcpyAsync(out_hitpoint + 3 * first, base + off_hp, n * 12, hipMemcpyDeviceToHost, c->stream));
-        if (out_normal) HIP_TRY(hipMemcpyAsync(out_normal + 3 * first, base + off_n, n * 12, hipMemcpyDeviceToHost, c->stream));
-        if (out_flags) HIP_TRY(hipMemcpyAsync(out_flags + first, base + off_f, n * 4, hipMemcpyDeviceToHost, c->stream));
-        if (out_uv) HIP_TRY(hipMemcpyAsync(out_uv + 2 * first, base + off_uv, n * 8, hipMemcpyDeviceToHost, c->stream));
-        if (out_material) HIP_TRY(hipMemcpyAsync(out_material + first, base + off_m, n * sizeof(mi_material), hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(hipStreamSynchronize(c->stream));          // the next chunk reuses the buffer
-        float ms = 0.0f;
-        HIP_TRY(hipEventElapsedTime(&ms, c->ev_start, c->ev_stop));
-        ms_sum += ms;
-    }
-    c->ms_summed = true; c->ms_sum = ms_sum;
-    return MI_OK;
+    MI_TRY(check_interval_args("mi_intersect_rays", "out_object", c, origins, dirs, t_min, t_max, out_object));
+    // 16-byte-friendly order: the 12-byte columns, material (40 B), uv (8 B), then the 4-byte ones
+    enum { kO, kD, kHitpoint, kNormal, kMaterial, kUv, kObject, kDistance, kFlags };
+    const RqColumn cols[] = { { origins, 12, false }, { dirs, 12, false }, { out_hitpoint, 12, true }, { out_normal, 12, true },
+                              { out_material, sizeof(mi_material), true }, { out_uv, 8, true }, { out_object, 4, true },
+                              { out_distance, 4, true }, { out_flags, 4, true } };
+    return rq_chunked(c, n_rays, cols, [&](uint32_t first, uint32_t n, void* const* d) {
+        return intersect_rays_device(c, n, (const float*)d[kO], (const float*)d[kD], t_min, t_max, seed, first_key + first, (int32_t*)d[kObject],
+                                     (float*)d[kDistance], (float*)d[kHitpoint], (float*)d[kNormal], (int32_t*)d[kFlags], (float*)d[kUv],
+                                     (mi_material*)d[kMaterial], c->stream);
+    });
 }
 
 // mi_occluded_rays: the any-hit query (rq_occluded).  Same shape as the intersect pair; ray_t_max (may be NULL) replaces t_max per ray.
@@ -866,30 +816,17 @@ static int occluded_rays_device(mi_ctx* c, uint32_t n_rays, const float* origins
                                 const float* ray_t_max, uint32_t seed, uint32_t first_key, uint8_t* out_occluded, hipStream_t stream) {
     RqOccArgs a;
     a.S = c->S;
-    const bool lds = c->S.n_meshes > 0 && c->scene.lds_bytes <= 64u * 1024u && !c->tune.global_bvh;
-    a.lds_nodes = lds ? (uint32_t)c->S.n_nodes : 0u;
-    a.lds_tris = lds ? (uint32_t)c->S.n_tris : 0u;
-    a.seed_key = lowbias32(seed ^ 0x68e31da4u);
+    const bool lds = stage_in_lds(c, a);
+    a.seed_key = seed_key(seed);
     a.first_key = first_key; a.n_rays = n_rays; a.t_min = t_min; a.t_max = t_max;
     a.origins = origins; a.dirs = dirs; a.ray_t_max = ray_t_max; a.out_occluded = out_occluded;
-    HIP_TRY(hipEventRecord(c->ev_start, stream));
-    HIP_TRY(launch_rq_occluded(a, lds, c->scene.gen_volumes, c->scene.lds_bytes, c->n_cus, stream));
-    HIP_TRY(hipEventRecord(c->ev_stop, stream));
-    c->ev_recorded = true; c->ms_summed = false;
-    return MI_OK;
-}
-
-static int check_occluded_args(mi_ctx* c, const float* origins, const float* dirs, float t_min, float t_max, const uint8_t* out_occluded) {
-    if (!c) return fail(MI_ERR_INVALID, "ctx is NULL");
-    if (!origins || !dirs || !out_occluded) return fail(MI_ERR_INVALID, "mi_occluded_rays: origins, dirs and out_occluded are required");
-    if (t_min != t_min || t_max != t_max) return fail(MI_ERR_INVALID, "mi_occluded_rays: t_min / t_max is NaN");
-    if (!c->have_scene) return fail(MI_ERR_NO_SCENE, "no scene uploaded");
+    RQ_LAUNCH_TIMED(c, stream, launch_rq_occluded(a, lds, c->scene.gen_volumes, c->scene.lds_bytes, c->n_cus, stream));
     return MI_OK;
 }
 
 extern "C" int mi_occluded_rays_device(mi_ctx* c, uint32_t n_rays, const float* origins, const float* dirs, float t_min, float t_max,
                                        const float* ray_t_max, uint32_t seed, uint32_t first_key, uint8_t* out_occluded, void* stream) {
-    MI_TRY(check_occluded_args(c, origins, dirs, t_min, t_max, out_occluded));
+    MI_TRY(check_interval_args("mi_occluded_rays", "out_occluded", c, origins, dirs, t_min, t_max, out_occluded));
     if (n_rays == 0) return MI_OK;
     HIP_TRY(hipSetDevice(c->device));
     return occluded_rays_device(c, n_rays, origins, dirs, t_min, t_max, ray_t_max, seed, first_key, out_occluded, (hipStream_t)stream);
@@ -897,47 +834,26 @@ extern "C" int mi_occluded_rays_device(mi_ctx* c, uint32_t n_rays, const float* 
 
 extern "C" int mi_occluded_rays(mi_ctx* c, uint32_t n_rays, const float* origins, const float* dirs, float t_min, float t_max,
                                 const float* ray_t_max, uint32_t seed, uint32_t first_key, uint8_t* out_occluded) {
-    MI_TRY(check_occluded_args(c, origins, dirs, t_min, t_max, out_occluded));
+    MI_TRY(check_interval_args("mi_occluded_rays", "out_occluded", c, origins, dirs, t_min, t_max, out_occluded));
     if (ray_t_max)
         for (size_t i = 0; i < n_rays; i++)
             if (ray_t_max[i] != ray_t_max[i]) return fail(MI_ERR_INVALID, "mi_occluded_rays: ray_t_max[%zu] is NaN", i);
-    if (n_rays == 0) return MI_OK;
-    HIP_TRY(hipSetDevice(c->device));
-    const size_t chunk = std::min<size_t>(n_rays, kRqChunk);
-    const size_t off_o = 0, off_d = off_o + chunk * 12, off_t = off_d + chunk * 12, off_out = off_t + chunk * 4, total = off_out + chunk;
-    MI_TRY(ensure(&c->d_rq, &c->rq_bytes, total));
-    char* base = (char*)c->d_rq;
-    float ms_sum = 0.0f;
-    for (size_t first = 0; first < n_rays; first += chunk) {
-        const size_t n = std::min<size_t>(chunk, (size_t)n_rays - first);
-        HIP_TRY(hipMemcpyAsync(base + off_o, origins + 3 * first, n * 12, hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(hipMemcpyAsync(base + off_d, dirs + 3 * first, n * 12, hipMemcpyHostToDevice, c->stream));
-        if (ray_t_max) HIP_TRY(hipMemcpyAsync(base + off_t, ray_t_max + first, n * 4, hipMemcpyHostToDevice, c->stream));
-        MI_TRY(occluded_rays_device(c, (uint32_t)n, (const float*)(base + off_o), (const float*)(base + off_d), t_min, t_max,
-                                    ray_t_max ? (const float*)(base + off_t) : nullptr, seed, first_key + (uint32_t)first,
-                                    (uint8_t*)(base + off_out), c->stream));
-        HIP_TRY(hipMemcpyAsync(out_occluded + first, base + off_out, n, hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(hipStreamSynchronize(c->stream));          // the next chunk reuses the buffer
-        float ms = 0.0f;
-        HIP_TRY(hipEventElapsedTime(&ms, c->ev_start, c->ev_stop));
-        ms_sum += ms;
-    }
-    c->ms_summed = true; c->ms_sum = ms_sum;
-    return MI_OK;
+    const RqColumn cols[] = { { origins, 12, false }, { dirs, 12, false }, { ray_t_max, 4, false }, { out_occluded, 1, true } };
+    return rq_chunked(c, n_rays, cols, [&](uint32_t first, uint32_t n, void* const* d) {
+        return occluded_rays_device(c, n, (const float*)d[0], (const float*)d[1], t_min, t_max, (const float*)d[2], seed, first_key + first,
+                                    (uint8_t*)d[3], c->stream);
+    });
 }
 
 static int shade_rays_device(mi_ctx* c, const mi_camera_desc* cam, uint32_t n_rays, const float* origins, const float* dirs,
                              uint32_t seed, uint32_t first_key, float* out_rgb, hipStream_t stream) {
     RqShadeArgs a;
     a.S = c->S;
-    a.seed_key = lowbias32(seed ^ 0x68e31da4u);
+    a.seed_key = seed_key(seed);
     a.first_key = first_key; a.n_rays = n_rays;
     a.path_depth = cam->path_depth; a.path_samples = cam->path_samples; a.max_trace_dist = cam->max_trace_dist;
     a.origins = origins; a.dirs = dirs; a.out_rgb = out_rgb;
-    HIP_TRY(hipEventRecord(c->ev_start, stream));
-    HIP_TRY(launch_rq_shade(a, stream));
-    HIP_TRY(hipEventRecord(c->ev_stop, stream));
-    c->ev_recorded = true; c->ms_summed = false;
+    RQ_LAUNCH_TIMED(c, stream, launch_rq_shade(a, stream));
     return MI_OK;
 }
 
@@ -964,26 +880,10 @@ extern "C" int mi_shade_rays_device(mi_ctx* c, const mi_camera_desc* cam, uint32
 extern "C" int mi_shade_rays(mi_ctx* c, const mi_camera_desc* cam, uint32_t n_rays, const float* origins, const float* dirs,
                              uint32_t seed, uint32_t first_key, float* out_rgb) {
     MI_TRY(check_shade_args(c, cam, origins, dirs, out_rgb));
-    if (n_rays == 0) return MI_OK;
-    HIP_TRY(hipSetDevice(c->device));
-    const size_t chunk = std::min<size_t>(n_rays, kRqChunk);
-    MI_TRY(ensure(&c->d_rq, &c->rq_bytes, chunk * 36));
-    char* base = (char*)c->d_rq;
-    float ms_sum = 0.0f;
-    for (size_t first = 0; first < n_rays; first += chunk) {
-        const size_t n = std::min<size_t>(chunk, (size_t)n_rays - first);
-        HIP_TRY(hipMemcpyAsync(base, origins + 3 * first, n * 12, hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(hipMemcpyAsync(base + chunk * 12, dirs + 3 * first, n * 12, hipMemcpyHostToDevice, c->stream));
-        MI_TRY(shade_rays_device(c, cam, (uint32_t)n, (const float*)base, (const float*)(base + chunk * 12), seed, first_key + (uint32_t)first,
-                                 (float*)(base + chunk * 24), c->stream));
-        HIP_TRY(hipMemcpyAsync(out_rgb + 3 * first, base + chunk * 24, n * 12, hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        float ms = 0.0f;
-        HIP_TRY(hipEventElapsedTime(&ms, c->ev_start, c->ev_stop));
-        ms_sum += ms;
-    }
-    c->ms_summed = true; c->ms_sum = ms_sum;
-    return MI_OK;
+    const RqColumn cols[] = { { origins, 12, false }, { dirs, 12, false }, { out_rgb, 12, true } };
+    return rq_chunked(c, n_rays, cols, [&](uint32_t first, uint32_t n, void* const* d) {
+        return shade_rays_device(c, cam, n, (const float*)d[0], (const float*)d[1], seed, first_key + first, (float*)d[2], c->stream);
+    });
 }
 
 extern "C" int mi_reserve(mi_ctx* c, const mi_camera_desc* cam, int32_t world, uint64_t max_state_bytes) {

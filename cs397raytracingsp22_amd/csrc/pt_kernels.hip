@@ -3495,45 +3495,28 @@ hipError_t launch_branch(const K1Args& a, uint32_t n_blocks, uint32_t path_sampl
     return hipGetLastError();
 }
 // Ray queries.  The grid is what the device holds at once (the kernel strides over the 256-ray chunks), at most one block per chunk.
-hipError_t launch_rq_intersect(const RqArgs& a, bool lds, bool gv, bool resolve, size_t lds_bytes, int n_cus, hipStream_t stream) {
-    const bool top = a.S.top_meshf >= 0;
-    const size_t dyn = lds ? lds_bytes : 0;
+template <class Args> static hipError_t launch_rq_resident(const void* fn, const Args& a, size_t dyn, int n_cus, hipStream_t stream) {
     const uint32_t n_chunks = (a.n_rays + (uint32_t)kBlock - 1u) / (uint32_t)kBlock;
-    const void* fn = nullptr;
-#define PT_RQ_PICK(L, G, T, R) fn = (const void*)&rq_intersect<L, G, T, R>
-#define PT_RQ_PICK3(L, G, T) do { if (resolve) PT_RQ_PICK(L, G, T, true); else PT_RQ_PICK(L, G, T, false); } while (0)
-#define PT_RQ_PICK2(L, G) do { if (top) PT_RQ_PICK3(L, G, true); else PT_RQ_PICK3(L, G, false); } while (0)
-    if (lds) { if (gv) PT_RQ_PICK2(true, true); else PT_RQ_PICK2(true, false); }
-    else     { if (gv) PT_RQ_PICK2(false, true); else PT_RQ_PICK2(false, false); }
-#undef PT_RQ_PICK2
-#undef PT_RQ_PICK3
-#undef PT_RQ_PICK
     int per_cu = 0;
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, kBlock, dyn) != hipSuccess || per_cu < 1) { (void)hipGetLastError(); per_cu = 1; }
     const uint64_t resident = (uint64_t)per_cu * (uint64_t)(n_cus > 0 ? n_cus : 1);
     const uint32_t n_blocks = (uint32_t)(resident < (uint64_t)n_chunks ? resident : (uint64_t)n_chunks);
-    RqArgs args = a;
+    Args args = a;
     void* params[] = { (void*)&args };
     return hipLaunchKernel(fn, dim3(n_blocks), dim3(kBlock), params, dyn, stream);
 }
+hipError_t launch_rq_intersect(const RqArgs& a, bool lds, bool gv, bool resolve, size_t lds_bytes, int n_cus, hipStream_t stream) {
+#define PT_RQ(L, G) { { (const void*)&rq_intersect<L, G, true, true>, (const void*)&rq_intersect<L, G, true, false> }, \
+                      { (const void*)&rq_intersect<L, G, false, true>, (const void*)&rq_intersect<L, G, false, false> } }
+    static const void* const fn[2][2][2][2] = { { PT_RQ(true, true), PT_RQ(true, false) }, { PT_RQ(false, true), PT_RQ(false, false) } };   // [!lds][!gv][!top][!resolve]: `true` first, the order the forms have always been instantiated in
+#undef PT_RQ
+    return launch_rq_resident(fn[!lds][!gv][a.S.top_meshf < 0][!resolve], a, lds ? lds_bytes : 0, n_cus, stream);
+}
 hipError_t launch_rq_occluded(const RqOccArgs& a, bool lds, bool gv, size_t lds_bytes, int n_cus, hipStream_t stream) {
-    const bool top = a.S.top_meshf >= 0;
-    const size_t dyn = lds ? lds_bytes : 0;
-    const uint32_t n_chunks = (a.n_rays + (uint32_t)kBlock - 1u) / (uint32_t)kBlock;
-    const void* fn = nullptr;
-#define PT_RQ_PICK(L, G, T) fn = (const void*)&rq_occluded<L, G, T>
-#define PT_RQ_PICK2(L, G) do { if (top) PT_RQ_PICK(L, G, true); else PT_RQ_PICK(L, G, false); } while (0)
-    if (lds) { if (gv) PT_RQ_PICK2(true, true); else PT_RQ_PICK2(true, false); }
-    else     { if (gv) PT_RQ_PICK2(false, true); else PT_RQ_PICK2(false, false); }
-#undef PT_RQ_PICK2
-#undef PT_RQ_PICK
-    int per_cu = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, kBlock, dyn) != hipSuccess || per_cu < 1) { (void)hipGetLastError(); per_cu = 1; }
-    const uint64_t resident = (uint64_t)per_cu * (uint64_t)(n_cus > 0 ? n_cus : 1);
-    const uint32_t n_blocks = (uint32_t)(resident < (uint64_t)n_chunks ? resident : (uint64_t)n_chunks);
-    RqOccArgs args = a;
-    void* params[] = { (void*)&args };
-    return hipLaunchKernel(fn, dim3(n_blocks), dim3(kBlock), params, dyn, stream);
+#define PT_RQ(L, G) { (const void*)&rq_occluded<L, G, true>, (const void*)&rq_occluded<L, G, false> }
+    static const void* const fn[2][2][2] = { { PT_RQ(true, true), PT_RQ(true, false) }, { PT_RQ(false, true), PT_RQ(false, false) } };   // [!lds][!gv][!top], likewise
+#undef PT_RQ
+    return launch_rq_resident(fn[!lds][!gv][a.S.top_meshf < 0], a, lds ? lds_bytes : 0, n_cus, stream);
 }
 hipError_t launch_rq_shade(const RqShadeArgs& a, hipStream_t stream) {
     const uint32_t n_blocks = (a.n_rays + (uint32_t)kBlock - 1u) / (uint32_t)kBlock;

@@ -354,4 +354,80 @@ WfBatch wf_batch(uint32_t npix, uint32_t s_batch) {
     return b;
 }
 
+// ---- the pass schedule (K1w).  mi_rt.cpp's pass loop asks pass_gate, waits if told to, asks plan_pass and launches what it names.
+PassHdr camera_pass_header(uint32_t n_in) { return PassHdr{ (n_in + kBlock - 1) / kBlock, n_in, 0u, 0u, 0u, 0u }; }
+
+WalkMasks walk_masks(const CompiledScene& sc, uint32_t flags) {
+    const uint32_t all_meshes = sc.S.n_meshes >= 32 ? 0xffffffffu : ((1u << sc.S.n_meshes) - 1u);
+    const uint32_t ts = two_stage_mask(sc, flags) & all_meshes;
+    return WalkMasks{ all_meshes & ~ts, ts };
+}
+
+PassSchedule pass_schedule(const CompiledScene& sc, WalkMasks masks, const WalkerPlan& walker, int n_cus, uint32_t path_depth, const ScheduleKnobs& knobs) {
+    PassSchedule s;
+    s.ref_mask = masks.ref; s.ts_mask = masks.ts; s.nowait_blocks = knobs.nowait_blocks;
+    s.have_walkers = masks.ref || masks.ts || sc.S.n_meshes > 32;
+    s.ref_walk = masks.ref || sc.S.n_meshes > 32;      // meshes 32, 33, ... have no mask bit: they always take the reference walk
+    // Meshes of both kinds: wf_trav and wf_trav_f read the same work list and write different things (the hit record / the
+    // candidate lists; each has its own cursor), so they go to two streams and wf_replay, which merges into the hit
+    // record, follows both.  With full grids the F-tree walkers move in as the reference walkers run out of queue and leave
+    // (HEAD 98.5 -> 96.5 ms).  Sharing every CU from the start — half the wave slots each — gains nothing: 68 ms for the
+    // pair, exactly the 43 + 25 ms they take one after the other (VALU issue 0.71 + 0.34: together they saturate it).
+    s.side_by_side = s.ref_walk && masks.ts && knobs.conc != 0;
+    s.split_enabled = s.have_walkers && knobs.split != 0;
+    // further shade + intersect rounds inside one wf_main launch: one when meshes park part of every wave's rays for the walker
+    // (cfg2: 1 / 2 / 3 rounds -> 99 / 101 / 103 ms), two in a scene without meshes, where every live lane can go on
+    // (cfg5 at 512 spp: 1 / 2 / 3 / 5 rounds -> 281.6 / 271.8 / 278.4 / 287.7 ms; the cfg1 scene at 1080p: 46.6 / 42.9 / 47.4 / 48.1 ms)
+    s.fuse_max = knobs.fuse_max ? knobs.fuse_max : (sc.S.n_meshes == 0 ? 2u : 1u);
+    s.fuse_min = knobs.fuse_min < 1 ? 1 : knobs.fuse_min; s.tail_fuse_max = path_depth + 2u;
+    // Tail threshold (MI_RT_WF_TAIL_PATHS): without meshes 4 Mi paths, the size below which passes are launched without waiting
+    // (cfg1 as BASELINE states it, 400x400 / 16 spp: 0.64 ms at 0, 0.55 at 64 Ki ... 2 Mi, 0.49 from 3 Mi on; cfg1 / cfg5 at
+    // 1080p unchanged up to 8 Mi); with meshes 1 Mi (a 1/8 share of cfg2: 11.0 ms up to 2 Mi, 11.1 at 4 Mi, 11.3 at 8 Mi).
+    s.tail_paths = knobs.tail_paths != 0xffffffffu ? knobs.tail_paths : (s.have_walkers ? (1u << 20) : (4u << 20));
+    const uint32_t cus = (uint32_t)n_cus, travf_bpc = knobs.travf_bpc > 0 ? (uint32_t)knobs.travf_bpc : 6u;
+    const uint32_t conc_trav_bpc = knobs.conc_trav_bpc > 0 ? (uint32_t)knobs.conc_trav_bpc : walker.blocks_per_cu;
+    const uint32_t conc_travf_bpc = knobs.conc_travf_bpc > 0 ? (uint32_t)knobs.conc_travf_bpc : travf_bpc;
+    s.walker_blocks = cus * (s.side_by_side ? conc_trav_bpc : walker.blocks_per_cu);
+    s.travf_blocks = cus * (s.side_by_side ? conc_travf_bpc : travf_bpc);
+    s.replay_blocks = cus * 8u; s.filter_blocks_per_shard = 8u;
+    return s;
+}
+
+// The grid of pass `it` comes from the header of pass it - 1.  While that pass is still running the host would have to wait for
+// it (the header is on its way while the walkers run, so for a big pass the wait is hidden); a SMALL pass is launched at once
+// instead, on a grid that is an upper bound — live paths only decrease, and every (class, shard) list may end in a partial
+// block — whose surplus blocks leave at their first instruction (wf_main compares its block number with the device-side table).
+// The host runs at most kRunAhead passes ahead of the headers.
+uint32_t pass_grid_bound(uint32_t live) { return live / (uint32_t)kBlock + 2u * (uint32_t)kWfShards; }
+
+PassGate pass_gate(const PassSchedule& s, uint32_t it, uint32_t seen, uint32_t live) {
+    if (seen == it) return PassGate::kExact;
+    if (s.nowait_blocks == 0 || pass_grid_bound(live) > s.nowait_blocks || it - seen > kRunAhead) return PassGate::kWait;
+    return PassGate::kBound;
+}
+
+PassPlan plan_pass(const PassSchedule& s, uint32_t it, bool exact, const PassHdr& last) {
+    PassPlan p;
+    p.grid_all = exact ? last.blocks : pass_grid_bound(last.live);
+    p.grid_a = exact ? last.blocks_a : p.grid_all;
+    if (it == 0) { p.grid_all = last.blocks; p.grid_a = 0; }          // the camera pass: last = camera_pass_header
+    p.stop = p.grid_all == 0;
+    // THE TAIL.  Once the live paths no longer fill the chip (last.live bounds this pass' input: paths only end), thin waves
+    // cost nothing — there is nobody to give their lanes to — while every further pass costs two launches and a header.
+    // So each wave keeps shading as long as ANY of its lanes can go on (a path that enters a mesh root still parks for
+    // the walker).  Per path the operations and their order are those of the pass-by-pass schedule.  Without meshes
+    // nothing ever parks: this launch ends every path and is the last one.  (Threshold: pass_schedule.)
+    p.tail = it > 0 && s.tail_paths != 0 && last.live <= s.tail_paths;      // (the camera pass in this form too: 0.49 -> 0.58 ms on cfg1 as stated)
+    p.last = p.tail && !s.have_walkers;
+    p.fuse_max = p.tail ? s.tail_fuse_max : s.fuse_max; p.fuse_min = p.tail ? 1u : s.fuse_min;
+    // A pass after the first is launched in TWO PARTS.  Its class-A blocks (paths whose pending hit is a plain Triangle /
+    // Plane: nothing a walker could still change) go to a second stream, ordered only behind the previous pass' wf_prefix:
+    // they fill the CUs the persistent walkers of that pass leave idle as their queue runs out (a walker launch ends
+    // with ~0.1 ms of tail whatever its queue size, eleven times per frame and per rank).  The class-B blocks follow the
+    // walkers on the main stream; wf_prefix waits for both parts.  Same blocks, same work, another schedule.
+    p.split = it > 0 && s.split_enabled && (!exact || (p.grid_a >= 64u && p.grid_a < p.grid_all));
+    p.grid_b = exact ? p.grid_all - p.grid_a : p.grid_all;
+    return p;
+}
+
 }  // namespace pt

@@ -1,6 +1,9 @@
 // render_plan.hpp — the host-side decisions of a render: camera validation, the tile grid of the partition, the camera
-// constants, the primary-ray tile masks, which meshes are walked two-stage, and the wavefront pipeline's batch.  Host code
-// only: no HIP call, no context; mi_rt.cpp plans with these, then launches.
+// constants, the primary-ray tile masks, which meshes are walked two-stage, the wavefront pipeline's batch, and its pass schedule:
+// what is fixed for a render (pass_schedule), whether a pass may be launched before the previous header has arrived (pass_gate), and
+// its grids, parts and in-launch rounds (plan_pass).  Host code only: no HIP call, no context; mi_rt.cpp plans with these, then
+// launches.  All of it runs on the CPU: tests/test_render_plan_host.py and tests/test_pass_schedule_host.py, through
+// tests/cpp/render_plan_shim.cpp; the launches a schedule leads to are pinned by tests/test_gpu_walkers.py (golden/pass_schedule_counts.json).
 #pragma once
 #include <cstdint>
 #include <vector>
@@ -54,5 +57,43 @@ int wf_first_batch(uint32_t npix, uint32_t spp, uint64_t max_state_bytes, uint64
 // What a batch of s_batch samples of npix pixels needs: the shards' region and the plane stride, and the bytes of each buffer
 struct WfBatch { uint32_t region, cap; size_t state_bytes, samp_bytes, acc_bytes, cand_bytes, cand_hdr_bytes; };
 WfBatch wf_batch(uint32_t npix, uint32_t s_batch);
+
+// ---- the wavefront pipeline's pass schedule: what the host decides while it enqueues one pass (wf_main, wf_prefix, the walkers) per path segment
+// The scheduling subset of the developer knobs (MI_RT_WF_*): mi_ctx::Tuning embeds it, mi_ctx_create reads it once
+struct ScheduleKnobs {
+    int split = 1;                          // wf_main in two parts, class A beside the previous pass' walkers (0 = one launch per pass)
+    int conc = 1, conc_trav_bpc = 0, conc_travf_bpc = 0;   // wf_trav and wf_trav_f on two streams (0 = one after the other); their blocks per CU then (0 = the usual)
+    int travf_bpc = 0;                      // wf_trav_f blocks per CU override (0 = default)
+    uint32_t tail_paths = 0xffffffffu;      // a pass that starts with at most this many live paths runs every path as far as it can inside the launch (0 = never; default: automatic)
+    uint32_t nowait_blocks = 16384;         // passes whose grid bound is at most this many blocks are launched without waiting for the previous header (0 = always wait)
+    uint32_t fuse_max = 0, fuse_min = 32;   // wf_main: in-launch continuation (rounds: 0 = automatic; lanes needed)
+};
+constexpr uint32_t kRunAhead = 3;           // passes the host may launch before it has read the header of an earlier one
+// The header of a pass as the host reads it from wf_prefix's slot (pt_device.h kHdr*), and the "header of pass -1": the camera rays
+struct PassHdr { uint32_t blocks, live, queue, live_b, blocks_a, segments; };
+PassHdr camera_pass_header(uint32_t n_in);
+// Which meshes are walked how: ts = two-stage (wf_trav_f + wf_replay), ref = the rest, through the reference's tree (wf_trav).
+// Bit m = live mesh m; meshes 32, 33, ... have no bit: they always take the reference walk.
+struct WalkMasks { uint32_t ref, ts; };
+WalkMasks walk_masks(const CompiledScene& sc, uint32_t flags);
+// What is constant for the passes of one render
+struct PassSchedule {
+    uint32_t ref_mask, ts_mask;
+    bool have_walkers, ref_walk, side_by_side;   // a pass has launches behind wf_prefix / wf_trav among them / wf_trav and wf_trav_f on two streams
+    bool split_enabled;                     // passes may be launched in two parts (plan_pass decides per pass)
+    uint32_t fuse_max, fuse_min, tail_fuse_max;   // in-launch rounds of a normal pass; a tail pass takes tail_fuse_max and 1
+    uint32_t tail_paths, nowait_blocks;     // the knobs, tail_paths resolved (0 = never)
+    uint32_t walker_blocks, travf_blocks, replay_blocks, filter_blocks_per_shard;   // grids as launched (side by side: the MI_RT_WF_CONC_*_BPC values)
+};
+PassSchedule pass_schedule(const CompiledScene& sc, WalkMasks masks, const WalkerPlan& walker, int n_cus, uint32_t path_depth, const ScheduleKnobs& knobs);
+// May pass `it` be launched now, and on which grid: that of header it - 1, an upper bound (pass_grid_bound), or wait for the headers
+// first?  `seen`: the headers of passes [0, seen) have been read; `live`: live paths in the last of them.
+enum class PassGate { kExact, kBound, kWait };
+uint32_t pass_grid_bound(uint32_t live);
+PassGate pass_gate(const PassSchedule& s, uint32_t it, uint32_t seen, uint32_t live);
+// Pass `it` of a batch from the last header read (`exact`: it is that of pass it - 1).  stop: nothing to launch, the batch is done;
+// grid_all: the pass as one launch, grid_a / grid_b: its class-A / class-B part when split; last: this launch ends every path.
+struct PassPlan { bool stop, split, tail, last; uint32_t grid_all, grid_a, grid_b, fuse_max, fuse_min; };
+PassPlan plan_pass(const PassSchedule& s, uint32_t it, bool exact, const PassHdr& last);
 
 }  // namespace pt

@@ -1,5 +1,6 @@
 // render_plan_shim.cpp — CPU entry into the render planner (TEST INFRASTRUCTURE, compiled with render_plan.cpp and
-// scene_compile.cpp by tests/test_render_plan_host.py with g++ -ffp-contract=off into a shared object loaded with ctypes).
+// scene_compile.cpp by tests/test_render_plan_host.py and tests/test_pass_schedule_host.py with g++ -ffp-contract=off into a
+// shared object loaded with ctypes).
 // It stands in for mi_rt.cpp: it defines pt::fail and runs what a render plans, without a GPU.
 #include <cstdarg>
 #include <cstdio>
@@ -70,4 +71,61 @@ extern "C" int render_plan_query(int op, PlanQuery* q) {
     }
     snprintf(q->err, sizeof q->err, "%s", g_err);
     return rc;
+}
+
+// mirrored by ScheduleQuery in tests/test_pass_schedule_host.py: the wavefront pipeline's pass schedule for a scene of n_meshes live
+// meshes (bit m of qualifies / default_ts: CompiledScene::Mesh m, m < 32), then the gate and the plan of one pass under it
+struct ScheduleQuery {
+    // pass_schedule's inputs.  have_masks: ref_mask / ts_mask are given instead of taken from walk_masks(scene, flags)
+    int32_t n_meshes; uint32_t qualifies, default_ts, flags;
+    int32_t have_masks; uint32_t ref_mask, ts_mask;
+    uint32_t walker_bpc; int32_t n_cus; uint32_t path_depth;
+    int32_t split, conc, conc_trav_bpc, conc_travf_bpc, travf_bpc;
+    uint32_t tail_paths, nowait_blocks, fuse_max, fuse_min;
+    // the pass: gate(it, seen, hdr_live), plan(it, exact, header); n_in != 0: the header is camera_pass_header(n_in)
+    uint32_t it, seen; int32_t exact; uint32_t n_in, hdr_blocks, hdr_live, hdr_blocks_a;
+    // out: the schedule
+    uint32_t s_ref_mask, s_ts_mask; int32_t have_walkers, ref_walk, side_by_side, split_enabled;
+    uint32_t s_fuse_max, s_fuse_min, tail_fuse_max, s_tail_paths, s_nowait_blocks;
+    uint32_t walker_blocks, travf_blocks, replay_blocks, filter_blocks_per_shard;
+    // out: the gate (0 exact, 1 upper bound, 2 wait) and the bound for hdr_live; the plan
+    int32_t gate; uint32_t bound;
+    int32_t stop, p_split, tail, last; uint32_t grid_all, grid_a, grid_b, p_fuse_max, p_fuse_min;
+};
+
+// the knobs as a context without any MI_RT_WF_* variable has them
+extern "C" void pass_schedule_defaults(ScheduleQuery* q) {
+    const pt::ScheduleKnobs k;
+    q->split = k.split; q->conc = k.conc; q->conc_trav_bpc = k.conc_trav_bpc; q->conc_travf_bpc = k.conc_travf_bpc; q->travf_bpc = k.travf_bpc;
+    q->tail_paths = k.tail_paths; q->nowait_blocks = k.nowait_blocks; q->fuse_max = k.fuse_max; q->fuse_min = k.fuse_min;
+}
+
+extern "C" void pass_schedule_query(ScheduleQuery* q) {
+    pt::CompiledScene sc;
+    sc.S.n_meshes = q->n_meshes;
+    for (int m = 0; m < q->n_meshes; m++) {
+        pt::CompiledScene::Mesh mesh{};
+        mesh.qualifies = m < 32 && ((q->qualifies >> m) & 1u); mesh.default_ts = m < 32 && ((q->default_ts >> m) & 1u);
+        sc.meshes.push_back(mesh);
+    }
+    pt::ScheduleKnobs k;
+    k.split = q->split; k.conc = q->conc; k.conc_trav_bpc = q->conc_trav_bpc; k.conc_travf_bpc = q->conc_travf_bpc; k.travf_bpc = q->travf_bpc;
+    k.tail_paths = q->tail_paths; k.nowait_blocks = q->nowait_blocks; k.fuse_max = q->fuse_max; k.fuse_min = q->fuse_min;
+    pt::WalkerPlan walker{};
+    walker.blocks_per_cu = q->walker_bpc;
+    const pt::WalkMasks masks = q->have_masks ? pt::WalkMasks{ q->ref_mask, q->ts_mask } : pt::walk_masks(sc, q->flags);
+    const pt::PassSchedule s = pt::pass_schedule(sc, masks, walker, q->n_cus, q->path_depth, k);
+    q->s_ref_mask = s.ref_mask; q->s_ts_mask = s.ts_mask;
+    q->have_walkers = s.have_walkers; q->ref_walk = s.ref_walk; q->side_by_side = s.side_by_side; q->split_enabled = s.split_enabled;
+    q->s_fuse_max = s.fuse_max; q->s_fuse_min = s.fuse_min; q->tail_fuse_max = s.tail_fuse_max;
+    q->s_tail_paths = s.tail_paths; q->s_nowait_blocks = s.nowait_blocks;
+    q->walker_blocks = s.walker_blocks; q->travf_blocks = s.travf_blocks; q->replay_blocks = s.replay_blocks;
+    q->filter_blocks_per_shard = s.filter_blocks_per_shard;
+    q->gate = (int32_t)pt::pass_gate(s, q->it, q->seen, q->hdr_live);
+    q->bound = pt::pass_grid_bound(q->hdr_live);
+    pt::PassHdr h = { q->hdr_blocks, q->hdr_live, 0u, 0u, q->hdr_blocks_a, 0u };
+    if (q->n_in) h = pt::camera_pass_header(q->n_in);
+    const pt::PassPlan p = pt::plan_pass(s, q->it, q->exact != 0, h);
+    q->stop = p.stop; q->p_split = p.split; q->tail = p.tail; q->last = p.last;
+    q->grid_all = p.grid_all; q->grid_a = p.grid_a; q->grid_b = p.grid_b; q->p_fuse_max = p.fuse_max; q->p_fuse_min = p.fuse_min;
 }
