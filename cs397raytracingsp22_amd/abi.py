@@ -26,6 +26,7 @@ MI_SHADE_PHONG, MI_SHADE_PATHTRACE = 0, 1
 MI_VARIANT_DEFAULT, MI_VARIANT_SIMPLE, MI_VARIANT_VOTED, MI_VARIANT_VOTED_DIAG = 0, 1, 3, 4      # 2, 5, 6: removed in ABI 3
 MI_VARIANT_WAVEFRONT, MI_VARIANT_RECURSIVE = 7, 8
 MI_OPT_NO_TILE_MASKS, MI_OPT_REFERENCE_WALK, MI_OPT_TWO_STAGE, MI_OPT_NO_LIST_TREE = 1, 2, 4, 8
+MI_HEMI_WORLD_RADIUS = 1   # mi_hemisphere_occlusion flags: t_max is a world-space radius
 
 f3 = C.c_float * 3
 f16 = C.c_float * 16
@@ -112,6 +113,7 @@ EXPORTS = [
     "mi_reserve", "mi_render_samples_device", "mi_last_pipeline_ms", "mi_last_pipeline_counts", "mi_last_diag", "mi_selftest", "mi_last_error", "mi_abi_version",
     "mi_intersect_rays", "mi_intersect_rays_device", "mi_shade_rays", "mi_shade_rays_device",
     "mi_occluded_rays", "mi_occluded_rays_device",
+    "mi_hemisphere_occlusion", "mi_hemisphere_occlusion_device",
     "mi_render_rays", "mi_render_rays_device",
     "mi_multi_create", "mi_multi_create_loopback", "mi_multi_destroy", "mi_multi_device_count", "mi_multi_context", "mi_multi_scene_upload", "mi_multi_reserve", "mi_multi_render",
 ]
@@ -190,6 +192,13 @@ def load() -> C.CDLL:
     lib.mi_occluded_rays.restype = C.c_int
     lib.mi_occluded_rays_device.argtypes = lib.mi_occluded_rays.argtypes + [vp]
     lib.mi_occluded_rays_device.restype = C.c_int
+    # hemisphere occlusion (added within ABI 5): n_points, points, normals, first_sample, n_samples, t_min, t_max, flags, seed, first_key,
+    # out_open, out_bent
+    lib.mi_hemisphere_occlusion.argtypes = [vp, C.c_uint32, vp, vp, C.c_uint32, C.c_uint32, C.c_float, C.c_float, C.c_uint32, C.c_uint32,
+                                            C.c_uint32, vp, vp]
+    lib.mi_hemisphere_occlusion.restype = C.c_int
+    lib.mi_hemisphere_occlusion_device.argtypes = lib.mi_hemisphere_occlusion.argtypes + [vp]
+    lib.mi_hemisphere_occlusion_device.restype = C.c_int
     # ray-table rendering (added within ABI 5): cam, opts, origins, dirs, rays_per_pixel, then mi_render's outputs / the device form's
     # sample range, accumulator, compact buffer, signatures and stream
     lib.mi_render_rays.argtypes = [vp, C.POINTER(mi_camera_desc), C.POINTER(mi_render_opts), vp, vp, C.c_uint32,

@@ -37,6 +37,7 @@ hipError_t launch_phong(const K1Args& a, uint32_t n_blocks, bool sig, hipStream_
 hipError_t launch_branch(const K1Args& a, uint32_t n_blocks, uint32_t path_samples, bool sig, hipStream_t stream);
 hipError_t launch_rq_intersect(const RqArgs& a, bool lds, bool gv, bool resolve, size_t lds_bytes, int n_cus, hipStream_t stream);
 hipError_t launch_rq_occluded(const RqOccArgs& a, bool lds, bool gv, size_t lds_bytes, int n_cus, hipStream_t stream);
+hipError_t launch_rq_hemi(const RqHemiArgs& a, bool lds, bool gv, size_t lds_bytes, int n_cus, hipStream_t stream);
 hipError_t launch_rq_shade(const RqShadeArgs& a, hipStream_t stream);
 hipError_t launch_walker(const WfArgs& a, const WalkerPlan& p, uint32_t n_blocks, bool* big_lds_enabled, hipStream_t stream);
 hipError_t launch_wf_filter_f(const WfArgs& a, uint32_t blocks_per_shard, hipStream_t stream);
@@ -735,10 +736,12 @@ static const uint32_t kRqChunk = 1u << 18;      // rays per chunk of the host-po
 // the launch or (`out`) downloaded after it.  rq_chunked carves d_rq into one array of a chunk per column, in the order given, and for every
 // chunk uploads, calls launch(first, n, dev) — dev[i] = column i's device array, nullptr when absent — downloads and synchronises.
 struct RqColumn { const void* host; size_t bytes; bool out; };
-template <size_t N, class Launch> static int rq_chunked(mi_ctx* c, uint32_t n_rays, const RqColumn (&cols)[N], Launch launch) {
+// max_chunk: rows per chunk (a row is a ray, or a point of the hemisphere query, whose rows stand for n_samples rays each).
+template <size_t N, class Launch> static int rq_chunked(mi_ctx* c, uint32_t n_rays, const RqColumn (&cols)[N], Launch launch,
+                                                        size_t max_chunk = kRqChunk) {
     if (n_rays == 0) return MI_OK;
     HIP_TRY(hipSetDevice(c->device));
-    const size_t chunk = std::min<size_t>(n_rays, kRqChunk);
+    const size_t chunk = std::min<size_t>(n_rays, max_chunk);
     size_t off[N + 1] = { 0 };
     for (size_t i = 0; i < N; i++) off[i + 1] = off[i] + chunk * cols[i].bytes;
     MI_TRY(ensure(&c->d_rq, &c->rq_bytes, off[N]));
@@ -843,6 +846,60 @@ extern "C" int mi_occluded_rays(mi_ctx* c, uint32_t n_rays, const float* origins
         return occluded_rays_device(c, n, (const float*)d[0], (const float*)d[1], t_min, t_max, (const float*)d[2], seed, first_key + first,
                                     (uint8_t*)d[3], c->stream);
     });
+}
+
+// mi_hemisphere_occlusion: rq_hemi makes the rays of every point on the device and reduces per point.
+static int check_hemi_args(mi_ctx* c, const float* points, const float* normals, uint32_t first_sample, uint32_t n_samples, float t_min,
+                           float t_max, uint32_t flags, const uint32_t* out_open) {
+    if (!c) return fail(MI_ERR_INVALID, "ctx is NULL");
+    if (!points || !normals || !out_open) return fail(MI_ERR_INVALID, "mi_hemisphere_occlusion: points, normals and out_open are required");
+    if (n_samples == 0 || n_samples > 65535u) return fail(MI_ERR_INVALID, "mi_hemisphere_occlusion: n_samples %u is not in 1 .. 65535", n_samples);
+    if ((uint64_t)first_sample + n_samples > (1ull << 31))
+        return fail(MI_ERR_INVALID, "mi_hemisphere_occlusion: first_sample + n_samples = %llu exceeds 2^31", (unsigned long long)first_sample + n_samples);
+    if (t_min != t_min || t_max != t_max) return fail(MI_ERR_INVALID, "mi_hemisphere_occlusion: t_min / t_max is NaN");
+    if (flags & ~(uint32_t)MI_HEMI_WORLD_RADIUS) return fail(MI_ERR_INVALID, "mi_hemisphere_occlusion: unknown flag bits 0x%x", flags & ~(uint32_t)MI_HEMI_WORLD_RADIUS);
+    if (!c->have_scene) return fail(MI_ERR_NO_SCENE, "no scene uploaded");
+    return MI_OK;
+}
+
+static int hemisphere_occlusion_device(mi_ctx* c, uint32_t n_points, const float* points, const float* normals, uint32_t first_sample,
+                                       uint32_t n_samples, float t_min, float t_max, uint32_t flags, uint32_t seed, uint32_t first_key,
+                                       uint32_t* out_open, float* out_bent, hipStream_t stream) {
+    RqHemiArgs a;
+    a.S = c->S;
+    const bool lds = stage_in_lds(c, a);
+    a.seed_key = seed_key(seed);
+    a.first_key = first_key; a.n_points = n_points; a.first_sample = first_sample; a.n_samples = n_samples;
+    a.group_log2 = 0;
+    while (a.group_log2 < 6u && (1u << a.group_log2) < n_samples) a.group_log2++;      // G = min(64, next_pow2(n_samples))
+    a.world_radius = (flags & MI_HEMI_WORLD_RADIUS) ? 1u : 0u;
+    a.t_min = t_min; a.t_max = t_max;
+    a.points = points; a.normals = normals; a.out_open = out_open; a.out_bent = out_bent;
+    RQ_LAUNCH_TIMED(c, stream, launch_rq_hemi(a, lds, c->scene.gen_volumes, c->scene.lds_bytes, c->n_cus, stream));
+    return MI_OK;
+}
+
+extern "C" int mi_hemisphere_occlusion_device(mi_ctx* c, uint32_t n_points, const float* points, const float* normals, uint32_t first_sample,
+                                              uint32_t n_samples, float t_min, float t_max, uint32_t flags, uint32_t seed,
+                                              uint32_t first_key, uint32_t* out_open, float* out_bent, void* stream) {
+    MI_TRY(check_hemi_args(c, points, normals, first_sample, n_samples, t_min, t_max, flags, out_open));
+    if (n_points == 0) return MI_OK;
+    HIP_TRY(hipSetDevice(c->device));
+    return hemisphere_occlusion_device(c, n_points, points, normals, first_sample, n_samples, t_min, t_max, flags, seed, first_key, out_open,
+                                       out_bent, (hipStream_t)stream);
+}
+
+extern "C" int mi_hemisphere_occlusion(mi_ctx* c, uint32_t n_points, const float* points, const float* normals, uint32_t first_sample,
+                                       uint32_t n_samples, float t_min, float t_max, uint32_t flags, uint32_t seed, uint32_t first_key,
+                                       uint32_t* out_open, float* out_bent) {
+    MI_TRY(check_hemi_args(c, points, normals, first_sample, n_samples, t_min, t_max, flags, out_open));
+    // chunked over points: at most about 2^24 rays per launch, and never more points than a chunk of rays (28 B of scratch per point)
+    const size_t max_points = std::min<size_t>(kRqChunk, std::max<size_t>(1, ((size_t)1 << 24) / n_samples));
+    const RqColumn cols[] = { { points, 12, false }, { normals, 12, false }, { out_bent, 12, true }, { out_open, 4, true } };
+    return rq_chunked(c, n_points, cols, [&](uint32_t first, uint32_t n, void* const* d) {
+        return hemisphere_occlusion_device(c, n, (const float*)d[0], (const float*)d[1], first_sample, n_samples, t_min, t_max, flags, seed,
+                                           first_key + first, (uint32_t*)d[3], (float*)d[2], c->stream);
+    }, max_points);
 }
 
 static int shade_rays_device(mi_ctx* c, const mi_camera_desc* cam, uint32_t n_rays, const float* origins, const float* dirs,

@@ -253,6 +253,21 @@ struct RqOccArgs {
     const float* ray_t_max;          // [n] or nullptr
     uint8_t* out_occluded;           // [n] 0 / 1
 };
+// rq_hemi (mi_hemisphere_occlusion): the rays are made on the device.  A group of 1 << group_log2 lanes owns one point; sample
+// s = first_sample + k of point i takes its direction from the stream (seed, first_key + i, 2s) and its ray draws from (.., 2s + 1).
+struct RqHemiArgs {
+    DScene  S;
+    uint32_t lds_nodes, lds_tris;
+    uint32_t seed_key, first_key, n_points;
+    uint32_t first_sample, n_samples;
+    uint32_t group_log2;             // G = min(64, next_pow2(n_samples)) as a shift
+    uint32_t world_radius;           // MI_HEMI_WORLD_RADIUS: the upper end is t_max / |d|
+    float    t_min, t_max;
+    const float* points;             // [n][3]
+    const float* normals;            // [n][3], used as given (not normalised)
+    uint32_t* out_open;              // [n] samples not occluded
+    float*    out_bent;              // [n][3] sum of their directions, or nullptr
+};
 struct RqShadeArgs {
     DScene  S;
     uint32_t seed_key, first_key, n_rays;

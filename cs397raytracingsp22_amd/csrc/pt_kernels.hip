@@ -1775,6 +1775,84 @@ __global__ __launch_bounds__(kBlock) void rq_occluded(RqOccArgs A) {
     }
 }
 
+// ---- rq_hemi: hemisphere occlusion (mi_hemisphere_occlusion) — rq_occluded's sibling whose rays are made HERE, for ambient-occlusion
+// baking: nothing per ray crosses the bus.  A group of G = 1 << group_log2 = min(64, next_pow2(n_samples)) lanes owns one point, so a
+// wave holds 64 / G points and a block trip 256 / G; the lanes of a group take the samples k = lane, lane + G, ...  The rays of a wave
+// share one origin (G == 64) or a few: the list and tree data they touch first is the same.  Per sample s = first_sample + k:
+//   d = Lambertian::scatter -> sample_hemisphere(normal) (materials.rs:33-48, 171-178) on the fresh stream (seed, first_key + i, 2s):
+//       rand_sphere_vec, dir.y = |dir.y|, rotate_from_unit_y — scatter_raw's diffuse branch without the rotation table, which is keyed
+//       by list object and not by normal; the same f32 operations;
+//   the any-hit question of rq_occluded for (point, d) over [t_min, t_max] (or t_max / |d| with world_radius) with the second fresh
+//       stream (seed, first_key + i, 2s + 1): occluded_list, then the occluded_mesh loop with the same voted exits.
+// Every sample has streams of its own, so the counts do not depend on G, on the grid or on how a bake is split.  A lane keeps a u32
+// count and an f3 sum of its open directions (in k order); a butterfly over the group (xor widths below G) adds them and the group's
+// first lane writes with plain stores: no atomics, no memset, and an order of additions fixed by n_samples alone.  Lanes past n_points
+// or past n_samples are done from the start.  The point and the normal are loaded once per trip, outside the sample loop; gfx950 has
+// no scalar float ALU, so the origin's transform into mesh space is VALU work whether or not the wave shares it.
+template <bool LDS, bool GV, bool TOP>
+__global__ __launch_bounds__(kBlock) void rq_hemi(RqHemiArgs A) {
+    const DScene& S = A.S;
+    Bvh<LDS> B;
+    if (LDS) {
+        cf4_ptr gn = (cf4_ptr)S.nodes;
+        cf4_ptr gt = (cf4_ptr)S.tris;
+        const int nn = (int)A.lds_nodes * 2, nt = (int)A.lds_tris * 3;
+        for (int k = threadIdx.x; k < nn; k += kBlock) k1_lds[k] = gn[k];
+        for (int k = threadIdx.x; k < nt; k += kBlock) k1_lds[nn + k] = gt[k];
+        __syncthreads();
+    }
+    bvh_bind(B, S, (int)A.lds_nodes * 2);
+    const float t_min = A.t_min;
+    const uint32_t gl = A.group_log2, G = 1u << gl;
+    const uint32_t sub = threadIdx.x & (G - 1u);                            // this lane's place in its group
+    const uint32_t per_trip = (uint32_t)kBlock >> gl;                       // points per block trip
+    const uint32_t n_trips = A.n_points / per_trip + ((A.n_points & (per_trip - 1u)) != 0u ? 1u : 0u);      // no wrap near 2^32
+    for (uint32_t trip = blockIdx.x; trip < n_trips; trip += gridDim.x) {
+        const uint32_t i = trip * per_trip + (threadIdx.x >> gl);
+        const bool live = i < A.n_points;
+        const size_t r = live ? (size_t)i : 0;                              // idle groups of the last trip read point 0 and store nothing
+        const f3 o = mk3(A.points[3 * r], A.points[3 * r + 1], A.points[3 * r + 2]);
+        const f3 n = mk3(A.normals[3 * r], A.normals[3 * r + 1], A.normals[3 * r + 2]);
+        const uint32_t key = A.first_key + (uint32_t)r;
+        uint32_t open = 0u;
+        f3 bent = mk3(0.0f, 0.0f, 0.0f);
+        for (uint32_t k0 = 0u; k0 < A.n_samples; k0 += G) {                 // block-uniform trip count
+            const uint32_t k = k0 + sub;
+            const bool have = live & (k < A.n_samples);
+            const uint32_t s = A.first_sample + (have ? k : 0u);            // < 2^31 (checked by the host): 2s + 1 does not wrap
+            Rng rng;
+            rng_init(rng, A.seed_key, key, 2u * s);
+            f3 v = rand_sphere_vec(rng);                                    // materials.rs:172
+            v.y = fabsf(v.y);                                               // :173
+            const f3 d = rotate_from_unit_y(n, v);                          // :176-177
+            const float t_max = A.world_radius ? A.t_max / sqrtf(mag2(d)) : A.t_max;
+            rng_init(rng, A.seed_key, key, 2u * s + 1u);
+            bool done = !have;                                              // tail lanes ask nothing
+            occluded_list<GV, TOP>(S, o, d, t_min, t_max, rng, done);
+            for (int m = 0; m < S.n_meshes; m++) {                          // geometry.rs:301-314
+                if (__builtin_amdgcn_ballot_w64(!done) == 0ull) break;     // a mesh no lane of the wave needs
+                auto M = &S.meshes[m];
+                const f3 oo = xform_point(M->inv_transform, o), od = xform_vector(M->inv_transform, d);
+                done = done | occluded_mesh(B, M->node_begin, M->node_end, M->tri_begin, !done, oo, od, t_min, t_max);
+            }
+            const bool is_open = have & !done;
+            open += is_open ? 1u : 0u;
+            bent = mk3(is_open ? bent.x + d.x : bent.x, is_open ? bent.y + d.y : bent.y, is_open ? bent.z + d.z : bent.z);
+        }
+#pragma unroll
+        for (int w = 32; w >= 1; w >>= 1) {                                 // butterfly over the group: xor widths below G stay inside it
+            if ((uint32_t)w < G) {
+                open += (uint32_t)__shfl_xor((int)open, w);
+                bent = mk3(bent.x + __shfl_xor(bent.x, w), bent.y + __shfl_xor(bent.y, w), bent.z + __shfl_xor(bent.z, w));
+            }
+        }
+        if (live & (sub == 0u)) {
+            A.out_open[i] = open;
+            if (A.out_bent) { float* p = A.out_bent + 3 * (size_t)i; p[0] = bent.x; p[1] = bent.y; p[2] = bent.z; }
+        }
+    }
+}
+
 // rq_shade: Scene::shade_ray(ray, 0) (tracing.rs:300-324) as written for caller-supplied rays: pt_branch's per-sample body on ray i with
 // the stream (seed, first_key + i, 0).  A completeness path like pt_branch (per-lane frame stack in scratch, BVH from global memory),
 // bit-identical to the CPU restatement for every path_samples; not tuned.
@@ -3517,6 +3595,23 @@ hipError_t launch_rq_occluded(const RqOccArgs& a, bool lds, bool gv, size_t lds_
     static const void* const fn[2][2][2] = { { PT_RQ(true, true), PT_RQ(true, false) }, { PT_RQ(false, true), PT_RQ(false, false) } };   // [!lds][!gv][!top], likewise
 #undef PT_RQ
     return launch_rq_resident(fn[!lds][!gv][a.S.top_meshf < 0], a, lds ? lds_bytes : 0, n_cus, stream);
+}
+// rq_hemi: the resident grid again, over the block trips of 256 >> group_log2 points
+hipError_t launch_rq_hemi(const RqHemiArgs& a, bool lds, bool gv, size_t lds_bytes, int n_cus, hipStream_t stream) {
+#define PT_RQ(L, G) { (const void*)&rq_hemi<L, G, true>, (const void*)&rq_hemi<L, G, false> }
+    static const void* const fn[2][2][2] = { { PT_RQ(true, true), PT_RQ(true, false) }, { PT_RQ(false, true), PT_RQ(false, false) } };   // [!lds][!gv][!top]
+#undef PT_RQ
+    const void* f = fn[!lds][!gv][a.S.top_meshf < 0];
+    const size_t dyn = lds ? lds_bytes : 0;
+    const uint32_t per_trip = (uint32_t)kBlock >> a.group_log2;
+    const uint32_t n_trips = a.n_points / per_trip + ((a.n_points & (per_trip - 1u)) != 0u ? 1u : 0u);
+    int per_cu = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, f, kBlock, dyn) != hipSuccess || per_cu < 1) { (void)hipGetLastError(); per_cu = 1; }
+    const uint64_t resident = (uint64_t)per_cu * (uint64_t)(n_cus > 0 ? n_cus : 1);
+    const uint32_t n_blocks = (uint32_t)(resident < (uint64_t)n_trips ? resident : (uint64_t)n_trips);
+    RqHemiArgs args = a;
+    void* params[] = { (void*)&args };
+    return hipLaunchKernel(f, dim3(n_blocks), dim3(kBlock), params, dyn, stream);
 }
 hipError_t launch_rq_shade(const RqShadeArgs& a, hipStream_t stream) {
     const uint32_t n_blocks = (a.n_rays + (uint32_t)kBlock - 1u) / (uint32_t)kBlock;

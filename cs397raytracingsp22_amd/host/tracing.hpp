@@ -122,6 +122,26 @@ struct Scene : Intersectable {                         // tracing.rs:213-218; `i
         return occluded;
     }
 
+    // Ambient-occlusion baking with rays made on the GPU through mi_hemisphere_occlusion: per surface point, how many of n_samples hemisphere
+    // rays about its normal are NOT occluded within [t_min, t_max] (`open`, [n]) and the sum of the open directions (`bent`, [n][3]).
+    // Sample s = first_sample + k of point i: direction from Lambertian::scatter's sample_hemisphere on the stream (seed, first_key + i, 2s),
+    // the ray's own stream (seed, first_key + i, 2s + 1); normal and direction are used as given.  flags: 0 or MI_HEMI_WORLD_RADIUS (t_max
+    // is a world-space radius).  Split by points (first_key advanced) or by samples (first_sample advanced): the counts of one call, exactly.
+    struct HemisphereOcclusion { std::vector<uint32_t> open; std::vector<float> bent; };
+    HemisphereOcclusion hemisphere_occlusion(const std::vector<float>& points, const std::vector<float>& normals, uint32_t n_samples,
+                                             float t_min = 0.001f, float t_max = INFINITY, uint32_t flags = 0, uint32_t seed = 1,
+                                             uint32_t first_key = 0, uint32_t first_sample = 0, int device = 0) const {
+        if (points.size() != normals.size() || points.size() % 3 != 0) throw std::runtime_error("mi_rt: points and normals must both be [n][3]");
+        if (n_samples == 0 || n_samples > 65535) throw std::runtime_error("mi_rt: n_samples must be in 1 .. 65535");
+        const size_t n = points.size() / 3;
+        HemisphereOcclusion h; h.open.resize(n); h.bent.resize(3 * n);
+        with_context(device, [&](mi_ctx* ctx) {
+            return mi_hemisphere_occlusion(ctx, (uint32_t)n, points.data(), normals.data(), first_sample, n_samples, t_min, t_max, flags, seed,
+                                           first_key, h.open.data(), h.bent.data());
+        });
+        return h;
+    }
+
     // Scene::shade_ray (tracing.rs:300-324) at level 0 for n rays through mi_shade_rays -> [n][3] radiance; the camera supplies path_depth,
     // path_samples and max_trace_dist.
     std::vector<float> shade_rays(const std::vector<float>& origins, const std::vector<float>& dirs, uint32_t seed = 1, uint32_t first_key = 0,

@@ -119,6 +119,33 @@ def check_ray_t_max(ray_t_max, n_rays: int):
     return a
 
 
+def check_hemisphere(points, normals, n_samples: int, t_min: float = 0.001, t_max: float = float("inf"), flags: int = 0,
+                     first_sample: int = 0):
+    """Input checking of mi_hemisphere_occlusion (no GPU needed): `points` and `normals` as C-contiguous float32 arrays of shape (n, 3)
+    and equal length, n_samples in 1 .. 65535, first_sample + n_samples <= 2^31, t_min / t_max not NaN, flags 0 or
+    MI_HEMI_WORLD_RADIUS.  Normals are NOT normalised.  -> (points, normals, n_samples, t_min, t_max, flags, first_sample)."""
+    p = np.ascontiguousarray(np.asarray(points, dtype=np.float32))
+    n = np.ascontiguousarray(np.asarray(normals, dtype=np.float32))
+    for name, a in (("points", p), ("normals", n)):
+        if a.ndim != 2 or a.shape[1] != 3:
+            raise ValueError(f"{name} must have shape (n, 3), got {a.shape}")
+    if len(p) != len(n):
+        raise ValueError(f"points and normals differ in length: {len(p)} and {len(n)}")
+    if len(p) >= 1 << 32:
+        raise ValueError("at most 2^32 - 1 points per call")
+    n_samples, first_sample, flags = int(n_samples), int(first_sample), int(flags)
+    if not 1 <= n_samples <= 65535:
+        raise ValueError(f"n_samples must be in 1 .. 65535, got {n_samples}")
+    if first_sample < 0 or first_sample + n_samples > 1 << 31:
+        raise ValueError(f"first_sample + n_samples must not exceed 2^31, got {first_sample} + {n_samples}")
+    if flags & ~abi.MI_HEMI_WORLD_RADIUS:
+        raise ValueError(f"unknown flag bits {flags & ~abi.MI_HEMI_WORLD_RADIUS:#x}")
+    t_min, t_max = float(t_min), float(t_max)
+    if t_min != t_min or t_max != t_max:
+        raise ValueError("t_min / t_max must not be NaN")
+    return p, n, n_samples, t_min, t_max, flags, first_sample
+
+
 def check_shade_camera(cam: "Camera"):
     """Input checking of mi_shade_rays' camera (no GPU needed), the refusals of the library's check_shade_args that concern values:
     path_samples >= 1 (tracing.rs:318 divides by it) and a max_trace_dist that is not NaN (+inf is legal)."""
@@ -420,6 +447,33 @@ class Context:
         abi.check(self._lib.mi_occluded_rays_device(self._h, n_rays, d_origins, d_dirs, t_min, t_max, d_ray_t_max, seed,
                                                     first_key & 0xffffffff, d_occluded, stream))
 
+    def hemisphere_occlusion(self, points, normals, n_samples: int, t_min: float = 0.001, t_max: float = float("inf"), flags: int = 0,
+                             seed: int = 1, first_key: int = 0, first_sample: int = 0, want_bent: bool = True):
+        """mi_hemisphere_occlusion: per surface point, how many of `n_samples` hemisphere rays about its normal are NOT occluded within
+        [t_min, t_max] -> (open [n] uint32, bent [n, 3] f32 or None: the sum of the open directions).  The rays are made on the GPU:
+        sample s = first_sample + k of point i takes its direction from Lambertian::scatter's sample_hemisphere on the stream
+        (seed, first_key + i, 2s) and its ray draws from (seed, first_key + i, 2s + 1).  Normals and directions are used as given;
+        flags = abi.MI_HEMI_WORLD_RADIUS makes t_max a world-space radius.  A bake split by points (first_key advanced) or by samples
+        (first_sample advanced, counts added) gives the counts of one call exactly."""
+        p, n, n_samples, t_min, t_max, flags, first_sample = check_hemisphere(points, normals, n_samples, t_min, t_max, flags, first_sample)
+        out_open = np.zeros(len(p), np.uint32)
+        out_bent = np.zeros((len(p), 3), np.float32) if want_bent else None
+        abi.check(self._lib.mi_hemisphere_occlusion(self._h, len(p), p.ctypes.data, n.ctypes.data, first_sample, n_samples, t_min, t_max,
+                                                    flags, seed, first_key & 0xffffffff, out_open.ctypes.data,
+                                                    out_bent.ctypes.data if want_bent else None))
+        return out_open, out_bent
+
+    def hemisphere_occlusion_device(self, n_points: int, d_points: int, d_normals: int, d_open: int, n_samples: int,
+                                    d_bent: Optional[int] = None, t_min: float = 0.001, t_max: float = float("inf"), flags: int = 0,
+                                    seed: int = 1, first_key: int = 0, first_sample: int = 0, stream: Optional[int] = None):
+        """mi_hemisphere_occlusion_device: raw device pointers (ints; d_points / d_normals [n][3] f32, d_open [n] uint32, d_bent [n][3]
+        f32 or None), one kernel queued on `stream`, no synchronisation."""
+        t_min, t_max = float(t_min), float(t_max)
+        if t_min != t_min or t_max != t_max:
+            raise ValueError("t_min / t_max must not be NaN")
+        abi.check(self._lib.mi_hemisphere_occlusion_device(self._h, n_points, d_points, d_normals, first_sample, n_samples, t_min, t_max,
+                                                           flags, seed, first_key & 0xffffffff, d_open, d_bent, stream))
+
     def shade_rays(self, cam: Camera, origins, dirs, seed: int = 1, first_key: int = 0) -> np.ndarray:
         """mi_shade_rays: Scene::shade_ray at level 0 for every ray -> [n, 3] f32 radiance.  `cam` supplies path_depth,
         path_samples and max_trace_dist."""
@@ -558,6 +612,25 @@ class Scene:                         # tracing.rs:213-218
             return ctx.occluded_rays(o, d, t_min, t_max, ray_t_max=tm, seed=seed, first_key=first_key)
         finally:
             ctx.close()
+
+    def ambient_occlusion(self, points, normals, samples: int = 64, radius: float = float("inf"), t_min: float = 0.001, seed: int = 1,
+                          first_key: int = 0, first_sample: int = 0, world_radius: bool = True, want_bent: bool = False, device: int = 0):
+        """Ambient occlusion of surface points (mi_hemisphere_occlusion): flatten -> upload -> one query.  -> the open fraction
+        `out_open / samples` per point ([n] float64 in [0, 1]; 1 = nothing within `radius`), or with want_bent (fraction, bent [n, 3]
+        f32: the sum of the open directions).  `radius` is in world units (MI_HEMI_WORLD_RADIUS) unless world_radius is False, then in
+        units of each direction's own length, like every t_max of the ray queries.  Offset the points off the surface yourself, or
+        rely on t_min."""
+        flags = abi.MI_HEMI_WORLD_RADIUS if world_radius else 0
+        p, n, samples, t_min, radius, flags, first_sample = check_hemisphere(points, normals, samples, t_min, radius, flags, first_sample)
+        ctx = Context(device)
+        try:
+            ctx.upload(self.flatten())
+            out_open, bent = ctx.hemisphere_occlusion(p, n, samples, t_min, radius, flags, seed=seed, first_key=first_key,
+                                                      first_sample=first_sample, want_bent=want_bent)
+        finally:
+            ctx.close()
+        frac = out_open.astype(np.float64) / samples
+        return (frac, bent) if want_bent else frac
 
     def render_rays(self, origins, dirs, seed: int = 1, device: int = 0) -> np.ndarray:
         """Scene::render_to_image (tracing.rs:221-263) with a ray table in place of Camera::generate_rays (mi_render_rays): the RgbImage

@@ -201,6 +201,8 @@ typedef struct mi_render_opts {
 #define MI_OPT_TWO_STAGE       4u   /* meshes: use the two-stage traversal for every mesh, whatever its size: same image */
 #define MI_OPT_NO_LIST_TREE    8u   /* long lists: test every Triangle of Scene.objects one by one instead of walking the top-level tree the scene
                                      * compiler builds over them (>= 96 small triangles): same image */
+/* `flags` of mi_hemisphere_occlusion (below) */
+#define MI_HEMI_WORLD_RADIUS 1u     /* t_max is a world-space radius: the interval of a sample ends at t_max / |d| */
 
 typedef enum mi_variant {
     MI_VARIANT_DEFAULT    = 0,  /* library picks (currently MI_VARIANT_WAVEFRONT)                  */
@@ -342,6 +344,39 @@ int  mi_occluded_rays(mi_ctx* ctx, uint32_t n_rays, const float* origins, const 
                       const float* ray_t_max, uint32_t seed, uint32_t first_key, uint8_t* out_occluded);
 int  mi_occluded_rays_device(mi_ctx* ctx, uint32_t n_rays, const float* origins, const float* dirs, float t_min, float t_max,
                              const float* ray_t_max, uint32_t seed, uint32_t first_key, uint8_t* out_occluded, void* stream);
+
+/* ---- hemisphere occlusion: ambient-occlusion baking with rays made ON THE GPU (added within ABI version 5 like the queries above:
+ * detect by symbol lookup) ----
+ * For each of n_points surface points the kernel draws n_samples hemisphere directions about the point's normal, asks the any-hit
+ *   question of mi_occluded_rays for each and reduces per point: nothing per ray crosses the bus.  `points` and `normals` are
+ *   [n_points][3] f32.
+ * Sample s of point i, s = first_sample + k the GLOBAL sample index, k < n_samples:
+ *   direction d = exactly what Lambertian::scatter -> sample_hemisphere (materials.rs:33-48, 171-178) returns for a hit whose normal is
+ *     normals[i] — the normal as given, NOT normalised — drawn from a fresh RNG stream (seed, first_key + i, 2s).  d is NOT normalised:
+ *     rand_sphere_vec returns a point of the unit ball, |d| <= 1.
+ *   ray: origin = points[i] as given (the caller applies any offset), direction d, interval [t_min, t_max] in units of |d| as everywhere
+ *     in this ABI, tested as by mi_occluded_rays — Scene::intersect_ray(..).is_some() — with a second fresh stream
+ *     (seed, first_key + i, 2s + 1), which only a ConvexVolume reads.  Two streams, so that the free-flight draw is independent of the
+ *     direction.
+ * flags: 0, or MI_HEMI_WORLD_RADIUS (defined with the MI_OPT_ bits above): the upper end of the interval becomes t_max / sqrtf(dot(d, d)), in f32 with IEEE `/` and sqrtf,
+ *   which makes t_max a world-space radius; t_min is left alone.  Any other bit is MI_ERR_INVALID.
+ * out_open[i] (REQUIRED, uint32): how many of the n_samples samples are NOT occluded.  out_bent[i] (float[3], may be NULL): the f32 sum
+ *   of d over those samples, taken in a fixed order that depends only on (first_sample, n_samples): two identical calls give identical
+ *   bits (no float atomics).  Divide by out_open[i] and normalise for the bent normal.
+ * Splitting a bake: by points (first_key advanced by the points already done) and by samples (first_sample advanced by the samples
+ *   already done, the counts added up) both give the counts of one call EXACTLY, because every sample has streams of its own.  The bent
+ *   sums of a split by samples add up to the one call's within f32 rounding, not bit for bit.
+ * n_points == 0 is MI_OK and launches nothing.  MI_ERR_INVALID: n_samples == 0 or > 65535, first_sample + n_samples > 2^31, NULL points,
+ *   normals or out_open, a NaN t_min or t_max.  A context without a scene is MI_ERR_NO_SCENE.  A zero or non-finite normal or point gives
+ *   an UNSPECIFIED count (and bent sum) for that point; it never faults and never disturbs another point.
+ * Host / _device forms, the buffers of mi_reserve and mi_last_kernel_ms: as for mi_occluded_rays.  The host form chunks over points so
+ *   that one launch holds at most about 2^24 rays. */
+int  mi_hemisphere_occlusion(mi_ctx* ctx, uint32_t n_points, const float* points, const float* normals, uint32_t first_sample,
+                             uint32_t n_samples, float t_min, float t_max, uint32_t flags, uint32_t seed, uint32_t first_key,
+                             uint32_t* out_open, float* out_bent);
+int  mi_hemisphere_occlusion_device(mi_ctx* ctx, uint32_t n_points, const float* points, const float* normals, uint32_t first_sample,
+                                    uint32_t n_samples, float t_min, float t_max, uint32_t flags, uint32_t seed, uint32_t first_key,
+                                    uint32_t* out_open, float* out_bent, void* stream);
 
 /* ---- ray-table rendering: a whole render from rays of the CALLER's making, through the wavefront pipeline (added within ABI version 5
  * like the queries above: detect by symbol lookup) ----

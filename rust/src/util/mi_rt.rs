@@ -40,6 +40,7 @@ pub enum mi_ctx {}
 pub enum mi_multi {}
 pub const MI_OPT_NO_TILE_MASKS: u32 = 1; pub const MI_OPT_REFERENCE_WALK: u32 = 2; pub const MI_OPT_TWO_STAGE: u32 = 4; pub const MI_OPT_NO_LIST_TREE: u32 = 8;
 pub const MI_RT_ABI_VERSION: c_int = 5;
+pub const MI_HEMI_WORLD_RADIUS: u32 = 1;
 // mi_material_kind / mi_object_kind / projection and shading modes (include/mi_rt.h)
 pub const MI_MAT_LAMBERTIAN: i32 = 0; pub const MI_MAT_METAL: i32 = 1; pub const MI_MAT_DIELECTRIC: i32 = 2;
 pub const MI_MAT_PARAMETERIZED: i32 = 3; pub const MI_MAT_ISOTROPIC: i32 = 4;
@@ -84,6 +85,12 @@ extern "C" {
                             ray_t_max: *const f32, seed: u32, first_key: u32, out_occluded: *mut u8) -> c_int;
     pub fn mi_occluded_rays_device(ctx: *mut mi_ctx, n_rays: u32, origins: *const f32, dirs: *const f32, t_min: f32, t_max: f32,
                                    ray_t_max: *const f32, seed: u32, first_key: u32, out_occluded: *mut u8, stream: *mut c_void) -> c_int;
+    pub fn mi_hemisphere_occlusion(ctx: *mut mi_ctx, n_points: u32, points: *const f32, normals: *const f32, first_sample: u32,
+                                   n_samples: u32, t_min: f32, t_max: f32, flags: u32, seed: u32, first_key: u32,
+                                   out_open: *mut u32, out_bent: *mut f32) -> c_int;
+    pub fn mi_hemisphere_occlusion_device(ctx: *mut mi_ctx, n_points: u32, points: *const f32, normals: *const f32, first_sample: u32,
+                                          n_samples: u32, t_min: f32, t_max: f32, flags: u32, seed: u32, first_key: u32,
+                                          out_open: *mut u32, out_bent: *mut f32, stream: *mut c_void) -> c_int;
     // ray-table rendering (added within ABI 5): origins / dirs are [rays_per_pixel][H][W][3], rays_per_pixel = 1 or aa_sample_count
     pub fn mi_render_rays(ctx: *mut mi_ctx, cam: *const mi_camera_desc, opts: *const mi_render_opts,
                           origins: *const f32, dirs: *const f32, rays_per_pixel: u32,

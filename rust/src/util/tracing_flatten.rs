@@ -125,6 +125,27 @@ impl Scene {
         occluded.into_iter().map(|b| b != 0).collect()
     }
 
+    /// Ambient-occlusion baking with rays made on the GPU (mi_hemisphere_occlusion): for every surface point, how many of `n_samples`
+    /// hemisphere rays about its normal are NOT occluded within [t_min, t_max], and the sum of the open directions (the bent normal
+    /// before normalisation).  Sample s = first_sample + k of point i takes its direction from Lambertian::scatter's sample_hemisphere
+    /// on the stream (seed, first_key + i, 2s) and tests the ray with the stream (seed, first_key + i, 2s + 1); the normal and the
+    /// direction are used as given.  `world_radius`: t_max is a world-space radius (MI_HEMI_WORLD_RADIUS), not a multiple of |d|.
+    /// A bake split by points (first_key advanced) or by samples (first_sample advanced) gives the counts of one call exactly.
+    pub fn hemisphere_occlusion(&self, points: &[[f32; 3]], normals: &[[f32; 3]], first_sample: u32, n_samples: u32, t_min: f32, t_max: f32,
+                                world_radius: bool, seed: u32, first_key: u32) -> (Vec<u32>, Vec<[f32; 3]>) {
+        assert_eq!(points.len(), normals.len(), "mi_rt: points and normals differ in length");
+        let n = points.len();
+        let mut open = vec![0u32; n];
+        let mut bent = vec![[0.0f32; 3]; n];
+        let (pp, pn) = (points.as_ptr() as *const f32, normals.as_ptr() as *const f32);
+        let (popen, pbent) = (open.as_mut_ptr(), bent.as_mut_ptr() as *mut f32);
+        let flags = if world_radius { mi_rt::MI_HEMI_WORLD_RADIUS } else { 0 };
+        self.with_gpu_scene(|ctx| unsafe {
+            mi_rt::mi_hemisphere_occlusion(ctx, n as u32, pp, pn, first_sample, n_samples, t_min, t_max, flags, seed, first_key, popen, pbent)
+        });
+        (open, bent)
+    }
+
     /// Scene::shade_ray (tracing.rs:300-324) at level 0 for a batch of rays on the GPU (mi_shade_rays): the radiance per ray; the camera
     /// supplies path_depth, path_samples and max_trace_dist.
     pub fn shade_rays(&self, origins: &[[f32; 3]], dirs: &[[f32; 3]], seed: u32, first_key: u32) -> Vec<[f32; 3]> {

@@ -24,7 +24,16 @@ mi_last_kernel_ms for each).  Ray sets: `camera` and `bounce` as above, and
 recursive kernel) on the same rays: one table per scene built from the `camera` rays above, rays_per_pixel = 1.  In one context: the
 shade query on the table's rays, then the table render with aa_sample_count = 1 and with 16; for each 5 warm-up calls, then --calls
 timed calls, median / min / max of mi_last_kernel_ms and Msamples/s (rays x aa_sample_count) from the median.  Context for users, not
-a pass bar."""
+a pass bar.
+
+--mode hemisphere compares hemisphere occlusion (mi_hemisphere_occlusion_device: the rays are made on the GPU and reduced per point)
+with mi_occluded_rays_device fed the IDENTICAL rays, pre-made and already resident — so that run excludes what the feature saves, making
+and uploading the rays.  Points and normals: the library's camera hits (zero normals dropped), at most --points of them, evenly
+strided; 64 samples per point; t_max = 4 in units of |d| (|d| <= 1: about 3 world units in a 6 x 5 x 6 box), flags 0.  The pre-made
+directions come from the library itself: 64 calls with n_samples = 1, first_sample = s and the EMPTY interval [1, 0], under which
+every sample is open and out_bent is that one direction; ray i * 64 + s of the any-hit call is sample s of point i, so a wave holds
+one point's 64 samples in both kernels.  The two alternate call by call (5 warm-up pairs, then --calls timed pairs; median / min / max
+of mi_last_kernel_ms) and the tool checks that the any-hit answers reduce to the hemisphere counts."""
 import argparse
 import json
 import os
@@ -112,6 +121,54 @@ def measure_pair(ctx, o, d, t_max, ray_t_max, calls, warmup):
     return occ, vis
 
 
+HEMI_SAMPLES = 64
+HEMI_T_MAX = 4.0
+
+
+def hemisphere_rows(ctx, cfg, points, normals, calls, warmup):
+    dev = torch.device("cuda:0")
+    n, S = len(points), HEMI_SAMPLES
+    t_p, t_n = torch.from_numpy(points).to(dev), torch.from_numpy(normals).to(dev)
+    t_open = torch.empty(n, dtype=torch.int32, device=dev)
+    t_bent = torch.empty((n, 3), dtype=torch.float32, device=dev)
+    t_d = torch.empty((n, S, 3), dtype=torch.float32, device=dev)
+    for s in range(S):                                   # the directions, from the library: one sample, the empty interval
+        ctx.hemisphere_occlusion_device(n, t_p.data_ptr(), t_n.data_ptr(), t_open.data_ptr(), 1, d_bent=t_bent.data_ptr(),
+                                        t_min=1.0, t_max=0.0, seed=1, first_key=0, first_sample=s)
+        torch.cuda.synchronize()
+        if not bool((t_open == 1).all().item()):
+            raise SystemExit("ray_query_bench: a sample is occluded under the empty interval; the directions cannot be read back")
+        t_d[:, s, :] = t_bent
+    t_o = t_p[:, None, :].expand(n, S, 3).contiguous()
+    t_occ = torch.empty(n * S, dtype=torch.uint8, device=dev)
+    torch.cuda.synchronize()
+    hemi_ms, occ_ms = [], []
+    for k in range(warmup + calls):
+        ctx.hemisphere_occlusion_device(n, t_p.data_ptr(), t_n.data_ptr(), t_open.data_ptr(), S, d_bent=t_bent.data_ptr(),
+                                        t_min=0.001, t_max=HEMI_T_MAX, seed=1, first_key=0)
+        torch.cuda.synchronize()
+        a = ctx.last_kernel_ms()
+        ctx.occluded_rays_device(n * S, t_o.data_ptr(), t_d.data_ptr(), t_occ.data_ptr(), None, t_min=0.001, t_max=HEMI_T_MAX, seed=1)
+        torch.cuda.synchronize()
+        b = ctx.last_kernel_ms()
+        if k >= warmup:
+            hemi_ms.append(a)
+            occ_ms.append(b)
+    reduced = (t_occ.view(n, S) == 0).sum(dim=1).to(torch.int32)
+    mismatches = int((reduced != t_open).sum().item())
+    stat = lambda v: {"kernel_ms_median": round(float(np.median(v)), 4), "kernel_ms_min": round(float(np.min(v)), 4),
+                      "kernel_ms_max": round(float(np.max(v)), 4), "mrays_per_s_kernel": round(n * S / float(np.median(v)) / 1e3, 1)}
+    base = {"config": cfg, "mode": "hemisphere", "n_points": n, "n_samples": S, "t_max": HEMI_T_MAX, "calls": calls,
+            "open_share": round(float(t_open.sum().item()) / (n * S), 4), "count_mismatches": mismatches}
+    rows = [dict(base, query="hemisphere_occlusion", **stat(hemi_ms)), dict(base, query="occluded_rays (pre-made rays)", **stat(occ_ms)),
+            dict(base, query="ratio hemisphere / occluded", kernel_ms_median=round(float(np.median(hemi_ms)) / float(np.median(occ_ms)), 4))]
+    for row in rows:
+        print(json.dumps(row), flush=True)
+    if mismatches:
+        raise SystemExit(f"ray_query_bench: {mismatches} points whose any-hit answers do not reduce to the hemisphere count")
+    return rows
+
+
 SHADOW_POINT = (0.0, 5.9, 0.0)          # just under the Cornell box's ceiling light (y = 6)
 
 
@@ -182,9 +239,11 @@ def main():
     ap.add_argument("--width", type=int, default=1920)
     ap.add_argument("--height", type=int, default=1080)
     ap.add_argument("--configs", default="2,4")
-    ap.add_argument("--mode", choices=("intersect", "occlusion", "render"), default="intersect",
+    ap.add_argument("--mode", choices=("intersect", "occlusion", "render", "hemisphere"), default="intersect",
                     help="intersect: the closest-hit rows; occlusion: the any-hit query against the visibility form; "
-                         "render: ray-table rendering against mi_shade_rays_device")
+                         "render: ray-table rendering against mi_shade_rays_device; "
+                         "hemisphere: hemisphere occlusion against the any-hit query on the identical pre-made rays")
+    ap.add_argument("--points", type=int, default=1 << 18, help="--mode hemisphere: at most this many surface points (64 rays each)")
     ap.add_argument("--out", default=None, help="also append the JSON lines to this file")
     a = ap.parse_args()
     if a.calls < 20:
@@ -206,6 +265,12 @@ def main():
         bd = rng.standard_normal((int(hit.sum()), 3))
         bd = np.ascontiguousarray(bd / np.linalg.norm(bd, axis=1, keepdims=True), np.float32)
         bo = np.ascontiguousarray(first.hitpoint[hit])
+        if a.mode == "hemisphere":
+            ok = np.flatnonzero(hit & np.any(first.normal != 0.0, axis=1))
+            ok = ok[np.linspace(0, len(ok) - 1, min(len(ok), a.points)).astype(np.int64)]
+            rows += hemisphere_rows(ctx, cfg, np.ascontiguousarray(first.hitpoint[ok]), np.ascontiguousarray(first.normal[ok]),
+                                    a.calls, a.warmup)
+            continue
         if a.mode == "occlusion":
             rows += occlusion_rows(ctx, cfg, sc, co, cd, bo, bd, np.ascontiguousarray(first.hitpoint[hit]), a.calls, a.warmup)
             continue
