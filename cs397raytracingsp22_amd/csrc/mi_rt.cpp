@@ -107,7 +107,7 @@ struct mi_ctx {
     uint32_t* d_sigi = nullptr; size_t sigi_bytes = 0;
     unsigned long long* d_diag = nullptr;    // 16 counters of the diagnostic variant
     void* d_rq = nullptr; size_t rq_bytes = 0;               // ray queries, host-pointer forms: rays and results of one chunk (its own buffer: never the pipeline's)
-    void* d_rays = nullptr; size_t rays_bytes = 0;           // mi_render_rays: the uploaded ray table, origins then dirs (its own buffer too)
+    void* d_rays = nullptr; size_t rays_bytes = 0;           // mi_render_rays / mi_render_points: the uploaded table, origins then dirs / points then normals (its own buffer too)
     hipEvent_t ev_t0 = nullptr, ev_t1 = nullptr;     // mi_render's whole-call timer
     bool big_lds_enabled = false;                    // wf_trav_i<1024>'s > 64 KB dynamic-LDS opt-in, set on THIS context's device
     // wavefront pipeline buffers
@@ -476,7 +476,9 @@ private:
 // begin == 0 starts the sums from zero; end == aa_sample_count also writes the per-pixel means.
 struct SampleRange { uint32_t begin, end; float4* accum; };
 // Ray-table rendering: DEVICE arrays [rows][H][W][3] that replace Camera::generate_rays, rows = 1 or aa_sample_count
-struct RayTable { const float* origins; const float* dirs; uint32_t rows; };
+// Point-table rendering (points = true): `origins` holds surface points and `dirs` their normals, same layout; the camera pass draws
+// the direction of each sample itself (the POINTS form of wf_main)
+struct RayTable { const float* origins; const float* dirs; uint32_t rows; bool points; };
 
 static int render_tiles_wavefront(mi_ctx* c, const K1Args& k, const mi_camera_desc* cam, WfArgs a, uint32_t s_batch, uint32_t flags,
                                   float* d_compact, uint32_t* d_sig, SampleRange range, hipStream_t stream) {
@@ -488,7 +490,7 @@ static int render_tiles_wavefront(mi_ctx* c, const K1Args& k, const mi_camera_de
     a.samp = (float4*)c->d_wf_samp; a.accum = range.accum ? range.accum : (float4*)c->d_wf_acc;
     a.out = d_compact; a.sig = d_sig;
     // the tile masks are derived from the camera: a ray table renders without them, whatever the flags say
-    if (a.ray_o) a.tile_mask = nullptr;
+    if (a.ray_o || a.pt_p) a.tile_mask = nullptr;
     else MI_TRY(device_tile_masks(c, cam, flags, a.R.tiles_x, stream, &a.tile_mask));
     a.diag = nullptr;           // developer builds (-DPT_WF_STAMPS): phase stamps of wf_main
     if (c->tune.wf_stamps) { a.diag = c->d_diag; HIP_TRY(hipMemsetAsync(c->d_diag, 0, 16 * sizeof(unsigned long long), stream)); }
@@ -650,7 +652,8 @@ static int render_tiles(mi_ctx* c, const mi_camera_desc* cam, const mi_render_op
         if (cam->aa_sample_count > 0xffffu) return fail(MI_ERR_UNSUPPORTED, "wavefront variant: aa_sample_count must be <= 65535");
         if (cam->path_depth > 0xffffu) return fail(MI_ERR_UNSUPPORTED, "wavefront variant: path_depth must be <= 65535");
         MI_TRY(wf_prepare(c, g.padded, cam->aa_sample_count, o->max_state_bytes, two_stage_mask(c->scene, o->flags) != 0u, wa, wf_batch));
-        if (table) { wa.ray_o = table->origins; wa.ray_d = table->dirs; wa.rays_per_pixel = table->rows; }
+        if (table && table->points) { wa.pt_p = table->origins; wa.pt_n = table->dirs; wa.pt_rows = table->rows; }
+        else if (table) { wa.ray_o = table->origins; wa.ray_d = table->dirs; wa.rays_per_pixel = table->rows; }
     }
     HIP_TRY(hipEventRecord(c->ev_start, stream));
     if (phong)
@@ -987,7 +990,7 @@ extern "C" int mi_selftest(mi_ctx* c, uint64_t* out4) {
     return MI_OK;
 }
 
-// The whole image on this GPU into host buffers: render, un-permute, tone-map, download (mi_render; with `table`, mi_render_rays).
+// The whole image on this GPU into host buffers: render, un-permute, tone-map, download (mi_render; with `table`, mi_render_rays / _points).
 static int render_image(mi_ctx* c, const mi_camera_desc* cam, const mi_render_opts* opts, const RayTable* table, float* out_rgb_f32,
                         uint8_t* out_rgb_u8, uint32_t* out_sig, mi_stats* stats) {
     int rc;
@@ -1043,10 +1046,11 @@ extern "C" int mi_render(mi_ctx* c, const mi_camera_desc* cam, const mi_render_o
 // A table [rows][H][W][3] of origins and one of directions replaces Camera::generate_rays for one render; everything behind the camera
 // pass of the pipeline is mi_render's.  Every refusal happens here, before anything is allocated, copied or launched.
 static int check_table_args(mi_ctx* c, const mi_camera_desc* cam, const mi_render_opts* opts, const float* origins, const float* dirs,
-                            uint32_t rays_per_pixel) {
+                            uint32_t rays_per_pixel, bool points = false) {
     if (!c) return fail(MI_ERR_INVALID, "ctx is NULL");
     if (!opts) return fail(MI_ERR_INVALID, "opts is NULL");
-    if (!origins || !dirs) return fail(MI_ERR_INVALID, "mi_render_rays: the origins and dirs tables are required");
+    if (!origins || !dirs)
+        return fail(MI_ERR_INVALID, points ? "mi_render_points: the points and normals tables are required" : "mi_render_rays: the origins and dirs tables are required");
     MI_TRY(check_table_camera(cam, rays_per_pixel));
     if (opts->variant != MI_VARIANT_DEFAULT && opts->variant != MI_VARIANT_WAVEFRONT)
         return fail(MI_ERR_UNSUPPORTED, "ray-table rendering runs on the default (wavefront) variant only, not variant %d: use mi_shade_rays for the recursive estimator", opts->variant);
@@ -1057,31 +1061,61 @@ static int check_table_args(mi_ctx* c, const mi_camera_desc* cam, const mi_rende
     return MI_OK;
 }
 
-extern "C" int mi_render_rays(mi_ctx* c, const mi_camera_desc* cam, const mi_render_opts* opts, const float* origins, const float* dirs,
-                              uint32_t rays_per_pixel, float* out_rgb_f32, uint8_t* out_rgb_u8, uint32_t* out_sig, mi_stats* stats) {
-    MI_TRY(check_table_args(c, cam, opts, origins, dirs, rays_per_pixel));
-    if (opts->rank != 0 || opts->world != 1) return fail(MI_ERR_INVALID, "mi_render_rays renders a whole image: rank/world must be 0/1");
+// Host pointers: upload the two tables into the context's own buffer, then mi_render's body.  `what` names the entry point in messages.
+static int render_table_host(mi_ctx* c, const mi_camera_desc* cam, const mi_render_opts* opts, const float* first, const float* second,
+                             uint32_t rows, bool points, const char* what, float* out_rgb_f32, uint8_t* out_rgb_u8, uint32_t* out_sig,
+                             mi_stats* stats) {
+    MI_TRY(check_table_args(c, cam, opts, first, second, rows, points));
+    if (opts->rank != 0 || opts->world != 1) return fail(MI_ERR_INVALID, "%s renders a whole image: rank/world must be 0/1", what);
     HIP_TRY(hipSetDevice(c->device));
-    const size_t bytes = (size_t)rays_per_pixel * cam->screen_height * cam->screen_width * 3 * sizeof(float);     // of each table
+    const size_t bytes = (size_t)rows * cam->screen_height * cam->screen_width * 3 * sizeof(float);     // of each table
     MI_TRY(ensure(&c->d_rays, &c->rays_bytes, 2 * bytes));
-    HIP_TRY(hipMemcpyAsync(c->d_rays, origins, bytes, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync((char*)c->d_rays + bytes, dirs, bytes, hipMemcpyHostToDevice, c->stream));
-    const RayTable table = { (const float*)c->d_rays, (const float*)((const char*)c->d_rays + bytes), rays_per_pixel };
+    HIP_TRY(hipMemcpyAsync(c->d_rays, first, bytes, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync((char*)c->d_rays + bytes, second, bytes, hipMemcpyHostToDevice, c->stream));
+    const RayTable table = { (const float*)c->d_rays, (const float*)((const char*)c->d_rays + bytes), rows, points };
     const mi_camera_desc tc = table_camera(cam);
     return render_image(c, &tc, opts, &table, out_rgb_f32, out_rgb_u8, out_sig, stats);
 }
 
-extern "C" int mi_render_rays_device(mi_ctx* c, const mi_camera_desc* cam, const mi_render_opts* opts, const float* d_origins,
-                                     const float* d_dirs, uint32_t rays_per_pixel, uint32_t sample_begin, uint32_t sample_end,
-                                     void* d_accum_f32x4, void* d_compact_f32, void* d_sig_u32, void* stream, mi_stats* stats) {
-    MI_TRY(check_table_args(c, cam, opts, d_origins, d_dirs, rays_per_pixel));
+// Device pointers: mi_render_tiles_device and mi_render_samples_device in one call
+static int render_table_device(mi_ctx* c, const mi_camera_desc* cam, const mi_render_opts* opts, const float* d_first, const float* d_second,
+                               uint32_t rows, bool points, uint32_t sample_begin, uint32_t sample_end, void* d_accum_f32x4,
+                               void* d_compact_f32, void* d_sig_u32, void* stream, mi_stats* stats) {
+    MI_TRY(check_table_args(c, cam, opts, d_first, d_second, rows, points));
     HIP_TRY(hipSetDevice(c->device));
-    const RayTable table = { d_origins, d_dirs, rays_per_pixel };
+    const RayTable table = { d_first, d_second, rows, points };
     const mi_camera_desc tc = table_camera(cam);
     // [0, aa_sample_count) without an accumulator is a whole render (mi_render_tiles_device); anything else a progressive call
     const bool whole = sample_begin == 0 && sample_end == cam->aa_sample_count && !d_accum_f32x4;
     SampleRange r = { sample_begin, sample_end, (float4*)d_accum_f32x4 };
     return render_tiles(c, &tc, opts, (float*)d_compact_f32, (uint32_t*)d_sig_u32, (hipStream_t)stream, stats, whole ? nullptr : &r, &table);
+}
+
+extern "C" int mi_render_rays(mi_ctx* c, const mi_camera_desc* cam, const mi_render_opts* opts, const float* origins, const float* dirs,
+                              uint32_t rays_per_pixel, float* out_rgb_f32, uint8_t* out_rgb_u8, uint32_t* out_sig, mi_stats* stats) {
+    return render_table_host(c, cam, opts, origins, dirs, rays_per_pixel, false, "mi_render_rays", out_rgb_f32, out_rgb_u8, out_sig, stats);
+}
+
+extern "C" int mi_render_rays_device(mi_ctx* c, const mi_camera_desc* cam, const mi_render_opts* opts, const float* d_origins,
+                                     const float* d_dirs, uint32_t rays_per_pixel, uint32_t sample_begin, uint32_t sample_end,
+                                     void* d_accum_f32x4, void* d_compact_f32, void* d_sig_u32, void* stream, mi_stats* stats) {
+    return render_table_device(c, cam, opts, d_origins, d_dirs, rays_per_pixel, false, sample_begin, sample_end, d_accum_f32x4,
+                               d_compact_f32, d_sig_u32, stream, stats);
+}
+
+// ------------------------------------------------------------------ point-table rendering (lightmap baking: the rays are made on the GPU)
+// mi_render_rays with a table of surface points and one of normals: the camera pass draws sample_hemisphere(normal) per sample on a
+// stream of its own, so 24 B per texel cross the bus whatever the sample count.  Same checks, same upload buffer, same body.
+extern "C" int mi_render_points(mi_ctx* c, const mi_camera_desc* cam, const mi_render_opts* opts, const float* points, const float* normals,
+                                uint32_t rows_per_pixel, float* out_rgb_f32, uint8_t* out_rgb_u8, uint32_t* out_sig, mi_stats* stats) {
+    return render_table_host(c, cam, opts, points, normals, rows_per_pixel, true, "mi_render_points", out_rgb_f32, out_rgb_u8, out_sig, stats);
+}
+
+extern "C" int mi_render_points_device(mi_ctx* c, const mi_camera_desc* cam, const mi_render_opts* opts, const float* d_points,
+                                       const float* d_normals, uint32_t rows_per_pixel, uint32_t sample_begin, uint32_t sample_end,
+                                       void* d_accum_f32x4, void* d_compact_f32, void* d_sig_u32, void* stream, mi_stats* stats) {
+    return render_table_device(c, cam, opts, d_points, d_normals, rows_per_pixel, true, sample_begin, sample_end, d_accum_f32x4,
+                               d_compact_f32, d_sig_u32, stream, stats);
 }
 
 // ------------------------------------------------------------------ multi-GPU behind the ABI

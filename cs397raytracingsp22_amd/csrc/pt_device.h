@@ -355,6 +355,12 @@ struct WfArgs {
     const float* ray_o;
     const float* ray_d;
     uint32_t rays_per_pixel;
+    // Point-table rendering (mi_render_points): the camera pass takes the surface point and the normal of sample s of pixel (x, y) from
+    // pt_p / pt_n at the same index (row = s when pt_rows == aa_sample_count, 0 when it is 1) and draws the direction itself:
+    // sample_hemisphere(normal) on the stream (seed, W H + y W + x, s).  A zero normal is an empty texel.  nullptr = no point table.
+    uint32_t pt_rows;
+    const float* pt_p;
+    const float* pt_n;
 };
 
 // How a render walks the meshes that take the reference's tree (scene_compile.cpp plan_walker -> pt_kernels.hip launch_walker).

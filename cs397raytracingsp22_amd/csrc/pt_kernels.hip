@@ -2179,9 +2179,13 @@ __device__ __forceinline__ void wf_pixel_of(const WfArgs& A, uint32_t pix, uint3
 // ITER0 = true: the camera-ray pass (Camera::generate_rays instead of a state load; always the lean form)
 // TOP = true: the list's Triangles sit in a top-level tree (intersect_list<.., TOP>; scenes with long lists only)
 // RAYS = true (with ITER0 only): ray-table rendering — the lane takes (o, d) from the caller's table instead of Camera::generate_rays
-template <bool LDS, bool SIG, bool GV, int MESH, bool RARE, bool ITER0, bool TOP = false, bool RAYS = false>
+// POINTS = true (with ITER0 only, never with RAYS): point-table rendering — the lane takes a surface point and a normal from the caller's
+//   table and draws the direction itself, sample_hemisphere(normal) on a stream of its own; a zero normal marks an empty texel
+template <bool LDS, bool SIG, bool GV, int MESH, bool RARE, bool ITER0, bool TOP = false, bool RAYS = false, bool POINTS = false>
 __global__ __launch_bounds__(kBlock, (MESH == 2 ? PT_MAIN_WAVES : (MESH == 1 ? PT_MAIN_WAVES_NOTEX : PT_MAIN_WAVES_LEAN))) void wf_main(WfArgs A) {
     static_assert(ITER0 || !RAYS, "the ray table replaces Camera::generate_rays: the camera-ray pass only");
+    static_assert(ITER0 || !POINTS, "the point table replaces Camera::generate_rays: the camera-ray pass only");
+    static_assert(!(RAYS && POINTS), "one source of primary rays per form: the ray table or the point table");
     const DScene& S = A.S;
     const DCamera& C = A.C;
     Bvh<LDS> B;            // only the mesh ROOT nodes are read here
@@ -2239,8 +2243,33 @@ __global__ __launch_bounds__(kBlock, (MESH == 2 ? PT_MAIN_WAVES : (MESH == 1 ? P
             A.samp[(size_t)(sample - A.s_base) * A.npix + pix] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
             alive = false;
         }
+        if (POINTS) {
+            if (alive) {
+                // the caller's texel (row, y, x) at ((row H + y) W + x) * 3, row = 0 for a one-row table; 64-bit index, and never formed by a
+                // lane outside the image, as in the RAYS form.  The values are used as given: whatever they hold, no address depends on them.
+                const size_t r = (((size_t)(A.pt_rows == 1u ? 0u : sample) * C.height + py) * C.width + px) * 3;
+                const Ray3 tp = *(const Ray3*)(A.pt_p + r), tn = *(const Ray3*)(A.pt_n + r);
+                if (tn.x == 0.0f && tn.y == 0.0f && tn.z == 0.0f) {
+                    // an empty texel (no surface covers it; either sign of zero): the slot of a lane outside the image, no RNG, no path
+                    A.samp[(size_t)(sample - A.s_base) * A.npix + pix] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+                    alive = false;
+                } else {
+                    // sample_hemisphere(normal) (materials.rs:171-178) as rq_hemi and scatter_raw's diffuse branch make it, on the stream
+                    // (seed, W H + y W + x, sample): pixel keys >= W H belong to no path stream of the image (W, H <= 32768: below 2^31).
+                    // The normal is not normalised and neither is d (|d| <= 1).  `tmp` dies here: the list test sees the RAYS form's registers.
+                    Rng tmp;
+                    rng_init(tmp, A.seed_key, C.width * C.height + (py * C.width + px), sample);
+                    f3 v = rand_sphere_vec(tmp);                                // materials.rs:172
+                    v.y = fabsf(v.y);                                           // :173
+                    P.o = mk3(tp.x, tp.y, tp.z);
+                    P.d = rotate_from_unit_y(mk3(tn.x, tn.y, tn.z), v);         // :176-177
+                }
+            }
+            // a wave of empty texels (and lanes outside the image) has written its slots and owns no path: it leaves before any scene data
+            if (__builtin_amdgcn_ballot_w64(alive) == 0ull) return;
+        }
         if (alive) {
-            rng_init(P.rng, A.seed_key, py * C.width + px, sample);
+            rng_init(P.rng, A.seed_key, py * C.width + px, sample);             // the path's stream: mi_render_rays' for the ray (p, d)
             if (RAYS) {
                 // the caller's ray (s, y, x) at ((s H + y) W + x) * 3, s = 0 for a one-row table; 64-bit index (S W H 3 passes 2^32 at 4K).
                 // Used as given: no draw from the stream, no normalisation.  A lane outside the image never comes here (the table has no
@@ -2248,7 +2277,7 @@ __global__ __launch_bounds__(kBlock, (MESH == 2 ? PT_MAIN_WAVES : (MESH == 1 ? P
                 const size_t r = (((size_t)(A.rays_per_pixel == 1u ? 0u : sample) * C.height + py) * C.width + px) * 3;
                 const Ray3 ro = *(const Ray3*)(A.ray_o + r), rd = *(const Ray3*)(A.ray_d + r);
                 P.o = mk3(ro.x, ro.y, ro.z); P.d = mk3(rd.x, rd.y, rd.z);
-            } else generate_ray(C, px, py, sample, P.rng, P.o, P.d);
+            } else if (!POINTS) generate_ray(C, px, py, sample, P.rng, P.o, P.d);       // POINTS: P.o, P.d were made above
             if (C.path_depth == 0u) {                                     // tracing.rs:301 at level 0: the background, before any intersection
                 if (SIG) P.sig = sig_end_depth(P.sig);
                 A.samp[(size_t)(sample - A.s_base) * A.npix + pix] = make_float4(0.0f, 0.0f, 0.0f, __uint_as_float(P.sig));
@@ -3632,13 +3661,18 @@ hipError_t launch_wf_main(const WfArgs& a, uint32_t n_blocks, bool sig, bool gv,
     // ray-table rendering: the camera pass reads the caller's table (the RAYS form of ITER0); every later pass is the usual one
 #define PT_WF_RAYS(G, V, R) do { if (top) hipLaunchKernelGGL((wf_main<false, G, V, 0, R, true, true, true>), grid, block, 0, stream, a); \
                                  else hipLaunchKernelGGL((wf_main<false, G, V, 0, R, true, false, true>), grid, block, 0, stream, a); } while (0)
-#define PT_WF_MESH(V, R) do { if (a.iter0 && a.ray_o) { if (sig) PT_WF_RAYS(true, V, R); else PT_WF_RAYS(false, V, R); } \
+    // point-table rendering: the camera pass makes its rays from the caller's points and normals (the POINTS form of ITER0), likewise
+#define PT_WF_POINTS(G, V, R) do { if (top) hipLaunchKernelGGL((wf_main<false, G, V, 0, R, true, true, false, true>), grid, block, 0, stream, a); \
+                                   else hipLaunchKernelGGL((wf_main<false, G, V, 0, R, true, false, false, true>), grid, block, 0, stream, a); } while (0)
+#define PT_WF_MESH(V, R) do { if (a.iter0 && a.pt_p) { if (sig) PT_WF_POINTS(true, V, R); else PT_WF_POINTS(false, V, R); } \
+                              else if (a.iter0 && a.ray_o) { if (sig) PT_WF_RAYS(true, V, R); else PT_WF_RAYS(false, V, R); } \
                               else if (a.iter0) PT_WF_SIG(V, 0, R, true); else if (lean) PT_WF_SIG(V, 0, R, false); \
                               else if (tex) PT_WF_SIG(V, 2, R, false); else PT_WF_SIG(V, 1, R, false); } while (0)
     if (!rare) PT_WF_MESH(false, false);
     else if (gv) PT_WF_MESH(true, true);
     else PT_WF_MESH(false, true);
 #undef PT_WF_MESH
+#undef PT_WF_POINTS
 #undef PT_WF_RAYS
 #undef PT_WF_SIG
 #undef PT_WF_MAIN2

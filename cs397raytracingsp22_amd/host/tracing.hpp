@@ -176,6 +176,26 @@ struct Scene : Intersectable {                         // tracing.rs:213-218; `i
         return img;
     }
 
+    // Lightmap baking through mi_render_points: points / normals are [rows_per_pixel][H][W][3], rows_per_pixel = 1 or camera.aa_sample_count.
+    // Sample s of texel (x, y) leaves its point along sample_hemisphere(normal) (materials.rs:171-178), drawn on the GPU from the stream
+    // (seed, W * H + y * W + x, s); its path draws from (seed, y * W + x, s), so the image is render_rays' for those directions.  A zero
+    // normal marks an empty texel (black); points are used as given (the caller offsets them along the normal).
+    RgbImage render_points(const std::vector<float>& points, const std::vector<float>& normals, uint32_t rows_per_pixel, uint32_t seed = 1,
+                           int device = 0, mi_stats* stats = nullptr, std::vector<float>* linear = nullptr) const {
+        const size_t n = (size_t)rows_per_pixel * camera.screen_height * camera.screen_width * 3;
+        if (points.size() != n || normals.size() != n) throw std::runtime_error("mi_rt: points and normals must both be [rows_per_pixel][H][W][3]");
+        const mi_camera_desc cam = camera.flatten();
+        RgbImage img; img.width = camera.screen_width; img.height = camera.screen_height;
+        img.data.resize((size_t)img.width * img.height * 3);
+        if (linear) linear->resize(img.data.size());
+        mi_render_opts opts{}; opts.seed = seed; opts.rank = 0; opts.world = 1;
+        with_context(device, [&](mi_ctx* ctx) {
+            return mi_render_points(ctx, &cam, &opts, points.data(), normals.data(), rows_per_pixel, linear ? linear->data() : nullptr,
+                                    img.data.data(), nullptr, stats);
+        });
+        return img;
+    }
+
 private:
     // flatten -> context -> upload -> `call(ctx)` -> destroy; a failure surfaces as std::runtime_error carrying mi_last_error()
     template <class F> void with_context(int device, F call) const {

@@ -163,6 +163,11 @@ def check_ray_table(cam: "Camera", origins, dirs):
     checked for what the call reads — image size, aa_sample_count in 1..65535 (any value, not only squares), path_depth, path_samples
     (1: the wavefront pipeline), shading_mode (PathTrace), max_trace_dist (not NaN), gamma (finite, > 0); eyepoint .. lens_radius are
     ignored and may hold anything.  Returns (origins, dirs, rays_per_pixel) as C-contiguous [S, H, W, 3] arrays; raises ValueError."""
+    return _check_table(cam, origins, dirs, "ray", "origins", "dirs", "rays")
+
+
+def _check_table(cam: "Camera", first, second, kind: str, first_name: str, second_name: str, unit: str):
+    """check_ray_table / check_point_table: the camera fields a table render reads and the two tables' dtype and shape"""
     W, H, aa = int(cam.screen_width), int(cam.screen_height), int(cam.aa_sample_count)
     if not (1 <= W <= 32768 and 1 <= H <= 32768):
         raise ValueError(f"bad image size {W}x{H}")
@@ -173,9 +178,9 @@ def check_ray_table(cam: "Camera", origins, dirs):
     if int(cam.path_samples) < 1:
         raise ValueError("path_samples must be >= 1 (tracing.rs:318 divides by it)")
     if int(cam.path_samples) != 1:
-        raise ValueError("ray-table rendering runs the wavefront pipeline, path_samples == 1 only: use shade_rays (mi_shade_rays)")
+        raise ValueError(f"{kind}-table rendering runs the wavefront pipeline, path_samples == 1 only: use shade_rays (mi_shade_rays)")
     if cam.shading_mode == ShadingMode.Phong:
-        raise ValueError("ray-table rendering: ShadingMode.Phong is not available for caller-supplied rays (shade_rays has none either)")
+        raise ValueError(f"{kind}-table rendering: ShadingMode.Phong is not available for caller-supplied rays (shade_rays has none either)")
     if cam.shading_mode != ShadingMode.PathTrace:
         raise ValueError(f"unknown shading_mode {cam.shading_mode}")
     if float(cam.max_trace_dist) != float(cam.max_trace_dist):
@@ -184,7 +189,7 @@ def check_ray_table(cam: "Camera", origins, dirs):
     if not (g > 0.0) or g == float("inf"):
         raise ValueError("gamma must be finite and > 0 (tracing.rs:254 raises to 1/gamma)")
     out = []
-    for name, a in (("origins", origins), ("dirs", dirs)):
+    for name, a in ((first_name, first), (second_name, second)):
         a = np.asarray(a)
         if a.dtype != np.float32:
             raise ValueError(f"{name} must be float32, got {a.dtype}")
@@ -193,11 +198,86 @@ def check_ray_table(cam: "Camera", origins, dirs):
         if a.ndim != 4 or a.shape[1:] != (H, W, 3):
             raise ValueError(f"{name} must have shape [S, {H}, {W}, 3] or [{H}, {W}, 3], got {tuple(np.shape(a))}")
         if a.shape[0] not in (1, aa):
-            raise ValueError(f"{name} holds {a.shape[0]} rays per pixel: a ray table holds 1 row or aa_sample_count = {aa} rows")
+            raise ValueError(f"{name} holds {a.shape[0]} {unit} per pixel: a {kind} table holds 1 row or aa_sample_count = {aa} rows")
         out.append(np.ascontiguousarray(a))
     if out[0].shape != out[1].shape:
-        raise ValueError(f"origins and dirs differ in shape: {out[0].shape} and {out[1].shape}")
+        raise ValueError(f"{first_name} and {second_name} differ in shape: {out[0].shape} and {out[1].shape}")
     return out[0], out[1], int(out[0].shape[0])
+
+
+def check_point_table(cam: "Camera", points, normals):
+    """Input checking of point-table rendering (mi_render_points), no GPU needed: check_ray_table for a table of surface points and one
+    of normals — float32 arrays of shape [S, H, W, 3] or [H, W, 3] (= one row), S = 1 or cam.aa_sample_count, and the camera fields a table
+    render reads.  The values are not looked at: a zero normal marks an empty texel, and non-finite texels are the caller's business (they
+    spoil their own pixel only).  Returns (points, normals, rows_per_pixel) as C-contiguous [S, H, W, 3] arrays; raises ValueError."""
+    return _check_table(cam, points, normals, "point", "points", "normals", "rows")
+
+
+def lightmap_texels(positions, normals, texcoords, indices, width: int, height: int, transform=None, offset: float = 0.0):
+    """The point table of a mesh's lightmap, on the host (numpy only): (points [H, W, 3] f32, normals [H, W, 3] f32, covered [H, W] bool)
+    for render_points.  `positions`, `normals` [V, 3], `texcoords` [V, 2] and `indices` [T, 3] are a single-index triangle mesh
+    (objload.Mesh's arrays, flat or shaped).  Texel (x, y) has its centre at u = (x + 0.5) / W, v = 1 - (y + 0.5) / H: the inverse of
+    Texture::sample's x = floor(u W), y = floor((1 - v) H) (texture.rs:28-29), so the baked image, loaded as that mesh's texture, puts
+    every texel back where it was gathered.  A texel is covered when its centre lies inside or on the edge of a triangle in uv space
+    (edge functions in f64, >= 0); where triangles overlap or share an edge the LOWEST triangle index wins; triangles without area in uv
+    cover nothing.  Point and normal are the barycentric interpolation of the triangle's vertices, taken through `transform` (a 4 x 4
+    matrix indexed [row, col] as cgmath.py builds them, e.g. StaticMesh.transform; None = identity): points as points, normals through
+    the inverse transpose of its upper 3 x 3, then normalised.  The point is moved by `offset` along that unit normal (mi_render_points
+    uses the origin as given: a small positive offset keeps the sample rays clear of their own surface).  Uncovered texels — and texels
+    whose interpolated normal has no length — have a zero normal and a zero point: the empty-texel mark of mi_render_points."""
+    W, H = int(width), int(height)
+    if W < 1 or H < 1:
+        raise ValueError("width and height must be >= 1")
+    P = np.asarray(positions, np.float64).reshape(-1, 3)
+    N = np.asarray(normals, np.float64).reshape(-1, 3)
+    T = np.asarray(texcoords, np.float64).reshape(-1, 2)
+    I = np.asarray(indices, np.int64).reshape(-1, 3)
+    if not (len(P) == len(N) == len(T)):
+        raise ValueError(f"positions, normals and texcoords must describe the same vertices, got {len(P)}, {len(N)} and {len(T)}")
+    if I.size and (I.min() < 0 or I.max() >= len(P)):
+        raise ValueError("indices out of range")
+    M = np.eye(4) if transform is None else np.asarray(transform, np.float64).reshape(4, 4)
+    NM = np.linalg.inv(M[:3, :3]).T
+    cu = (np.arange(W) + 0.5) / W                                       # texel centres
+    cv = 1.0 - (np.arange(H) + 0.5) / H
+    pts = np.zeros((H, W, 3), np.float64)
+    nrm = np.zeros((H, W, 3), np.float64)
+    covered = np.zeros((H, W), bool)
+    for a, b, c in I:
+        (ua, va), (ub, vb), (uc, vc) = T[a], T[b], T[c]
+        area = (ub - ua) * (vc - va) - (vb - va) * (uc - ua)
+        if area == 0.0 or not np.isfinite(area):
+            continue
+        # the texel columns / rows whose centres can lie in the triangle's uv box (one texel of slack: the edge functions decide)
+        x0 = max(0, int(np.floor(min(ua, ub, uc) * W - 0.5)) - 1)
+        x1 = min(W - 1, int(np.ceil(max(ua, ub, uc) * W - 0.5)) + 1)
+        y0 = max(0, int(np.floor((1.0 - max(va, vb, vc)) * H - 0.5)) - 1)
+        y1 = min(H - 1, int(np.ceil((1.0 - min(va, vb, vc)) * H - 0.5)) + 1)
+        if x0 > x1 or y0 > y1:
+            continue
+        u, v = np.meshgrid(cu[x0:x1 + 1], cv[y0:y1 + 1])
+        sgn = 1.0 if area > 0.0 else -1.0
+        ea = ((ub - u) * (vc - v) - (vb - v) * (uc - u)) * sgn           # weight of vertex a, times |area|
+        eb = ((uc - u) * (va - v) - (vc - v) * (ua - u)) * sgn
+        ec = ((ua - u) * (vb - v) - (va - v) * (ub - u)) * sgn
+        take = (ea >= 0.0) & (eb >= 0.0) & (ec >= 0.0) & ~covered[y0:y1 + 1, x0:x1 + 1]
+        if not take.any():
+            continue
+        tot = ea + eb + ec
+        wa, wb, wc = (ea / tot)[take], (eb / tot)[take], (ec / tot)[take]
+        yy, xx = np.nonzero(take)
+        pts[y0 + yy, x0 + xx] = wa[:, None] * P[a] + wb[:, None] * P[b] + wc[:, None] * P[c]
+        nrm[y0 + yy, x0 + xx] = wa[:, None] * N[a] + wb[:, None] * N[b] + wc[:, None] * N[c]
+        covered[y0 + yy, x0 + xx] = True
+    pts = pts @ M[:3, :3].T + M[:3, 3]
+    nrm = nrm @ NM.T
+    length = np.sqrt((nrm * nrm).sum(axis=-1))
+    covered &= np.isfinite(length) & (length > 0.0)
+    nrm = nrm / np.where(covered, length, 1.0)[..., None]
+    pts = pts + float(offset) * nrm
+    pts[~covered] = 0.0
+    nrm[~covered] = 0.0
+    return np.ascontiguousarray(pts, np.float32), np.ascontiguousarray(nrm, np.float32), covered
 
 
 def equirect_dirs(lon, lat) -> np.ndarray:
@@ -288,6 +368,10 @@ class Context:
         aa_sample_count) instead of Camera::generate_rays, through the wavefront pipeline.  Sample s of pixel (x, y) draws from the stream
         (seed, y*W + x, s).  Returns what render returns."""
         o, d, rows = check_ray_table(cam, origins, dirs)
+        return self._render_table(self._lib.mi_render_rays, cam, o, d, rows, seed, want_f32, want_u8, want_sig, flags, max_state_bytes)
+
+    def _render_table(self, entry, cam, first, second, rows, seed, want_f32, want_u8, want_sig, flags, max_state_bytes):
+        """mi_render_rays / mi_render_points on checked, contiguous host tables"""
         pod = cam.to_pod()
         opts = abi.mi_render_opts(seed=seed, rank=0, world=1, variant=abi.MI_VARIANT_DEFAULT, want_signature=int(want_sig),
                                   flags=flags, max_state_bytes=max_state_bytes)
@@ -296,14 +380,32 @@ class Context:
         u8 = np.empty((H, W, 3), np.uint8) if want_u8 else None
         sig = np.empty((H, W), np.uint32) if want_sig else None
         st = abi.mi_stats()
-        abi.check(self._lib.mi_render_rays(
-            self._h, C.byref(pod), C.byref(opts), o.ctypes.data, d.ctypes.data, rows,
+        abi.check(entry(
+            self._h, C.byref(pod), C.byref(opts), first.ctypes.data, second.ctypes.data, rows,
             f32.ctypes.data if f32 is not None else None,
             u8.ctypes.data if u8 is not None else None,
             sig.ctypes.data if sig is not None else None, C.byref(st)))
         return f32, u8, sig, st
 
+    def render_points(self, cam: Camera, points, normals, seed: int = 1, want_f32=True, want_u8=True, want_sig=False,
+                      flags: int = 0, max_state_bytes: int = 0):
+        """mi_render_points: the whole image from a point table (check_point_table: surface points and normals, [S, H, W, 3] or
+        [H, W, 3] float32, S = 1 or aa_sample_count), the directions drawn on the GPU: sample s of pixel (x, y) leaves its point along
+        sample_hemisphere(normal) from the stream (seed, W*H + y*W + x, s) and its path draws from (seed, y*W + x, s).  A zero normal is
+        an empty texel (black).  Returns what render returns."""
+        p, n, rows = check_point_table(cam, points, normals)
+        return self._render_table(self._lib.mi_render_points, cam, p, n, rows, seed, want_f32, want_u8, want_sig, flags, max_state_bytes)
+
     # ---- device-pointer building blocks (multi-GPU; pointers are ints, e.g. tensor.data_ptr()) ----
+    def render_points_device(self, cam: Camera, d_points: int, d_normals: int, rows_per_pixel: int, d_compact: Optional[int] = None,
+                             d_sig: Optional[int] = None, sample_begin: int = 0, sample_end: Optional[int] = None,
+                             d_accum: Optional[int] = None, seed: int = 1, rank: int = 0, world: int = 1, stream: Optional[int] = None,
+                             flags: int = 0, max_state_bytes: int = 0):
+        """mi_render_points_device: render_rays_device for a point table held on the device (raw pointers, [rows_per_pixel, H, W, 3]
+        float32 each); the same sample-range, accumulator and rank / world rules."""
+        return self._render_table_device(self._lib.mi_render_points_device, cam, d_points, d_normals, rows_per_pixel, d_compact, d_sig,
+                                         sample_begin, sample_end, d_accum, seed, rank, world, stream, flags, max_state_bytes)
+
     def render_rays_device(self, cam: Camera, d_origins: int, d_dirs: int, rays_per_pixel: int, d_compact: Optional[int] = None,
                            d_sig: Optional[int] = None, sample_begin: int = 0, sample_end: Optional[int] = None,
                            d_accum: Optional[int] = None, seed: int = 1, rank: int = 0, world: int = 1, stream: Optional[int] = None,
@@ -311,13 +413,19 @@ class Context:
         """mi_render_rays_device: render_tiles_device and render_samples_device for a ray table held on the device (raw pointers,
         [rays_per_pixel, H, W, 3] float32 each).  The default range with d_accum None is a whole render of this rank's tiles; any other
         range adds samples [sample_begin, sample_end) to the accumulator, and the call that reaches aa_sample_count writes d_compact."""
+        return self._render_table_device(self._lib.mi_render_rays_device, cam, d_origins, d_dirs, rays_per_pixel, d_compact, d_sig,
+                                         sample_begin, sample_end, d_accum, seed, rank, world, stream, flags, max_state_bytes)
+
+    def _render_table_device(self, entry, cam, d_first, d_second, rows, d_compact, d_sig, sample_begin, sample_end, d_accum, seed, rank,
+                             world, stream, flags, max_state_bytes):
+        """mi_render_rays_device / mi_render_points_device"""
         pod = cam.to_pod()
         opts = abi.mi_render_opts(seed=seed, rank=rank, world=world, variant=abi.MI_VARIANT_DEFAULT,
                                   want_signature=int(d_sig is not None), flags=flags, max_state_bytes=max_state_bytes)
         st = abi.mi_stats()
         end = cam.aa_sample_count if sample_end is None else sample_end
-        abi.check(self._lib.mi_render_rays_device(self._h, C.byref(pod), C.byref(opts), d_origins, d_dirs, rays_per_pixel,
-                                                  sample_begin, end, d_accum, d_compact, d_sig, stream, C.byref(st)))
+        abi.check(entry(self._h, C.byref(pod), C.byref(opts), d_first, d_second, rows,
+                        sample_begin, end, d_accum, d_compact, d_sig, stream, C.byref(st)))
         return st
 
     def render_tiles_device(self, cam: Camera, d_compact: int, d_sig: Optional[int] = None, seed: int = 1,
@@ -640,6 +748,20 @@ class Scene:                         # tracing.rs:213-218
         try:
             ctx.upload(self.flatten())
             _, u8, _, _ = ctx.render_rays(self.camera, o, d, seed=seed, want_f32=False, want_u8=True)
+            return u8
+        finally:
+            ctx.close()
+
+    def render_points(self, points, normals, seed: int = 1, device: int = 0) -> np.ndarray:
+        """A lightmap / irradiance bake (mi_render_points): the RgbImage bytes [H,W,3] u8 of the light gathered at a table of surface
+        points and normals (lightmap_texels makes one from a mesh) — per texel the mean over aa_sample_count cosine-distributed
+        directions of Scene::shade_ray, the directions drawn on the GPU.  This scene's camera supplies the image size, aa_sample_count,
+        path_depth, max_trace_dist and gamma.  Texels with a zero normal are empty and stay black."""
+        p, n, _ = check_point_table(self.camera, points, normals)
+        ctx = Context(device)
+        try:
+            ctx.upload(self.flatten())
+            _, u8, _, _ = ctx.render_points(self.camera, p, n, seed=seed, want_f32=False, want_u8=True)
             return u8
         finally:
             ctx.close()

@@ -383,7 +383,8 @@ int  mi_hemisphere_occlusion_device(mi_ctx* ctx, uint32_t n_points, const float*
  * A ray table replaces Camera::generate_rays (tracing.rs:159-209) for one render; the rest of Scene::render_to_image (tracing.rs:221-263)
  *   stays: per-pixel sums in sample order, the mean, saturation / gamma / bytes.  Fisheye, panoramic and stereo cameras, light probes,
  *   lightmap baking at any sample count: the tuned path of mi_render (classes, LDS walkers, two-stage traversal, batches), not the
- *   recursive kernel of mi_shade_rays.
+ *   recursive kernel of mi_shade_rays.  (A lightmap whose rays are hemisphere samples about a normal needs no ray table at all:
+ *   mi_render_points below takes the points and normals and draws the directions on the GPU.)
  * Layout: the image is cam->screen_width x screen_height (W x H) with cam->aa_sample_count samples per pixel.  `origins` and `dirs` are
  *   two arrays [rays_per_pixel][H][W][3] f32: ray (s, y, x) sits at ((s*H + y)*W + x)*3 (indexed in 64 bits).  rays_per_pixel is
  *   aa_sample_count (sample s of a pixel uses row s) or 1 (every sample of a pixel uses the same ray); anything else is MI_ERR_INVALID.
@@ -416,6 +417,46 @@ int  mi_render_rays_device(mi_ctx* ctx, const mi_camera_desc* cam, const mi_rend
                            const float* d_origins, const float* d_dirs, uint32_t rays_per_pixel,
                            uint32_t sample_begin, uint32_t sample_end, void* d_accum_f32x4,
                            void* d_compact_f32, void* d_sig_u32, void* stream, mi_stats* stats);
+
+/* ---- point-table rendering: lightmap / irradiance baking with the rays made on the GPU (added within ABI version 5: detect by symbol
+ * lookup) ----
+ * mi_render_rays for a table of SURFACE POINTS and NORMALS: 24 B per texel cross the bus whatever the sample count, and the camera pass
+ *   draws the direction of every sample itself.  The pixel's value is the mean over its aa_sample_count samples of
+ *   Scene::shade_ray(Ray(p, d_s), 0) (tracing.rs:300-324) with d_s = sample_hemisphere(n) (materials.rs:171-178), the direction a
+ *   Lambertian::scatter (materials.rs:33-48) would take at that point: the incoming radiance a Lambertian texel gathers, cosine-weighted
+ *   by the sampling — what a lightmap or an irradiance bake stores (multiply by the albedo for outgoing radiance).
+ * Layout: `points` and `normals` are two arrays [rows_per_pixel][H][W][3] f32, texel (row, y, x) at ((row*H + y)*W + x)*3 (indexed in 64
+ *   bits); rows_per_pixel is aa_sample_count (sample s uses row s: a jittered position inside the texel) or 1 (every sample of the pixel
+ *   starts at the same point); anything else is MI_ERR_INVALID.
+ * Two streams per sample s of pixel (x, y):
+ *   direction: (seed, W*H + y*W + x, s), fresh: rand_sphere_vec, y = |y|, rotate_from_unit_y(n, .) — sample_hemisphere with the normal as
+ *     given (NOT normalised: only its direction matters to the rotation, whose quaternion is normalised) and the direction not normalised
+ *     either (|d| <= 1: a point of the unit ball).  Pixel keys >= W*H are used by no path stream of the image; W, H <= 32768 keeps the
+ *     key below 2^31.
+ *   path: (seed, y*W + x, s), fresh: the stream of mi_render_rays.
+ *   Hence the equivalence: mi_render_points(points, normals) == mi_render_rays(points, d) for the table d of those directions, the same
+ *   f32 operations in the same order.
+ * Empty texels: a normal whose three components are all zero (either sign of zero) marks a texel no surface covers.  It draws nothing
+ *   and traces nothing; its samples are zero: f32 0, u8 tone-mapped 0, signature 0.  An image of empty texels only is MI_OK and black.
+ * Origin: the point is used as given.  The caller applies any offset along the normal (lightmap_texels' `offset` in Python); t_min = 0.001
+ *   and t_max = cam->max_trace_dist are in units of |d| <= 1, not of world length, as for any unnormalised ray.
+ * Non-finite input: a NaN or infinite point or normal is not rejected and never faults; it gives an unspecified value for that pixel
+ *   only (no address depends on the table's values; every other pixel's bits are those of the clean render).
+ * Everything else is mi_render_rays', word for word: the camera fields read and ignored, the refusals (NULL tables, rows_per_pixel,
+ *   path_samples != 1, MI_SHADE_PHONG, a variant other than DEFAULT / WAVEFRONT, no scene, rank / world), masks OFF (entry 7 of
+ *   mi_last_pipeline_counts is 0), mi_reserve, max_state_bytes, mi_last_kernel_ms, mi_last_pipeline_ms / _counts, the output layouts.
+ *   stats->samples counts slots, W*H*aa_sample_count for a whole image, empty texels included (the device form cannot know the table's
+ *   contents without reading it).
+ * mi_render_points: HOST pointers, blocking, rank / world 0 / 1; the tables are uploaded into the context's table buffer (mi_render_rays').
+ * mi_render_points_device: DEVICE pointers; the sample range, the accumulator and the rank / world rules are mi_render_rays_device's.
+ *   mi_multi_* takes no table. */
+int  mi_render_points(mi_ctx* ctx, const mi_camera_desc* cam, const mi_render_opts* opts,
+                      const float* points, const float* normals, uint32_t rows_per_pixel,
+                      float* out_rgb_f32, uint8_t* out_rgb_u8, uint32_t* out_sig, mi_stats* stats);
+int  mi_render_points_device(mi_ctx* ctx, const mi_camera_desc* cam, const mi_render_opts* opts,
+                             const float* d_points, const float* d_normals, uint32_t rows_per_pixel,
+                             uint32_t sample_begin, uint32_t sample_end, void* d_accum_f32x4,
+                             void* d_compact_f32, void* d_sig_u32, void* stream, mi_stats* stats);
 
 /* Size and allocate the wavefront pipeline's HBM buffers (path state, sample slots) for
  * this camera with the image shared by `world` ranks, so that the first render does not pay the

@@ -176,6 +176,24 @@ impl Scene {
         img
     }
 
+    /// Lightmap baking (mi_render_points): `points` and `normals` hold `rows_per_pixel` x height x width texels, row-major ([row][y][x]),
+    /// rows_per_pixel = 1 or camera.aa_sample_count.  Sample s of texel (x, y) leaves its point along sample_hemisphere(normal), drawn on
+    /// the GPU from the stream (seed, width * height + y * width + x, s), and its path draws from (seed, y * width + x, s): the image
+    /// render_rays gives for those directions.  A zero normal marks an empty texel (black).  Points are used as given.
+    pub fn render_points(&self, points: &[[f32; 3]], normals: &[[f32; 3]], rows_per_pixel: u32, seed: u32) -> RgbImage {
+        let n = rows_per_pixel as usize * self.camera.screen_height as usize * self.camera.screen_width as usize;
+        assert_eq!(points.len(), n, "mi_rt: the points table must hold rows_per_pixel * height * width texels");
+        assert_eq!(normals.len(), n, "mi_rt: the normals table must hold rows_per_pixel * height * width texels");
+        let cam = self.camera.flatten();
+        let opts = mi_rt::mi_render_opts { seed: seed, rank: 0, world: 1, ..Default::default() };
+        let mut img = RgbImage::new(self.camera.screen_width, self.camera.screen_height);
+        let (pp, pn, pimg) = (points.as_ptr() as *const f32, normals.as_ptr() as *const f32, img.as_mut_ptr());
+        self.with_gpu_scene(|ctx| unsafe {
+            mi_rt::mi_render_points(ctx, &cam, &opts, pp, pn, rows_per_pixel, std::ptr::null_mut(), pimg, std::ptr::null_mut(), std::ptr::null_mut())
+        });
+        img
+    }
+
     /// flatten -> context on device 0 -> upload -> `call` -> destroy; panics with the library's message on failure.
     fn with_gpu_scene<F: FnOnce(*mut mi_rt::mi_ctx) -> i32>(&self, call: F) {
         let sb = self.flatten_scene();

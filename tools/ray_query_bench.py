@@ -33,7 +33,17 @@ strided; 64 samples per point; t_max = 4 in units of |d| (|d| <= 1: about 3 worl
 directions come from the library itself: 64 calls with n_samples = 1, first_sample = s and the EMPTY interval [1, 0], under which
 every sample is open and out_bent is that one direction; ray i * 64 + s of the any-hit call is sample s of point i, so a wave holds
 one point's 64 samples in both kernels.  The two alternate call by call (5 warm-up pairs, then --calls timed pairs; median / min / max
-of mi_last_kernel_ms) and the tool checks that the any-hit answers reduce to the hemisphere counts."""
+of mi_last_kernel_ms) and the tool checks that the any-hit answers reduce to the hemisphere counts.
+
+--mode bake compares point-table rendering (mi_render_points_device: the camera pass draws each sample's hemisphere direction itself)
+with ray-table rendering (mi_render_rays_device) fed the IDENTICAL rays, pre-made and already resident — so that run excludes what the
+feature saves, making and uploading aa_sample_count directions per texel.  The point table is one [H][W] row: the library's camera
+first hits, point = hitpoint + 1e-3 * normal; misses (and hits with a zero normal) are empty texels, whose share is printed.
+aa_sample_count = 16, path_depth 10.  The pre-made directions are restated on the host in numpy (hemisphere_dirs below: the stream
+(seed, W*H + y*W + x, s), rand_sphere_vec, |y|, the rotation from unit y, operation for operation in f32); an empty texel's ray in the
+table starts far outside the scene and meets nothing.  The two alternate call by call (5 warm-up pairs, then --calls timed pairs;
+median / min / max of mi_last_kernel_ms, and their ratio) and the tool checks that the two compact images agree bit for bit on the live
+texels: if they did not, the restated directions would not be the kernel's and the rows would not compare like with like."""
 import argparse
 import json
 import os
@@ -169,6 +179,147 @@ def hemisphere_rows(ctx, cfg, points, normals, calls, warmup):
     return rows
 
 
+BAKE_AA = 16
+
+
+def _lowbias32(x):
+    x = x ^ (x >> np.uint32(16))
+    x = x * np.uint32(0x7feb352d)
+    x = x ^ (x >> np.uint32(15))
+    x = x * np.uint32(0x846ca68b)
+    return x ^ (x >> np.uint32(16))
+
+
+def _rotl(x, k):
+    return (x << np.uint32(k)) | (x >> np.uint32(32 - k))
+
+
+def _ulps_eq(a, b):
+    """approx::ulps_eq!(a, b) with f32 defaults (epsilon = f32::EPSILON, max_ulps = 4), b a scalar"""
+    b = np.float32(b)
+    near = np.abs(a - b) <= np.float32(1.1920929e-07)
+    ia, ib = a.view(np.int32).astype(np.int64), int(np.array(b).view(np.int32))
+    return near | (((a < 0) == (b < 0)) & (np.abs(ia - ib) <= 4))
+
+
+def hemisphere_dirs(normals, seed, key0, sample):
+    """sample_hemisphere(normal) as mi_render_points draws it, for texels i = 0 .. n-1 with keys key0 + i and one sample index:
+    normals [n, 3] f32 (non-zero, finite) -> directions [n, 3] f32.  Every step is the kernel's f32 / u32 operation, in its order."""
+    F, U = np.float32, np.uint32
+    with np.errstate(over="ignore"):
+        n = len(normals)
+        seed_key = _lowbias32(np.array([seed], U) ^ U(0x68e31da4))[0]
+        p0 = _lowbias32(np.arange(n, dtype=U) + U(key0) + seed_key)
+        p1 = _lowbias32(p0 ^ U(0xb5297a4d))
+        smp = np.array([sample], U)
+        s0 = _lowbias32(p0 + (smp * U(0x9e3779b9))[0])
+        s1 = _lowbias32(p1 ^ (smp * U(0x85ebca6b))[0])
+        s1 = np.where((s0 | s1) == 0, U(1), s1)
+
+        def genm11():                                   # xoroshiro64**, then gen_range(-1.0..1.0): value1_2 * 2 + (-1 - 2)
+            nonlocal s0, s1
+            res = _rotl(s0 * U(0x9e3779bb), 5) * U(5)
+            t = s1 ^ s0
+            s0, s1 = _rotl(s0, 26) ^ t ^ (t << U(9)), _rotl(t, 13)
+            return (U(0x3f800000) | (res >> U(9))).view(F) * F(2.0) + F(-3.0)
+
+        v = np.zeros((n, 3), F)
+        todo = np.ones(n, bool)
+        while todo.any():                               # rand_sphere_vec: draw until the point lies in the unit ball
+            c = np.stack([genm11(), genm11(), genm11()], axis=-1)       # (lanes that are done draw on; their stream is not used again)
+            ok = todo & (((c[:, 0] * c[:, 0] + c[:, 1] * c[:, 1]) + c[:, 2] * c[:, 2]) <= F(1.0))
+            v[ok] = c[ok]
+            todo &= ~ok
+    v[:, 1] = np.abs(v[:, 1])
+    nx, ny, nz = (np.ascontiguousarray(normals[:, k], F) for k in range(3))
+    ident = _ulps_eq(ny, 1.0)
+    with np.errstate(all="ignore"):
+        k = np.sqrt(F(1.0) * ((nx * nx + ny * ny) + nz * nz))
+        flip = _ulps_eq(ny / k, -1.0)
+        s = k + ny
+        cx, cz = nz, -nx
+        inv = F(1.0) / np.sqrt(s * s + ((cx * cx + F(0.0)) + cz * cz))
+        qs, qx, qz = np.where(flip, F(0.0), s * inv), np.where(flip, F(0.0), cx * inv), np.where(flip, F(-1.0), cz * inv)
+    x2, z2 = qx + qx, qz + qz
+    xx2, xz2, zz2, sz2, sx2 = x2 * qx, x2 * qz, z2 * qz, z2 * qs, x2 * qs
+    c0 = (F(1.0) - zz2, sz2, xz2)
+    c1 = (-sz2, (F(1.0) - xx2) - zz2, sx2)
+    c2 = (xz2, -sx2, F(1.0) - xx2)
+    d = np.stack([(c0[a] * v[:, 0] + c1[a] * v[:, 1]) + c2[a] * v[:, 2] for a in range(3)], axis=-1).astype(F)
+    d[ident] = v[ident]
+    return d
+
+
+def bake_rows(ctx, cfg, sc, first, calls, warmup):
+    from cs397raytracingsp22_amd import dist as pdist
+    dev = torch.device("cuda:0")
+    cam = sc.camera
+    W, H = cam.screen_width, cam.screen_height
+    cam.aa_sample_count = BAKE_AA
+    live = (first.object >= 0) & np.any(first.normal != 0.0, axis=1)
+    nrm = np.where(live[:, None], first.normal, np.float32(0.0)).astype(np.float32)
+    pts = np.where(live[:, None], first.hitpoint + np.float32(1e-3) * first.normal, np.float32(0.0)).astype(np.float32)
+    idx = np.flatnonzero(live)
+    t_p, t_n = torch.from_numpy(pts).to(dev), torch.from_numpy(nrm).to(dev)        # [H*W, 3] row-major = a table [1][H][W][3]
+    # the same rays as a ray table [aa][H][W][3]; an empty texel's ray starts far above the scene, points away and meets nothing
+    o_row = pts.copy()
+    o_row[~live] = (0.0, 1.0e6, 0.0)
+    t_o = torch.from_numpy(o_row).to(dev)[None].expand(BAKE_AA, W * H, 3).contiguous()
+    t_d = torch.empty((BAKE_AA, W * H, 3), dtype=torch.float32, device=dev)
+    for s in range(BAKE_AA):
+        row = np.zeros((W * H, 3), np.float32)
+        row[:, 1] = 1.0
+        keyed = np.zeros((W * H, 3), np.float32)
+        keyed[:, 1] = 1.0                                # (a unit normal for the empty texels: their directions are discarded)
+        keyed[idx] = nrm[idx]
+        row[idx] = hemisphere_dirs(keyed, 1, W * H, s)[idx]
+        t_d[s] = torch.from_numpy(row).to(dev)
+    n_compact = pdist.tiles_padded(W, H, 1) * pdist.TILE_PIXELS
+    c_pts = torch.empty((n_compact, 3), dtype=torch.float32, device=dev)
+    c_rays = torch.empty((n_compact, 3), dtype=torch.float32, device=dev)
+    torch.cuda.synchronize()
+    pts_ms, rays_ms = [], []
+    for k in range(warmup + calls):
+        ctx.render_points_device(cam, t_p.data_ptr(), t_n.data_ptr(), 1, c_pts.data_ptr(), seed=1)
+        torch.cuda.synchronize()
+        a = ctx.last_kernel_ms()
+        seg_p = ctx.last_pipeline_counts()["segments"]
+        ctx.render_rays_device(cam, t_o.data_ptr(), t_d.data_ptr(), BAKE_AA, c_rays.data_ptr(), seed=1)
+        torch.cuda.synchronize()
+        b = ctx.last_kernel_ms()
+        seg_r = ctx.last_pipeline_counts()["segments"]
+        if k >= warmup:
+            pts_ms.append(a)
+            rays_ms.append(b)
+    # compare on the live texels, through the image layout
+    img_p = torch.empty((H, W, 3), dtype=torch.float32, device=dev)
+    img_r = torch.empty((H, W, 3), dtype=torch.float32, device=dev)
+    ctx.unpermute_device(cam, 1, c_pts.data_ptr(), img_p.data_ptr())
+    ctx.unpermute_device(cam, 1, c_rays.data_ptr(), img_r.data_ptr())
+    torch.cuda.synchronize()
+    t_live = torch.from_numpy(live.reshape(H, W)).to(dev)
+    differ = int(((img_p.view(torch.int32) != img_r.view(torch.int32)).any(dim=-1) & t_live).sum().item())
+    n_live = int(live.sum())
+    stat = lambda v: {"kernel_ms_median": round(float(np.median(v)), 4), "kernel_ms_min": round(float(np.min(v)), 4),
+                      "kernel_ms_max": round(float(np.max(v)), 4),
+                      "msamples_per_s_kernel": round(n_live * BAKE_AA / float(np.median(v)) / 1e3, 1)}
+    ratios = [a / b for a, b in zip(pts_ms, rays_ms)]
+    base = {"config": cfg, "mode": "bake", "width": W, "height": H, "aa_sample_count": BAKE_AA, "path_depth": cam.path_depth,
+            "calls": calls, "live_texels": n_live, "empty_share": round(1.0 - n_live / (W * H), 4), "live_texels_that_differ": differ}
+    rows = [dict(base, query="render_points", segments=seg_p, mean_radiance=round(float(img_p.mean().item()), 6), **stat(pts_ms)),
+            dict(base, query="render_rays (pre-made rays)", segments=seg_r, mean_radiance=round(float(img_r.mean().item()), 6),
+                 **stat(rays_ms)),
+            dict(base, query="ratio render_points / render_rays", kernel_ms_median=round(float(np.median(pts_ms)) / float(np.median(rays_ms)), 4),
+                 pairwise_ratio_median=round(float(np.median(ratios)), 4), pairwise_ratio_min=round(float(np.min(ratios)), 4),
+                 pairwise_ratio_max=round(float(np.max(ratios)), 4))]
+    for row in rows:
+        print(json.dumps(row), flush=True)
+    if differ:
+        raise SystemExit(f"ray_query_bench: {differ} live texels differ between the point-table and the ray-table render: the restated "
+                         "directions are not the kernel's")
+    return rows
+
+
 SHADOW_POINT = (0.0, 5.9, 0.0)          # just under the Cornell box's ceiling light (y = 6)
 
 
@@ -239,10 +390,11 @@ def main():
     ap.add_argument("--width", type=int, default=1920)
     ap.add_argument("--height", type=int, default=1080)
     ap.add_argument("--configs", default="2,4")
-    ap.add_argument("--mode", choices=("intersect", "occlusion", "render", "hemisphere"), default="intersect",
+    ap.add_argument("--mode", choices=("intersect", "occlusion", "render", "hemisphere", "bake"), default="intersect",
                     help="intersect: the closest-hit rows; occlusion: the any-hit query against the visibility form; "
                          "render: ray-table rendering against mi_shade_rays_device; "
-                         "hemisphere: hemisphere occlusion against the any-hit query on the identical pre-made rays")
+                         "hemisphere: hemisphere occlusion against the any-hit query on the identical pre-made rays; "
+                         "bake: point-table rendering against ray-table rendering on the identical pre-made rays")
     ap.add_argument("--points", type=int, default=1 << 18, help="--mode hemisphere: at most this many surface points (64 rays each)")
     ap.add_argument("--out", default=None, help="also append the JSON lines to this file")
     a = ap.parse_args()
@@ -260,6 +412,9 @@ def main():
             rows += render_rows(ctx, cfg, sc, co, cd, a.calls, a.warmup)
             continue
         first = ctx.intersect_rays(co, cd, t_max=sc.camera.max_trace_dist)
+        if a.mode == "bake":
+            rows += bake_rows(ctx, cfg, sc, first, a.calls, a.warmup)
+            continue
         hit = first.object >= 0
         rng = np.random.default_rng(1)
         bd = rng.standard_normal((int(hit.sum()), 3))
