@@ -506,6 +506,19 @@ struct Bvh {
 extern __shared__ float4 k1_lds[];
 __device__ __forceinline__ void bvh_bind(Bvh<true>& B, const DScene&, int nn) { B.nodes = k1_lds; B.tris = k1_lds + nn; }
 __device__ __forceinline__ void bvh_bind(Bvh<false>& B, const DScene& S, int) { B.nodes = (cf4_ptr)S.nodes; B.tris = (cf4_ptr)S.tris; }
+// A kernel's prologue: the whole block stages the mesh pools into LDS (nodes, then triangles) when LDS, then binds B to where they are.
+template <bool LDS>
+__device__ __forceinline__ void stage_bvh(Bvh<LDS>& B, const DScene& S, uint32_t lds_nodes, uint32_t lds_tris) {
+    if (LDS) {
+        cf4_ptr gn = (cf4_ptr)S.nodes;
+        cf4_ptr gt = (cf4_ptr)S.tris;
+        const int nn = (int)lds_nodes * 2, nt = (int)lds_tris * 3;
+        for (int k = threadIdx.x; k < nn; k += kBlock) k1_lds[k] = gn[k];
+        for (int k = threadIdx.x; k < nt; k += kBlock) k1_lds[nn + k] = gt[k];
+        __syncthreads();
+    }
+    bvh_bind(B, S, (int)lds_nodes * 2);
+}
 
 // BVHNode::intersect_ray (geometry.rs:94-119) as a stackless threaded walk.
 // The recursion passes t_max down unchanged to the left child and the left subtree's
@@ -832,6 +845,66 @@ __device__ __forceinline__ void fq_box(float4 c, float4 g, f3& bmin, f3& bmax) {
     bmax = mk3(__builtin_fmaf((float)(w1 >> 16), g.x, g.y), __builtin_fmaf((float)(w2 & 0xffffu), g.x, g.z), __builtin_fmaf((float)(w2 >> 16), g.x, g.w));
 }
 
+// The walk of the list's top-level tree (TOP = true: long lists; the scene compiler decides).  The small Triangles of the list sit in a tree
+// (scene_compile.cpp, bvh_build.hpp FTree: SAH over the triangles' boxes, 16-byte quantised nodes) that every lane walks with the boxes
+// padded by the proven bound (rho, dt of two_stage_pad; the caller has checked that the bound covers the ray) on what the reference's f32
+// test can accept, running the reference's own test on the triangles of the leaves it reaches.  A triangle whose padded box the ray misses
+// would have failed that test; the closest hit over the rest does not depend on the order of evaluation (ties: the lower Scene.objects
+// index, which the leaf triangles carry), and neither does "is there any hit".
+// Pre-order with skip links, no stack (all hits are wanted); the wave votes between a burst of box steps and the triangle tests of the
+// leaves reached, as the walkers do (a lane that has reached a leaf waits for the leaf step).  `enter` = false: the lane walks nothing.
+//   leaf(FT, first, count) -> bool   tests the `count` triangles from `first` of the pool FT; true when the lane is finished
+//   far_end(t_hi) -> float           the far end of the window, asked for at the start and after every leaf
+// The far end may follow the closest hit so far (intersect_list): a triangle that can still win (strictly closer, or as close with a lower
+// index) passes the reference's test at a computed t <= best.t, so the exact line meets its padded box before best.t + dt (the bound's dt
+// covers computed-vs-exact); nothing beyond that can change the result.  NaN distances leave the window as it is.  An any-hit walk has no
+// closest hit to shrink the window to and passes the identity.
+template <class LEAF, class FAR_END>
+__device__ __forceinline__ void walk_list_tree(const DScene& S, const PT_CONST_AS DMeshF* F, f3 o, f3 d, float rho, float dt, float t_min, float t_max,
+                                               bool enter, LEAF leaf, FAR_END far_end) {
+    cf4_ptr FN = (cf4_ptr)S.fnodes;
+    cf4_ptr FT = (cf4_ptr)S.ftris;
+    f3 inv;
+    rcp3_exact(d.x, d.y, d.z, inv.x, inv.y, inv.z);
+    const float t_lo = t_min - dt, t_hi = t_max + dt;
+    const float4 grid = make_float4(F->qs, F->qbx, F->qby, F->qbz);
+    const int fend = F->fnode_end, ftb = F->ftri_begin;
+    int fi = enter ? F->fnode_begin : fend;
+    bool atleaf = false;
+    float4 c = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    if (fi < fend) c = FN[fi];
+    float thi = far_end(t_hi);
+    while (__builtin_amdgcn_ballot_w64(fi < fend) != 0ull) {
+#pragma unroll
+        for (int j = 0; j < 6; j++) {
+            const bool act = (fi < fend) & !atleaf;
+            f3 bmin, bmax;
+            fq_box(c, grid, bmin, bmax);
+            const bool hit = slab_padded(bmin, bmax, o, rho, inv, t_lo, thi);
+            const int link = __float_as_int(c.w);
+            const bool isleaf = link < 0;
+            const bool stop = act & hit & isleaf;
+            const int nxt = (hit | isleaf) ? fi + 1 : link;          // a leaf's successor is the next node either way
+            atleaf = atleaf | stop;
+            const bool move = act & !stop;
+            fi = move ? nxt : fi;
+            if (move & (fi < fend)) c = FN[fi];
+        }
+        const int n_leaf = __popcll(__builtin_amdgcn_ballot_w64(atleaf));
+        const int n_walk = __popcll(__builtin_amdgcn_ballot_w64((fi < fend) & !atleaf));
+        if (n_leaf * 3 >= n_walk) {
+            if (atleaf) {
+                const int payload = __float_as_int(c.w) & 0x7fffffff;
+                const bool fin = leaf(FT, ftb + (payload >> 3), (payload & 7) + 1);
+                fi = fin ? fend : fi + 1;
+                atleaf = false;
+                if (fi < fend) c = FN[fi];
+                thi = far_end(t_hi);
+            }
+        }
+    }
+}
+
 
 // Scene::intersect_ray over the non-mesh objects (tracing.rs:330-344) through the
 // kind-grouped list: one tight loop per kind, the record of the next object loaded (scalar
@@ -880,10 +953,7 @@ __device__ __forceinline__ void sphere_stage1(REC ob, f3 o, f3 d, float a, float
 
 // RARE = false compiles the Plane / ConvexVolume loop out (a scene without either: the Cornell configurations)
 // TOP = true (long lists; the scene compiler decides): only the first n_list_lin Triangles — the large ones — are tested one by one; the others
-// sit in a top-level tree (scene_compile.cpp, bvh_build.hpp FTree: SAH over the triangles' boxes, 16-byte quantised nodes) that every lane walks
-// with the boxes padded by the proven bound on what the reference's f32 test can accept, running the reference's own test on the triangles of
-// the leaves it reaches.  A triangle whose padded box the ray misses would have failed that test; the closest hit over the rest does not
-// depend on the order of evaluation (ties: the lower Scene.objects index, which the leaf triangles carry).  A ray the bound does not cover
+// sit in the top-level tree (walk_list_tree above), whose window follows the closest hit so far.  A ray the bound does not cover
 // (B > 1/2, anything non-finite) makes its whole wave test the rest of the list one by one.
 // (Round 4, measured negative: the Triangle / Sphere records of short lists staged in LDS by wf_main and read from there — a broadcast read
 // lands in VGPRs, and on gfx950 a v_mul_f32 with an SGPR operand issues at 0.6 of the rate of the same multiply on VGPRs
@@ -933,58 +1003,17 @@ __device__ __forceinline__ void intersect_list(const DScene& S, f3 o, f3 d, floa
                 consider_list(best, have, ok0, t0, r0->index, -1);
             }
         } else {
-            cf4_ptr FN = (cf4_ptr)S.fnodes;
-            cf4_ptr FT = (cf4_ptr)S.ftris;
-            f3 inv;
-            rcp3_exact(d.x, d.y, d.z, inv.x, inv.y, inv.z);
-            const float t_lo = t_min - dt, t_hi = t_max + dt;
-            const float4 grid = make_float4(F->qs, F->qbx, F->qby, F->qbz);
-            const int fend = F->fnode_end, ftb = F->ftri_begin;
-            int fi = F->fnode_begin;
-            // pre-order with skip links, no stack (all hits are wanted); the wave votes between a burst of box steps and the triangle tests
-            // of the leaves reached, as the walkers do (a lane that has reached a leaf waits for the leaf step)
-            bool atleaf = false;
-            float4 c = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-            if (fi < fend) c = FN[fi];
-            // The window's far end follows the closest hit so far: a triangle that can still win (strictly closer, or as close with a lower
-            // index) passes the reference's test at a computed t <= best.t, so the exact line meets its padded box before best.t + dt (the
-            // bound's dt covers computed-vs-exact); nothing beyond that can change the result.  NaN distances leave the window as it is.
-            float thi = have ? fminf(t_hi, best.t + dt) : t_hi;
-            while (__builtin_amdgcn_ballot_w64(fi < fend) != 0ull) {
-#pragma unroll
-                for (int j = 0; j < 6; j++) {
-                    const bool act = (fi < fend) & !atleaf;
-                    f3 bmin, bmax;
-                    fq_box(c, grid, bmin, bmax);
-                    const bool hit = slab_padded(bmin, bmax, o, rho, inv, t_lo, thi);
-                    const int link = __float_as_int(c.w);
-                    const bool leaf = link < 0;
-                    const bool stop = act & hit & leaf;
-                    const int nxt = (hit | leaf) ? fi + 1 : link;            // a leaf's successor is the next node either way
-                    atleaf = atleaf | stop;
-                    const bool move = act & !stop;
-                    fi = move ? nxt : fi;
-                    if (move & (fi < fend)) c = FN[fi];
-                }
-                const int n_leaf = __popcll(__builtin_amdgcn_ballot_w64(atleaf));
-                const int n_walk = __popcll(__builtin_amdgcn_ballot_w64((fi < fend) & !atleaf));
-                if (n_leaf * 3 >= n_walk) {
-                    if (atleaf) {
-                        const int payload = __float_as_int(c.w) & 0x7fffffff;
-                        const int first = ftb + (payload >> 3), count = (payload & 7) + 1;
-                        for (int j = 0; j < count; j++) {
-                            const float4 t0 = FT[3 * (first + j)], t1 = FT[3 * (first + j) + 1], t2 = FT[3 * (first + j) + 2];
-                            float t, u, v;
-                            const bool ok = tri_t(o, d, mk3(t0.x, t0.y, t0.z), mk3(t1.x, t1.y, t1.z), mk3(t2.x, t2.y, t2.z), t_min, t_max, t, u, v);
-                            consider_list(best, have, ok, t, __float_as_int(t0.w), -1);       // t0.w: the triangle's Scene.objects index
-                        }
-                        fi = fi + 1;
-                        atleaf = false;
-                        if (fi < fend) c = FN[fi];
-                        thi = have ? fminf(t_hi, best.t + dt) : t_hi;
+            walk_list_tree(S, F, o, d, rho, dt, t_min, t_max, true,
+                [&](cf4_ptr FT, int first, int count) {
+                    for (int j = 0; j < count; j++) {
+                        const float4 t0 = FT[3 * (first + j)], t1 = FT[3 * (first + j) + 1], t2 = FT[3 * (first + j) + 2];
+                        float t, u, v;
+                        const bool ok = tri_t(o, d, mk3(t0.x, t0.y, t0.z), mk3(t1.x, t1.y, t1.z), mk3(t2.x, t2.y, t2.z), t_min, t_max, t, u, v);
+                        consider_list(best, have, ok, t, __float_as_int(t0.w), -1);       // t0.w: the triangle's Scene.objects index
                     }
-                }
-            }
+                    return false;                                                         // all hits are wanted
+                },
+                [&](float t_hi) { return have ? fminf(t_hi, best.t + dt) : t_hi; });
         }
         k = S.n_list_tri;
     }
@@ -1150,15 +1179,7 @@ __global__ __launch_bounds__(kBlock) void pt_megakernel(K1Args A) {
 
     // ---- stage the mesh BVH into LDS (nodes then triangles) ----
     Bvh<LDS> B;
-    if (LDS) {
-        cf4_ptr gn = (cf4_ptr)S.nodes;
-        cf4_ptr gt = (cf4_ptr)S.tris;
-        int nn = (int)A.R.lds_nodes * 2, nt = (int)A.R.lds_tris * 3;
-        for (int k = threadIdx.x; k < nn; k += kBlock) k1_lds[k] = gn[k];
-        for (int k = threadIdx.x; k < nt; k += kBlock) k1_lds[nn + k] = gt[k];
-        __syncthreads();
-    }
-    bvh_bind(B, S, (int)A.R.lds_nodes * 2);
+    stage_bvh(B, S, A.R.lds_nodes, A.R.lds_tris);
 
     // ---- lane -> pixel ----
     const uint32_t slot = blockIdx.x / kBlocksPerTile;            // tile slot of this rank
@@ -1262,11 +1283,13 @@ __global__ __launch_bounds__(kBlock) void pt_megakernel(K1Args A) {
 // Scene::phong_shade_ray (tracing.rs:277-297), the reference's debug shader: one primary hit, a point
 // light with a shadow ray, ambient + diffuse*attenuation + specular.  Not a performance path: one lane
 // per pixel, samples in order, BVH walked in line from global memory.
-template <class BVH>
+// intersect_scene: `impl Intersectable for Scene` (tracing.rs:326-346) for one lane, walks run to completion in line — the completeness paths
+// (pt_phong, pt_branch, rq_shade) with the defaults, rq_intersect with the forms its scene needs.
+template <bool GV = true, bool TOP = false, class BVH>
 __device__ __forceinline__ void intersect_scene(const DScene& S, const BVH& B, f3 o, f3 d, float t_min, float t_max,
                                                 Rng& rng, Best& best) {
     best.obj = -1; best.t = 0.0f; best.tri = -1; best.u = best.v = 0.0f;
-    intersect_list(S, o, d, t_min, t_max, rng, best);
+    intersect_list<GV, true, TOP>(S, o, d, t_min, t_max, rng, best);     // tracing.rs:330-344
     for (int m = 0; m < S.n_meshes; m++) {                               // geometry.rs:301-314
         auto M = &S.meshes[m];
         f3 oo = xform_point(M->inv_transform, o);
@@ -1470,24 +1493,16 @@ __global__ __launch_bounds__(kBlock) void pt_branch(K1Args A, uint32_t path_samp
 // ---------------------------------------------------------------- ray queries: caller-supplied rays (mi_intersect_rays / mi_shade_rays)
 // rq_intersect: `impl Intersectable for Scene` (tracing.rs:326-346) for a batch of rays the CALLER made — picking, visibility and occlusion
 // probes, cameras the reference does not have.  One lane per ray, a grid-stride loop over 256-ray chunks on a grid of at most what is
-// resident, so that the LDS form stages the meshes' node and triangle pools once per block and not once per chunk.  Per ray: intersect_list
-// over the kind-grouped list (wave-uniform records, the staged Sphere test, the top-level tree when the scene has one), then every mesh of
-// Scene.objects through the reference's own tree (traverse_mesh; exact for every mesh — the two-stage machinery is not wired in here), as
-// intersect_scene does.  Ray i draws from the stream (seed, first_key + i, 0), fresh: only a ConvexVolume reads it.
+// resident, so that the LDS form stages the meshes' node and triangle pools once per block and not once per chunk.  Per ray: intersect_scene
+// — intersect_list over the kind-grouped list (wave-uniform records, the staged Sphere test, the top-level tree when the scene has one), then
+// every mesh of Scene.objects through the reference's own tree (traverse_mesh; exact for every mesh — the two-stage machinery is not wired in
+// here).  Ray i draws from the stream (seed, first_key + i, 0), fresh: only a ConvexVolume reads it.
 // RESOLVE = false is the visibility form: object and distance only, resolve_hit and its attribute / texel gathers compiled out.
 template <bool LDS, bool GV, bool TOP, bool RESOLVE>
 __global__ __launch_bounds__(kBlock) void rq_intersect(RqArgs A) {
     const DScene& S = A.S;
     Bvh<LDS> B;
-    if (LDS) {
-        cf4_ptr gn = (cf4_ptr)S.nodes;
-        cf4_ptr gt = (cf4_ptr)S.tris;
-        const int nn = (int)A.lds_nodes * 2, nt = (int)A.lds_tris * 3;
-        for (int k = threadIdx.x; k < nn; k += kBlock) k1_lds[k] = gn[k];
-        for (int k = threadIdx.x; k < nt; k += kBlock) k1_lds[nn + k] = gt[k];
-        __syncthreads();
-    }
-    bvh_bind(B, S, (int)A.lds_nodes * 2);
+    stage_bvh(B, S, A.lds_nodes, A.lds_tris);
     const float t_min = A.t_min, t_max = A.t_max;
     const uint32_t n_chunks = (A.n_rays + (uint32_t)kBlock - 1u) / (uint32_t)kBlock;
     for (uint32_t chunk = blockIdx.x; chunk < n_chunks; chunk += gridDim.x) {
@@ -1498,15 +1513,8 @@ __global__ __launch_bounds__(kBlock) void rq_intersect(RqArgs A) {
         const f3 d = mk3(A.dirs[3 * r], A.dirs[3 * r + 1], A.dirs[3 * r + 2]);
         Rng rng;
         rng_init(rng, A.seed_key, A.first_key + (uint32_t)r, 0u);
-        Best best; best.obj = -1; best.t = 0.0f; best.tri = -1; best.u = best.v = 0.0f;
-        intersect_list<GV, true, TOP>(S, o, d, t_min, t_max, rng, best);    // tracing.rs:330-344
-        for (int m = 0; m < S.n_meshes; m++) {                              // geometry.rs:301-314
-            auto M = &S.meshes[m];
-            const f3 oo = xform_point(M->inv_transform, o), od = xform_vector(M->inv_transform, d);
-            float bt, bu, bv; int btri;
-            traverse_mesh(B, M->node_begin, M->node_end, M->tri_begin, oo, od, t_min, t_max, bt, btri, bu, bv);
-            if (btri >= 0) consider(best, bt, M->object_index, btri, bu, bv);
-        }
+        Best best;
+        intersect_scene<GV, TOP>(S, B, o, d, t_min, t_max, rng, best);      // tracing.rs:326-346
         if (!live) continue;
         const bool hit = best.obj >= 0;
         A.out_object[i] = best.obj;
@@ -1586,6 +1594,16 @@ __device__ __forceinline__ bool occluded_mesh(const BVH& B, int node_begin, int 
     }
     return found;
 }
+// every mesh of Scene.objects (geometry.rs:301-314), any-hit: the wave leaves before a mesh that none of its lanes needs
+template <class BVH>
+__device__ __forceinline__ void occluded_meshes(const DScene& S, const BVH& B, f3 o, f3 d, float t_min, float t_max, bool& done) {
+    for (int m = 0; m < S.n_meshes; m++) {
+        if (__builtin_amdgcn_ballot_w64(!done) == 0ull) break;
+        auto M = &S.meshes[m];
+        const f3 oo = xform_point(M->inv_transform, o), od = xform_vector(M->inv_transform, d);
+        done = done | occluded_mesh(B, M->node_begin, M->node_end, M->tri_begin, !done, oo, od, t_min, t_max);
+    }
+}
 
 // `boundary.intersect_ray(..)` of a ConvexVolume is a closest-hit question (its distance is used): boundary_hit as it stands.
 // ConvexVolume::intersect_ray geometry.rs:502-526 -> Some / None, one draw where the reference draws one.
@@ -1608,7 +1626,7 @@ __device__ __forceinline__ bool occluded_volume(const DScene& S, OP ob, f3 o, f3
 }
 
 // The kind-grouped list, any-hit.  Returns with `done` set for every lane some list entry stops; returns early (wave-uniform) once no lane
-// of the wave is left.  TOP: the top-level tree over the small Triangles of a long list (intersect_list<.., TOP> above) with the same
+// of the wave is left.  TOP: the top-level tree over the small Triangles of a long list (walk_list_tree above) with the same
 // padded-box bound and the same fallback to the plain loop for a wave that holds an uncovered ray; the window is not shrunk (there is no
 // closest hit to shrink it to) and a lane stops at its first accepted leaf triangle.
 template <bool GV, bool TOP>
@@ -1645,52 +1663,18 @@ __device__ __forceinline__ void occluded_list(const DScene& S, f3 o, f3 d, float
                 done = done | tri_t(o, d, ld3(r0->f), ld3(r0->f + 3), ld3(r0->f + 6), t_min, t_max, t0, u0, v0);
             }
         } else {
-            cf4_ptr FN = (cf4_ptr)S.fnodes;
-            cf4_ptr FT = (cf4_ptr)S.ftris;
-            f3 inv;
-            rcp3_exact(d.x, d.y, d.z, inv.x, inv.y, inv.z);
-            const float t_lo = t_min - dt, t_hi = t_max + dt;
-            const float4 grid = make_float4(F->qs, F->qbx, F->qby, F->qbz);
-            const int fend = F->fnode_end, ftb = F->ftri_begin;
-            int fi = done ? fend : F->fnode_begin;
-            bool atleaf = false;
-            float4 c = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-            if (fi < fend) c = FN[fi];
-            while (__builtin_amdgcn_ballot_w64(fi < fend) != 0ull) {
-#pragma unroll
-                for (int j = 0; j < 6; j++) {
-                    const bool act = (fi < fend) & !atleaf;
-                    f3 bmin, bmax;
-                    fq_box(c, grid, bmin, bmax);
-                    const bool hit = slab_padded(bmin, bmax, o, rho, inv, t_lo, t_hi);
-                    const int link = __float_as_int(c.w);
-                    const bool leaf = link < 0;
-                    const bool stop = act & hit & leaf;
-                    const int nxt = (hit | leaf) ? fi + 1 : link;            // a leaf's successor is the next node either way
-                    atleaf = atleaf | stop;
-                    const bool move = act & !stop;
-                    fi = move ? nxt : fi;
-                    if (move & (fi < fend)) c = FN[fi];
-                }
-                const int n_leaf = __popcll(__builtin_amdgcn_ballot_w64(atleaf));
-                const int n_walk = __popcll(__builtin_amdgcn_ballot_w64((fi < fend) & !atleaf));
-                if (n_leaf * 3 >= n_walk) {
-                    if (atleaf) {
-                        const int payload = __float_as_int(c.w) & 0x7fffffff;
-                        const int first = ftb + (payload >> 3), count = (payload & 7) + 1;
-                        bool ok = false;
-                        for (int j = 0; j < count && !ok; j++) {
-                            const float4 t0 = FT[3 * (first + j)], t1 = FT[3 * (first + j) + 1], t2 = FT[3 * (first + j) + 2];
-                            float t, u, v;
-                            ok = tri_t(o, d, mk3(t0.x, t0.y, t0.z), mk3(t1.x, t1.y, t1.z), mk3(t2.x, t2.y, t2.z), t_min, t_max, t, u, v);
-                        }
-                        done = done | ok;
-                        fi = ok ? fend : fi + 1;
-                        atleaf = false;
-                        if (fi < fend) c = FN[fi];
+            walk_list_tree(S, F, o, d, rho, dt, t_min, t_max, !done,
+                [&](cf4_ptr FT, int first, int count) {
+                    bool ok = false;
+                    for (int j = 0; j < count && !ok; j++) {
+                        const float4 t0 = FT[3 * (first + j)], t1 = FT[3 * (first + j) + 1], t2 = FT[3 * (first + j) + 2];
+                        float t, u, v;
+                        ok = tri_t(o, d, mk3(t0.x, t0.y, t0.z), mk3(t1.x, t1.y, t1.z), mk3(t2.x, t2.y, t2.z), t_min, t_max, t, u, v);
                     }
-                }
-            }
+                    done = done | ok;
+                    return ok;                                                            // the lane leaves at its first accepted triangle
+                },
+                [](float t_hi) { return t_hi; });
         }
         k = S.n_list_tri;
         if (__builtin_amdgcn_ballot_w64(!done) == 0ull) return;
@@ -1743,15 +1727,7 @@ template <bool LDS, bool GV, bool TOP>
 __global__ __launch_bounds__(kBlock) void rq_occluded(RqOccArgs A) {
     const DScene& S = A.S;
     Bvh<LDS> B;
-    if (LDS) {
-        cf4_ptr gn = (cf4_ptr)S.nodes;
-        cf4_ptr gt = (cf4_ptr)S.tris;
-        const int nn = (int)A.lds_nodes * 2, nt = (int)A.lds_tris * 3;
-        for (int k = threadIdx.x; k < nn; k += kBlock) k1_lds[k] = gn[k];
-        for (int k = threadIdx.x; k < nt; k += kBlock) k1_lds[nn + k] = gt[k];
-        __syncthreads();
-    }
-    bvh_bind(B, S, (int)A.lds_nodes * 2);
+    stage_bvh(B, S, A.lds_nodes, A.lds_tris);
     const float t_min = A.t_min;
     const uint32_t n_chunks = (A.n_rays + (uint32_t)kBlock - 1u) / (uint32_t)kBlock;
     for (uint32_t chunk = blockIdx.x; chunk < n_chunks; chunk += gridDim.x) {
@@ -1765,12 +1741,7 @@ __global__ __launch_bounds__(kBlock) void rq_occluded(RqOccArgs A) {
         rng_init(rng, A.seed_key, A.first_key + (uint32_t)r, 0u);
         bool done = !live;                                                  // idle lanes of the last chunk ask nothing
         occluded_list<GV, TOP>(S, o, d, t_min, t_max, rng, done);
-        for (int m = 0; m < S.n_meshes; m++) {                              // geometry.rs:301-314
-            if (__builtin_amdgcn_ballot_w64(!done) == 0ull) break;         // a mesh no lane of the wave needs
-            auto M = &S.meshes[m];
-            const f3 oo = xform_point(M->inv_transform, o), od = xform_vector(M->inv_transform, d);
-            done = done | occluded_mesh(B, M->node_begin, M->node_end, M->tri_begin, !done, oo, od, t_min, t_max);
-        }
+        occluded_meshes(S, B, o, d, t_min, t_max, done);
         if (live) A.out_occluded[i] = done ? (uint8_t)1 : (uint8_t)0;
     }
 }
@@ -1793,15 +1764,7 @@ template <bool LDS, bool GV, bool TOP>
 __global__ __launch_bounds__(kBlock) void rq_hemi(RqHemiArgs A) {
     const DScene& S = A.S;
     Bvh<LDS> B;
-    if (LDS) {
-        cf4_ptr gn = (cf4_ptr)S.nodes;
-        cf4_ptr gt = (cf4_ptr)S.tris;
-        const int nn = (int)A.lds_nodes * 2, nt = (int)A.lds_tris * 3;
-        for (int k = threadIdx.x; k < nn; k += kBlock) k1_lds[k] = gn[k];
-        for (int k = threadIdx.x; k < nt; k += kBlock) k1_lds[nn + k] = gt[k];
-        __syncthreads();
-    }
-    bvh_bind(B, S, (int)A.lds_nodes * 2);
+    stage_bvh(B, S, A.lds_nodes, A.lds_tris);
     const float t_min = A.t_min;
     const uint32_t gl = A.group_log2, G = 1u << gl;
     const uint32_t sub = threadIdx.x & (G - 1u);                            // this lane's place in its group
@@ -1829,12 +1792,7 @@ __global__ __launch_bounds__(kBlock) void rq_hemi(RqHemiArgs A) {
             rng_init(rng, A.seed_key, key, 2u * s + 1u);
             bool done = !have;                                              // tail lanes ask nothing
             occluded_list<GV, TOP>(S, o, d, t_min, t_max, rng, done);
-            for (int m = 0; m < S.n_meshes; m++) {                          // geometry.rs:301-314
-                if (__builtin_amdgcn_ballot_w64(!done) == 0ull) break;     // a mesh no lane of the wave needs
-                auto M = &S.meshes[m];
-                const f3 oo = xform_point(M->inv_transform, o), od = xform_vector(M->inv_transform, d);
-                done = done | occluded_mesh(B, M->node_begin, M->node_end, M->tri_begin, !done, oo, od, t_min, t_max);
-            }
+            occluded_meshes(S, B, o, d, t_min, t_max, done);
             const bool is_open = have & !done;
             open += is_open ? 1u : 0u;
             bent = mk3(is_open ? bent.x + d.x : bent.x, is_open ? bent.y + d.y : bent.y, is_open ? bent.z + d.z : bent.z);
@@ -1922,15 +1880,7 @@ __global__ __launch_bounds__(kBlock, PT_MIN_WAVES) void pt_megakernel_voted(K1Ar
     const DCamera& C = A.C;
 
     Bvh<LDS> B;
-    if (LDS) {
-        cf4_ptr gn = (cf4_ptr)S.nodes;
-        cf4_ptr gt = (cf4_ptr)S.tris;
-        int nn = (int)A.R.lds_nodes * 2, nt = (int)A.R.lds_tris * 3;
-        for (int k = threadIdx.x; k < nn; k += kBlock) k1_lds[k] = gn[k];
-        for (int k = threadIdx.x; k < nt; k += kBlock) k1_lds[nn + k] = gt[k];
-        __syncthreads();
-    }
-    bvh_bind(B, S, (int)A.R.lds_nodes * 2);
+    stage_bvh(B, S, A.R.lds_nodes, A.R.lds_tris);
 
     const uint32_t slot = blockIdx.x / kBlocksPerTile;
     const uint32_t sub = blockIdx.x % kBlocksPerTile;
@@ -2174,21 +2124,22 @@ __device__ __forceinline__ void wf_pixel_of(const WfArgs& A, uint32_t pix, uint3
     }
 }
 
-// MESH = false: the lean form for launches that cannot meet a mesh hit (iteration 0 and the class-A part of a later pass)
+// MESH = 0: the lean form for launches that cannot meet a mesh hit (iteration 0 and the class-A part of a later pass); 1: meshes without maps; 2: with
 // RARE = false: the scene holds no Plane and no ConvexVolume (their loop and the free-flight code are compiled out)
-// ITER0 = true: the camera-ray pass (Camera::generate_rays instead of a state load; always the lean form)
+// SRC: where a lane's ray comes from.  WF_STATE: the path state of the previous pass.  The other three are the camera-ray pass (always the
+//   lean form), which makes primary rays instead of loading a state:
+//   WF_CAMERA  Camera::generate_rays
+//   WF_RAYS    ray-table rendering — the lane takes (o, d) from the caller's table instead
+//   WF_POINTS  point-table rendering — the lane takes a surface point and a normal from the caller's table and draws the direction itself,
+//              sample_hemisphere(normal) on a stream of its own; a zero normal marks an empty texel
 // TOP = true: the list's Triangles sit in a top-level tree (intersect_list<.., TOP>; scenes with long lists only)
-// RAYS = true (with ITER0 only): ray-table rendering — the lane takes (o, d) from the caller's table instead of Camera::generate_rays
-// POINTS = true (with ITER0 only, never with RAYS): point-table rendering — the lane takes a surface point and a normal from the caller's
-//   table and draws the direction itself, sample_hemisphere(normal) on a stream of its own; a zero normal marks an empty texel
-template <bool LDS, bool SIG, bool GV, int MESH, bool RARE, bool ITER0, bool TOP = false, bool RAYS = false, bool POINTS = false>
+enum WfSrc { WF_STATE, WF_CAMERA, WF_RAYS, WF_POINTS };
+template <bool SIG, bool GV, int MESH, bool RARE, WfSrc SRC, bool TOP>
 __global__ __launch_bounds__(kBlock, (MESH == 2 ? PT_MAIN_WAVES : (MESH == 1 ? PT_MAIN_WAVES_NOTEX : PT_MAIN_WAVES_LEAN))) void wf_main(WfArgs A) {
-    static_assert(ITER0 || !RAYS, "the ray table replaces Camera::generate_rays: the camera-ray pass only");
-    static_assert(ITER0 || !POINTS, "the point table replaces Camera::generate_rays: the camera-ray pass only");
-    static_assert(!(RAYS && POINTS), "one source of primary rays per form: the ray table or the point table");
+    constexpr bool ITER0 = SRC != WF_STATE, RAYS = SRC == WF_RAYS, POINTS = SRC == WF_POINTS;
     const DScene& S = A.S;
     const DCamera& C = A.C;
-    Bvh<LDS> B;            // only the mesh ROOT nodes are read here
+    Bvh<false> B;          // only the mesh ROOT nodes are read here
     bvh_bind(B, S, 0);     // roots come from global memory (scalar load: wave-uniform address)
     const float t_min = 0.001f, t_max = C.max_trace_dist;
     const uint32_t cap = A.cap;
@@ -3564,29 +3515,28 @@ hipError_t launch_selftest_rcp(unsigned long long* d_mismatches, hipStream_t str
     hipLaunchKernelGGL(selftest_rcp, dim3(4096), dim3(256), 0, stream, d_mismatches);
     return hipGetLastError();
 }
-hipError_t launch_megakernel(const K1Args& args, uint32_t n_blocks, bool lds, bool sig, size_t lds_bytes, hipStream_t stream) {
-    dim3 grid(n_blocks), block(kBlock);
-#define PT_LAUNCH(L, G) hipLaunchKernelGGL((pt_megakernel<L, G>), grid, block, (L) ? lds_bytes : 0, stream, args)
-    if (lds) { if (sig) PT_LAUNCH(true, true); else PT_LAUNCH(true, false); }
-    else     { if (sig) PT_LAUNCH(false, true); else PT_LAUNCH(false, false); }
-#undef PT_LAUNCH
+// One launch of a kernel picked from a table of instantiations: `fn` takes the one argument struct `a` by value.
+template <class Args> static hipError_t launch_form(const void* fn, const Args& a, uint32_t n_blocks, size_t dyn, hipStream_t stream) {
+    Args args = a;
+    void* params[] = { (void*)&args };
+    (void)hipLaunchKernel(fn, dim3(n_blocks), dim3(kBlock), params, dyn, stream);
     return hipGetLastError();
+}
+hipError_t launch_megakernel(const K1Args& args, uint32_t n_blocks, bool lds, bool sig, size_t lds_bytes, hipStream_t stream) {
+    static const void* const fn[2][2] = { { (const void*)&pt_megakernel<false, false>, (const void*)&pt_megakernel<false, true> },
+                                          { (const void*)&pt_megakernel<true, false>, (const void*)&pt_megakernel<true, true> } };   // [lds][sig]
+    return launch_form(fn[lds][sig], args, n_blocks, lds ? lds_bytes : 0, stream);
 }
 
 hipError_t launch_megakernel_voted(const K1Args& args, uint32_t n_blocks, bool lds, bool sig, bool diag, bool gv,
                                    size_t lds_bytes, hipStream_t stream) {
-    dim3 grid(n_blocks), block(kBlock);
-    // gv: the scene holds a ConvexVolume whose boundary is not the inline sphere (boundary_hit); the diagnostic form always carries it
-#define PT_LAUNCH_V(L, G, D, V) hipLaunchKernelGGL((pt_megakernel_voted<L, G, D, V>), grid, block, (L) ? lds_bytes : 0, stream, args)
-    if (diag) { if (lds) PT_LAUNCH_V(true, true, true, true); else PT_LAUNCH_V(false, true, true, true); }
-    else if (gv) {
-        if (lds) { if (sig) PT_LAUNCH_V(true, true, false, true); else PT_LAUNCH_V(true, false, false, true); }
-        else     { if (sig) PT_LAUNCH_V(false, true, false, true); else PT_LAUNCH_V(false, false, false, true); }
-    }
-    else if (lds) { if (sig) PT_LAUNCH_V(true, true, false, false); else PT_LAUNCH_V(true, false, false, false); }
-    else          { if (sig) PT_LAUNCH_V(false, true, false, false); else PT_LAUNCH_V(false, false, false, false); }
-#undef PT_LAUNCH_V
-    return hipGetLastError();
+    // gv: the scene holds a ConvexVolume whose boundary is not the inline sphere (boundary_hit); the diagnostic form always carries it, and SIG
+#define PT_V(L) { (const void*)&pt_megakernel_voted<L, false, false, false>, (const void*)&pt_megakernel_voted<L, true, false, false>, \
+                  (const void*)&pt_megakernel_voted<L, false, false, true>, (const void*)&pt_megakernel_voted<L, true, false, true>, \
+                  (const void*)&pt_megakernel_voted<L, true, true, true> }
+    static const void* const fn[2][5] = { PT_V(false), PT_V(true) };     // [lds][sig + 2 * gv; 4: the diagnostic form]
+#undef PT_V
+    return launch_form(fn[lds][diag ? 4 : (int)sig + 2 * (int)gv], args, n_blocks, lds ? lds_bytes : 0, stream);
 }
 
 hipError_t launch_phong(const K1Args& a, uint32_t n_blocks, bool sig, hipStream_t stream) {
@@ -3601,46 +3551,39 @@ hipError_t launch_branch(const K1Args& a, uint32_t n_blocks, uint32_t path_sampl
     else hipLaunchKernelGGL((pt_branch<false>), grid, block, 0, stream, a, path_samples);
     return hipGetLastError();
 }
-// Ray queries.  The grid is what the device holds at once (the kernel strides over the 256-ray chunks), at most one block per chunk.
-template <class Args> static hipError_t launch_rq_resident(const void* fn, const Args& a, size_t dyn, int n_cus, hipStream_t stream) {
-    const uint32_t n_chunks = (a.n_rays + (uint32_t)kBlock - 1u) / (uint32_t)kBlock;
+// Ray queries.  The grid is what the device holds at once (the kernel strides over its `n_units` units of work: 256-ray chunks, or
+// rq_hemi's block trips), at most one block per unit.
+template <class Args> static hipError_t launch_rq_resident(const void* fn, const Args& a, uint32_t n_units, size_t dyn, int n_cus, hipStream_t stream) {
     int per_cu = 0;
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, kBlock, dyn) != hipSuccess || per_cu < 1) { (void)hipGetLastError(); per_cu = 1; }
     const uint64_t resident = (uint64_t)per_cu * (uint64_t)(n_cus > 0 ? n_cus : 1);
-    const uint32_t n_blocks = (uint32_t)(resident < (uint64_t)n_chunks ? resident : (uint64_t)n_chunks);
+    const uint32_t n_blocks = (uint32_t)(resident < (uint64_t)n_units ? resident : (uint64_t)n_units);
     Args args = a;
     void* params[] = { (void*)&args };
     return hipLaunchKernel(fn, dim3(n_blocks), dim3(kBlock), params, dyn, stream);
 }
+static uint32_t rq_chunks(uint32_t n_rays) { return (n_rays + (uint32_t)kBlock - 1u) / (uint32_t)kBlock; }
 hipError_t launch_rq_intersect(const RqArgs& a, bool lds, bool gv, bool resolve, size_t lds_bytes, int n_cus, hipStream_t stream) {
 #define PT_RQ(L, G) { { (const void*)&rq_intersect<L, G, true, true>, (const void*)&rq_intersect<L, G, true, false> }, \
                       { (const void*)&rq_intersect<L, G, false, true>, (const void*)&rq_intersect<L, G, false, false> } }
     static const void* const fn[2][2][2][2] = { { PT_RQ(true, true), PT_RQ(true, false) }, { PT_RQ(false, true), PT_RQ(false, false) } };   // [!lds][!gv][!top][!resolve]: `true` first, the order the forms have always been instantiated in
 #undef PT_RQ
-    return launch_rq_resident(fn[!lds][!gv][a.S.top_meshf < 0][!resolve], a, lds ? lds_bytes : 0, n_cus, stream);
+    return launch_rq_resident(fn[!lds][!gv][a.S.top_meshf < 0][!resolve], a, rq_chunks(a.n_rays), lds ? lds_bytes : 0, n_cus, stream);
 }
 hipError_t launch_rq_occluded(const RqOccArgs& a, bool lds, bool gv, size_t lds_bytes, int n_cus, hipStream_t stream) {
 #define PT_RQ(L, G) { (const void*)&rq_occluded<L, G, true>, (const void*)&rq_occluded<L, G, false> }
     static const void* const fn[2][2][2] = { { PT_RQ(true, true), PT_RQ(true, false) }, { PT_RQ(false, true), PT_RQ(false, false) } };   // [!lds][!gv][!top], likewise
 #undef PT_RQ
-    return launch_rq_resident(fn[!lds][!gv][a.S.top_meshf < 0], a, lds ? lds_bytes : 0, n_cus, stream);
+    return launch_rq_resident(fn[!lds][!gv][a.S.top_meshf < 0], a, rq_chunks(a.n_rays), lds ? lds_bytes : 0, n_cus, stream);
 }
 // rq_hemi: the resident grid again, over the block trips of 256 >> group_log2 points
 hipError_t launch_rq_hemi(const RqHemiArgs& a, bool lds, bool gv, size_t lds_bytes, int n_cus, hipStream_t stream) {
 #define PT_RQ(L, G) { (const void*)&rq_hemi<L, G, true>, (const void*)&rq_hemi<L, G, false> }
     static const void* const fn[2][2][2] = { { PT_RQ(true, true), PT_RQ(true, false) }, { PT_RQ(false, true), PT_RQ(false, false) } };   // [!lds][!gv][!top]
 #undef PT_RQ
-    const void* f = fn[!lds][!gv][a.S.top_meshf < 0];
-    const size_t dyn = lds ? lds_bytes : 0;
     const uint32_t per_trip = (uint32_t)kBlock >> a.group_log2;
-    const uint32_t n_trips = a.n_points / per_trip + ((a.n_points & (per_trip - 1u)) != 0u ? 1u : 0u);
-    int per_cu = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, f, kBlock, dyn) != hipSuccess || per_cu < 1) { (void)hipGetLastError(); per_cu = 1; }
-    const uint64_t resident = (uint64_t)per_cu * (uint64_t)(n_cus > 0 ? n_cus : 1);
-    const uint32_t n_blocks = (uint32_t)(resident < (uint64_t)n_trips ? resident : (uint64_t)n_trips);
-    RqHemiArgs args = a;
-    void* params[] = { (void*)&args };
-    return hipLaunchKernel(f, dim3(n_blocks), dim3(kBlock), params, dyn, stream);
+    const uint32_t n_trips = a.n_points / per_trip + ((a.n_points & (per_trip - 1u)) != 0u ? 1u : 0u);      // no wrap near 2^32, as in the kernel
+    return launch_rq_resident(fn[!lds][!gv][a.S.top_meshf < 0], a, n_trips, lds ? lds_bytes : 0, n_cus, stream);
 }
 hipError_t launch_rq_shade(const RqShadeArgs& a, hipStream_t stream) {
     const uint32_t n_blocks = (a.n_rays + (uint32_t)kBlock - 1u) / (uint32_t)kBlock;
@@ -3648,35 +3591,25 @@ hipError_t launch_rq_shade(const RqShadeArgs& a, hipStream_t stream) {
     return hipGetLastError();
 }
 hipError_t launch_wf_main(const WfArgs& a, uint32_t n_blocks, bool sig, bool gv, bool tex, hipStream_t stream) {
-    dim3 grid(n_blocks), block(kBlock);
+#define PT_WF_TOP(G, V, M, R, SRC) { (const void*)&wf_main<G, V, M, R, SRC, false>, (const void*)&wf_main<G, V, M, R, SRC, true> }
+#define PT_WF_FORMS(G, V, R) { PT_WF_TOP(G, V, 0, R, WF_STATE), PT_WF_TOP(G, V, 1, R, WF_STATE), PT_WF_TOP(G, V, 2, R, WF_STATE), \
+                               PT_WF_TOP(G, V, 0, R, WF_CAMERA), PT_WF_TOP(G, V, 0, R, WF_RAYS), PT_WF_TOP(G, V, 0, R, WF_POINTS) }
+#define PT_WF_LISTS(G) { PT_WF_FORMS(G, false, false), PT_WF_FORMS(G, false, true), PT_WF_FORMS(G, true, true) }
+    // [sig][list kinds: plain / rare / rare + gv][form: state lean / notex / tex (= MESH), camera, ray table, point table][top]
+    static const void* const fn[2][3][6][2] = { PT_WF_LISTS(false), PT_WF_LISTS(true) };
+#undef PT_WF_LISTS
+#undef PT_WF_FORMS
+#undef PT_WF_TOP
     // gv: the scene holds a ConvexVolume whose boundary is not the inline sphere.  tex: some mesh takes its material from maps or has a
     // normal map.  The lean form (no mesh branch) serves the launches that cannot meet a mesh hit: the camera-ray pass, the class-A
     // part of a later pass, every pass of a scene without meshes.
     const bool lean = a.iter0 != 0u || a.part == 1u || a.S.n_meshes == 0;
     const bool rare = a.S.n_list_plane + a.S.n_list_volume > 0;          // (gv implies rare: it is a kind of ConvexVolume)
     const bool top = a.S.top_meshf >= 0;                                  // the list's Triangles in a top-level tree (long lists)
-#define PT_WF_MAIN2(G, V, M, R, I) do { if (top) hipLaunchKernelGGL((wf_main<false, G, V, M, R, I, true>), grid, block, 0, stream, a); \
-                                        else hipLaunchKernelGGL((wf_main<false, G, V, M, R, I, false>), grid, block, 0, stream, a); } while (0)
-#define PT_WF_SIG(V, M, R, I) do { if (sig) PT_WF_MAIN2(true, V, M, R, I); else PT_WF_MAIN2(false, V, M, R, I); } while (0)
-    // ray-table rendering: the camera pass reads the caller's table (the RAYS form of ITER0); every later pass is the usual one
-#define PT_WF_RAYS(G, V, R) do { if (top) hipLaunchKernelGGL((wf_main<false, G, V, 0, R, true, true, true>), grid, block, 0, stream, a); \
-                                 else hipLaunchKernelGGL((wf_main<false, G, V, 0, R, true, false, true>), grid, block, 0, stream, a); } while (0)
-    // point-table rendering: the camera pass makes its rays from the caller's points and normals (the POINTS form of ITER0), likewise
-#define PT_WF_POINTS(G, V, R) do { if (top) hipLaunchKernelGGL((wf_main<false, G, V, 0, R, true, true, false, true>), grid, block, 0, stream, a); \
-                                   else hipLaunchKernelGGL((wf_main<false, G, V, 0, R, true, false, false, true>), grid, block, 0, stream, a); } while (0)
-#define PT_WF_MESH(V, R) do { if (a.iter0 && a.pt_p) { if (sig) PT_WF_POINTS(true, V, R); else PT_WF_POINTS(false, V, R); } \
-                              else if (a.iter0 && a.ray_o) { if (sig) PT_WF_RAYS(true, V, R); else PT_WF_RAYS(false, V, R); } \
-                              else if (a.iter0) PT_WF_SIG(V, 0, R, true); else if (lean) PT_WF_SIG(V, 0, R, false); \
-                              else if (tex) PT_WF_SIG(V, 2, R, false); else PT_WF_SIG(V, 1, R, false); } while (0)
-    if (!rare) PT_WF_MESH(false, false);
-    else if (gv) PT_WF_MESH(true, true);
-    else PT_WF_MESH(false, true);
-#undef PT_WF_MESH
-#undef PT_WF_POINTS
-#undef PT_WF_RAYS
-#undef PT_WF_SIG
-#undef PT_WF_MAIN2
-    return hipGetLastError();
+    // the camera pass of point-table rendering makes its rays from the caller's points and normals, that of ray-table rendering reads the
+    // caller's table; every later pass is the usual one
+    const int form = a.iter0 ? (a.pt_p ? 5 : a.ray_o ? 4 : 3) : lean ? 0 : tex ? 2 : 1;
+    return launch_form(fn[sig][!rare ? 0 : gv ? 2 : 1][form][top], a, n_blocks, 0, stream);
 }
 // The walker of the reference's tree that `p` names (scene_compile.cpp plan_walker).  big_lds_enabled: the calling context's record of
 // wf_trav_i<1024>'s > 64 KB dynamic-LDS opt-in.  The attribute belongs to the function ON THE CURRENT DEVICE, so it is kept per
