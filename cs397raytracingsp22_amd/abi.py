@@ -116,6 +116,7 @@ EXPORTS = [
     "mi_hemisphere_occlusion", "mi_hemisphere_occlusion_device",
     "mi_render_rays", "mi_render_rays_device",
     "mi_render_points", "mi_render_points_device",
+    "mi_render_probes", "mi_render_probes_device",
     "mi_multi_create", "mi_multi_create_loopback", "mi_multi_destroy", "mi_multi_device_count", "mi_multi_context", "mi_multi_scene_upload", "mi_multi_reserve", "mi_multi_render",
 ]
 
@@ -215,6 +216,13 @@ def load() -> C.CDLL:
     lib.mi_render_points_device.argtypes = [vp, C.POINTER(mi_camera_desc), C.POINTER(mi_render_opts), vp, vp, C.c_uint32,
                                             C.c_uint32, C.c_uint32, vp, vp, vp, vp, C.POINTER(mi_stats)]
     lib.mi_render_points_device.restype = C.c_int
+    # light probes (added within ABI 5): mi_render_points' argument lists without the normals, with out_sh / d_compact_sh
+    lib.mi_render_probes.argtypes = [vp, C.POINTER(mi_camera_desc), C.POINTER(mi_render_opts), vp, C.c_uint32,
+                                     vp, vp, vp, vp, C.POINTER(mi_stats)]
+    lib.mi_render_probes.restype = C.c_int
+    lib.mi_render_probes_device.argtypes = [vp, C.POINTER(mi_camera_desc), C.POINTER(mi_render_opts), vp, C.c_uint32,
+                                            C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp, C.POINTER(mi_stats)]
+    lib.mi_render_probes_device.restype = C.c_int
     lib.mi_multi_create.argtypes = [C.c_int, C.POINTER(C.c_int), C.POINTER(vp)]
     lib.mi_multi_create.restype = C.c_int
     lib.mi_multi_create_loopback.argtypes = [C.c_int, C.c_int, C.POINTER(vp)]

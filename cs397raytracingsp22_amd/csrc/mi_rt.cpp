@@ -46,10 +46,13 @@ hipError_t launch_wf_replay(const WfArgs& a, uint32_t n_blocks, hipStream_t stre
 hipError_t launch_wf_prefix(uint32_t* out_count, uint32_t* trav_count, uint32_t* in_count, uint32_t* in_blkpfx,
                             uint32_t* trav_pfx, uint32_t* hdr, uint32_t* host_hdr, uint32_t seq, hipStream_t stream);
 hipError_t launch_wf_reduce(const WfArgs& a, bool first_batch, bool last_batch, hipStream_t stream);
+hipError_t launch_wf_reduce_sh(const WfArgs& a, bool first_batch, bool last_batch, hipStream_t stream);
 hipError_t launch_unpermute(const float* gathered, float* image, uint32_t width, uint32_t height, uint32_t tiles_x,
                             uint32_t world, uint32_t tiles_padded, hipStream_t stream);
 hipError_t launch_sig_unpermute(const uint32_t* gathered, uint32_t* image, uint32_t width, uint32_t height,
                                 uint32_t tiles_x, uint32_t world, uint32_t tiles_padded, hipStream_t stream);
+hipError_t launch_sh_unpermute(const float* gathered, float* image, uint32_t width, uint32_t height, uint32_t tiles_x,
+                               uint32_t world, uint32_t tiles_padded, hipStream_t stream);
 hipError_t launch_tonemap(const float* image, uint8_t* out, uint32_t n_pixels, float inv_gamma, hipStream_t stream);
 hipError_t launch_selftest_rcp(unsigned long long* d_mismatches, hipStream_t stream);
 }  // namespace pt
@@ -108,6 +111,7 @@ struct mi_ctx {
     unsigned long long* d_diag = nullptr;    // 16 counters of the diagnostic variant
     void* d_rq = nullptr; size_t rq_bytes = 0;               // ray queries, host-pointer forms: rays and results of one chunk (its own buffer: never the pipeline's)
     void* d_rays = nullptr; size_t rays_bytes = 0;           // mi_render_rays / mi_render_points: the uploaded table, origins then dirs / points then normals (its own buffer too)
+    void* d_sh = nullptr; size_t sh_bytes = 0;               // mi_render_probes: the compact SH records, then the un-permuted [H][W][9][3] plane
     hipEvent_t ev_t0 = nullptr, ev_t1 = nullptr;     // mi_render's whole-call timer
     bool big_lds_enabled = false;                    // wf_trav_i<1024>'s > 64 KB dynamic-LDS opt-in, set on THIS context's device
     // wavefront pipeline buffers
@@ -128,7 +132,7 @@ struct mi_ctx {
         void* d_words = nullptr; size_t d_bytes = 0;
     } masks;
     std::vector<hipEvent_t> wf_ev;                   // event pool for per-kernel timing of the pipeline
-    float wf_ms[8] = { 0, 0, 0, 0, 0, 0, 0, 0 };     // last frame: wf_main, wf_trav, wf_reduce totals (ms), launches, wf_trav_f, wf_replay
+    float wf_ms[8] = { 0, 0, 0, 0, 0, 0, 0, 0 };     // last frame: wf_main, wf_trav, wf_reduce totals (ms), launches, wf_trav_f, wf_replay, class A, wf_reduce_sh
     int n_cus = 256;
     // Developer knobs (MI_RT_* environment variables), read ONCE in mi_ctx_create; none is needed for
     // normal operation and none changes a result — what a caller may want to control is in mi_render_opts.
@@ -261,6 +265,7 @@ extern "C" void mi_ctx_destroy(mi_ctx* c) {
     if (c->d_diag) (void)hipFree(c->d_diag);
     if (c->d_rq) (void)hipFree(c->d_rq);
     if (c->d_rays) (void)hipFree(c->d_rays);
+    if (c->d_sh) (void)hipFree(c->d_sh);
     if (c->d_wf_a) (void)hipFree(c->d_wf_a);
     if (c->d_wf_b) (void)hipFree(c->d_wf_b);
     if (c->d_wf_samp) (void)hipFree(c->d_wf_samp);
@@ -436,7 +441,7 @@ private:
 // Per-launch timing of the pipeline: one event pair per launch from the context's pool, summed per kind into wf_ms after the
 // frame.  One pair is ~0.4 ms per frame of extra barriers: nothing on a whole frame (109 ms), 3 % of a 1/8 share, so multi-rank
 // renders skip it unless asked (MI_RT_WF_KERNEL_TIMING=0/1 overrides).
-enum LaunchKind { kMain, kTrav, kReduce, kTravF, kReplay, kMainA };      // kTravF: wf_filter_f too; kMainA: wf_main's class-A part on the second stream
+enum LaunchKind { kMain, kTrav, kReduce, kTravF, kReplay, kMainA, kReduceSh };      // kTravF: wf_filter_f too; kMainA: wf_main's class-A part on the second stream
 class LaunchTimer {
 public:
     LaunchTimer(mi_ctx* c, bool on) : c_(c), on_(on) {}
@@ -447,7 +452,7 @@ public:
         if (stamp(kind, on) != MI_OK) return fail(MI_ERR_HIP, "event");
         return MI_OK;
     }
-    // after the frame (the streams have drained): wf_ms = {wf_main, wf_trav, wf_reduce} ms, launches, {wf_trav_f, wf_replay, class A} ms
+    // after the frame (the streams have drained): wf_ms = {wf_main, wf_trav, wf_reduce} ms, launches, {wf_trav_f, wf_replay, class A, wf_reduce_sh} ms
     void finish() {
         for (int k = 0; k < 8; k++) c_->wf_ms[k] = 0.0f;
         c_->wf_ms[3] = (float)(used_ / 2);
@@ -458,7 +463,7 @@ public:
         }
     }
 private:
-    static constexpr const char* kNames[6] = { "wf_main", "wf_trav", "wf_reduce", "wf_trav_f", "wf_replay", "wf_main (class A, beside the walkers)" };
+    static constexpr const char* kNames[7] = { "wf_main", "wf_trav", "wf_reduce", "wf_trav_f", "wf_replay", "wf_main (class A, beside the walkers)", "wf_reduce_sh" };
     int stamp(LaunchKind kind, hipStream_t on) {          // before AND after the launch
         if (!on_) return MI_OK;
         if (used_ == c_->wf_ev.size()) { hipEvent_t e; if (hipEventCreate(&e) != hipSuccess) return MI_ERR_HIP; c_->wf_ev.push_back(e); }
@@ -478,7 +483,10 @@ struct SampleRange { uint32_t begin, end; float4* accum; };
 // Ray-table rendering: DEVICE arrays [rows][H][W][3] that replace Camera::generate_rays, rows = 1 or aa_sample_count
 // Point-table rendering (points = true): `origins` holds surface points and `dirs` their normals, same layout; the camera pass draws
 // the direction of each sample itself (the POINTS form of wf_main)
-struct RayTable { const float* origins; const float* dirs; uint32_t rows; bool points; };
+// Light probes (kind = kTableProbes): `origins` holds probe positions, `dirs` is nullptr; the camera pass draws a full-sphere direction (the
+// PROBES form) and `sh`, DEVICE [tiles_padded][1024][27] or nullptr, takes the SH L2 sums (wf_reduce_sh)
+enum TableKind { kTableRays, kTablePoints, kTableProbes };
+struct RayTable { const float* origins; const float* dirs; uint32_t rows; TableKind kind; float* sh; };
 
 static int render_tiles_wavefront(mi_ctx* c, const K1Args& k, const mi_camera_desc* cam, WfArgs a, uint32_t s_batch, uint32_t flags,
                                   float* d_compact, uint32_t* d_sig, SampleRange range, hipStream_t stream) {
@@ -588,6 +596,8 @@ static int render_tiles_wavefront(mi_ctx* c, const K1Args& k, const mi_camera_de
             if (p.last) { it++; break; }
         }
         MI_TRY(timer.run(kReduce, stream, [&] { return launch_wf_reduce(a, s0 == 0, s0 + a.s_count >= spp, stream); }));
+        // light probes: the SH sums of the same slots, same batch rules (the slots are rewritten by the next batch only, behind this)
+        if (a.sh) MI_TRY(timer.run(kReduceSh, stream, [&] { return launch_wf_reduce_sh(a, s0 == 0, s0 + a.s_count >= spp, stream); }));
         // the headers not read yet (statistics; passes launched behind the one that ended every path are not counted)
         const uint32_t launched = c->hdr_seq + 1u - seq0;
         while (seen < launched) { MI_TRY(ring.wait(seq0 + seen)); consume(!all_dead); }
@@ -652,7 +662,10 @@ static int render_tiles(mi_ctx* c, const mi_camera_desc* cam, const mi_render_op
         if (cam->aa_sample_count > 0xffffu) return fail(MI_ERR_UNSUPPORTED, "wavefront variant: aa_sample_count must be <= 65535");
         if (cam->path_depth > 0xffffu) return fail(MI_ERR_UNSUPPORTED, "wavefront variant: path_depth must be <= 65535");
         MI_TRY(wf_prepare(c, g.padded, cam->aa_sample_count, o->max_state_bytes, two_stage_mask(c->scene, o->flags) != 0u, wa, wf_batch));
-        if (table && table->points) { wa.pt_p = table->origins; wa.pt_n = table->dirs; wa.pt_rows = table->rows; }
+        if (table && table->kind != kTableRays) {
+            wa.pt_p = table->origins; wa.pt_n = table->dirs; wa.pt_rows = table->rows;
+            wa.pt_probes = table->kind == kTableProbes ? 1u : 0u; wa.sh = table->sh;
+        }
         else if (table) { wa.ray_o = table->origins; wa.ray_d = table->dirs; wa.rays_per_pixel = table->rows; }
     }
     HIP_TRY(hipEventRecord(c->ev_start, stream));
@@ -991,8 +1004,9 @@ extern "C" int mi_selftest(mi_ctx* c, uint64_t* out4) {
 }
 
 // The whole image on this GPU into host buffers: render, un-permute, tone-map, download (mi_render; with `table`, mi_render_rays / _points).
+// out_sh (mi_render_probes): table->sh holds the compact SH records; un-permuted into the plane behind them and downloaded as well.
 static int render_image(mi_ctx* c, const mi_camera_desc* cam, const mi_render_opts* opts, const RayTable* table, float* out_rgb_f32,
-                        uint8_t* out_rgb_u8, uint32_t* out_sig, mi_stats* stats) {
+                        uint8_t* out_rgb_u8, uint32_t* out_sig, mi_stats* stats, float* out_sh = nullptr) {
     int rc;
     const hipEvent_t t0 = c->ev_t0, t1 = c->ev_t1;      // owned by the context: no early return can leak them
     const TileGrid g = tile_grid(cam, 1);
@@ -1021,6 +1035,11 @@ static int render_image(mi_ctx* c, const mi_camera_desc* cam, const mi_render_op
         HIP_TRY(launch_sig_unpermute(c->d_sigc, c->d_sigi, cam->screen_width, cam->screen_height, g.tx, 1, g.padded, c->stream));
         HIP_TRY(hipMemcpyAsync(out_sig, c->d_sigi, npix * 4, hipMemcpyDeviceToHost, c->stream));
     }
+    if (out_sh) {
+        float* plane = table->sh + (size_t)g.padded * kTilePixels * kShFloats;
+        HIP_TRY(launch_sh_unpermute(table->sh, plane, cam->screen_width, cam->screen_height, g.tx, 1, g.padded, c->stream));
+        HIP_TRY(hipMemcpyAsync(out_sh, plane, npix * kShFloats * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    }
     HIP_TRY(hipEventRecord(t1, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     if (stats) {
@@ -1046,11 +1065,12 @@ extern "C" int mi_render(mi_ctx* c, const mi_camera_desc* cam, const mi_render_o
 // A table [rows][H][W][3] of origins and one of directions replaces Camera::generate_rays for one render; everything behind the camera
 // pass of the pipeline is mi_render's.  Every refusal happens here, before anything is allocated, copied or launched.
 static int check_table_args(mi_ctx* c, const mi_camera_desc* cam, const mi_render_opts* opts, const float* origins, const float* dirs,
-                            uint32_t rays_per_pixel, bool points = false) {
+                            uint32_t rays_per_pixel, TableKind kind = kTableRays) {
     if (!c) return fail(MI_ERR_INVALID, "ctx is NULL");
     if (!opts) return fail(MI_ERR_INVALID, "opts is NULL");
-    if (!origins || !dirs)
-        return fail(MI_ERR_INVALID, points ? "mi_render_points: the points and normals tables are required" : "mi_render_rays: the origins and dirs tables are required");
+    if (kind == kTableProbes ? !origins : (!origins || !dirs))        // a probe has no second table
+        return fail(MI_ERR_INVALID, kind == kTableProbes ? "mi_render_probes: the points table is required" :
+                    kind == kTablePoints ? "mi_render_points: the points and normals tables are required" : "mi_render_rays: the origins and dirs tables are required");
     MI_TRY(check_table_camera(cam, rays_per_pixel));
     if (opts->variant != MI_VARIANT_DEFAULT && opts->variant != MI_VARIANT_WAVEFRONT)
         return fail(MI_ERR_UNSUPPORTED, "ray-table rendering runs on the default (wavefront) variant only, not variant %d: use mi_shade_rays for the recursive estimator", opts->variant);
@@ -1061,29 +1081,36 @@ static int check_table_args(mi_ctx* c, const mi_camera_desc* cam, const mi_rende
     return MI_OK;
 }
 
-// Host pointers: upload the two tables into the context's own buffer, then mi_render's body.  `what` names the entry point in messages.
+// Host pointers: upload the two tables (light probes: the one) into the context's own buffer, then mi_render's body.  `what` names the
+// entry point in messages.  out_sh: light probes only, and required there.
 static int render_table_host(mi_ctx* c, const mi_camera_desc* cam, const mi_render_opts* opts, const float* first, const float* second,
-                             uint32_t rows, bool points, const char* what, float* out_rgb_f32, uint8_t* out_rgb_u8, uint32_t* out_sig,
-                             mi_stats* stats) {
-    MI_TRY(check_table_args(c, cam, opts, first, second, rows, points));
+                             uint32_t rows, TableKind kind, const char* what, float* out_rgb_f32, uint8_t* out_rgb_u8, uint32_t* out_sig,
+                             mi_stats* stats, float* out_sh = nullptr) {
+    MI_TRY(check_table_args(c, cam, opts, first, second, rows, kind));
     if (opts->rank != 0 || opts->world != 1) return fail(MI_ERR_INVALID, "%s renders a whole image: rank/world must be 0/1", what);
+    if (kind == kTableProbes && !out_sh) return fail(MI_ERR_INVALID, "%s: out_sh is required", what);
     HIP_TRY(hipSetDevice(c->device));
     const size_t bytes = (size_t)rows * cam->screen_height * cam->screen_width * 3 * sizeof(float);     // of each table
-    MI_TRY(ensure(&c->d_rays, &c->rays_bytes, 2 * bytes));
+    MI_TRY(ensure(&c->d_rays, &c->rays_bytes, (second ? 2 : 1) * bytes));
     HIP_TRY(hipMemcpyAsync(c->d_rays, first, bytes, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync((char*)c->d_rays + bytes, second, bytes, hipMemcpyHostToDevice, c->stream));
-    const RayTable table = { (const float*)c->d_rays, (const float*)((const char*)c->d_rays + bytes), rows, points };
+    if (second) HIP_TRY(hipMemcpyAsync((char*)c->d_rays + bytes, second, bytes, hipMemcpyHostToDevice, c->stream));
+    RayTable table = { (const float*)c->d_rays, second ? (const float*)((const char*)c->d_rays + bytes) : nullptr, rows, kind, nullptr };
+    if (out_sh) {           // the compact records, then the plane render_image un-permutes them into
+        const size_t slots = (size_t)tile_grid(cam, 1).padded * kTilePixels + (size_t)cam->screen_width * cam->screen_height;
+        MI_TRY(ensure(&c->d_sh, &c->sh_bytes, slots * kShFloats * sizeof(float)));
+        table.sh = (float*)c->d_sh;
+    }
     const mi_camera_desc tc = table_camera(cam);
-    return render_image(c, &tc, opts, &table, out_rgb_f32, out_rgb_u8, out_sig, stats);
+    return render_image(c, &tc, opts, &table, out_rgb_f32, out_rgb_u8, out_sig, stats, out_sh);
 }
 
-// Device pointers: mi_render_tiles_device and mi_render_samples_device in one call
+// Device pointers: mi_render_tiles_device and mi_render_samples_device in one call.  d_compact_sh: light probes only, may be NULL.
 static int render_table_device(mi_ctx* c, const mi_camera_desc* cam, const mi_render_opts* opts, const float* d_first, const float* d_second,
-                               uint32_t rows, bool points, uint32_t sample_begin, uint32_t sample_end, void* d_accum_f32x4,
-                               void* d_compact_f32, void* d_sig_u32, void* stream, mi_stats* stats) {
-    MI_TRY(check_table_args(c, cam, opts, d_first, d_second, rows, points));
+                               uint32_t rows, TableKind kind, uint32_t sample_begin, uint32_t sample_end, void* d_accum_f32x4,
+                               void* d_compact_f32, void* d_sig_u32, void* stream, mi_stats* stats, void* d_compact_sh = nullptr) {
+    MI_TRY(check_table_args(c, cam, opts, d_first, d_second, rows, kind));
     HIP_TRY(hipSetDevice(c->device));
-    const RayTable table = { d_first, d_second, rows, points };
+    const RayTable table = { d_first, d_second, rows, kind, (float*)d_compact_sh };
     const mi_camera_desc tc = table_camera(cam);
     // [0, aa_sample_count) without an accumulator is a whole render (mi_render_tiles_device); anything else a progressive call
     const bool whole = sample_begin == 0 && sample_end == cam->aa_sample_count && !d_accum_f32x4;
@@ -1093,13 +1120,13 @@ static int render_table_device(mi_ctx* c, const mi_camera_desc* cam, const mi_re
 
 extern "C" int mi_render_rays(mi_ctx* c, const mi_camera_desc* cam, const mi_render_opts* opts, const float* origins, const float* dirs,
                               uint32_t rays_per_pixel, float* out_rgb_f32, uint8_t* out_rgb_u8, uint32_t* out_sig, mi_stats* stats) {
-    return render_table_host(c, cam, opts, origins, dirs, rays_per_pixel, false, "mi_render_rays", out_rgb_f32, out_rgb_u8, out_sig, stats);
+    return render_table_host(c, cam, opts, origins, dirs, rays_per_pixel, kTableRays, "mi_render_rays", out_rgb_f32, out_rgb_u8, out_sig, stats);
 }
 
 extern "C" int mi_render_rays_device(mi_ctx* c, const mi_camera_desc* cam, const mi_render_opts* opts, const float* d_origins,
                                      const float* d_dirs, uint32_t rays_per_pixel, uint32_t sample_begin, uint32_t sample_end,
                                      void* d_accum_f32x4, void* d_compact_f32, void* d_sig_u32, void* stream, mi_stats* stats) {
-    return render_table_device(c, cam, opts, d_origins, d_dirs, rays_per_pixel, false, sample_begin, sample_end, d_accum_f32x4,
+    return render_table_device(c, cam, opts, d_origins, d_dirs, rays_per_pixel, kTableRays, sample_begin, sample_end, d_accum_f32x4,
                                d_compact_f32, d_sig_u32, stream, stats);
 }
 
@@ -1108,14 +1135,31 @@ extern "C" int mi_render_rays_device(mi_ctx* c, const mi_camera_desc* cam, const
 // stream of its own, so 24 B per texel cross the bus whatever the sample count.  Same checks, same upload buffer, same body.
 extern "C" int mi_render_points(mi_ctx* c, const mi_camera_desc* cam, const mi_render_opts* opts, const float* points, const float* normals,
                                 uint32_t rows_per_pixel, float* out_rgb_f32, uint8_t* out_rgb_u8, uint32_t* out_sig, mi_stats* stats) {
-    return render_table_host(c, cam, opts, points, normals, rows_per_pixel, true, "mi_render_points", out_rgb_f32, out_rgb_u8, out_sig, stats);
+    return render_table_host(c, cam, opts, points, normals, rows_per_pixel, kTablePoints, "mi_render_points", out_rgb_f32, out_rgb_u8, out_sig, stats);
 }
 
 extern "C" int mi_render_points_device(mi_ctx* c, const mi_camera_desc* cam, const mi_render_opts* opts, const float* d_points,
                                        const float* d_normals, uint32_t rows_per_pixel, uint32_t sample_begin, uint32_t sample_end,
                                        void* d_accum_f32x4, void* d_compact_f32, void* d_sig_u32, void* stream, mi_stats* stats) {
-    return render_table_device(c, cam, opts, d_points, d_normals, rows_per_pixel, true, sample_begin, sample_end, d_accum_f32x4,
+    return render_table_device(c, cam, opts, d_points, d_normals, rows_per_pixel, kTablePoints, sample_begin, sample_end, d_accum_f32x4,
                                d_compact_f32, d_sig_u32, stream, stats);
+}
+
+// ------------------------------------------------------------------ light probes (SH L2 radiance probes: the directions are drawn on the GPU)
+// mi_render_points without normals and with a second output: the camera pass draws a full-sphere direction per sample (the PROBES form of
+// wf_main) and wf_reduce_sh, behind wf_reduce in every batch, weights the same samples by the SH basis of their directions.  Same checks,
+// same upload buffer, same body; the plain outputs are the unchanged wf_reduce's.
+extern "C" int mi_render_probes(mi_ctx* c, const mi_camera_desc* cam, const mi_render_opts* opts, const float* points, uint32_t rows_per_pixel,
+                                float* out_sh, float* out_rgb_f32, uint8_t* out_rgb_u8, uint32_t* out_sig, mi_stats* stats) {
+    return render_table_host(c, cam, opts, points, nullptr, rows_per_pixel, kTableProbes, "mi_render_probes", out_rgb_f32, out_rgb_u8, out_sig,
+                             stats, out_sh);
+}
+
+extern "C" int mi_render_probes_device(mi_ctx* c, const mi_camera_desc* cam, const mi_render_opts* opts, const float* d_points,
+                                       uint32_t rows_per_pixel, uint32_t sample_begin, uint32_t sample_end, void* d_accum_f32x4,
+                                       void* d_compact_sh, void* d_compact_f32, void* d_sig_u32, void* stream, mi_stats* stats) {
+    return render_table_device(c, cam, opts, d_points, nullptr, rows_per_pixel, kTableProbes, sample_begin, sample_end, d_accum_f32x4,
+                               d_compact_f32, d_sig_u32, stream, stats, d_compact_sh);
 }
 
 // ------------------------------------------------------------------ multi-GPU behind the ABI

@@ -361,7 +361,14 @@ struct WfArgs {
     uint32_t pt_rows;
     const float* pt_p;
     const float* pt_n;
+    // Light probes (mi_render_probes): pt_probes != 0 makes pt_p a table of probe positions without normals (pt_n is nullptr): the camera
+    // pass draws a full-sphere direction, rand_sphere_vec on the direction stream above (the PROBES form of wf_main).  sh, or nullptr:
+    // [npix][9][3] running SH L2 sums in the compact tile-major layout, which wf_reduce_sh advances behind wf_reduce in every batch.
+    uint32_t pt_probes;
+    float* sh;
 };
+
+constexpr int kShFloats = 27;        // one probe's SH L2 record: 9 coefficients x 3 colour channels
 
 // How a render walks the meshes that take the reference's tree (scene_compile.cpp plan_walker -> pt_kernels.hip launch_walker).
 // The form values are those of MI_RT_WF_TRAV_LDS.

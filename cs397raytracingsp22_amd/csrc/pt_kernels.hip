@@ -20,6 +20,7 @@
 //   wf_filter_f / wf_trav_f / wf_replay   exact two-stage traversal of large meshes: root-box filter -> padded SAH tree of
 //                 16-byte quantised nodes + the reference's triangle test -> replay of the reference's walk over the candidates
 //   wf_reduce     per-pixel sums in sample order (tracing.rs:232-241)
+//   wf_reduce_sh  light probes only: per-probe SH L2 sums of the same samples in the same order, the directions drawn again
 // K1 (below) are the single-launch variants the pipeline grew out of; they remain selectable as structural cross-checks.
 //
 // Execution model of K1 (DESIGN.md "K1"):
@@ -2132,11 +2133,13 @@ __device__ __forceinline__ void wf_pixel_of(const WfArgs& A, uint32_t pix, uint3
 //   WF_RAYS    ray-table rendering — the lane takes (o, d) from the caller's table instead
 //   WF_POINTS  point-table rendering — the lane takes a surface point and a normal from the caller's table and draws the direction itself,
 //              sample_hemisphere(normal) on a stream of its own; a zero normal marks an empty texel
+//   WF_PROBES  light probes — the lane takes a position from the caller's table and draws a full-sphere direction, rand_sphere_vec, on
+//              that same stream of its own; there is no normal and no empty probe
 // TOP = true: the list's Triangles sit in a top-level tree (intersect_list<.., TOP>; scenes with long lists only)
-enum WfSrc { WF_STATE, WF_CAMERA, WF_RAYS, WF_POINTS };
+enum WfSrc { WF_STATE, WF_CAMERA, WF_RAYS, WF_POINTS, WF_PROBES };
 template <bool SIG, bool GV, int MESH, bool RARE, WfSrc SRC, bool TOP>
 __global__ __launch_bounds__(kBlock, (MESH == 2 ? PT_MAIN_WAVES : (MESH == 1 ? PT_MAIN_WAVES_NOTEX : PT_MAIN_WAVES_LEAN))) void wf_main(WfArgs A) {
-    constexpr bool ITER0 = SRC != WF_STATE, RAYS = SRC == WF_RAYS, POINTS = SRC == WF_POINTS;
+    constexpr bool ITER0 = SRC != WF_STATE, RAYS = SRC == WF_RAYS, POINTS = SRC == WF_POINTS, PROBES = SRC == WF_PROBES;
     const DScene& S = A.S;
     const DCamera& C = A.C;
     Bvh<false> B;          // only the mesh ROOT nodes are read here
@@ -2219,6 +2222,17 @@ __global__ __launch_bounds__(kBlock, (MESH == 2 ? PT_MAIN_WAVES : (MESH == 1 ? P
             // a wave of empty texels (and lanes outside the image) has written its slots and owns no path: it leaves before any scene data
             if (__builtin_amdgcn_ballot_w64(alive) == 0ull) return;
         }
+        if (PROBES && alive) {
+            // the caller's probe (row, y, x): the POINTS form's index, formed by no lane outside the image, and no address depends on the value.
+            // Isotropic::scatter's direction (materials.rs:158-166) on the POINTS form's direction stream: a point of the unit ball, not
+            // normalised (|d| <= 1), uniform in direction.  wf_reduce_sh draws it again for the SH weights: nothing is stored per sample.
+            const size_t r = (((size_t)(A.pt_rows == 1u ? 0u : sample) * C.height + py) * C.width + px) * 3;
+            const Ray3 tp = *(const Ray3*)(A.pt_p + r);
+            Rng tmp;
+            rng_init(tmp, A.seed_key, C.width * C.height + (py * C.width + px), sample);
+            P.o = mk3(tp.x, tp.y, tp.z);
+            P.d = rand_sphere_vec(tmp);
+        }
         if (alive) {
             rng_init(P.rng, A.seed_key, py * C.width + px, sample);             // the path's stream: mi_render_rays' for the ray (p, d)
             if (RAYS) {
@@ -2228,7 +2242,7 @@ __global__ __launch_bounds__(kBlock, (MESH == 2 ? PT_MAIN_WAVES : (MESH == 1 ? P
                 const size_t r = (((size_t)(A.rays_per_pixel == 1u ? 0u : sample) * C.height + py) * C.width + px) * 3;
                 const Ray3 ro = *(const Ray3*)(A.ray_o + r), rd = *(const Ray3*)(A.ray_d + r);
                 P.o = mk3(ro.x, ro.y, ro.z); P.d = mk3(rd.x, rd.y, rd.z);
-            } else if (!POINTS) generate_ray(C, px, py, sample, P.rng, P.o, P.d);       // POINTS: P.o, P.d were made above
+            } else if (!POINTS && !PROBES) generate_ray(C, px, py, sample, P.rng, P.o, P.d);       // POINTS, PROBES: P.o, P.d were made above
             if (C.path_depth == 0u) {                                     // tracing.rs:301 at level 0: the background, before any intersection
                 if (SIG) P.sig = sig_end_depth(P.sig);
                 A.samp[(size_t)(sample - A.s_base) * A.npix + pix] = make_float4(0.0f, 0.0f, 0.0f, __uint_as_float(P.sig));
@@ -3449,6 +3463,57 @@ __global__ __launch_bounds__(256) void wf_reduce(WfArgs A, uint32_t first_batch,
     }
 }
 
+// Light probes: the SH L2 projection of one batch of samples, behind wf_reduce.  One thread per probe (pixel): per sample of the batch in
+// order it draws the direction again (the PROBES form's calls on the same stream, so the same bits), normalises it, and adds L * Y_k to
+// the probe's 27 sums, which live in A.sh between batches and calls.  Every sum is one f32 chain in sample order from +0.0, scaled once
+// at the end: the record is bit-identical however the samples are cut into batches, calls and ranks.  Only reads the sample slots.
+// Real SH basis, order and constants of include/mi_rt.h.  dot(d, d) == 0 (one draw in 2^72) gives NaN weights for that sample.
+__global__ __launch_bounds__(256) void wf_reduce_sh(WfArgs A, uint32_t first_batch, uint32_t last_batch) {
+    const uint32_t pix = blockIdx.x * blockDim.x + threadIdx.x;
+    if (pix >= A.npix) return;
+    float* rec = A.sh + (size_t)pix * kShFloats;
+    uint32_t px, py; bool in_image;
+    wf_pixel_of(A, pix, px, py, in_image);
+    if (!in_image) {                       // outside the image, or a padding slot: zeros, whatever the buffer held
+        for (int k = 0; k < kShFloats; k++) rec[k] = 0.0f;
+        return;
+    }
+    float acc[kShFloats];
+    for (int k = 0; k < kShFloats; k++) acc[k] = first_batch ? 0.0f : rec[k];
+    const uint32_t key = A.C.width * A.C.height + (py * A.C.width + px);
+    for (uint32_t s = 0; s < A.s_count; s++) {
+        const float4 v = A.samp[(size_t)s * A.npix + pix];
+        Rng tmp;
+        rng_init(tmp, A.seed_key, key, A.s_base + s);
+        const f3 d = rand_sphere_vec(tmp);
+        const float inv = 1.0f / sqrtf(d.x * d.x + d.y * d.y + d.z * d.z);
+        const float x = d.x * inv, y = d.y * inv, z = d.z * inv;
+        const float Y[9] = { 0.28209479177387814f, 0.4886025119029199f * y, 0.4886025119029199f * z, 0.4886025119029199f * x,
+                             1.0925484305920792f * (x * y), 1.0925484305920792f * (y * z), 0.31539156525252005f * (3.0f * (z * z) - 1.0f),
+                             1.0925484305920792f * (x * z), 0.5462742152960396f * (x * x - y * y) };
+#pragma unroll
+        for (int k = 0; k < 9; k++) {
+            acc[3 * k] = acc[3 * k] + v.x * Y[k]; acc[3 * k + 1] = acc[3 * k + 1] + v.y * Y[k]; acc[3 * k + 2] = acc[3 * k + 2] + v.z * Y[k];
+        }
+    }
+    const float scale = last_batch ? 12.566370614359172f / (float)A.C.spp : 1.0f;      // 4 pi / S, once, behind the last sample
+#pragma unroll
+    for (int k = 0; k < kShFloats; k++) rec[k] = last_batch ? acc[k] * scale : acc[k];
+}
+
+// gathered[world][tiles_padded][1024][27] -> image[H][W][9][3]: fb_unpermute's mapping for the SH records.  One thread per float.
+__global__ __launch_bounds__(256) void sh_unpermute(const float* __restrict__ gathered, float* __restrict__ image,
+                                                    uint32_t width, uint32_t height, uint32_t tiles_x,
+                                                    uint32_t world, uint32_t tiles_padded) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (size_t)width * height * kShFloats) return;
+    const uint32_t idx = (uint32_t)(i / kShFloats), k = (uint32_t)(i % kShFloats);
+    uint32_t x = idx % width, y = idx / width;
+    uint32_t tile = (y / kTile) * tiles_x + (x / kTile);
+    uint32_t rank = tile % world, slot = tile / world;
+    image[i] = gathered[(((size_t)rank * tiles_padded + slot) * kTilePixels + (y % kTile) * kTile + (x % kTile)) * kShFloats + k];
+}
+
 // ---------------------------------------------------------------- K3: un-permute
 // gathered[world][tiles_padded][1024][3] -> image[H][W][3].  One thread per pixel.
 __global__ __launch_bounds__(256) void fb_unpermute(const float* __restrict__ gathered, float* __restrict__ image,
@@ -3593,10 +3658,11 @@ hipError_t launch_rq_shade(const RqShadeArgs& a, hipStream_t stream) {
 hipError_t launch_wf_main(const WfArgs& a, uint32_t n_blocks, bool sig, bool gv, bool tex, hipStream_t stream) {
 #define PT_WF_TOP(G, V, M, R, SRC) { (const void*)&wf_main<G, V, M, R, SRC, false>, (const void*)&wf_main<G, V, M, R, SRC, true> }
 #define PT_WF_FORMS(G, V, R) { PT_WF_TOP(G, V, 0, R, WF_STATE), PT_WF_TOP(G, V, 1, R, WF_STATE), PT_WF_TOP(G, V, 2, R, WF_STATE), \
-                               PT_WF_TOP(G, V, 0, R, WF_CAMERA), PT_WF_TOP(G, V, 0, R, WF_RAYS), PT_WF_TOP(G, V, 0, R, WF_POINTS) }
+                               PT_WF_TOP(G, V, 0, R, WF_CAMERA), PT_WF_TOP(G, V, 0, R, WF_RAYS), PT_WF_TOP(G, V, 0, R, WF_POINTS), \
+                               PT_WF_TOP(G, V, 0, R, WF_PROBES) }
 #define PT_WF_LISTS(G) { PT_WF_FORMS(G, false, false), PT_WF_FORMS(G, false, true), PT_WF_FORMS(G, true, true) }
-    // [sig][list kinds: plain / rare / rare + gv][form: state lean / notex / tex (= MESH), camera, ray table, point table][top]
-    static const void* const fn[2][3][6][2] = { PT_WF_LISTS(false), PT_WF_LISTS(true) };
+    // [sig][list kinds: plain / rare / rare + gv][form: state lean / notex / tex (= MESH), camera, ray table, point table, probes][top]
+    static const void* const fn[2][3][7][2] = { PT_WF_LISTS(false), PT_WF_LISTS(true) };
 #undef PT_WF_LISTS
 #undef PT_WF_FORMS
 #undef PT_WF_TOP
@@ -3606,9 +3672,9 @@ hipError_t launch_wf_main(const WfArgs& a, uint32_t n_blocks, bool sig, bool gv,
     const bool lean = a.iter0 != 0u || a.part == 1u || a.S.n_meshes == 0;
     const bool rare = a.S.n_list_plane + a.S.n_list_volume > 0;          // (gv implies rare: it is a kind of ConvexVolume)
     const bool top = a.S.top_meshf >= 0;                                  // the list's Triangles in a top-level tree (long lists)
-    // the camera pass of point-table rendering makes its rays from the caller's points and normals, that of ray-table rendering reads the
-    // caller's table; every later pass is the usual one
-    const int form = a.iter0 ? (a.pt_p ? 5 : a.ray_o ? 4 : 3) : lean ? 0 : tex ? 2 : 1;
+    // the camera pass of point-table rendering makes its rays from the caller's points and normals (a probe render: from the points alone),
+    // that of ray-table rendering reads the caller's table; every later pass is the usual one
+    const int form = a.iter0 ? (a.pt_p ? (a.pt_probes ? 6 : 5) : a.ray_o ? 4 : 3) : lean ? 0 : tex ? 2 : 1;
     return launch_form(fn[sig][!rare ? 0 : gv ? 2 : 1][form][top], a, n_blocks, 0, stream);
 }
 // The walker of the reference's tree that `p` names (scene_compile.cpp plan_walker).  big_lds_enabled: the calling context's record of
@@ -3663,6 +3729,19 @@ hipError_t launch_wf_prefix(uint32_t* out_count, uint32_t* trav_count, uint32_t*
 }
 hipError_t launch_wf_reduce(const WfArgs& a, bool first_batch, bool last_batch, hipStream_t stream) {
     hipLaunchKernelGGL(wf_reduce, dim3((a.npix + 255) / 256), dim3(256), 0, stream, a, first_batch ? 1u : 0u, last_batch ? 1u : 0u);
+    return hipGetLastError();
+}
+
+hipError_t launch_wf_reduce_sh(const WfArgs& a, bool first_batch, bool last_batch, hipStream_t stream) {
+    hipLaunchKernelGGL(wf_reduce_sh, dim3((a.npix + 255) / 256), dim3(256), 0, stream, a, first_batch ? 1u : 0u, last_batch ? 1u : 0u);
+    return hipGetLastError();
+}
+
+hipError_t launch_sh_unpermute(const float* gathered, float* image, uint32_t width, uint32_t height, uint32_t tiles_x,
+                               uint32_t world, uint32_t tiles_padded, hipStream_t stream) {
+    const size_t n = (size_t)width * height * kShFloats;
+    hipLaunchKernelGGL(sh_unpermute, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, stream, gathered, image, width, height,
+                       tiles_x, world, tiles_padded);
     return hipGetLastError();
 }
 

@@ -196,6 +196,27 @@ struct Scene : Intersectable {                         // tracing.rs:213-218; `i
         return img;
     }
 
+    // Light probes through mi_render_probes: points is [rows_per_pixel][H][W][3], one probe position per pixel, rows_per_pixel = 1 or
+    // camera.aa_sample_count.  Sample s of probe (x, y) leaves its point along rand_sphere_vec (Isotropic::scatter's direction,
+    // materials.rs:158-166: uniform over the sphere), drawn on the GPU from the stream (seed, W * H + y * W + x, s); its path draws from
+    // (seed, y * W + x, s).  Returns the SH L2 radiance coefficients [H][W][9][3] (the basis and its order: mi_rt.h); `image` takes the
+    // tone-mapped mean, `linear` the f32 mean.
+    std::vector<float> render_probes(const std::vector<float>& points, uint32_t rows_per_pixel, uint32_t seed = 1, int device = 0,
+                                     mi_stats* stats = nullptr, RgbImage* image = nullptr, std::vector<float>* linear = nullptr) const {
+        const size_t n = (size_t)camera.screen_height * camera.screen_width;
+        if (points.size() != n * rows_per_pixel * 3) throw std::runtime_error("mi_rt: points must be [rows_per_pixel][H][W][3]");
+        const mi_camera_desc cam = camera.flatten();
+        std::vector<float> sh(n * 27);
+        if (image) { image->width = camera.screen_width; image->height = camera.screen_height; image->data.resize(n * 3); }
+        if (linear) linear->resize(n * 3);
+        mi_render_opts opts{}; opts.seed = seed; opts.rank = 0; opts.world = 1;
+        with_context(device, [&](mi_ctx* ctx) {
+            return mi_render_probes(ctx, &cam, &opts, points.data(), rows_per_pixel, sh.data(), linear ? linear->data() : nullptr,
+                                    image ? image->data.data() : nullptr, nullptr, stats);
+        });
+        return sh;
+    }
+
 private:
     // flatten -> context -> upload -> `call(ctx)` -> destroy; a failure surfaces as std::runtime_error carrying mi_last_error()
     template <class F> void with_context(int device, F call) const {

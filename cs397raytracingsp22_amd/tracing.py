@@ -213,6 +213,66 @@ def check_point_table(cam: "Camera", points, normals):
     return _check_table(cam, points, normals, "point", "points", "normals", "rows")
 
 
+def check_probe_table(cam: "Camera", points):
+    """Input checking of light-probe rendering (mi_render_probes), no GPU needed: check_point_table for the one table a probe render
+    takes — probe positions, float32 of shape [S, H, W, 3] or [H, W, 3] (= one row), S = 1 or cam.aa_sample_count — and the camera fields
+    a table render reads.  The values are not looked at: every position is a probe, (0, 0, 0) included, and a non-finite one spoils its
+    own probe only.  Returns (points, rows_per_pixel) with points C-contiguous [S, H, W, 3]; raises ValueError."""
+    p, _, rows = _check_table(cam, points, points, "probe", "points", "points", "rows")
+    return p, rows
+
+
+SH9_Y0 = 0.28209479177387814        # the real SH basis of order <= 2 in mi_rt.h's order: Y_0; Y_1..3 = SH9_Y1 * (y, z, x);
+SH9_Y1 = 0.4886025119029199         # Y_4, 5, 7 = SH9_Y2 * (xy, yz, xz); Y_6 = SH9_Y20 * (3 z^2 - 1); Y_8 = SH9_Y22 * (x^2 - y^2)
+SH9_Y2 = 1.0925484305920792
+SH9_Y20 = 0.31539156525252005
+SH9_Y22 = 0.5462742152960396
+SH9_COSINE = np.array([np.pi] + [2.0 * np.pi / 3.0] * 3 + [np.pi / 4.0] * 5)      # A_l per coefficient: the clamped-cosine lobe's zonal factors
+
+
+def sh9_basis(dirs) -> np.ndarray:
+    """The nine real spherical harmonics of order <= 2 at directions `dirs` [..., 3] (any length: normalised here, in float64), in the
+    order and with the constants of mi_render_probes: [..., 9] float64.  Orthonormal over the sphere."""
+    d = np.asarray(dirs, np.float64)
+    d = d / np.sqrt((d * d).sum(axis=-1, keepdims=True))
+    x, y, z = d[..., 0], d[..., 1], d[..., 2]
+    return np.stack([np.full_like(x, SH9_Y0), SH9_Y1 * y, SH9_Y1 * z, SH9_Y1 * x, SH9_Y2 * x * y, SH9_Y2 * y * z,
+                     SH9_Y20 * (3.0 * z * z - 1.0), SH9_Y2 * x * z, SH9_Y22 * (x * x - y * y)], axis=-1)
+
+
+def sh9_irradiance(sh, normal) -> np.ndarray:
+    """Irradiance E(n) = sum_k A_l(k) c_k Y_k(n) from SH L2 radiance coefficients `sh` [..., 9, C] (render_probes' first result) for a
+    normal [3] or one normal per probe [..., 3]: [..., C] float64.  A_0 = pi, A_1 = 2 pi / 3, A_2 = pi / 4 (Ramamoorthi & Hanrahan 2001):
+    constant radiance L gives pi L.  Divide by pi and multiply by the albedo for a Lambertian surface's outgoing radiance."""
+    w = sh9_basis(normal) * SH9_COSINE                                  # [..., 9]
+    return (np.asarray(sh, np.float64) * w[..., None]).sum(axis=-2)
+
+
+def probe_grid(lo, hi, counts, width: Optional[int] = None):
+    """A regular grid of light probes inside the box [lo, hi] as a probe table: (points [H, W, 3] float32, n).  counts = (nx, ny, nz);
+    probe (i, j, k) sits at the centre of its cell, lo + (i + 0.5, j + 0.5, k + 0.5) / counts * (hi - lo), and has the number
+    (k * ny + j) * nx + i (x runs fastest).  The n = nx ny nz probes fill the table row-major: W = `width`, or, when width is None, the
+    multiple of 32 next above sqrt(n) (the renderer works in 32 x 32 tiles: a squarish table wastes the fewest lanes, a single row 31 of
+    every 32); H = ceil(n / W).  The H W - n padding slots repeat the last probe, so every slot is a finite position; only the first n
+    results (reshape(-1, ...)[:n]) mean anything."""
+    lo, hi = np.asarray(lo, np.float64).reshape(3), np.asarray(hi, np.float64).reshape(3)
+    nx, ny, nz = (int(c) for c in counts)
+    if min(nx, ny, nz) < 1:
+        raise ValueError(f"counts must all be >= 1, got {(nx, ny, nz)}")
+    n = nx * ny * nz
+    W = min(32768, 32 * int(np.ceil(np.sqrt(n) / 32.0))) if width is None else int(width)
+    if not 1 <= W <= 32768:
+        raise ValueError(f"width must be in 1..32768, got {W}")
+    H = (n + W - 1) // W
+    if H > 32768:
+        raise ValueError(f"{n} probes do not fit {W} columns x 32768 rows")
+    ax = [lo[a] + (np.arange(c) + 0.5) / c * (hi[a] - lo[a]) for a, c in enumerate((nx, ny, nz))]
+    z, y, x = np.meshgrid(ax[2], ax[1], ax[0], indexing="ij")
+    pts = np.stack([x, y, z], axis=-1).reshape(n, 3)
+    pts = np.concatenate([pts, np.repeat(pts[-1:], H * W - n, axis=0)])
+    return np.ascontiguousarray(pts.reshape(H, W, 3), np.float32), n
+
+
 def lightmap_texels(positions, normals, texcoords, indices, width: int, height: int, transform=None, offset: float = 0.0):
     """The point table of a mesh's lightmap, on the host (numpy only): (points [H, W, 3] f32, normals [H, W, 3] f32, covered [H, W] bool)
     for render_points.  `positions`, `normals` [V, 3], `texcoords` [V, 2] and `indices` [T, 3] are a single-index triangle mesh
@@ -396,7 +456,48 @@ class Context:
         p, n, rows = check_point_table(cam, points, normals)
         return self._render_table(self._lib.mi_render_points, cam, p, n, rows, seed, want_f32, want_u8, want_sig, flags, max_state_bytes)
 
+    def render_probes(self, cam: Camera, points, seed: int = 1, want_f32=True, want_u8=True, want_sig=False,
+                      flags: int = 0, max_state_bytes: int = 0):
+        """mi_render_probes: light probes.  `points` (check_probe_table: [S, H, W, 3] or [H, W, 3] float32, S = 1 or aa_sample_count)
+        holds one probe position per pixel; sample s of probe (x, y) leaves it along rand_sphere_vec from the stream
+        (seed, W*H + y*W + x, s) — uniform over the whole sphere — and its path draws from (seed, y*W + x, s).  Returns
+        (sh, f32, u8, sig, stats): sh [H, W, 9, 3] float32, the SH L2 radiance coefficients per colour channel (sh9_irradiance turns
+        them into irradiance), then what render returns (the mean over the samples)."""
+        p, rows = check_probe_table(cam, points)
+        pod = cam.to_pod()
+        opts = abi.mi_render_opts(seed=seed, rank=0, world=1, variant=abi.MI_VARIANT_DEFAULT, want_signature=int(want_sig),
+                                  flags=flags, max_state_bytes=max_state_bytes)
+        H, W = cam.screen_height, cam.screen_width
+        sh = np.empty((H, W, 9, 3), np.float32)
+        f32 = np.empty((H, W, 3), np.float32) if want_f32 else None
+        u8 = np.empty((H, W, 3), np.uint8) if want_u8 else None
+        sig = np.empty((H, W), np.uint32) if want_sig else None
+        st = abi.mi_stats()
+        abi.check(self._lib.mi_render_probes(
+            self._h, C.byref(pod), C.byref(opts), p.ctypes.data, rows, sh.ctypes.data,
+            f32.ctypes.data if f32 is not None else None,
+            u8.ctypes.data if u8 is not None else None,
+            sig.ctypes.data if sig is not None else None, C.byref(st)))
+        return sh, f32, u8, sig, st
+
     # ---- device-pointer building blocks (multi-GPU; pointers are ints, e.g. tensor.data_ptr()) ----
+    def render_probes_device(self, cam: Camera, d_points: int, rows_per_pixel: int, d_compact_sh: Optional[int] = None,
+                             d_compact: Optional[int] = None, d_sig: Optional[int] = None, sample_begin: int = 0,
+                             sample_end: Optional[int] = None, d_accum: Optional[int] = None, seed: int = 1, rank: int = 0, world: int = 1,
+                             stream: Optional[int] = None, flags: int = 0, max_state_bytes: int = 0):
+        """mi_render_probes_device: render_points_device for a probe table held on the device (raw pointer, [rows_per_pixel, H, W, 3]
+        float32); the same sample-range, accumulator and rank / world rules.  d_compact_sh, [compact_size(...)[1] * 1024, 9, 3] float32,
+        is the SH output and its running accumulator across progressive calls (started by the call with sample_begin == 0, scaled by the
+        one that reaches aa_sample_count); None gives the plain outputs only."""
+        pod = cam.to_pod()
+        opts = abi.mi_render_opts(seed=seed, rank=rank, world=world, variant=abi.MI_VARIANT_DEFAULT,
+                                  want_signature=int(d_sig is not None), flags=flags, max_state_bytes=max_state_bytes)
+        st = abi.mi_stats()
+        end = cam.aa_sample_count if sample_end is None else sample_end
+        abi.check(self._lib.mi_render_probes_device(self._h, C.byref(pod), C.byref(opts), d_points, rows_per_pixel,
+                                                    sample_begin, end, d_accum, d_compact_sh, d_compact, d_sig, stream, C.byref(st)))
+        return st
+
     def render_points_device(self, cam: Camera, d_points: int, d_normals: int, rows_per_pixel: int, d_compact: Optional[int] = None,
                              d_sig: Optional[int] = None, sample_begin: int = 0, sample_end: Optional[int] = None,
                              d_accum: Optional[int] = None, seed: int = 1, rank: int = 0, world: int = 1, stream: Optional[int] = None,
@@ -473,6 +574,13 @@ class Context:
         abi.check(self._lib.mi_last_pipeline_ms(self._h, out))
         return {"wf_main_ms": float(out[0]), "wf_trav_ms": float(out[1]), "wf_reduce_ms": float(out[2]), "launches": int(out[3]),
                 "wf_trav_f_ms": float(out[4]), "wf_replay_ms": float(out[5]), "wf_main_a_ms": float(out[6])}
+
+    def last_reduce_sh_ms(self) -> float:
+        """Sum of the wf_reduce_sh launch durations (ms) of the last render: entry 7 of mi_last_pipeline_ms, the SH reduction of
+        render_probes / render_probes_device; 0.0 after any other render."""
+        out = (C.c_float * 8)()
+        abi.check(self._lib.mi_last_pipeline_ms(self._h, out))
+        return float(out[7])
 
     def last_pipeline_counts(self):
         """Path counts of the last wavefront render (mi_last_pipeline_counts), for traffic accounting."""
@@ -763,6 +871,19 @@ class Scene:                         # tracing.rs:213-218
             ctx.upload(self.flatten())
             _, u8, _, _ = ctx.render_points(self.camera, p, n, seed=seed, want_f32=False, want_u8=True)
             return u8
+        finally:
+            ctx.close()
+
+    def render_probes(self, points, seed: int = 1, device: int = 0):
+        """Light probes (mi_render_probes): the radiance arriving at a table of points in free space (probe_grid makes one), projected
+        onto the SH L2 basis — per probe aa_sample_count directions uniform over the sphere, drawn on the GPU, each shaded by
+        Scene::shade_ray.  This scene's camera supplies the table's size (screen_width x screen_height probes), aa_sample_count,
+        path_depth, max_trace_dist and gamma.  Returns (sh [H, W, 9, 3] f32, mean [H, W, 3] f32, u8 [H, W, 3], sig [H, W] u32, stats)."""
+        p, _ = check_probe_table(self.camera, points)
+        ctx = Context(device)
+        try:
+            ctx.upload(self.flatten())
+            return ctx.render_probes(self.camera, p, seed=seed, want_sig=True)
         finally:
             ctx.close()
 

@@ -458,6 +458,48 @@ int  mi_render_points_device(mi_ctx* ctx, const mi_camera_desc* cam, const mi_re
                              uint32_t sample_begin, uint32_t sample_end, void* d_accum_f32x4,
                              void* d_compact_f32, void* d_sig_u32, void* stream, mi_stats* stats);
 
+/* ---- light probes: SH L2 radiance probes with the directions drawn on the GPU (added within ABI version 5: detect by symbol lookup) ----
+ * mi_render_points without normals and with a second output.  One "pixel" is one probe, a point in free space; its samples leave it in
+ *   directions uniform over the whole sphere, and beside their mean the call returns the radiance field's projection onto the nine real
+ *   spherical harmonics of order <= 2 per colour channel, from which the irradiance for any normal is a dot product (sh9_irradiance in
+ *   Python).  A caller with n probes uses W = n, H = 1, or any grid that holds them.
+ * Layout: `points` is [rows_per_pixel][H][W][3] f32, W x H = cam->screen_width x screen_height, probe (row, y, x) at ((row*H + y)*W + x)*3
+ *   (indexed in 64 bits); rows_per_pixel is 1 or aa_sample_count, as for the point table.
+ * Two streams per sample s of probe (x, y), the point table's keys:
+ *   direction: (seed, W*H + y*W + x, s), fresh: d = rand_sphere_vec(), what Isotropic::scatter (materials.rs:158-166) returns on that
+ *     stream.  d is NOT normalised (|d| <= 1); rejection from the cube makes its direction uniform on the sphere, pdf 1 / (4 pi).
+ *   path: (seed, y*W + x, s), fresh: L_s = Scene::shade_ray(Ray(p, d), 0), t_min = 0.001 and t_max = cam->max_trace_dist in units of |d|.
+ *   Hence mi_render_probes(points) has the mean image of mi_render_rays(points, d) for the table d of those directions, bit for bit.
+ * Plain outputs: the mean (f32), u8 and signature outputs of mi_render_points, made by the same reduction.
+ * SH output: out_sh is [H][W][9][3] f32, c_k = (4 pi / S) * sum_s L_s * Y_k(u_s), u_s = d_s / |d_s|, S = aa_sample_count, with the real
+ *   basis in this order (constants rounded to f32):
+ *     Y_0 = 0.28209479177387814          Y_1 = 0.4886025119029199 y       Y_2 = 0.4886025119029199 z      Y_3 = 0.4886025119029199 x
+ *     Y_4 = 1.0925484305920792 x y       Y_5 = 1.0925484305920792 y z     Y_6 = 0.31539156525252005 (3 z^2 - 1)
+ *     Y_7 = 1.0925484305920792 x z       Y_8 = 0.5462742152960396 (x^2 - y^2)
+ *   Each of the 27 sums is accumulated in f32 in sample order from +0.0 (one multiply and one add per sample, not fused), and scaled
+ *   once at the end by 12.566370614359172f / (float)S: out_sh is bit-identical across max_state_bytes, ranks, MI_OPT_* flags and
+ *   progressive splits.
+ * No empty-probe marker: a probe has no normal, and (0, 0, 0) is a legitimate position.  A non-finite point gives unspecified values
+ *   for that probe only; it never faults and changes no other probe's bits (no address depends on a table value).  A d with
+ *   dot(d, d) == 0 (all three draws exactly 0) has no direction: that sample's contribution to the 27 sums is unspecified (NaN).
+ * Everything else is mi_render_points', word for word: the camera fields read and ignored, the refusals (NULL table, rows_per_pixel,
+ *   path_samples != 1, MI_SHADE_PHONG, a variant other than DEFAULT / WAVEFRONT, no scene, rank / world), masks OFF (entry 7 of
+ *   mi_last_pipeline_counts is 0), mi_reserve, max_state_bytes, stats->samples = W*H*aa_sample_count.  Entry 7 of mi_last_pipeline_ms
+ *   is the time of the SH reduction (wf_reduce_sh), which runs behind wf_reduce in every batch.
+ * mi_render_probes: HOST pointers, blocking, rank / world 0 / 1; out_sh is required (MI_ERR_INVALID if NULL), the other outputs may be NULL.
+ * mi_render_probes_device: DEVICE pointers; the sample range, the accumulator and the rank / world rules are mi_render_rays_device's.
+ *   d_compact_sh is [tiles_padded][1024][27] f32 in the compact tile-major layout ([9][3] per slot), output AND running accumulator: the
+ *   call with sample_begin == 0 starts the sums from zero (the buffer need not be cleared), later calls add to it, the call that ends at
+ *   aa_sample_count applies the scale; it may be copied out and back between calls.  Slots outside the image and padding slots are
+ *   written as zeros.  d_compact_sh == NULL is legal and gives the plain outputs only.  mi_multi_* takes no table. */
+int  mi_render_probes(mi_ctx* ctx, const mi_camera_desc* cam, const mi_render_opts* opts,
+                      const float* points, uint32_t rows_per_pixel, float* out_sh,
+                      float* out_rgb_f32, uint8_t* out_rgb_u8, uint32_t* out_sig, mi_stats* stats);
+int  mi_render_probes_device(mi_ctx* ctx, const mi_camera_desc* cam, const mi_render_opts* opts,
+                             const float* d_points, uint32_t rows_per_pixel,
+                             uint32_t sample_begin, uint32_t sample_end, void* d_accum_f32x4, void* d_compact_sh,
+                             void* d_compact_f32, void* d_sig_u32, void* stream, mi_stats* stats);
+
 /* Size and allocate the wavefront pipeline's HBM buffers (path state, sample slots) for
  * this camera with the image shared by `world` ranks, so that the first render does not pay the
  * allocation (about 110 GB for a whole 1080p / 256 spp frame on one GPU).  `max_state_bytes` as in
@@ -466,7 +508,8 @@ int  mi_reserve(mi_ctx* ctx, const mi_camera_desc* cam, int32_t world, uint64_t 
 
 /* Wavefront pipeline (MI_VARIANT_WAVEFRONT) of the most recent render: out8 = { sum of wf_main
  * launch durations, of wf_trav, of wf_reduce (ms, HIP events around every launch), launches, sum of wf_trav_f, of
- * wf_replay (the two-stage mesh traversal), sum of the spans of wf_main's class-A parts, 0 }.  A pass after the first launches
+ * wf_replay (the two-stage mesh traversal), sum of the spans of wf_main's class-A parts, sum of wf_reduce_sh (mi_render_probes only;
+ * 0 for every other render) }.  A pass after the first launches
  * wf_main in two parts: the class-A blocks run on a second stream BESIDE the walkers of the previous pass (their span includes
  * waiting for CUs the walkers still hold, so it overlaps the wf_trav figure and must not be added to it), the class-B blocks
  * behind the walkers (counted under wf_main). */

@@ -107,6 +107,14 @@ extern "C" {
                                    d_points: *const f32, d_normals: *const f32, rows_per_pixel: u32,
                                    sample_begin: u32, sample_end: u32, d_accum_f32x4: *mut c_void,
                                    d_compact_f32: *mut c_void, d_sig_u32: *mut c_void, stream: *mut c_void, stats: *mut mi_stats) -> c_int;
+    // light probes (added within ABI 5): points is [rows_per_pixel][H][W][3]; out_sh [H][W][9][3], d_compact_sh [tiles_padded][1024][27]
+    pub fn mi_render_probes(ctx: *mut mi_ctx, cam: *const mi_camera_desc, opts: *const mi_render_opts,
+                            points: *const f32, rows_per_pixel: u32, out_sh: *mut f32,
+                            out_rgb_f32: *mut f32, out_rgb_u8: *mut u8, out_sig: *mut u32, stats: *mut mi_stats) -> c_int;
+    pub fn mi_render_probes_device(ctx: *mut mi_ctx, cam: *const mi_camera_desc, opts: *const mi_render_opts,
+                                   d_points: *const f32, rows_per_pixel: u32,
+                                   sample_begin: u32, sample_end: u32, d_accum_f32x4: *mut c_void, d_compact_sh: *mut c_void,
+                                   d_compact_f32: *mut c_void, d_sig_u32: *mut c_void, stream: *mut c_void, stats: *mut mi_stats) -> c_int;
     pub fn mi_reserve(ctx: *mut mi_ctx, cam: *const mi_camera_desc, world: i32, max_state_bytes: u64) -> c_int;
     pub fn mi_last_pipeline_ms(ctx: *mut mi_ctx, out8: *mut f32) -> c_int;
     pub fn mi_last_pipeline_counts(ctx: *mut mi_ctx, out8: *mut u64) -> c_int;

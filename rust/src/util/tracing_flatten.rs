@@ -194,6 +194,24 @@ impl Scene {
         img
     }
 
+    /// Light probes (mi_render_probes): `points` holds `rows_per_pixel` x height x width probe positions, row-major ([row][y][x]),
+    /// rows_per_pixel = 1 or camera.aa_sample_count.  Sample s of probe (x, y) leaves its point along rand_sphere_vec (what
+    /// Isotropic::scatter returns: uniform over the sphere), drawn on the GPU from the stream (seed, width * height + y * width + x, s),
+    /// and its path draws from (seed, y * width + x, s).  Returns the SH L2 radiance coefficients, height x width records of
+    /// [coefficient 0..9][channel r, g, b], in the basis order of mi_rt.h.
+    pub fn render_probes(&self, points: &[[f32; 3]], rows_per_pixel: u32, seed: u32) -> Vec<[[f32; 3]; 9]> {
+        let n = self.camera.screen_height as usize * self.camera.screen_width as usize;
+        assert_eq!(points.len(), rows_per_pixel as usize * n, "mi_rt: the points table must hold rows_per_pixel * height * width probes");
+        let cam = self.camera.flatten();
+        let opts = mi_rt::mi_render_opts { seed: seed, rank: 0, world: 1, ..Default::default() };
+        let mut sh = vec![[[0.0f32; 3]; 9]; n];
+        let (pp, psh) = (points.as_ptr() as *const f32, sh.as_mut_ptr() as *mut f32);
+        self.with_gpu_scene(|ctx| unsafe {
+            mi_rt::mi_render_probes(ctx, &cam, &opts, pp, rows_per_pixel, psh, std::ptr::null_mut(), std::ptr::null_mut(), std::ptr::null_mut(), std::ptr::null_mut())
+        });
+        sh
+    }
+
     /// flatten -> context on device 0 -> upload -> `call` -> destroy; panics with the library's message on failure.
     fn with_gpu_scene<F: FnOnce(*mut mi_rt::mi_ctx) -> i32>(&self, call: F) {
         let sb = self.flatten_scene();

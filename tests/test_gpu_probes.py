@@ -1,0 +1,477 @@
+"""Light probes (mi_render_probes / mi_render_probes_device): SH L2 radiance probes with the directions drawn on the GPU, against the oracle.
+
+Probe positions are the points of tests/test_gpu_point_table.py::point_table (its empty texels hold (0, 0, 0), a legitimate probe).  The
+oracle's side of sample s of probe (x, y), call by call and cached per scene:
+    d = orc.scatter(Isotropic, p, any normal, 1, any dir, seed, W*H + y*W + x, s)[0]        (rand_sphere_vec, materials.rs:158-166)
+    L = orc_shade(p, d, seed, y*W + x, s)
+The mean is their f32 sum in sample order / n in f32 (bars of tests/test_gpu_parity.py); the SH reference is the float64 projection
+ref_k,c = (4 pi / S) sum_s L_s,c Y_k(d_s / |d_s|) of the oracle's f32 L_s and d_s, with the bar
+    |gpu - ref| <= 2e-5 * max(1, (4 pi / S) sum_s |L_s,c| |Y_k(u_s)|)
+the project's parity bar scaled by the sum's absolute mass (cancellation between samples is what an SH coefficient is).  c_0 must also
+equal mean * 4 pi * Y_0 within 4 ulp-equivalents (4 * 2^-23) of that same scale: two roundings of the same sum.  Images are 75 x 41
+(ragged in both tile directions)."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+from cs397raytracingsp22_amd import (Camera, Context, Isotropic, Lambertian, Scene, Sphere, abi, dist as pdist, probe_grid, scenes, sh9_basis,
+                                     sh9_irradiance)
+from cs397raytracingsp22_amd.tracing import ShadingMode
+
+from test_gpu_point_table import point_table
+from test_gpu_ray_table import H, SCENES, SEED, W, assert_within_bars, bits, same
+
+pytestmark = pytest.mark.gpu
+
+ISO = Isotropic(albedo=(1.0, 1.0, 1.0), emission=(0.0, 0.0, 0.0))
+ANY_N, ANY_DIR = (0.0, 1.0, 0.0), (0.0, 0.0, -1.0)          # Isotropic::scatter reads neither the normal nor the incoming ray
+FOUR_PI = 4.0 * np.pi
+Y0 = 0.28209479177387814
+_cache = {}
+
+
+def oracle_samples(orc, sc, p, seed=SEED):
+    """(d, L) [aa, h, w, 3] f32 each: the oracle's direction and radiance of every sample of every probe of the table p [rows, h, w, 3]"""
+    cam = sc.camera
+    aa, h, w = cam.aa_sample_count, cam.screen_height, cam.screen_width
+    p = p if p.ndim == 4 else p[None]
+    assert p.shape[1:] == (h, w, 3)
+    lib, osc, pod = orc.load(), orc.OracleScene(sc.flatten()), cam.to_pod()
+    fp = C.POINTER(C.c_float)
+    d = np.zeros((aa, h, w, 3), np.float32)
+    L = np.zeros((aa, h, w, 3), np.float32)
+    for s in range(aa):
+        row = s if p.shape[0] > 1 else 0
+        for y in range(h):
+            for x in range(w):
+                d[s, y, x] = orc.scatter(ISO, p[row, y, x], ANY_N, 1, ANY_DIR, seed, w * h + y * w + x, s)[0]
+                rc = lib.orc_shade(osc._h, C.byref(pod), C.cast(p[row, y, x].ctypes.data, fp), C.cast(d[s, y, x].ctypes.data, fp),
+                                   seed, y * w + x, s, C.cast(L[s, y, x].ctypes.data, fp))
+                assert rc == 0
+    osc.close()
+    return d, L
+
+
+def project(d, L):
+    """(ref, mass) [h, w, 9, 3] float64: the SH projection of the samples and its absolute mass"""
+    S = d.shape[0]
+    Y = sh9_basis(d.astype(np.float64))                                             # [S, h, w, 9], normalises d
+    L64 = L.astype(np.float64)
+    ref = (FOUR_PI / S) * (Y[..., :, None] * L64[..., None, :]).sum(axis=0)
+    mass = (FOUR_PI / S) * (np.abs(Y)[..., :, None] * np.abs(L64)[..., None, :]).sum(axis=0)
+    return ref, mass
+
+
+def sh_ratio(sh, ref, mass):
+    """max over coefficients and channels of |gpu - ref| / max(1, mass): the bar is 2e-5"""
+    assert np.isfinite(ref).all() and np.isfinite(sh).all()
+    return float((np.abs(sh.astype(np.float64) - ref) / np.maximum(1.0, mass)).max())
+
+
+def reference(orc, name):
+    """The oracle's side for scene `name` with the one-row point table as probes: dict of d, L, mean f32, u8, SH ref and mass; cached"""
+    key = ("ref", name)
+    if key not in _cache:
+        sc = SCENES[name][0]()
+        p = point_table(orc, name, 1)[0]
+        d, L = oracle_samples(orc, sc, p)
+        aa = sc.camera.aa_sample_count
+        acc = np.zeros((H, W, 3), np.float32)
+        for s in range(aa):
+            acc = acc + L[s]                                    # final_color += shade_ray(..)  tracing.rs:238
+        r32 = acc / np.float32(aa)                              # :241
+        r8 = np.stack([orc.tonemap_pixel(px, sc.camera.gamma) for px in r32.reshape(-1, 3)]).reshape(H, W, 3)
+        ref, mass = project(d, L)
+        for a in (d, L, r32, r8, ref, mass):
+            a.setflags(write=False)
+        _cache[key] = dict(d=d, L=L, r32=r32, r8=r8, ref=ref, mass=mass)
+    return _cache[key]
+
+
+# ---------------------------------------------------------------- 1. the mean against the oracle
+@pytest.mark.parametrize("name", list(SCENES))
+def test_mean_against_the_oracle(gpu_ctx, orc, name):
+    sc = SCENES[name][0]()
+    aa = sc.camera.aa_sample_count
+    gpu_ctx.upload(sc.flatten())
+    p = point_table(orc, name, 1)[0]
+    r = reference(orc, name)
+    lit = int((r["r32"].sum(axis=-1) > 0).sum())
+    print(f"{name}: {lit} probes with a non-zero reference mean")
+    assert lit >= 100                                                              # the oracle's side alone: the case is not vacuous
+    assert (np.abs(r["d"]).max(axis=-1) > 0).all() and ((r["d"].astype(np.float64) ** 2).sum(axis=-1) <= 1.0 + 1e-6).all()
+    sh, f32, u8, sig, st = gpu_ctx.render_probes(sc.camera, p, seed=SEED, want_sig=True)
+    assert st.samples == W * H * aa and sh.shape == (H, W, 9, 3)
+    assert gpu_ctx.last_pipeline_counts()["dead_tile_samples"] == 0
+    sh2, g32, g8, none, _ = gpu_ctx.render_probes(sc.camera, p, seed=SEED, want_sig=False)
+    assert none is None and gpu_ctx.last_pipeline_counts()["dead_tile_samples"] == 0
+    assert same((sh, f32, u8), (sh2, g32, g8))                                     # signatures on / off: the same outputs, bit for bit
+    assert_within_bars(f32, u8, r["r32"], r["r8"], name)
+
+
+# ---------------------------------------------------------------- 2. equals a ray-table render of the same rays
+@pytest.mark.parametrize("name", list(SCENES))
+def test_equals_a_ray_table_render(gpu_ctx, orc, name):
+    """render_probes(P) against render_rays(P, D), D the oracle's directions: the same path stream and the same f32 operations, so the
+    plain outputs agree to the bit exactly when the kernel's direction has the oracle's bits."""
+    sc = SCENES[name][0]()
+    aa = sc.camera.aa_sample_count
+    gpu_ctx.upload(sc.flatten())
+    p = point_table(orc, name, 1)[0]
+    d = reference(orc, name)["d"]
+    probes = gpu_ctx.render_probes(sc.camera, p, seed=SEED, want_sig=True)[1:4]
+    o = np.ascontiguousarray(np.broadcast_to(p, (aa, H, W, 3)))
+    rays = gpu_ctx.render_rays(sc.camera, o, d, seed=SEED, want_sig=True)[:3]
+    diff32 = int((bits(probes[0]) != bits(rays[0])).any(axis=-1).sum())
+    diff8 = int((probes[1] != rays[1]).any(axis=-1).sum())
+    diffsig = int((probes[2] != rays[2]).sum())
+    print(f"{name}: {diff32} of {W * H} probes differ in f32 bits, {diff8} in bytes, {diffsig} in signature")
+    assert diff32 == 0 and diff8 == 0 and diffsig == 0
+
+
+# ---------------------------------------------------------------- 3. the SH against an f64 projection of the oracle's samples
+@pytest.mark.parametrize("name", list(SCENES))
+def test_sh_against_the_f64_projection(gpu_ctx, orc, name):
+    sc = SCENES[name][0]()
+    gpu_ctx.upload(sc.flatten())
+    p = point_table(orc, name, 1)[0]
+    r = reference(orc, name)
+    sh, f32, _, _, _ = gpu_ctx.render_probes(sc.camera, p, seed=SEED)
+    ratio = sh_ratio(sh, r["ref"], r["mass"])
+    # c_0 and the mean are two roundings of the same sum
+    c0 = np.abs(sh[:, :, 0, :].astype(np.float64) - f32.astype(np.float64) * (FOUR_PI * Y0)) / np.maximum(1.0, r["mass"][:, :, 0, :])
+    print(f"{name}: max |sh - ref| / max(1, mass) = {ratio:.3e} (bar 2e-5); max |c_0 - mean 4 pi Y_0| / max(1, mass) = "
+          f"{float(c0.max()) * 2 ** 23:.2f} ulp (bar 4); largest |coefficient| {float(np.abs(r['ref']).max()):.3f}")
+    assert float(np.abs(r["ref"][:, :, 1:, :]).max()) > 0.1                        # directional content, not only the L0 term
+    assert ratio <= 2e-5
+    assert float(c0.max()) <= 4 * 2.0 ** -23
+
+
+# ---------------------------------------------------------------- 4. furnace
+def test_furnace(gpu_ctx, orc):
+    """Inside one emissive sphere every sample's radiance is the emission, so c_0 = sqrt(4 pi) * emission whatever the directions: an
+    anchor that does not pass through this file's projection code."""
+    E = np.float32([1.0, 2.0, 3.0])
+    cam = Camera(screen_width=4, screen_height=1, aa_sample_count=64, path_depth=1, max_trace_dist=100.0, gamma=2.0)
+    sc = Scene(cam, [Sphere((0.0, 0.0, 0.0), 10.0, Lambertian(albedo=(0.5, 0.5, 0.5), emission=tuple(float(e) for e in E)))])
+    p = np.float32([[(0, 0, 0), (3, 0, 0), (0, -6, 2), (-4, 5, -7)]])             # the centre and three off-centre, all inside
+    d, L = oracle_samples(orc, sc, p)
+    assert np.array_equal(L, np.broadcast_to(E, L.shape))                          # the oracle agrees: every sample is the emission
+    gpu_ctx.upload(sc.flatten())
+    sh, f32, _, _, st = gpu_ctx.render_probes(cam, p, seed=SEED)
+    assert st.samples == 4 * 64 and np.array_equal(f32, np.broadcast_to(E, f32.shape))
+    rel = float((np.abs(sh[:, :, 0, :].astype(np.float64) - np.sqrt(FOUR_PI) * E) / (np.sqrt(FOUR_PI) * E)).max())
+    ref, mass = project(d, L)
+    ratio = sh_ratio(sh, ref, mass)
+    print(f"furnace: c_0 relative error {rel:.3e} (bar 1e-5), c_1..8 ratio {ratio:.3e} (bar 2e-5)")
+    assert rel <= 1e-5
+    assert ratio <= 2e-5
+
+
+# ---------------------------------------------------------------- 5. exactness across schedules
+def device_render(ctx, cam, p, world, seed, flags=0, split=None, max_state_bytes=0, with_sh=True):
+    """The device form: every rank's tiles in turn into gathered buffers (pre-filled with NaN), the plain outputs un-permuted and tone
+    mapped on the device, the SH records and signatures un-permuted with the numpy mirror of the mapping.  split = k renders [0, k) and
+    [k, aa) as two progressive calls with BOTH accumulators (the float4 sums and the SH records) copied out to the host and back in
+    between.  Returns (sh or None, f32, u8, sig)."""
+    import torch
+    dev = torch.device("cuda:0")
+    t_p = torch.from_numpy(np.array(p)).to(dev)
+    Wc, Hc = cam.screen_width, cam.screen_height
+    padded = pdist.tiles_padded(Wc, Hc, world)
+    nan = float("nan")
+    gathered = torch.full((world, padded, pdist.TILE_PIXELS, 3), nan, dtype=torch.float32, device=dev)
+    gsh = torch.full((world, padded, pdist.TILE_PIXELS, 27), nan, dtype=torch.float32, device=dev)
+    gsig = torch.zeros((world, padded, pdist.TILE_PIXELS), dtype=torch.int32, device=dev)
+    torch.cuda.synchronize(dev)
+    samples = 0
+    for r in range(world):
+        kw = dict(seed=seed, rank=r, world=world, flags=flags, max_state_bytes=max_state_bytes)
+        psh = gsh[r].data_ptr() if with_sh else None
+        if split is None:
+            st = ctx.render_probes_device(cam, t_p.data_ptr(), p.shape[0], psh, gathered[r].data_ptr(), gsig[r].data_ptr(), **kw)
+            samples += st.samples
+        else:
+            acc = torch.full((padded * pdist.TILE_PIXELS, 4), nan, dtype=torch.float32, device=dev)
+            st = ctx.render_probes_device(cam, t_p.data_ptr(), p.shape[0], psh, None, gsig[r].data_ptr(), 0, split, acc.data_ptr(), **kw)
+            samples += st.samples
+            saved, saved_sh = acc.cpu(), gsh[r].cpu()
+            gsh[r] = nan
+            acc2, sh2 = saved.to(dev), saved_sh.to(dev)     # "another process": both sums travel through the host
+            torch.cuda.synchronize(dev)
+            st = ctx.render_probes_device(cam, t_p.data_ptr(), p.shape[0], sh2.data_ptr() if with_sh else None, gathered[r].data_ptr(),
+                                          gsig[r].data_ptr(), split, cam.aa_sample_count, acc2.data_ptr(), **kw)
+            samples += st.samples
+            gsh[r] = sh2
+    image = torch.empty((Hc, Wc, 3), dtype=torch.float32, device=dev)
+    u8 = torch.empty((Hc, Wc, 3), dtype=torch.uint8, device=dev)
+    ctx.unpermute_device(cam, world, gathered.data_ptr(), image.data_ptr())
+    ctx.tonemap_device(cam, image.data_ptr(), u8.data_ptr())
+    torch.cuda.synchronize(dev)
+    assert not torch.isnan(gathered).any()                  # padding slots and pixels outside the image are written as zeros
+    r_of, idx = pdist.compact_index(Wc, Hc, world)
+    sig = gsig.cpu().numpy().view(np.uint32).reshape(world, -1)[r_of, idx]
+    assert samples == Wc * Hc * cam.aa_sample_count
+    sh = None
+    if with_sh:
+        assert not torch.isnan(gsh).any()                   # likewise, and no sum started from what the buffer held
+        flat = gsh.cpu().numpy().reshape(world, -1, 27)
+        inside = np.zeros(flat.shape[:2], bool)
+        inside[r_of, idx] = True
+        assert not flat.view(np.uint32)[~inside].any()      # +0.0 in every slot that is no probe
+        sh = flat[r_of, idx].reshape(Hc, Wc, 9, 3)
+    else:
+        assert torch.isnan(gsh).all()                       # NULL: not touched
+    return sh, image.cpu().numpy(), u8.cpu().numpy(), sig
+
+
+@pytest.mark.parametrize("name", ["config2", "long_list", "head"])
+def test_schedules_are_bit_identical(gpu_ctx, orc, name):
+    sc = SCENES[name][0]()
+    cam = sc.camera
+    gpu_ctx.upload(sc.flatten())
+    p = point_table(orc, name, "aa")[0]
+    assert p.shape[0] == cam.aa_sample_count
+    base = gpu_ctx.render_probes(cam, p, seed=SEED, want_sig=True)[:4]
+    assert base[1].max() > 0 and len(np.unique(base[3])) > 100 and np.abs(base[0][:, :, 1:, :]).max() > 0.1
+    ms = gpu_ctx.last_pipeline_ms()
+    assert gpu_ctx.last_reduce_sh_ms() > 0.0
+    # one sample per batch: the budget of one sample of every padded pixel (208 B per path, 72 B more with a two-stage mesh)
+    npix = pdist.tiles_padded(W, H, 1) * pdist.TILE_PIXELS
+    got = gpu_ctx.render_probes(cam, p, seed=SEED, want_sig=True, max_state_bytes=npix * (2 * 6 * 16 + 16 + 72))[:4]
+    assert gpu_ctx.last_pipeline_ms()["launches"] > ms["launches"]
+    assert same(got, base), "one sample per batch"
+    for flags in (abi.MI_OPT_NO_LIST_TREE, abi.MI_OPT_REFERENCE_WALK, abi.MI_OPT_TWO_STAGE, abi.MI_OPT_NO_TILE_MASKS):
+        got = gpu_ctx.render_probes(cam, p, seed=SEED, want_sig=True, flags=flags)[:4]
+        assert same(got, base), f"flags {flags}"
+        assert gpu_ctx.last_pipeline_counts()["dead_tile_samples"] == 0
+    for world in (1, 2, 3):                                                        # world 1 is also: the host against the device entry point
+        assert same(device_render(gpu_ctx, cam, p, world, SEED), base), f"world {world}"
+    assert same(device_render(gpu_ctx, cam, p, 1, SEED, split=1), base), "progressive split [0, 1) + [1, aa)"
+    assert same(device_render(gpu_ctx, cam, p, 2, SEED, split=1), base), "progressive, two ranks"
+
+
+# ---------------------------------------------------------------- 6. edges
+def _small(sc, w, h, aa=4, depth=6):
+    cam = sc.camera
+    cam.screen_width, cam.screen_height, cam.aa_sample_count, cam.path_depth = w, h, aa, depth
+    return sc
+
+
+PROBE_P = (0.3, 4.5, 0.5)                                                          # under the Cornell box's ceiling light
+
+
+def _check_small(gpu_ctx, orc, sc, p, what):
+    """a whole small table against the oracle: mean under the parity bar, SH under bar 3; returns the GPU's outputs"""
+    cam = sc.camera
+    gpu_ctx.upload(sc.flatten())
+    sh, f32, u8, sig, st = gpu_ctx.render_probes(cam, p, seed=SEED, want_sig=True)
+    assert st.samples == cam.screen_width * cam.screen_height * cam.aa_sample_count
+    d, L = oracle_samples(orc, sc, p)
+    acc = np.zeros(L.shape[1:], np.float32)
+    for s in range(cam.aa_sample_count):
+        acc = acc + L[s]
+    r32 = acc / np.float32(cam.aa_sample_count)
+    assert r32.sum() > 0, what
+    assert float((np.abs(f32.astype(np.float64) - r32) / np.maximum(1.0, np.abs(r32))).max()) <= 2e-5, what
+    ratio = sh_ratio(sh, *project(d, L))
+    print(f"{what}: SH ratio {ratio:.3e}")
+    assert ratio <= 2e-5, what
+    return sh, f32, u8, sig
+
+
+def test_one_pixel_image(gpu_ctx, orc):
+    sh, f32, _, _ = _check_small(gpu_ctx, orc, _small(scenes.config1(), 1, 1), np.float32(PROBE_P).reshape(1, 1, 3), "1 x 1")
+    assert sh.shape == (1, 1, 9, 3) and f32.shape == (1, 1, 3)
+
+
+def test_a_second_tile_column_one_pixel_wide(gpu_ctx, orc):
+    p = np.zeros((1, 33, 3), np.float32)
+    p[0, :, 0] = np.linspace(-2.0, 2.0, 33)
+    p[0, :, 1] = 4.5
+    sc = _small(scenes.config1(), 33, 1)
+    sh, f32, u8, sig = _check_small(gpu_ctx, orc, sc, p, "33 x 1")
+    assert f32[0, 32].sum() > 0 and sig[0, 32] != 0 and np.abs(sh[0, 32]).max() > 0
+    assert same(device_render(gpu_ctx, sc.camera, p[None], 2, SEED), (sh, f32, u8, sig))      # one tile per rank
+
+
+@pytest.mark.parametrize("aa", [1, 5])
+def test_other_sample_counts(gpu_ctx, orc, aa):
+    p = np.random.default_rng(aa).uniform(-2.0, 2.0, (aa, 3, 5, 3)).astype(np.float32) + np.float32([0.0, 3.0, 0.0])
+    _check_small(gpu_ctx, orc, _small(scenes.config1(), 5, 3, aa=aa), p, f"aa = {aa}")
+
+
+def test_path_depth_zero_is_all_positive_zero(gpu_ctx, orc):
+    sc = SCENES["config2"][0]()
+    sc.camera.path_depth = 0
+    gpu_ctx.upload(sc.flatten())
+    p = point_table(orc, "config2", 1)[0]
+    sh, f32, u8, sig, _ = gpu_ctx.render_probes(sc.camera, p, seed=SEED, want_sig=True)
+    assert not bits(sh).any() and not bits(f32).any() and not u8.any()             # +0.0: not one sign bit
+    got = device_render(gpu_ctx, sc.camera, p, 1, SEED)
+    assert not bits(got[0]).any() and not bits(got[1]).any()
+
+
+def test_a_null_sh_buffer_gives_the_plain_outputs_only(gpu_ctx, orc):
+    sc = SCENES["config2"][0]()
+    gpu_ctx.upload(sc.flatten())
+    p = point_table(orc, "config2", "aa")[0]
+    full = device_render(gpu_ctx, sc.camera, p, 1, SEED)
+    assert full[1].max() > 0
+    assert gpu_ctx.last_reduce_sh_ms() > 0.0
+    plain = device_render(gpu_ctx, sc.camera, p, 1, SEED, with_sh=False)
+    assert plain[0] is None and same(plain[1:], full[1:])
+    assert gpu_ctx.last_reduce_sh_ms() == 0.0                    # wf_reduce_sh was not launched
+    assert same(device_render(gpu_ctx, sc.camera, p, 2, SEED, split=1, with_sh=False)[1:], full[1:])
+
+
+# ---------------------------------------------------------------- 7. bad probes
+@pytest.mark.parametrize("name", ["config2", "head"])
+def test_bad_probes_do_not_disturb_their_neighbours(gpu_ctx, orc, name):
+    """NaN, infinite and huge positions at 60 random probes and the four corners: MI_OK, every other probe's 27 + 3 values (and its
+    bytes and signature) keep the clean render's bits, and a clean render afterwards is unchanged."""
+    sc = SCENES[name][0]()
+    cam = sc.camera
+    gpu_ctx.upload(sc.flatten())
+    p = point_table(orc, name, "aa")[0]
+    good = gpu_ctx.render_probes(cam, p, seed=SEED, want_sig=True)[:4]
+    nan, inf = np.float32("nan"), np.float32("inf")
+    bad_p = [(nan, 0.0, 0.0), (inf, inf, inf), (0.0, -inf, 5.0), (3e38, 3.0, 6.6), (nan, nan, nan), (-3e38, 3e38, 3e38), (0.0, nan, inf)]
+    p2 = np.array(p)
+    mask = np.zeros((H, W), bool)
+    for k, q in enumerate(np.random.default_rng(2).choice(H * W, 60, replace=False)):
+        y, x = divmod(int(q), W)
+        p2[k % cam.aa_sample_count if k % 3 else slice(None), y, x] = bad_p[k % len(bad_p)]      # one row of the probe, or all of them
+        mask[y, x] = True
+    for y, x in ((0, 0), (H - 1, 0), (0, W - 1), (H - 1, W - 1)):                 # the image corners, next to the padded lanes
+        p2[:, y, x] = (inf, nan, -inf)
+        mask[y, x] = True
+    got = gpu_ctx.render_probes(cam, p2, seed=SEED, want_sig=True)[:4]             # MI_OK, or check() raises
+    keep = ~mask
+    assert keep.sum() > 3000
+    for a, b in zip(got, good):
+        assert np.array_equal(bits(a)[keep], bits(b)[keep])
+    again = gpu_ctx.render_probes(cam, p, seed=SEED, want_sig=True)[:4]            # and the context is as good as before
+    assert same(again, good)
+
+
+# ---------------------------------------------------------------- 8. refusals
+def test_refusals_launch_nothing(gpu_ctx, orc):
+    lib = abi.load()
+    sc = SCENES["config1"][0]()
+    gpu_ctx.upload(sc.flatten())
+    p = np.array(point_table(orc, "config1", "aa")[0])
+    f32 = np.full((H, W, 3), -7.0, np.float32)
+    sh = np.full((H, W, 9, 3), -7.0, np.float32)
+    h, pp, pf, ps = gpu_ctx._h, p.ctypes.data, f32.ctypes.data, sh.ctypes.data
+    nan = float("nan")
+
+    def call(ctx=h, rows=4, pts=pp, out_sh=ps, variant=0, rank=0, world=1, device=False, **cam_kw):
+        cam = SCENES["config1"][0]().camera
+        for k, v in cam_kw.items():
+            setattr(cam, k, v)
+        pod = cam.to_pod()
+        opts = abi.mi_render_opts(seed=SEED, rank=rank, world=world, variant=variant, want_signature=0, flags=0, max_state_bytes=0)
+        if device:        # every refusal comes before a pointer is used: the host arrays stand in for device memory here
+            rc = lib.mi_render_probes_device(ctx, C.byref(pod), C.byref(opts), pts, rows, 0, cam.aa_sample_count, None, out_sh, pf, None, None, None)
+        else:
+            rc = lib.mi_render_probes(ctx, C.byref(pod), C.byref(opts), pts, rows, out_sh, pf, None, None, None)
+        msg = lib.mi_last_error().decode()
+        assert rc == abi.MI_OK or len(msg) > 10, (rc, msg)
+        return rc, msg
+
+    assert call()[0] == abi.MI_OK and f32.max() > 0 and np.abs(sh).max() > 0 and not (sh == -7.0).any()
+    f32[:] = -7.0
+    sh[:] = -7.0
+    ms_before = gpu_ctx.last_kernel_ms()
+    counts_before = gpu_ctx.last_pipeline_counts()
+    for device in (False, True):
+        kw = dict(device=device)
+        rc, msg = call(path_samples=2, **kw)
+        assert rc == abi.MI_ERR_UNSUPPORTED and "mi_shade_rays" in msg
+        rc, msg = call(shading_mode=ShadingMode.Phong, **kw)
+        assert rc == abi.MI_ERR_UNSUPPORTED and len(msg) > 10
+        for variant in (abi.MI_VARIANT_SIMPLE, abi.MI_VARIANT_VOTED, abi.MI_VARIANT_VOTED_DIAG, abi.MI_VARIANT_RECURSIVE, 2, 99):
+            assert call(variant=variant, **kw)[0] == abi.MI_ERR_UNSUPPORTED, variant
+        for bad in (dict(path_samples=0), dict(max_trace_dist=nan), dict(gamma=0.0), dict(gamma=nan), dict(screen_width=0),
+                    dict(screen_width=40000), dict(aa_sample_count=0)):
+            assert call(**bad, **kw)[0] == abi.MI_ERR_INVALID, bad
+        for rows in (0, 2, 3, 5, 16):
+            assert call(rows=rows, **kw)[0] == abi.MI_ERR_INVALID, rows
+        rc, msg = call(pts=None, **kw)
+        assert rc == abi.MI_ERR_INVALID and "mi_render_probes" in msg
+        assert call(ctx=None, **kw)[0] == abi.MI_ERR_INVALID
+        assert call(rank=1, world=1, **kw)[0] == abi.MI_ERR_INVALID
+    assert call(rank=0, world=2)[0] == abi.MI_ERR_INVALID                           # the host form renders a whole image
+    rc, msg = call(out_sh=None)                                                     # and requires out_sh
+    assert rc == abi.MI_ERR_INVALID and "out_sh" in msg
+    assert np.all(f32 == -7.0) and np.all(sh == -7.0)                               # nothing was written ...
+    assert gpu_ctx.last_kernel_ms() == ms_before and gpu_ctx.last_pipeline_counts() == counts_before      # ... and nothing was launched
+    fresh = Context(0)
+    try:
+        for device in (False, True):
+            assert call(ctx=fresh._h, device=device)[0] == abi.MI_ERR_NO_SCENE
+    finally:
+        fresh.close()
+    assert call()[0] == abi.MI_OK and f32.max() > 0                                 # the context is still good
+    # a device-form range without an accumulator, and the other progressive rules of mi_render_samples_device
+    import torch
+    cam = sc.camera
+    n = pdist.tiles_padded(W, H, 1) * pdist.TILE_PIXELS
+    t_p = torch.from_numpy(p).to("cuda:0")
+    acc = torch.zeros((n, 4), dtype=torch.float32, device="cuda:0")
+    out = torch.zeros((n, 3), dtype=torch.float32, device="cuda:0")
+    tsh = torch.full((n, 27), -7.0, dtype=torch.float32, device="cuda:0")
+    torch.cuda.synchronize()
+    for b, e, a, c in ((0, 2, None, None), (0, 2, None, out), (1, 4, None, out), (2, 2, acc, out), (3, 2, acc, out), (0, 5, acc, out),
+                       (0, 4, acc, None), (0, 4, None, None)):
+        with pytest.raises(abi.MiError) as ei:
+            gpu_ctx.render_probes_device(cam, t_p.data_ptr(), 4, tsh.data_ptr(), c.data_ptr() if c is not None else None, None, b, e,
+                                         a.data_ptr() if a is not None else None)
+        assert ei.value.code == abi.MI_ERR_INVALID and len(str(ei.value)) > 10, (b, e)
+    assert bool((tsh == -7.0).all())
+    with pytest.raises(ValueError):                                                 # and the Python mirror checks before any call
+        gpu_ctx.render_probes(cam, p[:2])
+
+
+# ---------------------------------------------------------------- 9. mi_render is untouched
+def test_render_is_bit_identical_before_and_after_a_probe_render(gpu_ctx, orc):
+    sc = scenes.config2(240, 136, 16, 10)
+    gpu_ctx.upload(sc.flatten())
+    gpu_ctx.reserve(sc.camera)
+    a32, a8, asig, _ = gpu_ctx.render(sc.camera, seed=1, want_sig=True)
+    gpu_ctx.render(sc.camera, seed=1)
+    dead = gpu_ctx.last_pipeline_counts()["dead_tile_samples"]
+    assert dead > 0 and gpu_ctx.last_reduce_sh_ms() == 0.0       # the camera render culls dead tiles and reduces no SH ...
+    small = SCENES["config2"][0]().camera
+    p = point_table(orc, "config2", 1)[0]
+    sh, t32, _, _, _ = gpu_ctx.render_probes(small, p, seed=1)
+    assert t32.max() > 0 and np.abs(sh).max() > 0 and gpu_ctx.last_pipeline_counts()["dead_tile_samples"] == 0      # ... the probe render does
+    b32, b8, bsig, _ = gpu_ctx.render(sc.camera, seed=1, want_sig=True)
+    assert np.array_equal(bits(a32), bits(b32)) and np.array_equal(asig, bsig) and np.array_equal(a8, b8)
+    c32, _, _, _ = gpu_ctx.render(sc.camera, seed=1, want_sig=False)
+    assert np.array_equal(bits(a32), bits(c32)) and gpu_ctx.last_pipeline_counts()["dead_tile_samples"] == dead
+    assert gpu_ctx.last_reduce_sh_ms() == 0.0
+
+
+# ---------------------------------------------------------------- 10. end to end: a probe grid in the Cornell box
+def test_probe_grid_in_the_cornell_box(gpu_ctx, orc):
+    pts, n = probe_grid((-3.0, 0.0, -3.0), (3.0, 6.0, 3.0), (4, 4, 4), width=16)   # the box itself, cut into 4 x 4 x 4 cells
+    assert n == 64 and pts.shape == (4, 16, 3)
+    cam = Camera(screen_width=16, screen_height=4, aa_sample_count=64, path_depth=6, max_trace_dist=100.0, gamma=2.0)
+    sc = Scene(cam, scenes.cornell_walls())
+    sh, mean, u8, sig, st = sc.render_probes(pts, seed=SEED)                        # the whole public path, a context of its own
+    assert sh.shape == (4, 16, 9, 3) and mean.shape == (4, 16, 3) and u8.shape == (4, 16, 3) and sig.shape == (4, 16)
+    assert st.samples == 64 * 64
+    light = np.float32([0.0, 6.0, 0.0])                                             # the ceiling light's centre
+    near = np.unravel_index(int(((pts - light) ** 2).sum(axis=-1).argmin()), (4, 16))
+    up, down = sh9_irradiance(sh[near], (0, 1, 0)), sh9_irradiance(sh[near], (0, -1, 0))
+    print(f"probe {near} at {pts[near]}: irradiance facing up {up}, facing down {down}")
+    assert (up > 2.0 * down).all() and (down > 0.0).all()
+    d, L = oracle_samples(orc, sc, pts)
+    ref, mass = project(d, L)
+    assert (sh9_irradiance(ref[near], (0, 1, 0)) > 2.0 * sh9_irradiance(ref[near], (0, -1, 0))).all()      # so says the oracle too
+    ratio = sh_ratio(sh, ref, mass)
+    print(f"probe grid: SH ratio {ratio:.3e}")
+    assert ratio <= 2e-5

@@ -43,7 +43,17 @@ aa_sample_count = 16, path_depth 10.  The pre-made directions are restated on th
 (seed, W*H + y*W + x, s), rand_sphere_vec, |y|, the rotation from unit y, operation for operation in f32); an empty texel's ray in the
 table starts far outside the scene and meets nothing.  The two alternate call by call (5 warm-up pairs, then --calls timed pairs;
 median / min / max of mi_last_kernel_ms, and their ratio) and the tool checks that the two compact images agree bit for bit on the live
-texels: if they did not, the restated directions would not be the kernel's and the rows would not compare like with like."""
+texels: if they did not, the restated directions would not be the kernel's and the rows would not compare like with like.
+
+--mode probes compares light-probe rendering (mi_render_probes_device: the camera pass draws each sample's full-sphere direction, and
+wf_reduce_sh projects the samples onto the SH L2 basis) with ray-table rendering (mi_render_rays_device) fed the IDENTICAL rays,
+pre-made and resident — the same protocol as --mode bake, and the same exclusion: the ray-table run neither makes nor uploads its
+directions, and it produces no SH output at all, so the rows are like for like in the traced paths only.  The probes are a cubic grid
+inside the Cornell box (probe_grid over [-2.8, 2.8] x [0.2, 5.8] x [-2.8, 2.8]) laid out as a square table: 4096 probes x 256 samples
+(a 64 x 64 table) and 65536 probes x 64 samples (256 x 256), path_depth 10.  The pre-made directions are rand_sphere_vec restated in
+numpy (sphere_dirs below).  Each row reports median / min / max of mi_last_kernel_ms; the probes row also the time of wf_reduce_sh
+(entry 7 of mi_last_pipeline_ms: HIP events around its launches) and its share of the kernel time.  The tool checks that the two
+compact images agree bit for bit."""
 import argparse
 import json
 import os
@@ -202,12 +212,11 @@ def _ulps_eq(a, b):
     return near | (((a < 0) == (b < 0)) & (np.abs(ia - ib) <= 4))
 
 
-def hemisphere_dirs(normals, seed, key0, sample):
-    """sample_hemisphere(normal) as mi_render_points draws it, for texels i = 0 .. n-1 with keys key0 + i and one sample index:
-    normals [n, 3] f32 (non-zero, finite) -> directions [n, 3] f32.  Every step is the kernel's f32 / u32 operation, in its order."""
+def sphere_dirs(n, seed, key0, sample):
+    """rand_sphere_vec as mi_render_points / mi_render_probes draw it on the direction stream, for pixels i = 0 .. n-1 with keys key0 + i
+    and one sample index: [n, 3] f32 points of the unit ball.  Every step is the kernel's f32 / u32 operation, in its order."""
     F, U = np.float32, np.uint32
     with np.errstate(over="ignore"):
-        n = len(normals)
         seed_key = _lowbias32(np.array([seed], U) ^ U(0x68e31da4))[0]
         p0 = _lowbias32(np.arange(n, dtype=U) + U(key0) + seed_key)
         p1 = _lowbias32(p0 ^ U(0xb5297a4d))
@@ -230,6 +239,14 @@ def hemisphere_dirs(normals, seed, key0, sample):
             ok = todo & (((c[:, 0] * c[:, 0] + c[:, 1] * c[:, 1]) + c[:, 2] * c[:, 2]) <= F(1.0))
             v[ok] = c[ok]
             todo &= ~ok
+    return v
+
+
+def hemisphere_dirs(normals, seed, key0, sample):
+    """sample_hemisphere(normal) as mi_render_points draws it, for texels i = 0 .. n-1 with keys key0 + i and one sample index:
+    normals [n, 3] f32 (non-zero, finite) -> directions [n, 3] f32.  Every step is the kernel's f32 / u32 operation, in its order."""
+    F = np.float32
+    v = sphere_dirs(len(normals), seed, key0, sample)
     v[:, 1] = np.abs(v[:, 1])
     nx, ny, nz = (np.ascontiguousarray(normals[:, k], F) for k in range(3))
     ident = _ulps_eq(ny, 1.0)
@@ -320,6 +337,65 @@ def bake_rows(ctx, cfg, sc, first, calls, warmup):
     return rows
 
 
+def probes_rows(ctx, cfg, sc, calls, warmup):
+    from cs397raytracingsp22_amd import dist as pdist, probe_grid
+    dev = torch.device("cuda:0")
+    cam = sc.camera
+    rows = []
+    for side, aa in ((64, 256), (256, 64)):
+        cells = {64: (16, 16, 16), 256: (64, 32, 32)}[side]                  # 4096 and 65536 probes
+        pts, n = probe_grid((-2.8, 0.2, -2.8), (2.8, 5.8, 2.8), cells, width=side)
+        assert n == side * side and pts.shape == (side, side, 3)
+        W = H = side
+        cam.screen_width, cam.screen_height, cam.aa_sample_count = W, H, aa
+        t_p = torch.from_numpy(pts).to(dev)                                  # [1][H][W][3]
+        t_o = t_p[None].expand(aa, H, W, 3).contiguous()
+        t_d = torch.empty((aa, H * W, 3), dtype=torch.float32, device=dev)
+        for s in range(aa):
+            t_d[s] = torch.from_numpy(sphere_dirs(W * H, 1, W * H, s)).to(dev)
+        n_compact = pdist.tiles_padded(W, H, 1) * pdist.TILE_PIXELS
+        c_prb = torch.empty((n_compact, 3), dtype=torch.float32, device=dev)
+        c_rays = torch.empty((n_compact, 3), dtype=torch.float32, device=dev)
+        c_sh = torch.empty((n_compact, 27), dtype=torch.float32, device=dev)
+        torch.cuda.synchronize()
+        prb_ms, rays_ms, sh_ms = [], [], []
+        for k in range(warmup + calls):
+            ctx.render_probes_device(cam, t_p.data_ptr(), 1, c_sh.data_ptr(), c_prb.data_ptr(), seed=1)
+            torch.cuda.synchronize()
+            a, sh = ctx.last_kernel_ms(), ctx.last_reduce_sh_ms()
+            seg_p = ctx.last_pipeline_counts()["segments"]
+            ctx.render_rays_device(cam, t_o.data_ptr(), t_d.data_ptr(), aa, c_rays.data_ptr(), seed=1)
+            torch.cuda.synchronize()
+            b = ctx.last_kernel_ms()
+            seg_r = ctx.last_pipeline_counts()["segments"]
+            if k >= warmup:
+                prb_ms.append(a)
+                rays_ms.append(b)
+                sh_ms.append(sh)
+        differ = int((c_prb.view(torch.int32) != c_rays.view(torch.int32)).any(dim=-1).sum().item())
+        stat = lambda v: {"kernel_ms_median": round(float(np.median(v)), 4), "kernel_ms_min": round(float(np.min(v)), 4),
+                          "kernel_ms_max": round(float(np.max(v)), 4),
+                          "msamples_per_s_kernel": round(W * H * aa / float(np.median(v)) / 1e3, 1)}
+        ratios = [a / b for a, b in zip(prb_ms, rays_ms)]
+        base = {"config": cfg, "mode": "probes", "probes": W * H, "aa_sample_count": aa, "path_depth": cam.path_depth, "calls": calls,
+                "probes_that_differ": differ}
+        out = [dict(base, query="render_probes", segments=seg_p, wf_reduce_sh_ms_median=round(float(np.median(sh_ms)), 4),
+                    wf_reduce_sh_ms_min=round(float(np.min(sh_ms)), 4), wf_reduce_sh_ms_max=round(float(np.max(sh_ms)), 4),
+                    wf_reduce_sh_share=round(float(np.median(sh_ms)) / float(np.median(prb_ms)), 4),
+                    sh_abs_mean=round(float(c_sh.abs().mean().item()), 6), **stat(prb_ms)),
+               dict(base, query="render_rays (pre-made rays)", segments=seg_r, **stat(rays_ms)),
+               dict(base, query="ratio render_probes / render_rays", kernel_ms_median=round(float(np.median(prb_ms)) / float(np.median(rays_ms)), 4),
+                    pairwise_ratio_median=round(float(np.median(ratios)), 4), pairwise_ratio_min=round(float(np.min(ratios)), 4),
+                    pairwise_ratio_max=round(float(np.max(ratios)), 4))]
+        for row in out:
+            print(json.dumps(row), flush=True)
+        rows += out
+        if differ:
+            raise SystemExit(f"ray_query_bench: {differ} probes differ between the probe and the ray-table render: the restated "
+                             "directions are not the kernel's")
+    return rows
+
+
 SHADOW_POINT = (0.0, 5.9, 0.0)          # just under the Cornell box's ceiling light (y = 6)
 
 
@@ -390,11 +466,12 @@ def main():
     ap.add_argument("--width", type=int, default=1920)
     ap.add_argument("--height", type=int, default=1080)
     ap.add_argument("--configs", default="2,4")
-    ap.add_argument("--mode", choices=("intersect", "occlusion", "render", "hemisphere", "bake"), default="intersect",
+    ap.add_argument("--mode", choices=("intersect", "occlusion", "render", "hemisphere", "bake", "probes"), default="intersect",
                     help="intersect: the closest-hit rows; occlusion: the any-hit query against the visibility form; "
                          "render: ray-table rendering against mi_shade_rays_device; "
                          "hemisphere: hemisphere occlusion against the any-hit query on the identical pre-made rays; "
-                         "bake: point-table rendering against ray-table rendering on the identical pre-made rays")
+                         "bake: point-table rendering against ray-table rendering on the identical pre-made rays; "
+                         "probes: light-probe rendering against ray-table rendering on the identical pre-made rays")
     ap.add_argument("--points", type=int, default=1 << 18, help="--mode hemisphere: at most this many surface points (64 rays each)")
     ap.add_argument("--out", default=None, help="also append the JSON lines to this file")
     a = ap.parse_args()
@@ -408,6 +485,9 @@ def main():
         sc = {2: scenes.config2, 4: scenes.config4}[cfg](a.width, a.height, 1, 10)
         ctx.upload(sc.flatten())
         co, cd = pinhole_rays(sc.camera)
+        if a.mode == "probes":
+            rows += probes_rows(ctx, cfg, sc, a.calls, a.warmup)
+            continue
         if a.mode == "render":
             rows += render_rows(ctx, cfg, sc, co, cd, a.calls, a.warmup)
             continue
