@@ -226,7 +226,7 @@ def device_render(ctx, cam, p, world, seed, flags=0, split=None, max_state_bytes
     return sh, image.cpu().numpy(), u8.cpu().numpy(), sig
 
 
-@pytest.mark.parametrize("name", ["config2", "long_list", "head"])
+@pytest.mark.parametrize("name", ["config2", "long_list", "head", "rare_top", "gv_mesh_top"])
 def test_schedules_are_bit_identical(gpu_ctx, orc, name):
     sc = SCENES[name][0]()
     cam = sc.camera

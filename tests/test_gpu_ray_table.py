@@ -9,7 +9,8 @@ import ctypes as C
 import numpy as np
 import pytest
 
-from cs397raytracingsp22_amd import Context, Triangle, abi, dist as pdist, scenes
+from cs397raytracingsp22_amd import (Context, ConvexVolume, Isotropic, Lambertian, Plane, Sphere, StaticMesh, Triangle, abi, cgmath,
+                                     dist as pdist, scenes)
 from cs397raytracingsp22_amd.tracing import ShadingMode, equirect_ray_table
 
 from test_gpu_parity import RMS_TOL
@@ -28,6 +29,32 @@ def _sized(sc, aa, depth):
     return sc
 
 
+def rare_top_scene():
+    """The top-level tree beside the rare kinds: long_triangle_list() + a sphere-bounded ConvexVolume + a Plane (no general boundary)."""
+    sc = long_triangle_list()
+    sc.objects += [ConvexVolume(Sphere((0.6, 1.6, 0.9), 0.9, Lambertian(albedo=(0.6, 0.6, 0.6))), Isotropic(albedo=(0.9, 0.8, 0.7)), 1.5),
+                   Plane((0.0, -0.5, 0.0), (0.0, 1.0, 0.0), Lambertian(albedo=(0.4, 0.5, 0.4), emission=(0.05, 0.05, 0.05)))]
+    return sc
+
+
+def gv_top_scene():
+    """The top-level tree beside a general boundary: cube_volume_scene() + the 120 small Triangles of long_triangle_list()."""
+    sc = cube_volume_scene()
+    sc.objects += long_triangle_list().objects[-120:]
+    return sc
+
+
+def gv_mesh_top_scene():
+    """gv_top + a small untextured teapot near the opening of the box: the later passes take the M = 1 state form beside the tree and the
+    general volume, and the scene's mesh trees are staged in LDS beside the tree's pools."""
+    sc = gv_top_scene()
+    xf = cgmath.mul(cgmath.from_translation(TEAPOT_AT), cgmath.from_angle_x(-90.0), cgmath.from_scale(TEAPOT_SCALE))
+    sc.objects.append(StaticMesh(scenes.load_asset_mesh("teapot"), Lambertian(albedo=(0.6, 0.3, 0.2), emission=(0.2, 0.2, 0.2)), [None] * 5, xf))
+    return sc
+
+
+TEAPOT_AT, TEAPOT_SCALE = (1.45, 0.62, 1.8), 1.7
+
 # scene -> (builder, aa_sample_count, an eye inside the scene for the panorama); between them they select every RAYS form of wf_main
 SCENES = {
     "config1": (lambda: _sized(scenes.config1(), 4, 8), (0.3, 2.5, 1.0)),                      # plain
@@ -37,6 +64,9 @@ SCENES = {
     "long_list": (lambda: _sized(long_triangle_list(), 4, 6), (0.2, 5.5, 2.5)),                # TOP: >= 96 small triangles in a tree
     "config4": (lambda: _sized(scenes.config4(tex_size=64), 4, 8), (1.5, 1.0, 2.0)),           # textured class B
     "head": (lambda: _sized(scenes.head_scene(), 3, 8), (0.0, 2.0, 4.0)),                      # two-stage meshes; aa = 3 is no square
+    "rare_top": (lambda: _sized(rare_top_scene(), 4, 6), (0.2, 5.5, 2.5)),                     # RARE + TOP: a Plane and a sphere volume behind the tree
+    "gv_top": (lambda: _sized(gv_top_scene(), 4, 6), (-0.5, 4.0, 2.0)),                        # GV + TOP
+    "gv_mesh_top": (lambda: _sized(gv_mesh_top_scene(), 4, 6), (-0.5, 4.0, 2.0)),              # GV + TOP with a mesh: M = 1 state passes
 }
 
 
@@ -186,7 +216,7 @@ def device_render(ctx, cam, o, d, world, seed, flags=0, split=None, max_state_by
     return image.cpu().numpy(), u8.cpu().numpy(), sig
 
 
-@pytest.mark.parametrize("name", ["config2", "long_list", "head"])
+@pytest.mark.parametrize("name", ["config2", "long_list", "head", "rare_top", "gv_mesh_top"])
 def test_schedules_are_bit_identical(gpu_ctx, name):
     sc = SCENES[name][0]()
     cam = sc.camera

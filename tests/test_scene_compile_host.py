@@ -1230,3 +1230,135 @@ def test_census_every_compiler_branch_is_rendered_against_the_oracle(shim):
     for item, tests in reached.items():
         print(f"{item}: {tests[0] if tests else 'NOT REACHED'}" + (f" (+{len(tests) - 1})" if len(tests) > 1 else ""))
     assert not [item for item, tests in reached.items() if not tests]
+
+
+# ---------------------------------------------------------------------------------------------- j. launch-form census
+# The launchers of pt_kernels.hip pick one instantiation per launch by indexing a table with facts about the compiled scene.  Restated:
+#   launch_rq_intersect  [lds][gv][top][resolve]      launch_rq_occluded, launch_rq_hemi  [lds][gv][top]
+#   launch_wf_main, the camera pass of a table render  [sig][plain / rare / rare + gv][ray table / point table / probes][top]
+# lds (mi_rt.cpp stage_in_lds): the scene lists a mesh, its trees fit 64 KB of LDS and the context was not made under MI_RT_GLOBAL_BVH.
+def query_cell(b, context):
+    lds = b.n_meshes > 0 and b.info.lds_bytes <= 64 * 1024 and context != "global_ctx"
+    return ("lds" if lds else "global", "gv" if b.info.gen_volumes else "sphere volumes only", "top" if b.top_meshf >= 0 else "flat")
+
+
+def table_cell(b):
+    rare = b.n_list_plane + b.n_list_volume > 0
+    return ("plain" if not rare else "rare + gv" if b.info.gen_volumes else "rare", "top" if b.top_meshf >= 0 else "flat")
+
+
+QUERY_CELLS = list(itertools.product(("lds", "global"), ("gv", "sphere volumes only"), ("top", "flat")))
+LAUNCH_CELLS = [("rq_intersect", *c, r) for c in QUERY_CELLS for r in ("resolve", "visibility")] + \
+               [(k, *c) for k in ("rq_occluded", "rq_hemi") for c in QUERY_CELLS] + \
+               [("wf_main", s, l, f, t) for s in ("sig", "no sig") for l in ("plain", "rare", "rare + gv")
+                for f in ("ray table", "point table", "probes") for t in ("top", "flat")]
+
+
+def launch_compared():
+    """(GPU test, scene builder, context kind, the launches of the test as (kernel, extra cell parts)): every entry calls the builder, and
+    takes the parameters from the list, that the GPU test itself uses."""
+    import test_gpu_query_forms as qf
+    import test_gpu_ray_table as ray_table
+    out = []
+    for (form, which), case_id in zip(qf.CASES, qf.CASE_IDS):
+        make = (lambda form=form: form_scene(*form))
+        out.append((f"test_gpu_query_forms.py::test_closest_hits[{case_id}]", make, which, [("rq_intersect", "resolve"), ("rq_intersect", "visibility")]))
+        out.append((f"test_gpu_query_forms.py::test_any_hit_scalar_interval[{case_id}]", make, which, [("rq_occluded",)]))
+        out.append((f"test_gpu_query_forms.py::test_any_hit_per_ray_t_max[{case_id}]", make, which, [("rq_occluded",)]))
+        out.append((f"test_gpu_query_forms.py::test_hemisphere_occlusion[{case_id}]", make, which, [("rq_hemi",)]))
+    both = lambda f: [("wf_main", "sig", f), ("wf_main", "no sig", f)]      # each of these tests renders with and without signatures
+    for name, (make, _) in ray_table.SCENES.items():
+        out.append((f"test_gpu_ray_table.py::test_against_the_oracle[{name}-fan-aa]", make, "gpu_ctx", both("ray table")))
+        out.append((f"test_gpu_point_table.py::test_against_the_oracle[{name}-1]", make, "gpu_ctx", both("point table")))
+        out.append((f"test_gpu_probes.py::test_mean_against_the_oracle[{name}]", make, "gpu_ctx", both("probes")))
+    return out
+
+
+def test_census_every_query_and_table_form_is_compared_with_the_oracle(shim):
+    assert len(LAUNCH_CELLS) == 16 + 8 + 8 + 36 and len(set(LAUNCH_CELLS)) == len(LAUNCH_CELLS)
+    reached = {cell: [] for cell in LAUNCH_CELLS}
+    cells = {}
+    for test, make, context, launches in launch_compared():
+        if (make, context) not in cells:
+            flat = make().flatten()
+            b = Blob(shim, flat.desc)
+            assert b.rc == abi.MI_OK, (test, b.err)
+            cells[(make, context)] = (query_cell(b, context), table_cell(b))
+            b.close()
+        qc, tc = cells[(make, context)]
+        for launch in launches:
+            cell = (launch[0], launch[1], tc[0], launch[2], tc[1]) if launch[0] == "wf_main" else (launch[0], *qc, *launch[1:])
+            reached[cell].append(test)
+    for cell, tests in reached.items():
+        print(f"{' / '.join(cell)}: {tests[0] if tests else 'NOT REACHED'}" + (f" (+{len(tests) - 1})" if len(tests) > 1 else ""))
+    assert not [cell for cell, tests in reached.items() if not tests]
+
+
+def test_table_scenes_compile_to_the_forms_they_are_there_for(shim):
+    import test_gpu_ray_table as ray_table
+    want = {"rare_top": ((0, 0, 0, 0), ("rare", "top")), "gv_top": ((1, 1, 0, 1312), ("rare + gv", "top")),
+            "gv_mesh_top": ((2, 1, 1, 28160), ("rare + gv", "top"))}
+    for name, (tup, cell) in want.items():
+        sc = ray_table.SCENES[name][0]()
+        b = Blob(shim, sc.flatten().desc)
+        assert b.rc == abi.MI_OK, (name, b.err)
+        assert (b.top_meshf, b.info.gen_volumes, b.n_meshes, b.info.lds_bytes) == tup and table_cell(b) == cell, name
+        assert b.n_list_lin < b.n_list_tri                                             # some Triangles sit in the tree
+        if name == "rare_top":
+            assert (b.n_list_plane, b.n_list_volume) == (1, 1)
+        b.close()
+
+
+def test_query_form_scenes_and_the_fate_of_their_waves(shim):
+    """The 18 scenes of tests/test_gpu_query_forms.py compile to the tuples that module relies on, and its rays take every branch of the
+    tree walk's entry — counted with the tree's own constants, read from the blob, through the restated two_stage_pad:
+      rq_intersect (fallback on ballot(!covered)): at t_max = 100 the 8 waves of group A walk the tree and the 8 of group B take the
+      plain loop; at +inf every wave takes the plain loop.
+      rq_occluded (fallback on ballot(!covered & !done)): both kinds at t_max = 100 too; of the per-ray waves every (a) wave takes the
+      plain loop, every (b) wave walks the tree although half of its lanes are not covered, every (c) wave leaves before the tree."""
+    import ray_batteries as rb
+    import test_gpu_query_forms as qf
+    for form in FORMS:
+        kind, meshes, top = form
+        sc = form_scene(*form)
+        b = Blob(shim, sc.flatten().desc)
+        assert b.rc == abi.MI_OK, (form, b.err)
+        assert (b.top_meshf >= 0) == top and (b.info.gen_volumes == 1) == (kind == "gv") and b.info.gen_volumes in (0, 1), form
+        assert b.n_meshes == (1 if meshes != "none" else 0), form
+        assert (0 < b.info.lds_bytes <= 28160) if meshes != "none" else (b.n_meshes == 0), form
+        o, d, groups = qf.aimed_rays(sc)
+        po, pd, ptm, wave_kinds = qf.per_ray_waves(sc, o, d, groups)
+        front = qf.front_triangles(sc)
+        what = qf.form_id(*form)
+        if not top:
+            assert b.top_meshf < 0 and len(front) == b.n_list_tri == 2, form
+            stopped = qf.front_stops(sc, po, pd, 0.001, ptm).reshape(-1, 64)
+            assert wave_kinds == ["a"] * 4 + ["c"] * 2 and not stopped[:4].any() and stopped[4:].all(), form
+            b.close()
+            continue
+        assert (b.n_list_lin, b.n_list_tri) == (1, 102), form
+        assert [int(k) for k in b.host_list[:b.n_list_lin]["index"]] == front, form         # the restated front is the compiler's
+        fc = b.meshf[b.top_meshf]
+        fconst = {"E2": float(fc["E2"]), "L": float(fc["L"]), "c": [float(x) for x in fc["c"]], "R": float(fc["R"])}
+        b.close()
+        n_a, n_b = (groups["A"].stop - groups["A"].start) // 64, (groups["B"].stop - groups["B"].start) // 64
+        for t_min, t_max, _ in qf.CALLS:
+            closest = qf.closest_wave_fates(fconst, o, d, t_max)
+            anyhit = qf.wave_fates(sc, fconst, o, d, t_min, t_max)
+            cov = rb.two_stage_covered(fconst, o, d, t_max)
+            print(f"{what} t_max {t_max}: rq_intersect waves {({k: closest.count(k) for k in ('tree', 'plain')})}, rq_occluded waves "
+                  f"{({k: anyhit.count(k) for k in ('tree', 'plain', 'leaves')})}, covered rays A {int(cov[groups['A']].sum())} B {int(cov[groups['B']].sum())}")
+            if t_max == 100.0:
+                assert closest[:n_a] == ["tree"] * n_a and closest[n_a:n_a + n_b] == ["plain"] * n_b, (form, closest)
+                assert cov[groups["B"]].mean() >= 0.5                                    # the plain loop is the wave's doing, not every lane's
+                assert anyhit.count("tree") >= 8 and anyhit.count("plain") >= 8, (form, anyhit)
+            if t_max == qf.INF:
+                assert set(closest) == {"plain"} and "tree" not in anyhit, (form, t_max)
+        fates = qf.wave_fates(sc, fconst, po, pd, 0.001, ptm)
+        print(f"{what} per-ray t_max: waves {list(zip(wave_kinds, fates))}")
+        assert fates == [{"a": "plain", "b": "tree", "c": "leaves"}[k] for k in wave_kinds], (form, fates)
+        cov = rb.two_stage_covered(fconst, po, pd, ptm).reshape(-1, 64)
+        for w, k in enumerate(wave_kinds):
+            assert not cov[w, 0::2].any(), (form, w)                                     # the +inf lanes are refused
+            if k == "b":
+                assert cov[w, 1::2].all(), (form, w)                                     # the lanes that walk the tree are covered
