@@ -18,7 +18,7 @@ from .geometry import ConvexVolume, Intersectable, Plane, Sphere, StaticMesh, Tr
 from .texture import Texture  # noqa: F401
 from .tracing import Camera, CameraProjectionMode, Context, MultiContext, Scene, ShadingMode, compact_size  # noqa: F401
 from .tracing import check_ray_table, equirect_dirs, equirect_ray_table  # noqa: F401
-from .tracing import check_point_table, lightmap_texels  # noqa: F401
+from .tracing import check_point_table, lightmap_jitter, lightmap_texels  # noqa: F401
 from .tracing import check_probe_table, probe_grid, sh9_basis, sh9_irradiance  # noqa: F401
 
 __all__ = [

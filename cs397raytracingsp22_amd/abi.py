@@ -27,6 +27,7 @@ MI_VARIANT_DEFAULT, MI_VARIANT_SIMPLE, MI_VARIANT_VOTED, MI_VARIANT_VOTED_DIAG =
 MI_VARIANT_WAVEFRONT, MI_VARIANT_RECURSIVE = 7, 8
 MI_OPT_NO_TILE_MASKS, MI_OPT_REFERENCE_WALK, MI_OPT_TWO_STAGE, MI_OPT_NO_LIST_TREE = 1, 2, 4, 8
 MI_HEMI_WORLD_RADIUS = 1   # mi_hemisphere_occlusion flags: t_max is a world-space radius
+MI_LM_JITTER = 1           # mi_lightmap_texels / mi_bake_lightmap flags: one jittered position per row instead of the texel centre
 
 f3 = C.c_float * 3
 f16 = C.c_float * 16
@@ -117,6 +118,7 @@ EXPORTS = [
     "mi_render_rays", "mi_render_rays_device",
     "mi_render_points", "mi_render_points_device",
     "mi_render_probes", "mi_render_probes_device",
+    "mi_lightmap_texels", "mi_lightmap_texels_device", "mi_bake_lightmap",
     "mi_multi_create", "mi_multi_create_loopback", "mi_multi_destroy", "mi_multi_device_count", "mi_multi_context", "mi_multi_scene_upload", "mi_multi_reserve", "mi_multi_render",
 ]
 
@@ -223,6 +225,16 @@ def load() -> C.CDLL:
     lib.mi_render_probes_device.argtypes = [vp, C.POINTER(mi_camera_desc), C.POINTER(mi_render_opts), vp, C.c_uint32,
                                             C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp, C.POINTER(mi_stats)]
     lib.mi_render_probes_device.restype = C.c_int
+    # lightmap atlas (added within ABI 5): mesh, width, height, rows, flags, seed, offset, out_points, out_normals, out_triangle (, stream);
+    # the bake: cam, opts, mesh, flags, offset, then mi_render's outputs with out_triangle before the stats
+    lib.mi_lightmap_texels.argtypes = [vp, C.POINTER(mi_mesh), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_float,
+                                       vp, vp, vp]
+    lib.mi_lightmap_texels.restype = C.c_int
+    lib.mi_lightmap_texels_device.argtypes = lib.mi_lightmap_texels.argtypes + [vp]
+    lib.mi_lightmap_texels_device.restype = C.c_int
+    lib.mi_bake_lightmap.argtypes = [vp, C.POINTER(mi_camera_desc), C.POINTER(mi_render_opts), C.POINTER(mi_mesh), C.c_uint32, C.c_float,
+                                     vp, vp, vp, vp, C.POINTER(mi_stats)]
+    lib.mi_bake_lightmap.restype = C.c_int
     lib.mi_multi_create.argtypes = [C.c_int, C.POINTER(C.c_int), C.POINTER(vp)]
     lib.mi_multi_create.restype = C.c_int
     lib.mi_multi_create_loopback.argtypes = [C.c_int, C.c_int, C.POINTER(vp)]

@@ -55,6 +55,8 @@ hipError_t launch_sh_unpermute(const float* gathered, float* image, uint32_t wid
                                uint32_t world, uint32_t tiles_padded, hipStream_t stream);
 hipError_t launch_tonemap(const float* image, uint8_t* out, uint32_t n_pixels, float inv_gamma, hipStream_t stream);
 hipError_t launch_selftest_rcp(unsigned long long* d_mismatches, hipStream_t stream);
+hipError_t launch_lm_count(const LmArgs& a, hipStream_t stream);
+hipError_t launch_lm_resolve(const LmArgs& a, hipStream_t stream);
 }  // namespace pt
 
 using namespace pt;
@@ -112,6 +114,13 @@ struct mi_ctx {
     void* d_rq = nullptr; size_t rq_bytes = 0;               // ray queries, host-pointer forms: rays and results of one chunk (its own buffer: never the pipeline's)
     void* d_rays = nullptr; size_t rays_bytes = 0;           // mi_render_rays / mi_render_points: the uploaded table, origins then dirs / points then normals (its own buffer too)
     void* d_sh = nullptr; size_t sh_bytes = 0;               // mi_render_probes: the compact SH records, then the un-permuted [H][W][9][3] plane
+    // mi_lightmap_texels: the bins' counters and offsets, the bins' list (grown on demand, never the buffers mi_reserve sized), the pinned
+    // word lm_scan leaves the list's full length in, and mi_lightmap_texels' / mi_bake_lightmap's uploaded mesh and triangle plane
+    void* d_lm_hdr = nullptr; size_t lm_hdr_bytes = 0;
+    void* d_lm_list = nullptr; size_t lm_list_bytes = 0;
+    unsigned long long* h_lm_total = nullptr; unsigned long long* h_lm_total_dev = nullptr;
+    void* d_lm_mesh = nullptr; size_t lm_mesh_bytes = 0;
+    void* d_lm_out = nullptr; size_t lm_out_bytes = 0;
     hipEvent_t ev_t0 = nullptr, ev_t1 = nullptr;     // mi_render's whole-call timer
     bool big_lds_enabled = false;                    // wf_trav_i<1024>'s > 64 KB dynamic-LDS opt-in, set on THIS context's device
     // wavefront pipeline buffers
@@ -266,6 +275,11 @@ extern "C" void mi_ctx_destroy(mi_ctx* c) {
     if (c->d_rq) (void)hipFree(c->d_rq);
     if (c->d_rays) (void)hipFree(c->d_rays);
     if (c->d_sh) (void)hipFree(c->d_sh);
+    if (c->d_lm_hdr) (void)hipFree(c->d_lm_hdr);
+    if (c->d_lm_list) (void)hipFree(c->d_lm_list);
+    if (c->h_lm_total) (void)hipHostFree(c->h_lm_total);
+    if (c->d_lm_mesh) (void)hipFree(c->d_lm_mesh);
+    if (c->d_lm_out) (void)hipFree(c->d_lm_out);
     if (c->d_wf_a) (void)hipFree(c->d_wf_a);
     if (c->d_wf_b) (void)hipFree(c->d_wf_b);
     if (c->d_wf_samp) (void)hipFree(c->d_wf_samp);
@@ -1143,6 +1157,153 @@ extern "C" int mi_render_points_device(mi_ctx* c, const mi_camera_desc* cam, con
                                        void* d_accum_f32x4, void* d_compact_f32, void* d_sig_u32, void* stream, mi_stats* stats) {
     return render_table_device(c, cam, opts, d_points, d_normals, rows_per_pixel, kTablePoints, sample_begin, sample_end, d_accum_f32x4,
                                d_compact_f32, d_sig_u32, stream, stats);
+}
+
+// ------------------------------------------------------------------ lightmap atlas (the point table of a mesh's uv atlas, made on the GPU)
+// tracing.py lightmap_texels as kernels: the table mi_render_points reads is made in HBM from the mesh, one row or one jittered row per
+// sample.  The arguments are checked before the context, so that a caller's mistakes are reported the same with and without a device.
+static int check_lm_args(const char* who, mi_ctx* c, const mi_mesh* mesh, uint32_t width, uint32_t height, uint32_t rows, uint32_t flags,
+                         float offset, const void* out_points, const void* out_normals) {
+    if (!mesh) return fail(MI_ERR_INVALID, "%s: mesh is NULL", who);
+    if (mesh->n_vertices < 0 || mesh->n_triangles < 0) return fail(MI_ERR_INVALID, "%s: negative n_vertices / n_triangles", who);
+    if ((mesh->n_vertices > 0 && (!mesh->positions || !mesh->normals || !mesh->texcoords)) || (mesh->n_triangles > 0 && !mesh->indices))
+        return fail(MI_ERR_INVALID, "%s: the mesh's positions, normals, texcoords and indices are required", who);
+    if (!out_points || !out_normals) return fail(MI_ERR_INVALID, "%s: out_points and out_normals are required", who);
+    if (width == 0 || width > 32768u || height == 0 || height > 32768u)
+        return fail(MI_ERR_INVALID, "%s: width %u / height %u is not in 1 .. 32768", who, width, height);
+    if (rows == 0 || rows > 65535u) return fail(MI_ERR_INVALID, "%s: rows %u is not in 1 .. 65535", who, rows);
+    if (flags & ~(uint32_t)MI_LM_JITTER) return fail(MI_ERR_INVALID, "%s: unknown flag bits 0x%x", who, flags & ~(uint32_t)MI_LM_JITTER);
+    if (offset != offset) return fail(MI_ERR_INVALID, "%s: offset is NaN", who);
+    if (3ull * width * height > (1ull << 31))
+        return fail(MI_ERR_INVALID, "%s: 3 * width * height = %llu exceeds 2^31 (the jitter streams' keys end at 3 W H)", who, 3ull * width * height);
+    if (!c) return fail(MI_ERR_INVALID, "ctx is NULL");
+    return MI_OK;
+}
+
+static int check_lm_indices(const char* who, const mi_mesh* mesh) {
+    for (size_t i = 0; i < 3 * (size_t)mesh->n_triangles; i++)
+        if (mesh->indices[i] >= (uint32_t)mesh->n_vertices)
+            return fail(MI_ERR_INVALID, "%s: index %u of triangle %zu is outside the %d vertices", who, mesh->indices[i], i / 3, mesh->n_vertices);
+    return MI_OK;
+}
+
+// Queue the kernels on `stream`; `mesh`'s arrays and the outputs are device pointers.  exact: wait for the count pass and size the bins'
+// list to its sum (the blocking forms); otherwise size it from what the previous call needed and never wait — a list that turns out too
+// short costs time, not correctness (LmArgs).  Growing a buffer frees the old one, which waits for the device.
+static int lightmap_texels_device(mi_ctx* c, const mi_mesh* mesh, uint32_t width, uint32_t height, uint32_t rows, uint32_t flags, uint32_t seed,
+                                  float offset, float* d_points, float* d_normals, int32_t* d_triangle, hipStream_t stream, bool exact) {
+    LmArgs a;
+    a.positions = mesh->positions; a.normals = mesh->normals; a.texcoords = mesh->texcoords; a.indices = mesh->indices;
+    a.n_vertices = (uint32_t)mesh->n_vertices; a.n_triangles = (uint32_t)mesh->n_triangles;
+    a.width = width; a.height = height; a.rows = rows; a.jitter = (flags & MI_LM_JITTER) ? 1u : 0u;
+    a.seed_key = seed_key(seed);
+    a.tiles_x = (width + kTile - 1) / kTile; a.tiles_y = (height + kTile - 1) / kTile;
+    double M[3][4];
+    for (int r = 0; r < 3; r++) for (int k = 0; k < 4; k++) a.m[4 * r + k] = M[r][k] = (double)mesh->transform[4 * k + r];     // column-major
+    const double cof[9] = { M[1][1] * M[2][2] - M[1][2] * M[2][1], M[1][2] * M[2][0] - M[1][0] * M[2][2], M[1][0] * M[2][1] - M[1][1] * M[2][0],
+                            M[0][2] * M[2][1] - M[0][1] * M[2][2], M[0][0] * M[2][2] - M[0][2] * M[2][0], M[0][1] * M[2][0] - M[0][0] * M[2][1],
+                            M[0][1] * M[1][2] - M[0][2] * M[1][1], M[0][2] * M[1][0] - M[0][0] * M[1][2], M[0][0] * M[1][1] - M[0][1] * M[1][0] };
+    const double det = M[0][0] * cof[0] + M[0][1] * cof[1] + M[0][2] * cof[2];
+    for (int k = 0; k < 9; k++) a.nm[k] = cof[k] / det;          // the inverse transpose; a singular transform leaves no finite normal: every texel empty
+    a.offset = (double)offset;
+    a.out_points = d_points; a.out_normals = d_normals; a.out_triangle = d_triangle;
+
+    const size_t nt = (size_t)a.tiles_x * a.tiles_y;
+    if (!c->h_lm_total) {
+        HIP_TRY(hipHostMalloc((void**)&c->h_lm_total, sizeof(unsigned long long), hipHostMallocMapped | hipHostMallocCoherent));
+        *c->h_lm_total = 0;
+        HIP_TRY(hipHostGetDevicePointer((void**)&c->h_lm_total_dev, c->h_lm_total, 0));
+    }
+    MI_TRY(ensure(&c->d_lm_hdr, &c->lm_hdr_bytes, nt * 8 + (nt + 1) * 8));
+    a.counts = (uint32_t*)c->d_lm_hdr; a.cursors = a.counts + nt; a.offsets = (unsigned long long*)(a.cursors + nt);
+    a.host_total = c->h_lm_total_dev;
+    const unsigned long long kMaxList = 1ull << 30;               // entries: 4 GiB; bins beyond it are resolved from the whole mesh
+    auto size_list = [&](unsigned long long entries) {
+        MI_TRY(ensure(&c->d_lm_list, &c->lm_list_bytes, (size_t)std::max<unsigned long long>(1, std::min(entries, kMaxList)) * sizeof(uint32_t)));
+        a.list = (uint32_t*)c->d_lm_list; a.cap = c->lm_list_bytes / sizeof(uint32_t);
+        return (int)MI_OK;
+    };
+    if (!exact) {
+        const unsigned long long last = *(volatile unsigned long long*)c->h_lm_total;      // what the previous call's bins held: a hint only
+        MI_TRY(size_list(std::min<unsigned long long>((unsigned long long)a.n_triangles * nt, std::max<unsigned long long>(last, 4ull * a.n_triangles + 1024))));
+    }
+    HIP_TRY(hipEventRecord(c->ev_start, stream));
+    HIP_TRY(hipMemsetAsync(c->d_lm_hdr, 0, nt * 8, stream));
+    HIP_TRY(launch_lm_count(a, stream));
+    if (exact) {
+        HIP_TRY(hipStreamSynchronize(stream));
+        MI_TRY(size_list(*(volatile unsigned long long*)c->h_lm_total));
+    }
+    HIP_TRY(launch_lm_resolve(a, stream));
+    HIP_TRY(hipEventRecord(c->ev_stop, stream));
+    c->ev_recorded = true; c->ms_summed = false;
+    return MI_OK;
+}
+
+extern "C" int mi_lightmap_texels_device(mi_ctx* c, const mi_mesh* mesh, uint32_t width, uint32_t height, uint32_t rows, uint32_t flags,
+                                         uint32_t seed, float offset, float* out_points, float* out_normals, int32_t* out_triangle, void* stream) {
+    MI_TRY(check_lm_args("mi_lightmap_texels_device", c, mesh, width, height, rows, flags, offset, out_points, out_normals));
+    HIP_TRY(hipSetDevice(c->device));
+    return lightmap_texels_device(c, mesh, width, height, rows, flags, seed, offset, out_points, out_normals, out_triangle, (hipStream_t)stream, false);
+}
+
+// The mesh's four arrays into the context's mesh buffer (on c->stream); `dev` is `mesh` with device pointers
+static int upload_lm_mesh(mi_ctx* c, const mi_mesh* mesh, mi_mesh* dev) {
+    const size_t nv = (size_t)mesh->n_vertices, ni = 3 * (size_t)mesh->n_triangles;
+    const size_t off[5] = { 0, nv * 12, nv * 24, nv * 32, nv * 32 + ni * 4 };
+    MI_TRY(ensure(&c->d_lm_mesh, &c->lm_mesh_bytes, std::max<size_t>(off[4], 16)));
+    const void* src[4] = { mesh->positions, mesh->normals, mesh->texcoords, mesh->indices };
+    for (int k = 0; k < 4; k++)
+        if (off[k + 1] > off[k]) HIP_TRY(hipMemcpyAsync((char*)c->d_lm_mesh + off[k], src[k], off[k + 1] - off[k], hipMemcpyHostToDevice, c->stream));
+    *dev = *mesh;
+    dev->positions = (const float*)((char*)c->d_lm_mesh + off[0]); dev->normals = (const float*)((char*)c->d_lm_mesh + off[1]);
+    dev->texcoords = (const float*)((char*)c->d_lm_mesh + off[2]); dev->indices = (const uint32_t*)((char*)c->d_lm_mesh + off[3]);
+    return MI_OK;
+}
+
+extern "C" int mi_lightmap_texels(mi_ctx* c, const mi_mesh* mesh, uint32_t width, uint32_t height, uint32_t rows, uint32_t flags, uint32_t seed,
+                                  float offset, float* out_points, float* out_normals, int32_t* out_triangle) {
+    MI_TRY(check_lm_args("mi_lightmap_texels", c, mesh, width, height, rows, flags, offset, out_points, out_normals));
+    MI_TRY(check_lm_indices("mi_lightmap_texels", mesh));
+    HIP_TRY(hipSetDevice(c->device));
+    mi_mesh dev;
+    MI_TRY(upload_lm_mesh(c, mesh, &dev));
+    const size_t n = (size_t)rows * height * width;
+    MI_TRY(ensure(&c->d_lm_out, &c->lm_out_bytes, n * (out_triangle ? 28 : 24)));
+    float* d_points = (float*)c->d_lm_out; float* d_normals = d_points + 3 * n;
+    int32_t* d_triangle = out_triangle ? (int32_t*)(d_normals + 3 * n) : nullptr;
+    MI_TRY(lightmap_texels_device(c, &dev, width, height, rows, flags, seed, offset, d_points, d_normals, d_triangle, c->stream, true));
+    HIP_TRY(hipMemcpyAsync(out_points, d_points, n * 12, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(out_normals, d_normals, n * 12, hipMemcpyDeviceToHost, c->stream));
+    if (out_triangle) HIP_TRY(hipMemcpyAsync(out_triangle, d_triangle, n * 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return MI_OK;
+}
+
+// The whole bake: the mesh up, its table made in the context's table buffer (mi_render_rays'), then mi_render_points' body on it.
+extern "C" int mi_bake_lightmap(mi_ctx* c, const mi_camera_desc* cam, const mi_render_opts* opts, const mi_mesh* mesh, uint32_t flags,
+                                float offset, float* out_rgb_f32, uint8_t* out_rgb_u8, uint32_t* out_sig, int32_t* out_triangle, mi_stats* stats) {
+    if (!c) return fail(MI_ERR_INVALID, "ctx is NULL");
+    if (!mesh) return fail(MI_ERR_INVALID, "mi_bake_lightmap: mesh is NULL");
+    const uint32_t rows = (cam && (flags & MI_LM_JITTER)) ? cam->aa_sample_count : 1u;
+    MI_TRY(check_table_args(c, cam, opts, (const float*)mesh, (const float*)mesh, rows, kTablePoints));       // (the tables are made here: any non-NULL)
+    if (opts->rank != 0 || opts->world != 1) return fail(MI_ERR_INVALID, "mi_bake_lightmap renders a whole image: rank/world must be 0/1");
+    const uint32_t W = cam->screen_width, H = cam->screen_height;
+    MI_TRY(check_lm_args("mi_bake_lightmap", c, mesh, W, H, rows, flags, offset, mesh, mesh));
+    MI_TRY(check_lm_indices("mi_bake_lightmap", mesh));
+    HIP_TRY(hipSetDevice(c->device));
+    mi_mesh dev;
+    MI_TRY(upload_lm_mesh(c, mesh, &dev));
+    const size_t n = (size_t)rows * H * W, bytes = n * 3 * sizeof(float);
+    MI_TRY(ensure(&c->d_rays, &c->rays_bytes, 2 * bytes));
+    if (out_triangle) MI_TRY(ensure(&c->d_lm_out, &c->lm_out_bytes, n * 4));
+    float* d_points = (float*)c->d_rays; float* d_normals = (float*)((char*)c->d_rays + bytes);
+    MI_TRY(lightmap_texels_device(c, &dev, W, H, rows, flags, opts->seed, offset, d_points, d_normals, out_triangle ? (int32_t*)c->d_lm_out : nullptr,
+                                  c->stream, true));
+    if (out_triangle) HIP_TRY(hipMemcpyAsync(out_triangle, c->d_lm_out, n * 4, hipMemcpyDeviceToHost, c->stream));
+    const RayTable table = { d_points, d_normals, rows, kTablePoints, nullptr };
+    const mi_camera_desc tc = table_camera(cam);
+    return render_image(c, &tc, opts, &table, out_rgb_f32, out_rgb_u8, out_sig, stats);
 }
 
 // ------------------------------------------------------------------ light probes (SH L2 radiance probes: the directions are drawn on the GPU)

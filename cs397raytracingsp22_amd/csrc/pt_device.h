@@ -386,4 +386,33 @@ struct WalkerPlan {
     uint32_t blocks_per_cu;
 };
 
+// ---- lightmap atlas (mi_lightmap_texels; pt_kernels.hip "lm_*") ----
+// A single-index triangle mesh's uv atlas rasterised into the point and normal tables of mi_render_points.  Triangles are binned to
+// kTile x kTile-texel tiles (lm_bin counts, lm_scan sums, lm_bin fills), then lm_resolve runs one block per tile.
+// Scratch: counts[tiles] cursors[tiles] (u32, zeroed per call) offsets[tiles + 1] (u64) and list[cap] (u32).  A tile whose list does not
+// lie inside [0, cap) is resolved by testing every triangle of the mesh instead: cap changes the speed, never the result.
+struct LmArgs {
+    const float*    positions;       // [n_vertices][3]
+    const float*    normals;         // [n_vertices][3]
+    const float*    texcoords;       // [n_vertices][2]
+    const uint32_t* indices;         // [n_triangles][3]
+    uint32_t n_vertices, n_triangles;
+    uint32_t width, height, rows;
+    uint32_t jitter;                 // MI_LM_JITTER: row r of texel (x, y) draws (jx, jy) from the stream (seed, 2 W H + y W + x, r)
+    uint32_t seed_key;
+    uint32_t tiles_x, tiles_y;
+    double   m[12];                  // mi_mesh.transform, rows of its upper 3 x 4, promoted to f64
+    double   nm[9];                  // inverse transpose of its upper 3 x 3, row-major, computed in f64
+    double   offset;
+    uint32_t* counts;
+    uint32_t* cursors;
+    unsigned long long* offsets;
+    uint32_t* list;
+    unsigned long long cap;
+    unsigned long long* host_total;  // pinned, device-mapped: the sum of the counts, for sizing the list
+    float*   out_points;             // [rows][H][W][3]
+    float*   out_normals;            // [rows][H][W][3]
+    int32_t* out_triangle;           // [rows][H][W] or nullptr
+};
+
 }  // namespace pt

@@ -3575,7 +3575,223 @@ __global__ __launch_bounds__(256) void selftest_rcp(unsigned long long* mismatch
     if (bad) atomicAdd(mismatches, bad);
 }
 
+// ---------------------------------------------------------------- lightmap atlas (mi_lightmap_texels)
+// tracing.py lightmap_texels on the device, sample by sample: which triangle of the uv atlas covers the sample (the lowest index whose three
+// f64 edge functions are >= 0), then position and normal interpolated, transformed, normalised and offset in f64 and rounded once to f32.
+// Every decision is the helper's f64 expression, operation by operation, with no contraction into FMA, so a sample on an edge decides the
+// same way on both sides.  Nothing here is ordered by scheduling: the bins are unordered sets and the winner is an integer minimum.
+#pragma clang fp contract(off)
+
+// The triangle's uv corners (ua, va, ub, vb, uc, vc) and the sign of its uv area; false when it covers nothing (an index outside the
+// vertex arrays, which are then not read; no area, or a non-finite one: NaN and infinite texcoords end here).
+__device__ __forceinline__ bool lm_triangle(const LmArgs& a, uint32_t tri, double* uv, double& sgn, uint32_t* idx) {
+    idx[0] = a.indices[3 * (size_t)tri]; idx[1] = a.indices[3 * (size_t)tri + 1]; idx[2] = a.indices[3 * (size_t)tri + 2];
+    if (idx[0] >= a.n_vertices || idx[1] >= a.n_vertices || idx[2] >= a.n_vertices) return false;
+    for (int k = 0; k < 3; k++) {
+        uv[2 * k] = (double)a.texcoords[2 * (size_t)idx[k]];
+        uv[2 * k + 1] = (double)a.texcoords[2 * (size_t)idx[k] + 1];
+    }
+    const double area = (uv[2] - uv[0]) * (uv[5] - uv[1]) - (uv[3] - uv[1]) * (uv[4] - uv[0]);
+    if (area == 0.0 || !(fabs(area) <= 1.7976931348623157e308)) return false;
+    sgn = area > 0.0 ? 1.0 : -1.0;
+    return true;
+}
+// The texels whose samples can lie in the triangle's uv box, one texel of slack on every side (a sample lies anywhere in its texel, and
+// the edge functions decide, not the box): x0 <= x <= x1, y0 <= y <= y1, clamped to the atlas; false when the box misses it.
+__device__ __forceinline__ bool lm_texel_box(const LmArgs& a, const double* uv, int& x0, int& x1, int& y0, int& y1) {
+    const double W = (double)a.width, H = (double)a.height;
+    const double fx0 = floor(fmin(uv[0], fmin(uv[2], uv[4])) * W) - 1.0, fx1 = floor(fmax(uv[0], fmax(uv[2], uv[4])) * W) + 1.0;
+    const double fy0 = floor((1.0 - fmax(uv[1], fmax(uv[3], uv[5]))) * H) - 1.0, fy1 = floor((1.0 - fmin(uv[1], fmin(uv[3], uv[5]))) * H) + 1.0;
+    if (!(fx1 >= 0.0 && fx0 <= W - 1.0 && fy1 >= 0.0 && fy0 <= H - 1.0)) return false;
+    x0 = (int)fmax(fx0, 0.0); x1 = (int)fmin(fx1, W - 1.0);
+    y0 = (int)fmax(fy0, 0.0); y1 = (int)fmin(fy1, H - 1.0);
+    return true;
+}
+// The helper's three edge functions: the weights of a, b and c, times |area|
+__device__ __forceinline__ void lm_edges(const double* uv, double sgn, double u, double v, double& ea, double& eb, double& ec) {
+    ea = ((uv[2] - u) * (uv[5] - v) - (uv[3] - v) * (uv[4] - u)) * sgn;
+    eb = ((uv[4] - u) * (uv[1] - v) - (uv[5] - v) * (uv[0] - u)) * sgn;
+    ec = ((uv[0] - u) * (uv[3] - v) - (uv[1] - v) * (uv[2] - u)) * sgn;
+}
+
+constexpr int kLmSelf = 8;           // lm_bin: a lane walks a tile box of at most this many tiles itself; the block shares a larger one
+
+// Count (FILL = false) or fill (true) the tiles' bins: one lane per triangle.  No lane loops over a large box alone: boxes of more than
+// kLmSelf tiles are queued in LDS and walked by the whole block.
+template <bool FILL> __global__ __launch_bounds__(kBlock) void lm_bin(const LmArgs a) {
+    __shared__ uint32_t s_big[kBlock][4];        // triangle, first tile, box width in tiles, tiles in the box
+    __shared__ uint32_t s_nbig;
+    if (threadIdx.x == 0) s_nbig = 0;
+    __syncthreads();
+    auto emit = [&](uint32_t tile, uint32_t tri) {
+        if (!FILL) { atomicAdd(&a.counts[tile], 1u); return; }
+        const unsigned long long pos = a.offsets[tile] + atomicAdd(&a.cursors[tile], 1u);
+        if (pos < a.cap) a.list[pos] = tri;
+    };
+    const uint32_t tri = blockIdx.x * (uint32_t)kBlock + threadIdx.x;
+    double uv[6], sgn;
+    uint32_t idx[3];
+    int x0, x1, y0, y1;
+    if (tri < a.n_triangles && lm_triangle(a, tri, uv, sgn, idx) && lm_texel_box(a, uv, x0, x1, y0, y1)) {
+        const uint32_t tx0 = (uint32_t)x0 / kTile, ty0 = (uint32_t)y0 / kTile;
+        const uint32_t w = (uint32_t)x1 / kTile - tx0 + 1u, n = w * ((uint32_t)y1 / kTile - ty0 + 1u);
+        if (n <= (uint32_t)kLmSelf) {
+            for (uint32_t i = 0; i < n; i++) emit((ty0 + i / w) * a.tiles_x + tx0 + i % w, tri);
+        } else {
+            const uint32_t q = atomicAdd(&s_nbig, 1u);
+            s_big[q][0] = tri; s_big[q][1] = ty0 * a.tiles_x + tx0; s_big[q][2] = w; s_big[q][3] = n;
+        }
+    }
+    __syncthreads();
+    const uint32_t nbig = s_nbig;
+    for (uint32_t q = 0; q < nbig; q++) {
+        const uint32_t t = s_big[q][0], first = s_big[q][1], w = s_big[q][2], n = s_big[q][3];
+        for (uint32_t i = threadIdx.x; i < n; i += (uint32_t)kBlock) emit(first + (i / w) * a.tiles_x + i % w, t);
+    }
+}
+
+// Exclusive prefix of the counts (one block): offsets[tiles + 1] in u64, the total to the host's pinned word as well.
+__global__ __launch_bounds__(1024) void lm_scan(const LmArgs a) {
+    __shared__ unsigned long long s_sum[1024];
+    const uint32_t nt = a.tiles_x * a.tiles_y, per = (nt + 1023u) / 1024u;
+    const uint32_t lo = min(nt, threadIdx.x * per), hi = min(nt, lo + per);
+    unsigned long long sum = 0;
+    for (uint32_t i = lo; i < hi; i++) sum += a.counts[i];
+    s_sum[threadIdx.x] = sum;
+    __syncthreads();
+    for (uint32_t d = 1; d < 1024u; d <<= 1) {              // inclusive scan of the threads' sums
+        const unsigned long long v = threadIdx.x >= d ? s_sum[threadIdx.x - d] : 0ull;
+        __syncthreads();
+        s_sum[threadIdx.x] += v;
+        __syncthreads();
+    }
+    unsigned long long run = s_sum[threadIdx.x] - sum;
+    for (uint32_t i = lo; i < hi; i++) { a.offsets[i] = run; run += a.counts[i]; }
+    if (threadIdx.x == 1023u) {
+        a.offsets[nt] = s_sum[1023];
+        *a.host_total = s_sum[1023];
+        __threadfence_system();
+    }
+}
+
+// One block per tile; a thread owns the texels (x, y + 8 k), k < 4, of the tile, row after row.  The tile's bin is staged through LDS 256
+// triangles at a time (corners, sign, index) and every thread keeps the lowest covering index of each of its samples in a register; it then
+// resolves its winners from the mesh.  Without MI_LM_JITTER the one row is written `rows` times.
+__global__ __launch_bounds__(kBlock) void lm_resolve(const LmArgs a) {
+    __shared__ double s_uv[6][kBlock];
+    __shared__ double s_sgn[kBlock];             // 0: the triangle covers nothing of this tile
+    __shared__ uint32_t s_tri[kBlock];
+    const uint32_t tile = blockIdx.x, tile_x = tile % a.tiles_x, tile_y = tile / a.tiles_x;
+    const uint32_t count = a.counts[tile];
+    const unsigned long long off = a.offsets[tile];
+    const bool binned = off + count <= a.cap;                     // else: every triangle of the mesh (the list was not written in full)
+    const uint32_t n_list = binned ? count : a.n_triangles;
+    const uint32_t x = tile_x * kTile + (threadIdx.x & 31u), ybase = tile_y * kTile + (threadIdx.x >> 5);
+    const int tx0 = (int)(tile_x * kTile), ty0 = (int)(tile_y * kTile);
+    const size_t plane = (size_t)a.width * a.height;
+    const uint32_t n_eval = a.jitter ? a.rows : 1u, n_copy = a.jitter ? 1u : a.rows;
+    for (uint32_t r = 0; r < n_eval; r++) {
+        double u[4], v[4];
+        uint32_t best[4];
+        for (int k = 0; k < 4; k++) {
+            const uint32_t y = ybase + 8u * k;
+            best[k] = 0xffffffffu;
+            float jx = 0.5f, jy = 0.5f;
+            if (a.jitter && x < a.width && y < a.height) {
+                Rng rng;
+                rng_init(rng, a.seed_key, 2u * a.width * a.height + y * a.width + x, r);
+                jx = gen01(rng); jy = gen01(rng);
+            }
+            u[k] = ((double)x + (double)jx) / (double)a.width;
+            v[k] = 1.0 - ((double)y + (double)jy) / (double)a.height;
+        }
+        for (uint32_t base = 0; base < n_list; base += (uint32_t)kBlock) {
+            __syncthreads();
+            {
+                double uv[6], sgn = 0.0;
+                uint32_t idx[3], tri = 0;
+                int x0, x1, y0, y1;
+                const uint32_t i = base + threadIdx.x;
+                if (i < n_list) {
+                    tri = binned ? a.list[off + i] : i;
+                    const bool in = lm_triangle(a, tri, uv, sgn, idx) && lm_texel_box(a, uv, x0, x1, y0, y1) &&
+                                    x1 >= tx0 && x0 < tx0 + kTile && y1 >= ty0 && y0 < ty0 + kTile;
+                    if (!in) sgn = 0.0;
+                }
+                for (int j = 0; j < 6; j++) s_uv[j][threadIdx.x] = sgn != 0.0 ? uv[j] : 0.0;
+                s_sgn[threadIdx.x] = sgn;
+                s_tri[threadIdx.x] = tri;
+            }
+            __syncthreads();
+            const uint32_t m = min((uint32_t)kBlock, n_list - base);
+            for (uint32_t j = 0; j < m; j++) {
+                const double sgn = s_sgn[j];
+                if (sgn == 0.0) continue;
+                const uint32_t tri = s_tri[j];
+                const double uv[6] = { s_uv[0][j], s_uv[1][j], s_uv[2][j], s_uv[3][j], s_uv[4][j], s_uv[5][j] };
+                for (int k = 0; k < 4; k++) {
+                    if (tri >= best[k]) continue;
+                    double ea, eb, ec;
+                    lm_edges(uv, sgn, u[k], v[k], ea, eb, ec);
+                    if (ea >= 0.0 && eb >= 0.0 && ec >= 0.0) best[k] = tri;
+                }
+            }
+        }
+        for (int k = 0; k < 4; k++) {
+            const uint32_t y = ybase + 8u * k;
+            if (x >= a.width || y >= a.height) continue;
+            float p[3] = { 0.0f, 0.0f, 0.0f }, n[3] = { 0.0f, 0.0f, 0.0f };
+            int32_t won = -1;
+            if (best[k] != 0xffffffffu) {
+                double uv[6], sgn, ea, eb, ec;
+                uint32_t idx[3];
+                (void)lm_triangle(a, best[k], uv, sgn, idx);
+                lm_edges(uv, sgn, u[k], v[k], ea, eb, ec);
+                const double tot = ea + eb + ec;
+                const double wa = ea / tot, wb = eb / tot, wc = ec / tot;
+                double P[3], N[3];
+                for (int i = 0; i < 3; i++) {
+                    P[i] = wa * (double)a.positions[3 * (size_t)idx[0] + i] + wb * (double)a.positions[3 * (size_t)idx[1] + i] +
+                           wc * (double)a.positions[3 * (size_t)idx[2] + i];
+                    N[i] = wa * (double)a.normals[3 * (size_t)idx[0] + i] + wb * (double)a.normals[3 * (size_t)idx[1] + i] +
+                           wc * (double)a.normals[3 * (size_t)idx[2] + i];
+                }
+                double Q[3], G[3];
+                for (int i = 0; i < 3; i++) {
+                    Q[i] = a.m[4 * i] * P[0] + a.m[4 * i + 1] * P[1] + a.m[4 * i + 2] * P[2] + a.m[4 * i + 3];
+                    G[i] = a.nm[3 * i] * N[0] + a.nm[3 * i + 1] * N[1] + a.nm[3 * i + 2] * N[2];
+                }
+                const double len = sqrt(G[0] * G[0] + G[1] * G[1] + G[2] * G[2]);
+                if (len > 0.0 && len <= 1.7976931348623157e308) {         // else (no length, NaN, infinite): an empty texel
+                    won = (int32_t)best[k];
+                    for (int i = 0; i < 3; i++) {
+                        const double g = G[i] / len;
+                        n[i] = (float)g;
+                        p[i] = (float)(Q[i] + a.offset * g);
+                    }
+                }
+            }
+            for (uint32_t c = 0; c < n_copy; c++) {
+                const size_t at = (size_t)(r + c) * plane + (size_t)y * a.width + x;
+                for (int i = 0; i < 3; i++) { a.out_points[3 * at + i] = p[i]; a.out_normals[3 * at + i] = n[i]; }
+                if (a.out_triangle) a.out_triangle[at] = won;
+            }
+        }
+    }
+}
+
 // ---------------------------------------------------------------- launch wrappers
+// lightmap atlas: count, scan, (the caller may size the list here,) fill, resolve
+hipError_t launch_lm_count(const LmArgs& a, hipStream_t stream) {
+    if (a.n_triangles) hipLaunchKernelGGL(lm_bin<false>, dim3((a.n_triangles + kBlock - 1) / kBlock), dim3(kBlock), 0, stream, a);
+    hipLaunchKernelGGL(lm_scan, dim3(1), dim3(1024), 0, stream, a);
+    return hipGetLastError();
+}
+hipError_t launch_lm_resolve(const LmArgs& a, hipStream_t stream) {
+    if (a.n_triangles) hipLaunchKernelGGL(lm_bin<true>, dim3((a.n_triangles + kBlock - 1) / kBlock), dim3(kBlock), 0, stream, a);
+    hipLaunchKernelGGL(lm_resolve, dim3(a.tiles_x * a.tiles_y), dim3(kBlock), 0, stream, a);
+    return hipGetLastError();
+}
 hipError_t launch_selftest_rcp(unsigned long long* d_mismatches, hipStream_t stream) {
     hipLaunchKernelGGL(selftest_rcp, dim3(4096), dim3(256), 0, stream, d_mismatches);
     return hipGetLastError();

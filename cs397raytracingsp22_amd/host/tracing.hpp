@@ -196,6 +196,23 @@ struct Scene : Intersectable {                         // tracing.rs:213-218; `i
         return img;
     }
 
+    // The lightmap of `mesh` through mi_bake_lightmap: its uv atlas, width x height texels, is rasterised on the GPU into the point table
+    // render_points would take and gathered with `samples` samples per texel, each from its own jittered position inside the texel
+    // (jitter) or all from the centre; `offset` lifts the points off the surface along the normal.  Of `mesh` the four arrays, the two
+    // counts and transform are read.  The camera supplies path_depth, max_trace_dist and gamma.
+    RgbImage bake_lightmap(const mi_mesh& mesh, uint32_t width, uint32_t height, uint32_t samples, bool jitter = true, float offset = 1e-3f,
+                           uint32_t seed = 1, int device = 0, mi_stats* stats = nullptr) const {
+        mi_camera_desc cam = camera.flatten();
+        cam.screen_width = width; cam.screen_height = height; cam.aa_sample_count = samples;
+        RgbImage img; img.width = width; img.height = height;
+        img.data.resize((size_t)width * height * 3);
+        mi_render_opts opts{}; opts.seed = seed; opts.rank = 0; opts.world = 1;
+        with_context(device, [&](mi_ctx* ctx) {
+            return mi_bake_lightmap(ctx, &cam, &opts, &mesh, jitter ? MI_LM_JITTER : 0u, offset, nullptr, img.data.data(), nullptr, nullptr, stats);
+        });
+        return img;
+    }
+
     // Light probes through mi_render_probes: points is [rows_per_pixel][H][W][3], one probe position per pixel, rows_per_pixel = 1 or
     // camera.aa_sample_count.  Sample s of probe (x, y) leaves its point along rand_sphere_vec (Isotropic::scatter's direction,
     // materials.rs:158-166: uniform over the sphere), drawn on the GPU from the stream (seed, W * H + y * W + x, s); its path draws from

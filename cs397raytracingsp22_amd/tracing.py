@@ -273,7 +273,47 @@ def probe_grid(lo, hi, counts, width: Optional[int] = None):
     return np.ascontiguousarray(pts.reshape(H, W, 3), np.float32), n
 
 
-def lightmap_texels(positions, normals, texcoords, indices, width: int, height: int, transform=None, offset: float = 0.0):
+def _lowbias32(x):
+    x = x ^ (x >> np.uint32(16)); x = x * np.uint32(0x7feb352d)
+    x = x ^ (x >> np.uint32(15)); x = x * np.uint32(0x846ca68b)
+    return x ^ (x >> np.uint32(16))
+
+
+def _rotl32(x, k: int):
+    return (x << np.uint32(k)) | (x >> np.uint32(32 - k))
+
+
+def lightmap_jitter(width: int, height: int, rows: int, seed: int) -> np.ndarray:
+    """The sample positions of a jittered lightmap atlas (MI_LM_JITTER), [rows, H, W, 2] float32 in [0, 1): (jx, jy) of row r of texel
+    (x, y) are the first two gen_range(0.0..1.0) draws of the fresh stream (seed, 2 W H + y W + x, r) — DESIGN.md "RNG" restated in numpy:
+    three rounds of lowbias32 key xoroshiro64**, a draw is bits(0x3f800000 | u32 >> 9) * 1 + (0 - 1).  The sample lies at
+    u = (x + jx) / W, v = 1 - (y + jy) / H; lightmap_texels(jitter=...) takes the array."""
+    W, H, R = int(width), int(height), int(rows)
+    if W < 1 or H < 1 or R < 1:
+        raise ValueError("width, height and rows must be >= 1")
+    if 3 * W * H > 1 << 31:
+        raise ValueError("3 * width * height exceeds 2^31: the jitter streams' keys end at 3 W H")
+    with np.errstate(over="ignore"):
+        u32 = np.uint32
+        k0 = _lowbias32(np.asarray(int(seed) & 0xffffffff, u32) ^ u32(0x68e31da4))
+        pixel = (2 * W * H + np.arange(W * H, dtype=np.int64)).astype(u32).reshape(1, H, W)
+        sample = np.arange(R, dtype=u32).reshape(R, 1, 1)
+        p0 = _lowbias32(pixel + k0)
+        p1 = _lowbias32(p0 ^ u32(0xb5297a4d))
+        s0 = _lowbias32(p0 + sample * u32(0x9e3779b9))
+        s1 = _lowbias32(p1 ^ (sample * u32(0x85ebca6b)))
+        s1 = np.where((s0 | s1) == 0, u32(1), s1)
+        out = np.empty((R, H, W, 2), np.float32)
+        for k in range(2):
+            word = _rotl32(s0 * u32(0x9e3779bb), 5) * u32(5)
+            s1 = s1 ^ s0
+            s0, s1 = _rotl32(s0, 26) ^ s1 ^ (s1 << u32(9)), _rotl32(s1, 13)
+            out[..., k] = (u32(0x3f800000) | (word >> u32(9))).view(np.float32) * np.float32(1.0) + np.float32(0.0 - 1.0)
+    return out
+
+
+def lightmap_texels(positions, normals, texcoords, indices, width: int, height: int, transform=None, offset: float = 0.0, jitter=None,
+                    with_triangle: bool = False):
     """The point table of a mesh's lightmap, on the host (numpy only): (points [H, W, 3] f32, normals [H, W, 3] f32, covered [H, W] bool)
     for render_points.  `positions`, `normals` [V, 3], `texcoords` [V, 2] and `indices` [T, 3] are a single-index triangle mesh
     (objload.Mesh's arrays, flat or shaped).  Texel (x, y) has its centre at u = (x + 0.5) / W, v = 1 - (y + 0.5) / H: the inverse of
@@ -284,7 +324,17 @@ def lightmap_texels(positions, normals, texcoords, indices, width: int, height: 
     matrix indexed [row, col] as cgmath.py builds them, e.g. StaticMesh.transform; None = identity): points as points, normals through
     the inverse transpose of its upper 3 x 3, then normalised.  The point is moved by `offset` along that unit normal (mi_render_points
     uses the origin as given: a small positive offset keeps the sample rays clear of their own surface).  Uncovered texels — and texels
-    whose interpolated normal has no length — have a zero normal and a zero point: the empty-texel mark of mi_render_points."""
+    whose interpolated normal has no length — have a zero normal and a zero point: the empty-texel mark of mi_render_points.
+    `jitter` ([rows, H, W, 2], e.g. lightmap_jitter's) moves the sample of row r of texel (x, y) from the centre to
+    u = (x + jx) / W, v = 1 - (y + jy) / H and gives every table a leading [rows] axis: what mi_lightmap_texels makes on the GPU with
+    MI_LM_JITTER.  with_triangle adds a fourth result: the winning triangle's index per sample, int32, -1 where not covered."""
+    if jitter is not None:
+        return _lightmap_texels_jittered(positions, normals, texcoords, indices, width, height, transform, offset, jitter, with_triangle)
+    if with_triangle:
+        H_, W_ = int(height), int(width)
+        out = _lightmap_texels_jittered(positions, normals, texcoords, indices, width, height, transform, offset,
+                                        np.full((1, max(H_, 0), max(W_, 0), 2), 0.5, np.float32), True)
+        return tuple(t[0] for t in out)
     W, H = int(width), int(height)
     if W < 1 or H < 1:
         raise ValueError("width and height must be >= 1")
@@ -340,6 +390,69 @@ def lightmap_texels(positions, normals, texcoords, indices, width: int, height: 
     return np.ascontiguousarray(pts, np.float32), np.ascontiguousarray(nrm, np.float32), covered
 
 
+def _lightmap_texels_jittered(positions, normals, texcoords, indices, width, height, transform, offset, jitter, with_triangle):
+    """lightmap_texels with one sample position per (row, texel): the same f64 expressions in the same order, the sample's (u, v) in place
+    of the centre's, the triangle's texel box widened to every texel a sample of which can lie in its uv box."""
+    W, H = int(width), int(height)
+    if W < 1 or H < 1:
+        raise ValueError("width and height must be >= 1")
+    J = np.asarray(jitter, np.float64)
+    if J.ndim != 4 or J.shape[1:] != (H, W, 2) or J.shape[0] < 1:
+        raise ValueError(f"jitter must be [rows, {H}, {W}, 2], got {list(J.shape)}")
+    R = J.shape[0]
+    P = np.asarray(positions, np.float64).reshape(-1, 3)
+    N = np.asarray(normals, np.float64).reshape(-1, 3)
+    T = np.asarray(texcoords, np.float64).reshape(-1, 2)
+    I = np.asarray(indices, np.int64).reshape(-1, 3)
+    if not (len(P) == len(N) == len(T)):
+        raise ValueError(f"positions, normals and texcoords must describe the same vertices, got {len(P)}, {len(N)} and {len(T)}")
+    if I.size and (I.min() < 0 or I.max() >= len(P)):
+        raise ValueError("indices out of range")
+    M = np.eye(4) if transform is None else np.asarray(transform, np.float64).reshape(4, 4)
+    NM = np.linalg.inv(M[:3, :3]).T
+    U = (np.arange(W)[None, None, :] + J[..., 0]) / W                     # [R, H, W] sample positions
+    V = 1.0 - (np.arange(H)[None, :, None] + J[..., 1]) / H
+    pts = np.zeros((R, H, W, 3), np.float64)
+    nrm = np.zeros((R, H, W, 3), np.float64)
+    tri = np.full((R, H, W), -1, np.int32)
+    for k, (a, b, c) in enumerate(I):
+        (ua, va), (ub, vb), (uc, vc) = T[a], T[b], T[c]
+        area = (ub - ua) * (vc - va) - (vb - va) * (uc - ua)
+        if area == 0.0 or not np.isfinite(area):
+            continue
+        fx0, fx1 = np.floor(min(ua, ub, uc) * W) - 1, np.floor(max(ua, ub, uc) * W) + 1
+        fy0, fy1 = np.floor((1.0 - max(va, vb, vc)) * H) - 1, np.floor((1.0 - min(va, vb, vc)) * H) + 1
+        if not (fx1 >= 0 and fx0 <= W - 1 and fy1 >= 0 and fy0 <= H - 1):
+            continue
+        x0, x1, y0, y1 = int(max(fx0, 0)), int(min(fx1, W - 1)), int(max(fy0, 0)), int(min(fy1, H - 1))
+        u, v = U[:, y0:y1 + 1, x0:x1 + 1], V[:, y0:y1 + 1, x0:x1 + 1]
+        sgn = 1.0 if area > 0.0 else -1.0
+        ea = ((ub - u) * (vc - v) - (vb - v) * (uc - u)) * sgn
+        eb = ((uc - u) * (va - v) - (vc - v) * (ua - u)) * sgn
+        ec = ((ua - u) * (vb - v) - (va - v) * (ub - u)) * sgn
+        take = (ea >= 0.0) & (eb >= 0.0) & (ec >= 0.0) & (tri[:, y0:y1 + 1, x0:x1 + 1] < 0)
+        if not take.any():
+            continue
+        tot = ea + eb + ec
+        wa, wb, wc = (ea / tot)[take], (eb / tot)[take], (ec / tot)[take]
+        rr, yy, xx = np.nonzero(take)
+        pts[rr, y0 + yy, x0 + xx] = wa[:, None] * P[a] + wb[:, None] * P[b] + wc[:, None] * P[c]
+        nrm[rr, y0 + yy, x0 + xx] = wa[:, None] * N[a] + wb[:, None] * N[b] + wc[:, None] * N[c]
+        tri[rr, y0 + yy, x0 + xx] = k
+    pts = pts @ M[:3, :3].T + M[:3, 3]
+    nrm = nrm @ NM.T
+    with np.errstate(invalid="ignore", over="ignore"):
+        length = np.sqrt((nrm * nrm).sum(axis=-1))
+    covered = (tri >= 0) & np.isfinite(length) & (length > 0.0)
+    nrm = nrm / np.where(covered, length, 1.0)[..., None]
+    pts = pts + float(offset) * nrm
+    pts[~covered] = 0.0
+    nrm[~covered] = 0.0
+    tri[~covered] = -1
+    out = (np.ascontiguousarray(pts, np.float32), np.ascontiguousarray(nrm, np.float32), covered)
+    return out + (tri,) if with_triangle else out
+
+
 def equirect_dirs(lon, lat) -> np.ndarray:
     """Unit directions [..., 3] float32 of a latitude-longitude panorama for arrays of longitudes / latitudes in radians:
     (sin lon cos lat, sin lat, -cos lon cos lat) — longitude 0 looks down -z, +pi/2 down +x, +-pi (the seam) down +z; latitude +pi/2 is
@@ -374,6 +487,28 @@ def equirect_ray_table(width: int, height: int, eye, samples: int = 1, seed: int
     dirs = equirect_dirs(lon, lat)
     origins = np.ascontiguousarray(np.broadcast_to(np.asarray(eye, np.float32).reshape(3), dirs.shape))
     return origins, dirs
+
+
+def mesh_pod(mesh, transform=None):
+    """(abi.mi_mesh, what keeps its arrays alive) for mi_lightmap_texels / mi_bake_lightmap: `mesh` is a StaticMesh (geometry.py; its
+    own transform unless one is given) or an objload.Mesh (identity unless one is given).  Only the four arrays, the two counts and the
+    transform are filled in: the calls read nothing else."""
+    from . import cgmath
+    if hasattr(mesh, "mesh") and hasattr(mesh, "transform"):              # a StaticMesh
+        transform = mesh.transform if transform is None else transform
+        mesh = mesh.mesh
+    M = np.asarray(cgmath.identity() if transform is None else transform, np.float32).reshape(4, 4)
+    keep = [np.ascontiguousarray(mesh.positions, np.float32).reshape(-1), np.ascontiguousarray(mesh.normals, np.float32).reshape(-1),
+            np.ascontiguousarray(mesh.texcoords, np.float32).reshape(-1), np.ascontiguousarray(mesh.indices, np.uint32).reshape(-1)]
+    if keep[1].size != keep[0].size or keep[2].size * 3 != keep[0].size * 2 or keep[0].size % 3 or keep[3].size % 3:
+        raise ValueError("mesh needs positions and normals [V, 3], texcoords [V, 2] and indices [T, 3]")
+    pod = abi.mi_mesh()
+    pod.positions, pod.normals, pod.texcoords = (a.ctypes.data_as(C.POINTER(C.c_float)) for a in keep[:3])
+    pod.indices = keep[3].ctypes.data_as(C.POINTER(C.c_uint32))
+    pod.n_vertices, pod.n_triangles = keep[0].size // 3, keep[3].size // 3
+    pod.transform = abi.f16(*cgmath.cols16(M))
+    pod.material = -1
+    return pod, keep
 
 
 class Context:
@@ -455,6 +590,65 @@ class Context:
         an empty texel (black).  Returns what render returns."""
         p, n, rows = check_point_table(cam, points, normals)
         return self._render_table(self._lib.mi_render_points, cam, p, n, rows, seed, want_f32, want_u8, want_sig, flags, max_state_bytes)
+
+    def lightmap_texels(self, mesh, width: int, height: int, rows: int = 1, jitter: bool = False, seed: int = 1, offset: float = 0.0,
+                        transform=None, want_triangle: bool = True):
+        """mi_lightmap_texels: the point table of a mesh's uv atlas, made on the GPU — what the helper lightmap_texels computes on the
+        host, sample by sample.  `mesh` is a StaticMesh (its transform is used unless `transform` is given) or an objload.Mesh.  Returns
+        (points [rows, H, W, 3] f32, normals [rows, H, W, 3] f32, triangle [rows, H, W] int32 | None): the winning triangle per sample,
+        -1 and a zero normal where the texel is empty.  With jitter, row r of texel (x, y) sits at lightmap_jitter(...)[r, y, x];
+        without, every row is the texel's centre.  No scene is needed."""
+        pod, keep = mesh_pod(mesh, transform)
+        shape = (max(int(rows), 0), max(int(height), 0), max(int(width), 0))
+        pts = np.empty(shape + (3,), np.float32)
+        nrm = np.empty(shape + (3,), np.float32)
+        tri = np.empty(shape, np.int32) if want_triangle else None
+        abi.check(self._lib.mi_lightmap_texels(self._h, C.byref(pod), width, height, rows, abi.MI_LM_JITTER if jitter else 0, seed, offset,
+                                               pts.ctypes.data, nrm.ctypes.data, tri.ctypes.data if tri is not None else None))
+        del keep
+        return pts, nrm, tri
+
+    def lightmap_texels_device(self, d_positions: int, d_normals: int, d_texcoords: int, d_indices: int, n_vertices: int, n_triangles: int,
+                               width: int, height: int, d_out_points: int, d_out_normals: int, d_out_triangle: Optional[int] = None,
+                               rows: int = 1, jitter: bool = False, seed: int = 1, offset: float = 0.0, transform=None,
+                               stream: Optional[int] = None):
+        """mi_lightmap_texels_device: the same for a mesh and tables held on the device (raw pointers, e.g. tensor.data_ptr(): positions
+        and normals [V, 3] f32, texcoords [V, 2] f32, indices [T, 3] u32; outputs [rows, H, W, 3] f32 and [rows, H, W] int32).  Queued on
+        `stream`; the tables can go straight into render_points_device.  A triangle with an index >= n_vertices covers nothing."""
+        pod = abi.mi_mesh()
+        pod.positions = C.cast(d_positions, C.POINTER(C.c_float))
+        pod.normals = C.cast(d_normals, C.POINTER(C.c_float))
+        pod.texcoords = C.cast(d_texcoords, C.POINTER(C.c_float))
+        pod.indices = C.cast(d_indices, C.POINTER(C.c_uint32))
+        pod.n_vertices, pod.n_triangles = n_vertices, n_triangles
+        from . import cgmath
+        pod.transform = abi.f16(*cgmath.cols16(np.asarray(cgmath.identity() if transform is None else transform, np.float32).reshape(4, 4)))
+        abi.check(self._lib.mi_lightmap_texels_device(self._h, C.byref(pod), width, height, rows, abi.MI_LM_JITTER if jitter else 0, seed,
+                                                      offset, d_out_points, d_out_normals, d_out_triangle, stream))
+
+    def bake_lightmap(self, cam: Camera, mesh, jitter: bool = True, offset: float = 1e-3, seed: int = 1, transform=None, want_f32=True,
+                      want_u8=True, want_sig=False, want_triangle=False, flags: int = 0, max_state_bytes: int = 0):
+        """mi_bake_lightmap: lightmap_texels and render_points in one call, the table never leaving the GPU.  The atlas is
+        cam.screen_width x screen_height; with jitter every one of the aa_sample_count samples of a texel starts at its own position
+        inside the texel.  Returns (f32, u8, sig, triangle [rows, H, W] int32 | None, stats)."""
+        pod, keep = mesh_pod(mesh, transform)
+        cpod = cam.to_pod()
+        opts = abi.mi_render_opts(seed=seed, rank=0, world=1, variant=abi.MI_VARIANT_DEFAULT, want_signature=int(want_sig),
+                                  flags=flags, max_state_bytes=max_state_bytes)
+        H, W = cam.screen_height, cam.screen_width
+        f32 = np.empty((H, W, 3), np.float32) if want_f32 else None
+        u8 = np.empty((H, W, 3), np.uint8) if want_u8 else None
+        sig = np.empty((H, W), np.uint32) if want_sig else None
+        tri = np.empty((cam.aa_sample_count if jitter else 1, H, W), np.int32) if want_triangle else None
+        st = abi.mi_stats()
+        abi.check(self._lib.mi_bake_lightmap(
+            self._h, C.byref(cpod), C.byref(opts), C.byref(pod), abi.MI_LM_JITTER if jitter else 0, offset,
+            f32.ctypes.data if f32 is not None else None,
+            u8.ctypes.data if u8 is not None else None,
+            sig.ctypes.data if sig is not None else None,
+            tri.ctypes.data if tri is not None else None, C.byref(st)))
+        del keep
+        return f32, u8, sig, tri, st
 
     def render_probes(self, cam: Camera, points, seed: int = 1, want_f32=True, want_u8=True, want_sig=False,
                       flags: int = 0, max_state_bytes: int = 0):
@@ -870,6 +1064,24 @@ class Scene:                         # tracing.rs:213-218
         try:
             ctx.upload(self.flatten())
             _, u8, _, _ = ctx.render_points(self.camera, p, n, seed=seed, want_f32=False, want_u8=True)
+            return u8
+        finally:
+            ctx.close()
+
+    def bake_lightmap(self, mesh, width: int, height: int, samples: int, jitter: bool = True, offset: float = 1e-3, seed: int = 1,
+                      device: int = 0) -> np.ndarray:
+        """The lightmap of `mesh` (a StaticMesh of this scene, or any objload.Mesh) in one call (mi_bake_lightmap): the RgbImage bytes
+        [height, width, 3] u8 of its uv atlas, `samples` cosine-distributed gathers per texel, each from its own jittered position inside
+        the texel (jitter) or all from the centre.  The atlas is rasterised, sampled and traced on the GPU: only the mesh goes up and the
+        image comes back.  This scene's camera supplies path_depth, max_trace_dist and gamma; `offset` lifts the points off the surface
+        along the normal."""
+        from dataclasses import replace
+        cam = replace(self.camera, screen_width=int(width), screen_height=int(height), aa_sample_count=int(samples))
+        check_point_table(cam, np.zeros((height, width, 3), np.float32), np.zeros((height, width, 3), np.float32))
+        ctx = Context(device)
+        try:
+            ctx.upload(self.flatten())
+            _, u8, _, _, _ = ctx.bake_lightmap(cam, mesh, jitter=jitter, offset=offset, seed=seed, want_f32=False, want_u8=True)
             return u8
         finally:
             ctx.close()

@@ -203,6 +203,8 @@ typedef struct mi_render_opts {
                                      * compiler builds over them (>= 96 small triangles): same image */
 /* `flags` of mi_hemisphere_occlusion (below) */
 #define MI_HEMI_WORLD_RADIUS 1u     /* t_max is a world-space radius: the interval of a sample ends at t_max / |d| */
+/* mi_lightmap_texels / mi_bake_lightmap flags */
+#define MI_LM_JITTER 1u             /* row r of a texel is a jittered position inside it, not its centre */
 
 typedef enum mi_variant {
     MI_VARIANT_DEFAULT    = 0,  /* library picks (currently MI_VARIANT_WAVEFRONT)                  */
@@ -457,6 +459,46 @@ int  mi_render_points_device(mi_ctx* ctx, const mi_camera_desc* cam, const mi_re
                              const float* d_points, const float* d_normals, uint32_t rows_per_pixel,
                              uint32_t sample_begin, uint32_t sample_end, void* d_accum_f32x4,
                              void* d_compact_f32, void* d_sig_u32, void* stream, mi_stats* stats);
+
+/* ---- lightmap atlas: the point table of a mesh's uv atlas made on the GPU (added within ABI version 5: detect by symbol lookup) ----
+ * The table mi_render_points reads, rasterised from a single-index triangle mesh in HBM: `out_points` and `out_normals`
+ *   [rows][H][W][3] f32 and, when not NULL, `out_triangle` [rows][H][W] int32 (the winning triangle's index, -1 = empty texel).  Of the
+ *   mi_mesh it reads positions, normals, texcoords, indices, the two counts and transform; inv_transform, material and textures are
+ *   ignored.  No scene is needed.  These are the semantics of lightmap_texels (Python), from "texel centre" to "sample position":
+ * Sample position: row r of texel (x, y) lies at u = (x + jx) / W, v = 1 - (y + jy) / H, in f64 — the inverse of Texture::sample's
+ *   x = floor(u W), y = floor((1 - v) H) (texture.rs:28-29).  Without MI_LM_JITTER jx = jy = 0.5, the texel's centre, and every row
+ *   is the same row.  With MI_LM_JITTER jx, then jy, are the first two gen_range(0.0..1.0) draws (f32, promoted to f64) of the fresh stream
+ *   (seed, 2*W*H + y*W + x, r).  Keys in [2 W H, 3 W H) are used by no other stream of the image (paths: [0, W H), directions:
+ *   [W H, 2 W H)); 3*W*H > 2^31 is MI_ERR_INVALID, with or without the flag.
+ * Coverage: a triangle (a, b, c) whose uv area is finite and not zero covers the sample when its three edge functions
+ *   ea = ((ub - u)(vc - v) - (vb - v)(uc - u)) * sign(area), eb, ec (cyclic) are >= 0, evaluated in f64 without fused multiply-adds.
+ *   Where several triangles cover a sample the LOWEST triangle index wins.  NaN texcoords cover nothing; a triangle with an index
+ *   >= n_vertices covers nothing (device form; its vertices are not read).
+ * Resolve: weights ea / (ea + eb + ec), ...; position and normal interpolated in f64; the position through transform, the normal through
+ *   the inverse transpose of its upper 3 x 3 (computed in f64 from transform), normalised; point += offset * normal; one rounding to
+ *   f32.  A sample nothing covers, and one whose normal has no or no finite length, is all zero with triangle -1: the empty-texel mark
+ *   of mi_render_points.  The result does not depend on scheduling: the winner is an integer minimum, nothing is summed across threads.
+ * rows: 1 .. 65535.  A mesh of 0 triangles is MI_OK and all empty.  MI_ERR_INVALID (each with a message, checked before the context):
+ *   NULL mesh, arrays or outputs (out_triangle may be NULL), width or height of 0 or above 32768, rows of 0 or above 65535, an unknown
+ *   flag, a NaN offset, and, host forms only, an index >= n_vertices.
+ * Scratch: per call 16 B per 32 x 32-texel tile plus 4 B per (triangle, tile) pair of the triangles' uv boxes, in buffers the context
+ *   owns (grown on demand, freed with the context, never the buffers mi_reserve sized; MI_ERR_OOM if they cannot be allocated).  The
+ *   pairs are bounded by n_triangles * tiles and capped at 2^30; tiles whose pairs do not fit test the whole mesh: slower, same result.
+ * mi_lightmap_texels: HOST pointers, blocking; mesh and outputs pass through buffers the context owns.
+ * mi_lightmap_texels_device: the mesh's four arrays and the outputs are DEVICE pointers on ctx's device.  Queues on `stream` and does
+ *   not synchronise, except when it has to grow its scratch; it sizes the pair list by what the previous call needed.
+ *   mi_last_kernel_ms reports the kernels of the last call.
+ * mi_bake_lightmap: the whole bake, blocking: W x H = cam->screen_width x screen_height, seed = opts->seed, rows = aa_sample_count with
+ *   MI_LM_JITTER, else 1.  Uploads the mesh, makes the table in the context's table buffer (the one mi_render_rays uploads into), then
+ *   does exactly what mi_render_points does from there: the same image, bit for bit, as mi_render_points on the table
+ *   mi_lightmap_texels returns.  Every refusal and camera rule of mi_render_points applies, word for word, and every refusal above;
+ *   out_triangle ([rows][H][W]) may be NULL.  Only the mesh crosses the bus. */
+int  mi_lightmap_texels(mi_ctx* ctx, const mi_mesh* mesh, uint32_t width, uint32_t height, uint32_t rows, uint32_t flags,
+                        uint32_t seed, float offset, float* out_points, float* out_normals, int32_t* out_triangle);
+int  mi_lightmap_texels_device(mi_ctx* ctx, const mi_mesh* mesh, uint32_t width, uint32_t height, uint32_t rows, uint32_t flags,
+                               uint32_t seed, float offset, float* out_points, float* out_normals, int32_t* out_triangle, void* stream);
+int  mi_bake_lightmap(mi_ctx* ctx, const mi_camera_desc* cam, const mi_render_opts* opts, const mi_mesh* mesh, uint32_t flags,
+                      float offset, float* out_rgb_f32, uint8_t* out_rgb_u8, uint32_t* out_sig, int32_t* out_triangle, mi_stats* stats);
 
 /* ---- light probes: SH L2 radiance probes with the directions drawn on the GPU (added within ABI version 5: detect by symbol lookup) ----
  * mi_render_points without normals and with a second output.  One "pixel" is one probe, a point in free space; its samples leave it in

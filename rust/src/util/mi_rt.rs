@@ -41,6 +41,7 @@ pub enum mi_multi {}
 pub const MI_OPT_NO_TILE_MASKS: u32 = 1; pub const MI_OPT_REFERENCE_WALK: u32 = 2; pub const MI_OPT_TWO_STAGE: u32 = 4; pub const MI_OPT_NO_LIST_TREE: u32 = 8;
 pub const MI_RT_ABI_VERSION: c_int = 5;
 pub const MI_HEMI_WORLD_RADIUS: u32 = 1;
+pub const MI_LM_JITTER: u32 = 1;
 // mi_material_kind / mi_object_kind / projection and shading modes (include/mi_rt.h)
 pub const MI_MAT_LAMBERTIAN: i32 = 0; pub const MI_MAT_METAL: i32 = 1; pub const MI_MAT_DIELECTRIC: i32 = 2;
 pub const MI_MAT_PARAMETERIZED: i32 = 3; pub const MI_MAT_ISOTROPIC: i32 = 4;
@@ -107,6 +108,15 @@ extern "C" {
                                    d_points: *const f32, d_normals: *const f32, rows_per_pixel: u32,
                                    sample_begin: u32, sample_end: u32, d_accum_f32x4: *mut c_void,
                                    d_compact_f32: *mut c_void, d_sig_u32: *mut c_void, stream: *mut c_void, stats: *mut mi_stats) -> c_int;
+    // lightmap atlas (added within ABI 5): the point table of a mesh's uv atlas made on the GPU, [rows][H][W][3] / [rows][H][W]
+    pub fn mi_lightmap_texels(ctx: *mut mi_ctx, mesh: *const mi_mesh, width: u32, height: u32, rows: u32, flags: u32,
+                              seed: u32, offset: f32, out_points: *mut f32, out_normals: *mut f32, out_triangle: *mut i32) -> c_int;
+    pub fn mi_lightmap_texels_device(ctx: *mut mi_ctx, mesh: *const mi_mesh, width: u32, height: u32, rows: u32, flags: u32,
+                                     seed: u32, offset: f32, out_points: *mut f32, out_normals: *mut f32, out_triangle: *mut i32,
+                                     stream: *mut c_void) -> c_int;
+    pub fn mi_bake_lightmap(ctx: *mut mi_ctx, cam: *const mi_camera_desc, opts: *const mi_render_opts, mesh: *const mi_mesh, flags: u32,
+                            offset: f32, out_rgb_f32: *mut f32, out_rgb_u8: *mut u8, out_sig: *mut u32, out_triangle: *mut i32,
+                            stats: *mut mi_stats) -> c_int;
     // light probes (added within ABI 5): points is [rows_per_pixel][H][W][3]; out_sh [H][W][9][3], d_compact_sh [tiles_padded][1024][27]
     pub fn mi_render_probes(ctx: *mut mi_ctx, cam: *const mi_camera_desc, opts: *const mi_render_opts,
                             points: *const f32, rows_per_pixel: u32, out_sh: *mut f32,

@@ -194,6 +194,25 @@ impl Scene {
         img
     }
 
+    /// The lightmap of `mesh` (mi_bake_lightmap): its uv atlas, width x height texels, is rasterised on the GPU into the point table
+    /// render_points would take and gathered with `samples` samples per texel, each from its own jittered position inside the texel
+    /// (`jitter`) or all from the centre; `offset` lifts the points off the surface along the normal.  Of `mesh` the four arrays, the two
+    /// counts and transform are read.  The camera supplies path_depth, max_trace_dist and gamma.  Only the mesh crosses the bus.
+    pub fn bake_lightmap(&self, mesh: &mi_rt::mi_mesh, width: u32, height: u32, samples: u32, jitter: bool, offset: f32, seed: u32) -> RgbImage {
+        let mut cam = self.camera.flatten();
+        cam.screen_width = width;
+        cam.screen_height = height;
+        cam.aa_sample_count = samples;
+        let opts = mi_rt::mi_render_opts { seed: seed, rank: 0, world: 1, ..Default::default() };
+        let flags = if jitter { mi_rt::MI_LM_JITTER } else { 0 };
+        let mut img = RgbImage::new(width, height);
+        let pimg = img.as_mut_ptr();
+        self.with_gpu_scene(|ctx| unsafe {
+            mi_rt::mi_bake_lightmap(ctx, &cam, &opts, mesh, flags, offset, std::ptr::null_mut(), pimg, std::ptr::null_mut(), std::ptr::null_mut(), std::ptr::null_mut())
+        });
+        img
+    }
+
     /// Light probes (mi_render_probes): `points` holds `rows_per_pixel` x height x width probe positions, row-major ([row][y][x]),
     /// rows_per_pixel = 1 or camera.aa_sample_count.  Sample s of probe (x, y) leaves its point along rand_sphere_vec (what
     /// Isotropic::scatter returns: uniform over the sphere), drawn on the GPU from the stream (seed, width * height + y * width + x, s),

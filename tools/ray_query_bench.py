@@ -53,7 +53,16 @@ inside the Cornell box (probe_grid over [-2.8, 2.8] x [0.2, 5.8] x [-2.8, 2.8]) 
 (a 64 x 64 table) and 65536 probes x 64 samples (256 x 256), path_depth 10.  The pre-made directions are rand_sphere_vec restated in
 numpy (sphere_dirs below).  Each row reports median / min / max of mi_last_kernel_ms; the probes row also the time of wf_reduce_sh
 (entry 7 of mi_last_pipeline_ms: HIP events around its launches) and its share of the kernel time.  The tool checks that the two
-compact images agree bit for bit."""
+compact images agree bit for bit.
+
+--mode atlas times the lightmap atlas (mi_lightmap_texels_device / mi_bake_lightmap) against the host helper lightmap_texels on the drone
+of config 4, at --atlas-sizes (square atlases, default 1024 and 2048), aa_sample_count = 16, path_depth 10.  Per size: the helper's wall
+time (one run: it takes seconds); the kernels' time (HIP events around count, scan, fill and resolve: mi_last_kernel_ms) with the mesh
+resident, rows = 1 and rows = 16 jittered, 5 warm-up calls then --calls timed ones; and the whole bake both ways, wall clock around the
+blocking calls, --atlas-bakes times each, alternating: mi_bake_lightmap (mesh up, table made on the GPU, render, image down) against
+lightmap_texels + mi_render_points (table made on the host, uploaded, the same render).  The tool checks that the GPU's triangle plane
+equals the helper's and that the two bakes give the same bytes.  --atlas-grid N replaces the drone (1736 triangles in this repository's
+asset) by a height field of N x N quads, 2 N^2 triangles, for the table's timings alone."""
 import argparse
 import json
 import os
@@ -399,6 +408,95 @@ def probes_rows(ctx, cfg, sc, calls, warmup):
 SHADOW_POINT = (0.0, 5.9, 0.0)          # just under the Cornell box's ceiling light (y = 6)
 
 
+def grid_mesh(n):
+    """A height field of n x n quads (2 n^2 triangles) whose uv atlas is the unit square less a 1 % margin: a mesh of any size for the
+    atlas timings, with analytic normals."""
+    from cs397raytracingsp22_amd import cgmath, objload
+    from cs397raytracingsp22_amd.geometry import StaticMesh
+    g = np.linspace(0.01, 0.99, n + 1)
+    u, v = np.meshgrid(g, g)
+    P = np.stack([4 * u - 2, 0.3 * np.sin(7 * u) * np.cos(5 * v), 4 * v - 2], axis=-1)
+    N = np.stack([-0.3 * 7 * np.cos(7 * u) * np.cos(5 * v) / 4, np.ones_like(u), 0.3 * 5 * np.sin(7 * u) * np.sin(5 * v) / 4], axis=-1)
+    N /= np.linalg.norm(N, axis=-1, keepdims=True)
+    k = (np.arange(n)[:, None] * (n + 1) + np.arange(n)[None, :]).reshape(-1)
+    I = np.concatenate([np.stack([k, k + 1, k + n + 2], axis=1), np.stack([k, k + n + 2, k + n + 1], axis=1)])
+    mesh = objload.Mesh(P.reshape(-1, 3), N.reshape(-1, 3), np.stack([u, v], axis=-1).reshape(-1, 2), I)
+    return StaticMesh(mesh, None, [None] * 5, cgmath.identity())
+
+
+def atlas_rows(ctx, size, calls, warmup, bakes, grid=0):
+    from cs397raytracingsp22_amd import lightmap_texels
+    dev = torch.device("cuda:0")
+    offset = float(np.float32(1e-3))
+    if grid:                                          # the table alone (it needs no scene): timings and the check against the helper
+        drone, name, bakes = grid_mesh(grid), f"grid {grid}x{grid}", 0
+    else:
+        sc = scenes.config4(size, size, BAKE_AA, 10)
+        cam = sc.camera
+        drone, name = sc.objects[-1], "drone"
+        ctx.upload(sc.flatten())
+    mesh = drone.mesh
+    t0 = time.perf_counter()
+    h_p, h_n, h_cov, h_tri = lightmap_texels(mesh.positions, mesh.normals, mesh.texcoords, mesh.indices, size, size,
+                                             transform=drone.transform, offset=offset, with_triangle=True)
+    helper_s = time.perf_counter() - t0
+    base = {"mode": "atlas", "mesh": name, "triangles": mesh.n_triangles, "vertices": mesh.n_vertices, "width": size, "height": size}
+    rows = [dict(base, query="lightmap_texels (host, numpy)", wall_s=round(helper_s, 3), covered_share=round(float(h_cov.mean()), 4))]
+    print(json.dumps(rows[-1]), flush=True)
+    t_mesh = [torch.from_numpy(np.array(a)).to(dev) for a in (mesh.positions, mesh.normals, mesh.texcoords, mesh.indices.view(np.int32))]
+    for n_rows, jitter in ((1, False), (BAKE_AA, True)):
+        o_p = torch.empty((n_rows, size, size, 3), dtype=torch.float32, device=dev)
+        o_n = torch.empty((n_rows, size, size, 3), dtype=torch.float32, device=dev)
+        o_t = torch.empty((n_rows, size, size), dtype=torch.int32, device=dev)
+        torch.cuda.synchronize()
+        ms = []
+        for k in range(warmup + calls):
+            ctx.lightmap_texels_device(t_mesh[0].data_ptr(), t_mesh[1].data_ptr(), t_mesh[2].data_ptr(), t_mesh[3].data_ptr(), mesh.n_vertices,
+                                       mesh.n_triangles, size, size, o_p.data_ptr(), o_n.data_ptr(), o_t.data_ptr(), rows=n_rows, jitter=jitter,
+                                       seed=1, offset=offset, transform=drone.transform)
+            torch.cuda.synchronize()
+            if k >= warmup:
+                ms.append(ctx.last_kernel_ms())
+        row = dict(base, query=f"mi_lightmap_texels_device rows={n_rows}" + (" jittered" if jitter else ""), calls=calls,
+                   kernel_ms_median=round(float(np.median(ms)), 4), kernel_ms_min=round(float(np.min(ms)), 4),
+                   kernel_ms_max=round(float(np.max(ms)), 4), msamples_per_s_kernel=round(n_rows * size * size / float(np.median(ms)) / 1e3, 1))
+        if not jitter:
+            differ = int((o_t[0].cpu().numpy() != h_tri).sum())
+            row["samples_whose_triangle_differs_from_the_helper"] = differ
+            if differ:
+                raise SystemExit(f"ray_query_bench: {differ} texels are won by another triangle than in lightmap_texels")
+        rows.append(row)
+        print(json.dumps(row), flush=True)
+        del o_p, o_n, o_t
+    if not bakes:
+        return rows
+    gpu_s, host_s, table_s = [], [], []
+    for k in range(1 + bakes):
+        t0 = time.perf_counter()
+        g32, g8, _, _, _ = ctx.bake_lightmap(cam, drone, jitter=False, offset=offset, seed=1)
+        t1 = time.perf_counter()
+        p, n, _ = lightmap_texels(mesh.positions, mesh.normals, mesh.texcoords, mesh.indices, size, size, transform=drone.transform, offset=offset)
+        t2 = time.perf_counter()
+        r32, r8, _, _ = ctx.render_points(cam, p, n, seed=1)
+        t3 = time.perf_counter()
+        if k >= 1:
+            gpu_s.append(t1 - t0)
+            table_s.append(t2 - t1)
+            host_s.append(t3 - t1)
+    # the helper's table and the GPU's agree to 1 ulp, not to the bit, so the two images are compared by their means and their differing texels
+    differ = int((g8 != r8).any(axis=-1).sum())
+    rows.append(dict(base, query="mi_bake_lightmap", aa_sample_count=BAKE_AA, bakes=bakes, wall_s_median=round(float(np.median(gpu_s)), 4),
+                     wall_s_min=round(float(np.min(gpu_s)), 4), wall_s_max=round(float(np.max(gpu_s)), 4),
+                     mean_radiance=round(float(g32.mean()), 6)))
+    rows.append(dict(base, query="lightmap_texels + mi_render_points", aa_sample_count=BAKE_AA, bakes=bakes,
+                     wall_s_median=round(float(np.median(host_s)), 4), wall_s_min=round(float(np.min(host_s)), 4),
+                     wall_s_max=round(float(np.max(host_s)), 4), of_which_lightmap_texels_s_median=round(float(np.median(table_s)), 4),
+                     mean_radiance=round(float(r32.mean()), 6), texels_whose_u8_differs=differ))
+    for row in rows[-2:]:
+        print(json.dumps(row), flush=True)
+    return rows
+
+
 def occlusion_rows(ctx, cfg, sc, co, cd, bo, bd, hitpoints, calls, warmup):
     to = (np.array(SHADOW_POINT, np.float32) - hitpoints).astype(np.float32)
     dist = np.sqrt((to.astype(np.float64) ** 2).sum(axis=1))
@@ -466,12 +564,17 @@ def main():
     ap.add_argument("--width", type=int, default=1920)
     ap.add_argument("--height", type=int, default=1080)
     ap.add_argument("--configs", default="2,4")
-    ap.add_argument("--mode", choices=("intersect", "occlusion", "render", "hemisphere", "bake", "probes"), default="intersect",
+    ap.add_argument("--mode", choices=("intersect", "occlusion", "render", "hemisphere", "bake", "probes", "atlas"), default="intersect",
                     help="intersect: the closest-hit rows; occlusion: the any-hit query against the visibility form; "
                          "render: ray-table rendering against mi_shade_rays_device; "
                          "hemisphere: hemisphere occlusion against the any-hit query on the identical pre-made rays; "
                          "bake: point-table rendering against ray-table rendering on the identical pre-made rays; "
-                         "probes: light-probe rendering against ray-table rendering on the identical pre-made rays")
+                         "probes: light-probe rendering against ray-table rendering on the identical pre-made rays; "
+                         "atlas: the lightmap atlas on the GPU against the host helper, on the drone")
+    ap.add_argument("--atlas-sizes", default="1024,2048", help="--mode atlas: the square atlas sizes")
+    ap.add_argument("--atlas-grid", type=int, default=0, help="--mode atlas: a synthetic height field of N x N quads (2 N^2 triangles) instead "
+                    "of the drone; the table's timings and the check against the helper only, no bake")
+    ap.add_argument("--atlas-bakes", type=int, default=3, help="--mode atlas: timed whole bakes per size and side (after one warm-up)")
     ap.add_argument("--points", type=int, default=1 << 18, help="--mode hemisphere: at most this many surface points (64 rays each)")
     ap.add_argument("--out", default=None, help="also append the JSON lines to this file")
     a = ap.parse_args()
@@ -481,7 +584,11 @@ def main():
         raise SystemExit("ray_query_bench: no GPU; there is no CPU fallback")
     ctx = Context(0)
     rows = []
-    for cfg in [int(c) for c in a.configs.split(",")]:
+    if a.mode == "atlas":
+        for size in [int(v) for v in a.atlas_sizes.split(",")]:
+            rows += atlas_rows(ctx, size, a.calls, a.warmup, a.atlas_bakes, a.atlas_grid)
+        a.configs = ""
+    for cfg in [int(c) for c in a.configs.split(",") if c]:
         sc = {2: scenes.config2, 4: scenes.config4}[cfg](a.width, a.height, 1, 10)
         ctx.upload(sc.flatten())
         co, cd = pinhole_rays(sc.camera)
