@@ -119,6 +119,7 @@ EXPORTS = [
     "mi_render_points", "mi_render_points_device",
     "mi_render_probes", "mi_render_probes_device",
     "mi_lightmap_texels", "mi_lightmap_texels_device", "mi_bake_lightmap",
+    "mi_lightmap_finish", "mi_lightmap_finish_device",
     "mi_multi_create", "mi_multi_create_loopback", "mi_multi_destroy", "mi_multi_device_count", "mi_multi_context", "mi_multi_scene_upload", "mi_multi_reserve", "mi_multi_render",
 ]
 
@@ -235,6 +236,13 @@ def load() -> C.CDLL:
     lib.mi_bake_lightmap.argtypes = [vp, C.POINTER(mi_camera_desc), C.POINTER(mi_render_opts), C.POINTER(mi_mesh), C.c_uint32, C.c_float,
                                      vp, vp, vp, vp, C.POINTER(mi_stats)]
     lib.mi_bake_lightmap.restype = C.c_int
+    # lightmap finishing (added within ABI 5): width, height, image, points, normals, levels, normal_power_log2, sigma_plane, reach,
+    # sigma_color, dilate, out_image, out_valid (, stream)
+    lib.mi_lightmap_finish.argtypes = [vp, C.c_uint32, C.c_uint32, vp, vp, vp, C.c_uint32, C.c_uint32, C.c_float, C.c_float, C.c_float,
+                                       C.c_uint32, vp, vp]
+    lib.mi_lightmap_finish.restype = C.c_int
+    lib.mi_lightmap_finish_device.argtypes = lib.mi_lightmap_finish.argtypes + [vp]
+    lib.mi_lightmap_finish_device.restype = C.c_int
     lib.mi_multi_create.argtypes = [C.c_int, C.POINTER(C.c_int), C.POINTER(vp)]
     lib.mi_multi_create.restype = C.c_int
     lib.mi_multi_create_loopback.argtypes = [C.c_int, C.c_int, C.POINTER(vp)]

@@ -57,6 +57,9 @@ hipError_t launch_tonemap(const float* image, uint8_t* out, uint32_t n_pixels, f
 hipError_t launch_selftest_rcp(unsigned long long* d_mismatches, hipStream_t stream);
 hipError_t launch_lm_count(const LmArgs& a, hipStream_t stream);
 hipError_t launch_lm_resolve(const LmArgs& a, hipStream_t stream);
+hipError_t launch_lmf_mask(const LmfArgs& a, hipStream_t stream);
+hipError_t launch_lmf_atrous(const LmfArgs& a, bool lds, bool* big_lds_enabled, hipStream_t stream);
+hipError_t launch_lmf_dilate(const LmfArgs& a, hipStream_t stream);
 }  // namespace pt
 
 using namespace pt;
@@ -121,6 +124,11 @@ struct mi_ctx {
     unsigned long long* h_lm_total = nullptr; unsigned long long* h_lm_total_dev = nullptr;
     void* d_lm_mesh = nullptr; size_t lm_mesh_bytes = 0;
     void* d_lm_out = nullptr; size_t lm_out_bytes = 0;
+    // mi_lightmap_finish: two ping-pong images and two masks (grown on demand, never the buffers mi_reserve sized); the host form's
+    // uploaded image and guides, its result and its mask; lmf_atrous' > 64 KB dynamic-LDS opt-in on THIS context's device
+    void* d_lmf = nullptr; size_t lmf_bytes = 0;
+    void* d_lmf_io = nullptr; size_t lmf_io_bytes = 0;
+    bool lmf_big_lds_enabled = false;
     hipEvent_t ev_t0 = nullptr, ev_t1 = nullptr;     // mi_render's whole-call timer
     bool big_lds_enabled = false;                    // wf_trav_i<1024>'s > 64 KB dynamic-LDS opt-in, set on THIS context's device
     // wavefront pipeline buffers
@@ -157,6 +165,7 @@ struct mi_ctx {
         bool debug_mask = false;                        // print tile-mask statistics
         bool dump_launches = false;                     // print every pipeline launch's duration (needs per-launch events)
         ScheduleKnobs sched;                            // the pass schedule's knobs (render_plan.hpp)
+        uint32_t lmf_lds_max_step = 1;                  // lmf_atrous: stage the tile and its halo in LDS up to this step, read HBM directly above (measured: DESIGN.md "Lightmap finishing")
         uint32_t spin_timeout_ms = 120000;              // header wait: give up after this long without progress
     } tune;
 };
@@ -227,6 +236,8 @@ static int ctx_init(mi_ctx* c, const hipDeviceProp_t& prop) {
     t.debug_mask = getenv("MI_RT_DEBUG_MASK") != nullptr;
     t.dump_launches = getenv("MI_RT_WF_DUMP_LAUNCHES") != nullptr;
     env_u("MI_RT_SPIN_TIMEOUT_MS", t.spin_timeout_ms);
+    env_u("MI_RT_LMF_LDS_MAX_STEP", t.lmf_lds_max_step);
+    if (t.lmf_lds_max_step > kLmfMaxLdsStep) t.lmf_lds_max_step = kLmfMaxLdsStep;
     if (t.vote_t < 1) t.vote_t = 1;
     if (t.k_steps < 1) t.k_steps = 1;
     if (t.refill_min < 1) t.refill_min = 1;
@@ -280,6 +291,8 @@ extern "C" void mi_ctx_destroy(mi_ctx* c) {
     if (c->h_lm_total) (void)hipHostFree(c->h_lm_total);
     if (c->d_lm_mesh) (void)hipFree(c->d_lm_mesh);
     if (c->d_lm_out) (void)hipFree(c->d_lm_out);
+    if (c->d_lmf) (void)hipFree(c->d_lmf);
+    if (c->d_lmf_io) (void)hipFree(c->d_lmf_io);
     if (c->d_wf_a) (void)hipFree(c->d_wf_a);
     if (c->d_wf_b) (void)hipFree(c->d_wf_b);
     if (c->d_wf_samp) (void)hipFree(c->d_wf_samp);
@@ -1304,6 +1317,96 @@ extern "C" int mi_bake_lightmap(mi_ctx* c, const mi_camera_desc* cam, const mi_r
     const RayTable table = { d_points, d_normals, rows, kTablePoints, nullptr };
     const mi_camera_desc tc = table_camera(cam);
     return render_image(c, &tc, opts, &table, out_rgb_f32, out_rgb_u8, out_sig, stats);
+}
+
+// ------------------------------------------------------------------ lightmap finishing (edge-aware a-trous filter, gutter dilation)
+// tracing.py lightmap_finish as kernels, one pass per launch.  The arguments are checked before the context, as the atlas' are.
+static int check_lmf_args(const char* who, mi_ctx* c, uint32_t width, uint32_t height, const float* image, const float* points,
+                          const float* normals, uint32_t levels, uint32_t normal_power_log2, float sigma_plane, float reach,
+                          float sigma_color, uint32_t dilate, const float* out_image) {
+    if (!image || !points || !normals || !out_image) return fail(MI_ERR_INVALID, "%s: image, points, normals and out_image are required", who);
+    if (width == 0 || width > 32768u || height == 0 || height > 32768u)
+        return fail(MI_ERR_INVALID, "%s: width %u / height %u is not in 1 .. 32768", who, width, height);
+    if (levels > 8) return fail(MI_ERR_INVALID, "%s: levels %u is above 8", who, levels);
+    if (normal_power_log2 > 7) return fail(MI_ERR_INVALID, "%s: normal_power_log2 %u is above 7", who, normal_power_log2);
+    if (dilate > 256) return fail(MI_ERR_INVALID, "%s: dilate %u is above 256", who, dilate);
+    if (!(sigma_plane > 0.0f)) return fail(MI_ERR_INVALID, "%s: sigma_plane must be > 0 (+inf turns the plane weight off)", who);
+    if (!(reach > 0.0f)) return fail(MI_ERR_INVALID, "%s: reach must be > 0 (+inf turns the reach test off)", who);
+    if (!(sigma_color > 0.0f)) return fail(MI_ERR_INVALID, "%s: sigma_color must be > 0 (+inf turns the colour weight off)", who);
+    if (!c) return fail(MI_ERR_INVALID, "ctx is NULL");
+    return MI_OK;
+}
+
+// Queue the passes on `stream`; every pointer is a device pointer and d_out overlaps no input.  Pass p of levels + dilate reads what pass
+// p - 1 wrote; the passes alternate between the context's two images and the last one writes d_out.  The masks alternate likewise, and
+// the last one is written to d_valid when the caller wants it.
+static int lightmap_finish_device(mi_ctx* c, uint32_t width, uint32_t height, const float* d_image, const float* d_points,
+                                  const float* d_normals, uint32_t levels, uint32_t normal_power_log2, float sigma_plane, float reach,
+                                  float sigma_color, uint32_t dilate, float* d_out, uint8_t* d_valid, hipStream_t stream) {
+    const size_t n = (size_t)width * height, img = n * 3 * sizeof(float), msk = (n + 255) / 256 * 256;
+    MI_TRY(ensure(&c->d_lmf, &c->lmf_bytes, 2 * img + 2 * msk));
+    float* const ping[2] = { (float*)c->d_lmf, (float*)((char*)c->d_lmf + img) };
+    uint8_t* const mping[2] = { (uint8_t*)c->d_lmf + 2 * img, (uint8_t*)c->d_lmf + 2 * img + msk };
+    LmfArgs a{};
+    a.points = d_points; a.normals = d_normals;
+    a.width = width; a.height = height;
+    a.tiles_x = (width + kTile - 1) / kTile; a.tiles_y = (height + kTile - 1) / kTile;
+    a.npow = normal_power_log2; a.sigma_plane = sigma_plane; a.reach = reach; a.sigma_color = sigma_color;
+    const uint32_t passes = levels + dilate;
+    auto mask_target = [&](uint32_t k) { return (k == dilate && d_valid) ? d_valid : mping[k & 1u]; };
+    HIP_TRY(hipEventRecord(c->ev_start, stream));
+    a.src = d_image; a.dst = d_out; a.copy = passes == 0 ? 1u : 0u; a.mask_out = mask_target(0);
+    HIP_TRY(launch_lmf_mask(a, stream));
+    a.copy = 0;
+    for (uint32_t p = 0; p < passes; p++) {
+        a.dst = p + 1 == passes ? d_out : ping[p & 1u];
+        if (p < levels) {
+            a.step = 1u << p;
+            HIP_TRY(launch_lmf_atrous(a, a.step <= c->tune.lmf_lds_max_step, &c->lmf_big_lds_enabled, stream));
+        } else {
+            a.mask_in = mask_target(p - levels); a.mask_out = mask_target(p - levels + 1);
+            HIP_TRY(launch_lmf_dilate(a, stream));
+        }
+        a.src = a.dst;
+    }
+    HIP_TRY(hipEventRecord(c->ev_stop, stream));
+    c->ev_recorded = true; c->ms_summed = false;
+    return MI_OK;
+}
+
+extern "C" int mi_lightmap_finish_device(mi_ctx* c, uint32_t width, uint32_t height, const float* image, const float* points,
+                                         const float* normals, uint32_t levels, uint32_t normal_power_log2, float sigma_plane, float reach,
+                                         float sigma_color, uint32_t dilate, float* out_image, uint8_t* out_valid, void* stream) {
+    MI_TRY(check_lmf_args("mi_lightmap_finish_device", c, width, height, image, points, normals, levels, normal_power_log2, sigma_plane,
+                          reach, sigma_color, dilate, out_image));
+    const uintptr_t bytes = (uintptr_t)width * height * 3 * sizeof(float), o = (uintptr_t)out_image;
+    for (const float* in : { image, points, normals })
+        if (o < (uintptr_t)in + bytes && (uintptr_t)in < o + bytes)
+            return fail(MI_ERR_INVALID, "mi_lightmap_finish_device: out_image overlaps an input (the passes are never in place)");
+    HIP_TRY(hipSetDevice(c->device));
+    return lightmap_finish_device(c, width, height, image, points, normals, levels, normal_power_log2, sigma_plane, reach, sigma_color, dilate,
+                                  out_image, out_valid, (hipStream_t)stream);
+}
+
+extern "C" int mi_lightmap_finish(mi_ctx* c, uint32_t width, uint32_t height, const float* image, const float* points, const float* normals,
+                                  uint32_t levels, uint32_t normal_power_log2, float sigma_plane, float reach, float sigma_color,
+                                  uint32_t dilate, float* out_image, uint8_t* out_valid) {
+    MI_TRY(check_lmf_args("mi_lightmap_finish", c, width, height, image, points, normals, levels, normal_power_log2, sigma_plane, reach,
+                          sigma_color, dilate, out_image));
+    HIP_TRY(hipSetDevice(c->device));
+    const size_t n = (size_t)width * height, img = n * 3 * sizeof(float);
+    MI_TRY(ensure(&c->d_lmf_io, &c->lmf_io_bytes, 4 * img + n));
+    char* const io = (char*)c->d_lmf_io;
+    HIP_TRY(hipMemcpyAsync(io, image, img, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(io + img, points, img, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(io + 2 * img, normals, img, hipMemcpyHostToDevice, c->stream));
+    MI_TRY(lightmap_finish_device(c, width, height, (const float*)io, (const float*)(io + img), (const float*)(io + 2 * img), levels,
+                                  normal_power_log2, sigma_plane, reach, sigma_color, dilate, (float*)(io + 3 * img),
+                                  out_valid ? (uint8_t*)(io + 4 * img) : nullptr, c->stream));
+    HIP_TRY(hipMemcpyAsync(out_image, io + 3 * img, img, hipMemcpyDeviceToHost, c->stream));      // after the uploads: out_image may alias image
+    if (out_valid) HIP_TRY(hipMemcpyAsync(out_valid, io + 4 * img, n, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return MI_OK;
 }
 
 // ------------------------------------------------------------------ light probes (SH L2 radiance probes: the directions are drawn on the GPU)

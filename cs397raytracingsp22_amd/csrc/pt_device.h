@@ -415,4 +415,25 @@ struct LmArgs {
     int32_t* out_triangle;           // [rows][H][W] or nullptr
 };
 
+// ---- lightmap finishing (mi_lightmap_finish; pt_kernels.hip "lmf_*") ----
+// One pass of tracing.py lightmap_finish: lmf_mask (the covered mask from the normals, and the masked copy when there is no other pass),
+// lmf_atrous (one filter level, step `step`, one kTile x kTile tile per block) or lmf_dilate (one dilation pass).  Every pass reads `src`
+// (and `mask_in`) and writes `dst` (and `mask_out`): ping-pong, never in place.
+struct LmfArgs {
+    const float*   src;              // [H][W][3] the previous pass's image
+    const float*   points;           // [H][W][3] guides (lmf_atrous)
+    const float*   normals;          // [H][W][3] guides: all-zero = empty texel
+    float*         dst;              // [H][W][3]
+    const uint8_t* mask_in;          // [H][W] lmf_dilate: the previous pass's valid mask
+    uint8_t*       mask_out;         // [H][W] lmf_mask, lmf_dilate
+    uint32_t width, height, tiles_x, tiles_y;
+    uint32_t step;                   // lmf_atrous: s = 2^level
+    uint32_t npow;                   // normal_power_log2
+    uint32_t copy;                   // lmf_mask: also write dst = covered ? src : +0
+    float sigma_plane, reach, sigma_color;
+};
+// Largest step whose tile plus 2 s halo (9 planes of (kTile + 4 s)^2 f32) fits the CU's 160 KiB of LDS
+constexpr uint32_t kLmfMaxLdsStep = 8;
+inline size_t lmf_lds_bytes(uint32_t step) { const size_t e = (size_t)kTile + 4u * step; return 9u * e * e * sizeof(float); }
+
 }  // namespace pt

@@ -3780,7 +3780,167 @@ __global__ __launch_bounds__(kBlock) void lm_resolve(const LmArgs a) {
     }
 }
 
+// ---------------------------------------------------------------- lightmap finishing (mi_lightmap_finish)
+// tracing.py lightmap_finish on the device, pass by pass: an edge-aware a-trous filter guided by the atlas's own point and normal tables,
+// then gutter dilation.  Pure f32, the helper's operations in the helper's order (no fused multiply-add: the pragma above; IEEE division),
+// a fixed tap order per texel, nothing summed across threads: the image is the helper's bit for bit and does not depend on scheduling.
+// No address depends on a table value: a non-finite texel spoils its own footprint only.
+__device__ __forceinline__ bool lmf_covered(float nx, float ny, float nz) { return !(nx == 0.0f && ny == 0.0f && nz == 0.0f); }
+
+// The covered mask from the guide normals; with a.copy also dst = covered ? src : +0 (the whole of a call with no level and no pass)
+__global__ __launch_bounds__(kBlock) void lmf_mask(const LmfArgs a) {
+    const size_t n = (size_t)a.width * a.height, i = (size_t)blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n) return;
+    const bool cov = lmf_covered(a.normals[3 * i], a.normals[3 * i + 1], a.normals[3 * i + 2]);
+    a.mask_out[i] = cov ? 1 : 0;
+    if (a.copy)
+        for (int k = 0; k < 3; k++) a.dst[3 * i + k] = cov ? a.src[3 * i + k] : 0.0f;
+}
+
+// One filter level.  One block per kTile x kTile tile; a thread owns the texels (x, y + 8 k), k < 4, as lm_resolve does.
+// LDS form: the tile and its 2 s halo are staged as NINE PLANES of (kTile + 4 s)^2 f32 (colour, point, normal; the mask is the normal):
+//   a wave's lanes read 32 consecutive dwords of a plane row per tap, twice (two rows of the tile), so every ds_read_b32 is free of bank
+//   conflicts in both 32-lane halves, which 12-byte records read with ds_read_b96 (16-byte alignment, 8-lane groups) are not.  Texels
+//   of the halo that lie outside the image are staged as empty ones.
+// Direct form: the taps come straight from HBM (neighbouring lanes read neighbouring texels); for large steps the halo dwarfs the tile.
+// Both forms visit the same taps in the same order with the same values: identical bits.
+template <bool LDS> __global__ __launch_bounds__(kBlock) void lmf_atrous(const LmfArgs a) {
+    extern __shared__ float lmf_lds[];
+    const int s = (int)a.step, W = (int)a.width, H = (int)a.height;
+    const int x0 = (int)(blockIdx.x % a.tiles_x) * kTile, y0 = (int)(blockIdx.x / a.tiles_x) * kTile;
+    const int E = kTile + 4 * s, EE = E * E;
+    if (LDS) {
+        for (int i = (int)threadIdx.x; i < EE; i += kBlock) {
+            const int ey = i / E, ex = i - ey * E;
+            const int gx = x0 - 2 * s + ex, gy = y0 - 2 * s + ey;
+            float v[9] = { 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f };
+            if (gx >= 0 && gx < W && gy >= 0 && gy < H) {
+                const size_t at = 3 * ((size_t)gy * W + gx);
+                for (int k = 0; k < 3; k++) { v[k] = a.src[at + k]; v[3 + k] = a.points[at + k]; v[6 + k] = a.normals[at + k]; }
+            }
+            for (int k = 0; k < 9; k++) lmf_lds[k * EE + i] = v[k];
+        }
+        __syncthreads();
+    }
+    // texel (qx, qy) of the image: colour, point, normal (LDS: the tile's window; out-of-image halo texels are empty there)
+    auto fetch3 = [&](int plane, int qx, int qy, float* out) {
+        if (LDS) {
+            const int i = (qy - y0 + 2 * s) * E + (qx - x0 + 2 * s);
+            for (int k = 0; k < 3; k++) out[k] = lmf_lds[(plane + k) * EE + i];
+        } else {
+            const float* t = plane == 0 ? a.src : plane == 3 ? a.points : a.normals;
+            const size_t at = 3 * ((size_t)qy * W + qx);
+            for (int k = 0; k < 3; k++) out[k] = t[at + k];
+        }
+    };
+    const float H5[5] = { 0.0625f, 0.25f, 0.375f, 0.25f, 0.0625f };
+    const float fs = (float)s;
+    const float r = a.reach * fs, rr = r * r, sig_c = a.sigma_color / fs;
+    const int gx = x0 + (int)(threadIdx.x & 31u);
+    for (int k4 = 0; k4 < 4; k4++) {
+        const int gy = y0 + (int)(threadIdx.x >> 5) + 8 * k4;
+        if (gx >= W || gy >= H) continue;
+        float cp[3], pp[3], np[3];
+        fetch3(6, gx, gy, np);
+        float out[3] = { 0.0f, 0.0f, 0.0f };
+        if (lmf_covered(np[0], np[1], np[2])) {
+            fetch3(0, gx, gy, cp); fetch3(3, gx, gy, pp);
+            float sw = 0.0f, sc[3] = { 0.0f, 0.0f, 0.0f };
+#pragma unroll
+            for (int dy = -2; dy <= 2; dy++) {
+#pragma unroll
+                for (int dx = -2; dx <= 2; dx++) {
+                    const int qx = gx + s * dx, qy = gy + s * dy;
+                    if (qx < 0 || qx >= W || qy < 0 || qy >= H) continue;
+                    float nq[3];
+                    fetch3(6, qx, qy, nq);
+                    if (!lmf_covered(nq[0], nq[1], nq[2])) continue;
+                    float cq[3], pq[3];
+                    fetch3(0, qx, qy, cq); fetch3(3, qx, qy, pq);
+                    const float D[3] = { pq[0] - pp[0], pq[1] - pp[1], pq[2] - pp[2] };
+                    // the reach test: a hard cut; the centre tap passes without it (literally its bound is inf * 0 for an infinite reach)
+                    const float d2 = (D[0] * D[0] + D[1] * D[1]) + D[2] * D[2];
+                    if ((dx != 0 || dy != 0) && !(d2 <= rr * (float)(dx * dx + dy * dy))) continue;
+                    const float h = H5[dy + 2] * H5[dx + 2];
+                    float wn = fmaxf(0.0f, (np[0] * nq[0] + np[1] * nq[1]) + np[2] * nq[2]);
+                    for (uint32_t i = 0; i < a.npow; i++) wn = wn * wn;
+                    const float dpl = fabsf((np[0] * D[0] + np[1] * D[1]) + np[2] * D[2]);
+                    const float wp = fmaxf(0.0f, 1.0f - dpl / a.sigma_plane);
+                    const float dc = (fabsf(cq[0] - cp[0]) + fabsf(cq[1] - cp[1])) + fabsf(cq[2] - cp[2]);
+                    const float wc = fmaxf(0.0f, 1.0f - dc / sig_c);
+                    const float w = ((h * wn) * wp) * wc;
+                    sw = sw + w;
+                    for (int k = 0; k < 3; k++) sc[k] = sc[k] + w * cq[k];
+                }
+            }
+            for (int k = 0; k < 3; k++) out[k] = sc[k] / sw;
+        }
+        const size_t at = 3 * ((size_t)gy * W + gx);
+        for (int k = 0; k < 3; k++) a.dst[at + k] = out[k];
+    }
+}
+
+// One dilation pass: a texel that is not valid and has a valid 8-neighbour in the PREVIOUS pass's mask takes the mean of those neighbours'
+// colours (summed in dy-outer, dx-inner order from +0) and turns valid; valid texels are copied.
+__global__ __launch_bounds__(kBlock) void lmf_dilate(const LmfArgs a) {
+    const size_t n = (size_t)a.width * a.height, i = (size_t)blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n) return;
+    const int W = (int)a.width, H = (int)a.height;
+    const int y = (int)(i / a.width), x = (int)(i - (size_t)y * a.width);
+    float out[3] = { 0.0f, 0.0f, 0.0f };
+    uint8_t valid = a.mask_in[i];
+    if (valid) {
+        for (int k = 0; k < 3; k++) out[k] = a.src[3 * i + k];
+    } else {
+        float sum[3] = { 0.0f, 0.0f, 0.0f };
+        int count = 0;
+        for (int dy = -1; dy <= 1; dy++)
+            for (int dx = -1; dx <= 1; dx++) {
+                const int qx = x + dx, qy = y + dy;
+                if ((dx == 0 && dy == 0) || qx < 0 || qx >= W || qy < 0 || qy >= H) continue;
+                const size_t j = (size_t)qy * W + qx;
+                if (!a.mask_in[j]) continue;
+                for (int k = 0; k < 3; k++) sum[k] = sum[k] + a.src[3 * j + k];
+                count++;
+            }
+        if (count) {
+            for (int k = 0; k < 3; k++) out[k] = sum[k] / (float)count;
+            valid = 1;
+        }
+    }
+    for (int k = 0; k < 3; k++) a.dst[3 * i + k] = out[k];
+    a.mask_out[i] = valid;
+}
+
 // ---------------------------------------------------------------- launch wrappers
+// lightmap finishing: one pass per launch.  lmf_atrous stages through LDS when `lds`; a window above 64 KB needs the opt-in, which
+// belongs to the function on the current device, so the calling context keeps its record (as launch_walker's big_lds_enabled).
+hipError_t launch_lmf_mask(const LmfArgs& a, hipStream_t stream) {
+    const size_t n = (size_t)a.width * a.height;
+    hipLaunchKernelGGL(lmf_mask, dim3((uint32_t)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, stream, a);
+    return hipGetLastError();
+}
+hipError_t launch_lmf_atrous(const LmfArgs& a, bool lds, bool* big_lds_enabled, hipStream_t stream) {
+    const dim3 grid(a.tiles_x * a.tiles_y);
+    if (!lds) {
+        hipLaunchKernelGGL(lmf_atrous<false>, grid, dim3(kBlock), 0, stream, a);
+        return hipGetLastError();
+    }
+    if (a.step > kLmfMaxLdsStep) return hipErrorInvalidValue;
+    const size_t bytes = lmf_lds_bytes(a.step);
+    if (bytes > 64u * 1024u && !*big_lds_enabled) {
+        const hipError_t e = hipFuncSetAttribute((const void*)lmf_atrous<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        if (e != hipSuccess) return e;
+        *big_lds_enabled = true;
+    }
+    hipLaunchKernelGGL(lmf_atrous<true>, grid, dim3(kBlock), bytes, stream, a);
+    return hipGetLastError();
+}
+hipError_t launch_lmf_dilate(const LmfArgs& a, hipStream_t stream) {
+    const size_t n = (size_t)a.width * a.height;
+    hipLaunchKernelGGL(lmf_dilate, dim3((uint32_t)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, stream, a);
+    return hipGetLastError();
+}
 // lightmap atlas: count, scan, (the caller may size the list here,) fill, resolve
 hipError_t launch_lm_count(const LmArgs& a, hipStream_t stream) {
     if (a.n_triangles) hipLaunchKernelGGL(lm_bin<false>, dim3((a.n_triangles + kBlock - 1) / kBlock), dim3(kBlock), 0, stream, a);

@@ -213,6 +213,29 @@ struct Scene : Intersectable {                         // tracing.rs:213-218; `i
         return img;
     }
 
+    // Finish a baked lightmap through mi_lightmap_finish: the edge-aware a-trous filter guided by the atlas's centre table (points / normals:
+    // mi_lightmap_texels with rows = 1, no jitter), then `dilate` passes of gutter dilation.  image / points / normals are [H][W][3]; `image` is
+    // the bake's f32 image (bake-side `linear`).  INFINITY turns sigma_plane, reach or sigma_color off.  Returns the finished [H][W][3] image;
+    // `valid` takes the [H][W] mask (1 = covered or filled by the dilation).  Needs no scene: a static member.
+    static std::vector<float> finish_lightmap(const std::vector<float>& image, const std::vector<float>& points, const std::vector<float>& normals,
+                                              uint32_t width, uint32_t height, uint32_t levels = 3, uint32_t normal_power_log2 = 5,
+                                              float sigma_plane = INFINITY, float reach = INFINITY, float sigma_color = INFINITY,
+                                              uint32_t dilate = 4, int device = 0, std::vector<uint8_t>* valid = nullptr) {
+        const size_t n = (size_t)width * height;
+        if (image.size() != n * 3 || points.size() != n * 3 || normals.size() != n * 3)
+            throw std::runtime_error("mi_rt: image, points and normals must all be [H][W][3]");
+        std::vector<float> out(n * 3);
+        if (valid) valid->resize(n);
+        mi_ctx* ctx = nullptr;
+        mi_check(mi_ctx_create(device, &ctx));
+        const int rc = mi_lightmap_finish(ctx, width, height, image.data(), points.data(), normals.data(), levels, normal_power_log2, sigma_plane,
+                                          reach, sigma_color, dilate, out.data(), valid ? valid->data() : nullptr);
+        const std::string err = rc == MI_OK ? "" : mi_last_error();
+        mi_ctx_destroy(ctx);
+        if (rc != MI_OK) throw std::runtime_error("mi_rt: " + err);
+        return out;
+    }
+
     // Light probes through mi_render_probes: points is [rows_per_pixel][H][W][3], one probe position per pixel, rows_per_pixel = 1 or
     // camera.aa_sample_count.  Sample s of probe (x, y) leaves its point along rand_sphere_vec (Isotropic::scatter's direction,
     // materials.rs:158-166: uniform over the sphere), drawn on the GPU from the stream (seed, W * H + y * W + x, s); its path draws from

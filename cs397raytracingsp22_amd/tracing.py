@@ -453,6 +453,103 @@ def _lightmap_texels_jittered(positions, normals, texcoords, indices, width, hei
     return out + (tri,) if with_triangle else out
 
 
+_LMF_TAPS = tuple((dy, dx) for dy in range(-2, 3) for dx in range(-2, 3))                          # dy outer, dx inner
+_LMF_RING = tuple((dy, dx) for dy in (-1, 0, 1) for dx in (-1, 0, 1) if (dy, dx) != (0, 0))        # the 8-neighbours, same order
+
+
+def check_finish_tables(image, points, normals):
+    """(image, points, normals) as contiguous float32 [H, W, 3] arrays of one shape, 1 <= W, H <= 32768, for lightmap_finish"""
+    img = np.ascontiguousarray(image, np.float32)
+    P = np.ascontiguousarray(points, np.float32)
+    N = np.ascontiguousarray(normals, np.float32)
+    if img.ndim != 3 or img.shape[2] != 3 or P.shape != img.shape or N.shape != img.shape:
+        raise ValueError(f"image, points and normals must be [H, W, 3] arrays of one shape, got {img.shape}, {P.shape} and {N.shape}")
+    if not (1 <= img.shape[0] <= 32768 and 1 <= img.shape[1] <= 32768):
+        raise ValueError(f"width and height must be in 1 .. 32768, got {img.shape[1]} x {img.shape[0]}")
+    return img, P, N
+
+
+def lightmap_finish(image, points, normals, levels: int = 3, normal_power_log2: int = 5, sigma_plane: float = float("inf"),
+                    reach: float = float("inf"), sigma_color: float = float("inf"), dilate: int = 4):
+    """Finish a baked lightmap on the host (numpy only): an edge-aware a-trous filter guided by the atlas's own table, then gutter
+    dilation.  This is the DEFINITION of mi_lightmap_finish, which equals it bit for bit.  `image` [H, W, 3] f32 is the raw bake
+    (bake_lightmap's f32 image: empty texels zero), `points` and `normals` [H, W, 3] f32 the CENTRE table of the atlas (lightmap_texels
+    without jitter, also for a jittered bake).  Returns (out [H, W, 3] f32, valid [H, W] bool).
+    A texel is covered when its normal is not all-zero.  Everything is f32, one rounding per operation, in the order written below.
+    Filter: levels i = 0 .. levels-1, step s = 2^i, each reading the previous level's image.  A covered texel p visits the 25 taps
+    q = p + s (dx, dy), dy outer, dx inner, both -2 .. 2, skipping taps outside the image and empty ones, and those the reach test
+    rejects: with D = P_q - P_p a tap other than the centre is kept only when |D|^2 <= (reach s)^2 (dx^2 + dy^2) — `reach` is the world
+    length one texel step may span, a hard cut against taps that land in another chart.  Its weight is the product of the B3 kernel
+    H5[dy] H5[dx], the normal weight max(0, n_p . n_q)^(2^normal_power_log2), the plane weight max(0, 1 - |n_p . D| / sigma_plane)
+    and the colour weight max(0, 1 - (|dr| + |dg| + |db|) / (sigma_color / s)); the texel becomes the weighted mean.  inf turns
+    sigma_plane, reach or sigma_color off.  Empty texels are +0.0.
+    Dilation: `dilate` passes; in each a texel that is not valid but has valid 8-neighbours in the previous pass's state takes their
+    mean (summed dy outer, dx inner) and turns valid: texel t is filled in pass number Chebyshev-distance(t, covered).
+    Non-finite values spoil the texels whose footprint (radius 2 (2^levels - 1) + dilate) reaches them, and no others."""
+    f32 = np.float32
+    img, P, N = check_finish_tables(image, points, normals)
+    levels, npow, dilate = int(levels), int(normal_power_log2), int(dilate)
+    if not (0 <= levels <= 8 and 0 <= npow <= 7 and 0 <= dilate <= 256):
+        raise ValueError("levels must be in 0 .. 8, normal_power_log2 in 0 .. 7 and dilate in 0 .. 256")
+    sig_p, rch, sig_c0 = f32(sigma_plane), f32(reach), f32(sigma_color)
+    if not (sig_p > 0 and rch > 0 and sig_c0 > 0):
+        raise ValueError("sigma_plane, reach and sigma_color must be > 0 (inf turns one off)")
+    H, W = img.shape[:2]
+    zero, one = f32(0.0), f32(1.0)
+    H5 = (f32(0.0625), f32(0.25), f32(0.375), f32(0.25), f32(0.0625))
+    covered = (N[..., 0] != 0) | (N[..., 1] != 0) | (N[..., 2] != 0)
+    cur = np.where(covered[..., None], img, zero)
+    with np.errstate(all="ignore"):
+        for level in range(levels):
+            s = 1 << level
+            fs = f32(s)
+            r = rch * fs
+            rr = r * r
+            sig_c = sig_c0 / fs
+            pad = 2 * s
+            cpad, ppad, npad = (np.pad(t, ((pad, pad), (pad, pad), (0, 0))) for t in (cur, P, N))      # beyond the image: empty texels
+            sw = np.zeros((H, W), f32)
+            sc = np.zeros((H, W, 3), f32)
+            for dy, dx in _LMF_TAPS:
+                ys, xs = pad + s * dy, pad + s * dx
+                cq, pq, nq = (t[ys:ys + H, xs:xs + W] for t in (cpad, ppad, npad))
+                take = covered & ((nq[..., 0] != 0) | (nq[..., 1] != 0) | (nq[..., 2] != 0))
+                D = pq - P
+                d2 = (D[..., 0] * D[..., 0] + D[..., 1] * D[..., 1]) + D[..., 2] * D[..., 2]
+                if dx != 0 or dy != 0:                # the centre always passes (0 <= 0; inf * 0 must not reject it)
+                    take = take & (d2 <= rr * f32(dx * dx + dy * dy))
+                h = H5[dy + 2] * H5[dx + 2]
+                wn = np.fmax(zero, (N[..., 0] * nq[..., 0] + N[..., 1] * nq[..., 1]) + N[..., 2] * nq[..., 2])
+                for _ in range(npow):
+                    wn = wn * wn
+                dpl = np.abs((N[..., 0] * D[..., 0] + N[..., 1] * D[..., 1]) + N[..., 2] * D[..., 2])
+                wp = np.fmax(zero, one - dpl / sig_p)
+                dc = (np.abs(cq[..., 0] - cur[..., 0]) + np.abs(cq[..., 1] - cur[..., 1])) + np.abs(cq[..., 2] - cur[..., 2])
+                wc = np.fmax(zero, one - dc / sig_c)
+                w = ((h * wn) * wp) * wc
+                sw = np.where(take, sw + w, sw)
+                sc = np.where(take[..., None], sc + w[..., None] * cq, sc)
+            cur = np.where(covered[..., None], sc / sw[..., None], zero)
+        valid = covered.copy()
+        cur = np.ascontiguousarray(cur, f32)
+        for _ in range(dilate):
+            prev_valid, prev = valid.copy(), cur.copy()
+            vpad = np.pad(prev_valid, 1)
+            near = np.zeros((H, W), bool)
+            for dy, dx in _LMF_RING:
+                near |= vpad[1 + dy:1 + dy + H, 1 + dx:1 + dx + W]
+            for y, x in np.argwhere(near & ~prev_valid):         # the pass's frontier, texel by texel: the order of the sum is the contract
+                total, count = np.zeros(3, f32), 0
+                for dy, dx in _LMF_RING:
+                    qy, qx = y + dy, x + dx
+                    if 0 <= qy < H and 0 <= qx < W and prev_valid[qy, qx]:
+                        total = total + prev[qy, qx]
+                        count += 1
+                cur[y, x] = total / f32(count)
+                valid[y, x] = True
+    return cur, valid
+
+
 def equirect_dirs(lon, lat) -> np.ndarray:
     """Unit directions [..., 3] float32 of a latitude-longitude panorama for arrays of longitudes / latitudes in radians:
     (sin lon cos lat, sin lat, -cos lon cos lat) — longitude 0 looks down -z, +pi/2 down +x, +-pi (the seam) down +z; latitude +pi/2 is
@@ -649,6 +746,30 @@ class Context:
             tri.ctypes.data if tri is not None else None, C.byref(st)))
         del keep
         return f32, u8, sig, tri, st
+
+    def lightmap_finish(self, image, points, normals, levels: int = 3, normal_power_log2: int = 5, sigma_plane: float = float("inf"),
+                        reach: float = float("inf"), sigma_color: float = float("inf"), dilate: int = 4):
+        """mi_lightmap_finish: the edge-aware a-trous filter and the gutter dilation of the helper lightmap_finish on the GPU, bit for
+        bit.  `image` is the raw bake [H, W, 3] f32, `points` and `normals` the atlas's centre table ([H, W, 3], or lightmap_texels'
+        [1, H, W, 3]).  Returns (out [H, W, 3] f32, valid [H, W] bool).  No scene is needed."""
+        P, N = np.asarray(points), np.asarray(normals)
+        img, P, N = check_finish_tables(image, P[0] if P.ndim == 4 and P.shape[0] == 1 else P, N[0] if N.ndim == 4 and N.shape[0] == 1 else N)
+        H, W = img.shape[:2]
+        out = np.empty((H, W, 3), np.float32)
+        valid = np.empty((H, W), np.uint8)
+        abi.check(self._lib.mi_lightmap_finish(self._h, W, H, img.ctypes.data, P.ctypes.data, N.ctypes.data, levels, normal_power_log2,
+                                               sigma_plane, reach, sigma_color, dilate, out.ctypes.data, valid.ctypes.data))
+        return out, valid.astype(bool)
+
+    def lightmap_finish_device(self, width: int, height: int, d_image: int, d_points: int, d_normals: int, d_out_image: int,
+                               d_out_valid: Optional[int] = None, levels: int = 3, normal_power_log2: int = 5,
+                               sigma_plane: float = float("inf"), reach: float = float("inf"), sigma_color: float = float("inf"),
+                               dilate: int = 4, stream: Optional[int] = None):
+        """mi_lightmap_finish_device: the same for an image and a table held on the device (raw pointers, e.g. tensor.data_ptr(): three
+        [H, W, 3] f32 inputs, the [H, W, 3] f32 output, which must overlap none of them, and an optional [H, W] u8 mask).  Queued on
+        `stream`; the output can go straight into tonemap_device."""
+        abi.check(self._lib.mi_lightmap_finish_device(self._h, width, height, d_image, d_points, d_normals, levels, normal_power_log2,
+                                                      sigma_plane, reach, sigma_color, dilate, d_out_image, d_out_valid, stream))
 
     def render_probes(self, cam: Camera, points, seed: int = 1, want_f32=True, want_u8=True, want_sig=False,
                       flags: int = 0, max_state_bytes: int = 0):
@@ -1069,20 +1190,28 @@ class Scene:                         # tracing.rs:213-218
             ctx.close()
 
     def bake_lightmap(self, mesh, width: int, height: int, samples: int, jitter: bool = True, offset: float = 1e-3, seed: int = 1,
-                      device: int = 0) -> np.ndarray:
+                      device: int = 0, finish: Optional[dict] = None):
         """The lightmap of `mesh` (a StaticMesh of this scene, or any objload.Mesh) in one call (mi_bake_lightmap): the RgbImage bytes
         [height, width, 3] u8 of its uv atlas, `samples` cosine-distributed gathers per texel, each from its own jittered position inside
         the texel (jitter) or all from the centre.  The atlas is rasterised, sampled and traced on the GPU: only the mesh goes up and the
         image comes back.  This scene's camera supplies path_depth, max_trace_dist and gamma; `offset` lifts the points off the surface
-        along the normal."""
+        along the normal.
+        `finish` (None: the raw bake, as above) is a dict of lightmap_finish's parameters (levels, normal_power_log2, sigma_plane, reach,
+        sigma_color, dilate; {} for the defaults): the bake's f32 image is then filtered and dilated on the GPU (mi_lightmap_finish),
+        guided by the atlas's centre table (Context.lightmap_texels with rows=1, the same offset), and the call returns the finished
+        lightmap (out [height, width, 3] f32, valid [height, width] bool) instead of bytes."""
         from dataclasses import replace
         cam = replace(self.camera, screen_width=int(width), screen_height=int(height), aa_sample_count=int(samples))
         check_point_table(cam, np.zeros((height, width, 3), np.float32), np.zeros((height, width, 3), np.float32))
         ctx = Context(device)
         try:
             ctx.upload(self.flatten())
-            _, u8, _, _, _ = ctx.bake_lightmap(cam, mesh, jitter=jitter, offset=offset, seed=seed, want_f32=False, want_u8=True)
-            return u8
+            if finish is None:
+                _, u8, _, _, _ = ctx.bake_lightmap(cam, mesh, jitter=jitter, offset=offset, seed=seed, want_f32=False, want_u8=True)
+                return u8
+            f32, _, _, _, _ = ctx.bake_lightmap(cam, mesh, jitter=jitter, offset=offset, seed=seed, want_f32=True, want_u8=False)
+            points, normals, _ = ctx.lightmap_texels(mesh, int(width), int(height), rows=1, offset=offset, want_triangle=False)
+            return ctx.lightmap_finish(f32, points, normals, **finish)
         finally:
             ctx.close()
 

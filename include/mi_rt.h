@@ -500,6 +500,53 @@ int  mi_lightmap_texels_device(mi_ctx* ctx, const mi_mesh* mesh, uint32_t width,
 int  mi_bake_lightmap(mi_ctx* ctx, const mi_camera_desc* cam, const mi_render_opts* opts, const mi_mesh* mesh, uint32_t flags,
                       float offset, float* out_rgb_f32, uint8_t* out_rgb_u8, uint32_t* out_sig, int32_t* out_triangle, mi_stats* stats);
 
+/* ---- lightmap finishing: edge-aware a-trous filter and gutter dilation (added within ABI version 5: detect by symbol lookup) ----
+ * Turns the raw per-texel mean of a bake (mi_bake_lightmap's out_rgb_f32: empty texels exactly zero) into an image a renderer can sample:
+ *   a denoise guided by the atlas's own world-space point and normal per texel, which cannot leak light between charts that are
+ *   neighbours in uv only, then edge padding, so that bilinear filtering and mip-mapping do not smear black onto the surface at uv seams.
+ *   These are the semantics of lightmap_finish (Python), which is the definition; the result equals the helper's BIT FOR BIT: pure f32,
+ *   every operation one of + - * /, fabsf, fmaxf, comparisons and exact int-to-float conversions, in the order written here, no fused
+ *   multiply-add, IEEE division.  No scene is needed.
+ * Layout: `image`, `points`, `normals` and `out_image` are [H][W][3] f32, out_valid [H][W] bytes (0 / 1; may be NULL).  The guides are the
+ *   CENTRE table (mi_lightmap_texels with rows = 1 and no MI_LM_JITTER), also for a jittered bake.  A texel is covered when its guide
+ *   normal is not all-zero (either sign of zero), the empty-texel mark of mi_render_points; normals and points are used as given.
+ * Filter: levels i = 0 .. levels-1 with step s = 2^i, each reading the previous level's image (ping-pong, never in place).  For a covered
+ *   texel p the 25 taps q = p + s (dx, dy), dy outer -2 .. 2, dx inner -2 .. 2; a tap outside the image or on an empty texel is skipped.
+ *   With D = P_q - P_p:
+ *     h  = H5[dy+2] * H5[dx+2], H5 = { 1/16, 1/4, 3/8, 1/4, 1/16 }
+ *     wn = fmaxf(0, (n_p.x n_q.x + n_p.y n_q.y) + n_p.z n_q.z), then wn = wn * wn repeated normal_power_log2 times
+ *     wp = fmaxf(0, 1 - fabsf((n_p.x D.x + n_p.y D.y) + n_p.z D.z) / sigma_plane)
+ *     reach: the tap is accepted only when (D.x D.x + D.y D.y) + D.z D.z <= (r r) (float)(dx dx + dy dy), r = reach * (float)s: `reach`
+ *       is the world length one texel step may span, a hard cut against taps that land in another chart.  The centre tap is accepted
+ *       without the comparison (0 <= 0 for a finite reach; taken literally an infinite reach would make its bound inf * 0).
+ *     wc = fmaxf(0, 1 - ((|dr| + |dg|) + |db|) / (sigma_color / (float)s)), the differences between the current level's colours at q and p
+ *     w  = ((h wn) wp) wc;  sw = sw + w;  sc[k] = sc[k] + w c_q[k]
+ *   and the texel becomes sc / sw.  Empty texels are +0.0 at every level.  +inf for sigma_plane, reach or sigma_color turns that
+ *   weight off (1 - x / inf == 1 for finite x).
+ * Dilation: `dilate` passes after the filter, ping-pong again; valid starts as covered.  In one pass a texel that is not valid and has a
+ *   valid 8-neighbour in the PREVIOUS pass's state takes the f32 sum of those neighbours' colours — dy outer -1 .. 1, dx inner -1 .. 1,
+ *   without the centre, added in that order from +0.0 — divided by (float)count, and is valid from the next pass on.  Valid texels never
+ *   change.  A texel turns valid in the pass that equals its Chebyshev distance from the nearest covered texel.
+ * levels == 0 && dilate == 0 copies covered texels and zeroes empty ones.  An all-empty table is MI_OK: a zero image, out_valid all 0.
+ * Non-finite image or guide values are not rejected and never fault; they give unspecified values only for texels whose footprint
+ *   (Chebyshev radius 2 (2^levels - 1) + dilate) reaches them; every other texel keeps the bits of the clean run.  No address depends on
+ *   a table value.  The result does not depend on scheduling: no atomics, nothing is summed across threads.
+ * MI_ERR_INVALID (each with a message, checked before the context, nothing is launched): NULL image, points, normals or out_image; width
+ *   or height of 0 or above 32768; levels > 8, normal_power_log2 > 7, dilate > 256; a sigma_plane, reach or sigma_color that is NaN or <= 0.
+ * Scratch: two [H][W][3] f32 images and two [H][W] byte masks in a buffer the context owns (grown on demand, freed with the context,
+ *   never the buffers mi_reserve sized; MI_ERR_OOM if it cannot be allocated).  One kernel per level and per pass (a level stages its
+ *   32 x 32 tile and halo in LDS for small steps and reads HBM directly for large ones: the same bits); mi_last_kernel_ms reports
+ *   their sum.
+ * mi_lightmap_finish: HOST pointers, blocking; the tables pass through a buffer the context owns; out_image may alias image.
+ * mi_lightmap_finish_device: DEVICE pointers on ctx's device.  Queues on `stream` and does not synchronise, except when it has to grow
+ *   its scratch.  An out_image that overlaps image, points or normals is MI_ERR_INVALID. */
+int  mi_lightmap_finish(mi_ctx* ctx, uint32_t width, uint32_t height, const float* image, const float* points, const float* normals,
+                        uint32_t levels, uint32_t normal_power_log2, float sigma_plane, float reach, float sigma_color,
+                        uint32_t dilate, float* out_image, uint8_t* out_valid);
+int  mi_lightmap_finish_device(mi_ctx* ctx, uint32_t width, uint32_t height, const float* image, const float* points, const float* normals,
+                               uint32_t levels, uint32_t normal_power_log2, float sigma_plane, float reach, float sigma_color,
+                               uint32_t dilate, float* out_image, uint8_t* out_valid, void* stream);
+
 /* ---- light probes: SH L2 radiance probes with the directions drawn on the GPU (added within ABI version 5: detect by symbol lookup) ----
  * mi_render_points without normals and with a second output.  One "pixel" is one probe, a point in free space; its samples leave it in
  *   directions uniform over the whole sphere, and beside their mean the call returns the radiance field's projection onto the nine real

@@ -117,6 +117,14 @@ extern "C" {
     pub fn mi_bake_lightmap(ctx: *mut mi_ctx, cam: *const mi_camera_desc, opts: *const mi_render_opts, mesh: *const mi_mesh, flags: u32,
                             offset: f32, out_rgb_f32: *mut f32, out_rgb_u8: *mut u8, out_sig: *mut u32, out_triangle: *mut i32,
                             stats: *mut mi_stats) -> c_int;
+    // lightmap finishing (added within ABI 5): edge-aware a-trous filter and gutter dilation; image / points / normals / out_image are
+    // [H][W][3], out_valid [H][W] bytes or null
+    pub fn mi_lightmap_finish(ctx: *mut mi_ctx, width: u32, height: u32, image: *const f32, points: *const f32, normals: *const f32,
+                              levels: u32, normal_power_log2: u32, sigma_plane: f32, reach: f32, sigma_color: f32,
+                              dilate: u32, out_image: *mut f32, out_valid: *mut u8) -> c_int;
+    pub fn mi_lightmap_finish_device(ctx: *mut mi_ctx, width: u32, height: u32, image: *const f32, points: *const f32, normals: *const f32,
+                                     levels: u32, normal_power_log2: u32, sigma_plane: f32, reach: f32, sigma_color: f32,
+                                     dilate: u32, out_image: *mut f32, out_valid: *mut u8, stream: *mut c_void) -> c_int;
     // light probes (added within ABI 5): points is [rows_per_pixel][H][W][3]; out_sh [H][W][9][3], d_compact_sh [tiles_padded][1024][27]
     pub fn mi_render_probes(ctx: *mut mi_ctx, cam: *const mi_camera_desc, opts: *const mi_render_opts,
                             points: *const f32, rows_per_pixel: u32, out_sh: *mut f32,

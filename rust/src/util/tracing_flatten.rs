@@ -213,6 +213,29 @@ impl Scene {
         img
     }
 
+    /// Finish a baked lightmap (mi_lightmap_finish): the edge-aware a-trous filter guided by the atlas's centre table (`points`, `normals`:
+    /// mi_lightmap_texels with rows = 1, no jitter), then `dilate` passes of gutter dilation.  `image` is the bake's f32 image; all three hold
+    /// height x width texels, row-major.  f32::INFINITY turns sigma_plane, reach or sigma_color off.  Returns the finished image and the valid
+    /// mask (1 = covered or filled by the dilation).  Needs no scene: an associated function.
+    pub fn finish_lightmap(image: &[[f32; 3]], points: &[[f32; 3]], normals: &[[f32; 3]], width: u32, height: u32, levels: u32,
+                           normal_power_log2: u32, sigma_plane: f32, reach: f32, sigma_color: f32, dilate: u32) -> (Vec<[f32; 3]>, Vec<u8>) {
+        let n = width as usize * height as usize;
+        assert!(image.len() == n && points.len() == n && normals.len() == n, "mi_rt: image, points and normals must hold height * width texels");
+        let mut out = vec![[0.0f32; 3]; n];
+        let mut valid = vec![0u8; n];
+        unsafe {
+            let mut ctx = std::ptr::null_mut();
+            assert_eq!(mi_rt::mi_ctx_create(0, &mut ctx), 0, "{}", mi_rt::last_error());
+            let rc = mi_rt::mi_lightmap_finish(ctx, width, height, image.as_ptr() as *const f32, points.as_ptr() as *const f32,
+                                               normals.as_ptr() as *const f32, levels, normal_power_log2, sigma_plane, reach, sigma_color, dilate,
+                                               out.as_mut_ptr() as *mut f32, valid.as_mut_ptr());
+            let msg = mi_rt::last_error();
+            mi_rt::mi_ctx_destroy(ctx);
+            assert_eq!(rc, 0, "{}", msg);
+        }
+        (out, valid)
+    }
+
     /// Light probes (mi_render_probes): `points` holds `rows_per_pixel` x height x width probe positions, row-major ([row][y][x]),
     /// rows_per_pixel = 1 or camera.aa_sample_count.  Sample s of probe (x, y) leaves its point along rand_sphere_vec (what
     /// Isotropic::scatter returns: uniform over the sphere), drawn on the GPU from the stream (seed, width * height + y * width + x, s),

@@ -62,7 +62,17 @@ resident, rows = 1 and rows = 16 jittered, 5 warm-up calls then --calls timed on
 blocking calls, --atlas-bakes times each, alternating: mi_bake_lightmap (mesh up, table made on the GPU, render, image down) against
 lightmap_texels + mi_render_points (table made on the host, uploaded, the same render).  The tool checks that the GPU's triangle plane
 equals the helper's and that the two bakes give the same bytes.  --atlas-grid N replaces the drone (1736 triangles in this repository's
-asset) by a height field of N x N quads, 2 N^2 triangles, for the table's timings alone."""
+asset) by a height field of N x N quads, 2 N^2 triangles, for the table's timings alone.
+
+--mode finish times lightmap finishing (mi_lightmap_finish_device) on the drone's atlas at --finish-sizes (square, default 1024, 2048 and
+4096) with levels = 5 and dilate = 8, on device-resident tables: the guides are mi_lightmap_texels_device's centre table, the image is
+seeded noise on the covered texels (the passes' cost does not depend on the colours).  A call's kernels are timed by HIP events
+(mi_last_kernel_ms: their sum), 5 warm-up calls then --calls timed ones, medians; one pass's time is the difference between the medians of
+two calls that differ by that pass (levels = k + 1 against levels = k, both without dilation; levels = 5 with dilate = 8 against
+dilate = 0, divided by 8).  Every level is run in both forms of lmf_atrous, in two contexts created under the developer knob
+MI_RT_LMF_LDS_MAX_STEP (0: every step reads HBM directly; 8: steps 1 .. 8 stage tile and halo in LDS; step 16 has no LDS form), the whole
+call also in a context with the library's own threshold, and the images of all three are compared bit for bit.  Per level: effective GB/s on the compulsory bytes (60 B per texel: 36 B of guides and 12 B of
+colour read, 12 B written), beside the rate of a device-to-device copy that moves the same byte count, timed by events in the same run."""
 import argparse
 import json
 import os
@@ -497,6 +507,98 @@ def atlas_rows(ctx, size, calls, warmup, bakes, grid=0):
     return rows
 
 
+FINISH_LEVELS, FINISH_DILATE = 5, 8
+
+
+def finish_rows(size, calls, warmup):
+    """--mode finish at one atlas size; contexts of its own (the knob is read when a context is created)"""
+    dev = torch.device("cuda:0")
+    sc = scenes.config4(size, size, 1, 10)
+    drone = sc.objects[-1]
+    mesh = drone.mesh
+    n = size * size
+    t_mesh = [torch.from_numpy(np.array(a)).to(dev) for a in (mesh.positions, mesh.normals, mesh.texcoords, mesh.indices.view(np.int32))]
+    pts = torch.empty((size, size, 3), dtype=torch.float32, device=dev)
+    nrm = torch.empty((size, size, 3), dtype=torch.float32, device=dev)
+    out = {form: torch.empty((size, size, 3), dtype=torch.float32, device=dev) for form in ("direct", "lds", "default")}
+    valid = torch.empty((size, size), dtype=torch.uint8, device=dev)
+    ctxs = {}
+    for form, knob in (("direct", "0"), ("lds", "8")):
+        os.environ["MI_RT_LMF_LDS_MAX_STEP"] = knob
+        ctxs[form] = Context(0)
+    del os.environ["MI_RT_LMF_LDS_MAX_STEP"]
+    ctxs["default"] = Context(0)                     # the library's own threshold
+    ctxs["lds"].lightmap_texels_device(t_mesh[0].data_ptr(), t_mesh[1].data_ptr(), t_mesh[2].data_ptr(), t_mesh[3].data_ptr(), mesh.n_vertices,
+                                       mesh.n_triangles, size, size, pts.data_ptr(), nrm.data_ptr(), None, rows=1, jitter=False, seed=1,
+                                       offset=float(np.float32(1e-3)), transform=drone.transform)
+    torch.cuda.synchronize()
+    covered = (nrm != 0).any(dim=-1)
+    gen = torch.Generator(device=dev)
+    gen.manual_seed(1)
+    img = (1.0 + 0.5 * torch.randn((size, size, 3), generator=gen, dtype=torch.float32, device=dev)).abs() * covered[..., None]
+    base = {"mode": "finish", "mesh": "drone", "width": size, "height": size, "covered_share": round(float(covered.float().mean()), 4),
+            "calls": calls}
+    moved = 60 * n                                   # compulsory bytes of one level
+
+    def median_ms(form, levels, dilate):
+        ms = []
+        for k in range(warmup + calls):
+            ctxs[form].lightmap_finish_device(size, size, img.data_ptr(), pts.data_ptr(), nrm.data_ptr(), out[form].data_ptr(), valid.data_ptr(),
+                                              levels=levels, dilate=dilate)
+            torch.cuda.synchronize()
+            if k >= warmup:
+                ms.append(ctxs[form].last_kernel_ms())
+        return float(np.median(ms))
+
+    # the yardstick: a device-to-device copy that reads 30 n and writes 30 n bytes
+    src, dst = torch.empty(30 * n, dtype=torch.uint8, device=dev), torch.empty(30 * n, dtype=torch.uint8, device=dev)
+    copy_ms = []
+    for k in range(warmup + calls):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        dst.copy_(src)
+        e1.record()
+        torch.cuda.synchronize()
+        if k >= warmup:
+            copy_ms.append(e0.elapsed_time(e1))
+    copy = float(np.median(copy_ms))
+    rows = [dict(base, query="device-to-device copy of the same byte count", bytes_moved=moved, ms_median=round(copy, 4),
+                 gb_per_s=round(moved / copy / 1e6, 1))]
+    print(json.dumps(rows[-1]), flush=True)
+    del src, dst
+    totals = {form: [median_ms(form, k, 0) for k in range(FINISH_LEVELS + 1)] for form in ("direct", "lds")}
+    for level in range(FINISH_LEVELS):
+        step = 1 << level
+        row = dict(base, query=f"lmf_atrous level {level}", step=step, bytes_moved=moved)
+        for form in ("direct", "lds"):
+            if form == "lds" and step > 8:
+                continue
+            ms = totals[form][level + 1] - totals[form][level]
+            row[f"{form}_ms"] = round(ms, 4)
+            row[f"{form}_gb_per_s"] = round(moved / ms / 1e6, 1) if ms > 0 else None
+        row["copy_gb_per_s"] = rows[0]["gb_per_s"]
+        rows.append(row)
+        print(json.dumps(row), flush=True)
+    for form in ("direct", "lds"):
+        full = median_ms(form, FINISH_LEVELS, FINISH_DILATE)
+        rows.append(dict(base, query=f"whole call, every step {form} (step 16: direct)", levels=FINISH_LEVELS, dilate=FINISH_DILATE,
+                         ms_median=round(full, 4), lmf_mask_ms=round(totals[form][0], 4),
+                         lmf_dilate_ms_per_pass=round((full - totals[form][FINISH_LEVELS]) / FINISH_DILATE, 4)))
+        print(json.dumps(rows[-1]), flush=True)
+    full = median_ms("default", FINISH_LEVELS, FINISH_DILATE)
+    rows.append(dict(base, query="whole call, the library's threshold", levels=FINISH_LEVELS, dilate=FINISH_DILATE, ms_median=round(full, 4)))
+    print(json.dumps(rows[-1]), flush=True)
+    same = bool(torch.equal(out["direct"].view(torch.int32), out["lds"].view(torch.int32)) and
+                torch.equal(out["direct"].view(torch.int32), out["default"].view(torch.int32)))
+    rows.append(dict(base, query="direct and LDS forms give the same bits", same=same))
+    print(json.dumps(rows[-1]), flush=True)
+    for c in ctxs.values():
+        c.close()
+    if not same:
+        raise SystemExit("ray_query_bench: the LDS and the direct form of lmf_atrous differ")
+    return rows
+
+
 def occlusion_rows(ctx, cfg, sc, co, cd, bo, bd, hitpoints, calls, warmup):
     to = (np.array(SHADOW_POINT, np.float32) - hitpoints).astype(np.float32)
     dist = np.sqrt((to.astype(np.float64) ** 2).sum(axis=1))
@@ -564,13 +666,15 @@ def main():
     ap.add_argument("--width", type=int, default=1920)
     ap.add_argument("--height", type=int, default=1080)
     ap.add_argument("--configs", default="2,4")
-    ap.add_argument("--mode", choices=("intersect", "occlusion", "render", "hemisphere", "bake", "probes", "atlas"), default="intersect",
+    ap.add_argument("--mode", choices=("intersect", "occlusion", "render", "hemisphere", "bake", "probes", "atlas", "finish"), default="intersect",
                     help="intersect: the closest-hit rows; occlusion: the any-hit query against the visibility form; "
                          "render: ray-table rendering against mi_shade_rays_device; "
                          "hemisphere: hemisphere occlusion against the any-hit query on the identical pre-made rays; "
                          "bake: point-table rendering against ray-table rendering on the identical pre-made rays; "
                          "probes: light-probe rendering against ray-table rendering on the identical pre-made rays; "
-                         "atlas: the lightmap atlas on the GPU against the host helper, on the drone")
+                         "atlas: the lightmap atlas on the GPU against the host helper, on the drone; "
+                         "finish: lightmap finishing pass by pass, both forms of the filter, against a copy of the same bytes")
+    ap.add_argument("--finish-sizes", default="1024,2048,4096", help="--mode finish: the square atlas sizes")
     ap.add_argument("--atlas-sizes", default="1024,2048", help="--mode atlas: the square atlas sizes")
     ap.add_argument("--atlas-grid", type=int, default=0, help="--mode atlas: a synthetic height field of N x N quads (2 N^2 triangles) instead "
                     "of the drone; the table's timings and the check against the helper only, no bake")
@@ -582,8 +686,12 @@ def main():
         ap.error("--calls must be at least 20")
     if not torch.cuda.is_available():
         raise SystemExit("ray_query_bench: no GPU; there is no CPU fallback")
-    ctx = Context(0)
     rows = []
+    if a.mode == "finish":
+        for size in [int(v) for v in a.finish_sizes.split(",")]:
+            rows += finish_rows(size, a.calls, a.warmup)
+        a.configs = ""
+    ctx = Context(0)
     if a.mode == "atlas":
         for size in [int(v) for v in a.atlas_sizes.split(",")]:
             rows += atlas_rows(ctx, size, a.calls, a.warmup, a.atlas_bakes, a.atlas_grid)
