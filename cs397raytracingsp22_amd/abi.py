@@ -28,6 +28,7 @@ MI_VARIANT_WAVEFRONT, MI_VARIANT_RECURSIVE = 7, 8
 MI_OPT_NO_TILE_MASKS, MI_OPT_REFERENCE_WALK, MI_OPT_TWO_STAGE, MI_OPT_NO_LIST_TREE = 1, 2, 4, 8
 MI_HEMI_WORLD_RADIUS = 1   # mi_hemisphere_occlusion flags: t_max is a world-space radius
 MI_LM_JITTER = 1           # mi_lightmap_texels / mi_bake_lightmap flags: one jittered position per row instead of the texel centre
+MI_PV_NORMAL_WEIGHT = 1    # mi_probe_volume.flags: weight the eight corners by how far they lie in front of the surface
 
 f3 = C.c_float * 3
 f16 = C.c_float * 16
@@ -101,6 +102,11 @@ class mi_render_opts(C.Structure):
                 ("max_state_bytes", C.c_uint64)]
 
 
+class mi_probe_volume(C.Structure):
+    _fields_ = [("lo", f3), ("hi", f3), ("counts", C.c_uint32 * 3), ("flags", C.c_uint32),
+                ("sh", C.c_void_p), ("valid", C.c_void_p)]          # host or device addresses, by the entry point
+
+
 class mi_stats(C.Structure):
     _fields_ = [("samples", C.c_uint64), ("pixels", C.c_uint64), ("tiles", C.c_uint32),
                 ("tiles_padded", C.c_uint32), ("kernel_ms", C.c_float), ("total_ms", C.c_float),
@@ -120,6 +126,7 @@ EXPORTS = [
     "mi_render_probes", "mi_render_probes_device",
     "mi_lightmap_texels", "mi_lightmap_texels_device", "mi_bake_lightmap",
     "mi_lightmap_finish", "mi_lightmap_finish_device",
+    "mi_probe_volume_sample", "mi_probe_volume_sample_device",
     "mi_multi_create", "mi_multi_create_loopback", "mi_multi_destroy", "mi_multi_device_count", "mi_multi_context", "mi_multi_scene_upload", "mi_multi_reserve", "mi_multi_render",
 ]
 
@@ -243,6 +250,11 @@ def load() -> C.CDLL:
     lib.mi_lightmap_finish.restype = C.c_int
     lib.mi_lightmap_finish_device.argtypes = lib.mi_lightmap_finish.argtypes + [vp]
     lib.mi_lightmap_finish_device.restype = C.c_int
+    # irradiance volumes (added within ABI 5): volume, n_points, points, normals, out_irradiance, out_weight (, stream)
+    lib.mi_probe_volume_sample.argtypes = [vp, C.POINTER(mi_probe_volume), C.c_uint32, vp, vp, vp, vp]
+    lib.mi_probe_volume_sample.restype = C.c_int
+    lib.mi_probe_volume_sample_device.argtypes = lib.mi_probe_volume_sample.argtypes + [vp]
+    lib.mi_probe_volume_sample_device.restype = C.c_int
     lib.mi_multi_create.argtypes = [C.c_int, C.POINTER(C.c_int), C.POINTER(vp)]
     lib.mi_multi_create.restype = C.c_int
     lib.mi_multi_create_loopback.argtypes = [C.c_int, C.c_int, C.POINTER(vp)]

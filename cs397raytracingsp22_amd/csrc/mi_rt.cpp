@@ -60,6 +60,8 @@ hipError_t launch_lm_resolve(const LmArgs& a, hipStream_t stream);
 hipError_t launch_lmf_mask(const LmfArgs& a, hipStream_t stream);
 hipError_t launch_lmf_atrous(const LmfArgs& a, bool lds, bool* big_lds_enabled, hipStream_t stream);
 hipError_t launch_lmf_dilate(const LmfArgs& a, hipStream_t stream);
+hipError_t launch_pv_prepare(const PvArgs& a, hipStream_t stream);
+hipError_t launch_pv_sample(const PvArgs& a, hipStream_t stream);
 }  // namespace pt
 
 using namespace pt;
@@ -129,6 +131,9 @@ struct mi_ctx {
     void* d_lmf = nullptr; size_t lmf_bytes = 0;
     void* d_lmf_io = nullptr; size_t lmf_io_bytes = 0;
     bool lmf_big_lds_enabled = false;
+    // mi_probe_volume_sample: the prepared 112-byte probe records and, behind them, the host form's uploaded sh and valid (grown on
+    // demand, never the buffers mi_reserve sized)
+    void* d_pv = nullptr; size_t pv_bytes = 0;
     hipEvent_t ev_t0 = nullptr, ev_t1 = nullptr;     // mi_render's whole-call timer
     bool big_lds_enabled = false;                    // wf_trav_i<1024>'s > 64 KB dynamic-LDS opt-in, set on THIS context's device
     // wavefront pipeline buffers
@@ -293,6 +298,7 @@ extern "C" void mi_ctx_destroy(mi_ctx* c) {
     if (c->d_lm_out) (void)hipFree(c->d_lm_out);
     if (c->d_lmf) (void)hipFree(c->d_lmf);
     if (c->d_lmf_io) (void)hipFree(c->d_lmf_io);
+    if (c->d_pv) (void)hipFree(c->d_pv);
     if (c->d_wf_a) (void)hipFree(c->d_wf_a);
     if (c->d_wf_b) (void)hipFree(c->d_wf_b);
     if (c->d_wf_samp) (void)hipFree(c->d_wf_samp);
@@ -1407,6 +1413,91 @@ extern "C" int mi_lightmap_finish(mi_ctx* c, uint32_t width, uint32_t height, co
     if (out_valid) HIP_TRY(hipMemcpyAsync(out_valid, io + 4 * img, n, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return MI_OK;
+}
+
+// ------------------------------------------------------------------ irradiance volumes (SH L2 probe grids sampled at surface points)
+// tracing.py probe_volume_sample as two kernels: pv_prepare (one 112-byte record per probe) and pv_sample (one lane per point).  The
+// arguments are checked before the context, as the finishing pass's are.
+static int check_pv_args(const char* who, mi_ctx* c, const mi_probe_volume* v, const float* points, const float* normals,
+                         const float* out_irradiance) {
+    if (!v) return fail(MI_ERR_INVALID, "%s: volume is NULL", who);
+    if (!v->sh || !points || !normals || !out_irradiance)
+        return fail(MI_ERR_INVALID, "%s: volume->sh, points, normals and out_irradiance are required", who);
+    uint64_t n_probes = 1;
+    for (int a = 0; a < 3; a++) {
+        if (v->counts[a] == 0 || v->counts[a] > kPvMaxCount)
+            return fail(MI_ERR_INVALID, "%s: counts[%d] = %u is not in 1 .. %u", who, a, v->counts[a], kPvMaxCount);
+        n_probes *= v->counts[a];
+    }
+    if (n_probes > kPvMaxProbes) return fail(MI_ERR_INVALID, "%s: %llu probes exceed 2^22", who, (unsigned long long)n_probes);
+    if (v->flags & ~(uint32_t)MI_PV_NORMAL_WEIGHT)
+        return fail(MI_ERR_INVALID, "%s: unknown flag bits 0x%x", who, v->flags & ~(uint32_t)MI_PV_NORMAL_WEIGHT);
+    for (int a = 0; a < 3; a++) {
+        if (!std::isfinite(v->lo[a]) || !std::isfinite(v->hi[a])) return fail(MI_ERR_INVALID, "%s: lo[%d] / hi[%d] is not finite", who, a, a);
+        if (!(v->hi[a] > v->lo[a])) return fail(MI_ERR_INVALID, "%s: hi[%d] = %g is not above lo[%d] = %g", who, a, v->hi[a], a, v->lo[a]);
+    }
+    if (!c) return fail(MI_ERR_INVALID, "ctx is NULL");
+    return MI_OK;
+}
+
+// The volume's part of the kernel arguments: the grid constants in f32, as the helper computes them
+static PvArgs pv_volume_args(const mi_probe_volume* v) {
+    PvArgs a{};
+    a.n_probes = v->counts[0] * v->counts[1] * v->counts[2];
+    a.normal_weight = (v->flags & MI_PV_NORMAL_WEIGHT) ? 1u : 0u;
+    for (int k = 0; k < 3; k++) {
+        const float extent = v->hi[k] - v->lo[k], n = (float)v->counts[k];
+        a.counts[k] = v->counts[k]; a.lo[k] = v->lo[k];
+        a.cell[k] = extent / n; a.inv[k] = n / extent;
+    }
+    return a;
+}
+
+static size_t pv_record_bytes(uint32_t n_probes) { return (size_t)n_probes * kPvRecordFloats * sizeof(float); }
+
+extern "C" int mi_probe_volume_sample_device(mi_ctx* c, const mi_probe_volume* v, uint32_t n_points, const float* points, const float* normals,
+                                             float* out_irradiance, float* out_weight, void* stream) {
+    MI_TRY(check_pv_args("mi_probe_volume_sample_device", c, v, points, normals, out_irradiance));
+    if (n_points == 0) return MI_OK;
+    HIP_TRY(hipSetDevice(c->device));
+    PvArgs a = pv_volume_args(v);
+    MI_TRY(ensure(&c->d_pv, &c->pv_bytes, pv_record_bytes(a.n_probes)));
+    a.sh = v->sh; a.valid = v->valid; a.records = (float*)c->d_pv;
+    a.n_points = n_points; a.points = points; a.normals = normals; a.out_irradiance = out_irradiance; a.out_weight = out_weight;
+    const hipStream_t s = (hipStream_t)stream;
+    HIP_TRY(hipEventRecord(c->ev_start, s));
+    HIP_TRY(launch_pv_prepare(a, s));
+    HIP_TRY(launch_pv_sample(a, s));
+    HIP_TRY(hipEventRecord(c->ev_stop, s));
+    c->ev_recorded = true; c->ms_summed = false;
+    return MI_OK;
+}
+
+extern "C" int mi_probe_volume_sample(mi_ctx* c, const mi_probe_volume* v, uint32_t n_points, const float* points, const float* normals,
+                                      float* out_irradiance, float* out_weight) {
+    MI_TRY(check_pv_args("mi_probe_volume_sample", c, v, points, normals, out_irradiance));
+    if (n_points == 0) return MI_OK;
+    HIP_TRY(hipSetDevice(c->device));
+    PvArgs a = pv_volume_args(v);
+    // the records, then the caller's sh and valid as uploaded (both offsets are multiples of 16)
+    const size_t rec = pv_record_bytes(a.n_probes), sh_bytes = (size_t)a.n_probes * 27 * sizeof(float);
+    MI_TRY(ensure(&c->d_pv, &c->pv_bytes, rec + sh_bytes + a.n_probes));
+    char* const base = (char*)c->d_pv;
+    HIP_TRY(hipMemcpyAsync(base + rec, v->sh, sh_bytes, hipMemcpyHostToDevice, c->stream));
+    if (v->valid) HIP_TRY(hipMemcpyAsync(base + rec + sh_bytes, v->valid, a.n_probes, hipMemcpyHostToDevice, c->stream));
+    a.records = (float*)base; a.sh = (const float*)(base + rec); a.valid = v->valid ? (const uint8_t*)(base + rec + sh_bytes) : nullptr;
+    // chunked over points; the first chunk's timed region holds the record pass as well
+    const RqColumn cols[] = { { points, 12, false }, { normals, 12, false }, { out_irradiance, 12, true }, { out_weight, 4, true } };
+    return rq_chunked(c, n_points, cols, [&](uint32_t first, uint32_t n, void* const* d) {
+        a.n_points = n; a.points = (const float*)d[0]; a.normals = (const float*)d[1];
+        a.out_irradiance = (float*)d[2]; a.out_weight = (float*)d[3];
+        HIP_TRY(hipEventRecord(c->ev_start, c->stream));
+        if (first == 0) HIP_TRY(launch_pv_prepare(a, c->stream));
+        HIP_TRY(launch_pv_sample(a, c->stream));
+        HIP_TRY(hipEventRecord(c->ev_stop, c->stream));
+        c->ev_recorded = true; c->ms_summed = false;
+        return (int)MI_OK;
+    });
 }
 
 // ------------------------------------------------------------------ light probes (SH L2 radiance probes: the directions are drawn on the GPU)

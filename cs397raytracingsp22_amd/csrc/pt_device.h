@@ -436,4 +436,25 @@ struct LmfArgs {
 constexpr uint32_t kLmfMaxLdsStep = 8;
 inline size_t lmf_lds_bytes(uint32_t step) { const size_t e = (size_t)kTile + 4u * step; return 9u * e * e * sizeof(float); }
 
+// ---- irradiance volumes (mi_probe_volume_sample; pt_kernels.hip "pv_*") ----
+// tracing.py probe_volume_sample: pv_prepare turns every probe's 27 SH coefficients into one 112-byte record (the coefficients times the
+// cosine-lobe constants K_k, then the validity as 0.0 / 1.0: 28 floats, seven 16-byte loads), pv_sample interpolates the eight records
+// around every point.  The grid constants are computed once on the host, in f32, as the helper does.
+constexpr uint32_t kPvRecordFloats = 28;
+constexpr uint32_t kPvMaxCount = 1024;           // per axis
+constexpr uint32_t kPvMaxProbes = 1u << 22;      // 448 MiB of records
+struct PvArgs {
+    const float*   sh;               // [n_probes][9][3] (pv_prepare)
+    const uint8_t* valid;            // [n_probes] or nullptr = all valid (pv_prepare)
+    float*         records;          // [n_probes][28], 16-byte aligned: pv_prepare writes, pv_sample reads
+    const float*   points;           // [n_points][3]
+    const float*   normals;          // [n_points][3]: all-zero = empty texel
+    float*         out_irradiance;   // [n_points][3]
+    float*         out_weight;       // [n_points] or nullptr
+    uint32_t n_probes, n_points;
+    uint32_t counts[3];
+    uint32_t normal_weight;          // MI_PV_NORMAL_WEIGHT
+    float lo[3], cell[3], inv[3];    // cell_a = (hi_a - lo_a) / (float)n_a, inv_a = (float)n_a / (hi_a - lo_a)
+};
+
 }  // namespace pt

@@ -3912,7 +3912,118 @@ __global__ __launch_bounds__(kBlock) void lmf_dilate(const LmfArgs a) {
     a.mask_out[i] = valid;
 }
 
+// ---------------------------------------------------------------- irradiance volumes (mi_probe_volume_sample)
+// tracing.py probe_volume_sample on the device: trilinear interpolation of a grid of SH L2 radiance probes at surface points, convolved
+// with the clamped cosine lobe about each point's normal.  Pure f32, the helper's operations in the helper's order (no fused multiply-add:
+// the pragma above; IEEE division and square root), a fixed corner order per point, nothing summed across threads: the result is the
+// helper's bit for bit and does not depend on scheduling.  The only addresses that depend on a table value are the eight record
+// addresses, through indices clamped to the grid: a non-finite point or normal spoils its own output only.
+
+// One thread per probe: r[k][c] = sh[q][k][c] * K_k, K_k = the cosine-lobe factor A_l times the basis constant of Y_k rounded to f32, and
+// the validity as 0.0 / 1.0 in the 28th float.  One 112-byte record, written as seven 16-byte stores.
+__global__ __launch_bounds__(kBlock) void pv_prepare(const PvArgs a) {
+    const uint32_t q = blockIdx.x * kBlock + threadIdx.x;
+    if (q >= a.n_probes) return;
+    const float K1 = (float)1.0233267079464885, K2 = (float)0.8580855308097834;
+    const float K[9] = { (float)0.886226925452758, K1, K1, K1, K2, K2, (float)0.24770795610037571, K2, (float)0.4290427654048917 };
+    const float* sh = a.sh + (size_t)q * 27;
+    float r[kPvRecordFloats];
+#pragma unroll
+    for (int k = 0; k < 9; k++)
+#pragma unroll
+        for (int c = 0; c < 3; c++) r[3 * k + c] = sh[3 * k + c] * K[k];
+    r[27] = (a.valid && a.valid[q] == 0) ? 0.0f : 1.0f;
+    float4* out = reinterpret_cast<float4*>(a.records + (size_t)q * kPvRecordFloats);
+#pragma unroll
+    for (int i = 0; i < 7; i++) out[i] = make_float4(r[4 * i], r[4 * i + 1], r[4 * i + 2], r[4 * i + 3]);
+}
+
+// One lane per point: 24 bytes in, the eight corner records by 16-byte loads (L2 serves them: neighbouring points share corners and a
+// 32^3 volume is 3.7 MB of records), three accumulators and the weight sum, 12 or 16 bytes out.  No LDS, no atomics.
+#ifdef MI_RT_PV_WAVES_PER_SIMD      // developer knob (MI_RT_EXTRA_FLAGS): cap the registers for this many waves per SIMD; DESIGN.md has the numbers
+__attribute__((amdgpu_waves_per_eu(MI_RT_PV_WAVES_PER_SIMD, MI_RT_PV_WAVES_PER_SIMD)))
+#endif
+__global__ __launch_bounds__(kBlock) void pv_sample(const PvArgs a) {
+    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= a.n_points) return;
+    const float p[3] = { a.points[3 * (size_t)i], a.points[3 * (size_t)i + 1], a.points[3 * (size_t)i + 2] };
+    const float nx = a.normals[3 * (size_t)i], ny = a.normals[3 * (size_t)i + 1], nz = a.normals[3 * (size_t)i + 2];
+    float E[3] = { 0.0f, 0.0f, 0.0f }, sw = 0.0f;
+    if (lmf_covered(nx, ny, nz)) {                             // an all-zero normal is mi_render_points' empty-texel mark: +0 and weight 0
+        const float l = sqrtf((nx * nx + ny * ny) + nz * nz);
+        const float x = nx / l, y = ny / l, z = nz / l;
+        const float d[3] = { x, y, z };
+        const float b[9] = { 1.0f, y, z, x, x * y, y * z, 3.0f * (z * z) - 1.0f, x * z, x * x - y * y };
+        // per axis: the two corner indices, their trilinear weights and, for the normal-facing weight, D = probe - point, D D and D n
+        uint32_t idx[3][2];
+        float wa[3][2], DD[3][2], Dn[3][2];
+#pragma unroll
+        for (int ax = 0; ax < 3; ax++) {
+            const int n = (int)a.counts[ax];
+            float g = (p[ax] - a.lo[ax]) * a.inv[ax] - 0.5f;
+            g = fminf(fmaxf(g, 0.0f), (float)(n - 1));         // also what keeps every index in range for NaN and infinite points
+            const int i0 = max(min((int)floorf(g), max(n - 2, 0)), 0);
+            const float f = g - (float)i0;
+            wa[ax][0] = 1.0f - f; wa[ax][1] = f;
+#pragma unroll
+            for (int dd = 0; dd < 2; dd++) {
+                const int ia = min(i0 + dd, n - 1);
+                idx[ax][dd] = (uint32_t)ia;
+                const float D = (a.lo[ax] + ((float)ia + 0.5f) * a.cell[ax]) - p[ax];
+                DD[ax][dd] = D * D; Dn[ax][dd] = D * d[ax];
+            }
+        }
+        float acc[3] = { 0.0f, 0.0f, 0.0f };
+#pragma unroll
+        for (int dz = 0; dz < 2; dz++)
+#pragma unroll
+            for (int dy = 0; dy < 2; dy++)
+#pragma unroll
+                for (int dx = 0; dx < 2; dx++) {
+                    const size_t q = ((size_t)idx[2][dz] * a.counts[1] + idx[1][dy]) * a.counts[0] + idx[0][dx];
+                    const float4* rec = reinterpret_cast<const float4*>(a.records + q * kPvRecordFloats);
+                    float r[kPvRecordFloats];
+#pragma unroll
+                    for (int k = 0; k < 7; k++) { const float4 v = rec[k]; r[4 * k] = v.x; r[4 * k + 1] = v.y; r[4 * k + 2] = v.z; r[4 * k + 3] = v.w; }
+                    float w = (wa[0][dx] * wa[1][dy]) * wa[2][dz];
+                    if (r[27] == 0.0f) w = 0.0f;
+                    if (a.normal_weight) {
+                        const float dd = (DD[0][dx] + DD[1][dy]) + DD[2][dz];
+                        if (dd > 0.0f) {
+                            const float t = ((Dn[0][dx] + Dn[1][dy]) + Dn[2][dz]) / sqrtf(dd);
+                            const float h = (t + 1.0f) * 0.5f;
+                            w = w * (h * h + 0.2f);
+                        }
+                    }
+#pragma unroll
+                    for (int c = 0; c < 3; c++) {
+                        float e = b[0] * r[c];
+#pragma unroll
+                        for (int k = 1; k < 9; k++) e = e + b[k] * r[3 * k + c];
+                        acc[c] = acc[c] + w * e;
+                    }
+                    sw = sw + w;
+                }
+        if (sw > 0.0f) {
+#pragma unroll
+            for (int c = 0; c < 3; c++) E[c] = acc[c] / sw;
+        }
+    }
+#pragma unroll
+    for (int c = 0; c < 3; c++) a.out_irradiance[3 * (size_t)i + c] = E[c];
+    if (a.out_weight) a.out_weight[i] = sw;
+}
+
 // ---------------------------------------------------------------- launch wrappers
+// irradiance volumes: the record pass, then the sampling pass
+hipError_t launch_pv_prepare(const PvArgs& a, hipStream_t stream) {
+    hipLaunchKernelGGL(pv_prepare, dim3((a.n_probes + kBlock - 1) / kBlock), dim3(kBlock), 0, stream, a);
+    return hipGetLastError();
+}
+hipError_t launch_pv_sample(const PvArgs& a, hipStream_t stream) {
+    hipLaunchKernelGGL(pv_sample, dim3((a.n_points + kBlock - 1) / kBlock), dim3(kBlock), 0, stream, a);
+    return hipGetLastError();
+}
 // lightmap finishing: one pass per launch.  lmf_atrous stages through LDS when `lds`; a window above 64 KB needs the opt-in, which
 // belongs to the function on the current device, so the calling context keeps its record (as launch_walker's big_lds_enabled).
 hipError_t launch_lmf_mask(const LmfArgs& a, hipStream_t stream) {

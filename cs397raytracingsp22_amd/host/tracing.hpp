@@ -257,6 +257,35 @@ struct Scene : Intersectable {                         // tracing.rs:213-218; `i
         return sh;
     }
 
+    // Sample an irradiance volume through mi_probe_volume_sample: `sh` holds the first nx * ny * nz records ([9][3] each) of render_probes'
+    // result for the probe grid of the box [lo, hi] (probe (i, j, k) has number (k * ny + j) * nx + i and sits at the centre of its cell);
+    // `valid` is empty (every probe takes part) or one byte per probe (0 = takes no part).  points / normals are [n][3]; every point is lit
+    // through its normal: trilinear interpolation of the eight probes around it, convolved with the clamped cosine lobe; normal_weight sets
+    // MI_PV_NORMAL_WEIGHT.  An all-zero normal marks an empty texel (+0.0, weight 0).  Returns the irradiance [n][3]; `weight` takes the
+    // weight sum per point (0: every corner was invalid).  Needs no scene: a static member.
+    static std::vector<float> sample_probe_volume(const float lo[3], const float hi[3], const uint32_t counts[3], const std::vector<float>& sh,
+                                                  const std::vector<uint8_t>& valid, bool normal_weight, const std::vector<float>& points,
+                                                  const std::vector<float>& normals, int device = 0, std::vector<float>* weight = nullptr) {
+        const size_t n_probes = (size_t)counts[0] * counts[1] * counts[2], n = points.size() / 3;
+        if (sh.size() != n_probes * 27 || (!valid.empty() && valid.size() != n_probes))
+            throw std::runtime_error("mi_rt: sh must be [nx ny nz][9][3] and valid empty or [nx ny nz]");
+        if (points.size() != n * 3 || normals.size() != points.size()) throw std::runtime_error("mi_rt: points and normals must both be [n][3]");
+        mi_probe_volume v{};
+        for (int a = 0; a < 3; a++) { v.lo[a] = lo[a]; v.hi[a] = hi[a]; v.counts[a] = counts[a]; }
+        v.flags = normal_weight ? MI_PV_NORMAL_WEIGHT : 0u;
+        v.sh = sh.data(); v.valid = valid.empty() ? nullptr : valid.data();
+        std::vector<float> out(n * 3);
+        if (weight) weight->resize(n);
+        if (n == 0) return out;                              // (an empty vector has no address to pass)
+        mi_ctx* ctx = nullptr;
+        mi_check(mi_ctx_create(device, &ctx));
+        const int rc = mi_probe_volume_sample(ctx, &v, (uint32_t)n, points.data(), normals.data(), out.data(), weight ? weight->data() : nullptr);
+        const std::string err = rc == MI_OK ? "" : mi_last_error();
+        mi_ctx_destroy(ctx);
+        if (rc != MI_OK) throw std::runtime_error("mi_rt: " + err);
+        return out;
+    }
+
 private:
     // flatten -> context -> upload -> `call(ctx)` -> destroy; a failure surfaces as std::runtime_error carrying mi_last_error()
     template <class F> void with_context(int device, F call) const {

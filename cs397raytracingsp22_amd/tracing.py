@@ -273,6 +273,162 @@ def probe_grid(lo, hi, counts, width: Optional[int] = None):
     return np.ascontiguousarray(pts.reshape(H, W, 3), np.float32), n
 
 
+# K_k of mi_probe_volume_sample: the clamped-cosine lobe's A_l times the basis constant of Y_k, rounded from f64 to f32
+PV_K = np.array([0.886226925452758] + [1.0233267079464885] * 3 + [0.8580855308097834] * 2 + [0.24770795610037571, 0.8580855308097834,
+                0.4290427654048917], np.float64).astype(np.float32)
+PV_MAX_COUNT = 1024
+PV_MAX_PROBES = 1 << 22
+
+
+def check_probe_volume(lo, hi, counts, sh, valid=None, flags: int = 0):
+    """Input checking of an irradiance volume (mi_probe_volume_sample), no GPU needed: the box [lo, hi] probe_grid was given (finite,
+    hi > lo on every axis, as float32), counts = (nx, ny, nz) each in 1 .. 1024 with at most 2^22 probes, sh [n, 9, 3] float32 (the first
+    n = nx ny nz records of render_probes' sh), valid None or [n] (0 = the probe takes no part), flags 0 or abi.MI_PV_NORMAL_WEIGHT.
+    Returns (lo [3] f32, hi [3] f32, (nx, ny, nz), sh [n, 9, 3] f32 contiguous, valid [n] uint8 or None, flags); raises ValueError."""
+    lo32, hi32 = np.asarray(lo, np.float32).reshape(-1), np.asarray(hi, np.float32).reshape(-1)
+    if lo32.shape != (3,) or hi32.shape != (3,):
+        raise ValueError("lo and hi must have three components each")
+    if not (np.isfinite(lo32).all() and np.isfinite(hi32).all()):
+        raise ValueError(f"lo and hi must be finite, got {lo32} and {hi32}")
+    if not (hi32 > lo32).all():
+        raise ValueError(f"hi must be above lo on every axis, got lo {lo32} and hi {hi32}")
+    try:
+        nx, ny, nz = (int(c) for c in counts)
+    except (TypeError, ValueError):
+        raise ValueError(f"counts must be three integers, got {counts!r}") from None
+    if not all(1 <= c <= PV_MAX_COUNT for c in (nx, ny, nz)):
+        raise ValueError(f"counts must all be in 1 .. {PV_MAX_COUNT}, got {(nx, ny, nz)}")
+    n = nx * ny * nz
+    if n > PV_MAX_PROBES:
+        raise ValueError(f"{n} probes exceed 2^22")
+    flags = int(flags)
+    if flags & ~abi.MI_PV_NORMAL_WEIGHT:
+        raise ValueError(f"unknown flag bits {flags & ~abi.MI_PV_NORMAL_WEIGHT:#x}")
+    sh32 = np.ascontiguousarray(sh, np.float32)
+    if sh32.shape != (n, 9, 3):
+        raise ValueError(f"sh must be [{n}, 9, 3] for counts {(nx, ny, nz)}, got {sh32.shape}")
+    v8 = None
+    if valid is not None:
+        v8 = np.ascontiguousarray(np.asarray(valid) != 0, np.uint8)
+        if v8.shape != (n,):
+            raise ValueError(f"valid must be [{n}], got {v8.shape}")
+    return lo32, hi32, (nx, ny, nz), sh32, v8, flags
+
+
+def check_volume_points(points, normals):
+    """(points [n, 3] f32, normals [n, 3] f32, leading shape) of the surface points an irradiance volume is sampled at: two float32 arrays
+    of one shape [..., 3] (an atlas table [rows, H, W, 3] is one).  The values are not looked at: an all-zero normal is an empty texel,
+    a non-finite point or normal spoils its own result only.  Raises ValueError."""
+    P, N = np.asarray(points, np.float32), np.asarray(normals, np.float32)
+    if P.ndim < 1 or P.shape[-1] != 3 or N.shape != P.shape:
+        raise ValueError(f"points and normals must be [..., 3] arrays of one shape, got {P.shape} and {N.shape}")
+    if P.size // 3 >= 1 << 32:
+        raise ValueError(f"{P.size // 3} points exceed 2^32 - 1")
+    return np.ascontiguousarray(P.reshape(-1, 3)), np.ascontiguousarray(N.reshape(-1, 3)), P.shape[:-1]
+
+
+def probe_volume_sample(lo, hi, counts, sh, points, normals, valid=None, flags: int = 0):
+    """Sample an irradiance volume on the host (numpy only): trilinear interpolation of a probe_grid of SH L2 radiance probes at surface
+    points, convolved with the clamped cosine lobe about each point's normal.  This is the DEFINITION of mi_probe_volume_sample, which
+    equals it bit for bit.  Arguments as check_probe_volume and check_volume_points.  Returns (E [..., 3] f32, weight [...] f32).
+    Everything is f32, one rounding per operation (+ - *, IEEE / and sqrt, floor, fmin, fmax), in the order written below.
+    Per axis a: cell = (hi - lo) / n, inv = n / (hi - lo).  Prepared record r[q][k][c] = sh[q][k][c] * PV_K[k].
+    An all-zero normal gives E = +0 and weight 0.  Otherwise (x, y, z) = n / sqrt((nx nx + ny ny) + nz nz) and
+    b = (1, y, z, x, x y, y z, 3 (z z) - 1, x z, x x - y y).  Cell: g = (p - lo) * inv - 0.5, clamped by fmin(fmax(g, 0), n - 1) (which
+    also keeps every index in range for NaN and infinite points), i0 = min(floor(g), max(n - 2, 0)), f = g - i0.  The eight corners, dz
+    outer, dy, dx inner: i = min(i0 + d, n - 1), w_a = f or 1 - f, w = (w_x w_y) w_z, w = 0 for an invalid probe; with
+    MI_PV_NORMAL_WEIGHT D = (lo + (i + 0.5) cell) - p, dd = (Dx Dx + Dy Dy) + Dz Dz and, when dd > 0,
+    t = ((Dx x + Dy y) + Dz z) / sqrt(dd), h = (t + 1) 0.5, w = w (h h + 0.2).  e[c] = b0 r[0][c] + ... + b8 r[8][c] left to right,
+    acc += w e, sw += w.  E = acc / sw when sw > 0, else +0; weight = sw."""
+    f32 = np.float32
+    lo, hi, cnt, sh, valid, flags = check_probe_volume(lo, hi, counts, sh, valid, flags)
+    P, N, shape = check_volume_points(points, normals)
+    n_pts = len(P)
+    with np.errstate(all="ignore"):
+        nf = np.array(cnt, np.float32)
+        ext = hi - lo
+        cell, inv = ext / nf, nf / ext
+        rec = sh * PV_K[None, :, None]
+        ok = np.ones(len(sh), bool) if valid is None else valid != 0
+        nx, ny, nz = N[:, 0], N[:, 1], N[:, 2]
+        covered = ~((nx == 0) & (ny == 0) & (nz == 0))
+        l = np.sqrt((nx * nx + ny * ny) + nz * nz)
+        x, y, z = nx / l, ny / l, nz / l
+        d = (x, y, z)
+        b = (np.ones(n_pts, f32), y, z, x, x * y, y * z, f32(3.0) * (z * z) - f32(1.0), x * z, x * x - y * y)
+        idx, wa, DD, Dn = [], [], [], []
+        for a in range(3):
+            n = cnt[a]
+            g = (P[:, a] - lo[a]) * inv[a] - f32(0.5)
+            g = np.fmin(np.fmax(g, f32(0.0)), f32(n - 1))
+            i0 = np.minimum(np.floor(g).astype(np.int64), max(n - 2, 0))
+            f = g - i0.astype(f32)
+            ia = [np.minimum(i0 + dd, n - 1) for dd in (0, 1)]
+            D = [(lo[a] + (i.astype(f32) + f32(0.5)) * cell[a]) - P[:, a] for i in ia]
+            idx.append(ia); wa.append((f32(1.0) - f, f))
+            DD.append([Di * Di for Di in D]); Dn.append([Di * d[a] for Di in D])
+        acc = np.zeros((n_pts, 3), f32)
+        sw = np.zeros(n_pts, f32)
+        for dz in (0, 1):
+            for dy in (0, 1):
+                for dx in (0, 1):
+                    q = (idx[2][dz] * cnt[1] + idx[1][dy]) * cnt[0] + idx[0][dx]
+                    r = rec[q]                                                     # [n_pts, 9, 3]
+                    w = (wa[0][dx] * wa[1][dy]) * wa[2][dz]
+                    w = np.where(ok[q], w, f32(0.0))
+                    if flags & abi.MI_PV_NORMAL_WEIGHT:
+                        dd = (DD[0][dx] + DD[1][dy]) + DD[2][dz]
+                        t = ((Dn[0][dx] + Dn[1][dy]) + Dn[2][dz]) / np.sqrt(dd)
+                        h = (t + f32(1.0)) * f32(0.5)
+                        w = np.where(dd > 0, w * (h * h + f32(0.2)), w)
+                    e = b[0][:, None] * r[:, 0, :]
+                    for k in range(1, 9):
+                        e = e + b[k][:, None] * r[:, k, :]
+                    acc = acc + w[:, None] * e
+                    sw = sw + w
+        E = np.where((sw > 0)[:, None], acc / sw[:, None], f32(0.0))
+        E = np.where(covered[:, None], E, f32(0.0))
+        sw = np.where(covered, sw, f32(0.0))
+    assert E.dtype == np.float32 and sw.dtype == np.float32
+    return np.ascontiguousarray(E.reshape(shape + (3,))), np.ascontiguousarray(sw.reshape(shape))
+
+
+@dataclass
+class ProbeVolume:
+    """An irradiance volume: a probe_grid of SH L2 radiance probes ready to be sampled.  lo / hi / counts are what probe_grid was given,
+    sh [n, 9, 3] f32 the first n records of render_probes' sh, valid None or [n] (0 = the probe takes no part: the caller decides, e.g.
+    probes inside geometry).  Scene.irradiance_volume makes one."""
+    lo: np.ndarray
+    hi: np.ndarray
+    counts: tuple
+    sh: np.ndarray
+    valid: Optional[np.ndarray] = None
+
+    def __post_init__(self):
+        self.lo, self.hi, self.counts, self.sh, self.valid, _ = check_probe_volume(self.lo, self.hi, self.counts, self.sh, self.valid)
+
+    def sample(self, points, normals, normal_weight: bool = False, want_weight: bool = False, ctx: Optional["Context"] = None,
+               device: int = 0):
+        """The irradiance at surface points ([..., 3] f32 each; an atlas table from lightmap_texels goes in as it stands: its empty
+        texels come back zero) on the GPU (mi_probe_volume_sample): E [..., 3] f32, or with want_weight (E, weight [...]) — weight 0
+        marks a point all of whose corners were invalid.  normal_weight sets MI_PV_NORMAL_WEIGHT: corners in front of the surface count
+        more.  `ctx`: a Context to run on (one is made on `device` and closed otherwise).  Divide by pi and multiply by the albedo for
+        a Lambertian surface's outgoing radiance."""
+        own = ctx is None
+        c = Context(device) if own else ctx
+        try:
+            E, w = c.probe_volume_sample(self, points, normals, flags=abi.MI_PV_NORMAL_WEIGHT if normal_weight else 0)
+        finally:
+            if own:
+                c.close()
+        return (E, w) if want_weight else E
+
+    def sample_host(self, points, normals, normal_weight: bool = False):
+        """The same on the host (probe_volume_sample, the definition): (E, weight)."""
+        return probe_volume_sample(self.lo, self.hi, self.counts, self.sh, points, normals, self.valid,
+                                   abi.MI_PV_NORMAL_WEIGHT if normal_weight else 0)
+
+
 def _lowbias32(x):
     x = x ^ (x >> np.uint32(16)); x = x * np.uint32(0x7feb352d)
     x = x ^ (x >> np.uint32(15)); x = x * np.uint32(0x846ca68b)
@@ -771,6 +927,29 @@ class Context:
         abi.check(self._lib.mi_lightmap_finish_device(self._h, width, height, d_image, d_points, d_normals, levels, normal_power_log2,
                                                       sigma_plane, reach, sigma_color, dilate, d_out_image, d_out_valid, stream))
 
+    def probe_volume_sample(self, volume: "ProbeVolume", points, normals, flags: int = 0):
+        """mi_probe_volume_sample: the helper probe_volume_sample on the GPU, bit for bit.  `volume` is a ProbeVolume, points and
+        normals [..., 3] f32 of one shape (check_volume_points).  Returns (E [..., 3] f32, weight [...] f32).  No scene is needed."""
+        lo, hi, cnt, sh, valid, flags = check_probe_volume(volume.lo, volume.hi, volume.counts, volume.sh, volume.valid, flags)
+        P, N, shape = check_volume_points(points, normals)
+        pod = abi.mi_probe_volume(lo=abi.f3(*lo.tolist()), hi=abi.f3(*hi.tolist()), counts=(C.c_uint32 * 3)(*cnt), flags=flags,
+                                  sh=sh.ctypes.data, valid=valid.ctypes.data if valid is not None else None)
+        E = np.empty((len(P), 3), np.float32)
+        w = np.empty(len(P), np.float32)
+        abi.check(self._lib.mi_probe_volume_sample(self._h, C.byref(pod), len(P), P.ctypes.data, N.ctypes.data, E.ctypes.data, w.ctypes.data))
+        return E.reshape(shape + (3,)), w.reshape(shape)
+
+    def probe_volume_sample_device(self, lo, hi, counts, d_sh: int, n_points: int, d_points: int, d_normals: int, d_irradiance: int,
+                                   d_weight: Optional[int] = None, d_valid: Optional[int] = None, flags: int = 0,
+                                   stream: Optional[int] = None):
+        """mi_probe_volume_sample_device: the same for a volume and points held on the device (raw pointers, e.g. tensor.data_ptr():
+        d_sh [n_probes, 9, 3] f32 — render_probes' sh buffer as it is —, d_valid [n_probes] u8 or None, d_points / d_normals /
+        d_irradiance [n_points, 3] f32, d_weight [n_points] f32 or None).  Queued on `stream`, no synchronisation."""
+        pod = abi.mi_probe_volume(lo=abi.f3(*[float(v) for v in lo]), hi=abi.f3(*[float(v) for v in hi]),
+                                  counts=(C.c_uint32 * 3)(*[int(c) for c in counts]), flags=flags, sh=d_sh, valid=d_valid)
+        abi.check(self._lib.mi_probe_volume_sample_device(self._h, C.byref(pod), n_points, d_points, d_normals, d_irradiance, d_weight,
+                                                          stream))
+
     def render_probes(self, cam: Camera, points, seed: int = 1, want_f32=True, want_u8=True, want_sig=False,
                       flags: int = 0, max_state_bytes: int = 0):
         """mi_render_probes: light probes.  `points` (check_probe_table: [S, H, W, 3] or [H, W, 3] float32, S = 1 or aa_sample_count)
@@ -1227,6 +1406,26 @@ class Scene:                         # tracing.rs:213-218
             return ctx.render_probes(self.camera, p, seed=seed, want_sig=True)
         finally:
             ctx.close()
+
+    def irradiance_volume(self, lo, hi, counts, samples: int, seed: int = 1, device: int = 0, valid=None) -> "ProbeVolume":
+        """An irradiance volume of this scene: probe_grid(lo, hi, counts), then render_probes with `samples` directions per probe, then the
+        first n records of its sh as a ProbeVolume — .sample(points, normals) lights whatever moves through the scene.  This scene's
+        camera supplies path_depth and max_trace_dist.  `valid` (None, or [n]: 0 = the probe takes no part) is the caller's."""
+        from dataclasses import replace
+        cnt = tuple(int(c) for c in counts)
+        if len(cnt) != 3 or not all(1 <= c <= PV_MAX_COUNT for c in cnt) or cnt[0] * cnt[1] * cnt[2] > PV_MAX_PROBES:
+            raise ValueError(f"counts must be three integers in 1 .. {PV_MAX_COUNT} with at most 2^22 probes, got {cnt}")
+        check_probe_volume(lo, hi, (1, 1, 1), np.zeros((1, 9, 3), np.float32))          # the box, before anything is rendered
+        pts, n = probe_grid(lo, hi, cnt)
+        cam = replace(self.camera, screen_width=pts.shape[1], screen_height=pts.shape[0], aa_sample_count=int(samples))
+        p, _ = check_probe_table(cam, pts)
+        ctx = Context(device)
+        try:
+            ctx.upload(self.flatten())
+            sh, _, _, _, _ = ctx.render_probes(cam, p, seed=seed, want_f32=False, want_u8=False)
+        finally:
+            ctx.close()
+        return ProbeVolume(lo, hi, tuple(int(c) for c in counts), sh.reshape(-1, 9, 3)[:n].copy(), valid)
 
     def shade_rays(self, origins, dirs, seed: int = 1, first_key: int = 0, device: int = 0) -> np.ndarray:
         """Scene::shade_ray (tracing.rs:300-324) at level 0 for a batch of rays, with this scene's camera settings."""

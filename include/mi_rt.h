@@ -205,6 +205,8 @@ typedef struct mi_render_opts {
 #define MI_HEMI_WORLD_RADIUS 1u     /* t_max is a world-space radius: the interval of a sample ends at t_max / |d| */
 /* mi_lightmap_texels / mi_bake_lightmap flags */
 #define MI_LM_JITTER 1u             /* row r of a texel is a jittered position inside it, not its centre */
+/* mi_probe_volume.flags (mi_probe_volume_sample, below) */
+#define MI_PV_NORMAL_WEIGHT 1u      /* weight the eight corners by how far they lie in front of the surface */
 
 typedef enum mi_variant {
     MI_VARIANT_DEFAULT    = 0,  /* library picks (currently MI_VARIANT_WAVEFRONT)                  */
@@ -588,6 +590,56 @@ int  mi_render_probes_device(mi_ctx* ctx, const mi_camera_desc* cam, const mi_re
                              const float* d_points, uint32_t rows_per_pixel,
                              uint32_t sample_begin, uint32_t sample_end, void* d_accum_f32x4, void* d_compact_sh,
                              void* d_compact_f32, void* d_sig_u32, void* stream, mi_stats* stats);
+
+/* ---- irradiance volumes: SH L2 probe grids sampled at surface points (added within ABI version 5: detect by symbol lookup) ----
+ * What uses mi_render_probes' result: the grid of radiance probes that probe_grid (Python) places in a box is interpolated at arbitrary
+ *   surface points and convolved with the clamped cosine lobe about each point's normal, giving the irradiance E(n) there (constant
+ *   radiance L gives pi L; divide by pi and multiply by the albedo for a Lambertian surface).  Millions of points per call: the vertices of
+ *   moving meshes, or the texels of an atlas table (mi_lightmap_texels) for a preview lightmap in milliseconds.  No scene is needed.
+ * These are the semantics of probe_volume_sample (Python), which is the definition; the result equals the helper's BIT FOR BIT: pure
+ *   f32, every operation one of + - * /, sqrtf, floorf, fminf, fmaxf, comparisons and exact int-to-float conversions, in the order
+ *   written here, no fused multiply-add, IEEE division and square root.
+ * Volume: `sh` is exactly the first n_probes = nx ny nz records of mi_render_probes' out_sh for a probe_grid table (the flat prefix of
+ *   [H][W][9][3] is [n_probes][9][3]: pass that buffer as it is).  `valid` marks probes that take no part (inside geometry, say); the
+ *   caller computes it.  Grid constants per axis a, in f32: cell_a = (hi_a - lo_a) / (float)n_a, inv_a = (float)n_a / (hi_a - lo_a).
+ * Prepared record of probe q: r[k][c] = sh[q][k][c] * K_k, rounded once; K_k is the cosine-lobe factor times the basis constant, rounded
+ *   from f64 to f32: K_0 = 0.886226925452758, K_1..3 = 1.0233267079464885, K_4 = K_5 = K_7 = 0.8580855308097834,
+ *   K_6 = 0.24770795610037571, K_8 = 0.4290427654048917.
+ * Normal (nx, ny, nz): all-zero (either sign of zero) is the empty-texel mark of mi_render_points: the output is +0.0 and the weight 0, so
+ *   an atlas table is a legal input as it stands.  Otherwise l = sqrtf((nx nx + ny ny) + nz nz), x = nx / l, y = ny / l, z = nz / l and
+ *   b = { 1, y, z, x, x*y, y*z, 3*(z*z) - 1, x*z, x*x - y*y }.
+ * Cell, per axis: g = (p_a - lo_a) * inv_a - 0.5f; g = fminf(fmaxf(g, 0), (float)(n_a - 1)) (which also keeps every index in range for
+ *   NaN and infinite points); i0 = min((int)floorf(g), max(n_a - 2, 0)); f = g - (float)i0.  Outside the box the edge cells extend.
+ * Eight corners, dz outer, dy, dx inner: index i_a = min(i0_a + d_a, n_a - 1); w_a = d_a ? f_a : 1 - f_a; w = (w_x * w_y) * w_z;
+ *   w = 0 when valid[q] == 0.  With MI_PV_NORMAL_WEIGHT: D_a = (lo_a + ((float)i_a + 0.5f) * cell_a) - p_a,
+ *   dd = (Dx Dx + Dy Dy) + Dz Dz, and when dd > 0: t = ((Dx x + Dy y) + Dz z) / sqrtf(dd), h = (t + 1) * 0.5f, w = w * (h*h + 0.2f)
+ *   (a probe behind the surface counts less, never nothing; w is unchanged when dd == 0).  Then, summed left to right,
+ *   e[c] = b0*r[0][c] + b1*r[1][c] + ... + b8*r[8][c];  acc[c] = acc[c] + w * e[c];  sw = sw + w.
+ * Result: out_irradiance[c] = acc[c] / sw when sw > 0, else +0.0; out_weight = sw (0: every corner was invalid).
+ * A non-finite point or normal gives an unspecified value for that point only; it never faults and changes no other point's bits.  The
+ *   result does not depend on scheduling: no atomics, nothing is summed across threads.
+ * MI_ERR_INVALID (each with a message, checked before the context, nothing is launched): a NULL volume, sh, points, normals or
+ *   out_irradiance; a count of 0 or above 1024; more than 2^22 probes; an unknown flag; a lo or hi that is not finite, or hi[a] <= lo[a].
+ *   n_points == 0 is MI_OK and launches nothing.
+ * Scratch: one 112-byte record per probe (28 floats: the 27 products and the validity as 0.0 / 1.0) in a buffer the context owns (grown on
+ *   demand, freed with the context, never the buffers mi_reserve sized; MI_ERR_OOM if it cannot be allocated); the host form keeps the
+ *   uploaded sh and valid behind it.  Two kernels per call (the records, then one lane per point); mi_last_kernel_ms reports their sum.
+ * mi_probe_volume_sample: HOST pointers (sh and valid included), blocking; the points go through the ray queries' chunk buffer.
+ * mi_probe_volume_sample_device: sh, valid, points, normals and the outputs are DEVICE pointers on ctx's device (the struct itself is
+ *   host memory).  Queues on `stream` and does not synchronise, except when it has to grow its scratch.  The records belong to the
+ *   context: calls on different streams of one context must not overlap. */
+typedef struct mi_probe_volume {
+    float          lo[3];           /* the box probe_grid was given                                  */
+    float          hi[3];
+    uint32_t       counts[3];       /* nx, ny, nz: probe (i,j,k) has number (k*ny + j)*nx + i        */
+    uint32_t       flags;           /* MI_PV_* bits                                                  */
+    const float*   sh;              /* [n_probes][9][3] f32, mi_render_probes' out_sh order          */
+    const uint8_t* valid;           /* [n_probes] bytes, 0 = probe takes no part; NULL = all valid   */
+} mi_probe_volume;              /* 56 bytes */
+int  mi_probe_volume_sample(mi_ctx* ctx, const mi_probe_volume* volume, uint32_t n_points, const float* points, const float* normals,
+                            float* out_irradiance, float* out_weight);
+int  mi_probe_volume_sample_device(mi_ctx* ctx, const mi_probe_volume* volume, uint32_t n_points, const float* points, const float* normals,
+                                   float* out_irradiance, float* out_weight, void* stream);
 
 /* Size and allocate the wavefront pipeline's HBM buffers (path state, sample slots) for
  * this camera with the image shared by `world` ranks, so that the first render does not pay the

@@ -36,12 +36,18 @@ use std::os::raw::{c_char, c_int, c_void};
 }
 #[repr(C)] #[derive(Default)] pub struct mi_render_opts { pub seed: u32, pub rank: i32, pub world: i32, pub variant: i32, pub want_signature: i32, pub flags: u32, pub max_state_bytes: u64 }
 #[repr(C)] #[derive(Default)] pub struct mi_stats { pub samples: u64, pub pixels: u64, pub tiles: u32, pub tiles_padded: u32, pub kernel_ms: f32, pub total_ms: f32, pub scene_bytes: u32, pub scene_in_lds: u32 }
+// A probe grid for mi_probe_volume_sample (sh and valid: host addresses for the host form, device addresses for the _device form).  The C
+// layout, 56 bytes; align(8) spells out the alignment its pointers give it.  tests/test_probe_volume_host.py compares it with the header.
+#[repr(C, align(8))] #[derive(Clone, Copy)] pub struct mi_probe_volume {
+    pub lo: [f32; 3], pub hi: [f32; 3], pub counts: [u32; 3], pub flags: u32, pub sh: *const f32, pub valid: *const u8,
+}
 pub enum mi_ctx {}
 pub enum mi_multi {}
 pub const MI_OPT_NO_TILE_MASKS: u32 = 1; pub const MI_OPT_REFERENCE_WALK: u32 = 2; pub const MI_OPT_TWO_STAGE: u32 = 4; pub const MI_OPT_NO_LIST_TREE: u32 = 8;
 pub const MI_RT_ABI_VERSION: c_int = 5;
 pub const MI_HEMI_WORLD_RADIUS: u32 = 1;
 pub const MI_LM_JITTER: u32 = 1;
+pub const MI_PV_NORMAL_WEIGHT: u32 = 1;
 // mi_material_kind / mi_object_kind / projection and shading modes (include/mi_rt.h)
 pub const MI_MAT_LAMBERTIAN: i32 = 0; pub const MI_MAT_METAL: i32 = 1; pub const MI_MAT_DIELECTRIC: i32 = 2;
 pub const MI_MAT_PARAMETERIZED: i32 = 3; pub const MI_MAT_ISOTROPIC: i32 = 4;
@@ -133,6 +139,12 @@ extern "C" {
                                    d_points: *const f32, rows_per_pixel: u32,
                                    sample_begin: u32, sample_end: u32, d_accum_f32x4: *mut c_void, d_compact_sh: *mut c_void,
                                    d_compact_f32: *mut c_void, d_sig_u32: *mut c_void, stream: *mut c_void, stats: *mut mi_stats) -> c_int;
+    // irradiance volumes (added within ABI 5): SH L2 probe grids sampled at surface points; points / normals / out_irradiance are [n][3],
+    // out_weight [n] or null; the _device form takes device addresses (in the struct too)
+    pub fn mi_probe_volume_sample(ctx: *mut mi_ctx, volume: *const mi_probe_volume, n_points: u32, points: *const f32, normals: *const f32,
+                                  out_irradiance: *mut f32, out_weight: *mut f32) -> c_int;
+    pub fn mi_probe_volume_sample_device(ctx: *mut mi_ctx, volume: *const mi_probe_volume, n_points: u32, points: *const f32,
+                                         normals: *const f32, out_irradiance: *mut f32, out_weight: *mut f32, stream: *mut c_void) -> c_int;
     pub fn mi_reserve(ctx: *mut mi_ctx, cam: *const mi_camera_desc, world: i32, max_state_bytes: u64) -> c_int;
     pub fn mi_last_pipeline_ms(ctx: *mut mi_ctx, out8: *mut f32) -> c_int;
     pub fn mi_last_pipeline_counts(ctx: *mut mi_ctx, out8: *mut u64) -> c_int;

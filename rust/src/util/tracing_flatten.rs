@@ -254,6 +254,35 @@ impl Scene {
         sh
     }
 
+    /// Sample an irradiance volume (mi_probe_volume_sample): `sh` holds the first nx * ny * nz records of render_probes' result for
+    /// the probe grid of the box [lo, hi] (probe (i, j, k) has number (k * ny + j) * nx + i and sits at the centre of its cell), `valid`
+    /// is empty (every probe takes part) or one byte per probe (0 = takes no part).  Every point is lit through its normal: trilinear
+    /// interpolation of the eight probes around it, convolved with the clamped cosine lobe; `normal_weight` sets MI_PV_NORMAL_WEIGHT.
+    /// An all-zero normal marks an empty texel (+0.0, weight 0).  Returns the irradiance and the weight sum per point (0: every corner
+    /// was invalid).  Needs no scene: an associated function.
+    pub fn sample_probe_volume(lo: [f32; 3], hi: [f32; 3], counts: [u32; 3], sh: &[[[f32; 3]; 9]], valid: &[u8], normal_weight: bool,
+                               points: &[[f32; 3]], normals: &[[f32; 3]]) -> (Vec<[f32; 3]>, Vec<f32>) {
+        let n = counts[0] as usize * counts[1] as usize * counts[2] as usize;
+        assert!(sh.len() == n && (valid.is_empty() || valid.len() == n), "mi_rt: sh (and valid) must hold nx * ny * nz probes");
+        assert_eq!(points.len(), normals.len(), "mi_rt: one normal per point");
+        let volume = mi_rt::mi_probe_volume {
+            lo: lo, hi: hi, counts: counts, flags: if normal_weight { mi_rt::MI_PV_NORMAL_WEIGHT } else { 0 },
+            sh: sh.as_ptr() as *const f32, valid: if valid.is_empty() { std::ptr::null() } else { valid.as_ptr() },
+        };
+        let mut out = vec![[0.0f32; 3]; points.len()];
+        let mut weight = vec![0.0f32; points.len()];
+        unsafe {
+            let mut ctx = std::ptr::null_mut();
+            assert_eq!(mi_rt::mi_ctx_create(0, &mut ctx), 0, "{}", mi_rt::last_error());
+            let rc = mi_rt::mi_probe_volume_sample(ctx, &volume, points.len() as u32, points.as_ptr() as *const f32,
+                                                   normals.as_ptr() as *const f32, out.as_mut_ptr() as *mut f32, weight.as_mut_ptr());
+            let msg = mi_rt::last_error();
+            mi_rt::mi_ctx_destroy(ctx);
+            assert_eq!(rc, 0, "{}", msg);
+        }
+        (out, weight)
+    }
+
     /// flatten -> context on device 0 -> upload -> `call` -> destroy; panics with the library's message on failure.
     fn with_gpu_scene<F: FnOnce(*mut mi_rt::mi_ctx) -> i32>(&self, call: F) {
         let sb = self.flatten_scene();

@@ -72,7 +72,15 @@ two calls that differ by that pass (levels = k + 1 against levels = k, both with
 dilate = 0, divided by 8).  Every level is run in both forms of lmf_atrous, in two contexts created under the developer knob
 MI_RT_LMF_LDS_MAX_STEP (0: every step reads HBM directly; 8: steps 1 .. 8 stage tile and halo in LDS; step 16 has no LDS form), the whole
 call also in a context with the library's own threshold, and the images of all three are compared bit for bit.  Per level: effective GB/s on the compulsory bytes (60 B per texel: 36 B of guides and 12 B of
-colour read, 12 B written), beside the rate of a device-to-device copy that moves the same byte count, timed by events in the same run."""
+colour read, 12 B written), beside the rate of a device-to-device copy that moves the same byte count, timed by events in the same run.
+
+--mode volume times irradiance-volume sampling (mi_probe_volume_sample_device) on device-resident tables: volumes of --volume-grids probes
+per axis (default 16 and 32) over the bounding box of the drone's atlas, seeded sh (the cost does not depend on the values), every fifth
+probe invalid, MI_PV_NORMAL_WEIGHT set; --volume-points (default 2^20 and 2^22) surface points taken from the covered texels of the
+drone's 4096 x 4096 atlas table in raster order ("coherent": neighbouring lanes share corners) and the same points shuffled
+("incoherent").  A call's two kernels are timed by HIP events (mi_last_kernel_ms), 5 warm-up calls then --calls timed ones: median and
+min - max.  pv_prepare alone is a call with one point.  The floor is a device-to-device copy of the same input and output bytes (40 B per
+point: 24 in, 16 out), timed by events in the same run.  The first 4096 points of every row are compared with the helper bit for bit."""
 import argparse
 import json
 import os
@@ -86,7 +94,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
-from cs397raytracingsp22_amd import Context, scenes  # noqa: E402
+from cs397raytracingsp22_amd import Context, abi, scenes  # noqa: E402
 
 
 def pinhole_rays(cam):
@@ -659,6 +667,84 @@ def render_rows(ctx, cfg, sc, co, cd, calls, warmup):
     return rows
 
 
+def volume_rows(ctx, grids, point_counts, calls, warmup):
+    """--mode volume (the module's docstring)"""
+    from cs397raytracingsp22_amd import probe_volume_sample
+    dev = torch.device("cuda:0")
+    size = 4096
+    sc = scenes.config4(size, size, 1, 10)
+    drone = sc.objects[-1]
+    mesh = drone.mesh
+    t_mesh = [torch.from_numpy(np.array(a)).to(dev) for a in (mesh.positions, mesh.normals, mesh.texcoords, mesh.indices.view(np.int32))]
+    pts = torch.empty((size, size, 3), dtype=torch.float32, device=dev)
+    nrm = torch.empty((size, size, 3), dtype=torch.float32, device=dev)
+    ctx.lightmap_texels_device(t_mesh[0].data_ptr(), t_mesh[1].data_ptr(), t_mesh[2].data_ptr(), t_mesh[3].data_ptr(), mesh.n_vertices,
+                               mesh.n_triangles, size, size, pts.data_ptr(), nrm.data_ptr(), None, rows=1, jitter=False, seed=1,
+                               offset=float(np.float32(1e-3)), transform=drone.transform)
+    torch.cuda.synchronize()
+    covered = (nrm != 0).any(dim=-1).reshape(-1)
+    all_p, all_n = pts.reshape(-1, 3)[covered], nrm.reshape(-1, 3)[covered]                  # raster order
+    del pts, nrm
+    lo = (all_p.min(dim=0).values - 0.05).cpu().numpy().astype(np.float32)
+    hi = (all_p.max(dim=0).values + 0.05).cpu().numpy().astype(np.float32)
+    gen = torch.Generator(device=dev)
+    gen.manual_seed(1)
+    rows = []
+    for n_points in point_counts:
+        reps = (n_points + len(all_p) - 1) // len(all_p)
+        coh_p, coh_n = all_p.repeat(reps, 1)[:n_points].contiguous(), all_n.repeat(reps, 1)[:n_points].contiguous()
+        perm = torch.randperm(n_points, generator=gen, device=dev)
+        sets = {"coherent": (coh_p, coh_n), "incoherent": (coh_p[perm].contiguous(), coh_n[perm].contiguous())}
+        out_E = torch.empty((n_points, 3), dtype=torch.float32, device=dev)
+        out_w = torch.empty(n_points, dtype=torch.float32, device=dev)
+        moved = 40 * n_points
+        src, dst = torch.empty(moved // 2, dtype=torch.uint8, device=dev), torch.empty(moved // 2, dtype=torch.uint8, device=dev)
+        copy_ms = []
+        for k in range(warmup + calls):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            dst.copy_(src)
+            e1.record()
+            torch.cuda.synchronize()
+            if k >= warmup:
+                copy_ms.append(e0.elapsed_time(e1))
+        copy = float(np.median(copy_ms))
+        del src, dst
+        for g in grids:
+            n_probes = g ** 3
+            sh_host = np.random.default_rng(g).normal(0.0, 1.0, (n_probes, 9, 3)).astype(np.float32)
+            sh_host[:, 0, :] += 3.0
+            valid_host = (np.arange(n_probes) % 5 != 0).astype(np.uint8)
+            sh, valid = torch.from_numpy(sh_host).to(dev), torch.from_numpy(valid_host).to(dev)
+
+            def timed(p, nn, n):
+                ms = []
+                for k in range(warmup + calls):
+                    ctx.probe_volume_sample_device(lo, hi, (g, g, g), sh.data_ptr(), n, p.data_ptr(), nn.data_ptr(), out_E.data_ptr(),
+                                                   d_weight=out_w.data_ptr(), d_valid=valid.data_ptr(), flags=abi.MI_PV_NORMAL_WEIGHT)
+                    torch.cuda.synchronize()
+                    if k >= warmup:
+                        ms.append(ctx.last_kernel_ms())
+                return float(np.median(ms)), float(np.min(ms)), float(np.max(ms))
+
+            prep = timed(coh_p, coh_n, 1)
+            for name, (p, nn) in sets.items():
+                med, mn, mx = timed(p, nn, n_points)
+                k = min(4096, n_points)
+                want_E, want_w = probe_volume_sample(lo, hi, (g, g, g), sh_host, p[:k].cpu().numpy(), nn[:k].cpu().numpy(), valid_host,
+                                                     abi.MI_PV_NORMAL_WEIGHT)
+                got_E, got_w = out_E[:k].cpu().numpy(), out_w[:k].cpu().numpy()
+                differ = int(((got_E.view(np.uint32) != want_E.view(np.uint32)).any(axis=-1) | (got_w.view(np.uint32) != want_w.view(np.uint32))).sum())
+                row = {"mode": "volume", "grid": g, "record_bytes": 112 * n_probes, "n_points": n_points, "points": name, "calls": calls,
+                       "kernel_ms_median": round(med, 4), "kernel_ms_min": round(mn, 4), "kernel_ms_max": round(mx, 4),
+                       "pv_prepare_ms_median": round(prep[0], 4), "mpoints_per_s": round(n_points / med / 1e3, 1),
+                       "gb_per_s_on_40_bytes": round(moved / med / 1e6, 1), "copy_ms_median": round(copy, 4),
+                       "copy_gb_per_s": round(moved / copy / 1e6, 1), "checked_points": k, "differ_from_helper": differ}
+                rows.append(row)
+                print(json.dumps(row), flush=True)
+    return rows
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--calls", type=int, default=20, help="timed calls per row (at least 20)")
@@ -666,14 +752,17 @@ def main():
     ap.add_argument("--width", type=int, default=1920)
     ap.add_argument("--height", type=int, default=1080)
     ap.add_argument("--configs", default="2,4")
-    ap.add_argument("--mode", choices=("intersect", "occlusion", "render", "hemisphere", "bake", "probes", "atlas", "finish"), default="intersect",
+    ap.add_argument("--mode", choices=("intersect", "occlusion", "render", "hemisphere", "bake", "probes", "atlas", "finish", "volume"), default="intersect",
                     help="intersect: the closest-hit rows; occlusion: the any-hit query against the visibility form; "
                          "render: ray-table rendering against mi_shade_rays_device; "
                          "hemisphere: hemisphere occlusion against the any-hit query on the identical pre-made rays; "
                          "bake: point-table rendering against ray-table rendering on the identical pre-made rays; "
                          "probes: light-probe rendering against ray-table rendering on the identical pre-made rays; "
                          "atlas: the lightmap atlas on the GPU against the host helper, on the drone; "
-                         "finish: lightmap finishing pass by pass, both forms of the filter, against a copy of the same bytes")
+                         "finish: lightmap finishing pass by pass, both forms of the filter, against a copy of the same bytes; "
+                         "volume: irradiance-volume sampling, coherent and shuffled points, against a copy of the same bytes")
+    ap.add_argument("--volume-grids", default="16,32", help="--mode volume: probes per axis")
+    ap.add_argument("--volume-points", default=f"{1 << 20},{1 << 22}", help="--mode volume: point counts")
     ap.add_argument("--finish-sizes", default="1024,2048,4096", help="--mode finish: the square atlas sizes")
     ap.add_argument("--atlas-sizes", default="1024,2048", help="--mode atlas: the square atlas sizes")
     ap.add_argument("--atlas-grid", type=int, default=0, help="--mode atlas: a synthetic height field of N x N quads (2 N^2 triangles) instead "
@@ -692,6 +781,9 @@ def main():
             rows += finish_rows(size, a.calls, a.warmup)
         a.configs = ""
     ctx = Context(0)
+    if a.mode == "volume":
+        rows += volume_rows(ctx, [int(v) for v in a.volume_grids.split(",")], [int(v) for v in a.volume_points.split(",")], a.calls, a.warmup)
+        a.configs = ""
     if a.mode == "atlas":
         for size in [int(v) for v in a.atlas_sizes.split(",")]:
             rows += atlas_rows(ctx, size, a.calls, a.warmup, a.atlas_bakes, a.atlas_grid)
