@@ -126,6 +126,8 @@ EXPORTS = [
     "mi_render_probes", "mi_render_probes_device",
     "mi_lightmap_texels", "mi_lightmap_texels_device", "mi_bake_lightmap",
     "mi_lightmap_finish", "mi_lightmap_finish_device",
+    "mi_render_points_moments", "mi_render_points_moments_device", "mi_bake_lightmap_moments",
+    "mi_lightmap_finish_var", "mi_lightmap_finish_var_device",
     "mi_probe_volume_sample", "mi_probe_volume_sample_device",
     "mi_multi_create", "mi_multi_create_loopback", "mi_multi_destroy", "mi_multi_device_count", "mi_multi_context", "mi_multi_scene_upload", "mi_multi_reserve", "mi_multi_render",
 ]
@@ -250,6 +252,23 @@ def load() -> C.CDLL:
     lib.mi_lightmap_finish.restype = C.c_int
     lib.mi_lightmap_finish_device.argtypes = lib.mi_lightmap_finish.argtypes + [vp]
     lib.mi_lightmap_finish_device.restype = C.c_int
+    # lightmap variance (added within ABI 5): mi_render_points' / mi_bake_lightmap's argument lists with out_m2 before the plain outputs,
+    # mi_render_points_device's with d_compact_m2 behind the accumulator; mi_lightmap_finish's with m2 and samples behind the image,
+    # color_floor behind sigma_color and out_var behind out_image
+    lib.mi_render_points_moments.argtypes = [vp, C.POINTER(mi_camera_desc), C.POINTER(mi_render_opts), vp, vp, C.c_uint32,
+                                             vp, vp, vp, vp, C.POINTER(mi_stats)]
+    lib.mi_render_points_moments.restype = C.c_int
+    lib.mi_render_points_moments_device.argtypes = [vp, C.POINTER(mi_camera_desc), C.POINTER(mi_render_opts), vp, vp, C.c_uint32,
+                                                    C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp, C.POINTER(mi_stats)]
+    lib.mi_render_points_moments_device.restype = C.c_int
+    lib.mi_bake_lightmap_moments.argtypes = [vp, C.POINTER(mi_camera_desc), C.POINTER(mi_render_opts), C.POINTER(mi_mesh), C.c_uint32,
+                                             C.c_float, vp, vp, vp, vp, vp, C.POINTER(mi_stats)]
+    lib.mi_bake_lightmap_moments.restype = C.c_int
+    lib.mi_lightmap_finish_var.argtypes = [vp, C.c_uint32, C.c_uint32, vp, vp, C.c_uint32, vp, vp, C.c_uint32, C.c_uint32, C.c_float,
+                                           C.c_float, C.c_float, C.c_float, C.c_uint32, vp, vp, vp]
+    lib.mi_lightmap_finish_var.restype = C.c_int
+    lib.mi_lightmap_finish_var_device.argtypes = lib.mi_lightmap_finish_var.argtypes + [vp]
+    lib.mi_lightmap_finish_var_device.restype = C.c_int
     # irradiance volumes (added within ABI 5): volume, n_points, points, normals, out_irradiance, out_weight (, stream)
     lib.mi_probe_volume_sample.argtypes = [vp, C.POINTER(mi_probe_volume), C.c_uint32, vp, vp, vp, vp]
     lib.mi_probe_volume_sample.restype = C.c_int

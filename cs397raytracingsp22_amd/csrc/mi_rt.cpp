@@ -62,6 +62,10 @@ hipError_t launch_lmf_atrous(const LmfArgs& a, bool lds, bool* big_lds_enabled, 
 hipError_t launch_lmf_dilate(const LmfArgs& a, hipStream_t stream);
 hipError_t launch_pv_prepare(const PvArgs& a, hipStream_t stream);
 hipError_t launch_pv_sample(const PvArgs& a, hipStream_t stream);
+hipError_t launch_wf_reduce_m2(const WfArgs& a, bool first_batch, bool last_batch, hipStream_t stream);
+hipError_t launch_lmv_init(const LmvArgs& a, hipStream_t stream);
+hipError_t launch_lmv_blur(const LmvArgs& a, hipStream_t stream);
+hipError_t launch_lmv_atrous(const LmvArgs& a, hipStream_t stream);
 }  // namespace pt
 
 using namespace pt;
@@ -134,6 +138,12 @@ struct mi_ctx {
     // mi_probe_volume_sample: the prepared 112-byte probe records and, behind them, the host form's uploaded sh and valid (grown on
     // demand, never the buffers mi_reserve sized)
     void* d_pv = nullptr; size_t pv_bytes = 0;
+    // mi_render_points_moments / mi_bake_lightmap_moments: the compact second-moment records, then the un-permuted [H][W][3] plane;
+    // mi_lightmap_finish_var: two variance planes and the colour weight's denominators, and the host form's uploaded moments and its
+    // variance result (all grown on demand, never the buffers mi_reserve sized)
+    void* d_m2 = nullptr; size_t m2_bytes = 0;
+    void* d_lmv = nullptr; size_t lmv_bytes = 0;
+    void* d_lmv_io = nullptr; size_t lmv_io_bytes = 0;
     hipEvent_t ev_t0 = nullptr, ev_t1 = nullptr;     // mi_render's whole-call timer
     bool big_lds_enabled = false;                    // wf_trav_i<1024>'s > 64 KB dynamic-LDS opt-in, set on THIS context's device
     // wavefront pipeline buffers
@@ -154,7 +164,7 @@ struct mi_ctx {
         void* d_words = nullptr; size_t d_bytes = 0;
     } masks;
     std::vector<hipEvent_t> wf_ev;                   // event pool for per-kernel timing of the pipeline
-    float wf_ms[8] = { 0, 0, 0, 0, 0, 0, 0, 0 };     // last frame: wf_main, wf_trav, wf_reduce totals (ms), launches, wf_trav_f, wf_replay, class A, wf_reduce_sh
+    float wf_ms[8] = { 0, 0, 0, 0, 0, 0, 0, 0 };     // last frame: wf_main, wf_trav, wf_reduce totals (ms), launches, wf_trav_f, wf_replay, class A, wf_reduce_sh or wf_reduce_m2
     int n_cus = 256;
     // Developer knobs (MI_RT_* environment variables), read ONCE in mi_ctx_create; none is needed for
     // normal operation and none changes a result — what a caller may want to control is in mi_render_opts.
@@ -299,6 +309,9 @@ extern "C" void mi_ctx_destroy(mi_ctx* c) {
     if (c->d_lmf) (void)hipFree(c->d_lmf);
     if (c->d_lmf_io) (void)hipFree(c->d_lmf_io);
     if (c->d_pv) (void)hipFree(c->d_pv);
+    if (c->d_m2) (void)hipFree(c->d_m2);
+    if (c->d_lmv) (void)hipFree(c->d_lmv);
+    if (c->d_lmv_io) (void)hipFree(c->d_lmv_io);
     if (c->d_wf_a) (void)hipFree(c->d_wf_a);
     if (c->d_wf_b) (void)hipFree(c->d_wf_b);
     if (c->d_wf_samp) (void)hipFree(c->d_wf_samp);
@@ -474,7 +487,7 @@ private:
 // Per-launch timing of the pipeline: one event pair per launch from the context's pool, summed per kind into wf_ms after the
 // frame.  One pair is ~0.4 ms per frame of extra barriers: nothing on a whole frame (109 ms), 3 % of a 1/8 share, so multi-rank
 // renders skip it unless asked (MI_RT_WF_KERNEL_TIMING=0/1 overrides).
-enum LaunchKind { kMain, kTrav, kReduce, kTravF, kReplay, kMainA, kReduceSh };      // kTravF: wf_filter_f too; kMainA: wf_main's class-A part on the second stream
+enum LaunchKind { kMain, kTrav, kReduce, kTravF, kReplay, kMainA, kReduceSh, kReduceM2 };      // kTravF: wf_filter_f too; kMainA: wf_main's class-A part on the second stream
 class LaunchTimer {
 public:
     LaunchTimer(mi_ctx* c, bool on) : c_(c), on_(on) {}
@@ -485,18 +498,20 @@ public:
         if (stamp(kind, on) != MI_OK) return fail(MI_ERR_HIP, "event");
         return MI_OK;
     }
-    // after the frame (the streams have drained): wf_ms = {wf_main, wf_trav, wf_reduce} ms, launches, {wf_trav_f, wf_replay, class A, wf_reduce_sh} ms
+    // after the frame (the streams have drained): wf_ms = {wf_main, wf_trav, wf_reduce} ms, launches, {wf_trav_f, wf_replay, class A, wf_reduce_sh} ms;
+    // wf_reduce_m2 shares entry 7 with wf_reduce_sh (no render runs both)
     void finish() {
         for (int k = 0; k < 8; k++) c_->wf_ms[k] = 0.0f;
         c_->wf_ms[3] = (float)(used_ / 2);
         for (size_t e = 0; e + 1 < used_; e += 2) {
             float ms = 0.0f;
-            if (hipEventElapsedTime(&ms, c_->wf_ev[e], c_->wf_ev[e + 1]) == hipSuccess) c_->wf_ms[kinds_[e] < 3 ? kinds_[e] : kinds_[e] + 1] += ms;
+            if (hipEventElapsedTime(&ms, c_->wf_ev[e], c_->wf_ev[e + 1]) == hipSuccess) c_->wf_ms[kinds_[e] < 3 ? kinds_[e] : kinds_[e] == kReduceM2 ? 7 : kinds_[e] + 1] += ms;
             if (c_->tune.dump_launches) fprintf(stderr, "[mi_rt] launch %zu %s %.4f ms\n", e / 2, kNames[kinds_[e]], ms);
         }
     }
 private:
-    static constexpr const char* kNames[7] = { "wf_main", "wf_trav", "wf_reduce", "wf_trav_f", "wf_replay", "wf_main (class A, beside the walkers)", "wf_reduce_sh" };
+    static constexpr const char* kNames[8] = { "wf_main", "wf_trav", "wf_reduce", "wf_trav_f", "wf_replay", "wf_main (class A, beside the walkers)", "wf_reduce_sh",
+                                               "wf_reduce_m2" };
     int stamp(LaunchKind kind, hipStream_t on) {          // before AND after the launch
         if (!on_) return MI_OK;
         if (used_ == c_->wf_ev.size()) { hipEvent_t e; if (hipEventCreate(&e) != hipSuccess) return MI_ERR_HIP; c_->wf_ev.push_back(e); }
@@ -518,8 +533,9 @@ struct SampleRange { uint32_t begin, end; float4* accum; };
 // the direction of each sample itself (the POINTS form of wf_main)
 // Light probes (kind = kTableProbes): `origins` holds probe positions, `dirs` is nullptr; the camera pass draws a full-sphere direction (the
 // PROBES form) and `sh`, DEVICE [tiles_padded][1024][27] or nullptr, takes the SH L2 sums (wf_reduce_sh)
+// Second moments (point tables): `m2`, DEVICE [tiles_padded][1024][3] or nullptr, takes the sums of squares (wf_reduce_m2)
 enum TableKind { kTableRays, kTablePoints, kTableProbes };
-struct RayTable { const float* origins; const float* dirs; uint32_t rows; TableKind kind; float* sh; };
+struct RayTable { const float* origins; const float* dirs; uint32_t rows; TableKind kind; float* sh; float* m2; };
 
 static int render_tiles_wavefront(mi_ctx* c, const K1Args& k, const mi_camera_desc* cam, WfArgs a, uint32_t s_batch, uint32_t flags,
                                   float* d_compact, uint32_t* d_sig, SampleRange range, hipStream_t stream) {
@@ -631,6 +647,8 @@ static int render_tiles_wavefront(mi_ctx* c, const K1Args& k, const mi_camera_de
         MI_TRY(timer.run(kReduce, stream, [&] { return launch_wf_reduce(a, s0 == 0, s0 + a.s_count >= spp, stream); }));
         // light probes: the SH sums of the same slots, same batch rules (the slots are rewritten by the next batch only, behind this)
         if (a.sh) MI_TRY(timer.run(kReduceSh, stream, [&] { return launch_wf_reduce_sh(a, s0 == 0, s0 + a.s_count >= spp, stream); }));
+        // second moments of a point-table bake: the sums of squares of the same slots, same batch rules
+        if (a.m2) MI_TRY(timer.run(kReduceM2, stream, [&] { return launch_wf_reduce_m2(a, s0 == 0, s0 + a.s_count >= spp, stream); }));
         // the headers not read yet (statistics; passes launched behind the one that ended every path are not counted)
         const uint32_t launched = c->hdr_seq + 1u - seq0;
         while (seen < launched) { MI_TRY(ring.wait(seq0 + seen)); consume(!all_dead); }
@@ -697,7 +715,7 @@ static int render_tiles(mi_ctx* c, const mi_camera_desc* cam, const mi_render_op
         MI_TRY(wf_prepare(c, g.padded, cam->aa_sample_count, o->max_state_bytes, two_stage_mask(c->scene, o->flags) != 0u, wa, wf_batch));
         if (table && table->kind != kTableRays) {
             wa.pt_p = table->origins; wa.pt_n = table->dirs; wa.pt_rows = table->rows;
-            wa.pt_probes = table->kind == kTableProbes ? 1u : 0u; wa.sh = table->sh;
+            wa.pt_probes = table->kind == kTableProbes ? 1u : 0u; wa.sh = table->sh; wa.m2 = table->m2;
         }
         else if (table) { wa.ray_o = table->origins; wa.ray_d = table->dirs; wa.rays_per_pixel = table->rows; }
     }
@@ -1038,8 +1056,9 @@ extern "C" int mi_selftest(mi_ctx* c, uint64_t* out4) {
 
 // The whole image on this GPU into host buffers: render, un-permute, tone-map, download (mi_render; with `table`, mi_render_rays / _points).
 // out_sh (mi_render_probes): table->sh holds the compact SH records; un-permuted into the plane behind them and downloaded as well.
+// out_m2 (mi_render_points_moments): the same for table->m2, whose 3-float records fb_unpermute un-permutes.
 static int render_image(mi_ctx* c, const mi_camera_desc* cam, const mi_render_opts* opts, const RayTable* table, float* out_rgb_f32,
-                        uint8_t* out_rgb_u8, uint32_t* out_sig, mi_stats* stats, float* out_sh = nullptr) {
+                        uint8_t* out_rgb_u8, uint32_t* out_sig, mi_stats* stats, float* out_sh = nullptr, float* out_m2 = nullptr) {
     int rc;
     const hipEvent_t t0 = c->ev_t0, t1 = c->ev_t1;      // owned by the context: no early return can leak them
     const TileGrid g = tile_grid(cam, 1);
@@ -1072,6 +1091,11 @@ static int render_image(mi_ctx* c, const mi_camera_desc* cam, const mi_render_op
         float* plane = table->sh + (size_t)g.padded * kTilePixels * kShFloats;
         HIP_TRY(launch_sh_unpermute(table->sh, plane, cam->screen_width, cam->screen_height, g.tx, 1, g.padded, c->stream));
         HIP_TRY(hipMemcpyAsync(out_sh, plane, npix * kShFloats * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    }
+    if (out_m2) {
+        float* plane = table->m2 + (size_t)g.padded * kTilePixels * 3;
+        HIP_TRY(launch_unpermute(table->m2, plane, cam->screen_width, cam->screen_height, g.tx, 1, g.padded, c->stream));
+        HIP_TRY(hipMemcpyAsync(out_m2, plane, npix * 3 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
     }
     HIP_TRY(hipEventRecord(t1, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
@@ -1114,11 +1138,19 @@ static int check_table_args(mi_ctx* c, const mi_camera_desc* cam, const mi_rende
     return MI_OK;
 }
 
+// The context's moments buffer for a W x H image: the compact records, then the plane render_image un-permutes them into
+static int moments_buffer(mi_ctx* c, const mi_camera_desc* cam, float** out) {
+    const size_t slots = (size_t)tile_grid(cam, 1).padded * kTilePixels + (size_t)cam->screen_width * cam->screen_height;
+    MI_TRY(ensure(&c->d_m2, &c->m2_bytes, slots * 3 * sizeof(float)));
+    *out = (float*)c->d_m2;
+    return MI_OK;
+}
+
 // Host pointers: upload the two tables (light probes: the one) into the context's own buffer, then mi_render's body.  `what` names the
-// entry point in messages.  out_sh: light probes only, and required there.
+// entry point in messages.  out_sh: light probes only, and required there.  out_m2: point tables only (the _moments calls).
 static int render_table_host(mi_ctx* c, const mi_camera_desc* cam, const mi_render_opts* opts, const float* first, const float* second,
                              uint32_t rows, TableKind kind, const char* what, float* out_rgb_f32, uint8_t* out_rgb_u8, uint32_t* out_sig,
-                             mi_stats* stats, float* out_sh = nullptr) {
+                             mi_stats* stats, float* out_sh = nullptr, float* out_m2 = nullptr) {
     MI_TRY(check_table_args(c, cam, opts, first, second, rows, kind));
     if (opts->rank != 0 || opts->world != 1) return fail(MI_ERR_INVALID, "%s renders a whole image: rank/world must be 0/1", what);
     if (kind == kTableProbes && !out_sh) return fail(MI_ERR_INVALID, "%s: out_sh is required", what);
@@ -1127,23 +1159,26 @@ static int render_table_host(mi_ctx* c, const mi_camera_desc* cam, const mi_rend
     MI_TRY(ensure(&c->d_rays, &c->rays_bytes, (second ? 2 : 1) * bytes));
     HIP_TRY(hipMemcpyAsync(c->d_rays, first, bytes, hipMemcpyHostToDevice, c->stream));
     if (second) HIP_TRY(hipMemcpyAsync((char*)c->d_rays + bytes, second, bytes, hipMemcpyHostToDevice, c->stream));
-    RayTable table = { (const float*)c->d_rays, second ? (const float*)((const char*)c->d_rays + bytes) : nullptr, rows, kind, nullptr };
+    RayTable table = { (const float*)c->d_rays, second ? (const float*)((const char*)c->d_rays + bytes) : nullptr, rows, kind, nullptr, nullptr };
     if (out_sh) {           // the compact records, then the plane render_image un-permutes them into
         const size_t slots = (size_t)tile_grid(cam, 1).padded * kTilePixels + (size_t)cam->screen_width * cam->screen_height;
         MI_TRY(ensure(&c->d_sh, &c->sh_bytes, slots * kShFloats * sizeof(float)));
         table.sh = (float*)c->d_sh;
     }
+    if (out_m2) MI_TRY(moments_buffer(c, cam, &table.m2));
     const mi_camera_desc tc = table_camera(cam);
-    return render_image(c, &tc, opts, &table, out_rgb_f32, out_rgb_u8, out_sig, stats, out_sh);
+    return render_image(c, &tc, opts, &table, out_rgb_f32, out_rgb_u8, out_sig, stats, out_sh, out_m2);
 }
 
-// Device pointers: mi_render_tiles_device and mi_render_samples_device in one call.  d_compact_sh: light probes only, may be NULL.
+// Device pointers: mi_render_tiles_device and mi_render_samples_device in one call.  d_compact_sh: light probes only, may be NULL;
+// d_compact_m2: point tables only, may be NULL.
 static int render_table_device(mi_ctx* c, const mi_camera_desc* cam, const mi_render_opts* opts, const float* d_first, const float* d_second,
                                uint32_t rows, TableKind kind, uint32_t sample_begin, uint32_t sample_end, void* d_accum_f32x4,
-                               void* d_compact_f32, void* d_sig_u32, void* stream, mi_stats* stats, void* d_compact_sh = nullptr) {
+                               void* d_compact_f32, void* d_sig_u32, void* stream, mi_stats* stats, void* d_compact_sh = nullptr,
+                               void* d_compact_m2 = nullptr) {
     MI_TRY(check_table_args(c, cam, opts, d_first, d_second, rows, kind));
     HIP_TRY(hipSetDevice(c->device));
-    const RayTable table = { d_first, d_second, rows, kind, (float*)d_compact_sh };
+    const RayTable table = { d_first, d_second, rows, kind, (float*)d_compact_sh, (float*)d_compact_m2 };
     const mi_camera_desc tc = table_camera(cam);
     // [0, aa_sample_count) without an accumulator is a whole render (mi_render_tiles_device); anything else a progressive call
     const bool whole = sample_begin == 0 && sample_end == cam->aa_sample_count && !d_accum_f32x4;
@@ -1176,6 +1211,25 @@ extern "C" int mi_render_points_device(mi_ctx* c, const mi_camera_desc* cam, con
                                        void* d_accum_f32x4, void* d_compact_f32, void* d_sig_u32, void* stream, mi_stats* stats) {
     return render_table_device(c, cam, opts, d_points, d_normals, rows_per_pixel, kTablePoints, sample_begin, sample_end, d_accum_f32x4,
                                d_compact_f32, d_sig_u32, stream, stats);
+}
+
+// ------------------------------------------------------------------ second moments of a point-table bake
+// mi_render_points with a second output: wf_reduce_m2, behind wf_reduce in every batch, sums the squares of the same samples.  Same
+// checks, same upload buffer, same body; the plain outputs are mi_render_points' bits (no timed kernel changes).
+extern "C" int mi_render_points_moments(mi_ctx* c, const mi_camera_desc* cam, const mi_render_opts* opts, const float* points,
+                                        const float* normals, uint32_t rows_per_pixel, float* out_m2, float* out_rgb_f32,
+                                        uint8_t* out_rgb_u8, uint32_t* out_sig, mi_stats* stats) {
+    if (!out_m2) return fail(MI_ERR_INVALID, "mi_render_points_moments: out_m2 is required");
+    return render_table_host(c, cam, opts, points, normals, rows_per_pixel, kTablePoints, "mi_render_points_moments", out_rgb_f32, out_rgb_u8,
+                             out_sig, stats, nullptr, out_m2);
+}
+
+extern "C" int mi_render_points_moments_device(mi_ctx* c, const mi_camera_desc* cam, const mi_render_opts* opts, const float* d_points,
+                                               const float* d_normals, uint32_t rows_per_pixel, uint32_t sample_begin, uint32_t sample_end,
+                                               void* d_accum_f32x4, void* d_compact_m2, void* d_compact_f32, void* d_sig_u32, void* stream,
+                                               mi_stats* stats) {
+    return render_table_device(c, cam, opts, d_points, d_normals, rows_per_pixel, kTablePoints, sample_begin, sample_end, d_accum_f32x4,
+                               d_compact_f32, d_sig_u32, stream, stats, nullptr, d_compact_m2);
 }
 
 // ------------------------------------------------------------------ lightmap atlas (the point table of a mesh's uv atlas, made on the GPU)
@@ -1300,16 +1354,18 @@ extern "C" int mi_lightmap_texels(mi_ctx* c, const mi_mesh* mesh, uint32_t width
 }
 
 // The whole bake: the mesh up, its table made in the context's table buffer (mi_render_rays'), then mi_render_points' body on it.
-extern "C" int mi_bake_lightmap(mi_ctx* c, const mi_camera_desc* cam, const mi_render_opts* opts, const mi_mesh* mesh, uint32_t flags,
-                                float offset, float* out_rgb_f32, uint8_t* out_rgb_u8, uint32_t* out_sig, int32_t* out_triangle, mi_stats* stats) {
+// out_m2 (mi_bake_lightmap_moments): the second moments as well, as mi_render_points_moments returns them.
+static int bake_lightmap(const char* who, mi_ctx* c, const mi_camera_desc* cam, const mi_render_opts* opts, const mi_mesh* mesh, uint32_t flags,
+                         float offset, float* out_rgb_f32, uint8_t* out_rgb_u8, uint32_t* out_sig, int32_t* out_triangle, mi_stats* stats,
+                         float* out_m2) {
     if (!c) return fail(MI_ERR_INVALID, "ctx is NULL");
-    if (!mesh) return fail(MI_ERR_INVALID, "mi_bake_lightmap: mesh is NULL");
+    if (!mesh) return fail(MI_ERR_INVALID, "%s: mesh is NULL", who);
     const uint32_t rows = (cam && (flags & MI_LM_JITTER)) ? cam->aa_sample_count : 1u;
     MI_TRY(check_table_args(c, cam, opts, (const float*)mesh, (const float*)mesh, rows, kTablePoints));       // (the tables are made here: any non-NULL)
-    if (opts->rank != 0 || opts->world != 1) return fail(MI_ERR_INVALID, "mi_bake_lightmap renders a whole image: rank/world must be 0/1");
+    if (opts->rank != 0 || opts->world != 1) return fail(MI_ERR_INVALID, "%s renders a whole image: rank/world must be 0/1", who);
     const uint32_t W = cam->screen_width, H = cam->screen_height;
-    MI_TRY(check_lm_args("mi_bake_lightmap", c, mesh, W, H, rows, flags, offset, mesh, mesh));
-    MI_TRY(check_lm_indices("mi_bake_lightmap", mesh));
+    MI_TRY(check_lm_args(who, c, mesh, W, H, rows, flags, offset, mesh, mesh));
+    MI_TRY(check_lm_indices(who, mesh));
     HIP_TRY(hipSetDevice(c->device));
     mi_mesh dev;
     MI_TRY(upload_lm_mesh(c, mesh, &dev));
@@ -1320,9 +1376,23 @@ extern "C" int mi_bake_lightmap(mi_ctx* c, const mi_camera_desc* cam, const mi_r
     MI_TRY(lightmap_texels_device(c, &dev, W, H, rows, flags, opts->seed, offset, d_points, d_normals, out_triangle ? (int32_t*)c->d_lm_out : nullptr,
                                   c->stream, true));
     if (out_triangle) HIP_TRY(hipMemcpyAsync(out_triangle, c->d_lm_out, n * 4, hipMemcpyDeviceToHost, c->stream));
-    const RayTable table = { d_points, d_normals, rows, kTablePoints, nullptr };
+    RayTable table = { d_points, d_normals, rows, kTablePoints, nullptr, nullptr };
+    if (out_m2) MI_TRY(moments_buffer(c, cam, &table.m2));
     const mi_camera_desc tc = table_camera(cam);
-    return render_image(c, &tc, opts, &table, out_rgb_f32, out_rgb_u8, out_sig, stats);
+    return render_image(c, &tc, opts, &table, out_rgb_f32, out_rgb_u8, out_sig, stats, nullptr, out_m2);
+}
+
+extern "C" int mi_bake_lightmap(mi_ctx* c, const mi_camera_desc* cam, const mi_render_opts* opts, const mi_mesh* mesh, uint32_t flags,
+                                float offset, float* out_rgb_f32, uint8_t* out_rgb_u8, uint32_t* out_sig, int32_t* out_triangle, mi_stats* stats) {
+    return bake_lightmap("mi_bake_lightmap", c, cam, opts, mesh, flags, offset, out_rgb_f32, out_rgb_u8, out_sig, out_triangle, stats, nullptr);
+}
+
+extern "C" int mi_bake_lightmap_moments(mi_ctx* c, const mi_camera_desc* cam, const mi_render_opts* opts, const mi_mesh* mesh, uint32_t flags,
+                                        float offset, float* out_m2, float* out_rgb_f32, uint8_t* out_rgb_u8, uint32_t* out_sig,
+                                        int32_t* out_triangle, mi_stats* stats) {
+    if (!out_m2) return fail(MI_ERR_INVALID, "mi_bake_lightmap_moments: out_m2 is required");
+    return bake_lightmap("mi_bake_lightmap_moments", c, cam, opts, mesh, flags, offset, out_rgb_f32, out_rgb_u8, out_sig, out_triangle, stats,
+                         out_m2);
 }
 
 // ------------------------------------------------------------------ lightmap finishing (edge-aware a-trous filter, gutter dilation)
@@ -1411,6 +1481,121 @@ extern "C" int mi_lightmap_finish(mi_ctx* c, uint32_t width, uint32_t height, co
                                   out_valid ? (uint8_t*)(io + 4 * img) : nullptr, c->stream));
     HIP_TRY(hipMemcpyAsync(out_image, io + 3 * img, img, hipMemcpyDeviceToHost, c->stream));      // after the uploads: out_image may alias image
     if (out_valid) HIP_TRY(hipMemcpyAsync(out_valid, io + 4 * img, n, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return MI_OK;
+}
+
+// ------------------------------------------------------------------ variance-guided lightmap finishing
+// tracing.py lightmap_finish_var as kernels: lmv_init, then lmv_blur and lmv_atrous per level, then lmf_dilate per pass.  The arguments
+// are checked before the context, as mi_lightmap_finish's are (the device form's overlap test too).
+static int check_lmv_args(const char* who, uint32_t width, uint32_t height, const float* image, const float* m2, uint32_t samples,
+                          const float* points, const float* normals, uint32_t levels, uint32_t normal_power_log2, float sigma_plane,
+                          float reach, float sigma_color, float color_floor, uint32_t dilate, const float* out_image) {
+    if (!image || !m2 || !points || !normals || !out_image)
+        return fail(MI_ERR_INVALID, "%s: image, m2, points, normals and out_image are required", who);
+    if (width == 0 || width > 32768u || height == 0 || height > 32768u)
+        return fail(MI_ERR_INVALID, "%s: width %u / height %u is not in 1 .. 32768", who, width, height);
+    if (levels > 8) return fail(MI_ERR_INVALID, "%s: levels %u is above 8", who, levels);
+    if (normal_power_log2 > 7) return fail(MI_ERR_INVALID, "%s: normal_power_log2 %u is above 7", who, normal_power_log2);
+    if (dilate > 256) return fail(MI_ERR_INVALID, "%s: dilate %u is above 256", who, dilate);
+    if (samples < 2 || samples > 65535u) return fail(MI_ERR_INVALID, "%s: samples %u is not in 2 .. 65535", who, samples);
+    if (!(sigma_plane > 0.0f)) return fail(MI_ERR_INVALID, "%s: sigma_plane must be > 0 (+inf turns the plane weight off)", who);
+    if (!(reach > 0.0f)) return fail(MI_ERR_INVALID, "%s: reach must be > 0 (+inf turns the reach test off)", who);
+    if (!(sigma_color >= 0.0f) || std::isinf(sigma_color)) return fail(MI_ERR_INVALID, "%s: sigma_color must be finite and >= 0", who);
+    if (!(color_floor > 0.0f)) return fail(MI_ERR_INVALID, "%s: color_floor must be > 0 (+inf turns the colour weight off)", who);
+    return MI_OK;
+}
+
+// Queue the passes on `stream`; every pointer is a device pointer and the outputs overlap no input.  The images and masks alternate as in
+// lightmap_finish_device (the same scratch); the variance alternates between the context's two planes, the last level writing d_var when
+// the caller wants it (the dilation passes do not touch it).
+static int lightmap_finish_var_device(mi_ctx* c, uint32_t width, uint32_t height, const float* d_image, const float* d_m2, uint32_t samples,
+                                      const float* d_points, const float* d_normals, uint32_t levels, uint32_t normal_power_log2,
+                                      float sigma_plane, float reach, float sigma_color, float color_floor, uint32_t dilate, float* d_out,
+                                      float* d_var, uint8_t* d_valid, hipStream_t stream) {
+    const size_t n = (size_t)width * height, img = n * 3 * sizeof(float), msk = (n + 255) / 256 * 256, pln = msk * sizeof(float);
+    MI_TRY(ensure(&c->d_lmf, &c->lmf_bytes, 2 * img + 2 * msk));
+    MI_TRY(ensure(&c->d_lmv, &c->lmv_bytes, 3 * pln));
+    float* const ping[2] = { (float*)c->d_lmf, (float*)((char*)c->d_lmf + img) };
+    uint8_t* const mping[2] = { (uint8_t*)c->d_lmf + 2 * img, (uint8_t*)c->d_lmf + 2 * img + msk };
+    float* const vping[2] = { (float*)c->d_lmv, (float*)((char*)c->d_lmv + pln) };
+    LmfArgs a{};
+    a.points = d_points; a.normals = d_normals;
+    a.width = width; a.height = height;
+    a.tiles_x = (width + kTile - 1) / kTile; a.tiles_y = (height + kTile - 1) / kTile;
+    LmvArgs v{};
+    v.m2 = d_m2; v.points = d_points; v.normals = d_normals;
+    v.width = width; v.height = height; v.tiles_x = a.tiles_x; v.tiles_y = a.tiles_y;
+    v.npow = normal_power_log2; v.samples = samples;
+    v.sigma_plane = sigma_plane; v.reach = reach; v.sigma_color = sigma_color; v.color_floor = color_floor;
+    v.den = v.den_out = (float*)((char*)c->d_lmv + 2 * pln);
+    const uint32_t passes = levels + dilate;
+    auto mask_target = [&](uint32_t k) { return (k == dilate && d_valid) ? d_valid : mping[k & 1u]; };
+    auto var_target = [&](uint32_t k) { return (k == levels && d_var) ? d_var : vping[k & 1u]; };      // the variance after k levels
+    HIP_TRY(hipEventRecord(c->ev_start, stream));
+    a.src = d_image; a.dst = d_out; a.copy = passes == 0 ? 1u : 0u; a.mask_out = mask_target(0);
+    HIP_TRY(launch_lmf_mask(a, stream));
+    a.copy = 0;
+    v.src = d_image; v.var_out = var_target(0);
+    HIP_TRY(launch_lmv_init(v, stream));
+    for (uint32_t p = 0; p < passes; p++) {
+        a.dst = p + 1 == passes ? d_out : ping[p & 1u];
+        if (p < levels) {
+            v.src = a.src; v.dst = a.dst; v.step = 1u << p;
+            v.var_in = var_target(p); v.var_out = var_target(p + 1);
+            HIP_TRY(launch_lmv_blur(v, stream));
+            HIP_TRY(launch_lmv_atrous(v, stream));
+        } else {
+            a.mask_in = mask_target(p - levels); a.mask_out = mask_target(p - levels + 1);
+            HIP_TRY(launch_lmf_dilate(a, stream));
+        }
+        a.src = a.dst;
+    }
+    HIP_TRY(hipEventRecord(c->ev_stop, stream));
+    c->ev_recorded = true; c->ms_summed = false;
+    return MI_OK;
+}
+
+extern "C" int mi_lightmap_finish_var_device(mi_ctx* c, uint32_t width, uint32_t height, const float* image, const float* m2, uint32_t samples,
+                                             const float* points, const float* normals, uint32_t levels, uint32_t normal_power_log2,
+                                             float sigma_plane, float reach, float sigma_color, float color_floor, uint32_t dilate,
+                                             float* out_image, float* out_var, uint8_t* out_valid, void* stream) {
+    MI_TRY(check_lmv_args("mi_lightmap_finish_var_device", width, height, image, m2, samples, points, normals, levels, normal_power_log2,
+                          sigma_plane, reach, sigma_color, color_floor, dilate, out_image));
+    const uintptr_t bytes = (uintptr_t)width * height * 3 * sizeof(float);
+    const struct { uintptr_t at, bytes; const char* name; } outs[2] = { { (uintptr_t)out_image, bytes, "out_image" },
+                                                                        { (uintptr_t)out_var, bytes / 3, "out_var" } };
+    for (const auto& o : outs)
+        for (const float* in : { image, m2, points, normals })
+            if (o.at && o.at < (uintptr_t)in + bytes && (uintptr_t)in < o.at + o.bytes)
+                return fail(MI_ERR_INVALID, "mi_lightmap_finish_var_device: %s overlaps an input (the passes are never in place)", o.name);
+    if (!c) return fail(MI_ERR_INVALID, "ctx is NULL");
+    HIP_TRY(hipSetDevice(c->device));
+    return lightmap_finish_var_device(c, width, height, image, m2, samples, points, normals, levels, normal_power_log2, sigma_plane, reach,
+                                      sigma_color, color_floor, dilate, out_image, out_var, out_valid, (hipStream_t)stream);
+}
+
+extern "C" int mi_lightmap_finish_var(mi_ctx* c, uint32_t width, uint32_t height, const float* image, const float* m2, uint32_t samples,
+                                      const float* points, const float* normals, uint32_t levels, uint32_t normal_power_log2,
+                                      float sigma_plane, float reach, float sigma_color, float color_floor, uint32_t dilate,
+                                      float* out_image, float* out_var, uint8_t* out_valid) {
+    MI_TRY(check_lmv_args("mi_lightmap_finish_var", width, height, image, m2, samples, points, normals, levels, normal_power_log2,
+                          sigma_plane, reach, sigma_color, color_floor, dilate, out_image));
+    if (!c) return fail(MI_ERR_INVALID, "ctx is NULL");
+    HIP_TRY(hipSetDevice(c->device));
+    // image, m2, points, normals, the result, its variance, its mask
+    const size_t n = (size_t)width * height, img = n * 3 * sizeof(float), pln = n * sizeof(float);
+    MI_TRY(ensure(&c->d_lmv_io, &c->lmv_io_bytes, 5 * img + pln + n));
+    char* const io = (char*)c->d_lmv_io;
+    const float* const src[4] = { image, m2, points, normals };
+    for (int k = 0; k < 4; k++) HIP_TRY(hipMemcpyAsync(io + k * img, src[k], img, hipMemcpyHostToDevice, c->stream));
+    MI_TRY(lightmap_finish_var_device(c, width, height, (const float*)io, (const float*)(io + img), samples, (const float*)(io + 2 * img),
+                                      (const float*)(io + 3 * img), levels, normal_power_log2, sigma_plane, reach, sigma_color, color_floor,
+                                      dilate, (float*)(io + 4 * img), out_var ? (float*)(io + 5 * img) : nullptr,
+                                      out_valid ? (uint8_t*)(io + 5 * img + pln) : nullptr, c->stream));
+    HIP_TRY(hipMemcpyAsync(out_image, io + 4 * img, img, hipMemcpyDeviceToHost, c->stream));      // after the uploads: out_image may alias image
+    if (out_var) HIP_TRY(hipMemcpyAsync(out_var, io + 5 * img, pln, hipMemcpyDeviceToHost, c->stream));
+    if (out_valid) HIP_TRY(hipMemcpyAsync(out_valid, io + 5 * img + pln, n, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return MI_OK;
 }

@@ -366,6 +366,9 @@ struct WfArgs {
     // [npix][9][3] running SH L2 sums in the compact tile-major layout, which wf_reduce_sh advances behind wf_reduce in every batch.
     uint32_t pt_probes;
     float* sh;
+    // Second moments of a point-table bake (mi_render_points_moments): m2, or nullptr: [npix][3] running sums of squares of the samples in
+    // the compact tile-major layout, which wf_reduce_m2 advances behind wf_reduce in every batch (never together with sh).
+    float* m2;
 };
 
 constexpr int kShFloats = 27;        // one probe's SH L2 record: 9 coefficients x 3 colour channels
@@ -435,6 +438,28 @@ struct LmfArgs {
 // Largest step whose tile plus 2 s halo (9 planes of (kTile + 4 s)^2 f32) fits the CU's 160 KiB of LDS
 constexpr uint32_t kLmfMaxLdsStep = 8;
 inline size_t lmf_lds_bytes(uint32_t step) { const size_t e = (size_t)kTile + 4u * step; return 9u * e * e * sizeof(float); }
+
+// ---- variance-guided lightmap finishing (mi_lightmap_finish_var; pt_kernels.hip "lmv_*") ----
+// One pass of tracing.py lightmap_finish_var: lmv_init (the variance of the mean per texel from the bake's mean and second moments),
+// lmv_blur (the colour weight's denominator per texel from the 3 x 3 blur of the variance) or lmv_atrous (one filter level of the image
+// and its variance, step `step`, one kTile x kTile tile per block, the taps straight from HBM).  The mask and the dilation are
+// lmf_mask's and lmf_dilate's.  Every pass reads `src` / `var_in` and writes `dst` / `var_out`: ping-pong, never in place.
+struct LmvArgs {
+    const float* src;                // [H][W][3] the previous pass's image (lmv_init: the raw bake)
+    const float* m2;                 // [H][W][3] the bake's means of squares (lmv_init)
+    const float* points;             // [H][W][3] guides (lmv_atrous)
+    const float* normals;            // [H][W][3] guides: all-zero = empty texel
+    const float* var_in;             // [H][W] the previous pass's variance (lmv_blur, lmv_atrous)
+    const float* den;                // [H][W] lmv_blur's result (lmv_atrous)
+    float*       dst;                // [H][W][3] (lmv_atrous)
+    float*       var_out;            // [H][W] (lmv_init, lmv_atrous)
+    float*       den_out;            // [H][W] (lmv_blur)
+    uint32_t width, height, tiles_x, tiles_y;
+    uint32_t step;                   // lmv_atrous: s = 2^level
+    uint32_t npow;                   // normal_power_log2
+    uint32_t samples;                // lmv_init: S
+    float sigma_plane, reach, sigma_color, color_floor;
+};
 
 // ---- irradiance volumes (mi_probe_volume_sample; pt_kernels.hip "pv_*") ----
 // tracing.py probe_volume_sample: pv_prepare turns every probe's 27 SH coefficients into one 112-byte record (the coefficients times the

@@ -4251,4 +4251,161 @@ hipError_t launch_tonemap(const float* image, uint8_t* out, uint32_t n_pixels, f
     return hipGetLastError();
 }
 
+// ---------------------------------------------------------------- lightmap variance (mi_render_points_moments, mi_lightmap_finish_var)
+// Second moments of a point-table bake: the sums of squares of one batch of samples, behind wf_reduce.  One thread per texel (pixel): per
+// sample of the batch in order acc[c] = acc[c] + v.c * v.c (one multiply, one add, not fused: the pragma above), the sums living in A.m2
+// between batches and calls.  Every sum is one f32 chain in sample order from +0.0, divided once at the end by (float)S, wf_reduce's
+// division for the mean: the record is bit-identical however the samples are cut into batches, calls and ranks.  Only reads the sample
+// slots; empty texels' slots are +0.0 (wf_main's POINTS branch), so their moments are.  A table render carries no tile mask: no slot of
+// the image is left unwritten.
+__global__ __launch_bounds__(256) void wf_reduce_m2(WfArgs A, uint32_t first_batch, uint32_t last_batch) {
+    const uint32_t pix = blockIdx.x * blockDim.x + threadIdx.x;
+    if (pix >= A.npix) return;
+    float* rec = A.m2 + (size_t)pix * 3;
+    uint32_t px, py; bool in_image;
+    wf_pixel_of(A, pix, px, py, in_image);
+    if (!in_image) {                       // outside the image, or a padding slot: zeros, whatever the buffer held
+        rec[0] = 0.0f; rec[1] = 0.0f; rec[2] = 0.0f;
+        return;
+    }
+    float acc[3];
+    for (int k = 0; k < 3; k++) acc[k] = first_batch ? 0.0f : rec[k];
+    for (uint32_t s = 0; s < A.s_count; s++) {
+        const float4 v = A.samp[(size_t)s * A.npix + pix];
+        acc[0] = acc[0] + v.x * v.x; acc[1] = acc[1] + v.y * v.y; acc[2] = acc[2] + v.z * v.z;
+    }
+    const float n = (float)A.C.spp;
+    for (int k = 0; k < 3; k++) rec[k] = last_batch ? acc[k] / n : acc[k];
+}
+
+// tracing.py lightmap_finish_var on the device, pass by pass: lightmap_finish with a colour weight whose width follows each texel's own
+// noise (the variance of its mean, from the bake's second moments, filtered along with the image).  Pure f32, the helper's operations in
+// the helper's order (no fused multiply-add: the pragma above; IEEE division and square root), a fixed tap order per texel, nothing
+// summed across threads: image and variance are the helper's bit for bit.  No address depends on a table value.
+
+// The variance of the mean per texel: v_c = fmaxf(0, m2_c - mean_c mean_c) / (float)(S - 1), V = (v_r + v_g) + v_b; empty texels +0.0
+__global__ __launch_bounds__(kBlock) void lmv_init(const LmvArgs a) {
+    const size_t n = (size_t)a.width * a.height, i = (size_t)blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n) return;
+    float V = 0.0f;
+    if (lmf_covered(a.normals[3 * i], a.normals[3 * i + 1], a.normals[3 * i + 2])) {
+        const float d = (float)(a.samples - 1u);
+        float v[3];
+        for (int k = 0; k < 3; k++) {
+            const float mean = a.src[3 * i + k];
+            v[k] = fmaxf(0.0f, a.m2[3 * i + k] - mean * mean) / d;
+        }
+        V = (v[0] + v[1]) + v[2];
+    }
+    a.var_out[i] = V;
+}
+
+// The colour weight's denominator per covered texel: the variance blurred over the nine step-1 neighbours that lie in the image and are
+// covered (dy outer, dx inner, G3 = {1/4, 1/2, 1/4}), sd = sqrtf(bs / bw), den = sigma_color * sd + color_floor.  Empty texels +0.0
+// (never read).
+__global__ __launch_bounds__(kBlock) void lmv_blur(const LmvArgs a) {
+    const size_t n = (size_t)a.width * a.height, i = (size_t)blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n) return;
+    const int W = (int)a.width, H = (int)a.height;
+    const int y = (int)(i / a.width), x = (int)(i - (size_t)y * a.width);
+    float den = 0.0f;
+    if (lmf_covered(a.normals[3 * i], a.normals[3 * i + 1], a.normals[3 * i + 2])) {
+        const float G3[3] = { 0.25f, 0.5f, 0.25f };
+        float bs = 0.0f, bw = 0.0f;
+#pragma unroll
+        for (int dy = -1; dy <= 1; dy++) {
+#pragma unroll
+            for (int dx = -1; dx <= 1; dx++) {
+                const int qx = x + dx, qy = y + dy;
+                if (qx < 0 || qx >= W || qy < 0 || qy >= H) continue;
+                const size_t j = (size_t)qy * W + qx;
+                if (!lmf_covered(a.normals[3 * j], a.normals[3 * j + 1], a.normals[3 * j + 2])) continue;
+                const float g = G3[dy + 1] * G3[dx + 1];
+                bs = bs + g * a.var_in[j];
+                bw = bw + g;
+            }
+        }
+        den = a.sigma_color * sqrtf(bs / bw) + a.color_floor;
+    }
+    a.den_out[i] = den;
+}
+
+// One filter level of the image and its variance.  lmf_atrous' direct form (one block per kTile x kTile tile, a thread owns the texels
+// (x, y + 8 k), k < 4, the taps straight from HBM / L2), with the colour weight wc = fmaxf(0, 1 - dc / den_p) and, beside sw and sc,
+// sv = sv + (w * w) * V_q: the texel becomes sc / sw and its variance sv / (sw * sw).
+__global__ __launch_bounds__(kBlock) void lmv_atrous(const LmvArgs a) {
+    const int s = (int)a.step, W = (int)a.width, H = (int)a.height;
+    const int x0 = (int)(blockIdx.x % a.tiles_x) * kTile, y0 = (int)(blockIdx.x / a.tiles_x) * kTile;
+    auto fetch3 = [&](const float* t, int qx, int qy, float* out) {
+        const size_t at = 3 * ((size_t)qy * W + qx);
+        for (int k = 0; k < 3; k++) out[k] = t[at + k];
+    };
+    const float H5[5] = { 0.0625f, 0.25f, 0.375f, 0.25f, 0.0625f };
+    const float r = a.reach * (float)s, rr = r * r;
+    const int gx = x0 + (int)(threadIdx.x & 31u);
+    for (int k4 = 0; k4 < 4; k4++) {
+        const int gy = y0 + (int)(threadIdx.x >> 5) + 8 * k4;
+        if (gx >= W || gy >= H) continue;
+        const size_t ip = (size_t)gy * W + gx;
+        float cp[3], pp[3], np[3];
+        fetch3(a.normals, gx, gy, np);
+        float out[3] = { 0.0f, 0.0f, 0.0f }, vout = 0.0f;
+        if (lmf_covered(np[0], np[1], np[2])) {
+            fetch3(a.src, gx, gy, cp); fetch3(a.points, gx, gy, pp);
+            const float den = a.den[ip];
+            float sw = 0.0f, sv = 0.0f, sc[3] = { 0.0f, 0.0f, 0.0f };
+#pragma unroll
+            for (int dy = -2; dy <= 2; dy++) {
+#pragma unroll
+                for (int dx = -2; dx <= 2; dx++) {
+                    const int qx = gx + s * dx, qy = gy + s * dy;
+                    if (qx < 0 || qx >= W || qy < 0 || qy >= H) continue;
+                    float nq[3];
+                    fetch3(a.normals, qx, qy, nq);
+                    if (!lmf_covered(nq[0], nq[1], nq[2])) continue;
+                    float cq[3], pq[3];
+                    fetch3(a.src, qx, qy, cq); fetch3(a.points, qx, qy, pq);
+                    const float D[3] = { pq[0] - pp[0], pq[1] - pp[1], pq[2] - pp[2] };
+                    const float d2 = (D[0] * D[0] + D[1] * D[1]) + D[2] * D[2];
+                    if ((dx != 0 || dy != 0) && !(d2 <= rr * (float)(dx * dx + dy * dy))) continue;      // the reach test, as lmf_atrous'
+                    const float h = H5[dy + 2] * H5[dx + 2];
+                    float wn = fmaxf(0.0f, (np[0] * nq[0] + np[1] * nq[1]) + np[2] * nq[2]);
+                    for (uint32_t i = 0; i < a.npow; i++) wn = wn * wn;
+                    const float dpl = fabsf((np[0] * D[0] + np[1] * D[1]) + np[2] * D[2]);
+                    const float wp = fmaxf(0.0f, 1.0f - dpl / a.sigma_plane);
+                    const float dc = (fabsf(cq[0] - cp[0]) + fabsf(cq[1] - cp[1])) + fabsf(cq[2] - cp[2]);
+                    const float wc = fmaxf(0.0f, 1.0f - dc / den);
+                    const float w = ((h * wn) * wp) * wc;
+                    sw = sw + w;
+                    for (int k = 0; k < 3; k++) sc[k] = sc[k] + w * cq[k];
+                    sv = sv + (w * w) * a.var_in[(size_t)qy * W + qx];
+                }
+            }
+            for (int k = 0; k < 3; k++) out[k] = sc[k] / sw;
+            vout = sv / (sw * sw);
+        }
+        for (int k = 0; k < 3; k++) a.dst[3 * ip + k] = out[k];
+        a.var_out[ip] = vout;
+    }
+}
+
+hipError_t launch_wf_reduce_m2(const WfArgs& a, bool first_batch, bool last_batch, hipStream_t stream) {
+    hipLaunchKernelGGL(wf_reduce_m2, dim3((a.npix + 255) / 256), dim3(256), 0, stream, a, first_batch ? 1u : 0u, last_batch ? 1u : 0u);
+    return hipGetLastError();
+}
+hipError_t launch_lmv_init(const LmvArgs& a, hipStream_t stream) {
+    const size_t n = (size_t)a.width * a.height;
+    hipLaunchKernelGGL(lmv_init, dim3((uint32_t)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, stream, a);
+    return hipGetLastError();
+}
+hipError_t launch_lmv_blur(const LmvArgs& a, hipStream_t stream) {
+    const size_t n = (size_t)a.width * a.height;
+    hipLaunchKernelGGL(lmv_blur, dim3((uint32_t)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, stream, a);
+    return hipGetLastError();
+}
+hipError_t launch_lmv_atrous(const LmvArgs& a, hipStream_t stream) {
+    hipLaunchKernelGGL(lmv_atrous, dim3(a.tiles_x * a.tiles_y), dim3(kBlock), 0, stream, a);
+    return hipGetLastError();
+}
+
 }  // namespace pt

@@ -706,6 +706,122 @@ def lightmap_finish(image, points, normals, levels: int = 3, normal_power_log2: 
     return cur, valid
 
 
+_LMV_BLUR = tuple((dy, dx) for dy in (-1, 0, 1) for dx in (-1, 0, 1))                              # dy outer, dx inner, the centre included
+
+
+def lightmap_finish_var(image, m2, samples, points, normals, levels: int = 3, normal_power_log2: int = 5,
+                        sigma_plane: float = float("inf"), reach: float = float("inf"), sigma_color: float = 8.0,
+                        color_floor: float = 1e-6, dilate: int = 4):
+    """lightmap_finish with a variance-guided colour weight (numpy only).  This is the DEFINITION of mi_lightmap_finish_var, which equals
+    it bit for bit.  `image` and `m2` [H, W, 3] f32 are the mean and the mean of squares of a bake of `samples` = S samples per texel
+    (bake_lightmap_moments), `points` and `normals` the centre table, as for lightmap_finish.  Returns (out [H, W, 3] f32,
+    var [H, W] f32, valid [H, W] bool).  The coverage rule, the tap order, h, wn, wp, the reach test, the centre tap's exemption and the
+    dilation are lightmap_finish's; everything is f32, one rounding per operation, in the order written below.
+    Initial variance of the mean, covered texels: v_c = max(0, m2_c - mean_c mean_c) / (S - 1), V = (v_r + v_g) + v_b; empty texels +0.0.
+    The difference cancels in f32: V means nothing where the true noise is below about 1e-3 of the mean; `color_floor` is for that case.
+    Per level (step s = 2^i): first the blur, bs = sum g V_q and bw = sum g over the nine neighbours at step 1 (whatever s is) that lie
+    in the image and are covered, g = G3[dy] G3[dx], G3 = (1/4, 1/2, 1/4); sd = sqrt(bs / bw), den = sigma_color sd + color_floor.  Then
+    the a-trous level with the colour weight max(0, 1 - (|dr| + |dg| + |db|) / den), den taken at p only and not divided by s, and
+    beside sw and sc the sum sv = sv + (w w) V_q: the texel becomes sc / sw, its variance sv / (sw sw).  color_floor = inf turns the
+    colour weight off: the image is then lightmap_finish(sigma_color=inf)'s, bit for bit.
+    `var` is the final V for covered texels and +0.0 elsewhere, dilated texels included; levels == 0 gives the masked copy and the
+    initial V.  Non-finite values spoil the texels within Chebyshev radius 2 (2^levels - 1) + levels + dilate, and no others."""
+    f32 = np.float32
+    img, P, N = check_finish_tables(image, points, normals)
+    M2 = np.ascontiguousarray(m2, f32)
+    if M2.shape != img.shape:
+        raise ValueError(f"m2 must have the image's shape {img.shape}, got {M2.shape}")
+    S = int(samples)
+    if not 2 <= S <= 65535:
+        raise ValueError(f"samples must be in 2 .. 65535, got {samples}")
+    levels, npow, dilate = int(levels), int(normal_power_log2), int(dilate)
+    if not (0 <= levels <= 8 and 0 <= npow <= 7 and 0 <= dilate <= 256):
+        raise ValueError("levels must be in 0 .. 8, normal_power_log2 in 0 .. 7 and dilate in 0 .. 256")
+    sig_p, rch, sig_c0, floor = f32(sigma_plane), f32(reach), f32(sigma_color), f32(color_floor)
+    if not (sig_p > 0 and rch > 0):
+        raise ValueError("sigma_plane and reach must be > 0 (inf turns one off)")
+    if not (sig_c0 >= 0 and np.isfinite(sig_c0)):
+        raise ValueError("sigma_color must be finite and >= 0")
+    if not floor > 0:
+        raise ValueError("color_floor must be > 0 (inf turns the colour weight off)")
+    H, W = img.shape[:2]
+    zero, one = f32(0.0), f32(1.0)
+    H5 = (f32(0.0625), f32(0.25), f32(0.375), f32(0.25), f32(0.0625))
+    G3 = (f32(0.25), f32(0.5), f32(0.25))
+    covered = (N[..., 0] != 0) | (N[..., 1] != 0) | (N[..., 2] != 0)
+    cur = np.where(covered[..., None], img, zero)
+    with np.errstate(all="ignore"):
+        v3 = np.fmax(zero, M2 - cur * cur) / f32(S - 1)
+        V = np.where(covered, (v3[..., 0] + v3[..., 1]) + v3[..., 2], zero)
+        for level in range(levels):
+            s = 1 << level
+            fs = f32(s)
+            r = rch * fs
+            rr = r * r
+            # the blur of the variance: always at step 1
+            b = 1
+            vb, nb = np.pad(V, b), np.pad(N, ((b, b), (b, b), (0, 0)))
+            bs = np.zeros((H, W), f32)
+            bw = np.zeros((H, W), f32)
+            for dy, dx in _LMV_BLUR:
+                ys, xs = b + b * dy, b + b * dx
+                vq, nq = vb[ys:ys + H, xs:xs + W], nb[ys:ys + H, xs:xs + W]
+                btake = covered & ((nq[..., 0] != 0) | (nq[..., 1] != 0) | (nq[..., 2] != 0))
+                g = G3[dy + 1] * G3[dx + 1]
+                bs = np.where(btake, bs + g * vq, bs)
+                bw = np.where(btake, bw + g, bw)
+            sd = np.sqrt(bs / bw)
+            den = sig_c0 * sd + floor
+            pad = 2 * s
+            cpad, ppad, npad = (np.pad(t, ((pad, pad), (pad, pad), (0, 0))) for t in (cur, P, N))      # beyond the image: empty texels
+            vpad = np.pad(V, pad)
+            sw = np.zeros((H, W), f32)
+            sv = np.zeros((H, W), f32)
+            sc = np.zeros((H, W, 3), f32)
+            for dy, dx in _LMF_TAPS:
+                ys, xs = pad + s * dy, pad + s * dx
+                cq, pq, nq = (t[ys:ys + H, xs:xs + W] for t in (cpad, ppad, npad))
+                vq = vpad[ys:ys + H, xs:xs + W]
+                take = covered & ((nq[..., 0] != 0) | (nq[..., 1] != 0) | (nq[..., 2] != 0))
+                D = pq - P
+                d2 = (D[..., 0] * D[..., 0] + D[..., 1] * D[..., 1]) + D[..., 2] * D[..., 2]
+                if dx != 0 or dy != 0:                # the centre always passes (0 <= 0; inf * 0 must not reject it)
+                    take = take & (d2 <= rr * f32(dx * dx + dy * dy))
+                h = H5[dy + 2] * H5[dx + 2]
+                wn = np.fmax(zero, (N[..., 0] * nq[..., 0] + N[..., 1] * nq[..., 1]) + N[..., 2] * nq[..., 2])
+                for _ in range(npow):
+                    wn = wn * wn
+                dpl = np.abs((N[..., 0] * D[..., 0] + N[..., 1] * D[..., 1]) + N[..., 2] * D[..., 2])
+                wp = np.fmax(zero, one - dpl / sig_p)
+                dc = (np.abs(cq[..., 0] - cur[..., 0]) + np.abs(cq[..., 1] - cur[..., 1])) + np.abs(cq[..., 2] - cur[..., 2])
+                wc = np.fmax(zero, one - dc / den)
+                w = ((h * wn) * wp) * wc
+                sw = np.where(take, sw + w, sw)
+                sc = np.where(take[..., None], sc + w[..., None] * cq, sc)
+                sv = np.where(take, sv + (w * w) * vq, sv)
+            cur = np.where(covered[..., None], sc / sw[..., None], zero)
+            V = np.where(covered, sv / (sw * sw), zero)
+        # lightmap_finish's dilation, restated here: that helper's own text is what its mutant tests edit, so it is not shared
+        valid = covered.copy()
+        cur = np.ascontiguousarray(cur, f32)
+        for _ in range(dilate):
+            prev_valid, prev = valid.copy(), cur.copy()
+            vpad = np.pad(prev_valid, 1)
+            near = np.zeros((H, W), bool)
+            for dy, dx in _LMF_RING:
+                near |= vpad[1 + dy:1 + dy + H, 1 + dx:1 + dx + W]
+            for y, x in np.argwhere(near & ~prev_valid):         # the pass's frontier, texel by texel: the order of the sum is the contract
+                total, count = np.zeros(3, f32), 0
+                for dy, dx in _LMF_RING:
+                    qy, qx = y + dy, x + dx
+                    if 0 <= qy < H and 0 <= qx < W and prev_valid[qy, qx]:
+                        total = total + prev[qy, qx]
+                        count += 1
+                cur[y, x] = total / f32(count)
+                valid[y, x] = True
+    return cur, np.ascontiguousarray(V, f32), valid
+
+
 def equirect_dirs(lon, lat) -> np.ndarray:
     """Unit directions [..., 3] float32 of a latitude-longitude panorama for arrays of longitudes / latitudes in radians:
     (sin lon cos lat, sin lat, -cos lon cos lat) — longitude 0 looks down -z, +pi/2 down +x, +-pi (the seam) down +z; latitude +pi/2 is
@@ -927,6 +1043,102 @@ class Context:
         abi.check(self._lib.mi_lightmap_finish_device(self._h, width, height, d_image, d_points, d_normals, levels, normal_power_log2,
                                                       sigma_plane, reach, sigma_color, dilate, d_out_image, d_out_valid, stream))
 
+    # ---- lightmap variance: second moments of a bake, and the finish they guide ----
+    def render_points_moments(self, cam: Camera, points, normals, seed: int = 1, want_f32=True, want_u8=True, want_sig=False,
+                              flags: int = 0, max_state_bytes: int = 0):
+        """mi_render_points_moments: render_points with the per-texel mean of squares of the samples as a further output.  Returns
+        (m2 [H, W, 3] f32, f32, u8, sig, stats): m2 sums v * v in sample order in f32 and divides by aa_sample_count, as the mean does;
+        the rest is what render_points returns, bit for bit."""
+        p, n, rows = check_point_table(cam, points, normals)
+        pod = cam.to_pod()
+        opts = abi.mi_render_opts(seed=seed, rank=0, world=1, variant=abi.MI_VARIANT_DEFAULT, want_signature=int(want_sig),
+                                  flags=flags, max_state_bytes=max_state_bytes)
+        H, W = cam.screen_height, cam.screen_width
+        m2 = np.empty((H, W, 3), np.float32)
+        f32 = np.empty((H, W, 3), np.float32) if want_f32 else None
+        u8 = np.empty((H, W, 3), np.uint8) if want_u8 else None
+        sig = np.empty((H, W), np.uint32) if want_sig else None
+        st = abi.mi_stats()
+        abi.check(self._lib.mi_render_points_moments(
+            self._h, C.byref(pod), C.byref(opts), p.ctypes.data, n.ctypes.data, rows, m2.ctypes.data,
+            f32.ctypes.data if f32 is not None else None,
+            u8.ctypes.data if u8 is not None else None,
+            sig.ctypes.data if sig is not None else None, C.byref(st)))
+        return m2, f32, u8, sig, st
+
+    def render_points_moments_device(self, cam: Camera, d_points: int, d_normals: int, rows_per_pixel: int,
+                                     d_compact_m2: Optional[int] = None, d_compact: Optional[int] = None, d_sig: Optional[int] = None,
+                                     sample_begin: int = 0, sample_end: Optional[int] = None, d_accum: Optional[int] = None, seed: int = 1,
+                                     rank: int = 0, world: int = 1, stream: Optional[int] = None, flags: int = 0, max_state_bytes: int = 0):
+        """mi_render_points_moments_device: render_points_device with d_compact_m2, [compact_size(...)[1] * 1024, 3] float32 in the
+        compact layout (unpermute_device un-permutes it), the moments output and their running accumulator across progressive calls
+        (started by the call with sample_begin == 0, divided by the one that reaches aa_sample_count); None is exactly
+        render_points_device."""
+        pod = cam.to_pod()
+        opts = abi.mi_render_opts(seed=seed, rank=rank, world=world, variant=abi.MI_VARIANT_DEFAULT,
+                                  want_signature=int(d_sig is not None), flags=flags, max_state_bytes=max_state_bytes)
+        st = abi.mi_stats()
+        end = cam.aa_sample_count if sample_end is None else sample_end
+        abi.check(self._lib.mi_render_points_moments_device(self._h, C.byref(pod), C.byref(opts), d_points, d_normals, rows_per_pixel,
+                                                            sample_begin, end, d_accum, d_compact_m2, d_compact, d_sig, stream, C.byref(st)))
+        return st
+
+    def bake_lightmap_moments(self, cam: Camera, mesh, jitter: bool = True, offset: float = 1e-3, seed: int = 1, transform=None,
+                              want_f32=True, want_u8=True, want_sig=False, want_triangle=False, flags: int = 0, max_state_bytes: int = 0):
+        """mi_bake_lightmap_moments: bake_lightmap with the second moments.  Returns (m2 [H, W, 3] f32, f32, u8, sig, triangle, stats);
+        everything behind m2 is what bake_lightmap returns, bit for bit."""
+        pod, keep = mesh_pod(mesh, transform)
+        cpod = cam.to_pod()
+        opts = abi.mi_render_opts(seed=seed, rank=0, world=1, variant=abi.MI_VARIANT_DEFAULT, want_signature=int(want_sig),
+                                  flags=flags, max_state_bytes=max_state_bytes)
+        H, W = cam.screen_height, cam.screen_width
+        m2 = np.empty((H, W, 3), np.float32)
+        f32 = np.empty((H, W, 3), np.float32) if want_f32 else None
+        u8 = np.empty((H, W, 3), np.uint8) if want_u8 else None
+        sig = np.empty((H, W), np.uint32) if want_sig else None
+        tri = np.empty((cam.aa_sample_count if jitter else 1, H, W), np.int32) if want_triangle else None
+        st = abi.mi_stats()
+        abi.check(self._lib.mi_bake_lightmap_moments(
+            self._h, C.byref(cpod), C.byref(opts), C.byref(pod), abi.MI_LM_JITTER if jitter else 0, offset, m2.ctypes.data,
+            f32.ctypes.data if f32 is not None else None,
+            u8.ctypes.data if u8 is not None else None,
+            sig.ctypes.data if sig is not None else None,
+            tri.ctypes.data if tri is not None else None, C.byref(st)))
+        del keep
+        return m2, f32, u8, sig, tri, st
+
+    def lightmap_finish_var(self, image, m2, samples: int, points, normals, levels: int = 3, normal_power_log2: int = 5,
+                            sigma_plane: float = float("inf"), reach: float = float("inf"), sigma_color: float = 8.0,
+                            color_floor: float = 1e-6, dilate: int = 4):
+        """mi_lightmap_finish_var: the helper lightmap_finish_var on the GPU, bit for bit.  `image` and `m2` are a bake's mean and
+        second moments [H, W, 3] f32 (bake_lightmap_moments), `samples` its sample count, `points` and `normals` the atlas's centre table
+        ([H, W, 3], or lightmap_texels' [1, H, W, 3]).  Returns (out [H, W, 3] f32, var [H, W] f32, valid [H, W] bool).  No scene is
+        needed."""
+        P, N = np.asarray(points), np.asarray(normals)
+        img, P, N = check_finish_tables(image, P[0] if P.ndim == 4 and P.shape[0] == 1 else P, N[0] if N.ndim == 4 and N.shape[0] == 1 else N)
+        M2 = np.ascontiguousarray(m2, np.float32)
+        if M2.shape != img.shape:
+            raise ValueError(f"m2 must have the image's shape {img.shape}, got {M2.shape}")
+        H, W = img.shape[:2]
+        out = np.empty((H, W, 3), np.float32)
+        var = np.empty((H, W), np.float32)
+        valid = np.empty((H, W), np.uint8)
+        abi.check(self._lib.mi_lightmap_finish_var(self._h, W, H, img.ctypes.data, M2.ctypes.data, samples, P.ctypes.data, N.ctypes.data,
+                                                   levels, normal_power_log2, sigma_plane, reach, sigma_color, color_floor, dilate,
+                                                   out.ctypes.data, var.ctypes.data, valid.ctypes.data))
+        return out, var, valid.astype(bool)
+
+    def lightmap_finish_var_device(self, width: int, height: int, d_image: int, d_m2: int, samples: int, d_points: int, d_normals: int,
+                                   d_out_image: int, d_out_var: Optional[int] = None, d_out_valid: Optional[int] = None, levels: int = 3,
+                                   normal_power_log2: int = 5, sigma_plane: float = float("inf"), reach: float = float("inf"),
+                                   sigma_color: float = 8.0, color_floor: float = 1e-6, dilate: int = 4, stream: Optional[int] = None):
+        """mi_lightmap_finish_var_device: the same for tables held on the device (raw pointers, e.g. tensor.data_ptr(): four [H, W, 3]
+        f32 inputs, the [H, W, 3] f32 output and the optional [H, W] f32 variance, which must overlap none of them, and an optional
+        [H, W] u8 mask).  Queued on `stream`."""
+        abi.check(self._lib.mi_lightmap_finish_var_device(self._h, width, height, d_image, d_m2, samples, d_points, d_normals, levels,
+                                                          normal_power_log2, sigma_plane, reach, sigma_color, color_floor, dilate,
+                                                          d_out_image, d_out_var, d_out_valid, stream))
+
     def probe_volume_sample(self, volume: "ProbeVolume", points, normals, flags: int = 0):
         """mi_probe_volume_sample: the helper probe_volume_sample on the GPU, bit for bit.  `volume` is a ProbeVolume, points and
         normals [..., 3] f32 of one shape (check_volume_points).  Returns (E [..., 3] f32, weight [...] f32).  No scene is needed."""
@@ -1075,6 +1287,12 @@ class Context:
         out = (C.c_float * 8)()
         abi.check(self._lib.mi_last_pipeline_ms(self._h, out))
         return float(out[7])
+
+    def last_reduce_m2_ms(self) -> float:
+        """Sum of the wf_reduce_m2 launch durations (ms) of the last render: entry 7 of mi_last_pipeline_ms after
+        render_points_moments / render_points_moments_device / bake_lightmap_moments (the entry wf_reduce_sh has after render_probes: the
+        two never run in one render); 0.0 after any other render."""
+        return self.last_reduce_sh_ms()
 
     def last_pipeline_counts(self):
         """Path counts of the last wavefront render (mi_last_pipeline_counts), for traffic accounting."""
@@ -1378,7 +1596,11 @@ class Scene:                         # tracing.rs:213-218
         `finish` (None: the raw bake, as above) is a dict of lightmap_finish's parameters (levels, normal_power_log2, sigma_plane, reach,
         sigma_color, dilate; {} for the defaults): the bake's f32 image is then filtered and dilated on the GPU (mi_lightmap_finish),
         guided by the atlas's centre table (Context.lightmap_texels with rows=1, the same offset), and the call returns the finished
-        lightmap (out [height, width, 3] f32, valid [height, width] bool) instead of bytes."""
+        lightmap (out [height, width, 3] f32, valid [height, width] bool) instead of bytes.
+        A true "variance" key in `finish` selects the variance-guided finish: the bake also returns its second moments
+        (mi_bake_lightmap_moments), the remaining keys are lightmap_finish_var's parameters (levels, normal_power_log2, sigma_plane,
+        reach, sigma_color, color_floor, dilate), and the call returns (out, var [height, width] f32, valid) (mi_lightmap_finish_var).
+        Without the key, or with a false one, nothing changes."""
         from dataclasses import replace
         cam = replace(self.camera, screen_width=int(width), screen_height=int(height), aa_sample_count=int(samples))
         check_point_table(cam, np.zeros((height, width, 3), np.float32), np.zeros((height, width, 3), np.float32))
@@ -1388,6 +1610,13 @@ class Scene:                         # tracing.rs:213-218
             if finish is None:
                 _, u8, _, _, _ = ctx.bake_lightmap(cam, mesh, jitter=jitter, offset=offset, seed=seed, want_f32=False, want_u8=True)
                 return u8
+            if "variance" in finish:
+                finish = dict(finish)
+                if finish.pop("variance"):
+                    m2, f32, _, _, _, _ = ctx.bake_lightmap_moments(cam, mesh, jitter=jitter, offset=offset, seed=seed, want_f32=True,
+                                                                    want_u8=False)
+                    points, normals, _ = ctx.lightmap_texels(mesh, int(width), int(height), rows=1, offset=offset, want_triangle=False)
+                    return ctx.lightmap_finish_var(f32, m2, int(samples), points, normals, **finish)
             f32, _, _, _, _ = ctx.bake_lightmap(cam, mesh, jitter=jitter, offset=offset, seed=seed, want_f32=True, want_u8=False)
             points, normals, _ = ctx.lightmap_texels(mesh, int(width), int(height), rows=1, offset=offset, want_triangle=False)
             return ctx.lightmap_finish(f32, points, normals, **finish)

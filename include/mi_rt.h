@@ -549,6 +549,87 @@ int  mi_lightmap_finish_device(mi_ctx* ctx, uint32_t width, uint32_t height, con
                                uint32_t levels, uint32_t normal_power_log2, float sigma_plane, float reach, float sigma_color,
                                uint32_t dilate, float* out_image, uint8_t* out_valid, void* stream);
 
+/* ---- lightmap variance: second moments of a point-table bake (added within ABI version 5: detect by symbol lookup) ----
+ * mi_render_points / mi_bake_lightmap with a second output: per texel and colour channel the MEAN OF THE SQUARES of its aa_sample_count
+ *   samples, beside their mean.  Together the two give each texel's own noise (mi_lightmap_finish_var below turns them into the variance
+ *   of the mean), which a filter, or a caller who decides where more samples are worth their time, needs and the mean alone cannot give.
+ * Definition: out_m2 is [H][W][3] f32, m2_c = (sum_s L_s.c * L_s.c) / (float)S, S = aa_sample_count, L_s the sample the mean is made of.
+ *   Each of the three sums is accumulated in f32 in sample order from +0.0 (one multiply and one add per sample, not fused) and divided
+ *   once at the end by (float)S, the division the mean uses: out_m2 is bit-identical across max_state_bytes, ranks, MI_OPT_* flags and
+ *   progressive splits.  With S == 1, m2_c == mean_c * mean_c exactly.  Empty texels (an all-zero normal) are +0.0.
+ * Plain outputs: the mean (f32), u8 and signature outputs are mi_render_points' / mi_bake_lightmap's BIT FOR BIT: the sums of squares
+ *   are a further reduction (wf_reduce_m2) of the same sample slots behind wf_reduce in every batch; no other kernel runs differently.
+ * Everything else is mi_render_points' / mi_bake_lightmap's, word for word: the tables, the two streams, the camera fields read and
+ *   ignored, the refusals (NULL tables, rows_per_pixel, path_samples != 1, MI_SHADE_PHONG, a variant other than DEFAULT / WAVEFRONT, no
+ *   scene, rank / world, the mesh's), masks OFF, mi_reserve, max_state_bytes, stats->samples = W*H*aa_sample_count.  Entry 7 of
+ *   mi_last_pipeline_ms is the time of wf_reduce_m2 after these calls.
+ * mi_render_points_moments: HOST pointers, blocking, rank / world 0 / 1; out_m2 is required (MI_ERR_INVALID if NULL, checked first), the
+ *   other outputs may be NULL.  The compact records and the un-permuted plane live in a buffer the context owns (grown on demand, freed
+ *   with the context, never the buffers mi_reserve sized; MI_ERR_OOM if it cannot be allocated).
+ * mi_render_points_moments_device: DEVICE pointers; the sample range, the accumulator and the rank / world rules are
+ *   mi_render_rays_device's.  d_compact_m2 is [tiles_padded][1024][3] f32 in the compact tile-major layout (mi_unpermute_device turns it
+ *   into [H][W][3]), output AND running accumulator: the call with sample_begin == 0 starts the sums from zero (the buffer need not be
+ *   cleared), later calls add to it, the call that ends at aa_sample_count divides; it may be copied out and back between calls.  Slots
+ *   outside the image and padding slots are written as zeros by every call.  d_compact_m2 == NULL is legal and is then exactly
+ *   mi_render_points_device.  mi_multi_* takes no table.
+ * mi_bake_lightmap_moments: mi_bake_lightmap with out_m2 (required): the same moments, bit for bit, as mi_render_points_moments on the
+ *   table mi_lightmap_texels returns. */
+int  mi_render_points_moments(mi_ctx* ctx, const mi_camera_desc* cam, const mi_render_opts* opts,
+                              const float* points, const float* normals, uint32_t rows_per_pixel, float* out_m2,
+                              float* out_rgb_f32, uint8_t* out_rgb_u8, uint32_t* out_sig, mi_stats* stats);
+int  mi_render_points_moments_device(mi_ctx* ctx, const mi_camera_desc* cam, const mi_render_opts* opts,
+                                     const float* d_points, const float* d_normals, uint32_t rows_per_pixel,
+                                     uint32_t sample_begin, uint32_t sample_end, void* d_accum_f32x4, void* d_compact_m2,
+                                     void* d_compact_f32, void* d_sig_u32, void* stream, mi_stats* stats);
+int  mi_bake_lightmap_moments(mi_ctx* ctx, const mi_camera_desc* cam, const mi_render_opts* opts, const mi_mesh* mesh, uint32_t flags,
+                              float offset, float* out_m2, float* out_rgb_f32, uint8_t* out_rgb_u8, uint32_t* out_sig,
+                              int32_t* out_triangle, mi_stats* stats);
+
+/* ---- lightmap variance: variance-guided finishing (added within ABI version 5: detect by symbol lookup) ----
+ * mi_lightmap_finish with a colour weight that follows each texel's own noise instead of one sigma_color for the whole atlas: a 16-sample
+ *   bake has texels in direct light that are nearly converged beside texels in deep indirect light whose standard error is tens of times
+ *   larger, and one sigma either leaves the second kind noisy or blurs real detail in the first.  Here the weight's width is sigma_color
+ *   standard errors of the texel itself, the variance filtered along with the image (as SVGF does).
+ *   These are the semantics of lightmap_finish_var (Python), which is the definition; the result equals the helper's BIT FOR BIT: pure
+ *   f32, every operation one of + - * /, sqrtf, fabsf, fmaxf, comparisons and exact int-to-float conversions, in the order written here,
+ *   no fused multiply-add, IEEE division and square root.  No scene is needed.
+ * Layout: mi_lightmap_finish's, and `m2` [H][W][3] f32 is the bake's out_m2, `samples` its aa_sample_count S (2 .. 65535), out_var
+ *   [H][W] f32 (may be NULL).  The coverage rule, the tap order, h, wn, wp, the reach test, the centre tap's exemption and the dilation
+ *   are mi_lightmap_finish's, letter for letter.  New:
+ * Initial variance of the mean, covered texels: v_c = fmaxf(0, m2_c - mean_c * mean_c) / (float)(S - 1), V = (v_r + v_g) + v_b; empty
+ *   texels V = +0.0.  The difference cancels in f32: V is meaningless where the true noise is below about 1e-3 of the mean (it may come
+ *   out as 0 or as rounding noise of the order mean^2 * 6e-8 / S); color_floor exists for that case.
+ * Per level (s = 2^i, ping-pong, never in place), for a covered texel p:
+ *   blur: bs = sum g V_q, bw = sum g over the nine neighbours q = p + (dx, dy) at step 1 WHATEVER s is, dy outer -1 .. 1, dx inner
+ *     -1 .. 1, both sums from +0.0; a neighbour counts when it lies in the image and is covered; g = G3[dy+1] * G3[dx+1],
+ *     G3 = { 1/4, 1/2, 1/4 }.  sd = sqrtf(bs / bw), den = sigma_color * sd + color_floor.
+ *   a-trous: wc = fmaxf(0, 1 - dc / den), dc as mi_lightmap_finish's from the current level's colours, den taken at p only and NOT
+ *     divided by s; w = ((h wn) wp) wc; sw = sw + w; sc[k] = sc[k] + w c_q[k]; sv = sv + (w * w) * V_q.  The texel becomes sc / sw and
+ *     its variance sv / (sw * sw).
+ *   color_floor = +inf turns the colour weight off (1 - dc / inf == 1): the image is then mi_lightmap_finish's with sigma_color = +inf,
+ *   bit for bit.
+ * out_var: the final V for covered texels, +0.0 elsewhere, texels filled by the dilation included.  levels == 0 gives the masked copy
+ *   and the initial V.
+ * Non-finite values never fault; they give unspecified values only for texels within Chebyshev radius 2 (2^levels - 1) + levels + dilate
+ *   (the blur widens each level's reach by one); every other texel keeps the bits of the clean run.  No address depends on a table value.
+ * MI_ERR_INVALID (each with a message, checked before the context, nothing is launched): NULL image, m2, points, normals or out_image;
+ *   width or height of 0 or above 32768; levels > 8, normal_power_log2 > 7, dilate > 256; samples < 2 or > 65535; a sigma_plane or reach
+ *   that is NaN or <= 0; a sigma_color that is NaN, infinite or < 0; a color_floor that is NaN or <= 0 (+inf is legal).
+ * Scratch: mi_lightmap_finish's, and three [H][W] f32 planes (two variances, the denominators) in a buffer the context owns (grown on
+ *   demand, freed with the context, never the buffers mi_reserve sized; MI_ERR_OOM).  lmv_init once, lmv_blur and lmv_atrous per level
+ *   (one 32 x 32 tile per block, the taps straight from HBM / L2), lmf_dilate per pass; mi_last_kernel_ms reports their sum.
+ * mi_lightmap_finish_var: HOST pointers, blocking; the tables pass through a buffer the context owns; out_image may alias image.
+ * mi_lightmap_finish_var_device: DEVICE pointers on ctx's device.  Queues on `stream` and does not synchronise, except when it has to
+ *   grow its scratch.  An out_image or out_var that overlaps image, m2, points or normals is MI_ERR_INVALID. */
+int  mi_lightmap_finish_var(mi_ctx* ctx, uint32_t width, uint32_t height, const float* image, const float* m2, uint32_t samples,
+                            const float* points, const float* normals, uint32_t levels, uint32_t normal_power_log2, float sigma_plane,
+                            float reach, float sigma_color, float color_floor, uint32_t dilate, float* out_image, float* out_var,
+                            uint8_t* out_valid);
+int  mi_lightmap_finish_var_device(mi_ctx* ctx, uint32_t width, uint32_t height, const float* image, const float* m2, uint32_t samples,
+                                   const float* points, const float* normals, uint32_t levels, uint32_t normal_power_log2,
+                                   float sigma_plane, float reach, float sigma_color, float color_floor, uint32_t dilate, float* out_image,
+                                   float* out_var, uint8_t* out_valid, void* stream);
+
 /* ---- light probes: SH L2 radiance probes with the directions drawn on the GPU (added within ABI version 5: detect by symbol lookup) ----
  * mi_render_points without normals and with a second output.  One "pixel" is one probe, a point in free space; its samples leave it in
  *   directions uniform over the whole sphere, and beside their mean the call returns the radiance field's projection onto the nine real
@@ -649,8 +730,9 @@ int  mi_reserve(mi_ctx* ctx, const mi_camera_desc* cam, int32_t world, uint64_t 
 
 /* Wavefront pipeline (MI_VARIANT_WAVEFRONT) of the most recent render: out8 = { sum of wf_main
  * launch durations, of wf_trav, of wf_reduce (ms, HIP events around every launch), launches, sum of wf_trav_f, of
- * wf_replay (the two-stage mesh traversal), sum of the spans of wf_main's class-A parts, sum of wf_reduce_sh (mi_render_probes only;
- * 0 for every other render) }.  A pass after the first launches
+ * wf_replay (the two-stage mesh traversal), sum of the spans of wf_main's class-A parts, sum of wf_reduce_sh (mi_render_probes) or of
+ * wf_reduce_m2 (mi_render_points_moments, mi_bake_lightmap_moments): the two never run in one render, and the entry is 0 for every other
+ * render }.  A pass after the first launches
  * wf_main in two parts: the class-A blocks run on a second stream BESIDE the walkers of the previous pass (their span includes
  * waiting for CUs the walkers still hold, so it overlaps the wf_trav figure and must not be added to it), the class-B blocks
  * behind the walkers (counted under wf_main). */

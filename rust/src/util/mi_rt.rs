@@ -131,6 +131,26 @@ extern "C" {
     pub fn mi_lightmap_finish_device(ctx: *mut mi_ctx, width: u32, height: u32, image: *const f32, points: *const f32, normals: *const f32,
                                      levels: u32, normal_power_log2: u32, sigma_plane: f32, reach: f32, sigma_color: f32,
                                      dilate: u32, out_image: *mut f32, out_valid: *mut u8, stream: *mut c_void) -> c_int;
+    // lightmap variance (added within ABI 5): the bake's second moments, out_m2 [H][W][3] / d_compact_m2 [tiles_padded][1024][3], and the
+    // finish they guide (m2 and samples behind the image, color_floor behind sigma_color, out_var [H][W] or null behind out_image)
+    pub fn mi_render_points_moments(ctx: *mut mi_ctx, cam: *const mi_camera_desc, opts: *const mi_render_opts,
+                                    points: *const f32, normals: *const f32, rows_per_pixel: u32, out_m2: *mut f32,
+                                    out_rgb_f32: *mut f32, out_rgb_u8: *mut u8, out_sig: *mut u32, stats: *mut mi_stats) -> c_int;
+    pub fn mi_render_points_moments_device(ctx: *mut mi_ctx, cam: *const mi_camera_desc, opts: *const mi_render_opts,
+                                           d_points: *const f32, d_normals: *const f32, rows_per_pixel: u32,
+                                           sample_begin: u32, sample_end: u32, d_accum_f32x4: *mut c_void, d_compact_m2: *mut c_void,
+                                           d_compact_f32: *mut c_void, d_sig_u32: *mut c_void, stream: *mut c_void, stats: *mut mi_stats) -> c_int;
+    pub fn mi_bake_lightmap_moments(ctx: *mut mi_ctx, cam: *const mi_camera_desc, opts: *const mi_render_opts, mesh: *const mi_mesh, flags: u32,
+                                    offset: f32, out_m2: *mut f32, out_rgb_f32: *mut f32, out_rgb_u8: *mut u8, out_sig: *mut u32,
+                                    out_triangle: *mut i32, stats: *mut mi_stats) -> c_int;
+    pub fn mi_lightmap_finish_var(ctx: *mut mi_ctx, width: u32, height: u32, image: *const f32, m2: *const f32, samples: u32,
+                                  points: *const f32, normals: *const f32, levels: u32, normal_power_log2: u32, sigma_plane: f32,
+                                  reach: f32, sigma_color: f32, color_floor: f32, dilate: u32, out_image: *mut f32, out_var: *mut f32,
+                                  out_valid: *mut u8) -> c_int;
+    pub fn mi_lightmap_finish_var_device(ctx: *mut mi_ctx, width: u32, height: u32, image: *const f32, m2: *const f32, samples: u32,
+                                         points: *const f32, normals: *const f32, levels: u32, normal_power_log2: u32,
+                                         sigma_plane: f32, reach: f32, sigma_color: f32, color_floor: f32, dilate: u32, out_image: *mut f32,
+                                         out_var: *mut f32, out_valid: *mut u8, stream: *mut c_void) -> c_int;
     // light probes (added within ABI 5): points is [rows_per_pixel][H][W][3]; out_sh [H][W][9][3], d_compact_sh [tiles_padded][1024][27]
     pub fn mi_render_probes(ctx: *mut mi_ctx, cam: *const mi_camera_desc, opts: *const mi_render_opts,
                             points: *const f32, rows_per_pixel: u32, out_sh: *mut f32,

@@ -80,7 +80,16 @@ probe invalid, MI_PV_NORMAL_WEIGHT set; --volume-points (default 2^20 and 2^22) 
 drone's 4096 x 4096 atlas table in raster order ("coherent": neighbouring lanes share corners) and the same points shuffled
 ("incoherent").  A call's two kernels are timed by HIP events (mi_last_kernel_ms), 5 warm-up calls then --calls timed ones: median and
 min - max.  pv_prepare alone is a call with one point.  The floor is a device-to-device copy of the same input and output bytes (40 B per
-point: 24 in, 16 out), timed by events in the same run.  The first 4096 points of every row are compared with the helper bit for bit."""
+point: 24 in, 16 out), timed by events in the same run.  The first 4096 points of every row are compared with the helper bit for bit.
+
+--mode variance times the lightmap variance calls on device-resident tables, HIP events, 5 warm-up and --calls timed calls, median and
+min - max.  Moments: on the drone's atlas at 1024 x 1024 (mi_lightmap_texels_device's centre table), aa_sample_count = 16, path_depth 10,
+mi_render_points_moments_device alternates call by call with mi_render_points_device; the rows give mi_last_kernel_ms of each, the ratio
+of the medians, and wf_reduce_m2 (entry 7 of mi_last_pipeline_ms) beside wf_reduce (entry 2) of the same runs, which read the same
+sample slots.  The tool checks that the two compact images agree bit for bit.  Finish: at --finish-sizes, levels = 5 and dilate = 8,
+mi_lightmap_finish_var_device (sigma_color 8, color_floor 1e-6) alternates with mi_lightmap_finish_device (sigma_color 8) on seeded noise
+over the covered texels, the moments those of 16 samples with a relative standard deviation of 0.3; the rows give each call's time and
+the ratio (three kernels per level instead of one)."""
 import argparse
 import json
 import os
@@ -745,6 +754,110 @@ def volume_rows(ctx, grids, point_counts, calls, warmup):
     return rows
 
 
+def variance_rows(ctx, sizes, calls, warmup):
+    """--mode variance (the module's docstring)"""
+    from cs397raytracingsp22_amd import dist as pdist
+    dev = torch.device("cuda:0")
+    offset = float(np.float32(1e-3))
+    rows = []
+
+    def atlas(size, aa):
+        sc = scenes.config4(size, size, aa, 10)
+        drone = sc.objects[-1]
+        mesh = drone.mesh
+        t_mesh = [torch.from_numpy(np.array(a)).to(dev) for a in (mesh.positions, mesh.normals, mesh.texcoords, mesh.indices.view(np.int32))]
+        pts = torch.empty((size, size, 3), dtype=torch.float32, device=dev)
+        nrm = torch.empty((size, size, 3), dtype=torch.float32, device=dev)
+        ctx.lightmap_texels_device(t_mesh[0].data_ptr(), t_mesh[1].data_ptr(), t_mesh[2].data_ptr(), t_mesh[3].data_ptr(), mesh.n_vertices,
+                                   mesh.n_triangles, size, size, pts.data_ptr(), nrm.data_ptr(), None, rows=1, jitter=False, seed=1,
+                                   offset=offset, transform=drone.transform)
+        torch.cuda.synchronize()
+        return sc, pts, nrm
+
+    def stats(ms):
+        return {"ms_median": round(float(np.median(ms)), 4), "ms_min": round(float(np.min(ms)), 4), "ms_max": round(float(np.max(ms)), 4)}
+
+    # 1. the moments
+    size = 1024
+    sc, pts, nrm = atlas(size, BAKE_AA)
+    cam = sc.camera
+    ctx.upload(sc.flatten())
+    slots = pdist.tiles_padded(size, size, 1) * pdist.TILE_PIXELS
+    c_plain = torch.empty((slots, 3), dtype=torch.float32, device=dev)
+    c_mom = torch.empty((slots, 3), dtype=torch.float32, device=dev)
+    c_m2 = torch.empty((slots, 3), dtype=torch.float32, device=dev)
+    torch.cuda.synchronize()
+    ms = {"plain": [], "moments": []}
+    reduce_ms = {"plain": [], "moments": []}
+    m2_ms = []
+    for k in range(warmup + calls):
+        ctx.render_points_moments_device(cam, pts.data_ptr(), nrm.data_ptr(), 1, c_m2.data_ptr(), c_mom.data_ptr(), seed=1)
+        torch.cuda.synchronize()
+        if k >= warmup:
+            ms["moments"].append(ctx.last_kernel_ms())
+            reduce_ms["moments"].append(ctx.last_pipeline_ms()["wf_reduce_ms"])
+            m2_ms.append(ctx.last_reduce_m2_ms())
+        ctx.render_points_device(cam, pts.data_ptr(), nrm.data_ptr(), 1, c_plain.data_ptr(), seed=1)
+        torch.cuda.synchronize()
+        if k >= warmup:
+            ms["plain"].append(ctx.last_kernel_ms())
+            reduce_ms["plain"].append(ctx.last_pipeline_ms()["wf_reduce_ms"])
+    same = bool(torch.equal(c_plain.view(torch.int32), c_mom.view(torch.int32)))
+    base = {"mode": "variance", "mesh": "drone", "width": size, "height": size, "aa_sample_count": BAKE_AA, "path_depth": cam.path_depth,
+            "covered_share": round(float((nrm != 0).any(dim=-1).float().mean()), 4), "calls": calls}
+    rows.append(dict(base, query="mi_render_points_device", **stats(ms["plain"]), wf_reduce_ms_median=round(float(np.median(reduce_ms["plain"])), 4)))
+    rows.append(dict(base, query="mi_render_points_moments_device", **stats(ms["moments"]),
+                     wf_reduce_ms_median=round(float(np.median(reduce_ms["moments"])), 4), wf_reduce_m2_ms_median=round(float(np.median(m2_ms)), 4),
+                     wf_reduce_m2_ms_min=round(float(np.min(m2_ms)), 4), wf_reduce_m2_ms_max=round(float(np.max(m2_ms)), 4),
+                     mean_of_squares=round(float(c_m2.mean().item()), 6)))
+    rows.append(dict(base, query="ratio moments / plain", ms_median=round(float(np.median(ms["moments"])) / float(np.median(ms["plain"])), 4),
+                     wf_reduce_m2_over_wf_reduce=round(float(np.median(m2_ms)) / float(np.median(reduce_ms["moments"])), 3),
+                     compact_images_bit_identical=same))
+    for row in rows[-3:]:
+        print(json.dumps(row), flush=True)
+    if not same:
+        raise SystemExit("ray_query_bench: the moments call's image differs from mi_render_points_device's")
+    del c_plain, c_mom, c_m2, pts, nrm
+
+    # 2. the finish
+    for size in sizes:
+        _, pts, nrm = atlas(size, 1)
+        covered = (nrm != 0).any(dim=-1)
+        gen = torch.Generator(device=dev)
+        gen.manual_seed(1)
+        img = (1.0 + 0.5 * torch.randn((size, size, 3), generator=gen, dtype=torch.float32, device=dev)).abs() * covered[..., None]
+        sd = 0.3 * img * (0.5 + torch.rand((size, size, 3), generator=gen, dtype=torch.float32, device=dev))
+        m2 = img * img + sd * sd * ((BAKE_AA - 1) / BAKE_AA)
+        out = torch.empty((size, size, 3), dtype=torch.float32, device=dev)
+        var = torch.empty((size, size), dtype=torch.float32, device=dev)
+        valid = torch.empty((size, size), dtype=torch.uint8, device=dev)
+        torch.cuda.synchronize()
+        ms = {"fixed": [], "variance": []}
+        for k in range(warmup + calls):
+            ctx.lightmap_finish_device(size, size, img.data_ptr(), pts.data_ptr(), nrm.data_ptr(), out.data_ptr(), valid.data_ptr(),
+                                       levels=FINISH_LEVELS, sigma_color=8.0, dilate=FINISH_DILATE)
+            torch.cuda.synchronize()
+            if k >= warmup:
+                ms["fixed"].append(ctx.last_kernel_ms())
+            ctx.lightmap_finish_var_device(size, size, img.data_ptr(), m2.data_ptr(), BAKE_AA, pts.data_ptr(), nrm.data_ptr(), out.data_ptr(),
+                                           var.data_ptr(), valid.data_ptr(), levels=FINISH_LEVELS, sigma_color=8.0, color_floor=1e-6,
+                                           dilate=FINISH_DILATE)
+            torch.cuda.synchronize()
+            if k >= warmup:
+                ms["variance"].append(ctx.last_kernel_ms())
+        base = {"mode": "variance", "mesh": "drone", "width": size, "height": size, "levels": FINISH_LEVELS, "dilate": FINISH_DILATE,
+                "covered_share": round(float(covered.float().mean()), 4), "calls": calls}
+        rows.append(dict(base, query="mi_lightmap_finish_device", **stats(ms["fixed"])))
+        rows.append(dict(base, query="mi_lightmap_finish_var_device", **stats(ms["variance"]),
+                         mean_variance=float(var.mean().item())))
+        rows.append(dict(base, query="ratio variance-guided / fixed",
+                         ms_median=round(float(np.median(ms["variance"])) / float(np.median(ms["fixed"])), 4)))
+        for row in rows[-3:]:
+            print(json.dumps(row), flush=True)
+        del pts, nrm, img, sd, m2, out, var, valid
+    return rows
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--calls", type=int, default=20, help="timed calls per row (at least 20)")
@@ -752,7 +865,7 @@ def main():
     ap.add_argument("--width", type=int, default=1920)
     ap.add_argument("--height", type=int, default=1080)
     ap.add_argument("--configs", default="2,4")
-    ap.add_argument("--mode", choices=("intersect", "occlusion", "render", "hemisphere", "bake", "probes", "atlas", "finish", "volume"), default="intersect",
+    ap.add_argument("--mode", choices=("intersect", "occlusion", "render", "hemisphere", "bake", "probes", "atlas", "finish", "volume", "variance"), default="intersect",
                     help="intersect: the closest-hit rows; occlusion: the any-hit query against the visibility form; "
                          "render: ray-table rendering against mi_shade_rays_device; "
                          "hemisphere: hemisphere occlusion against the any-hit query on the identical pre-made rays; "
@@ -760,10 +873,11 @@ def main():
                          "probes: light-probe rendering against ray-table rendering on the identical pre-made rays; "
                          "atlas: the lightmap atlas on the GPU against the host helper, on the drone; "
                          "finish: lightmap finishing pass by pass, both forms of the filter, against a copy of the same bytes; "
-                         "volume: irradiance-volume sampling, coherent and shuffled points, against a copy of the same bytes")
+                         "volume: irradiance-volume sampling, coherent and shuffled points, against a copy of the same bytes; "
+                         "variance: the bake's second moments against the plain bake, the variance-guided finish against the fixed one")
     ap.add_argument("--volume-grids", default="16,32", help="--mode volume: probes per axis")
     ap.add_argument("--volume-points", default=f"{1 << 20},{1 << 22}", help="--mode volume: point counts")
-    ap.add_argument("--finish-sizes", default="1024,2048,4096", help="--mode finish: the square atlas sizes")
+    ap.add_argument("--finish-sizes", default="1024,2048,4096", help="--mode finish and --mode variance: the square atlas sizes")
     ap.add_argument("--atlas-sizes", default="1024,2048", help="--mode atlas: the square atlas sizes")
     ap.add_argument("--atlas-grid", type=int, default=0, help="--mode atlas: a synthetic height field of N x N quads (2 N^2 triangles) instead "
                     "of the drone; the table's timings and the check against the helper only, no bake")
@@ -783,6 +897,9 @@ def main():
     ctx = Context(0)
     if a.mode == "volume":
         rows += volume_rows(ctx, [int(v) for v in a.volume_grids.split(",")], [int(v) for v in a.volume_points.split(",")], a.calls, a.warmup)
+        a.configs = ""
+    if a.mode == "variance":
+        rows += variance_rows(ctx, [int(v) for v in a.finish_sizes.split(",")], a.calls, a.warmup)
         a.configs = ""
     if a.mode == "atlas":
         for size in [int(v) for v in a.atlas_sizes.split(",")]:
