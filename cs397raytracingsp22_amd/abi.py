@@ -26,6 +26,7 @@ MI_SHADE_PHONG, MI_SHADE_PATHTRACE = 0, 1
 MI_VARIANT_DEFAULT, MI_VARIANT_SIMPLE, MI_VARIANT_VOTED, MI_VARIANT_VOTED_DIAG = 0, 1, 3, 4      # 2, 5, 6: removed in ABI 3
 MI_VARIANT_WAVEFRONT, MI_VARIANT_RECURSIVE = 7, 8
 MI_OPT_NO_TILE_MASKS, MI_OPT_REFERENCE_WALK, MI_OPT_TWO_STAGE, MI_OPT_NO_LIST_TREE = 1, 2, 4, 8
+MI_OPT_NO_FINAL_CULL = 16
 MI_HEMI_WORLD_RADIUS = 1   # mi_hemisphere_occlusion flags: t_max is a world-space radius
 MI_LM_JITTER = 1           # mi_lightmap_texels / mi_bake_lightmap flags: one jittered position per row instead of the texel centre
 MI_PV_NORMAL_WEIGHT = 1    # mi_probe_volume.flags: weight the eight corners by how far they lie in front of the surface

@@ -107,6 +107,7 @@ struct mi_ctx {
 
     // device scene: the blob, its pools (S), and the compiler's tables for the host side of a render (scene.image is emptied once copied)
     void* blob = nullptr; size_t blob_bytes = 0;
+    const uint32_t* d_fin = nullptr;         // inside the blob's allocation, behind the image: WfArgs.fin (flags, then the may-emit bit of every Scene.objects entry)
     DScene S{};
     CompiledScene scene;
     bool have_scene = false;
@@ -345,14 +346,20 @@ extern "C" int mi_scene_upload(mi_ctx* c, const mi_scene_desc* d) {
     if (rc != MI_OK) return rc;
     HIP_TRY(hipSetDevice(c->device));
     if (c->blob) (void)hipFree(c->blob);
-    c->blob = nullptr; c->blob_bytes = 0; c->S = DScene{}; c->scene = CompiledScene(); c->have_scene = false;
+    c->blob = nullptr; c->blob_bytes = 0; c->d_fin = nullptr; c->S = DScene{}; c->scene = CompiledScene(); c->have_scene = false;
     c->masks.valid = false;
     const size_t total = sc.image.size();
+    // behind the image, in the same allocation: the table of wf_main's final-segment cull (WfArgs.fin; not part of the blob)
+    std::vector<uint32_t> fin(1, sc.emit.any_mesh ? (uint32_t)kFinMeshEmit : 0u);
+    fin.insert(fin.end(), sc.emit.object_bits.begin(), sc.emit.object_bits.end());
+    const size_t fin_off = (total + 255) & ~(size_t)255, fin_bytes = fin.size() * sizeof(uint32_t);
     void* blob = nullptr;
-    hipError_t e = hipMalloc(&blob, total);
-    if (e != hipSuccess) return fail(MI_ERR_OOM, "hipMalloc(%zu) for the scene failed: %s", total, hipGetErrorString(e));
+    hipError_t e = hipMalloc(&blob, fin_off + fin_bytes);
+    if (e != hipSuccess) return fail(MI_ERR_OOM, "hipMalloc(%zu) for the scene failed: %s", fin_off + fin_bytes, hipGetErrorString(e));
     c->blob = blob; c->blob_bytes = total;
+    c->d_fin = (const uint32_t*)((const uint8_t*)blob + fin_off);
     HIP_TRY(hipMemcpy(c->blob, sc.image.data(), total, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy((uint8_t*)c->blob + fin_off, fin.data(), fin_bytes, hipMemcpyHostToDevice));
     sc.image = std::vector<uint8_t>();
     c->S = sc.device_scene(c->blob);
     c->scene = std::move(sc);
@@ -552,6 +559,7 @@ static int render_tiles_wavefront(mi_ctx* c, const K1Args& k, const mi_camera_de
     a.diag = nullptr;           // developer builds (-DPT_WF_STAMPS): phase stamps of wf_main
     if (c->tune.wf_stamps) { a.diag = c->d_diag; HIP_TRY(hipMemsetAsync(c->d_diag, 0, 16 * sizeof(unsigned long long), stream)); }
     a.refill_min = c->tune.refill_min;
+    a.fin = (flags & MI_OPT_NO_FINAL_CULL) ? nullptr : c->d_fin;       // wf_main's final-segment cull (SIG = false forms)
     const WalkMasks masks = walk_masks(c->scene, flags);
     const WalkerPlan walker = plan_walker(c->scene, masks.ref, c->tune.trav_lds, c->tune.trav_bpc, c->tune.global_bvh);
     const PassSchedule sched = pass_schedule(c->scene, masks, walker, c->n_cus, cam->path_depth, c->tune.sched);

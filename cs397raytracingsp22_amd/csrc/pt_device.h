@@ -302,6 +302,7 @@ constexpr int kHdrSegments = 6;      // Scene::intersect_ray evaluations of the 
 constexpr int kHdrSlotWords = 8;
 constexpr int32_t kIdEnd = (int32_t)0x80000000;   // split pools: "no further node"
 constexpr int kPairStride = 56;                    // wf_trav_i<.., PAIR>: bytes of an interior record in the paired LDS layout (pt_kernels.hip)
+enum : uint32_t { kFinMeshEmit = 1u };   // WfArgs.fin[0]
 struct WfArgs {
     DScene  S;
     DCamera C;
@@ -349,6 +350,9 @@ struct WfArgs {
     // {position of the path in st_out, count | bit (8 + m): mesh m must take the reference walk (overflow, bound not applicable)}
     uint2* cand;
     uint2* cand_hdr;
+    // Final-segment cull (wf_main, SIG = false forms; scene_compile.hpp EmitFlags): nullptr = off.  fin[0] = flags (kFinMeshEmit: some mesh of
+    // the scene may emit), then one bit per Scene.objects entry: bit i % 32 of fin[1 + i / 32] = entry i may emit.
+    const PT_CONST_AS uint32_t* fin;
     unsigned long long* diag;   // developer builds with -DPT_WF_STAMPS: [16] summed s_memtime deltas of sampled wf_main waves
     // Ray-table rendering (mi_render_rays): the camera pass takes sample s of pixel (x, y) from ray_o / ray_d at
     // ((row * height + y) * width + x) * 3, row = s when rays_per_pixel == aa_sample_count, 0 when it is 1.  nullptr = Camera::generate_rays.

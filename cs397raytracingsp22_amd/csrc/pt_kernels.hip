@@ -2368,6 +2368,28 @@ __global__ __launch_bounds__(kBlock, (MESH == 2 ? PT_MAIN_WAVES : (MESH == 1 ? P
             }
             need = false;
         }
+        // Final-segment cull (SIG = false only).  A ray traced at level path_depth - 1 can only ever add the EMISSION of
+        // its closest hit: the next shade_ray level returns before it scatters (above: P.depth++, then the depth test).  That last
+        // shading is L + T e.  When e = (+-0, +-0, +-0) and T is finite, T e = +-0; L starts at +0 and a sum is -0 only when both
+        // addends are, so L is never -0 and L + T e == L bit for bit: whatever the tests still to come would find — a hit that cannot
+        // emit, or a miss — leaves the same L.  So a final ray whose closest LIST hit is a miss or an object that cannot emit, and which
+        // waits for no mesh (or no mesh of the scene may emit), ends its path here with L as it is: no class-B round trip, no walk of
+        // the tree, no shading pass.  A non-finite T gives 0 inf = NaN for a hit and nothing for a miss, so such a lane goes on as
+        // before.  The RNG state of an ended path is read by nobody when signatures are off (the SIG forms keep every segment).
+        // The live lanes here are the ones just traced and the ones that have been waiting for a walk since an earlier trip; the rule
+        // holds for both.  Cost when no live lane is final: one vote — the flag word and the may-emit bits sit behind A.fin and are
+        // read only past it (this kernel is bound by instruction issue, and the lean form sits at its SGPR limit: the same rule with
+        // its flags and masks as kernel arguments cost every trip v_readlane spills, cfg2 wf_main + 1.5 to 2.1 ms with the cull off).
+        if (!SIG && __builtin_amdgcn_ballot_w64(alive && P.depth + 1u == C.path_depth) != 0ull && A.fin != nullptr) {
+            if (alive && P.depth + 1u == C.path_depth && __builtin_isfinite(P.T.x) && __builtin_isfinite(P.T.y) && __builtin_isfinite(P.T.z) &&
+                !(enters && (A.fin[0] & kFinMeshEmit))) {
+                const uint32_t word = best.obj >= 0 ? A.fin[1 + (best.obj >> 5)] : 0u;       // no list hit at all: the ray only waits for a mesh that cannot emit
+                if (!((word >> (best.obj & 31)) & 1u)) {
+                    A.samp[(size_t)(sample - A.s_base) * A.npix + pix] = make_float4(P.L.x, P.L.y, P.L.z, __uint_as_float(P.sig));
+                    alive = false;
+                }
+            }
+        }
         first = false;
         const bool cont = alive && !enters;             // its hit is known: nothing left to wait for
         // (Round 4, measured negative: the BLOCK votes instead of the wave, and the continuing paths of its four waves are packed through LDS

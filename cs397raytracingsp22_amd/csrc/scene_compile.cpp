@@ -600,7 +600,28 @@ int layout(const Build& b, CompiledScene& out) {
     return MI_OK;
 }
 
+// The may-emit flags (scene_compile.hpp EmitFlags) of Scene.objects, of the kind-grouped list and of the live meshes
+EmitFlags emit_flags(const mi_scene_desc* d, const Build& b) {
+    EmitFlags e;
+    auto mat = [&](int id) { return material_may_emit(d->materials[id]); };
+    auto mesh = [&](const DMesh& M) { return (M.material >= 0 && mat(M.material)) || M.tex[1] >= 0; };
+    auto object = [&](const DObject& o) { return o.kind == OBJ_MESH ? mesh(b.live[(size_t)o.ref]) : mat(o.material); };
+    e.object_bits.assign(b.objs.size() / 32 + 1, 0u);
+    for (size_t i = 0; i < b.objs.size(); i++) if (object(b.objs[i])) e.object_bits[i / 32] |= 1u << (i % 32);
+    for (const DObject& o : b.list) if (o.kind == OBJ_VOLUME && object(o)) e.any_volume = true;
+    e.list_mask_valid = b.list.size() <= 64;
+    for (size_t k = 0; k < b.list.size() && k < 64; k++) if (object(b.list[k])) e.list_mask |= 1ull << k;
+    for (size_t m = 0; m < b.n_scene_meshes; m++)
+        if (mesh(b.live[m])) { e.any_mesh = true; if (m < 32) e.mesh_mask |= 1u << m; }
+    return e;
+}
+
 }  // namespace
+
+bool material_may_emit(const mi_material& m) {
+    if (m.kind == MI_MAT_DIELECTRIC) return false;
+    return !(m.emission[0] == 0.0f && m.emission[1] == 0.0f && m.emission[2] == 0.0f);      // -0 == 0; a NaN is not
+}
 
 int compile_scene(const mi_scene_desc* d, CompiledScene* out) {
     if (d->n_objects < 0 || d->n_materials < 0 || d->n_meshes < 0 || d->n_textures < 0)
@@ -622,6 +643,7 @@ int compile_scene(const mi_scene_desc* d, CompiledScene* out) {
     rotations(b);
     rc = layout(b, c);
     if (rc != MI_OK) return rc;
+    c.emit = emit_flags(d, b);
     c.list = std::move(b.list);
     c.n_list_tri = b.n_list[0]; c.n_list_sphere = b.n_list[1]; c.n_unmasked = b.n_list[2] + b.n_list[3];
     c.gen_volumes = !b.bobjs.empty();

@@ -26,6 +26,23 @@ inline float dot(h3 a, h3 b) { return (a.x * b.x + a.y * b.y) + a.z * b.z; }
 inline h3 cross(h3 a, h3 b) { return H3(a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x); }
 inline h3 normalize(h3 a) { return scale(a, 1.0f / sqrtf(dot(a, a))); }
 
+// May a hit of this material add light to a path?  False only when the emission the kernels would read is exactly (+-0, +-0, +-0): a NaN
+// component counts as emitting, and a Dielectric never emits whatever its descriptor says (materials.rs:102: the compiler stores zeros).
+bool material_may_emit(const mi_material& m);
+
+// What wf_main's final-segment cull (pt_kernels.hip) needs to know about the scene: which entries MAY emit.  A list
+// object takes the flag of its material, a ConvexVolume that of its phase material; a mesh may emit when its fixed material does or an
+// emission map is bound.  Carried beside the blob, never inside it.  The kernel reads object_bits and any_mesh (mi_scene_upload: WfArgs.fin);
+// the list and mesh masks are what a test order "emitters first" needs (DESIGN_HISTORY.md "Final-segment cull": built, measured, no gain).
+struct EmitFlags {
+    std::vector<uint32_t> object_bits;   // bit i of the array: Scene.objects entry i may emit (at least one word)
+    uint64_t list_mask = 0;              // bit k: entry k of the kind-grouped list may emit; complete when list_mask_valid
+    bool list_mask_valid = false;        // the list has at most 64 entries
+    uint32_t mesh_mask = 0;              // bit m: live mesh m < 32 may emit
+    bool any_mesh = false;               // some live mesh may emit (meshes 32, 33, ... included)
+    bool any_volume = false;             // some ConvexVolume may emit
+};
+
 struct CompiledScene {
     // the blob: objects | list | boundary records | rotations | materials | meshes | F-tree meshes | F-tree nodes / triangles |
     // nodes | e2 | interior / leaf records | triangles | attributes | textures | texels, each pool 256-byte aligned
@@ -39,6 +56,7 @@ struct CompiledScene {
     std::vector<Mesh> meshes;
     std::vector<DObject> list;        // the kind-grouped list as the kernels read it (tile masks: its Triangles and Spheres)
     int n_list_tri = 0, n_list_sphere = 0, n_unmasked = 0;   // planes + volumes: never masked
+    EmitFlags emit;                   // may-emit flags of the objects, the list positions and the live meshes
     bool mesh_maps = false;           // some mesh takes its material from maps or has a normal map: wf_main's MESH = 2 form
     bool gen_volumes = false;         // a ConvexVolume whose boundary is not the inline sphere: the kernels' GV forms
     uint32_t lds_bytes = 0;           // bytes needed to stage nodes + tris (the K1 megakernels), 0 = no meshes

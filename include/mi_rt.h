@@ -201,6 +201,8 @@ typedef struct mi_render_opts {
 #define MI_OPT_TWO_STAGE       4u   /* meshes: use the two-stage traversal for every mesh, whatever its size: same image */
 #define MI_OPT_NO_LIST_TREE    8u   /* long lists: test every Triangle of Scene.objects one by one instead of walking the top-level tree the scene
                                      * compiler builds over them (>= 96 small triangles): same image */
+#define MI_OPT_NO_FINAL_CULL   16u   /* path tracing without signatures: trace the final segment of every path like any other, even where no emitter
+                                     * can be its closest hit (no final-segment cull): same image */
 /* `flags` of mi_hemisphere_occlusion (below) */
 #define MI_HEMI_WORLD_RADIUS 1u     /* t_max is a world-space radius: the interval of a sample ends at t_max / |d| */
 /* mi_lightmap_texels / mi_bake_lightmap flags */

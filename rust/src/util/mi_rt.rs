@@ -43,7 +43,7 @@ use std::os::raw::{c_char, c_int, c_void};
 }
 pub enum mi_ctx {}
 pub enum mi_multi {}
-pub const MI_OPT_NO_TILE_MASKS: u32 = 1; pub const MI_OPT_REFERENCE_WALK: u32 = 2; pub const MI_OPT_TWO_STAGE: u32 = 4; pub const MI_OPT_NO_LIST_TREE: u32 = 8;
+pub const MI_OPT_NO_TILE_MASKS: u32 = 1; pub const MI_OPT_REFERENCE_WALK: u32 = 2; pub const MI_OPT_TWO_STAGE: u32 = 4; pub const MI_OPT_NO_LIST_TREE: u32 = 8; pub const MI_OPT_NO_FINAL_CULL: u32 = 16;
 pub const MI_RT_ABI_VERSION: c_int = 5;
 pub const MI_HEMI_WORLD_RADIUS: u32 = 1;
 pub const MI_LM_JITTER: u32 = 1;
