@@ -20,6 +20,7 @@ from .tracing import Camera, CameraProjectionMode, Context, MultiContext, Scene,
 from .tracing import check_ray_table, equirect_dirs, equirect_ray_table  # noqa: F401
 from .tracing import check_point_table, lightmap_jitter, lightmap_texels  # noqa: F401
 from .tracing import check_finish_tables, lightmap_finish, lightmap_finish_var  # noqa: F401
+from .tracing import check_counts_plane, lightmap_gather, lightmap_merge, lightmap_select  # noqa: F401
 from .tracing import check_probe_table, probe_grid, sh9_basis, sh9_irradiance  # noqa: F401
 from .tracing import ProbeVolume, check_probe_volume, check_volume_points, probe_volume_sample  # noqa: F401
 

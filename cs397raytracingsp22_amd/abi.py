@@ -108,6 +108,11 @@ class mi_probe_volume(C.Structure):
                 ("sh", C.c_void_p), ("valid", C.c_void_p)]          # host or device addresses, by the entry point
 
 
+class mi_lightmap_adaptive(C.Structure):
+    _fields_ = [("first_samples", C.c_uint32), ("round_samples", C.c_uint32), ("max_rounds", C.c_uint32),
+                ("target_rel", C.c_float), ("target_abs", C.c_float)]
+
+
 class mi_stats(C.Structure):
     _fields_ = [("samples", C.c_uint64), ("pixels", C.c_uint64), ("tiles", C.c_uint32),
                 ("tiles_padded", C.c_uint32), ("kernel_ms", C.c_float), ("total_ms", C.c_float),
@@ -129,6 +134,9 @@ EXPORTS = [
     "mi_lightmap_finish", "mi_lightmap_finish_device",
     "mi_render_points_moments", "mi_render_points_moments_device", "mi_bake_lightmap_moments",
     "mi_lightmap_finish_var", "mi_lightmap_finish_var_device",
+    "mi_lightmap_select", "mi_lightmap_select_device", "mi_lightmap_gather", "mi_lightmap_gather_device",
+    "mi_lightmap_merge", "mi_lightmap_merge_device", "mi_lightmap_finish_var_counts", "mi_lightmap_finish_var_counts_device",
+    "mi_bake_lightmap_adaptive",
     "mi_probe_volume_sample", "mi_probe_volume_sample_device",
     "mi_multi_create", "mi_multi_create_loopback", "mi_multi_destroy", "mi_multi_device_count", "mi_multi_context", "mi_multi_scene_upload", "mi_multi_reserve", "mi_multi_render",
 ]
@@ -270,6 +278,24 @@ def load() -> C.CDLL:
     lib.mi_lightmap_finish_var.restype = C.c_int
     lib.mi_lightmap_finish_var_device.argtypes = lib.mi_lightmap_finish_var.argtypes + [vp]
     lib.mi_lightmap_finish_var_device.restype = C.c_int
+    # adaptive lightmap bake (added within ABI 5): select (the planes, the two targets, capacity, the list, its length, the error plane),
+    # gather (the list, the source tables, cw, the compact tables), merge (the list, the round's tables and count, the planes in place),
+    # mi_lightmap_finish_var with a counts plane in the place of samples, and mi_bake_lightmap_moments with the adaptive POD and out_counts
+    u32, f = C.c_uint32, C.c_float
+    lib.mi_lightmap_select.argtypes = [vp, u32, u32, vp, vp, vp, vp, f, f, u32, vp, vp, vp]
+    lib.mi_lightmap_select_device.argtypes = lib.mi_lightmap_select.argtypes + [vp]
+    lib.mi_lightmap_gather.argtypes = [vp, u32, u32, u32, u32, vp, vp, vp, u32, vp, vp]
+    lib.mi_lightmap_gather_device.argtypes = lib.mi_lightmap_gather.argtypes + [vp]
+    lib.mi_lightmap_merge.argtypes = [vp, u32, u32, u32, vp, vp, vp, u32, vp, vp, vp]
+    lib.mi_lightmap_merge_device.argtypes = lib.mi_lightmap_merge.argtypes + [vp]
+    lib.mi_lightmap_finish_var_counts.argtypes = [vp, u32, u32, vp, vp, vp, vp, vp, u32, u32, f, f, f, f, u32, vp, vp, vp]
+    lib.mi_lightmap_finish_var_counts_device.argtypes = lib.mi_lightmap_finish_var_counts.argtypes + [vp]
+    lib.mi_bake_lightmap_adaptive.argtypes = [vp, C.POINTER(mi_camera_desc), C.POINTER(mi_render_opts), C.POINTER(mi_mesh), u32, f,
+                                              C.POINTER(mi_lightmap_adaptive), vp, vp, vp, vp, vp, vp, C.POINTER(mi_stats)]
+    for name in ("select", "select_device", "gather", "gather_device", "merge", "merge_device", "finish_var_counts",
+                 "finish_var_counts_device"):
+        getattr(lib, "mi_lightmap_" + name).restype = C.c_int
+    lib.mi_bake_lightmap_adaptive.restype = C.c_int
     # irradiance volumes (added within ABI 5): volume, n_points, points, normals, out_irradiance, out_weight (, stream)
     lib.mi_probe_volume_sample.argtypes = [vp, C.POINTER(mi_probe_volume), C.c_uint32, vp, vp, vp, vp]
     lib.mi_probe_volume_sample.restype = C.c_int

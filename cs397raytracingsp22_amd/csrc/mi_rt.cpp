@@ -66,6 +66,10 @@ hipError_t launch_wf_reduce_m2(const WfArgs& a, bool first_batch, bool last_batc
 hipError_t launch_lmv_init(const LmvArgs& a, hipStream_t stream);
 hipError_t launch_lmv_blur(const LmvArgs& a, hipStream_t stream);
 hipError_t launch_lmv_atrous(const LmvArgs& a, hipStream_t stream);
+hipError_t launch_lmv_init_counts(const LmvArgs& a, const uint32_t* counts, bool few_inf, hipStream_t stream);
+hipError_t launch_lma_select(const LmaArgs& a, hipStream_t stream);
+hipError_t launch_lma_gather(const LmaListArgs& a, hipStream_t stream);
+hipError_t launch_lma_merge(const LmaListArgs& a, hipStream_t stream);
 }  // namespace pt
 
 using namespace pt;
@@ -145,6 +149,14 @@ struct mi_ctx {
     void* d_m2 = nullptr; size_t m2_bytes = 0;
     void* d_lmv = nullptr; size_t lmv_bytes = 0;
     void* d_lmv_io = nullptr; size_t lmv_io_bytes = 0;
+    // mi_lightmap_select: the variance plane, the flags, the block counts and offsets; the host forms' uploaded planes, lists and results;
+    // mi_bake_lightmap_adaptive: the running planes with the centre table, the list with its length, and a round's compact tables and
+    // results (all grown on demand, never the buffers mi_reserve sized)
+    void* d_lma = nullptr; size_t lma_bytes = 0;
+    void* d_lma_io = nullptr; size_t lma_io_bytes = 0;
+    void* d_lma_bake = nullptr; size_t lma_bake_bytes = 0;
+    void* d_lma_list = nullptr; size_t lma_list_bytes = 0;
+    void* d_lma_round = nullptr; size_t lma_round_bytes = 0;
     hipEvent_t ev_t0 = nullptr, ev_t1 = nullptr;     // mi_render's whole-call timer
     bool big_lds_enabled = false;                    // wf_trav_i<1024>'s > 64 KB dynamic-LDS opt-in, set on THIS context's device
     // wavefront pipeline buffers
@@ -313,6 +325,11 @@ extern "C" void mi_ctx_destroy(mi_ctx* c) {
     if (c->d_m2) (void)hipFree(c->d_m2);
     if (c->d_lmv) (void)hipFree(c->d_lmv);
     if (c->d_lmv_io) (void)hipFree(c->d_lmv_io);
+    if (c->d_lma) (void)hipFree(c->d_lma);
+    if (c->d_lma_io) (void)hipFree(c->d_lma_io);
+    if (c->d_lma_bake) (void)hipFree(c->d_lma_bake);
+    if (c->d_lma_list) (void)hipFree(c->d_lma_list);
+    if (c->d_lma_round) (void)hipFree(c->d_lma_round);
     if (c->d_wf_a) (void)hipFree(c->d_wf_a);
     if (c->d_wf_b) (void)hipFree(c->d_wf_b);
     if (c->d_wf_samp) (void)hipFree(c->d_wf_samp);
@@ -1516,11 +1533,12 @@ static int check_lmv_args(const char* who, uint32_t width, uint32_t height, cons
 
 // Queue the passes on `stream`; every pointer is a device pointer and the outputs overlap no input.  The images and masks alternate as in
 // lightmap_finish_device (the same scratch); the variance alternates between the context's two planes, the last level writing d_var when
-// the caller wants it (the dilation passes do not touch it).
+// the caller wants it (the dilation passes do not touch it).  d_counts (mi_lightmap_finish_var_counts): the per-texel counts that take
+// the place of `samples` in the initial variance, or nullptr.
 static int lightmap_finish_var_device(mi_ctx* c, uint32_t width, uint32_t height, const float* d_image, const float* d_m2, uint32_t samples,
                                       const float* d_points, const float* d_normals, uint32_t levels, uint32_t normal_power_log2,
                                       float sigma_plane, float reach, float sigma_color, float color_floor, uint32_t dilate, float* d_out,
-                                      float* d_var, uint8_t* d_valid, hipStream_t stream) {
+                                      float* d_var, uint8_t* d_valid, hipStream_t stream, const uint32_t* d_counts = nullptr) {
     const size_t n = (size_t)width * height, img = n * 3 * sizeof(float), msk = (n + 255) / 256 * 256, pln = msk * sizeof(float);
     MI_TRY(ensure(&c->d_lmf, &c->lmf_bytes, 2 * img + 2 * msk));
     MI_TRY(ensure(&c->d_lmv, &c->lmv_bytes, 3 * pln));
@@ -1545,7 +1563,8 @@ static int lightmap_finish_var_device(mi_ctx* c, uint32_t width, uint32_t height
     HIP_TRY(launch_lmf_mask(a, stream));
     a.copy = 0;
     v.src = d_image; v.var_out = var_target(0);
-    HIP_TRY(launch_lmv_init(v, stream));
+    if (d_counts) HIP_TRY(launch_lmv_init_counts(v, d_counts, false, stream));
+    else HIP_TRY(launch_lmv_init(v, stream));
     for (uint32_t p = 0; p < passes; p++) {
         a.dst = p + 1 == passes ? d_out : ping[p & 1u];
         if (p < levels) {
@@ -1605,6 +1624,385 @@ extern "C" int mi_lightmap_finish_var(mi_ctx* c, uint32_t width, uint32_t height
     if (out_var) HIP_TRY(hipMemcpyAsync(out_var, io + 5 * img, pln, hipMemcpyDeviceToHost, c->stream));
     if (out_valid) HIP_TRY(hipMemcpyAsync(out_valid, io + 5 * img + pln, n, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
+    return MI_OK;
+}
+
+// mi_lightmap_finish_var with the per-texel counts of an adaptive bake in place of `samples`: one more form of lmv_init, everything else
+// the same passes.
+extern "C" int mi_lightmap_finish_var_counts_device(mi_ctx* c, uint32_t width, uint32_t height, const float* image, const float* m2,
+                                                    const uint32_t* counts, const float* points, const float* normals, uint32_t levels,
+                                                    uint32_t normal_power_log2, float sigma_plane, float reach, float sigma_color,
+                                                    float color_floor, uint32_t dilate, float* out_image, float* out_var, uint8_t* out_valid,
+                                                    void* stream) {
+    if (!counts) return fail(MI_ERR_INVALID, "mi_lightmap_finish_var_counts_device: counts is required");
+    MI_TRY(check_lmv_args("mi_lightmap_finish_var_counts_device", width, height, image, m2, 2, points, normals, levels, normal_power_log2,
+                          sigma_plane, reach, sigma_color, color_floor, dilate, out_image));
+    const uintptr_t bytes = (uintptr_t)width * height * 3 * sizeof(float);
+    const struct { uintptr_t at, bytes; const char* name; } outs[2] = { { (uintptr_t)out_image, bytes, "out_image" },
+                                                                        { (uintptr_t)out_var, bytes / 3, "out_var" } };
+    const struct { uintptr_t at, bytes; } ins[5] = { { (uintptr_t)image, bytes }, { (uintptr_t)m2, bytes }, { (uintptr_t)points, bytes },
+                                                     { (uintptr_t)normals, bytes }, { (uintptr_t)counts, bytes / 3 } };
+    for (const auto& o : outs)
+        for (const auto& in : ins)
+            if (o.at && o.at < in.at + in.bytes && in.at < o.at + o.bytes)
+                return fail(MI_ERR_INVALID, "mi_lightmap_finish_var_counts_device: %s overlaps an input (the passes are never in place)", o.name);
+    if (!c) return fail(MI_ERR_INVALID, "ctx is NULL");
+    HIP_TRY(hipSetDevice(c->device));
+    return lightmap_finish_var_device(c, width, height, image, m2, 2, points, normals, levels, normal_power_log2, sigma_plane, reach,
+                                      sigma_color, color_floor, dilate, out_image, out_var, out_valid, (hipStream_t)stream, counts);
+}
+
+extern "C" int mi_lightmap_finish_var_counts(mi_ctx* c, uint32_t width, uint32_t height, const float* image, const float* m2,
+                                             const uint32_t* counts, const float* points, const float* normals, uint32_t levels,
+                                             uint32_t normal_power_log2, float sigma_plane, float reach, float sigma_color, float color_floor,
+                                             uint32_t dilate, float* out_image, float* out_var, uint8_t* out_valid) {
+    if (!counts) return fail(MI_ERR_INVALID, "mi_lightmap_finish_var_counts: counts is required");
+    MI_TRY(check_lmv_args("mi_lightmap_finish_var_counts", width, height, image, m2, 2, points, normals, levels, normal_power_log2,
+                          sigma_plane, reach, sigma_color, color_floor, dilate, out_image));
+    if (!c) return fail(MI_ERR_INVALID, "ctx is NULL");
+    HIP_TRY(hipSetDevice(c->device));
+    // image, m2, points, normals, the result, its variance, the counts, the mask
+    const size_t n = (size_t)width * height, img = n * 3 * sizeof(float), pln = n * sizeof(float);
+    MI_TRY(ensure(&c->d_lmv_io, &c->lmv_io_bytes, 5 * img + 2 * pln + n));
+    char* const io = (char*)c->d_lmv_io;
+    const float* const src[4] = { image, m2, points, normals };
+    for (int k = 0; k < 4; k++) HIP_TRY(hipMemcpyAsync(io + k * img, src[k], img, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(io + 5 * img + pln, counts, pln, hipMemcpyHostToDevice, c->stream));
+    MI_TRY(lightmap_finish_var_device(c, width, height, (const float*)io, (const float*)(io + img), 2, (const float*)(io + 2 * img),
+                                      (const float*)(io + 3 * img), levels, normal_power_log2, sigma_plane, reach, sigma_color, color_floor,
+                                      dilate, (float*)(io + 4 * img), out_var ? (float*)(io + 5 * img) : nullptr,
+                                      out_valid ? (uint8_t*)(io + 5 * img + 2 * pln) : nullptr, c->stream,
+                                      (const uint32_t*)(io + 5 * img + pln)));
+    HIP_TRY(hipMemcpyAsync(out_image, io + 4 * img, img, hipMemcpyDeviceToHost, c->stream));      // after the uploads: out_image may alias image
+    if (out_var) HIP_TRY(hipMemcpyAsync(out_var, io + 5 * img, pln, hipMemcpyDeviceToHost, c->stream));
+    if (out_valid) HIP_TRY(hipMemcpyAsync(out_valid, io + 5 * img + 2 * pln, n, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return MI_OK;
+}
+
+// ------------------------------------------------------------------ adaptive lightmap baking (select, gather, merge, the whole bake)
+// tracing.py lightmap_select, lightmap_gather and lightmap_merge as kernels, and the bake that composes them with the moments render.
+// The arguments are checked before the context, as the finishing pass's are.
+static inline size_t up256(size_t x) { return (x + 255) / 256 * 256; }
+static const uint32_t kLmaMaxList = 1u << 25;          // mi_bake_lightmap_adaptive's capacity: 128 MiB of texel numbers
+static const uint32_t kLmaCompactWidth = 1024;         // ... and the width of its compact tables
+
+static int check_lma_size(const char* who, uint32_t width, uint32_t height) {
+    if (width == 0 || width > 32768u || height == 0 || height > 32768u)
+        return fail(MI_ERR_INVALID, "%s: width %u / height %u is not in 1 .. 32768", who, width, height);
+    return MI_OK;
+}
+
+static int check_select_args(const char* who, uint32_t width, uint32_t height, const float* image, const float* m2, const uint32_t* counts,
+                             const float* normals, float target_rel, float target_abs, uint32_t capacity, const uint32_t* out_index,
+                             const uint32_t* out_count) {
+    if (!image || !m2 || !counts || !normals || !out_count)
+        return fail(MI_ERR_INVALID, "%s: image, m2, counts, normals and out_count are required", who);
+    if (capacity > 0 && !out_index) return fail(MI_ERR_INVALID, "%s: out_index is required when capacity is not 0", who);
+    MI_TRY(check_lma_size(who, width, height));
+    if (!(target_rel >= 0.0f)) return fail(MI_ERR_INVALID, "%s: target_rel must be >= 0 and not NaN", who);
+    if (!(target_abs >= 0.0f)) return fail(MI_ERR_INVALID, "%s: target_abs must be >= 0 and not NaN (+inf selects nothing)", who);
+    return MI_OK;
+}
+
+// Queue lmv_init_counts, lma_mark, lma_scan and lma_fill on `stream`; every pointer is a device pointer.  timed: between the context's
+// timing events (the public forms; the whole bake keeps the events for its renders).
+static int lightmap_select_device(mi_ctx* c, uint32_t width, uint32_t height, const float* d_image, const float* d_m2, const uint32_t* d_counts,
+                                  const float* d_normals, float target_rel, float target_abs, uint32_t capacity, uint32_t* d_index,
+                                  uint32_t* d_count, float* d_error, hipStream_t stream, bool timed) {
+    const size_t n = (size_t)width * height, nb = (n + kLmaBlock - 1) / kLmaBlock;
+    const size_t o_flags = up256(n * sizeof(float)), o_counts = o_flags + up256(n), o_offsets = o_counts + up256(nb * 4);
+    MI_TRY(ensure(&c->d_lma, &c->lma_bytes, o_offsets + up256(nb * 4)));
+    char* const s = (char*)c->d_lma;
+    LmvArgs v{};
+    v.src = d_image; v.m2 = d_m2; v.normals = d_normals; v.var_out = (float*)s;
+    v.width = width; v.height = height;
+    LmaArgs a{};
+    a.image = d_image; a.normals = d_normals; a.var = (const float*)s; a.error = d_error;
+    a.flags = (uint8_t*)(s + o_flags); a.block_counts = (uint32_t*)(s + o_counts); a.block_offsets = (uint32_t*)(s + o_offsets);
+    a.out_index = d_index; a.out_count = d_count;
+    a.width = width; a.height = height; a.blocks = (uint32_t)nb; a.capacity = capacity;
+    a.target_rel = target_rel; a.target_abs = target_abs;
+    if (timed) HIP_TRY(hipEventRecord(c->ev_start, stream));
+    HIP_TRY(launch_lmv_init_counts(v, d_counts, true, stream));
+    HIP_TRY(launch_lma_select(a, stream));
+    if (timed) {
+        HIP_TRY(hipEventRecord(c->ev_stop, stream));
+        c->ev_recorded = true; c->ms_summed = false;
+    }
+    return MI_OK;
+}
+
+extern "C" int mi_lightmap_select_device(mi_ctx* c, uint32_t width, uint32_t height, const float* image, const float* m2,
+                                         const uint32_t* counts, const float* normals, float target_rel, float target_abs, uint32_t capacity,
+                                         uint32_t* out_index, uint32_t* out_count, float* out_error, void* stream) {
+    MI_TRY(check_select_args("mi_lightmap_select_device", width, height, image, m2, counts, normals, target_rel, target_abs, capacity,
+                             out_index, out_count));
+    if (!c) return fail(MI_ERR_INVALID, "ctx is NULL");
+    HIP_TRY(hipSetDevice(c->device));
+    return lightmap_select_device(c, width, height, image, m2, counts, normals, target_rel, target_abs, capacity, out_index, out_count,
+                                  out_error, (hipStream_t)stream, true);
+}
+
+extern "C" int mi_lightmap_select(mi_ctx* c, uint32_t width, uint32_t height, const float* image, const float* m2, const uint32_t* counts,
+                                  const float* normals, float target_rel, float target_abs, uint32_t capacity, uint32_t* out_index,
+                                  uint32_t* out_count, float* out_error) {
+    MI_TRY(check_select_args("mi_lightmap_select", width, height, image, m2, counts, normals, target_rel, target_abs, capacity, out_index,
+                             out_count));
+    if (!c) return fail(MI_ERR_INVALID, "ctx is NULL");
+    HIP_TRY(hipSetDevice(c->device));
+    // image, m2, normals, counts, the error plane, the list (no longer than the atlas), its length
+    const size_t n = (size_t)width * height, img = up256(n * 3 * sizeof(float)), pln = up256(n * sizeof(float));
+    const uint32_t cap = (uint32_t)std::min<size_t>(capacity, n);
+    const size_t o_list = 3 * img + 2 * pln, o_count = o_list + up256((size_t)cap * 4);
+    MI_TRY(ensure(&c->d_lma_io, &c->lma_io_bytes, o_count + 256));
+    char* const io = (char*)c->d_lma_io;
+    const float* const src[3] = { image, m2, normals };
+    for (int k = 0; k < 3; k++) HIP_TRY(hipMemcpyAsync(io + k * img, src[k], n * 3 * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(io + 3 * img, counts, n * 4, hipMemcpyHostToDevice, c->stream));
+    MI_TRY(lightmap_select_device(c, width, height, (const float*)io, (const float*)(io + img), (const uint32_t*)(io + 3 * img),
+                                  (const float*)(io + 2 * img), target_rel, target_abs, cap, (uint32_t*)(io + o_list),
+                                  (uint32_t*)(io + o_count), out_error ? (float*)(io + 3 * img + pln) : nullptr, c->stream, true));
+    uint32_t count = 0;
+    HIP_TRY(hipMemcpyAsync(&count, io + o_count, 4, hipMemcpyDeviceToHost, c->stream));
+    if (out_error) HIP_TRY(hipMemcpyAsync(out_error, io + 3 * img + pln, n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    const uint32_t held = std::min(count, cap);            // the entries behind them are not written
+    if (held) HIP_TRY(hipMemcpy(out_index, io + o_list, (size_t)held * 4, hipMemcpyDeviceToHost));
+    *out_count = count;
+    return MI_OK;
+}
+
+static int check_gather_args(const char* who, uint32_t width, uint32_t height, uint32_t rows, uint32_t n, const uint32_t* index,
+                             const float* points, const float* normals, uint32_t cw, const float* out_points, const float* out_normals) {
+    if (!index || !points || !normals || !out_points || !out_normals)
+        return fail(MI_ERR_INVALID, "%s: index, points, normals, out_points and out_normals are required", who);
+    MI_TRY(check_lma_size(who, width, height));
+    if (rows == 0 || rows > 65535u) return fail(MI_ERR_INVALID, "%s: rows %u is not in 1 .. 65535", who, rows);
+    if (cw == 0 || cw > 32768u) return fail(MI_ERR_INVALID, "%s: cw %u is not in 1 .. 32768", who, cw);
+    const uint64_t ch = ((uint64_t)n + cw - 1) / cw;
+    if (ch == 0 || ch > 32768u)
+        return fail(MI_ERR_INVALID, "%s: n %u entries at cw %u give %llu rows of slots: not in 1 .. 32768", who, n, cw, (unsigned long long)ch);
+    return MI_OK;
+}
+
+static LmaListArgs gather_args(uint32_t width, uint32_t height, uint32_t rows, uint32_t n, const uint32_t* d_index, const float* d_points,
+                               const float* d_normals, uint32_t cw, float* d_out_points, float* d_out_normals) {
+    LmaListArgs a{};
+    a.index = d_index; a.n = n; a.width = width; a.height = height;
+    a.points = d_points; a.normals = d_normals; a.out_points = d_out_points; a.out_normals = d_out_normals;
+    a.rows = rows; a.slots = (n + cw - 1) / cw * cw;
+    return a;
+}
+
+extern "C" int mi_lightmap_gather_device(mi_ctx* c, uint32_t width, uint32_t height, uint32_t rows, uint32_t n, const uint32_t* index,
+                                         const float* points, const float* normals, uint32_t cw, float* out_points, float* out_normals,
+                                         void* stream) {
+    MI_TRY(check_gather_args("mi_lightmap_gather_device", width, height, rows, n, index, points, normals, cw, out_points, out_normals));
+    if (!c) return fail(MI_ERR_INVALID, "ctx is NULL");
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipEventRecord(c->ev_start, (hipStream_t)stream));
+    HIP_TRY(launch_lma_gather(gather_args(width, height, rows, n, index, points, normals, cw, out_points, out_normals), (hipStream_t)stream));
+    HIP_TRY(hipEventRecord(c->ev_stop, (hipStream_t)stream));
+    c->ev_recorded = true; c->ms_summed = false;
+    return MI_OK;
+}
+
+extern "C" int mi_lightmap_gather(mi_ctx* c, uint32_t width, uint32_t height, uint32_t rows, uint32_t n, const uint32_t* index,
+                                  const float* points, const float* normals, uint32_t cw, float* out_points, float* out_normals) {
+    MI_TRY(check_gather_args("mi_lightmap_gather", width, height, rows, n, index, points, normals, cw, out_points, out_normals));
+    if (!c) return fail(MI_ERR_INVALID, "ctx is NULL");
+    HIP_TRY(hipSetDevice(c->device));
+    // the list, the two source tables, the two compact tables
+    const size_t lst = up256((size_t)n * 4), tab = up256((size_t)rows * width * height * 3 * sizeof(float));
+    const size_t slots = ((size_t)n + cw - 1) / cw * cw, out = up256((size_t)rows * slots * 3 * sizeof(float));
+    MI_TRY(ensure(&c->d_lma_io, &c->lma_io_bytes, lst + 2 * tab + 2 * out));
+    char* const io = (char*)c->d_lma_io;
+    HIP_TRY(hipMemcpyAsync(io, index, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(io + lst, points, (size_t)rows * width * height * 12, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(io + lst + tab, normals, (size_t)rows * width * height * 12, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipEventRecord(c->ev_start, c->stream));
+    HIP_TRY(launch_lma_gather(gather_args(width, height, rows, n, (const uint32_t*)io, (const float*)(io + lst), (const float*)(io + lst + tab),
+                                          cw, (float*)(io + lst + 2 * tab), (float*)(io + lst + 2 * tab + out)), c->stream));
+    HIP_TRY(hipEventRecord(c->ev_stop, c->stream));
+    c->ev_recorded = true; c->ms_summed = false;
+    HIP_TRY(hipMemcpyAsync(out_points, io + lst + 2 * tab, (size_t)rows * slots * 12, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(out_normals, io + lst + 2 * tab + out, (size_t)rows * slots * 12, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return MI_OK;
+}
+
+static int check_merge_args(const char* who, uint32_t width, uint32_t height, uint32_t n, const uint32_t* index, const float* mean,
+                            const float* m2_round, uint32_t round_samples, const float* image, const float* m2, const uint32_t* counts) {
+    if (!index || !mean || !m2_round || !image || !m2 || !counts)
+        return fail(MI_ERR_INVALID, "%s: index, mean, m2_round, image, m2 and counts are required", who);
+    MI_TRY(check_lma_size(who, width, height));
+    if (round_samples == 0 || round_samples > 65535u) return fail(MI_ERR_INVALID, "%s: round_samples %u is not in 1 .. 65535", who, round_samples);
+    return MI_OK;
+}
+
+static LmaListArgs merge_args(uint32_t width, uint32_t height, uint32_t n, const uint32_t* d_index, const float* d_mean, const float* d_m2_round,
+                              uint32_t round_samples, float* d_image, float* d_m2, uint32_t* d_counts) {
+    LmaListArgs a{};
+    a.index = d_index; a.n = n; a.width = width; a.height = height;
+    a.mean = d_mean; a.m2_round = d_m2_round; a.image = d_image; a.m2 = d_m2; a.counts = d_counts; a.round_samples = round_samples;
+    return a;
+}
+
+extern "C" int mi_lightmap_merge_device(mi_ctx* c, uint32_t width, uint32_t height, uint32_t n, const uint32_t* index, const float* mean,
+                                        const float* m2_round, uint32_t round_samples, float* image, float* m2, uint32_t* counts,
+                                        void* stream) {
+    MI_TRY(check_merge_args("mi_lightmap_merge_device", width, height, n, index, mean, m2_round, round_samples, image, m2, counts));
+    if (!c) return fail(MI_ERR_INVALID, "ctx is NULL");
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipEventRecord(c->ev_start, (hipStream_t)stream));
+    if (n) HIP_TRY(launch_lma_merge(merge_args(width, height, n, index, mean, m2_round, round_samples, image, m2, counts), (hipStream_t)stream));
+    HIP_TRY(hipEventRecord(c->ev_stop, (hipStream_t)stream));
+    c->ev_recorded = true; c->ms_summed = false;
+    return MI_OK;
+}
+
+extern "C" int mi_lightmap_merge(mi_ctx* c, uint32_t width, uint32_t height, uint32_t n, const uint32_t* index, const float* mean,
+                                 const float* m2_round, uint32_t round_samples, float* image, float* m2, uint32_t* counts) {
+    MI_TRY(check_merge_args("mi_lightmap_merge", width, height, n, index, mean, m2_round, round_samples, image, m2, counts));
+    {   // one lane per entry: a texel listed twice would be merged by two lanes at once
+        std::vector<uint32_t> seen;
+        seen.reserve(n);
+        for (uint32_t i = 0; i < n; i++) if (index[i] < (uint64_t)width * height) seen.push_back(index[i]);
+        std::sort(seen.begin(), seen.end());
+        const auto dup = std::adjacent_find(seen.begin(), seen.end());
+        if (dup != seen.end()) return fail(MI_ERR_INVALID, "mi_lightmap_merge: the list holds texel %u twice", *dup);
+    }
+    if (!c) return fail(MI_ERR_INVALID, "ctx is NULL");
+    HIP_TRY(hipSetDevice(c->device));
+    // the list, the round's two tables, the three planes
+    const size_t npix = (size_t)width * height, lst = up256((size_t)n * 4), rnd = up256((size_t)n * 12), img = up256(npix * 12);
+    MI_TRY(ensure(&c->d_lma_io, &c->lma_io_bytes, lst + 2 * rnd + 2 * img + up256(npix * 4)));
+    char* const io = (char*)c->d_lma_io;
+    char* const d_img = io + lst + 2 * rnd;
+    HIP_TRY(hipMemcpyAsync(io, index, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(io + lst, mean, (size_t)n * 12, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(io + lst + rnd, m2_round, (size_t)n * 12, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(d_img, image, npix * 12, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(d_img + img, m2, npix * 12, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(d_img + 2 * img, counts, npix * 4, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipEventRecord(c->ev_start, c->stream));
+    if (n) HIP_TRY(launch_lma_merge(merge_args(width, height, n, (const uint32_t*)io, (const float*)(io + lst), (const float*)(io + lst + rnd),
+                                               round_samples, (float*)d_img, (float*)(d_img + img), (uint32_t*)(d_img + 2 * img)), c->stream));
+    HIP_TRY(hipEventRecord(c->ev_stop, c->stream));
+    c->ev_recorded = true; c->ms_summed = false;
+    HIP_TRY(hipMemcpyAsync(image, d_img, npix * 12, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(m2, d_img + img, npix * 12, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(counts, d_img + 2 * img, npix * 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return MI_OK;
+}
+
+// The whole bake: mi_bake_lightmap_moments' body for round 0, then per round select, gather, the moments render of the compact table and
+// merge, all on the context's stream, the planes never leaving the device; one word (the list's length) comes back per round.
+extern "C" int mi_bake_lightmap_adaptive(mi_ctx* c, const mi_camera_desc* cam, const mi_render_opts* opts, const mi_mesh* mesh, uint32_t flags,
+                                         float offset, const mi_lightmap_adaptive* adaptive, uint32_t* out_counts, float* out_m2,
+                                         float* out_rgb_f32, uint8_t* out_rgb_u8, uint32_t* out_sig, int32_t* out_triangle, mi_stats* stats) {
+    const char* const who = "mi_bake_lightmap_adaptive";
+    if (!out_m2 || !out_counts) return fail(MI_ERR_INVALID, "%s: out_m2 and out_counts are required", who);
+    if (!adaptive) return fail(MI_ERR_INVALID, "%s: adaptive is NULL", who);
+    const mi_lightmap_adaptive ad = *adaptive;
+    if (ad.first_samples < 2 || ad.first_samples > 65535u)
+        return fail(MI_ERR_INVALID, "%s: first_samples %u is not in 2 .. 65535", who, ad.first_samples);
+    if (ad.round_samples == 0 || ad.round_samples > 65535u)
+        return fail(MI_ERR_INVALID, "%s: round_samples %u is not in 1 .. 65535", who, ad.round_samples);
+    if ((uint64_t)ad.first_samples + (uint64_t)ad.max_rounds * ad.round_samples > (1ull << 24))
+        return fail(MI_ERR_INVALID, "%s: first_samples + max_rounds * round_samples exceeds 2^24 (a count must stay exact in f32)", who);
+    if (!(ad.target_rel >= 0.0f) || !(ad.target_abs >= 0.0f))
+        return fail(MI_ERR_INVALID, "%s: target_rel and target_abs must be >= 0 and not NaN", who);
+    if (!c) return fail(MI_ERR_INVALID, "ctx is NULL");
+    if (!cam) return fail(MI_ERR_INVALID, "%s: cam is NULL", who);
+    // round 0: mi_bake_lightmap_moments at first_samples (every refusal of that call happens in here, before anything is launched)
+    mi_camera_desc cam0 = *cam;
+    cam0.aa_sample_count = ad.first_samples;
+    mi_stats st0;
+    MI_TRY(bake_lightmap(who, c, &cam0, opts, mesh, flags, offset, nullptr, nullptr, out_sig, out_triangle, &st0, out_m2));
+    const uint32_t W = cam->screen_width, H = cam->screen_height;
+    const size_t n = (size_t)W * H, img = up256(n * 3 * sizeof(float)), pln = up256(n * 4);
+    const bool jitter = (flags & MI_LM_JITTER) != 0;
+    // the running planes: mean, m2, the centre table's normals and points, the counts, the bytes
+    MI_TRY(ensure(&c->d_lma_bake, &c->lma_bake_bytes, 4 * img + pln + up256(n * 3)));
+    char* const b = (char*)c->d_lma_bake;
+    float* const d_mean = (float*)b; float* const d_m2 = (float*)(b + img);
+    float* const d_cn = (float*)(b + 2 * img); float* const d_cp = (float*)(b + 3 * img);
+    uint32_t* const d_counts = (uint32_t*)(b + 4 * img); uint8_t* const d_u8 = (uint8_t*)(b + 4 * img + pln);
+    const size_t m2_plane = (size_t)tile_grid(&cam0, 1).padded * kTilePixels * 3;        // render_image un-permuted the moments there
+    HIP_TRY(hipEventRecord(c->ev_t0, c->stream));
+    HIP_TRY(hipMemcpyAsync(d_mean, c->d_image, n * 12, hipMemcpyDeviceToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(d_m2, (const float*)c->d_m2 + m2_plane, n * 12, hipMemcpyDeviceToDevice, c->stream));
+    HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)d_counts, (int)ad.first_samples, n, c->stream));
+    uint64_t samples = st0.samples;
+    float kernel_ms = st0.kernel_ms;
+    if (ad.max_rounds > 0) {
+        mi_mesh dev;
+        MI_TRY(upload_lm_mesh(c, mesh, &dev));
+        MI_TRY(lightmap_texels_device(c, &dev, W, H, 1, 0, opts->seed, offset, d_cp, d_cn, nullptr, c->stream, true));
+        const uint32_t cap = (uint32_t)std::min<size_t>(kLmaMaxList, n);
+        MI_TRY(ensure(&c->d_lma_list, &c->lma_list_bytes, 256 + (size_t)cap * 4));
+        uint32_t* const d_count = (uint32_t*)c->d_lma_list; uint32_t* const d_list = (uint32_t*)((char*)c->d_lma_list + 256);
+        for (uint32_t r = 1; r <= ad.max_rounds; r++) {
+            MI_TRY(lightmap_select_device(c, W, H, d_mean, d_m2, d_counts, d_cn, ad.target_rel, ad.target_abs, cap, d_list, d_count, nullptr,
+                                          c->stream, false));
+            uint32_t count = 0;
+            HIP_TRY(hipMemcpyAsync(&count, d_count, 4, hipMemcpyDeviceToHost, c->stream));
+            HIP_TRY(hipStreamSynchronize(c->stream));
+            if (count == 0) break;
+            const uint32_t nsel = std::min(count, cap), cw = kLmaCompactWidth, ch = (nsel + cw - 1) / cw, rows = jitter ? ad.round_samples : 1u;
+            const size_t slots = (size_t)cw * ch;
+            const float* d_sp = d_cp; const float* d_sn = d_cn;
+            if (jitter) {           // a fresh table of the whole atlas, in the table buffer round 0 is done with
+                const size_t bytes = (size_t)rows * n * 3 * sizeof(float);
+                MI_TRY(ensure(&c->d_rays, &c->rays_bytes, 2 * bytes));
+                float* d_jp = (float*)c->d_rays; float* d_jn = (float*)((char*)c->d_rays + bytes);
+                MI_TRY(lightmap_texels_device(c, &dev, W, H, rows, MI_LM_JITTER, opts->seed + r, offset, d_jp, d_jn, nullptr, c->stream, true));
+                d_sp = d_jp; d_sn = d_jn;
+            }
+            mi_camera_desc camr = *cam;
+            camr.screen_width = cw; camr.screen_height = ch; camr.aa_sample_count = ad.round_samples;
+            const TileGrid g = tile_grid(&camr, 1);
+            // the round's compact tables, its compact results (mean, moments) and their two [ch][cw][3] planes
+            const size_t tab = up256((size_t)rows * slots * 12), cmp = up256((size_t)g.padded * kTilePixels * 12), rpl = up256(slots * 12);
+            MI_TRY(ensure(&c->d_lma_round, &c->lma_round_bytes, 2 * tab + 2 * cmp + 2 * rpl));
+            char* const q = (char*)c->d_lma_round;
+            float* const d_tp = (float*)q; float* const d_tn = (float*)(q + tab);
+            float* const d_rc = (float*)(q + 2 * tab); float* const d_rm = (float*)(q + 2 * tab + cmp);
+            float* const d_pmean = (float*)(q + 2 * tab + 2 * cmp); float* const d_pm2 = (float*)(q + 2 * tab + 2 * cmp + rpl);
+            HIP_TRY(launch_lma_gather(gather_args(W, H, rows, nsel, d_list, d_sp, d_sn, cw, d_tp, d_tn), c->stream));
+            mi_render_opts o = *opts;
+            o.seed = opts->seed + r; o.want_signature = 0;
+            const RayTable table = { d_tp, d_tn, rows, kTablePoints, nullptr, d_rm };
+            const mi_camera_desc tc = table_camera(&camr);
+            mi_stats st;
+            MI_TRY(render_tiles(c, &tc, &o, d_rc, nullptr, c->stream, &st, nullptr, &table));
+            HIP_TRY(launch_unpermute(d_rc, d_pmean, cw, ch, g.tx, 1, g.padded, c->stream));
+            HIP_TRY(launch_unpermute(d_rm, d_pm2, cw, ch, g.tx, 1, g.padded, c->stream));
+            HIP_TRY(launch_lma_merge(merge_args(W, H, nsel, d_list, d_pmean, d_pm2, ad.round_samples, d_mean, d_m2, d_counts), c->stream));
+            HIP_TRY(hipStreamSynchronize(c->stream));
+            float ms = 0.0f;
+            HIP_TRY(hipEventElapsedTime(&ms, c->ev_start, c->ev_stop));
+            kernel_ms += ms; samples += st.samples;
+        }
+    }
+    HIP_TRY(hipMemcpyAsync(out_m2, d_m2, n * 12, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(out_counts, d_counts, n * 4, hipMemcpyDeviceToHost, c->stream));
+    if (out_rgb_f32) HIP_TRY(hipMemcpyAsync(out_rgb_f32, d_mean, n * 12, hipMemcpyDeviceToHost, c->stream));
+    if (out_rgb_u8) {
+        HIP_TRY(launch_tonemap(d_mean, d_u8, (uint32_t)n, 1.0f / cam->gamma, c->stream));
+        HIP_TRY(hipMemcpyAsync(out_rgb_u8, d_u8, n * 3, hipMemcpyDeviceToHost, c->stream));
+    }
+    HIP_TRY(hipEventRecord(c->ev_t1, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (stats) {
+        float ms = 0.0f;
+        HIP_TRY(hipEventElapsedTime(&ms, c->ev_t0, c->ev_t1));
+        *stats = st0;
+        stats->samples = samples; stats->kernel_ms = kernel_ms; stats->total_ms = st0.total_ms + ms;
+    }
     return MI_OK;
 }
 

@@ -465,6 +465,44 @@ struct LmvArgs {
     float sigma_plane, reach, sigma_color, color_floor;
 };
 
+// ---- adaptive lightmap baking (mi_lightmap_select / _gather / _merge, mi_bake_lightmap_adaptive; pt_kernels.hip "lma_*") ----
+// tracing.py lightmap_select as four passes: lmv_init_counts (the variance of the mean per texel from the texel's own count; a further
+// form of lmv_init, which mi_lightmap_finish_var_counts runs as well), lma_mark (the blur, the threshold, one flag per texel and the number
+// of flags of each block of kLmaBlock consecutive texels), lma_scan (the exclusive prefix of the block counts, the total) and lma_fill
+// (every block writes its texels' numbers at its offset, ascending).  lma_gather and lma_merge are lightmap_gather and lightmap_merge,
+// one lane per slot / per list entry.  The list is the only value an address is made from, and every entry is tested against W * H first.
+constexpr uint32_t kLmaBlock = 1024;             // texels per block of lma_mark / lma_fill (16 waves)
+struct LmaArgs {
+    const float*    image;           // [H][W][3] the bake's mean (lma_mark: the luminance)
+    const float*    normals;         // [H][W][3] the centre table: all-zero = empty texel
+    const float*    var;             // [H][W] lmv_init_counts' result (lma_mark)
+    float*          error;           // [H][W] or nullptr: sd (lma_mark)
+    uint8_t*        flags;           // [H][W] 1 = selected (lma_mark writes, lma_fill reads)
+    uint32_t*       block_counts;    // [blocks] (lma_mark writes, lma_scan reads)
+    uint32_t*       block_offsets;   // [blocks] (lma_scan writes, lma_fill reads)
+    uint32_t*       out_index;       // [capacity] (lma_fill)
+    uint32_t*       out_count;       // [1] (lma_scan)
+    uint32_t width, height, blocks, capacity;
+    float target_rel, target_abs;
+};
+struct LmaListArgs {
+    const uint32_t* index;           // [n] texel numbers; an entry >= width * height is skipped
+    uint32_t n, width, height;
+    // lma_gather
+    const float*    points;          // [rows][H][W][3]
+    const float*    normals;         // [rows][H][W][3]
+    float*          out_points;      // [rows][slots][3]
+    float*          out_normals;     // [rows][slots][3]
+    uint32_t rows, slots;            // slots = ch * cw
+    // lma_merge
+    const float*    mean;            // [n][3] the round's mean, slot i for entry i
+    const float*    m2_round;        // [n][3]
+    float*          image;           // [H][W][3] in / out
+    float*          m2;              // [H][W][3] in / out
+    uint32_t*       counts;          // [H][W] in / out
+    uint32_t round_samples;
+};
+
 // ---- irradiance volumes (mi_probe_volume_sample; pt_kernels.hip "pv_*") ----
 // tracing.py probe_volume_sample: pv_prepare turns every probe's 27 SH coefficients into one 112-byte record (the coefficients times the
 // cosine-lobe constants K_k, then the validity as 0.0 / 1.0: 28 floats, seven 16-byte loads), pv_sample interpolates the eight records

@@ -4430,4 +4430,173 @@ hipError_t launch_lmv_atrous(const LmvArgs& a, hipStream_t stream) {
     return hipGetLastError();
 }
 
+// ---------------------------------------------------------------- adaptive lightmap baking (mi_lightmap_select / _gather / _merge)
+// tracing.py lightmap_select, lightmap_gather and lightmap_merge on the device.  Pure f32, the helpers' operations in the helpers' order
+// (no fused multiply-add: the pragma above; IEEE division and square root), nothing summed across threads but integer counts, no atomics:
+// the list and the merged planes are the helpers' bit for bit and do not depend on scheduling.  No address depends on a table value but
+// through the list, whose entries are tested against W * H before they are used.
+
+// lmv_init with the texel's own count n: v_c = fmaxf(0, m2_c - mean_c mean_c) / (float)(n - 1), V = (v_r + v_g) + v_b; a covered texel
+// with n < 2 gets +inf (few_inf: mi_lightmap_select, "no information") or +0.0 (mi_lightmap_finish_var_counts); empty texels +0.0
+__global__ __launch_bounds__(kBlock) void lmv_init_counts(const LmvArgs a, const uint32_t* __restrict__ counts, uint32_t few_inf) {
+    const size_t n = (size_t)a.width * a.height, i = (size_t)blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n) return;
+    float V = 0.0f;
+    if (lmf_covered(a.normals[3 * i], a.normals[3 * i + 1], a.normals[3 * i + 2])) {
+        const uint32_t cnt = counts[i];
+        if (cnt >= 2u) {
+            const float d = (float)(cnt - 1u);
+            float v[3];
+            for (int k = 0; k < 3; k++) {
+                const float mean = a.src[3 * i + k];
+                v[k] = fmaxf(0.0f, a.m2[3 * i + k] - mean * mean) / d;
+            }
+            V = (v[0] + v[1]) + v[2];
+        } else {
+            V = few_inf ? __builtin_inff() : 0.0f;
+        }
+    }
+    a.var_out[i] = V;
+}
+
+// One lane per texel, kLmaBlock consecutive texels per block: lmv_blur's sums in lmv_blur's order, sd = sqrtf(bs / bw), the texel's flag
+// sd > target_rel * lum + target_abs, and the number of flags in the block (a ballot per wave, the sixteen wave counts through LDS).
+__global__ __launch_bounds__(kLmaBlock) void lma_mark(const LmaArgs a) {
+    __shared__ uint32_t s_wave[kLmaBlock / 64];
+    const size_t n = (size_t)a.width * a.height, i = (size_t)blockIdx.x * kLmaBlock + threadIdx.x;
+    bool sel = false;
+    if (i < n) {
+        const int W = (int)a.width, H = (int)a.height;
+        const int y = (int)(i / a.width), x = (int)(i - (size_t)y * a.width);
+        float sd = 0.0f;
+        if (lmf_covered(a.normals[3 * i], a.normals[3 * i + 1], a.normals[3 * i + 2])) {
+            const float G3[3] = { 0.25f, 0.5f, 0.25f };
+            float bs = 0.0f, bw = 0.0f;
+#pragma unroll
+            for (int dy = -1; dy <= 1; dy++) {
+#pragma unroll
+                for (int dx = -1; dx <= 1; dx++) {
+                    const int qx = x + dx, qy = y + dy;
+                    if (qx < 0 || qx >= W || qy < 0 || qy >= H) continue;
+                    const size_t j = (size_t)qy * W + qx;
+                    if (!lmf_covered(a.normals[3 * j], a.normals[3 * j + 1], a.normals[3 * j + 2])) continue;
+                    const float g = G3[dy + 1] * G3[dx + 1];
+                    bs = bs + g * a.var[j];
+                    bw = bw + g;
+                }
+            }
+            sd = sqrtf(bs / bw);
+            const float lum = (fabsf(a.image[3 * i]) + fabsf(a.image[3 * i + 1])) + fabsf(a.image[3 * i + 2]);
+            const float thr = a.target_rel * lum + a.target_abs;
+            sel = sd > thr;
+        }
+        if (a.error) a.error[i] = sd;
+        a.flags[i] = sel ? (uint8_t)1 : (uint8_t)0;
+    }
+    const unsigned long long m = __builtin_amdgcn_ballot_w64(sel);
+    if ((threadIdx.x & 63u) == 0u) s_wave[threadIdx.x >> 6] = (uint32_t)__popcll(m);
+    __syncthreads();
+    if (threadIdx.x == 0u) {
+        uint32_t total = 0;
+        for (uint32_t k = 0; k < kLmaBlock / 64; k++) total += s_wave[k];
+        a.block_counts[blockIdx.x] = total;
+    }
+}
+
+// Exclusive prefix of the block counts (one block, the pattern of lm_scan); the total to *out_count
+__global__ __launch_bounds__(1024) void lma_scan(const LmaArgs a) {
+    __shared__ uint32_t s_sum[1024];
+    const uint32_t nb = a.blocks, per = (nb + 1023u) / 1024u;
+    const uint32_t lo = min(nb, threadIdx.x * per), hi = min(nb, lo + per);
+    uint32_t sum = 0;
+    for (uint32_t i = lo; i < hi; i++) sum += a.block_counts[i];
+    s_sum[threadIdx.x] = sum;
+    __syncthreads();
+    for (uint32_t d = 1; d < 1024u; d <<= 1) {              // inclusive scan of the threads' sums
+        const uint32_t v = threadIdx.x >= d ? s_sum[threadIdx.x - d] : 0u;
+        __syncthreads();
+        s_sum[threadIdx.x] += v;
+        __syncthreads();
+    }
+    uint32_t run = s_sum[threadIdx.x] - sum;
+    for (uint32_t i = lo; i < hi; i++) { a.block_offsets[i] = run; run += a.block_counts[i]; }
+    if (threadIdx.x == 1023u) *a.out_count = s_sum[1023];
+}
+
+// Every block writes its flagged texels' numbers at its offset, ascending: the waves before this one through LDS, the lanes before this
+// one from the ballot.  Positions at or beyond `capacity` are not written.
+__global__ __launch_bounds__(kLmaBlock) void lma_fill(const LmaArgs a) {
+    __shared__ uint32_t s_wave[kLmaBlock / 64];
+    const size_t n = (size_t)a.width * a.height, i = (size_t)blockIdx.x * kLmaBlock + threadIdx.x;
+    const bool sel = i < n && a.flags[i] != 0;
+    const unsigned long long m = __builtin_amdgcn_ballot_w64(sel);
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    if (lane == 0u) s_wave[wave] = (uint32_t)__popcll(m);
+    __syncthreads();
+    if (!sel) return;
+    uint32_t pos = a.block_offsets[blockIdx.x];
+    for (uint32_t k = 0; k < wave; k++) pos += s_wave[k];
+    pos += (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
+    if (pos < a.capacity) a.out_index[pos] = (uint32_t)i;
+}
+
+// One lane per slot of the compact table: entry `slot` of the list into every row, zeros (the empty-texel mark) behind the list's end
+// and for an entry outside the atlas
+__global__ __launch_bounds__(kBlock) void lma_gather(const LmaListArgs a) {
+    const size_t slot = (size_t)blockIdx.x * kBlock + threadIdx.x;
+    if (slot >= a.slots) return;
+    const size_t npix = (size_t)a.width * a.height;
+    size_t texel = 0;
+    bool live = slot < a.n;
+    if (live) {
+        const uint32_t idx = a.index[slot];
+        live = idx < npix;
+        texel = live ? idx : 0;
+    }
+    for (uint32_t r = 0; r < a.rows; r++) {
+        const size_t src = 3 * ((size_t)r * npix + texel), dst = 3 * ((size_t)r * a.slots + slot);
+        for (int k = 0; k < 3; k++) {
+            a.out_points[dst + k] = live ? a.points[src + k] : 0.0f;
+            a.out_normals[dst + k] = live ? a.normals[src + k] : 0.0f;
+        }
+    }
+}
+
+// One lane per list entry: x = ((float)n0 * x + (float)S' * x') / (float)(n0 + S') for the six values of the texel, counts = n0 + S'
+__global__ __launch_bounds__(kBlock) void lma_merge(const LmaListArgs a) {
+    const size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x;
+    if (i >= a.n) return;
+    const uint32_t idx = a.index[i];
+    if (idx >= (size_t)a.width * a.height) return;
+    const uint32_t n0 = a.counts[idx];
+    const float f0 = (float)n0, fs = (float)a.round_samples, ft = (float)(n0 + a.round_samples);
+    for (int k = 0; k < 3; k++) {
+        const size_t at = 3 * (size_t)idx + k;
+        a.image[at] = (f0 * a.image[at] + fs * a.mean[3 * i + k]) / ft;
+        a.m2[at] = (f0 * a.m2[at] + fs * a.m2_round[3 * i + k]) / ft;
+    }
+    a.counts[idx] = n0 + a.round_samples;
+}
+
+hipError_t launch_lmv_init_counts(const LmvArgs& a, const uint32_t* counts, bool few_inf, hipStream_t stream) {
+    const size_t n = (size_t)a.width * a.height;
+    hipLaunchKernelGGL(lmv_init_counts, dim3((uint32_t)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, stream, a, counts, few_inf ? 1u : 0u);
+    return hipGetLastError();
+}
+// lma_mark, lma_scan, lma_fill: a.blocks = ceil(W H / kLmaBlock)
+hipError_t launch_lma_select(const LmaArgs& a, hipStream_t stream) {
+    hipLaunchKernelGGL(lma_mark, dim3(a.blocks), dim3(kLmaBlock), 0, stream, a);
+    hipLaunchKernelGGL(lma_scan, dim3(1), dim3(1024), 0, stream, a);
+    if (a.capacity > 0) hipLaunchKernelGGL(lma_fill, dim3(a.blocks), dim3(kLmaBlock), 0, stream, a);
+    return hipGetLastError();
+}
+hipError_t launch_lma_gather(const LmaListArgs& a, hipStream_t stream) {
+    hipLaunchKernelGGL(lma_gather, dim3((uint32_t)(((size_t)a.slots + kBlock - 1) / kBlock)), dim3(kBlock), 0, stream, a);
+    return hipGetLastError();
+}
+hipError_t launch_lma_merge(const LmaListArgs& a, hipStream_t stream) {
+    hipLaunchKernelGGL(lma_merge, dim3((a.n + kBlock - 1) / kBlock), dim3(kBlock), 0, stream, a);
+    return hipGetLastError();
+}
+
 }  // namespace pt

@@ -280,6 +280,53 @@ struct Scene : Intersectable {                         // tracing.rs:213-218; `i
         return out;
     }
 
+    // The adaptive bake, through mi_bake_lightmap_adaptive: every texel gets ad.first_samples samples, then up to ad.max_rounds rounds of
+    // ad.round_samples more go to the texels whose blurred standard error exceeds ad.target_rel * luminance + ad.target_abs.  Returns the
+    // merged f32 mean [H][W][3]; `m2` takes the merged means of squares, `counts` the samples behind each texel [H][W]: what
+    // finish_lightmap_var_counts takes.  `image` takes the tone-mapped bytes.
+    std::vector<float> bake_lightmap_adaptive(const mi_mesh& mesh, uint32_t width, uint32_t height, const mi_lightmap_adaptive& ad,
+                                              std::vector<float>& m2, std::vector<uint32_t>& counts, bool jitter = true, float offset = 1e-3f,
+                                              uint32_t seed = 1, int device = 0, mi_stats* stats = nullptr, RgbImage* image = nullptr) const {
+        mi_camera_desc cam = camera.flatten();
+        cam.screen_width = width; cam.screen_height = height; cam.aa_sample_count = ad.first_samples;
+        std::vector<float> mean((size_t)width * height * 3);
+        m2.resize(mean.size());
+        counts.resize((size_t)width * height);
+        if (image) { image->width = width; image->height = height; image->data.resize(mean.size()); }
+        mi_render_opts opts{}; opts.seed = seed; opts.rank = 0; opts.world = 1;
+        with_context(device, [&](mi_ctx* ctx) {
+            return mi_bake_lightmap_adaptive(ctx, &cam, &opts, &mesh, jitter ? MI_LM_JITTER : 0u, offset, &ad, counts.data(), m2.data(),
+                                             mean.data(), image ? image->data.data() : nullptr, nullptr, nullptr, stats);
+        });
+        return mean;
+    }
+
+    // finish_lightmap_var for an adaptive bake, through mi_lightmap_finish_var_counts: `counts` [H][W] holds every texel's own sample
+    // count in the place of `samples`.  A static member.
+    static std::vector<float> finish_lightmap_var_counts(const std::vector<float>& image, const std::vector<float>& m2,
+                                                         const std::vector<uint32_t>& counts, const std::vector<float>& points,
+                                                         const std::vector<float>& normals, uint32_t width, uint32_t height,
+                                                         uint32_t levels = 3, uint32_t normal_power_log2 = 5, float sigma_plane = INFINITY,
+                                                         float reach = INFINITY, float sigma_color = 8.0f, float color_floor = 1e-6f,
+                                                         uint32_t dilate = 4, int device = 0, std::vector<float>* var = nullptr,
+                                                         std::vector<uint8_t>* valid = nullptr) {
+        const size_t n = (size_t)width * height;
+        if (image.size() != n * 3 || m2.size() != n * 3 || points.size() != n * 3 || normals.size() != n * 3 || counts.size() != n)
+            throw std::runtime_error("mi_rt: image, m2, points and normals must all be [H][W][3] and counts [H][W]");
+        std::vector<float> out(n * 3);
+        if (var) var->resize(n);
+        if (valid) valid->resize(n);
+        mi_ctx* ctx = nullptr;
+        mi_check(mi_ctx_create(device, &ctx));
+        const int rc = mi_lightmap_finish_var_counts(ctx, width, height, image.data(), m2.data(), counts.data(), points.data(), normals.data(),
+                                                     levels, normal_power_log2, sigma_plane, reach, sigma_color, color_floor, dilate,
+                                                     out.data(), var ? var->data() : nullptr, valid ? valid->data() : nullptr);
+        const std::string err = rc == MI_OK ? "" : mi_last_error();
+        mi_ctx_destroy(ctx);
+        if (rc != MI_OK) throw std::runtime_error("mi_rt: " + err);
+        return out;
+    }
+
     // Light probes through mi_render_probes: points is [rows_per_pixel][H][W][3], one probe position per pixel, rows_per_pixel = 1 or
     // camera.aa_sample_count.  Sample s of probe (x, y) leaves its point along rand_sphere_vec (Isotropic::scatter's direction,
     // materials.rs:158-166: uniform over the sphere), drawn on the GPU from the stream (seed, W * H + y * W + x, s); its path draws from

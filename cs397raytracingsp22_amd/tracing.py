@@ -725,15 +725,22 @@ def lightmap_finish_var(image, m2, samples, points, normals, levels: int = 3, no
     beside sw and sc the sum sv = sv + (w w) V_q: the texel becomes sc / sw, its variance sv / (sw sw).  color_floor = inf turns the
     colour weight off: the image is then lightmap_finish(sigma_color=inf)'s, bit for bit.
     `var` is the final V for covered texels and +0.0 elsewhere, dilated texels included; levels == 0 gives the masked copy and the
-    initial V.  Non-finite values spoil the texels within Chebyshev radius 2 (2^levels - 1) + levels + dilate, and no others."""
+    initial V.  Non-finite values spoil the texels within Chebyshev radius 2 (2^levels - 1) + levels + dilate, and no others.
+    `samples` may also be an [H, W] integer array, the per-texel counts of an adaptive bake (the definition of
+    mi_lightmap_finish_var_counts): the initial variance then divides by the texel's own n - 1, and a texel with n < 2 starts from
+    V = +0.0.  A plane that holds one value S everywhere gives the result of samples = S, bit for bit."""
     f32 = np.float32
     img, P, N = check_finish_tables(image, points, normals)
     M2 = np.ascontiguousarray(m2, f32)
     if M2.shape != img.shape:
         raise ValueError(f"m2 must have the image's shape {img.shape}, got {M2.shape}")
-    S = int(samples)
-    if not 2 <= S <= 65535:
-        raise ValueError(f"samples must be in 2 .. 65535, got {samples}")
+    counts = None
+    if np.ndim(samples) != 0:                # a plane of per-texel counts (mi_lightmap_finish_var_counts)
+        counts = check_counts_plane(samples, img.shape[:2])
+    else:
+        S = int(samples)
+        if not 2 <= S <= 65535:
+            raise ValueError(f"samples must be in 2 .. 65535, got {samples}")
     levels, npow, dilate = int(levels), int(normal_power_log2), int(dilate)
     if not (0 <= levels <= 8 and 0 <= npow <= 7 and 0 <= dilate <= 256):
         raise ValueError("levels must be in 0 .. 8, normal_power_log2 in 0 .. 7 and dilate in 0 .. 256")
@@ -751,8 +758,11 @@ def lightmap_finish_var(image, m2, samples, points, normals, levels: int = 3, no
     covered = (N[..., 0] != 0) | (N[..., 1] != 0) | (N[..., 2] != 0)
     cur = np.where(covered[..., None], img, zero)
     with np.errstate(all="ignore"):
-        v3 = np.fmax(zero, M2 - cur * cur) / f32(S - 1)
-        V = np.where(covered, (v3[..., 0] + v3[..., 1]) + v3[..., 2], zero)
+        if counts is None:
+            v3 = np.fmax(zero, M2 - cur * cur) / f32(S - 1)
+            V = np.where(covered, (v3[..., 0] + v3[..., 1]) + v3[..., 2], zero)
+        else:
+            V = _lmv_init_counts(cur, M2, counts, covered, zero)
         for level in range(levels):
             s = 1 << level
             fs = f32(s)
@@ -820,6 +830,154 @@ def lightmap_finish_var(image, m2, samples, points, normals, levels: int = 3, no
                 cur[y, x] = total / f32(count)
                 valid[y, x] = True
     return cur, np.ascontiguousarray(V, f32), valid
+
+
+def check_counts_plane(counts, shape):
+    """An [H, W] array of per-texel sample counts as contiguous uint32: an integer dtype, the given shape, values in 0 .. 2^32 - 1"""
+    c = np.asarray(counts)
+    if c.dtype.kind not in "iu":
+        raise ValueError(f"counts must be an integer array, got {c.dtype}")
+    if c.shape != tuple(shape):
+        raise ValueError(f"counts must have shape {tuple(shape)}, got {c.shape}")
+    if c.size and (int(c.min()) < 0 or int(c.max()) > 0xffffffff):
+        raise ValueError("counts must lie in 0 .. 2^32 - 1")
+    return np.ascontiguousarray(c, np.uint32)
+
+
+def _lmv_init_counts(cur, M2, counts, covered, few):
+    """lightmap_finish_var's initial variance with the texel's own n: v_c = max(0, m2_c - mean_c mean_c) / (n - 1), `few` where n < 2"""
+    f32 = np.float32
+    n = counts.astype(np.int64)
+    d = np.maximum(n - 1, 1).astype(f32)
+    v3 = np.fmax(f32(0.0), M2 - cur * cur) / d[..., None]
+    V = np.where(n >= 2, (v3[..., 0] + v3[..., 1]) + v3[..., 2], few)
+    return np.where(covered, V, f32(0.0)).astype(f32)
+
+
+def _check_index_list(index):
+    idx = np.asarray(index)
+    if idx.ndim != 1 or idx.dtype.kind not in "iu":
+        raise ValueError(f"index must be a 1-d integer array, got {idx.dtype} {idx.shape}")
+    if idx.size and (int(idx.min()) < 0 or int(idx.max()) > 0xffffffff):
+        raise ValueError("index entries must lie in 0 .. 2^32 - 1")
+    return np.ascontiguousarray(idx, np.uint32)
+
+
+def lightmap_select(image, m2, counts, normals, target_rel: float, target_abs: float, capacity: Optional[int] = None):
+    """The texels of a bake that are worth further samples (numpy only).  This is the DEFINITION of mi_lightmap_select, which equals it
+    bit for bit.  `image` and `m2` [H, W, 3] f32 are the bake's running mean and mean of squares, `counts` [H, W] integers the samples
+    behind each texel, `normals` [H, W, 3] the centre table (an all-zero normal: an empty texel, never selected).
+    Per covered texel with n = counts: n >= 2 gives v_c = max(0, m2_c - mean_c mean_c) / (n - 1), V = (v_r + v_g) + v_b, the variance of
+    the mean (lightmap_finish_var's initial variance with the texel's own n); n < 2 gives V = +inf: no information, always selected.
+    Empty texels +0.0.  Then sd = sqrt(bs / bw) with lightmap_finish_var's blur (the nine step-1 neighbours that lie in the image and are
+    covered, dy outer, dx inner, g = G3[dy] G3[dx]): a dark texel whose few samples all missed the light is judged with its neighbours.
+    With lum = (|mean_r| + |mean_g|) + |mean_b| the texel is selected when sd > target_rel * lum + target_abs.  Everything is f32, one
+    rounding per operation.  Returns (index, count, error): the selected texel numbers y * W + x ascending as uint32, the lowest
+    `capacity` of them (None: all); count, the number of selected texels whatever the capacity; error [H, W] f32, sd (+0.0 on empty
+    texels).  A non-finite texel changes the selection within Chebyshev distance 1 only."""
+    f32 = np.float32
+    img, M2, N = check_finish_tables(image, m2, normals)
+    cnt = check_counts_plane(counts, img.shape[:2])
+    trel, tabs = f32(target_rel), f32(target_abs)
+    if not (trel >= 0 and tabs >= 0):
+        raise ValueError("target_rel and target_abs must be >= 0 and not NaN")
+    H, W = img.shape[:2]
+    cap = H * W if capacity is None else int(capacity)
+    if not 0 <= cap <= 0xffffffff:
+        raise ValueError(f"capacity must be in 0 .. 2^32 - 1, got {capacity}")
+    zero = f32(0.0)
+    G3 = (f32(0.25), f32(0.5), f32(0.25))
+    covered = (N[..., 0] != 0) | (N[..., 1] != 0) | (N[..., 2] != 0)
+    with np.errstate(all="ignore"):
+        # lightmap_finish_var's initial variance and blur, restated here: this helper's own text is what its mutant tests edit
+        n = cnt.astype(np.int64)
+        d = np.maximum(n - 1, 1).astype(f32)
+        v3 = np.fmax(zero, M2 - img * img) / d[..., None]
+        V = np.where(n >= 2, (v3[..., 0] + v3[..., 1]) + v3[..., 2], f32(np.inf))
+        V = np.where(covered, V, zero).astype(f32)
+        vb, nb = np.pad(V, 1), np.pad(N, ((1, 1), (1, 1), (0, 0)))
+        bs = np.zeros((H, W), f32)
+        bw = np.zeros((H, W), f32)
+        for dy, dx in _LMV_BLUR:
+            ys, xs = 1 + dy, 1 + dx
+            vq, nq = vb[ys:ys + H, xs:xs + W], nb[ys:ys + H, xs:xs + W]
+            btake = covered & ((nq[..., 0] != 0) | (nq[..., 1] != 0) | (nq[..., 2] != 0))
+            g = G3[dy + 1] * G3[dx + 1]
+            bs = np.where(btake, bs + g * vq, bs)
+            bw = np.where(btake, bw + g, bw)
+        sd = np.where(covered, np.sqrt(bs / bw), zero).astype(f32)
+        lum = (np.abs(img[..., 0]) + np.abs(img[..., 1])) + np.abs(img[..., 2])
+        thr = trel * lum + tabs
+        selected = covered & (sd > thr)
+    index = np.flatnonzero(selected).astype(np.uint32)
+    return index[:cap], int(index.size), np.ascontiguousarray(sd, f32)
+
+
+def lightmap_gather(index, points, normals, cw: int):
+    """The compact point table of a list of texels (numpy only): the DEFINITION of mi_lightmap_gather.  `index` holds n texel numbers
+    y * W + x, `points` and `normals` are [rows, H, W, 3] (or [H, W, 3]) f32.  Returns (points, normals) [rows, ch, cw, 3] with
+    ch = ceil(n / cw): entry i goes to slot (i // cw, i % cw) of every row; the slots at or after n are all zero, the empty-texel mark
+    (render_points traces nothing for them), and so is the slot of an index >= W * H."""
+    idx = _check_index_list(index)
+    P, N = np.asarray(points), np.asarray(normals)
+    if P.dtype != np.float32 or N.dtype != np.float32:
+        raise ValueError(f"points and normals must be float32, got {P.dtype} and {N.dtype}")
+    if P.ndim == 3:
+        P = P[None]
+    if N.ndim == 3:
+        N = N[None]
+    if P.ndim != 4 or P.shape[3] != 3 or P.shape != N.shape:
+        raise ValueError(f"points and normals must be [rows, H, W, 3] arrays of one shape, got {P.shape} and {N.shape}")
+    rows, H, W = P.shape[:3]
+    if not (1 <= W <= 32768 and 1 <= H <= 32768 and 1 <= rows <= 65535):
+        raise ValueError(f"width and height must be in 1 .. 32768 and rows in 1 .. 65535, got {W} x {H} x {rows}")
+    cw, n = int(cw), int(idx.size)
+    if not 1 <= cw <= 32768:
+        raise ValueError(f"cw must be in 1 .. 32768, got {cw}")
+    ch = (n + cw - 1) // cw
+    if not 1 <= ch <= 32768:
+        raise ValueError(f"{n} entries at cw = {cw} give {ch} rows of slots: not in 1 .. 32768")
+    ok = idx < W * H
+    outs = []
+    for t in (P, N):
+        out = np.zeros((rows, ch * cw, 3), np.float32)
+        out[:, np.flatnonzero(ok)] = t.reshape(rows, H * W, 3)[:, idx[ok]]
+        outs.append(out.reshape(rows, ch, cw, 3))
+    return outs[0], outs[1]
+
+
+def lightmap_merge(index, mean, m2_round, round_samples: int, image, m2, counts):
+    """Merge a refinement round into a bake (numpy only): the DEFINITION of mi_lightmap_merge.  `index` lists n texels; `mean` and
+    `m2_round` hold, in their first n slots ([ch, cw, 3], or any shape of at least n triples), the mean and mean of squares of a round of
+    `round_samples` = S' samples of those texels; `image`, `m2` [H, W, 3] f32 and `counts` [H, W] are the bake so far.  For each listed
+    texel with count n0, per channel: image = (n0 * image + S' * mean') / (n0 + S') in f32, one rounding per operation, m2 likewise,
+    counts = n0 + S'.  Every other texel keeps its bits; an index >= W * H is skipped.  Returns new (image, m2, counts uint32).  A list
+    with duplicates is refused (the kernel runs one lane per entry)."""
+    f32 = np.float32
+    idx = _check_index_list(index)
+    img, M2, _ = check_finish_tables(image, m2, m2)
+    cnt = check_counts_plane(counts, img.shape[:2]).copy()
+    S = int(round_samples)
+    if not 1 <= S <= 65535:
+        raise ValueError(f"round_samples must be in 1 .. 65535, got {round_samples}")
+    n = int(idx.size)
+    mr, m2r = np.ascontiguousarray(mean, f32).reshape(-1), np.ascontiguousarray(m2_round, f32).reshape(-1)
+    if mr.size < 3 * n or m2r.size < 3 * n or mr.size % 3 or m2r.size % 3:
+        raise ValueError(f"mean and m2_round must hold at least {n} triples, got {mr.size} and {m2r.size} values")
+    H, W = img.shape[:2]
+    ok = idx < W * H
+    t = idx[ok].astype(np.int64)
+    if np.unique(t).size != t.size:
+        raise ValueError("index lists a texel twice")
+    img, M2 = img.copy().reshape(-1, 3), M2.copy().reshape(-1, 3)
+    n0_int = cnt.reshape(-1)[t].astype(np.int64)
+    n0, Sf, tot = n0_int.astype(f32)[:, None], f32(S), (n0_int + S).astype(f32)[:, None]
+    with np.errstate(all="ignore"):
+        for plane, new in ((img, mr), (M2, m2r)):
+            a, b = plane[t], new.reshape(-1, 3)[:n][ok]
+            plane[t] = (n0 * a + Sf * b) / tot
+    cnt.reshape(-1)[t] = ((n0_int + S) & 0xffffffff).astype(np.uint32)
+    return img.reshape(H, W, 3), M2.reshape(H, W, 3), cnt
 
 
 def equirect_dirs(lon, lat) -> np.ndarray:
@@ -1138,6 +1296,137 @@ class Context:
         abi.check(self._lib.mi_lightmap_finish_var_device(self._h, width, height, d_image, d_m2, samples, d_points, d_normals, levels,
                                                           normal_power_log2, sigma_plane, reach, sigma_color, color_floor, dilate,
                                                           d_out_image, d_out_var, d_out_valid, stream))
+
+    # ---- adaptive lightmap bake: select, gather, merge, the finish with counts, the whole bake ----
+    def lightmap_select(self, image, m2, counts, normals, target_rel: float, target_abs: float, capacity: Optional[int] = None,
+                        want_error: bool = True):
+        """mi_lightmap_select: the helper lightmap_select on the GPU, bit for bit.  Returns (index uint32 [min(count, capacity)], count,
+        error [H, W] f32 | None).  capacity None: W * H.  No scene is needed."""
+        N = np.asarray(normals)
+        img, M2, N = check_finish_tables(image, m2, N[0] if N.ndim == 4 and N.shape[0] == 1 else N)
+        cnt = check_counts_plane(counts, img.shape[:2])
+        H, W = img.shape[:2]
+        cap = H * W if capacity is None else int(capacity)
+        index = np.empty(min(cap, H * W), np.uint32)
+        count = C.c_uint32(0)
+        err = np.empty((H, W), np.float32) if want_error else None
+        abi.check(self._lib.mi_lightmap_select(self._h, W, H, img.ctypes.data, M2.ctypes.data, cnt.ctypes.data, N.ctypes.data, target_rel,
+                                               target_abs, cap, index.ctypes.data if index.size else None, C.addressof(count),
+                                               err.ctypes.data if err is not None else None))
+        return index[:min(count.value, cap)].copy(), int(count.value), err
+
+    def lightmap_select_device(self, width: int, height: int, d_image: int, d_m2: int, d_counts: int, d_normals: int, target_rel: float,
+                               target_abs: float, capacity: int, d_out_index: Optional[int], d_out_count: int,
+                               d_out_error: Optional[int] = None, stream: Optional[int] = None):
+        """mi_lightmap_select_device: the same for planes held on the device (raw pointers: [H, W, 3] f32 image, m2 and normals, [H, W]
+        u32 counts; outputs: `capacity` u32, one u32, an optional [H, W] f32 plane).  Queued on `stream`; entries at and behind
+        min(count, capacity) are not written."""
+        abi.check(self._lib.mi_lightmap_select_device(self._h, width, height, d_image, d_m2, d_counts, d_normals, target_rel, target_abs,
+                                                      capacity, d_out_index, d_out_count, d_out_error, stream))
+
+    def lightmap_gather(self, index, points, normals, cw: int = 1024):
+        """mi_lightmap_gather: the helper lightmap_gather on the GPU.  Returns the compact (points, normals) [rows, ch, cw, 3] f32."""
+        idx = _check_index_list(index)
+        P, N = (np.ascontiguousarray(t[None] if np.ndim(t) == 3 else t) for t in (points, normals))
+        if P.dtype != np.float32 or N.dtype != np.float32 or P.ndim != 4 or P.shape[3] != 3 or P.shape != N.shape:
+            raise ValueError("points and normals must be float32 [rows, H, W, 3] arrays of one shape")
+        rows, H, W = P.shape[:3]
+        cw = int(cw)
+        ch = (idx.size + cw - 1) // cw if cw > 0 else 0
+        cp = np.empty((rows, ch, max(cw, 0), 3), np.float32)
+        cn = np.empty((rows, ch, max(cw, 0), 3), np.float32)
+        abi.check(self._lib.mi_lightmap_gather(self._h, W, H, rows, idx.size, idx.ctypes.data, P.ctypes.data, N.ctypes.data, cw,
+                                               cp.ctypes.data, cn.ctypes.data))
+        return cp, cn
+
+    def lightmap_gather_device(self, width: int, height: int, rows: int, n: int, d_index: int, d_points: int, d_normals: int, cw: int,
+                               d_out_points: int, d_out_normals: int, stream: Optional[int] = None):
+        """mi_lightmap_gather_device: the same for a list and tables held on the device; the outputs are [rows, ceil(n / cw), cw, 3] f32."""
+        abi.check(self._lib.mi_lightmap_gather_device(self._h, width, height, rows, n, d_index, d_points, d_normals, cw, d_out_points,
+                                                      d_out_normals, stream))
+
+    def lightmap_merge(self, index, mean, m2_round, round_samples: int, image, m2, counts):
+        """mi_lightmap_merge: the helper lightmap_merge on the GPU, bit for bit.  Returns new (image, m2, counts uint32); the arguments
+        are not modified."""
+        idx = _check_index_list(index)
+        img, M2, _ = check_finish_tables(image, m2, m2)
+        img, M2 = img.copy(), M2.copy()
+        cnt = check_counts_plane(counts, img.shape[:2]).copy()
+        mr, m2r = np.ascontiguousarray(mean, np.float32).reshape(-1), np.ascontiguousarray(m2_round, np.float32).reshape(-1)
+        if mr.size < 3 * idx.size or m2r.size < 3 * idx.size:
+            raise ValueError(f"mean and m2_round must hold at least {idx.size} triples")
+        H, W = img.shape[:2]
+        abi.check(self._lib.mi_lightmap_merge(self._h, W, H, idx.size, idx.ctypes.data, mr.ctypes.data, m2r.ctypes.data, round_samples,
+                                              img.ctypes.data, M2.ctypes.data, cnt.ctypes.data))
+        return img, M2, cnt
+
+    def lightmap_merge_device(self, width: int, height: int, n: int, d_index: int, d_mean: int, d_m2_round: int, round_samples: int,
+                              d_image: int, d_m2: int, d_counts: int, stream: Optional[int] = None):
+        """mi_lightmap_merge_device: the same in place on planes held on the device.  Queued on `stream`."""
+        abi.check(self._lib.mi_lightmap_merge_device(self._h, width, height, n, d_index, d_mean, d_m2_round, round_samples, d_image, d_m2,
+                                                     d_counts, stream))
+
+    def lightmap_finish_var_counts(self, image, m2, counts, points, normals, levels: int = 3, normal_power_log2: int = 5,
+                                   sigma_plane: float = float("inf"), reach: float = float("inf"), sigma_color: float = 8.0,
+                                   color_floor: float = 1e-6, dilate: int = 4):
+        """mi_lightmap_finish_var_counts: lightmap_finish_var(samples=counts plane) on the GPU, bit for bit: the variance-guided finish of
+        an adaptive bake, whose texels have counts of their own.  Returns (out, var, valid) as lightmap_finish_var does."""
+        P, N = np.asarray(points), np.asarray(normals)
+        img, P, N = check_finish_tables(image, P[0] if P.ndim == 4 and P.shape[0] == 1 else P, N[0] if N.ndim == 4 and N.shape[0] == 1 else N)
+        M2 = np.ascontiguousarray(m2, np.float32)
+        if M2.shape != img.shape:
+            raise ValueError(f"m2 must have the image's shape {img.shape}, got {M2.shape}")
+        cnt = check_counts_plane(counts, img.shape[:2])
+        H, W = img.shape[:2]
+        out = np.empty((H, W, 3), np.float32)
+        var = np.empty((H, W), np.float32)
+        valid = np.empty((H, W), np.uint8)
+        abi.check(self._lib.mi_lightmap_finish_var_counts(self._h, W, H, img.ctypes.data, M2.ctypes.data, cnt.ctypes.data, P.ctypes.data,
+                                                          N.ctypes.data, levels, normal_power_log2, sigma_plane, reach, sigma_color,
+                                                          color_floor, dilate, out.ctypes.data, var.ctypes.data, valid.ctypes.data))
+        return out, var, valid.astype(bool)
+
+    def lightmap_finish_var_counts_device(self, width: int, height: int, d_image: int, d_m2: int, d_counts: int, d_points: int,
+                                          d_normals: int, d_out_image: int, d_out_var: Optional[int] = None,
+                                          d_out_valid: Optional[int] = None, levels: int = 3, normal_power_log2: int = 5,
+                                          sigma_plane: float = float("inf"), reach: float = float("inf"), sigma_color: float = 8.0,
+                                          color_floor: float = 1e-6, dilate: int = 4, stream: Optional[int] = None):
+        """mi_lightmap_finish_var_counts_device: lightmap_finish_var_device with a [H, W] u32 counts plane in the place of `samples`."""
+        abi.check(self._lib.mi_lightmap_finish_var_counts_device(self._h, width, height, d_image, d_m2, d_counts, d_points, d_normals,
+                                                                 levels, normal_power_log2, sigma_plane, reach, sigma_color, color_floor,
+                                                                 dilate, d_out_image, d_out_var, d_out_valid, stream))
+
+    def bake_lightmap_adaptive(self, cam: Camera, mesh, first_samples: int, round_samples: int, max_rounds: int, target_rel: float,
+                               target_abs: float, jitter: bool = True, offset: float = 1e-3, seed: int = 1, transform=None, want_f32=True,
+                               want_u8=True, want_sig=False, want_triangle=False, flags: int = 0, max_state_bytes: int = 0):
+        """mi_bake_lightmap_adaptive: bake_lightmap_moments at `first_samples`, then up to `max_rounds` rounds of `round_samples` further
+        samples for the texels lightmap_select picks with the two targets (cam.aa_sample_count is ignored).  Returns (counts [H, W]
+        uint32, m2, f32, u8, sig, triangle, stats): the merged mean and moments and the samples behind each texel; sig and triangle are
+        round 0's.  Bit for bit the composition of bake_lightmap_moments, lightmap_select, lightmap_gather, render_points_moments (seed
+        + r) and lightmap_merge."""
+        pod, keep = mesh_pod(mesh, transform)
+        cpod = cam.to_pod()
+        opts = abi.mi_render_opts(seed=seed, rank=0, world=1, variant=abi.MI_VARIANT_DEFAULT, want_signature=int(want_sig),
+                                  flags=flags, max_state_bytes=max_state_bytes)
+        ad = abi.mi_lightmap_adaptive(first_samples=first_samples, round_samples=round_samples, max_rounds=max_rounds,
+                                      target_rel=target_rel, target_abs=target_abs)
+        H, W = cam.screen_height, cam.screen_width
+        counts = np.empty((H, W), np.uint32)
+        m2 = np.empty((H, W, 3), np.float32)
+        f32 = np.empty((H, W, 3), np.float32) if want_f32 else None
+        u8 = np.empty((H, W, 3), np.uint8) if want_u8 else None
+        sig = np.empty((H, W), np.uint32) if want_sig else None
+        tri = np.empty((max(int(first_samples), 0) if jitter else 1, H, W), np.int32) if want_triangle else None
+        st = abi.mi_stats()
+        abi.check(self._lib.mi_bake_lightmap_adaptive(
+            self._h, C.byref(cpod), C.byref(opts), C.byref(pod), abi.MI_LM_JITTER if jitter else 0, offset, C.byref(ad),
+            counts.ctypes.data, m2.ctypes.data,
+            f32.ctypes.data if f32 is not None else None,
+            u8.ctypes.data if u8 is not None else None,
+            sig.ctypes.data if sig is not None else None,
+            tri.ctypes.data if tri is not None else None, C.byref(st)))
+        del keep
+        return counts, m2, f32, u8, sig, tri, st
 
     def probe_volume_sample(self, volume: "ProbeVolume", points, normals, flags: int = 0):
         """mi_probe_volume_sample: the helper probe_volume_sample on the GPU, bit for bit.  `volume` is a ProbeVolume, points and
@@ -1587,7 +1876,7 @@ class Scene:                         # tracing.rs:213-218
             ctx.close()
 
     def bake_lightmap(self, mesh, width: int, height: int, samples: int, jitter: bool = True, offset: float = 1e-3, seed: int = 1,
-                      device: int = 0, finish: Optional[dict] = None):
+                      device: int = 0, finish: Optional[dict] = None, adaptive: Optional[dict] = None):
         """The lightmap of `mesh` (a StaticMesh of this scene, or any objload.Mesh) in one call (mi_bake_lightmap): the RgbImage bytes
         [height, width, 3] u8 of its uv atlas, `samples` cosine-distributed gathers per texel, each from its own jittered position inside
         the texel (jitter) or all from the centre.  The atlas is rasterised, sampled and traced on the GPU: only the mesh goes up and the
@@ -1600,13 +1889,30 @@ class Scene:                         # tracing.rs:213-218
         A true "variance" key in `finish` selects the variance-guided finish: the bake also returns its second moments
         (mi_bake_lightmap_moments), the remaining keys are lightmap_finish_var's parameters (levels, normal_power_log2, sigma_plane,
         reach, sigma_color, color_floor, dilate), and the call returns (out, var [height, width] f32, valid) (mi_lightmap_finish_var).
-        Without the key, or with a false one, nothing changes."""
+        Without the key, or with a false one, nothing changes.
+        `adaptive` (None: a uniform bake, as above) is a dict with round_samples, max_rounds, target_rel and target_abs, and optionally
+        first_samples (default: `samples`): the bake is mi_bake_lightmap_adaptive, which gives every texel first_samples samples and
+        then up to max_rounds rounds of round_samples more to the texels lightmap_select picks.  Without `finish` the call returns the
+        bytes of the merged mean; with a fixed finish that is applied to the merged mean; with finish={"variance": True, ...} the
+        finish takes the bake's per-texel counts (mi_lightmap_finish_var_counts)."""
         from dataclasses import replace
         cam = replace(self.camera, screen_width=int(width), screen_height=int(height), aa_sample_count=int(samples))
         check_point_table(cam, np.zeros((height, width, 3), np.float32), np.zeros((height, width, 3), np.float32))
         ctx = Context(device)
         try:
             ctx.upload(self.flatten())
+            if adaptive is not None:
+                ad = dict(adaptive)
+                ad.setdefault("first_samples", int(samples))
+                counts, m2, f32, u8, _, _, _ = ctx.bake_lightmap_adaptive(cam, mesh, jitter=jitter, offset=offset, seed=seed,
+                                                                          want_f32=finish is not None, want_u8=finish is None, **ad)
+                if finish is None:
+                    return u8
+                finish = dict(finish)
+                points, normals, _ = ctx.lightmap_texels(mesh, int(width), int(height), rows=1, offset=offset, want_triangle=False)
+                if finish.pop("variance", False):
+                    return ctx.lightmap_finish_var_counts(f32, m2, counts, points, normals, **finish)
+                return ctx.lightmap_finish(f32, points, normals, **finish)
             if finish is None:
                 _, u8, _, _, _ = ctx.bake_lightmap(cam, mesh, jitter=jitter, offset=offset, seed=seed, want_f32=False, want_u8=True)
                 return u8

@@ -632,6 +632,104 @@ int  mi_lightmap_finish_var_device(mi_ctx* ctx, uint32_t width, uint32_t height,
                                    float sigma_plane, float reach, float sigma_color, float color_floor, uint32_t dilate, float* out_image,
                                    float* out_var, uint8_t* out_valid, void* stream);
 
+/* ---- adaptive lightmap bake: further samples where the variance asks (added within ABI version 5: detect by symbol lookup) ----
+ * A bake spends the same aa_sample_count on a texel in direct light, converged after 16 samples, as on one lit only through two bounces.
+ *   The second moments say which texels are which; these calls act on it without touching the wavefront pipeline: a refinement round is
+ *   an ordinary mi_render_points_moments render of a COMPACT point table that holds the selected texels only.  New are the selection, the
+ *   compaction, the merge, and a finish that takes per-texel counts.  The numpy helpers lightmap_select, lightmap_gather and lightmap_merge
+ *   (Python) are the definitions; the results equal them BIT FOR BIT: pure f32, every operation one of + - * /, sqrtf, fabsf, fmaxf,
+ *   comparisons and exact int-to-float conversions, in the order written here, no fused multiply-add, IEEE division and square root, no
+ *   float atomics, nothing summed across threads but integer counts: no result depends on scheduling.  No scene is needed.  No address
+ *   depends on a table value except through the index list, whose entries are tested against W * H before use.
+ * mi_lightmap_select: `image` and `m2` [H][W][3] f32 are a bake's mean and mean of squares, `counts` [H][W] u32 the samples behind each
+ *   texel, `normals` [H][W][3] the centre table (mi_lightmap_finish's coverage rule: an all-zero normal is an empty texel, never
+ *   selected); target_rel and target_abs are >= 0 (+inf is legal).
+ *   Per covered texel with n = counts: n >= 2 gives v_c = fmaxf(0, m2_c - mean_c * mean_c) / (float)(n - 1), V = (v_r + v_g) + v_b
+ *   (mi_lightmap_finish_var's initial variance with the texel's own n); n < 2 gives V = +inf: the texel has no information and is always
+ *   selected.  Empty texels V = +0.0.  Then sd = sqrtf(bs / bw) with mi_lightmap_finish_var's blur, sums and order (the nine step-1
+ *   neighbours that lie in the image and are covered): a dark texel whose few samples all missed the light is not judged converged
+ *   beside bright neighbours.  With lum = (fabsf(mean_r) + fabsf(mean_g)) + fabsf(mean_b) the texel is selected when
+ *   sd > target_rel * lum + target_abs (one multiply, one add).
+ *   out_index [capacity] u32: the selected texel numbers y * W + x, ascending; out_count [1] u32: the number of selected texels, which
+ *   may exceed capacity: the list then holds the lowest `capacity` of them.  Entries at and behind min(out_count, capacity) are not
+ *   written.  out_index may be NULL when capacity is 0.  out_error [H][W] f32 (may be NULL): sd, +0.0 on empty texels.
+ *   A NaN or infinite texel of image or m2 changes the selection within Chebyshev distance 1 only.  Kernels: lmv_init_counts, lma_mark
+ *   (blur, threshold and the count of every block of 1024 consecutive texels, by wave ballot), lma_scan (the prefix of the block counts),
+ *   lma_fill (every block writes its texels at its offset).
+ * mi_lightmap_gather: `index` [n] lists texels; `points` and `normals` are [rows][H][W][3] f32 (rows in 1 .. 65535); the outputs are the
+ *   compact tables [rows][ch][cw][3], ch = ceil(n / cw), cw in 1 .. 32768, ch in 1 .. 32768 (so n >= 1).  Entry i goes to slot
+ *   (i / cw, i % cw) of every row; the slots at or behind n are all zero, the empty-texel mark: mi_render_points traces nothing for them.
+ *   An index >= W * H gives an empty slot; the table is not read through it.
+ * mi_lightmap_merge: `mean` and `m2_round` [ch][cw][3] f32 (their first n slots are read) are the mean and mean of squares of a round
+ *   of round_samples = S' (1 .. 65535) samples of the n listed texels; `image`, `m2` [H][W][3] f32 and `counts` [H][W] u32 are read AND
+ *   written.  For each listed texel with count n0, per channel: image = ((float)n0 * image + (float)S' * mean') / (float)(n0 + S'), m2
+ *   likewise, counts = n0 + S'.  Every other texel keeps its bits; an index >= W * H is skipped; n == 0 does nothing.  One lane per
+ *   entry: a list with a texel twice gives unspecified values for that texel only (the device form) and is MI_ERR_INVALID in the host
+ *   form, which can check.  Counts above 2^24 give unspecified values for that texel.
+ * mi_lightmap_finish_var_counts: mi_lightmap_finish_var letter for letter with `counts` [H][W] u32 in place of `samples`: the initial
+ *   variance divides by (float)(n - 1) with the texel's own n, and n < 2 gives V = +0.0 there.  A plane that holds one value S
+ *   everywhere gives mi_lightmap_finish_var's result for samples = S, bit for bit.  The device form refuses outputs that overlap counts
+ *   as well.
+ * MI_ERR_INVALID (each with a message, checked before the context, nothing is launched): a NULL pointer other than out_error, out_var,
+ *   out_valid (and out_index at capacity 0); width or height of 0 or above 32768; a target that is NaN or negative; rows, cw, ch or
+ *   round_samples outside their ranges; mi_lightmap_finish_var's for the finish.
+ * Scratch: one f32 plane, one u8 plane and two words per 1024 texels for select, in a buffer the context owns (grown on demand, freed
+ *   with the context, never the buffers mi_reserve sized; MI_ERR_OOM); mi_last_kernel_ms reports the sum of the call's kernels.
+ * The forms without _device take HOST pointers, block, and pass their tables through a buffer the context owns; the _device forms take
+ *   DEVICE pointers on ctx's device, queue on `stream` and do not synchronise, except when they have to grow their scratch. */
+int  mi_lightmap_select(mi_ctx* ctx, uint32_t width, uint32_t height, const float* image, const float* m2, const uint32_t* counts,
+                        const float* normals, float target_rel, float target_abs, uint32_t capacity, uint32_t* out_index,
+                        uint32_t* out_count, float* out_error);
+int  mi_lightmap_select_device(mi_ctx* ctx, uint32_t width, uint32_t height, const float* image, const float* m2, const uint32_t* counts,
+                               const float* normals, float target_rel, float target_abs, uint32_t capacity, uint32_t* out_index,
+                               uint32_t* out_count, float* out_error, void* stream);
+int  mi_lightmap_gather(mi_ctx* ctx, uint32_t width, uint32_t height, uint32_t rows, uint32_t n, const uint32_t* index,
+                        const float* points, const float* normals, uint32_t cw, float* out_points, float* out_normals);
+int  mi_lightmap_gather_device(mi_ctx* ctx, uint32_t width, uint32_t height, uint32_t rows, uint32_t n, const uint32_t* index,
+                               const float* points, const float* normals, uint32_t cw, float* out_points, float* out_normals,
+                               void* stream);
+int  mi_lightmap_merge(mi_ctx* ctx, uint32_t width, uint32_t height, uint32_t n, const uint32_t* index, const float* mean,
+                       const float* m2_round, uint32_t round_samples, float* image, float* m2, uint32_t* counts);
+int  mi_lightmap_merge_device(mi_ctx* ctx, uint32_t width, uint32_t height, uint32_t n, const uint32_t* index, const float* mean,
+                              const float* m2_round, uint32_t round_samples, float* image, float* m2, uint32_t* counts, void* stream);
+int  mi_lightmap_finish_var_counts(mi_ctx* ctx, uint32_t width, uint32_t height, const float* image, const float* m2,
+                                   const uint32_t* counts, const float* points, const float* normals, uint32_t levels,
+                                   uint32_t normal_power_log2, float sigma_plane, float reach, float sigma_color, float color_floor,
+                                   uint32_t dilate, float* out_image, float* out_var, uint8_t* out_valid);
+int  mi_lightmap_finish_var_counts_device(mi_ctx* ctx, uint32_t width, uint32_t height, const float* image, const float* m2,
+                                          const uint32_t* counts, const float* points, const float* normals, uint32_t levels,
+                                          uint32_t normal_power_log2, float sigma_plane, float reach, float sigma_color, float color_floor,
+                                          uint32_t dilate, float* out_image, float* out_var, uint8_t* out_valid, void* stream);
+
+/* mi_bake_lightmap_adaptive: mi_bake_lightmap_moments with refinement rounds.  HOST pointers, blocking.  out_counts [H][W] u32 and out_m2
+ *   are required; cam->aa_sample_count is ignored.
+ * Round 0 is mi_bake_lightmap_moments with aa_sample_count = first_samples and seed opts->seed; every texel's count is first_samples.
+ * Round r = 1 .. max_rounds: mi_lightmap_select on the device with capacity 2^25; the one count is read back, and 0 ends the bake;
+ *   mi_lightmap_gather with cw = 1024, without MI_LM_JITTER from the centre table (mi_lightmap_texels with rows = 1), with MI_LM_JITTER
+ *   from a fresh mi_lightmap_texels table of round_samples rows made with seed opts->seed + r; the compact table is rendered exactly as
+ *   mi_render_points_moments does for a camera of 1024 x ch with aa_sample_count = round_samples and seed opts->seed + r (u32 wrap: a
+ *   different seed per round keeps each round's samples independent of all earlier ones under the existing stream keys); mi_lightmap_merge.
+ * Outputs: the merged mean (out_rgb_f32), the merged out_m2 and out_counts; out_rgb_u8 is mi_tonemap_device of the merged mean; out_sig
+ *   and out_triangle are round 0's; stats->samples counts the slots of all rounds (W * H * first_samples + 1024 * ch * round_samples
+ *   per round), kernel_ms and total_ms are sums.  The result is BIT FOR BIT what the public calls above and mi_render_points_moments
+ *   give when composed in that order: nothing is hidden in this call.
+ * Selection looks at the running estimate, so the merged mean is consistent, not strictly unbiased: a texel whose first samples
+ *   happen to agree stops early with whatever they agree on.  This is a documented property, not a defect; the blur of the variance and
+ *   the n < 2 rule bound it.
+ * MI_ERR_INVALID: every refusal of mi_bake_lightmap_moments, and first_samples < 2, round_samples == 0, either above 65535,
+ *   first_samples + max_rounds * round_samples > 2^24 (a count stays exact in f32), a NaN or negative target, a NULL adaptive, out_m2
+ *   or out_counts.  Nothing is launched.  The planes, the list and the compact tables live in buffers the context owns. */
+typedef struct mi_lightmap_adaptive {
+    uint32_t first_samples;     /* round 0: samples of every texel (2 .. 65535)           */
+    uint32_t round_samples;     /* samples a selected texel gets per round (1 .. 65535)   */
+    uint32_t max_rounds;        /* refinement rounds at most (0: mi_bake_lightmap_moments) */
+    float    target_rel;        /* a texel is done when sd <= target_rel * lum + target_abs */
+    float    target_abs;
+} mi_lightmap_adaptive;         /* 20 bytes */
+int  mi_bake_lightmap_adaptive(mi_ctx* ctx, const mi_camera_desc* cam, const mi_render_opts* opts, const mi_mesh* mesh, uint32_t flags,
+                               float offset, const mi_lightmap_adaptive* adaptive, uint32_t* out_counts, float* out_m2,
+                               float* out_rgb_f32, uint8_t* out_rgb_u8, uint32_t* out_sig, int32_t* out_triangle, mi_stats* stats);
+
 /* ---- light probes: SH L2 radiance probes with the directions drawn on the GPU (added within ABI version 5: detect by symbol lookup) ----
  * mi_render_points without normals and with a second output.  One "pixel" is one probe, a point in free space; its samples leave it in
  *   directions uniform over the whole sphere, and beside their mean the call returns the radiance field's projection onto the nine real

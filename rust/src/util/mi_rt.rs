@@ -41,6 +41,10 @@ use std::os::raw::{c_char, c_int, c_void};
 #[repr(C, align(8))] #[derive(Clone, Copy)] pub struct mi_probe_volume {
     pub lo: [f32; 3], pub hi: [f32; 3], pub counts: [u32; 3], pub flags: u32, pub sh: *const f32, pub valid: *const u8,
 }
+// The parameters of mi_bake_lightmap_adaptive.  The C layout, 20 bytes; align(4) spells out the alignment its fields give it.
+#[repr(C, align(4))] #[derive(Clone, Copy)] pub struct mi_lightmap_adaptive {
+    pub first_samples: u32, pub round_samples: u32, pub max_rounds: u32, pub target_rel: f32, pub target_abs: f32,
+}
 pub enum mi_ctx {}
 pub enum mi_multi {}
 pub const MI_OPT_NO_TILE_MASKS: u32 = 1; pub const MI_OPT_REFERENCE_WALK: u32 = 2; pub const MI_OPT_TWO_STAGE: u32 = 4; pub const MI_OPT_NO_LIST_TREE: u32 = 8; pub const MI_OPT_NO_FINAL_CULL: u32 = 16;
@@ -151,6 +155,38 @@ extern "C" {
                                          points: *const f32, normals: *const f32, levels: u32, normal_power_log2: u32,
                                          sigma_plane: f32, reach: f32, sigma_color: f32, color_floor: f32, dilate: u32, out_image: *mut f32,
                                          out_var: *mut f32, out_valid: *mut u8, stream: *mut c_void) -> c_int;
+    // adaptive lightmap bake (added within ABI 5): the texels whose variance asks for more samples (ascending texel numbers, their count,
+    // the error plane or null), their compact point tables [rows][ceil(n / cw)][cw][3], the merge of a round into the running planes, the
+    // variance-guided finish with per-texel counts, and the bake that composes them with mi_render_points_moments
+    pub fn mi_lightmap_select(ctx: *mut mi_ctx, width: u32, height: u32, image: *const f32, m2: *const f32, counts: *const u32,
+                              normals: *const f32, target_rel: f32, target_abs: f32, capacity: u32, out_index: *mut u32,
+                              out_count: *mut u32, out_error: *mut f32) -> c_int;
+    pub fn mi_lightmap_select_device(ctx: *mut mi_ctx, width: u32, height: u32, image: *const f32, m2: *const f32, counts: *const u32,
+                                     normals: *const f32, target_rel: f32, target_abs: f32, capacity: u32, out_index: *mut u32,
+                                     out_count: *mut u32, out_error: *mut f32, stream: *mut c_void) -> c_int;
+    pub fn mi_lightmap_gather(ctx: *mut mi_ctx, width: u32, height: u32, rows: u32, n: u32, index: *const u32,
+                              points: *const f32, normals: *const f32, cw: u32, out_points: *mut f32, out_normals: *mut f32) -> c_int;
+    pub fn mi_lightmap_gather_device(ctx: *mut mi_ctx, width: u32, height: u32, rows: u32, n: u32, index: *const u32,
+                                     points: *const f32, normals: *const f32, cw: u32, out_points: *mut f32, out_normals: *mut f32,
+                                     stream: *mut c_void) -> c_int;
+    pub fn mi_lightmap_merge(ctx: *mut mi_ctx, width: u32, height: u32, n: u32, index: *const u32, mean: *const f32,
+                             m2_round: *const f32, round_samples: u32, image: *mut f32, m2: *mut f32, counts: *mut u32) -> c_int;
+    pub fn mi_lightmap_merge_device(ctx: *mut mi_ctx, width: u32, height: u32, n: u32, index: *const u32, mean: *const f32,
+                                    m2_round: *const f32, round_samples: u32, image: *mut f32, m2: *mut f32, counts: *mut u32,
+                                    stream: *mut c_void) -> c_int;
+    pub fn mi_lightmap_finish_var_counts(ctx: *mut mi_ctx, width: u32, height: u32, image: *const f32, m2: *const f32,
+                                         counts: *const u32, points: *const f32, normals: *const f32, levels: u32,
+                                         normal_power_log2: u32, sigma_plane: f32, reach: f32, sigma_color: f32, color_floor: f32,
+                                         dilate: u32, out_image: *mut f32, out_var: *mut f32, out_valid: *mut u8) -> c_int;
+    pub fn mi_lightmap_finish_var_counts_device(ctx: *mut mi_ctx, width: u32, height: u32, image: *const f32, m2: *const f32,
+                                                counts: *const u32, points: *const f32, normals: *const f32, levels: u32,
+                                                normal_power_log2: u32, sigma_plane: f32, reach: f32, sigma_color: f32, color_floor: f32,
+                                                dilate: u32, out_image: *mut f32, out_var: *mut f32, out_valid: *mut u8,
+                                                stream: *mut c_void) -> c_int;
+    pub fn mi_bake_lightmap_adaptive(ctx: *mut mi_ctx, cam: *const mi_camera_desc, opts: *const mi_render_opts, mesh: *const mi_mesh, flags: u32,
+                                     offset: f32, adaptive: *const mi_lightmap_adaptive, out_counts: *mut u32, out_m2: *mut f32,
+                                     out_rgb_f32: *mut f32, out_rgb_u8: *mut u8, out_sig: *mut u32, out_triangle: *mut i32,
+                                     stats: *mut mi_stats) -> c_int;
     // light probes (added within ABI 5): points is [rows_per_pixel][H][W][3]; out_sh [H][W][9][3], d_compact_sh [tiles_padded][1024][27]
     pub fn mi_render_probes(ctx: *mut mi_ctx, cam: *const mi_camera_desc, opts: *const mi_render_opts,
                             points: *const f32, rows_per_pixel: u32, out_sh: *mut f32,

@@ -282,6 +282,55 @@ impl Scene {
         (out, var, valid)
     }
 
+    /// The adaptive bake (mi_bake_lightmap_adaptive): every texel gets `first_samples` samples, then up to `max_rounds` rounds of
+    /// `round_samples` more go to the texels whose blurred standard error exceeds `target_rel` times their luminance plus `target_abs`.
+    /// Returns the merged mean, the merged means of squares and the samples behind each texel: what finish_lightmap_var_counts takes.
+    pub fn bake_lightmap_adaptive(&self, mesh: &mi_rt::mi_mesh, width: u32, height: u32, first_samples: u32, round_samples: u32, max_rounds: u32,
+                                  target_rel: f32, target_abs: f32, jitter: bool, offset: f32, seed: u32) -> (Vec<[f32; 3]>, Vec<[f32; 3]>, Vec<u32>) {
+        let mut cam = self.camera.flatten();
+        cam.screen_width = width;
+        cam.screen_height = height;
+        cam.aa_sample_count = first_samples;
+        let opts = mi_rt::mi_render_opts { seed: seed, rank: 0, world: 1, ..Default::default() };
+        let ad = mi_rt::mi_lightmap_adaptive { first_samples: first_samples, round_samples: round_samples, max_rounds: max_rounds,
+                                               target_rel: target_rel, target_abs: target_abs };
+        let flags = if jitter { mi_rt::MI_LM_JITTER } else { 0 };
+        let n = width as usize * height as usize;
+        let mut mean = vec![[0.0f32; 3]; n];
+        let mut m2 = vec![[0.0f32; 3]; n];
+        let mut counts = vec![0u32; n];
+        let (pmean, pm2, pcounts) = (mean.as_mut_ptr() as *mut f32, m2.as_mut_ptr() as *mut f32, counts.as_mut_ptr());
+        self.with_gpu_scene(|ctx| unsafe {
+            mi_rt::mi_bake_lightmap_adaptive(ctx, &cam, &opts, mesh, flags, offset, &ad, pcounts, pm2, pmean, std::ptr::null_mut(), std::ptr::null_mut(), std::ptr::null_mut(), std::ptr::null_mut())
+        });
+        (mean, m2, counts)
+    }
+
+    /// finish_lightmap_var for an adaptive bake (mi_lightmap_finish_var_counts): `counts` holds every texel's own sample count in the
+    /// place of `samples`.  Returns the finished image, its per-texel variance and the valid mask.
+    pub fn finish_lightmap_var_counts(image: &[[f32; 3]], m2: &[[f32; 3]], counts: &[u32], points: &[[f32; 3]], normals: &[[f32; 3]], width: u32,
+                                      height: u32, levels: u32, normal_power_log2: u32, sigma_plane: f32, reach: f32, sigma_color: f32,
+                                      color_floor: f32, dilate: u32) -> (Vec<[f32; 3]>, Vec<f32>, Vec<u8>) {
+        let n = width as usize * height as usize;
+        assert!(image.len() == n && m2.len() == n && counts.len() == n && points.len() == n && normals.len() == n,
+                "mi_rt: image, m2, counts, points and normals must hold height * width texels");
+        let mut out = vec![[0.0f32; 3]; n];
+        let mut var = vec![0.0f32; n];
+        let mut valid = vec![0u8; n];
+        unsafe {
+            let mut ctx = std::ptr::null_mut();
+            assert_eq!(mi_rt::mi_ctx_create(0, &mut ctx), 0, "{}", mi_rt::last_error());
+            let rc = mi_rt::mi_lightmap_finish_var_counts(ctx, width, height, image.as_ptr() as *const f32, m2.as_ptr() as *const f32,
+                                                          counts.as_ptr(), points.as_ptr() as *const f32, normals.as_ptr() as *const f32,
+                                                          levels, normal_power_log2, sigma_plane, reach, sigma_color, color_floor, dilate,
+                                                          out.as_mut_ptr() as *mut f32, var.as_mut_ptr(), valid.as_mut_ptr());
+            let msg = mi_rt::last_error();
+            mi_rt::mi_ctx_destroy(ctx);
+            assert_eq!(rc, 0, "{}", msg);
+        }
+        (out, var, valid)
+    }
+
     /// Light probes (mi_render_probes): `points` holds `rows_per_pixel` x height x width probe positions, row-major ([row][y][x]),
     /// rows_per_pixel = 1 or camera.aa_sample_count.  Sample s of probe (x, y) leaves its point along rand_sphere_vec (what
     /// Isotropic::scatter returns: uniform over the sphere), drawn on the GPU from the stream (seed, width * height + y * width + x, s),

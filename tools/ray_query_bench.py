@@ -106,6 +106,11 @@ if ROOT not in sys.path:
 from cs397raytracingsp22_amd import Context, abi, scenes  # noqa: E402
 
 
+# --mode adaptive (appended to the notes above): times mi_bake_lightmap_adaptive (16 first samples, 2 rounds of 16, the relative target the
+# median of round 0's error over its luminance) on the cube in the one-light box and on the drone, atlas --atlas-sizes[0] squared, against
+# uniform mi_bake_lightmap_moments bakes at the adaptive run's own slots per texel and at first + max_rounds * round_samples; reports every
+# bake's mean absolute and mean relative error over the covered texels against a uniform bake at 16 x the larger count with another seed, and the HIP-event
+# times of select, gather and merge on resident tables beside the kernel time of the round's render.  --atlas-bakes timed bakes per row.
 def pinhole_rays(cam):
     """Rays through the pixel centres of `cam` (tracing.rs:160-163,187-191 without jitter and lens), row-major."""
     W, H = cam.screen_width, cam.screen_height
@@ -858,6 +863,105 @@ def variance_rows(ctx, sizes, calls, warmup):
     return rows
 
 
+def adaptive_rows(ctx, size, bakes, first=16, per_round=16, rounds=2):
+    """--mode adaptive (the module's docstring)"""
+    from dataclasses import replace
+    from cs397raytracingsp22_amd import Lambertian, Scene, StaticMesh, cgmath, lightmap_select, objload
+    dev = torch.device("cuda:0")
+    offset = float(np.float32(1e-3))
+    rows = []
+    drone_scene = scenes.config4(size, size, first, 10)
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    import gzip
+    with gzip.open(os.path.join(root, "tests", "golden", "obj", "cube.obj.gz"), "rt") as fh:
+        cube = objload.load_obj_text(fh.read())[0]
+    xf = cgmath.mul(cgmath.from_translation((0.2, 1.6, -0.3)), cgmath.from_angle_y(25.0), cgmath.from_scale(0.8))
+    box = StaticMesh(cube, Lambertian(albedo=(0.7, 0.7, 0.7)), [None] * 5, xf)
+    box_scene = Scene(replace(drone_scene.camera, path_depth=6), scenes.cornell_walls() + [box])
+    for name, sc, mesh in (("cube-in-box", box_scene, box), ("drone", drone_scene, drone_scene.objects[-1])):
+        cam = replace(sc.camera, screen_width=size, screen_height=size, aa_sample_count=first)
+        ctx.upload(sc.flatten())
+        # the targets: the median of the first round's error over its luminance, so that round 1 takes about half of the lit texels
+        m2_0, f32_0, _, _, _, _ = ctx.bake_lightmap_moments(cam, mesh, offset=offset, seed=1, want_u8=False)
+        _, normals, _ = ctx.lightmap_texels(mesh, size, size, rows=1, offset=offset, want_triangle=False)
+        covered = (normals[0] != 0).any(axis=-1)
+        counts_0 = np.full((size, size), first, np.uint32)
+        _, _, err = lightmap_select(f32_0, m2_0, counts_0, normals[0], 0.0, 0.0)
+        lum = np.abs(f32_0).sum(axis=-1)
+        lit = covered & (lum > 0) & (err > 0)
+        trel = float(np.float32(np.median(err[lit] / lum[lit])))
+        total_b = first + rounds * per_round
+        ref = ctx.bake_lightmap_moments(replace(cam, aa_sample_count=16 * total_b), mesh, offset=offset, seed=977, want_u8=False)[1]
+
+        def error(img):            # mean absolute error per channel, and the mean of the texel's error over its luminance (+ 1e-3)
+            d = np.abs(img.astype(np.float64) - ref)
+            return {"mean_abs_error": round(float(d[covered].mean()), 6),
+                    "mean_rel_error": round(float((d.sum(axis=-1) / (np.abs(ref).sum(axis=-1) + 1e-3))[covered].mean()), 6)}
+
+        ms, st = [], None
+        for k in range(bakes + 1):
+            counts, _, f32_a, _, _, _, st = ctx.bake_lightmap_adaptive(cam, mesh, first, per_round, rounds, trel, 0.0, offset=offset, seed=1,
+                                                                       want_u8=False)
+            if k:
+                ms.append(st.total_ms)
+        total_a = max(first, int(round(st.samples / (size * size))))
+        base = {"mode": "adaptive", "mesh": name, "width": size, "height": size, "first_samples": first, "round_samples": per_round,
+                "max_rounds": rounds, "target_rel": round(trel, 5), "covered_share": round(float(covered.mean()), 4), "bakes": bakes}
+        rows.append(dict(base, query="mi_bake_lightmap_adaptive", ms_median=round(float(np.median(ms)), 3), ms_min=round(float(np.min(ms)), 3),
+                         ms_max=round(float(np.max(ms)), 3), slots=int(st.samples), slots_per_texel=round(st.samples / (size * size), 3),
+                         mean_count_covered=round(float(counts[covered].mean()), 3), refined_share=round(float((counts[covered] > first).mean()), 4),
+                         **error(f32_a)))
+        print(json.dumps(rows[-1]), flush=True)
+        for what, spp in (("the adaptive run's slots per texel", total_a), ("first + max_rounds * round_samples", total_b)):
+            ms_u, f32_u = [], None
+            for k in range(bakes + 1):
+                _, f32_u, _, _, _, st_u = ctx.bake_lightmap_moments(replace(cam, aa_sample_count=spp), mesh, offset=offset, seed=1, want_u8=False)
+                if k:
+                    ms_u.append(st_u.total_ms)
+            rows.append(dict(base, query=f"mi_bake_lightmap_moments at {spp} samples ({what})", ms_median=round(float(np.median(ms_u)), 3),
+                             ms_min=round(float(np.min(ms_u)), 3), ms_max=round(float(np.max(ms_u)), 3), **error(f32_u)))
+            print(json.dumps(rows[-1]), flush=True)
+        # the bookkeeping of round 1 beside its render: device forms on resident tables, HIP events
+        index, count, _ = ctx.lightmap_select(f32_0, m2_0, counts_0, normals[0], trel, 0.0, want_error=False)
+        jp, jn, _ = ctx.lightmap_texels(mesh, size, size, rows=per_round, jitter=True, seed=2, offset=offset, want_triangle=False)
+        t = [torch.from_numpy(np.ascontiguousarray(a)).to(dev) for a in (f32_0, m2_0, counts_0.view(np.int32), normals[0], jp, jn)]
+        n, cw = int(index.size), 1024
+        ch = (n + cw - 1) // cw
+        d_index = torch.empty((size * size,), dtype=torch.int32, device=dev)
+        d_count = torch.zeros((1,), dtype=torch.int32, device=dev)
+        tp = torch.empty((per_round, ch, cw, 3), dtype=torch.float32, device=dev)
+        tn = torch.empty((per_round, ch, cw, 3), dtype=torch.float32, device=dev)
+        camr = replace(cam, screen_width=cw, screen_height=ch, aa_sample_count=per_round)
+        part = {"select": [], "gather": [], "merge": [], "render": []}
+        for k in range(bakes + 1):
+            torch.cuda.synchronize()
+            ctx.lightmap_select_device(size, size, t[0].data_ptr(), t[1].data_ptr(), t[2].data_ptr(), t[3].data_ptr(), trel, 0.0, size * size,
+                                       d_index.data_ptr(), d_count.data_ptr())
+            torch.cuda.synchronize()
+            sel = ctx.last_kernel_ms()
+            ctx.lightmap_gather_device(size, size, per_round, n, d_index.data_ptr(), t[4].data_ptr(), t[5].data_ptr(), cw, tp.data_ptr(), tn.data_ptr())
+            torch.cuda.synchronize()
+            gat = ctx.last_kernel_ms()
+            rm2, rmean, _, _, rst = ctx.render_points_moments(camr, tp.cpu().numpy(), tn.cpu().numpy(), seed=2, want_u8=False)
+            t_mean, t_rm2 = torch.from_numpy(rmean).to(dev), torch.from_numpy(rm2).to(dev)
+            img, m2c, cnt = t[0].clone(), t[1].clone(), t[2].clone()
+            torch.cuda.synchronize()
+            ctx.lightmap_merge_device(size, size, n, d_index.data_ptr(), t_mean.data_ptr(), t_rm2.data_ptr(), per_round, img.data_ptr(),
+                                      m2c.data_ptr(), cnt.data_ptr())
+            torch.cuda.synchronize()
+            if k:
+                for key, v in (("select", sel), ("gather", gat), ("merge", ctx.last_kernel_ms()), ("render", rst.kernel_ms)):
+                    part[key].append(v)
+        med = {k: float(np.median(v)) for k, v in part.items()}
+        book = med["select"] + med["gather"] + med["merge"]
+        assert int(d_count.item()) == count == n
+        rows.append(dict(base, query="round 1: select + gather + merge beside the render", selected=n,
+                         **{f"{k}_ms_median": round(v, 4) for k, v in med.items()}, bookkeeping_share_of_round=round(book / (book + med["render"]), 4)))
+        print(json.dumps(rows[-1]), flush=True)
+        del t, tp, tn, d_index
+    return rows
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--calls", type=int, default=20, help="timed calls per row (at least 20)")
@@ -865,7 +969,7 @@ def main():
     ap.add_argument("--width", type=int, default=1920)
     ap.add_argument("--height", type=int, default=1080)
     ap.add_argument("--configs", default="2,4")
-    ap.add_argument("--mode", choices=("intersect", "occlusion", "render", "hemisphere", "bake", "probes", "atlas", "finish", "volume", "variance"), default="intersect",
+    ap.add_argument("--mode", choices=("intersect", "occlusion", "render", "hemisphere", "bake", "probes", "atlas", "finish", "volume", "variance", "adaptive"), default="intersect",
                     help="intersect: the closest-hit rows; occlusion: the any-hit query against the visibility form; "
                          "render: ray-table rendering against mi_shade_rays_device; "
                          "hemisphere: hemisphere occlusion against the any-hit query on the identical pre-made rays; "
@@ -874,7 +978,9 @@ def main():
                          "atlas: the lightmap atlas on the GPU against the host helper, on the drone; "
                          "finish: lightmap finishing pass by pass, both forms of the filter, against a copy of the same bytes; "
                          "volume: irradiance-volume sampling, coherent and shuffled points, against a copy of the same bytes; "
-                         "variance: the bake's second moments against the plain bake, the variance-guided finish against the fixed one")
+                         "variance: the bake's second moments against the plain bake, the variance-guided finish against the fixed one; "
+                         "adaptive: the adaptive bake against uniform bakes at the same and at the largest sample count, errors against a "
+                         "16 x reference, and the bookkeeping kernels' share of a round")
     ap.add_argument("--volume-grids", default="16,32", help="--mode volume: probes per axis")
     ap.add_argument("--volume-points", default=f"{1 << 20},{1 << 22}", help="--mode volume: point counts")
     ap.add_argument("--finish-sizes", default="1024,2048,4096", help="--mode finish and --mode variance: the square atlas sizes")
@@ -900,6 +1006,9 @@ def main():
         a.configs = ""
     if a.mode == "variance":
         rows += variance_rows(ctx, [int(v) for v in a.finish_sizes.split(",")], a.calls, a.warmup)
+        a.configs = ""
+    if a.mode == "adaptive":
+        rows += adaptive_rows(ctx, int(a.atlas_sizes.split(",")[0]), a.atlas_bakes)
         a.configs = ""
     if a.mode == "atlas":
         for size in [int(v) for v in a.atlas_sizes.split(",")]:
