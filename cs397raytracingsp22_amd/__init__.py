@@ -23,6 +23,7 @@ from .tracing import check_finish_tables, lightmap_finish, lightmap_finish_var  
 from .tracing import check_counts_plane, lightmap_gather, lightmap_merge, lightmap_select  # noqa: F401
 from .tracing import check_probe_table, probe_grid, sh9_basis, sh9_irradiance  # noqa: F401
 from .tracing import ProbeVolume, check_probe_volume, check_volume_points, probe_volume_sample  # noqa: F401
+from .tracing import check_finish_sh_tables, check_sh_eval, lightmap_finish_sh, lightmap_sh_eval  # noqa: F401
 
 __all__ = [
     "abi", "Camera", "CameraProjectionMode", "ShadingMode", "Scene", "Context", "MultiContext", "compact_size",

@@ -138,6 +138,8 @@ EXPORTS = [
     "mi_lightmap_merge", "mi_lightmap_merge_device", "mi_lightmap_finish_var_counts", "mi_lightmap_finish_var_counts_device",
     "mi_bake_lightmap_adaptive",
     "mi_probe_volume_sample", "mi_probe_volume_sample_device",
+    "mi_render_points_sh", "mi_render_points_sh_device", "mi_bake_lightmap_sh",
+    "mi_lightmap_finish_sh", "mi_lightmap_finish_sh_device", "mi_lightmap_sh_eval", "mi_lightmap_sh_eval_device",
     "mi_multi_create", "mi_multi_create_loopback", "mi_multi_destroy", "mi_multi_device_count", "mi_multi_context", "mi_multi_scene_upload", "mi_multi_reserve", "mi_multi_render",
 ]
 
@@ -301,6 +303,18 @@ def load() -> C.CDLL:
     lib.mi_probe_volume_sample.restype = C.c_int
     lib.mi_probe_volume_sample_device.argtypes = lib.mi_probe_volume_sample.argtypes + [vp]
     lib.mi_probe_volume_sample_device.restype = C.c_int
+    # directional lightmaps (added within ABI 5): the _moments argument lists with out_sh / d_compact_sh in the place of out_m2 /
+    # d_compact_m2; mi_lightmap_finish's with [H][W][9][3] records; n, sh, normals, out_irradiance (, stream)
+    lib.mi_render_points_sh.argtypes = lib.mi_render_points_moments.argtypes
+    lib.mi_render_points_sh_device.argtypes = lib.mi_render_points_moments_device.argtypes
+    lib.mi_bake_lightmap_sh.argtypes = lib.mi_bake_lightmap_moments.argtypes
+    lib.mi_lightmap_finish_sh.argtypes = lib.mi_lightmap_finish.argtypes
+    lib.mi_lightmap_finish_sh_device.argtypes = lib.mi_lightmap_finish_device.argtypes
+    lib.mi_lightmap_sh_eval.argtypes = [vp, u32, vp, vp, vp]
+    lib.mi_lightmap_sh_eval_device.argtypes = lib.mi_lightmap_sh_eval.argtypes + [vp]
+    for name in ("render_points_sh", "render_points_sh_device", "bake_lightmap_sh", "lightmap_finish_sh", "lightmap_finish_sh_device",
+                 "lightmap_sh_eval", "lightmap_sh_eval_device"):
+        getattr(lib, "mi_" + name).restype = C.c_int
     lib.mi_multi_create.argtypes = [C.c_int, C.POINTER(C.c_int), C.POINTER(vp)]
     lib.mi_multi_create.restype = C.c_int
     lib.mi_multi_create_loopback.argtypes = [C.c_int, C.c_int, C.POINTER(vp)]

@@ -70,6 +70,11 @@ hipError_t launch_lmv_init_counts(const LmvArgs& a, const uint32_t* counts, bool
 hipError_t launch_lma_select(const LmaArgs& a, hipStream_t stream);
 hipError_t launch_lma_gather(const LmaListArgs& a, hipStream_t stream);
 hipError_t launch_lma_merge(const LmaListArgs& a, hipStream_t stream);
+hipError_t launch_wf_reduce_psh(const WfArgs& a, bool first_batch, bool last_batch, hipStream_t stream);
+hipError_t launch_lsh_mask(const LmfArgs& a, hipStream_t stream);
+hipError_t launch_lsh_atrous(const LmfArgs& a, hipStream_t stream);
+hipError_t launch_lsh_dilate(const LmfArgs& a, hipStream_t stream);
+hipError_t launch_lsh_eval(const LshEvalArgs& a, hipStream_t stream);
 }  // namespace pt
 
 using namespace pt;
@@ -127,7 +132,7 @@ struct mi_ctx {
     unsigned long long* d_diag = nullptr;    // 16 counters of the diagnostic variant
     void* d_rq = nullptr; size_t rq_bytes = 0;               // ray queries, host-pointer forms: rays and results of one chunk (its own buffer: never the pipeline's)
     void* d_rays = nullptr; size_t rays_bytes = 0;           // mi_render_rays / mi_render_points: the uploaded table, origins then dirs / points then normals (its own buffer too)
-    void* d_sh = nullptr; size_t sh_bytes = 0;               // mi_render_probes: the compact SH records, then the un-permuted [H][W][9][3] plane
+    void* d_sh = nullptr; size_t sh_bytes = 0;               // mi_render_probes / mi_render_points_sh: the compact SH records, then the un-permuted [H][W][9][3] plane
     // mi_lightmap_texels: the bins' counters and offsets, the bins' list (grown on demand, never the buffers mi_reserve sized), the pinned
     // word lm_scan leaves the list's full length in, and mi_lightmap_texels' / mi_bake_lightmap's uploaded mesh and triangle plane
     void* d_lm_hdr = nullptr; size_t lm_hdr_bytes = 0;
@@ -140,6 +145,9 @@ struct mi_ctx {
     void* d_lmf = nullptr; size_t lmf_bytes = 0;
     void* d_lmf_io = nullptr; size_t lmf_io_bytes = 0;
     bool lmf_big_lds_enabled = false;
+    // mi_lightmap_finish_sh: the same for [H][W][9][3] records; mi_lightmap_sh_eval (host form): the uploaded records and normals, the result
+    void* d_lsh = nullptr; size_t lsh_bytes = 0;
+    void* d_lsh_io = nullptr; size_t lsh_io_bytes = 0;
     // mi_probe_volume_sample: the prepared 112-byte probe records and, behind them, the host form's uploaded sh and valid (grown on
     // demand, never the buffers mi_reserve sized)
     void* d_pv = nullptr; size_t pv_bytes = 0;
@@ -177,7 +185,7 @@ struct mi_ctx {
         void* d_words = nullptr; size_t d_bytes = 0;
     } masks;
     std::vector<hipEvent_t> wf_ev;                   // event pool for per-kernel timing of the pipeline
-    float wf_ms[8] = { 0, 0, 0, 0, 0, 0, 0, 0 };     // last frame: wf_main, wf_trav, wf_reduce totals (ms), launches, wf_trav_f, wf_replay, class A, wf_reduce_sh or wf_reduce_m2
+    float wf_ms[8] = { 0, 0, 0, 0, 0, 0, 0, 0 };     // last frame: wf_main, wf_trav, wf_reduce totals (ms), launches, wf_trav_f, wf_replay, class A, wf_reduce_sh / wf_reduce_m2 / wf_reduce_psh
     int n_cus = 256;
     // Developer knobs (MI_RT_* environment variables), read ONCE in mi_ctx_create; none is needed for
     // normal operation and none changes a result — what a caller may want to control is in mi_render_opts.
@@ -314,6 +322,8 @@ extern "C" void mi_ctx_destroy(mi_ctx* c) {
     if (c->d_rq) (void)hipFree(c->d_rq);
     if (c->d_rays) (void)hipFree(c->d_rays);
     if (c->d_sh) (void)hipFree(c->d_sh);
+    if (c->d_lsh) (void)hipFree(c->d_lsh);
+    if (c->d_lsh_io) (void)hipFree(c->d_lsh_io);
     if (c->d_lm_hdr) (void)hipFree(c->d_lm_hdr);
     if (c->d_lm_list) (void)hipFree(c->d_lm_list);
     if (c->h_lm_total) (void)hipHostFree(c->h_lm_total);
@@ -511,7 +521,7 @@ private:
 // Per-launch timing of the pipeline: one event pair per launch from the context's pool, summed per kind into wf_ms after the
 // frame.  One pair is ~0.4 ms per frame of extra barriers: nothing on a whole frame (109 ms), 3 % of a 1/8 share, so multi-rank
 // renders skip it unless asked (MI_RT_WF_KERNEL_TIMING=0/1 overrides).
-enum LaunchKind { kMain, kTrav, kReduce, kTravF, kReplay, kMainA, kReduceSh, kReduceM2 };      // kTravF: wf_filter_f too; kMainA: wf_main's class-A part on the second stream
+enum LaunchKind { kMain, kTrav, kReduce, kTravF, kReplay, kMainA, kReduceSh, kReduceM2, kReducePsh };      // kTravF: wf_filter_f too; kMainA: wf_main's class-A part on the second stream
 class LaunchTimer {
 public:
     LaunchTimer(mi_ctx* c, bool on) : c_(c), on_(on) {}
@@ -523,19 +533,19 @@ public:
         return MI_OK;
     }
     // after the frame (the streams have drained): wf_ms = {wf_main, wf_trav, wf_reduce} ms, launches, {wf_trav_f, wf_replay, class A, wf_reduce_sh} ms;
-    // wf_reduce_m2 shares entry 7 with wf_reduce_sh (no render runs both)
+    // wf_reduce_m2 and wf_reduce_psh share entry 7 with wf_reduce_sh (no render runs two of them)
     void finish() {
         for (int k = 0; k < 8; k++) c_->wf_ms[k] = 0.0f;
         c_->wf_ms[3] = (float)(used_ / 2);
         for (size_t e = 0; e + 1 < used_; e += 2) {
             float ms = 0.0f;
-            if (hipEventElapsedTime(&ms, c_->wf_ev[e], c_->wf_ev[e + 1]) == hipSuccess) c_->wf_ms[kinds_[e] < 3 ? kinds_[e] : kinds_[e] == kReduceM2 ? 7 : kinds_[e] + 1] += ms;
+            if (hipEventElapsedTime(&ms, c_->wf_ev[e], c_->wf_ev[e + 1]) == hipSuccess) c_->wf_ms[kinds_[e] < 3 ? kinds_[e] : kinds_[e] >= kReduceSh ? 7 : kinds_[e] + 1] += ms;
             if (c_->tune.dump_launches) fprintf(stderr, "[mi_rt] launch %zu %s %.4f ms\n", e / 2, kNames[kinds_[e]], ms);
         }
     }
 private:
-    static constexpr const char* kNames[8] = { "wf_main", "wf_trav", "wf_reduce", "wf_trav_f", "wf_replay", "wf_main (class A, beside the walkers)", "wf_reduce_sh",
-                                               "wf_reduce_m2" };
+    static constexpr const char* kNames[9] = { "wf_main", "wf_trav", "wf_reduce", "wf_trav_f", "wf_replay", "wf_main (class A, beside the walkers)", "wf_reduce_sh",
+                                               "wf_reduce_m2", "wf_reduce_psh" };
     int stamp(LaunchKind kind, hipStream_t on) {          // before AND after the launch
         if (!on_) return MI_OK;
         if (used_ == c_->wf_ev.size()) { hipEvent_t e; if (hipEventCreate(&e) != hipSuccess) return MI_ERR_HIP; c_->wf_ev.push_back(e); }
@@ -557,6 +567,7 @@ struct SampleRange { uint32_t begin, end; float4* accum; };
 // the direction of each sample itself (the POINTS form of wf_main)
 // Light probes (kind = kTableProbes): `origins` holds probe positions, `dirs` is nullptr; the camera pass draws a full-sphere direction (the
 // PROBES form) and `sh`, DEVICE [tiles_padded][1024][27] or nullptr, takes the SH L2 sums (wf_reduce_sh)
+// Directional lightmaps (kind = kTablePoints with `sh`): the SH L2 sums over the POINTS form's hemisphere directions (wf_reduce_psh)
 // Second moments (point tables): `m2`, DEVICE [tiles_padded][1024][3] or nullptr, takes the sums of squares (wf_reduce_m2)
 enum TableKind { kTableRays, kTablePoints, kTableProbes };
 struct RayTable { const float* origins; const float* dirs; uint32_t rows; TableKind kind; float* sh; float* m2; };
@@ -671,7 +682,9 @@ static int render_tiles_wavefront(mi_ctx* c, const K1Args& k, const mi_camera_de
         }
         MI_TRY(timer.run(kReduce, stream, [&] { return launch_wf_reduce(a, s0 == 0, s0 + a.s_count >= spp, stream); }));
         // light probes: the SH sums of the same slots, same batch rules (the slots are rewritten by the next batch only, behind this)
-        if (a.sh) MI_TRY(timer.run(kReduceSh, stream, [&] { return launch_wf_reduce_sh(a, s0 == 0, s0 + a.s_count >= spp, stream); }));
+        if (a.sh && a.pt_probes) MI_TRY(timer.run(kReduceSh, stream, [&] { return launch_wf_reduce_sh(a, s0 == 0, s0 + a.s_count >= spp, stream); }));
+        // directional lightmaps: the same sums of a point table's samples, whose directions lie about the table's normals
+        if (a.sh && !a.pt_probes) MI_TRY(timer.run(kReducePsh, stream, [&] { return launch_wf_reduce_psh(a, s0 == 0, s0 + a.s_count >= spp, stream); }));
         // second moments of a point-table bake: the sums of squares of the same slots, same batch rules
         if (a.m2) MI_TRY(timer.run(kReduceM2, stream, [&] { return launch_wf_reduce_m2(a, s0 == 0, s0 + a.s_count >= spp, stream); }));
         // the headers not read yet (statistics; passes launched behind the one that ended every path are not counted)
@@ -1171,6 +1184,14 @@ static int moments_buffer(mi_ctx* c, const mi_camera_desc* cam, float** out) {
     return MI_OK;
 }
 
+// The context's SH buffer for a W x H image: the compact records, then the plane render_image un-permutes them into
+static int sh_buffer(mi_ctx* c, const mi_camera_desc* cam, float** out) {
+    const size_t slots = (size_t)tile_grid(cam, 1).padded * kTilePixels + (size_t)cam->screen_width * cam->screen_height;
+    MI_TRY(ensure(&c->d_sh, &c->sh_bytes, slots * kShFloats * sizeof(float)));
+    *out = (float*)c->d_sh;
+    return MI_OK;
+}
+
 // Host pointers: upload the two tables (light probes: the one) into the context's own buffer, then mi_render's body.  `what` names the
 // entry point in messages.  out_sh: light probes only, and required there.  out_m2: point tables only (the _moments calls).
 static int render_table_host(mi_ctx* c, const mi_camera_desc* cam, const mi_render_opts* opts, const float* first, const float* second,
@@ -1185,11 +1206,7 @@ static int render_table_host(mi_ctx* c, const mi_camera_desc* cam, const mi_rend
     HIP_TRY(hipMemcpyAsync(c->d_rays, first, bytes, hipMemcpyHostToDevice, c->stream));
     if (second) HIP_TRY(hipMemcpyAsync((char*)c->d_rays + bytes, second, bytes, hipMemcpyHostToDevice, c->stream));
     RayTable table = { (const float*)c->d_rays, second ? (const float*)((const char*)c->d_rays + bytes) : nullptr, rows, kind, nullptr, nullptr };
-    if (out_sh) {           // the compact records, then the plane render_image un-permutes them into
-        const size_t slots = (size_t)tile_grid(cam, 1).padded * kTilePixels + (size_t)cam->screen_width * cam->screen_height;
-        MI_TRY(ensure(&c->d_sh, &c->sh_bytes, slots * kShFloats * sizeof(float)));
-        table.sh = (float*)c->d_sh;
-    }
+    if (out_sh) MI_TRY(sh_buffer(c, cam, &table.sh));
     if (out_m2) MI_TRY(moments_buffer(c, cam, &table.m2));
     const mi_camera_desc tc = table_camera(cam);
     return render_image(c, &tc, opts, &table, out_rgb_f32, out_rgb_u8, out_sig, stats, out_sh, out_m2);
@@ -1255,6 +1272,26 @@ extern "C" int mi_render_points_moments_device(mi_ctx* c, const mi_camera_desc* 
                                                mi_stats* stats) {
     return render_table_device(c, cam, opts, d_points, d_normals, rows_per_pixel, kTablePoints, sample_begin, sample_end, d_accum_f32x4,
                                d_compact_f32, d_sig_u32, stream, stats, nullptr, d_compact_m2);
+}
+
+// ------------------------------------------------------------------ directional lightmaps: the SH L2 projection of a point-table bake
+// mi_render_points with a second output: wf_reduce_psh, behind wf_reduce in every batch, weights the same samples by the SH basis of their
+// hemisphere directions (mi_render_probes' records, scaled by 2 pi / S).  Same checks, same upload buffer, same body; the plain outputs
+// are mi_render_points' bits (no timed kernel changes).  The records live in the buffer mi_render_probes' do.
+extern "C" int mi_render_points_sh(mi_ctx* c, const mi_camera_desc* cam, const mi_render_opts* opts, const float* points,
+                                   const float* normals, uint32_t rows_per_pixel, float* out_sh, float* out_rgb_f32,
+                                   uint8_t* out_rgb_u8, uint32_t* out_sig, mi_stats* stats) {
+    if (!out_sh) return fail(MI_ERR_INVALID, "mi_render_points_sh: out_sh is required");
+    return render_table_host(c, cam, opts, points, normals, rows_per_pixel, kTablePoints, "mi_render_points_sh", out_rgb_f32, out_rgb_u8,
+                             out_sig, stats, out_sh);
+}
+
+extern "C" int mi_render_points_sh_device(mi_ctx* c, const mi_camera_desc* cam, const mi_render_opts* opts, const float* d_points,
+                                          const float* d_normals, uint32_t rows_per_pixel, uint32_t sample_begin, uint32_t sample_end,
+                                          void* d_accum_f32x4, void* d_compact_sh, void* d_compact_f32, void* d_sig_u32, void* stream,
+                                          mi_stats* stats) {
+    return render_table_device(c, cam, opts, d_points, d_normals, rows_per_pixel, kTablePoints, sample_begin, sample_end, d_accum_f32x4,
+                               d_compact_f32, d_sig_u32, stream, stats, d_compact_sh);
 }
 
 // ------------------------------------------------------------------ lightmap atlas (the point table of a mesh's uv atlas, made on the GPU)
@@ -1380,9 +1417,10 @@ extern "C" int mi_lightmap_texels(mi_ctx* c, const mi_mesh* mesh, uint32_t width
 
 // The whole bake: the mesh up, its table made in the context's table buffer (mi_render_rays'), then mi_render_points' body on it.
 // out_m2 (mi_bake_lightmap_moments): the second moments as well, as mi_render_points_moments returns them.
+// out_sh (mi_bake_lightmap_sh): the SH L2 records as well, as mi_render_points_sh returns them (never together with out_m2).
 static int bake_lightmap(const char* who, mi_ctx* c, const mi_camera_desc* cam, const mi_render_opts* opts, const mi_mesh* mesh, uint32_t flags,
                          float offset, float* out_rgb_f32, uint8_t* out_rgb_u8, uint32_t* out_sig, int32_t* out_triangle, mi_stats* stats,
-                         float* out_m2) {
+                         float* out_m2, float* out_sh = nullptr) {
     if (!c) return fail(MI_ERR_INVALID, "ctx is NULL");
     if (!mesh) return fail(MI_ERR_INVALID, "%s: mesh is NULL", who);
     const uint32_t rows = (cam && (flags & MI_LM_JITTER)) ? cam->aa_sample_count : 1u;
@@ -1403,8 +1441,9 @@ static int bake_lightmap(const char* who, mi_ctx* c, const mi_camera_desc* cam, 
     if (out_triangle) HIP_TRY(hipMemcpyAsync(out_triangle, c->d_lm_out, n * 4, hipMemcpyDeviceToHost, c->stream));
     RayTable table = { d_points, d_normals, rows, kTablePoints, nullptr, nullptr };
     if (out_m2) MI_TRY(moments_buffer(c, cam, &table.m2));
+    if (out_sh) MI_TRY(sh_buffer(c, cam, &table.sh));
     const mi_camera_desc tc = table_camera(cam);
-    return render_image(c, &tc, opts, &table, out_rgb_f32, out_rgb_u8, out_sig, stats, nullptr, out_m2);
+    return render_image(c, &tc, opts, &table, out_rgb_f32, out_rgb_u8, out_sig, stats, out_sh, out_m2);
 }
 
 extern "C" int mi_bake_lightmap(mi_ctx* c, const mi_camera_desc* cam, const mi_render_opts* opts, const mi_mesh* mesh, uint32_t flags,
@@ -1418,6 +1457,14 @@ extern "C" int mi_bake_lightmap_moments(mi_ctx* c, const mi_camera_desc* cam, co
     if (!out_m2) return fail(MI_ERR_INVALID, "mi_bake_lightmap_moments: out_m2 is required");
     return bake_lightmap("mi_bake_lightmap_moments", c, cam, opts, mesh, flags, offset, out_rgb_f32, out_rgb_u8, out_sig, out_triangle, stats,
                          out_m2);
+}
+
+extern "C" int mi_bake_lightmap_sh(mi_ctx* c, const mi_camera_desc* cam, const mi_render_opts* opts, const mi_mesh* mesh, uint32_t flags,
+                                   float offset, float* out_sh, float* out_rgb_f32, uint8_t* out_rgb_u8, uint32_t* out_sig,
+                                   int32_t* out_triangle, mi_stats* stats) {
+    if (!out_sh) return fail(MI_ERR_INVALID, "mi_bake_lightmap_sh: out_sh is required");
+    return bake_lightmap("mi_bake_lightmap_sh", c, cam, opts, mesh, flags, offset, out_rgb_f32, out_rgb_u8, out_sig, out_triangle, stats,
+                         nullptr, out_sh);
 }
 
 // ------------------------------------------------------------------ lightmap finishing (edge-aware a-trous filter, gutter dilation)
@@ -1506,6 +1553,120 @@ extern "C" int mi_lightmap_finish(mi_ctx* c, uint32_t width, uint32_t height, co
                                   out_valid ? (uint8_t*)(io + 4 * img) : nullptr, c->stream));
     HIP_TRY(hipMemcpyAsync(out_image, io + 3 * img, img, hipMemcpyDeviceToHost, c->stream));      // after the uploads: out_image may alias image
     if (out_valid) HIP_TRY(hipMemcpyAsync(out_valid, io + 4 * img, n, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return MI_OK;
+}
+
+// ------------------------------------------------------------------ directional lightmaps: the finish and the evaluation
+// tracing.py lightmap_finish_sh as kernels: lightmap_finish_device for [H][W][9][3] records (lsh_mask, lsh_atrous per level, lsh_dilate
+// per pass), with scratch of its own.  The arguments are mi_lightmap_finish's and are checked by the same function.
+static int lightmap_finish_sh_device(mi_ctx* c, uint32_t width, uint32_t height, const float* d_image, const float* d_points,
+                                     const float* d_normals, uint32_t levels, uint32_t normal_power_log2, float sigma_plane, float reach,
+                                     float sigma_color, uint32_t dilate, float* d_out, uint8_t* d_valid, hipStream_t stream) {
+    const size_t n = (size_t)width * height, img = n * kShFloats * sizeof(float), msk = (n + 255) / 256 * 256;
+    MI_TRY(ensure(&c->d_lsh, &c->lsh_bytes, 2 * img + 2 * msk));
+    float* const ping[2] = { (float*)c->d_lsh, (float*)((char*)c->d_lsh + img) };
+    uint8_t* const mping[2] = { (uint8_t*)c->d_lsh + 2 * img, (uint8_t*)c->d_lsh + 2 * img + msk };
+    LmfArgs a{};
+    a.points = d_points; a.normals = d_normals;
+    a.width = width; a.height = height;
+    a.tiles_x = (width + kTile - 1) / kTile; a.tiles_y = (height + kTile - 1) / kTile;
+    a.npow = normal_power_log2; a.sigma_plane = sigma_plane; a.reach = reach; a.sigma_color = sigma_color;
+    const uint32_t passes = levels + dilate;
+    auto mask_target = [&](uint32_t k) { return (k == dilate && d_valid) ? d_valid : mping[k & 1u]; };
+    HIP_TRY(hipEventRecord(c->ev_start, stream));
+    a.src = d_image; a.dst = d_out; a.copy = passes == 0 ? 1u : 0u; a.mask_out = mask_target(0);
+    HIP_TRY(launch_lsh_mask(a, stream));
+    a.copy = 0;
+    for (uint32_t p = 0; p < passes; p++) {
+        a.dst = p + 1 == passes ? d_out : ping[p & 1u];
+        if (p < levels) {
+            a.step = 1u << p;
+            HIP_TRY(launch_lsh_atrous(a, stream));
+        } else {
+            a.mask_in = mask_target(p - levels); a.mask_out = mask_target(p - levels + 1);
+            HIP_TRY(launch_lsh_dilate(a, stream));
+        }
+        a.src = a.dst;
+    }
+    HIP_TRY(hipEventRecord(c->ev_stop, stream));
+    c->ev_recorded = true; c->ms_summed = false;
+    return MI_OK;
+}
+
+extern "C" int mi_lightmap_finish_sh_device(mi_ctx* c, uint32_t width, uint32_t height, const float* sh, const float* points,
+                                            const float* normals, uint32_t levels, uint32_t normal_power_log2, float sigma_plane, float reach,
+                                            float sigma_color, uint32_t dilate, float* out_sh, uint8_t* out_valid, void* stream) {
+    MI_TRY(check_lmf_args("mi_lightmap_finish_sh_device", c, width, height, sh, points, normals, levels, normal_power_log2, sigma_plane,
+                          reach, sigma_color, dilate, out_sh));
+    const uintptr_t texels = (uintptr_t)width * height, o = (uintptr_t)out_sh, obytes = texels * kShFloats * sizeof(float);
+    const struct { const float* at; uintptr_t bytes; } ins[3] = { { sh, obytes }, { points, texels * 12 }, { normals, texels * 12 } };
+    for (const auto& in : ins)
+        if (o < (uintptr_t)in.at + in.bytes && (uintptr_t)in.at < o + obytes)
+            return fail(MI_ERR_INVALID, "mi_lightmap_finish_sh_device: out_sh overlaps an input (the passes are never in place)");
+    HIP_TRY(hipSetDevice(c->device));
+    return lightmap_finish_sh_device(c, width, height, sh, points, normals, levels, normal_power_log2, sigma_plane, reach, sigma_color, dilate,
+                                     out_sh, out_valid, (hipStream_t)stream);
+}
+
+extern "C" int mi_lightmap_finish_sh(mi_ctx* c, uint32_t width, uint32_t height, const float* sh, const float* points, const float* normals,
+                                     uint32_t levels, uint32_t normal_power_log2, float sigma_plane, float reach, float sigma_color,
+                                     uint32_t dilate, float* out_sh, uint8_t* out_valid) {
+    MI_TRY(check_lmf_args("mi_lightmap_finish_sh", c, width, height, sh, points, normals, levels, normal_power_log2, sigma_plane, reach,
+                          sigma_color, dilate, out_sh));
+    HIP_TRY(hipSetDevice(c->device));
+    // the records, points, normals, the result, its mask
+    const size_t n = (size_t)width * height, rec = n * kShFloats * sizeof(float), tab = n * 3 * sizeof(float);
+    MI_TRY(ensure(&c->d_lsh_io, &c->lsh_io_bytes, 2 * rec + 2 * tab + n));
+    char* const io = (char*)c->d_lsh_io;
+    HIP_TRY(hipMemcpyAsync(io, sh, rec, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(io + rec, points, tab, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(io + rec + tab, normals, tab, hipMemcpyHostToDevice, c->stream));
+    char* const res = io + rec + 2 * tab;
+    MI_TRY(lightmap_finish_sh_device(c, width, height, (const float*)io, (const float*)(io + rec), (const float*)(io + rec + tab), levels,
+                                     normal_power_log2, sigma_plane, reach, sigma_color, dilate, (float*)res,
+                                     out_valid ? (uint8_t*)(res + rec) : nullptr, c->stream));
+    HIP_TRY(hipMemcpyAsync(out_sh, res, rec, hipMemcpyDeviceToHost, c->stream));      // after the uploads: out_sh may alias sh
+    if (out_valid) HIP_TRY(hipMemcpyAsync(out_valid, res + rec, n, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return MI_OK;
+}
+
+// tracing.py lightmap_sh_eval as one kernel (lsh_eval): one lane per point.  Checked before the context; n == 0 launches nothing.
+static int check_lsh_eval_args(const char* who, mi_ctx* c, const float* sh, const float* normals, const float* out_irradiance) {
+    if (!sh || !normals || !out_irradiance) return fail(MI_ERR_INVALID, "%s: sh, normals and out_irradiance are required", who);
+    if (!c) return fail(MI_ERR_INVALID, "ctx is NULL");
+    return MI_OK;
+}
+
+static int lightmap_sh_eval_device(mi_ctx* c, uint32_t n, const float* d_sh, const float* d_normals, float* d_out, hipStream_t stream) {
+    LshEvalArgs a{};
+    a.sh = d_sh; a.normals = d_normals; a.out_irradiance = d_out; a.n = n;
+    HIP_TRY(hipEventRecord(c->ev_start, stream));
+    HIP_TRY(launch_lsh_eval(a, stream));
+    HIP_TRY(hipEventRecord(c->ev_stop, stream));
+    c->ev_recorded = true; c->ms_summed = false;
+    return MI_OK;
+}
+
+extern "C" int mi_lightmap_sh_eval_device(mi_ctx* c, uint32_t n, const float* sh, const float* normals, float* out_irradiance, void* stream) {
+    MI_TRY(check_lsh_eval_args("mi_lightmap_sh_eval_device", c, sh, normals, out_irradiance));
+    if (n == 0) return MI_OK;
+    HIP_TRY(hipSetDevice(c->device));
+    return lightmap_sh_eval_device(c, n, sh, normals, out_irradiance, (hipStream_t)stream);
+}
+
+extern "C" int mi_lightmap_sh_eval(mi_ctx* c, uint32_t n, const float* sh, const float* normals, float* out_irradiance) {
+    MI_TRY(check_lsh_eval_args("mi_lightmap_sh_eval", c, sh, normals, out_irradiance));
+    if (n == 0) return MI_OK;
+    HIP_TRY(hipSetDevice(c->device));
+    const size_t rec = (size_t)n * kShFloats * sizeof(float), tab = (size_t)n * 3 * sizeof(float);
+    MI_TRY(ensure(&c->d_lsh_io, &c->lsh_io_bytes, rec + 2 * tab));
+    char* const io = (char*)c->d_lsh_io;
+    HIP_TRY(hipMemcpyAsync(io, sh, rec, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(io + rec, normals, tab, hipMemcpyHostToDevice, c->stream));
+    MI_TRY(lightmap_sh_eval_device(c, n, (const float*)io, (const float*)(io + rec), (float*)(io + rec + tab), c->stream));
+    HIP_TRY(hipMemcpyAsync(out_irradiance, io + rec + tab, tab, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return MI_OK;
 }

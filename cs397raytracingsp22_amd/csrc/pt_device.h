@@ -368,6 +368,8 @@ struct WfArgs {
     // Light probes (mi_render_probes): pt_probes != 0 makes pt_p a table of probe positions without normals (pt_n is nullptr): the camera
     // pass draws a full-sphere direction, rand_sphere_vec on the direction stream above (the PROBES form of wf_main).  sh, or nullptr:
     // [npix][9][3] running SH L2 sums in the compact tile-major layout, which wf_reduce_sh advances behind wf_reduce in every batch.
+    // A point table (pt_probes == 0) with sh (mi_render_points_sh): the same sums over the POINTS form's hemisphere directions, which
+    // wf_reduce_psh advances instead (it reads pt_n and pt_rows again); never together with m2.
     uint32_t pt_probes;
     float* sh;
     // Second moments of a point-table bake (mi_render_points_moments): m2, or nullptr: [npix][3] running sums of squares of the samples in
@@ -442,6 +444,16 @@ struct LmfArgs {
 // Largest step whose tile plus 2 s halo (9 planes of (kTile + 4 s)^2 f32) fits the CU's 160 KiB of LDS
 constexpr uint32_t kLmfMaxLdsStep = 8;
 inline size_t lmf_lds_bytes(uint32_t step) { const size_t e = (size_t)kTile + 4u * step; return 9u * e * e * sizeof(float); }
+
+// ---- directional lightmaps (mi_lightmap_finish_sh, mi_lightmap_sh_eval; pt_kernels.hip "lsh_*") ----
+// tracing.py lightmap_finish_sh: lsh_mask, lsh_atrous and lsh_dilate are lmf_mask, lmf_atrous' direct form and lmf_dilate for images of
+// [H][W][9][3] records; they take LmfArgs with src and dst holding kShFloats floats per texel.  lsh_eval is tracing.py lightmap_sh_eval:
+struct LshEvalArgs {
+    const float* sh;                 // [n][9][3]
+    const float* normals;            // [n][3]: all-zero = empty texel, +0.0
+    float*       out_irradiance;     // [n][3]
+    uint32_t     n;
+};
 
 // ---- variance-guided lightmap finishing (mi_lightmap_finish_var; pt_kernels.hip "lmv_*") ----
 // One pass of tracing.py lightmap_finish_var: lmv_init (the variance of the mean per texel from the bake's mean and second moments),

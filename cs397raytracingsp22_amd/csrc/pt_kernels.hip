@@ -21,6 +21,7 @@
 //                 16-byte quantised nodes + the reference's triangle test -> replay of the reference's walk over the candidates
 //   wf_reduce     per-pixel sums in sample order (tracing.rs:232-241)
 //   wf_reduce_sh  light probes only: per-probe SH L2 sums of the same samples in the same order, the directions drawn again
+//   wf_reduce_psh point tables with an SH output only: the same sums over the hemisphere directions of the POINTS form (at the file's end)
 // K1 (below) are the single-launch variants the pipeline grew out of; they remain selectable as structural cross-checks.
 //
 // Execution model of K1 (DESIGN.md "K1"):
@@ -4596,6 +4597,222 @@ hipError_t launch_lma_gather(const LmaListArgs& a, hipStream_t stream) {
 }
 hipError_t launch_lma_merge(const LmaListArgs& a, hipStream_t stream) {
     hipLaunchKernelGGL(lma_merge, dim3((a.n + kBlock - 1) / kBlock), dim3(kBlock), 0, stream, a);
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------- directional lightmaps (mi_render_points_sh, mi_lightmap_finish_sh, mi_lightmap_sh_eval)
+// Point tables: the SH L2 projection of one batch of samples, behind wf_reduce.  wf_reduce_sh for the POINTS form: one thread per texel; per
+// sample of the batch in order it reads the row's normal from the caller's table, draws the direction again (the POINTS form's calls on
+// the same stream with the same device functions, so the same bits: rand_sphere_vec, y = |y|, rotate_from_unit_y), normalises it as
+// wf_reduce_sh does, and adds L * Y_k to the texel's 27 sums, which live in A.sh between batches and calls.  Every sum is one f32 chain in
+// sample order from +0.0, scaled once at the end by 2 pi / S (the directions are uniform over the hemisphere, pdf 1 / (2 pi)): the record
+// is bit-identical however the samples are cut into batches, calls and ranks.  A row whose normal is all-zero adds nothing and draws
+// nothing (its slot is +0.0, but the rotation about a zero normal is no direction).  Only reads the sample slots and the table; the
+// table's index is wf_main's, formed by no lane outside the image, and no address depends on a table value.
+__global__ __launch_bounds__(256) void wf_reduce_psh(WfArgs A, uint32_t first_batch, uint32_t last_batch) {
+    const uint32_t pix = blockIdx.x * blockDim.x + threadIdx.x;
+    if (pix >= A.npix) return;
+    float* rec = A.sh + (size_t)pix * kShFloats;
+    uint32_t px, py; bool in_image;
+    wf_pixel_of(A, pix, px, py, in_image);
+    if (!in_image) {                       // outside the image, or a padding slot: zeros, whatever the buffer held
+        for (int k = 0; k < kShFloats; k++) rec[k] = 0.0f;
+        return;
+    }
+    float acc[kShFloats];
+    for (int k = 0; k < kShFloats; k++) acc[k] = first_batch ? 0.0f : rec[k];
+    const uint32_t key = A.C.width * A.C.height + (py * A.C.width + px);
+    for (uint32_t s = 0; s < A.s_count; s++) {
+        const uint32_t sample = A.s_base + s;
+        const size_t r = (((size_t)(A.pt_rows == 1u ? 0u : sample) * A.C.height + py) * A.C.width + px) * 3;
+        const Ray3 tn = *(const Ray3*)(A.pt_n + r);
+        if (tn.x == 0.0f && tn.y == 0.0f && tn.z == 0.0f) continue;       // an empty row (either sign of zero)
+        const float4 v = A.samp[(size_t)s * A.npix + pix];
+        Rng tmp;
+        rng_init(tmp, A.seed_key, key, sample);
+        f3 u = rand_sphere_vec(tmp);                                       // materials.rs:172
+        u.y = fabsf(u.y);                                                  // :173
+        const f3 d = rotate_from_unit_y(mk3(tn.x, tn.y, tn.z), u);         // :176-177
+        const float inv = 1.0f / sqrtf(d.x * d.x + d.y * d.y + d.z * d.z);
+        const float x = d.x * inv, y = d.y * inv, z = d.z * inv;
+        const float Y[9] = { 0.28209479177387814f, 0.4886025119029199f * y, 0.4886025119029199f * z, 0.4886025119029199f * x,
+                             1.0925484305920792f * (x * y), 1.0925484305920792f * (y * z), 0.31539156525252005f * (3.0f * (z * z) - 1.0f),
+                             1.0925484305920792f * (x * z), 0.5462742152960396f * (x * x - y * y) };
+#pragma unroll
+        for (int k = 0; k < 9; k++) {
+            acc[3 * k] = acc[3 * k] + v.x * Y[k]; acc[3 * k + 1] = acc[3 * k + 1] + v.y * Y[k]; acc[3 * k + 2] = acc[3 * k + 2] + v.z * Y[k];
+        }
+    }
+    const float scale = last_batch ? 6.283185307179586f / (float)A.C.spp : 1.0f;       // 2 pi / S, once, behind the last sample
+#pragma unroll
+    for (int k = 0; k < kShFloats; k++) rec[k] = last_batch ? acc[k] * scale : acc[k];
+}
+
+// tracing.py lightmap_finish_sh on the device, pass by pass: lightmap_finish for [H][W][9][3] records.  The weights are lmf_atrous', the
+// colour distance taken from the three k = 0 coefficients; one weight per tap serves all 27 channels.  Pure f32, the helper's operations
+// in the helper's order, a fixed tap order per texel, nothing summed across threads.  No address depends on a table value.
+
+// The covered mask from the guide normals; with a.copy also dst = covered ? src : +0 for the 27 channels
+__global__ __launch_bounds__(kBlock) void lsh_mask(const LmfArgs a) {
+    const size_t n = (size_t)a.width * a.height, i = (size_t)blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n) return;
+    const bool cov = lmf_covered(a.normals[3 * i], a.normals[3 * i + 1], a.normals[3 * i + 2]);
+    a.mask_out[i] = cov ? 1 : 0;
+    if (a.copy)
+        for (int k = 0; k < kShFloats; k++) a.dst[kShFloats * i + k] = cov ? a.src[kShFloats * i + k] : 0.0f;
+}
+
+// One filter level of the 27 channels.  lmf_atrous' direct form (one block per kTile x kTile tile, a thread owns the texels (x, y + 8 k),
+// k < 4, one after the other: 28 live accumulators, not 112), the taps straight from HBM / L2: a tap's guides and k = 0 coefficients
+// decide the weight, then its other 24 floats are read only when the tap is accepted.  Thirty-three planes of tile and halo do not fit
+// the LDS at any step, and the 108-byte records of neighbouring lanes share their cache lines, so nothing is staged.
+__global__ __launch_bounds__(kBlock) void lsh_atrous(const LmfArgs a) {
+    const int s = (int)a.step, W = (int)a.width, H = (int)a.height;
+    const int x0 = (int)(blockIdx.x % a.tiles_x) * kTile, y0 = (int)(blockIdx.x / a.tiles_x) * kTile;
+    auto fetch3 = [&](const float* t, size_t i, float* out) {
+        for (int k = 0; k < 3; k++) out[k] = t[3 * i + k];
+    };
+    const float H5[5] = { 0.0625f, 0.25f, 0.375f, 0.25f, 0.0625f };
+    const float fs = (float)s;
+    const float r = a.reach * fs, rr = r * r, sig_c = a.sigma_color / fs;
+    const int gx = x0 + (int)(threadIdx.x & 31u);
+#pragma unroll 1
+    for (int k4 = 0; k4 < 4; k4++) {
+        const int gy = y0 + (int)(threadIdx.x >> 5) + 8 * k4;
+        if (gx >= W || gy >= H) continue;
+        const size_t ip = (size_t)gy * W + gx;
+        float np[3];
+        fetch3(a.normals, ip, np);
+        float sc[kShFloats];
+#pragma unroll
+        for (int k = 0; k < kShFloats; k++) sc[k] = 0.0f;
+        const bool cov = lmf_covered(np[0], np[1], np[2]);
+        if (cov) {
+            float cp[3], pp[3];
+            fetch3(a.src, 9 * ip, cp); fetch3(a.points, ip, pp);          // the k = 0 coefficients head the record
+            float sw = 0.0f;
+#pragma unroll
+            for (int dy = -2; dy <= 2; dy++) {
+#pragma unroll
+                for (int dx = -2; dx <= 2; dx++) {
+                    const int qx = gx + s * dx, qy = gy + s * dy;
+                    if (qx < 0 || qx >= W || qy < 0 || qy >= H) continue;
+                    const size_t iq = (size_t)qy * W + qx;
+                    float nq[3];
+                    fetch3(a.normals, iq, nq);
+                    if (!lmf_covered(nq[0], nq[1], nq[2])) continue;
+                    float cq[3], pq[3];
+                    fetch3(a.src, 9 * iq, cq); fetch3(a.points, iq, pq);
+                    const float D[3] = { pq[0] - pp[0], pq[1] - pp[1], pq[2] - pp[2] };
+                    const float d2 = (D[0] * D[0] + D[1] * D[1]) + D[2] * D[2];
+                    if ((dx != 0 || dy != 0) && !(d2 <= rr * (float)(dx * dx + dy * dy))) continue;      // the reach test, as lmf_atrous'
+                    const float h = H5[dy + 2] * H5[dx + 2];
+                    float wn = fmaxf(0.0f, (np[0] * nq[0] + np[1] * nq[1]) + np[2] * nq[2]);
+                    for (uint32_t i = 0; i < a.npow; i++) wn = wn * wn;
+                    const float dpl = fabsf((np[0] * D[0] + np[1] * D[1]) + np[2] * D[2]);
+                    const float wp = fmaxf(0.0f, 1.0f - dpl / a.sigma_plane);
+                    const float dc = (fabsf(cq[0] - cp[0]) + fabsf(cq[1] - cp[1])) + fabsf(cq[2] - cp[2]);
+                    const float wc = fmaxf(0.0f, 1.0f - dc / sig_c);
+                    const float w = ((h * wn) * wp) * wc;
+                    sw = sw + w;
+                    const float* q = a.src + kShFloats * iq;
+#pragma unroll
+                    for (int k = 0; k < 3; k++) sc[k] = sc[k] + w * cq[k];
+#pragma unroll
+                    for (int k = 3; k < kShFloats; k++) sc[k] = sc[k] + w * q[k];
+                }
+            }
+#pragma unroll
+            for (int k = 0; k < kShFloats; k++) sc[k] = sc[k] / sw;
+        }
+        float* o = a.dst + kShFloats * ip;
+#pragma unroll
+        for (int k = 0; k < kShFloats; k++) o[k] = sc[k];
+    }
+}
+
+// One dilation pass of the 27 channels: lmf_dilate's neighbours, order and count
+__global__ __launch_bounds__(kBlock) void lsh_dilate(const LmfArgs a) {
+    const size_t n = (size_t)a.width * a.height, i = (size_t)blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n) return;
+    const int W = (int)a.width, H = (int)a.height;
+    const int y = (int)(i / a.width), x = (int)(i - (size_t)y * a.width);
+    float out[kShFloats];
+#pragma unroll
+    for (int k = 0; k < kShFloats; k++) out[k] = 0.0f;
+    uint8_t valid = a.mask_in[i];
+    if (valid) {
+#pragma unroll
+        for (int k = 0; k < kShFloats; k++) out[k] = a.src[kShFloats * i + k];
+    } else {
+        int count = 0;
+        for (int dy = -1; dy <= 1; dy++)
+            for (int dx = -1; dx <= 1; dx++) {
+                const int qx = x + dx, qy = y + dy;
+                if ((dx == 0 && dy == 0) || qx < 0 || qx >= W || qy < 0 || qy >= H) continue;
+                const size_t j = (size_t)qy * W + qx;
+                if (!a.mask_in[j]) continue;
+#pragma unroll
+                for (int k = 0; k < kShFloats; k++) out[k] = out[k] + a.src[kShFloats * j + k];
+                count++;
+            }
+        if (count) {
+#pragma unroll
+            for (int k = 0; k < kShFloats; k++) out[k] = out[k] / (float)count;
+            valid = 1;
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < kShFloats; k++) a.dst[kShFloats * i + k] = out[k];
+    a.mask_out[i] = valid;
+}
+
+// tracing.py lightmap_sh_eval on the device: the irradiance E(n) of one SH L2 record per point at the caller's normal, pv_sample's
+// normal, basis and constants K_k without the grid.  One lane per point: 108 + 12 bytes in, 12 out.  An all-zero normal gives +0.0.
+__global__ __launch_bounds__(kBlock) void lsh_eval(const LshEvalArgs a) {
+    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= a.n) return;
+    const float nx = a.normals[3 * (size_t)i], ny = a.normals[3 * (size_t)i + 1], nz = a.normals[3 * (size_t)i + 2];
+    float E[3] = { 0.0f, 0.0f, 0.0f };
+    if (lmf_covered(nx, ny, nz)) {
+        const float K1 = (float)1.0233267079464885, K2 = (float)0.8580855308097834;
+        const float K[9] = { (float)0.886226925452758, K1, K1, K1, K2, K2, (float)0.24770795610037571, K2, (float)0.4290427654048917 };
+        const float l = sqrtf((nx * nx + ny * ny) + nz * nz);
+        const float x = nx / l, y = ny / l, z = nz / l;
+        const float b[9] = { 1.0f, y, z, x, x * y, y * z, 3.0f * (z * z) - 1.0f, x * z, x * x - y * y };
+        const float* sh = a.sh + (size_t)i * kShFloats;
+#pragma unroll
+        for (int c = 0; c < 3; c++) {
+            float e = b[0] * (sh[c] * K[0]);
+#pragma unroll
+            for (int k = 1; k < 9; k++) e = e + b[k] * (sh[3 * k + c] * K[k]);
+            E[c] = e;
+        }
+    }
+#pragma unroll
+    for (int c = 0; c < 3; c++) a.out_irradiance[3 * (size_t)i + c] = E[c];
+}
+
+hipError_t launch_wf_reduce_psh(const WfArgs& a, bool first_batch, bool last_batch, hipStream_t stream) {
+    hipLaunchKernelGGL(wf_reduce_psh, dim3((a.npix + 255) / 256), dim3(256), 0, stream, a, first_batch ? 1u : 0u, last_batch ? 1u : 0u);
+    return hipGetLastError();
+}
+hipError_t launch_lsh_mask(const LmfArgs& a, hipStream_t stream) {
+    const size_t n = (size_t)a.width * a.height;
+    hipLaunchKernelGGL(lsh_mask, dim3((uint32_t)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, stream, a);
+    return hipGetLastError();
+}
+hipError_t launch_lsh_atrous(const LmfArgs& a, hipStream_t stream) {
+    hipLaunchKernelGGL(lsh_atrous, dim3(a.tiles_x * a.tiles_y), dim3(kBlock), 0, stream, a);
+    return hipGetLastError();
+}
+hipError_t launch_lsh_dilate(const LmfArgs& a, hipStream_t stream) {
+    const size_t n = (size_t)a.width * a.height;
+    hipLaunchKernelGGL(lsh_dilate, dim3((uint32_t)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, stream, a);
+    return hipGetLastError();
+}
+hipError_t launch_lsh_eval(const LshEvalArgs& a, hipStream_t stream) {
+    hipLaunchKernelGGL(lsh_eval, dim3((a.n + kBlock - 1) / kBlock), dim3(kBlock), 0, stream, a);
     return hipGetLastError();
 }
 

@@ -377,6 +377,65 @@ struct Scene : Intersectable {                         // tracing.rs:213-218; `i
         return out;
     }
 
+    // A directional lightmap through mi_bake_lightmap_sh: bake_lightmap that returns, per texel, the SH L2 radiance records [H][W][9][3]
+    // (mi_render_probes' basis and order, scaled for the hemisphere's uniform directions), from which eval_lightmap_sh gives the
+    // irradiance at any normal.  `linear` takes the f32 mean bake_lightmap's image is made of, `image` the tone-mapped bytes.
+    std::vector<float> bake_lightmap_sh(const mi_mesh& mesh, uint32_t width, uint32_t height, uint32_t samples, bool jitter = true,
+                                        float offset = 1e-3f, uint32_t seed = 1, int device = 0, mi_stats* stats = nullptr,
+                                        RgbImage* image = nullptr, std::vector<float>* linear = nullptr) const {
+        mi_camera_desc cam = camera.flatten();
+        cam.screen_width = width; cam.screen_height = height; cam.aa_sample_count = samples;
+        const size_t n = (size_t)width * height;
+        std::vector<float> sh(n * 27);
+        if (image) { image->width = width; image->height = height; image->data.resize(n * 3); }
+        if (linear) linear->resize(n * 3);
+        mi_render_opts opts{}; opts.seed = seed; opts.rank = 0; opts.world = 1;
+        with_context(device, [&](mi_ctx* ctx) {
+            return mi_bake_lightmap_sh(ctx, &cam, &opts, &mesh, jitter ? MI_LM_JITTER : 0u, offset, sh.data(), linear ? linear->data() : nullptr,
+                                       image ? image->data.data() : nullptr, nullptr, nullptr, stats);
+        });
+        return sh;
+    }
+
+    // Finish a directional lightmap through mi_lightmap_finish_sh: finish_lightmap for [H][W][9][3] records; the colour weight is taken
+    // from the three k = 0 coefficients and one weight per tap serves all 27 channels.  Returns the finished records; `valid` takes the
+    // mask.  Needs no scene: a static member.
+    static std::vector<float> finish_lightmap_sh(const std::vector<float>& sh, const std::vector<float>& points, const std::vector<float>& normals,
+                                                 uint32_t width, uint32_t height, uint32_t levels = 3, uint32_t normal_power_log2 = 5,
+                                                 float sigma_plane = INFINITY, float reach = INFINITY, float sigma_color = INFINITY,
+                                                 uint32_t dilate = 4, int device = 0, std::vector<uint8_t>* valid = nullptr) {
+        const size_t n = (size_t)width * height;
+        if (sh.size() != n * 27 || points.size() != n * 3 || normals.size() != n * 3)
+            throw std::runtime_error("mi_rt: sh must be [H][W][9][3], points and normals [H][W][3]");
+        std::vector<float> out(n * 27);
+        if (valid) valid->resize(n);
+        mi_ctx* ctx = nullptr;
+        mi_check(mi_ctx_create(device, &ctx));
+        const int rc = mi_lightmap_finish_sh(ctx, width, height, sh.data(), points.data(), normals.data(), levels, normal_power_log2, sigma_plane,
+                                             reach, sigma_color, dilate, out.data(), valid ? valid->data() : nullptr);
+        const std::string err = rc == MI_OK ? "" : mi_last_error();
+        mi_ctx_destroy(ctx);
+        if (rc != MI_OK) throw std::runtime_error("mi_rt: " + err);
+        return out;
+    }
+
+    // The irradiance of a directional lightmap through mi_lightmap_sh_eval: sh is [n][9][3], normals [n][3] (an atlas: n = W * H, its own
+    // normal table for the plain irradiance map, normal-mapped normals for the detail).  An all-zero normal gives +0.0; the result is not
+    // clamped (SH ringing can take it slightly below zero).  Returns [n][3].  Needs no scene: a static member.
+    static std::vector<float> eval_lightmap_sh(const std::vector<float>& sh, const std::vector<float>& normals, int device = 0) {
+        const size_t n = normals.size() / 3;
+        if (normals.size() != n * 3 || sh.size() != n * 27) throw std::runtime_error("mi_rt: sh must be [n][9][3] and normals [n][3]");
+        std::vector<float> out(n * 3);
+        if (n == 0) return out;                              // (an empty vector has no address to pass)
+        mi_ctx* ctx = nullptr;
+        mi_check(mi_ctx_create(device, &ctx));
+        const int rc = mi_lightmap_sh_eval(ctx, (uint32_t)n, sh.data(), normals.data(), out.data());
+        const std::string err = rc == MI_OK ? "" : mi_last_error();
+        mi_ctx_destroy(ctx);
+        if (rc != MI_OK) throw std::runtime_error("mi_rt: " + err);
+        return out;
+    }
+
 private:
     // flatten -> context -> upload -> `call(ctx)` -> destroy; a failure surfaces as std::runtime_error carrying mi_last_error()
     template <class F> void with_context(int device, F call) const {

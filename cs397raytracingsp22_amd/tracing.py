@@ -706,6 +706,142 @@ def lightmap_finish(image, points, normals, levels: int = 3, normal_power_log2: 
     return cur, valid
 
 
+def _lightmap_finish_channels(img, P, N, levels, normal_power_log2, sigma_plane, reach, sigma_color, dilate):
+    """lightmap_finish's body, statement for statement, for a checked image of C >= 3 channels [H, W, C]: every channel takes the same
+    weights, whose colour distance is taken from the first three.  (lightmap_finish keeps its own text: tests mutate its source.)"""
+    f32 = np.float32
+    C = img.shape[2]
+    levels, npow, dilate = int(levels), int(normal_power_log2), int(dilate)
+    if not (0 <= levels <= 8 and 0 <= npow <= 7 and 0 <= dilate <= 256):
+        raise ValueError("levels must be in 0 .. 8, normal_power_log2 in 0 .. 7 and dilate in 0 .. 256")
+    sig_p, rch, sig_c0 = f32(sigma_plane), f32(reach), f32(sigma_color)
+    if not (sig_p > 0 and rch > 0 and sig_c0 > 0):
+        raise ValueError("sigma_plane, reach and sigma_color must be > 0 (inf turns one off)")
+    H, W = img.shape[:2]
+    zero, one = f32(0.0), f32(1.0)
+    H5 = (f32(0.0625), f32(0.25), f32(0.375), f32(0.25), f32(0.0625))
+    covered = (N[..., 0] != 0) | (N[..., 1] != 0) | (N[..., 2] != 0)
+    cur = np.where(covered[..., None], img, zero)
+    with np.errstate(all="ignore"):
+        for level in range(levels):
+            s = 1 << level
+            fs = f32(s)
+            r = rch * fs
+            rr = r * r
+            sig_c = sig_c0 / fs
+            pad = 2 * s
+            cpad, ppad, npad = (np.pad(t, ((pad, pad), (pad, pad), (0, 0))) for t in (cur, P, N))      # beyond the image: empty texels
+            sw = np.zeros((H, W), f32)
+            sc = np.zeros((H, W, C), f32)
+            for dy, dx in _LMF_TAPS:
+                ys, xs = pad + s * dy, pad + s * dx
+                cq, pq, nq = (t[ys:ys + H, xs:xs + W] for t in (cpad, ppad, npad))
+                take = covered & ((nq[..., 0] != 0) | (nq[..., 1] != 0) | (nq[..., 2] != 0))
+                D = pq - P
+                d2 = (D[..., 0] * D[..., 0] + D[..., 1] * D[..., 1]) + D[..., 2] * D[..., 2]
+                if dx != 0 or dy != 0:                # the centre always passes (0 <= 0; inf * 0 must not reject it)
+                    take = take & (d2 <= rr * f32(dx * dx + dy * dy))
+                h = H5[dy + 2] * H5[dx + 2]
+                wn = np.fmax(zero, (N[..., 0] * nq[..., 0] + N[..., 1] * nq[..., 1]) + N[..., 2] * nq[..., 2])
+                for _ in range(npow):
+                    wn = wn * wn
+                dpl = np.abs((N[..., 0] * D[..., 0] + N[..., 1] * D[..., 1]) + N[..., 2] * D[..., 2])
+                wp = np.fmax(zero, one - dpl / sig_p)
+                dc = (np.abs(cq[..., 0] - cur[..., 0]) + np.abs(cq[..., 1] - cur[..., 1])) + np.abs(cq[..., 2] - cur[..., 2])
+                wc = np.fmax(zero, one - dc / sig_c)
+                w = ((h * wn) * wp) * wc
+                sw = np.where(take, sw + w, sw)
+                sc = np.where(take[..., None], sc + w[..., None] * cq, sc)
+            cur = np.where(covered[..., None], sc / sw[..., None], zero)
+        valid = covered.copy()
+        cur = np.ascontiguousarray(cur, f32)
+        for _ in range(dilate):
+            prev_valid, prev = valid.copy(), cur.copy()
+            vpad = np.pad(prev_valid, 1)
+            near = np.zeros((H, W), bool)
+            for dy, dx in _LMF_RING:
+                near |= vpad[1 + dy:1 + dy + H, 1 + dx:1 + dx + W]
+            for y, x in np.argwhere(near & ~prev_valid):         # the pass's frontier, texel by texel: the order of the sum is the contract
+                total, count = np.zeros(C, f32), 0
+                for dy, dx in _LMF_RING:
+                    qy, qx = y + dy, x + dx
+                    if 0 <= qy < H and 0 <= qx < W and prev_valid[qy, qx]:
+                        total = total + prev[qy, qx]
+                        count += 1
+                cur[y, x] = total / f32(count)
+                valid[y, x] = True
+    return cur, valid
+
+
+def check_finish_sh_tables(sh, points, normals):
+    """(sh [H, W, 9, 3], points [H, W, 3], normals [H, W, 3]) as contiguous float32 arrays, 1 <= W, H <= 32768, for lightmap_finish_sh;
+    the guides may be lightmap_texels' [1, H, W, 3]"""
+    S = np.ascontiguousarray(sh, np.float32)
+    P, N = np.asarray(points, np.float32), np.asarray(normals, np.float32)
+    P, N = (t[0] if t.ndim == 4 and t.shape[0] == 1 else t for t in (P, N))
+    P, N = np.ascontiguousarray(P), np.ascontiguousarray(N)
+    if S.ndim != 4 or S.shape[2:] != (9, 3) or P.shape != S.shape[:2] + (3,) or N.shape != P.shape:
+        raise ValueError(f"sh must be [H, W, 9, 3] and points and normals [H, W, 3], got {S.shape}, {P.shape} and {N.shape}")
+    if not (1 <= S.shape[0] <= 32768 and 1 <= S.shape[1] <= 32768):
+        raise ValueError(f"width and height must be in 1 .. 32768, got {S.shape[1]} x {S.shape[0]}")
+    return S, P, N
+
+
+def lightmap_finish_sh(sh, points, normals, levels: int = 3, normal_power_log2: int = 5, sigma_plane: float = float("inf"),
+                       reach: float = float("inf"), sigma_color: float = float("inf"), dilate: int = 4):
+    """Finish a directional lightmap on the host (numpy only): lightmap_finish for [H, W, 9, 3] SH L2 records (bake_lightmap_sh's first
+    result).  This is the DEFINITION of mi_lightmap_finish_sh, which equals it bit for bit.  Guides, levels, taps, tap order, the B3
+    kernel, the normal and plane weights, the reach test, the dilation and the parameter ranges are lightmap_finish's; the colour
+    distance is taken from the three k = 0 coefficients of the current level, and the one weight per tap serves all 27 channels:
+    sc[j] = sc[j] + w c_q[j], then sc[j] / sw.  The dilation sums all 27 channels over the same neighbours with one count.  Empty
+    texels are 27 x +0.0.  Returns (out [H, W, 9, 3] f32, valid [H, W] bool).
+    Two identities follow: out[..., 0, :] is lightmap_finish of sh[..., 0, :] with the same parameters, and with sigma_color = inf
+    out[..., k, :] is lightmap_finish of sh[..., k, :] for every k."""
+    S, P, N = check_finish_sh_tables(sh, points, normals)
+    H, W = S.shape[:2]
+    out, valid = _lightmap_finish_channels(S.reshape(H, W, 27), P, N, levels, normal_power_log2, sigma_plane, reach, sigma_color, dilate)
+    return np.ascontiguousarray(out.reshape(H, W, 9, 3)), valid
+
+
+def check_sh_eval(sh, normals):
+    """(sh [n, 9, 3] f32, normals [n, 3] f32, leading shape) for lightmap_sh_eval: sh [..., 9, 3] and normals [..., 3] with one leading
+    shape (an atlas [H, W, 9, 3] with its [H, W, 3] normal table is one; lightmap_texels' [1, H, W, 3] as well).  The values are not
+    looked at.  Raises ValueError."""
+    S, N = np.asarray(sh, np.float32), np.asarray(normals, np.float32)
+    if N.ndim == S.ndim and N.shape[0] == 1 and N.shape[1:-1] == S.shape[:-2]:
+        N = N[0]
+    if S.ndim < 2 or S.shape[-2:] != (9, 3) or N.ndim < 1 or N.shape[-1] != 3 or N.shape[:-1] != S.shape[:-2]:
+        raise ValueError(f"sh must be [..., 9, 3] and normals [..., 3] with the same leading shape, got {S.shape} and {N.shape}")
+    if N.size // 3 >= 1 << 32:
+        raise ValueError(f"{N.size // 3} points exceed 2^32 - 1")
+    return np.ascontiguousarray(S.reshape(-1, 9, 3)), np.ascontiguousarray(N.reshape(-1, 3)), N.shape[:-1]
+
+
+def lightmap_sh_eval(sh, normals) -> np.ndarray:
+    """The irradiance of a directional lightmap on the host (numpy only): E(n) of every SH L2 record `sh` [..., 9, 3] at its normal
+    [..., 3].  This is the DEFINITION of mi_lightmap_sh_eval, which equals it bit for bit, and it is probe_volume_sample on a
+    1 x 1 x 1 volume holding the record: all f32, (x, y, z) = n / sqrt((nx nx + ny ny) + nz nz),
+    b = (1, y, z, x, x y, y z, 3 (z z) - 1, x z, x x - y y), r[k] = sh[k] * PV_K[k], e = b0 r[0] + ... + b8 r[8] left to right.
+    An all-zero normal gives +0.0.  NOT clamped: SH ringing can take E slightly below zero beside strong directional light.  The
+    atlas's own normals give the plain irradiance map, normal-mapped normals the detail.  Returns [..., 3] f32; divide by pi and
+    multiply by the albedo for a Lambertian surface's outgoing radiance."""
+    f32 = np.float32
+    S, N, shape = check_sh_eval(sh, normals)
+    with np.errstate(all="ignore"):
+        nx, ny, nz = N[:, 0], N[:, 1], N[:, 2]
+        covered = ~((nx == 0) & (ny == 0) & (nz == 0))
+        l = np.sqrt((nx * nx + ny * ny) + nz * nz)
+        x, y, z = nx / l, ny / l, nz / l
+        b = (np.ones(len(N), f32), y, z, x, x * y, y * z, f32(3.0) * (z * z) - f32(1.0), x * z, x * x - y * y)
+        r = S * PV_K[None, :, None]
+        e = b[0][:, None] * r[:, 0, :]
+        for k in range(1, 9):
+            e = e + b[k][:, None] * r[:, k, :]
+        E = np.where(covered[:, None], e, f32(0.0))
+    assert E.dtype == np.float32
+    return np.ascontiguousarray(E.reshape(shape + (3,)))
+
+
 _LMV_BLUR = tuple((dy, dx) for dy in (-1, 0, 1) for dx in (-1, 0, 1))                              # dy outer, dx inner, the centre included
 
 
@@ -1201,6 +1337,105 @@ class Context:
         abi.check(self._lib.mi_lightmap_finish_device(self._h, width, height, d_image, d_points, d_normals, levels, normal_power_log2,
                                                       sigma_plane, reach, sigma_color, dilate, d_out_image, d_out_valid, stream))
 
+    # ---- directional lightmaps: the SH L2 records of a bake, their finish and their evaluation ----
+    def _render_sh(self, entry, cam, head, want_f32, want_u8, want_sig, tri_rows, seed, flags, max_state_bytes):
+        """mi_render_points_sh / mi_bake_lightmap_sh: `head` holds the arguments between opts and out_sh"""
+        pod = cam.to_pod()
+        opts = abi.mi_render_opts(seed=seed, rank=0, world=1, variant=abi.MI_VARIANT_DEFAULT, want_signature=int(want_sig),
+                                  flags=flags, max_state_bytes=max_state_bytes)
+        H, W = cam.screen_height, cam.screen_width
+        sh = np.empty((H, W, 9, 3), np.float32)
+        f32 = np.empty((H, W, 3), np.float32) if want_f32 else None
+        u8 = np.empty((H, W, 3), np.uint8) if want_u8 else None
+        sig = np.empty((H, W), np.uint32) if want_sig else None
+        tri = np.empty((tri_rows, H, W), np.int32) if tri_rows else None
+        st = abi.mi_stats()
+        outs = [f32.ctypes.data if f32 is not None else None, u8.ctypes.data if u8 is not None else None,
+                sig.ctypes.data if sig is not None else None]
+        if tri_rows is not None:
+            outs.append(tri.ctypes.data if tri is not None else None)
+        abi.check(entry(self._h, C.byref(pod), C.byref(opts), *head, sh.ctypes.data, *outs, C.byref(st)))
+        return sh, f32, u8, sig, tri, st
+
+    def render_points_sh(self, cam: Camera, points, normals, seed: int = 1, want_f32=True, want_u8=True, want_sig=False,
+                         flags: int = 0, max_state_bytes: int = 0):
+        """mi_render_points_sh: render_points with the per-texel SH L2 radiance records as a further output.  Returns
+        (sh [H, W, 9, 3] f32, f32, u8, sig, stats): sh[k] = (2 pi / S) sum_s L_s Y_k(d_s / |d_s|) over the texel's hemisphere
+        directions, each sum an f32 chain in sample order (lightmap_sh_eval turns it into irradiance at any normal); the rest is what
+        render_points returns, bit for bit."""
+        p, n, rows = check_point_table(cam, points, normals)
+        sh, f32, u8, sig, _, st = self._render_sh(self._lib.mi_render_points_sh, cam, (p.ctypes.data, n.ctypes.data, rows), want_f32,
+                                                  want_u8, want_sig, None, seed, flags, max_state_bytes)
+        return sh, f32, u8, sig, st
+
+    def render_points_sh_device(self, cam: Camera, d_points: int, d_normals: int, rows_per_pixel: int,
+                                d_compact_sh: Optional[int] = None, d_compact: Optional[int] = None, d_sig: Optional[int] = None,
+                                sample_begin: int = 0, sample_end: Optional[int] = None, d_accum: Optional[int] = None, seed: int = 1,
+                                rank: int = 0, world: int = 1, stream: Optional[int] = None, flags: int = 0, max_state_bytes: int = 0):
+        """mi_render_points_sh_device: render_points_device with d_compact_sh, [compact_size(...)[1] * 1024, 9, 3] float32 in the
+        compact layout, the SH output and its running accumulator across progressive calls with render_probes_device's rules
+        (started by the call with sample_begin == 0, scaled by the one that reaches aa_sample_count); None is exactly
+        render_points_device."""
+        pod = cam.to_pod()
+        opts = abi.mi_render_opts(seed=seed, rank=rank, world=world, variant=abi.MI_VARIANT_DEFAULT,
+                                  want_signature=int(d_sig is not None), flags=flags, max_state_bytes=max_state_bytes)
+        st = abi.mi_stats()
+        end = cam.aa_sample_count if sample_end is None else sample_end
+        abi.check(self._lib.mi_render_points_sh_device(self._h, C.byref(pod), C.byref(opts), d_points, d_normals, rows_per_pixel,
+                                                       sample_begin, end, d_accum, d_compact_sh, d_compact, d_sig, stream, C.byref(st)))
+        return st
+
+    def bake_lightmap_sh(self, cam: Camera, mesh, jitter: bool = True, offset: float = 1e-3, seed: int = 1, transform=None,
+                         want_f32=True, want_u8=True, want_sig=False, want_triangle=False, flags: int = 0, max_state_bytes: int = 0):
+        """mi_bake_lightmap_sh: bake_lightmap with the SH L2 records.  Returns (sh [H, W, 9, 3] f32, f32, u8, sig, triangle, stats);
+        everything behind sh is what bake_lightmap returns, bit for bit."""
+        pod, keep = mesh_pod(mesh, transform)
+        out = self._render_sh(self._lib.mi_bake_lightmap_sh, cam, (C.byref(pod), abi.MI_LM_JITTER if jitter else 0, offset), want_f32,
+                              want_u8, want_sig, (cam.aa_sample_count if jitter else 1) if want_triangle else 0, seed, flags,
+                              max_state_bytes)
+        del keep
+        return out
+
+    def lightmap_finish_sh(self, sh, points, normals, levels: int = 3, normal_power_log2: int = 5, sigma_plane: float = float("inf"),
+                           reach: float = float("inf"), sigma_color: float = float("inf"), dilate: int = 4):
+        """mi_lightmap_finish_sh: the helper lightmap_finish_sh on the GPU, bit for bit.  `sh` is the raw bake [H, W, 9, 3] f32,
+        `points` and `normals` the atlas's centre table ([H, W, 3], or lightmap_texels' [1, H, W, 3]).  Returns
+        (out [H, W, 9, 3] f32, valid [H, W] bool).  No scene is needed."""
+        S, P, N = check_finish_sh_tables(sh, points, normals)
+        H, W = S.shape[:2]
+        out = np.empty((H, W, 9, 3), np.float32)
+        valid = np.empty((H, W), np.uint8)
+        abi.check(self._lib.mi_lightmap_finish_sh(self._h, W, H, S.ctypes.data, P.ctypes.data, N.ctypes.data, levels, normal_power_log2,
+                                                  sigma_plane, reach, sigma_color, dilate, out.ctypes.data, valid.ctypes.data))
+        return out, valid.astype(bool)
+
+    def lightmap_finish_sh_device(self, width: int, height: int, d_sh: int, d_points: int, d_normals: int, d_out_sh: int,
+                                  d_out_valid: Optional[int] = None, levels: int = 3, normal_power_log2: int = 5,
+                                  sigma_plane: float = float("inf"), reach: float = float("inf"), sigma_color: float = float("inf"),
+                                  dilate: int = 4, stream: Optional[int] = None):
+        """mi_lightmap_finish_sh_device: the same for records and a table held on the device (raw pointers: [H, W, 9, 3] f32 in and
+        out, which must not overlap, two [H, W, 3] f32 guides and an optional [H, W] u8 mask).  Queued on `stream`."""
+        abi.check(self._lib.mi_lightmap_finish_sh_device(self._h, width, height, d_sh, d_points, d_normals, levels, normal_power_log2,
+                                                         sigma_plane, reach, sigma_color, dilate, d_out_sh, d_out_valid, stream))
+
+    def lightmap_sh_eval(self, sh, normals) -> np.ndarray:
+        """mi_lightmap_sh_eval: the helper lightmap_sh_eval on the GPU, bit for bit: the irradiance E(n) [..., 3] f32 of every SH L2
+        record sh [..., 9, 3] at its normal [..., 3] (check_sh_eval); an all-zero normal gives zero; not clamped.  No scene is needed."""
+        S, N, shape = check_sh_eval(sh, normals)
+        E = np.empty((len(N), 3), np.float32)
+        abi.check(self._lib.mi_lightmap_sh_eval(self._h, len(N), S.ctypes.data, N.ctypes.data, E.ctypes.data))
+        return E.reshape(shape + (3,))
+
+    def lightmap_sh_eval_device(self, n: int, d_sh: int, d_normals: int, d_irradiance: int, stream: Optional[int] = None):
+        """mi_lightmap_sh_eval_device: the same for n records held on the device (raw pointers: [n, 9, 3], [n, 3] and [n, 3] f32).
+        Queued on `stream`, no synchronisation."""
+        abi.check(self._lib.mi_lightmap_sh_eval_device(self._h, n, d_sh, d_normals, d_irradiance, stream))
+
+    def last_reduce_psh_ms(self) -> float:
+        """Sum of the wf_reduce_psh launch durations (ms) of the last render: entry 7 of mi_last_pipeline_ms after render_points_sh /
+        render_points_sh_device / bake_lightmap_sh (the entry wf_reduce_sh and wf_reduce_m2 have after their renders)."""
+        return self.last_reduce_sh_ms()
+
     # ---- lightmap variance: second moments of a bake, and the finish they guide ----
     def render_points_moments(self, cam: Camera, points, normals, seed: int = 1, want_f32=True, want_u8=True, want_sig=False,
                               flags: int = 0, max_state_bytes: int = 0):
@@ -1572,7 +1807,8 @@ class Context:
 
     def last_reduce_sh_ms(self) -> float:
         """Sum of the wf_reduce_sh launch durations (ms) of the last render: entry 7 of mi_last_pipeline_ms, the SH reduction of
-        render_probes / render_probes_device; 0.0 after any other render."""
+        render_probes / render_probes_device; 0.0 after any other render but a moments or a directional bake, whose own reductions
+        (last_reduce_m2_ms, last_reduce_psh_ms) report through the same entry."""
         out = (C.c_float * 8)()
         abi.check(self._lib.mi_last_pipeline_ms(self._h, out))
         return float(out[7])
@@ -1876,7 +2112,7 @@ class Scene:                         # tracing.rs:213-218
             ctx.close()
 
     def bake_lightmap(self, mesh, width: int, height: int, samples: int, jitter: bool = True, offset: float = 1e-3, seed: int = 1,
-                      device: int = 0, finish: Optional[dict] = None, adaptive: Optional[dict] = None):
+                      device: int = 0, finish: Optional[dict] = None, adaptive: Optional[dict] = None, directional: bool = False):
         """The lightmap of `mesh` (a StaticMesh of this scene, or any objload.Mesh) in one call (mi_bake_lightmap): the RgbImage bytes
         [height, width, 3] u8 of its uv atlas, `samples` cosine-distributed gathers per texel, each from its own jittered position inside
         the texel (jitter) or all from the centre.  The atlas is rasterised, sampled and traced on the GPU: only the mesh goes up and the
@@ -1894,13 +2130,28 @@ class Scene:                         # tracing.rs:213-218
         first_samples (default: `samples`): the bake is mi_bake_lightmap_adaptive, which gives every texel first_samples samples and
         then up to max_rounds rounds of round_samples more to the texels lightmap_select picks.  Without `finish` the call returns the
         bytes of the merged mean; with a fixed finish that is applied to the merged mean; with finish={"variance": True, ...} the
-        finish takes the bake's per-texel counts (mi_lightmap_finish_var_counts)."""
+        finish takes the bake's per-texel counts (mi_lightmap_finish_var_counts).
+        `directional` (False: everything above) bakes a directional lightmap (mi_bake_lightmap_sh): the call returns
+        (sh [height, width, 9, 3] f32, mean [height, width, 3] f32) — the SH L2 radiance records lightmap_sh_eval turns into the
+        irradiance at any normal, beside the mean the plain bake stores.  With `finish` (lightmap_finish's parameters; no "variance"
+        key) both are finished on the GPU, by mi_lightmap_finish_sh and mi_lightmap_finish with the same parameters, and the call
+        returns (sh, mean, valid).  It does not combine with `adaptive`."""
         from dataclasses import replace
         cam = replace(self.camera, screen_width=int(width), screen_height=int(height), aa_sample_count=int(samples))
         check_point_table(cam, np.zeros((height, width, 3), np.float32), np.zeros((height, width, 3), np.float32))
+        if directional and (adaptive is not None or (finish is not None and "variance" in finish)):
+            raise ValueError("a directional bake combines with neither `adaptive` nor the variance-guided finish")
         ctx = Context(device)
         try:
             ctx.upload(self.flatten())
+            if directional:
+                sh, f32, _, _, _, _ = ctx.bake_lightmap_sh(cam, mesh, jitter=jitter, offset=offset, seed=seed, want_f32=True, want_u8=False)
+                if finish is None:
+                    return sh, f32
+                points, normals, _ = ctx.lightmap_texels(mesh, int(width), int(height), rows=1, offset=offset, want_triangle=False)
+                sh, valid = ctx.lightmap_finish_sh(sh, points, normals, **finish)
+                f32, _ = ctx.lightmap_finish(f32, points, normals, **finish)
+                return sh, f32, valid
             if adaptive is not None:
                 ad = dict(adaptive)
                 ad.setdefault("first_samples", int(samples))

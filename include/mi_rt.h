@@ -822,6 +822,69 @@ int  mi_probe_volume_sample(mi_ctx* ctx, const mi_probe_volume* volume, uint32_t
 int  mi_probe_volume_sample_device(mi_ctx* ctx, const mi_probe_volume* volume, uint32_t n_points, const float* points, const float* normals,
                                    float* out_irradiance, float* out_weight, void* stream);
 
+/* ---- directional lightmaps: per-texel SH L2 bake, finish and evaluation (added within ABI version 5: detect by symbol lookup) ----
+ * What mi_render_points stores per texel is the plain mean of its samples over directions UNIFORM on the hemisphere (sample_hemisphere's
+ *   pdf is 1 / (2 pi)): the mean incoming radiance, not the irradiance, and fixed to the table's normal.  These calls store the radiance
+ *   field's projection onto the nine real SH of order <= 2 per texel instead, from which mi_lightmap_sh_eval gives the cosine-weighted
+ *   irradiance E(n') for whatever normal n' the caller passes: the table's own normal for a plain irradiance map, a normal-mapped one
+ *   for the detail a lightmap is too coarse to hold.
+ * mi_render_points_sh / mi_render_points_sh_device / mi_bake_lightmap_sh: mi_render_points / _device / mi_bake_lightmap with one more
+ *   output, out_sh [H][W][9][3] f32: c_k = (2 pi / S) * sum_s L_s * Y_k(u_s), u_s = d_s / |d_s|, d_s the direction the point table's
+ *   direction stream (seed, W*H + y*W + x, s) gives sample s, L_s the sample the mean is made of, S = aa_sample_count; basis, order and
+ *   constants are mi_render_probes'.  Each of the 27 sums is accumulated in f32 in sample order from +0.0 (one multiply and one add per
+ *   sample, not fused) and scaled once at the end by 6.283185307179586f / (float)S: out_sh is bit-identical across max_state_bytes,
+ *   ranks, MI_OPT_* flags and progressive splits.  The directions cover the hemisphere about the table's normal only:
+ *   radiance from below that horizon is not sampled and counts as zero (constant radiance L gives E(n) = pi L at the table's normal).
+ *   Empty texels: a sample whose row's normal is all-zero (either sign of zero) adds nothing and draws nothing; a texel whose rows are
+ *   all empty is 27 x +0.0; with a jittered table (rows == S) a texel may have some empty rows, and the scale stays 2 pi / S, as the
+ *   mean's divisor stays S.  A non-finite point or normal gives unspecified values for that texel's 27 floats only.
+ *   Plain outputs: the mean (f32), u8 and signature outputs are mi_render_points' / mi_bake_lightmap's BIT FOR BIT: the SH sums are a
+ *   further reduction (wf_reduce_psh) of the same sample slots behind wf_reduce in every batch, which reads the normal table again; no
+ *   other kernel runs differently, and it never runs in one render with wf_reduce_m2.  Entry 7 of mi_last_pipeline_ms is its time after
+ *   these calls.  Everything else is mi_render_points' / mi_bake_lightmap's, word for word: the tables, the two streams, the camera
+ *   fields, the refusals, masks OFF, mi_reserve, max_state_bytes, stats.
+ *   Host forms: out_sh is required (MI_ERR_INVALID if NULL, checked first), the other outputs may be NULL; the records live in the buffer
+ *   mi_render_probes' do.  Device form: d_compact_sh is [tiles_padded][1024][27] f32, output AND running accumulator with
+ *   mi_render_probes_device's rules: the call with sample_begin == 0 starts the sums from zero (the buffer need not be cleared), later
+ *   calls add to it, the call that ends at aa_sample_count applies the scale; it may be copied out and back between calls; slots outside
+ *   the image and padding slots are written as zeros.  d_compact_sh == NULL is exactly mi_render_points_device.
+ * mi_lightmap_finish_sh / _device: mi_lightmap_finish for images of [H][W][9][3] records (`sh`, `out_sh`): the same guides (centre
+ *   table), levels, taps and tap order, h, wn, wp, reach test and centre-tap exemption, dilation, parameter ranges and refusals.  The
+ *   colour distance dc is taken from the three k = 0 coefficients of the current level; one weight w = ((h wn) wp) wc per tap serves
+ *   all 27 channels, sc[j] = sc[j] + w c_q[j], and the record becomes sc[j] / sw.  The dilation sums all 27 channels over the same
+ *   neighbours in the same order with one count.  Empty texels are 27 x +0.0 at every level; out_valid is mi_lightmap_finish's.
+ *   lightmap_finish_sh (Python) is the definition; the result equals it BIT FOR BIT.  Hence the k = 0 plane of the result is
+ *   mi_lightmap_finish of the k = 0 plane alone, and with sigma_color = +inf every plane k is mi_lightmap_finish of that plane.
+ *   Scratch: two [H][W][27] f32 images and two byte masks in a buffer the context owns (grown on demand, freed with the context, never
+ *   the buffers mi_reserve sized; MI_ERR_OOM); one kernel per level and per pass (lsh_atrous: one 32 x 32 tile per block, the taps
+ *   straight from HBM / L2), mi_last_kernel_ms reports their sum.  The host form blocks and out_sh may alias sh; the device form queues
+ *   on `stream`, does not synchronise except to grow its scratch, and refuses an out_sh that overlaps sh, points or normals.
+ * mi_lightmap_sh_eval / _device: `sh` [n][9][3], `normals` [n][3], out_irradiance [n][3]; an atlas is n = W*H with the flat buffers as
+ *   they stand.  An all-zero normal gives +0.0 (an atlas's normal table is a legal input).  Otherwise l, x, y, z and b[9] are
+ *   mi_probe_volume_sample's, r_k = sh_k * K_k rounded once (its K_k), e[c] = b0*r[0][c] + ... + b8*r[8][c] summed left to right: the
+ *   value mi_probe_volume_sample gives for a 1 x 1 x 1 volume holding that record, bit for bit.  lightmap_sh_eval (Python) is the
+ *   definition.  The result is NOT clamped: SH ringing can take it slightly below zero beside strong directional light.  One lane per
+ *   point; mi_last_kernel_ms reports the kernel.  NULL sh, normals or out_irradiance are MI_ERR_INVALID (checked before the context);
+ *   n == 0 is MI_OK and launches nothing.  The host form passes its arrays through a buffer the context owns. */
+int  mi_render_points_sh(mi_ctx* ctx, const mi_camera_desc* cam, const mi_render_opts* opts,
+                         const float* points, const float* normals, uint32_t rows_per_pixel, float* out_sh,
+                         float* out_rgb_f32, uint8_t* out_rgb_u8, uint32_t* out_sig, mi_stats* stats);
+int  mi_render_points_sh_device(mi_ctx* ctx, const mi_camera_desc* cam, const mi_render_opts* opts,
+                                const float* d_points, const float* d_normals, uint32_t rows_per_pixel,
+                                uint32_t sample_begin, uint32_t sample_end, void* d_accum_f32x4, void* d_compact_sh,
+                                void* d_compact_f32, void* d_sig_u32, void* stream, mi_stats* stats);
+int  mi_bake_lightmap_sh(mi_ctx* ctx, const mi_camera_desc* cam, const mi_render_opts* opts, const mi_mesh* mesh, uint32_t flags,
+                         float offset, float* out_sh, float* out_rgb_f32, uint8_t* out_rgb_u8, uint32_t* out_sig,
+                         int32_t* out_triangle, mi_stats* stats);
+int  mi_lightmap_finish_sh(mi_ctx* ctx, uint32_t width, uint32_t height, const float* sh, const float* points, const float* normals,
+                           uint32_t levels, uint32_t normal_power_log2, float sigma_plane, float reach, float sigma_color,
+                           uint32_t dilate, float* out_sh, uint8_t* out_valid);
+int  mi_lightmap_finish_sh_device(mi_ctx* ctx, uint32_t width, uint32_t height, const float* sh, const float* points, const float* normals,
+                                  uint32_t levels, uint32_t normal_power_log2, float sigma_plane, float reach, float sigma_color,
+                                  uint32_t dilate, float* out_sh, uint8_t* out_valid, void* stream);
+int  mi_lightmap_sh_eval(mi_ctx* ctx, uint32_t n, const float* sh, const float* normals, float* out_irradiance);
+int  mi_lightmap_sh_eval_device(mi_ctx* ctx, uint32_t n, const float* sh, const float* normals, float* out_irradiance, void* stream);
+
 /* Size and allocate the wavefront pipeline's HBM buffers (path state, sample slots) for
  * this camera with the image shared by `world` ranks, so that the first render does not pay the
  * allocation (about 110 GB for a whole 1080p / 256 spp frame on one GPU).  `max_state_bytes` as in
@@ -831,8 +894,8 @@ int  mi_reserve(mi_ctx* ctx, const mi_camera_desc* cam, int32_t world, uint64_t 
 /* Wavefront pipeline (MI_VARIANT_WAVEFRONT) of the most recent render: out8 = { sum of wf_main
  * launch durations, of wf_trav, of wf_reduce (ms, HIP events around every launch), launches, sum of wf_trav_f, of
  * wf_replay (the two-stage mesh traversal), sum of the spans of wf_main's class-A parts, sum of wf_reduce_sh (mi_render_probes) or of
- * wf_reduce_m2 (mi_render_points_moments, mi_bake_lightmap_moments): the two never run in one render, and the entry is 0 for every other
- * render }.  A pass after the first launches
+ * wf_reduce_m2 (mi_render_points_moments, mi_bake_lightmap_moments) or of wf_reduce_psh (mi_render_points_sh, mi_bake_lightmap_sh): no two
+ * of them run in one render, and the entry is 0 for every other render }.  A pass after the first launches
  * wf_main in two parts: the class-A blocks run on a second stream BESIDE the walkers of the previous pass (their span includes
  * waiting for CUs the walkers still hold, so it overlaps the wf_trav figure and must not be added to it), the class-B blocks
  * behind the walkers (counted under wf_main). */

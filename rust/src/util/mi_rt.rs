@@ -201,6 +201,27 @@ extern "C" {
                                   out_irradiance: *mut f32, out_weight: *mut f32) -> c_int;
     pub fn mi_probe_volume_sample_device(ctx: *mut mi_ctx, volume: *const mi_probe_volume, n_points: u32, points: *const f32,
                                          normals: *const f32, out_irradiance: *mut f32, out_weight: *mut f32, stream: *mut c_void) -> c_int;
+    // directional lightmaps (added within ABI 5): the point-table bake with out_sh [H][W][9][3] / d_compact_sh [tiles_padded][1024][27],
+    // mi_lightmap_finish for such records, and the irradiance of n records [n][9][3] at n normals [n][3]
+    pub fn mi_render_points_sh(ctx: *mut mi_ctx, cam: *const mi_camera_desc, opts: *const mi_render_opts,
+                               points: *const f32, normals: *const f32, rows_per_pixel: u32, out_sh: *mut f32,
+                               out_rgb_f32: *mut f32, out_rgb_u8: *mut u8, out_sig: *mut u32, stats: *mut mi_stats) -> c_int;
+    pub fn mi_render_points_sh_device(ctx: *mut mi_ctx, cam: *const mi_camera_desc, opts: *const mi_render_opts,
+                                      d_points: *const f32, d_normals: *const f32, rows_per_pixel: u32,
+                                      sample_begin: u32, sample_end: u32, d_accum_f32x4: *mut c_void, d_compact_sh: *mut c_void,
+                                      d_compact_f32: *mut c_void, d_sig_u32: *mut c_void, stream: *mut c_void, stats: *mut mi_stats) -> c_int;
+    pub fn mi_bake_lightmap_sh(ctx: *mut mi_ctx, cam: *const mi_camera_desc, opts: *const mi_render_opts, mesh: *const mi_mesh, flags: u32,
+                               offset: f32, out_sh: *mut f32, out_rgb_f32: *mut f32, out_rgb_u8: *mut u8, out_sig: *mut u32,
+                               out_triangle: *mut i32, stats: *mut mi_stats) -> c_int;
+    pub fn mi_lightmap_finish_sh(ctx: *mut mi_ctx, width: u32, height: u32, sh: *const f32, points: *const f32, normals: *const f32,
+                                 levels: u32, normal_power_log2: u32, sigma_plane: f32, reach: f32, sigma_color: f32,
+                                 dilate: u32, out_sh: *mut f32, out_valid: *mut u8) -> c_int;
+    pub fn mi_lightmap_finish_sh_device(ctx: *mut mi_ctx, width: u32, height: u32, sh: *const f32, points: *const f32, normals: *const f32,
+                                        levels: u32, normal_power_log2: u32, sigma_plane: f32, reach: f32, sigma_color: f32,
+                                        dilate: u32, out_sh: *mut f32, out_valid: *mut u8, stream: *mut c_void) -> c_int;
+    pub fn mi_lightmap_sh_eval(ctx: *mut mi_ctx, n: u32, sh: *const f32, normals: *const f32, out_irradiance: *mut f32) -> c_int;
+    pub fn mi_lightmap_sh_eval_device(ctx: *mut mi_ctx, n: u32, sh: *const f32, normals: *const f32, out_irradiance: *mut f32,
+                                      stream: *mut c_void) -> c_int;
     pub fn mi_reserve(ctx: *mut mi_ctx, cam: *const mi_camera_desc, world: i32, max_state_bytes: u64) -> c_int;
     pub fn mi_last_pipeline_ms(ctx: *mut mi_ctx, out8: *mut f32) -> c_int;
     pub fn mi_last_pipeline_counts(ctx: *mut mi_ctx, out8: *mut u64) -> c_int;

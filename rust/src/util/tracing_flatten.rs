@@ -378,6 +378,68 @@ impl Scene {
         (out, weight)
     }
 
+    /// A directional lightmap (mi_bake_lightmap_sh): bake_lightmap that returns, per texel, the SH L2 radiance records (render_probes'
+    /// basis and order, scaled for the hemisphere's uniform directions) and the f32 mean, both height x width texels, row-major.
+    /// eval_lightmap_sh turns the records into the irradiance at any normal.
+    pub fn bake_lightmap_sh(&self, mesh: &mi_rt::mi_mesh, width: u32, height: u32, samples: u32, jitter: bool, offset: f32,
+                            seed: u32) -> (Vec<[[f32; 3]; 9]>, Vec<[f32; 3]>) {
+        let mut cam = self.camera.flatten();
+        cam.screen_width = width;
+        cam.screen_height = height;
+        cam.aa_sample_count = samples;
+        let opts = mi_rt::mi_render_opts { seed: seed, rank: 0, world: 1, ..Default::default() };
+        let flags = if jitter { mi_rt::MI_LM_JITTER } else { 0 };
+        let n = width as usize * height as usize;
+        let mut sh = vec![[[0.0f32; 3]; 9]; n];
+        let mut mean = vec![[0.0f32; 3]; n];
+        let (psh, pmean) = (sh.as_mut_ptr() as *mut f32, mean.as_mut_ptr() as *mut f32);
+        self.with_gpu_scene(|ctx| unsafe {
+            mi_rt::mi_bake_lightmap_sh(ctx, &cam, &opts, mesh, flags, offset, psh, pmean, std::ptr::null_mut(), std::ptr::null_mut(), std::ptr::null_mut(), std::ptr::null_mut())
+        });
+        (sh, mean)
+    }
+
+    /// Finish a directional lightmap (mi_lightmap_finish_sh): finish_lightmap for SH L2 records; the colour weight is taken from the three
+    /// k = 0 coefficients and one weight per tap serves all 27 channels.  Returns the finished records and the valid mask.  Needs no
+    /// scene: an associated function.
+    pub fn finish_lightmap_sh(sh: &[[[f32; 3]; 9]], points: &[[f32; 3]], normals: &[[f32; 3]], width: u32, height: u32, levels: u32,
+                              normal_power_log2: u32, sigma_plane: f32, reach: f32, sigma_color: f32, dilate: u32) -> (Vec<[[f32; 3]; 9]>, Vec<u8>) {
+        let n = width as usize * height as usize;
+        assert!(sh.len() == n && points.len() == n && normals.len() == n, "mi_rt: sh, points and normals must hold height * width texels");
+        let mut out = vec![[[0.0f32; 3]; 9]; n];
+        let mut valid = vec![0u8; n];
+        unsafe {
+            let mut ctx = std::ptr::null_mut();
+            assert_eq!(mi_rt::mi_ctx_create(0, &mut ctx), 0, "{}", mi_rt::last_error());
+            let rc = mi_rt::mi_lightmap_finish_sh(ctx, width, height, sh.as_ptr() as *const f32, points.as_ptr() as *const f32,
+                                                  normals.as_ptr() as *const f32, levels, normal_power_log2, sigma_plane, reach, sigma_color, dilate,
+                                                  out.as_mut_ptr() as *mut f32, valid.as_mut_ptr());
+            let msg = mi_rt::last_error();
+            mi_rt::mi_ctx_destroy(ctx);
+            assert_eq!(rc, 0, "{}", msg);
+        }
+        (out, valid)
+    }
+
+    /// The irradiance of a directional lightmap (mi_lightmap_sh_eval): one SH L2 record and one normal per point (an atlas with its own
+    /// normal table gives the plain irradiance map, normal-mapped normals the detail).  An all-zero normal gives +0.0; the result is not
+    /// clamped.  Needs no scene: an associated function.
+    pub fn eval_lightmap_sh(sh: &[[[f32; 3]; 9]], normals: &[[f32; 3]]) -> Vec<[f32; 3]> {
+        assert_eq!(sh.len(), normals.len(), "mi_rt: one normal per record");
+        let mut out = vec![[0.0f32; 3]; normals.len()];
+        if normals.is_empty() { return out; }
+        unsafe {
+            let mut ctx = std::ptr::null_mut();
+            assert_eq!(mi_rt::mi_ctx_create(0, &mut ctx), 0, "{}", mi_rt::last_error());
+            let rc = mi_rt::mi_lightmap_sh_eval(ctx, normals.len() as u32, sh.as_ptr() as *const f32, normals.as_ptr() as *const f32,
+                                                out.as_mut_ptr() as *mut f32);
+            let msg = mi_rt::last_error();
+            mi_rt::mi_ctx_destroy(ctx);
+            assert_eq!(rc, 0, "{}", msg);
+        }
+        out
+    }
+
     /// flatten -> context on device 0 -> upload -> `call` -> destroy; panics with the library's message on failure.
     fn with_gpu_scene<F: FnOnce(*mut mi_rt::mi_ctx) -> i32>(&self, call: F) {
         let sb = self.flatten_scene();

@@ -89,7 +89,10 @@ of the medians, and wf_reduce_m2 (entry 7 of mi_last_pipeline_ms) beside wf_redu
 sample slots.  The tool checks that the two compact images agree bit for bit.  Finish: at --finish-sizes, levels = 5 and dilate = 8,
 mi_lightmap_finish_var_device (sigma_color 8, color_floor 1e-6) alternates with mi_lightmap_finish_device (sigma_color 8) on seeded noise
 over the covered texels, the moments those of 16 samples with a relative standard deviation of 0.3; the rows give each call's time and
-the ratio (three kernels per level instead of one)."""
+the ratio (three kernels per level instead of one).
+
+--mode directional times the directional lightmap calls (mi_render_points_sh_device, mi_lightmap_finish_sh_device,
+mi_lightmap_sh_eval_device); its protocol and the measured figures are in directional_rows' docstring."""
 import argparse
 import json
 import os
@@ -962,6 +965,162 @@ def adaptive_rows(ctx, size, bakes, first=16, per_round=16, rounds=2):
     return rows
 
 
+def directional_rows(ctx, sizes, point_counts, calls, warmup):
+    """--mode directional: the three measurements of the directional lightmap calls on device-resident tables, HIP events, `warmup`
+    warm-up and `calls` timed calls, medians (min - max beside them).
+    Bake: the drone's atlas at 1024 x 1024 (mi_lightmap_texels_device's centre table), path_depth 10, aa_sample_count 16 and 64:
+    mi_render_points_sh_device alternates call by call with mi_render_points_device; the rows give mi_last_kernel_ms of each, wf_reduce_psh
+    (entry 7 of mi_last_pipeline_ms) and its share of the call, and beside it wf_reduce_sh's time and share in a mi_render_probes_device
+    render of the same points and sample count (equal slot count).  The tool checks that the two compact images agree bit for bit.
+    Finish: at --finish-sizes, levels = 5 and dilate = 8, mi_lightmap_finish_sh_device on seeded records against NINE
+    mi_lightmap_finish_device calls on the nine planes, both with sigma_color = +inf, and checks that they give the same bits.
+    Evaluation: mi_lightmap_sh_eval_device at --volume-points points (132 B per point: 108 + 12 in, 12 out) against a device-to-device
+    copy of the same byte count timed in the same run.
+    Measured on one MI355X (DESIGN.md "Directional lightmaps" has the table and the reading):
+      wf_reduce_psh: 0.153 ms of a 13.74 ms bake at 16 samples (1.1 %), 0.574 ms of 45.72 ms at 64 (1.3 %); the plain bakes take 13.59
+        and 45.17 ms, so the SH bake costs 1.011 x and 1.012 x.  wf_reduce_sh in a probes render of the same slots: 0.134 ms of 26.4 ms
+        and 0.495 ms of 96.9 ms (0.5 %): wf_reduce_psh takes 1.14 x and 1.16 x wf_reduce_sh's time.
+      finish, levels 5 and dilate 8: 1024^2 2.03 ms against 5.23 ms for the nine calls (0.39 x); 2048^2 6.80 ms against 12.40 ms (0.55 x)
+      eval: 2^20 points 0.024 ms = 5.7 TB/s (the copy of the same 138 MB: 5.2 TB/s; both from the Infinity Cache);
+        2^22 points 0.115 ms = 4.8 TB/s (the copy of the same 554 MB: 5.7 TB/s), 0.60 of the 8 TB/s roof bench.py accounts against"""
+    from cs397raytracingsp22_amd import dist as pdist
+    dev = torch.device("cuda:0")
+    offset = float(np.float32(1e-3))
+    rows = []
+
+    def atlas(size, aa):
+        sc = scenes.config4(size, size, aa, 10)
+        drone = sc.objects[-1]
+        mesh = drone.mesh
+        t_mesh = [torch.from_numpy(np.array(a)).to(dev) for a in (mesh.positions, mesh.normals, mesh.texcoords, mesh.indices.view(np.int32))]
+        pts = torch.empty((size, size, 3), dtype=torch.float32, device=dev)
+        nrm = torch.empty((size, size, 3), dtype=torch.float32, device=dev)
+        ctx.lightmap_texels_device(t_mesh[0].data_ptr(), t_mesh[1].data_ptr(), t_mesh[2].data_ptr(), t_mesh[3].data_ptr(), mesh.n_vertices,
+                                   mesh.n_triangles, size, size, pts.data_ptr(), nrm.data_ptr(), None, rows=1, jitter=False, seed=1,
+                                   offset=offset, transform=drone.transform)
+        torch.cuda.synchronize()
+        return sc, pts, nrm
+
+    def stats(ms, key="ms"):
+        return {f"{key}_median": round(float(np.median(ms)), 4), f"{key}_min": round(float(np.min(ms)), 4), f"{key}_max": round(float(np.max(ms)), 4)}
+
+    # 1. wf_reduce_psh
+    size = 1024
+    slots = pdist.tiles_padded(size, size, 1) * pdist.TILE_PIXELS
+    for aa in (16, 64):
+        sc, pts, nrm = atlas(size, aa)
+        cam = sc.camera
+        ctx.upload(sc.flatten())
+        c_plain = torch.empty((slots, 3), dtype=torch.float32, device=dev)
+        c_sh3 = torch.empty((slots, 3), dtype=torch.float32, device=dev)
+        c_sh = torch.empty((slots, 27), dtype=torch.float32, device=dev)
+        torch.cuda.synchronize()
+        ms = {"plain": [], "sh": [], "probes": []}
+        red = {"psh": [], "probes_sh": [], "wf_reduce": []}
+        for k in range(warmup + calls):
+            ctx.render_points_sh_device(cam, pts.data_ptr(), nrm.data_ptr(), 1, c_sh.data_ptr(), c_sh3.data_ptr(), seed=1)
+            torch.cuda.synchronize()
+            if k >= warmup:
+                ms["sh"].append(ctx.last_kernel_ms())
+                red["psh"].append(ctx.last_reduce_psh_ms())
+                red["wf_reduce"].append(ctx.last_pipeline_ms()["wf_reduce_ms"])
+            ctx.render_points_device(cam, pts.data_ptr(), nrm.data_ptr(), 1, c_plain.data_ptr(), seed=1)
+            torch.cuda.synchronize()
+            if k >= warmup:
+                ms["plain"].append(ctx.last_kernel_ms())
+        same = bool(torch.equal(c_plain.view(torch.int32), c_sh3.view(torch.int32)))
+        for k in range(warmup + calls):                      # the kernel it is modelled on: the same points as probes, equal slot count
+            ctx.render_probes_device(cam, pts.data_ptr(), 1, c_sh.data_ptr(), c_sh3.data_ptr(), seed=1)
+            torch.cuda.synchronize()
+            if k >= warmup:
+                ms["probes"].append(ctx.last_kernel_ms())
+                red["probes_sh"].append(ctx.last_reduce_sh_ms())
+        base = {"mode": "directional", "mesh": "drone", "width": size, "height": size, "aa_sample_count": aa, "path_depth": cam.path_depth,
+                "covered_share": round(float((nrm != 0).any(dim=-1).float().mean()), 4), "calls": calls}
+        psh, plain, sh_ms = float(np.median(red["psh"])), float(np.median(ms["plain"])), float(np.median(ms["sh"]))
+        prb, prb_sh = float(np.median(ms["probes"])), float(np.median(red["probes_sh"]))
+        rows.append(dict(base, query="mi_render_points_device", **stats(ms["plain"])))
+        rows.append(dict(base, query="mi_render_points_sh_device", **stats(ms["sh"]), **stats(red["psh"], "wf_reduce_psh_ms"),
+                         wf_reduce_ms_median=round(float(np.median(red["wf_reduce"])), 4), wf_reduce_psh_share=round(psh / sh_ms, 5),
+                         sh_over_plain=round(sh_ms / plain, 4), compact_images_bit_identical=same))
+        rows.append(dict(base, query="mi_render_probes_device, the same points", **stats(ms["probes"]), **stats(red["probes_sh"], "wf_reduce_sh_ms"),
+                         wf_reduce_sh_share=round(prb_sh / prb, 5), wf_reduce_psh_over_wf_reduce_sh=round(psh / prb_sh, 3)))
+        for row in rows[-3:]:
+            print(json.dumps(row), flush=True)
+        if not same:
+            raise SystemExit("ray_query_bench: the SH call's image differs from mi_render_points_device's")
+        del c_plain, c_sh3, c_sh, pts, nrm
+
+    # 2. the finish: one call on 27 channels against nine calls on three
+    for size in sizes:
+        _, pts, nrm = atlas(size, 1)
+        covered = (nrm != 0).any(dim=-1)
+        gen = torch.Generator(device=dev)
+        gen.manual_seed(1)
+        rec = torch.randn((size, size, 9, 3), generator=gen, dtype=torch.float32, device=dev) * covered[..., None, None]
+        planes = [rec[:, :, k, :].contiguous() for k in range(9)]
+        out = torch.empty((size, size, 9, 3), dtype=torch.float32, device=dev)
+        out3 = [torch.empty((size, size, 3), dtype=torch.float32, device=dev) for _ in range(9)]
+        valid = torch.empty((size, size), dtype=torch.uint8, device=dev)
+        torch.cuda.synchronize()
+        ms = {"one": [], "nine": []}
+        for k in range(warmup + calls):
+            ctx.lightmap_finish_sh_device(size, size, rec.data_ptr(), pts.data_ptr(), nrm.data_ptr(), out.data_ptr(), valid.data_ptr(),
+                                          levels=FINISH_LEVELS, dilate=FINISH_DILATE)
+            torch.cuda.synchronize()
+            if k >= warmup:
+                ms["one"].append(ctx.last_kernel_ms())
+            total = 0.0
+            for j in range(9):
+                ctx.lightmap_finish_device(size, size, planes[j].data_ptr(), pts.data_ptr(), nrm.data_ptr(), out3[j].data_ptr(), valid.data_ptr(),
+                                           levels=FINISH_LEVELS, dilate=FINISH_DILATE)
+                torch.cuda.synchronize()
+                total += ctx.last_kernel_ms()
+            if k >= warmup:
+                ms["nine"].append(total)
+        same = all(bool(torch.equal(out[:, :, j, :].contiguous().view(torch.int32), out3[j].view(torch.int32))) for j in range(9))
+        base = {"mode": "directional", "mesh": "drone", "width": size, "height": size, "levels": FINISH_LEVELS, "dilate": FINISH_DILATE,
+                "covered_share": round(float(covered.float().mean()), 4), "calls": calls}
+        rows.append(dict(base, query="mi_lightmap_finish_sh_device", **stats(ms["one"])))
+        rows.append(dict(base, query="nine mi_lightmap_finish_device calls", **stats(ms["nine"])))
+        rows.append(dict(base, query="ratio one call / nine calls", ms_median=round(float(np.median(ms["one"])) / float(np.median(ms["nine"])), 4),
+                         same_bits=same))
+        for row in rows[-3:]:
+            print(json.dumps(row), flush=True)
+        if not same:
+            raise SystemExit("ray_query_bench: mi_lightmap_finish_sh_device differs from mi_lightmap_finish_device plane by plane")
+        del pts, nrm, rec, planes, out, out3, valid
+
+    # 3. the evaluation
+    for n in point_counts:
+        gen = torch.Generator(device=dev)
+        gen.manual_seed(2)
+        rec = torch.randn((n, 9, 3), generator=gen, dtype=torch.float32, device=dev)
+        nrm = torch.randn((n, 3), generator=gen, dtype=torch.float32, device=dev)
+        E = torch.empty((n, 3), dtype=torch.float32, device=dev)
+        src, dst = torch.empty(66 * n, dtype=torch.uint8, device=dev), torch.empty(66 * n, dtype=torch.uint8, device=dev)
+        torch.cuda.synchronize()
+        ms, copy_ms = [], []
+        for k in range(warmup + calls):
+            ctx.lightmap_sh_eval_device(n, rec.data_ptr(), nrm.data_ptr(), E.data_ptr())
+            torch.cuda.synchronize()
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            dst.copy_(src)
+            e1.record()
+            torch.cuda.synchronize()
+            if k >= warmup:
+                ms.append(ctx.last_kernel_ms())
+                copy_ms.append(e0.elapsed_time(e1))
+        moved = 132 * n
+        rows.append(dict(mode="directional", query="mi_lightmap_sh_eval_device", n_points=n, bytes_moved=moved, calls=calls, **stats(ms),
+                         gb_per_s=round(moved / float(np.median(ms)) / 1e6, 1), copy_ms_median=round(float(np.median(copy_ms)), 4),
+                         copy_gb_per_s=round(moved / float(np.median(copy_ms)) / 1e6, 1)))
+        print(json.dumps(rows[-1]), flush=True)
+        del rec, nrm, E, src, dst
+    return rows
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--calls", type=int, default=20, help="timed calls per row (at least 20)")
@@ -969,7 +1128,7 @@ def main():
     ap.add_argument("--width", type=int, default=1920)
     ap.add_argument("--height", type=int, default=1080)
     ap.add_argument("--configs", default="2,4")
-    ap.add_argument("--mode", choices=("intersect", "occlusion", "render", "hemisphere", "bake", "probes", "atlas", "finish", "volume", "variance", "adaptive"), default="intersect",
+    ap.add_argument("--mode", choices=("intersect", "occlusion", "render", "hemisphere", "bake", "probes", "atlas", "finish", "volume", "variance", "adaptive", "directional"), default="intersect",
                     help="intersect: the closest-hit rows; occlusion: the any-hit query against the visibility form; "
                          "render: ray-table rendering against mi_shade_rays_device; "
                          "hemisphere: hemisphere occlusion against the any-hit query on the identical pre-made rays; "
@@ -980,9 +1139,11 @@ def main():
                          "volume: irradiance-volume sampling, coherent and shuffled points, against a copy of the same bytes; "
                          "variance: the bake's second moments against the plain bake, the variance-guided finish against the fixed one; "
                          "adaptive: the adaptive bake against uniform bakes at the same and at the largest sample count, errors against a "
-                         "16 x reference, and the bookkeeping kernels' share of a round")
+                         "16 x reference, and the bookkeeping kernels' share of a round; "
+                         "directional: wf_reduce_psh's share of an SH bake, the 27-channel finish against nine 3-channel ones, and the "
+                         "evaluation against a copy of the same bytes")
     ap.add_argument("--volume-grids", default="16,32", help="--mode volume: probes per axis")
-    ap.add_argument("--volume-points", default=f"{1 << 20},{1 << 22}", help="--mode volume: point counts")
+    ap.add_argument("--volume-points", default=f"{1 << 20},{1 << 22}", help="--mode volume and --mode directional: point counts")
     ap.add_argument("--finish-sizes", default="1024,2048,4096", help="--mode finish and --mode variance: the square atlas sizes")
     ap.add_argument("--atlas-sizes", default="1024,2048", help="--mode atlas: the square atlas sizes")
     ap.add_argument("--atlas-grid", type=int, default=0, help="--mode atlas: a synthetic height field of N x N quads (2 N^2 triangles) instead "
@@ -1006,6 +1167,9 @@ def main():
         a.configs = ""
     if a.mode == "variance":
         rows += variance_rows(ctx, [int(v) for v in a.finish_sizes.split(",")], a.calls, a.warmup)
+        a.configs = ""
+    if a.mode == "directional":
+        rows += directional_rows(ctx, [int(v) for v in a.finish_sizes.split(",")], [int(v) for v in a.volume_points.split(",")], a.calls, a.warmup)
         a.configs = ""
     if a.mode == "adaptive":
         rows += adaptive_rows(ctx, int(a.atlas_sizes.split(",")[0]), a.atlas_bakes)
