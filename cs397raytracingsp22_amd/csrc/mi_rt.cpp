@@ -140,28 +140,27 @@ struct mi_ctx {
     unsigned long long* h_lm_total = nullptr; unsigned long long* h_lm_total_dev = nullptr;
     void* d_lm_mesh = nullptr; size_t lm_mesh_bytes = 0;
     void* d_lm_out = nullptr; size_t lm_out_bytes = 0;
-    // mi_lightmap_finish: two ping-pong images and two masks (grown on demand, never the buffers mi_reserve sized); the host form's
-    // uploaded image and guides, its result and its mask; lmf_atrous' > 64 KB dynamic-LDS opt-in on THIS context's device
+    // mi_lightmap_finish: two ping-pong images and two masks (grown on demand, never the buffers mi_reserve sized); lmf_atrous' > 64 KB
+    // dynamic-LDS opt-in on THIS context's device
     void* d_lmf = nullptr; size_t lmf_bytes = 0;
-    void* d_lmf_io = nullptr; size_t lmf_io_bytes = 0;
     bool lmf_big_lds_enabled = false;
-    // mi_lightmap_finish_sh: the same for [H][W][9][3] records; mi_lightmap_sh_eval (host form): the uploaded records and normals, the result
+    // mi_lightmap_finish_sh: the same for [H][W][9][3] records
     void* d_lsh = nullptr; size_t lsh_bytes = 0;
-    void* d_lsh_io = nullptr; size_t lsh_io_bytes = 0;
+    // the host forms of the lightmap post-process calls (finish, finish_sh, sh_eval, finish_var, finish_var_counts, select, gather, merge):
+    // the uploaded columns and the results of ONE call (staged; every such call synchronises before it returns)
+    void* d_io = nullptr; size_t io_bytes = 0;
     // mi_probe_volume_sample: the prepared 112-byte probe records and, behind them, the host form's uploaded sh and valid (grown on
     // demand, never the buffers mi_reserve sized)
     void* d_pv = nullptr; size_t pv_bytes = 0;
     // mi_render_points_moments / mi_bake_lightmap_moments: the compact second-moment records, then the un-permuted [H][W][3] plane;
-    // mi_lightmap_finish_var: two variance planes and the colour weight's denominators, and the host form's uploaded moments and its
-    // variance result (all grown on demand, never the buffers mi_reserve sized)
+    // mi_lightmap_finish_var: two variance planes and the colour weight's denominators (all grown on demand, never the buffers
+    // mi_reserve sized)
     void* d_m2 = nullptr; size_t m2_bytes = 0;
     void* d_lmv = nullptr; size_t lmv_bytes = 0;
-    void* d_lmv_io = nullptr; size_t lmv_io_bytes = 0;
-    // mi_lightmap_select: the variance plane, the flags, the block counts and offsets; the host forms' uploaded planes, lists and results;
+    // mi_lightmap_select: the variance plane, the flags, the block counts and offsets;
     // mi_bake_lightmap_adaptive: the running planes with the centre table, the list with its length, and a round's compact tables and
     // results (all grown on demand, never the buffers mi_reserve sized)
     void* d_lma = nullptr; size_t lma_bytes = 0;
-    void* d_lma_io = nullptr; size_t lma_io_bytes = 0;
     void* d_lma_bake = nullptr; size_t lma_bake_bytes = 0;
     void* d_lma_list = nullptr; size_t lma_list_bytes = 0;
     void* d_lma_round = nullptr; size_t lma_round_bytes = 0;
@@ -323,20 +322,17 @@ extern "C" void mi_ctx_destroy(mi_ctx* c) {
     if (c->d_rays) (void)hipFree(c->d_rays);
     if (c->d_sh) (void)hipFree(c->d_sh);
     if (c->d_lsh) (void)hipFree(c->d_lsh);
-    if (c->d_lsh_io) (void)hipFree(c->d_lsh_io);
     if (c->d_lm_hdr) (void)hipFree(c->d_lm_hdr);
     if (c->d_lm_list) (void)hipFree(c->d_lm_list);
     if (c->h_lm_total) (void)hipHostFree(c->h_lm_total);
     if (c->d_lm_mesh) (void)hipFree(c->d_lm_mesh);
     if (c->d_lm_out) (void)hipFree(c->d_lm_out);
     if (c->d_lmf) (void)hipFree(c->d_lmf);
-    if (c->d_lmf_io) (void)hipFree(c->d_lmf_io);
+    if (c->d_io) (void)hipFree(c->d_io);
     if (c->d_pv) (void)hipFree(c->d_pv);
     if (c->d_m2) (void)hipFree(c->d_m2);
     if (c->d_lmv) (void)hipFree(c->d_lmv);
-    if (c->d_lmv_io) (void)hipFree(c->d_lmv_io);
     if (c->d_lma) (void)hipFree(c->d_lma);
-    if (c->d_lma_io) (void)hipFree(c->d_lma_io);
     if (c->d_lma_bake) (void)hipFree(c->d_lma_bake);
     if (c->d_lma_list) (void)hipFree(c->d_lma_list);
     if (c->d_lma_round) (void)hipFree(c->d_lma_round);
@@ -824,19 +820,21 @@ extern "C" int mi_last_kernel_ms(mi_ctx* c, float* ms) {
     return MI_OK;
 }
 
+// What mi_last_kernel_ms measures: `queue` (a callable returning MI_OK or a recorded failure) queues its launches on `stream` between the
+// context's two timing events.  The host forms' uploads and downloads stay outside the timed region.
+template <class Queue> static int timed(mi_ctx* c, hipStream_t stream, Queue queue) {
+    HIP_TRY(hipEventRecord(c->ev_start, stream));
+    MI_TRY(queue());
+    HIP_TRY(hipEventRecord(c->ev_stop, stream));
+    c->ev_recorded = true; c->ms_summed = false;
+    return MI_OK;
+}
+
 // ------------------------------------------------------------------ ray queries (caller-supplied rays)
 // Scene::intersect_ray / Scene::shade_ray for rays the caller made.  The device forms queue ONE kernel on `stream` between the context's
 // timing events and return; they own no device memory.  The host forms move one chunk of rays at a time through a buffer of their own
 // (never the wavefront pipeline's reserved ones) and advance first_key per chunk — the same answers as one call, by the keying.
 static const uint32_t kRqChunk = 1u << 18;      // rays per chunk of the host-pointer forms: 27 MB of device scratch for a full intersect query
-// The device forms: one kernel on `stream` between the context's timing events
-#define RQ_LAUNCH_TIMED(c, stream, launch)                                                     \
-    do {                                                                                       \
-        HIP_TRY(hipEventRecord(c->ev_start, stream));                                          \
-        HIP_TRY(launch);                                                                       \
-        HIP_TRY(hipEventRecord(c->ev_stop, stream));                                           \
-        c->ev_recorded = true; c->ms_summed = false;                                           \
-    } while (0)
 // The host forms.  A per-ray column of the caller's: `bytes` per ray at `host` (nullptr: an optional column that is absent), uploaded before
 // the launch or (`out`) downloaded after it.  rq_chunked carves d_rq into one array of a chunk per column, in the order given, and for every
 // chunk uploads, calls launch(first, n, dev) — dev[i] = column i's device array, nullptr when absent — downloads and synchronises.
@@ -880,8 +878,10 @@ static int intersect_rays_device(mi_ctx* c, uint32_t n_rays, const float* origin
     a.out_object = out_object; a.out_distance = out_distance; a.out_hitpoint = out_hitpoint; a.out_normal = out_normal;
     a.out_flags = out_flags; a.out_uv = out_uv; a.out_material = (uint32_t*)out_material;
     const bool resolve = out_hitpoint || out_normal || out_flags || out_uv || out_material;     // else the visibility form
-    RQ_LAUNCH_TIMED(c, stream, launch_rq_intersect(a, lds, c->scene.gen_volumes, resolve, c->scene.lds_bytes, c->n_cus, stream));
-    return MI_OK;
+    return timed(c, stream, [&]() -> int {
+        HIP_TRY(launch_rq_intersect(a, lds, c->scene.gen_volumes, resolve, c->scene.lds_bytes, c->n_cus, stream));
+        return MI_OK;
+    });
 }
 
 static int check_interval_args(const char* who, const char* out_name, mi_ctx* c, const float* origins, const float* dirs, float t_min, float t_max, const void* out) {
@@ -928,8 +928,10 @@ static int occluded_rays_device(mi_ctx* c, uint32_t n_rays, const float* origins
     a.seed_key = seed_key(seed);
     a.first_key = first_key; a.n_rays = n_rays; a.t_min = t_min; a.t_max = t_max;
     a.origins = origins; a.dirs = dirs; a.ray_t_max = ray_t_max; a.out_occluded = out_occluded;
-    RQ_LAUNCH_TIMED(c, stream, launch_rq_occluded(a, lds, c->scene.gen_volumes, c->scene.lds_bytes, c->n_cus, stream));
-    return MI_OK;
+    return timed(c, stream, [&]() -> int {
+        HIP_TRY(launch_rq_occluded(a, lds, c->scene.gen_volumes, c->scene.lds_bytes, c->n_cus, stream));
+        return MI_OK;
+    });
 }
 
 extern "C" int mi_occluded_rays_device(mi_ctx* c, uint32_t n_rays, const float* origins, const float* dirs, float t_min, float t_max,
@@ -980,8 +982,10 @@ static int hemisphere_occlusion_device(mi_ctx* c, uint32_t n_points, const float
     a.world_radius = (flags & MI_HEMI_WORLD_RADIUS) ? 1u : 0u;
     a.t_min = t_min; a.t_max = t_max;
     a.points = points; a.normals = normals; a.out_open = out_open; a.out_bent = out_bent;
-    RQ_LAUNCH_TIMED(c, stream, launch_rq_hemi(a, lds, c->scene.gen_volumes, c->scene.lds_bytes, c->n_cus, stream));
-    return MI_OK;
+    return timed(c, stream, [&]() -> int {
+        HIP_TRY(launch_rq_hemi(a, lds, c->scene.gen_volumes, c->scene.lds_bytes, c->n_cus, stream));
+        return MI_OK;
+    });
 }
 
 extern "C" int mi_hemisphere_occlusion_device(mi_ctx* c, uint32_t n_points, const float* points, const float* normals, uint32_t first_sample,
@@ -1015,8 +1019,10 @@ static int shade_rays_device(mi_ctx* c, const mi_camera_desc* cam, uint32_t n_ra
     a.first_key = first_key; a.n_rays = n_rays;
     a.path_depth = cam->path_depth; a.path_samples = cam->path_samples; a.max_trace_dist = cam->max_trace_dist;
     a.origins = origins; a.dirs = dirs; a.out_rgb = out_rgb;
-    RQ_LAUNCH_TIMED(c, stream, launch_rq_shade(a, stream));
-    return MI_OK;
+    return timed(c, stream, [&]() -> int {
+        HIP_TRY(launch_rq_shade(a, stream));
+        return MI_OK;
+    });
 }
 
 static int check_shade_args(mi_ctx* c, const mi_camera_desc* cam, const float* origins, const float* dirs, const float* out_rgb) {
@@ -1362,17 +1368,16 @@ static int lightmap_texels_device(mi_ctx* c, const mi_mesh* mesh, uint32_t width
         const unsigned long long last = *(volatile unsigned long long*)c->h_lm_total;      // what the previous call's bins held: a hint only
         MI_TRY(size_list(std::min<unsigned long long>((unsigned long long)a.n_triangles * nt, std::max<unsigned long long>(last, 4ull * a.n_triangles + 1024))));
     }
-    HIP_TRY(hipEventRecord(c->ev_start, stream));
-    HIP_TRY(hipMemsetAsync(c->d_lm_hdr, 0, nt * 8, stream));
-    HIP_TRY(launch_lm_count(a, stream));
-    if (exact) {
-        HIP_TRY(hipStreamSynchronize(stream));
-        MI_TRY(size_list(*(volatile unsigned long long*)c->h_lm_total));
-    }
-    HIP_TRY(launch_lm_resolve(a, stream));
-    HIP_TRY(hipEventRecord(c->ev_stop, stream));
-    c->ev_recorded = true; c->ms_summed = false;
-    return MI_OK;
+    return timed(c, stream, [&]() -> int {
+        HIP_TRY(hipMemsetAsync(c->d_lm_hdr, 0, nt * 8, stream));
+        HIP_TRY(launch_lm_count(a, stream));
+        if (exact) {
+            HIP_TRY(hipStreamSynchronize(stream));
+            MI_TRY(size_list(*(volatile unsigned long long*)c->h_lm_total));
+        }
+        HIP_TRY(launch_lm_resolve(a, stream));
+        return MI_OK;
+    });
 }
 
 extern "C" int mi_lightmap_texels_device(mi_ctx* c, const mi_mesh* mesh, uint32_t width, uint32_t height, uint32_t rows, uint32_t flags,
@@ -1467,169 +1472,205 @@ extern "C" int mi_bake_lightmap_sh(mi_ctx* c, const mi_camera_desc* cam, const m
                          nullptr, out_sh);
 }
 
-// ------------------------------------------------------------------ lightmap finishing (edge-aware a-trous filter, gutter dilation)
-// tracing.py lightmap_finish as kernels, one pass per launch.  The arguments are checked before the context, as the atlas' are.
-static int check_lmf_args(const char* who, mi_ctx* c, uint32_t width, uint32_t height, const float* image, const float* points,
-                          const float* normals, uint32_t levels, uint32_t normal_power_log2, float sigma_plane, float reach,
-                          float sigma_color, uint32_t dilate, const float* out_image) {
-    if (!image || !points || !normals || !out_image) return fail(MI_ERR_INVALID, "%s: image, points, normals and out_image are required", who);
-    if (width == 0 || width > 32768u || height == 0 || height > 32768u)
-        return fail(MI_ERR_INVALID, "%s: width %u / height %u is not in 1 .. 32768", who, width, height);
-    if (levels > 8) return fail(MI_ERR_INVALID, "%s: levels %u is above 8", who, levels);
-    if (normal_power_log2 > 7) return fail(MI_ERR_INVALID, "%s: normal_power_log2 %u is above 7", who, normal_power_log2);
-    if (dilate > 256) return fail(MI_ERR_INVALID, "%s: dilate %u is above 256", who, dilate);
-    if (!(sigma_plane > 0.0f)) return fail(MI_ERR_INVALID, "%s: sigma_plane must be > 0 (+inf turns the plane weight off)", who);
-    if (!(reach > 0.0f)) return fail(MI_ERR_INVALID, "%s: reach must be > 0 (+inf turns the reach test off)", who);
-    if (!(sigma_color > 0.0f)) return fail(MI_ERR_INVALID, "%s: sigma_color must be > 0 (+inf turns the colour weight off)", who);
-    if (!c) return fail(MI_ERR_INVALID, "ctx is NULL");
+// ------------------------------------------------------------------ lightmap post-processing: what the calls below share
+static inline size_t up256(size_t x) { return (x + 255) / 256 * 256; }
+
+// The device forms never work in place: no output may overlap an input.  A null address (an optional plane that is absent) is skipped.
+struct Span { const void* at; size_t bytes; const char* name; };       // (an input needs no name)
+static int check_no_overlap(const char* who, std::initializer_list<Span> outs, std::initializer_list<Span> ins) {
+    for (const Span& o : outs)
+        for (const Span& in : ins) {
+            const uintptr_t a = (uintptr_t)o.at, b = (uintptr_t)in.at;
+            if (a && b && a < b + in.bytes && b < a + o.bytes)
+                return fail(MI_ERR_INVALID, "%s: %s overlaps an input (the passes are never in place)", who, o.name);
+        }
     return MI_OK;
 }
 
-// Queue the passes on `stream`; every pointer is a device pointer and d_out overlaps no input.  Pass p of levels + dilate reads what pass
-// p - 1 wrote; the passes alternate between the context's two images and the last one writes d_out.  The masks alternate likewise, and
-// the last one is written to d_valid when the caller wants it.
-static int lightmap_finish_device(mi_ctx* c, uint32_t width, uint32_t height, const float* d_image, const float* d_points,
-                                  const float* d_normals, uint32_t levels, uint32_t normal_power_log2, float sigma_plane, float reach,
-                                  float sigma_color, uint32_t dilate, float* d_out, uint8_t* d_valid, hipStream_t stream) {
-    const size_t n = (size_t)width * height, img = n * 3 * sizeof(float), msk = (n + 255) / 256 * 256;
-    MI_TRY(ensure(&c->d_lmf, &c->lmf_bytes, 2 * img + 2 * msk));
-    float* const ping[2] = { (float*)c->d_lmf, (float*)((char*)c->d_lmf + img) };
-    uint8_t* const mping[2] = { (uint8_t*)c->d_lmf + 2 * img, (uint8_t*)c->d_lmf + 2 * img + msk };
-    LmfArgs a{};
-    a.points = d_points; a.normals = d_normals;
-    a.width = width; a.height = height;
-    a.tiles_x = (width + kTile - 1) / kTile; a.tiles_y = (height + kTile - 1) / kTile;
-    a.npow = normal_power_log2; a.sigma_plane = sigma_plane; a.reach = reach; a.sigma_color = sigma_color;
-    const uint32_t passes = levels + dilate;
-    auto mask_target = [&](uint32_t k) { return (k == dilate && d_valid) ? d_valid : mping[k & 1u]; };
-    HIP_TRY(hipEventRecord(c->ev_start, stream));
-    a.src = d_image; a.dst = d_out; a.copy = passes == 0 ? 1u : 0u; a.mask_out = mask_target(0);
-    HIP_TRY(launch_lmf_mask(a, stream));
-    a.copy = 0;
-    for (uint32_t p = 0; p < passes; p++) {
-        a.dst = p + 1 == passes ? d_out : ping[p & 1u];
-        if (p < levels) {
-            a.step = 1u << p;
-            HIP_TRY(launch_lmf_atrous(a, a.step <= c->tune.lmf_lds_max_step, &c->lmf_big_lds_enabled, stream));
-        } else {
-            a.mask_in = mask_target(p - levels); a.mask_out = mask_target(p - levels + 1);
-            HIP_TRY(launch_lmf_dilate(a, stream));
-        }
-        a.src = a.dst;
-    }
-    HIP_TRY(hipEventRecord(c->ev_stop, stream));
-    c->ev_recorded = true; c->ms_summed = false;
+// The host forms.  A column of the caller's: `bytes` at `host` (nullptr: an optional column that is absent — no space, a null device
+// pointer), uploaded before the body (kIn, kInOut), downloaded after it (kOut, kInOut) or neither (kDevice: the caller fetches what it
+// needs of it before the next staged call).  staged lays the columns out at 256-byte-aligned offsets of the context's ONE staging buffer,
+// in the order given, uploads on c->stream, calls body(dev) — dev[i] = column i's device array — downloads and synchronises.  All uploads
+// precede all downloads, so an output of the caller's may alias one of its inputs; the copies stay outside the body's timed region.
+enum class Stage { kIn, kOut, kInOut, kDevice };
+struct StageColumn { const void* host; size_t bytes; Stage dir; };
+template <size_t N, class Body> static int staged(mi_ctx* c, const StageColumn (&cols)[N], Body body) {
+    HIP_TRY(hipSetDevice(c->device));
+    size_t off[N + 1] = { 0 };
+    for (size_t i = 0; i < N; i++) off[i + 1] = off[i] + (cols[i].host ? up256(cols[i].bytes) : 0);
+    MI_TRY(ensure(&c->d_io, &c->io_bytes, off[N]));
+    void* dev[N];
+    for (size_t i = 0; i < N; i++) dev[i] = cols[i].host ? (char*)c->d_io + off[i] : nullptr;
+    for (size_t i = 0; i < N; i++) if (dev[i] && (cols[i].dir == Stage::kIn || cols[i].dir == Stage::kInOut))
+        HIP_TRY(hipMemcpyAsync(dev[i], cols[i].host, cols[i].bytes, hipMemcpyHostToDevice, c->stream));
+    MI_TRY(body(dev));
+    for (size_t i = 0; i < N; i++) if (dev[i] && (cols[i].dir == Stage::kOut || cols[i].dir == Stage::kInOut))
+        HIP_TRY(hipMemcpyAsync((void*)cols[i].host, dev[i], cols[i].bytes, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
     return MI_OK;
+}
+
+// ------------------------------------------------------------------ lightmap finishing (edge-aware a-trous filter, gutter dilation)
+// tracing.py lightmap_finish, lightmap_finish_sh and lightmap_finish_var as kernels, one pass per launch, in three forms:
+//   plain     [H][W][3] texels; scratch d_lmf; lmf_mask, lmf_atrous per level, lmf_dilate per pass
+//   SH        [H][W][9][3] records; scratch of its own (d_lsh: a plain and an SH finish may be queued on two streams); lsh_mask, lsh_atrous, lsh_dilate
+//   variance  the plain form's texels, scratch, mask and dilation; lmv_init (with counts: lmv_init_counts), then lmv_blur and lmv_atrous per
+//             level, the variance planes in d_lmv
+// The arguments every form takes, and the variance form's further ones (counts: mi_lightmap_finish_var_counts' per-texel counts, which take
+// the place of `samples` in the initial variance — samples is then 2 — or nullptr).
+enum class FinishForm { kPlain, kSh, kVar };
+struct FinishArgs {
+    uint32_t width, height; const float* image; const float* points; const float* normals; uint32_t levels, normal_power_log2;
+    float sigma_plane, reach, sigma_color; uint32_t dilate; float* out; uint8_t* out_valid;
+};
+struct FinishVarArgs { const float* m2; const uint32_t* counts; uint32_t samples; float color_floor; float* out_var; };
+
+// The arguments are checked before the context, as the atlas' are.  What the forms check alike, in their shared order (samples: the
+// variance form's, or nullptr):
+static int check_finish_args(const char* who, const FinishArgs& f, const uint32_t* samples) {
+    if (f.width == 0 || f.width > 32768u || f.height == 0 || f.height > 32768u)
+        return fail(MI_ERR_INVALID, "%s: width %u / height %u is not in 1 .. 32768", who, f.width, f.height);
+    if (f.levels > 8) return fail(MI_ERR_INVALID, "%s: levels %u is above 8", who, f.levels);
+    if (f.normal_power_log2 > 7) return fail(MI_ERR_INVALID, "%s: normal_power_log2 %u is above 7", who, f.normal_power_log2);
+    if (f.dilate > 256) return fail(MI_ERR_INVALID, "%s: dilate %u is above 256", who, f.dilate);
+    if (samples && (*samples < 2 || *samples > 65535u)) return fail(MI_ERR_INVALID, "%s: samples %u is not in 2 .. 65535", who, *samples);
+    if (!(f.sigma_plane > 0.0f)) return fail(MI_ERR_INVALID, "%s: sigma_plane must be > 0 (+inf turns the plane weight off)", who);
+    if (!(f.reach > 0.0f)) return fail(MI_ERR_INVALID, "%s: reach must be > 0 (+inf turns the reach test off)", who);
+    return MI_OK;
+}
+
+static int check_lmf_args(const char* who, const FinishArgs& f) {
+    if (!f.image || !f.points || !f.normals || !f.out) return fail(MI_ERR_INVALID, "%s: image, points, normals and out_image are required", who);
+    MI_TRY(check_finish_args(who, f, nullptr));
+    if (!(f.sigma_color > 0.0f)) return fail(MI_ERR_INVALID, "%s: sigma_color must be > 0 (+inf turns the colour weight off)", who);
+    return MI_OK;
+}
+
+static int check_lmv_args(const char* who, const FinishArgs& f, const FinishVarArgs& v) {
+    if (!f.image || !v.m2 || !f.points || !f.normals || !f.out)
+        return fail(MI_ERR_INVALID, "%s: image, m2, points, normals and out_image are required", who);
+    MI_TRY(check_finish_args(who, f, &v.samples));
+    if (!(f.sigma_color >= 0.0f) || std::isinf(f.sigma_color)) return fail(MI_ERR_INVALID, "%s: sigma_color must be finite and >= 0", who);
+    if (!(v.color_floor > 0.0f)) return fail(MI_ERR_INVALID, "%s: color_floor must be > 0 (+inf turns the colour weight off)", who);
+    return MI_OK;
+}
+
+// Queue a finish on `stream` by its plan (render_plan.cpp finish_plan: which slot the initial step and every pass reads and writes);
+// every pointer is a device pointer and no output overlaps an input.  fv: the variance form's arguments, nullptr for the other two.
+static int finish_device(mi_ctx* c, FinishForm form, const FinishArgs& f, const FinishVarArgs* fv, hipStream_t stream) {
+    const bool sh = form == FinishForm::kSh, var = form == FinishForm::kVar;
+    const size_t n = (size_t)f.width * f.height, img = n * (sh ? kShFloats : 3) * sizeof(float), msk = up256(n), pln = msk * sizeof(float);
+    MI_TRY(ensure(sh ? &c->d_lsh : &c->d_lmf, sh ? &c->lsh_bytes : &c->lmf_bytes, 2 * img + 2 * msk));
+    if (var) MI_TRY(ensure(&c->d_lmv, &c->lmv_bytes, 3 * pln));
+    // the plan's slots, by their enums' values: two images and two masks in the form's scratch, two variance planes (and the colour weight's
+    // denominators behind them) in d_lmv
+    char* const s = (char*)(sh ? c->d_lsh : c->d_lmf);
+    float* const image[4] = { (float*)f.image, f.out, (float*)s, (float*)(s + img) };
+    uint8_t* const mask[3] = { (uint8_t*)s + 2 * img, (uint8_t*)s + 2 * img + msk, f.out_valid };
+    float* const vplane[3] = { (float*)c->d_lmv, var ? (float*)((char*)c->d_lmv + pln) : nullptr, var ? fv->out_var : nullptr };
+    LmfArgs a{};
+    a.points = f.points; a.normals = f.normals;
+    a.width = f.width; a.height = f.height;
+    a.tiles_x = (f.width + kTile - 1) / kTile; a.tiles_y = (f.height + kTile - 1) / kTile;
+    LmvArgs v{};
+    if (var) {              // the weights are lmv_atrous' then: lmf_mask and lmf_dilate read none
+        v.m2 = fv->m2; v.points = f.points; v.normals = f.normals;
+        v.width = f.width; v.height = f.height; v.tiles_x = a.tiles_x; v.tiles_y = a.tiles_y;
+        v.npow = f.normal_power_log2; v.samples = fv->samples;
+        v.sigma_plane = f.sigma_plane; v.reach = f.reach; v.sigma_color = f.sigma_color; v.color_floor = fv->color_floor;
+        v.den = v.den_out = (float*)((char*)c->d_lmv + 2 * pln);
+    } else {
+        a.npow = f.normal_power_log2; a.sigma_plane = f.sigma_plane; a.reach = f.reach; a.sigma_color = f.sigma_color;
+    }
+    const FinishPlan plan = finish_plan(f.levels, f.dilate, f.out_valid != nullptr, var, var && fv->out_var);
+    return timed(c, stream, [&]() -> int {
+        a.src = f.image; a.dst = f.out; a.copy = plan.copy; a.mask_out = mask[(int)plan.mask_init];
+        HIP_TRY(sh ? launch_lsh_mask(a, stream) : launch_lmf_mask(a, stream));
+        a.copy = 0;
+        if (var) {
+            v.src = f.image; v.var_out = vplane[(int)plan.var_init];
+            HIP_TRY(fv->counts ? launch_lmv_init_counts(v, fv->counts, false, stream) : launch_lmv_init(v, stream));
+        }
+        for (const FinishPass& p : plan.passes) {
+            a.src = image[(int)p.src]; a.dst = image[(int)p.dst];
+            if (!p.level) {
+                a.mask_in = mask[(int)p.mask_in]; a.mask_out = mask[(int)p.mask_out];
+                HIP_TRY(sh ? launch_lsh_dilate(a, stream) : launch_lmf_dilate(a, stream));
+            } else if (var) {
+                v.src = a.src; v.dst = a.dst; v.step = p.step;
+                v.var_in = vplane[(int)p.var_in]; v.var_out = vplane[(int)p.var_out];
+                HIP_TRY(launch_lmv_blur(v, stream));
+                HIP_TRY(launch_lmv_atrous(v, stream));
+            } else {
+                a.step = p.step;            // (the choice between lmf_atrous' two forms is the plain form's alone)
+                HIP_TRY(sh ? launch_lsh_atrous(a, stream)
+                           : launch_lmf_atrous(a, a.step <= c->tune.lmf_lds_max_step, &c->lmf_big_lds_enabled, stream));
+            }
+        }
+        return MI_OK;
+    });
+}
+
+// The device-pointer entry of every form.  The refusals in order: the arguments, then — the plain and the SH form — a NULL context and an
+// overlap, or — the variance forms — an overlap and a NULL context.
+static int finish_entry_device(const char* who, FinishForm form, mi_ctx* c, const FinishArgs& f, const FinishVarArgs* fv, void* stream) {
+    MI_TRY(fv ? check_lmv_args(who, f, *fv) : check_lmf_args(who, f));
+    if (!fv && !c) return fail(MI_ERR_INVALID, "ctx is NULL");
+    const size_t n = (size_t)f.width * f.height, tab = n * 3 * sizeof(float), rec = form == FinishForm::kSh ? n * kShFloats * sizeof(float) : tab;
+    MI_TRY(check_no_overlap(who, { { f.out, rec, form == FinishForm::kSh ? "out_sh" : "out_image" }, { fv ? fv->out_var : nullptr, n * 4, "out_var" } },
+                            { { f.image, rec }, { fv ? fv->m2 : nullptr, tab }, { f.points, tab }, { f.normals, tab }, { fv ? fv->counts : nullptr, n * 4 } }));
+    if (!c) return fail(MI_ERR_INVALID, "ctx is NULL");
+    HIP_TRY(hipSetDevice(c->device));
+    return finish_device(c, form, f, fv, (hipStream_t)stream);
+}
+
+// The host-pointer entry of every form: the arguments, then the context, then the call staged (out may alias image: see staged).
+static int finish_entry_host(const char* who, FinishForm form, mi_ctx* c, const FinishArgs& f, const FinishVarArgs* fv) {
+    MI_TRY(fv ? check_lmv_args(who, f, *fv) : check_lmf_args(who, f));
+    if (!c) return fail(MI_ERR_INVALID, "ctx is NULL");
+    const size_t n = (size_t)f.width * f.height, tab = n * 3 * sizeof(float), rec = form == FinishForm::kSh ? n * kShFloats * sizeof(float) : tab;
+    enum { kImage, kM2, kPoints, kNormals, kCounts, kOut, kOutVar, kOutValid };
+    const StageColumn cols[] = { { f.image, rec, Stage::kIn }, { fv ? fv->m2 : nullptr, tab, Stage::kIn }, { f.points, tab, Stage::kIn },
+                                 { f.normals, tab, Stage::kIn }, { fv ? fv->counts : nullptr, n * 4, Stage::kIn }, { f.out, rec, Stage::kOut },
+                                 { fv ? fv->out_var : nullptr, n * 4, Stage::kOut }, { f.out_valid, n, Stage::kOut } };
+    return staged(c, cols, [&](void* const* d) -> int {
+        FinishArgs df = f;
+        df.image = (const float*)d[kImage]; df.points = (const float*)d[kPoints]; df.normals = (const float*)d[kNormals];
+        df.out = (float*)d[kOut]; df.out_valid = (uint8_t*)d[kOutValid];
+        FinishVarArgs dv{};
+        if (fv) { dv = *fv; dv.m2 = (const float*)d[kM2]; dv.counts = (const uint32_t*)d[kCounts]; dv.out_var = (float*)d[kOutVar]; }
+        return finish_device(c, form, df, fv ? &dv : nullptr, c->stream);
+    });
 }
 
 extern "C" int mi_lightmap_finish_device(mi_ctx* c, uint32_t width, uint32_t height, const float* image, const float* points,
                                          const float* normals, uint32_t levels, uint32_t normal_power_log2, float sigma_plane, float reach,
                                          float sigma_color, uint32_t dilate, float* out_image, uint8_t* out_valid, void* stream) {
-    MI_TRY(check_lmf_args("mi_lightmap_finish_device", c, width, height, image, points, normals, levels, normal_power_log2, sigma_plane,
-                          reach, sigma_color, dilate, out_image));
-    const uintptr_t bytes = (uintptr_t)width * height * 3 * sizeof(float), o = (uintptr_t)out_image;
-    for (const float* in : { image, points, normals })
-        if (o < (uintptr_t)in + bytes && (uintptr_t)in < o + bytes)
-            return fail(MI_ERR_INVALID, "mi_lightmap_finish_device: out_image overlaps an input (the passes are never in place)");
-    HIP_TRY(hipSetDevice(c->device));
-    return lightmap_finish_device(c, width, height, image, points, normals, levels, normal_power_log2, sigma_plane, reach, sigma_color, dilate,
-                                  out_image, out_valid, (hipStream_t)stream);
+    return finish_entry_device("mi_lightmap_finish_device", FinishForm::kPlain, c, { width, height, image, points, normals, levels,
+                               normal_power_log2, sigma_plane, reach, sigma_color, dilate, out_image, out_valid }, nullptr, stream);
 }
 
 extern "C" int mi_lightmap_finish(mi_ctx* c, uint32_t width, uint32_t height, const float* image, const float* points, const float* normals,
                                   uint32_t levels, uint32_t normal_power_log2, float sigma_plane, float reach, float sigma_color,
                                   uint32_t dilate, float* out_image, uint8_t* out_valid) {
-    MI_TRY(check_lmf_args("mi_lightmap_finish", c, width, height, image, points, normals, levels, normal_power_log2, sigma_plane, reach,
-                          sigma_color, dilate, out_image));
-    HIP_TRY(hipSetDevice(c->device));
-    const size_t n = (size_t)width * height, img = n * 3 * sizeof(float);
-    MI_TRY(ensure(&c->d_lmf_io, &c->lmf_io_bytes, 4 * img + n));
-    char* const io = (char*)c->d_lmf_io;
-    HIP_TRY(hipMemcpyAsync(io, image, img, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(io + img, points, img, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(io + 2 * img, normals, img, hipMemcpyHostToDevice, c->stream));
-    MI_TRY(lightmap_finish_device(c, width, height, (const float*)io, (const float*)(io + img), (const float*)(io + 2 * img), levels,
-                                  normal_power_log2, sigma_plane, reach, sigma_color, dilate, (float*)(io + 3 * img),
-                                  out_valid ? (uint8_t*)(io + 4 * img) : nullptr, c->stream));
-    HIP_TRY(hipMemcpyAsync(out_image, io + 3 * img, img, hipMemcpyDeviceToHost, c->stream));      // after the uploads: out_image may alias image
-    if (out_valid) HIP_TRY(hipMemcpyAsync(out_valid, io + 4 * img, n, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return MI_OK;
+    return finish_entry_host("mi_lightmap_finish", FinishForm::kPlain, c, { width, height, image, points, normals, levels, normal_power_log2,
+                             sigma_plane, reach, sigma_color, dilate, out_image, out_valid }, nullptr);
 }
 
 // ------------------------------------------------------------------ directional lightmaps: the finish and the evaluation
-// tracing.py lightmap_finish_sh as kernels: lightmap_finish_device for [H][W][9][3] records (lsh_mask, lsh_atrous per level, lsh_dilate
-// per pass), with scratch of its own.  The arguments are mi_lightmap_finish's and are checked by the same function.
-static int lightmap_finish_sh_device(mi_ctx* c, uint32_t width, uint32_t height, const float* d_image, const float* d_points,
-                                     const float* d_normals, uint32_t levels, uint32_t normal_power_log2, float sigma_plane, float reach,
-                                     float sigma_color, uint32_t dilate, float* d_out, uint8_t* d_valid, hipStream_t stream) {
-    const size_t n = (size_t)width * height, img = n * kShFloats * sizeof(float), msk = (n + 255) / 256 * 256;
-    MI_TRY(ensure(&c->d_lsh, &c->lsh_bytes, 2 * img + 2 * msk));
-    float* const ping[2] = { (float*)c->d_lsh, (float*)((char*)c->d_lsh + img) };
-    uint8_t* const mping[2] = { (uint8_t*)c->d_lsh + 2 * img, (uint8_t*)c->d_lsh + 2 * img + msk };
-    LmfArgs a{};
-    a.points = d_points; a.normals = d_normals;
-    a.width = width; a.height = height;
-    a.tiles_x = (width + kTile - 1) / kTile; a.tiles_y = (height + kTile - 1) / kTile;
-    a.npow = normal_power_log2; a.sigma_plane = sigma_plane; a.reach = reach; a.sigma_color = sigma_color;
-    const uint32_t passes = levels + dilate;
-    auto mask_target = [&](uint32_t k) { return (k == dilate && d_valid) ? d_valid : mping[k & 1u]; };
-    HIP_TRY(hipEventRecord(c->ev_start, stream));
-    a.src = d_image; a.dst = d_out; a.copy = passes == 0 ? 1u : 0u; a.mask_out = mask_target(0);
-    HIP_TRY(launch_lsh_mask(a, stream));
-    a.copy = 0;
-    for (uint32_t p = 0; p < passes; p++) {
-        a.dst = p + 1 == passes ? d_out : ping[p & 1u];
-        if (p < levels) {
-            a.step = 1u << p;
-            HIP_TRY(launch_lsh_atrous(a, stream));
-        } else {
-            a.mask_in = mask_target(p - levels); a.mask_out = mask_target(p - levels + 1);
-            HIP_TRY(launch_lsh_dilate(a, stream));
-        }
-        a.src = a.dst;
-    }
-    HIP_TRY(hipEventRecord(c->ev_stop, stream));
-    c->ev_recorded = true; c->ms_summed = false;
-    return MI_OK;
-}
-
+// The SH form of the finish: the arguments are mi_lightmap_finish's and are checked by the same function.
 extern "C" int mi_lightmap_finish_sh_device(mi_ctx* c, uint32_t width, uint32_t height, const float* sh, const float* points,
                                             const float* normals, uint32_t levels, uint32_t normal_power_log2, float sigma_plane, float reach,
                                             float sigma_color, uint32_t dilate, float* out_sh, uint8_t* out_valid, void* stream) {
-    MI_TRY(check_lmf_args("mi_lightmap_finish_sh_device", c, width, height, sh, points, normals, levels, normal_power_log2, sigma_plane,
-                          reach, sigma_color, dilate, out_sh));
-    const uintptr_t texels = (uintptr_t)width * height, o = (uintptr_t)out_sh, obytes = texels * kShFloats * sizeof(float);
-    const struct { const float* at; uintptr_t bytes; } ins[3] = { { sh, obytes }, { points, texels * 12 }, { normals, texels * 12 } };
-    for (const auto& in : ins)
-        if (o < (uintptr_t)in.at + in.bytes && (uintptr_t)in.at < o + obytes)
-            return fail(MI_ERR_INVALID, "mi_lightmap_finish_sh_device: out_sh overlaps an input (the passes are never in place)");
-    HIP_TRY(hipSetDevice(c->device));
-    return lightmap_finish_sh_device(c, width, height, sh, points, normals, levels, normal_power_log2, sigma_plane, reach, sigma_color, dilate,
-                                     out_sh, out_valid, (hipStream_t)stream);
+    return finish_entry_device("mi_lightmap_finish_sh_device", FinishForm::kSh, c, { width, height, sh, points, normals, levels,
+                               normal_power_log2, sigma_plane, reach, sigma_color, dilate, out_sh, out_valid }, nullptr, stream);
 }
 
 extern "C" int mi_lightmap_finish_sh(mi_ctx* c, uint32_t width, uint32_t height, const float* sh, const float* points, const float* normals,
                                      uint32_t levels, uint32_t normal_power_log2, float sigma_plane, float reach, float sigma_color,
                                      uint32_t dilate, float* out_sh, uint8_t* out_valid) {
-    MI_TRY(check_lmf_args("mi_lightmap_finish_sh", c, width, height, sh, points, normals, levels, normal_power_log2, sigma_plane, reach,
-                          sigma_color, dilate, out_sh));
-    HIP_TRY(hipSetDevice(c->device));
-    // the records, points, normals, the result, its mask
-    const size_t n = (size_t)width * height, rec = n * kShFloats * sizeof(float), tab = n * 3 * sizeof(float);
-    MI_TRY(ensure(&c->d_lsh_io, &c->lsh_io_bytes, 2 * rec + 2 * tab + n));
-    char* const io = (char*)c->d_lsh_io;
-    HIP_TRY(hipMemcpyAsync(io, sh, rec, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(io + rec, points, tab, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(io + rec + tab, normals, tab, hipMemcpyHostToDevice, c->stream));
-    char* const res = io + rec + 2 * tab;
-    MI_TRY(lightmap_finish_sh_device(c, width, height, (const float*)io, (const float*)(io + rec), (const float*)(io + rec + tab), levels,
-                                     normal_power_log2, sigma_plane, reach, sigma_color, dilate, (float*)res,
-                                     out_valid ? (uint8_t*)(res + rec) : nullptr, c->stream));
-    HIP_TRY(hipMemcpyAsync(out_sh, res, rec, hipMemcpyDeviceToHost, c->stream));      // after the uploads: out_sh may alias sh
-    if (out_valid) HIP_TRY(hipMemcpyAsync(out_valid, res + rec, n, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return MI_OK;
+    return finish_entry_host("mi_lightmap_finish_sh", FinishForm::kSh, c, { width, height, sh, points, normals, levels, normal_power_log2,
+                             sigma_plane, reach, sigma_color, dilate, out_sh, out_valid }, nullptr);
 }
 
 // tracing.py lightmap_sh_eval as one kernel (lsh_eval): one lane per point.  Checked before the context; n == 0 launches nothing.
@@ -1642,11 +1683,10 @@ static int check_lsh_eval_args(const char* who, mi_ctx* c, const float* sh, cons
 static int lightmap_sh_eval_device(mi_ctx* c, uint32_t n, const float* d_sh, const float* d_normals, float* d_out, hipStream_t stream) {
     LshEvalArgs a{};
     a.sh = d_sh; a.normals = d_normals; a.out_irradiance = d_out; a.n = n;
-    HIP_TRY(hipEventRecord(c->ev_start, stream));
-    HIP_TRY(launch_lsh_eval(a, stream));
-    HIP_TRY(hipEventRecord(c->ev_stop, stream));
-    c->ev_recorded = true; c->ms_summed = false;
-    return MI_OK;
+    return timed(c, stream, [&]() -> int {
+        HIP_TRY(launch_lsh_eval(a, stream));
+        return MI_OK;
+    });
 }
 
 extern "C" int mi_lightmap_sh_eval_device(mi_ctx* c, uint32_t n, const float* sh, const float* normals, float* out_irradiance, void* stream) {
@@ -1658,159 +1698,44 @@ extern "C" int mi_lightmap_sh_eval_device(mi_ctx* c, uint32_t n, const float* sh
 
 extern "C" int mi_lightmap_sh_eval(mi_ctx* c, uint32_t n, const float* sh, const float* normals, float* out_irradiance) {
     MI_TRY(check_lsh_eval_args("mi_lightmap_sh_eval", c, sh, normals, out_irradiance));
-    if (n == 0) return MI_OK;
-    HIP_TRY(hipSetDevice(c->device));
+    if (n == 0) return MI_OK;                  // before any device call
     const size_t rec = (size_t)n * kShFloats * sizeof(float), tab = (size_t)n * 3 * sizeof(float);
-    MI_TRY(ensure(&c->d_lsh_io, &c->lsh_io_bytes, rec + 2 * tab));
-    char* const io = (char*)c->d_lsh_io;
-    HIP_TRY(hipMemcpyAsync(io, sh, rec, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(io + rec, normals, tab, hipMemcpyHostToDevice, c->stream));
-    MI_TRY(lightmap_sh_eval_device(c, n, (const float*)io, (const float*)(io + rec), (float*)(io + rec + tab), c->stream));
-    HIP_TRY(hipMemcpyAsync(out_irradiance, io + rec + tab, tab, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return MI_OK;
+    const StageColumn cols[] = { { sh, rec, Stage::kIn }, { normals, tab, Stage::kIn }, { out_irradiance, tab, Stage::kOut } };
+    return staged(c, cols, [&](void* const* d) -> int {
+        return lightmap_sh_eval_device(c, n, (const float*)d[0], (const float*)d[1], (float*)d[2], c->stream);
+    });
 }
 
 // ------------------------------------------------------------------ variance-guided lightmap finishing
-// tracing.py lightmap_finish_var as kernels: lmv_init, then lmv_blur and lmv_atrous per level, then lmf_dilate per pass.  The arguments
-// are checked before the context, as mi_lightmap_finish's are (the device form's overlap test too).
-static int check_lmv_args(const char* who, uint32_t width, uint32_t height, const float* image, const float* m2, uint32_t samples,
-                          const float* points, const float* normals, uint32_t levels, uint32_t normal_power_log2, float sigma_plane,
-                          float reach, float sigma_color, float color_floor, uint32_t dilate, const float* out_image) {
-    if (!image || !m2 || !points || !normals || !out_image)
-        return fail(MI_ERR_INVALID, "%s: image, m2, points, normals and out_image are required", who);
-    if (width == 0 || width > 32768u || height == 0 || height > 32768u)
-        return fail(MI_ERR_INVALID, "%s: width %u / height %u is not in 1 .. 32768", who, width, height);
-    if (levels > 8) return fail(MI_ERR_INVALID, "%s: levels %u is above 8", who, levels);
-    if (normal_power_log2 > 7) return fail(MI_ERR_INVALID, "%s: normal_power_log2 %u is above 7", who, normal_power_log2);
-    if (dilate > 256) return fail(MI_ERR_INVALID, "%s: dilate %u is above 256", who, dilate);
-    if (samples < 2 || samples > 65535u) return fail(MI_ERR_INVALID, "%s: samples %u is not in 2 .. 65535", who, samples);
-    if (!(sigma_plane > 0.0f)) return fail(MI_ERR_INVALID, "%s: sigma_plane must be > 0 (+inf turns the plane weight off)", who);
-    if (!(reach > 0.0f)) return fail(MI_ERR_INVALID, "%s: reach must be > 0 (+inf turns the reach test off)", who);
-    if (!(sigma_color >= 0.0f) || std::isinf(sigma_color)) return fail(MI_ERR_INVALID, "%s: sigma_color must be finite and >= 0", who);
-    if (!(color_floor > 0.0f)) return fail(MI_ERR_INVALID, "%s: color_floor must be > 0 (+inf turns the colour weight off)", who);
-    return MI_OK;
-}
-
-// Queue the passes on `stream`; every pointer is a device pointer and the outputs overlap no input.  The images and masks alternate as in
-// lightmap_finish_device (the same scratch); the variance alternates between the context's two planes, the last level writing d_var when
-// the caller wants it (the dilation passes do not touch it).  d_counts (mi_lightmap_finish_var_counts): the per-texel counts that take
-// the place of `samples` in the initial variance, or nullptr.
-static int lightmap_finish_var_device(mi_ctx* c, uint32_t width, uint32_t height, const float* d_image, const float* d_m2, uint32_t samples,
-                                      const float* d_points, const float* d_normals, uint32_t levels, uint32_t normal_power_log2,
-                                      float sigma_plane, float reach, float sigma_color, float color_floor, uint32_t dilate, float* d_out,
-                                      float* d_var, uint8_t* d_valid, hipStream_t stream, const uint32_t* d_counts = nullptr) {
-    const size_t n = (size_t)width * height, img = n * 3 * sizeof(float), msk = (n + 255) / 256 * 256, pln = msk * sizeof(float);
-    MI_TRY(ensure(&c->d_lmf, &c->lmf_bytes, 2 * img + 2 * msk));
-    MI_TRY(ensure(&c->d_lmv, &c->lmv_bytes, 3 * pln));
-    float* const ping[2] = { (float*)c->d_lmf, (float*)((char*)c->d_lmf + img) };
-    uint8_t* const mping[2] = { (uint8_t*)c->d_lmf + 2 * img, (uint8_t*)c->d_lmf + 2 * img + msk };
-    float* const vping[2] = { (float*)c->d_lmv, (float*)((char*)c->d_lmv + pln) };
-    LmfArgs a{};
-    a.points = d_points; a.normals = d_normals;
-    a.width = width; a.height = height;
-    a.tiles_x = (width + kTile - 1) / kTile; a.tiles_y = (height + kTile - 1) / kTile;
-    LmvArgs v{};
-    v.m2 = d_m2; v.points = d_points; v.normals = d_normals;
-    v.width = width; v.height = height; v.tiles_x = a.tiles_x; v.tiles_y = a.tiles_y;
-    v.npow = normal_power_log2; v.samples = samples;
-    v.sigma_plane = sigma_plane; v.reach = reach; v.sigma_color = sigma_color; v.color_floor = color_floor;
-    v.den = v.den_out = (float*)((char*)c->d_lmv + 2 * pln);
-    const uint32_t passes = levels + dilate;
-    auto mask_target = [&](uint32_t k) { return (k == dilate && d_valid) ? d_valid : mping[k & 1u]; };
-    auto var_target = [&](uint32_t k) { return (k == levels && d_var) ? d_var : vping[k & 1u]; };      // the variance after k levels
-    HIP_TRY(hipEventRecord(c->ev_start, stream));
-    a.src = d_image; a.dst = d_out; a.copy = passes == 0 ? 1u : 0u; a.mask_out = mask_target(0);
-    HIP_TRY(launch_lmf_mask(a, stream));
-    a.copy = 0;
-    v.src = d_image; v.var_out = var_target(0);
-    if (d_counts) HIP_TRY(launch_lmv_init_counts(v, d_counts, false, stream));
-    else HIP_TRY(launch_lmv_init(v, stream));
-    for (uint32_t p = 0; p < passes; p++) {
-        a.dst = p + 1 == passes ? d_out : ping[p & 1u];
-        if (p < levels) {
-            v.src = a.src; v.dst = a.dst; v.step = 1u << p;
-            v.var_in = var_target(p); v.var_out = var_target(p + 1);
-            HIP_TRY(launch_lmv_blur(v, stream));
-            HIP_TRY(launch_lmv_atrous(v, stream));
-        } else {
-            a.mask_in = mask_target(p - levels); a.mask_out = mask_target(p - levels + 1);
-            HIP_TRY(launch_lmf_dilate(a, stream));
-        }
-        a.src = a.dst;
-    }
-    HIP_TRY(hipEventRecord(c->ev_stop, stream));
-    c->ev_recorded = true; c->ms_summed = false;
-    return MI_OK;
-}
-
+// The variance form of the finish.  The counts forms refuse a missing `counts` before anything else and pass samples = 2 to the checks and
+// the kernels: one more form of lmv_init, everything else the same passes.
 extern "C" int mi_lightmap_finish_var_device(mi_ctx* c, uint32_t width, uint32_t height, const float* image, const float* m2, uint32_t samples,
                                              const float* points, const float* normals, uint32_t levels, uint32_t normal_power_log2,
                                              float sigma_plane, float reach, float sigma_color, float color_floor, uint32_t dilate,
                                              float* out_image, float* out_var, uint8_t* out_valid, void* stream) {
-    MI_TRY(check_lmv_args("mi_lightmap_finish_var_device", width, height, image, m2, samples, points, normals, levels, normal_power_log2,
-                          sigma_plane, reach, sigma_color, color_floor, dilate, out_image));
-    const uintptr_t bytes = (uintptr_t)width * height * 3 * sizeof(float);
-    const struct { uintptr_t at, bytes; const char* name; } outs[2] = { { (uintptr_t)out_image, bytes, "out_image" },
-                                                                        { (uintptr_t)out_var, bytes / 3, "out_var" } };
-    for (const auto& o : outs)
-        for (const float* in : { image, m2, points, normals })
-            if (o.at && o.at < (uintptr_t)in + bytes && (uintptr_t)in < o.at + o.bytes)
-                return fail(MI_ERR_INVALID, "mi_lightmap_finish_var_device: %s overlaps an input (the passes are never in place)", o.name);
-    if (!c) return fail(MI_ERR_INVALID, "ctx is NULL");
-    HIP_TRY(hipSetDevice(c->device));
-    return lightmap_finish_var_device(c, width, height, image, m2, samples, points, normals, levels, normal_power_log2, sigma_plane, reach,
-                                      sigma_color, color_floor, dilate, out_image, out_var, out_valid, (hipStream_t)stream);
+    const FinishVarArgs fv = { m2, nullptr, samples, color_floor, out_var };
+    return finish_entry_device("mi_lightmap_finish_var_device", FinishForm::kVar, c, { width, height, image, points, normals, levels,
+                               normal_power_log2, sigma_plane, reach, sigma_color, dilate, out_image, out_valid }, &fv, stream);
 }
 
 extern "C" int mi_lightmap_finish_var(mi_ctx* c, uint32_t width, uint32_t height, const float* image, const float* m2, uint32_t samples,
                                       const float* points, const float* normals, uint32_t levels, uint32_t normal_power_log2,
                                       float sigma_plane, float reach, float sigma_color, float color_floor, uint32_t dilate,
                                       float* out_image, float* out_var, uint8_t* out_valid) {
-    MI_TRY(check_lmv_args("mi_lightmap_finish_var", width, height, image, m2, samples, points, normals, levels, normal_power_log2,
-                          sigma_plane, reach, sigma_color, color_floor, dilate, out_image));
-    if (!c) return fail(MI_ERR_INVALID, "ctx is NULL");
-    HIP_TRY(hipSetDevice(c->device));
-    // image, m2, points, normals, the result, its variance, its mask
-    const size_t n = (size_t)width * height, img = n * 3 * sizeof(float), pln = n * sizeof(float);
-    MI_TRY(ensure(&c->d_lmv_io, &c->lmv_io_bytes, 5 * img + pln + n));
-    char* const io = (char*)c->d_lmv_io;
-    const float* const src[4] = { image, m2, points, normals };
-    for (int k = 0; k < 4; k++) HIP_TRY(hipMemcpyAsync(io + k * img, src[k], img, hipMemcpyHostToDevice, c->stream));
-    MI_TRY(lightmap_finish_var_device(c, width, height, (const float*)io, (const float*)(io + img), samples, (const float*)(io + 2 * img),
-                                      (const float*)(io + 3 * img), levels, normal_power_log2, sigma_plane, reach, sigma_color, color_floor,
-                                      dilate, (float*)(io + 4 * img), out_var ? (float*)(io + 5 * img) : nullptr,
-                                      out_valid ? (uint8_t*)(io + 5 * img + pln) : nullptr, c->stream));
-    HIP_TRY(hipMemcpyAsync(out_image, io + 4 * img, img, hipMemcpyDeviceToHost, c->stream));      // after the uploads: out_image may alias image
-    if (out_var) HIP_TRY(hipMemcpyAsync(out_var, io + 5 * img, pln, hipMemcpyDeviceToHost, c->stream));
-    if (out_valid) HIP_TRY(hipMemcpyAsync(out_valid, io + 5 * img + pln, n, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return MI_OK;
+    const FinishVarArgs fv = { m2, nullptr, samples, color_floor, out_var };
+    return finish_entry_host("mi_lightmap_finish_var", FinishForm::kVar, c, { width, height, image, points, normals, levels,
+                             normal_power_log2, sigma_plane, reach, sigma_color, dilate, out_image, out_valid }, &fv);
 }
 
-// mi_lightmap_finish_var with the per-texel counts of an adaptive bake in place of `samples`: one more form of lmv_init, everything else
-// the same passes.
 extern "C" int mi_lightmap_finish_var_counts_device(mi_ctx* c, uint32_t width, uint32_t height, const float* image, const float* m2,
                                                     const uint32_t* counts, const float* points, const float* normals, uint32_t levels,
                                                     uint32_t normal_power_log2, float sigma_plane, float reach, float sigma_color,
                                                     float color_floor, uint32_t dilate, float* out_image, float* out_var, uint8_t* out_valid,
                                                     void* stream) {
     if (!counts) return fail(MI_ERR_INVALID, "mi_lightmap_finish_var_counts_device: counts is required");
-    MI_TRY(check_lmv_args("mi_lightmap_finish_var_counts_device", width, height, image, m2, 2, points, normals, levels, normal_power_log2,
-                          sigma_plane, reach, sigma_color, color_floor, dilate, out_image));
-    const uintptr_t bytes = (uintptr_t)width * height * 3 * sizeof(float);
-    const struct { uintptr_t at, bytes; const char* name; } outs[2] = { { (uintptr_t)out_image, bytes, "out_image" },
-                                                                        { (uintptr_t)out_var, bytes / 3, "out_var" } };
-    const struct { uintptr_t at, bytes; } ins[5] = { { (uintptr_t)image, bytes }, { (uintptr_t)m2, bytes }, { (uintptr_t)points, bytes },
-                                                     { (uintptr_t)normals, bytes }, { (uintptr_t)counts, bytes / 3 } };
-    for (const auto& o : outs)
-        for (const auto& in : ins)
-            if (o.at && o.at < in.at + in.bytes && in.at < o.at + o.bytes)
-                return fail(MI_ERR_INVALID, "mi_lightmap_finish_var_counts_device: %s overlaps an input (the passes are never in place)", o.name);
-    if (!c) return fail(MI_ERR_INVALID, "ctx is NULL");
-    HIP_TRY(hipSetDevice(c->device));
-    return lightmap_finish_var_device(c, width, height, image, m2, 2, points, normals, levels, normal_power_log2, sigma_plane, reach,
-                                      sigma_color, color_floor, dilate, out_image, out_var, out_valid, (hipStream_t)stream, counts);
+    const FinishVarArgs fv = { m2, counts, 2, color_floor, out_var };
+    return finish_entry_device("mi_lightmap_finish_var_counts_device", FinishForm::kVar, c, { width, height, image, points, normals, levels,
+                               normal_power_log2, sigma_plane, reach, sigma_color, dilate, out_image, out_valid }, &fv, stream);
 }
 
 extern "C" int mi_lightmap_finish_var_counts(mi_ctx* c, uint32_t width, uint32_t height, const float* image, const float* m2,
@@ -1818,33 +1743,14 @@ extern "C" int mi_lightmap_finish_var_counts(mi_ctx* c, uint32_t width, uint32_t
                                              uint32_t normal_power_log2, float sigma_plane, float reach, float sigma_color, float color_floor,
                                              uint32_t dilate, float* out_image, float* out_var, uint8_t* out_valid) {
     if (!counts) return fail(MI_ERR_INVALID, "mi_lightmap_finish_var_counts: counts is required");
-    MI_TRY(check_lmv_args("mi_lightmap_finish_var_counts", width, height, image, m2, 2, points, normals, levels, normal_power_log2,
-                          sigma_plane, reach, sigma_color, color_floor, dilate, out_image));
-    if (!c) return fail(MI_ERR_INVALID, "ctx is NULL");
-    HIP_TRY(hipSetDevice(c->device));
-    // image, m2, points, normals, the result, its variance, the counts, the mask
-    const size_t n = (size_t)width * height, img = n * 3 * sizeof(float), pln = n * sizeof(float);
-    MI_TRY(ensure(&c->d_lmv_io, &c->lmv_io_bytes, 5 * img + 2 * pln + n));
-    char* const io = (char*)c->d_lmv_io;
-    const float* const src[4] = { image, m2, points, normals };
-    for (int k = 0; k < 4; k++) HIP_TRY(hipMemcpyAsync(io + k * img, src[k], img, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(io + 5 * img + pln, counts, pln, hipMemcpyHostToDevice, c->stream));
-    MI_TRY(lightmap_finish_var_device(c, width, height, (const float*)io, (const float*)(io + img), 2, (const float*)(io + 2 * img),
-                                      (const float*)(io + 3 * img), levels, normal_power_log2, sigma_plane, reach, sigma_color, color_floor,
-                                      dilate, (float*)(io + 4 * img), out_var ? (float*)(io + 5 * img) : nullptr,
-                                      out_valid ? (uint8_t*)(io + 5 * img + 2 * pln) : nullptr, c->stream,
-                                      (const uint32_t*)(io + 5 * img + pln)));
-    HIP_TRY(hipMemcpyAsync(out_image, io + 4 * img, img, hipMemcpyDeviceToHost, c->stream));      // after the uploads: out_image may alias image
-    if (out_var) HIP_TRY(hipMemcpyAsync(out_var, io + 5 * img, pln, hipMemcpyDeviceToHost, c->stream));
-    if (out_valid) HIP_TRY(hipMemcpyAsync(out_valid, io + 5 * img + 2 * pln, n, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return MI_OK;
+    const FinishVarArgs fv = { m2, counts, 2, color_floor, out_var };
+    return finish_entry_host("mi_lightmap_finish_var_counts", FinishForm::kVar, c, { width, height, image, points, normals, levels,
+                             normal_power_log2, sigma_plane, reach, sigma_color, dilate, out_image, out_valid }, &fv);
 }
 
 // ------------------------------------------------------------------ adaptive lightmap baking (select, gather, merge, the whole bake)
 // tracing.py lightmap_select, lightmap_gather and lightmap_merge as kernels, and the bake that composes them with the moments render.
 // The arguments are checked before the context, as the finishing pass's are.
-static inline size_t up256(size_t x) { return (x + 255) / 256 * 256; }
 static const uint32_t kLmaMaxList = 1u << 25;          // mi_bake_lightmap_adaptive's capacity: 128 MiB of texel numbers
 static const uint32_t kLmaCompactWidth = 1024;         // ... and the width of its compact tables
 
@@ -1884,14 +1790,12 @@ static int lightmap_select_device(mi_ctx* c, uint32_t width, uint32_t height, co
     a.out_index = d_index; a.out_count = d_count;
     a.width = width; a.height = height; a.blocks = (uint32_t)nb; a.capacity = capacity;
     a.target_rel = target_rel; a.target_abs = target_abs;
-    if (timed) HIP_TRY(hipEventRecord(c->ev_start, stream));
-    HIP_TRY(launch_lmv_init_counts(v, d_counts, true, stream));
-    HIP_TRY(launch_lma_select(a, stream));
-    if (timed) {
-        HIP_TRY(hipEventRecord(c->ev_stop, stream));
-        c->ev_recorded = true; c->ms_summed = false;
-    }
-    return MI_OK;
+    auto queue = [&]() -> int {
+        HIP_TRY(launch_lmv_init_counts(v, d_counts, true, stream));
+        HIP_TRY(launch_lma_select(a, stream));
+        return MI_OK;
+    };
+    return timed ? ::timed(c, stream, queue) : queue();          // (the helper, which the parameter hides)
 }
 
 extern "C" int mi_lightmap_select_device(mi_ctx* c, uint32_t width, uint32_t height, const float* image, const float* m2,
@@ -1911,25 +1815,24 @@ extern "C" int mi_lightmap_select(mi_ctx* c, uint32_t width, uint32_t height, co
     MI_TRY(check_select_args("mi_lightmap_select", width, height, image, m2, counts, normals, target_rel, target_abs, capacity, out_index,
                              out_count));
     if (!c) return fail(MI_ERR_INVALID, "ctx is NULL");
-    HIP_TRY(hipSetDevice(c->device));
-    // image, m2, normals, counts, the error plane, the list (no longer than the atlas), its length
-    const size_t n = (size_t)width * height, img = up256(n * 3 * sizeof(float)), pln = up256(n * sizeof(float));
+    // The list (no longer than the atlas) stays on the device: only the entries the count says were written are copied out afterwards, so
+    // that the entries behind them stay unwritten in the caller's array.
+    const size_t n = (size_t)width * height;
     const uint32_t cap = (uint32_t)std::min<size_t>(capacity, n);
-    const size_t o_list = 3 * img + 2 * pln, o_count = o_list + up256((size_t)cap * 4);
-    MI_TRY(ensure(&c->d_lma_io, &c->lma_io_bytes, o_count + 256));
-    char* const io = (char*)c->d_lma_io;
-    const float* const src[3] = { image, m2, normals };
-    for (int k = 0; k < 3; k++) HIP_TRY(hipMemcpyAsync(io + k * img, src[k], n * 3 * sizeof(float), hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(io + 3 * img, counts, n * 4, hipMemcpyHostToDevice, c->stream));
-    MI_TRY(lightmap_select_device(c, width, height, (const float*)io, (const float*)(io + img), (const uint32_t*)(io + 3 * img),
-                                  (const float*)(io + 2 * img), target_rel, target_abs, cap, (uint32_t*)(io + o_list),
-                                  (uint32_t*)(io + o_count), out_error ? (float*)(io + 3 * img + pln) : nullptr, c->stream, true));
     uint32_t count = 0;
-    HIP_TRY(hipMemcpyAsync(&count, io + o_count, 4, hipMemcpyDeviceToHost, c->stream));
-    if (out_error) HIP_TRY(hipMemcpyAsync(out_error, io + 3 * img + pln, n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
+    const void* d_list = nullptr;
+    enum { kImage, kM2, kNormals, kCounts, kCount, kError, kList };
+    const StageColumn cols[] = { { image, n * 12, Stage::kIn }, { m2, n * 12, Stage::kIn }, { normals, n * 12, Stage::kIn },
+                                 { counts, n * 4, Stage::kIn }, { &count, 4, Stage::kOut }, { out_error, n * 4, Stage::kOut },
+                                 { out_index, (size_t)cap * 4, Stage::kDevice } };
+    MI_TRY(staged(c, cols, [&](void* const* d) -> int {
+        d_list = d[kList];
+        return lightmap_select_device(c, width, height, (const float*)d[kImage], (const float*)d[kM2], (const uint32_t*)d[kCounts],
+                                      (const float*)d[kNormals], target_rel, target_abs, cap, (uint32_t*)d[kList], (uint32_t*)d[kCount],
+                                      (float*)d[kError], c->stream, true);
+    }));
     const uint32_t held = std::min(count, cap);            // the entries behind them are not written
-    if (held) HIP_TRY(hipMemcpy(out_index, io + o_list, (size_t)held * 4, hipMemcpyDeviceToHost));
+    if (held) HIP_TRY(hipMemcpy(out_index, d_list, (size_t)held * 4, hipMemcpyDeviceToHost));
     *out_count = count;
     return MI_OK;
 }
@@ -1956,41 +1859,37 @@ static LmaListArgs gather_args(uint32_t width, uint32_t height, uint32_t rows, u
     return a;
 }
 
+// lma_gather on `stream` between the context's timing events; every pointer is a device pointer
+static int lightmap_gather_device(mi_ctx* c, uint32_t width, uint32_t height, uint32_t rows, uint32_t n, const uint32_t* d_index,
+                                  const float* d_points, const float* d_normals, uint32_t cw, float* d_out_points, float* d_out_normals,
+                                  hipStream_t stream) {
+    return timed(c, stream, [&]() -> int {
+        HIP_TRY(launch_lma_gather(gather_args(width, height, rows, n, d_index, d_points, d_normals, cw, d_out_points, d_out_normals), stream));
+        return MI_OK;
+    });
+}
+
 extern "C" int mi_lightmap_gather_device(mi_ctx* c, uint32_t width, uint32_t height, uint32_t rows, uint32_t n, const uint32_t* index,
                                          const float* points, const float* normals, uint32_t cw, float* out_points, float* out_normals,
                                          void* stream) {
     MI_TRY(check_gather_args("mi_lightmap_gather_device", width, height, rows, n, index, points, normals, cw, out_points, out_normals));
     if (!c) return fail(MI_ERR_INVALID, "ctx is NULL");
     HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(hipEventRecord(c->ev_start, (hipStream_t)stream));
-    HIP_TRY(launch_lma_gather(gather_args(width, height, rows, n, index, points, normals, cw, out_points, out_normals), (hipStream_t)stream));
-    HIP_TRY(hipEventRecord(c->ev_stop, (hipStream_t)stream));
-    c->ev_recorded = true; c->ms_summed = false;
-    return MI_OK;
+    return lightmap_gather_device(c, width, height, rows, n, index, points, normals, cw, out_points, out_normals, (hipStream_t)stream);
 }
 
 extern "C" int mi_lightmap_gather(mi_ctx* c, uint32_t width, uint32_t height, uint32_t rows, uint32_t n, const uint32_t* index,
                                   const float* points, const float* normals, uint32_t cw, float* out_points, float* out_normals) {
     MI_TRY(check_gather_args("mi_lightmap_gather", width, height, rows, n, index, points, normals, cw, out_points, out_normals));
     if (!c) return fail(MI_ERR_INVALID, "ctx is NULL");
-    HIP_TRY(hipSetDevice(c->device));
     // the list, the two source tables, the two compact tables
-    const size_t lst = up256((size_t)n * 4), tab = up256((size_t)rows * width * height * 3 * sizeof(float));
-    const size_t slots = ((size_t)n + cw - 1) / cw * cw, out = up256((size_t)rows * slots * 3 * sizeof(float));
-    MI_TRY(ensure(&c->d_lma_io, &c->lma_io_bytes, lst + 2 * tab + 2 * out));
-    char* const io = (char*)c->d_lma_io;
-    HIP_TRY(hipMemcpyAsync(io, index, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(io + lst, points, (size_t)rows * width * height * 12, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(io + lst + tab, normals, (size_t)rows * width * height * 12, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipEventRecord(c->ev_start, c->stream));
-    HIP_TRY(launch_lma_gather(gather_args(width, height, rows, n, (const uint32_t*)io, (const float*)(io + lst), (const float*)(io + lst + tab),
-                                          cw, (float*)(io + lst + 2 * tab), (float*)(io + lst + 2 * tab + out)), c->stream));
-    HIP_TRY(hipEventRecord(c->ev_stop, c->stream));
-    c->ev_recorded = true; c->ms_summed = false;
-    HIP_TRY(hipMemcpyAsync(out_points, io + lst + 2 * tab, (size_t)rows * slots * 12, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipMemcpyAsync(out_normals, io + lst + 2 * tab + out, (size_t)rows * slots * 12, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return MI_OK;
+    const size_t tab = (size_t)rows * width * height * 12, slots = ((size_t)n + cw - 1) / cw * cw, out = (size_t)rows * slots * 12;
+    const StageColumn cols[] = { { index, (size_t)n * 4, Stage::kIn }, { points, tab, Stage::kIn }, { normals, tab, Stage::kIn },
+                                 { out_points, out, Stage::kOut }, { out_normals, out, Stage::kOut } };
+    return staged(c, cols, [&](void* const* d) -> int {
+        return lightmap_gather_device(c, width, height, rows, n, (const uint32_t*)d[0], (const float*)d[1], (const float*)d[2], cw,
+                                      (float*)d[3], (float*)d[4], c->stream);
+    });
 }
 
 static int check_merge_args(const char* who, uint32_t width, uint32_t height, uint32_t n, const uint32_t* index, const float* mean,
@@ -2010,17 +1909,24 @@ static LmaListArgs merge_args(uint32_t width, uint32_t height, uint32_t n, const
     return a;
 }
 
+// lma_merge on `stream` between the context's timing events; every pointer is a device pointer.  n == 0 launches nothing, and still
+// records the events.
+static int lightmap_merge_device(mi_ctx* c, uint32_t width, uint32_t height, uint32_t n, const uint32_t* d_index, const float* d_mean,
+                                 const float* d_m2_round, uint32_t round_samples, float* d_image, float* d_m2, uint32_t* d_counts,
+                                 hipStream_t stream) {
+    return timed(c, stream, [&]() -> int {
+        if (n) HIP_TRY(launch_lma_merge(merge_args(width, height, n, d_index, d_mean, d_m2_round, round_samples, d_image, d_m2, d_counts), stream));
+        return MI_OK;
+    });
+}
+
 extern "C" int mi_lightmap_merge_device(mi_ctx* c, uint32_t width, uint32_t height, uint32_t n, const uint32_t* index, const float* mean,
                                         const float* m2_round, uint32_t round_samples, float* image, float* m2, uint32_t* counts,
                                         void* stream) {
     MI_TRY(check_merge_args("mi_lightmap_merge_device", width, height, n, index, mean, m2_round, round_samples, image, m2, counts));
     if (!c) return fail(MI_ERR_INVALID, "ctx is NULL");
     HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(hipEventRecord(c->ev_start, (hipStream_t)stream));
-    if (n) HIP_TRY(launch_lma_merge(merge_args(width, height, n, index, mean, m2_round, round_samples, image, m2, counts), (hipStream_t)stream));
-    HIP_TRY(hipEventRecord(c->ev_stop, (hipStream_t)stream));
-    c->ev_recorded = true; c->ms_summed = false;
-    return MI_OK;
+    return lightmap_merge_device(c, width, height, n, index, mean, m2_round, round_samples, image, m2, counts, (hipStream_t)stream);
 }
 
 extern "C" int mi_lightmap_merge(mi_ctx* c, uint32_t width, uint32_t height, uint32_t n, const uint32_t* index, const float* mean,
@@ -2035,28 +1941,14 @@ extern "C" int mi_lightmap_merge(mi_ctx* c, uint32_t width, uint32_t height, uin
         if (dup != seen.end()) return fail(MI_ERR_INVALID, "mi_lightmap_merge: the list holds texel %u twice", *dup);
     }
     if (!c) return fail(MI_ERR_INVALID, "ctx is NULL");
-    HIP_TRY(hipSetDevice(c->device));
-    // the list, the round's two tables, the three planes
-    const size_t npix = (size_t)width * height, lst = up256((size_t)n * 4), rnd = up256((size_t)n * 12), img = up256(npix * 12);
-    MI_TRY(ensure(&c->d_lma_io, &c->lma_io_bytes, lst + 2 * rnd + 2 * img + up256(npix * 4)));
-    char* const io = (char*)c->d_lma_io;
-    char* const d_img = io + lst + 2 * rnd;
-    HIP_TRY(hipMemcpyAsync(io, index, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(io + lst, mean, (size_t)n * 12, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(io + lst + rnd, m2_round, (size_t)n * 12, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(d_img, image, npix * 12, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(d_img + img, m2, npix * 12, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(d_img + 2 * img, counts, npix * 4, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipEventRecord(c->ev_start, c->stream));
-    if (n) HIP_TRY(launch_lma_merge(merge_args(width, height, n, (const uint32_t*)io, (const float*)(io + lst), (const float*)(io + lst + rnd),
-                                               round_samples, (float*)d_img, (float*)(d_img + img), (uint32_t*)(d_img + 2 * img)), c->stream));
-    HIP_TRY(hipEventRecord(c->ev_stop, c->stream));
-    c->ev_recorded = true; c->ms_summed = false;
-    HIP_TRY(hipMemcpyAsync(image, d_img, npix * 12, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipMemcpyAsync(m2, d_img + img, npix * 12, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipMemcpyAsync(counts, d_img + 2 * img, npix * 4, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return MI_OK;
+    // the list, the round's two tables, the three planes (which make the round trip with n == 0 too)
+    const size_t npix = (size_t)width * height;
+    const StageColumn cols[] = { { index, (size_t)n * 4, Stage::kIn }, { mean, (size_t)n * 12, Stage::kIn }, { m2_round, (size_t)n * 12, Stage::kIn },
+                                 { image, npix * 12, Stage::kInOut }, { m2, npix * 12, Stage::kInOut }, { counts, npix * 4, Stage::kInOut } };
+    return staged(c, cols, [&](void* const* d) -> int {
+        return lightmap_merge_device(c, width, height, n, (const uint32_t*)d[0], (const float*)d[1], (const float*)d[2], round_samples,
+                                     (float*)d[3], (float*)d[4], (uint32_t*)d[5], c->stream);
+    });
 }
 
 // The whole bake: mi_bake_lightmap_moments' body for round 0, then per round select, gather, the moments render of the compact table and
@@ -2217,12 +2109,11 @@ extern "C" int mi_probe_volume_sample_device(mi_ctx* c, const mi_probe_volume* v
     a.sh = v->sh; a.valid = v->valid; a.records = (float*)c->d_pv;
     a.n_points = n_points; a.points = points; a.normals = normals; a.out_irradiance = out_irradiance; a.out_weight = out_weight;
     const hipStream_t s = (hipStream_t)stream;
-    HIP_TRY(hipEventRecord(c->ev_start, s));
-    HIP_TRY(launch_pv_prepare(a, s));
-    HIP_TRY(launch_pv_sample(a, s));
-    HIP_TRY(hipEventRecord(c->ev_stop, s));
-    c->ev_recorded = true; c->ms_summed = false;
-    return MI_OK;
+    return timed(c, s, [&]() -> int {
+        HIP_TRY(launch_pv_prepare(a, s));
+        HIP_TRY(launch_pv_sample(a, s));
+        return MI_OK;
+    });
 }
 
 extern "C" int mi_probe_volume_sample(mi_ctx* c, const mi_probe_volume* v, uint32_t n_points, const float* points, const float* normals,
@@ -2243,12 +2134,11 @@ extern "C" int mi_probe_volume_sample(mi_ctx* c, const mi_probe_volume* v, uint3
     return rq_chunked(c, n_points, cols, [&](uint32_t first, uint32_t n, void* const* d) {
         a.n_points = n; a.points = (const float*)d[0]; a.normals = (const float*)d[1];
         a.out_irradiance = (float*)d[2]; a.out_weight = (float*)d[3];
-        HIP_TRY(hipEventRecord(c->ev_start, c->stream));
-        if (first == 0) HIP_TRY(launch_pv_prepare(a, c->stream));
-        HIP_TRY(launch_pv_sample(a, c->stream));
-        HIP_TRY(hipEventRecord(c->ev_stop, c->stream));
-        c->ev_recorded = true; c->ms_summed = false;
-        return (int)MI_OK;
+        return timed(c, c->stream, [&]() -> int {
+            if (first == 0) HIP_TRY(launch_pv_prepare(a, c->stream));
+            HIP_TRY(launch_pv_sample(a, c->stream));
+            return MI_OK;
+        });
     });
 }
 

@@ -430,4 +430,24 @@ PassPlan plan_pass(const PassSchedule& s, uint32_t it, bool exact, const PassHdr
     return p;
 }
 
+FinishPlan finish_plan(uint32_t levels, uint32_t dilate, bool want_valid, bool with_var, bool want_var) {
+    const uint32_t passes = levels + dilate;
+    auto mask_after = [&](uint32_t k) { return k == dilate && want_valid ? FinishMask::kCaller : k & 1u ? FinishMask::kPing1 : FinishMask::kPing0; };
+    auto var_after = [&](uint32_t k) {
+        return !with_var ? FinishVar::kNone : k == levels && want_var ? FinishVar::kCaller : k & 1u ? FinishVar::kPing1 : FinishVar::kPing0;
+    };
+    FinishPlan plan{ passes == 0 ? 1u : 0u, mask_after(0), var_after(0), {} };
+    FinishImage src = FinishImage::kInput;
+    for (uint32_t p = 0; p < passes; p++) {
+        const bool level = p < levels;
+        const uint32_t k = p - levels;                                      // a dilation's number
+        const FinishImage dst = p + 1 == passes ? FinishImage::kOutput : p & 1u ? FinishImage::kPing1 : FinishImage::kPing0;
+        plan.passes.push_back({ level, level ? 1u << p : 0u, src, dst,
+                                level ? FinishMask::kNone : mask_after(k), level ? FinishMask::kNone : mask_after(k + 1),
+                                level ? var_after(p) : FinishVar::kNone, level ? var_after(p + 1) : FinishVar::kNone });
+        src = dst;
+    }
+    return plan;
+}
+
 }  // namespace pt

@@ -1,8 +1,9 @@
 // render_plan.hpp — the host-side decisions of a render: camera validation, the tile grid of the partition, the camera
 // constants, the primary-ray tile masks, which meshes are walked two-stage, the wavefront pipeline's batch, and its pass schedule:
 // what is fixed for a render (pass_schedule), whether a pass may be launched before the previous header has arrived (pass_gate), and
-// its grids, parts and in-launch rounds (plan_pass).  Host code only: no HIP call, no context; mi_rt.cpp plans with these, then
-// launches.  All of it runs on the CPU: tests/test_render_plan_host.py and tests/test_pass_schedule_host.py, through
+// its grids, parts and in-launch rounds (plan_pass); and the buffers every launch of a lightmap finish reads and writes (finish_plan).
+// Host code only: no HIP call, no context; mi_rt.cpp plans with these, then launches.  All of it runs on the CPU:
+// tests/test_render_plan_host.py, tests/test_pass_schedule_host.py and tests/test_finish_plan_host.py, through
 // tests/cpp/render_plan_shim.cpp; the launches a schedule leads to are pinned by tests/test_gpu_walkers.py (golden/pass_schedule_counts.json).
 #pragma once
 #include <cstdint>
@@ -95,5 +96,29 @@ PassGate pass_gate(const PassSchedule& s, uint32_t it, uint32_t seen, uint32_t l
 // grid_all: the pass as one launch, grid_a / grid_b: its class-A / class-B part when split; last: this launch ends every path.
 struct PassPlan { bool stop, split, tail, last; uint32_t grid_all, grid_a, grid_b, fuse_max, fuse_min; };
 PassPlan plan_pass(const PassSchedule& s, uint32_t it, bool exact, const PassHdr& last);
+
+// ---- the lightmap finish's pass plan: which buffer every launch of a finish (plain, SH or variance-guided) reads and writes
+// A finish is an initial step (the mask kernel; with_var: the initial variance) and levels + dilate passes, the levels first, level p
+// at step 1 << p.  The rules:
+//   * pass 0 reads the caller's input, pass p what pass p - 1 wrote; pass p writes the caller's output when it is the last one,
+//     otherwise image ping p & 1.  With no pass at all the mask kernel copies (copy = 1) the input into the caller's output.
+//   * the mask after k dilations lives in the caller's buffer when k == dilate && want_valid, otherwise in mask ping k & 1: the initial
+//     step writes the mask after 0, dilation k reads the mask after k and writes the mask after k + 1.
+//   * the variance after k levels lives in the caller's buffer when k == levels && want_var, otherwise in variance ping k & 1: the
+//     initial step writes the variance after 0, level k reads the variance after k and writes the variance after k + 1; the dilations
+//     never touch it.
+// kNone: the step does not touch that kind (a level's masks, a dilation's variances, every variance without with_var).
+// CPU tests: tests/test_finish_plan_host.py.
+enum class FinishImage : uint8_t { kInput, kOutput, kPing0, kPing1 };
+enum class FinishMask : uint8_t { kPing0, kPing1, kCaller, kNone };
+enum class FinishVar : uint8_t { kPing0, kPing1, kCaller, kNone };
+struct FinishPass {
+    bool level; uint32_t step;              // a filter level at `step`, or a dilation (step 0)
+    FinishImage src, dst;
+    FinishMask mask_in, mask_out;
+    FinishVar var_in, var_out;
+};
+struct FinishPlan { uint32_t copy; FinishMask mask_init; FinishVar var_init; std::vector<FinishPass> passes; };
+FinishPlan finish_plan(uint32_t levels, uint32_t dilate, bool want_valid, bool with_var, bool want_var);
 
 }  // namespace pt

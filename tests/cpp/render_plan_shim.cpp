@@ -1,6 +1,6 @@
 // render_plan_shim.cpp — CPU entry into the render planner (TEST INFRASTRUCTURE, compiled with render_plan.cpp and
-// scene_compile.cpp by tests/test_render_plan_host.py and tests/test_pass_schedule_host.py with g++ -ffp-contract=off into a
-// shared object loaded with ctypes).
+// scene_compile.cpp by tests/test_render_plan_host.py, tests/test_pass_schedule_host.py and tests/test_finish_plan_host.py with
+// g++ -ffp-contract=off into a shared object loaded with ctypes).
 // It stands in for mi_rt.cpp: it defines pt::fail and runs what a render plans, without a GPU.
 #include <cstdarg>
 #include <cstdio>
@@ -128,4 +128,28 @@ extern "C" void pass_schedule_query(ScheduleQuery* q) {
     const pt::PassPlan p = pt::plan_pass(s, q->it, q->exact != 0, h);
     q->stop = p.stop; q->p_split = p.split; q->tail = p.tail; q->last = p.last;
     q->grid_all = p.grid_all; q->grid_a = p.grid_a; q->grid_b = p.grid_b; q->p_fuse_max = p.fuse_max; q->p_fuse_min = p.fuse_min;
+}
+
+// mirrored by FinishPlanQuery in tests/test_finish_plan_host.py: finish_plan as plain numbers, the slots by their enums' values
+// (images: 0 input, 1 output, 2 ping 0, 3 ping 1; masks and variances: 0 ping 0, 1 ping 1, 2 the caller's, 3 untouched).  A pass is
+// eight words: level, step, image in, image out, mask in, mask out, variance in, variance out.  Returns the number of passes, or
+// -1 when they do not fit passes_cap.
+struct FinishPlanQuery {
+    uint32_t levels, dilate; int32_t want_valid, with_var, want_var;
+    uint32_t copy, mask_init, var_init;
+    uint32_t* passes; uint32_t passes_cap;
+};
+
+extern "C" int finish_plan_query(FinishPlanQuery* q) {
+    const pt::FinishPlan plan = pt::finish_plan(q->levels, q->dilate, q->want_valid != 0, q->with_var != 0, q->want_var != 0);
+    q->copy = plan.copy; q->mask_init = (uint32_t)plan.mask_init; q->var_init = (uint32_t)plan.var_init;
+    if (plan.passes.size() > q->passes_cap) return -1;
+    uint32_t* w = q->passes;
+    for (const pt::FinishPass& p : plan.passes) {
+        const uint32_t words[8] = { p.level ? 1u : 0u, p.step, (uint32_t)p.src, (uint32_t)p.dst, (uint32_t)p.mask_in, (uint32_t)p.mask_out,
+                                    (uint32_t)p.var_in, (uint32_t)p.var_out };
+        memcpy(w, words, sizeof words);
+        w += 8;
+    }
+    return (int)plan.passes.size();
 }

@@ -113,6 +113,75 @@ def test_device_form_refuses_an_overlapping_output(gpu_ctx):
     assert (buf.cpu().numpy() == -7.0).all()
 
 
+# ---------------------------------------------------------------- 2b. the host forms' shared staging buffer
+def _staging_steps():
+    """(name, call(ctx) -> tuple of arrays, the numpy helper's tuple) for the host forms of finish, finish_sh, finish_var,
+    finish_var_counts and select -> gather -> merge, a larger input (the 75 x 41 noisy cube) and a smaller one (the 9 x 9 single texel,
+    the 1 x 1 image) alternating across the families.  The helpers' results are computed here, once."""
+    from cs397raytracingsp22_amd import (lightmap_finish_sh, lightmap_finish_var, lightmap_gather, lightmap_merge, lightmap_select)
+    import adaptive_batteries as ab
+    import variance_batteries as vb
+    from test_lightmap_sh_host import sh_records
+
+    big = fb.cube_batteries(2, 1)[1]                              # 75 x 41, noisy
+    single, one = fb.single_texel_battery(3), fb.limiting_batteries()[1]
+    big_var, single_var, one_var = (vb.from_finish_battery(b) for b in (big, single, one))
+    steps = []
+
+    def finish(b):
+        _, img, P, N, params = b
+        steps.append((f"finish {b[0]}", lambda ctx: ctx.lightmap_finish(img, P, N, **params), lightmap_finish(img, P, N, **params)))
+
+    def finish_sh(b):
+        _, img, P, N, params = b
+        sh = sh_records(img)
+        steps.append((f"finish_sh {b[0]}", lambda ctx: ctx.lightmap_finish_sh(sh, P, N, **params), lightmap_finish_sh(sh, P, N, **params)))
+
+    def finish_var(b):
+        _, img, m2, S, P, N, params = b
+        steps.append((f"finish_var {b[0]}", lambda ctx: ctx.lightmap_finish_var(img, m2, S, P, N, **params),
+                      lightmap_finish_var(img, m2, S, P, N, **params)))
+
+    def finish_var_counts(b):
+        _, img, m2, _, P, N, params = b
+        cnt = ab.from_variance_battery(b, "mixed", 0.0)[3]
+        steps.append((f"finish_var_counts {b[0]}", lambda ctx: ctx.lightmap_finish_var_counts(img, m2, cnt, P, N, **params),
+                      lightmap_finish_var(img, m2, cnt, P, N, **params)))
+
+    def adaptive(b):
+        """select at both targets zero (every covered texel with some variance), gather at cw = 7, merge a made-up round"""
+        name, img, m2, cnt, P, N, _, _ = ab.everything_noisy_selected(ab.from_variance_battery(b, "single", 0.0))
+        index, count, err = lightmap_select(img, m2, cnt, N, 0.0, 0.0)
+        assert count == index.size >= 1, name
+        mean, m2r = ab.round_for((name, img, m2), index)
+        want = (index, err) + tuple(lightmap_gather(index, P[None], N[None], 7)) + tuple(lightmap_merge(index, mean, m2r, 4, img, m2, cnt))
+
+        def call(ctx):
+            got_index, got_count, got_err = ctx.lightmap_select(img, m2, cnt, N, 0.0, 0.0)
+            assert got_count == count, name
+            return ((got_index, got_err) + tuple(ctx.lightmap_gather(got_index, P[None], N[None], 7))
+                    + tuple(ctx.lightmap_merge(got_index, mean, m2r, 4, img, m2, cnt)))
+        steps.append((f"select, gather, merge {name}", call, want))
+
+    finish(big), finish_sh(single), finish_var(big_var), finish_var_counts(one_var), adaptive(big_var)
+    finish(one), finish_sh(big), finish_var(single_var), finish_var_counts(big_var), adaptive(single_var)
+    return steps
+
+
+def test_host_forms_share_one_staging_buffer(gpu_ctx):
+    """Every host form of the lightmap post-process calls stages its columns in ONE buffer of the context, each at its own offsets: a
+    call must read nothing another family's call left there, larger or smaller, before or after.  The sequence runs forward and
+    reversed on one context; every result has the numpy helper's bits."""
+    steps = _staging_steps()
+    for order in (steps, steps[::-1]):
+        for name, call, want in order:
+            got = call(gpu_ctx)
+            assert len(got) == len(want), name
+            for k, (g, w) in enumerate(zip(got, want)):
+                g, w = np.ascontiguousarray(g), np.ascontiguousarray(w)
+                assert g.dtype == w.dtype and g.shape == w.shape and np.array_equal(g.view(np.uint8), w.view(np.uint8)), (name, k)
+
+
 # ---------------------------------------------------------------- 3. non-finite input
 def test_a_nan_texel_spoils_its_footprint_only(gpu_ctx):
     W, H = fb.CUBE_SIZES[0]
