@@ -84,6 +84,11 @@ int  orc_generate_rays(const mi_camera_desc* cam, uint32_t seed, uint32_t x, uin
 /* Scene::shade_ray (tracing.rs:300-324) for one ray. */
 int  orc_shade(const orc_scene* s, const mi_camera_desc* cam, const float origin[3], const float dir[3],
                uint32_t seed, uint32_t pixel, uint32_t sample, float out_rgb[3]);
+/* orc_shade that also returns the path signature of that one sample (out_sig may be NULL), the term orc_render sums
+ * per pixel.  The stream (seed, pixel, sample) is used from its start — orc_render's sample has spent generate_ray's
+ * draws on it first — so for the camera's own ray the two agree as far as no draw decides: the first segment. */
+int  orc_shade_sig(const orc_scene* s, const mi_camera_desc* cam, const float origin[3], const float dir[3],
+                   uint32_t seed, uint32_t pixel, uint32_t sample, float out_rgb[3], uint32_t* out_sig);
 /* Material::scatter (materials.rs) on a synthetic hit: out = dir[3], brdf[3], pdf. */
 int  orc_scatter(const mi_material* m, const float hitpoint[3], const float normal[3], int frontface,
                  const float ray_dir[3], uint32_t seed, uint32_t pixel, uint32_t sample, float out[7]);

@@ -102,6 +102,8 @@ def load(path=None):
                                       C.POINTER(orc_hit_rec)]
         lib.orc_generate_rays.argtypes = [C.POINTER(abi.mi_camera_desc), C.c_uint32, C.c_uint32, C.c_uint32, vp]
         lib.orc_shade.argtypes = [vp, C.POINTER(abi.mi_camera_desc), fp, fp, C.c_uint32, C.c_uint32, C.c_uint32, fp]
+        lib.orc_shade_sig.argtypes = [vp, C.POINTER(abi.mi_camera_desc), fp, fp, C.c_uint32, C.c_uint32, C.c_uint32, fp,
+                                      C.POINTER(C.c_uint32)]
         lib.orc_scatter.argtypes = [C.POINTER(abi.mi_material), fp, fp, C.c_int, fp, C.c_uint32, C.c_uint32,
                                     C.c_uint32, fp]
         lib.orc_reflect.argtypes = [fp, fp, fp]
@@ -187,6 +189,17 @@ class OracleScene:
         if rc != 0:
             raise RuntimeError(f"orc_shade failed: {rc}")
         return np.array(out[:], np.float32)
+
+    def shade_sig(self, cam, origin, direction, seed=1, pixel=0, sample=0):
+        """shade() plus the path signature of that sample: (rgb f32 [3], sig)."""
+        pod = cam.to_pod()
+        out = (C.c_float * 3)()
+        sig = C.c_uint32()
+        rc = self._lib.orc_shade_sig(self._h, C.byref(pod), _f3(origin), _f3(direction), seed, pixel, sample, out,
+                                     C.byref(sig))
+        if rc != 0:
+            raise RuntimeError(f"orc_shade_sig failed: {rc}")
+        return np.array(out[:], np.float32), int(sig.value)
 
     def bvh_stats(self, mesh=0):
         a, b, c = C.c_int(), C.c_int(), C.c_int()

@@ -424,14 +424,20 @@ int orc_generate_rays(const mi_camera_desc* cam, uint32_t seed, uint32_t x, uint
     return MI_OK;
 }
 
-int orc_shade(const orc_scene* s, const mi_camera_desc* cam, const float origin[3], const float dir[3],
-              uint32_t seed, uint32_t pixel, uint32_t sample, float out_rgb[3]) {
+int orc_shade_sig(const orc_scene* s, const mi_camera_desc* cam, const float origin[3], const float dir[3],
+                  uint32_t seed, uint32_t pixel, uint32_t sample, float out_rgb[3], uint32_t* out_sig) {
     int rc = check_camera(cam); if (rc != MI_OK) return rc;
     orc_path p; p.cnt = NULL; p.sig = 0; orc_rng_init(&p.rng, seed, pixel, sample);
     orc_ray ray; ray.origin = v3_from(origin); ray.direction = v3_from(dir);
     v3 c = (cam->shading_mode == MI_SHADE_PHONG) ? phong_shade_ray(s, cam, &ray, &p) : shade_ray(s, cam, &ray, 0, &p);
     out_rgb[0] = c.x; out_rgb[1] = c.y; out_rgb[2] = c.z;
+    if (out_sig) *out_sig = p.sig;
     return MI_OK;
+}
+
+int orc_shade(const orc_scene* s, const mi_camera_desc* cam, const float origin[3], const float dir[3],
+              uint32_t seed, uint32_t pixel, uint32_t sample, float out_rgb[3]) {
+    return orc_shade_sig(s, cam, origin, dir, seed, pixel, sample, out_rgb, NULL);
 }
 
 int orc_scatter(const mi_material* m, const float hitpoint[3], const float normal[3], int frontface,

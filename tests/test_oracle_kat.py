@@ -516,3 +516,50 @@ def test_same_static_mesh_twice_in_scene_objects(orc):
     b, _, _, _ = oscene(orc, [m], cam).render(cam, seed=3)
     assert np.array_equal(a, b)
     assert orc.OracleScene(flat2).intersect((0, 1, 0), (0, 0, -1)).object == 0
+
+
+# ---------------------------------------------------------------- orc_shade_sig: the signature of a caller-made ray
+def _shade_sig_image(orc, o, cam, W, H, seed):
+    got32, gotsig = np.empty((H, W, 3), np.float32), np.empty((H, W), np.uint32)
+    for y in range(H):
+        for x in range(W):
+            ray = orc.generate_rays(cam, x, y, seed=seed)[0]
+            got32[y, x], gotsig[y, x] = o.shade_sig(cam, ray[0:3], ray[3:6], seed=seed, pixel=y * W + x, sample=0)
+            plain = o.shade(cam, ray[0:3], ray[3:6], seed=seed, pixel=y * W + x, sample=0)
+            assert np.array_equal(plain.view(np.uint32), got32[y, x].view(np.uint32))   # orc_shade is the same call
+    return got32, gotsig
+
+
+@pytest.mark.parametrize("config", ["config2", "config5"])
+def test_shade_sig_on_the_cameras_own_rays_is_orc_render(orc, config):
+    """orc_shade_sig on the ray of orc_generate_rays, stream (seed, y*W + x, 0), against orc_render at aa_sample_count == 1.
+
+    render_pixel makes the ray on the sample's stream first (generate_ray: two gen_range draws and the lens disk's rejection loop,
+    tracing.rs:167-168,184) and shades on what is left of it; orc_shade_sig, like orc_shade and every ray-table entry point of the
+    product, shades on the stream from its start.  The two therefore walk the same path exactly as far as no draw decides anything:
+    the first segment.  So the pin is made at path_depth == 1, where sig_hit folds the first hit's distance bits and object and
+    sig_end_depth folds no RNG state: signature and f32 colour of every pixel that hits are orc_render's, bit for bit, and a pixel
+    that misses is black on both sides.  At the scene's own depth the first hit must still be the one orc_render saw, which the
+    depth-1 signature already states; what is checked there is that orc_shade is orc_shade_sig and that the signatures tell paths
+    apart.  (At full depth a bit-for-bit match with orc_render does not exist for a stream that starts afresh: the RNG state the
+    path ends with is part of the signature.  Measured at path_depth 6: 15 of 384 signatures and 261 colours equal in config2, 17 and
+    271 in config5 — the colours that agree are black.)"""
+    W, H, seed = 24, 16, 5
+    sc = getattr(scenes, config)(width=W, height=H, spp=1, depth=1)
+    cam = sc.camera
+    o = orc.OracleScene(sc.flatten())
+    f32, _, sig, _ = o.render(cam, seed=seed)
+    got32, gotsig = _shade_sig_image(orc, o, cam, W, H, seed)
+    hit = np.array([[o.intersect(*np.split(orc.generate_rays(cam, x, y, seed=seed)[0], 2), t_max=cam.max_trace_dist, seed=seed,
+                                 pixel=y * W + x).hit for x in range(W)] for y in range(H)], bool)
+    print(f"{config}: {int(hit.sum())} of {W * H} pixels hit, {len(np.unique(sig[hit]))} distinct depth-1 signatures, "
+          f"{int((f32.sum(axis=-1) > 0).sum())} lit")
+    assert hit.sum() >= W * H // 2 and len(np.unique(sig[hit])) > hit.sum() // 2
+    assert np.array_equal(gotsig[hit], sig[hit])
+    assert np.array_equal(got32.view(np.uint32), f32.view(np.uint32))
+    assert (f32.sum(axis=-1) > 0).any() and not f32[~hit].any()
+    # the scene's own depth: the same entry point, a signature per path
+    cam.path_depth = 6
+    full32, fullsig = _shade_sig_image(orc, o, cam, W, H, seed)
+    assert len(np.unique(fullsig)) > W * H // 2
+    assert np.isfinite(full32).all() and (full32.sum(axis=-1) > 0).sum() > W * H // 4
