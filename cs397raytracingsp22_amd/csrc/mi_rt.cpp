@@ -57,23 +57,20 @@ hipError_t launch_tonemap(const float* image, uint8_t* out, uint32_t n_pixels, f
 hipError_t launch_selftest_rcp(unsigned long long* d_mismatches, hipStream_t stream);
 hipError_t launch_lm_count(const LmArgs& a, hipStream_t stream);
 hipError_t launch_lm_resolve(const LmArgs& a, hipStream_t stream);
-hipError_t launch_lmf_mask(const LmfArgs& a, hipStream_t stream);
+hipError_t launch_lmf_mask(const LmfArgs& a, bool sh, hipStream_t stream);
 hipError_t launch_lmf_atrous(const LmfArgs& a, bool lds, bool* big_lds_enabled, hipStream_t stream);
-hipError_t launch_lmf_dilate(const LmfArgs& a, hipStream_t stream);
+hipError_t launch_lmf_dilate(const LmfArgs& a, bool sh, hipStream_t stream);
 hipError_t launch_pv_prepare(const PvArgs& a, hipStream_t stream);
 hipError_t launch_pv_sample(const PvArgs& a, hipStream_t stream);
 hipError_t launch_wf_reduce_m2(const WfArgs& a, bool first_batch, bool last_batch, hipStream_t stream);
-hipError_t launch_lmv_init(const LmvArgs& a, hipStream_t stream);
+hipError_t launch_lmv_init(const LmvArgs& a, const uint32_t* counts, bool few_inf, hipStream_t stream);
 hipError_t launch_lmv_blur(const LmvArgs& a, hipStream_t stream);
 hipError_t launch_lmv_atrous(const LmvArgs& a, hipStream_t stream);
-hipError_t launch_lmv_init_counts(const LmvArgs& a, const uint32_t* counts, bool few_inf, hipStream_t stream);
 hipError_t launch_lma_select(const LmaArgs& a, hipStream_t stream);
 hipError_t launch_lma_gather(const LmaListArgs& a, hipStream_t stream);
 hipError_t launch_lma_merge(const LmaListArgs& a, hipStream_t stream);
 hipError_t launch_wf_reduce_psh(const WfArgs& a, bool first_batch, bool last_batch, hipStream_t stream);
-hipError_t launch_lsh_mask(const LmfArgs& a, hipStream_t stream);
 hipError_t launch_lsh_atrous(const LmfArgs& a, hipStream_t stream);
-hipError_t launch_lsh_dilate(const LmfArgs& a, hipStream_t stream);
 hipError_t launch_lsh_eval(const LshEvalArgs& a, hipStream_t stream);
 }  // namespace pt
 
@@ -1513,8 +1510,8 @@ template <size_t N, class Body> static int staged(mi_ctx* c, const StageColumn (
 // ------------------------------------------------------------------ lightmap finishing (edge-aware a-trous filter, gutter dilation)
 // tracing.py lightmap_finish, lightmap_finish_sh and lightmap_finish_var as kernels, one pass per launch, in three forms:
 //   plain     [H][W][3] texels; scratch d_lmf; lmf_mask, lmf_atrous per level, lmf_dilate per pass
-//   SH        [H][W][9][3] records; scratch of its own (d_lsh: a plain and an SH finish may be queued on two streams); lsh_mask, lsh_atrous, lsh_dilate
-//   variance  the plain form's texels, scratch, mask and dilation; lmv_init (with counts: lmv_init_counts), then lmv_blur and lmv_atrous per
+//   SH        [H][W][9][3] records; scratch of its own (d_lsh: a plain and an SH finish may be queued on two streams); lmf_mask, lsh_atrous, lmf_dilate at 27 floats
+//   variance  the plain form's texels, scratch, mask and dilation; lmv_init (with or without counts), then lmv_blur and lmv_atrous per
 //             level, the variance planes in d_lmv
 // The arguments every form takes, and the variance form's further ones (counts: mi_lightmap_finish_var_counts' per-texel counts, which take
 // the place of `samples` in the initial variance — samples is then 2 — or nullptr).
@@ -1585,17 +1582,17 @@ static int finish_device(mi_ctx* c, FinishForm form, const FinishArgs& f, const 
     const FinishPlan plan = finish_plan(f.levels, f.dilate, f.out_valid != nullptr, var, var && fv->out_var);
     return timed(c, stream, [&]() -> int {
         a.src = f.image; a.dst = f.out; a.copy = plan.copy; a.mask_out = mask[(int)plan.mask_init];
-        HIP_TRY(sh ? launch_lsh_mask(a, stream) : launch_lmf_mask(a, stream));
+        HIP_TRY(launch_lmf_mask(a, sh, stream));
         a.copy = 0;
         if (var) {
             v.src = f.image; v.var_out = vplane[(int)plan.var_init];
-            HIP_TRY(fv->counts ? launch_lmv_init_counts(v, fv->counts, false, stream) : launch_lmv_init(v, stream));
+            HIP_TRY(launch_lmv_init(v, fv->counts, false, stream));
         }
         for (const FinishPass& p : plan.passes) {
             a.src = image[(int)p.src]; a.dst = image[(int)p.dst];
             if (!p.level) {
                 a.mask_in = mask[(int)p.mask_in]; a.mask_out = mask[(int)p.mask_out];
-                HIP_TRY(sh ? launch_lsh_dilate(a, stream) : launch_lmf_dilate(a, stream));
+                HIP_TRY(launch_lmf_dilate(a, sh, stream));
             } else if (var) {
                 v.src = a.src; v.dst = a.dst; v.step = p.step;
                 v.var_in = vplane[(int)p.var_in]; v.var_out = vplane[(int)p.var_out];
@@ -1772,7 +1769,7 @@ static int check_select_args(const char* who, uint32_t width, uint32_t height, c
     return MI_OK;
 }
 
-// Queue lmv_init_counts, lma_mark, lma_scan and lma_fill on `stream`; every pointer is a device pointer.  timed: between the context's
+// Queue lmv_init, lma_mark, lma_scan and lma_fill on `stream`; every pointer is a device pointer.  timed: between the context's
 // timing events (the public forms; the whole bake keeps the events for its renders).
 static int lightmap_select_device(mi_ctx* c, uint32_t width, uint32_t height, const float* d_image, const float* d_m2, const uint32_t* d_counts,
                                   const float* d_normals, float target_rel, float target_abs, uint32_t capacity, uint32_t* d_index,
@@ -1791,7 +1788,7 @@ static int lightmap_select_device(mi_ctx* c, uint32_t width, uint32_t height, co
     a.width = width; a.height = height; a.blocks = (uint32_t)nb; a.capacity = capacity;
     a.target_rel = target_rel; a.target_abs = target_abs;
     auto queue = [&]() -> int {
-        HIP_TRY(launch_lmv_init_counts(v, d_counts, true, stream));
+        HIP_TRY(launch_lmv_init(v, d_counts, true, stream));
         HIP_TRY(launch_lma_select(a, stream));
         return MI_OK;
     };

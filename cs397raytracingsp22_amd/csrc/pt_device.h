@@ -446,7 +446,7 @@ constexpr uint32_t kLmfMaxLdsStep = 8;
 inline size_t lmf_lds_bytes(uint32_t step) { const size_t e = (size_t)kTile + 4u * step; return 9u * e * e * sizeof(float); }
 
 // ---- directional lightmaps (mi_lightmap_finish_sh, mi_lightmap_sh_eval; pt_kernels.hip "lsh_*") ----
-// tracing.py lightmap_finish_sh: lsh_mask, lsh_atrous and lsh_dilate are lmf_mask, lmf_atrous' direct form and lmf_dilate for images of
+// tracing.py lightmap_finish_sh: lmf_mask<27>, lsh_atrous and lmf_dilate<27> are lmf_mask, lmf_atrous' direct form and lmf_dilate for images of
 // [H][W][9][3] records; they take LmfArgs with src and dst holding kShFloats floats per texel.  lsh_eval is tracing.py lightmap_sh_eval:
 struct LshEvalArgs {
     const float* sh;                 // [n][9][3]
@@ -473,13 +473,13 @@ struct LmvArgs {
     uint32_t width, height, tiles_x, tiles_y;
     uint32_t step;                   // lmv_atrous: s = 2^level
     uint32_t npow;                   // normal_power_log2
-    uint32_t samples;                // lmv_init: S
+    uint32_t samples;                // lmv_init without a counts plane: S
     float sigma_plane, reach, sigma_color, color_floor;
 };
 
 // ---- adaptive lightmap baking (mi_lightmap_select / _gather / _merge, mi_bake_lightmap_adaptive; pt_kernels.hip "lma_*") ----
-// tracing.py lightmap_select as four passes: lmv_init_counts (the variance of the mean per texel from the texel's own count; a further
-// form of lmv_init, which mi_lightmap_finish_var_counts runs as well), lma_mark (the blur, the threshold, one flag per texel and the number
+// tracing.py lightmap_select as four passes: lmv_init with a counts plane (the variance of the mean per texel from the texel's own count,
+// which mi_lightmap_finish_var_counts runs as well), lma_mark (the blur, the threshold, one flag per texel and the number
 // of flags of each block of kLmaBlock consecutive texels), lma_scan (the exclusive prefix of the block counts, the total) and lma_fill
 // (every block writes its texels' numbers at its offset, ascending).  lma_gather and lma_merge are lightmap_gather and lightmap_merge,
 // one lane per slot / per list entry.  The list is the only value an address is made from, and every entry is tested against W * H first.
@@ -487,7 +487,7 @@ constexpr uint32_t kLmaBlock = 1024;             // texels per block of lma_mark
 struct LmaArgs {
     const float*    image;           // [H][W][3] the bake's mean (lma_mark: the luminance)
     const float*    normals;         // [H][W][3] the centre table: all-zero = empty texel
-    const float*    var;             // [H][W] lmv_init_counts' result (lma_mark)
+    const float*    var;             // [H][W] lmv_init's result (lma_mark)
     float*          error;           // [H][W] or nullptr: sd (lma_mark)
     uint8_t*        flags;           // [H][W] 1 = selected (lma_mark writes, lma_fill reads)
     uint32_t*       block_counts;    // [blocks] (lma_mark writes, lma_scan reads)

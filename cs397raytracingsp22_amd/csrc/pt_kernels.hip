@@ -3525,6 +3525,79 @@ __global__ __launch_bounds__(256) void wf_reduce_sh(WfArgs A, uint32_t first_bat
 }
 
 // gathered[world][tiles_padded][1024][27] -> image[H][W][9][3]: fb_unpermute's mapping for the SH records.  One thread per float.
+// Second moments of a point-table bake: the sums of squares of one batch of samples, behind wf_reduce.  One thread per texel (pixel): per
+// sample of the batch in order acc[c] = acc[c] + v.c * v.c (one multiply, one add, not fused: the pragma above), the sums living in A.m2
+// between batches and calls.  Every sum is one f32 chain in sample order from +0.0, divided once at the end by (float)S, wf_reduce's
+// division for the mean: the record is bit-identical however the samples are cut into batches, calls and ranks.  Only reads the sample
+// slots; empty texels' slots are +0.0 (wf_main's POINTS branch), so their moments are.  A table render carries no tile mask: no slot of
+// the image is left unwritten.
+__global__ __launch_bounds__(256) void wf_reduce_m2(WfArgs A, uint32_t first_batch, uint32_t last_batch) {
+    const uint32_t pix = blockIdx.x * blockDim.x + threadIdx.x;
+    if (pix >= A.npix) return;
+    float* rec = A.m2 + (size_t)pix * 3;
+    uint32_t px, py; bool in_image;
+    wf_pixel_of(A, pix, px, py, in_image);
+    if (!in_image) {                       // outside the image, or a padding slot: zeros, whatever the buffer held
+        rec[0] = 0.0f; rec[1] = 0.0f; rec[2] = 0.0f;
+        return;
+    }
+    float acc[3];
+    for (int k = 0; k < 3; k++) acc[k] = first_batch ? 0.0f : rec[k];
+    for (uint32_t s = 0; s < A.s_count; s++) {
+        const float4 v = A.samp[(size_t)s * A.npix + pix];
+        acc[0] = acc[0] + v.x * v.x; acc[1] = acc[1] + v.y * v.y; acc[2] = acc[2] + v.z * v.z;
+    }
+    const float n = (float)A.C.spp;
+    for (int k = 0; k < 3; k++) rec[k] = last_batch ? acc[k] / n : acc[k];
+}
+
+// Point tables: the SH L2 projection of one batch of samples, behind wf_reduce.  wf_reduce_sh for the POINTS form: one thread per texel; per
+// sample of the batch in order it reads the row's normal from the caller's table, draws the direction again (the POINTS form's calls on
+// the same stream with the same device functions, so the same bits: rand_sphere_vec, y = |y|, rotate_from_unit_y), normalises it as
+// wf_reduce_sh does, and adds L * Y_k to the texel's 27 sums, which live in A.sh between batches and calls.  Every sum is one f32 chain in
+// sample order from +0.0, scaled once at the end by 2 pi / S (the directions are uniform over the hemisphere, pdf 1 / (2 pi)): the record
+// is bit-identical however the samples are cut into batches, calls and ranks.  A row whose normal is all-zero adds nothing and draws
+// nothing (its slot is +0.0, but the rotation about a zero normal is no direction).  Only reads the sample slots and the table; the
+// table's index is wf_main's, formed by no lane outside the image, and no address depends on a table value.
+__global__ __launch_bounds__(256) void wf_reduce_psh(WfArgs A, uint32_t first_batch, uint32_t last_batch) {
+    const uint32_t pix = blockIdx.x * blockDim.x + threadIdx.x;
+    if (pix >= A.npix) return;
+    float* rec = A.sh + (size_t)pix * kShFloats;
+    uint32_t px, py; bool in_image;
+    wf_pixel_of(A, pix, px, py, in_image);
+    if (!in_image) {                       // outside the image, or a padding slot: zeros, whatever the buffer held
+        for (int k = 0; k < kShFloats; k++) rec[k] = 0.0f;
+        return;
+    }
+    float acc[kShFloats];
+    for (int k = 0; k < kShFloats; k++) acc[k] = first_batch ? 0.0f : rec[k];
+    const uint32_t key = A.C.width * A.C.height + (py * A.C.width + px);
+    for (uint32_t s = 0; s < A.s_count; s++) {
+        const uint32_t sample = A.s_base + s;
+        const size_t r = (((size_t)(A.pt_rows == 1u ? 0u : sample) * A.C.height + py) * A.C.width + px) * 3;
+        const Ray3 tn = *(const Ray3*)(A.pt_n + r);
+        if (tn.x == 0.0f && tn.y == 0.0f && tn.z == 0.0f) continue;       // an empty row (either sign of zero)
+        const float4 v = A.samp[(size_t)s * A.npix + pix];
+        Rng tmp;
+        rng_init(tmp, A.seed_key, key, sample);
+        f3 u = rand_sphere_vec(tmp);                                       // materials.rs:172
+        u.y = fabsf(u.y);                                                  // :173
+        const f3 d = rotate_from_unit_y(mk3(tn.x, tn.y, tn.z), u);         // :176-177
+        const float inv = 1.0f / sqrtf(d.x * d.x + d.y * d.y + d.z * d.z);
+        const float x = d.x * inv, y = d.y * inv, z = d.z * inv;
+        const float Y[9] = { 0.28209479177387814f, 0.4886025119029199f * y, 0.4886025119029199f * z, 0.4886025119029199f * x,
+                             1.0925484305920792f * (x * y), 1.0925484305920792f * (y * z), 0.31539156525252005f * (3.0f * (z * z) - 1.0f),
+                             1.0925484305920792f * (x * z), 0.5462742152960396f * (x * x - y * y) };
+#pragma unroll
+        for (int k = 0; k < 9; k++) {
+            acc[3 * k] = acc[3 * k] + v.x * Y[k]; acc[3 * k + 1] = acc[3 * k + 1] + v.y * Y[k]; acc[3 * k + 2] = acc[3 * k + 2] + v.z * Y[k];
+        }
+    }
+    const float scale = last_batch ? 6.283185307179586f / (float)A.C.spp : 1.0f;       // 2 pi / S, once, behind the last sample
+#pragma unroll
+    for (int k = 0; k < kShFloats; k++) rec[k] = last_batch ? acc[k] * scale : acc[k];
+}
+
 __global__ __launch_bounds__(256) void sh_unpermute(const float* __restrict__ gathered, float* __restrict__ image,
                                                     uint32_t width, uint32_t height, uint32_t tiles_x,
                                                     uint32_t world, uint32_t tiles_padded) {
@@ -3810,14 +3883,39 @@ __global__ __launch_bounds__(kBlock) void lm_resolve(const LmArgs a) {
 // No address depends on a table value: a non-finite texel spoils its own footprint only.
 __device__ __forceinline__ bool lmf_covered(float nx, float ny, float nz) { return !(nx == 0.0f && ny == 0.0f && nz == 0.0f); }
 
-// The covered mask from the guide normals; with a.copy also dst = covered ? src : +0 (the whole of a call with no level and no pass)
-__global__ __launch_bounds__(kBlock) void lmf_mask(const LmfArgs a) {
+// The weight of tap q = p + s (dx, dy) of a covered texel p, from values the caller has fetched (normal, point and colour of p and of q):
+// the one place lmf_atrous and lmv_atrous take it from (lsh_atrous restates it, for the reason given there).  The reach test rejects a
+// tap by returning: a hard cut, |D|^2 <= rr (dx^2 + dy^2) with D = P_q - P_p, which the centre tap passes without it (literally its
+// bound is inf * 0 for an infinite reach).  An accepted tap's w = ((h wn) wp) wc — the B3 kernel, the normal weight squared npow times,
+// the plane weight and the colour weight 1 - dc / color_den — goes to `accept`, the caller's sums.  (A form that returned accepted and
+// w left a second branch on the same condition per tap in all three kernels; this one compiles to the code the inline text gave.)
+template <class Accept>
+__device__ __forceinline__ void lmf_tap_weight(const float* np, const float* pp, const float* cp, const float* nq, const float* pq,
+                                               const float* cq, int dx, int dy, float rr, uint32_t npow, float sigma_plane,
+                                               float color_den, Accept accept) {
+    const float H5[5] = { 0.0625f, 0.25f, 0.375f, 0.25f, 0.0625f };
+    const float D[3] = { pq[0] - pp[0], pq[1] - pp[1], pq[2] - pp[2] };
+    const float d2 = (D[0] * D[0] + D[1] * D[1]) + D[2] * D[2];
+    if ((dx != 0 || dy != 0) && !(d2 <= rr * (float)(dx * dx + dy * dy))) return;
+    const float h = H5[dy + 2] * H5[dx + 2];
+    float wn = fmaxf(0.0f, (np[0] * nq[0] + np[1] * nq[1]) + np[2] * nq[2]);
+    for (uint32_t i = 0; i < npow; i++) wn = wn * wn;
+    const float dpl = fabsf((np[0] * D[0] + np[1] * D[1]) + np[2] * D[2]);
+    const float wp = fmaxf(0.0f, 1.0f - dpl / sigma_plane);
+    const float dc = (fabsf(cq[0] - cp[0]) + fabsf(cq[1] - cp[1])) + fabsf(cq[2] - cp[2]);
+    const float wc = fmaxf(0.0f, 1.0f - dc / color_den);
+    accept(((h * wn) * wp) * wc);
+}
+
+// The covered mask from the guide normals; with a.copy also dst = covered ? src : +0 for the texel's C floats (the whole of a call with
+// no level and no pass).  C = 3: an image; kShFloats: SH records.
+template <int C> __global__ __launch_bounds__(kBlock) void lmf_mask(const LmfArgs a) {
     const size_t n = (size_t)a.width * a.height, i = (size_t)blockIdx.x * kBlock + threadIdx.x;
     if (i >= n) return;
     const bool cov = lmf_covered(a.normals[3 * i], a.normals[3 * i + 1], a.normals[3 * i + 2]);
     a.mask_out[i] = cov ? 1 : 0;
     if (a.copy)
-        for (int k = 0; k < 3; k++) a.dst[3 * i + k] = cov ? a.src[3 * i + k] : 0.0f;
+        for (int k = 0; k < C; k++) a.dst[C * i + k] = cov ? a.src[C * i + k] : 0.0f;
 }
 
 // One filter level.  One block per kTile x kTile tile; a thread owns the texels (x, y + 8 k), k < 4, as lm_resolve does.
@@ -3856,7 +3954,6 @@ template <bool LDS> __global__ __launch_bounds__(kBlock) void lmf_atrous(const L
             for (int k = 0; k < 3; k++) out[k] = t[at + k];
         }
     };
-    const float H5[5] = { 0.0625f, 0.25f, 0.375f, 0.25f, 0.0625f };
     const float fs = (float)s;
     const float r = a.reach * fs, rr = r * r, sig_c = a.sigma_color / fs;
     const int gx = x0 + (int)(threadIdx.x & 31u);
@@ -3880,20 +3977,10 @@ template <bool LDS> __global__ __launch_bounds__(kBlock) void lmf_atrous(const L
                     if (!lmf_covered(nq[0], nq[1], nq[2])) continue;
                     float cq[3], pq[3];
                     fetch3(0, qx, qy, cq); fetch3(3, qx, qy, pq);
-                    const float D[3] = { pq[0] - pp[0], pq[1] - pp[1], pq[2] - pp[2] };
-                    // the reach test: a hard cut; the centre tap passes without it (literally its bound is inf * 0 for an infinite reach)
-                    const float d2 = (D[0] * D[0] + D[1] * D[1]) + D[2] * D[2];
-                    if ((dx != 0 || dy != 0) && !(d2 <= rr * (float)(dx * dx + dy * dy))) continue;
-                    const float h = H5[dy + 2] * H5[dx + 2];
-                    float wn = fmaxf(0.0f, (np[0] * nq[0] + np[1] * nq[1]) + np[2] * nq[2]);
-                    for (uint32_t i = 0; i < a.npow; i++) wn = wn * wn;
-                    const float dpl = fabsf((np[0] * D[0] + np[1] * D[1]) + np[2] * D[2]);
-                    const float wp = fmaxf(0.0f, 1.0f - dpl / a.sigma_plane);
-                    const float dc = (fabsf(cq[0] - cp[0]) + fabsf(cq[1] - cp[1])) + fabsf(cq[2] - cp[2]);
-                    const float wc = fmaxf(0.0f, 1.0f - dc / sig_c);
-                    const float w = ((h * wn) * wp) * wc;
-                    sw = sw + w;
-                    for (int k = 0; k < 3; k++) sc[k] = sc[k] + w * cq[k];
+                    lmf_tap_weight(np, pp, cp, nq, pq, cq, dx, dy, rr, a.npow, a.sigma_plane, sig_c, [&](float w) {
+                        sw = sw + w;
+                        for (int k = 0; k < 3; k++) sc[k] = sc[k] + w * cq[k];
+                    });
                 }
             }
             for (int k = 0; k < 3; k++) out[k] = sc[k] / sw;
@@ -3903,19 +3990,21 @@ template <bool LDS> __global__ __launch_bounds__(kBlock) void lmf_atrous(const L
     }
 }
 
-// One dilation pass: a texel that is not valid and has a valid 8-neighbour in the PREVIOUS pass's mask takes the mean of those neighbours'
-// colours (summed in dy-outer, dx-inner order from +0) and turns valid; valid texels are copied.
-__global__ __launch_bounds__(kBlock) void lmf_dilate(const LmfArgs a) {
+// One dilation pass of C floats per texel: a texel that is not valid and has a valid 8-neighbour in the PREVIOUS pass's mask takes the mean
+// of those neighbours (every channel summed in dy-outer, dx-inner order from +0, one count) and turns valid; valid texels are copied.
+template <int C> __global__ __launch_bounds__(kBlock) void lmf_dilate(const LmfArgs a) {
     const size_t n = (size_t)a.width * a.height, i = (size_t)blockIdx.x * kBlock + threadIdx.x;
     if (i >= n) return;
     const int W = (int)a.width, H = (int)a.height;
     const int y = (int)(i / a.width), x = (int)(i - (size_t)y * a.width);
-    float out[3] = { 0.0f, 0.0f, 0.0f };
+    float out[C];
+#pragma unroll
+    for (int k = 0; k < C; k++) out[k] = 0.0f;
     uint8_t valid = a.mask_in[i];
     if (valid) {
-        for (int k = 0; k < 3; k++) out[k] = a.src[3 * i + k];
+#pragma unroll
+        for (int k = 0; k < C; k++) out[k] = a.src[C * i + k];
     } else {
-        float sum[3] = { 0.0f, 0.0f, 0.0f };
         int count = 0;
         for (int dy = -1; dy <= 1; dy++)
             for (int dx = -1; dx <= 1; dx++) {
@@ -3923,15 +4012,18 @@ __global__ __launch_bounds__(kBlock) void lmf_dilate(const LmfArgs a) {
                 if ((dx == 0 && dy == 0) || qx < 0 || qx >= W || qy < 0 || qy >= H) continue;
                 const size_t j = (size_t)qy * W + qx;
                 if (!a.mask_in[j]) continue;
-                for (int k = 0; k < 3; k++) sum[k] = sum[k] + a.src[3 * j + k];
+#pragma unroll
+                for (int k = 0; k < C; k++) out[k] = out[k] + a.src[C * j + k];
                 count++;
             }
         if (count) {
-            for (int k = 0; k < 3; k++) out[k] = sum[k] / (float)count;
+#pragma unroll
+            for (int k = 0; k < C; k++) out[k] = out[k] / (float)count;
             valid = 1;
         }
     }
-    for (int k = 0; k < 3; k++) a.dst[3 * i + k] = out[k];
+#pragma unroll
+    for (int k = 0; k < C; k++) a.dst[C * i + k] = out[k];
     a.mask_out[i] = valid;
 }
 
@@ -4037,23 +4129,360 @@ __global__ __launch_bounds__(kBlock) void pv_sample(const PvArgs a) {
     if (a.out_weight) a.out_weight[i] = sw;
 }
 
+// ---------------------------------------------------------------- lightmap variance (mi_render_points_moments, mi_lightmap_finish_var)
+// tracing.py lightmap_finish_var on the device, pass by pass: lightmap_finish with a colour weight whose width follows each texel's own
+// noise (the variance of its mean, from the bake's second moments, filtered along with the image).  Pure f32, the helper's operations in
+// the helper's order (no fused multiply-add: the pragma above; IEEE division and square root), a fixed tap order per texel, nothing
+// summed across threads: image and variance are the helper's bit for bit.  No address depends on a table value.
+
+// The variance of the mean per texel with n samples behind it, n = counts[i] or, without a counts plane, a.samples everywhere:
+// v_c = fmaxf(0, m2_c - mean_c mean_c) / (float)(n - 1), V = (v_r + v_g) + v_b.  A covered texel with n < 2 gets +inf (few_inf:
+// mi_lightmap_select, "no information") or +0.0 (mi_lightmap_finish_var_counts); empty texels +0.0.
+__global__ __launch_bounds__(kBlock) void lmv_init(const LmvArgs a, const uint32_t* __restrict__ counts, uint32_t few_inf) {
+    const size_t n = (size_t)a.width * a.height, i = (size_t)blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n) return;
+    float V = 0.0f;
+    if (lmf_covered(a.normals[3 * i], a.normals[3 * i + 1], a.normals[3 * i + 2])) {
+        const uint32_t cnt = counts ? counts[i] : a.samples;
+        if (cnt >= 2u) {
+            const float d = (float)(cnt - 1u);
+            float v[3];
+            for (int k = 0; k < 3; k++) {
+                const float mean = a.src[3 * i + k];
+                v[k] = fmaxf(0.0f, a.m2[3 * i + k] - mean * mean) / d;
+            }
+            V = (v[0] + v[1]) + v[2];
+        } else {
+            V = few_inf ? __builtin_inff() : 0.0f;
+        }
+    }
+    a.var_out[i] = V;
+}
+
+// The blur of the variance about the covered texel (x, y), the one place lmv_blur and lma_mark take it from: bs = the sum of g V_q and
+// bw = the sum of g over the nine step-1 neighbours that lie in the image and are covered (dy outer, dx inner, g = G3[dy] G3[dx],
+// G3 = {1/4, 1/2, 1/4}).
+__device__ __forceinline__ void lmv_blur9(const float* normals, const float* var, int x, int y, int W, int H, float& bs, float& bw) {
+    const float G3[3] = { 0.25f, 0.5f, 0.25f };
+    bs = 0.0f; bw = 0.0f;
+#pragma unroll
+    for (int dy = -1; dy <= 1; dy++) {
+#pragma unroll
+        for (int dx = -1; dx <= 1; dx++) {
+            const int qx = x + dx, qy = y + dy;
+            if (qx < 0 || qx >= W || qy < 0 || qy >= H) continue;
+            const size_t j = (size_t)qy * W + qx;
+            if (!lmf_covered(normals[3 * j], normals[3 * j + 1], normals[3 * j + 2])) continue;
+            const float g = G3[dy + 1] * G3[dx + 1];
+            bs = bs + g * var[j];
+            bw = bw + g;
+        }
+    }
+}
+
+// The colour weight's denominator per covered texel: sd = sqrtf(bs / bw) of the blur, den = sigma_color * sd + color_floor.  Empty texels
+// +0.0 (never read).
+__global__ __launch_bounds__(kBlock) void lmv_blur(const LmvArgs a) {
+    const size_t n = (size_t)a.width * a.height, i = (size_t)blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n) return;
+    const int y = (int)(i / a.width), x = (int)(i - (size_t)y * a.width);
+    float den = 0.0f;
+    if (lmf_covered(a.normals[3 * i], a.normals[3 * i + 1], a.normals[3 * i + 2])) {
+        float bs, bw;
+        lmv_blur9(a.normals, a.var_in, x, y, (int)a.width, (int)a.height, bs, bw);
+        den = a.sigma_color * sqrtf(bs / bw) + a.color_floor;
+    }
+    a.den_out[i] = den;
+}
+
+// One filter level of the image and its variance.  lmf_atrous' direct form (one block per kTile x kTile tile, a thread owns the texels
+// (x, y + 8 k), k < 4, the taps straight from HBM / L2), with the colour weight wc = fmaxf(0, 1 - dc / den_p) and, beside sw and sc,
+// sv = sv + (w * w) * V_q: the texel becomes sc / sw and its variance sv / (sw * sw).
+__global__ __launch_bounds__(kBlock) void lmv_atrous(const LmvArgs a) {
+    const int s = (int)a.step, W = (int)a.width, H = (int)a.height;
+    const int x0 = (int)(blockIdx.x % a.tiles_x) * kTile, y0 = (int)(blockIdx.x / a.tiles_x) * kTile;
+    auto fetch3 = [&](const float* t, int qx, int qy, float* out) {
+        const size_t at = 3 * ((size_t)qy * W + qx);
+        for (int k = 0; k < 3; k++) out[k] = t[at + k];
+    };
+    const float r = a.reach * (float)s, rr = r * r;
+    const int gx = x0 + (int)(threadIdx.x & 31u);
+    for (int k4 = 0; k4 < 4; k4++) {
+        const int gy = y0 + (int)(threadIdx.x >> 5) + 8 * k4;
+        if (gx >= W || gy >= H) continue;
+        const size_t ip = (size_t)gy * W + gx;
+        float cp[3], pp[3], np[3];
+        fetch3(a.normals, gx, gy, np);
+        float out[3] = { 0.0f, 0.0f, 0.0f }, vout = 0.0f;
+        if (lmf_covered(np[0], np[1], np[2])) {
+            fetch3(a.src, gx, gy, cp); fetch3(a.points, gx, gy, pp);
+            const float den = a.den[ip];
+            float sw = 0.0f, sv = 0.0f, sc[3] = { 0.0f, 0.0f, 0.0f };
+#pragma unroll
+            for (int dy = -2; dy <= 2; dy++) {
+#pragma unroll
+                for (int dx = -2; dx <= 2; dx++) {
+                    const int qx = gx + s * dx, qy = gy + s * dy;
+                    if (qx < 0 || qx >= W || qy < 0 || qy >= H) continue;
+                    float nq[3];
+                    fetch3(a.normals, qx, qy, nq);
+                    if (!lmf_covered(nq[0], nq[1], nq[2])) continue;
+                    float cq[3], pq[3];
+                    fetch3(a.src, qx, qy, cq); fetch3(a.points, qx, qy, pq);
+                    lmf_tap_weight(np, pp, cp, nq, pq, cq, dx, dy, rr, a.npow, a.sigma_plane, den, [&](float w) {
+                        sw = sw + w;
+                        for (int k = 0; k < 3; k++) sc[k] = sc[k] + w * cq[k];
+                        sv = sv + (w * w) * a.var_in[(size_t)qy * W + qx];
+                    });
+                }
+            }
+            for (int k = 0; k < 3; k++) out[k] = sc[k] / sw;
+            vout = sv / (sw * sw);
+        }
+        for (int k = 0; k < 3; k++) a.dst[3 * ip + k] = out[k];
+        a.var_out[ip] = vout;
+    }
+}
+
+// ---------------------------------------------------------------- adaptive lightmap baking (mi_lightmap_select / _gather / _merge)
+// tracing.py lightmap_select, lightmap_gather and lightmap_merge on the device.  Pure f32, the helpers' operations in the helpers' order
+// (no fused multiply-add: the pragma above; IEEE division and square root), nothing summed across threads but integer counts, no atomics:
+// the list and the merged planes are the helpers' bit for bit and do not depend on scheduling.  No address depends on a table value but
+// through the list, whose entries are tested against W * H before they are used.
+
+// One lane per texel, kLmaBlock consecutive texels per block: lmv_blur's sums (lmv_blur9), sd = sqrtf(bs / bw), the texel's flag
+// sd > target_rel * lum + target_abs, and the number of flags in the block (a ballot per wave, the sixteen wave counts through LDS).
+__global__ __launch_bounds__(kLmaBlock) void lma_mark(const LmaArgs a) {
+    __shared__ uint32_t s_wave[kLmaBlock / 64];
+    const size_t n = (size_t)a.width * a.height, i = (size_t)blockIdx.x * kLmaBlock + threadIdx.x;
+    bool sel = false;
+    if (i < n) {
+        const int y = (int)(i / a.width), x = (int)(i - (size_t)y * a.width);
+        float sd = 0.0f;
+        if (lmf_covered(a.normals[3 * i], a.normals[3 * i + 1], a.normals[3 * i + 2])) {
+            float bs, bw;
+            lmv_blur9(a.normals, a.var, x, y, (int)a.width, (int)a.height, bs, bw);
+            sd = sqrtf(bs / bw);
+            const float lum = (fabsf(a.image[3 * i]) + fabsf(a.image[3 * i + 1])) + fabsf(a.image[3 * i + 2]);
+            const float thr = a.target_rel * lum + a.target_abs;
+            sel = sd > thr;
+        }
+        if (a.error) a.error[i] = sd;
+        a.flags[i] = sel ? (uint8_t)1 : (uint8_t)0;
+    }
+    const unsigned long long m = __builtin_amdgcn_ballot_w64(sel);
+    if ((threadIdx.x & 63u) == 0u) s_wave[threadIdx.x >> 6] = (uint32_t)__popcll(m);
+    __syncthreads();
+    if (threadIdx.x == 0u) {
+        uint32_t total = 0;
+        for (uint32_t k = 0; k < kLmaBlock / 64; k++) total += s_wave[k];
+        a.block_counts[blockIdx.x] = total;
+    }
+}
+
+// Exclusive prefix of the block counts (one block, the pattern of lm_scan); the total to *out_count
+__global__ __launch_bounds__(1024) void lma_scan(const LmaArgs a) {
+    __shared__ uint32_t s_sum[1024];
+    const uint32_t nb = a.blocks, per = (nb + 1023u) / 1024u;
+    const uint32_t lo = min(nb, threadIdx.x * per), hi = min(nb, lo + per);
+    uint32_t sum = 0;
+    for (uint32_t i = lo; i < hi; i++) sum += a.block_counts[i];
+    s_sum[threadIdx.x] = sum;
+    __syncthreads();
+    for (uint32_t d = 1; d < 1024u; d <<= 1) {              // inclusive scan of the threads' sums
+        const uint32_t v = threadIdx.x >= d ? s_sum[threadIdx.x - d] : 0u;
+        __syncthreads();
+        s_sum[threadIdx.x] += v;
+        __syncthreads();
+    }
+    uint32_t run = s_sum[threadIdx.x] - sum;
+    for (uint32_t i = lo; i < hi; i++) { a.block_offsets[i] = run; run += a.block_counts[i]; }
+    if (threadIdx.x == 1023u) *a.out_count = s_sum[1023];
+}
+
+// Every block writes its flagged texels' numbers at its offset, ascending: the waves before this one through LDS, the lanes before this
+// one from the ballot.  Positions at or beyond `capacity` are not written.
+__global__ __launch_bounds__(kLmaBlock) void lma_fill(const LmaArgs a) {
+    __shared__ uint32_t s_wave[kLmaBlock / 64];
+    const size_t n = (size_t)a.width * a.height, i = (size_t)blockIdx.x * kLmaBlock + threadIdx.x;
+    const bool sel = i < n && a.flags[i] != 0;
+    const unsigned long long m = __builtin_amdgcn_ballot_w64(sel);
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    if (lane == 0u) s_wave[wave] = (uint32_t)__popcll(m);
+    __syncthreads();
+    if (!sel) return;
+    uint32_t pos = a.block_offsets[blockIdx.x];
+    for (uint32_t k = 0; k < wave; k++) pos += s_wave[k];
+    pos += (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
+    if (pos < a.capacity) a.out_index[pos] = (uint32_t)i;
+}
+
+// One lane per slot of the compact table: entry `slot` of the list into every row, zeros (the empty-texel mark) behind the list's end
+// and for an entry outside the atlas
+__global__ __launch_bounds__(kBlock) void lma_gather(const LmaListArgs a) {
+    const size_t slot = (size_t)blockIdx.x * kBlock + threadIdx.x;
+    if (slot >= a.slots) return;
+    const size_t npix = (size_t)a.width * a.height;
+    size_t texel = 0;
+    bool live = slot < a.n;
+    if (live) {
+        const uint32_t idx = a.index[slot];
+        live = idx < npix;
+        texel = live ? idx : 0;
+    }
+    for (uint32_t r = 0; r < a.rows; r++) {
+        const size_t src = 3 * ((size_t)r * npix + texel), dst = 3 * ((size_t)r * a.slots + slot);
+        for (int k = 0; k < 3; k++) {
+            a.out_points[dst + k] = live ? a.points[src + k] : 0.0f;
+            a.out_normals[dst + k] = live ? a.normals[src + k] : 0.0f;
+        }
+    }
+}
+
+// One lane per list entry: x = ((float)n0 * x + (float)S' * x') / (float)(n0 + S') for the six values of the texel, counts = n0 + S'
+__global__ __launch_bounds__(kBlock) void lma_merge(const LmaListArgs a) {
+    const size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x;
+    if (i >= a.n) return;
+    const uint32_t idx = a.index[i];
+    if (idx >= (size_t)a.width * a.height) return;
+    const uint32_t n0 = a.counts[idx];
+    const float f0 = (float)n0, fs = (float)a.round_samples, ft = (float)(n0 + a.round_samples);
+    for (int k = 0; k < 3; k++) {
+        const size_t at = 3 * (size_t)idx + k;
+        a.image[at] = (f0 * a.image[at] + fs * a.mean[3 * i + k]) / ft;
+        a.m2[at] = (f0 * a.m2[at] + fs * a.m2_round[3 * i + k]) / ft;
+    }
+    a.counts[idx] = n0 + a.round_samples;
+}
+
+// ---------------------------------------------------------------- directional lightmaps (mi_render_points_sh, mi_lightmap_finish_sh, mi_lightmap_sh_eval)
+// tracing.py lightmap_finish_sh on the device, pass by pass: lightmap_finish for [H][W][9][3] records.  The weights are lmf_atrous', the
+// colour distance taken from the three k = 0 coefficients; one weight per tap serves all 27 channels.  Pure f32, the helper's operations
+// in the helper's order, a fixed tap order per texel, nothing summed across threads.  No address depends on a table value.
+
+// One filter level of the 27 channels.  lmf_atrous' direct form (one block per kTile x kTile tile, a thread owns the texels (x, y + 8 k),
+// k < 4, one after the other: 28 live accumulators, not 112), the taps straight from HBM / L2: a tap's guides and k = 0 coefficients
+// decide the weight, then its other 24 floats are read only when the tap is accepted.  Thirty-three planes of tile and halo do not fit
+// the LDS at any step, and the 108-byte records of neighbouring lanes share their cache lines, so nothing is staged.
+// The tap weight is lmf_tap_weight's text restated, not a call of it: through the call this kernel alone was compiled to another register
+// allocation (130 VGPRs / 3 waves became 90 / 5 with the deferred reads rescheduled) and measured 9 % to 25 % slower on an MI355X.
+__global__ __launch_bounds__(kBlock) void lsh_atrous(const LmfArgs a) {
+    const int s = (int)a.step, W = (int)a.width, H = (int)a.height;
+    const int x0 = (int)(blockIdx.x % a.tiles_x) * kTile, y0 = (int)(blockIdx.x / a.tiles_x) * kTile;
+    auto fetch3 = [&](const float* t, size_t i, float* out) {
+        for (int k = 0; k < 3; k++) out[k] = t[3 * i + k];
+    };
+    const float H5[5] = { 0.0625f, 0.25f, 0.375f, 0.25f, 0.0625f };
+    const float fs = (float)s;
+    const float r = a.reach * fs, rr = r * r, sig_c = a.sigma_color / fs;
+    const int gx = x0 + (int)(threadIdx.x & 31u);
+#pragma unroll 1
+    for (int k4 = 0; k4 < 4; k4++) {
+        const int gy = y0 + (int)(threadIdx.x >> 5) + 8 * k4;
+        if (gx >= W || gy >= H) continue;
+        const size_t ip = (size_t)gy * W + gx;
+        float np[3];
+        fetch3(a.normals, ip, np);
+        float sc[kShFloats];
+#pragma unroll
+        for (int k = 0; k < kShFloats; k++) sc[k] = 0.0f;
+        const bool cov = lmf_covered(np[0], np[1], np[2]);
+        if (cov) {
+            float cp[3], pp[3];
+            fetch3(a.src, 9 * ip, cp); fetch3(a.points, ip, pp);          // the k = 0 coefficients head the record
+            float sw = 0.0f;
+#pragma unroll
+            for (int dy = -2; dy <= 2; dy++) {
+#pragma unroll
+                for (int dx = -2; dx <= 2; dx++) {
+                    const int qx = gx + s * dx, qy = gy + s * dy;
+                    if (qx < 0 || qx >= W || qy < 0 || qy >= H) continue;
+                    const size_t iq = (size_t)qy * W + qx;
+                    float nq[3];
+                    fetch3(a.normals, iq, nq);
+                    if (!lmf_covered(nq[0], nq[1], nq[2])) continue;
+                    float cq[3], pq[3];
+                    fetch3(a.src, 9 * iq, cq); fetch3(a.points, iq, pq);
+                    // lmf_tap_weight's text, restated (see above)
+                    const float D[3] = { pq[0] - pp[0], pq[1] - pp[1], pq[2] - pp[2] };
+                    const float d2 = (D[0] * D[0] + D[1] * D[1]) + D[2] * D[2];
+                    if ((dx != 0 || dy != 0) && !(d2 <= rr * (float)(dx * dx + dy * dy))) continue;
+                    const float h = H5[dy + 2] * H5[dx + 2];
+                    float wn = fmaxf(0.0f, (np[0] * nq[0] + np[1] * nq[1]) + np[2] * nq[2]);
+                    for (uint32_t i = 0; i < a.npow; i++) wn = wn * wn;
+                    const float dpl = fabsf((np[0] * D[0] + np[1] * D[1]) + np[2] * D[2]);
+                    const float wp = fmaxf(0.0f, 1.0f - dpl / a.sigma_plane);
+                    const float dc = (fabsf(cq[0] - cp[0]) + fabsf(cq[1] - cp[1])) + fabsf(cq[2] - cp[2]);
+                    const float wc = fmaxf(0.0f, 1.0f - dc / sig_c);
+                    const float w = ((h * wn) * wp) * wc;
+                    sw = sw + w;
+                    const float* q = a.src + kShFloats * iq;
+#pragma unroll
+                    for (int k = 0; k < 3; k++) sc[k] = sc[k] + w * cq[k];
+#pragma unroll
+                    for (int k = 3; k < kShFloats; k++) sc[k] = sc[k] + w * q[k];
+                }
+            }
+#pragma unroll
+            for (int k = 0; k < kShFloats; k++) sc[k] = sc[k] / sw;
+        }
+        float* o = a.dst + kShFloats * ip;
+#pragma unroll
+        for (int k = 0; k < kShFloats; k++) o[k] = sc[k];
+    }
+}
+
+// tracing.py lightmap_sh_eval on the device: the irradiance E(n) of one SH L2 record per point at the caller's normal, pv_sample's
+// normal, basis and constants K_k without the grid.  One lane per point: 108 + 12 bytes in, 12 out.  An all-zero normal gives +0.0.
+__global__ __launch_bounds__(kBlock) void lsh_eval(const LshEvalArgs a) {
+    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= a.n) return;
+    const float nx = a.normals[3 * (size_t)i], ny = a.normals[3 * (size_t)i + 1], nz = a.normals[3 * (size_t)i + 2];
+    float E[3] = { 0.0f, 0.0f, 0.0f };
+    if (lmf_covered(nx, ny, nz)) {
+        const float K1 = (float)1.0233267079464885, K2 = (float)0.8580855308097834;
+        const float K[9] = { (float)0.886226925452758, K1, K1, K1, K2, K2, (float)0.24770795610037571, K2, (float)0.4290427654048917 };
+        const float l = sqrtf((nx * nx + ny * ny) + nz * nz);
+        const float x = nx / l, y = ny / l, z = nz / l;
+        const float b[9] = { 1.0f, y, z, x, x * y, y * z, 3.0f * (z * z) - 1.0f, x * z, x * x - y * y };
+        const float* sh = a.sh + (size_t)i * kShFloats;
+#pragma unroll
+        for (int c = 0; c < 3; c++) {
+            float e = b[0] * (sh[c] * K[0]);
+#pragma unroll
+            for (int k = 1; k < 9; k++) e = e + b[k] * (sh[3 * k + c] * K[k]);
+            E[c] = e;
+        }
+    }
+#pragma unroll
+    for (int c = 0; c < 3; c++) a.out_irradiance[3 * (size_t)i + c] = E[c];
+}
+
 // ---------------------------------------------------------------- launch wrappers
+// One lane per item (a texel, a probe, a point, a list entry): ceil(n / kBlock) blocks of `kernel`, which tests its index against n itself
+template <class Kernel, class... Args> static hipError_t launch_per_item(Kernel kernel, size_t n, hipStream_t stream, const Args&... args) {
+    hipLaunchKernelGGL(kernel, dim3((uint32_t)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, stream, args...);
+    return hipGetLastError();
+}
 // irradiance volumes: the record pass, then the sampling pass
-hipError_t launch_pv_prepare(const PvArgs& a, hipStream_t stream) {
-    hipLaunchKernelGGL(pv_prepare, dim3((a.n_probes + kBlock - 1) / kBlock), dim3(kBlock), 0, stream, a);
-    return hipGetLastError();
-}
-hipError_t launch_pv_sample(const PvArgs& a, hipStream_t stream) {
-    hipLaunchKernelGGL(pv_sample, dim3((a.n_points + kBlock - 1) / kBlock), dim3(kBlock), 0, stream, a);
-    return hipGetLastError();
-}
-// lightmap finishing: one pass per launch.  lmf_atrous stages through LDS when `lds`; a window above 64 KB needs the opt-in, which
-// belongs to the function on the current device, so the calling context keeps its record (as launch_walker's big_lds_enabled).
-hipError_t launch_lmf_mask(const LmfArgs& a, hipStream_t stream) {
+hipError_t launch_pv_prepare(const PvArgs& a, hipStream_t stream) { return launch_per_item(pv_prepare, a.n_probes, stream, a); }
+hipError_t launch_pv_sample(const PvArgs& a, hipStream_t stream) { return launch_per_item(pv_sample, a.n_points, stream, a); }
+// lightmap finishing: one pass per launch, `sh`: of [H][W][9][3] records (mi_lightmap_finish_sh), else of an [H][W][3] image
+hipError_t launch_lmf_mask(const LmfArgs& a, bool sh, hipStream_t stream) {
     const size_t n = (size_t)a.width * a.height;
-    hipLaunchKernelGGL(lmf_mask, dim3((uint32_t)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, stream, a);
+    return sh ? launch_per_item(lmf_mask<kShFloats>, n, stream, a) : launch_per_item(lmf_mask<3>, n, stream, a);
+}
+hipError_t launch_lmf_dilate(const LmfArgs& a, bool sh, hipStream_t stream) {
+    const size_t n = (size_t)a.width * a.height;
+    return sh ? launch_per_item(lmf_dilate<kShFloats>, n, stream, a) : launch_per_item(lmf_dilate<3>, n, stream, a);
+}
+hipError_t launch_lsh_atrous(const LmfArgs& a, hipStream_t stream) {
+    hipLaunchKernelGGL(lsh_atrous, dim3(a.tiles_x * a.tiles_y), dim3(kBlock), 0, stream, a);
     return hipGetLastError();
 }
+hipError_t launch_lsh_eval(const LshEvalArgs& a, hipStream_t stream) { return launch_per_item(lsh_eval, a.n, stream, a); }
+// The plain form's level.  lmf_atrous stages through LDS when `lds`; a window above 64 KB needs the opt-in, which
+// belongs to the function on the current device, so the calling context keeps its record (as launch_walker's big_lds_enabled).
 hipError_t launch_lmf_atrous(const LmfArgs& a, bool lds, bool* big_lds_enabled, hipStream_t stream) {
     const dim3 grid(a.tiles_x * a.tiles_y);
     if (!lds) {
@@ -4068,11 +4497,6 @@ hipError_t launch_lmf_atrous(const LmfArgs& a, bool lds, bool* big_lds_enabled, 
         *big_lds_enabled = true;
     }
     hipLaunchKernelGGL(lmf_atrous<true>, grid, dim3(kBlock), bytes, stream, a);
-    return hipGetLastError();
-}
-hipError_t launch_lmf_dilate(const LmfArgs& a, hipStream_t stream) {
-    const size_t n = (size_t)a.width * a.height;
-    hipLaunchKernelGGL(lmf_dilate, dim3((uint32_t)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, stream, a);
     return hipGetLastError();
 }
 // lightmap atlas: count, scan, (the caller may size the list here,) fill, resolve
@@ -4237,15 +4661,15 @@ hipError_t launch_wf_prefix(uint32_t* out_count, uint32_t* trav_count, uint32_t*
                        (volatile uint32_t*)host_hdr, seq);
     return hipGetLastError();
 }
-hipError_t launch_wf_reduce(const WfArgs& a, bool first_batch, bool last_batch, hipStream_t stream) {
-    hipLaunchKernelGGL(wf_reduce, dim3((a.npix + 255) / 256), dim3(256), 0, stream, a, first_batch ? 1u : 0u, last_batch ? 1u : 0u);
+// wf_reduce and its siblings behind it: one thread per pixel of the rank's tiles
+static hipError_t launch_reduce(void (*kernel)(WfArgs, uint32_t, uint32_t), const WfArgs& a, bool first_batch, bool last_batch, hipStream_t stream) {
+    hipLaunchKernelGGL(kernel, dim3((a.npix + 255) / 256), dim3(256), 0, stream, a, first_batch ? 1u : 0u, last_batch ? 1u : 0u);
     return hipGetLastError();
 }
-
-hipError_t launch_wf_reduce_sh(const WfArgs& a, bool first_batch, bool last_batch, hipStream_t stream) {
-    hipLaunchKernelGGL(wf_reduce_sh, dim3((a.npix + 255) / 256), dim3(256), 0, stream, a, first_batch ? 1u : 0u, last_batch ? 1u : 0u);
-    return hipGetLastError();
-}
+hipError_t launch_wf_reduce(const WfArgs& a, bool first_batch, bool last_batch, hipStream_t stream) { return launch_reduce(wf_reduce, a, first_batch, last_batch, stream); }
+hipError_t launch_wf_reduce_sh(const WfArgs& a, bool first_batch, bool last_batch, hipStream_t stream) { return launch_reduce(wf_reduce_sh, a, first_batch, last_batch, stream); }
+hipError_t launch_wf_reduce_m2(const WfArgs& a, bool first_batch, bool last_batch, hipStream_t stream) { return launch_reduce(wf_reduce_m2, a, first_batch, last_batch, stream); }
+hipError_t launch_wf_reduce_psh(const WfArgs& a, bool first_batch, bool last_batch, hipStream_t stream) { return launch_reduce(wf_reduce_psh, a, first_batch, last_batch, stream); }
 
 hipError_t launch_sh_unpermute(const float* gathered, float* image, uint32_t width, uint32_t height, uint32_t tiles_x,
                                uint32_t world, uint32_t tiles_padded, hipStream_t stream) {
@@ -4274,314 +4698,13 @@ hipError_t launch_tonemap(const float* image, uint8_t* out, uint32_t n_pixels, f
     return hipGetLastError();
 }
 
-// ---------------------------------------------------------------- lightmap variance (mi_render_points_moments, mi_lightmap_finish_var)
-// Second moments of a point-table bake: the sums of squares of one batch of samples, behind wf_reduce.  One thread per texel (pixel): per
-// sample of the batch in order acc[c] = acc[c] + v.c * v.c (one multiply, one add, not fused: the pragma above), the sums living in A.m2
-// between batches and calls.  Every sum is one f32 chain in sample order from +0.0, divided once at the end by (float)S, wf_reduce's
-// division for the mean: the record is bit-identical however the samples are cut into batches, calls and ranks.  Only reads the sample
-// slots; empty texels' slots are +0.0 (wf_main's POINTS branch), so their moments are.  A table render carries no tile mask: no slot of
-// the image is left unwritten.
-__global__ __launch_bounds__(256) void wf_reduce_m2(WfArgs A, uint32_t first_batch, uint32_t last_batch) {
-    const uint32_t pix = blockIdx.x * blockDim.x + threadIdx.x;
-    if (pix >= A.npix) return;
-    float* rec = A.m2 + (size_t)pix * 3;
-    uint32_t px, py; bool in_image;
-    wf_pixel_of(A, pix, px, py, in_image);
-    if (!in_image) {                       // outside the image, or a padding slot: zeros, whatever the buffer held
-        rec[0] = 0.0f; rec[1] = 0.0f; rec[2] = 0.0f;
-        return;
-    }
-    float acc[3];
-    for (int k = 0; k < 3; k++) acc[k] = first_batch ? 0.0f : rec[k];
-    for (uint32_t s = 0; s < A.s_count; s++) {
-        const float4 v = A.samp[(size_t)s * A.npix + pix];
-        acc[0] = acc[0] + v.x * v.x; acc[1] = acc[1] + v.y * v.y; acc[2] = acc[2] + v.z * v.z;
-    }
-    const float n = (float)A.C.spp;
-    for (int k = 0; k < 3; k++) rec[k] = last_batch ? acc[k] / n : acc[k];
+// variance-guided finishing and the adaptive bake.  launch_lmv_init: counts == nullptr means a.samples for every texel
+hipError_t launch_lmv_init(const LmvArgs& a, const uint32_t* counts, bool few_inf, hipStream_t stream) {
+    return launch_per_item(lmv_init, (size_t)a.width * a.height, stream, a, counts, few_inf ? 1u : 0u);
 }
-
-// tracing.py lightmap_finish_var on the device, pass by pass: lightmap_finish with a colour weight whose width follows each texel's own
-// noise (the variance of its mean, from the bake's second moments, filtered along with the image).  Pure f32, the helper's operations in
-// the helper's order (no fused multiply-add: the pragma above; IEEE division and square root), a fixed tap order per texel, nothing
-// summed across threads: image and variance are the helper's bit for bit.  No address depends on a table value.
-
-// The variance of the mean per texel: v_c = fmaxf(0, m2_c - mean_c mean_c) / (float)(S - 1), V = (v_r + v_g) + v_b; empty texels +0.0
-__global__ __launch_bounds__(kBlock) void lmv_init(const LmvArgs a) {
-    const size_t n = (size_t)a.width * a.height, i = (size_t)blockIdx.x * kBlock + threadIdx.x;
-    if (i >= n) return;
-    float V = 0.0f;
-    if (lmf_covered(a.normals[3 * i], a.normals[3 * i + 1], a.normals[3 * i + 2])) {
-        const float d = (float)(a.samples - 1u);
-        float v[3];
-        for (int k = 0; k < 3; k++) {
-            const float mean = a.src[3 * i + k];
-            v[k] = fmaxf(0.0f, a.m2[3 * i + k] - mean * mean) / d;
-        }
-        V = (v[0] + v[1]) + v[2];
-    }
-    a.var_out[i] = V;
-}
-
-// The colour weight's denominator per covered texel: the variance blurred over the nine step-1 neighbours that lie in the image and are
-// covered (dy outer, dx inner, G3 = {1/4, 1/2, 1/4}), sd = sqrtf(bs / bw), den = sigma_color * sd + color_floor.  Empty texels +0.0
-// (never read).
-__global__ __launch_bounds__(kBlock) void lmv_blur(const LmvArgs a) {
-    const size_t n = (size_t)a.width * a.height, i = (size_t)blockIdx.x * kBlock + threadIdx.x;
-    if (i >= n) return;
-    const int W = (int)a.width, H = (int)a.height;
-    const int y = (int)(i / a.width), x = (int)(i - (size_t)y * a.width);
-    float den = 0.0f;
-    if (lmf_covered(a.normals[3 * i], a.normals[3 * i + 1], a.normals[3 * i + 2])) {
-        const float G3[3] = { 0.25f, 0.5f, 0.25f };
-        float bs = 0.0f, bw = 0.0f;
-#pragma unroll
-        for (int dy = -1; dy <= 1; dy++) {
-#pragma unroll
-            for (int dx = -1; dx <= 1; dx++) {
-                const int qx = x + dx, qy = y + dy;
-                if (qx < 0 || qx >= W || qy < 0 || qy >= H) continue;
-                const size_t j = (size_t)qy * W + qx;
-                if (!lmf_covered(a.normals[3 * j], a.normals[3 * j + 1], a.normals[3 * j + 2])) continue;
-                const float g = G3[dy + 1] * G3[dx + 1];
-                bs = bs + g * a.var_in[j];
-                bw = bw + g;
-            }
-        }
-        den = a.sigma_color * sqrtf(bs / bw) + a.color_floor;
-    }
-    a.den_out[i] = den;
-}
-
-// One filter level of the image and its variance.  lmf_atrous' direct form (one block per kTile x kTile tile, a thread owns the texels
-// (x, y + 8 k), k < 4, the taps straight from HBM / L2), with the colour weight wc = fmaxf(0, 1 - dc / den_p) and, beside sw and sc,
-// sv = sv + (w * w) * V_q: the texel becomes sc / sw and its variance sv / (sw * sw).
-__global__ __launch_bounds__(kBlock) void lmv_atrous(const LmvArgs a) {
-    const int s = (int)a.step, W = (int)a.width, H = (int)a.height;
-    const int x0 = (int)(blockIdx.x % a.tiles_x) * kTile, y0 = (int)(blockIdx.x / a.tiles_x) * kTile;
-    auto fetch3 = [&](const float* t, int qx, int qy, float* out) {
-        const size_t at = 3 * ((size_t)qy * W + qx);
-        for (int k = 0; k < 3; k++) out[k] = t[at + k];
-    };
-    const float H5[5] = { 0.0625f, 0.25f, 0.375f, 0.25f, 0.0625f };
-    const float r = a.reach * (float)s, rr = r * r;
-    const int gx = x0 + (int)(threadIdx.x & 31u);
-    for (int k4 = 0; k4 < 4; k4++) {
-        const int gy = y0 + (int)(threadIdx.x >> 5) + 8 * k4;
-        if (gx >= W || gy >= H) continue;
-        const size_t ip = (size_t)gy * W + gx;
-        float cp[3], pp[3], np[3];
-        fetch3(a.normals, gx, gy, np);
-        float out[3] = { 0.0f, 0.0f, 0.0f }, vout = 0.0f;
-        if (lmf_covered(np[0], np[1], np[2])) {
-            fetch3(a.src, gx, gy, cp); fetch3(a.points, gx, gy, pp);
-            const float den = a.den[ip];
-            float sw = 0.0f, sv = 0.0f, sc[3] = { 0.0f, 0.0f, 0.0f };
-#pragma unroll
-            for (int dy = -2; dy <= 2; dy++) {
-#pragma unroll
-                for (int dx = -2; dx <= 2; dx++) {
-                    const int qx = gx + s * dx, qy = gy + s * dy;
-                    if (qx < 0 || qx >= W || qy < 0 || qy >= H) continue;
-                    float nq[3];
-                    fetch3(a.normals, qx, qy, nq);
-                    if (!lmf_covered(nq[0], nq[1], nq[2])) continue;
-                    float cq[3], pq[3];
-                    fetch3(a.src, qx, qy, cq); fetch3(a.points, qx, qy, pq);
-                    const float D[3] = { pq[0] - pp[0], pq[1] - pp[1], pq[2] - pp[2] };
-                    const float d2 = (D[0] * D[0] + D[1] * D[1]) + D[2] * D[2];
-                    if ((dx != 0 || dy != 0) && !(d2 <= rr * (float)(dx * dx + dy * dy))) continue;      // the reach test, as lmf_atrous'
-                    const float h = H5[dy + 2] * H5[dx + 2];
-                    float wn = fmaxf(0.0f, (np[0] * nq[0] + np[1] * nq[1]) + np[2] * nq[2]);
-                    for (uint32_t i = 0; i < a.npow; i++) wn = wn * wn;
-                    const float dpl = fabsf((np[0] * D[0] + np[1] * D[1]) + np[2] * D[2]);
-                    const float wp = fmaxf(0.0f, 1.0f - dpl / a.sigma_plane);
-                    const float dc = (fabsf(cq[0] - cp[0]) + fabsf(cq[1] - cp[1])) + fabsf(cq[2] - cp[2]);
-                    const float wc = fmaxf(0.0f, 1.0f - dc / den);
-                    const float w = ((h * wn) * wp) * wc;
-                    sw = sw + w;
-                    for (int k = 0; k < 3; k++) sc[k] = sc[k] + w * cq[k];
-                    sv = sv + (w * w) * a.var_in[(size_t)qy * W + qx];
-                }
-            }
-            for (int k = 0; k < 3; k++) out[k] = sc[k] / sw;
-            vout = sv / (sw * sw);
-        }
-        for (int k = 0; k < 3; k++) a.dst[3 * ip + k] = out[k];
-        a.var_out[ip] = vout;
-    }
-}
-
-hipError_t launch_wf_reduce_m2(const WfArgs& a, bool first_batch, bool last_batch, hipStream_t stream) {
-    hipLaunchKernelGGL(wf_reduce_m2, dim3((a.npix + 255) / 256), dim3(256), 0, stream, a, first_batch ? 1u : 0u, last_batch ? 1u : 0u);
-    return hipGetLastError();
-}
-hipError_t launch_lmv_init(const LmvArgs& a, hipStream_t stream) {
-    const size_t n = (size_t)a.width * a.height;
-    hipLaunchKernelGGL(lmv_init, dim3((uint32_t)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, stream, a);
-    return hipGetLastError();
-}
-hipError_t launch_lmv_blur(const LmvArgs& a, hipStream_t stream) {
-    const size_t n = (size_t)a.width * a.height;
-    hipLaunchKernelGGL(lmv_blur, dim3((uint32_t)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, stream, a);
-    return hipGetLastError();
-}
+hipError_t launch_lmv_blur(const LmvArgs& a, hipStream_t stream) { return launch_per_item(lmv_blur, (size_t)a.width * a.height, stream, a); }
 hipError_t launch_lmv_atrous(const LmvArgs& a, hipStream_t stream) {
     hipLaunchKernelGGL(lmv_atrous, dim3(a.tiles_x * a.tiles_y), dim3(kBlock), 0, stream, a);
-    return hipGetLastError();
-}
-
-// ---------------------------------------------------------------- adaptive lightmap baking (mi_lightmap_select / _gather / _merge)
-// tracing.py lightmap_select, lightmap_gather and lightmap_merge on the device.  Pure f32, the helpers' operations in the helpers' order
-// (no fused multiply-add: the pragma above; IEEE division and square root), nothing summed across threads but integer counts, no atomics:
-// the list and the merged planes are the helpers' bit for bit and do not depend on scheduling.  No address depends on a table value but
-// through the list, whose entries are tested against W * H before they are used.
-
-// lmv_init with the texel's own count n: v_c = fmaxf(0, m2_c - mean_c mean_c) / (float)(n - 1), V = (v_r + v_g) + v_b; a covered texel
-// with n < 2 gets +inf (few_inf: mi_lightmap_select, "no information") or +0.0 (mi_lightmap_finish_var_counts); empty texels +0.0
-__global__ __launch_bounds__(kBlock) void lmv_init_counts(const LmvArgs a, const uint32_t* __restrict__ counts, uint32_t few_inf) {
-    const size_t n = (size_t)a.width * a.height, i = (size_t)blockIdx.x * kBlock + threadIdx.x;
-    if (i >= n) return;
-    float V = 0.0f;
-    if (lmf_covered(a.normals[3 * i], a.normals[3 * i + 1], a.normals[3 * i + 2])) {
-        const uint32_t cnt = counts[i];
-        if (cnt >= 2u) {
-            const float d = (float)(cnt - 1u);
-            float v[3];
-            for (int k = 0; k < 3; k++) {
-                const float mean = a.src[3 * i + k];
-                v[k] = fmaxf(0.0f, a.m2[3 * i + k] - mean * mean) / d;
-            }
-            V = (v[0] + v[1]) + v[2];
-        } else {
-            V = few_inf ? __builtin_inff() : 0.0f;
-        }
-    }
-    a.var_out[i] = V;
-}
-
-// One lane per texel, kLmaBlock consecutive texels per block: lmv_blur's sums in lmv_blur's order, sd = sqrtf(bs / bw), the texel's flag
-// sd > target_rel * lum + target_abs, and the number of flags in the block (a ballot per wave, the sixteen wave counts through LDS).
-__global__ __launch_bounds__(kLmaBlock) void lma_mark(const LmaArgs a) {
-    __shared__ uint32_t s_wave[kLmaBlock / 64];
-    const size_t n = (size_t)a.width * a.height, i = (size_t)blockIdx.x * kLmaBlock + threadIdx.x;
-    bool sel = false;
-    if (i < n) {
-        const int W = (int)a.width, H = (int)a.height;
-        const int y = (int)(i / a.width), x = (int)(i - (size_t)y * a.width);
-        float sd = 0.0f;
-        if (lmf_covered(a.normals[3 * i], a.normals[3 * i + 1], a.normals[3 * i + 2])) {
-            const float G3[3] = { 0.25f, 0.5f, 0.25f };
-            float bs = 0.0f, bw = 0.0f;
-#pragma unroll
-            for (int dy = -1; dy <= 1; dy++) {
-#pragma unroll
-                for (int dx = -1; dx <= 1; dx++) {
-                    const int qx = x + dx, qy = y + dy;
-                    if (qx < 0 || qx >= W || qy < 0 || qy >= H) continue;
-                    const size_t j = (size_t)qy * W + qx;
-                    if (!lmf_covered(a.normals[3 * j], a.normals[3 * j + 1], a.normals[3 * j + 2])) continue;
-                    const float g = G3[dy + 1] * G3[dx + 1];
-                    bs = bs + g * a.var[j];
-                    bw = bw + g;
-                }
-            }
-            sd = sqrtf(bs / bw);
-            const float lum = (fabsf(a.image[3 * i]) + fabsf(a.image[3 * i + 1])) + fabsf(a.image[3 * i + 2]);
-            const float thr = a.target_rel * lum + a.target_abs;
-            sel = sd > thr;
-        }
-        if (a.error) a.error[i] = sd;
-        a.flags[i] = sel ? (uint8_t)1 : (uint8_t)0;
-    }
-    const unsigned long long m = __builtin_amdgcn_ballot_w64(sel);
-    if ((threadIdx.x & 63u) == 0u) s_wave[threadIdx.x >> 6] = (uint32_t)__popcll(m);
-    __syncthreads();
-    if (threadIdx.x == 0u) {
-        uint32_t total = 0;
-        for (uint32_t k = 0; k < kLmaBlock / 64; k++) total += s_wave[k];
-        a.block_counts[blockIdx.x] = total;
-    }
-}
-
-// Exclusive prefix of the block counts (one block, the pattern of lm_scan); the total to *out_count
-__global__ __launch_bounds__(1024) void lma_scan(const LmaArgs a) {
-    __shared__ uint32_t s_sum[1024];
-    const uint32_t nb = a.blocks, per = (nb + 1023u) / 1024u;
-    const uint32_t lo = min(nb, threadIdx.x * per), hi = min(nb, lo + per);
-    uint32_t sum = 0;
-    for (uint32_t i = lo; i < hi; i++) sum += a.block_counts[i];
-    s_sum[threadIdx.x] = sum;
-    __syncthreads();
-    for (uint32_t d = 1; d < 1024u; d <<= 1) {              // inclusive scan of the threads' sums
-        const uint32_t v = threadIdx.x >= d ? s_sum[threadIdx.x - d] : 0u;
-        __syncthreads();
-        s_sum[threadIdx.x] += v;
-        __syncthreads();
-    }
-    uint32_t run = s_sum[threadIdx.x] - sum;
-    for (uint32_t i = lo; i < hi; i++) { a.block_offsets[i] = run; run += a.block_counts[i]; }
-    if (threadIdx.x == 1023u) *a.out_count = s_sum[1023];
-}
-
-// Every block writes its flagged texels' numbers at its offset, ascending: the waves before this one through LDS, the lanes before this
-// one from the ballot.  Positions at or beyond `capacity` are not written.
-__global__ __launch_bounds__(kLmaBlock) void lma_fill(const LmaArgs a) {
-    __shared__ uint32_t s_wave[kLmaBlock / 64];
-    const size_t n = (size_t)a.width * a.height, i = (size_t)blockIdx.x * kLmaBlock + threadIdx.x;
-    const bool sel = i < n && a.flags[i] != 0;
-    const unsigned long long m = __builtin_amdgcn_ballot_w64(sel);
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    if (lane == 0u) s_wave[wave] = (uint32_t)__popcll(m);
-    __syncthreads();
-    if (!sel) return;
-    uint32_t pos = a.block_offsets[blockIdx.x];
-    for (uint32_t k = 0; k < wave; k++) pos += s_wave[k];
-    pos += (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
-    if (pos < a.capacity) a.out_index[pos] = (uint32_t)i;
-}
-
-// One lane per slot of the compact table: entry `slot` of the list into every row, zeros (the empty-texel mark) behind the list's end
-// and for an entry outside the atlas
-__global__ __launch_bounds__(kBlock) void lma_gather(const LmaListArgs a) {
-    const size_t slot = (size_t)blockIdx.x * kBlock + threadIdx.x;
-    if (slot >= a.slots) return;
-    const size_t npix = (size_t)a.width * a.height;
-    size_t texel = 0;
-    bool live = slot < a.n;
-    if (live) {
-        const uint32_t idx = a.index[slot];
-        live = idx < npix;
-        texel = live ? idx : 0;
-    }
-    for (uint32_t r = 0; r < a.rows; r++) {
-        const size_t src = 3 * ((size_t)r * npix + texel), dst = 3 * ((size_t)r * a.slots + slot);
-        for (int k = 0; k < 3; k++) {
-            a.out_points[dst + k] = live ? a.points[src + k] : 0.0f;
-            a.out_normals[dst + k] = live ? a.normals[src + k] : 0.0f;
-        }
-    }
-}
-
-// One lane per list entry: x = ((float)n0 * x + (float)S' * x') / (float)(n0 + S') for the six values of the texel, counts = n0 + S'
-__global__ __launch_bounds__(kBlock) void lma_merge(const LmaListArgs a) {
-    const size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x;
-    if (i >= a.n) return;
-    const uint32_t idx = a.index[i];
-    if (idx >= (size_t)a.width * a.height) return;
-    const uint32_t n0 = a.counts[idx];
-    const float f0 = (float)n0, fs = (float)a.round_samples, ft = (float)(n0 + a.round_samples);
-    for (int k = 0; k < 3; k++) {
-        const size_t at = 3 * (size_t)idx + k;
-        a.image[at] = (f0 * a.image[at] + fs * a.mean[3 * i + k]) / ft;
-        a.m2[at] = (f0 * a.m2[at] + fs * a.m2_round[3 * i + k]) / ft;
-    }
-    a.counts[idx] = n0 + a.round_samples;
-}
-
-hipError_t launch_lmv_init_counts(const LmvArgs& a, const uint32_t* counts, bool few_inf, hipStream_t stream) {
-    const size_t n = (size_t)a.width * a.height;
-    hipLaunchKernelGGL(lmv_init_counts, dim3((uint32_t)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, stream, a, counts, few_inf ? 1u : 0u);
     return hipGetLastError();
 }
 // lma_mark, lma_scan, lma_fill: a.blocks = ceil(W H / kLmaBlock)
@@ -4591,229 +4714,7 @@ hipError_t launch_lma_select(const LmaArgs& a, hipStream_t stream) {
     if (a.capacity > 0) hipLaunchKernelGGL(lma_fill, dim3(a.blocks), dim3(kLmaBlock), 0, stream, a);
     return hipGetLastError();
 }
-hipError_t launch_lma_gather(const LmaListArgs& a, hipStream_t stream) {
-    hipLaunchKernelGGL(lma_gather, dim3((uint32_t)(((size_t)a.slots + kBlock - 1) / kBlock)), dim3(kBlock), 0, stream, a);
-    return hipGetLastError();
-}
-hipError_t launch_lma_merge(const LmaListArgs& a, hipStream_t stream) {
-    hipLaunchKernelGGL(lma_merge, dim3((a.n + kBlock - 1) / kBlock), dim3(kBlock), 0, stream, a);
-    return hipGetLastError();
-}
-
-// ---------------------------------------------------------------- directional lightmaps (mi_render_points_sh, mi_lightmap_finish_sh, mi_lightmap_sh_eval)
-// Point tables: the SH L2 projection of one batch of samples, behind wf_reduce.  wf_reduce_sh for the POINTS form: one thread per texel; per
-// sample of the batch in order it reads the row's normal from the caller's table, draws the direction again (the POINTS form's calls on
-// the same stream with the same device functions, so the same bits: rand_sphere_vec, y = |y|, rotate_from_unit_y), normalises it as
-// wf_reduce_sh does, and adds L * Y_k to the texel's 27 sums, which live in A.sh between batches and calls.  Every sum is one f32 chain in
-// sample order from +0.0, scaled once at the end by 2 pi / S (the directions are uniform over the hemisphere, pdf 1 / (2 pi)): the record
-// is bit-identical however the samples are cut into batches, calls and ranks.  A row whose normal is all-zero adds nothing and draws
-// nothing (its slot is +0.0, but the rotation about a zero normal is no direction).  Only reads the sample slots and the table; the
-// table's index is wf_main's, formed by no lane outside the image, and no address depends on a table value.
-__global__ __launch_bounds__(256) void wf_reduce_psh(WfArgs A, uint32_t first_batch, uint32_t last_batch) {
-    const uint32_t pix = blockIdx.x * blockDim.x + threadIdx.x;
-    if (pix >= A.npix) return;
-    float* rec = A.sh + (size_t)pix * kShFloats;
-    uint32_t px, py; bool in_image;
-    wf_pixel_of(A, pix, px, py, in_image);
-    if (!in_image) {                       // outside the image, or a padding slot: zeros, whatever the buffer held
-        for (int k = 0; k < kShFloats; k++) rec[k] = 0.0f;
-        return;
-    }
-    float acc[kShFloats];
-    for (int k = 0; k < kShFloats; k++) acc[k] = first_batch ? 0.0f : rec[k];
-    const uint32_t key = A.C.width * A.C.height + (py * A.C.width + px);
-    for (uint32_t s = 0; s < A.s_count; s++) {
-        const uint32_t sample = A.s_base + s;
-        const size_t r = (((size_t)(A.pt_rows == 1u ? 0u : sample) * A.C.height + py) * A.C.width + px) * 3;
-        const Ray3 tn = *(const Ray3*)(A.pt_n + r);
-        if (tn.x == 0.0f && tn.y == 0.0f && tn.z == 0.0f) continue;       // an empty row (either sign of zero)
-        const float4 v = A.samp[(size_t)s * A.npix + pix];
-        Rng tmp;
-        rng_init(tmp, A.seed_key, key, sample);
-        f3 u = rand_sphere_vec(tmp);                                       // materials.rs:172
-        u.y = fabsf(u.y);                                                  // :173
-        const f3 d = rotate_from_unit_y(mk3(tn.x, tn.y, tn.z), u);         // :176-177
-        const float inv = 1.0f / sqrtf(d.x * d.x + d.y * d.y + d.z * d.z);
-        const float x = d.x * inv, y = d.y * inv, z = d.z * inv;
-        const float Y[9] = { 0.28209479177387814f, 0.4886025119029199f * y, 0.4886025119029199f * z, 0.4886025119029199f * x,
-                             1.0925484305920792f * (x * y), 1.0925484305920792f * (y * z), 0.31539156525252005f * (3.0f * (z * z) - 1.0f),
-                             1.0925484305920792f * (x * z), 0.5462742152960396f * (x * x - y * y) };
-#pragma unroll
-        for (int k = 0; k < 9; k++) {
-            acc[3 * k] = acc[3 * k] + v.x * Y[k]; acc[3 * k + 1] = acc[3 * k + 1] + v.y * Y[k]; acc[3 * k + 2] = acc[3 * k + 2] + v.z * Y[k];
-        }
-    }
-    const float scale = last_batch ? 6.283185307179586f / (float)A.C.spp : 1.0f;       // 2 pi / S, once, behind the last sample
-#pragma unroll
-    for (int k = 0; k < kShFloats; k++) rec[k] = last_batch ? acc[k] * scale : acc[k];
-}
-
-// tracing.py lightmap_finish_sh on the device, pass by pass: lightmap_finish for [H][W][9][3] records.  The weights are lmf_atrous', the
-// colour distance taken from the three k = 0 coefficients; one weight per tap serves all 27 channels.  Pure f32, the helper's operations
-// in the helper's order, a fixed tap order per texel, nothing summed across threads.  No address depends on a table value.
-
-// The covered mask from the guide normals; with a.copy also dst = covered ? src : +0 for the 27 channels
-__global__ __launch_bounds__(kBlock) void lsh_mask(const LmfArgs a) {
-    const size_t n = (size_t)a.width * a.height, i = (size_t)blockIdx.x * kBlock + threadIdx.x;
-    if (i >= n) return;
-    const bool cov = lmf_covered(a.normals[3 * i], a.normals[3 * i + 1], a.normals[3 * i + 2]);
-    a.mask_out[i] = cov ? 1 : 0;
-    if (a.copy)
-        for (int k = 0; k < kShFloats; k++) a.dst[kShFloats * i + k] = cov ? a.src[kShFloats * i + k] : 0.0f;
-}
-
-// One filter level of the 27 channels.  lmf_atrous' direct form (one block per kTile x kTile tile, a thread owns the texels (x, y + 8 k),
-// k < 4, one after the other: 28 live accumulators, not 112), the taps straight from HBM / L2: a tap's guides and k = 0 coefficients
-// decide the weight, then its other 24 floats are read only when the tap is accepted.  Thirty-three planes of tile and halo do not fit
-// the LDS at any step, and the 108-byte records of neighbouring lanes share their cache lines, so nothing is staged.
-__global__ __launch_bounds__(kBlock) void lsh_atrous(const LmfArgs a) {
-    const int s = (int)a.step, W = (int)a.width, H = (int)a.height;
-    const int x0 = (int)(blockIdx.x % a.tiles_x) * kTile, y0 = (int)(blockIdx.x / a.tiles_x) * kTile;
-    auto fetch3 = [&](const float* t, size_t i, float* out) {
-        for (int k = 0; k < 3; k++) out[k] = t[3 * i + k];
-    };
-    const float H5[5] = { 0.0625f, 0.25f, 0.375f, 0.25f, 0.0625f };
-    const float fs = (float)s;
-    const float r = a.reach * fs, rr = r * r, sig_c = a.sigma_color / fs;
-    const int gx = x0 + (int)(threadIdx.x & 31u);
-#pragma unroll 1
-    for (int k4 = 0; k4 < 4; k4++) {
-        const int gy = y0 + (int)(threadIdx.x >> 5) + 8 * k4;
-        if (gx >= W || gy >= H) continue;
-        const size_t ip = (size_t)gy * W + gx;
-        float np[3];
-        fetch3(a.normals, ip, np);
-        float sc[kShFloats];
-#pragma unroll
-        for (int k = 0; k < kShFloats; k++) sc[k] = 0.0f;
-        const bool cov = lmf_covered(np[0], np[1], np[2]);
-        if (cov) {
-            float cp[3], pp[3];
-            fetch3(a.src, 9 * ip, cp); fetch3(a.points, ip, pp);          // the k = 0 coefficients head the record
-            float sw = 0.0f;
-#pragma unroll
-            for (int dy = -2; dy <= 2; dy++) {
-#pragma unroll
-                for (int dx = -2; dx <= 2; dx++) {
-                    const int qx = gx + s * dx, qy = gy + s * dy;
-                    if (qx < 0 || qx >= W || qy < 0 || qy >= H) continue;
-                    const size_t iq = (size_t)qy * W + qx;
-                    float nq[3];
-                    fetch3(a.normals, iq, nq);
-                    if (!lmf_covered(nq[0], nq[1], nq[2])) continue;
-                    float cq[3], pq[3];
-                    fetch3(a.src, 9 * iq, cq); fetch3(a.points, iq, pq);
-                    const float D[3] = { pq[0] - pp[0], pq[1] - pp[1], pq[2] - pp[2] };
-                    const float d2 = (D[0] * D[0] + D[1] * D[1]) + D[2] * D[2];
-                    if ((dx != 0 || dy != 0) && !(d2 <= rr * (float)(dx * dx + dy * dy))) continue;      // the reach test, as lmf_atrous'
-                    const float h = H5[dy + 2] * H5[dx + 2];
-                    float wn = fmaxf(0.0f, (np[0] * nq[0] + np[1] * nq[1]) + np[2] * nq[2]);
-                    for (uint32_t i = 0; i < a.npow; i++) wn = wn * wn;
-                    const float dpl = fabsf((np[0] * D[0] + np[1] * D[1]) + np[2] * D[2]);
-                    const float wp = fmaxf(0.0f, 1.0f - dpl / a.sigma_plane);
-                    const float dc = (fabsf(cq[0] - cp[0]) + fabsf(cq[1] - cp[1])) + fabsf(cq[2] - cp[2]);
-                    const float wc = fmaxf(0.0f, 1.0f - dc / sig_c);
-                    const float w = ((h * wn) * wp) * wc;
-                    sw = sw + w;
-                    const float* q = a.src + kShFloats * iq;
-#pragma unroll
-                    for (int k = 0; k < 3; k++) sc[k] = sc[k] + w * cq[k];
-#pragma unroll
-                    for (int k = 3; k < kShFloats; k++) sc[k] = sc[k] + w * q[k];
-                }
-            }
-#pragma unroll
-            for (int k = 0; k < kShFloats; k++) sc[k] = sc[k] / sw;
-        }
-        float* o = a.dst + kShFloats * ip;
-#pragma unroll
-        for (int k = 0; k < kShFloats; k++) o[k] = sc[k];
-    }
-}
-
-// One dilation pass of the 27 channels: lmf_dilate's neighbours, order and count
-__global__ __launch_bounds__(kBlock) void lsh_dilate(const LmfArgs a) {
-    const size_t n = (size_t)a.width * a.height, i = (size_t)blockIdx.x * kBlock + threadIdx.x;
-    if (i >= n) return;
-    const int W = (int)a.width, H = (int)a.height;
-    const int y = (int)(i / a.width), x = (int)(i - (size_t)y * a.width);
-    float out[kShFloats];
-#pragma unroll
-    for (int k = 0; k < kShFloats; k++) out[k] = 0.0f;
-    uint8_t valid = a.mask_in[i];
-    if (valid) {
-#pragma unroll
-        for (int k = 0; k < kShFloats; k++) out[k] = a.src[kShFloats * i + k];
-    } else {
-        int count = 0;
-        for (int dy = -1; dy <= 1; dy++)
-            for (int dx = -1; dx <= 1; dx++) {
-                const int qx = x + dx, qy = y + dy;
-                if ((dx == 0 && dy == 0) || qx < 0 || qx >= W || qy < 0 || qy >= H) continue;
-                const size_t j = (size_t)qy * W + qx;
-                if (!a.mask_in[j]) continue;
-#pragma unroll
-                for (int k = 0; k < kShFloats; k++) out[k] = out[k] + a.src[kShFloats * j + k];
-                count++;
-            }
-        if (count) {
-#pragma unroll
-            for (int k = 0; k < kShFloats; k++) out[k] = out[k] / (float)count;
-            valid = 1;
-        }
-    }
-#pragma unroll
-    for (int k = 0; k < kShFloats; k++) a.dst[kShFloats * i + k] = out[k];
-    a.mask_out[i] = valid;
-}
-
-// tracing.py lightmap_sh_eval on the device: the irradiance E(n) of one SH L2 record per point at the caller's normal, pv_sample's
-// normal, basis and constants K_k without the grid.  One lane per point: 108 + 12 bytes in, 12 out.  An all-zero normal gives +0.0.
-__global__ __launch_bounds__(kBlock) void lsh_eval(const LshEvalArgs a) {
-    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
-    if (i >= a.n) return;
-    const float nx = a.normals[3 * (size_t)i], ny = a.normals[3 * (size_t)i + 1], nz = a.normals[3 * (size_t)i + 2];
-    float E[3] = { 0.0f, 0.0f, 0.0f };
-    if (lmf_covered(nx, ny, nz)) {
-        const float K1 = (float)1.0233267079464885, K2 = (float)0.8580855308097834;
-        const float K[9] = { (float)0.886226925452758, K1, K1, K1, K2, K2, (float)0.24770795610037571, K2, (float)0.4290427654048917 };
-        const float l = sqrtf((nx * nx + ny * ny) + nz * nz);
-        const float x = nx / l, y = ny / l, z = nz / l;
-        const float b[9] = { 1.0f, y, z, x, x * y, y * z, 3.0f * (z * z) - 1.0f, x * z, x * x - y * y };
-        const float* sh = a.sh + (size_t)i * kShFloats;
-#pragma unroll
-        for (int c = 0; c < 3; c++) {
-            float e = b[0] * (sh[c] * K[0]);
-#pragma unroll
-            for (int k = 1; k < 9; k++) e = e + b[k] * (sh[3 * k + c] * K[k]);
-            E[c] = e;
-        }
-    }
-#pragma unroll
-    for (int c = 0; c < 3; c++) a.out_irradiance[3 * (size_t)i + c] = E[c];
-}
-
-hipError_t launch_wf_reduce_psh(const WfArgs& a, bool first_batch, bool last_batch, hipStream_t stream) {
-    hipLaunchKernelGGL(wf_reduce_psh, dim3((a.npix + 255) / 256), dim3(256), 0, stream, a, first_batch ? 1u : 0u, last_batch ? 1u : 0u);
-    return hipGetLastError();
-}
-hipError_t launch_lsh_mask(const LmfArgs& a, hipStream_t stream) {
-    const size_t n = (size_t)a.width * a.height;
-    hipLaunchKernelGGL(lsh_mask, dim3((uint32_t)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, stream, a);
-    return hipGetLastError();
-}
-hipError_t launch_lsh_atrous(const LmfArgs& a, hipStream_t stream) {
-    hipLaunchKernelGGL(lsh_atrous, dim3(a.tiles_x * a.tiles_y), dim3(kBlock), 0, stream, a);
-    return hipGetLastError();
-}
-hipError_t launch_lsh_dilate(const LmfArgs& a, hipStream_t stream) {
-    const size_t n = (size_t)a.width * a.height;
-    hipLaunchKernelGGL(lsh_dilate, dim3((uint32_t)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, stream, a);
-    return hipGetLastError();
-}
-hipError_t launch_lsh_eval(const LshEvalArgs& a, hipStream_t stream) {
-    hipLaunchKernelGGL(lsh_eval, dim3((a.n + kBlock - 1) / kBlock), dim3(kBlock), 0, stream, a);
-    return hipGetLastError();
-}
+hipError_t launch_lma_gather(const LmaListArgs& a, hipStream_t stream) { return launch_per_item(lma_gather, a.slots, stream, a); }
+hipError_t launch_lma_merge(const LmaListArgs& a, hipStream_t stream) { return launch_per_item(lma_merge, a.n, stream, a); }
 
 }  // namespace pt

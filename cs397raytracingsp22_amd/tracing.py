@@ -611,6 +611,13 @@ def _lightmap_texels_jittered(positions, normals, texcoords, indices, width, hei
 
 _LMF_TAPS = tuple((dy, dx) for dy in range(-2, 3) for dx in range(-2, 3))                          # dy outer, dx inner
 _LMF_RING = tuple((dy, dx) for dy in (-1, 0, 1) for dx in (-1, 0, 1) if (dy, dx) != (0, 0))        # the 8-neighbours, same order
+_LMV_BLUR = tuple((dy, dx) for dy in (-1, 0, 1) for dx in (-1, 0, 1))                              # dy outer, dx inner, the centre included
+
+
+def _centre_table(table):
+    """lightmap_texels' [1, H, W, 3] centre table as [H, W, 3]; any other array as it is"""
+    t = np.asarray(table)
+    return t[0] if t.ndim == 4 and t.shape[0] == 1 else t
 
 
 def check_finish_tables(image, points, normals):
@@ -625,13 +632,140 @@ def check_finish_tables(image, points, normals):
     return img, P, N
 
 
+# The building blocks of lightmap_finish, lightmap_finish_sh, lightmap_finish_var and lightmap_select: each rule of those definitions is
+# written once, here.  All f32, one rounding per operation, in the order written; the callers hold np.errstate(all="ignore").
+def _lm_covered(N):
+    """A texel is covered when its normal is not all-zero (either sign of zero is empty)"""
+    return (N[..., 0] != 0) | (N[..., 1] != 0) | (N[..., 2] != 0)
+
+
+def _lmv_variance(mean, M2, n, covered, few):
+    """The variance of the mean: v_c = max(0, m2_c - mean_c mean_c) / (n - 1), V = (v_r + v_g) + v_b, with n one number or the texels' own
+    [H, W] counts; `few` where n < 2, +0.0 on empty texels"""
+    f32 = np.float32
+    n = np.asarray(n).astype(np.int64)
+    d = np.maximum(n - 1, 1).astype(f32)
+    v3 = np.fmax(f32(0.0), M2 - mean * mean) / d[..., None]
+    V = np.where(n >= 2, (v3[..., 0] + v3[..., 1]) + v3[..., 2], few)
+    return np.where(covered, V, f32(0.0)).astype(f32)
+
+
+def _lmv_blur(V, N, covered, b):
+    """(bs, bw): the sums g V_q and g over the nine neighbours at spacing b that lie in the image and are covered, dy outer, dx inner,
+    g = G3[dy] G3[dx].  Meaningful on covered texels only."""
+    f32 = np.float32
+    G3 = (f32(0.25), f32(0.5), f32(0.25))
+    H, W = V.shape
+    vb, nb = np.pad(V, b), np.pad(N, ((b, b), (b, b), (0, 0)))
+    bs = np.zeros((H, W), f32)
+    bw = np.zeros((H, W), f32)
+    for dy, dx in _LMV_BLUR:
+        ys, xs = b + b * dy, b + b * dx
+        vq, nq = vb[ys:ys + H, xs:xs + W], nb[ys:ys + H, xs:xs + W]
+        btake = covered & _lm_covered(nq)
+        g = G3[dy + 1] * G3[dx + 1]
+        bs = np.where(btake, bs + g * vq, bs)
+        bw = np.where(btake, bw + g, bw)
+    return bs, bw
+
+
+def _lmf_level(cur, P, N, covered, s, npow, sig_p, rch, den, V=None):
+    """One a-trous level at step s of an image [H, W, C], C >= 3: every channel takes the same weights, whose colour distance is taken from
+    the first three and divided by `den`, one number or an [H, W] plane read at p.  With a variance plane V also sv = sv + (w w) V_q.
+    Returns (sc / sw, sv / (sw sw) or None), +0.0 on empty texels."""
+    f32 = np.float32
+    zero, one = f32(0.0), f32(1.0)
+    H5 = (f32(0.0625), f32(0.25), f32(0.375), f32(0.25), f32(0.0625))
+    H, W, C = cur.shape
+    r = rch * f32(s)
+    rr = r * r
+    pad = 2 * s
+    cpad, ppad, npad = (np.pad(t, ((pad, pad), (pad, pad), (0, 0))) for t in (cur, P, N))      # beyond the image: empty texels
+    sw = np.zeros((H, W), f32)
+    sc = np.zeros((H, W, C), f32)
+    if V is not None:
+        vpad = np.pad(V, pad)
+        sv = np.zeros((H, W), f32)
+    for dy, dx in _LMF_TAPS:
+        ys, xs = pad + s * dy, pad + s * dx
+        cq, pq, nq = (t[ys:ys + H, xs:xs + W] for t in (cpad, ppad, npad))
+        take = covered & _lm_covered(nq)
+        D = pq - P
+        d2 = (D[..., 0] * D[..., 0] + D[..., 1] * D[..., 1]) + D[..., 2] * D[..., 2]
+        if dx != 0 or dy != 0:                # the centre always passes (0 <= 0; inf * 0 must not reject it)
+            take = take & (d2 <= rr * f32(dx * dx + dy * dy))
+        h = H5[dy + 2] * H5[dx + 2]
+        wn = np.fmax(zero, (N[..., 0] * nq[..., 0] + N[..., 1] * nq[..., 1]) + N[..., 2] * nq[..., 2])
+        for _ in range(npow):
+            wn = wn * wn
+        dpl = np.abs((N[..., 0] * D[..., 0] + N[..., 1] * D[..., 1]) + N[..., 2] * D[..., 2])
+        wp = np.fmax(zero, one - dpl / sig_p)
+        dc = (np.abs(cq[..., 0] - cur[..., 0]) + np.abs(cq[..., 1] - cur[..., 1])) + np.abs(cq[..., 2] - cur[..., 2])
+        wc = np.fmax(zero, one - dc / den)
+        w = ((h * wn) * wp) * wc
+        sw = np.where(take, sw + w, sw)
+        sc = np.where(take[..., None], sc + w[..., None] * cq, sc)
+        if V is not None:
+            vq = vpad[ys:ys + H, xs:xs + W]
+            sv = np.where(take, sv + (w * w) * vq, sv)
+    out = np.where(covered[..., None], sc / sw[..., None], zero)
+    return out, None if V is None else np.where(covered, sv / (sw * sw), zero)
+
+
+def _lmf_dilate(cur, covered, passes):
+    """`passes` dilation passes of an image [H, W, C] whose valid texels are the covered ones: (image, valid)"""
+    f32 = np.float32
+    H, W, C = cur.shape
+    valid = covered.copy()
+    cur = np.ascontiguousarray(cur, f32)
+    for _ in range(passes):
+        prev_valid, prev = valid.copy(), cur.copy()
+        vpad = np.pad(prev_valid, 1)
+        near = np.zeros((H, W), bool)
+        for dy, dx in _LMF_RING:
+            near |= vpad[1 + dy:1 + dy + H, 1 + dx:1 + dx + W]
+        for y, x in np.argwhere(near & ~prev_valid):         # the pass's frontier, texel by texel: the order of the sum is the contract
+            total, count = np.zeros(C, f32), 0
+            for dy, dx in _LMF_RING:
+                qy, qx = y + dy, x + dx
+                if 0 <= qy < H and 0 <= qx < W and prev_valid[qy, qx]:
+                    total = total + prev[qy, qx]
+                    count += 1
+            cur[y, x] = total / f32(count)
+            valid[y, x] = True
+    return cur, valid
+
+
+def _check_finish_passes(levels, normal_power_log2, dilate):
+    levels, npow, dilate = int(levels), int(normal_power_log2), int(dilate)
+    if not (0 <= levels <= 8 and 0 <= npow <= 7 and 0 <= dilate <= 256):
+        raise ValueError("levels must be in 0 .. 8, normal_power_log2 in 0 .. 7 and dilate in 0 .. 256")
+    return levels, npow, dilate
+
+
+def _lmf_finish(img, P, N, levels, normal_power_log2, sigma_plane, reach, sigma_color, dilate):
+    """lightmap_finish behind its table check, for an image [H, W, C], C >= 3: the parameter checks, the levels, the dilation"""
+    f32 = np.float32
+    levels, npow, dilate = _check_finish_passes(levels, normal_power_log2, dilate)
+    sig_p, rch, sig_c0 = f32(sigma_plane), f32(reach), f32(sigma_color)
+    if not (sig_p > 0 and rch > 0 and sig_c0 > 0):
+        raise ValueError("sigma_plane, reach and sigma_color must be > 0 (inf turns one off)")
+    covered = _lm_covered(N)
+    cur = np.where(covered[..., None], img, f32(0.0))
+    with np.errstate(all="ignore"):
+        for level in range(levels):
+            s = 1 << level
+            cur, _ = _lmf_level(cur, P, N, covered, s, npow, sig_p, rch, sig_c0 / f32(s))
+        return _lmf_dilate(cur, covered, dilate)
+
+
 def lightmap_finish(image, points, normals, levels: int = 3, normal_power_log2: int = 5, sigma_plane: float = float("inf"),
                     reach: float = float("inf"), sigma_color: float = float("inf"), dilate: int = 4):
     """Finish a baked lightmap on the host (numpy only): an edge-aware a-trous filter guided by the atlas's own table, then gutter
     dilation.  This is the DEFINITION of mi_lightmap_finish, which equals it bit for bit.  `image` [H, W, 3] f32 is the raw bake
     (bake_lightmap's f32 image: empty texels zero), `points` and `normals` [H, W, 3] f32 the CENTRE table of the atlas (lightmap_texels
     without jitter, also for a jittered bake).  Returns (out [H, W, 3] f32, valid [H, W] bool).
-    A texel is covered when its normal is not all-zero.  Everything is f32, one rounding per operation, in the order written below.
+    A texel is covered when its normal is not all-zero.  Everything is f32, one rounding per operation, in the order of the building blocks above.
     Filter: levels i = 0 .. levels-1, step s = 2^i, each reading the previous level's image.  A covered texel p visits the 25 taps
     q = p + s (dx, dy), dy outer, dx inner, both -2 .. 2, skipping taps outside the image and empty ones, and those the reach test
     rejects: with D = P_q - P_p a tap other than the centre is kept only when |D|^2 <= (reach s)^2 (dx^2 + dy^2) — `reach` is the world
@@ -642,144 +776,15 @@ def lightmap_finish(image, points, normals, levels: int = 3, normal_power_log2: 
     Dilation: `dilate` passes; in each a texel that is not valid but has valid 8-neighbours in the previous pass's state takes their
     mean (summed dy outer, dx inner) and turns valid: texel t is filled in pass number Chebyshev-distance(t, covered).
     Non-finite values spoil the texels whose footprint (radius 2 (2^levels - 1) + dilate) reaches them, and no others."""
-    f32 = np.float32
     img, P, N = check_finish_tables(image, points, normals)
-    levels, npow, dilate = int(levels), int(normal_power_log2), int(dilate)
-    if not (0 <= levels <= 8 and 0 <= npow <= 7 and 0 <= dilate <= 256):
-        raise ValueError("levels must be in 0 .. 8, normal_power_log2 in 0 .. 7 and dilate in 0 .. 256")
-    sig_p, rch, sig_c0 = f32(sigma_plane), f32(reach), f32(sigma_color)
-    if not (sig_p > 0 and rch > 0 and sig_c0 > 0):
-        raise ValueError("sigma_plane, reach and sigma_color must be > 0 (inf turns one off)")
-    H, W = img.shape[:2]
-    zero, one = f32(0.0), f32(1.0)
-    H5 = (f32(0.0625), f32(0.25), f32(0.375), f32(0.25), f32(0.0625))
-    covered = (N[..., 0] != 0) | (N[..., 1] != 0) | (N[..., 2] != 0)
-    cur = np.where(covered[..., None], img, zero)
-    with np.errstate(all="ignore"):
-        for level in range(levels):
-            s = 1 << level
-            fs = f32(s)
-            r = rch * fs
-            rr = r * r
-            sig_c = sig_c0 / fs
-            pad = 2 * s
-            cpad, ppad, npad = (np.pad(t, ((pad, pad), (pad, pad), (0, 0))) for t in (cur, P, N))      # beyond the image: empty texels
-            sw = np.zeros((H, W), f32)
-            sc = np.zeros((H, W, 3), f32)
-            for dy, dx in _LMF_TAPS:
-                ys, xs = pad + s * dy, pad + s * dx
-                cq, pq, nq = (t[ys:ys + H, xs:xs + W] for t in (cpad, ppad, npad))
-                take = covered & ((nq[..., 0] != 0) | (nq[..., 1] != 0) | (nq[..., 2] != 0))
-                D = pq - P
-                d2 = (D[..., 0] * D[..., 0] + D[..., 1] * D[..., 1]) + D[..., 2] * D[..., 2]
-                if dx != 0 or dy != 0:                # the centre always passes (0 <= 0; inf * 0 must not reject it)
-                    take = take & (d2 <= rr * f32(dx * dx + dy * dy))
-                h = H5[dy + 2] * H5[dx + 2]
-                wn = np.fmax(zero, (N[..., 0] * nq[..., 0] + N[..., 1] * nq[..., 1]) + N[..., 2] * nq[..., 2])
-                for _ in range(npow):
-                    wn = wn * wn
-                dpl = np.abs((N[..., 0] * D[..., 0] + N[..., 1] * D[..., 1]) + N[..., 2] * D[..., 2])
-                wp = np.fmax(zero, one - dpl / sig_p)
-                dc = (np.abs(cq[..., 0] - cur[..., 0]) + np.abs(cq[..., 1] - cur[..., 1])) + np.abs(cq[..., 2] - cur[..., 2])
-                wc = np.fmax(zero, one - dc / sig_c)
-                w = ((h * wn) * wp) * wc
-                sw = np.where(take, sw + w, sw)
-                sc = np.where(take[..., None], sc + w[..., None] * cq, sc)
-            cur = np.where(covered[..., None], sc / sw[..., None], zero)
-        valid = covered.copy()
-        cur = np.ascontiguousarray(cur, f32)
-        for _ in range(dilate):
-            prev_valid, prev = valid.copy(), cur.copy()
-            vpad = np.pad(prev_valid, 1)
-            near = np.zeros((H, W), bool)
-            for dy, dx in _LMF_RING:
-                near |= vpad[1 + dy:1 + dy + H, 1 + dx:1 + dx + W]
-            for y, x in np.argwhere(near & ~prev_valid):         # the pass's frontier, texel by texel: the order of the sum is the contract
-                total, count = np.zeros(3, f32), 0
-                for dy, dx in _LMF_RING:
-                    qy, qx = y + dy, x + dx
-                    if 0 <= qy < H and 0 <= qx < W and prev_valid[qy, qx]:
-                        total = total + prev[qy, qx]
-                        count += 1
-                cur[y, x] = total / f32(count)
-                valid[y, x] = True
-    return cur, valid
-
-
-def _lightmap_finish_channels(img, P, N, levels, normal_power_log2, sigma_plane, reach, sigma_color, dilate):
-    """lightmap_finish's body, statement for statement, for a checked image of C >= 3 channels [H, W, C]: every channel takes the same
-    weights, whose colour distance is taken from the first three.  (lightmap_finish keeps its own text: tests mutate its source.)"""
-    f32 = np.float32
-    C = img.shape[2]
-    levels, npow, dilate = int(levels), int(normal_power_log2), int(dilate)
-    if not (0 <= levels <= 8 and 0 <= npow <= 7 and 0 <= dilate <= 256):
-        raise ValueError("levels must be in 0 .. 8, normal_power_log2 in 0 .. 7 and dilate in 0 .. 256")
-    sig_p, rch, sig_c0 = f32(sigma_plane), f32(reach), f32(sigma_color)
-    if not (sig_p > 0 and rch > 0 and sig_c0 > 0):
-        raise ValueError("sigma_plane, reach and sigma_color must be > 0 (inf turns one off)")
-    H, W = img.shape[:2]
-    zero, one = f32(0.0), f32(1.0)
-    H5 = (f32(0.0625), f32(0.25), f32(0.375), f32(0.25), f32(0.0625))
-    covered = (N[..., 0] != 0) | (N[..., 1] != 0) | (N[..., 2] != 0)
-    cur = np.where(covered[..., None], img, zero)
-    with np.errstate(all="ignore"):
-        for level in range(levels):
-            s = 1 << level
-            fs = f32(s)
-            r = rch * fs
-            rr = r * r
-            sig_c = sig_c0 / fs
-            pad = 2 * s
-            cpad, ppad, npad = (np.pad(t, ((pad, pad), (pad, pad), (0, 0))) for t in (cur, P, N))      # beyond the image: empty texels
-            sw = np.zeros((H, W), f32)
-            sc = np.zeros((H, W, C), f32)
-            for dy, dx in _LMF_TAPS:
-                ys, xs = pad + s * dy, pad + s * dx
-                cq, pq, nq = (t[ys:ys + H, xs:xs + W] for t in (cpad, ppad, npad))
-                take = covered & ((nq[..., 0] != 0) | (nq[..., 1] != 0) | (nq[..., 2] != 0))
-                D = pq - P
-                d2 = (D[..., 0] * D[..., 0] + D[..., 1] * D[..., 1]) + D[..., 2] * D[..., 2]
-                if dx != 0 or dy != 0:                # the centre always passes (0 <= 0; inf * 0 must not reject it)
-                    take = take & (d2 <= rr * f32(dx * dx + dy * dy))
-                h = H5[dy + 2] * H5[dx + 2]
-                wn = np.fmax(zero, (N[..., 0] * nq[..., 0] + N[..., 1] * nq[..., 1]) + N[..., 2] * nq[..., 2])
-                for _ in range(npow):
-                    wn = wn * wn
-                dpl = np.abs((N[..., 0] * D[..., 0] + N[..., 1] * D[..., 1]) + N[..., 2] * D[..., 2])
-                wp = np.fmax(zero, one - dpl / sig_p)
-                dc = (np.abs(cq[..., 0] - cur[..., 0]) + np.abs(cq[..., 1] - cur[..., 1])) + np.abs(cq[..., 2] - cur[..., 2])
-                wc = np.fmax(zero, one - dc / sig_c)
-                w = ((h * wn) * wp) * wc
-                sw = np.where(take, sw + w, sw)
-                sc = np.where(take[..., None], sc + w[..., None] * cq, sc)
-            cur = np.where(covered[..., None], sc / sw[..., None], zero)
-        valid = covered.copy()
-        cur = np.ascontiguousarray(cur, f32)
-        for _ in range(dilate):
-            prev_valid, prev = valid.copy(), cur.copy()
-            vpad = np.pad(prev_valid, 1)
-            near = np.zeros((H, W), bool)
-            for dy, dx in _LMF_RING:
-                near |= vpad[1 + dy:1 + dy + H, 1 + dx:1 + dx + W]
-            for y, x in np.argwhere(near & ~prev_valid):         # the pass's frontier, texel by texel: the order of the sum is the contract
-                total, count = np.zeros(C, f32), 0
-                for dy, dx in _LMF_RING:
-                    qy, qx = y + dy, x + dx
-                    if 0 <= qy < H and 0 <= qx < W and prev_valid[qy, qx]:
-                        total = total + prev[qy, qx]
-                        count += 1
-                cur[y, x] = total / f32(count)
-                valid[y, x] = True
-    return cur, valid
+    return _lmf_finish(img, P, N, levels, normal_power_log2, sigma_plane, reach, sigma_color, dilate)
 
 
 def check_finish_sh_tables(sh, points, normals):
     """(sh [H, W, 9, 3], points [H, W, 3], normals [H, W, 3]) as contiguous float32 arrays, 1 <= W, H <= 32768, for lightmap_finish_sh;
     the guides may be lightmap_texels' [1, H, W, 3]"""
     S = np.ascontiguousarray(sh, np.float32)
-    P, N = np.asarray(points, np.float32), np.asarray(normals, np.float32)
-    P, N = (t[0] if t.ndim == 4 and t.shape[0] == 1 else t for t in (P, N))
-    P, N = np.ascontiguousarray(P), np.ascontiguousarray(N)
+    P, N = (np.ascontiguousarray(_centre_table(t), np.float32) for t in (points, normals))
     if S.ndim != 4 or S.shape[2:] != (9, 3) or P.shape != S.shape[:2] + (3,) or N.shape != P.shape:
         raise ValueError(f"sh must be [H, W, 9, 3] and points and normals [H, W, 3], got {S.shape}, {P.shape} and {N.shape}")
     if not (1 <= S.shape[0] <= 32768 and 1 <= S.shape[1] <= 32768):
@@ -799,7 +804,7 @@ def lightmap_finish_sh(sh, points, normals, levels: int = 3, normal_power_log2: 
     out[..., k, :] is lightmap_finish of sh[..., k, :] for every k."""
     S, P, N = check_finish_sh_tables(sh, points, normals)
     H, W = S.shape[:2]
-    out, valid = _lightmap_finish_channels(S.reshape(H, W, 27), P, N, levels, normal_power_log2, sigma_plane, reach, sigma_color, dilate)
+    out, valid = _lmf_finish(S.reshape(H, W, 27), P, N, levels, normal_power_log2, sigma_plane, reach, sigma_color, dilate)
     return np.ascontiguousarray(out.reshape(H, W, 9, 3)), valid
 
 
@@ -842,9 +847,6 @@ def lightmap_sh_eval(sh, normals) -> np.ndarray:
     return np.ascontiguousarray(E.reshape(shape + (3,)))
 
 
-_LMV_BLUR = tuple((dy, dx) for dy in (-1, 0, 1) for dx in (-1, 0, 1))                              # dy outer, dx inner, the centre included
-
-
 def lightmap_finish_var(image, m2, samples, points, normals, levels: int = 3, normal_power_log2: int = 5,
                         sigma_plane: float = float("inf"), reach: float = float("inf"), sigma_color: float = 8.0,
                         color_floor: float = 1e-6, dilate: int = 4):
@@ -852,7 +854,7 @@ def lightmap_finish_var(image, m2, samples, points, normals, levels: int = 3, no
     it bit for bit.  `image` and `m2` [H, W, 3] f32 are the mean and the mean of squares of a bake of `samples` = S samples per texel
     (bake_lightmap_moments), `points` and `normals` the centre table, as for lightmap_finish.  Returns (out [H, W, 3] f32,
     var [H, W] f32, valid [H, W] bool).  The coverage rule, the tap order, h, wn, wp, the reach test, the centre tap's exemption and the
-    dilation are lightmap_finish's; everything is f32, one rounding per operation, in the order written below.
+    dilation are lightmap_finish's; everything is f32, one rounding per operation, in the order of the building blocks above.
     Initial variance of the mean, covered texels: v_c = max(0, m2_c - mean_c mean_c) / (S - 1), V = (v_r + v_g) + v_b; empty texels +0.0.
     The difference cancels in f32: V means nothing where the true noise is below about 1e-3 of the mean; `color_floor` is for that case.
     Per level (step s = 2^i): first the blur, bs = sum g V_q and bw = sum g over the nine neighbours at step 1 (whatever s is) that lie
@@ -870,16 +872,13 @@ def lightmap_finish_var(image, m2, samples, points, normals, levels: int = 3, no
     M2 = np.ascontiguousarray(m2, f32)
     if M2.shape != img.shape:
         raise ValueError(f"m2 must have the image's shape {img.shape}, got {M2.shape}")
-    counts = None
     if np.ndim(samples) != 0:                # a plane of per-texel counts (mi_lightmap_finish_var_counts)
-        counts = check_counts_plane(samples, img.shape[:2])
+        n = check_counts_plane(samples, img.shape[:2])
     else:
-        S = int(samples)
-        if not 2 <= S <= 65535:
+        n = int(samples)
+        if not 2 <= n <= 65535:
             raise ValueError(f"samples must be in 2 .. 65535, got {samples}")
-    levels, npow, dilate = int(levels), int(normal_power_log2), int(dilate)
-    if not (0 <= levels <= 8 and 0 <= npow <= 7 and 0 <= dilate <= 256):
-        raise ValueError("levels must be in 0 .. 8, normal_power_log2 in 0 .. 7 and dilate in 0 .. 256")
+    levels, npow, dilate = _check_finish_passes(levels, normal_power_log2, dilate)
     sig_p, rch, sig_c0, floor = f32(sigma_plane), f32(reach), f32(sigma_color), f32(color_floor)
     if not (sig_p > 0 and rch > 0):
         raise ValueError("sigma_plane and reach must be > 0 (inf turns one off)")
@@ -887,84 +886,17 @@ def lightmap_finish_var(image, m2, samples, points, normals, levels: int = 3, no
         raise ValueError("sigma_color must be finite and >= 0")
     if not floor > 0:
         raise ValueError("color_floor must be > 0 (inf turns the colour weight off)")
-    H, W = img.shape[:2]
-    zero, one = f32(0.0), f32(1.0)
-    H5 = (f32(0.0625), f32(0.25), f32(0.375), f32(0.25), f32(0.0625))
-    G3 = (f32(0.25), f32(0.5), f32(0.25))
-    covered = (N[..., 0] != 0) | (N[..., 1] != 0) | (N[..., 2] != 0)
-    cur = np.where(covered[..., None], img, zero)
+    covered = _lm_covered(N)
+    cur = np.where(covered[..., None], img, f32(0.0))
     with np.errstate(all="ignore"):
-        if counts is None:
-            v3 = np.fmax(zero, M2 - cur * cur) / f32(S - 1)
-            V = np.where(covered, (v3[..., 0] + v3[..., 1]) + v3[..., 2], zero)
-        else:
-            V = _lmv_init_counts(cur, M2, counts, covered, zero)
+        V = _lmv_variance(cur, M2, n, covered, f32(0.0))
         for level in range(levels):
             s = 1 << level
-            fs = f32(s)
-            r = rch * fs
-            rr = r * r
-            # the blur of the variance: always at step 1
-            b = 1
-            vb, nb = np.pad(V, b), np.pad(N, ((b, b), (b, b), (0, 0)))
-            bs = np.zeros((H, W), f32)
-            bw = np.zeros((H, W), f32)
-            for dy, dx in _LMV_BLUR:
-                ys, xs = b + b * dy, b + b * dx
-                vq, nq = vb[ys:ys + H, xs:xs + W], nb[ys:ys + H, xs:xs + W]
-                btake = covered & ((nq[..., 0] != 0) | (nq[..., 1] != 0) | (nq[..., 2] != 0))
-                g = G3[dy + 1] * G3[dx + 1]
-                bs = np.where(btake, bs + g * vq, bs)
-                bw = np.where(btake, bw + g, bw)
+            bs, bw = _lmv_blur(V, N, covered, 1)              # always at step 1, whatever s is
             sd = np.sqrt(bs / bw)
             den = sig_c0 * sd + floor
-            pad = 2 * s
-            cpad, ppad, npad = (np.pad(t, ((pad, pad), (pad, pad), (0, 0))) for t in (cur, P, N))      # beyond the image: empty texels
-            vpad = np.pad(V, pad)
-            sw = np.zeros((H, W), f32)
-            sv = np.zeros((H, W), f32)
-            sc = np.zeros((H, W, 3), f32)
-            for dy, dx in _LMF_TAPS:
-                ys, xs = pad + s * dy, pad + s * dx
-                cq, pq, nq = (t[ys:ys + H, xs:xs + W] for t in (cpad, ppad, npad))
-                vq = vpad[ys:ys + H, xs:xs + W]
-                take = covered & ((nq[..., 0] != 0) | (nq[..., 1] != 0) | (nq[..., 2] != 0))
-                D = pq - P
-                d2 = (D[..., 0] * D[..., 0] + D[..., 1] * D[..., 1]) + D[..., 2] * D[..., 2]
-                if dx != 0 or dy != 0:                # the centre always passes (0 <= 0; inf * 0 must not reject it)
-                    take = take & (d2 <= rr * f32(dx * dx + dy * dy))
-                h = H5[dy + 2] * H5[dx + 2]
-                wn = np.fmax(zero, (N[..., 0] * nq[..., 0] + N[..., 1] * nq[..., 1]) + N[..., 2] * nq[..., 2])
-                for _ in range(npow):
-                    wn = wn * wn
-                dpl = np.abs((N[..., 0] * D[..., 0] + N[..., 1] * D[..., 1]) + N[..., 2] * D[..., 2])
-                wp = np.fmax(zero, one - dpl / sig_p)
-                dc = (np.abs(cq[..., 0] - cur[..., 0]) + np.abs(cq[..., 1] - cur[..., 1])) + np.abs(cq[..., 2] - cur[..., 2])
-                wc = np.fmax(zero, one - dc / den)
-                w = ((h * wn) * wp) * wc
-                sw = np.where(take, sw + w, sw)
-                sc = np.where(take[..., None], sc + w[..., None] * cq, sc)
-                sv = np.where(take, sv + (w * w) * vq, sv)
-            cur = np.where(covered[..., None], sc / sw[..., None], zero)
-            V = np.where(covered, sv / (sw * sw), zero)
-        # lightmap_finish's dilation, restated here: that helper's own text is what its mutant tests edit, so it is not shared
-        valid = covered.copy()
-        cur = np.ascontiguousarray(cur, f32)
-        for _ in range(dilate):
-            prev_valid, prev = valid.copy(), cur.copy()
-            vpad = np.pad(prev_valid, 1)
-            near = np.zeros((H, W), bool)
-            for dy, dx in _LMF_RING:
-                near |= vpad[1 + dy:1 + dy + H, 1 + dx:1 + dx + W]
-            for y, x in np.argwhere(near & ~prev_valid):         # the pass's frontier, texel by texel: the order of the sum is the contract
-                total, count = np.zeros(3, f32), 0
-                for dy, dx in _LMF_RING:
-                    qy, qx = y + dy, x + dx
-                    if 0 <= qy < H and 0 <= qx < W and prev_valid[qy, qx]:
-                        total = total + prev[qy, qx]
-                        count += 1
-                cur[y, x] = total / f32(count)
-                valid[y, x] = True
+            cur, V = _lmf_level(cur, P, N, covered, s, npow, sig_p, rch, den, V)
+        cur, valid = _lmf_dilate(cur, covered, dilate)
     return cur, np.ascontiguousarray(V, f32), valid
 
 
@@ -978,16 +910,6 @@ def check_counts_plane(counts, shape):
     if c.size and (int(c.min()) < 0 or int(c.max()) > 0xffffffff):
         raise ValueError("counts must lie in 0 .. 2^32 - 1")
     return np.ascontiguousarray(c, np.uint32)
-
-
-def _lmv_init_counts(cur, M2, counts, covered, few):
-    """lightmap_finish_var's initial variance with the texel's own n: v_c = max(0, m2_c - mean_c mean_c) / (n - 1), `few` where n < 2"""
-    f32 = np.float32
-    n = counts.astype(np.int64)
-    d = np.maximum(n - 1, 1).astype(f32)
-    v3 = np.fmax(f32(0.0), M2 - cur * cur) / d[..., None]
-    V = np.where(n >= 2, (v3[..., 0] + v3[..., 1]) + v3[..., 2], few)
-    return np.where(covered, V, f32(0.0)).astype(f32)
 
 
 def _check_index_list(index):
@@ -1022,25 +944,10 @@ def lightmap_select(image, m2, counts, normals, target_rel: float, target_abs: f
     if not 0 <= cap <= 0xffffffff:
         raise ValueError(f"capacity must be in 0 .. 2^32 - 1, got {capacity}")
     zero = f32(0.0)
-    G3 = (f32(0.25), f32(0.5), f32(0.25))
-    covered = (N[..., 0] != 0) | (N[..., 1] != 0) | (N[..., 2] != 0)
+    covered = _lm_covered(N)
     with np.errstate(all="ignore"):
-        # lightmap_finish_var's initial variance and blur, restated here: this helper's own text is what its mutant tests edit
-        n = cnt.astype(np.int64)
-        d = np.maximum(n - 1, 1).astype(f32)
-        v3 = np.fmax(zero, M2 - img * img) / d[..., None]
-        V = np.where(n >= 2, (v3[..., 0] + v3[..., 1]) + v3[..., 2], f32(np.inf))
-        V = np.where(covered, V, zero).astype(f32)
-        vb, nb = np.pad(V, 1), np.pad(N, ((1, 1), (1, 1), (0, 0)))
-        bs = np.zeros((H, W), f32)
-        bw = np.zeros((H, W), f32)
-        for dy, dx in _LMV_BLUR:
-            ys, xs = 1 + dy, 1 + dx
-            vq, nq = vb[ys:ys + H, xs:xs + W], nb[ys:ys + H, xs:xs + W]
-            btake = covered & ((nq[..., 0] != 0) | (nq[..., 1] != 0) | (nq[..., 2] != 0))
-            g = G3[dy + 1] * G3[dx + 1]
-            bs = np.where(btake, bs + g * vq, bs)
-            bw = np.where(btake, bw + g, bw)
+        V = _lmv_variance(img, M2, cnt, covered, f32(np.inf))
+        bs, bw = _lmv_blur(V, N, covered, 1)
         sd = np.where(covered, np.sqrt(bs / bw), zero).astype(f32)
         lum = (np.abs(img[..., 0]) + np.abs(img[..., 1])) + np.abs(img[..., 2])
         thr = trel * lum + tabs
@@ -1318,8 +1225,7 @@ class Context:
         """mi_lightmap_finish: the edge-aware a-trous filter and the gutter dilation of the helper lightmap_finish on the GPU, bit for
         bit.  `image` is the raw bake [H, W, 3] f32, `points` and `normals` the atlas's centre table ([H, W, 3], or lightmap_texels'
         [1, H, W, 3]).  Returns (out [H, W, 3] f32, valid [H, W] bool).  No scene is needed."""
-        P, N = np.asarray(points), np.asarray(normals)
-        img, P, N = check_finish_tables(image, P[0] if P.ndim == 4 and P.shape[0] == 1 else P, N[0] if N.ndim == 4 and N.shape[0] == 1 else N)
+        img, P, N = check_finish_tables(image, _centre_table(points), _centre_table(normals))
         H, W = img.shape[:2]
         out = np.empty((H, W, 3), np.float32)
         valid = np.empty((H, W), np.uint8)
@@ -1507,8 +1413,7 @@ class Context:
         second moments [H, W, 3] f32 (bake_lightmap_moments), `samples` its sample count, `points` and `normals` the atlas's centre table
         ([H, W, 3], or lightmap_texels' [1, H, W, 3]).  Returns (out [H, W, 3] f32, var [H, W] f32, valid [H, W] bool).  No scene is
         needed."""
-        P, N = np.asarray(points), np.asarray(normals)
-        img, P, N = check_finish_tables(image, P[0] if P.ndim == 4 and P.shape[0] == 1 else P, N[0] if N.ndim == 4 and N.shape[0] == 1 else N)
+        img, P, N = check_finish_tables(image, _centre_table(points), _centre_table(normals))
         M2 = np.ascontiguousarray(m2, np.float32)
         if M2.shape != img.shape:
             raise ValueError(f"m2 must have the image's shape {img.shape}, got {M2.shape}")
@@ -1537,8 +1442,7 @@ class Context:
                         want_error: bool = True):
         """mi_lightmap_select: the helper lightmap_select on the GPU, bit for bit.  Returns (index uint32 [min(count, capacity)], count,
         error [H, W] f32 | None).  capacity None: W * H.  No scene is needed."""
-        N = np.asarray(normals)
-        img, M2, N = check_finish_tables(image, m2, N[0] if N.ndim == 4 and N.shape[0] == 1 else N)
+        img, M2, N = check_finish_tables(image, m2, _centre_table(normals))
         cnt = check_counts_plane(counts, img.shape[:2])
         H, W = img.shape[:2]
         cap = H * W if capacity is None else int(capacity)
@@ -1606,8 +1510,7 @@ class Context:
                                    color_floor: float = 1e-6, dilate: int = 4):
         """mi_lightmap_finish_var_counts: lightmap_finish_var(samples=counts plane) on the GPU, bit for bit: the variance-guided finish of
         an adaptive bake, whose texels have counts of their own.  Returns (out, var, valid) as lightmap_finish_var does."""
-        P, N = np.asarray(points), np.asarray(normals)
-        img, P, N = check_finish_tables(image, P[0] if P.ndim == 4 and P.shape[0] == 1 else P, N[0] if N.ndim == 4 and N.shape[0] == 1 else N)
+        img, P, N = check_finish_tables(image, _centre_table(points), _centre_table(normals))
         M2 = np.ascontiguousarray(m2, np.float32)
         if M2.shape != img.shape:
             raise ValueError(f"m2 must have the image's shape {img.shape}, got {M2.shape}")

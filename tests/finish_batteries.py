@@ -9,11 +9,12 @@ Colours are BASE = (1, 0.5, 2) times a power of two wherever a test asks for unc
 of the weighted mean (sum(w c) == c sum(w) exactly), so a texel whose accepted taps all carry its own colour keeps its bits, and any
 leak from a texel of another colour shows as a changed bit."""
 import gzip
+import inspect
 import os
 
 import numpy as np
 
-from cs397raytracingsp22_amd import lightmap_texels, objload
+from cs397raytracingsp22_amd import lightmap_texels, objload, tracing
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 INF = float("inf")
@@ -199,3 +200,35 @@ def all_batteries(cube_levels=3, cube_dilate=0):
 
 def bits(a):
     return np.ascontiguousarray(a, np.float32).view(np.uint32)
+
+
+# ---------------------------------------------------------------- mutants of the definitions
+def mutant(helper, blocks, old, new):
+    """`helper` (a public definition of tracing.py) made again from its own source and that of `blocks`, the building blocks it is
+    composed of, with the text `old`, which must occur exactly once in all of it, replaced by `new`.  Everything is executed in one scope,
+    so the copy calls the copies of its blocks: a mutant of a shared block is a mutant of every helper built on it."""
+    src = "\n\n".join(inspect.getsource(f) for f in tuple(blocks) + (helper,))
+    assert src.count(old) == 1, old
+    scope = dict(vars(tracing))
+    exec(compile(src.replace(old, new), f"<mutant of {helper.__name__}>", "exec"), scope)
+    return scope[helper.__name__]
+
+
+# the blocks of lightmap_finish and lightmap_finish_sh, of lightmap_finish_var, of lightmap_select
+FINISH_BLOCKS = (tracing._lm_covered, tracing._lmf_level, tracing._lmf_dilate, tracing._check_finish_passes, tracing._lmf_finish)
+VAR_BLOCKS = (tracing._lm_covered, tracing._lmv_variance, tracing._lmv_blur, tracing._lmf_level, tracing._lmf_dilate, tracing._check_finish_passes)
+SELECT_BLOCKS = (tracing._lm_covered, tracing._lmv_variance, tracing._lmv_blur)
+
+# one-token mutants of the blocks that lightmap_finish, lightmap_finish_sh and lightmap_finish_var share: each form's batteries notice each
+LEVEL_AND_DILATION_MUTANTS = {
+    "tap order reversed": ("for dy, dx in _LMF_TAPS:", "for dy, dx in _LMF_TAPS[::-1]:"),
+    "H5's 3/8 and 1/4 swapped": ("f32(0.25), f32(0.375), f32(0.25)", "f32(0.375), f32(0.25), f32(0.375)"),
+    "reach test exclusive": ("(d2 <= rr", "(d2 < rr"),
+    "plane distance without fabsf": ("dpl = np.abs(", "dpl = ("),
+    "dilation reads the in-pass state": ("valid.copy(), cur.copy()", "valid, cur"),
+}
+# of the two that lightmap_finish_var (constant and per-texel counts) and lightmap_select share
+VARIANCE_MUTANTS = {
+    "n for n - 1": ("d = np.maximum(n - 1, 1).astype(f32)", "d = np.maximum(n, 1).astype(f32)"),
+    "blur includes empty neighbours": ("btake = covered & _lm_covered(nq)", "btake = covered"),
+}

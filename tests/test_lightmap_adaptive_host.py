@@ -10,6 +10,7 @@ import pytest
 from cs397raytracingsp22_amd import abi, lightmap_finish_var, lightmap_gather, lightmap_merge, lightmap_select, tracing
 
 import adaptive_batteries as ab
+import finish_batteries as fb
 import variance_batteries as vb
 from adaptive_batteries import INF, bits
 
@@ -239,6 +240,21 @@ def test_finish_with_counts_uses_the_texels_own_count():
     assert bits(lightmap_finish_var(img, m2, other, P, N, levels=0, dilate=0)[1][y, x]) != bits(var[y, x])
 
 
+def test_finish_with_counts_notices_n_for_n_minus_one():
+    """The initial variance is one block for the constant and the per-texel n: its mutant shows in the counts form on every battery
+    whose variance is not zero (lightmap_select's batteries notice it below, the constant form's in test_lightmap_variance_host.py)"""
+    wrong = fb.mutant(lightmap_finish_var, fb.VAR_BLOCKS, *fb.VARIANCE_MUTANTS["n for n - 1"])
+    noticed = []
+    for b in vb.all_batteries(3, 2):
+        _, img, m2, S, P, N, params = b
+        cnt = np.full(img.shape[:2], S, np.uint32)
+        x, y = lightmap_finish_var(img, m2, cnt, P, N, **params), wrong(img, m2, cnt, P, N, **params)
+        if not all(np.array_equal(bits(p), bits(q)) for p, q in zip(x[:2], y[:2])):
+            noticed.append(b[0])
+    print(f"noticed by {noticed}")
+    assert len(noticed) >= 8
+
+
 # ---------------------------------------------------------------- refusals of the helpers
 def test_bad_arguments_are_refused():
     _, img, m2, cnt, P, N, trel, tabs = ab.ragged_battery(31, 33)
@@ -274,12 +290,10 @@ def test_bad_arguments_are_refused():
 
 # ---------------------------------------------------------------- mutants
 SELECT_MUTANTS = {
-    "n for n - 1": ("d = np.maximum(n - 1, 1).astype(f32)", "d = np.maximum(n, 1).astype(f32)"),
+    **fb.VARIANCE_MUTANTS,
     ">= for >": ("selected = covered & (sd > thr)", "selected = covered & (sd >= thr)"),
-    "blur includes empty neighbours": ("btake = covered & ((nq[..., 0] != 0) | (nq[..., 1] != 0) | (nq[..., 2] != 0))", "btake = covered"),
     "no blur": ("sd = np.where(covered, np.sqrt(bs / bw), zero)", "sd = np.where(covered, np.sqrt(V), zero)"),
-    "a texel without samples counts as converged": ("V = np.where(n >= 2, (v3[..., 0] + v3[..., 1]) + v3[..., 2], f32(np.inf))",
-                                                    "V = np.where(n >= 2, (v3[..., 0] + v3[..., 1]) + v3[..., 2], f32(0.0))"),
+    "a texel without samples counts as converged": ("_lmv_variance(img, M2, cnt, covered, f32(np.inf))", "_lmv_variance(img, M2, cnt, covered, f32(0.0))"),
 }
 MERGE_MUTANTS = {
     "weights swapped": ("plane[t] = (n0 * a + Sf * b) / tot", "plane[t] = (Sf * a + n0 * b) / tot"),
@@ -289,11 +303,7 @@ MERGE_MUTANTS = {
 
 
 def mutant(fn, old, new):
-    src = inspect.getsource(fn)
-    assert src.count(old) == 1, old
-    scope = dict(vars(tracing))
-    exec(compile(src.replace(old, new), f"<mutant of {fn.__name__}>", "exec"), scope)
-    return scope[fn.__name__]
+    return fb.mutant(fn, fb.SELECT_BLOCKS if fn is lightmap_select else (), old, new)
 
 
 def same_selection(x, y):
@@ -463,7 +473,6 @@ def test_adaptive_bake_refusals_without_a_device():
 
 def test_mirrors_name_the_new_calls():
     import os
-    import finish_batteries as fb
     root = fb.ROOT
     hpp = open(os.path.join(root, "cs397raytracingsp22_amd", "host", "tracing.hpp")).read()
     assert "bake_lightmap_adaptive(" in hpp and "finish_lightmap_var_counts(" in hpp

@@ -7,7 +7,8 @@ import pytest
 from cs397raytracingsp22_amd import (Camera, Context, Scene, abi, check_finish_sh_tables, check_sh_eval, lightmap_finish, lightmap_finish_sh,
                                      lightmap_sh_eval, probe_volume_sample, sh9_basis, sh9_irradiance)
 
-from finish_batteries import CUBE_SIZES, INF, bits, cube_noisy, cube_paint, cube_table, islands_battery, two_halves
+import finish_batteries as fb
+from finish_batteries import CUBE_SIZES, INF, bits, cube_noisy, cube_paint, cube_table, islands_battery, plane_battery, reach_equal_battery, two_halves
 
 # nine distinct per-plane factors, none a power of two times another: a channel mix-up changes bits
 PLANE_SCALE = np.float32([1.0, -0.7, 0.3, 1.9, -0.11, 0.57, -2.3, 0.013, 5.1])
@@ -30,8 +31,8 @@ def sh_batteries():
     img, P, N = two_halves(gap=(0.0, 0.0, 1.0))
     out.append(("two-halves-plane", sh_records(img), P, N, dict(levels=2, normal_power_log2=1, sigma_plane=0.05, reach=1.5, sigma_color=2.0,
                                                                  dilate=1)))
-    name, img, P, N, params = islands_battery()
-    out.append((name, sh_records(img), P, N, params))
+    for name, img, P, N, params in (reach_equal_battery(), plane_battery(0.05), islands_battery()):
+        out.append((name, sh_records(img), P, N, params))
     return out
 
 
@@ -86,6 +87,26 @@ def test_finish_with_no_pass_is_the_masked_copy():
     out, valid = lightmap_finish_sh(sh, P, N, levels=0, dilate=0)
     assert np.array_equal(valid, covered)
     assert np.array_equal(bits(out)[covered], bits(sh)[covered]) and not bits(out)[~covered].any()
+
+
+# ---------------------------------------------------------------- mutants of the blocks shared with lightmap_finish
+def same_bits(x, y):
+    return np.array_equal(bits(x[0]), bits(y[0])) and np.array_equal(x[1], y[1])
+
+
+def test_unmutated_copy_is_the_helper():
+    copy = fb.mutant(lightmap_finish_sh, fb.FINISH_BLOCKS, "for dy, dx in _LMF_TAPS:", "for dy, dx in _LMF_TAPS:")
+    for _, sh, P, N, params in BATTERIES:
+        assert same_bits(copy(sh, P, N, **params), lightmap_finish_sh(sh, P, N, **params))
+
+
+@pytest.mark.parametrize("name", list(fb.LEVEL_AND_DILATION_MUTANTS))
+def test_batteries_notice(name):
+    """A slip in the level or the dilation that lightmap_finish's batteries notice does not pass the 27-channel form's either"""
+    wrong = fb.mutant(lightmap_finish_sh, fb.FINISH_BLOCKS, *fb.LEVEL_AND_DILATION_MUTANTS[name])
+    noticed = [b[0] for b in BATTERIES if not same_bits(wrong(*b[1:4], **b[4]), lightmap_finish_sh(*b[1:4], **b[4]))]
+    print(f"{name}: noticed by {noticed}")
+    assert noticed
 
 
 # ---------------------------------------------------------------- evaluation

@@ -1,7 +1,6 @@
 """lightmap_finish_var, the host helper that defines mi_lightmap_finish_var: what it must do with the batteries of variance_batteries.py,
 that those batteries notice one-token mutants of it, and the refusals of the five new entry points that need no device.  No GPU."""
 import ctypes as C
-import inspect
 
 import numpy as np
 import pytest
@@ -150,23 +149,20 @@ def test_bad_arguments_are_refused():
 
 # ---------------------------------------------------------------- mutants
 MUTANTS = {
-    "S for S - 1": ("/ f32(S - 1)", "/ f32(S)"),
+    "S for S - 1": fb.VARIANCE_MUTANTS["n for n - 1"],
     "w for w * w in sv": ("sv + (w * w) * vq", "sv + (w) * vq"),
     "sw for sw * sw": ("sv / (sw * sw)", "sv / (sw)"),
-    "blur taken at step s": ("            b = 1\n", "            b = s\n"),
-    "den divided by s": ("den = sig_c0 * sd + floor", "den = (sig_c0 * sd + floor) / fs"),
-    "blur includes empty neighbours": ("btake = covered & ((nq[..., 0] != 0) | (nq[..., 1] != 0) | (nq[..., 2] != 0))", "btake = covered"),
+    "blur taken at step s": ("_lmv_blur(V, N, covered, 1) ", "_lmv_blur(V, N, covered, s) "),
+    "den divided by s": ("den = sig_c0 * sd + floor", "den = (sig_c0 * sd + floor) / f32(s)"),
+    "blur includes empty neighbours": fb.VARIANCE_MUTANTS["blur includes empty neighbours"],
     "variance read at p, not at q": ("vq = vpad[ys:ys + H, xs:xs + W]", "vq = V"),
     "blur's G3 flattened": ("G3 = (f32(0.25), f32(0.5), f32(0.25))", "G3 = (f32(0.25), f32(0.25), f32(0.25))"),
+    **fb.LEVEL_AND_DILATION_MUTANTS,
 }
 
 
 def mutant(old, new):
-    src = inspect.getsource(tracing.lightmap_finish_var)
-    assert src.count(old) == 1, old
-    scope = dict(vars(tracing))
-    exec(compile(src.replace(old, new), "<mutant of lightmap_finish_var>", "exec"), scope)
-    return scope["lightmap_finish_var"]
+    return fb.mutant(lightmap_finish_var, fb.VAR_BLOCKS, old, new)
 
 
 def same_bits(x, y):
@@ -174,7 +170,7 @@ def same_bits(x, y):
 
 
 def test_unmutated_copy_is_the_helper():
-    copy = mutant("            b = 1\n", "            b = 1\n")
+    copy = mutant("den = sig_c0 * sd + floor", "den = sig_c0 * sd + floor")
     for b in vb.all_batteries(3, 2):
         assert same_bits(run(b, copy), reference(b)), b[0]
 

@@ -128,4 +128,5 @@ def edge_batteries():
 def all_batteries(cube_levels=3, cube_dilate=0):
     """Every battery the mutants and the kernels are held against (the noise battery once: seed 7)"""
     return (cube_batteries(cube_levels, cube_dilate) + colour_off_batteries() +
-            [zero_variance_battery(), propagation_battery(), noise_battery(NOISE_SEEDS[0]), ragged_battery(33, 33)] + edge_batteries())
+            [zero_variance_battery(), propagation_battery(), noise_battery(NOISE_SEEDS[0]), ragged_battery(33, 33),
+             from_finish_battery(fb.reach_equal_battery())] + edge_batteries())
