@@ -24,6 +24,7 @@ from .tracing import check_counts_plane, lightmap_gather, lightmap_merge, lightm
 from .tracing import check_probe_table, probe_grid, sh9_basis, sh9_irradiance  # noqa: F401
 from .tracing import ProbeVolume, check_probe_volume, check_volume_points, probe_volume_sample  # noqa: F401
 from .tracing import check_finish_sh_tables, check_sh_eval, lightmap_finish_sh, lightmap_sh_eval  # noqa: F401
+from .tracing import check_lightmap_lookup, lightmap_sample, lightmap_sh_sample, shade_hits_baked  # noqa: F401
 
 __all__ = [
     "abi", "Camera", "CameraProjectionMode", "ShadingMode", "Scene", "Context", "MultiContext", "compact_size",

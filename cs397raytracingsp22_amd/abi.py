@@ -30,6 +30,7 @@ MI_OPT_NO_FINAL_CULL = 16
 MI_HEMI_WORLD_RADIUS = 1   # mi_hemisphere_occlusion flags: t_max is a world-space radius
 MI_LM_JITTER = 1           # mi_lightmap_texels / mi_bake_lightmap flags: one jittered position per row instead of the texel centre
 MI_PV_NORMAL_WEIGHT = 1    # mi_probe_volume.flags: weight the eight corners by how far they lie in front of the surface
+MI_LS_NEAREST = 1          # mi_lightmap_sample / mi_lightmap_sh_sample flags: the reference's nearest-texel addressing, no interpolation
 
 f3 = C.c_float * 3
 f16 = C.c_float * 16
@@ -140,6 +141,7 @@ EXPORTS = [
     "mi_probe_volume_sample", "mi_probe_volume_sample_device",
     "mi_render_points_sh", "mi_render_points_sh_device", "mi_bake_lightmap_sh",
     "mi_lightmap_finish_sh", "mi_lightmap_finish_sh_device", "mi_lightmap_sh_eval", "mi_lightmap_sh_eval_device",
+    "mi_lightmap_sample", "mi_lightmap_sample_device", "mi_lightmap_sh_sample", "mi_lightmap_sh_sample_device",
     "mi_multi_create", "mi_multi_create_loopback", "mi_multi_destroy", "mi_multi_device_count", "mi_multi_context", "mi_multi_scene_upload", "mi_multi_reserve", "mi_multi_render",
 ]
 
@@ -314,6 +316,14 @@ def load() -> C.CDLL:
     lib.mi_lightmap_sh_eval_device.argtypes = lib.mi_lightmap_sh_eval.argtypes + [vp]
     for name in ("render_points_sh", "render_points_sh_device", "bake_lightmap_sh", "lightmap_finish_sh", "lightmap_finish_sh_device",
                  "lightmap_sh_eval", "lightmap_sh_eval_device"):
+        getattr(lib, "mi_" + name).restype = C.c_int
+    # lightmap lookup (added within ABI 5): width, height, channels, image, valid, n, uv, flags, out, out_weight (, stream); the fused SH
+    # form: width, height, sh, valid, n, uv, normals, flags, out_irradiance, out_weight (, stream)
+    lib.mi_lightmap_sample.argtypes = [vp, u32, u32, u32, vp, vp, u32, vp, u32, vp, vp]
+    lib.mi_lightmap_sample_device.argtypes = lib.mi_lightmap_sample.argtypes + [vp]
+    lib.mi_lightmap_sh_sample.argtypes = [vp, u32, u32, vp, vp, u32, vp, vp, u32, vp, vp]
+    lib.mi_lightmap_sh_sample_device.argtypes = lib.mi_lightmap_sh_sample.argtypes + [vp]
+    for name in ("lightmap_sample", "lightmap_sample_device", "lightmap_sh_sample", "lightmap_sh_sample_device"):
         getattr(lib, "mi_" + name).restype = C.c_int
     lib.mi_multi_create.argtypes = [C.c_int, C.POINTER(C.c_int), C.POINTER(vp)]
     lib.mi_multi_create.restype = C.c_int

@@ -72,6 +72,7 @@ hipError_t launch_lma_merge(const LmaListArgs& a, hipStream_t stream);
 hipError_t launch_wf_reduce_psh(const WfArgs& a, bool first_batch, bool last_batch, hipStream_t stream);
 hipError_t launch_lsh_atrous(const LmfArgs& a, hipStream_t stream);
 hipError_t launch_lsh_eval(const LshEvalArgs& a, hipStream_t stream);
+hipError_t launch_lml_sample(const LmlArgs& a, uint32_t channels, hipStream_t stream);
 }  // namespace pt
 
 using namespace pt;
@@ -1701,6 +1702,93 @@ extern "C" int mi_lightmap_sh_eval(mi_ctx* c, uint32_t n, const float* sh, const
     return staged(c, cols, [&](void* const* d) -> int {
         return lightmap_sh_eval_device(c, n, (const float*)d[0], (const float*)d[1], (float*)d[2], c->stream);
     });
+}
+
+// ------------------------------------------------------------------ lightmap lookup (a finished lightmap read at uv points)
+// tracing.py lightmap_sample and lightmap_sh_sample as one kernel each (lml_sample<3>, lml_sample<27>, lml_sh_sample): one lane per point,
+// no scratch, no scene.  One argument record serves both calls: channels == 0 is the fused SH form, which reads 27 floats per texel and
+// the normals and writes three per point.
+struct LookupArgs {
+    uint32_t width, height, channels; const float* image; const uint8_t* valid; uint32_t n; const float* uv; const float* normals;
+    uint32_t flags; float* out; float* out_weight;
+};
+
+// Checked before the context, nothing is launched: the pointers, the size, the channel count, the flags
+static int check_lookup_args(const char* who, const LookupArgs& l) {
+    const bool sh = l.channels == 0;
+    if (!l.image || !l.uv || !l.out || (sh && !l.normals))
+        return fail(MI_ERR_INVALID, sh ? "%s: sh, uv, normals and out_irradiance are required" : "%s: image, uv and out are required", who);
+    if (l.width == 0 || l.width > 32768u || l.height == 0 || l.height > 32768u)
+        return fail(MI_ERR_INVALID, "%s: width %u / height %u is not in 1 .. 32768", who, l.width, l.height);
+    if (!sh && l.channels != 3 && l.channels != (uint32_t)kShFloats) return fail(MI_ERR_INVALID, "%s: channels %u is not 3 or 27", who, l.channels);
+    if (l.flags & ~MI_LS_NEAREST) return fail(MI_ERR_INVALID, "%s: unknown flag bits 0x%x", who, l.flags & ~MI_LS_NEAREST);
+    return MI_OK;
+}
+
+static int lookup_device(mi_ctx* c, const LookupArgs& l, hipStream_t stream) {
+    LmlArgs a{};
+    a.image = l.image; a.valid = l.valid; a.uv = l.uv; a.normals = l.normals; a.out = l.out; a.out_weight = l.out_weight;
+    a.width = l.width; a.height = l.height; a.n = l.n; a.nearest = l.flags & MI_LS_NEAREST;
+    return timed(c, stream, [&]() -> int {
+        HIP_TRY(launch_lml_sample(a, l.channels, stream));
+        return MI_OK;
+    });
+}
+
+// The device-pointer entry: the arguments, the context, the overlaps (the kernels never work in place); n == 0 launches nothing
+static int lookup_entry_device(const char* who, mi_ctx* c, const LookupArgs& l, void* stream) {
+    MI_TRY(check_lookup_args(who, l));
+    if (!c) return fail(MI_ERR_INVALID, "ctx is NULL");
+    const size_t texels = (size_t)l.width * l.height, in_c = l.channels ? l.channels : (uint32_t)kShFloats, out_c = l.channels ? l.channels : 3u;
+    MI_TRY(check_no_overlap(who, { { l.out, (size_t)l.n * out_c * sizeof(float), l.channels ? "out" : "out_irradiance" },
+                                   { l.out_weight, (size_t)l.n * sizeof(float), "out_weight" } },
+                            { { l.image, texels * in_c * sizeof(float) }, { l.valid, texels }, { l.uv, (size_t)l.n * 2 * sizeof(float) },
+                              { l.normals, (size_t)l.n * 3 * sizeof(float) } }));
+    if (l.n == 0) return MI_OK;
+    HIP_TRY(hipSetDevice(c->device));
+    return lookup_device(c, l, (hipStream_t)stream);
+}
+
+// The host-pointer entry: the arguments, then the context, then the call staged
+static int lookup_entry_host(const char* who, mi_ctx* c, const LookupArgs& l) {
+    MI_TRY(check_lookup_args(who, l));
+    if (!c) return fail(MI_ERR_INVALID, "ctx is NULL");
+    if (l.n == 0) return MI_OK;                // before any device call
+    const size_t texels = (size_t)l.width * l.height, in_c = l.channels ? l.channels : (uint32_t)kShFloats, out_c = l.channels ? l.channels : 3u;
+    enum { kImage, kValid, kUv, kNormals, kOut, kWeight };
+    const StageColumn cols[] = { { l.image, texels * in_c * sizeof(float), Stage::kIn }, { l.valid, texels, Stage::kIn },
+                                 { l.uv, (size_t)l.n * 2 * sizeof(float), Stage::kIn }, { l.normals, (size_t)l.n * 3 * sizeof(float), Stage::kIn },
+                                 { l.out, (size_t)l.n * out_c * sizeof(float), Stage::kOut }, { l.out_weight, (size_t)l.n * sizeof(float), Stage::kOut } };
+    return staged(c, cols, [&](void* const* d) -> int {
+        LookupArgs dl = l;
+        dl.image = (const float*)d[kImage]; dl.valid = (const uint8_t*)d[kValid]; dl.uv = (const float*)d[kUv];
+        dl.normals = (const float*)d[kNormals]; dl.out = (float*)d[kOut]; dl.out_weight = (float*)d[kWeight];
+        return lookup_device(c, dl, c->stream);
+    });
+}
+
+extern "C" int mi_lightmap_sample_device(mi_ctx* c, uint32_t width, uint32_t height, uint32_t channels, const float* image, const uint8_t* valid,
+                                         uint32_t n, const float* uv, uint32_t flags, float* out, float* out_weight, void* stream) {
+    if (channels == 0) return fail(MI_ERR_INVALID, "mi_lightmap_sample_device: channels 0 is not 3 or 27");
+    return lookup_entry_device("mi_lightmap_sample_device", c, { width, height, channels, image, valid, n, uv, nullptr, flags, out, out_weight }, stream);
+}
+
+extern "C" int mi_lightmap_sample(mi_ctx* c, uint32_t width, uint32_t height, uint32_t channels, const float* image, const uint8_t* valid,
+                                  uint32_t n, const float* uv, uint32_t flags, float* out, float* out_weight) {
+    if (channels == 0) return fail(MI_ERR_INVALID, "mi_lightmap_sample: channels 0 is not 3 or 27");
+    return lookup_entry_host("mi_lightmap_sample", c, { width, height, channels, image, valid, n, uv, nullptr, flags, out, out_weight });
+}
+
+extern "C" int mi_lightmap_sh_sample_device(mi_ctx* c, uint32_t width, uint32_t height, const float* sh, const uint8_t* valid, uint32_t n,
+                                            const float* uv, const float* normals, uint32_t flags, float* out_irradiance, float* out_weight,
+                                            void* stream) {
+    return lookup_entry_device("mi_lightmap_sh_sample_device", c, { width, height, 0, sh, valid, n, uv, normals, flags, out_irradiance, out_weight },
+                               stream);
+}
+
+extern "C" int mi_lightmap_sh_sample(mi_ctx* c, uint32_t width, uint32_t height, const float* sh, const uint8_t* valid, uint32_t n,
+                                     const float* uv, const float* normals, uint32_t flags, float* out_irradiance, float* out_weight) {
+    return lookup_entry_host("mi_lightmap_sh_sample", c, { width, height, 0, sh, valid, n, uv, normals, flags, out_irradiance, out_weight });
 }
 
 // ------------------------------------------------------------------ variance-guided lightmap finishing

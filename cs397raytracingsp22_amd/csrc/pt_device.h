@@ -455,6 +455,19 @@ struct LshEvalArgs {
     uint32_t     n;
 };
 
+// ---- lightmap lookup (mi_lightmap_sample, mi_lightmap_sh_sample; pt_kernels.hip "lml_*") ----
+// tracing.py lightmap_sample (lml_sample<3>, lml_sample<27>) and lightmap_sh_sample (lml_sh_sample): one lane per uv point
+struct LmlArgs {
+    const float*   image;            // [H][W][C]: C = 3 or 27 (lml_sample<C>), 27 (lml_sh_sample)
+    const uint8_t* valid;            // [H][W] or nullptr = all valid: 0 = the texel takes no part and is not read
+    const float*   uv;               // [n][2]
+    const float*   normals;          // [n][3] (lml_sh_sample): all-zero = +0.0 and weight 0
+    float*         out;              // [n][C] (lml_sample<C>), [n][3] (lml_sh_sample)
+    float*         out_weight;       // [n] or nullptr
+    uint32_t width, height, n;
+    uint32_t nearest;                // MI_LS_NEAREST
+};
+
 // ---- variance-guided lightmap finishing (mi_lightmap_finish_var; pt_kernels.hip "lmv_*") ----
 // One pass of tracing.py lightmap_finish_var: lmv_init (the variance of the mean per texel from the bake's mean and second moments),
 // lmv_blur (the colour weight's denominator per texel from the 3 x 3 blur of the variance) or lmv_atrous (one filter level of the image

@@ -4458,6 +4458,131 @@ __global__ __launch_bounds__(kBlock) void lsh_eval(const LshEvalArgs a) {
     for (int c = 0; c < 3; c++) a.out_irradiance[3 * (size_t)i + c] = E[c];
 }
 
+// ---------------------------------------------------------------- lightmap lookup (mi_lightmap_sample, mi_lightmap_sh_sample)
+// tracing.py lightmap_sample and lightmap_sh_sample on the device: a finished lightmap read at uv points, bilinear over the valid texels
+// or (MI_LS_NEAREST) the reference's own addressing (texture.rs:28-29).  One lane per point, no LDS, no atomics, nothing summed across
+// lanes; pure f32, the helpers' operations in the helpers' order (no fused multiply-add: the pragma above).  Every address is made from
+// indices clamped to the image, whatever the uv, the normals and the texels hold; a tap that takes no part is not read.  A 27-float
+// record is 108 bytes, so a record is only 4-byte aligned: the taps are read as lsh_atrous reads its records, float by float.
+
+// One axis of the bilinear form: pv_sample's index expressions.  fmaxf sends a NaN to 0, so the indices stay in range for any t.
+__device__ __forceinline__ void lml_axis(float t, int n, int (&i)[2], float (&w)[2]) {
+    float g = t * (float)n - 0.5f;
+    g = fminf(fmaxf(g, 0.0f), (float)(n - 1));
+    const int i0 = max(min((int)floorf(g), max(n - 2, 0)), 0);
+    const float f = g - (float)i0;
+    i[0] = i0; i[1] = min(i0 + 1, n - 1);
+    w[0] = 1.0f - f; w[1] = f;
+}
+// One axis of the nearest form: lml_unit is the reference's clamp (a NaN leaves it as 0, so none reaches the conversion), lml_texel the
+// texel of the clamped coordinate, or of its mirror, times n; `nan`: the coordinate was a NaN, which Rust's saturating cast sends to 0
+__device__ __forceinline__ float lml_unit(float t) { return fminf(fmaxf(t, 0.0f), 0.999f); }
+__device__ __forceinline__ int lml_texel(float s, int n, bool nan) { return nan ? 0 : max(min((int)(s * (float)n), n - 1), 0); }
+__device__ __forceinline__ size_t lml_nearest(const LmlArgs& a, float u, float v) {
+    const int x = lml_texel(lml_unit(u), (int)a.width, u != u), y = lml_texel(1.0f - lml_unit(v), (int)a.height, v != v);
+    return (size_t)y * a.width + (size_t)x;
+}
+
+// lightmap_sample: C floats per texel (3: an image, 27: SH records), C + 1 accumulators
+template <int C> __global__ __launch_bounds__(kBlock) void lml_sample(const LmlArgs a) {
+    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= a.n) return;
+    const float u = a.uv[2 * (size_t)i], v = a.uv[2 * (size_t)i + 1];
+    float acc[C], sw = 0.0f;
+#pragma unroll
+    for (int k = 0; k < C; k++) acc[k] = 0.0f;
+    if (a.nearest) {
+        const size_t q = lml_nearest(a, u, v);
+        if (!a.valid || a.valid[q] != 0) {
+            const float* t = a.image + q * C;
+#pragma unroll
+            for (int k = 0; k < C; k++) acc[k] = t[k];             // as it stands: a -0.0 stays one
+            sw = 1.0f;
+        }
+    } else {
+        int ix[2], iy[2];
+        float wx[2], wy[2];
+        lml_axis(u, (int)a.width, ix, wx);
+        lml_axis(1.0f - v, (int)a.height, iy, wy);
+#pragma unroll
+        for (int dy = 0; dy < 2; dy++)
+#pragma unroll
+            for (int dx = 0; dx < 2; dx++) {
+                const float w = wx[dx] * wy[dy];
+                const size_t q = (size_t)iy[dy] * a.width + (size_t)ix[dx];
+                if (!(w > 0.0f) || (a.valid && a.valid[q] == 0)) continue;
+                const float* t = a.image + q * C;
+#pragma unroll
+                for (int k = 0; k < C; k++) acc[k] = acc[k] + w * t[k];
+                sw = sw + w;
+            }
+        if (sw > 0.0f) {
+#pragma unroll
+            for (int k = 0; k < C; k++) acc[k] = acc[k] / sw;
+        }
+    }
+    float* o = a.out + (size_t)i * C;
+#pragma unroll
+    for (int k = 0; k < C; k++) o[k] = acc[k];
+    if (a.out_weight) a.out_weight[i] = sw;
+}
+
+// lightmap_sh_sample, the fused form: every tap's record is turned into its irradiance e at the point's normal (lsh_eval's arithmetic)
+// and the three e are what is interpolated — pv_sample's order with four taps: 3 + 1 accumulators, never an interpolated record.
+__global__ __launch_bounds__(kBlock) void lml_sh_sample(const LmlArgs a) {
+    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= a.n) return;
+    const float u = a.uv[2 * (size_t)i], v = a.uv[2 * (size_t)i + 1];
+    const float nx = a.normals[3 * (size_t)i], ny = a.normals[3 * (size_t)i + 1], nz = a.normals[3 * (size_t)i + 2];
+    float E[3] = { 0.0f, 0.0f, 0.0f }, sw = 0.0f;
+    if (lmf_covered(nx, ny, nz)) {                             // an all-zero normal: +0 and weight 0, as pv_sample
+        const float K1 = (float)1.0233267079464885, K2 = (float)0.8580855308097834;
+        const float K[9] = { (float)0.886226925452758, K1, K1, K1, K2, K2, (float)0.24770795610037571, K2, (float)0.4290427654048917 };
+        const float l = sqrtf((nx * nx + ny * ny) + nz * nz);
+        const float x = nx / l, y = ny / l, z = nz / l;
+        const float b[9] = { 1.0f, y, z, x, x * y, y * z, 3.0f * (z * z) - 1.0f, x * z, x * x - y * y };
+        auto eval = [&](size_t q, float (&e)[3]) {
+            const float* sh = a.image + q * kShFloats;
+#pragma unroll
+            for (int c = 0; c < 3; c++) {
+                float s = b[0] * (sh[c] * K[0]);
+#pragma unroll
+                for (int k = 1; k < 9; k++) s = s + b[k] * (sh[3 * k + c] * K[k]);
+                e[c] = s;
+            }
+        };
+        if (a.nearest) {
+            const size_t q = lml_nearest(a, u, v);
+            if (!a.valid || a.valid[q] != 0) { eval(q, E); sw = 1.0f; }
+        } else {
+            int ix[2], iy[2];
+            float wx[2], wy[2];
+            lml_axis(u, (int)a.width, ix, wx);
+            lml_axis(1.0f - v, (int)a.height, iy, wy);
+#pragma unroll
+            for (int dy = 0; dy < 2; dy++)
+#pragma unroll
+                for (int dx = 0; dx < 2; dx++) {
+                    const float w = wx[dx] * wy[dy];
+                    const size_t q = (size_t)iy[dy] * a.width + (size_t)ix[dx];
+                    if (!(w > 0.0f) || (a.valid && a.valid[q] == 0)) continue;
+                    float e[3];
+                    eval(q, e);
+#pragma unroll
+                    for (int c = 0; c < 3; c++) E[c] = E[c] + w * e[c];
+                    sw = sw + w;
+                }
+            if (sw > 0.0f) {
+#pragma unroll
+                for (int c = 0; c < 3; c++) E[c] = E[c] / sw;
+            }
+        }
+    }
+#pragma unroll
+    for (int c = 0; c < 3; c++) a.out[3 * (size_t)i + c] = E[c];
+    if (a.out_weight) a.out_weight[i] = sw;
+}
+
 // ---------------------------------------------------------------- launch wrappers
 // One lane per item (a texel, a probe, a point, a list entry): ceil(n / kBlock) blocks of `kernel`, which tests its index against n itself
 template <class Kernel, class... Args> static hipError_t launch_per_item(Kernel kernel, size_t n, hipStream_t stream, const Args&... args) {
@@ -4481,6 +4606,13 @@ hipError_t launch_lsh_atrous(const LmfArgs& a, hipStream_t stream) {
     return hipGetLastError();
 }
 hipError_t launch_lsh_eval(const LshEvalArgs& a, hipStream_t stream) { return launch_per_item(lsh_eval, a.n, stream, a); }
+// lightmap lookup: `channels` floats per texel out (3 or 27), or 0: the fused SH form
+hipError_t launch_lml_sample(const LmlArgs& a, uint32_t channels, hipStream_t stream) {
+    if (channels == 0) return launch_per_item(lml_sh_sample, a.n, stream, a);
+    if (channels == 3) return launch_per_item(lml_sample<3>, a.n, stream, a);
+    if (channels == kShFloats) return launch_per_item(lml_sample<kShFloats>, a.n, stream, a);
+    return hipErrorInvalidValue;
+}
 // The plain form's level.  lmf_atrous stages through LDS when `lds`; a window above 64 KB needs the opt-in, which
 // belongs to the function on the current device, so the calling context keeps its record (as launch_walker's big_lds_enabled).
 hipError_t launch_lmf_atrous(const LmfArgs& a, bool lds, bool* big_lds_enabled, hipStream_t stream) {

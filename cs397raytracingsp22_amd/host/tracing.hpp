@@ -436,6 +436,51 @@ struct Scene : Intersectable {                         // tracing.rs:213-218; `i
         return out;
     }
 
+    // Read a finished lightmap at uv points through mi_lightmap_sample: image is [H][W][channels], channels 3 or 27, uv [n][2] (intersect's
+    // tex_coords as they stand: row 0 is v = 1), `valid` empty (every texel takes part) or finish_lightmap's mask.  Bilinear over the valid
+    // texels, or with `nearest` (MI_LS_NEAREST) the texel Texture::sample addresses.  Returns [n][channels]; `weight` takes the weight sum
+    // per point (0: nothing to read).  Needs no scene: a static member.
+    static std::vector<float> sample_lightmap(const std::vector<float>& image, const std::vector<uint8_t>& valid, uint32_t width, uint32_t height,
+                                              uint32_t channels, const std::vector<float>& uv, bool nearest = false, int device = 0,
+                                              std::vector<float>* weight = nullptr) {
+        const size_t texels = (size_t)width * height, n = uv.size() / 2;
+        if (image.size() != texels * channels || (!valid.empty() && valid.size() != texels) || uv.size() != n * 2)
+            throw std::runtime_error("mi_rt: image must be [H][W][channels], valid empty or [H][W] and uv [n][2]");
+        std::vector<float> out(n * channels);
+        if (weight) weight->resize(n);
+        if (n == 0) return out;                              // (an empty vector has no address to pass)
+        mi_ctx* ctx = nullptr;
+        mi_check(mi_ctx_create(device, &ctx));
+        const int rc = mi_lightmap_sample(ctx, width, height, channels, image.data(), valid.empty() ? nullptr : valid.data(), (uint32_t)n, uv.data(),
+                                          nearest ? MI_LS_NEAREST : 0u, out.data(), weight ? weight->data() : nullptr);
+        const std::string err = rc == MI_OK ? "" : mi_last_error();
+        mi_ctx_destroy(ctx);
+        if (rc != MI_OK) throw std::runtime_error("mi_rt: " + err);
+        return out;
+    }
+
+    // The irradiance of a finished directional lightmap at uv points and their normals through mi_lightmap_sh_sample: sample_lightmap and
+    // eval_lightmap_sh in one pass (sh is [H][W][9][3], normals [n][3]: a hit's shading normal shows its normal map).  An all-zero normal
+    // gives +0.0 and weight 0.  Returns [n][3].  Needs no scene: a static member.
+    static std::vector<float> sample_lightmap_sh(const std::vector<float>& sh, const std::vector<uint8_t>& valid, uint32_t width, uint32_t height,
+                                                 const std::vector<float>& uv, const std::vector<float>& normals, bool nearest = false,
+                                                 int device = 0, std::vector<float>* weight = nullptr) {
+        const size_t texels = (size_t)width * height, n = uv.size() / 2;
+        if (sh.size() != texels * 27 || (!valid.empty() && valid.size() != texels) || uv.size() != n * 2 || normals.size() != n * 3)
+            throw std::runtime_error("mi_rt: sh must be [H][W][9][3], valid empty or [H][W], uv [n][2] and normals [n][3]");
+        std::vector<float> out(n * 3);
+        if (weight) weight->resize(n);
+        if (n == 0) return out;                              // (an empty vector has no address to pass)
+        mi_ctx* ctx = nullptr;
+        mi_check(mi_ctx_create(device, &ctx));
+        const int rc = mi_lightmap_sh_sample(ctx, width, height, sh.data(), valid.empty() ? nullptr : valid.data(), (uint32_t)n, uv.data(),
+                                             normals.data(), nearest ? MI_LS_NEAREST : 0u, out.data(), weight ? weight->data() : nullptr);
+        const std::string err = rc == MI_OK ? "" : mi_last_error();
+        mi_ctx_destroy(ctx);
+        if (rc != MI_OK) throw std::runtime_error("mi_rt: " + err);
+        return out;
+    }
+
 private:
     // flatten -> context -> upload -> `call(ctx)` -> destroy; a failure surfaces as std::runtime_error carrying mi_last_error()
     template <class F> void with_context(int device, F call) const {

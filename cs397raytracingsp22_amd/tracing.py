@@ -847,6 +847,150 @@ def lightmap_sh_eval(sh, normals) -> np.ndarray:
     return np.ascontiguousarray(E.reshape(shape + (3,)))
 
 
+def check_lightmap_lookup(image, uv, valid=None, flags: int = 0, normals=None):
+    """Input checking of a lightmap lookup (mi_lightmap_sample, mi_lightmap_sh_sample), no GPU needed: `image` [H, W, 3], [H, W, 27] or
+    [H, W, 9, 3] with 1 <= W, H <= 32768; `uv` [..., 2]; `valid` None or [H, W] (0 = the texel takes no part: the finish calls' valid as
+    it stands); `normals` None or [..., 3] with uv's leading shape; flags 0 or abi.MI_LS_NEAREST.  The values are not looked at.  Returns
+    (image [H, W, C] f32, uv [n, 2] f32, valid [H, W] uint8 or None, flags, normals [n, 3] f32 or None, leading shape), all contiguous;
+    raises ValueError."""
+    img = np.asarray(image, np.float32)
+    if img.ndim == 4 and img.shape[2:] == (9, 3):
+        img = img.reshape(img.shape[:2] + (27,))
+    if img.ndim != 3 or img.shape[2] not in (3, 27):
+        raise ValueError(f"image must be [H, W, 3], [H, W, 27] or [H, W, 9, 3], got {np.shape(image)}")
+    H, W = img.shape[:2]
+    if not (1 <= H <= 32768 and 1 <= W <= 32768):
+        raise ValueError(f"width and height must be in 1 .. 32768, got {W} x {H}")
+    flags = int(flags)
+    if flags & ~abi.MI_LS_NEAREST:
+        raise ValueError(f"unknown flag bits {flags & ~abi.MI_LS_NEAREST:#x}")
+    T = np.asarray(uv, np.float32)
+    if T.ndim < 1 or T.shape[-1] != 2:
+        raise ValueError(f"uv must be [..., 2], got {T.shape}")
+    if T.size // 2 >= 1 << 32:
+        raise ValueError(f"{T.size // 2} points exceed 2^32 - 1")
+    v8 = None
+    if valid is not None:
+        v8 = np.ascontiguousarray(np.asarray(valid) != 0, np.uint8)
+        if v8.shape != (H, W):
+            raise ValueError(f"valid must be [{H}, {W}], got {v8.shape}")
+    N = None
+    if normals is not None:
+        N = np.asarray(normals, np.float32)
+        if N.ndim < 1 or N.shape[-1] != 3 or N.shape[:-1] != T.shape[:-1]:
+            raise ValueError(f"normals must be [..., 3] with uv's leading shape, got {N.shape} for uv {T.shape}")
+        N = np.ascontiguousarray(N.reshape(-1, 3))
+    return np.ascontiguousarray(img), np.ascontiguousarray(T.reshape(-1, 2)), v8, flags, N, T.shape[:-1]
+
+
+# The building blocks of lightmap_sample and lightmap_sh_sample: each rule of those definitions is written once, here.  All f32, one
+# rounding per operation, in the order written; the callers hold np.errstate(all="ignore").
+_LML_TAPS = ((0, 0), (0, 1), (1, 0), (1, 1))                      # (dy, dx): dy outer, dx inner
+
+
+def _lml_axis(t, n):
+    """One axis of the bilinear form at coordinate t in 0 .. 1 of n texels: ((i0, i1), (1 - f, f)).  probe_volume_sample's index
+    expressions; fmax sends a NaN to 0, so the indices stay in range for any t."""
+    f32 = np.float32
+    g = t * f32(n) - f32(0.5)
+    g = np.fmin(np.fmax(g, f32(0.0)), f32(n - 1))
+    i0 = np.minimum(np.floor(g).astype(np.int64), max(n - 2, 0))
+    f = g - i0.astype(f32)
+    return (i0, np.minimum(i0 + 1, n - 1)), (f32(1.0) - f, f)
+
+
+def _lml_unit(t):
+    """The reference's clamp of a texture coordinate (texture.rs:28-29); a NaN leaves it as 0"""
+    return np.fmin(np.fmax(t, np.float32(0.0)), np.float32(0.999))
+
+
+def _lml_texel(s, n, nan):
+    """The texel of the clamped coordinate s (or of its mirror 1 - s) among n: trunc(s n), at most n - 1; 0 where the coordinate was a
+    NaN (`nan`), as Rust's saturating cast gives"""
+    return np.where(nan, 0, np.minimum(np.trunc(s * np.float32(n)).astype(np.int64), n - 1))
+
+
+def _lml_lookup(img, ok, uv, flags, value, channels):
+    """The lookup both definitions share: `value` turns the texels [n, C] gathered for one tap into what is interpolated [n, channels].
+    Returns (out [n, channels] f32, weight [n] f32)."""
+    f32 = np.float32
+    zero, one = f32(0.0), f32(1.0)
+    H, W = img.shape[:2]
+    u, v = uv[:, 0], uv[:, 1]
+    if flags & abi.MI_LS_NEAREST:
+        x = _lml_texel(_lml_unit(u), W, np.isnan(u))
+        y = _lml_texel(one - _lml_unit(v), H, np.isnan(v))
+        take = ok[y, x]
+        return np.where(take[:, None], value(img[y, x]), zero), np.where(take, one, zero)
+    ix, wx = _lml_axis(u, W)
+    iy, wy = _lml_axis(one - v, H)
+    acc = np.zeros((len(uv), channels), f32)
+    sw = np.zeros(len(uv), f32)
+    for dy, dx in _LML_TAPS:
+        yi, xi = iy[dy], ix[dx]
+        w = wx[dx] * wy[dy]
+        take = (w > 0) & ok[yi, xi]                      # a tap that does not take part is not read: its texel may hold anything
+        acc = np.where(take[:, None], acc + w[:, None] * value(img[yi, xi]), acc)
+        sw = np.where(take, sw + w, sw)
+    return np.where((sw > 0)[:, None], acc / sw[:, None], zero), sw
+
+
+def lightmap_sample(image, uv, valid=None, flags: int = 0):
+    """Read a finished lightmap at uv points on the host (numpy only).  This is the DEFINITION of mi_lightmap_sample, which equals it bit
+    for bit.  Arguments as check_lightmap_lookup.  Returns (out [..., C] f32, weight [...] f32), C = 3 or 27.
+    Everything is f32, one rounding per operation (+ - * /, floor, fmin, fmax), in the order written in the blocks above.
+    Bilinear (flags == 0): gx = u W - 0.5, gy = (1 - v) H - 0.5 (row 0 is v = 1: Texture::sample's flip, texture.rs:29); per axis
+    g = fmin(fmax(g, 0), n - 1), i0 = min(floor(g), max(n - 2, 0)), f = g - i0, i1 = min(i0 + 1, n - 1) — probe_volume_sample's index
+    expressions, the clamp wrap mode.  Four taps, dy outer, dx inner: w = w_x[dx] w_y[dy] with w_a = (1 - f, f); a tap takes part when
+    w > 0 and its texel is valid, and one that does not is not read.  acc += w t, sw += w from +0; out = acc / sw when sw > 0, else +0;
+    weight = sw.  At a texel centre the result is the texel as a number (a -0 comes back +0).
+    MI_LS_NEAREST: the reference's own addressing (texture.rs:28-29), x = min(trunc(fmin(fmax(u, 0), 0.999) W), W - 1) and
+    y = min(trunc((1 - fmin(fmax(v, 0), 0.999)) H), H - 1), 0 for a NaN coordinate: the texel as it stands with weight 1, +0 with weight 0
+    when it is invalid.
+    Non-finite uv or texels spoil only the points whose taking-part taps touch them."""
+    img, T, v8, flags, _, shape = check_lightmap_lookup(image, uv, valid, flags)
+    ok = np.ones(img.shape[:2], bool) if v8 is None else v8 != 0
+    with np.errstate(all="ignore"):
+        out, sw = _lml_lookup(img, ok, T, flags, lambda t: t, img.shape[2])
+    assert out.dtype == np.float32 and sw.dtype == np.float32
+    return np.ascontiguousarray(out.reshape(shape + (img.shape[2],))), np.ascontiguousarray(sw.reshape(shape))
+
+
+def lightmap_sh_sample(sh, uv, normals, valid=None, flags: int = 0):
+    """The irradiance of a finished directional lightmap at uv points and their normals on the host (numpy only): lightmap_sample and
+    lightmap_sh_eval in one pass.  This is the DEFINITION of mi_lightmap_sh_sample, which equals it bit for bit.  `sh` [H, W, 9, 3] (or
+    flat [H, W, 27]); the other arguments as check_lightmap_lookup.  Returns (E [..., 3] f32, weight [...] f32).
+    An all-zero normal (either sign of zero) gives +0 and weight 0.  Otherwise x, y, z, b and PV_K are lightmap_sh_eval's, the taps and
+    their weights lightmap_sample's; per tap that takes part e = b0 (sh[0] K0) + ... + b8 (sh[8] K8) left to right, acc += w e,
+    sw += w, E = acc / sw: probe_volume_sample's order, never an interpolated record.  With MI_LS_NEAREST E is e of the one texel:
+    lightmap_sh_eval of that record, bit for bit.  NOT bit-equal to lightmap_sample of the 27 channels followed by lightmap_sh_eval."""
+    f32 = np.float32
+    if normals is None:
+        raise ValueError("normals are required")
+    img, T, v8, flags, N, shape = check_lightmap_lookup(sh, uv, valid, flags, normals)
+    if img.shape[2] != 27:
+        raise ValueError(f"sh must be [H, W, 9, 3] or [H, W, 27], got {np.shape(sh)}")
+    ok = np.ones(img.shape[:2], bool) if v8 is None else v8 != 0
+    with np.errstate(all="ignore"):
+        nx, ny, nz = N[:, 0], N[:, 1], N[:, 2]
+        covered = _lm_covered(N)
+        l = np.sqrt((nx * nx + ny * ny) + nz * nz)
+        x, y, z = nx / l, ny / l, nz / l
+        b = (np.ones(len(N), f32), y, z, x, x * y, y * z, f32(3.0) * (z * z) - f32(1.0), x * z, x * x - y * y)
+
+        def value(t):
+            r = t.reshape(-1, 9, 3) * PV_K[None, :, None]
+            e = b[0][:, None] * r[:, 0, :]
+            for k in range(1, 9):
+                e = e + b[k][:, None] * r[:, k, :]
+            return e
+        E, sw = _lml_lookup(img, ok, T, flags, value, 3)
+        E = np.where(covered[:, None], E, f32(0.0))
+        sw = np.where(covered, sw, f32(0.0))
+    assert E.dtype == np.float32 and sw.dtype == np.float32
+    return np.ascontiguousarray(E.reshape(shape + (3,))), np.ascontiguousarray(sw.reshape(shape))
+
+
 def lightmap_finish_var(image, m2, samples, points, normals, levels: int = 3, normal_power_log2: int = 5,
                         sigma_plane: float = float("inf"), reach: float = float("inf"), sigma_color: float = 8.0,
                         color_floor: float = 1e-6, dilate: int = 4):
@@ -1336,6 +1480,52 @@ class Context:
         """mi_lightmap_sh_eval_device: the same for n records held on the device (raw pointers: [n, 9, 3], [n, 3] and [n, 3] f32).
         Queued on `stream`, no synchronisation."""
         abi.check(self._lib.mi_lightmap_sh_eval_device(self._h, n, d_sh, d_normals, d_irradiance, stream))
+
+    # ---- lightmap lookup: a finished lightmap read at uv points ----
+    def lightmap_sample(self, image, uv, valid=None, flags: int = 0):
+        """mi_lightmap_sample: the helper lightmap_sample on the GPU, bit for bit: `image` [H, W, 3], [H, W, 27] or [H, W, 9, 3] f32 read
+        at `uv` [..., 2], bilinear over the texels `valid` ([H, W], None = all) lets take part, or with abi.MI_LS_NEAREST the reference's
+        nearest texel.  Returns (out [..., C] f32, weight [...] f32).  No scene is needed."""
+        img, T, v8, flags, _, shape = check_lightmap_lookup(image, uv, valid, flags)
+        H, W, ch = img.shape
+        out = np.empty((len(T), ch), np.float32)
+        weight = np.empty(len(T), np.float32)
+        abi.check(self._lib.mi_lightmap_sample(self._h, W, H, ch, img.ctypes.data, None if v8 is None else v8.ctypes.data, len(T),
+                                               T.ctypes.data, flags, out.ctypes.data, weight.ctypes.data))
+        return out.reshape(shape + (ch,)), weight.reshape(shape)
+
+    def lightmap_sample_device(self, width: int, height: int, channels: int, d_image: int, n: int, d_uv: int, d_out: int,
+                               d_weight: Optional[int] = None, d_valid: Optional[int] = None, flags: int = 0,
+                               stream: Optional[int] = None):
+        """mi_lightmap_sample_device: the same for an image and points held on the device (raw pointers: [H, W, channels] f32, an optional
+        [H, W] u8 mask, [n, 2] f32 in; [n, channels] f32 and an optional [n] f32 out, which must not overlap the inputs).  Queued on
+        `stream`, no synchronisation, no scratch."""
+        abi.check(self._lib.mi_lightmap_sample_device(self._h, width, height, channels, d_image, d_valid, n, d_uv, flags, d_out, d_weight,
+                                                      stream))
+
+    def lightmap_sh_sample(self, sh, uv, normals, valid=None, flags: int = 0):
+        """mi_lightmap_sh_sample: the helper lightmap_sh_sample on the GPU, bit for bit: the irradiance of a finished directional
+        lightmap `sh` [H, W, 9, 3] f32 at `uv` [..., 2] for the normals [..., 3] there (mi_intersect_rays' out_uv and out_normal go in as
+        they stand).  Returns (E [..., 3] f32, weight [...] f32).  No scene is needed."""
+        if normals is None:
+            raise ValueError("normals are required")
+        img, T, v8, flags, N, shape = check_lightmap_lookup(sh, uv, valid, flags, normals)
+        if img.shape[2] != 27:
+            raise ValueError(f"sh must be [H, W, 9, 3] or [H, W, 27], got {np.shape(sh)}")
+        H, W = img.shape[:2]
+        E = np.empty((len(T), 3), np.float32)
+        weight = np.empty(len(T), np.float32)
+        abi.check(self._lib.mi_lightmap_sh_sample(self._h, W, H, img.ctypes.data, None if v8 is None else v8.ctypes.data, len(T),
+                                                  T.ctypes.data, N.ctypes.data, flags, E.ctypes.data, weight.ctypes.data))
+        return E.reshape(shape + (3,)), weight.reshape(shape)
+
+    def lightmap_sh_sample_device(self, width: int, height: int, d_sh: int, n: int, d_uv: int, d_normals: int, d_irradiance: int,
+                                  d_weight: Optional[int] = None, d_valid: Optional[int] = None, flags: int = 0,
+                                  stream: Optional[int] = None):
+        """mi_lightmap_sh_sample_device: the same for records and points held on the device (raw pointers: [H, W, 9, 3] f32, an optional
+        [H, W] u8 mask, [n, 2] and [n, 3] f32 in; [n, 3] f32 and an optional [n] f32 out).  Queued on `stream`, no synchronisation."""
+        abi.check(self._lib.mi_lightmap_sh_sample_device(self._h, width, height, d_sh, d_valid, n, d_uv, d_normals, flags, d_irradiance,
+                                                         d_weight, stream))
 
     def last_reduce_psh_ms(self) -> float:
         """Sum of the wf_reduce_psh launch durations (ms) of the last render: entry 7 of mi_last_pipeline_ms after render_points_sh /
@@ -2126,3 +2316,39 @@ class Scene:                         # tracing.rs:213-218
             return ctx.shade_rays(self.camera, o, d, seed=seed, first_key=first_key)
         finally:
             ctx.close()
+
+    def shade_rays_baked(self, origins, dirs, lightmaps, t_min: float = 0.001, t_max: float = float("inf"), device: int = 0):
+        """Baked lighting for a batch of rays: one ray query and one lightmap lookup per lit object, no path is traced.  `lightmaps` maps
+        an index into Scene.objects to (sh [H, W, 9, 3], valid [H, W] or None): that object's finished directional lightmap
+        (bake_lightmap(directional=True) + lightmap_finish_sh).  Returns (rgb [n, 3] f32, RayHits): shade_hits_baked of the hits of
+        intersect_rays(resolve=True), the lookups on the GPU (mi_lightmap_sh_sample)."""
+        o, d, t_min, t_max = check_rays(origins, dirs, t_min, t_max)
+        ctx = Context(device)
+        try:
+            ctx.upload(self.flatten())
+            hits = ctx.intersect_rays(o, d, t_min, t_max, resolve=True)
+            return shade_hits_baked(hits, lightmaps, ctx.lightmap_sh_sample), hits
+        finally:
+            ctx.close()
+
+
+def shade_hits_baked(hits: RayHits, lightmaps, sample=lightmap_sh_sample) -> np.ndarray:
+    """The baked-lighting colour [n, 3] f32 of resolved ray hits: a miss is 0; a hit on an object listed in `lightmaps`
+    ({object index: (sh [H, W, 9, 3], valid or None)}) that has texture coordinates is
+    emission + (albedo * E) * f32(1 / pi) with E = sample(sh, hit uv, hit normal, valid)[0] — the hit's shading normal, so a normal map
+    shows; every other hit is its emission.  All f32, one rounding per operation.  `sample` is lightmap_sh_sample (the definition) or
+    Context.lightmap_sh_sample."""
+    f32 = np.float32
+    obj = np.asarray(hits.object)
+    rgb = np.zeros((len(obj), 3), f32)
+    hit = obj >= 0
+    rgb[hit] = hits.material["emission"][hit]
+    for index, (sh, valid) in lightmaps.items():
+        at = np.nonzero((obj == int(index)) & hits.has_uv)[0]
+        if len(at) == 0:
+            continue
+        E, _ = sample(sh, hits.uv[at], hits.normal[at], valid)
+        with np.errstate(all="ignore"):
+            rgb[at] = hits.material["emission"][at] + (hits.material["albedo"][at] * E) * f32(0.3183098861837907)
+    assert rgb.dtype == np.float32
+    return rgb

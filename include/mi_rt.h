@@ -209,6 +209,8 @@ typedef struct mi_render_opts {
 #define MI_LM_JITTER 1u             /* row r of a texel is a jittered position inside it, not its centre */
 /* mi_probe_volume.flags (mi_probe_volume_sample, below) */
 #define MI_PV_NORMAL_WEIGHT 1u      /* weight the eight corners by how far they lie in front of the surface */
+/* `flags` of mi_lightmap_sample / mi_lightmap_sh_sample (below) */
+#define MI_LS_NEAREST 1u            /* the reference's nearest-texel addressing (texture.rs:28-29), no interpolation */
 
 typedef enum mi_variant {
     MI_VARIANT_DEFAULT    = 0,  /* library picks (currently MI_VARIANT_WAVEFRONT)                  */
@@ -884,6 +886,48 @@ int  mi_lightmap_finish_sh_device(mi_ctx* ctx, uint32_t width, uint32_t height, 
                                   uint32_t dilate, float* out_sh, uint8_t* out_valid, void* stream);
 int  mi_lightmap_sh_eval(mi_ctx* ctx, uint32_t n, const float* sh, const float* normals, float* out_irradiance);
 int  mi_lightmap_sh_eval_device(mi_ctx* ctx, uint32_t n, const float* sh, const float* normals, float* out_irradiance, void* stream);
+
+/* ---- lightmap lookup: a finished lightmap read at uv points (added within ABI version 5: detect by symbol lookup) ----
+ * The last step of the lightmap pipeline: mi_intersect_rays gives, per ray, out_uv (RayHit.tex_coords) and the shading normal; these calls
+ *   give the lightmap there.  mi_lightmap_sample interpolates an [H][W][channels] f32 image, channels 3 (mi_lightmap_finish's) or 27
+ *   (mi_lightmap_finish_sh's records, flat); mi_lightmap_sh_sample reads [H][W][9][3] records and gives the irradiance at each point's own
+ *   normal in one pass.  `valid` is the finish calls' out_valid as it stands ([H][W] bytes, 0 = the texel takes no part; NULL = all
+ *   valid).  lightmap_sample and lightmap_sh_sample (Python) are the definitions; the results equal them BIT FOR BIT: pure f32, every
+ *   operation one of + - * /, sqrtf, floorf, fminf, fmaxf, comparisons and exact int-to-float conversions, in the order written here, no
+ *   fused multiply-add.  No scene is needed; nothing depends on scheduling (no atomics, nothing summed across threads).
+ * Bilinear (flags == 0), per point (u, v): gx = u * (float)W - 0.5f, gy = (1 - v) * (float)H - 0.5f (row 0 is v = 1: Texture::sample's
+ *   flip, texture.rs:29).  Per axis g = fminf(fmaxf(g, 0), (float)(n - 1)) — fmaxf sends a NaN to 0, so every index stays in range for NaN
+ *   and infinite coordinates — i0 = min((int)floorf(g), max(n - 2, 0)), f = g - (float)i0, i1 = min(i0 + 1, n - 1): the clamp wrap mode,
+ *   the only one.  Four taps, dy outer, dx inner: w = wx[dx] * wy[dy] with w_a = { 1 - f, f }.  A tap takes part when w > 0 and its texel
+ *   is valid; a tap that takes no part is not read.  acc[c] = acc[c] + w * t[c] and sw = sw + w from +0.0; out[c] = acc[c] / sw when
+ *   sw > 0, else +0.0; out_weight = sw (1 within rounding inside a chart, smaller where invalid texels were left out, 0: nothing to read).
+ * MI_LS_NEAREST, the reference's own addressing (texture.rs:28-29) in f32: x = 0 when u is a NaN (Rust's saturating cast), else
+ *   x = min((int)(fminf(fmaxf(u, 0), 0.999f) * (float)W), W - 1); y = 0 when v is a NaN, else
+ *   y = min((int)((1 - fminf(fmaxf(v, 0), 0.999f)) * (float)H), H - 1).  The output is that texel's values as they stand with weight 1,
+ *   or +0.0 with weight 0 when the texel is invalid.  No NaN reaches a float-to-int conversion.
+ * mi_lightmap_sh_sample: an all-zero normal (either sign of zero) gives +0.0 and weight 0.  Otherwise x, y, z, b[9] and K_k are
+ *   mi_lightmap_sh_eval's; per tap that takes part e[c] = b0*(sh[0][c]*K_0) + ... + b8*(sh[8][c]*K_8) summed left to right, then
+ *   acc[c] = acc[c] + w * e[c], sw = sw + w, out_irradiance[c] = acc[c] / sw: mi_probe_volume_sample's order, three accumulators and
+ *   never an interpolated record.  With MI_LS_NEAREST out_irradiance is e of the one texel: mi_lightmap_sh_eval of that record, bit for
+ *   bit.  NOT bit-equal to mi_lightmap_sample at 27 channels followed by mi_lightmap_sh_eval, which rounds in another order.
+ * Non-finite input: non-finite uv, normals or texel values never fault; they spoil only the points whose taking-part taps touch them (a
+ *   non-finite uv behaves as the clamped coordinate it becomes; a non-finite normal spoils its own point).  No address depends on anything
+ *   but the clamped indices.  Texels behind valid == 0 may hold anything: they are never read.
+ * MI_ERR_INVALID (each with a message, checked before the context, nothing is launched): a NULL image / sh, uv, normals or out /
+ *   out_irradiance (valid and out_weight may be NULL); width or height 0 or above 32768; channels other than 3 or 27; unknown flag bits;
+ *   in the _device forms an output that overlaps an input.  n == 0 is MI_OK and launches nothing.
+ * Host forms: HOST pointers, blocking; the arrays pass through a buffer the context owns.  _device forms: DEVICE pointers on ctx's device;
+ *   they queue one kernel on `stream`, do not synchronise and need no scratch, so calls on different streams may overlap;
+ *   mi_last_kernel_ms reports the kernel.  Indices are 64-bit: a 32768 x 32768 table of records is legal. */
+int  mi_lightmap_sample(mi_ctx* ctx, uint32_t width, uint32_t height, uint32_t channels, const float* image, const uint8_t* valid,
+                        uint32_t n, const float* uv, uint32_t flags, float* out, float* out_weight);
+int  mi_lightmap_sample_device(mi_ctx* ctx, uint32_t width, uint32_t height, uint32_t channels, const float* image, const uint8_t* valid,
+                               uint32_t n, const float* uv, uint32_t flags, float* out, float* out_weight, void* stream);
+int  mi_lightmap_sh_sample(mi_ctx* ctx, uint32_t width, uint32_t height, const float* sh, const uint8_t* valid, uint32_t n,
+                           const float* uv, const float* normals, uint32_t flags, float* out_irradiance, float* out_weight);
+int  mi_lightmap_sh_sample_device(mi_ctx* ctx, uint32_t width, uint32_t height, const float* sh, const uint8_t* valid, uint32_t n,
+                                  const float* uv, const float* normals, uint32_t flags, float* out_irradiance, float* out_weight,
+                                  void* stream);
 
 /* Size and allocate the wavefront pipeline's HBM buffers (path state, sample slots) for
  * this camera with the image shared by `world` ranks, so that the first render does not pay the

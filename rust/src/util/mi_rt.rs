@@ -52,6 +52,7 @@ pub const MI_RT_ABI_VERSION: c_int = 5;
 pub const MI_HEMI_WORLD_RADIUS: u32 = 1;
 pub const MI_LM_JITTER: u32 = 1;
 pub const MI_PV_NORMAL_WEIGHT: u32 = 1;
+pub const MI_LS_NEAREST: u32 = 1;
 // mi_material_kind / mi_object_kind / projection and shading modes (include/mi_rt.h)
 pub const MI_MAT_LAMBERTIAN: i32 = 0; pub const MI_MAT_METAL: i32 = 1; pub const MI_MAT_DIELECTRIC: i32 = 2;
 pub const MI_MAT_PARAMETERIZED: i32 = 3; pub const MI_MAT_ISOTROPIC: i32 = 4;
@@ -222,6 +223,16 @@ extern "C" {
     pub fn mi_lightmap_sh_eval(ctx: *mut mi_ctx, n: u32, sh: *const f32, normals: *const f32, out_irradiance: *mut f32) -> c_int;
     pub fn mi_lightmap_sh_eval_device(ctx: *mut mi_ctx, n: u32, sh: *const f32, normals: *const f32, out_irradiance: *mut f32,
                                       stream: *mut c_void) -> c_int;
+    // lightmap lookup: a finished lightmap read at uv points (bilinear over the valid texels, or MI_LS_NEAREST)
+    pub fn mi_lightmap_sample(ctx: *mut mi_ctx, width: u32, height: u32, channels: u32, image: *const f32, valid: *const u8,
+                              n: u32, uv: *const f32, flags: u32, out: *mut f32, out_weight: *mut f32) -> c_int;
+    pub fn mi_lightmap_sample_device(ctx: *mut mi_ctx, width: u32, height: u32, channels: u32, image: *const f32, valid: *const u8,
+                                     n: u32, uv: *const f32, flags: u32, out: *mut f32, out_weight: *mut f32, stream: *mut c_void) -> c_int;
+    pub fn mi_lightmap_sh_sample(ctx: *mut mi_ctx, width: u32, height: u32, sh: *const f32, valid: *const u8, n: u32,
+                                 uv: *const f32, normals: *const f32, flags: u32, out_irradiance: *mut f32, out_weight: *mut f32) -> c_int;
+    pub fn mi_lightmap_sh_sample_device(ctx: *mut mi_ctx, width: u32, height: u32, sh: *const f32, valid: *const u8, n: u32,
+                                        uv: *const f32, normals: *const f32, flags: u32, out_irradiance: *mut f32, out_weight: *mut f32,
+                                        stream: *mut c_void) -> c_int;
     pub fn mi_reserve(ctx: *mut mi_ctx, cam: *const mi_camera_desc, world: i32, max_state_bytes: u64) -> c_int;
     pub fn mi_last_pipeline_ms(ctx: *mut mi_ctx, out8: *mut f32) -> c_int;
     pub fn mi_last_pipeline_counts(ctx: *mut mi_ctx, out8: *mut u64) -> c_int;

@@ -440,6 +440,53 @@ impl Scene {
         out
     }
 
+    /// Read a finished lightmap at uv points (mi_lightmap_sample): `image` holds height * width texels of `channels` floats (3 or 27), `uv`
+    /// intersect's tex_coords as they stand (row 0 is v = 1), `valid` is empty (every texel takes part) or finish_lightmap's mask.
+    /// Bilinear over the valid texels, or with `nearest` (MI_LS_NEAREST) the texel Texture::sample addresses.  Returns `channels` floats
+    /// per point and the weight sum per point (0: nothing to read).  Needs no scene: an associated function.
+    pub fn sample_lightmap(image: &[f32], valid: &[u8], width: u32, height: u32, channels: u32, uv: &[[f32; 2]], nearest: bool) -> (Vec<f32>, Vec<f32>) {
+        let texels = width as usize * height as usize;
+        assert!(image.len() == texels * channels as usize && (valid.is_empty() || valid.len() == texels), "mi_rt: image (and valid) must hold height * width texels");
+        let mut out = vec![0.0f32; uv.len() * channels as usize];
+        let mut weight = vec![0.0f32; uv.len()];
+        if uv.is_empty() { return (out, weight); }
+        unsafe {
+            let mut ctx = std::ptr::null_mut();
+            assert_eq!(mi_rt::mi_ctx_create(0, &mut ctx), 0, "{}", mi_rt::last_error());
+            let rc = mi_rt::mi_lightmap_sample(ctx, width, height, channels, image.as_ptr(), if valid.is_empty() { std::ptr::null() } else { valid.as_ptr() },
+                                               uv.len() as u32, uv.as_ptr() as *const f32, if nearest { mi_rt::MI_LS_NEAREST } else { 0 },
+                                               out.as_mut_ptr(), weight.as_mut_ptr());
+            let msg = mi_rt::last_error();
+            mi_rt::mi_ctx_destroy(ctx);
+            assert_eq!(rc, 0, "{}", msg);
+        }
+        (out, weight)
+    }
+
+    /// The irradiance of a finished directional lightmap at uv points and their normals (mi_lightmap_sh_sample): sample_lightmap and
+    /// eval_lightmap_sh in one pass; a hit's shading normal shows its normal map.  An all-zero normal gives +0.0 and weight 0.  Returns
+    /// the irradiance and the weight sum per point.  Needs no scene: an associated function.
+    pub fn sample_lightmap_sh(sh: &[[[f32; 3]; 9]], valid: &[u8], width: u32, height: u32, uv: &[[f32; 2]], normals: &[[f32; 3]],
+                              nearest: bool) -> (Vec<[f32; 3]>, Vec<f32>) {
+        let texels = width as usize * height as usize;
+        assert!(sh.len() == texels && (valid.is_empty() || valid.len() == texels), "mi_rt: sh (and valid) must hold height * width texels");
+        assert_eq!(uv.len(), normals.len(), "mi_rt: one normal per point");
+        let mut out = vec![[0.0f32; 3]; uv.len()];
+        let mut weight = vec![0.0f32; uv.len()];
+        if uv.is_empty() { return (out, weight); }
+        unsafe {
+            let mut ctx = std::ptr::null_mut();
+            assert_eq!(mi_rt::mi_ctx_create(0, &mut ctx), 0, "{}", mi_rt::last_error());
+            let rc = mi_rt::mi_lightmap_sh_sample(ctx, width, height, sh.as_ptr() as *const f32, if valid.is_empty() { std::ptr::null() } else { valid.as_ptr() },
+                                                  uv.len() as u32, uv.as_ptr() as *const f32, normals.as_ptr() as *const f32,
+                                                  if nearest { mi_rt::MI_LS_NEAREST } else { 0 }, out.as_mut_ptr() as *mut f32, weight.as_mut_ptr());
+            let msg = mi_rt::last_error();
+            mi_rt::mi_ctx_destroy(ctx);
+            assert_eq!(rc, 0, "{}", msg);
+        }
+        (out, weight)
+    }
+
     /// flatten -> context on device 0 -> upload -> `call` -> destroy; panics with the library's message on failure.
     fn with_gpu_scene<F: FnOnce(*mut mi_rt::mi_ctx) -> i32>(&self, call: F) {
         let sb = self.flatten_scene();

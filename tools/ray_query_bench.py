@@ -92,7 +92,10 @@ over the covered texels, the moments those of 16 samples with a relative standar
 the ratio (three kernels per level instead of one).
 
 --mode directional times the directional lightmap calls (mi_render_points_sh_device, mi_lightmap_finish_sh_device,
-mi_lightmap_sh_eval_device); its protocol and the measured figures are in directional_rows' docstring."""
+mi_lightmap_sh_eval_device); its protocol and the measured figures are in directional_rows' docstring.
+
+--mode lookup times the lightmap lookup kernels (mi_lightmap_sample_device at 3 and 27 channels, mi_lightmap_sh_sample_device) at
+--lookup-sizes and --volume-points; its protocol is in lookup_rows' docstring, the measured figures in DESIGN.md."""
 import argparse
 import json
 import os
@@ -1121,6 +1124,102 @@ def directional_rows(ctx, sizes, point_counts, calls, warmup):
     return rows
 
 
+def lookup_rows(ctx, sizes, point_counts, calls, warmup):
+    """--mode lookup: the lightmap lookup kernels on resident tables, HIP events inside the library (mi_last_kernel_ms), `warmup` calls
+    then `calls` timed ones, medians with min - max.  Inputs: a seeded random SH lightmap [size, size, 9, 3] (all texels valid) and a
+    3-channel image of the same size, for size in `sizes`; n points for n in `point_counts`, unit normals.  The uv come in two orders:
+    "coherent" — the first n points, row-major, of the atlas's own grid at twice its resolution (neighbouring lanes share their taps;
+    the points span n / 4 texels, 113 MB of records at 2^22) — and "shuffled", n points of that grid drawn at random over the WHOLE
+    table (113 MB of records at 1024^2, 453 MB at 2048^2).  Rows per (size, n, order): lml_sample<3>, lml_sample<27>,
+    lml_sh_sample (the fused form), the composition lml_sample<27> + lsh_eval (the sum of the two kernels' times), and a device-to-device
+    copy of the fused form's nominal byte count (per point 8 + 12 in, four 108-byte taps, 12 + 4 out = 468 bytes, half of it copied:
+    read and written).  The results are checked against lightmap_sample / lightmap_sh_sample on a 4096-point subsample, bit for bit.
+    The measured figures are in DESIGN.md section 4, "Lightmap lookup"."""
+    from cs397raytracingsp22_amd import lightmap_sample, lightmap_sh_sample
+    dev = torch.device("cuda:0")
+    rows = []
+
+    def stats(ms):
+        return {"ms_median": round(float(np.median(ms)), 4), "ms_min": round(float(np.min(ms)), 4), "ms_max": round(float(np.max(ms)), 4)}
+
+    def bits(t):
+        return t.contiguous().view(torch.int32).cpu().numpy()
+
+    for size in sizes:
+        gen = torch.Generator(device=dev)
+        gen.manual_seed(3)
+        sh = torch.randn((size, size, 9, 3), generator=gen, dtype=torch.float32, device=dev)
+        img = torch.randn((size, size, 3), generator=gen, dtype=torch.float32, device=dev)
+        sh_host, img_host = sh.cpu().numpy(), img.cpu().numpy()
+        for n in point_counts:
+            k = torch.arange(n, device=dev, dtype=torch.int64)
+            gw = 2 * size
+            if n > gw * gw:
+                raise SystemExit(f"ray_query_bench: {n} points exceed the {gw} x {gw} grid")
+            def centres(k):                  # the uv of the points number k of the gw x gw grid, row-major
+                u = ((k % gw).to(torch.float32) + 0.5) / gw
+                v = 1.0 - ((k // gw).to(torch.float32) + 0.5) / gw
+                return torch.stack([u, v], dim=1).contiguous()
+
+            nrm = torch.randn((n, 3), generator=gen, dtype=torch.float32, device=dev)
+            nrm = (nrm / nrm.norm(dim=1, keepdim=True)).contiguous()
+            anywhere = torch.randint(0, gw * gw, (n,), generator=gen, device=dev, dtype=torch.int64)
+            out3 = torch.empty((n, 3), dtype=torch.float32, device=dev)
+            out27 = torch.empty((n, 27), dtype=torch.float32, device=dev)
+            E, E2 = torch.empty((n, 3), dtype=torch.float32, device=dev), torch.empty((n, 3), dtype=torch.float32, device=dev)
+            w = torch.empty(n, dtype=torch.float32, device=dev)
+            src, dst = torch.empty(234 * n, dtype=torch.uint8, device=dev), torch.empty(234 * n, dtype=torch.uint8, device=dev)
+            for order, uv in (("coherent", centres(k)), ("shuffled", centres(anywhere))):
+                torch.cuda.synchronize()
+                ms = {"lml_sample<3>": [], "lml_sample<27>": [], "lml_sh_sample": [], "lml_sample<27> + lsh_eval": [], "copy": []}
+                for it in range(warmup + calls):
+                    t = {}
+                    ctx.lightmap_sample_device(size, size, 3, img.data_ptr(), n, uv.data_ptr(), out3.data_ptr(), w.data_ptr())
+                    torch.cuda.synchronize()
+                    t["lml_sample<3>"] = ctx.last_kernel_ms()
+                    ctx.lightmap_sample_device(size, size, 27, sh.data_ptr(), n, uv.data_ptr(), out27.data_ptr(), w.data_ptr())
+                    torch.cuda.synchronize()
+                    t["lml_sample<27>"] = ctx.last_kernel_ms()
+                    ctx.lightmap_sh_eval_device(n, out27.data_ptr(), nrm.data_ptr(), E2.data_ptr())
+                    torch.cuda.synchronize()
+                    t["lml_sample<27> + lsh_eval"] = t["lml_sample<27>"] + ctx.last_kernel_ms()
+                    ctx.lightmap_sh_sample_device(size, size, sh.data_ptr(), n, uv.data_ptr(), nrm.data_ptr(), E.data_ptr(), w.data_ptr())
+                    torch.cuda.synchronize()
+                    t["lml_sh_sample"] = ctx.last_kernel_ms()
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    e0.record()
+                    dst.copy_(src)
+                    e1.record()
+                    torch.cuda.synchronize()
+                    t["copy"] = e0.elapsed_time(e1)
+                    if it >= warmup:
+                        for key, val in t.items():
+                            ms[key].append(val)
+                # the helpers on a 4096-point subsample
+                pick = torch.linspace(0, n - 1, 4096, device=dev).to(torch.int64)
+                uv_h, n_h = uv[pick].cpu().numpy(), nrm[pick].cpu().numpy()
+                want3, want27 = lightmap_sample(img_host, uv_h)[0], lightmap_sample(sh_host, uv_h)[0]
+                wantE, wantw = lightmap_sh_sample(sh_host, uv_h, n_h)
+                same = (np.array_equal(bits(out3[pick]), want3.view(np.int32)) and np.array_equal(bits(out27[pick]), want27.view(np.int32))
+                        and np.array_equal(bits(E[pick]), wantE.view(np.int32)) and np.array_equal(bits(w[pick]), wantw.view(np.int32)))
+                fused, comp = float(np.median(ms["lml_sh_sample"])), float(np.median(ms["lml_sample<27> + lsh_eval"]))
+                moved = 468 * n
+                for key in ("lml_sample<3>", "lml_sample<27>", "lml_sh_sample", "lml_sample<27> + lsh_eval", "copy"):
+                    row = dict(mode="lookup", size=size, n_points=n, order=order, query=key, calls=calls, **stats(ms[key]))
+                    if key == "lml_sh_sample":
+                        row.update(fused_over_composition=round(fused / comp, 4), nominal_gb_per_s=round(moved / fused / 1e6, 1),
+                                   equals_helpers=same)
+                    if key == "copy":
+                        row.update(bytes_moved=moved, gb_per_s=round(moved / float(np.median(ms["copy"])) / 1e6, 1))
+                    rows.append(row)
+                    print(json.dumps(row), flush=True)
+                if not same:
+                    raise SystemExit("ray_query_bench: the lookup kernels differ from lightmap_sample / lightmap_sh_sample")
+            del k, anywhere, nrm, out3, out27, E, E2, w, src, dst
+        del sh, img, sh_host, img_host
+    return rows
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--calls", type=int, default=20, help="timed calls per row (at least 20)")
@@ -1128,7 +1227,7 @@ def main():
     ap.add_argument("--width", type=int, default=1920)
     ap.add_argument("--height", type=int, default=1080)
     ap.add_argument("--configs", default="2,4")
-    ap.add_argument("--mode", choices=("intersect", "occlusion", "render", "hemisphere", "bake", "probes", "atlas", "finish", "volume", "variance", "adaptive", "directional"), default="intersect",
+    ap.add_argument("--mode", choices=("intersect", "occlusion", "render", "hemisphere", "bake", "probes", "atlas", "finish", "volume", "variance", "adaptive", "directional", "lookup"), default="intersect",
                     help="intersect: the closest-hit rows; occlusion: the any-hit query against the visibility form; "
                          "render: ray-table rendering against mi_shade_rays_device; "
                          "hemisphere: hemisphere occlusion against the any-hit query on the identical pre-made rays; "
@@ -1141,9 +1240,12 @@ def main():
                          "adaptive: the adaptive bake against uniform bakes at the same and at the largest sample count, errors against a "
                          "16 x reference, and the bookkeeping kernels' share of a round; "
                          "directional: wf_reduce_psh's share of an SH bake, the 27-channel finish against nine 3-channel ones, and the "
-                         "evaluation against a copy of the same bytes")
+                         "evaluation against a copy of the same bytes; "
+                         "lookup: the lightmap lookup kernels, coherent and shuffled uv, the fused SH form against lml_sample<27> + lsh_eval "
+                         "and against a copy of the same bytes")
+    ap.add_argument("--lookup-sizes", default="1024,2048", help="--mode lookup: the square lightmap sizes")
     ap.add_argument("--volume-grids", default="16,32", help="--mode volume: probes per axis")
-    ap.add_argument("--volume-points", default=f"{1 << 20},{1 << 22}", help="--mode volume and --mode directional: point counts")
+    ap.add_argument("--volume-points", default=f"{1 << 20},{1 << 22}", help="--mode volume, --mode directional and --mode lookup: point counts")
     ap.add_argument("--finish-sizes", default="1024,2048,4096", help="--mode finish and --mode variance: the square atlas sizes")
     ap.add_argument("--atlas-sizes", default="1024,2048", help="--mode atlas: the square atlas sizes")
     ap.add_argument("--atlas-grid", type=int, default=0, help="--mode atlas: a synthetic height field of N x N quads (2 N^2 triangles) instead "
@@ -1170,6 +1272,9 @@ def main():
         a.configs = ""
     if a.mode == "directional":
         rows += directional_rows(ctx, [int(v) for v in a.finish_sizes.split(",")], [int(v) for v in a.volume_points.split(",")], a.calls, a.warmup)
+        a.configs = ""
+    if a.mode == "lookup":
+        rows += lookup_rows(ctx, [int(v) for v in a.lookup_sizes.split(",")], [int(v) for v in a.volume_points.split(",")], a.calls, a.warmup)
         a.configs = ""
     if a.mode == "adaptive":
         rows += adaptive_rows(ctx, int(a.atlas_sizes.split(",")[0]), a.atlas_bakes)
