@@ -142,6 +142,8 @@ EXPORTS = [
     "mi_render_points_sh", "mi_render_points_sh_device", "mi_bake_lightmap_sh",
     "mi_lightmap_finish_sh", "mi_lightmap_finish_sh_device", "mi_lightmap_sh_eval", "mi_lightmap_sh_eval_device",
     "mi_lightmap_sample", "mi_lightmap_sample_device", "mi_lightmap_sh_sample", "mi_lightmap_sh_sample_device",
+    "mi_lightmap_mips", "mi_lightmap_mips_device", "mi_lightmap_sample_lod", "mi_lightmap_sample_lod_device",
+    "mi_lightmap_sh_sample_lod", "mi_lightmap_sh_sample_lod_device",
     "mi_multi_create", "mi_multi_create_loopback", "mi_multi_destroy", "mi_multi_device_count", "mi_multi_context", "mi_multi_scene_upload", "mi_multi_reserve", "mi_multi_render",
 ]
 
@@ -324,6 +326,18 @@ def load() -> C.CDLL:
     lib.mi_lightmap_sh_sample.argtypes = [vp, u32, u32, vp, vp, u32, vp, vp, u32, vp, vp]
     lib.mi_lightmap_sh_sample_device.argtypes = lib.mi_lightmap_sh_sample.argtypes + [vp]
     for name in ("lightmap_sample", "lightmap_sample_device", "lightmap_sh_sample", "lightmap_sh_sample_device"):
+        getattr(lib, "mi_" + name).restype = C.c_int
+    # lightmap mips (added within ABI 5): width, height, channels, image, valid, levels, out_mips, out_valid, out_coverage (, stream);
+    # the trilinear lookups: lightmap_sample's / lightmap_sh_sample's lists with levels, mips, mip_valid behind valid and lod behind
+    # uv / normals
+    lib.mi_lightmap_mips.argtypes = [vp, u32, u32, u32, vp, vp, u32, vp, vp, vp]
+    lib.mi_lightmap_mips_device.argtypes = lib.mi_lightmap_mips.argtypes + [vp]
+    lib.mi_lightmap_sample_lod.argtypes = [vp, u32, u32, u32, vp, vp, u32, vp, vp, u32, vp, vp, u32, vp, vp]
+    lib.mi_lightmap_sample_lod_device.argtypes = lib.mi_lightmap_sample_lod.argtypes + [vp]
+    lib.mi_lightmap_sh_sample_lod.argtypes = [vp, u32, u32, vp, vp, u32, vp, vp, u32, vp, vp, vp, u32, vp, vp]
+    lib.mi_lightmap_sh_sample_lod_device.argtypes = lib.mi_lightmap_sh_sample_lod.argtypes + [vp]
+    for name in ("lightmap_mips", "lightmap_mips_device", "lightmap_sample_lod", "lightmap_sample_lod_device", "lightmap_sh_sample_lod",
+                 "lightmap_sh_sample_lod_device"):
         getattr(lib, "mi_" + name).restype = C.c_int
     lib.mi_multi_create.argtypes = [C.c_int, C.POINTER(C.c_int), C.POINTER(vp)]
     lib.mi_multi_create.restype = C.c_int

@@ -73,6 +73,8 @@ hipError_t launch_wf_reduce_psh(const WfArgs& a, bool first_batch, bool last_bat
 hipError_t launch_lsh_atrous(const LmfArgs& a, hipStream_t stream);
 hipError_t launch_lsh_eval(const LshEvalArgs& a, hipStream_t stream);
 hipError_t launch_lml_sample(const LmlArgs& a, uint32_t channels, hipStream_t stream);
+hipError_t launch_lmm_reduce(const LmmArgs& a, uint32_t channels, hipStream_t stream);
+hipError_t launch_lml_sample_lod(const LmlLodArgs& a, uint32_t channels, hipStream_t stream);
 }  // namespace pt
 
 using namespace pt;
@@ -144,6 +146,8 @@ struct mi_ctx {
     bool lmf_big_lds_enabled = false;
     // mi_lightmap_finish_sh: the same for [H][W][9][3] records
     void* d_lsh = nullptr; size_t lsh_bytes = 0;
+    // mi_lightmap_mips_device without out_coverage: the coverage planes of levels 1 .. L - 1 (grown on demand)
+    void* d_lmm = nullptr; size_t lmm_bytes = 0;
     // the host forms of the lightmap post-process calls (finish, finish_sh, sh_eval, finish_var, finish_var_counts, select, gather, merge):
     // the uploaded columns and the results of ONE call (staged; every such call synchronises before it returns)
     void* d_io = nullptr; size_t io_bytes = 0;
@@ -199,6 +203,7 @@ struct mi_ctx {
         bool dump_launches = false;                     // print every pipeline launch's duration (needs per-launch events)
         ScheduleKnobs sched;                            // the pass schedule's knobs (render_plan.hpp)
         uint32_t lmf_lds_max_step = 1;                  // lmf_atrous: stage the tile and its halo in LDS up to this step, read HBM directly above (measured: DESIGN.md "Lightmap finishing")
+        uint32_t lmm_levels_per_launch = kMipFuse;      // lmm_reduce: levels written per launch; 1 is the unfused form (measured: DESIGN.md "Lightmap mips")
         uint32_t spin_timeout_ms = 120000;              // header wait: give up after this long without progress
     } tune;
 };
@@ -270,6 +275,8 @@ static int ctx_init(mi_ctx* c, const hipDeviceProp_t& prop) {
     t.dump_launches = getenv("MI_RT_WF_DUMP_LAUNCHES") != nullptr;
     env_u("MI_RT_SPIN_TIMEOUT_MS", t.spin_timeout_ms);
     env_u("MI_RT_LMF_LDS_MAX_STEP", t.lmf_lds_max_step);
+    env_u("MI_RT_LMM_LEVELS_PER_LAUNCH", t.lmm_levels_per_launch);
+    t.lmm_levels_per_launch = std::min(std::max(t.lmm_levels_per_launch, 1u), kMipFuse);
     if (t.lmf_lds_max_step > kLmfMaxLdsStep) t.lmf_lds_max_step = kLmfMaxLdsStep;
     if (t.vote_t < 1) t.vote_t = 1;
     if (t.k_steps < 1) t.k_steps = 1;
@@ -320,6 +327,7 @@ extern "C" void mi_ctx_destroy(mi_ctx* c) {
     if (c->d_rays) (void)hipFree(c->d_rays);
     if (c->d_sh) (void)hipFree(c->d_sh);
     if (c->d_lsh) (void)hipFree(c->d_lsh);
+    if (c->d_lmm) (void)hipFree(c->d_lmm);
     if (c->d_lm_hdr) (void)hipFree(c->d_lm_hdr);
     if (c->d_lm_list) (void)hipFree(c->d_lm_list);
     if (c->h_lm_total) (void)hipHostFree(c->h_lm_total);
@@ -1789,6 +1797,196 @@ extern "C" int mi_lightmap_sh_sample_device(mi_ctx* c, uint32_t width, uint32_t 
 extern "C" int mi_lightmap_sh_sample(mi_ctx* c, uint32_t width, uint32_t height, const float* sh, const uint8_t* valid, uint32_t n,
                                      const float* uv, const float* normals, uint32_t flags, float* out_irradiance, float* out_weight) {
     return lookup_entry_host("mi_lightmap_sh_sample", c, { width, height, 0, sh, valid, n, uv, normals, flags, out_irradiance, out_weight });
+}
+
+// ------------------------------------------------------------------ lightmap mips (the coverage-aware pyramid and the trilinear lookups)
+// tracing.py lightmap_mips as lmm_reduce<3> / lmm_reduce<27>, launched by render_plan.cpp mip_plan (the layout and which level every
+// launch reads and how many it writes), and lightmap_sample_lod / lightmap_sh_sample_lod as one kernel each, which read the same layout.
+struct MipsArgs {
+    uint32_t width, height, channels; const float* image; const uint8_t* valid; uint32_t levels; float* out_mips; uint8_t* out_valid;
+    float* out_coverage;
+};
+
+// Checked before the context, nothing is launched: the pointers, the size, the channel count, the levels
+static int check_mips_args(const char* who, const MipsArgs& m, MipPlan* plan) {
+    if (!m.image || !m.out_mips) return fail(MI_ERR_INVALID, "%s: image and out_mips are required", who);
+    if (m.width == 0 || m.width > 32768u || m.height == 0 || m.height > 32768u)
+        return fail(MI_ERR_INVALID, "%s: width %u / height %u is not in 1 .. 32768", who, m.width, m.height);
+    if (m.channels != 3 && m.channels != (uint32_t)kShFloats) return fail(MI_ERR_INVALID, "%s: channels %u is not 3 or 27", who, m.channels);
+    if (!mip_plan(m.width, m.height, m.levels, kMipFuse, plan))
+        return fail(MI_ERR_INVALID, "%s: levels %u is above the full chain of %u x %u, %u", who, m.levels, m.width, m.height,
+                    mip_full_chain(m.width, m.height));
+    return MI_OK;
+}
+
+// Queue the pyramid on `stream`: every pointer is a device pointer, cov the coverage planes of levels 1 .. L - 1 (the caller's or scratch)
+static int mips_device(mi_ctx* c, const MipsArgs& m, const MipPlan& plan, float* cov, hipStream_t stream) {
+    return timed(c, stream, [&]() -> int {
+        for (const MipLaunch& l : plan.launches) {
+            const MipLevel& src = plan.level[l.src];
+            LmmArgs a{};
+            a.src = l.src == 0 ? m.image : m.out_mips + src.offset * m.channels;
+            a.src_valid = l.src == 0 ? m.valid : nullptr;
+            a.src_cov = l.src == 0 ? nullptr : cov + src.offset;
+            a.mips = m.out_mips; a.mip_valid = m.out_valid; a.mip_cov = cov;
+            for (uint32_t j = 0; j < l.count; j++) a.off[j] = plan.level[l.src + 1 + j].offset;
+            a.src_w = src.width; a.src_h = src.height; a.count = l.count; a.tiles_x = (src.width + kTile - 1) / kTile;
+            HIP_TRY(launch_lmm_reduce(a, m.channels, stream));
+        }
+        return MI_OK;
+    });
+}
+
+extern "C" int mi_lightmap_mips_device(mi_ctx* c, uint32_t width, uint32_t height, uint32_t channels, const float* image, const uint8_t* valid,
+                                       uint32_t levels, float* out_mips, uint8_t* out_valid, float* out_coverage, void* stream) {
+    const char* who = "mi_lightmap_mips_device";
+    const MipsArgs m{ width, height, channels, image, valid, levels, out_mips, out_valid, out_coverage };
+    MipPlan plan;
+    MI_TRY(check_mips_args(who, m, &plan));
+    if (!c) return fail(MI_ERR_INVALID, "ctx is NULL");
+    const size_t texels = (size_t)width * height, made = (size_t)plan.texels;
+    MI_TRY(check_no_overlap(who, { { out_mips, made * channels * sizeof(float), "out_mips" }, { out_valid, made, "out_valid" },
+                                   { out_coverage, made * sizeof(float), "out_coverage" } },
+                            { { image, texels * channels * sizeof(float) }, { valid, texels } }));
+    if (plan.levels == 1) return MI_OK;                // one level: nothing to make
+    HIP_TRY(hipSetDevice(c->device));
+    if (c->tune.lmm_levels_per_launch != kMipFuse) mip_plan(width, height, levels, c->tune.lmm_levels_per_launch, &plan);
+    float* cov = out_coverage;
+    if (!cov) {                                        // the coverage planes in the context's own buffer: one such call at a time
+        MI_TRY(ensure(&c->d_lmm, &c->lmm_bytes, made * sizeof(float)));
+        cov = (float*)c->d_lmm;
+    }
+    return mips_device(c, m, plan, cov, (hipStream_t)stream);
+}
+
+extern "C" int mi_lightmap_mips(mi_ctx* c, uint32_t width, uint32_t height, uint32_t channels, const float* image, const uint8_t* valid,
+                                uint32_t levels, float* out_mips, uint8_t* out_valid, float* out_coverage) {
+    const char* who = "mi_lightmap_mips";
+    const MipsArgs m{ width, height, channels, image, valid, levels, out_mips, out_valid, out_coverage };
+    MipPlan plan;
+    MI_TRY(check_mips_args(who, m, &plan));
+    if (!c) return fail(MI_ERR_INVALID, "ctx is NULL");
+    if (plan.levels == 1) return MI_OK;                // before any device call
+    if (c->tune.lmm_levels_per_launch != kMipFuse) mip_plan(width, height, levels, c->tune.lmm_levels_per_launch, &plan);
+    const size_t texels = (size_t)width * height, made = (size_t)plan.texels;
+    enum { kImage, kValid, kMips, kMipValid, kCov, kScratch };
+    // without out_coverage the planes still have to exist on the device: a column that is neither uploaded nor fetched
+    static const char kScratchColumn = 0;
+    const StageColumn cols[] = { { image, texels * channels * sizeof(float), Stage::kIn }, { valid, texels, Stage::kIn },
+                                 { out_mips, made * channels * sizeof(float), Stage::kOut }, { out_valid, made, Stage::kOut },
+                                 { out_coverage, made * sizeof(float), Stage::kOut },
+                                 { out_coverage ? nullptr : &kScratchColumn, made * sizeof(float), Stage::kDevice } };
+    return staged(c, cols, [&](void* const* d) -> int {
+        MipsArgs dm = m;
+        dm.image = (const float*)d[kImage]; dm.valid = (const uint8_t*)d[kValid]; dm.out_mips = (float*)d[kMips];
+        dm.out_valid = (uint8_t*)d[kMipValid];
+        return mips_device(c, dm, plan, (float*)(d[kCov] ? d[kCov] : d[kScratch]), c->stream);
+    });
+}
+
+// The trilinear lookups.  One argument record serves both calls: channels == 0 is the fused SH form.
+struct LodArgs {
+    uint32_t width, height, channels; const float* image; const uint8_t* valid; uint32_t levels; const float* mips; const uint8_t* mip_valid;
+    uint32_t n; const float* uv; const float* normals; const float* lod; uint32_t flags; float* out; float* out_weight;
+};
+
+// Checked before the context, nothing is launched
+static int check_lod_args(const char* who, const LodArgs& l, MipPlan* plan) {
+    const bool sh = l.channels == 0;
+    if (!l.image || !l.uv || !l.lod || !l.out || (sh && !l.normals))
+        return fail(MI_ERR_INVALID, sh ? "%s: sh, uv, normals, lod and out_irradiance are required" : "%s: image, uv, lod and out are required", who);
+    if (l.width == 0 || l.width > 32768u || l.height == 0 || l.height > 32768u)
+        return fail(MI_ERR_INVALID, "%s: width %u / height %u is not in 1 .. 32768", who, l.width, l.height);
+    if (!sh && l.channels != 3 && l.channels != (uint32_t)kShFloats) return fail(MI_ERR_INVALID, "%s: channels %u is not 3 or 27", who, l.channels);
+    if (!mip_plan(l.width, l.height, l.levels, kMipFuse, plan))
+        return fail(MI_ERR_INVALID, "%s: levels %u is above the full chain of %u x %u, %u", who, l.levels, l.width, l.height,
+                    mip_full_chain(l.width, l.height));
+    if (plan->levels > 1 && !l.mips) return fail(MI_ERR_INVALID, "%s: mips is required with %u levels", who, plan->levels);
+    if (l.flags & MI_LS_NEAREST) return fail(MI_ERR_INVALID, "%s: MI_LS_NEAREST is refused: nearest addressing has no mips", who);
+    if (l.flags) return fail(MI_ERR_INVALID, "%s: unknown flag bits 0x%x", who, l.flags);
+    return MI_OK;
+}
+
+static int lod_device(mi_ctx* c, const LodArgs& l, const MipPlan& plan, hipStream_t stream) {
+    LmlLodArgs a{};
+    a.image = l.image; a.valid = l.valid; a.mips = l.mips; a.mip_valid = l.mip_valid; a.uv = l.uv; a.lod = l.lod; a.normals = l.normals;
+    a.out = l.out; a.out_weight = l.out_weight; a.levels = plan.levels; a.n = l.n;
+    for (uint32_t k = 0; k < plan.levels; k++) { a.off[k] = plan.level[k].offset; a.lw[k] = plan.level[k].width; a.lh[k] = plan.level[k].height; }
+    return timed(c, stream, [&]() -> int {
+        HIP_TRY(launch_lml_sample_lod(a, l.channels, stream));
+        return MI_OK;
+    });
+}
+
+static int lod_entry_device(const char* who, mi_ctx* c, const LodArgs& l, void* stream) {
+    MipPlan plan;
+    MI_TRY(check_lod_args(who, l, &plan));
+    if (!c) return fail(MI_ERR_INVALID, "ctx is NULL");
+    const size_t texels = (size_t)l.width * l.height, made = (size_t)plan.texels;
+    const size_t in_c = l.channels ? l.channels : (uint32_t)kShFloats, out_c = l.channels ? l.channels : 3u;
+    MI_TRY(check_no_overlap(who, { { l.out, (size_t)l.n * out_c * sizeof(float), l.channels ? "out" : "out_irradiance" },
+                                   { l.out_weight, (size_t)l.n * sizeof(float), "out_weight" } },
+                            { { l.image, texels * in_c * sizeof(float) }, { l.valid, texels }, { l.mips, made * in_c * sizeof(float) },
+                              { l.mip_valid, made }, { l.uv, (size_t)l.n * 2 * sizeof(float) }, { l.lod, (size_t)l.n * sizeof(float) },
+                              { l.normals, (size_t)l.n * 3 * sizeof(float) } }));
+    if (l.n == 0) return MI_OK;
+    HIP_TRY(hipSetDevice(c->device));
+    return lod_device(c, l, plan, (hipStream_t)stream);
+}
+
+static int lod_entry_host(const char* who, mi_ctx* c, const LodArgs& l) {
+    MipPlan plan;
+    MI_TRY(check_lod_args(who, l, &plan));
+    if (!c) return fail(MI_ERR_INVALID, "ctx is NULL");
+    if (l.n == 0) return MI_OK;                // before any device call
+    const size_t texels = (size_t)l.width * l.height, made = (size_t)plan.texels;
+    const size_t in_c = l.channels ? l.channels : (uint32_t)kShFloats, out_c = l.channels ? l.channels : 3u;
+    const bool chain = plan.levels > 1;
+    enum { kImage, kValid, kMips, kMipValid, kUv, kLod, kNormals, kOut, kWeight };
+    const StageColumn cols[] = { { l.image, texels * in_c * sizeof(float), Stage::kIn }, { l.valid, texels, Stage::kIn },
+                                 { chain ? l.mips : nullptr, made * in_c * sizeof(float), Stage::kIn },
+                                 { chain ? l.mip_valid : nullptr, made, Stage::kIn },
+                                 { l.uv, (size_t)l.n * 2 * sizeof(float), Stage::kIn }, { l.lod, (size_t)l.n * sizeof(float), Stage::kIn },
+                                 { l.normals, (size_t)l.n * 3 * sizeof(float), Stage::kIn },
+                                 { l.out, (size_t)l.n * out_c * sizeof(float), Stage::kOut }, { l.out_weight, (size_t)l.n * sizeof(float), Stage::kOut } };
+    return staged(c, cols, [&](void* const* d) -> int {
+        LodArgs dl = l;
+        dl.image = (const float*)d[kImage]; dl.valid = (const uint8_t*)d[kValid]; dl.mips = (const float*)d[kMips];
+        dl.mip_valid = (const uint8_t*)d[kMipValid]; dl.uv = (const float*)d[kUv]; dl.lod = (const float*)d[kLod];
+        dl.normals = (const float*)d[kNormals]; dl.out = (float*)d[kOut]; dl.out_weight = (float*)d[kWeight];
+        return lod_device(c, dl, plan, c->stream);
+    });
+}
+
+extern "C" int mi_lightmap_sample_lod_device(mi_ctx* c, uint32_t width, uint32_t height, uint32_t channels, const float* image,
+                                             const uint8_t* valid, uint32_t levels, const float* mips, const uint8_t* mip_valid, uint32_t n,
+                                             const float* uv, const float* lod, uint32_t flags, float* out, float* out_weight, void* stream) {
+    if (channels == 0) return fail(MI_ERR_INVALID, "mi_lightmap_sample_lod_device: channels 0 is not 3 or 27");
+    return lod_entry_device("mi_lightmap_sample_lod_device", c, { width, height, channels, image, valid, levels, mips, mip_valid, n, uv, nullptr,
+                            lod, flags, out, out_weight }, stream);
+}
+
+extern "C" int mi_lightmap_sample_lod(mi_ctx* c, uint32_t width, uint32_t height, uint32_t channels, const float* image, const uint8_t* valid,
+                                      uint32_t levels, const float* mips, const uint8_t* mip_valid, uint32_t n, const float* uv,
+                                      const float* lod, uint32_t flags, float* out, float* out_weight) {
+    if (channels == 0) return fail(MI_ERR_INVALID, "mi_lightmap_sample_lod: channels 0 is not 3 or 27");
+    return lod_entry_host("mi_lightmap_sample_lod", c, { width, height, channels, image, valid, levels, mips, mip_valid, n, uv, nullptr, lod,
+                          flags, out, out_weight });
+}
+
+extern "C" int mi_lightmap_sh_sample_lod_device(mi_ctx* c, uint32_t width, uint32_t height, const float* sh, const uint8_t* valid,
+                                                uint32_t levels, const float* mips, const uint8_t* mip_valid, uint32_t n, const float* uv,
+                                                const float* normals, const float* lod, uint32_t flags, float* out_irradiance,
+                                                float* out_weight, void* stream) {
+    return lod_entry_device("mi_lightmap_sh_sample_lod_device", c, { width, height, 0, sh, valid, levels, mips, mip_valid, n, uv, normals, lod,
+                            flags, out_irradiance, out_weight }, stream);
+}
+
+extern "C" int mi_lightmap_sh_sample_lod(mi_ctx* c, uint32_t width, uint32_t height, const float* sh, const uint8_t* valid, uint32_t levels,
+                                         const float* mips, const uint8_t* mip_valid, uint32_t n, const float* uv, const float* normals,
+                                         const float* lod, uint32_t flags, float* out_irradiance, float* out_weight) {
+    return lod_entry_host("mi_lightmap_sh_sample_lod", c, { width, height, 0, sh, valid, levels, mips, mip_valid, n, uv, normals, lod, flags,
+                          out_irradiance, out_weight });
 }
 
 // ------------------------------------------------------------------ variance-guided lightmap finishing

@@ -468,6 +468,37 @@ struct LmlArgs {
     uint32_t nearest;                // MI_LS_NEAREST
 };
 
+// ---- lightmap mips (mi_lightmap_mips, mi_lightmap_sample_lod, mi_lightmap_sh_sample_lod; pt_kernels.hip "lmm_*", "lml_*_lod") ----
+// The layout is render_plan.cpp mip_plan's: levels 1 .. L - 1 tightly one after the other, offsets in texels.
+constexpr uint32_t kMipMaxLevels = 16;   // the full chain of 32768 texels
+constexpr uint32_t kMipFuse = 5;         // the levels one launch of lmm_reduce writes from a 32 x 32 tile: 16, 8, 4, 2, 1 squared
+// tracing.py lightmap_mips (lmm_reduce<3>, lmm_reduce<27>): one block per 32 x 32 tile of the level read, `count` levels written
+struct LmmArgs {
+    const float*   src;              // the level read, [src_h][src_w][C]
+    const uint8_t* src_valid;        // level 0 only: [H][W] or nullptr = all valid
+    const float*   src_cov;          // levels >= 1: the coverage of the level read; nullptr: level 0, whose coverage is its mask's
+    float*         mips;             // levels 1 .. L - 1, tightly: [texels][C]
+    uint8_t*       mip_valid;        // [texels] or nullptr
+    float*         mip_cov;          // [texels]
+    uint64_t       off[kMipFuse];    // where the levels written start, in texels
+    uint32_t src_w, src_h, count, tiles_x;
+};
+// tracing.py lightmap_sample_lod (lml_sample_lod<3>, lml_sample_lod<27>) and lightmap_sh_sample_lod (lml_sh_sample_lod): one lane per point
+struct LmlLodArgs {
+    const float*   image;            // level 0, [H][W][C]
+    const uint8_t* valid;            // level 0's mask or nullptr = all valid
+    const float*   mips;             // levels 1 .. L - 1 (nullptr when levels == 1)
+    const uint8_t* mip_valid;        // their masks or nullptr = every texel of every level valid
+    const float*   uv;               // [n][2]
+    const float*   lod;              // [n]
+    const float*   normals;          // [n][3] (lml_sh_sample_lod)
+    float*         out;              // [n][C] (lml_sample_lod<C>), [n][3] (lml_sh_sample_lod)
+    float*         out_weight;       // [n] or nullptr
+    uint64_t       off[kMipMaxLevels];                        // level l starts at texel off[l] of mips (off[0] unused)
+    uint32_t       lw[kMipMaxLevels], lh[kMipMaxLevels];      // the levels' sizes
+    uint32_t levels, n;
+};
+
 // ---- variance-guided lightmap finishing (mi_lightmap_finish_var; pt_kernels.hip "lmv_*") ----
 // One pass of tracing.py lightmap_finish_var: lmv_init (the variance of the mean per texel from the bake's mean and second moments),
 // lmv_blur (the colour weight's denominator per texel from the 3 x 3 blur of the variance) or lmv_atrous (one filter level of the image

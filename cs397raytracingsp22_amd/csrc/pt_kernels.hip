@@ -4583,6 +4583,196 @@ __global__ __launch_bounds__(kBlock) void lml_sh_sample(const LmlArgs a) {
     if (a.out_weight) a.out_weight[i] = sw;
 }
 
+// ---------------------------------------------------------------- lightmap mips (mi_lightmap_mips)
+// tracing.py lightmap_mips on the device.  One block takes a 32 x 32 tile of the level it reads (kTile, the tile of the atlas and finish
+// kernels) and writes up to kMipFuse levels from it: 16, 8, 4, 2 and 1 squared.  The first is made from global memory, one lane per
+// output texel; every further one from the level before, which the block keeps in LDS as C + 1 planes of 256 floats (the C values and
+// the coverage of a texel at [plane][16 y + x]: 28 KB at 27 channels).  A level is stored to global memory as it is made.  A child is
+// weighed the same way whether it comes from LDS or from global memory (c * t, the sums from +0 in dy-outer, dx-inner order, one division),
+// so the bits depend on neither the tiling nor the number of launches.  No atomics, nothing summed across lanes, 64-bit indices; a
+// child that takes no part (outside its level, or coverage not > 0) is not read.  A 27-float record is only 4-byte aligned: read float
+// by float, as lml_sample<27> reads its taps.
+// LDS layout: planes, so that the lanes of a wave write consecutive words.  The readers of a further level step two texels per lane
+// and 32 words per row: the 32 lanes of a half-wave fall on 8 banks, four rows each (4-way) — on the 64, 16, 4 and 1 lanes of levels that
+// hold 1/4, 1/16, ... of the first level's work, whose global reads are what the launch waits for.  The level is written in place:
+// the children are in registers before the barrier that precedes the store.
+template <int C> __global__ __launch_bounds__(kBlock) void lmm_reduce(const LmmArgs a) {
+    __shared__ float tile[(C + 1) * kBlock];
+    const uint32_t tx = blockIdx.x % a.tiles_x, ty = blockIdx.x / a.tiles_x;
+    const int lane = (int)threadIdx.x;
+    int w = (int)a.src_w, h = (int)a.src_h;                       // the level being read
+    for (uint32_t j = 0; j < a.count; j++) {
+        const int side = 16 >> j;                                  // this block's part of the level being made is side x side
+        const int nw = (w + 1) >> 1, nh = (h + 1) >> 1;
+        const int lx = lane & (side - 1), ly = lane >> (4 - (int)j);
+        const int x = (int)tx * side + lx, y = (int)ty * side + ly;
+        const bool live = ly < side && x < nw && y < nh;
+        float acc[C], sc = 0.0f;
+#pragma unroll
+        for (int k = 0; k < C; k++) acc[k] = 0.0f;
+        if (live) {
+#pragma unroll
+            for (int dy = 0; dy < 2; dy++)
+#pragma unroll
+                for (int dx = 0; dx < 2; dx++) {
+                    const int cx = 2 * x + dx, cy = 2 * y + dy;
+                    if (cx >= w || cy >= h) continue;
+                    if (j == 0) {
+                        const size_t q = (size_t)cy * (size_t)w + (size_t)cx;
+                        const float c = a.src_cov ? a.src_cov[q] : (!a.src_valid || a.src_valid[q] != 0) ? 1.0f : 0.0f;
+                        if (!(c > 0.0f)) continue;
+                        const float* t = a.src + q * C;
+#pragma unroll
+                        for (int k = 0; k < C; k++) acc[k] = acc[k] + c * t[k];
+                        sc = sc + c;
+                    } else {
+                        const int q = (2 * ly + dy) * 16 + 2 * lx + dx;
+                        const float c = tile[C * kBlock + q];
+                        if (!(c > 0.0f)) continue;
+#pragma unroll
+                        for (int k = 0; k < C; k++) acc[k] = acc[k] + c * tile[k * kBlock + q];
+                        sc = sc + c;
+                    }
+                }
+            if (sc > 0.0f) {
+#pragma unroll
+                for (int k = 0; k < C; k++) acc[k] = acc[k] / sc;
+            }
+            sc = sc * 0.25f;                                       // the coverage of the texel made
+            const size_t p = (size_t)a.off[j] + (size_t)y * (size_t)nw + (size_t)x;
+            float* o = a.mips + p * C;
+#pragma unroll
+            for (int k = 0; k < C; k++) o[k] = acc[k];
+            a.mip_cov[p] = sc;
+            if (a.mip_valid) a.mip_valid[p] = sc > 0.0f ? 1 : 0;
+        }
+        if (j + 1 < a.count) {                                     // (uniform over the block: both barriers are reached by every lane)
+            if (j > 0) __syncthreads();                            // every reader of the level before is done
+            if (live) {
+#pragma unroll
+                for (int k = 0; k < C; k++) tile[k * kBlock + ly * 16 + lx] = acc[k];
+                tile[C * kBlock + ly * 16 + lx] = sc;
+            }
+            __syncthreads();
+        }
+        w = nw; h = nh;
+    }
+}
+
+// ---------------------------------------------------------------- trilinear lightmap lookup (mi_lightmap_sample_lod, mi_lightmap_sh_sample_lod)
+// tracing.py lightmap_sample_lod and lightmap_sh_sample_lod on the device: the lookup above over two levels of a mip chain.  One lane per
+// point, the helpers' operations in the helpers' order; every address is made from indices clamped to their level, whatever the uv,
+// the lod, the normals and the texels hold; a level or a tap that takes no part is not read.  (lml_sample and lml_sh_sample do not go
+// through these functions: their code objects stay as they were.)
+
+// One axis at level l: n0 texels at level 0, s = 2^-l (exact), n texels at level l; lml_axis' clamp and index expressions
+__device__ __forceinline__ void lml_axis_lod(float t, int n0, float s, int n, int (&i)[2], float (&w)[2]) {
+    float g = (t * (float)n0) * s - 0.5f;
+    g = fminf(fmaxf(g, 0.0f), (float)(n - 1));
+    const int i0 = max(min((int)floorf(g), max(n - 2, 0)), 0);
+    const float f = g - (float)i0;
+    i[0] = i0; i[1] = min(i0 + 1, n - 1);
+    w[0] = 1.0f - f; w[1] = f;
+}
+// The two levels of a point and their weights: fmaxf sends a NaN to 0
+__device__ __forceinline__ void lml_levels(float lod, int L, int (&l)[2], float (&w)[2]) {
+    const float lam = fminf(fmaxf(lod, 0.0f), (float)(L - 1));
+    const int la = max(min((int)floorf(lam), max(L - 2, 0)), 0);
+    const float f = lam - (float)la;
+    l[0] = la; l[1] = min(la + 1, L - 1);
+    w[0] = 1.0f - f; w[1] = f;
+}
+// The tap loop of one level, written once: tap(texels of the level, texel index, weight) for every tap that takes part, dy outer, dx inner
+template <int C, class Tap> __device__ __forceinline__ void lml_level_taps(const LmlLodArgs& a, int l, float wl, float u, float v, Tap tap) {
+    const int W = (int)a.lw[l], H = (int)a.lh[l];
+    const float s = __uint_as_float((uint32_t)(127 - l) << 23);                  // 2^-l, l <= 15
+    const float* texels = l == 0 ? a.image : a.mips + (size_t)a.off[l] * C;
+    const uint8_t* valid = l == 0 ? a.valid : a.mip_valid ? a.mip_valid + (size_t)a.off[l] : nullptr;
+    int ix[2], iy[2];
+    float wx[2], wy[2];
+    lml_axis_lod(u, (int)a.lw[0], s, W, ix, wx);
+    lml_axis_lod(1.0f - v, (int)a.lh[0], s, H, iy, wy);
+#pragma unroll
+    for (int dy = 0; dy < 2; dy++)
+#pragma unroll
+        for (int dx = 0; dx < 2; dx++) {
+            const float w = wl * (wx[dx] * wy[dy]);
+            const size_t q = (size_t)iy[dy] * (size_t)W + (size_t)ix[dx];
+            if (!(w > 0.0f) || (valid && valid[q] == 0)) continue;
+            tap(texels, q, w);
+        }
+}
+
+// lightmap_sample_lod: C + 1 accumulators over the up to eight taps
+template <int C> __global__ __launch_bounds__(kBlock) void lml_sample_lod(const LmlLodArgs a) {
+    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= a.n) return;
+    const float u = a.uv[2 * (size_t)i], v = a.uv[2 * (size_t)i + 1];
+    int lv[2];
+    float wl[2];
+    lml_levels(a.lod[i], (int)a.levels, lv, wl);
+    float acc[C], sw = 0.0f;
+#pragma unroll
+    for (int k = 0; k < C; k++) acc[k] = 0.0f;
+    for (int side = 0; side < 2; side++) {
+        if (!(wl[side] > 0.0f)) continue;
+        lml_level_taps<C>(a, lv[side], wl[side], u, v, [&](const float* texels, size_t q, float w) {
+            const float* t = texels + q * C;
+#pragma unroll
+            for (int k = 0; k < C; k++) acc[k] = acc[k] + w * t[k];
+            sw = sw + w;
+        });
+    }
+    if (sw > 0.0f) {
+#pragma unroll
+        for (int k = 0; k < C; k++) acc[k] = acc[k] / sw;
+    }
+    float* o = a.out + (size_t)i * C;
+#pragma unroll
+    for (int k = 0; k < C; k++) o[k] = acc[k];
+    if (a.out_weight) a.out_weight[i] = sw;
+}
+
+// lightmap_sh_sample_lod: every tap's record becomes its irradiance e at the point's normal (lml_sh_sample's eval) before it is weighted
+__global__ __launch_bounds__(kBlock) void lml_sh_sample_lod(const LmlLodArgs a) {
+    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= a.n) return;
+    const float u = a.uv[2 * (size_t)i], v = a.uv[2 * (size_t)i + 1];
+    const float nx = a.normals[3 * (size_t)i], ny = a.normals[3 * (size_t)i + 1], nz = a.normals[3 * (size_t)i + 2];
+    float E[3] = { 0.0f, 0.0f, 0.0f }, sw = 0.0f;
+    if (lmf_covered(nx, ny, nz)) {                             // an all-zero normal: +0 and weight 0
+        const float K1 = (float)1.0233267079464885, K2 = (float)0.8580855308097834;
+        const float K[9] = { (float)0.886226925452758, K1, K1, K1, K2, K2, (float)0.24770795610037571, K2, (float)0.4290427654048917 };
+        const float len = sqrtf((nx * nx + ny * ny) + nz * nz);
+        const float x = nx / len, y = ny / len, z = nz / len;
+        const float b[9] = { 1.0f, y, z, x, x * y, y * z, 3.0f * (z * z) - 1.0f, x * z, x * x - y * y };
+        int lv[2];
+        float wl[2];
+        lml_levels(a.lod[i], (int)a.levels, lv, wl);
+        for (int side = 0; side < 2; side++) {
+            if (!(wl[side] > 0.0f)) continue;
+            lml_level_taps<kShFloats>(a, lv[side], wl[side], u, v, [&](const float* texels, size_t q, float w) {
+                const float* sh = texels + q * kShFloats;
+#pragma unroll
+                for (int c = 0; c < 3; c++) {
+                    float s = b[0] * (sh[c] * K[0]);
+#pragma unroll
+                    for (int k = 1; k < 9; k++) s = s + b[k] * (sh[3 * k + c] * K[k]);
+                    E[c] = E[c] + w * s;
+                }
+                sw = sw + w;
+            });
+        }
+        if (sw > 0.0f) {
+#pragma unroll
+            for (int c = 0; c < 3; c++) E[c] = E[c] / sw;
+        }
+    }
+#pragma unroll
+    for (int c = 0; c < 3; c++) a.out[3 * (size_t)i + c] = E[c];
+    if (a.out_weight) a.out_weight[i] = sw;
+}
+
 // ---------------------------------------------------------------- launch wrappers
 // One lane per item (a texel, a probe, a point, a list entry): ceil(n / kBlock) blocks of `kernel`, which tests its index against n itself
 template <class Kernel, class... Args> static hipError_t launch_per_item(Kernel kernel, size_t n, hipStream_t stream, const Args&... args) {
@@ -4611,6 +4801,24 @@ hipError_t launch_lml_sample(const LmlArgs& a, uint32_t channels, hipStream_t st
     if (channels == 0) return launch_per_item(lml_sh_sample, a.n, stream, a);
     if (channels == 3) return launch_per_item(lml_sample<3>, a.n, stream, a);
     if (channels == kShFloats) return launch_per_item(lml_sample<kShFloats>, a.n, stream, a);
+    return hipErrorInvalidValue;
+}
+// lightmap mips: one block per 32 x 32 tile of the level read; `channels` 3 or 27
+hipError_t launch_lmm_reduce(const LmmArgs& a, uint32_t channels, hipStream_t stream) {
+    const uint32_t tiles_y = (a.src_h + kTile - 1) / kTile;
+    if (a.count == 0 || a.count > kMipFuse || a.tiles_x != (a.src_w + kTile - 1) / kTile) return hipErrorInvalidValue;
+    const dim3 grid(a.tiles_x * tiles_y), block(kBlock);
+    if (channels == 3) hipLaunchKernelGGL(lmm_reduce<3>, grid, block, 0, stream, a);
+    else if (channels == kShFloats) hipLaunchKernelGGL(lmm_reduce<kShFloats>, grid, block, 0, stream, a);
+    else return hipErrorInvalidValue;
+    return hipGetLastError();
+}
+// trilinear lightmap lookup: `channels` floats per texel out (3 or 27), or 0: the fused SH form
+hipError_t launch_lml_sample_lod(const LmlLodArgs& a, uint32_t channels, hipStream_t stream) {
+    if (a.levels == 0 || a.levels > kMipMaxLevels) return hipErrorInvalidValue;
+    if (channels == 0) return launch_per_item(lml_sh_sample_lod, a.n, stream, a);
+    if (channels == 3) return launch_per_item(lml_sample_lod<3>, a.n, stream, a);
+    if (channels == kShFloats) return launch_per_item(lml_sample_lod<kShFloats>, a.n, stream, a);
     return hipErrorInvalidValue;
 }
 // The plain form's level.  lmf_atrous stages through LDS when `lds`; a window above 64 KB needs the opt-in, which

@@ -450,4 +450,26 @@ FinishPlan finish_plan(uint32_t levels, uint32_t dilate, bool want_valid, bool w
     return plan;
 }
 
+uint32_t mip_full_chain(uint32_t width, uint32_t height) {
+    uint32_t levels = 1;
+    for (uint32_t n = std::max(width, height); n > 1; n = (n + 1) >> 1) levels++;
+    return levels;
+}
+
+bool mip_plan(uint32_t width, uint32_t height, uint32_t levels, uint32_t per_launch, MipPlan* plan) {
+    if (width == 0 || width > 32768u || height == 0 || height > 32768u) return false;
+    const uint32_t full = mip_full_chain(width, height);
+    if (levels > full) return false;
+    MipPlan p{};
+    p.levels = levels ? levels : full;
+    for (uint32_t l = 0; l < p.levels; l++) {
+        p.level[l] = { mip_extent(width, l), mip_extent(height, l), p.texels };
+        if (l) p.texels += (uint64_t)p.level[l].width * p.level[l].height;
+    }
+    per_launch = std::min(std::max(per_launch, 1u), kMipFuse);
+    for (uint32_t src = 0; src + 1 < p.levels; src += per_launch) p.launches.push_back({ src, std::min(per_launch, p.levels - 1 - src) });
+    *plan = p;
+    return true;
+}
+
 }  // namespace pt

@@ -1,10 +1,11 @@
 // render_plan.hpp — the host-side decisions of a render: camera validation, the tile grid of the partition, the camera
 // constants, the primary-ray tile masks, which meshes are walked two-stage, the wavefront pipeline's batch, and its pass schedule:
 // what is fixed for a render (pass_schedule), whether a pass may be launched before the previous header has arrived (pass_gate), and
-// its grids, parts and in-launch rounds (plan_pass); and the buffers every launch of a lightmap finish reads and writes (finish_plan).
+// its grids, parts and in-launch rounds (plan_pass); the buffers every launch of a lightmap finish reads and writes (finish_plan);
+// and the layout and launches of a lightmap's mip chain (mip_plan).
 // Host code only: no HIP call, no context; mi_rt.cpp plans with these, then launches.  All of it runs on the CPU:
 // tests/test_render_plan_host.py, tests/test_pass_schedule_host.py and tests/test_finish_plan_host.py, through
-// tests/cpp/render_plan_shim.cpp; the launches a schedule leads to are pinned by tests/test_gpu_walkers.py (golden/pass_schedule_counts.json).
+// tests/cpp/render_plan_shim.cpp (mip_plan: tests/test_lightmap_mips_host.py through tests/cpp/mip_plan_shim.cpp); the launches a schedule leads to are pinned by tests/test_gpu_walkers.py (golden/pass_schedule_counts.json).
 #pragma once
 #include <cstdint>
 #include <vector>
@@ -120,5 +121,22 @@ struct FinishPass {
 };
 struct FinishPlan { uint32_t copy; FinishMask mask_init; FinishVar var_init; std::vector<FinishPass> passes; };
 FinishPlan finish_plan(uint32_t levels, uint32_t dilate, bool want_valid, bool with_var, bool want_var);
+
+// ---- the lightmap mip chain's layout and launches (mi_lightmap_mips, the _lod lookups; tracing.py lightmap_mip_layout is the same rule)
+// `levels` counts level 0; 0 asks for the full chain, mip_full_chain(W, H) = 1 + ceil(log2(max(W, H))) levels (16 at 32768), whose last
+// level is 1 x 1.  Level l is mip_extent(W, l) x mip_extent(H, l) = ceil(W / 2^l) x ceil(H / 2^l): texel (x, y) of level l covers the
+// level-0 texels [x 2^l, (x + 1) 2^l) x [y 2^l, (y + 1) 2^l) that lie inside the image, power of two or not.  Levels 1 .. L - 1 lie
+// tightly one after the other in one buffer: level[l].offset is where level l starts, in texels (level 0 is the image itself: offset 0).
+// launches: lmm_reduce reads level `src` and writes the `count` levels src + 1 .. src + count, at most per_launch (itself at most
+// kMipFuse, the levels a 32 x 32 tile reaches: 16, 8, 4, 2, 1); every level 1 .. L - 1 is written exactly once, in order, and a launch
+// reads the last level the one before wrote.  CPU tests: tests/test_lightmap_mips_host.py.
+// (kMipMaxLevels and kMipFuse: pt_device.h, beside the kernels' argument records)
+struct MipLevel { uint32_t width, height; uint64_t offset; };
+struct MipLaunch { uint32_t src, count; };
+struct MipPlan { uint32_t levels; uint64_t texels; MipLevel level[kMipMaxLevels]; std::vector<MipLaunch> launches; };
+inline uint32_t mip_extent(uint32_t n, uint32_t l) { return (n + (1u << l) - 1u) >> l; }
+uint32_t mip_full_chain(uint32_t width, uint32_t height);
+// false: width or height is not in 1 .. 32768 or `levels` is above the full chain (plan is left alone)
+bool mip_plan(uint32_t width, uint32_t height, uint32_t levels, uint32_t per_launch, MipPlan* plan);
 
 }  // namespace pt

@@ -481,7 +481,109 @@ struct Scene : Intersectable {                         // tracing.rs:213-218; `i
         return out;
     }
 
+    // The mip chain's layout (include/mi_rt.h "lightmap mips"): {width, height, offset in texels} of levels 0 .. levels - 1, ceil halving,
+    // levels 1 .. tightly one after the other (level 0 is the image itself: offset 0); `levels` 0 is the full chain.
+    struct MipLevel { uint32_t width, height; size_t offset; };
+    static std::vector<MipLevel> lightmap_mip_layout(uint32_t width, uint32_t height, uint32_t levels = 0) {
+        uint32_t full = 1;
+        for (uint32_t n = std::max(width, height); n > 1; n = (n + 1) >> 1) full++;
+        if (width == 0 || width > 32768u || height == 0 || height > 32768u || levels > full)
+            throw std::runtime_error("mi_rt: width and height must be in 1 .. 32768 and levels at most the full chain");
+        std::vector<MipLevel> out;
+        size_t off = 0;
+        for (uint32_t l = 0; l < (levels ? levels : full); l++) {
+            const uint32_t w = (width + (1u << l) - 1) >> l, h = (height + (1u << l) - 1) >> l;
+            out.push_back({ w, h, off });
+            if (l) off += (size_t)w * h;
+        }
+        return out;
+    }
+
+    // The coverage-aware mip chain of a finished lightmap through mi_lightmap_mips: image [H][W][channels], channels 3 or 27, `valid`
+    // empty (every texel takes part) or finish_lightmap's mask, `levels` counting level 0 (0: the full chain).  Returns levels 1 ..
+    // tightly packed as lightmap_mip_layout lays them out; `mip_valid` and `coverage` take the masks and the valid fraction of every
+    // texel's footprint.  Needs no scene: a static member.
+    static std::vector<float> lightmap_mips(const std::vector<float>& image, const std::vector<uint8_t>& valid, uint32_t width, uint32_t height,
+                                            uint32_t channels, uint32_t levels = 0, std::vector<uint8_t>* mip_valid = nullptr,
+                                            std::vector<float>* coverage = nullptr, int device = 0) {
+        const size_t texels = (size_t)width * height;
+        if (image.size() != texels * channels || (!valid.empty() && valid.size() != texels))
+            throw std::runtime_error("mi_rt: image must be [H][W][channels] and valid empty or [H][W]");
+        const size_t made = mip_texels(width, height, levels);
+        std::vector<float> mips(std::max<size_t>(made, 1) * channels);
+        if (mip_valid) mip_valid->resize(std::max<size_t>(made, 1));
+        if (coverage) coverage->resize(std::max<size_t>(made, 1));
+        mi_ctx* ctx = nullptr;
+        mi_check(mi_ctx_create(device, &ctx));
+        const int rc = mi_lightmap_mips(ctx, width, height, channels, image.data(), valid.empty() ? nullptr : valid.data(), levels, mips.data(),
+                                        mip_valid ? mip_valid->data() : nullptr, coverage ? coverage->data() : nullptr);
+        const std::string err = rc == MI_OK ? "" : mi_last_error();
+        mi_ctx_destroy(ctx);
+        if (rc != MI_OK) throw std::runtime_error("mi_rt: " + err);
+        mips.resize(made * channels);
+        if (mip_valid) mip_valid->resize(made);
+        if (coverage) coverage->resize(made);
+        return mips;
+    }
+
+    // Read a lightmap's mip chain at uv points and levels of detail through mi_lightmap_sample_lod: sample_lightmap's arguments with the
+    // chain lightmap_mips returned (`mips`, `mip_valid`: empty = every texel valid) and one `lod` per point; trilinear over the valid
+    // texels.  Returns [n][channels]; `weight` takes the weight sum per point.  Needs no scene: a static member.
+    static std::vector<float> sample_lightmap_lod(const std::vector<float>& image, const std::vector<uint8_t>& valid, uint32_t width,
+                                                  uint32_t height, uint32_t channels, uint32_t levels, const std::vector<float>& mips,
+                                                  const std::vector<uint8_t>& mip_valid, const std::vector<float>& uv,
+                                                  const std::vector<float>& lod, int device = 0, std::vector<float>* weight = nullptr) {
+        const size_t texels = (size_t)width * height, n = uv.size() / 2, made = mip_texels(width, height, levels);
+        if (image.size() != texels * channels || (!valid.empty() && valid.size() != texels) || uv.size() != n * 2 || lod.size() != n ||
+            mips.size() != made * channels || (!mip_valid.empty() && mip_valid.size() != made))
+            throw std::runtime_error("mi_rt: image must be [H][W][channels], valid empty or [H][W], mips and mip_valid the layout's, uv [n][2], lod [n]");
+        std::vector<float> out(n * channels);
+        if (weight) weight->resize(n);
+        if (n == 0) return out;                              // (an empty vector has no address to pass)
+        mi_ctx* ctx = nullptr;
+        mi_check(mi_ctx_create(device, &ctx));
+        const int rc = mi_lightmap_sample_lod(ctx, width, height, channels, image.data(), valid.empty() ? nullptr : valid.data(), levels,
+                                              mips.empty() ? nullptr : mips.data(), mip_valid.empty() ? nullptr : mip_valid.data(), (uint32_t)n,
+                                              uv.data(), lod.data(), 0u, out.data(), weight ? weight->data() : nullptr);
+        const std::string err = rc == MI_OK ? "" : mi_last_error();
+        mi_ctx_destroy(ctx);
+        if (rc != MI_OK) throw std::runtime_error("mi_rt: " + err);
+        return out;
+    }
+
+    // The irradiance of a directional lightmap's mip chain at uv points, their normals and levels of detail through
+    // mi_lightmap_sh_sample_lod: sample_lightmap_sh's arguments with the chain lightmap_mips returned at 27 channels and one `lod` per
+    // point.  Returns [n][3].  Needs no scene: a static member.
+    static std::vector<float> sample_lightmap_sh_lod(const std::vector<float>& sh, const std::vector<uint8_t>& valid, uint32_t width,
+                                                     uint32_t height, uint32_t levels, const std::vector<float>& mips,
+                                                     const std::vector<uint8_t>& mip_valid, const std::vector<float>& uv,
+                                                     const std::vector<float>& normals, const std::vector<float>& lod, int device = 0,
+                                                     std::vector<float>* weight = nullptr) {
+        const size_t texels = (size_t)width * height, n = uv.size() / 2, made = mip_texels(width, height, levels);
+        if (sh.size() != texels * 27 || (!valid.empty() && valid.size() != texels) || uv.size() != n * 2 || normals.size() != n * 3 ||
+            lod.size() != n || mips.size() != made * 27 || (!mip_valid.empty() && mip_valid.size() != made))
+            throw std::runtime_error("mi_rt: sh must be [H][W][9][3], valid empty or [H][W], mips and mip_valid the layout's, uv [n][2], normals [n][3], lod [n]");
+        std::vector<float> out(n * 3);
+        if (weight) weight->resize(n);
+        if (n == 0) return out;                              // (an empty vector has no address to pass)
+        mi_ctx* ctx = nullptr;
+        mi_check(mi_ctx_create(device, &ctx));
+        const int rc = mi_lightmap_sh_sample_lod(ctx, width, height, sh.data(), valid.empty() ? nullptr : valid.data(), levels,
+                                                 mips.empty() ? nullptr : mips.data(), mip_valid.empty() ? nullptr : mip_valid.data(), (uint32_t)n,
+                                                 uv.data(), normals.data(), lod.data(), 0u, out.data(), weight ? weight->data() : nullptr);
+        const std::string err = rc == MI_OK ? "" : mi_last_error();
+        mi_ctx_destroy(ctx);
+        if (rc != MI_OK) throw std::runtime_error("mi_rt: " + err);
+        return out;
+    }
+
 private:
+    // the texels of levels 1 .. of a chain
+    static size_t mip_texels(uint32_t width, uint32_t height, uint32_t levels) {
+        const std::vector<MipLevel> layout = lightmap_mip_layout(width, height, levels);
+        return layout.size() < 2 ? 0 : layout.back().offset + (size_t)layout.back().width * layout.back().height;
+    }
+
     // flatten -> context -> upload -> `call(ctx)` -> destroy; a failure surfaces as std::runtime_error carrying mi_last_error()
     template <class F> void with_context(int device, F call) const {
         SceneBuilder sb;

@@ -991,6 +991,274 @@ def lightmap_sh_sample(sh, uv, normals, valid=None, flags: int = 0):
     return np.ascontiguousarray(E.reshape(shape + (3,))), np.ascontiguousarray(sw.reshape(shape))
 
 
+# ---- lightmap mips: the coverage-aware pyramid of a finished lightmap and the trilinear lookup that reads it ----
+# The layout rule, written once: level l of a W x H image is _lmm_extent(W, l) x _lmm_extent(H, l) (ceil halving), the full chain has
+# _lmm_full(W, H) levels, and levels 1 .. L - 1 lie tightly one after the other in one buffer.
+_LMM_CHILDREN = ((0, 0), (0, 1), (1, 0), (1, 1))                  # (dy, dx): dy outer, dx inner
+
+
+def _lmm_extent(n, l):
+    """The extent of level l of an axis of n texels: ceil(n / 2^l), so that texel x of level l covers the level-0 texels
+    [x 2^l, (x + 1) 2^l) that lie inside the image"""
+    return (n + (1 << l) - 1) >> l
+
+
+def _lmm_full(W, H):
+    """The number of levels of the full chain, level 0 counted: 1 + ceil(log2(max(W, H))); its last level is 1 x 1"""
+    return 1 + (max(W, H) - 1).bit_length()
+
+
+def lightmap_mip_layout(width: int, height: int, levels: int = 0):
+    """The layout of a lightmap's mip chain, no GPU needed (render_plan.cpp mip_plan is the same rule): [(W_l, H_l, offset_l)] for
+    l = 0 .. L - 1.  `levels` counts level 0; 0 means the full chain, 1 + ceil(log2(max(W, H))) levels; more than that is refused.
+    W_l = (W + 2^l - 1) >> l and H_l likewise.  offset_l is where level l starts, in texels, in the buffers that hold levels
+    1 .. L - 1 tightly one after the other (mips [sum W_l H_l][C] f32, mip_valid u8 and mip_coverage f32 [sum W_l H_l]): the running sum
+    from level 1 on.  Level 0 is the image itself and is not copied: its offset is given as 0.  Raises ValueError."""
+    W, H, levels = int(width), int(height), int(levels)
+    if not (1 <= W <= 32768 and 1 <= H <= 32768):
+        raise ValueError(f"width and height must be in 1 .. 32768, got {W} x {H}")
+    if not (0 <= levels <= _lmm_full(W, H)):
+        raise ValueError(f"levels {levels} is not in 0 .. {_lmm_full(W, H)}, the full chain of {W} x {H}")
+    out, off = [], 0
+    for l in range(levels or _lmm_full(W, H)):
+        wl, hl = _lmm_extent(W, l), _lmm_extent(H, l)
+        out.append((wl, hl, off))
+        off += wl * hl if l else 0
+    return out
+
+
+def check_lightmap_mips(image, valid=None, levels: int = 0):
+    """Input checking of mi_lightmap_mips, no GPU needed: `image` [H, W, 3], [H, W, 27] or [H, W, 9, 3] with 1 <= W, H <= 32768; `valid`
+    None or [H, W] (0 = the texel takes no part); `levels` 0 (the full chain) or at most the full chain.  The values are not looked at.
+    Returns (image [H, W, C] f32, valid [H, W] uint8 or None, the layout of lightmap_mip_layout); raises ValueError."""
+    img = np.asarray(image, np.float32)
+    if img.ndim == 4 and img.shape[2:] == (9, 3):
+        img = img.reshape(img.shape[:2] + (27,))
+    if img.ndim != 3 or img.shape[2] not in (3, 27):
+        raise ValueError(f"image must be [H, W, 3], [H, W, 27] or [H, W, 9, 3], got {np.shape(image)}")
+    H, W = img.shape[:2]
+    layout = lightmap_mip_layout(W, H, levels)
+    v8 = None
+    if valid is not None:
+        v8 = np.ascontiguousarray(np.asarray(valid) != 0, np.uint8)
+        if v8.shape != (H, W):
+            raise ValueError(f"valid must be [{H}, {W}], got {v8.shape}")
+    return np.ascontiguousarray(img), v8, layout
+
+
+def _lmm_level(prev, cov, Wn, Hn):
+    """One level of the pyramid from the one before: prev [Hp, Wp, C] f32 and its coverage cov [Hp, Wp] f32 to
+    (out [Hn, Wn, C] f32, coverage [Hn, Wn] f32).  The rule of lightmap_mips, written once."""
+    f32 = np.float32
+    Hp, Wp, C = prev.shape
+    y, x = np.mgrid[0:Hn, 0:Wn]
+    acc = np.zeros((Hn, Wn, C), f32)
+    sc = np.zeros((Hn, Wn), f32)
+    for dy, dx in _LMM_CHILDREN:
+        cy, cx = 2 * y + dy, 2 * x + dx
+        inside = (cy < Hp) & (cx < Wp)
+        yi, xi = np.minimum(cy, Hp - 1), np.minimum(cx, Wp - 1)          # (an address for the gather: what lies outside takes no part)
+        c = cov[yi, xi]
+        take = inside & (c > 0)                    # a child that takes no part is not read: its texel may hold anything
+        acc = np.where(take[..., None], acc + c[..., None] * prev[yi, xi], acc)
+        sc = np.where(take, sc + c, sc)
+    return np.where((sc > 0)[..., None], acc / sc[..., None], f32(0.0)), sc * f32(0.25)
+
+
+def lightmap_mips(image, valid=None, levels: int = 0):
+    """The coverage-aware mip chain of a finished lightmap on the host (numpy only).  This is the DEFINITION of mi_lightmap_mips, which
+    equals it bit for bit.  Arguments as check_lightmap_mips.  Returns (mips, valids, coverage): three lists with one array per level
+    l = 0 .. L - 1, [H_l, W_l, C] f32, [H_l, W_l] uint8 and [H_l, W_l] f32, sizes as lightmap_mip_layout; level 0 is the image itself,
+    its mask (all ones for None) and cov_0 = 1.0 where valid, else 0.0.
+    Everything is f32, one rounding per operation, in the order written.  For l >= 1 texel (x, y) has the children (2y + dy, 2x + dx) of
+    level l - 1, dy outer, dx inner; a child takes part when it lies inside level l - 1 and its c = cov_(l-1) > 0, and one that does not
+    is not read.  acc = acc + c t and sc = sc + c from +0; out = acc / sc when sc > 0, else +0; cov_l = sc * 0.25; valid_l = cov_l > 0.
+    So cov_l is the fraction of the texel's level-0 footprint that is valid (exact while 4^l <= 2^24, l <= 12; rounded as written
+    beyond) and out the mean over exactly those texels.  Texels behind valid == 0 may hold anything; a non-finite valid texel spoils
+    only its own ancestors."""
+    img, v8, layout = check_lightmap_mips(image, valid, levels)
+    f32 = np.float32
+    ok = np.ones(img.shape[:2], bool) if v8 is None else v8 != 0
+    mips, valids, covs = [img], [ok.astype(np.uint8)], [np.where(ok, f32(1.0), f32(0.0))]
+    with np.errstate(all="ignore"):
+        for wl, hl, _ in layout[1:]:
+            out, cov = _lmm_level(mips[-1], covs[-1], wl, hl)
+            assert out.dtype == np.float32 and cov.dtype == np.float32
+            mips.append(np.ascontiguousarray(out))
+            covs.append(np.ascontiguousarray(cov))
+            valids.append((cov > 0).astype(np.uint8))
+    return mips, valids, covs
+
+
+def _lmm_pack(chain, dtype, tail=()):
+    """Levels 1 .. L - 1 of a per-level list as the one tight buffer the C calls take (at least one element long)"""
+    flat = [np.asarray(a, dtype).reshape((-1,) + tuple(tail)) for a in chain[1:]]
+    return np.ascontiguousarray(np.concatenate(flat)) if flat else np.zeros((1,) + tuple(tail), dtype)
+
+
+def check_lightmap_lod(chain, uv, lod, valid_chain=None, flags: int = 0, normals=None):
+    """Input checking of the trilinear lookups (mi_lightmap_sample_lod, mi_lightmap_sh_sample_lod), no GPU needed.  `chain` is the list
+    lightmap_mips returns first: level 0 ([H, W, 3], [H, W, 27] or [H, W, 9, 3], 1 <= W, H <= 32768) and levels 1 .. L - 1 of
+    lightmap_mip_layout's sizes, L at most the full chain.  `valid_chain` is None (everything valid) or a list of L masks of the
+    levels' sizes; entry 0 may be None, and entries 1 .. L - 1 are either all None or all given.  `uv` [..., 2]; `lod` a scalar or uv's
+    leading shape; `normals` None or [..., 3] with uv's leading shape; `flags` must be 0: abi.MI_LS_NEAREST is refused (nearest
+    addressing is the reference's, and the reference has no mips).  The values are not looked at.  Returns (levels [L] of [H_l, W_l, C]
+    f32, masks [L] of bool [H_l, W_l] or None, uv [n, 2] f32, lod [n] f32, normals [n, 3] f32 or None, leading shape); raises
+    ValueError."""
+    if not isinstance(chain, (list, tuple)) or len(chain) == 0:
+        raise ValueError("chain must be a list of levels, level 0 first")
+    flags = int(flags)
+    if flags & abi.MI_LS_NEAREST:
+        raise ValueError("MI_LS_NEAREST is refused: the reference's nearest addressing has no mips")
+    if flags:
+        raise ValueError(f"unknown flag bits {flags:#x}")
+    img, T, _, _, N, shape = check_lightmap_lookup(chain[0], uv, None, 0, normals)
+    H, W, ch = img.shape
+    if len(chain) > _lmm_full(W, H):
+        raise ValueError(f"{len(chain)} levels are more than the full chain of {W} x {H}, {_lmm_full(W, H)}")
+    layout = lightmap_mip_layout(W, H, len(chain))
+    levels = [img]
+    for l in range(1, len(chain)):
+        a = np.asarray(chain[l], np.float32)
+        wl, hl, _ = layout[l]
+        if a.shape[:2] != (hl, wl) or a.size != hl * wl * ch:
+            raise ValueError(f"level {l} must be [{hl}, {wl}, {ch}], got {a.shape}")
+        levels.append(np.ascontiguousarray(a.reshape(hl, wl, ch)))
+    masks = [None] * len(chain)
+    if valid_chain is not None:
+        if not isinstance(valid_chain, (list, tuple)) or len(valid_chain) != len(chain):
+            raise ValueError(f"valid_chain must be None or a list of {len(chain)} masks")
+        given = [v is not None for v in valid_chain[1:]]
+        if any(given) and not all(given):
+            raise ValueError("the masks of levels 1 .. L - 1 are either all None or all given")
+        for l, v in enumerate(valid_chain):
+            if v is None:
+                continue
+            wl, hl, _ = layout[l]
+            m = np.asarray(v) != 0
+            if m.shape != (hl, wl):
+                raise ValueError(f"mask {l} must be [{hl}, {wl}], got {m.shape}")
+            masks[l] = np.ascontiguousarray(m)
+    D = np.asarray(lod, np.float32)
+    if D.ndim and D.shape != shape:
+        raise ValueError(f"lod must be a scalar or {shape}, got {D.shape}")
+    D = np.ascontiguousarray(np.broadcast_to(D, shape).reshape(-1))
+    return levels, masks, T, D, N, shape
+
+
+def _lod_buffers(levels, masks):
+    """What check_lightmap_lod returned as the buffers the C calls take: (level 0's mask u8 or None, levels 1 .. L - 1 packed
+    [sum W_l H_l, C] f32, their masks packed u8 or None)"""
+    v0 = None if masks[0] is None else np.ascontiguousarray(masks[0], np.uint8)
+    mv = None if len(masks) < 2 or masks[1] is None else _lmm_pack(masks, np.uint8)
+    return v0, _lmm_pack(levels, np.float32, (levels[0].shape[2],)), mv
+
+
+def _lml_axis_lod(t, n0, s, n):
+    """One axis of the bilinear form at level l: coordinate t in 0 .. 1, n0 texels at level 0, s = 2^-l (exact), n texels at level l:
+    ((i0, i1), (1 - f, f)).  _lml_axis' clamp and index expressions; at l = 0 this is _lml_axis itself."""
+    f32 = np.float32
+    g = (t * f32(n0)) * s - f32(0.5)
+    g = np.fmin(np.fmax(g, f32(0.0)), f32(n - 1))
+    i0 = np.minimum(np.floor(g).astype(np.int64), max(n - 2, 0))
+    f = g - i0.astype(f32)
+    return (i0, np.minimum(i0 + 1, n - 1)), (f32(1.0) - f, f)
+
+
+def _lml_levels(lod, L):
+    """The two levels a point reads among L and their weights: ((l_a, l_b), (1 - f, f)).  fmax sends a NaN to 0."""
+    f32 = np.float32
+    lam = np.fmin(np.fmax(lod, f32(0.0)), f32(L - 1))
+    la = np.minimum(np.floor(lam).astype(np.int64), max(L - 2, 0))
+    fl = lam - la.astype(f32)
+    return (la, np.minimum(la + 1, L - 1)), (f32(1.0) - fl, fl)
+
+
+def _lml_lookup_lod(levels, oks, uv, lod, value, channels):
+    """The trilinear lookup both _lod definitions share: `value(t, at)` turns the texels [m, C] gathered for one tap of the points `at`
+    into what is interpolated [m, channels].  Returns (out [n, channels] f32, weight [n] f32)."""
+    f32 = np.float32
+    zero, one = f32(0.0), f32(1.0)
+    H0, W0 = levels[0].shape[:2]
+    u, v = uv[:, 0], uv[:, 1]
+    lv, wl = _lml_levels(lod, len(levels))
+    acc = np.zeros((len(uv), channels), f32)
+    sw = np.zeros(len(uv), f32)
+    for side in (0, 1):                                  # level a, then level b
+        for l, img in enumerate(levels):
+            at = np.nonzero((lv[side] == l) & (wl[side] > 0))[0]        # a level whose weight is not > 0 takes no part
+            if len(at) == 0:
+                continue
+            H, W = img.shape[:2]
+            s = f32(2.0 ** -l)
+            ix, wx = _lml_axis_lod(u[at], W0, s, W)
+            iy, wy = _lml_axis_lod(one - v[at], H0, s, H)
+            a, b = acc[at], sw[at]
+            for dy, dx in _LML_TAPS:
+                yi, xi = iy[dy], ix[dx]
+                w = wl[side][at] * (wx[dx] * wy[dy])
+                take = (w > 0) & oks[l][yi, xi]            # a tap that does not take part is not read
+                a = np.where(take[:, None], a + w[:, None] * value(img[yi, xi], at), a)
+                b = np.where(take, b + w, b)
+            acc[at], sw[at] = a, b
+    return np.where((sw > 0)[:, None], acc / sw[:, None], zero), sw
+
+
+def lightmap_sample_lod(chain, uv, lod, valid_chain=None, flags: int = 0):
+    """Read a lightmap's mip chain at uv points and levels of detail on the host (numpy only): trilinear over the valid texels.  This
+    is the DEFINITION of mi_lightmap_sample_lod, which equals it bit for bit.  Arguments as check_lightmap_lod (`chain`, `valid_chain`:
+    lightmap_mips' first two results).  Returns (out [..., C] f32, weight [...] f32).
+    Everything is f32, one rounding per operation, in the order written.  With L levels: lam = fmin(fmax(lod, 0), L - 1) (a NaN becomes
+    0), l_a = min(floor(lam), max(L - 2, 0)), f = lam - l_a, l_b = min(l_a + 1, L - 1); the level weights are (1 - f, f), and a level
+    whose weight is not > 0 takes no part and is not read.  Per level l that takes part and per axis g = (t n_0) 2^-l - 0.5 (t = u, or
+    1 - v), then lightmap_sample's clamp and index expressions with n_l; the scaling is exact, and at l = 0 this is lightmap_sample's
+    expression.  Taps: level a then level b, each dy outer, dx inner; w = w_level (w_x[dx] w_y[dy]); a tap takes part when w > 0 and its
+    texel is valid at its level.  One acc and one sw over the up to eight taps; out = acc / sw when sw > 0, else +0; weight = sw.
+    With one level, lod <= 0 or a NaN lod the result is lightmap_sample of level 0, bit for bit; at an integer lod = l on a size
+    divisible by 2^l it is lightmap_sample of level l with that level's mask."""
+    levels, masks, T, D, _, shape = check_lightmap_lod(chain, uv, lod, valid_chain, flags)
+    oks = [np.ones(a.shape[:2], bool) if m is None else m for a, m in zip(levels, masks)]
+    ch = levels[0].shape[2]
+    with np.errstate(all="ignore"):
+        out, sw = _lml_lookup_lod(levels, oks, T, D, lambda t, at: t, ch)
+    assert out.dtype == np.float32 and sw.dtype == np.float32
+    return np.ascontiguousarray(out.reshape(shape + (ch,))), np.ascontiguousarray(sw.reshape(shape))
+
+
+def lightmap_sh_sample_lod(chain, uv, normals, lod, valid_chain=None, flags: int = 0):
+    """The irradiance of a directional lightmap's mip chain at uv points, their normals and levels of detail on the host (numpy only).
+    This is the DEFINITION of mi_lightmap_sh_sample_lod, which equals it bit for bit.  `chain` holds [H_l, W_l, 9, 3] (or flat 27)
+    records; the other arguments as check_lightmap_lod.  Returns (E [..., 3] f32, weight [...] f32).
+    An all-zero normal (either sign of zero) gives +0 and weight 0.  Otherwise the levels, taps and weights are lightmap_sample_lod's
+    and each tap's record becomes e as in lightmap_sh_sample before it is weighted: three accumulators, never an interpolated
+    record.  With one level, lod <= 0 or a NaN lod the result is lightmap_sh_sample of level 0, bit for bit."""
+    f32 = np.float32
+    if normals is None:
+        raise ValueError("normals are required")
+    levels, masks, T, D, N, shape = check_lightmap_lod(chain, uv, lod, valid_chain, flags, normals)
+    if levels[0].shape[2] != 27:
+        raise ValueError(f"the levels must be [H, W, 9, 3] or [H, W, 27], got {np.shape(chain[0])}")
+    oks = [np.ones(a.shape[:2], bool) if m is None else m for a, m in zip(levels, masks)]
+    with np.errstate(all="ignore"):
+        nx, ny, nz = N[:, 0], N[:, 1], N[:, 2]
+        covered = _lm_covered(N)
+        ln = np.sqrt((nx * nx + ny * ny) + nz * nz)
+        x, y, z = nx / ln, ny / ln, nz / ln
+        b = (np.ones(len(N), f32), y, z, x, x * y, y * z, f32(3.0) * (z * z) - f32(1.0), x * z, x * x - y * y)
+
+        def value(t, at):
+            r = t.reshape(-1, 9, 3) * PV_K[None, :, None]
+            e = b[0][at][:, None] * r[:, 0, :]
+            for k in range(1, 9):
+                e = e + b[k][at][:, None] * r[:, k, :]
+            return e
+        E, sw = _lml_lookup_lod(levels, oks, T, D, value, 3)
+        E = np.where(covered[:, None], E, f32(0.0))
+        sw = np.where(covered, sw, f32(0.0))
+    assert E.dtype == np.float32 and sw.dtype == np.float32
+    return np.ascontiguousarray(E.reshape(shape + (3,))), np.ascontiguousarray(sw.reshape(shape))
+
+
 def lightmap_finish_var(image, m2, samples, points, normals, levels: int = 3, normal_power_log2: int = 5,
                         sigma_plane: float = float("inf"), reach: float = float("inf"), sigma_color: float = 8.0,
                         color_floor: float = 1e-6, dilate: int = 4):
@@ -1526,6 +1794,88 @@ class Context:
         [H, W] u8 mask, [n, 2] and [n, 3] f32 in; [n, 3] f32 and an optional [n] f32 out).  Queued on `stream`, no synchronisation."""
         abi.check(self._lib.mi_lightmap_sh_sample_device(self._h, width, height, d_sh, d_valid, n, d_uv, d_normals, flags, d_irradiance,
                                                          d_weight, stream))
+
+    # ---- lightmap mips: the coverage-aware pyramid and the trilinear lookups ----
+    def lightmap_mips(self, image, valid=None, levels: int = 0, want_valid: bool = True, want_coverage: bool = True):
+        """mi_lightmap_mips: the helper lightmap_mips on the GPU, bit for bit: the coverage-aware mip chain of `image` [H, W, 3],
+        [H, W, 27] or [H, W, 9, 3] f32 under `valid` ([H, W], None = all).  Returns the helper's three per-level lists (mips, valids,
+        coverage), level 0 being the inputs themselves; without want_valid / want_coverage that plane is not asked for (out_valid /
+        out_coverage NULL) and its list is None.  No scene is needed."""
+        img, v8, layout = check_lightmap_mips(image, valid, levels)
+        H, W, ch = img.shape
+        total = sum(w * h for w, h, _ in layout[1:])
+        mips = np.empty((max(total, 1), ch), np.float32)
+        mv = np.empty(max(total, 1), np.uint8) if want_valid else None
+        cov = np.empty(max(total, 1), np.float32) if want_coverage else None
+        abi.check(self._lib.mi_lightmap_mips(self._h, W, H, ch, img.ctypes.data, None if v8 is None else v8.ctypes.data, len(layout),
+                                             mips.ctypes.data, None if mv is None else mv.ctypes.data,
+                                             None if cov is None else cov.ctypes.data))
+        ok = np.ones((H, W), np.uint8) if v8 is None else v8
+
+        def split(flat, first, tail=()):
+            return None if flat is None else [first] + [flat[o:o + w * h].reshape((h, w) + tail) for w, h, o in layout[1:]]
+        return split(mips, img, (ch,)), split(mv, ok), split(cov, np.where(ok != 0, np.float32(1.0), np.float32(0.0)))
+
+    def lightmap_mips_device(self, width: int, height: int, channels: int, d_image: int, levels: int, d_mips: int,
+                             d_mip_valid: Optional[int] = None, d_mip_coverage: Optional[int] = None, d_valid: Optional[int] = None,
+                             stream: Optional[int] = None):
+        """mi_lightmap_mips_device: the same for an image held on the device (raw pointers: [H, W, channels] f32 and an optional [H, W] u8
+        mask in; levels 1 .. L - 1 tightly packed as lightmap_mip_layout lays them out: [sum W_l H_l, channels] f32, and optionally
+        [sum W_l H_l] u8 and f32, out, which must not overlap the inputs).  Queued on `stream`, no synchronisation.  Without
+        d_mip_coverage the coverage planes live in a buffer the context owns: two such calls must not be in flight at once."""
+        abi.check(self._lib.mi_lightmap_mips_device(self._h, width, height, channels, d_image, d_valid, levels, d_mips, d_mip_valid,
+                                                    d_mip_coverage, stream))
+
+    def lightmap_sample_lod(self, chain, uv, lod, valid_chain=None, flags: int = 0):
+        """mi_lightmap_sample_lod: the helper lightmap_sample_lod on the GPU, bit for bit: the chain lightmap_mips returned (levels and
+        masks, per level) read at `uv` [..., 2] and `lod` (a scalar or uv's leading shape), trilinear over the valid texels.  Returns
+        (out [..., C] f32, weight [...] f32).  No scene is needed."""
+        levels, masks, T, D, _, shape = check_lightmap_lod(chain, uv, lod, valid_chain, flags)
+        H, W, ch = levels[0].shape
+        v0, mips, mv = _lod_buffers(levels, masks)
+        out = np.empty((len(T), ch), np.float32)
+        weight = np.empty(len(T), np.float32)
+        abi.check(self._lib.mi_lightmap_sample_lod(self._h, W, H, ch, levels[0].ctypes.data, None if v0 is None else v0.ctypes.data,
+                                                   len(levels), mips.ctypes.data, None if mv is None else mv.ctypes.data, len(T),
+                                                   T.ctypes.data, D.ctypes.data, flags, out.ctypes.data, weight.ctypes.data))
+        return out.reshape(shape + (ch,)), weight.reshape(shape)
+
+    def lightmap_sample_lod_device(self, width: int, height: int, channels: int, d_image: int, levels: int, d_mips: Optional[int], n: int,
+                                   d_uv: int, d_lod: int, d_out: int, d_weight: Optional[int] = None, d_valid: Optional[int] = None,
+                                   d_mip_valid: Optional[int] = None, flags: int = 0, stream: Optional[int] = None):
+        """mi_lightmap_sample_lod_device: the same for a chain and points held on the device (raw pointers: level 0 [H, W, channels] f32
+        and its optional mask, levels 1 .. L - 1 packed as mi_lightmap_mips_device writes them with their optional masks, [n, 2] and
+        [n] f32 in; [n, channels] f32 and an optional [n] f32 out).  Queued on `stream`, no synchronisation, no scratch."""
+        abi.check(self._lib.mi_lightmap_sample_lod_device(self._h, width, height, channels, d_image, d_valid, levels, d_mips, d_mip_valid,
+                                                          n, d_uv, d_lod, flags, d_out, d_weight, stream))
+
+    def lightmap_sh_sample_lod(self, chain, uv, normals, lod, valid_chain=None, flags: int = 0):
+        """mi_lightmap_sh_sample_lod: the helper lightmap_sh_sample_lod on the GPU, bit for bit: the irradiance of a directional
+        lightmap's mip chain at `uv` [..., 2], the normals [..., 3] there and `lod`.  Returns (E [..., 3] f32, weight [...] f32)."""
+        if normals is None:
+            raise ValueError("normals are required")
+        levels, masks, T, D, N, shape = check_lightmap_lod(chain, uv, lod, valid_chain, flags, normals)
+        if levels[0].shape[2] != 27:
+            raise ValueError(f"the levels must be [H, W, 9, 3] or [H, W, 27], got {np.shape(chain[0])}")
+        H, W = levels[0].shape[:2]
+        v0, mips, mv = _lod_buffers(levels, masks)
+        E = np.empty((len(T), 3), np.float32)
+        weight = np.empty(len(T), np.float32)
+        abi.check(self._lib.mi_lightmap_sh_sample_lod(self._h, W, H, levels[0].ctypes.data, None if v0 is None else v0.ctypes.data,
+                                                      len(levels), mips.ctypes.data, None if mv is None else mv.ctypes.data, len(T),
+                                                      T.ctypes.data, N.ctypes.data, D.ctypes.data, flags, E.ctypes.data,
+                                                      weight.ctypes.data))
+        return E.reshape(shape + (3,)), weight.reshape(shape)
+
+    def lightmap_sh_sample_lod_device(self, width: int, height: int, d_sh: int, levels: int, d_mips: Optional[int], n: int, d_uv: int,
+                                      d_normals: int, d_lod: int, d_irradiance: int, d_weight: Optional[int] = None,
+                                      d_valid: Optional[int] = None, d_mip_valid: Optional[int] = None, flags: int = 0,
+                                      stream: Optional[int] = None):
+        """mi_lightmap_sh_sample_lod_device: the same for records and points held on the device (raw pointers as
+        lightmap_sample_lod_device at 27 channels, and [n, 3] f32 normals in; [n, 3] f32 and an optional [n] f32 out).  Queued on
+        `stream`, no synchronisation."""
+        abi.check(self._lib.mi_lightmap_sh_sample_lod_device(self._h, width, height, d_sh, d_valid, levels, d_mips, d_mip_valid, n, d_uv,
+                                                             d_normals, d_lod, flags, d_irradiance, d_weight, stream))
 
     def last_reduce_psh_ms(self) -> float:
         """Sum of the wf_reduce_psh launch durations (ms) of the last render: entry 7 of mi_last_pipeline_ms after render_points_sh /

@@ -929,6 +929,67 @@ int  mi_lightmap_sh_sample_device(mi_ctx* ctx, uint32_t width, uint32_t height, 
                                   const float* uv, const float* normals, uint32_t flags, float* out_irradiance, float* out_weight,
                                   void* stream);
 
+/* ---- lightmap mips: the coverage-aware pyramid of a finished lightmap and the trilinear lookup that reads it (added within ABI
+ *   version 5: detect by symbol lookup) ----
+ * A lookup whose footprint spans many texels (distant surfaces, grazing angles) aliases at level 0.  mi_lightmap_mips makes the levels
+ *   above it; a plain 2 x 2 box would pull in the texels no pass filled, so every level carries the fraction of its footprint that is
+ *   valid and averages over exactly those texels.  lightmap_mips, lightmap_sample_lod and lightmap_sh_sample_lod (Python) are the
+ *   definitions; the results equal them BIT FOR BIT under the contract of the lookup section above: pure f32, one rounding per operation,
+ *   in the order written here, no fused multiply-add, nothing summed across threads.
+ * The layout, one rule: `levels` counts level 0.  Level l is W_l x H_l with W_l = (W + 2^l - 1) >> l and H_l likewise (ceil halving):
+ *   texel (x, y) of level l covers exactly the level-0 texels [x 2^l, (x+1) 2^l) x [y 2^l, (y+1) 2^l) that lie inside the image, for
+ *   any size.  The full chain has 1 + ceil(log2(max(W, H))) levels (16 at 32768) and ends at 1 x 1.  levels == 0 means the full chain;
+ *   levels above the full chain is refused.  Levels 1 .. L-1 are stored tightly, one after the other, level 1 first:
+ *   mips [sum W_l H_l][channels] f32, mip_valid [sum W_l H_l] u8, mip_coverage [sum W_l H_l] f32.  Level 0 is not copied.
+ * mi_lightmap_mips: cov_0 = 1.0 where valid (valid == NULL: everywhere), else 0.0.  For l >= 1 texel (x, y) has the children
+ *   (2y + dy, 2x + dx) of level l-1, dy outer, dx inner.  A child takes part when it lies inside level l-1 and its c = cov_(l-1) > 0; a
+ *   child that takes no part is not read.  acc[k] = acc[k] + c * t[k] and sc = sc + c from +0.0; out[k] = acc[k] / sc when sc > 0, else
+ *   +0.0; cov_l = sc * 0.25f; valid_l = cov_l > 0.  So cov_l is the fraction of the texel's level-0 footprint that is valid and out
+ *   the mean over exactly those texels.  cov_l is exact while 4^l <= 2^24, that is l <= 12; beyond that it is rounded as written, and
+ *   the helper remains the definition.  Texels behind valid == 0 may hold anything; a non-finite valid texel spoils only its own
+ *   ancestors.  out_valid and out_coverage may be NULL.  The bits depend on neither the tiling nor the number of launches.
+ * mi_lightmap_sample_lod / mi_lightmap_sh_sample_lod: the lists of mi_lightmap_sample / mi_lightmap_sh_sample with `levels`, `mips` and
+ *   `mip_valid` as mi_lightmap_mips wrote them (both may be NULL when the chain has one level; mip_valid == NULL: every texel of every
+ *   level above 0 is valid) and `lod` [n].  Per point: lam = fminf(fmaxf(lod, 0), (float)(L-1)) — a NaN becomes 0 —
+ *   l_a = min((int)floorf(lam), max(L-2, 0)), f = lam - (float)l_a, l_b = min(l_a + 1, L-1); the level weights are { 1 - f, f }, and a
+ *   level whose weight is not > 0 takes no part and is not read.  Per level l that takes part and per axis g = (t * (float)n_0) * 2^-l
+ *   - 0.5f, then the clamp and index expressions of the bilinear form above with n_l; the scaling is exact, and at l = 0 this is the
+ *   bilinear form's own expression.  Taps: level a then level b, each dy outer, dx inner; w = w_level * (wx[dx] * wy[dy]); a tap takes
+ *   part when w > 0 and its texel is valid at its level.  One acc and one sw over the up to eight taps; out = acc / sw when sw > 0, else
+ *   +0.0; out_weight = sw.  The SH form turns each tap's record into e (mi_lightmap_sh_sample's expression) before it is weighted:
+ *   three accumulators, never an interpolated record; an all-zero normal gives +0.0 and weight 0.
+ *   So with levels == 1, lod <= 0 or a NaN lod the result is mi_lightmap_sample / mi_lightmap_sh_sample of level 0, bit for bit; at an
+ *   integer lod = l on a size divisible by 2^l it is mi_lightmap_sample of level l with that level's mip_valid.
+ *   Every address is made from clamped indices, whatever uv, lod, the normals and the texels hold.
+ * MI_ERR_INVALID (each with a message, checked before the context, nothing is launched): a NULL image / sh, out_mips, uv, lod, normals
+ *   or out / out_irradiance; mips == NULL with more than one level in the lookups; width or height 0 or above 32768; channels other
+ *   than 3 or 27; levels above the full chain; unknown flag bits, and MI_LS_NEAREST in the _lod forms (nearest addressing is the
+ *   reference's, and the reference has no mips); in the _device forms an output that overlaps an input.  MI_OK and nothing launched:
+ *   mi_lightmap_mips with one level (levels == 1, or a 1 x 1 image), and n == 0.
+ * Host forms: HOST pointers, blocking.  _device forms: DEVICE pointers on ctx's device, queued on `stream`, no synchronisation;
+ *   mi_last_kernel_ms reports the launches' span.  mi_lightmap_mips_device launches ceil((L-1) / 5) kernels (five levels per launch
+ *   from one 32 x 32 tile, staged in LDS; MI_RT_LMM_LEVELS_PER_LAUNCH=1 at context creation: one level per launch, the same bytes).
+ *   A later launch reads the coverage of the last level the one before wrote: with out_coverage == NULL the coverage planes live in a
+ *   buffer the context owns, so two such calls on one context must not be in flight at once (pass out_coverage to overlap them).  The
+ *   lookups need no scratch.  Indices are 64-bit.
+ * Out of scope: packed or compressed formats, deriving lod from ray footprints, anisotropic filtering, wrap modes other than clamp. */
+int  mi_lightmap_mips(mi_ctx* ctx, uint32_t width, uint32_t height, uint32_t channels, const float* image, const uint8_t* valid,
+                      uint32_t levels, float* out_mips, uint8_t* out_valid, float* out_coverage);
+int  mi_lightmap_mips_device(mi_ctx* ctx, uint32_t width, uint32_t height, uint32_t channels, const float* image, const uint8_t* valid,
+                             uint32_t levels, float* out_mips, uint8_t* out_valid, float* out_coverage, void* stream);
+int  mi_lightmap_sample_lod(mi_ctx* ctx, uint32_t width, uint32_t height, uint32_t channels, const float* image, const uint8_t* valid,
+                            uint32_t levels, const float* mips, const uint8_t* mip_valid, uint32_t n, const float* uv, const float* lod,
+                            uint32_t flags, float* out, float* out_weight);
+int  mi_lightmap_sample_lod_device(mi_ctx* ctx, uint32_t width, uint32_t height, uint32_t channels, const float* image, const uint8_t* valid,
+                                   uint32_t levels, const float* mips, const uint8_t* mip_valid, uint32_t n, const float* uv,
+                                   const float* lod, uint32_t flags, float* out, float* out_weight, void* stream);
+int  mi_lightmap_sh_sample_lod(mi_ctx* ctx, uint32_t width, uint32_t height, const float* sh, const uint8_t* valid, uint32_t levels,
+                               const float* mips, const uint8_t* mip_valid, uint32_t n, const float* uv, const float* normals,
+                               const float* lod, uint32_t flags, float* out_irradiance, float* out_weight);
+int  mi_lightmap_sh_sample_lod_device(mi_ctx* ctx, uint32_t width, uint32_t height, const float* sh, const uint8_t* valid, uint32_t levels,
+                                      const float* mips, const uint8_t* mip_valid, uint32_t n, const float* uv, const float* normals,
+                                      const float* lod, uint32_t flags, float* out_irradiance, float* out_weight, void* stream);
+
 /* Size and allocate the wavefront pipeline's HBM buffers (path state, sample slots) for
  * this camera with the image shared by `world` ranks, so that the first render does not pay the
  * allocation (about 110 GB for a whole 1080p / 256 spp frame on one GPU).  `max_state_bytes` as in

@@ -233,6 +233,24 @@ extern "C" {
     pub fn mi_lightmap_sh_sample_device(ctx: *mut mi_ctx, width: u32, height: u32, sh: *const f32, valid: *const u8, n: u32,
                                         uv: *const f32, normals: *const f32, flags: u32, out_irradiance: *mut f32, out_weight: *mut f32,
                                         stream: *mut c_void) -> c_int;
+    // lightmap mips: the coverage-aware pyramid (levels 1 .. L - 1, tightly packed) and the trilinear lookups that read it
+    pub fn mi_lightmap_mips(ctx: *mut mi_ctx, width: u32, height: u32, channels: u32, image: *const f32, valid: *const u8,
+                            levels: u32, out_mips: *mut f32, out_valid: *mut u8, out_coverage: *mut f32) -> c_int;
+    pub fn mi_lightmap_mips_device(ctx: *mut mi_ctx, width: u32, height: u32, channels: u32, image: *const f32, valid: *const u8,
+                                   levels: u32, out_mips: *mut f32, out_valid: *mut u8, out_coverage: *mut f32, stream: *mut c_void) -> c_int;
+    pub fn mi_lightmap_sample_lod(ctx: *mut mi_ctx, width: u32, height: u32, channels: u32, image: *const f32, valid: *const u8,
+                                  levels: u32, mips: *const f32, mip_valid: *const u8, n: u32, uv: *const f32, lod: *const f32,
+                                  flags: u32, out: *mut f32, out_weight: *mut f32) -> c_int;
+    pub fn mi_lightmap_sample_lod_device(ctx: *mut mi_ctx, width: u32, height: u32, channels: u32, image: *const f32, valid: *const u8,
+                                         levels: u32, mips: *const f32, mip_valid: *const u8, n: u32, uv: *const f32, lod: *const f32,
+                                         flags: u32, out: *mut f32, out_weight: *mut f32, stream: *mut c_void) -> c_int;
+    pub fn mi_lightmap_sh_sample_lod(ctx: *mut mi_ctx, width: u32, height: u32, sh: *const f32, valid: *const u8, levels: u32,
+                                     mips: *const f32, mip_valid: *const u8, n: u32, uv: *const f32, normals: *const f32,
+                                     lod: *const f32, flags: u32, out_irradiance: *mut f32, out_weight: *mut f32) -> c_int;
+    pub fn mi_lightmap_sh_sample_lod_device(ctx: *mut mi_ctx, width: u32, height: u32, sh: *const f32, valid: *const u8, levels: u32,
+                                            mips: *const f32, mip_valid: *const u8, n: u32, uv: *const f32, normals: *const f32,
+                                            lod: *const f32, flags: u32, out_irradiance: *mut f32, out_weight: *mut f32,
+                                            stream: *mut c_void) -> c_int;
     pub fn mi_reserve(ctx: *mut mi_ctx, cam: *const mi_camera_desc, world: i32, max_state_bytes: u64) -> c_int;
     pub fn mi_last_pipeline_ms(ctx: *mut mi_ctx, out8: *mut f32) -> c_int;
     pub fn mi_last_pipeline_counts(ctx: *mut mi_ctx, out8: *mut u64) -> c_int;

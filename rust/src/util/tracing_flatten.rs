@@ -487,6 +487,98 @@ impl Scene {
         (out, weight)
     }
 
+    /// The mip chain's layout (include/mi_rt.h "lightmap mips"): (width, height, offset in texels) of levels 0 .. levels - 1, ceil halving,
+    /// levels 1 .. tightly one after the other (level 0 is the image itself: offset 0); `levels` 0 is the full chain.
+    pub fn lightmap_mip_layout(width: u32, height: u32, levels: u32) -> Vec<(u32, u32, usize)> {
+        let full = 1 + (32 - (width.max(height) - 1).leading_zeros());
+        assert!(width >= 1 && height >= 1 && width <= 32768 && height <= 32768 && levels <= full, "mi_rt: size or levels out of range");
+        let mut out = Vec::new();
+        let mut off = 0usize;
+        for l in 0..(if levels == 0 { full } else { levels }) {
+            let (w, h) = ((width + (1 << l) - 1) >> l, (height + (1 << l) - 1) >> l);
+            out.push((w, h, off));
+            if l > 0 { off += w as usize * h as usize; }
+        }
+        out
+    }
+
+    /// The coverage-aware mip chain of a finished lightmap (mi_lightmap_mips): `image` holds height * width texels of `channels` floats
+    /// (3 or 27), `valid` is empty (every texel takes part) or finish_lightmap's mask, `levels` counts level 0 (0: the full chain).
+    /// Returns levels 1 .. tightly packed as lightmap_mip_layout lays them out: (mips, mip_valid, mip_coverage).  Needs no scene.
+    pub fn lightmap_mips(image: &[f32], valid: &[u8], width: u32, height: u32, channels: u32, levels: u32) -> (Vec<f32>, Vec<u8>, Vec<f32>) {
+        let texels = width as usize * height as usize;
+        assert!(image.len() == texels * channels as usize && (valid.is_empty() || valid.len() == texels), "mi_rt: image (and valid) must hold height * width texels");
+        let made: usize = Self::lightmap_mip_layout(width, height, levels).iter().skip(1).map(|l| l.0 as usize * l.1 as usize).sum();
+        let mut mips = vec![0.0f32; made.max(1) * channels as usize];
+        let mut mip_valid = vec![0u8; made.max(1)];
+        let mut coverage = vec![0.0f32; made.max(1)];
+        unsafe {
+            let mut ctx = std::ptr::null_mut();
+            assert_eq!(mi_rt::mi_ctx_create(0, &mut ctx), 0, "{}", mi_rt::last_error());
+            let rc = mi_rt::mi_lightmap_mips(ctx, width, height, channels, image.as_ptr(), if valid.is_empty() { std::ptr::null() } else { valid.as_ptr() },
+                                             levels, mips.as_mut_ptr(), mip_valid.as_mut_ptr(), coverage.as_mut_ptr());
+            let msg = mi_rt::last_error();
+            mi_rt::mi_ctx_destroy(ctx);
+            assert_eq!(rc, 0, "{}", msg);
+        }
+        mips.truncate(made * channels as usize); mip_valid.truncate(made); coverage.truncate(made);
+        (mips, mip_valid, coverage)
+    }
+
+    /// Read a lightmap's mip chain at uv points and levels of detail (mi_lightmap_sample_lod): sample_lightmap's arguments with the chain
+    /// lightmap_mips returned (`mips`, `mip_valid`: empty = every texel valid) and one `lod` per point; trilinear over the valid texels.
+    /// Returns `channels` floats per point and the weight sum per point.  Needs no scene.
+    pub fn sample_lightmap_lod(image: &[f32], valid: &[u8], width: u32, height: u32, channels: u32, levels: u32, mips: &[f32], mip_valid: &[u8],
+                               uv: &[[f32; 2]], lod: &[f32]) -> (Vec<f32>, Vec<f32>) {
+        let texels = width as usize * height as usize;
+        assert!(image.len() == texels * channels as usize && (valid.is_empty() || valid.len() == texels), "mi_rt: image (and valid) must hold height * width texels");
+        let made: usize = Self::lightmap_mip_layout(width, height, levels).iter().skip(1).map(|l| l.0 as usize * l.1 as usize).sum();
+        assert!(mips.len() == made * channels as usize && (mip_valid.is_empty() || mip_valid.len() == made), "mi_rt: mips (and mip_valid) must hold levels 1 .. of the layout");
+        assert_eq!(uv.len(), lod.len(), "mi_rt: one lod per point");
+        let mut out = vec![0.0f32; uv.len() * channels as usize];
+        let mut weight = vec![0.0f32; uv.len()];
+        if uv.is_empty() { return (out, weight); }
+        unsafe {
+            let mut ctx = std::ptr::null_mut();
+            assert_eq!(mi_rt::mi_ctx_create(0, &mut ctx), 0, "{}", mi_rt::last_error());
+            let rc = mi_rt::mi_lightmap_sample_lod(ctx, width, height, channels, image.as_ptr(), if valid.is_empty() { std::ptr::null() } else { valid.as_ptr() },
+                                                   levels, if mips.is_empty() { std::ptr::null() } else { mips.as_ptr() },
+                                                   if mip_valid.is_empty() { std::ptr::null() } else { mip_valid.as_ptr() }, uv.len() as u32,
+                                                   uv.as_ptr() as *const f32, lod.as_ptr(), 0, out.as_mut_ptr(), weight.as_mut_ptr());
+            let msg = mi_rt::last_error();
+            mi_rt::mi_ctx_destroy(ctx);
+            assert_eq!(rc, 0, "{}", msg);
+        }
+        (out, weight)
+    }
+
+    /// The irradiance of a directional lightmap's mip chain at uv points, their normals and levels of detail (mi_lightmap_sh_sample_lod):
+    /// sample_lightmap_sh's arguments with the chain lightmap_mips returned at 27 channels and one `lod` per point.  Needs no scene.
+    pub fn sample_lightmap_sh_lod(sh: &[[[f32; 3]; 9]], valid: &[u8], width: u32, height: u32, levels: u32, mips: &[f32], mip_valid: &[u8],
+                                  uv: &[[f32; 2]], normals: &[[f32; 3]], lod: &[f32]) -> (Vec<[f32; 3]>, Vec<f32>) {
+        let texels = width as usize * height as usize;
+        assert!(sh.len() == texels && (valid.is_empty() || valid.len() == texels), "mi_rt: sh (and valid) must hold height * width texels");
+        let made: usize = Self::lightmap_mip_layout(width, height, levels).iter().skip(1).map(|l| l.0 as usize * l.1 as usize).sum();
+        assert!(mips.len() == made * 27 && (mip_valid.is_empty() || mip_valid.len() == made), "mi_rt: mips (and mip_valid) must hold levels 1 .. of the layout");
+        assert!(uv.len() == normals.len() && uv.len() == lod.len(), "mi_rt: one normal and one lod per point");
+        let mut out = vec![[0.0f32; 3]; uv.len()];
+        let mut weight = vec![0.0f32; uv.len()];
+        if uv.is_empty() { return (out, weight); }
+        unsafe {
+            let mut ctx = std::ptr::null_mut();
+            assert_eq!(mi_rt::mi_ctx_create(0, &mut ctx), 0, "{}", mi_rt::last_error());
+            let rc = mi_rt::mi_lightmap_sh_sample_lod(ctx, width, height, sh.as_ptr() as *const f32, if valid.is_empty() { std::ptr::null() } else { valid.as_ptr() },
+                                                      levels, if mips.is_empty() { std::ptr::null() } else { mips.as_ptr() },
+                                                      if mip_valid.is_empty() { std::ptr::null() } else { mip_valid.as_ptr() }, uv.len() as u32,
+                                                      uv.as_ptr() as *const f32, normals.as_ptr() as *const f32, lod.as_ptr(), 0,
+                                                      out.as_mut_ptr() as *mut f32, weight.as_mut_ptr());
+            let msg = mi_rt::last_error();
+            mi_rt::mi_ctx_destroy(ctx);
+            assert_eq!(rc, 0, "{}", msg);
+        }
+        (out, weight)
+    }
+
     /// flatten -> context on device 0 -> upload -> `call` -> destroy; panics with the library's message on failure.
     fn with_gpu_scene<F: FnOnce(*mut mi_rt::mi_ctx) -> i32>(&self, call: F) {
         let sb = self.flatten_scene();

@@ -95,7 +95,11 @@ the ratio (three kernels per level instead of one).
 mi_lightmap_sh_eval_device); its protocol and the measured figures are in directional_rows' docstring.
 
 --mode lookup times the lightmap lookup kernels (mi_lightmap_sample_device at 3 and 27 channels, mi_lightmap_sh_sample_device) at
---lookup-sizes and --volume-points; its protocol is in lookup_rows' docstring, the measured figures in DESIGN.md."""
+--lookup-sizes and --volume-points; its protocol is in lookup_rows' docstring, the measured figures in DESIGN.md.
+
+--mode mips times the lightmap mip chain (mi_lightmap_mips_device, five levels per launch against one) and the trilinear lookups
+(mi_lightmap_sample_lod_device, mi_lightmap_sh_sample_lod_device) at --lookup-sizes and --volume-points; its protocol is in mips_rows'
+docstring, the measured figures in DESIGN.md."""
 import argparse
 import json
 import os
@@ -1220,6 +1224,160 @@ def lookup_rows(ctx, sizes, point_counts, calls, warmup):
     return rows
 
 
+def mips_rows(ctx, sizes, point_counts, calls, warmup):
+    """--mode mips: the lightmap mip chain on resident tables, HIP events inside the library (mi_last_kernel_ms: the span of a call's
+    launches), `warmup` calls then `calls` timed ones, medians with min - max; `spread` is (max - min) / median of a row, the run-to-run
+    spread a difference between two rows has to exceed.  Inputs per size and channel count (3, 27): a seeded random image
+    [size, size, C] under a chart-and-gutter mask (60 x 60 charts on a 64-texel pitch: 88 % valid).  Rows:
+    "fused" — mi_lightmap_mips_device of the full chain as the library launches it by default (five levels per launch from one
+    32 x 32 tile); "unfused" — the same call on a context created with MI_RT_LMM_LEVELS_PER_LAUNCH=1 (one level per launch);
+    "copy" — a device-to-device copy of the nominal bytes (level 0 and its mask read once; every level's texels, mask and coverage
+    written once; half of it copied: read and written).  Both forms are checked against lightmap_mips, every level, bit for bit.
+    Then, per point count, the trilinear lookups at lod uniform in 0 .. 4 (fractional: two levels, eight taps) against the level-0
+    lookups on the same points, in lookup_rows' two orders, "coherent" and "shuffled"; checked against lightmap_sample_lod /
+    lightmap_sh_sample_lod on a 4096-point subsample, bit for bit.  The measured figures are in DESIGN.md section 4, "Lightmap mips"."""
+    from cs397raytracingsp22_amd import lightmap_mip_layout, lightmap_mips, lightmap_sample_lod, lightmap_sh_sample_lod
+    dev = torch.device("cuda:0")
+    knob = "MI_RT_LMM_LEVELS_PER_LAUNCH"
+    before = os.environ.get(knob)
+    os.environ[knob] = "1"
+    unfused = Context(0)
+    if before is None:
+        del os.environ[knob]
+    else:
+        os.environ[knob] = before
+    rows = []
+
+    def stats(ms):
+        med = float(np.median(ms))
+        return {"ms_median": round(med, 4), "ms_min": round(float(np.min(ms)), 4), "ms_max": round(float(np.max(ms)), 4),
+                "spread": round((float(np.max(ms)) - float(np.min(ms))) / med, 4)}
+
+    def bits(t):
+        return t.contiguous().view(torch.int32).cpu().numpy()
+
+    def emit(row):
+        rows.append(row)
+        print(json.dumps(row), flush=True)
+
+    for size in sizes:
+        layout = lightmap_mip_layout(size, size)
+        L, made = len(layout), sum(w * h for w, h, _ in layout[1:])
+        gen = torch.Generator(device=dev)
+        gen.manual_seed(3)
+        yy, xx = torch.meshgrid(torch.arange(size, device=dev), torch.arange(size, device=dev), indexing="ij")
+        valid = ((xx % 64 < 60) & (yy % 64 < 60)).to(torch.uint8).contiguous()
+        valid_host = valid.cpu().numpy()
+        chains = {}
+        for ch in (3, 27):
+            img = torch.randn((size, size, ch), generator=gen, dtype=torch.float32, device=dev)
+            mips = torch.empty((made, ch), dtype=torch.float32, device=dev)
+            mv = torch.empty(made, dtype=torch.uint8, device=dev)
+            cov = torch.empty(made, dtype=torch.float32, device=dev)
+            moved = size * size * (4 * ch + 1) + made * (4 * ch + 1 + 4)
+            src, dst = torch.empty(moved // 2, dtype=torch.uint8, device=dev), torch.empty(moved // 2, dtype=torch.uint8, device=dev)
+            want = lightmap_mips(img.cpu().numpy(), valid_host)
+            ms = {"fused": [], "unfused": [], "copy": []}
+            same = True
+            for it in range(warmup + calls):
+                t = {}
+                for name, c in (("fused", ctx), ("unfused", unfused)):
+                    if it == 0:
+                        mips.fill_(-7.0), mv.fill_(77), cov.fill_(-7.0)
+                    c.lightmap_mips_device(size, size, ch, img.data_ptr(), L, mips.data_ptr(), mv.data_ptr(), cov.data_ptr(), valid.data_ptr())
+                    torch.cuda.synchronize()
+                    t[name] = c.last_kernel_ms()
+                    if it == 0:                  # every level of both forms against the helper
+                        gm, gv, gc = bits(mips), mv.cpu().numpy(), bits(cov)
+                        for l, (w, h, o) in enumerate(layout[1:], 1):
+                            same = (same and np.array_equal(gm[o:o + w * h].reshape(h, w, ch), want[0][l].view(np.int32))
+                                    and np.array_equal(gv[o:o + w * h].reshape(h, w), want[1][l])
+                                    and np.array_equal(gc[o:o + w * h].reshape(h, w), want[2][l].view(np.int32)))
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                dst.copy_(src)
+                e1.record()
+                torch.cuda.synchronize()
+                t["copy"] = e0.elapsed_time(e1)
+                if it >= warmup:
+                    for key, val in t.items():
+                        ms[key].append(val)
+            fused, unf = float(np.median(ms["fused"])), float(np.median(ms["unfused"]))
+            for key in ("fused", "unfused", "copy"):
+                row = dict(mode="mips", size=size, channels=ch, levels=L, query=key, calls=calls, **stats(ms[key]))
+                if key == "fused":
+                    row.update(launches=-(-(L - 1) // 5), fused_over_unfused=round(fused / unf, 4), nominal_gb_per_s=round(moved / fused / 1e6, 1),
+                               equals_helper=bool(same))
+                if key == "unfused":
+                    row.update(launches=L - 1, nominal_gb_per_s=round(moved / unf / 1e6, 1))
+                if key == "copy":
+                    row.update(bytes_moved=moved, gb_per_s=round(moved / float(np.median(ms["copy"])) / 1e6, 1))
+                emit(row)
+            if not same:
+                raise SystemExit("ray_query_bench: the pyramid differs from lightmap_mips")
+            chains[ch] = (img, mips, mv, want)
+            del src, dst, cov
+        # the trilinear lookups against the level-0 lookups
+        img3, mips3, mv3, want3 = chains[3]
+        sh, mips27, mv27, want27 = chains[27]
+        for n in point_counts:
+            gw = 2 * size
+            if n > gw * gw:
+                raise SystemExit(f"ray_query_bench: {n} points exceed the {gw} x {gw} grid")
+
+            def centres(k):                  # the uv of the points number k of the gw x gw grid, row-major
+                u = ((k % gw).to(torch.float32) + 0.5) / gw
+                v = 1.0 - ((k // gw).to(torch.float32) + 0.5) / gw
+                return torch.stack([u, v], dim=1).contiguous()
+
+            k = torch.arange(n, device=dev, dtype=torch.int64)
+            anywhere = torch.randint(0, gw * gw, (n,), generator=gen, device=dev, dtype=torch.int64)
+            nrm = torch.randn((n, 3), generator=gen, dtype=torch.float32, device=dev)
+            nrm = (nrm / nrm.norm(dim=1, keepdim=True)).contiguous()
+            lod = (torch.rand(n, generator=gen, dtype=torch.float32, device=dev) * 4.0).contiguous()
+            out3, out27 = torch.empty((n, 3), dtype=torch.float32, device=dev), torch.empty((n, 27), dtype=torch.float32, device=dev)
+            E, w = torch.empty((n, 3), dtype=torch.float32, device=dev), torch.empty(n, dtype=torch.float32, device=dev)
+            b3, b27, bE = torch.empty_like(out3), torch.empty_like(out27), torch.empty_like(E)
+            for order, uv in (("coherent", centres(k)), ("shuffled", centres(anywhere))):
+                torch.cuda.synchronize()
+                calls_ = {
+                    "lml_sample_lod<3>": lambda: ctx.lightmap_sample_lod_device(size, size, 3, img3.data_ptr(), L, mips3.data_ptr(), n, uv.data_ptr(),
+                                                                                lod.data_ptr(), out3.data_ptr(), w.data_ptr(), valid.data_ptr(), mv3.data_ptr()),
+                    "lml_sample_lod<27>": lambda: ctx.lightmap_sample_lod_device(size, size, 27, sh.data_ptr(), L, mips27.data_ptr(), n, uv.data_ptr(),
+                                                                                 lod.data_ptr(), out27.data_ptr(), w.data_ptr(), valid.data_ptr(), mv27.data_ptr()),
+                    "lml_sh_sample_lod": lambda: ctx.lightmap_sh_sample_lod_device(size, size, sh.data_ptr(), L, mips27.data_ptr(), n, uv.data_ptr(),
+                                                                                   nrm.data_ptr(), lod.data_ptr(), E.data_ptr(), w.data_ptr(), valid.data_ptr(),
+                                                                                   mv27.data_ptr()),
+                    "lml_sample<3>": lambda: ctx.lightmap_sample_device(size, size, 3, img3.data_ptr(), n, uv.data_ptr(), b3.data_ptr(), None, valid.data_ptr()),
+                    "lml_sample<27>": lambda: ctx.lightmap_sample_device(size, size, 27, sh.data_ptr(), n, uv.data_ptr(), b27.data_ptr(), None, valid.data_ptr()),
+                    "lml_sh_sample": lambda: ctx.lightmap_sh_sample_device(size, size, sh.data_ptr(), n, uv.data_ptr(), nrm.data_ptr(), bE.data_ptr(), None,
+                                                                           valid.data_ptr()),
+                }
+                ms = {key: [] for key in calls_}
+                for it in range(warmup + calls):
+                    for key, call in calls_.items():
+                        call()
+                        torch.cuda.synchronize()
+                        if it >= warmup:
+                            ms[key].append(ctx.last_kernel_ms())
+                pick = torch.linspace(0, n - 1, 4096, device=dev).to(torch.int64)
+                uv_h, n_h, lod_h = uv[pick].cpu().numpy(), nrm[pick].cpu().numpy(), lod[pick].cpu().numpy()
+                g3, g27 = lightmap_sample_lod(want3[0], uv_h, lod_h, want3[1])[0], lightmap_sample_lod(want27[0], uv_h, lod_h, want27[1])[0]
+                gE, gw_ = lightmap_sh_sample_lod(want27[0], uv_h, n_h, lod_h, want27[1])
+                same = (np.array_equal(bits(out3[pick]), g3.view(np.int32)) and np.array_equal(bits(out27[pick]), g27.view(np.int32))
+                        and np.array_equal(bits(E[pick]), gE.view(np.int32)) and np.array_equal(bits(w[pick]), gw_.view(np.int32)))
+                for key, base in (("lml_sample_lod<3>", "lml_sample<3>"), ("lml_sample_lod<27>", "lml_sample<27>"), ("lml_sh_sample_lod", "lml_sh_sample")):
+                    emit(dict(mode="mips", size=size, n_points=n, order=order, query=base, calls=calls, **stats(ms[base])))
+                    emit(dict(mode="mips", size=size, n_points=n, order=order, query=key, calls=calls, **stats(ms[key]),
+                              lod_over_level0=round(float(np.median(ms[key])) / float(np.median(ms[base])), 4), equals_helpers=bool(same)))
+                if not same:
+                    raise SystemExit("ray_query_bench: the trilinear lookups differ from lightmap_sample_lod / lightmap_sh_sample_lod")
+            del k, anywhere, nrm, lod, out3, out27, E, w, b3, b27, bE
+        del chains
+    unfused.close()
+    return rows
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--calls", type=int, default=20, help="timed calls per row (at least 20)")
@@ -1227,7 +1385,7 @@ def main():
     ap.add_argument("--width", type=int, default=1920)
     ap.add_argument("--height", type=int, default=1080)
     ap.add_argument("--configs", default="2,4")
-    ap.add_argument("--mode", choices=("intersect", "occlusion", "render", "hemisphere", "bake", "probes", "atlas", "finish", "volume", "variance", "adaptive", "directional", "lookup"), default="intersect",
+    ap.add_argument("--mode", choices=("intersect", "occlusion", "render", "hemisphere", "bake", "probes", "atlas", "finish", "volume", "variance", "adaptive", "directional", "lookup", "mips"), default="intersect",
                     help="intersect: the closest-hit rows; occlusion: the any-hit query against the visibility form; "
                          "render: ray-table rendering against mi_shade_rays_device; "
                          "hemisphere: hemisphere occlusion against the any-hit query on the identical pre-made rays; "
@@ -1242,10 +1400,12 @@ def main():
                          "directional: wf_reduce_psh's share of an SH bake, the 27-channel finish against nine 3-channel ones, and the "
                          "evaluation against a copy of the same bytes; "
                          "lookup: the lightmap lookup kernels, coherent and shuffled uv, the fused SH form against lml_sample<27> + lsh_eval "
-                         "and against a copy of the same bytes")
-    ap.add_argument("--lookup-sizes", default="1024,2048", help="--mode lookup: the square lightmap sizes")
+                         "and against a copy of the same bytes; "
+                         "mips: the lightmap mip chain, five levels per launch against one, against a copy of the nominal bytes, and the "
+                         "trilinear lookups against the level-0 lookups on the same points")
+    ap.add_argument("--lookup-sizes", default="1024,2048", help="--mode lookup and --mode mips: the square lightmap sizes")
     ap.add_argument("--volume-grids", default="16,32", help="--mode volume: probes per axis")
-    ap.add_argument("--volume-points", default=f"{1 << 20},{1 << 22}", help="--mode volume, --mode directional and --mode lookup: point counts")
+    ap.add_argument("--volume-points", default=f"{1 << 20},{1 << 22}", help="--mode volume, --mode directional, --mode lookup and --mode mips: point counts")
     ap.add_argument("--finish-sizes", default="1024,2048,4096", help="--mode finish and --mode variance: the square atlas sizes")
     ap.add_argument("--atlas-sizes", default="1024,2048", help="--mode atlas: the square atlas sizes")
     ap.add_argument("--atlas-grid", type=int, default=0, help="--mode atlas: a synthetic height field of N x N quads (2 N^2 triangles) instead "
@@ -1275,6 +1435,9 @@ def main():
         a.configs = ""
     if a.mode == "lookup":
         rows += lookup_rows(ctx, [int(v) for v in a.lookup_sizes.split(",")], [int(v) for v in a.volume_points.split(",")], a.calls, a.warmup)
+        a.configs = ""
+    if a.mode == "mips":
+        rows += mips_rows(ctx, [int(v) for v in a.lookup_sizes.split(",")], [int(v) for v in a.volume_points.split(",")], a.calls, a.warmup)
         a.configs = ""
     if a.mode == "adaptive":
         rows += adaptive_rows(ctx, int(a.atlas_sizes.split(",")[0]), a.atlas_bakes)
