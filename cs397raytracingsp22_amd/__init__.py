@@ -27,10 +27,12 @@ from .tracing import check_finish_sh_tables, check_sh_eval, lightmap_finish_sh, 
 from .tracing import check_lightmap_lookup, lightmap_sample, lightmap_sh_sample, shade_hits_baked  # noqa: F401
 from .tracing import check_lightmap_lod, check_lightmap_mips, lightmap_mip_layout, lightmap_mips  # noqa: F401
 from .tracing import lightmap_sample_lod, lightmap_sh_sample_lod  # noqa: F401
+from .tracing import check_lightmap_packed, lightmap_pack, lightmap_unpack, lightmap_sample_packed, lightmap_sh_sample_packed  # noqa: F401
 
 __all__ = [
     "abi", "Camera", "CameraProjectionMode", "ShadingMode", "Scene", "Context", "MultiContext", "compact_size",
     "Intersectable", "Sphere", "Triangle", "Plane", "ConvexVolume", "StaticMesh",
     "Material", "Lambertian", "Metal", "Dielectric", "ParameterizedMaterial", "Isotropic", "Texture",
+    "lightmap_pack", "lightmap_unpack", "lightmap_sample_packed", "lightmap_sh_sample_packed", "check_lightmap_packed",
     "lightmap_mip_layout", "lightmap_mips", "lightmap_sample_lod", "lightmap_sh_sample_lod", "check_lightmap_mips", "check_lightmap_lod",
 ]

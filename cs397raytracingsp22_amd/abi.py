@@ -30,6 +30,8 @@ MI_OPT_NO_FINAL_CULL = 16
 MI_HEMI_WORLD_RADIUS = 1   # mi_hemisphere_occlusion flags: t_max is a world-space radius
 MI_LM_JITTER = 1           # mi_lightmap_texels / mi_bake_lightmap flags: one jittered position per row instead of the texel centre
 MI_PV_NORMAL_WEIGHT = 1    # mi_probe_volume.flags: weight the eight corners by how far they lie in front of the surface
+MI_LP_F16 = 1              # mi_lightmap_pack / _unpack / _*_packed format: `channels` binary16 per texel (0 is f32: refused there)
+MI_LP_RGB9E5 = 2           # ... one u32 per texel, three 9-bit mantissas and a shared 5-bit exponent (3 channels only)
 MI_LS_NEAREST = 1          # mi_lightmap_sample / mi_lightmap_sh_sample flags: the reference's nearest-texel addressing, no interpolation
 
 f3 = C.c_float * 3
@@ -144,6 +146,8 @@ EXPORTS = [
     "mi_lightmap_sample", "mi_lightmap_sample_device", "mi_lightmap_sh_sample", "mi_lightmap_sh_sample_device",
     "mi_lightmap_mips", "mi_lightmap_mips_device", "mi_lightmap_sample_lod", "mi_lightmap_sample_lod_device",
     "mi_lightmap_sh_sample_lod", "mi_lightmap_sh_sample_lod_device",
+    "mi_lightmap_pack", "mi_lightmap_pack_device", "mi_lightmap_unpack", "mi_lightmap_unpack_device",
+    "mi_lightmap_sample_packed", "mi_lightmap_sample_packed_device", "mi_lightmap_sh_sample_packed", "mi_lightmap_sh_sample_packed_device",
     "mi_multi_create", "mi_multi_create_loopback", "mi_multi_destroy", "mi_multi_device_count", "mi_multi_context", "mi_multi_scene_upload", "mi_multi_reserve", "mi_multi_render",
 ]
 
@@ -338,6 +342,19 @@ def load() -> C.CDLL:
     lib.mi_lightmap_sh_sample_lod_device.argtypes = lib.mi_lightmap_sh_sample_lod.argtypes + [vp]
     for name in ("lightmap_mips", "lightmap_mips_device", "lightmap_sample_lod", "lightmap_sample_lod_device", "lightmap_sh_sample_lod",
                  "lightmap_sh_sample_lod_device"):
+        getattr(lib, "mi_" + name).restype = C.c_int
+    # packed lightmaps (added within ABI 5): format, channels, n_texels (u64), in, out (, stream); the packed lookups: format in front of
+    # the _lod lookups' lists (lod may be NULL: the level-0 lookup)
+    lib.mi_lightmap_pack.argtypes = [vp, u32, u32, C.c_uint64, vp, vp]
+    lib.mi_lightmap_pack_device.argtypes = lib.mi_lightmap_pack.argtypes + [vp]
+    lib.mi_lightmap_unpack.argtypes = [vp, u32, u32, C.c_uint64, vp, vp]
+    lib.mi_lightmap_unpack_device.argtypes = lib.mi_lightmap_unpack.argtypes + [vp]
+    lib.mi_lightmap_sample_packed.argtypes = [vp, u32] + lib.mi_lightmap_sample_lod.argtypes[1:]
+    lib.mi_lightmap_sample_packed_device.argtypes = lib.mi_lightmap_sample_packed.argtypes + [vp]
+    lib.mi_lightmap_sh_sample_packed.argtypes = [vp, u32] + lib.mi_lightmap_sh_sample_lod.argtypes[1:]
+    lib.mi_lightmap_sh_sample_packed_device.argtypes = lib.mi_lightmap_sh_sample_packed.argtypes + [vp]
+    for name in ("lightmap_pack", "lightmap_pack_device", "lightmap_unpack", "lightmap_unpack_device", "lightmap_sample_packed",
+                 "lightmap_sample_packed_device", "lightmap_sh_sample_packed", "lightmap_sh_sample_packed_device"):
         getattr(lib, "mi_" + name).restype = C.c_int
     lib.mi_multi_create.argtypes = [C.c_int, C.POINTER(C.c_int), C.POINTER(vp)]
     lib.mi_multi_create.restype = C.c_int

@@ -75,6 +75,9 @@ hipError_t launch_lsh_eval(const LshEvalArgs& a, hipStream_t stream);
 hipError_t launch_lml_sample(const LmlArgs& a, uint32_t channels, hipStream_t stream);
 hipError_t launch_lmm_reduce(const LmmArgs& a, uint32_t channels, hipStream_t stream);
 hipError_t launch_lml_sample_lod(const LmlLodArgs& a, uint32_t channels, hipStream_t stream);
+hipError_t launch_lmp_pack(const LmpArgs& a, uint32_t format, bool unpack, hipStream_t stream);
+hipError_t launch_lmp_sample(const LmlArgs& a, uint32_t format, uint32_t channels, hipStream_t stream);
+hipError_t launch_lmp_sample_lod(const LmlLodArgs& a, uint32_t format, uint32_t channels, hipStream_t stream);
 }  // namespace pt
 
 using namespace pt;
@@ -1715,11 +1718,15 @@ extern "C" int mi_lightmap_sh_eval(mi_ctx* c, uint32_t n, const float* sh, const
 // ------------------------------------------------------------------ lightmap lookup (a finished lightmap read at uv points)
 // tracing.py lightmap_sample and lightmap_sh_sample as one kernel each (lml_sample<3>, lml_sample<27>, lml_sh_sample): one lane per point,
 // no scratch, no scene.  One argument record serves both calls: channels == 0 is the fused SH form, which reads 27 floats per texel and
-// the normals and writes three per point.
+// the normals and writes three per point.  format: 0 = f32 texels, else MI_LP_* (the packed lookups further down enter here).
 struct LookupArgs {
-    uint32_t width, height, channels; const float* image; const uint8_t* valid; uint32_t n; const float* uv; const float* normals;
-    uint32_t flags; float* out; float* out_weight;
+    uint32_t width, height, channels; const void* image; const uint8_t* valid; uint32_t n; const float* uv; const float* normals;
+    uint32_t flags; float* out; float* out_weight; uint32_t format = 0;
 };
+// The bytes of one stored texel of `channels` values
+static inline size_t texel_bytes(uint32_t format, size_t channels) {
+    return format == MI_LP_RGB9E5 ? sizeof(uint32_t) : channels * (format == MI_LP_F16 ? sizeof(uint16_t) : sizeof(float));
+}
 
 // Checked before the context, nothing is launched: the pointers, the size, the channel count, the flags
 static int check_lookup_args(const char* who, const LookupArgs& l) {
@@ -1738,7 +1745,7 @@ static int lookup_device(mi_ctx* c, const LookupArgs& l, hipStream_t stream) {
     a.image = l.image; a.valid = l.valid; a.uv = l.uv; a.normals = l.normals; a.out = l.out; a.out_weight = l.out_weight;
     a.width = l.width; a.height = l.height; a.n = l.n; a.nearest = l.flags & MI_LS_NEAREST;
     return timed(c, stream, [&]() -> int {
-        HIP_TRY(launch_lml_sample(a, l.channels, stream));
+        HIP_TRY(l.format ? launch_lmp_sample(a, l.format, l.channels, stream) : launch_lml_sample(a, l.channels, stream));
         return MI_OK;
     });
 }
@@ -1750,7 +1757,7 @@ static int lookup_entry_device(const char* who, mi_ctx* c, const LookupArgs& l, 
     const size_t texels = (size_t)l.width * l.height, in_c = l.channels ? l.channels : (uint32_t)kShFloats, out_c = l.channels ? l.channels : 3u;
     MI_TRY(check_no_overlap(who, { { l.out, (size_t)l.n * out_c * sizeof(float), l.channels ? "out" : "out_irradiance" },
                                    { l.out_weight, (size_t)l.n * sizeof(float), "out_weight" } },
-                            { { l.image, texels * in_c * sizeof(float) }, { l.valid, texels }, { l.uv, (size_t)l.n * 2 * sizeof(float) },
+                            { { l.image, texels * texel_bytes(l.format, in_c) }, { l.valid, texels }, { l.uv, (size_t)l.n * 2 * sizeof(float) },
                               { l.normals, (size_t)l.n * 3 * sizeof(float) } }));
     if (l.n == 0) return MI_OK;
     HIP_TRY(hipSetDevice(c->device));
@@ -1764,12 +1771,12 @@ static int lookup_entry_host(const char* who, mi_ctx* c, const LookupArgs& l) {
     if (l.n == 0) return MI_OK;                // before any device call
     const size_t texels = (size_t)l.width * l.height, in_c = l.channels ? l.channels : (uint32_t)kShFloats, out_c = l.channels ? l.channels : 3u;
     enum { kImage, kValid, kUv, kNormals, kOut, kWeight };
-    const StageColumn cols[] = { { l.image, texels * in_c * sizeof(float), Stage::kIn }, { l.valid, texels, Stage::kIn },
+    const StageColumn cols[] = { { l.image, texels * texel_bytes(l.format, in_c), Stage::kIn }, { l.valid, texels, Stage::kIn },
                                  { l.uv, (size_t)l.n * 2 * sizeof(float), Stage::kIn }, { l.normals, (size_t)l.n * 3 * sizeof(float), Stage::kIn },
                                  { l.out, (size_t)l.n * out_c * sizeof(float), Stage::kOut }, { l.out_weight, (size_t)l.n * sizeof(float), Stage::kOut } };
     return staged(c, cols, [&](void* const* d) -> int {
         LookupArgs dl = l;
-        dl.image = (const float*)d[kImage]; dl.valid = (const uint8_t*)d[kValid]; dl.uv = (const float*)d[kUv];
+        dl.image = d[kImage]; dl.valid = (const uint8_t*)d[kValid]; dl.uv = (const float*)d[kUv];
         dl.normals = (const float*)d[kNormals]; dl.out = (float*)d[kOut]; dl.out_weight = (float*)d[kWeight];
         return lookup_device(c, dl, c->stream);
     });
@@ -1886,8 +1893,8 @@ extern "C" int mi_lightmap_mips(mi_ctx* c, uint32_t width, uint32_t height, uint
 
 // The trilinear lookups.  One argument record serves both calls: channels == 0 is the fused SH form.
 struct LodArgs {
-    uint32_t width, height, channels; const float* image; const uint8_t* valid; uint32_t levels; const float* mips; const uint8_t* mip_valid;
-    uint32_t n; const float* uv; const float* normals; const float* lod; uint32_t flags; float* out; float* out_weight;
+    uint32_t width, height, channels; const void* image; const uint8_t* valid; uint32_t levels; const void* mips; const uint8_t* mip_valid;
+    uint32_t n; const float* uv; const float* normals; const float* lod; uint32_t flags; float* out; float* out_weight; uint32_t format = 0;
 };
 
 // Checked before the context, nothing is launched
@@ -1913,7 +1920,7 @@ static int lod_device(mi_ctx* c, const LodArgs& l, const MipPlan& plan, hipStrea
     a.out = l.out; a.out_weight = l.out_weight; a.levels = plan.levels; a.n = l.n;
     for (uint32_t k = 0; k < plan.levels; k++) { a.off[k] = plan.level[k].offset; a.lw[k] = plan.level[k].width; a.lh[k] = plan.level[k].height; }
     return timed(c, stream, [&]() -> int {
-        HIP_TRY(launch_lml_sample_lod(a, l.channels, stream));
+        HIP_TRY(l.format ? launch_lmp_sample_lod(a, l.format, l.channels, stream) : launch_lml_sample_lod(a, l.channels, stream));
         return MI_OK;
     });
 }
@@ -1926,7 +1933,7 @@ static int lod_entry_device(const char* who, mi_ctx* c, const LodArgs& l, void* 
     const size_t in_c = l.channels ? l.channels : (uint32_t)kShFloats, out_c = l.channels ? l.channels : 3u;
     MI_TRY(check_no_overlap(who, { { l.out, (size_t)l.n * out_c * sizeof(float), l.channels ? "out" : "out_irradiance" },
                                    { l.out_weight, (size_t)l.n * sizeof(float), "out_weight" } },
-                            { { l.image, texels * in_c * sizeof(float) }, { l.valid, texels }, { l.mips, made * in_c * sizeof(float) },
+                            { { l.image, texels * texel_bytes(l.format, in_c) }, { l.valid, texels }, { l.mips, made * texel_bytes(l.format, in_c) },
                               { l.mip_valid, made }, { l.uv, (size_t)l.n * 2 * sizeof(float) }, { l.lod, (size_t)l.n * sizeof(float) },
                               { l.normals, (size_t)l.n * 3 * sizeof(float) } }));
     if (l.n == 0) return MI_OK;
@@ -1943,15 +1950,15 @@ static int lod_entry_host(const char* who, mi_ctx* c, const LodArgs& l) {
     const size_t in_c = l.channels ? l.channels : (uint32_t)kShFloats, out_c = l.channels ? l.channels : 3u;
     const bool chain = plan.levels > 1;
     enum { kImage, kValid, kMips, kMipValid, kUv, kLod, kNormals, kOut, kWeight };
-    const StageColumn cols[] = { { l.image, texels * in_c * sizeof(float), Stage::kIn }, { l.valid, texels, Stage::kIn },
-                                 { chain ? l.mips : nullptr, made * in_c * sizeof(float), Stage::kIn },
+    const StageColumn cols[] = { { l.image, texels * texel_bytes(l.format, in_c), Stage::kIn }, { l.valid, texels, Stage::kIn },
+                                 { chain ? l.mips : nullptr, made * texel_bytes(l.format, in_c), Stage::kIn },
                                  { chain ? l.mip_valid : nullptr, made, Stage::kIn },
                                  { l.uv, (size_t)l.n * 2 * sizeof(float), Stage::kIn }, { l.lod, (size_t)l.n * sizeof(float), Stage::kIn },
                                  { l.normals, (size_t)l.n * 3 * sizeof(float), Stage::kIn },
                                  { l.out, (size_t)l.n * out_c * sizeof(float), Stage::kOut }, { l.out_weight, (size_t)l.n * sizeof(float), Stage::kOut } };
     return staged(c, cols, [&](void* const* d) -> int {
         LodArgs dl = l;
-        dl.image = (const float*)d[kImage]; dl.valid = (const uint8_t*)d[kValid]; dl.mips = (const float*)d[kMips];
+        dl.image = d[kImage]; dl.valid = (const uint8_t*)d[kValid]; dl.mips = d[kMips];
         dl.mip_valid = (const uint8_t*)d[kMipValid]; dl.uv = (const float*)d[kUv]; dl.lod = (const float*)d[kLod];
         dl.normals = (const float*)d[kNormals]; dl.out = (float*)d[kOut]; dl.out_weight = (float*)d[kWeight];
         return lod_device(c, dl, plan, c->stream);
@@ -1987,6 +1994,108 @@ extern "C" int mi_lightmap_sh_sample_lod(mi_ctx* c, uint32_t width, uint32_t hei
                                          const float* lod, uint32_t flags, float* out_irradiance, float* out_weight) {
     return lod_entry_host("mi_lightmap_sh_sample_lod", c, { width, height, 0, sh, valid, levels, mips, mip_valid, n, uv, normals, lod, flags,
                           out_irradiance, out_weight });
+}
+
+// ------------------------------------------------------------------ packed lightmaps (f16 and RGB9E5 storage, lookups that read them)
+// tracing.py lightmap_pack / lightmap_unpack as lmp_pack<F> / lmp_unpack<F>: a count of texels, whatever their layout.  The packed lookups
+// are the lookups above with LookupArgs / LodArgs' format set: the same checks, staging, plan and timing, the lmp_* kernels.
+struct PackArgs { uint32_t format, channels; uint64_t n_texels; const void* src; void* dst; bool unpack; };
+
+// What every packed call checks of its format, before anything else (sh: the fused form, which reads signed coefficients)
+static int check_packed_format(const char* who, uint32_t format, uint32_t channels, bool sh) {
+    if (format != MI_LP_F16 && format != MI_LP_RGB9E5)
+        return fail(MI_ERR_INVALID, "%s: format %u is not MI_LP_F16 or MI_LP_RGB9E5 (f32 texels take the unpacked calls)", who, format);
+    if (sh && format != MI_LP_F16) return fail(MI_ERR_INVALID, "%s: SH coefficients are signed: only MI_LP_F16 holds them", who);
+    if (!sh && channels != 3 && channels != (uint32_t)kShFloats) return fail(MI_ERR_INVALID, "%s: channels %u is not 3 or 27", who, channels);
+    if (format == MI_LP_RGB9E5 && channels != 3)
+        return fail(MI_ERR_INVALID, "%s: MI_LP_RGB9E5 holds 3 unsigned channels, not %u (SH records pack as MI_LP_F16)", who, channels);
+    return MI_OK;
+}
+
+static int pack_device(mi_ctx* c, const PackArgs& p, hipStream_t stream) {
+    LmpArgs a{};
+    a.src = p.src; a.dst = p.dst; a.n = p.format == MI_LP_F16 ? p.n_texels * p.channels : p.n_texels;
+    return timed(c, stream, [&]() -> int {
+        HIP_TRY(launch_lmp_pack(a, p.format, p.unpack, stream));
+        return MI_OK;
+    });
+}
+
+// host: HOST pointers, staged and blocking; else DEVICE pointers queued on `stream`
+static int pack_entry(const char* who, mi_ctx* c, const PackArgs& p, bool host, void* stream) {
+    MI_TRY(check_packed_format(who, p.format, p.channels, false));
+    if (!p.src || !p.dst) return fail(MI_ERR_INVALID, p.unpack ? "%s: packed and out_texels are required" : "%s: texels and out_packed are required", who);
+    if (p.n_texels > (1ull << 32)) return fail(MI_ERR_INVALID, "%s: n_texels %llu is above 2^32", who, (unsigned long long)p.n_texels);
+    if (!c) return fail(MI_ERR_INVALID, "ctx is NULL");
+    const size_t f32_bytes = (size_t)p.n_texels * p.channels * sizeof(float), packed_bytes = (size_t)p.n_texels * texel_bytes(p.format, p.channels);
+    const size_t src_bytes = p.unpack ? packed_bytes : f32_bytes, dst_bytes = p.unpack ? f32_bytes : packed_bytes;
+    if (!host) MI_TRY(check_no_overlap(who, { { p.dst, dst_bytes, p.unpack ? "out_texels" : "out_packed" } }, { { p.src, src_bytes } }));
+    if (p.n_texels == 0) return MI_OK;         // before any device call
+    if (!host) {
+        HIP_TRY(hipSetDevice(c->device));
+        return pack_device(c, p, (hipStream_t)stream);
+    }
+    const StageColumn cols[] = { { p.src, src_bytes, Stage::kIn }, { p.dst, dst_bytes, Stage::kOut } };
+    return staged(c, cols, [&](void* const* d) -> int {
+        PackArgs dp = p;
+        dp.src = d[0]; dp.dst = d[1];
+        return pack_device(c, dp, c->stream);
+    });
+}
+
+extern "C" int mi_lightmap_pack(mi_ctx* c, uint32_t format, uint32_t channels, uint64_t n_texels, const float* texels, void* out_packed) {
+    return pack_entry("mi_lightmap_pack", c, { format, channels, n_texels, texels, out_packed, false }, true, nullptr);
+}
+extern "C" int mi_lightmap_pack_device(mi_ctx* c, uint32_t format, uint32_t channels, uint64_t n_texels, const float* texels, void* out_packed,
+                                       void* stream) {
+    return pack_entry("mi_lightmap_pack_device", c, { format, channels, n_texels, texels, out_packed, false }, false, stream);
+}
+extern "C" int mi_lightmap_unpack(mi_ctx* c, uint32_t format, uint32_t channels, uint64_t n_texels, const void* packed, float* out_texels) {
+    return pack_entry("mi_lightmap_unpack", c, { format, channels, n_texels, packed, out_texels, true }, true, nullptr);
+}
+extern "C" int mi_lightmap_unpack_device(mi_ctx* c, uint32_t format, uint32_t channels, uint64_t n_texels, const void* packed, float* out_texels,
+                                         void* stream) {
+    return pack_entry("mi_lightmap_unpack_device", c, { format, channels, n_texels, packed, out_texels, true }, false, stream);
+}
+
+// The packed lookups: lod != NULL is the trilinear form over the mip plan; lod == NULL the level-0 form, which has no chain
+static int packed_lookup_entry(const char* who, mi_ctx* c, uint32_t format, LodArgs l, bool host, void* stream) {
+    MI_TRY(check_packed_format(who, format, l.channels, l.channels == 0));
+    l.format = format;
+    if (l.lod) return host ? lod_entry_host(who, c, l) : lod_entry_device(who, c, l, stream);
+    if (l.levels != 1 || l.mips || l.mip_valid)
+        return fail(MI_ERR_INVALID, "%s: lod == NULL reads level 0 alone: levels must be 1 (not %u) and mips, mip_valid NULL", who, l.levels);
+    LookupArgs k{ l.width, l.height, l.channels, l.image, l.valid, l.n, l.uv, l.normals, l.flags, l.out, l.out_weight, format };
+    return host ? lookup_entry_host(who, c, k) : lookup_entry_device(who, c, k, stream);
+}
+
+extern "C" int mi_lightmap_sample_packed(mi_ctx* c, uint32_t format, uint32_t width, uint32_t height, uint32_t channels, const void* image,
+                                         const uint8_t* valid, uint32_t levels, const void* mips, const uint8_t* mip_valid, uint32_t n,
+                                         const float* uv, const float* lod, uint32_t flags, float* out, float* out_weight) {
+    if (channels == 0) return fail(MI_ERR_INVALID, "mi_lightmap_sample_packed: channels 0 is not 3 or 27");
+    return packed_lookup_entry("mi_lightmap_sample_packed", c, format, { width, height, channels, image, valid, levels, mips, mip_valid, n, uv,
+                               nullptr, lod, flags, out, out_weight }, true, nullptr);
+}
+extern "C" int mi_lightmap_sample_packed_device(mi_ctx* c, uint32_t format, uint32_t width, uint32_t height, uint32_t channels,
+                                                const void* image, const uint8_t* valid, uint32_t levels, const void* mips,
+                                                const uint8_t* mip_valid, uint32_t n, const float* uv, const float* lod, uint32_t flags,
+                                                float* out, float* out_weight, void* stream) {
+    if (channels == 0) return fail(MI_ERR_INVALID, "mi_lightmap_sample_packed_device: channels 0 is not 3 or 27");
+    return packed_lookup_entry("mi_lightmap_sample_packed_device", c, format, { width, height, channels, image, valid, levels, mips, mip_valid,
+                               n, uv, nullptr, lod, flags, out, out_weight }, false, stream);
+}
+extern "C" int mi_lightmap_sh_sample_packed(mi_ctx* c, uint32_t format, uint32_t width, uint32_t height, const void* sh, const uint8_t* valid,
+                                            uint32_t levels, const void* mips, const uint8_t* mip_valid, uint32_t n, const float* uv,
+                                            const float* normals, const float* lod, uint32_t flags, float* out_irradiance, float* out_weight) {
+    return packed_lookup_entry("mi_lightmap_sh_sample_packed", c, format, { width, height, 0, sh, valid, levels, mips, mip_valid, n, uv, normals,
+                               lod, flags, out_irradiance, out_weight }, true, nullptr);
+}
+extern "C" int mi_lightmap_sh_sample_packed_device(mi_ctx* c, uint32_t format, uint32_t width, uint32_t height, const void* sh,
+                                                   const uint8_t* valid, uint32_t levels, const void* mips, const uint8_t* mip_valid,
+                                                   uint32_t n, const float* uv, const float* normals, const float* lod, uint32_t flags,
+                                                   float* out_irradiance, float* out_weight, void* stream) {
+    return packed_lookup_entry("mi_lightmap_sh_sample_packed_device", c, format, { width, height, 0, sh, valid, levels, mips, mip_valid, n, uv,
+                               normals, lod, flags, out_irradiance, out_weight }, false, stream);
 }
 
 // ------------------------------------------------------------------ variance-guided lightmap finishing

@@ -457,8 +457,9 @@ struct LshEvalArgs {
 
 // ---- lightmap lookup (mi_lightmap_sample, mi_lightmap_sh_sample; pt_kernels.hip "lml_*") ----
 // tracing.py lightmap_sample (lml_sample<3>, lml_sample<27>) and lightmap_sh_sample (lml_sh_sample): one lane per uv point
+// (the texels are f32 for the lml_* kernels and packed for the lmp_* ones below: the kernel's texel-fetch policy knows which)
 struct LmlArgs {
-    const float*   image;            // [H][W][C]: C = 3 or 27 (lml_sample<C>), 27 (lml_sh_sample)
+    const void*    image;            // [H][W][C]: C = 3 or 27 (lml_sample<C>), 27 (lml_sh_sample)
     const uint8_t* valid;            // [H][W] or nullptr = all valid: 0 = the texel takes no part and is not read
     const float*   uv;               // [n][2]
     const float*   normals;          // [n][3] (lml_sh_sample): all-zero = +0.0 and weight 0
@@ -485,9 +486,9 @@ struct LmmArgs {
 };
 // tracing.py lightmap_sample_lod (lml_sample_lod<3>, lml_sample_lod<27>) and lightmap_sh_sample_lod (lml_sh_sample_lod): one lane per point
 struct LmlLodArgs {
-    const float*   image;            // level 0, [H][W][C]
+    const void*    image;            // level 0, [H][W][C]
     const uint8_t* valid;            // level 0's mask or nullptr = all valid
-    const float*   mips;             // levels 1 .. L - 1 (nullptr when levels == 1)
+    const void*    mips;             // levels 1 .. L - 1 (nullptr when levels == 1)
     const uint8_t* mip_valid;        // their masks or nullptr = every texel of every level valid
     const float*   uv;               // [n][2]
     const float*   lod;              // [n]
@@ -497,6 +498,17 @@ struct LmlLodArgs {
     uint64_t       off[kMipMaxLevels];                        // level l starts at texel off[l] of mips (off[0] unused)
     uint32_t       lw[kMipMaxLevels], lh[kMipMaxLevels];      // the levels' sizes
     uint32_t levels, n;
+};
+
+// ---- packed lightmaps (mi_lightmap_pack, mi_lightmap_unpack, mi_lightmap_*_packed; pt_kernels.hip "lmp_*") ----
+// The storage formats (MI_LP_*): f16 texels are `channels` u16 each, tightly; an RGB9E5 texel is one u32 (3 channels only).  Both decode
+// to f32 exactly, so a packed lookup is the lml_* device code with another texel-fetch policy and takes LmlArgs / LmlLodArgs as they are.
+constexpr uint32_t kLpF16 = 1, kLpRgb9e5 = 2;
+// tracing.py lightmap_pack (lmp_pack<F>) and lightmap_unpack (lmp_unpack<F>): one lane per pair of f16 elements or per RGB9E5 texel
+struct LmpArgs {
+    const void* src;                 // pack: [n] f32; unpack: [n] packed items
+    void*       dst;                 // pack: [n] packed items; unpack: [n] f32
+    uint64_t    n;                   // f16: elements (texels x channels); RGB9E5: texels (three floats each)
 };
 
 // ---- variance-guided lightmap finishing (mi_lightmap_finish_var; pt_kernels.hip "lmv_*") ----

@@ -4465,6 +4465,31 @@ __global__ __launch_bounds__(kBlock) void lsh_eval(const LshEvalArgs a) {
 // indices clamped to the image, whatever the uv, the normals and the texels hold; a tap that takes no part is not read.  A 27-float
 // record is 108 bytes, so a record is only 4-byte aligned: the taps are read as lsh_atrous reads its records, float by float.
 
+// The lookup arithmetic exists once, in the lml_*_body functions below; what differs between the f32 kernels (lml_*) and the packed
+// ones (lmp_*) is the texel-fetch policy Tx: Tx::level(base, t, C) is where the texel t of a buffer starts, Tx(base, q, C) names texel q
+// behind it and [k] is its channel k as an f32.  Every policy decodes exactly, so a packed lookup is the f32 lookup of the unpacked
+// texels, bit for bit.  A texel is touched only through its Tx, which is made only for a tap that takes part.
+struct LmTexF32 {                                                  // C floats: read where they are used, as before
+    const float* p;
+    static __device__ __forceinline__ const void* level(const void* base, size_t t, int C) { return (const float*)base + t * C; }
+    __device__ __forceinline__ LmTexF32(const void* base, size_t q, int C) : p((const float*)base + q * C) {}
+    __device__ __forceinline__ float operator[](int k) const { return p[k]; }
+};
+struct LmTexF16 {                                                  // C halves, 2-byte aligned only (6 or 54 bytes a texel): one by one
+    const _Float16* p;
+    static __device__ __forceinline__ const void* level(const void* base, size_t t, int C) { return (const _Float16*)base + t * C; }
+    __device__ __forceinline__ LmTexF16(const void* base, size_t q, int C) : p((const _Float16*)base + q * C) {}
+    __device__ __forceinline__ float operator[](int k) const { return (float)p[k]; }
+};
+struct LmTexRgb9e5 {                                               // one dword: q_k * 2^(e - 24), the scale built from the exponent
+    uint32_t w; float s;
+    static __device__ __forceinline__ const void* level(const void* base, size_t t, int) { return (const uint32_t*)base + t; }
+    __device__ __forceinline__ LmTexRgb9e5(const void* base, size_t q, int) : w(((const uint32_t*)base)[q]) {
+        s = __uint_as_float(((w >> 27) + 103u) << 23);
+    }
+    __device__ __forceinline__ float operator[](int k) const { return (float)((w >> (9 * k)) & 511u) * s; }
+};
+
 // One axis of the bilinear form: pv_sample's index expressions.  fmaxf sends a NaN to 0, so the indices stay in range for any t.
 __device__ __forceinline__ void lml_axis(float t, int n, int (&i)[2], float (&w)[2]) {
     float g = t * (float)n - 0.5f;
@@ -4484,7 +4509,7 @@ __device__ __forceinline__ size_t lml_nearest(const LmlArgs& a, float u, float v
 }
 
 // lightmap_sample: C floats per texel (3: an image, 27: SH records), C + 1 accumulators
-template <int C> __global__ __launch_bounds__(kBlock) void lml_sample(const LmlArgs a) {
+template <class Tx, int C> __device__ __forceinline__ void lml_sample_body(const LmlArgs& a) {
     const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
     if (i >= a.n) return;
     const float u = a.uv[2 * (size_t)i], v = a.uv[2 * (size_t)i + 1];
@@ -4494,7 +4519,7 @@ template <int C> __global__ __launch_bounds__(kBlock) void lml_sample(const LmlA
     if (a.nearest) {
         const size_t q = lml_nearest(a, u, v);
         if (!a.valid || a.valid[q] != 0) {
-            const float* t = a.image + q * C;
+            const Tx t(a.image, q, C);
 #pragma unroll
             for (int k = 0; k < C; k++) acc[k] = t[k];             // as it stands: a -0.0 stays one
             sw = 1.0f;
@@ -4511,7 +4536,7 @@ template <int C> __global__ __launch_bounds__(kBlock) void lml_sample(const LmlA
                 const float w = wx[dx] * wy[dy];
                 const size_t q = (size_t)iy[dy] * a.width + (size_t)ix[dx];
                 if (!(w > 0.0f) || (a.valid && a.valid[q] == 0)) continue;
-                const float* t = a.image + q * C;
+                const Tx t(a.image, q, C);
 #pragma unroll
                 for (int k = 0; k < C; k++) acc[k] = acc[k] + w * t[k];
                 sw = sw + w;
@@ -4526,10 +4551,12 @@ template <int C> __global__ __launch_bounds__(kBlock) void lml_sample(const LmlA
     for (int k = 0; k < C; k++) o[k] = acc[k];
     if (a.out_weight) a.out_weight[i] = sw;
 }
+template <int C> __global__ __launch_bounds__(kBlock) void lml_sample(const LmlArgs a) { lml_sample_body<LmTexF32, C>(a); }
+template <class Tx, int C> __global__ __launch_bounds__(kBlock) void lmp_sample(const LmlArgs a) { lml_sample_body<Tx, C>(a); }
 
 // lightmap_sh_sample, the fused form: every tap's record is turned into its irradiance e at the point's normal (lsh_eval's arithmetic)
 // and the three e are what is interpolated — pv_sample's order with four taps: 3 + 1 accumulators, never an interpolated record.
-__global__ __launch_bounds__(kBlock) void lml_sh_sample(const LmlArgs a) {
+template <class Tx> __device__ __forceinline__ void lml_sh_sample_body(const LmlArgs& a) {
     const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
     if (i >= a.n) return;
     const float u = a.uv[2 * (size_t)i], v = a.uv[2 * (size_t)i + 1];
@@ -4542,7 +4569,7 @@ __global__ __launch_bounds__(kBlock) void lml_sh_sample(const LmlArgs a) {
         const float x = nx / l, y = ny / l, z = nz / l;
         const float b[9] = { 1.0f, y, z, x, x * y, y * z, 3.0f * (z * z) - 1.0f, x * z, x * x - y * y };
         auto eval = [&](size_t q, float (&e)[3]) {
-            const float* sh = a.image + q * kShFloats;
+            const Tx sh(a.image, q, kShFloats);
 #pragma unroll
             for (int c = 0; c < 3; c++) {
                 float s = b[0] * (sh[c] * K[0]);
@@ -4582,6 +4609,8 @@ __global__ __launch_bounds__(kBlock) void lml_sh_sample(const LmlArgs a) {
     for (int c = 0; c < 3; c++) a.out[3 * (size_t)i + c] = E[c];
     if (a.out_weight) a.out_weight[i] = sw;
 }
+__global__ __launch_bounds__(kBlock) void lml_sh_sample(const LmlArgs a) { lml_sh_sample_body<LmTexF32>(a); }
+template <class Tx> __global__ __launch_bounds__(kBlock) void lmp_sh_sample(const LmlArgs a) { lml_sh_sample_body<Tx>(a); }
 
 // ---------------------------------------------------------------- lightmap mips (mi_lightmap_mips)
 // tracing.py lightmap_mips on the device.  One block takes a 32 x 32 tile of the level it reads (kTile, the tile of the atlas and finish
@@ -4663,7 +4692,7 @@ template <int C> __global__ __launch_bounds__(kBlock) void lmm_reduce(const LmmA
 // tracing.py lightmap_sample_lod and lightmap_sh_sample_lod on the device: the lookup above over two levels of a mip chain.  One lane per
 // point, the helpers' operations in the helpers' order; every address is made from indices clamped to their level, whatever the uv,
 // the lod, the normals and the texels hold; a level or a tap that takes no part is not read.  (lml_sample and lml_sh_sample do not go
-// through these functions: their code objects stay as they were.)
+// through these functions.)  Tx: the texel-fetch policy of the lookup section above.
 
 // One axis at level l: n0 texels at level 0, s = 2^-l (exact), n texels at level l; lml_axis' clamp and index expressions
 __device__ __forceinline__ void lml_axis_lod(float t, int n0, float s, int n, int (&i)[2], float (&w)[2]) {
@@ -4683,10 +4712,10 @@ __device__ __forceinline__ void lml_levels(float lod, int L, int (&l)[2], float 
     w[0] = 1.0f - f; w[1] = f;
 }
 // The tap loop of one level, written once: tap(texels of the level, texel index, weight) for every tap that takes part, dy outer, dx inner
-template <int C, class Tap> __device__ __forceinline__ void lml_level_taps(const LmlLodArgs& a, int l, float wl, float u, float v, Tap tap) {
+template <class Tx, int C, class Tap> __device__ __forceinline__ void lml_level_taps(const LmlLodArgs& a, int l, float wl, float u, float v, Tap tap) {
     const int W = (int)a.lw[l], H = (int)a.lh[l];
     const float s = __uint_as_float((uint32_t)(127 - l) << 23);                  // 2^-l, l <= 15
-    const float* texels = l == 0 ? a.image : a.mips + (size_t)a.off[l] * C;
+    const void* texels = l == 0 ? a.image : Tx::level(a.mips, (size_t)a.off[l], C);
     const uint8_t* valid = l == 0 ? a.valid : a.mip_valid ? a.mip_valid + (size_t)a.off[l] : nullptr;
     int ix[2], iy[2];
     float wx[2], wy[2];
@@ -4704,7 +4733,7 @@ template <int C, class Tap> __device__ __forceinline__ void lml_level_taps(const
 }
 
 // lightmap_sample_lod: C + 1 accumulators over the up to eight taps
-template <int C> __global__ __launch_bounds__(kBlock) void lml_sample_lod(const LmlLodArgs a) {
+template <class Tx, int C> __device__ __forceinline__ void lml_sample_lod_body(const LmlLodArgs& a) {
     const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
     if (i >= a.n) return;
     const float u = a.uv[2 * (size_t)i], v = a.uv[2 * (size_t)i + 1];
@@ -4716,8 +4745,8 @@ template <int C> __global__ __launch_bounds__(kBlock) void lml_sample_lod(const 
     for (int k = 0; k < C; k++) acc[k] = 0.0f;
     for (int side = 0; side < 2; side++) {
         if (!(wl[side] > 0.0f)) continue;
-        lml_level_taps<C>(a, lv[side], wl[side], u, v, [&](const float* texels, size_t q, float w) {
-            const float* t = texels + q * C;
+        lml_level_taps<Tx, C>(a, lv[side], wl[side], u, v, [&](const void* texels, size_t q, float w) {
+            const Tx t(texels, q, C);
 #pragma unroll
             for (int k = 0; k < C; k++) acc[k] = acc[k] + w * t[k];
             sw = sw + w;
@@ -4732,9 +4761,11 @@ template <int C> __global__ __launch_bounds__(kBlock) void lml_sample_lod(const 
     for (int k = 0; k < C; k++) o[k] = acc[k];
     if (a.out_weight) a.out_weight[i] = sw;
 }
+template <int C> __global__ __launch_bounds__(kBlock) void lml_sample_lod(const LmlLodArgs a) { lml_sample_lod_body<LmTexF32, C>(a); }
+template <class Tx, int C> __global__ __launch_bounds__(kBlock) void lmp_sample_lod(const LmlLodArgs a) { lml_sample_lod_body<Tx, C>(a); }
 
 // lightmap_sh_sample_lod: every tap's record becomes its irradiance e at the point's normal (lml_sh_sample's eval) before it is weighted
-__global__ __launch_bounds__(kBlock) void lml_sh_sample_lod(const LmlLodArgs a) {
+template <class Tx> __device__ __forceinline__ void lml_sh_sample_lod_body(const LmlLodArgs& a) {
     const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
     if (i >= a.n) return;
     const float u = a.uv[2 * (size_t)i], v = a.uv[2 * (size_t)i + 1];
@@ -4751,8 +4782,8 @@ __global__ __launch_bounds__(kBlock) void lml_sh_sample_lod(const LmlLodArgs a) 
         lml_levels(a.lod[i], (int)a.levels, lv, wl);
         for (int side = 0; side < 2; side++) {
             if (!(wl[side] > 0.0f)) continue;
-            lml_level_taps<kShFloats>(a, lv[side], wl[side], u, v, [&](const float* texels, size_t q, float w) {
-                const float* sh = texels + q * kShFloats;
+            lml_level_taps<Tx, kShFloats>(a, lv[side], wl[side], u, v, [&](const void* texels, size_t q, float w) {
+                const Tx sh(texels, q, kShFloats);
 #pragma unroll
                 for (int c = 0; c < 3; c++) {
                     float s = b[0] * (sh[c] * K[0]);
@@ -4771,6 +4802,82 @@ __global__ __launch_bounds__(kBlock) void lml_sh_sample_lod(const LmlLodArgs a) 
 #pragma unroll
     for (int c = 0; c < 3; c++) a.out[3 * (size_t)i + c] = E[c];
     if (a.out_weight) a.out_weight[i] = sw;
+}
+__global__ __launch_bounds__(kBlock) void lml_sh_sample_lod(const LmlLodArgs a) { lml_sh_sample_lod_body<LmTexF32>(a); }
+template <class Tx> __global__ __launch_bounds__(kBlock) void lmp_sh_sample_lod(const LmlLodArgs a) { lml_sh_sample_lod_body<Tx>(a); }
+
+// ---------------------------------------------------------------- packed lightmaps (mi_lightmap_pack, mi_lightmap_unpack)
+// tracing.py lightmap_pack and lightmap_unpack on the device: streaming, one lane per pair of f16 elements or per RGB9E5 texel, consecutive lanes
+// on consecutive items, no LDS, nothing across lanes, 64-bit indices.  (The packed lookups are the lmp_* kernels beside the lml_* ones.)
+// Pure f32 with no fused multiply-add (the pragma above) and hipcc's default denormal modes: f16 subnormals are kept.
+template <uint32_t F> __global__ __launch_bounds__(kBlock) void lmp_pack(const LmpArgs a);
+template <uint32_t F> __global__ __launch_bounds__(kBlock) void lmp_unpack(const LmpArgs a);
+
+// f16: a NaN is 0x7E00 by a select; everything else is clamped to +-65504 and converted round-to-nearest-even, so no infinity is written
+__device__ __forceinline__ uint32_t lmp_f16_bits(float x) {
+    const _Float16 h = (_Float16)fminf(fmaxf(x, -65504.0f), 65504.0f);
+    uint16_t bits;
+    __builtin_memcpy(&bits, &h, sizeof(bits));
+    return x != x ? 0x7E00u : (uint32_t)bits;
+}
+__device__ __forceinline__ float lmp_f16_value(uint32_t bits) {
+    const uint16_t b = (uint16_t)bits;
+    _Float16 h;
+    __builtin_memcpy(&h, &b, sizeof(h));
+    return (float)h;
+}
+// One lane per PAIR of elements (2 i, 2 i + 1), so that a wave moves whole dwords on the packed side: one dword per lane where the packed
+// array is 4-byte aligned (uniform over the launch), two halves where it is only 2-byte aligned; the last lane of an odd count moves one.
+template <> __global__ __launch_bounds__(kBlock) void lmp_pack<kLpF16>(const LmpArgs a) {
+    const size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x, e = 2 * i;
+    if (e >= a.n) return;
+    const float* src = (const float*)a.src;
+    uint16_t* dst = (uint16_t*)a.dst;
+    const uint32_t lo = lmp_f16_bits(src[e]);
+    if (e + 1 >= a.n) { dst[e] = (uint16_t)lo; return; }
+    const uint32_t hi = lmp_f16_bits(src[e + 1]);
+    if (((uintptr_t)a.dst & 3u) == 0) ((uint32_t*)a.dst)[i] = lo | hi << 16;
+    else { dst[e] = (uint16_t)lo; dst[e + 1] = (uint16_t)hi; }
+}
+template <> __global__ __launch_bounds__(kBlock) void lmp_unpack<kLpF16>(const LmpArgs a) {
+    const size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x, e = 2 * i;
+    if (e >= a.n) return;
+    const uint16_t* src = (const uint16_t*)a.src;
+    float* dst = (float*)a.dst;
+    if (e + 1 >= a.n) { dst[e] = lmp_f16_value(src[e]); return; }
+    uint32_t w;
+    if (((uintptr_t)a.src & 3u) == 0) w = ((const uint32_t*)a.src)[i];
+    else w = (uint32_t)src[e] | (uint32_t)src[e + 1] << 16;
+    dst[e] = lmp_f16_value(w & 0xFFFFu);
+    dst[e + 1] = lmp_f16_value(w >> 16);
+}
+
+// RGB9E5 (N = 9, B = 15, largest value 65408): the shared exponent from the largest channel's own, one rounding per channel (+ 0.5f)
+template <> __global__ __launch_bounds__(kBlock) void lmp_pack<kLpRgb9e5>(const LmpArgs a) {
+    const size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x;
+    if (i >= a.n) return;
+    const float* t = (const float*)a.src + 3 * i;
+    float c[3];
+#pragma unroll
+    for (int k = 0; k < 3; k++) { const float x = t[k]; c[k] = x != x ? 0.0f : fminf(fmaxf(x, 0.0f), 65408.0f); }
+    const float m = fmaxf(fmaxf(c[0], c[1]), c[2]);
+    const int eb = (int)((__float_as_uint(m) >> 23) & 255u) - 127;
+    const int ep = max(eb, -16) + 16;                                              // 0 .. 31: m < 2^16
+    const float ms = floorf(m * __uint_as_float((uint32_t)(151 - ep) << 23) + 0.5f);       // m * 2^(24 - ep)
+    const int e = ep + (ms == 512.0f ? 1 : 0);                                     // (never from 31: 65408 * 2^-7 = 511)
+    const float s = __uint_as_float((uint32_t)(151 - e) << 23);                    // 2^(24 - e)
+    uint32_t w = (uint32_t)e << 27;
+#pragma unroll
+    for (int k = 0; k < 3; k++) w |= (uint32_t)floorf(c[k] * s + 0.5f) << (9 * k);
+    ((uint32_t*)a.dst)[i] = w;
+}
+template <> __global__ __launch_bounds__(kBlock) void lmp_unpack<kLpRgb9e5>(const LmpArgs a) {
+    const size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x;
+    if (i >= a.n) return;
+    const LmTexRgb9e5 t(a.src, i, 3);
+    float* o = (float*)a.dst + 3 * i;
+#pragma unroll
+    for (int k = 0; k < 3; k++) o[k] = t[k];
 }
 
 // ---------------------------------------------------------------- launch wrappers
@@ -4819,6 +4926,31 @@ hipError_t launch_lml_sample_lod(const LmlLodArgs& a, uint32_t channels, hipStre
     if (channels == 0) return launch_per_item(lml_sh_sample_lod, a.n, stream, a);
     if (channels == 3) return launch_per_item(lml_sample_lod<3>, a.n, stream, a);
     if (channels == kShFloats) return launch_per_item(lml_sample_lod<kShFloats>, a.n, stream, a);
+    return hipErrorInvalidValue;
+}
+// packed lightmaps: `format` MI_LP_*; a.n counts f16 elements or RGB9E5 texels
+hipError_t launch_lmp_pack(const LmpArgs& a, uint32_t format, bool unpack, hipStream_t stream) {
+    if ((a.n + kBlock - 1) / kBlock > 0x7fffffffull) return hipErrorInvalidValue;
+    if (format == kLpF16) return unpack ? launch_per_item(lmp_unpack<kLpF16>, (a.n + 1) / 2, stream, a) : launch_per_item(lmp_pack<kLpF16>, (a.n + 1) / 2, stream, a);
+    if (format == kLpRgb9e5) return unpack ? launch_per_item(lmp_unpack<kLpRgb9e5>, a.n, stream, a) : launch_per_item(lmp_pack<kLpRgb9e5>, a.n, stream, a);
+    return hipErrorInvalidValue;
+}
+// the packed lookups: launch_lml_sample's and launch_lml_sample_lod's forms per format (RGB9E5: 3 channels only)
+hipError_t launch_lmp_sample(const LmlArgs& a, uint32_t format, uint32_t channels, hipStream_t stream) {
+    if (format == kLpRgb9e5 && channels == 3) return launch_per_item(lmp_sample<LmTexRgb9e5, 3>, a.n, stream, a);
+    if (format != kLpF16) return hipErrorInvalidValue;
+    if (channels == 0) return launch_per_item(lmp_sh_sample<LmTexF16>, a.n, stream, a);
+    if (channels == 3) return launch_per_item(lmp_sample<LmTexF16, 3>, a.n, stream, a);
+    if (channels == kShFloats) return launch_per_item(lmp_sample<LmTexF16, kShFloats>, a.n, stream, a);
+    return hipErrorInvalidValue;
+}
+hipError_t launch_lmp_sample_lod(const LmlLodArgs& a, uint32_t format, uint32_t channels, hipStream_t stream) {
+    if (a.levels == 0 || a.levels > kMipMaxLevels) return hipErrorInvalidValue;
+    if (format == kLpRgb9e5 && channels == 3) return launch_per_item(lmp_sample_lod<LmTexRgb9e5, 3>, a.n, stream, a);
+    if (format != kLpF16) return hipErrorInvalidValue;
+    if (channels == 0) return launch_per_item(lmp_sh_sample_lod<LmTexF16>, a.n, stream, a);
+    if (channels == 3) return launch_per_item(lmp_sample_lod<LmTexF16, 3>, a.n, stream, a);
+    if (channels == kShFloats) return launch_per_item(lmp_sample_lod<LmTexF16, kShFloats>, a.n, stream, a);
     return hipErrorInvalidValue;
 }
 // The plain form's level.  lmf_atrous stages through LDS when `lds`; a window above 64 KB needs the opt-in, which

@@ -3,7 +3,9 @@
 // flatten -> mi_scene_upload -> mi_render through the C ABI of include/mi_rt.h.  Errors that the
 // reference raises as panics surface as std::runtime_error carrying mi_last_error().
 #pragma once
+#include <algorithm>
 #include <cmath>
+#include <cstring>
 #include <stdexcept>
 #include <string>
 #include <vector>
@@ -577,7 +579,146 @@ struct Scene : Intersectable {                         // tracing.rs:213-218; `i
         return out;
     }
 
+    // ---- packed lightmaps (include/mi_rt.h "packed lightmaps"): f16 and RGB9E5 storage and the lookups that read it ----
+    // pack_lightmap and unpack_lightmap are the formats' definitions on the host, in integer and f32 arithmetic alone: a storage
+    // conversion needs no device, and the bytes equal mi_lightmap_pack's and mi_lightmap_unpack's bit for bit (a NaN widens to a NaN).
+    // `texels` is [n][channels] f32, channels 3 or 27 (MI_LP_RGB9E5: 3); the result is n * channels u16 for MI_LP_F16, n u32 for
+    // MI_LP_RGB9E5, as raw bytes in the layout the C calls take.
+    static std::vector<uint8_t> pack_lightmap(const std::vector<float>& texels, uint32_t format, uint32_t channels) {
+        check_packed_format(format, channels);
+        const size_t n = texels.size() / channels;
+        if (texels.size() != n * channels) throw std::runtime_error("mi_rt: texels must be [n][channels]");
+        std::vector<uint8_t> out(n * (format == MI_LP_F16 ? 2u * channels : 4u));
+        if (format == MI_LP_F16) {
+            for (size_t i = 0; i < texels.size(); i++) {
+                const uint16_t h = f16_bits(texels[i]);
+                std::memcpy(&out[2 * i], &h, 2);
+            }
+            return out;
+        }
+        for (size_t i = 0; i < n; i++) {
+            float c[3];
+            for (int k = 0; k < 3; k++) { const float x = texels[3 * i + k]; c[k] = x != x ? 0.0f : std::fmin(std::fmax(x, 0.0f), 65408.0f); }
+            const float m = std::fmax(std::fmax(c[0], c[1]), c[2]);
+            const int eb = (int)((f32_bits(m) >> 23) & 255u) - 127;
+            const int ep = std::max(eb, -16) + 16;
+            const float ms = std::floor(m * pow2(24 - ep) + 0.5f);
+            const int e = ep + (ms == 512.0f ? 1 : 0);
+            const float s = pow2(24 - e);
+            uint32_t w = (uint32_t)e << 27;
+            for (int k = 0; k < 3; k++) w |= (uint32_t)std::floor(c[k] * s + 0.5f) << (9 * k);
+            std::memcpy(&out[4 * i], &w, 4);
+        }
+        return out;
+    }
+
+    // The exact decode of pack_lightmap's bytes: [n][channels] f32
+    static std::vector<float> unpack_lightmap(const std::vector<uint8_t>& packed, uint32_t format, uint32_t channels) {
+        check_packed_format(format, channels);
+        const size_t bytes = format == MI_LP_F16 ? 2u * channels : 4u, n = packed.size() / bytes;
+        if (packed.size() != n * bytes) throw std::runtime_error("mi_rt: packed must hold whole texels");
+        std::vector<float> out(n * channels);
+        if (format == MI_LP_F16) {
+            for (size_t i = 0; i < out.size(); i++) {
+                uint16_t h;
+                std::memcpy(&h, &packed[2 * i], 2);
+                const uint32_t sign = (uint32_t)(h & 0x8000u) << 16, ex = (h >> 10) & 31u, man = h & 1023u;
+                if (ex == 31u) out[i] = bits_f32(sign | 0x7F800000u | (man ? 0x00400000u | man << 13 : 0u));        // inf, or a quiet NaN
+                else if (ex) out[i] = bits_f32(sign | (ex + 112u) << 23 | man << 13);
+                else out[i] = bits_f32(sign | f32_bits((float)man * pow2(-24)));                                   // a subnormal, or zero
+            }
+            return out;
+        }
+        for (size_t i = 0; i < n; i++) {
+            uint32_t w;
+            std::memcpy(&w, &packed[4 * i], 4);
+            const float s = pow2((int)(w >> 27) - 24);
+            for (int k = 0; k < 3; k++) out[3 * i + k] = (float)((w >> (9 * k)) & 511u) * s;
+        }
+        return out;
+    }
+
+    // Read a packed lightmap at uv points through mi_lightmap_sample_packed: sample_lightmap_lod's arguments with `image` and `mips`
+    // as pack_lightmap made them; an empty `lod` reads level 0 alone (then levels must be 1 and mips empty, and `nearest` is allowed).
+    // Returns [n][channels]; equals sample_lightmap(_lod) on the unpacked texels bit for bit.  Needs no scene: a static member.
+    static std::vector<float> sample_lightmap_packed(uint32_t format, const std::vector<uint8_t>& image, const std::vector<uint8_t>& valid,
+                                                     uint32_t width, uint32_t height, uint32_t channels, uint32_t levels,
+                                                     const std::vector<uint8_t>& mips, const std::vector<uint8_t>& mip_valid,
+                                                     const std::vector<float>& uv, const std::vector<float>& lod, bool nearest = false,
+                                                     int device = 0, std::vector<float>* weight = nullptr) {
+        return packed_lookup(format, image, valid, width, height, channels, levels, mips, mip_valid, uv, nullptr, lod, nearest, device, weight);
+    }
+
+    // The irradiance of a directional lightmap packed as MI_LP_F16 through mi_lightmap_sh_sample_packed: sample_lightmap_sh_lod's
+    // arguments with packed records; an empty `lod` reads level 0 alone.  Returns [n][3].  Needs no scene: a static member.
+    static std::vector<float> sample_lightmap_sh_packed(uint32_t format, const std::vector<uint8_t>& sh, const std::vector<uint8_t>& valid,
+                                                        uint32_t width, uint32_t height, uint32_t levels, const std::vector<uint8_t>& mips,
+                                                        const std::vector<uint8_t>& mip_valid, const std::vector<float>& uv,
+                                                        const std::vector<float>& normals, const std::vector<float>& lod,
+                                                        bool nearest = false, int device = 0, std::vector<float>* weight = nullptr) {
+        if (normals.size() != uv.size() / 2 * 3) throw std::runtime_error("mi_rt: normals must be [n][3]");
+        return packed_lookup(format, sh, valid, width, height, 0, levels, mips, mip_valid, uv, &normals, lod, nearest, device, weight);
+    }
+
 private:
+    static uint32_t f32_bits(float x) { uint32_t u; std::memcpy(&u, &x, 4); return u; }
+    static float bits_f32(uint32_t u) { float x; std::memcpy(&x, &u, 4); return x; }
+    static float pow2(int e) { return bits_f32((uint32_t)(e + 127) << 23); }                 // exact, -126 <= e <= 127
+
+    static void check_packed_format(uint32_t format, uint32_t channels) {
+        if (format != MI_LP_F16 && format != MI_LP_RGB9E5) throw std::runtime_error("mi_rt: format must be MI_LP_F16 or MI_LP_RGB9E5");
+        if (channels != 3 && channels != 27) throw std::runtime_error("mi_rt: channels must be 3 or 27");
+        if (format == MI_LP_RGB9E5 && channels != 3) throw std::runtime_error("mi_rt: MI_LP_RGB9E5 holds 3 unsigned channels");
+    }
+
+    // f32 -> binary16 bits as the header defines them: a NaN is 0x7E00, everything else is clamped to +-65504 and rounded to nearest even
+    static uint16_t f16_bits(float x) {
+        if (x != x) return 0x7E00u;
+        const float c = std::fmin(std::fmax(x, -65504.0f), 65504.0f);
+        const uint32_t u = f32_bits(c), sign = (u >> 16) & 0x8000u, mag = u & 0x7FFFFFFFu;
+        if (mag >= 0x38800000u) {                              // a normal f16: drop 13 bits of the significand, to nearest even
+            const uint32_t r = mag + 0x0FFFu + ((mag >> 13) & 1u);
+            return (uint16_t)(sign | ((r >> 13) - (112u << 10)));
+        }
+        if (mag < 0x33000000u) return (uint16_t)sign;          // below 2^-25: zero (2^-25 itself is a tie, to the even zero, below)
+        const uint32_t man = (mag & 0x007FFFFFu) | 0x00800000u, shift = 126u - (mag >> 23);     // 14 .. 24: the value is man * 2^-(shift + 10) steps of 2^-24
+        const uint32_t q = man >> shift, rest = man & ((1u << shift) - 1u), half = 1u << (shift - 1);
+        return (uint16_t)(sign | (q + ((rest > half || (rest == half && (q & 1u))) ? 1u : 0u)));
+    }
+
+    static std::vector<float> packed_lookup(uint32_t format, const std::vector<uint8_t>& image, const std::vector<uint8_t>& valid, uint32_t width,
+                                            uint32_t height, uint32_t channels, uint32_t levels, const std::vector<uint8_t>& mips,
+                                            const std::vector<uint8_t>& mip_valid, const std::vector<float>& uv,
+                                            const std::vector<float>* normals, const std::vector<float>& lod, bool nearest, int device,
+                                            std::vector<float>* weight) {
+        const uint32_t in_c = channels ? channels : 27u, out_c = channels ? channels : 3u;
+        check_packed_format(format, in_c);
+        const size_t texels = (size_t)width * height, n = uv.size() / 2, made = mip_texels(width, height, levels);
+        const size_t bytes = format == MI_LP_F16 ? 2u * in_c : 4u;
+        if (image.size() != texels * bytes || (!valid.empty() && valid.size() != texels) || uv.size() != n * 2 || (!lod.empty() && lod.size() != n) ||
+            mips.size() != made * bytes || (!mip_valid.empty() && mip_valid.size() != made))
+            throw std::runtime_error("mi_rt: image must be [H][W] packed texels, valid empty or [H][W], mips and mip_valid the layout's, uv [n][2], lod empty or [n]");
+        std::vector<float> out(n * out_c);
+        if (weight) weight->resize(n);
+        if (n == 0) return out;                              // (an empty vector has no address to pass)
+        mi_ctx* ctx = nullptr;
+        mi_check(mi_ctx_create(device, &ctx));
+        const uint8_t* v = valid.empty() ? nullptr : valid.data();
+        const uint8_t* m = mips.empty() ? nullptr : mips.data();
+        const uint8_t* mv = mip_valid.empty() ? nullptr : mip_valid.data();
+        const float* d = lod.empty() ? nullptr : lod.data();
+        float* ow = weight ? weight->data() : nullptr;
+        const uint32_t flags = nearest ? MI_LS_NEAREST : 0u;
+        const int rc = normals ? mi_lightmap_sh_sample_packed(ctx, format, width, height, image.data(), v, levels, m, mv, (uint32_t)n, uv.data(),
+                                                              normals->data(), d, flags, out.data(), ow)
+                               : mi_lightmap_sample_packed(ctx, format, width, height, channels, image.data(), v, levels, m, mv, (uint32_t)n,
+                                                           uv.data(), d, flags, out.data(), ow);
+        const std::string err = rc == MI_OK ? "" : mi_last_error();
+        mi_ctx_destroy(ctx);
+        if (rc != MI_OK) throw std::runtime_error("mi_rt: " + err);
+        return out;
+    }
+
     // the texels of levels 1 .. of a chain
     static size_t mip_texels(uint32_t width, uint32_t height, uint32_t levels) {
         const std::vector<MipLevel> layout = lightmap_mip_layout(width, height, levels);

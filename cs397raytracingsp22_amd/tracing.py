@@ -1259,6 +1259,148 @@ def lightmap_sh_sample_lod(chain, uv, normals, lod, valid_chain=None, flags: int
     return np.ascontiguousarray(E.reshape(shape + (3,))), np.ascontiguousarray(sw.reshape(shape))
 
 
+# ---- packed lightmaps: f16 and RGB9E5 storage (mi_lightmap_pack, mi_lightmap_unpack, mi_lightmap_*_packed) ----
+# Both formats decode to f32 exactly, so a packed lookup IS the f32 lookup of the unpacked texels; the only arithmetic of their own is
+# in the two encoders below.
+
+def _check_packed_format(format, channels=None, sh: bool = False) -> int:
+    """What every packed call checks of its format: abi.MI_LP_F16 (3 or 27 channels) or abi.MI_LP_RGB9E5 (3 channels, not the SH
+    form); 0, the f32 of the unpacked calls, is refused.  Returns the format; raises ValueError."""
+    fmt = int(format)
+    if fmt not in (abi.MI_LP_F16, abi.MI_LP_RGB9E5):
+        raise ValueError(f"format {format} is not MI_LP_F16 or MI_LP_RGB9E5 (f32 texels take the unpacked calls)")
+    if sh and fmt != abi.MI_LP_F16:
+        raise ValueError("SH coefficients are signed: only MI_LP_F16 holds them")
+    if channels is not None:
+        if channels not in (3, 27):
+            raise ValueError(f"channels must be 3 or 27, got {channels}")
+        if fmt == abi.MI_LP_RGB9E5 and channels != 3:
+            raise ValueError(f"MI_LP_RGB9E5 holds 3 unsigned channels, not {channels} (SH records pack as MI_LP_F16)")
+    return fmt
+
+
+def _check_packed_array(packed, format):
+    """Packed texels are uint16 [..., 3 or 27] (abi.MI_LP_F16) or uint32 [...] (abi.MI_LP_RGB9E5).  Returns (format, contiguous array)."""
+    fmt = _check_packed_format(format)
+    p = np.ascontiguousarray(packed)
+    if fmt == abi.MI_LP_F16 and (p.dtype != np.uint16 or p.ndim < 1 or p.shape[-1] not in (3, 27)):
+        raise ValueError(f"MI_LP_F16 texels must be uint16 [..., 3] or [..., 27], got {p.dtype} {p.shape}")
+    if fmt == abi.MI_LP_RGB9E5 and p.dtype != np.uint32:
+        raise ValueError(f"MI_LP_RGB9E5 texels must be uint32, got {p.dtype}")
+    return fmt, p
+
+
+def _pow2_f32(e):
+    """2^e as an exact f32 built from its exponent field, -126 <= e <= 127 (an integer array)"""
+    return ((np.asarray(e, np.int64) + 127).astype(np.uint32) << np.uint32(23)).view(np.float32)
+
+
+def lightmap_pack(texels, format):
+    """Pack f32 lightmap texels on the host (numpy only).  This is the DEFINITION of mi_lightmap_pack, which equals it bit for bit.
+    `texels` [..., C] f32 with C = 3 or 27 (an [..., 9, 3] table of SH records packs to the same bytes); any leading shape: a level, a
+    whole mips buffer, a list of texels.  Returns uint16 [..., C] bit patterns for abi.MI_LP_F16 (not np.float16, so NaNs compare) or
+    uint32 [...] for abi.MI_LP_RGB9E5 (C = 3 only).
+    f16, per float x: a NaN gives 0x7E00 (a select, not a conversion); otherwise c = fmin(fmax(x, -65504), 65504) converted
+    round-to-nearest-even to binary16.  Subnormal results and the sign of zero are kept; infinities and everything beyond +-65504 become
+    0x7BFF / 0xFBFF, so no infinity is ever written.
+    RGB9E5 (N = 9, B = 15, largest value 65408), all f32, one rounding per operation: per channel c = 0 for a NaN, else
+    fmin(fmax(x, 0), 65408); m = max(c_r, c_g, c_b); eb = ((bits(m) >> 23) & 255) - 127 (floor(log2 m); -127 for a zero or subnormal m);
+    ep = max(eb, -16) + 16; ms = floor(m 2^(24 - ep) + 0.5); e = ep + (ms == 512); q_k = floor(c_k 2^(24 - e) + 0.5);
+    word = q_r | q_g << 9 | q_b << 18 | e << 27.  The products are exact; the one rounding per channel is the + 0.5, so 0.5 - 2^-25
+    scaled rounds up: that is the definition."""
+    f32 = np.float32
+    x = np.asarray(texels, f32)
+    if x.ndim < 1 or x.shape[-1] not in (3, 27):
+        raise ValueError(f"texels must be [..., 3] or [..., 27], got {x.shape}")
+    fmt = _check_packed_format(format, x.shape[-1])
+    with np.errstate(all="ignore"):
+        if fmt == abi.MI_LP_F16:
+            c = np.fmin(np.fmax(x, f32(-65504.0)), f32(65504.0))
+            bits = c.astype(np.float16).view(np.uint16)
+            return np.ascontiguousarray(np.where(x != x, np.uint16(0x7E00), bits))
+        c = np.where(x != x, f32(0.0), np.fmin(np.fmax(x, f32(0.0)), f32(65408.0)))
+        m = np.fmax(np.fmax(c[..., 0], c[..., 1]), c[..., 2])
+        eb = ((np.ascontiguousarray(m).view(np.uint32) >> np.uint32(23)) & np.uint32(255)).astype(np.int64) - 127
+        ep = np.maximum(eb, -16) + 16
+        ms = np.floor(m * _pow2_f32(24 - ep) + f32(0.5))
+        e = ep + (ms == f32(512.0))
+        q = np.floor(c * _pow2_f32(24 - e)[..., None] + f32(0.5)).astype(np.uint32)
+        assert ms.dtype == f32
+    word = q[..., 0] | q[..., 1] << np.uint32(9) | q[..., 2] << np.uint32(18) | e.astype(np.uint32) << np.uint32(27)
+    return np.ascontiguousarray(word).reshape(x.shape[:-1])
+
+
+def lightmap_unpack(packed, format):
+    """Unpack packed lightmap texels on the host (numpy only).  This is the DEFINITION of mi_lightmap_unpack; both decodes are exact.
+    abi.MI_LP_F16: `packed` uint16 [..., C] (C = 3 or 27) gives f32 [..., C], the binary16 -> f32 widening.  abi.MI_LP_RGB9E5: uint32
+    [...] gives f32 [..., 3], (float)q_k 2^(e - 24)."""
+    fmt, p = _check_packed_array(packed, format)
+    if fmt == abi.MI_LP_F16:
+        return p.view(np.float16).astype(np.float32)
+    s = _pow2_f32((p >> np.uint32(27)).astype(np.int64) - 24)
+    q = np.stack([(p >> np.uint32(9 * k)) & np.uint32(511) for k in range(3)], axis=-1)
+    return np.ascontiguousarray(q.astype(np.float32) * s[..., None])
+
+
+def check_lightmap_packed(packed_chain, format, uv, lod=None, valid_chain=None, flags: int = 0, normals=None, sh: bool = False):
+    """Input checking of the packed lookups (mi_lightmap_sample_packed; with sh: mi_lightmap_sh_sample_packed), no GPU needed.
+    `packed_chain` is a list of packed levels as lightmap_pack returns them (uint16 [H_l, W_l, C] or uint32 [H_l, W_l]), level 0 first,
+    or one such array; `format` abi.MI_LP_F16 or abi.MI_LP_RGB9E5 (3 channels, never the SH form).  With `lod` the rest is checked as
+    check_lightmap_lod checks it; with lod None as check_lightmap_lookup does (abi.MI_LS_NEAREST allowed), and then there must be one
+    level alone.  Returns (packed levels [L] contiguous, what the f32 check returned for the unpacked levels); raises ValueError where
+    the C calls refuse."""
+    fmt = _check_packed_format(format, None, sh)
+    chain = list(packed_chain) if isinstance(packed_chain, (list, tuple)) else [packed_chain]
+    if len(chain) == 0:
+        raise ValueError("packed_chain must hold level 0")
+    packed = [np.ascontiguousarray(p) for p in chain]
+    levels = [lightmap_unpack(p, fmt) for p in packed]
+    if levels[0].ndim == 4 and levels[0].shape[2:] == (9, 3) and fmt == abi.MI_LP_F16:
+        levels = [a.reshape(a.shape[:2] + (27,)) for a in levels]
+        packed = [p.reshape(p.shape[:2] + (27,)) for p in packed]
+    if sh and (levels[0].ndim != 3 or levels[0].shape[2] != 27):
+        raise ValueError(f"the levels must be [H, W, 9, 3] or [H, W, 27], got {np.shape(chain[0])}")
+    if sh and normals is None:
+        raise ValueError("normals are required")
+    if lod is not None:
+        return packed, check_lightmap_lod(levels, uv, lod, valid_chain, flags, normals)
+    if len(levels) != 1:
+        raise ValueError(f"lod None reads level 0 alone: {len(levels)} levels were given")
+    if isinstance(valid_chain, (list, tuple)):
+        if len(valid_chain) != 1:
+            raise ValueError("lod None reads level 0 alone: valid_chain must be None, one mask or a list of one")
+        valid_chain = valid_chain[0]
+    return packed, check_lightmap_lookup(levels[0], uv, valid_chain, flags, normals)
+
+
+def lightmap_sample_packed(packed_chain, format, uv, lod=None, valid_chain=None, flags: int = 0):
+    """Read a packed lightmap at uv points on the host (numpy only).  This is the DEFINITION of mi_lightmap_sample_packed: unpack, then
+    lightmap_sample_lod — or, with lod None, lightmap_sample of the one level (abi.MI_LS_NEAREST then gives the decoded texel as it
+    stands, a -0.0 included).  Arguments as check_lightmap_packed.  Returns (out [..., C] f32, weight [...] f32)."""
+    _, checked = check_lightmap_packed(packed_chain, format, uv, lod, valid_chain, flags)
+    if lod is None:
+        img, T, v8, flags, _, shape = checked
+        out, sw = lightmap_sample(img, T, v8, flags)
+    else:
+        levels, masks, T, D, _, shape = checked
+        out, sw = lightmap_sample_lod(levels, T, D, masks, flags)
+    return out.reshape(shape + out.shape[-1:]), sw.reshape(shape)
+
+
+def lightmap_sh_sample_packed(packed_chain, format, uv, normals, lod=None, valid_chain=None, flags: int = 0):
+    """The irradiance of a packed directional lightmap at uv points and their normals on the host (numpy only).  This is the DEFINITION
+    of mi_lightmap_sh_sample_packed: unpack (abi.MI_LP_F16 only), then lightmap_sh_sample_lod — or, with lod None, lightmap_sh_sample
+    of the one level.  Returns (E [..., 3] f32, weight [...] f32)."""
+    _, checked = check_lightmap_packed(packed_chain, format, uv, lod, valid_chain, flags, normals, sh=True)
+    if lod is None:
+        img, T, v8, flags, N, shape = checked
+        E, sw = lightmap_sh_sample(img, T, N, v8, flags)
+    else:
+        levels, masks, T, D, N, shape = checked
+        E, sw = lightmap_sh_sample_lod(levels, T, N, D, masks, flags)
+    return E.reshape(shape + (3,)), sw.reshape(shape)
+
+
 def lightmap_finish_var(image, m2, samples, points, normals, levels: int = 3, normal_power_log2: int = 5,
                         sigma_plane: float = float("inf"), reach: float = float("inf"), sigma_color: float = 8.0,
                         color_floor: float = 1e-6, dilate: int = 4):
@@ -1876,6 +2018,88 @@ class Context:
         `stream`, no synchronisation."""
         abi.check(self._lib.mi_lightmap_sh_sample_lod_device(self._h, width, height, d_sh, d_valid, levels, d_mips, d_mip_valid, n, d_uv,
                                                              d_normals, d_lod, flags, d_irradiance, d_weight, stream))
+
+    # ---- packed lightmaps: f16 / RGB9E5 storage and the lookups that read it ----
+    def lightmap_pack(self, texels, format):
+        """mi_lightmap_pack: the helper lightmap_pack on the GPU, bit for bit: `texels` [..., 3] or [..., 27] f32 as uint16 [..., C]
+        (abi.MI_LP_F16) or uint32 [...] (abi.MI_LP_RGB9E5, 3 channels).  No scene is needed."""
+        x = np.ascontiguousarray(np.asarray(texels, np.float32))
+        if x.ndim < 1 or x.shape[-1] not in (3, 27):
+            raise ValueError(f"texels must be [..., 3] or [..., 27], got {x.shape}")
+        ch = x.shape[-1]
+        fmt = _check_packed_format(format, ch)
+        out = np.empty(x.shape, np.uint16) if fmt == abi.MI_LP_F16 else np.empty(x.shape[:-1], np.uint32)
+        abi.check(self._lib.mi_lightmap_pack(self._h, fmt, ch, x.size // ch, x.ctypes.data, out.ctypes.data))
+        return out
+
+    def lightmap_pack_device(self, format: int, channels: int, n_texels: int, d_texels: int, d_packed: int, stream: Optional[int] = None):
+        """mi_lightmap_pack_device: the same for texels held on the device (raw pointers: [n_texels, channels] f32 in; [n_texels, channels]
+        u16 or [n_texels] u32 out, which must not overlap the input).  Queued on `stream`, no synchronisation, no scratch."""
+        abi.check(self._lib.mi_lightmap_pack_device(self._h, format, channels, n_texels, d_texels, d_packed, stream))
+
+    def lightmap_unpack(self, packed, format):
+        """mi_lightmap_unpack: the helper lightmap_unpack on the GPU, bit for bit (a NaN is a NaN): uint16 [..., C] or uint32 [...] as
+        f32 [..., C]."""
+        fmt, p = _check_packed_array(packed, format)
+        ch = 3 if fmt == abi.MI_LP_RGB9E5 else p.shape[-1]
+        n = p.size if fmt == abi.MI_LP_RGB9E5 else p.size // ch
+        out = np.empty((p.shape if fmt == abi.MI_LP_RGB9E5 else p.shape[:-1]) + (ch,), np.float32)
+        abi.check(self._lib.mi_lightmap_unpack(self._h, fmt, ch, n, p.ctypes.data, out.ctypes.data))
+        return out
+
+    def lightmap_unpack_device(self, format: int, channels: int, n_texels: int, d_packed: int, d_texels: int, stream: Optional[int] = None):
+        """mi_lightmap_unpack_device: the same for packed texels held on the device (raw pointers).  Queued on `stream`."""
+        abi.check(self._lib.mi_lightmap_unpack_device(self._h, format, channels, n_texels, d_packed, d_texels, stream))
+
+    def _packed_lookup(self, entry, packed, checked, fmt, lod, sh):
+        """One packed lookup through the host form `entry`: `packed`, `checked` as check_lightmap_packed returned them"""
+        if lod is None:
+            img, T, v0, flags, N, shape = checked
+            L, mips, mv, D = 1, None, None, None
+        else:
+            levels, masks, T, D, N, shape = checked
+            img, flags, L = levels[0], 0, len(levels)
+            v0 = None if masks[0] is None else np.ascontiguousarray(masks[0], np.uint8)
+            mv = None if L < 2 or masks[1] is None else _lmm_pack(masks, np.uint8)
+            mips = _lmm_pack(packed, packed[0].dtype, packed[0].shape[2:])
+        H, W, ch = img.shape
+        out = np.empty((len(T), 3 if sh else ch), np.float32)
+        weight = np.empty(len(T), np.float32)
+        ptr = lambda a: None if a is None else a.ctypes.data
+        head = (self._h, fmt, W, H) + (() if sh else (ch,)) + (packed[0].ctypes.data, ptr(v0), L, ptr(mips), ptr(mv), len(T), T.ctypes.data)
+        abi.check(entry(*head, *((N.ctypes.data,) if sh else ()), ptr(D), flags, out.ctypes.data, weight.ctypes.data))
+        return out.reshape(shape + out.shape[1:]), weight.reshape(shape)
+
+    def lightmap_sample_packed(self, packed_chain, format, uv, lod=None, valid_chain=None, flags: int = 0):
+        """mi_lightmap_sample_packed: the helper lightmap_sample_packed on the GPU, bit for bit: packed levels (a list as lightmap_pack
+        returns them per level, or one array) read at `uv` [..., 2], trilinearly at `lod`, or with lod None level 0 alone (bilinear or
+        abi.MI_LS_NEAREST).  Returns (out [..., C] f32, weight [...] f32)."""
+        packed, checked = check_lightmap_packed(packed_chain, format, uv, lod, valid_chain, flags)
+        return self._packed_lookup(self._lib.mi_lightmap_sample_packed, packed, checked, int(format), lod, False)
+
+    def lightmap_sample_packed_device(self, format: int, width: int, height: int, channels: int, d_image: int, levels: int,
+                                      d_mips: Optional[int], n: int, d_uv: int, d_lod: Optional[int], d_out: int,
+                                      d_weight: Optional[int] = None, d_valid: Optional[int] = None, d_mip_valid: Optional[int] = None,
+                                      flags: int = 0, stream: Optional[int] = None):
+        """mi_lightmap_sample_packed_device: the same for packed levels and points held on the device (raw pointers as
+        lightmap_sample_lod_device, the texels packed; d_lod None: level 0 alone, levels 1, d_mips None).  Queued on `stream`, no
+        synchronisation, no scratch."""
+        abi.check(self._lib.mi_lightmap_sample_packed_device(self._h, format, width, height, channels, d_image, d_valid, levels, d_mips,
+                                                             d_mip_valid, n, d_uv, d_lod, flags, d_out, d_weight, stream))
+
+    def lightmap_sh_sample_packed(self, packed_chain, format, uv, normals, lod=None, valid_chain=None, flags: int = 0):
+        """mi_lightmap_sh_sample_packed: the helper lightmap_sh_sample_packed on the GPU, bit for bit: the irradiance of a directional
+        lightmap packed as abi.MI_LP_F16 at `uv`, the normals there and `lod` (None: level 0 alone).  Returns (E [..., 3], weight [...])."""
+        packed, checked = check_lightmap_packed(packed_chain, format, uv, lod, valid_chain, flags, normals, sh=True)
+        return self._packed_lookup(self._lib.mi_lightmap_sh_sample_packed, packed, checked, int(format), lod, True)
+
+    def lightmap_sh_sample_packed_device(self, format: int, width: int, height: int, d_sh: int, levels: int, d_mips: Optional[int], n: int,
+                                         d_uv: int, d_normals: int, d_lod: Optional[int], d_irradiance: int,
+                                         d_weight: Optional[int] = None, d_valid: Optional[int] = None,
+                                         d_mip_valid: Optional[int] = None, flags: int = 0, stream: Optional[int] = None):
+        """mi_lightmap_sh_sample_packed_device: the same for packed records and points held on the device.  Queued on `stream`."""
+        abi.check(self._lib.mi_lightmap_sh_sample_packed_device(self._h, format, width, height, d_sh, d_valid, levels, d_mips, d_mip_valid,
+                                                                n, d_uv, d_normals, d_lod, flags, d_irradiance, d_weight, stream))
 
     def last_reduce_psh_ms(self) -> float:
         """Sum of the wf_reduce_psh launch durations (ms) of the last render: entry 7 of mi_last_pipeline_ms after render_points_sh /

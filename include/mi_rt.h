@@ -211,6 +211,9 @@ typedef struct mi_render_opts {
 #define MI_PV_NORMAL_WEIGHT 1u      /* weight the eight corners by how far they lie in front of the surface */
 /* `flags` of mi_lightmap_sample / mi_lightmap_sh_sample (below) */
 #define MI_LS_NEAREST 1u            /* the reference's nearest-texel addressing (texture.rs:28-29), no interpolation */
+/* `format` of mi_lightmap_pack / mi_lightmap_unpack / mi_lightmap_*_packed (below); 0 is reserved for f32 and refused there */
+#define MI_LP_F16 1u                /* `channels` IEEE binary16 per texel, tightly packed (3 or 27 channels) */
+#define MI_LP_RGB9E5 2u             /* one u32 per texel: three 9-bit mantissas and a shared 5-bit exponent (3 channels only) */
 
 typedef enum mi_variant {
     MI_VARIANT_DEFAULT    = 0,  /* library picks (currently MI_VARIANT_WAVEFRONT)                  */
@@ -972,7 +975,7 @@ int  mi_lightmap_sh_sample_device(mi_ctx* ctx, uint32_t width, uint32_t height, 
  *   A later launch reads the coverage of the last level the one before wrote: with out_coverage == NULL the coverage planes live in a
  *   buffer the context owns, so two such calls on one context must not be in flight at once (pass out_coverage to overlap them).  The
  *   lookups need no scratch.  Indices are 64-bit.
- * Out of scope: packed or compressed formats, deriving lod from ray footprints, anisotropic filtering, wrap modes other than clamp. */
+ * Out of scope: block-compressed formats (BC6H), deriving lod from ray footprints, anisotropic filtering, wrap modes other than clamp. */
 int  mi_lightmap_mips(mi_ctx* ctx, uint32_t width, uint32_t height, uint32_t channels, const float* image, const uint8_t* valid,
                       uint32_t levels, float* out_mips, uint8_t* out_valid, float* out_coverage);
 int  mi_lightmap_mips_device(mi_ctx* ctx, uint32_t width, uint32_t height, uint32_t channels, const float* image, const uint8_t* valid,
@@ -989,6 +992,63 @@ int  mi_lightmap_sh_sample_lod(mi_ctx* ctx, uint32_t width, uint32_t height, con
 int  mi_lightmap_sh_sample_lod_device(mi_ctx* ctx, uint32_t width, uint32_t height, const float* sh, const uint8_t* valid, uint32_t levels,
                                       const float* mips, const uint8_t* mip_valid, uint32_t n, const float* uv, const float* normals,
                                       const float* lod, uint32_t flags, float* out_irradiance, float* out_weight, void* stream);
+
+/* ---- packed lightmaps: f16 and RGB9E5 storage and lookups that read them (added within ABI version 5: detect by symbol lookup) ----
+ * A finished directional lightmap is 108 bytes per texel in f32.  mi_lightmap_pack stores it (or a plain one, or a mip chain) in one of
+ *   two formats that decode to f32 EXACTLY, and mi_lightmap_sample_packed / mi_lightmap_sh_sample_packed read such storage directly.
+ *   lightmap_pack, lightmap_unpack, lightmap_sample_packed and lightmap_sh_sample_packed (Python) are the definitions.
+ * MI_LP_F16 — channels 3 or 27; a texel is `channels` consecutive u16, tightly packed (6 or 54 bytes: 2-byte aligned only).
+ *   Encode per float x: if x != x, the bits are 0x7E00 (made by a select, not by a conversion, so they compare).  Otherwise
+ *   c = fminf(fmaxf(x, -65504.0f), 65504.0f), then IEEE round-to-nearest-even f32 -> binary16 of c.  Subnormal results are kept and the
+ *   sign of zero is kept.  Infinities and everything beyond +-65504 saturate to 0x7BFF / 0xFBFF: no infinity is ever written.
+ *   Decode: the exact binary16 -> f32 widening.
+ * MI_LP_RGB9E5 — channels 3 only; a texel is one u32: the shared-exponent format of EXT_texture_shared_exponent / DXGI R9G9B9E5,
+ *   N = 9, B = 15, largest value 65408.  The encoder is all f32, with no fused multiply-add.
+ *   Per channel: c = (x != x) ? 0 : fminf(fmaxf(x, 0), 65408.0f).  m = max(c_r, c_g, c_b).
+ *   eb = ((bits(m) >> 23) & 255) - 127: floor(log2 m) for every m that matters; a zero or subnormal m gives -127.
+ *   ep = max(eb, -16) + 16.  ms = floorf(m * 2^(24-ep) + 0.5f).  e = ep + (ms == 512).
+ *   q_k = (uint)floorf(c_k * 2^(24-e) + 0.5f).  word = q_r | q_g << 9 | q_b << 18 | e << 27.
+ *   The powers of two are exact f32 constants built from the exponent, and the products are exact.  The one rounding per channel is the
+ *   + 0.5f, so (0.5 - 2^-25) scaled rounds UP: that is the definition, not a bug.  Decode: (float)q_k * 2^(e-24), exact.
+ *   Every q stays <= 511 and every e <= 31; the error per channel is at most 2^(e-25) — half a step; 2^(e-49) more for a channel in
+ *   [0.5 - 2^-25, 0.5) steps, the one case where the + 0.5f itself rounds — and at most m / 511 where e > 0.
+ *   RGB9E5 at 27 channels is refused, because SH coefficients are signed: directional lightmaps pack as f16.
+ * mi_lightmap_pack / mi_lightmap_unpack are layout-agnostic: a count of texels, so level 0 and the `mips` buffer of mi_lightmap_mips
+ *   are packed by one call each.  The mip layout, `valid`, `mip_valid` and the coverage planes are unchanged and stay u8 / f32.
+ *   Texels behind valid == 0 are encoded like any other and never fault.
+ * mi_lightmap_sample_packed / mi_lightmap_sh_sample_packed (the latter MI_LP_F16 only): with lod != NULL the result is, BIT FOR BIT,
+ *   mi_lightmap_sample_lod / mi_lightmap_sh_sample_lod on the unpacked level 0 and mips.  With lod == NULL it is mi_lightmap_sample /
+ *   mi_lightmap_sh_sample on the unpacked image: then `levels` must be 1 and `mips`, `mip_valid` NULL, and MI_LS_NEAREST is allowed —
+ *   with it a texel comes back as it stands: the decoded value, -0.0 included for f16.  All the rules of the two sections above carry
+ *   over word for word: tap order, a tap that takes no part is not read, clamped indices only, 64-bit indexing, NaN behaviour,
+ *   out_weight.  The lookup arithmetic exists once: the packed kernels are the f32 kernels' device code with another texel fetch.
+ * MI_ERR_INVALID (each with a message, checked before the context, nothing is launched): everything the f32 calls refuse; an unknown
+ *   format or format 0; MI_LP_RGB9E5 with channels other than 3; any format but MI_LP_F16 in the SH form; lod == NULL with levels != 1
+ *   or a non-NULL mips / mip_valid; a NULL texels / packed / out_packed / out_texels; n_texels above 2^32; in the _device forms an
+ *   output that overlaps an input.  n_texels == 0 / n == 0 is MI_OK and launches nothing.
+ * Host forms: HOST pointers, blocking; the arrays pass through the buffer the context owns.  _device forms: DEVICE pointers on ctx's
+ *   device, queued on `stream`, no synchronisation, no scratch; mi_last_kernel_ms reports the kernel.
+ * Out of scope: block-compressed formats (BC6H), signed shared-exponent formats, packing `valid` or the coverage planes, packed outputs
+ *   of bake, finish or mips (pack is a separate call). */
+int  mi_lightmap_pack(mi_ctx* ctx, uint32_t format, uint32_t channels, uint64_t n_texels, const float* texels, void* out_packed);
+int  mi_lightmap_pack_device(mi_ctx* ctx, uint32_t format, uint32_t channels, uint64_t n_texels, const float* texels, void* out_packed,
+                             void* stream);
+int  mi_lightmap_unpack(mi_ctx* ctx, uint32_t format, uint32_t channels, uint64_t n_texels, const void* packed, float* out_texels);
+int  mi_lightmap_unpack_device(mi_ctx* ctx, uint32_t format, uint32_t channels, uint64_t n_texels, const void* packed, float* out_texels,
+                               void* stream);
+int  mi_lightmap_sample_packed(mi_ctx* ctx, uint32_t format, uint32_t width, uint32_t height, uint32_t channels, const void* image,
+                               const uint8_t* valid, uint32_t levels, const void* mips, const uint8_t* mip_valid, uint32_t n,
+                               const float* uv, const float* lod, uint32_t flags, float* out, float* out_weight);
+int  mi_lightmap_sample_packed_device(mi_ctx* ctx, uint32_t format, uint32_t width, uint32_t height, uint32_t channels, const void* image,
+                                      const uint8_t* valid, uint32_t levels, const void* mips, const uint8_t* mip_valid, uint32_t n,
+                                      const float* uv, const float* lod, uint32_t flags, float* out, float* out_weight, void* stream);
+int  mi_lightmap_sh_sample_packed(mi_ctx* ctx, uint32_t format, uint32_t width, uint32_t height, const void* sh, const uint8_t* valid,
+                                  uint32_t levels, const void* mips, const uint8_t* mip_valid, uint32_t n, const float* uv,
+                                  const float* normals, const float* lod, uint32_t flags, float* out_irradiance, float* out_weight);
+int  mi_lightmap_sh_sample_packed_device(mi_ctx* ctx, uint32_t format, uint32_t width, uint32_t height, const void* sh,
+                                         const uint8_t* valid, uint32_t levels, const void* mips, const uint8_t* mip_valid, uint32_t n,
+                                         const float* uv, const float* normals, const float* lod, uint32_t flags, float* out_irradiance,
+                                         float* out_weight, void* stream);
 
 /* Size and allocate the wavefront pipeline's HBM buffers (path state, sample slots) for
  * this camera with the image shared by `world` ranks, so that the first render does not pay the

@@ -53,6 +53,8 @@ pub const MI_HEMI_WORLD_RADIUS: u32 = 1;
 pub const MI_LM_JITTER: u32 = 1;
 pub const MI_PV_NORMAL_WEIGHT: u32 = 1;
 pub const MI_LS_NEAREST: u32 = 1;
+pub const MI_LP_F16: u32 = 1;
+pub const MI_LP_RGB9E5: u32 = 2;
 // mi_material_kind / mi_object_kind / projection and shading modes (include/mi_rt.h)
 pub const MI_MAT_LAMBERTIAN: i32 = 0; pub const MI_MAT_METAL: i32 = 1; pub const MI_MAT_DIELECTRIC: i32 = 2;
 pub const MI_MAT_PARAMETERIZED: i32 = 3; pub const MI_MAT_ISOTROPIC: i32 = 4;
@@ -251,6 +253,28 @@ extern "C" {
                                             mips: *const f32, mip_valid: *const u8, n: u32, uv: *const f32, normals: *const f32,
                                             lod: *const f32, flags: u32, out_irradiance: *mut f32, out_weight: *mut f32,
                                             stream: *mut c_void) -> c_int;
+    // packed lightmaps: f16 / RGB9E5 storage (MI_LP_*) and the lookups that read it; lod null = the level-0 lookup
+    pub fn mi_lightmap_pack(ctx: *mut mi_ctx, format: u32, channels: u32, n_texels: u64, texels: *const f32, out_packed: *mut c_void) -> c_int;
+    pub fn mi_lightmap_pack_device(ctx: *mut mi_ctx, format: u32, channels: u32, n_texels: u64, texels: *const f32, out_packed: *mut c_void,
+                                   stream: *mut c_void) -> c_int;
+    pub fn mi_lightmap_unpack(ctx: *mut mi_ctx, format: u32, channels: u32, n_texels: u64, packed: *const c_void, out_texels: *mut f32) -> c_int;
+    pub fn mi_lightmap_unpack_device(ctx: *mut mi_ctx, format: u32, channels: u32, n_texels: u64, packed: *const c_void, out_texels: *mut f32,
+                                     stream: *mut c_void) -> c_int;
+    pub fn mi_lightmap_sample_packed(ctx: *mut mi_ctx, format: u32, width: u32, height: u32, channels: u32, image: *const c_void,
+                                     valid: *const u8, levels: u32, mips: *const c_void, mip_valid: *const u8, n: u32, uv: *const f32,
+                                     lod: *const f32, flags: u32, out: *mut f32, out_weight: *mut f32) -> c_int;
+    pub fn mi_lightmap_sample_packed_device(ctx: *mut mi_ctx, format: u32, width: u32, height: u32, channels: u32, image: *const c_void,
+                                            valid: *const u8, levels: u32, mips: *const c_void, mip_valid: *const u8, n: u32,
+                                            uv: *const f32, lod: *const f32, flags: u32, out: *mut f32, out_weight: *mut f32,
+                                            stream: *mut c_void) -> c_int;
+    pub fn mi_lightmap_sh_sample_packed(ctx: *mut mi_ctx, format: u32, width: u32, height: u32, sh: *const c_void, valid: *const u8,
+                                        levels: u32, mips: *const c_void, mip_valid: *const u8, n: u32, uv: *const f32,
+                                        normals: *const f32, lod: *const f32, flags: u32, out_irradiance: *mut f32,
+                                        out_weight: *mut f32) -> c_int;
+    pub fn mi_lightmap_sh_sample_packed_device(ctx: *mut mi_ctx, format: u32, width: u32, height: u32, sh: *const c_void, valid: *const u8,
+                                               levels: u32, mips: *const c_void, mip_valid: *const u8, n: u32, uv: *const f32,
+                                               normals: *const f32, lod: *const f32, flags: u32, out_irradiance: *mut f32,
+                                               out_weight: *mut f32, stream: *mut c_void) -> c_int;
     pub fn mi_reserve(ctx: *mut mi_ctx, cam: *const mi_camera_desc, world: i32, max_state_bytes: u64) -> c_int;
     pub fn mi_last_pipeline_ms(ctx: *mut mi_ctx, out8: *mut f32) -> c_int;
     pub fn mi_last_pipeline_counts(ctx: *mut mi_ctx, out8: *mut u64) -> c_int;

@@ -579,6 +579,132 @@ impl Scene {
         (out, weight)
     }
 
+    /// Packed lightmaps (include/mi_rt.h "packed lightmaps").  `pack_lightmap` and `unpack_lightmap` are the formats' definitions on the
+    /// host, in integer and f32 arithmetic alone (a storage conversion needs no device); the bytes equal mi_lightmap_pack's and
+    /// mi_lightmap_unpack's bit for bit.  `texels` is [n][channels] f32, channels 3 or 27 (MI_LP_RGB9E5: 3); the result is n * channels
+    /// u16 for MI_LP_F16, n u32 for MI_LP_RGB9E5, as the little-endian bytes the C calls take.
+    pub fn pack_lightmap(texels: &[f32], format: u32, channels: u32) -> Vec<u8> {
+        Self::check_packed_format(format, channels);
+        assert!(texels.len() % channels as usize == 0, "mi_rt: texels must be [n][channels]");
+        let pow2 = |e: i32| f32::from_bits(((e + 127) as u32) << 23);
+        let mut out = Vec::with_capacity(texels.len() * 2);
+        if format == mi_rt::MI_LP_F16 {
+            for &x in texels { out.extend_from_slice(&Self::f16_bits(x).to_le_bytes()); }
+            return out;
+        }
+        for t in texels.chunks_exact(3) {
+            let mut c = [0.0f32; 3];
+            for k in 0..3 { c[k] = if t[k] != t[k] { 0.0 } else { t[k].max(0.0).min(65408.0) }; }
+            let m = c[0].max(c[1]).max(c[2]);
+            let eb = ((m.to_bits() >> 23) & 255) as i32 - 127;
+            let ep = eb.max(-16) + 16;
+            let ms = (m * pow2(24 - ep) + 0.5).floor();
+            let e = ep + (ms == 512.0) as i32;
+            let s = pow2(24 - e);
+            let mut w = (e as u32) << 27;
+            for k in 0..3 { w |= ((c[k] * s + 0.5).floor() as u32) << (9 * k); }
+            out.extend_from_slice(&w.to_le_bytes());
+        }
+        out
+    }
+
+    /// The exact decode of `pack_lightmap`'s bytes: [n][channels] f32.
+    pub fn unpack_lightmap(packed: &[u8], format: u32, channels: u32) -> Vec<f32> {
+        Self::check_packed_format(format, channels);
+        let pow2 = |e: i32| f32::from_bits(((e + 127) as u32) << 23);
+        if format == mi_rt::MI_LP_F16 {
+            assert!(packed.len() % (2 * channels as usize) == 0, "mi_rt: packed must hold whole texels");
+            return packed.chunks_exact(2).map(|b| {
+                let h = u16::from_le_bytes([b[0], b[1]]) as u32;
+                let (sign, ex, man) = ((h & 0x8000) << 16, (h >> 10) & 31, h & 1023);
+                if ex == 31 { f32::from_bits(sign | 0x7F80_0000 | if man != 0 { 0x0040_0000 | man << 13 } else { 0 }) }
+                else if ex != 0 { f32::from_bits(sign | (ex + 112) << 23 | man << 13) }
+                else { f32::from_bits(sign | (man as f32 * pow2(-24)).to_bits()) }
+            }).collect();
+        }
+        assert!(packed.len() % 4 == 0, "mi_rt: packed must hold whole texels");
+        let mut out = Vec::with_capacity(packed.len() / 4 * 3);
+        for b in packed.chunks_exact(4) {
+            let w = u32::from_le_bytes([b[0], b[1], b[2], b[3]]);
+            let s = pow2((w >> 27) as i32 - 24);
+            for k in 0..3 { out.push(((w >> (9 * k)) & 511) as f32 * s); }
+        }
+        out
+    }
+
+    /// Read a packed lightmap at uv points through mi_lightmap_sample_packed: `sample_lightmap_lod`'s arguments with `image` and `mips` as
+    /// `pack_lightmap` made them; an empty `lod` reads level 0 alone (then `levels` must be 1 and `mips` empty, and `nearest` is allowed).
+    /// Equals `sample_lightmap(_lod)` on the unpacked texels bit for bit.
+    pub fn sample_lightmap_packed(format: u32, image: &[u8], valid: &[u8], width: u32, height: u32, channels: u32, levels: u32, mips: &[u8],
+                                  mip_valid: &[u8], uv: &[[f32; 2]], lod: &[f32], nearest: bool) -> (Vec<f32>, Vec<f32>) {
+        Self::packed_lookup(format, image, valid, width, height, channels, levels, mips, mip_valid, uv, None, lod, nearest)
+    }
+
+    /// The irradiance of a directional lightmap packed as MI_LP_F16 through mi_lightmap_sh_sample_packed: `sample_lightmap_sh_lod`'s
+    /// arguments with packed records; an empty `lod` reads level 0 alone.
+    pub fn sample_lightmap_sh_packed(format: u32, sh: &[u8], valid: &[u8], width: u32, height: u32, levels: u32, mips: &[u8], mip_valid: &[u8],
+                                     uv: &[[f32; 2]], normals: &[[f32; 3]], lod: &[f32], nearest: bool) -> (Vec<[f32; 3]>, Vec<f32>) {
+        assert!(uv.len() == normals.len(), "mi_rt: one normal per point");
+        let (flat, weight) = Self::packed_lookup(format, sh, valid, width, height, 0, levels, mips, mip_valid, uv, Some(normals), lod, nearest);
+        (flat.chunks_exact(3).map(|e| [e[0], e[1], e[2]]).collect(), weight)
+    }
+
+    fn check_packed_format(format: u32, channels: u32) {
+        assert!(format == mi_rt::MI_LP_F16 || format == mi_rt::MI_LP_RGB9E5, "mi_rt: format must be MI_LP_F16 or MI_LP_RGB9E5");
+        assert!(channels == 3 || channels == 27, "mi_rt: channels must be 3 or 27");
+        assert!(format != mi_rt::MI_LP_RGB9E5 || channels == 3, "mi_rt: MI_LP_RGB9E5 holds 3 unsigned channels");
+    }
+
+    /// f32 -> binary16 bits as the header defines them: a NaN is 0x7E00, everything else is clamped to +-65504 and rounded to nearest even.
+    fn f16_bits(x: f32) -> u16 {
+        if x != x { return 0x7E00; }
+        let u = x.max(-65504.0).min(65504.0).to_bits();
+        let (sign, mag) = ((u >> 16) & 0x8000, u & 0x7FFF_FFFF);
+        if mag >= 0x3880_0000 {
+            let r = mag + 0x0FFF + ((mag >> 13) & 1);
+            return (sign | ((r >> 13) - (112 << 10))) as u16;
+        }
+        if mag < 0x3300_0000 { return sign as u16; }
+        let (man, shift) = ((mag & 0x007F_FFFF) | 0x0080_0000, 126 - (mag >> 23));
+        let (q, rest, half) = (man >> shift, man & ((1 << shift) - 1), 1 << (shift - 1));
+        (sign | (q + (rest > half || (rest == half && q & 1 == 1)) as u32)) as u16
+    }
+
+    fn packed_lookup(format: u32, image: &[u8], valid: &[u8], width: u32, height: u32, channels: u32, levels: u32, mips: &[u8], mip_valid: &[u8],
+                     uv: &[[f32; 2]], normals: Option<&[[f32; 3]]>, lod: &[f32], nearest: bool) -> (Vec<f32>, Vec<f32>) {
+        let (in_c, out_c) = if channels == 0 { (27, 3) } else { (channels, channels) };
+        Self::check_packed_format(format, in_c);
+        let bytes = if format == mi_rt::MI_LP_F16 { 2 * in_c as usize } else { 4 };
+        let texels = width as usize * height as usize;
+        assert!(image.len() == texels * bytes && (valid.is_empty() || valid.len() == texels), "mi_rt: image (and valid) must hold height * width texels");
+        let made: usize = Self::lightmap_mip_layout(width, height, levels).iter().skip(1).map(|l| l.0 as usize * l.1 as usize).sum();
+        assert!(mips.len() == made * bytes && (mip_valid.is_empty() || mip_valid.len() == made), "mi_rt: mips (and mip_valid) must hold levels 1 .. of the layout");
+        assert!(lod.is_empty() || lod.len() == uv.len(), "mi_rt: lod is empty or holds one value per point");
+        let mut out = vec![0.0f32; uv.len() * out_c as usize];
+        let mut weight = vec![0.0f32; uv.len()];
+        if uv.is_empty() { return (out, weight); }
+        let or_null = |s: &[u8]| if s.is_empty() { std::ptr::null() } else { s.as_ptr() };
+        let d = if lod.is_empty() { std::ptr::null() } else { lod.as_ptr() };
+        let flags = if nearest { mi_rt::MI_LS_NEAREST } else { 0 };
+        unsafe {
+            let mut ctx = std::ptr::null_mut();
+            assert_eq!(mi_rt::mi_ctx_create(0, &mut ctx), 0, "{}", mi_rt::last_error());
+            let rc = match normals {
+                Some(n) => mi_rt::mi_lightmap_sh_sample_packed(ctx, format, width, height, image.as_ptr() as *const std::ffi::c_void, or_null(valid), levels,
+                                                               or_null(mips) as *const std::ffi::c_void, or_null(mip_valid), uv.len() as u32,
+                                                               uv.as_ptr() as *const f32, n.as_ptr() as *const f32, d, flags, out.as_mut_ptr(),
+                                                               weight.as_mut_ptr()),
+                None => mi_rt::mi_lightmap_sample_packed(ctx, format, width, height, channels, image.as_ptr() as *const std::ffi::c_void, or_null(valid), levels,
+                                                         or_null(mips) as *const std::ffi::c_void, or_null(mip_valid), uv.len() as u32,
+                                                         uv.as_ptr() as *const f32, d, flags, out.as_mut_ptr(), weight.as_mut_ptr()),
+            };
+            let msg = mi_rt::last_error();
+            mi_rt::mi_ctx_destroy(ctx);
+            assert_eq!(rc, 0, "{}", msg);
+        }
+        (out, weight)
+    }
+
     /// flatten -> context on device 0 -> upload -> `call` -> destroy; panics with the library's message on failure.
     fn with_gpu_scene<F: FnOnce(*mut mi_rt::mi_ctx) -> i32>(&self, call: F) {
         let sb = self.flatten_scene();

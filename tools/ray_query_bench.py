@@ -116,6 +116,8 @@ if ROOT not in sys.path:
 from cs397raytracingsp22_amd import Context, abi, scenes  # noqa: E402
 
 
+# --mode packed (appended to the notes above): times mi_lightmap_pack_device / mi_lightmap_unpack_device against a device copy of the same
+# bytes, and every packed lookup against its f32 twin on coherent and shuffled uv, with and without lod (packed_rows' docstring).
 # --mode adaptive (appended to the notes above): times mi_bake_lightmap_adaptive (16 first samples, 2 rounds of 16, the relative target the
 # median of round 0's error over its luminance) on the cube in the one-light box and on the drone, atlas --atlas-sizes[0] squared, against
 # uniform mi_bake_lightmap_moments bakes at the adaptive run's own slots per texel and at first + max_rounds * round_samples; reports every
@@ -1378,6 +1380,167 @@ def mips_rows(ctx, sizes, point_counts, calls, warmup):
     return rows
 
 
+def packed_rows(ctx, sizes, point_counts, calls, warmup):
+    """--mode packed: packed lightmaps on resident tables, HIP events inside the library (mi_last_kernel_ms), `warmup` calls then `calls`
+    timed ones, medians with min - max; `spread` is (max - min) / median of a row.  Inputs per size: a seeded random image [size, size, 3]
+    in 0 .. 4 and records [size, size, 27] (normal deviates) under mips_rows' chart-and-gutter mask, and their full mip chains
+    (mi_lightmap_mips_device).  Rows:
+    "lmp_pack" / "lmp_unpack" of level 0 per format and channel count — MI_LP_F16 at 3 and 27, MI_LP_RGB9E5 at 3 — against "copy", a
+    device-to-device copy of the same bytes (the f32 texels and the packed ones, half of the sum copied: read and written);
+    `over_copy` is the ratio of the medians.  The packed words of the first 65536 texels are checked against lightmap_pack, the
+    unpacked ones against lightmap_unpack, bit for bit.
+    Then, per point count and in lookup_rows' two orders, "coherent" and "shuffled", every packed lookup against its f32 twin — the f32
+    kernel on the texels mi_lightmap_unpack_device made of the same packed bytes, so both sides compute the same values — with lod
+    (uniform in 0 .. 4) and without (level 0 alone); `packed_over_f32` is the ratio of the medians, and the two outputs are compared on
+    the device, every point, bit for bit.  The measured figures are in DESIGN.md section 4, "Packed lightmaps"."""
+    from cs397raytracingsp22_amd import abi, lightmap_mip_layout, lightmap_pack, lightmap_unpack
+    dev = torch.device("cuda:0")
+    F16, RGB = abi.MI_LP_F16, abi.MI_LP_RGB9E5
+    rows = []
+
+    def stats(ms):
+        med = float(np.median(ms))
+        return {"ms_median": round(med, 4), "ms_min": round(float(np.min(ms)), 4), "ms_max": round(float(np.max(ms)), 4),
+                "spread": round((float(np.max(ms)) - float(np.min(ms))) / med, 4)}
+
+    def emit(row):
+        rows.append(row)
+        print(json.dumps(row), flush=True)
+
+    def same_bits(a, b):
+        return bool(torch.equal(a.contiguous().view(torch.int32), b.contiguous().view(torch.int32)))
+
+    for size in sizes:
+        layout = lightmap_mip_layout(size, size)
+        L, made, texels = len(layout), sum(w * h for w, h, _ in layout[1:]), size * size
+        gen = torch.Generator(device=dev)
+        gen.manual_seed(3)
+        yy, xx = torch.meshgrid(torch.arange(size, device=dev), torch.arange(size, device=dev), indexing="ij")
+        valid = ((xx % 64 < 60) & (yy % 64 < 60)).to(torch.uint8).contiguous()
+        del yy, xx
+        stored = {}                                                # (format, channels) -> (packed level 0, packed mips, f32 level 0, f32 mips, mip masks)
+        for fmt, ch, name in ((F16, 3, "f16 x 3"), (RGB, 3, "rgb9e5 x 3"), (F16, 27, "f16 x 27")):
+            if ch == 3:
+                img = (torch.rand((size, size, 3), generator=gen, dtype=torch.float32, device=dev) * 4.0).contiguous()
+            else:
+                img = torch.randn((size, size, 27), generator=gen, dtype=torch.float32, device=dev)
+            mips = torch.empty((made, ch), dtype=torch.float32, device=dev)
+            mv = torch.empty(made, dtype=torch.uint8, device=dev)
+            ctx.lightmap_mips_device(size, size, ch, img.data_ptr(), L, mips.data_ptr(), mv.data_ptr(), None, valid.data_ptr())
+            words = (lambda count: torch.empty(count * ch, dtype=torch.int16, device=dev)) if fmt == F16 else (lambda count: torch.empty(count, dtype=torch.int32, device=dev))
+            p0, pm = words(texels), words(made)
+            u0, um = torch.empty_like(img), torch.empty_like(mips)
+            moved = texels * 4 * ch + p0.numel() * p0.element_size()
+            src, dst = torch.empty(moved // 2, dtype=torch.uint8, device=dev), torch.empty(moved // 2, dtype=torch.uint8, device=dev)
+            ms = {"lmp_pack": [], "lmp_unpack": [], "copy": []}
+            for it in range(warmup + calls):
+                t = {}
+                ctx.lightmap_pack_device(fmt, ch, texels, img.data_ptr(), p0.data_ptr())
+                torch.cuda.synchronize()
+                t["lmp_pack"] = ctx.last_kernel_ms()
+                ctx.lightmap_unpack_device(fmt, ch, texels, p0.data_ptr(), u0.data_ptr())
+                torch.cuda.synchronize()
+                t["lmp_unpack"] = ctx.last_kernel_ms()
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                dst.copy_(src)
+                e1.record()
+                torch.cuda.synchronize()
+                t["copy"] = e0.elapsed_time(e1)
+                if it >= warmup:
+                    for key, val in t.items():
+                        ms[key].append(val)
+            del src, dst
+            ctx.lightmap_pack_device(fmt, ch, made, mips.data_ptr(), pm.data_ptr())
+            ctx.lightmap_unpack_device(fmt, ch, made, pm.data_ptr(), um.data_ptr())
+            torch.cuda.synchronize()
+            head = min(texels, 65536)
+            host = img.reshape(-1, ch)[:head].cpu().numpy()
+            want = lightmap_pack(host, fmt)
+            got = p0[:want.size].cpu().numpy().view(want.dtype).reshape(want.shape)
+            same = bool(np.array_equal(got, want) and np.array_equal(u0.reshape(-1, ch)[:head].cpu().numpy().view(np.int32),
+                                                                     lightmap_unpack(want, fmt).view(np.int32)))
+            copy = float(np.median(ms["copy"]))
+            for key in ("lmp_pack", "lmp_unpack", "copy"):
+                row = dict(mode="packed", size=size, format=name, query=key, calls=calls, bytes_moved=moved, **stats(ms[key]),
+                           gb_per_s=round(moved / float(np.median(ms[key])) / 1e6, 1))
+                if key != "copy":
+                    row.update(over_copy=round(float(np.median(ms[key])) / copy, 4), equals_helper=same)
+                emit(row)
+            if not same:
+                raise SystemExit("ray_query_bench: the packed texels differ from lightmap_pack / lightmap_unpack")
+            stored[(fmt, ch)] = (p0, pm, u0, um, mv)
+            del img, mips
+        for n in point_counts:
+            gw = 2 * size
+            if n > gw * gw:
+                raise SystemExit(f"ray_query_bench: {n} points exceed the {gw} x {gw} grid")
+
+            def centres(k):                  # the uv of the points number k of the gw x gw grid, row-major
+                u = ((k % gw).to(torch.float32) + 0.5) / gw
+                v = 1.0 - ((k // gw).to(torch.float32) + 0.5) / gw
+                return torch.stack([u, v], dim=1).contiguous()
+
+            k = torch.arange(n, device=dev, dtype=torch.int64)
+            anywhere = torch.randint(0, gw * gw, (n,), generator=gen, device=dev, dtype=torch.int64)
+            nrm = torch.randn((n, 3), generator=gen, dtype=torch.float32, device=dev)
+            nrm = (nrm / nrm.norm(dim=1, keepdim=True)).contiguous()
+            lod = (torch.rand(n, generator=gen, dtype=torch.float32, device=dev) * 4.0).contiguous()
+            w = torch.empty(n, dtype=torch.float32, device=dev)
+            for order, uv in (("coherent", centres(k)), ("shuffled", centres(anywhere))):
+                for with_lod in (True, False):
+                    d, lv = (lod.data_ptr(), L) if with_lod else (None, 1)
+                    pairs = {}
+                    for (fmt, ch), (p0, pm, u0, um, mv) in stored.items():
+                        m_p, m_u, m_v = (pm.data_ptr(), um.data_ptr(), mv.data_ptr()) if with_lod else (None, None, None)
+                        out_p, out_f = torch.empty((n, ch), dtype=torch.float32, device=dev), torch.empty((n, ch), dtype=torch.float32, device=dev)
+                        tag = ("f16" if fmt == F16 else "rgb9e5") + f"<{ch}>"
+                        packed = (lambda fmt=fmt, ch=ch, p0=p0, m_p=m_p, m_v=m_v, o=out_p:
+                                  ctx.lightmap_sample_packed_device(fmt, size, size, ch, p0.data_ptr(), lv, m_p, n, uv.data_ptr(), d, o.data_ptr(), w.data_ptr(),
+                                                                    valid.data_ptr(), m_v))
+                        if with_lod:
+                            plain = (lambda ch=ch, u0=u0, m_u=m_u, m_v=m_v, o=out_f:
+                                     ctx.lightmap_sample_lod_device(size, size, ch, u0.data_ptr(), L, m_u, n, uv.data_ptr(), d, o.data_ptr(), w.data_ptr(),
+                                                                    valid.data_ptr(), m_v))
+                        else:
+                            plain = (lambda ch=ch, u0=u0, o=out_f:
+                                     ctx.lightmap_sample_device(size, size, ch, u0.data_ptr(), n, uv.data_ptr(), o.data_ptr(), w.data_ptr(), valid.data_ptr()))
+                        pairs["sample " + tag] = (packed, plain, out_p, out_f)
+                    p0, pm, u0, um, mv = stored[(F16, 27)]
+                    m_p, m_u, m_v = (pm.data_ptr(), um.data_ptr(), mv.data_ptr()) if with_lod else (None, None, None)
+                    E_p, E_f = torch.empty((n, 3), dtype=torch.float32, device=dev), torch.empty((n, 3), dtype=torch.float32, device=dev)
+                    packed = (lambda: ctx.lightmap_sh_sample_packed_device(F16, size, size, p0.data_ptr(), lv, m_p, n, uv.data_ptr(), nrm.data_ptr(), d,
+                                                                           E_p.data_ptr(), w.data_ptr(), valid.data_ptr(), m_v))
+                    if with_lod:
+                        plain = (lambda: ctx.lightmap_sh_sample_lod_device(size, size, u0.data_ptr(), L, m_u, n, uv.data_ptr(), nrm.data_ptr(), d,
+                                                                           E_f.data_ptr(), w.data_ptr(), valid.data_ptr(), m_v))
+                    else:
+                        plain = (lambda: ctx.lightmap_sh_sample_device(size, size, u0.data_ptr(), n, uv.data_ptr(), nrm.data_ptr(), E_f.data_ptr(), w.data_ptr(),
+                                                                       valid.data_ptr()))
+                    pairs["sh f16"] = (packed, plain, E_p, E_f)
+                    ms = {key: ([], []) for key in pairs}
+                    torch.cuda.synchronize()
+                    for it in range(warmup + calls):
+                        for key, (packed, plain, _, _) in pairs.items():
+                            for side, call in enumerate((packed, plain)):
+                                call()
+                                torch.cuda.synchronize()
+                                if it >= warmup:
+                                    ms[key][side].append(ctx.last_kernel_ms())
+                    for key, (_, _, out_p, out_f) in pairs.items():
+                        same = same_bits(out_p, out_f)
+                        base = dict(mode="packed", size=size, n_points=n, order=order, lod=with_lod, lookup=key, calls=calls)
+                        emit(dict(base, query="f32", **stats(ms[key][1])))
+                        emit(dict(base, query="packed", **stats(ms[key][0]),
+                                  packed_over_f32=round(float(np.median(ms[key][0])) / float(np.median(ms[key][1])), 4), equals_f32_twin=same))
+                        if not same:
+                            raise SystemExit("ray_query_bench: a packed lookup differs from the f32 lookup of the unpacked texels")
+                    del pairs, E_p, E_f
+            del k, anywhere, nrm, lod, w
+        del stored
+    return rows
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--calls", type=int, default=20, help="timed calls per row (at least 20)")
@@ -1385,7 +1548,7 @@ def main():
     ap.add_argument("--width", type=int, default=1920)
     ap.add_argument("--height", type=int, default=1080)
     ap.add_argument("--configs", default="2,4")
-    ap.add_argument("--mode", choices=("intersect", "occlusion", "render", "hemisphere", "bake", "probes", "atlas", "finish", "volume", "variance", "adaptive", "directional", "lookup", "mips"), default="intersect",
+    ap.add_argument("--mode", choices=("intersect", "occlusion", "render", "hemisphere", "bake", "probes", "atlas", "finish", "volume", "variance", "adaptive", "directional", "lookup", "mips", "packed"), default="intersect",
                     help="intersect: the closest-hit rows; occlusion: the any-hit query against the visibility form; "
                          "render: ray-table rendering against mi_shade_rays_device; "
                          "hemisphere: hemisphere occlusion against the any-hit query on the identical pre-made rays; "
@@ -1402,10 +1565,11 @@ def main():
                          "lookup: the lightmap lookup kernels, coherent and shuffled uv, the fused SH form against lml_sample<27> + lsh_eval "
                          "and against a copy of the same bytes; "
                          "mips: the lightmap mip chain, five levels per launch against one, against a copy of the nominal bytes, and the "
-                         "trilinear lookups against the level-0 lookups on the same points")
-    ap.add_argument("--lookup-sizes", default="1024,2048", help="--mode lookup and --mode mips: the square lightmap sizes")
+                         "trilinear lookups against the level-0 lookups on the same points; "
+                         "packed: lmp_pack / lmp_unpack against a copy of the same bytes, and every packed lookup against its f32 twin")
+    ap.add_argument("--lookup-sizes", default="1024,2048", help="--mode lookup, --mode mips and --mode packed: the square lightmap sizes")
     ap.add_argument("--volume-grids", default="16,32", help="--mode volume: probes per axis")
-    ap.add_argument("--volume-points", default=f"{1 << 20},{1 << 22}", help="--mode volume, --mode directional, --mode lookup and --mode mips: point counts")
+    ap.add_argument("--volume-points", default=f"{1 << 20},{1 << 22}", help="--mode volume, --mode directional, --mode lookup, --mode mips and --mode packed: point counts")
     ap.add_argument("--finish-sizes", default="1024,2048,4096", help="--mode finish and --mode variance: the square atlas sizes")
     ap.add_argument("--atlas-sizes", default="1024,2048", help="--mode atlas: the square atlas sizes")
     ap.add_argument("--atlas-grid", type=int, default=0, help="--mode atlas: a synthetic height field of N x N quads (2 N^2 triangles) instead "
@@ -1438,6 +1602,9 @@ def main():
         a.configs = ""
     if a.mode == "mips":
         rows += mips_rows(ctx, [int(v) for v in a.lookup_sizes.split(",")], [int(v) for v in a.volume_points.split(",")], a.calls, a.warmup)
+        a.configs = ""
+    if a.mode == "packed":
+        rows += packed_rows(ctx, [int(v) for v in a.lookup_sizes.split(",")], [int(v) for v in a.volume_points.split(",")], a.calls, a.warmup)
         a.configs = ""
     if a.mode == "adaptive":
         rows += adaptive_rows(ctx, int(a.atlas_sizes.split(",")[0]), a.atlas_bakes)
