@@ -27,12 +27,16 @@ from .tracing import check_finish_sh_tables, check_sh_eval, lightmap_finish_sh, 
 from .tracing import check_lightmap_lookup, lightmap_sample, lightmap_sh_sample, shade_hits_baked  # noqa: F401
 from .tracing import check_lightmap_lod, check_lightmap_mips, lightmap_mip_layout, lightmap_mips  # noqa: F401
 from .tracing import lightmap_sample_lod, lightmap_sh_sample_lod  # noqa: F401
+from .tracing import Bc6hLightmap, check_lightmap_bc6h, check_lightmap_bc6h_image, lightmap_bc6h_chain, lightmap_bc6h_decode  # noqa: F401
+from .tracing import lightmap_bc6h_encode, lightmap_bc6h_layout, lightmap_bc6h_modes, lightmap_sample_bc6h  # noqa: F401
 from .tracing import check_lightmap_packed, lightmap_pack, lightmap_unpack, lightmap_sample_packed, lightmap_sh_sample_packed  # noqa: F401
 
 __all__ = [
     "abi", "Camera", "CameraProjectionMode", "ShadingMode", "Scene", "Context", "MultiContext", "compact_size",
     "Intersectable", "Sphere", "Triangle", "Plane", "ConvexVolume", "StaticMesh",
     "Material", "Lambertian", "Metal", "Dielectric", "ParameterizedMaterial", "Isotropic", "Texture",
+    "lightmap_bc6h_layout", "lightmap_bc6h_encode", "lightmap_bc6h_decode", "lightmap_bc6h_modes", "lightmap_bc6h_chain",
+    "lightmap_sample_bc6h", "check_lightmap_bc6h", "check_lightmap_bc6h_image", "Bc6hLightmap",
     "lightmap_pack", "lightmap_unpack", "lightmap_sample_packed", "lightmap_sh_sample_packed", "check_lightmap_packed",
     "lightmap_mip_layout", "lightmap_mips", "lightmap_sample_lod", "lightmap_sh_sample_lod", "check_lightmap_mips", "check_lightmap_lod",
 ]

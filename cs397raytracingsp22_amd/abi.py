@@ -32,6 +32,10 @@ MI_LM_JITTER = 1           # mi_lightmap_texels / mi_bake_lightmap flags: one ji
 MI_PV_NORMAL_WEIGHT = 1    # mi_probe_volume.flags: weight the eight corners by how far they lie in front of the surface
 MI_LP_F16 = 1              # mi_lightmap_pack / _unpack / _*_packed format: `channels` binary16 per texel (0 is f32: refused there)
 MI_LP_RGB9E5 = 2           # ... one u32 per texel, three 9-bit mantissas and a shared 5-bit exponent (3 channels only)
+MI_BC6H_BLOCK_BYTES = 16   # mi_lightmap_bc6h_*: one block of MI_BC6H_BLOCK_DIM x MI_BC6H_BLOCK_DIM texels
+MI_BC6H_BLOCK_DIM = 4
+MI_BC6H_MODE = 3           # the low five bits of the one block mode written and read (two 10-bit direct endpoints, 4-bit indices)
+MI_BC6H_MAX_ROUNDS = 4     # mi_lightmap_bc6h_encode: the most least-squares rounds
 MI_LS_NEAREST = 1          # mi_lightmap_sample / mi_lightmap_sh_sample flags: the reference's nearest-texel addressing, no interpolation
 
 f3 = C.c_float * 3
@@ -148,6 +152,8 @@ EXPORTS = [
     "mi_lightmap_sh_sample_lod", "mi_lightmap_sh_sample_lod_device",
     "mi_lightmap_pack", "mi_lightmap_pack_device", "mi_lightmap_unpack", "mi_lightmap_unpack_device",
     "mi_lightmap_sample_packed", "mi_lightmap_sample_packed_device", "mi_lightmap_sh_sample_packed", "mi_lightmap_sh_sample_packed_device",
+    "mi_lightmap_bc6h_encode", "mi_lightmap_bc6h_encode_device", "mi_lightmap_bc6h_decode", "mi_lightmap_bc6h_decode_device",
+    "mi_lightmap_sample_bc6h", "mi_lightmap_sample_bc6h_device",
     "mi_multi_create", "mi_multi_create_loopback", "mi_multi_destroy", "mi_multi_device_count", "mi_multi_context", "mi_multi_scene_upload", "mi_multi_reserve", "mi_multi_render",
 ]
 
@@ -355,6 +361,17 @@ def load() -> C.CDLL:
     lib.mi_lightmap_sh_sample_packed_device.argtypes = lib.mi_lightmap_sh_sample_packed.argtypes + [vp]
     for name in ("lightmap_pack", "lightmap_pack_device", "lightmap_unpack", "lightmap_unpack_device", "lightmap_sample_packed",
                  "lightmap_sample_packed_device", "lightmap_sh_sample_packed", "lightmap_sh_sample_packed_device"):
+        getattr(lib, "mi_" + name).restype = C.c_int
+    # BC6H lightmaps (added within ABI 5): width, height, image, valid, rounds, out_blocks; width, height, blocks, out_image; the lookup:
+    # mi_lightmap_sample_packed's list without format and channels
+    lib.mi_lightmap_bc6h_encode.argtypes = [vp, u32, u32, vp, vp, u32, vp]
+    lib.mi_lightmap_bc6h_encode_device.argtypes = lib.mi_lightmap_bc6h_encode.argtypes + [vp]
+    lib.mi_lightmap_bc6h_decode.argtypes = [vp, u32, u32, vp, vp]
+    lib.mi_lightmap_bc6h_decode_device.argtypes = lib.mi_lightmap_bc6h_decode.argtypes + [vp]
+    lib.mi_lightmap_sample_bc6h.argtypes = lib.mi_lightmap_sample_packed.argtypes[:1] + lib.mi_lightmap_sample_packed.argtypes[2:4] + lib.mi_lightmap_sample_packed.argtypes[5:]
+    lib.mi_lightmap_sample_bc6h_device.argtypes = lib.mi_lightmap_sample_bc6h.argtypes + [vp]
+    for name in ("lightmap_bc6h_encode", "lightmap_bc6h_encode_device", "lightmap_bc6h_decode", "lightmap_bc6h_decode_device",
+                 "lightmap_sample_bc6h", "lightmap_sample_bc6h_device"):
         getattr(lib, "mi_" + name).restype = C.c_int
     lib.mi_multi_create.argtypes = [C.c_int, C.POINTER(C.c_int), C.POINTER(vp)]
     lib.mi_multi_create.restype = C.c_int

@@ -78,6 +78,8 @@ hipError_t launch_lml_sample_lod(const LmlLodArgs& a, uint32_t channels, hipStre
 hipError_t launch_lmp_pack(const LmpArgs& a, uint32_t format, bool unpack, hipStream_t stream);
 hipError_t launch_lmp_sample(const LmlArgs& a, uint32_t format, uint32_t channels, hipStream_t stream);
 hipError_t launch_lmp_sample_lod(const LmlLodArgs& a, uint32_t format, uint32_t channels, hipStream_t stream);
+hipError_t launch_lmb_encode(const LmbArgs& a, bool lane_per_block, hipStream_t stream);
+hipError_t launch_lmb_decode(const LmbArgs& a, hipStream_t stream);
 }  // namespace pt
 
 using namespace pt;
@@ -207,6 +209,7 @@ struct mi_ctx {
         ScheduleKnobs sched;                            // the pass schedule's knobs (render_plan.hpp)
         uint32_t lmf_lds_max_step = 1;                  // lmf_atrous: stage the tile and its halo in LDS up to this step, read HBM directly above (measured: DESIGN.md "Lightmap finishing")
         uint32_t lmm_levels_per_launch = kMipFuse;      // lmm_reduce: levels written per launch; 1 is the unfused form (measured: DESIGN.md "Lightmap mips")
+        uint32_t lmb_lane_per_block = 1;                // the BC6H encoder: 1 is lmb_encode_block (one lane per block, 1.3 - 1.65 x faster), 0 lmb_encode (one lane per texel); the same bytes (measured: DESIGN.md "BC6H lightmaps")
         uint32_t spin_timeout_ms = 120000;              // header wait: give up after this long without progress
     } tune;
 };
@@ -279,6 +282,7 @@ static int ctx_init(mi_ctx* c, const hipDeviceProp_t& prop) {
     env_u("MI_RT_SPIN_TIMEOUT_MS", t.spin_timeout_ms);
     env_u("MI_RT_LMF_LDS_MAX_STEP", t.lmf_lds_max_step);
     env_u("MI_RT_LMM_LEVELS_PER_LAUNCH", t.lmm_levels_per_launch);
+    env_u("MI_RT_LMB_LANE_PER_BLOCK", t.lmb_lane_per_block);
     t.lmm_levels_per_launch = std::min(std::max(t.lmm_levels_per_launch, 1u), kMipFuse);
     if (t.lmf_lds_max_step > kLmfMaxLdsStep) t.lmf_lds_max_step = kLmfMaxLdsStep;
     if (t.vote_t < 1) t.vote_t = 1;
@@ -1718,7 +1722,8 @@ extern "C" int mi_lightmap_sh_eval(mi_ctx* c, uint32_t n, const float* sh, const
 // ------------------------------------------------------------------ lightmap lookup (a finished lightmap read at uv points)
 // tracing.py lightmap_sample and lightmap_sh_sample as one kernel each (lml_sample<3>, lml_sample<27>, lml_sh_sample): one lane per point,
 // no scratch, no scene.  One argument record serves both calls: channels == 0 is the fused SH form, which reads 27 floats per texel and
-// the normals and writes three per point.  format: 0 = f32 texels, else MI_LP_* (the packed lookups further down enter here).
+// the normals and writes three per point.  format: 0 = f32 texels, else MI_LP_* (the packed lookups further down enter here) or kLpBc6h
+// (the BC6H lookup, further down still).
 struct LookupArgs {
     uint32_t width, height, channels; const void* image; const uint8_t* valid; uint32_t n; const float* uv; const float* normals;
     uint32_t flags; float* out; float* out_weight; uint32_t format = 0;
@@ -1726,6 +1731,14 @@ struct LookupArgs {
 // The bytes of one stored texel of `channels` values
 static inline size_t texel_bytes(uint32_t format, size_t channels) {
     return format == MI_LP_RGB9E5 ? sizeof(uint32_t) : channels * (format == MI_LP_F16 ? sizeof(uint16_t) : sizeof(float));
+}
+// The bytes of one stored level of width x height texels, and of levels 1 .. L - 1 of a chain: texels, or for kLpBc6h 16-byte blocks
+static inline size_t level_bytes(uint32_t format, uint32_t width, uint32_t height, size_t channels) {
+    if (format == kLpBc6h) return (size_t)bc6h_extent(width) * bc6h_extent(height) * 16u;
+    return (size_t)width * height * texel_bytes(format, channels);
+}
+static inline size_t mips_bytes(uint32_t format, const MipPlan& plan, size_t channels) {
+    return format == kLpBc6h ? (size_t)bc6h_plan(plan).blocks * 16u : (size_t)plan.texels * texel_bytes(format, channels);
 }
 
 // Checked before the context, nothing is launched: the pointers, the size, the channel count, the flags
@@ -1757,7 +1770,7 @@ static int lookup_entry_device(const char* who, mi_ctx* c, const LookupArgs& l, 
     const size_t texels = (size_t)l.width * l.height, in_c = l.channels ? l.channels : (uint32_t)kShFloats, out_c = l.channels ? l.channels : 3u;
     MI_TRY(check_no_overlap(who, { { l.out, (size_t)l.n * out_c * sizeof(float), l.channels ? "out" : "out_irradiance" },
                                    { l.out_weight, (size_t)l.n * sizeof(float), "out_weight" } },
-                            { { l.image, texels * texel_bytes(l.format, in_c) }, { l.valid, texels }, { l.uv, (size_t)l.n * 2 * sizeof(float) },
+                            { { l.image, level_bytes(l.format, l.width, l.height, in_c) }, { l.valid, texels }, { l.uv, (size_t)l.n * 2 * sizeof(float) },
                               { l.normals, (size_t)l.n * 3 * sizeof(float) } }));
     if (l.n == 0) return MI_OK;
     HIP_TRY(hipSetDevice(c->device));
@@ -1771,7 +1784,7 @@ static int lookup_entry_host(const char* who, mi_ctx* c, const LookupArgs& l) {
     if (l.n == 0) return MI_OK;                // before any device call
     const size_t texels = (size_t)l.width * l.height, in_c = l.channels ? l.channels : (uint32_t)kShFloats, out_c = l.channels ? l.channels : 3u;
     enum { kImage, kValid, kUv, kNormals, kOut, kWeight };
-    const StageColumn cols[] = { { l.image, texels * texel_bytes(l.format, in_c), Stage::kIn }, { l.valid, texels, Stage::kIn },
+    const StageColumn cols[] = { { l.image, level_bytes(l.format, l.width, l.height, in_c), Stage::kIn }, { l.valid, texels, Stage::kIn },
                                  { l.uv, (size_t)l.n * 2 * sizeof(float), Stage::kIn }, { l.normals, (size_t)l.n * 3 * sizeof(float), Stage::kIn },
                                  { l.out, (size_t)l.n * out_c * sizeof(float), Stage::kOut }, { l.out_weight, (size_t)l.n * sizeof(float), Stage::kOut } };
     return staged(c, cols, [&](void* const* d) -> int {
@@ -1919,6 +1932,10 @@ static int lod_device(mi_ctx* c, const LodArgs& l, const MipPlan& plan, hipStrea
     a.image = l.image; a.valid = l.valid; a.mips = l.mips; a.mip_valid = l.mip_valid; a.uv = l.uv; a.lod = l.lod; a.normals = l.normals;
     a.out = l.out; a.out_weight = l.out_weight; a.levels = plan.levels; a.n = l.n;
     for (uint32_t k = 0; k < plan.levels; k++) { a.off[k] = plan.level[k].offset; a.lw[k] = plan.level[k].width; a.lh[k] = plan.level[k].height; }
+    if (l.format == kLpBc6h) {
+        const Bc6hPlan blocks = bc6h_plan(plan);
+        for (uint32_t k = 0; k < plan.levels; k++) a.boff[k] = (uint32_t)blocks.level[k].offset;
+    }
     return timed(c, stream, [&]() -> int {
         HIP_TRY(l.format ? launch_lmp_sample_lod(a, l.format, l.channels, stream) : launch_lml_sample_lod(a, l.channels, stream));
         return MI_OK;
@@ -1933,7 +1950,7 @@ static int lod_entry_device(const char* who, mi_ctx* c, const LodArgs& l, void* 
     const size_t in_c = l.channels ? l.channels : (uint32_t)kShFloats, out_c = l.channels ? l.channels : 3u;
     MI_TRY(check_no_overlap(who, { { l.out, (size_t)l.n * out_c * sizeof(float), l.channels ? "out" : "out_irradiance" },
                                    { l.out_weight, (size_t)l.n * sizeof(float), "out_weight" } },
-                            { { l.image, texels * texel_bytes(l.format, in_c) }, { l.valid, texels }, { l.mips, made * texel_bytes(l.format, in_c) },
+                            { { l.image, level_bytes(l.format, l.width, l.height, in_c) }, { l.valid, texels }, { l.mips, mips_bytes(l.format, plan, in_c) },
                               { l.mip_valid, made }, { l.uv, (size_t)l.n * 2 * sizeof(float) }, { l.lod, (size_t)l.n * sizeof(float) },
                               { l.normals, (size_t)l.n * 3 * sizeof(float) } }));
     if (l.n == 0) return MI_OK;
@@ -1950,8 +1967,8 @@ static int lod_entry_host(const char* who, mi_ctx* c, const LodArgs& l) {
     const size_t in_c = l.channels ? l.channels : (uint32_t)kShFloats, out_c = l.channels ? l.channels : 3u;
     const bool chain = plan.levels > 1;
     enum { kImage, kValid, kMips, kMipValid, kUv, kLod, kNormals, kOut, kWeight };
-    const StageColumn cols[] = { { l.image, texels * texel_bytes(l.format, in_c), Stage::kIn }, { l.valid, texels, Stage::kIn },
-                                 { chain ? l.mips : nullptr, made * texel_bytes(l.format, in_c), Stage::kIn },
+    const StageColumn cols[] = { { l.image, level_bytes(l.format, l.width, l.height, in_c), Stage::kIn }, { l.valid, texels, Stage::kIn },
+                                 { chain ? l.mips : nullptr, mips_bytes(l.format, plan, in_c), Stage::kIn },
                                  { chain ? l.mip_valid : nullptr, made, Stage::kIn },
                                  { l.uv, (size_t)l.n * 2 * sizeof(float), Stage::kIn }, { l.lod, (size_t)l.n * sizeof(float), Stage::kIn },
                                  { l.normals, (size_t)l.n * 3 * sizeof(float), Stage::kIn },
@@ -2059,8 +2076,13 @@ extern "C" int mi_lightmap_unpack_device(mi_ctx* c, uint32_t format, uint32_t ch
 }
 
 // The packed lookups: lod != NULL is the trilinear form over the mip plan; lod == NULL the level-0 form, which has no chain
+static int format_lookup_entry(const char* who, mi_ctx* c, uint32_t format, LodArgs l, bool host, void* stream);
 static int packed_lookup_entry(const char* who, mi_ctx* c, uint32_t format, LodArgs l, bool host, void* stream) {
     MI_TRY(check_packed_format(who, format, l.channels, l.channels == 0));
+    return format_lookup_entry(who, c, format, l, host, stream);
+}
+// ... for a format already checked: MI_LP_* or kLpBc6h
+static int format_lookup_entry(const char* who, mi_ctx* c, uint32_t format, LodArgs l, bool host, void* stream) {
     l.format = format;
     if (l.lod) return host ? lod_entry_host(who, c, l) : lod_entry_device(who, c, l, stream);
     if (l.levels != 1 || l.mips || l.mip_valid)
@@ -2096,6 +2118,87 @@ extern "C" int mi_lightmap_sh_sample_packed_device(mi_ctx* c, uint32_t format, u
                                                    float* out_irradiance, float* out_weight, void* stream) {
     return packed_lookup_entry("mi_lightmap_sh_sample_packed_device", c, format, { width, height, 0, sh, valid, levels, mips, mip_valid, n, uv,
                                normals, lod, flags, out_irradiance, out_weight }, false, stream);
+}
+
+// ------------------------------------------------------------------ BC6H lightmaps (a block encoder, the decoder, the lookup that reads blocks)
+// tracing.py lightmap_bc6h_encode / lightmap_bc6h_decode as lmb_encode / lmb_decode, one level per call; the lookup is the lookups above
+// with the format kLpBc6h: the same checks, staging, plan and timing, the lmp_* kernels with the block policy.  BC6H is lossy, so it has
+// entry points of its own: the MI_LP_* calls keep refusing every format they refused.
+struct Bc6hArgs { uint32_t width, height; const float* image; const uint8_t* valid; uint32_t rounds; void* blocks; float* out; bool decode; };
+
+static int bc6h_device(mi_ctx* c, const Bc6hArgs& b, hipStream_t stream) {
+    LmbArgs a{};
+    a.image = b.image; a.valid = b.valid; a.blocks = b.blocks; a.out = b.out; a.rounds = b.rounds;
+    a.width = b.width; a.height = b.height; a.bw = bc6h_extent(b.width); a.bh = bc6h_extent(b.height);
+    return timed(c, stream, [&]() -> int {
+        HIP_TRY(b.decode ? launch_lmb_decode(a, stream) : launch_lmb_encode(a, c->tune.lmb_lane_per_block != 0, stream));
+        return MI_OK;
+    });
+}
+
+// host: HOST pointers, staged and blocking; else DEVICE pointers queued on `stream`
+static int bc6h_entry(const char* who, mi_ctx* c, const Bc6hArgs& b, bool host, void* stream) {
+    if (!b.blocks || (b.decode ? !b.out : !b.image))
+        return fail(MI_ERR_INVALID, b.decode ? "%s: blocks and out_image are required" : "%s: image and out_blocks are required", who);
+    if (b.width == 0 || b.width > 32768u || b.height == 0 || b.height > 32768u)
+        return fail(MI_ERR_INVALID, "%s: width %u / height %u is not in 1 .. 32768", who, b.width, b.height);
+    if (b.rounds > kBc6hMaxRounds) return fail(MI_ERR_INVALID, "%s: rounds %u is above %u", who, b.rounds, kBc6hMaxRounds);
+    if (!host && ((uintptr_t)b.blocks & 15u)) return fail(MI_ERR_INVALID, "%s: the blocks are not 16-byte aligned", who);
+    if (!c) return fail(MI_ERR_INVALID, "ctx is NULL");
+    const size_t texels = (size_t)b.width * b.height, f32_bytes = texels * 3 * sizeof(float), block_bytes = level_bytes(kLpBc6h, b.width, b.height, 3);
+    if (!host) {
+        if (b.decode) MI_TRY(check_no_overlap(who, { { b.out, f32_bytes, "out_image" } }, { { b.blocks, block_bytes } }));
+        else MI_TRY(check_no_overlap(who, { { b.blocks, block_bytes, "out_blocks" } }, { { b.image, f32_bytes }, { b.valid, texels } }));
+        HIP_TRY(hipSetDevice(c->device));
+        return bc6h_device(c, b, (hipStream_t)stream);
+    }
+    if (b.decode) {
+        const StageColumn cols[] = { { b.blocks, block_bytes, Stage::kIn }, { b.out, f32_bytes, Stage::kOut } };
+        return staged(c, cols, [&](void* const* d) -> int {
+            Bc6hArgs db = b;
+            db.blocks = d[0]; db.out = (float*)d[1];
+            return bc6h_device(c, db, c->stream);
+        });
+    }
+    const StageColumn cols[] = { { b.image, f32_bytes, Stage::kIn }, { b.valid, texels, Stage::kIn }, { b.blocks, block_bytes, Stage::kOut } };
+    return staged(c, cols, [&](void* const* d) -> int {
+        Bc6hArgs db = b;
+        db.image = (const float*)d[0]; db.valid = (const uint8_t*)d[1]; db.blocks = d[2];
+        return bc6h_device(c, db, c->stream);
+    });
+}
+
+extern "C" int mi_lightmap_bc6h_encode(mi_ctx* c, uint32_t width, uint32_t height, const float* image, const uint8_t* valid, uint32_t rounds,
+                                       void* out_blocks) {
+    return bc6h_entry("mi_lightmap_bc6h_encode", c, { width, height, image, valid, rounds, out_blocks, nullptr, false }, true, nullptr);
+}
+extern "C" int mi_lightmap_bc6h_encode_device(mi_ctx* c, uint32_t width, uint32_t height, const float* image, const uint8_t* valid,
+                                              uint32_t rounds, void* out_blocks, void* stream) {
+    return bc6h_entry("mi_lightmap_bc6h_encode_device", c, { width, height, image, valid, rounds, out_blocks, nullptr, false }, false, stream);
+}
+extern "C" int mi_lightmap_bc6h_decode(mi_ctx* c, uint32_t width, uint32_t height, const void* blocks, float* out_image) {
+    return bc6h_entry("mi_lightmap_bc6h_decode", c, { width, height, nullptr, nullptr, 0, (void*)blocks, out_image, true }, true, nullptr);
+}
+extern "C" int mi_lightmap_bc6h_decode_device(mi_ctx* c, uint32_t width, uint32_t height, const void* blocks, float* out_image, void* stream) {
+    return bc6h_entry("mi_lightmap_bc6h_decode_device", c, { width, height, nullptr, nullptr, 0, (void*)blocks, out_image, true }, false, stream);
+}
+
+// The lookup: mi_lightmap_sample_packed's rules word for word, three channels, the texels in blocks
+static int bc6h_lookup_entry(const char* who, mi_ctx* c, const LodArgs& l, bool host, void* stream) {
+    if (!host && (((uintptr_t)l.image | (uintptr_t)l.mips) & 15u)) return fail(MI_ERR_INVALID, "%s: the blocks are not 16-byte aligned", who);
+    return format_lookup_entry(who, c, kLpBc6h, l, host, stream);
+}
+extern "C" int mi_lightmap_sample_bc6h(mi_ctx* c, uint32_t width, uint32_t height, const void* image_blocks, const uint8_t* valid,
+                                       uint32_t levels, const void* mip_blocks, const uint8_t* mip_valid, uint32_t n, const float* uv,
+                                       const float* lod, uint32_t flags, float* out, float* out_weight) {
+    return bc6h_lookup_entry("mi_lightmap_sample_bc6h", c, { width, height, 3, image_blocks, valid, levels, mip_blocks, mip_valid, n, uv, nullptr,
+                             lod, flags, out, out_weight }, true, nullptr);
+}
+extern "C" int mi_lightmap_sample_bc6h_device(mi_ctx* c, uint32_t width, uint32_t height, const void* image_blocks, const uint8_t* valid,
+                                              uint32_t levels, const void* mip_blocks, const uint8_t* mip_valid, uint32_t n, const float* uv,
+                                              const float* lod, uint32_t flags, float* out, float* out_weight, void* stream) {
+    return bc6h_lookup_entry("mi_lightmap_sample_bc6h_device", c, { width, height, 3, image_blocks, valid, levels, mip_blocks, mip_valid, n, uv,
+                             nullptr, lod, flags, out, out_weight }, false, stream);
 }
 
 // ------------------------------------------------------------------ variance-guided lightmap finishing

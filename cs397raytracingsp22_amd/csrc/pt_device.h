@@ -498,6 +498,7 @@ struct LmlLodArgs {
     uint64_t       off[kMipMaxLevels];                        // level l starts at texel off[l] of mips (off[0] unused)
     uint32_t       lw[kMipMaxLevels], lh[kMipMaxLevels];      // the levels' sizes
     uint32_t levels, n;
+    uint32_t       boff[kMipMaxLevels];                       // BC6H texels only: level l starts at block boff[l] of mips (else unused)
 };
 
 // ---- packed lightmaps (mi_lightmap_pack, mi_lightmap_unpack, mi_lightmap_*_packed; pt_kernels.hip "lmp_*") ----
@@ -509,6 +510,23 @@ struct LmpArgs {
     const void* src;                 // pack: [n] f32; unpack: [n] packed items
     void*       dst;                 // pack: [n] packed items; unpack: [n] f32
     uint64_t    n;                   // f16: elements (texels x channels); RGB9E5: texels (three floats each)
+};
+
+// ---- BC6H lightmaps (mi_lightmap_bc6h_encode, mi_lightmap_bc6h_decode, mi_lightmap_sample_bc6h; pt_kernels.hip "lmb_*") ----
+// BC6H_UF16 blocks of the one mode tracing.py lightmap_bc6h_encode writes: 16 bytes per 4 x 4 texels, ceil(W / 4) x ceil(H / 4) blocks,
+// row-major (render_plan.cpp bc6h_plan).  A BC6H lookup is the lml_* device code with the texel-fetch policy LmTexBc6h; kLpBc6h names
+// it beside kLpF16 and kLpRgb9e5 inside the library only (the MI_LP_* calls refuse it: the format is lossy and has its own entry points).
+constexpr uint32_t kLpBc6h = 3;
+constexpr uint32_t kBc6hMaxRounds = 4;
+// tracing.py lightmap_bc6h_encode (lmb_encode: one lane per texel, or lmb_encode_block: one lane per block) and lightmap_bc6h_decode
+// (lmb_decode: one lane per texel)
+struct LmbArgs {
+    const float*   image;            // encode: [H][W][3] f32
+    const uint8_t* valid;            // encode: [H][W] or nullptr = every texel takes part
+    void*          blocks;           // [bh][bw] blocks of 16 bytes, 16-byte aligned: written by encode, read by decode
+    float*         out;              // decode: [H][W][3] f32
+    uint32_t width, height, bw, bh;
+    uint32_t rounds;                 // encode: least-squares rounds, 0 .. kBc6hMaxRounds
 };
 
 // ---- variance-guided lightmap finishing (mi_lightmap_finish_var; pt_kernels.hip "lmv_*") ----

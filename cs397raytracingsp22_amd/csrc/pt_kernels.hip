@@ -4466,28 +4466,55 @@ __global__ __launch_bounds__(kBlock) void lsh_eval(const LshEvalArgs a) {
 // record is 108 bytes, so a record is only 4-byte aligned: the taps are read as lsh_atrous reads its records, float by float.
 
 // The lookup arithmetic exists once, in the lml_*_body functions below; what differs between the f32 kernels (lml_*) and the packed
-// ones (lmp_*) is the texel-fetch policy Tx: Tx::level(base, t, C) is where the texel t of a buffer starts, Tx(base, q, C) names texel q
-// behind it and [k] is its channel k as an f32.  Every policy decodes exactly, so a packed lookup is the f32 lookup of the unpacked
+// ones (lmp_*) is the texel-fetch policy Tx: Tx::level(a, l, C) is where level l >= 1 of a chain starts in a.mips, Tx(base, q, C, x, y, W)
+// names texel q = y W + x of a level W texels wide behind it and [k] is its channel k as an f32.  The linear policies use q alone; the
+// block policy (LmTexBc6h) uses x, y and W alone.  Every policy decodes exactly, so a packed lookup is the f32 lookup of the unpacked
 // texels, bit for bit.  A texel is touched only through its Tx, which is made only for a tap that takes part.
 struct LmTexF32 {                                                  // C floats: read where they are used, as before
     const float* p;
-    static __device__ __forceinline__ const void* level(const void* base, size_t t, int C) { return (const float*)base + t * C; }
-    __device__ __forceinline__ LmTexF32(const void* base, size_t q, int C) : p((const float*)base + q * C) {}
+    static __device__ __forceinline__ const void* level(const LmlLodArgs& a, int l, int C) { return (const float*)a.mips + (size_t)a.off[l] * C; }
+    __device__ __forceinline__ LmTexF32(const void* base, size_t q, int C, int = 0, int = 0, int = 0) : p((const float*)base + q * C) {}
     __device__ __forceinline__ float operator[](int k) const { return p[k]; }
 };
 struct LmTexF16 {                                                  // C halves, 2-byte aligned only (6 or 54 bytes a texel): one by one
     const _Float16* p;
-    static __device__ __forceinline__ const void* level(const void* base, size_t t, int C) { return (const _Float16*)base + t * C; }
-    __device__ __forceinline__ LmTexF16(const void* base, size_t q, int C) : p((const _Float16*)base + q * C) {}
+    static __device__ __forceinline__ const void* level(const LmlLodArgs& a, int l, int C) { return (const _Float16*)a.mips + (size_t)a.off[l] * C; }
+    __device__ __forceinline__ LmTexF16(const void* base, size_t q, int C, int = 0, int = 0, int = 0) : p((const _Float16*)base + q * C) {}
     __device__ __forceinline__ float operator[](int k) const { return (float)p[k]; }
 };
 struct LmTexRgb9e5 {                                               // one dword: q_k * 2^(e - 24), the scale built from the exponent
     uint32_t w; float s;
-    static __device__ __forceinline__ const void* level(const void* base, size_t t, int) { return (const uint32_t*)base + t; }
-    __device__ __forceinline__ LmTexRgb9e5(const void* base, size_t q, int) : w(((const uint32_t*)base)[q]) {
+    static __device__ __forceinline__ const void* level(const LmlLodArgs& a, int l, int) { return (const uint32_t*)a.mips + (size_t)a.off[l]; }
+    __device__ __forceinline__ LmTexRgb9e5(const void* base, size_t q, int, int = 0, int = 0, int = 0) : w(((const uint32_t*)base)[q]) {
         s = __uint_as_float(((w >> 27) + 103u) << 23);
     }
     __device__ __forceinline__ float operator[](int k) const { return (float)((w >> (9 * k)) & 511u) * s; }
+};
+// BC6H_UF16, the one mode tracing.py lightmap_bc6h_decode reads (low five bits 3: two 10-bit direct endpoints, 4-bit indices); every
+// other mode is sixteen zero texels.  All integer: the shared pieces of the decoder, the encoder (lmb_* below) and this policy.
+__device__ __forceinline__ float lmp_f16_value(uint32_t bits);
+__device__ __forceinline__ uint32_t lmb_weight(uint32_t i) { return (i * 64u + 7u) / 15u; }      // {0, 4, 9, 13, 17, 21, 26, 30, 34, 38, 43, 47, 51, 55, 60, 64}[i]
+__device__ __forceinline__ uint32_t lmb_unq(uint32_t q) { return q == 0u ? 0u : q == 1023u ? 0xFFFFu : q * 64u + 32u; }
+// The binary16 bits of one channel: unquantised endpoints a, b and the weight w = lmb_weight(index)
+__device__ __forceinline__ uint32_t lmb_interp(uint32_t a, uint32_t b, uint32_t w) { return (((a * (64u - w) + b * w + 32u) >> 6) * 31u) >> 6; }
+// The 10-bit field at `bit` (5 .. 55) of a block
+__device__ __forceinline__ uint32_t lmb_field(const uint4& b, int bit) {
+    const uint64_t lo = (uint64_t)b.x | (uint64_t)b.y << 32;
+    return (uint32_t)((lo >> bit) | ((uint64_t)b.z << (64 - bit))) & 1023u;
+}
+struct LmTexBc6h {                                                 // one 16-byte load of the tap's block; the index once, a channel per [k]
+    uint4 b; uint32_t w;
+    static __device__ __forceinline__ const void* level(const LmlLodArgs& a, int l, int) { return (const uint4*)a.mips + (size_t)a.boff[l]; }
+    __device__ __forceinline__ LmTexBc6h(const void* base, size_t, int, int x, int y, int W)
+        : b(((const uint4*)base)[(size_t)(y >> 2) * (size_t)((W + 3) >> 2) + (size_t)(x >> 2)]) {
+        const int t = (y & 3) * 4 + (x & 3);
+        const uint32_t i = ((t < 8 ? b.z : b.w) >> (4 * (t & 7))) & 15u;       // texel t's index sits at bit 64 + 4 t
+        w = lmb_weight(t == 0 ? i >> 1 : i);                       // (texel 0 has three bits, from bit 65: bit 64 is the last field's)
+    }
+    __device__ __forceinline__ float operator[](int k) const {
+        const uint32_t h = lmb_interp(lmb_unq(lmb_field(b, 5 + 10 * k)), lmb_unq(lmb_field(b, 35 + 10 * k)), w);
+        return lmp_f16_value((b.x & 31u) == 3u ? h : 0u);
+    }
 };
 
 // One axis of the bilinear form: pv_sample's index expressions.  fmaxf sends a NaN to 0, so the indices stay in range for any t.
@@ -4503,8 +4530,8 @@ __device__ __forceinline__ void lml_axis(float t, int n, int (&i)[2], float (&w)
 // texel of the clamped coordinate, or of its mirror, times n; `nan`: the coordinate was a NaN, which Rust's saturating cast sends to 0
 __device__ __forceinline__ float lml_unit(float t) { return fminf(fmaxf(t, 0.0f), 0.999f); }
 __device__ __forceinline__ int lml_texel(float s, int n, bool nan) { return nan ? 0 : max(min((int)(s * (float)n), n - 1), 0); }
-__device__ __forceinline__ size_t lml_nearest(const LmlArgs& a, float u, float v) {
-    const int x = lml_texel(lml_unit(u), (int)a.width, u != u), y = lml_texel(1.0f - lml_unit(v), (int)a.height, v != v);
+__device__ __forceinline__ size_t lml_nearest(const LmlArgs& a, float u, float v, int& x, int& y) {
+    x = lml_texel(lml_unit(u), (int)a.width, u != u); y = lml_texel(1.0f - lml_unit(v), (int)a.height, v != v);
     return (size_t)y * a.width + (size_t)x;
 }
 
@@ -4517,9 +4544,10 @@ template <class Tx, int C> __device__ __forceinline__ void lml_sample_body(const
 #pragma unroll
     for (int k = 0; k < C; k++) acc[k] = 0.0f;
     if (a.nearest) {
-        const size_t q = lml_nearest(a, u, v);
+        int x, y;
+        const size_t q = lml_nearest(a, u, v, x, y);
         if (!a.valid || a.valid[q] != 0) {
-            const Tx t(a.image, q, C);
+            const Tx t(a.image, q, C, x, y, (int)a.width);
 #pragma unroll
             for (int k = 0; k < C; k++) acc[k] = t[k];             // as it stands: a -0.0 stays one
             sw = 1.0f;
@@ -4536,7 +4564,7 @@ template <class Tx, int C> __device__ __forceinline__ void lml_sample_body(const
                 const float w = wx[dx] * wy[dy];
                 const size_t q = (size_t)iy[dy] * a.width + (size_t)ix[dx];
                 if (!(w > 0.0f) || (a.valid && a.valid[q] == 0)) continue;
-                const Tx t(a.image, q, C);
+                const Tx t(a.image, q, C, ix[dx], iy[dy], (int)a.width);
 #pragma unroll
                 for (int k = 0; k < C; k++) acc[k] = acc[k] + w * t[k];
                 sw = sw + w;
@@ -4579,7 +4607,8 @@ template <class Tx> __device__ __forceinline__ void lml_sh_sample_body(const Lml
             }
         };
         if (a.nearest) {
-            const size_t q = lml_nearest(a, u, v);
+            int x, y;
+            const size_t q = lml_nearest(a, u, v, x, y);
             if (!a.valid || a.valid[q] != 0) { eval(q, E); sw = 1.0f; }
         } else {
             int ix[2], iy[2];
@@ -4711,11 +4740,12 @@ __device__ __forceinline__ void lml_levels(float lod, int L, int (&l)[2], float 
     l[0] = la; l[1] = min(la + 1, L - 1);
     w[0] = 1.0f - f; w[1] = f;
 }
-// The tap loop of one level, written once: tap(texels of the level, texel index, weight) for every tap that takes part, dy outer, dx inner
+// The tap loop of one level, written once: tap(texels of the level, texel index, weight, x, y, the level's width) for every tap that takes
+// part, dy outer, dx inner
 template <class Tx, int C, class Tap> __device__ __forceinline__ void lml_level_taps(const LmlLodArgs& a, int l, float wl, float u, float v, Tap tap) {
     const int W = (int)a.lw[l], H = (int)a.lh[l];
     const float s = __uint_as_float((uint32_t)(127 - l) << 23);                  // 2^-l, l <= 15
-    const void* texels = l == 0 ? a.image : Tx::level(a.mips, (size_t)a.off[l], C);
+    const void* texels = l == 0 ? a.image : Tx::level(a, l, C);
     const uint8_t* valid = l == 0 ? a.valid : a.mip_valid ? a.mip_valid + (size_t)a.off[l] : nullptr;
     int ix[2], iy[2];
     float wx[2], wy[2];
@@ -4728,7 +4758,7 @@ template <class Tx, int C, class Tap> __device__ __forceinline__ void lml_level_
             const float w = wl * (wx[dx] * wy[dy]);
             const size_t q = (size_t)iy[dy] * (size_t)W + (size_t)ix[dx];
             if (!(w > 0.0f) || (valid && valid[q] == 0)) continue;
-            tap(texels, q, w);
+            tap(texels, q, w, ix[dx], iy[dy], W);
         }
 }
 
@@ -4745,8 +4775,8 @@ template <class Tx, int C> __device__ __forceinline__ void lml_sample_lod_body(c
     for (int k = 0; k < C; k++) acc[k] = 0.0f;
     for (int side = 0; side < 2; side++) {
         if (!(wl[side] > 0.0f)) continue;
-        lml_level_taps<Tx, C>(a, lv[side], wl[side], u, v, [&](const void* texels, size_t q, float w) {
-            const Tx t(texels, q, C);
+        lml_level_taps<Tx, C>(a, lv[side], wl[side], u, v, [&](const void* texels, size_t q, float w, int x, int y, int W) {
+            const Tx t(texels, q, C, x, y, W);
 #pragma unroll
             for (int k = 0; k < C; k++) acc[k] = acc[k] + w * t[k];
             sw = sw + w;
@@ -4782,7 +4812,7 @@ template <class Tx> __device__ __forceinline__ void lml_sh_sample_lod_body(const
         lml_levels(a.lod[i], (int)a.levels, lv, wl);
         for (int side = 0; side < 2; side++) {
             if (!(wl[side] > 0.0f)) continue;
-            lml_level_taps<Tx, kShFloats>(a, lv[side], wl[side], u, v, [&](const void* texels, size_t q, float w) {
+            lml_level_taps<Tx, kShFloats>(a, lv[side], wl[side], u, v, [&](const void* texels, size_t q, float w, int, int, int) {
                 const Tx sh(texels, q, kShFloats);
 #pragma unroll
                 for (int c = 0; c < 3; c++) {
@@ -4880,6 +4910,317 @@ template <> __global__ __launch_bounds__(kBlock) void lmp_unpack<kLpRgb9e5>(cons
     for (int k = 0; k < 3; k++) o[k] = t[k];
 }
 
+// ---------------------------------------------------------------- BC6H lightmaps (mi_lightmap_bc6h_encode, mi_lightmap_bc6h_decode)
+// tracing.py lightmap_bc6h_encode and lightmap_bc6h_decode on the device, all integer after the binary16 conversion, so the bytes are the
+// helper's.  lmb_encode: one lane per texel, a 4 x 4 block is one 16-lane row of a wave (four blocks to a wave); the farthest pair, the
+// least-squares sums and the block's error are reductions within the row (__shfl / __shfl_xor, width 16), no LDS, and lane 0 of the row
+// writes the block as one 16-byte store.  Everything a row branches on is uniform over the row, and no shuffle sits inside a branch.
+// A texel that takes no part is not read.  lmb_decode: one lane per texel through LmTexBc6h, the lookups' policy.
+__device__ __forceinline__ uint32_t lmb_half_bits(float x) {                     // step 1: a NaN, a negative and -0.0 give 0; 0 .. 0x7BFF
+    const _Float16 h = (_Float16)(x > 0.0f ? fminf(x, 65504.0f) : 0.0f);
+    uint16_t bits;
+    __builtin_memcpy(&bits, &h, sizeof(bits));
+    return bits;
+}
+__device__ __forceinline__ uint32_t lmb_to_c(uint32_t h) { return (64u * h + 30u) / 31u; }        // the smallest c with (c * 31) >> 6 == h
+// The field whose unquantised value is nearest to c (0 .. 65535), the lower field on a tie: three candidates in ascending order
+__device__ __forceinline__ uint32_t lmb_quant(uint32_t c) {
+    const int q0 = min(max(((int)c - 1) >> 6, 0), 1023);
+    uint32_t best = (uint32_t)max(q0 - 1, 0);
+    int bd = abs((int)lmb_unq(best) - (int)c);
+#pragma unroll
+    for (int step = 0; step < 2; step++) {
+        const uint32_t q = (uint32_t)min(q0 + step, 1023);
+        const int d = abs((int)lmb_unq(q) - (int)c);
+        if (d < bd) { best = q; bd = d; }
+    }
+    return best;
+}
+// The index whose colour is nearest to the target t (binary16 bits) between the unquantised endpoints ua, ub: exhaustive, the lowest
+// index on a tie; err: that squared distance (at most 3 * 0x7BFF^2 < 2^32)
+__device__ __forceinline__ uint32_t lmb_best(const uint32_t (&t)[3], const uint32_t (&ua)[3], const uint32_t (&ub)[3], uint32_t& err) {
+    uint32_t bi = 0, be = 0xFFFFFFFFu;
+#pragma unroll
+    for (uint32_t i = 0; i < 16; i++) {
+        uint32_t e = 0;
+#pragma unroll
+        for (int k = 0; k < 3; k++) {
+            const int d = (int)t[k] - (int)lmb_interp(ua[k], ub[k], lmb_weight(i));
+            e += (uint32_t)(d * d);
+        }
+        if (e < be) { be = e; bi = i; }
+    }
+    err = be;
+    return bi;
+}
+// Reductions over the 16 lanes of a row; every lane gets the result
+__device__ __forceinline__ uint32_t lmb_row_sum(uint32_t v) {
+#pragma unroll
+    for (int m = 8; m > 0; m >>= 1) v += (uint32_t)__shfl_xor((int)v, m, 16);
+    return v;
+}
+__device__ __forceinline__ uint32_t lmb_row_or(uint32_t v) {
+#pragma unroll
+    for (int m = 8; m > 0; m >>= 1) v |= (uint32_t)__shfl_xor((int)v, m, 16);
+    return v;
+}
+__device__ __forceinline__ uint64_t lmb_xor64(uint64_t v, int m) {
+    return (uint64_t)(uint32_t)__shfl_xor((int)(uint32_t)v, m, 16) | (uint64_t)(uint32_t)__shfl_xor((int)(uint32_t)(v >> 32), m, 16) << 32;
+}
+__device__ __forceinline__ uint64_t lmb_row_sum64(uint64_t v) {
+#pragma unroll
+    for (int m = 8; m > 0; m >>= 1) v += lmb_xor64(v, m);
+    return v;
+}
+// One least-squares endpoint: (2 num + det) // (2 det) clamped to 0 .. 65535 (floor division: a numerator <= 0 clamps to 0); det > 0
+__device__ __forceinline__ uint32_t lmb_solve(int64_t num, int64_t det) {
+    const int64_t n2 = 2 * num + det;
+    if (n2 <= 0) return 0u;
+    const uint64_t q = (uint64_t)n2 / (uint64_t)(2 * det);
+    return (uint32_t)(q < 65535ull ? q : 65535ull);
+}
+// The block's 16 bytes from its fields f[endpoint][channel] and the index words (texel t's index at bit 4 t of z : w, texel 0's from bit 1)
+__device__ __forceinline__ uint4 lmb_block(const uint32_t (&f)[2][3], uint32_t z, uint32_t w) {
+    const uint64_t lo = 3ull | (uint64_t)f[0][0] << 5 | (uint64_t)f[0][1] << 15 | (uint64_t)f[0][2] << 25 | (uint64_t)f[1][0] << 35 |
+                        (uint64_t)f[1][1] << 45 | (uint64_t)(f[1][2] & 511u) << 55;
+    return make_uint4((uint32_t)lo, (uint32_t)(lo >> 32), z | f[1][2] >> 9, w);
+}
+
+__global__ __launch_bounds__(kBlock) void lmb_encode(const LmbArgs a) {
+    static_assert(kBlock % 16 == 0, "a row of 16 lanes is one block");
+    const size_t g = (size_t)blockIdx.x * kBlock + threadIdx.x;
+    const uint32_t blk = (uint32_t)(g >> 4), t = threadIdx.x & 15u;
+    if (g >> 4 >= (size_t)a.bw * a.bh) return;                                   // whole rows leave together
+    const uint32_t x = (blk % a.bw) * 4u + (t & 3u), y = (blk / a.bw) * 4u + (t >> 2);
+    const size_t q = (size_t)y * a.width + x;
+    bool part = x < a.width && y < a.height;
+    if (part && a.valid) part = a.valid[q] != 0;
+    uint32_t h[3] = { 0u, 0u, 0u };
+    if (part) {
+        const float* p = a.image + q * 3;
+#pragma unroll
+        for (int k = 0; k < 3; k++) h[k] = lmb_half_bits(p[k]);
+    }
+    const uint32_t n = lmb_row_sum(part ? 1u : 0u);
+    if (n == 0u) {                                                               // nothing takes part: the word 3 and zeros
+        if (t == 0u) ((uint4*)a.blocks)[blk] = make_uint4(3u, 0u, 0u, 0u);
+        return;
+    }
+    uint32_t tgt[3], ct[3], sc[3];
+#pragma unroll
+    for (int k = 0; k < 3; k++) {
+        const uint32_t mean = lmb_row_sum(h[k]) / n;                             // (h is 0 where the texel takes no part)
+        tgt[k] = part ? h[k] : mean;
+        ct[k] = part ? lmb_to_c(h[k]) : 0u;
+        sc[k] = lmb_row_sum(ct[k]);
+    }
+    // the farthest pair (i <= j) of texels that take part, the lowest (i, j) on a tie: lane i looks at every j >= i
+    const uint32_t p01 = h[0] | h[1] << 16, p2 = h[2] | (part ? 1u : 0u) << 16;
+    int64_t key = -1;
+#pragma unroll
+    for (int j = 0; j < 16; j++) {
+        const uint32_t o01 = (uint32_t)__shfl((int)p01, j, 16), o2 = (uint32_t)__shfl((int)p2, j, 16);
+        const int d0 = (int)h[0] - (int)(o01 & 0xFFFFu), d1 = (int)h[1] - (int)(o01 >> 16), d2 = (int)h[2] - (int)(o2 & 0xFFFFu);
+        const uint32_t dist = (uint32_t)(d0 * d0) + (uint32_t)(d1 * d1) + (uint32_t)(d2 * d2);
+        const int64_t k = (int64_t)dist * 256 + (int64_t)(255u - (16u * t + (uint32_t)j));
+        if (part && (o2 >> 16) != 0u && (uint32_t)j >= t && k > key) key = k;
+    }
+#pragma unroll
+    for (int m = 8; m > 0; m >>= 1) {
+        const int64_t o = (int64_t)lmb_xor64((uint64_t)key, m);
+        key = o > key ? o : key;
+    }
+    const uint32_t pair = 255u - (uint32_t)(key & 255);
+    uint32_t f[2][3], c0[3] = { 0u, 0u, 0u };
+#pragma unroll
+    for (int e = 0; e < 2; e++) {
+        const int src = (int)(e == 0 ? pair >> 4 : pair & 15u);
+        const uint32_t e01 = (uint32_t)__shfl((int)p01, src, 16), e2 = (uint32_t)__shfl((int)p2, src, 16);
+        const uint32_t c[3] = { lmb_to_c(e01 & 0xFFFFu), lmb_to_c(e01 >> 16), lmb_to_c(e2 & 0xFFFFu) };
+#pragma unroll
+        for (int k = 0; k < 3; k++) { f[e][k] = lmb_quant(c[k]); c0[k] = e == 0 ? c[k] : c0[k]; }
+    }
+    // a flat start (uniform over the row): a channel whose one field lies more than 32 from endpoint 0's c takes the two fields around c
+    const bool flat = f[0][0] == f[1][0] && f[0][1] == f[1][1] && f[0][2] == f[1][2];
+#pragma unroll
+    for (int k = 0; k < 3; k++) {
+        const bool wide = flat && abs((int)lmb_unq(f[0][k]) - (int)c0[k]) > 32;
+        const uint32_t below = c0[k] < 96u ? 0u : 1022u;
+        f[0][k] = wide ? below : f[0][k];
+        f[1][k] = wide ? below + 1u : f[1][k];
+    }
+    uint32_t ua[3], ub[3], e1;
+#pragma unroll
+    for (int k = 0; k < 3; k++) { ua[k] = lmb_unq(f[0][k]); ub[k] = lmb_unq(f[1][k]); }
+    uint32_t idx = lmb_best(tgt, ua, ub, e1);
+    uint64_t err = lmb_row_sum64(part ? e1 : 0u);
+    // least-squares rounds: u = 64 - v, so Suv = 64 Sv - Svv, Suu = 4096 n - 128 Sv + Svv and Suc = 64 Sc - Svc (the same integers)
+    for (uint32_t r = 0; r < a.rounds; r++) {
+        const uint32_t v = part ? lmb_weight(idx) : 0u;
+        const uint32_t s = lmb_row_sum(v * v | v << 20);                         // Svv <= 2^16 below Sv <= 2^10
+        const int64_t Sv = (int64_t)(s >> 20), Svv = (int64_t)(s & 0xFFFFFu);
+        const int64_t Suv = 64 * Sv - Svv, Suu = 4096 * (int64_t)n - 128 * Sv + Svv;
+        const int64_t det = Suu * Svv - Suv * Suv;
+        int64_t Suc[3], Svc[3];
+#pragma unroll
+        for (int k = 0; k < 3; k++) { Svc[k] = (int64_t)lmb_row_sum(v * ct[k]); Suc[k] = 64 * (int64_t)sc[k] - Svc[k]; }
+        // lanes 0 .. 5 divide one endpoint of one channel each: lane k + 3 e has endpoint e of channel k
+        const uint32_t ch = t % 3u;
+        const int64_t suc = ch == 0u ? Suc[0] : ch == 1u ? Suc[1] : Suc[2], svc = ch == 0u ? Svc[0] : ch == 1u ? Svc[1] : Svc[2];
+        const int64_t num = (t / 3u) & 1u ? 64 * (Suu * svc - Suv * suc) : 64 * (Svv * suc - Suv * svc);
+        const uint32_t solved = lmb_quant(lmb_solve(num, det != 0 ? det : 1));
+        uint32_t cf[2][3], ca[3], cb[3], e2;
+#pragma unroll
+        for (int e = 0; e < 2; e++)
+#pragma unroll
+            for (int k = 0; k < 3; k++) {
+                const uint32_t got = (uint32_t)__shfl((int)solved, k + 3 * e, 16);
+                cf[e][k] = det != 0 ? got : f[e][k];
+            }
+#pragma unroll
+        for (int k = 0; k < 3; k++) { ca[k] = lmb_unq(cf[0][k]); cb[k] = lmb_unq(cf[1][k]); }
+        const uint32_t cidx = lmb_best(tgt, ca, cb, e2);
+        const uint64_t cerr = lmb_row_sum64(part ? e2 : 0u);
+        const bool better = cerr < err;                                          // kept only if strictly lower
+#pragma unroll
+        for (int e = 0; e < 2; e++)
+#pragma unroll
+            for (int k = 0; k < 3; k++) f[e][k] = better ? cf[e][k] : f[e][k];
+        idx = better ? cidx : idx;
+        err = better ? cerr : err;
+    }
+    // the anchor: texel 0's index below 8
+    const bool swap = (uint32_t)__shfl((int)idx, 0, 16) >= 8u;
+    if (swap) {
+        idx = 15u - idx;
+#pragma unroll
+        for (int k = 0; k < 3; k++) { const uint32_t keep = f[0][k]; f[0][k] = f[1][k]; f[1][k] = keep; }
+    }
+    const uint32_t z = lmb_row_or(t == 0u ? idx << 1 : t < 8u ? idx << (4u * t) : 0u);
+    const uint32_t w = lmb_row_or(t >= 8u ? idx << (4u * (t - 8u)) : 0u);
+    if (t == 0u) ((uint4*)a.blocks)[blk] = lmb_block(f, z, w);
+}
+
+// The other lane mapping: one lane per block, the sixteen texels in registers (binary16 bits packed two to a word, the indices four
+// bits each in one 64-bit word), every loop over the texels unrolled so that no array is indexed by a variable.  The same integers in
+// the same order of decisions as lmb_encode, so the same bytes.  This form measured 1.25 - 1.65 x faster and is the one launched;
+// MI_RT_LMB_LANE_PER_BLOCK=0 at context creation selects lmb_encode (DESIGN.md "BC6H lightmaps").
+__global__ __launch_bounds__(kBlock) void lmb_encode_block(const LmbArgs a) {
+    const size_t g = (size_t)blockIdx.x * kBlock + threadIdx.x;
+    if (g >= (size_t)a.bw * a.bh) return;
+    const uint32_t blk = (uint32_t)g, bx = blk % a.bw, by = blk / a.bw;
+    uint32_t p01[16], p2[16], mask = 0u, n = 0u, sum[3] = { 0u, 0u, 0u }, sc[3] = { 0u, 0u, 0u };
+#pragma unroll
+    for (uint32_t t = 0; t < 16; t++) {
+        const uint32_t x = bx * 4u + (t & 3u), y = by * 4u + (t >> 2);
+        const size_t q = (size_t)y * a.width + x;
+        bool part = x < a.width && y < a.height;
+        if (part && a.valid) part = a.valid[q] != 0;
+        uint32_t h[3] = { 0u, 0u, 0u };
+        if (part) {
+            const float* p = a.image + q * 3;
+#pragma unroll
+            for (int k = 0; k < 3; k++) h[k] = lmb_half_bits(p[k]);
+        }
+        p01[t] = h[0] | h[1] << 16; p2[t] = h[2];
+        mask |= (part ? 1u : 0u) << t; n += part ? 1u : 0u;
+#pragma unroll
+        for (int k = 0; k < 3; k++) { sum[k] += h[k]; sc[k] += part ? lmb_to_c(h[k]) : 0u; }
+    }
+    if (n == 0u) { ((uint4*)a.blocks)[blk] = make_uint4(3u, 0u, 0u, 0u); return; }
+    // the farthest pair: i ascending, j >= i ascending, taken only if strictly farther, so the lowest (i, j) on a tie
+    int64_t far = -1;
+    uint32_t e01[2] = { 0u, 0u }, e2[2] = { 0u, 0u };
+#pragma unroll
+    for (uint32_t i = 0; i < 16; i++)
+#pragma unroll
+        for (uint32_t j = i; j < 16; j++) {
+            const int d0 = (int)(p01[i] & 0xFFFFu) - (int)(p01[j] & 0xFFFFu), d1 = (int)(p01[i] >> 16) - (int)(p01[j] >> 16), d2 = (int)p2[i] - (int)p2[j];
+            const int64_t dist = (int64_t)((uint32_t)(d0 * d0) + (uint32_t)(d1 * d1) + (uint32_t)(d2 * d2));
+            if (((mask >> i) & (mask >> j) & 1u) != 0u && dist > far) { far = dist; e01[0] = p01[i]; e2[0] = p2[i]; e01[1] = p01[j]; e2[1] = p2[j]; }
+        }
+    uint32_t f[2][3], c0[3] = { 0u, 0u, 0u };
+#pragma unroll
+    for (int e = 0; e < 2; e++) {
+        const uint32_t c[3] = { lmb_to_c(e01[e] & 0xFFFFu), lmb_to_c(e01[e] >> 16), lmb_to_c(e2[e]) };
+#pragma unroll
+        for (int k = 0; k < 3; k++) { f[e][k] = lmb_quant(c[k]); c0[k] = e == 0 ? c[k] : c0[k]; }
+    }
+    const bool flat = f[0][0] == f[1][0] && f[0][1] == f[1][1] && f[0][2] == f[1][2];
+#pragma unroll
+    for (int k = 0; k < 3; k++) {
+        const bool wide = flat && abs((int)lmb_unq(f[0][k]) - (int)c0[k]) > 32;
+        const uint32_t below = c0[k] < 96u ? 0u : 1022u;
+        f[0][k] = wide ? below : f[0][k];
+        f[1][k] = wide ? below + 1u : f[1][k];
+    }
+    const uint32_t mean[3] = { sum[0] / n, sum[1] / n, sum[2] / n };
+    // every texel's index for the fields cf: the indices four bits each, the error over the texels that take part
+    auto assign = [&](const uint32_t (&cf)[2][3], uint64_t& idxs) -> uint64_t {
+        uint32_t ua[3], ub[3];
+#pragma unroll
+        for (int k = 0; k < 3; k++) { ua[k] = lmb_unq(cf[0][k]); ub[k] = lmb_unq(cf[1][k]); }
+        uint64_t err = 0;
+        idxs = 0;
+#pragma unroll
+        for (uint32_t t = 0; t < 16; t++) {
+            const bool part = ((mask >> t) & 1u) != 0u;
+            const uint32_t tgt[3] = { part ? p01[t] & 0xFFFFu : mean[0], part ? p01[t] >> 16 : mean[1], part ? p2[t] : mean[2] };
+            uint32_t e;
+            idxs |= (uint64_t)lmb_best(tgt, ua, ub, e) << (4u * t);
+            err += part ? e : 0u;
+        }
+        return err;
+    };
+    uint64_t idxs;
+    uint64_t err = assign(f, idxs);
+    for (uint32_t r = 0; r < a.rounds; r++) {
+        int64_t Sv = 0, Svv = 0, Svc[3] = { 0, 0, 0 };
+#pragma unroll
+        for (uint32_t t = 0; t < 16; t++) {
+            const uint32_t v = ((mask >> t) & 1u) != 0u ? lmb_weight((uint32_t)(idxs >> (4u * t)) & 15u) : 0u;
+            Sv += v; Svv += v * v;
+            Svc[0] += (int64_t)(v * lmb_to_c(p01[t] & 0xFFFFu)); Svc[1] += (int64_t)(v * lmb_to_c(p01[t] >> 16)); Svc[2] += (int64_t)(v * lmb_to_c(p2[t]));
+        }
+        const int64_t Suv = 64 * Sv - Svv, Suu = 4096 * (int64_t)n - 128 * Sv + Svv, det = Suu * Svv - Suv * Suv;
+        uint32_t cf[2][3];
+#pragma unroll
+        for (int k = 0; k < 3; k++) {
+            const int64_t Suc = 64 * (int64_t)sc[k] - Svc[k];
+            const uint32_t qa = lmb_quant(lmb_solve(64 * (Svv * Suc - Suv * Svc[k]), det != 0 ? det : 1));
+            const uint32_t qb = lmb_quant(lmb_solve(64 * (Suu * Svc[k] - Suv * Suc), det != 0 ? det : 1));
+            cf[0][k] = det != 0 ? qa : f[0][k];
+            cf[1][k] = det != 0 ? qb : f[1][k];
+        }
+        uint64_t cidxs;
+        const uint64_t cerr = assign(cf, cidxs);
+        const bool better = cerr < err;                                          // kept only if strictly lower
+#pragma unroll
+        for (int e = 0; e < 2; e++)
+#pragma unroll
+            for (int k = 0; k < 3; k++) f[e][k] = better ? cf[e][k] : f[e][k];
+        idxs = better ? cidxs : idxs;
+        err = better ? cerr : err;
+    }
+    if (((uint32_t)idxs & 15u) >= 8u) {                                          // the anchor: 15 - i is the nibble's complement
+        idxs = ~idxs;
+#pragma unroll
+        for (int k = 0; k < 3; k++) { const uint32_t keep = f[0][k]; f[0][k] = f[1][k]; f[1][k] = keep; }
+    }
+    const uint32_t lo = (uint32_t)idxs;
+    ((uint4*)a.blocks)[blk] = lmb_block(f, (lo & ~15u) | (lo & 15u) << 1, (uint32_t)(idxs >> 32));
+}
+
+__global__ __launch_bounds__(kBlock) void lmb_decode(const LmbArgs a) {
+    const size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x;
+    if (i >= (size_t)a.width * a.height) return;
+    const uint32_t x = (uint32_t)i % a.width, y = (uint32_t)i / a.width;         // (at most 2^30 texels)
+    const LmTexBc6h t(a.blocks, i, 3, (int)x, (int)y, (int)a.width);
+    float* o = a.out + 3 * i;
+#pragma unroll
+    for (int k = 0; k < 3; k++) o[k] = t[k];
+}
+
 // ---------------------------------------------------------------- launch wrappers
 // One lane per item (a texel, a probe, a point, a list entry): ceil(n / kBlock) blocks of `kernel`, which tests its index against n itself
 template <class Kernel, class... Args> static hipError_t launch_per_item(Kernel kernel, size_t n, hipStream_t stream, const Args&... args) {
@@ -4937,6 +5278,7 @@ hipError_t launch_lmp_pack(const LmpArgs& a, uint32_t format, bool unpack, hipSt
 }
 // the packed lookups: launch_lml_sample's and launch_lml_sample_lod's forms per format (RGB9E5: 3 channels only)
 hipError_t launch_lmp_sample(const LmlArgs& a, uint32_t format, uint32_t channels, hipStream_t stream) {
+    if (format == kLpBc6h && channels == 3) return launch_per_item(lmp_sample<LmTexBc6h, 3>, a.n, stream, a);
     if (format == kLpRgb9e5 && channels == 3) return launch_per_item(lmp_sample<LmTexRgb9e5, 3>, a.n, stream, a);
     if (format != kLpF16) return hipErrorInvalidValue;
     if (channels == 0) return launch_per_item(lmp_sh_sample<LmTexF16>, a.n, stream, a);
@@ -4947,11 +5289,22 @@ hipError_t launch_lmp_sample(const LmlArgs& a, uint32_t format, uint32_t channel
 hipError_t launch_lmp_sample_lod(const LmlLodArgs& a, uint32_t format, uint32_t channels, hipStream_t stream) {
     if (a.levels == 0 || a.levels > kMipMaxLevels) return hipErrorInvalidValue;
     if (format == kLpRgb9e5 && channels == 3) return launch_per_item(lmp_sample_lod<LmTexRgb9e5, 3>, a.n, stream, a);
+    if (format == kLpBc6h && channels == 3) return launch_per_item(lmp_sample_lod<LmTexBc6h, 3>, a.n, stream, a);
     if (format != kLpF16) return hipErrorInvalidValue;
     if (channels == 0) return launch_per_item(lmp_sh_sample_lod<LmTexF16>, a.n, stream, a);
     if (channels == 3) return launch_per_item(lmp_sample_lod<LmTexF16, 3>, a.n, stream, a);
     if (channels == kShFloats) return launch_per_item(lmp_sample_lod<LmTexF16, kShFloats>, a.n, stream, a);
     return hipErrorInvalidValue;
+}
+// BC6H lightmaps: one lane per texel of the padded block grid (encode) or of the image (decode)
+hipError_t launch_lmb_encode(const LmbArgs& a, bool lane_per_block, hipStream_t stream) {
+    if (a.rounds > kBc6hMaxRounds || a.bw != (a.width + 3u) / 4u || a.bh != (a.height + 3u) / 4u) return hipErrorInvalidValue;
+    if (lane_per_block) return launch_per_item(lmb_encode_block, (size_t)a.bw * a.bh, stream, a);
+    return launch_per_item(lmb_encode, (size_t)a.bw * a.bh * 16u, stream, a);
+}
+hipError_t launch_lmb_decode(const LmbArgs& a, hipStream_t stream) {
+    if (a.bw != (a.width + 3u) / 4u || a.bh != (a.height + 3u) / 4u) return hipErrorInvalidValue;
+    return launch_per_item(lmb_decode, (size_t)a.width * a.height, stream, a);
 }
 // The plain form's level.  lmf_atrous stages through LDS when `lds`; a window above 64 KB needs the opt-in, which
 // belongs to the function on the current device, so the calling context keeps its record (as launch_walker's big_lds_enabled).

@@ -472,4 +472,16 @@ bool mip_plan(uint32_t width, uint32_t height, uint32_t levels, uint32_t per_lau
     return true;
 }
 
+// The block layout of a BC6H chain, stated once: level l of W_l x H_l texels is ceil(W_l / 4) x ceil(H_l / 4) blocks of 16 bytes,
+// row-major; level 0 is a buffer of its own and levels 1 .. L - 1 lie one after the other in a second one, offsets in blocks.
+Bc6hPlan bc6h_plan(const MipPlan& mips) {
+    Bc6hPlan p{};
+    p.levels = mips.levels;
+    for (uint32_t l = 0; l < p.levels; l++) {
+        p.level[l] = { bc6h_extent(mips.level[l].width), bc6h_extent(mips.level[l].height), p.blocks };
+        if (l) p.blocks += (uint64_t)p.level[l].bw * p.level[l].bh;
+    }
+    return p;
+}
+
 }  // namespace pt

@@ -139,4 +139,13 @@ uint32_t mip_full_chain(uint32_t width, uint32_t height);
 // false: width or height is not in 1 .. 32768 or `levels` is above the full chain (plan is left alone)
 bool mip_plan(uint32_t width, uint32_t height, uint32_t levels, uint32_t per_launch, MipPlan* plan);
 
+// ---- the block layout of a BC6H chain (mi_lightmap_bc6h_*, mi_lightmap_sample_bc6h; tracing.py lightmap_bc6h_layout is the same rule)
+// Level l of a mip plan as bc6h_extent(W_l) x bc6h_extent(H_l) blocks of 16 bytes (4 x 4 texels), row-major in the level's own row order.
+// Level 0 is a buffer of its own; level[l].offset is where level l >= 1 starts, in blocks, in the buffer that holds levels 1 .. L - 1
+// one after the other (`blocks` of them).  CPU test: tests/test_lightmap_bc6h_host.py through tests/cpp/bc6h_lightmap_check.cpp.
+struct Bc6hLevel { uint32_t bw, bh; uint64_t offset; };
+struct Bc6hPlan { uint32_t levels; uint64_t blocks; Bc6hLevel level[kMipMaxLevels]; };
+inline uint32_t bc6h_extent(uint32_t n) { return (n + 3u) >> 2; }
+Bc6hPlan bc6h_plan(const MipPlan& mips);
+
 }  // namespace pt

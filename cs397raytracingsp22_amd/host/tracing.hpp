@@ -5,6 +5,7 @@
 #pragma once
 #include <algorithm>
 #include <cmath>
+#include <cstdlib>
 #include <cstring>
 #include <stdexcept>
 #include <string>
@@ -660,6 +661,101 @@ struct Scene : Intersectable {                         // tracing.rs:213-218; `i
         return packed_lookup(format, sh, valid, width, height, 0, levels, mips, mip_valid, uv, &normals, lod, nearest, device, weight);
     }
 
+    // ---- BC6H lightmaps (include/mi_rt.h "BC6H lightmaps"): the block encoder, the decoder and the lookup that reads blocks ----
+    // encode_lightmap_bc6h and decode_lightmap_bc6h are the format's definitions on the host, one level per call, in integer arithmetic
+    // alone after the binary16 conversion: the bytes equal mi_lightmap_bc6h_encode's and mi_lightmap_bc6h_decode's.  `image` is
+    // [height][width][3] f32, `valid` empty (every texel takes part) or [height][width], `rounds` 0 .. 4; the result is
+    // ceil(height / 4) x ceil(width / 4) blocks of 16 bytes, row-major.
+    struct Bc6hLevel { uint32_t bw, bh; size_t offset; };
+    // The one rule for block counts and offsets (in blocks; level 0 is a buffer of its own: offset 0)
+    static std::vector<Bc6hLevel> lightmap_bc6h_layout(uint32_t width, uint32_t height, uint32_t levels = 0) {
+        std::vector<Bc6hLevel> out;
+        size_t off = 0;
+        for (const MipLevel& m : lightmap_mip_layout(width, height, levels)) {
+            const uint32_t bw = (m.width + 3) >> 2, bh = (m.height + 3) >> 2;
+            out.push_back({ bw, bh, off });
+            if (out.size() > 1) off += (size_t)bw * bh;
+        }
+        return out;
+    }
+
+    static std::vector<uint8_t> encode_lightmap_bc6h(const std::vector<float>& image, const std::vector<uint8_t>& valid, uint32_t width,
+                                                     uint32_t height, uint32_t rounds = 2) {
+        const size_t texels = (size_t)width * height;
+        if (width == 0 || width > 32768u || height == 0 || height > 32768u || image.size() != texels * 3 || (!valid.empty() && valid.size() != texels))
+            throw std::runtime_error("mi_rt: image must be [height][width][3] with 1 .. 32768 texels a side, valid empty or [height][width]");
+        if (rounds > 4) throw std::runtime_error("mi_rt: rounds must be in 0 .. 4");
+        const uint32_t bw = (width + 3) >> 2, bh = (height + 3) >> 2;
+        std::vector<uint8_t> out((size_t)bw * bh * 16);
+        for (uint32_t by = 0; by < bh; by++)
+            for (uint32_t bx = 0; bx < bw; bx++) {
+                int64_t h[16][3] = {};
+                bool part[16] = {};
+                for (uint32_t t = 0; t < 16; t++) {
+                    const uint32_t x = 4 * bx + (t & 3), y = 4 * by + (t >> 2);
+                    if (x >= width || y >= height) continue;
+                    const size_t q = (size_t)y * width + x;
+                    if (!valid.empty() && valid[q] == 0) continue;                       // takes no part: not read
+                    part[t] = true;
+                    for (int k = 0; k < 3; k++) { const float v = image[3 * q + k]; h[t][k] = f16_bits(v > 0.0f ? std::fmin(v, 65504.0f) : 0.0f); }
+                }
+                bc6h_encode_block(h, part, rounds, &out[((size_t)by * bw + bx) * 16]);
+            }
+        return out;
+    }
+
+    // The exact decode of a level's blocks: [height][width][3] f32; a block whose low five bits are not 3 gives zeros
+    static std::vector<float> decode_lightmap_bc6h(const std::vector<uint8_t>& blocks, uint32_t width, uint32_t height) {
+        const uint32_t bw = (width + 3) >> 2, bh = (height + 3) >> 2;
+        if (width == 0 || width > 32768u || height == 0 || height > 32768u || blocks.size() != (size_t)bw * bh * 16)
+            throw std::runtime_error("mi_rt: blocks must be ceil(height / 4) x ceil(width / 4) x 16 bytes");
+        std::vector<float> out((size_t)width * height * 3);
+        for (uint32_t y = 0; y < height; y++)
+            for (uint32_t x = 0; x < width; x++) {
+                const uint8_t* b = &blocks[((size_t)(y >> 2) * bw + (x >> 2)) * 16];
+                uint64_t lo = 0, hi = 0;
+                for (int i = 0; i < 8; i++) { lo |= (uint64_t)b[i] << (8 * i); hi |= (uint64_t)b[8 + i] << (8 * i); }
+                const uint32_t t = (y & 3) * 4 + (x & 3);
+                const uint32_t i = t == 0 ? (uint32_t)(hi >> 1) & 7u : (uint32_t)(hi >> (4 * t)) & 15u;
+                for (int k = 0; k < 3; k++) {
+                    const int64_t a = bc6h_unq(bc6h_field(lo, hi, 5 + 10 * k)), e = bc6h_unq(bc6h_field(lo, hi, 35 + 10 * k));
+                    const uint32_t hb = (lo & 31u) == 3u ? (uint32_t)bc6h_interp(a, e, bc6h_weight(i)) : 0u;
+                    out[3 * ((size_t)y * width + x) + k] = bits_f32(hb >> 10 ? ((hb >> 10) + 112u) << 23 | (hb & 1023u) << 13
+                                                                             : f32_bits((float)hb * pow2(-24)));     // hb <= 0x7BFF: no sign, no infinity
+                }
+            }
+        return out;
+    }
+
+    // Read a BC6H lightmap at uv points through mi_lightmap_sample_bc6h: sample_lightmap_packed's arguments, three channels, the levels
+    // as encode_lightmap_bc6h made them (level 0 in `image`, levels 1 .. one after the other in `mips`); an empty `lod` reads level 0
+    // alone.  Returns [n][3]; equals sample_lightmap(_lod) on the decoded texels bit for bit.  Needs no scene: a static member.
+    static std::vector<float> sample_lightmap_bc6h(const std::vector<uint8_t>& image, const std::vector<uint8_t>& valid, uint32_t width,
+                                                   uint32_t height, uint32_t levels, const std::vector<uint8_t>& mips,
+                                                   const std::vector<uint8_t>& mip_valid, const std::vector<float>& uv,
+                                                   const std::vector<float>& lod, bool nearest = false, int device = 0,
+                                                   std::vector<float>* weight = nullptr) {
+        const std::vector<Bc6hLevel> layout = lightmap_bc6h_layout(width, height, levels);
+        const size_t texels = (size_t)width * height, n = uv.size() / 2, made = mip_texels(width, height, levels);
+        const size_t made_blocks = layout.back().offset + (layout.size() > 1 ? (size_t)layout.back().bw * layout.back().bh : 0);
+        if (image.size() != (size_t)layout[0].bw * layout[0].bh * 16 || (!valid.empty() && valid.size() != texels) || uv.size() != n * 2 ||
+            (!lod.empty() && lod.size() != n) || mips.size() != made_blocks * 16 || (!mip_valid.empty() && mip_valid.size() != made))
+            throw std::runtime_error("mi_rt: image and mips must hold the layout's blocks, valid empty or [H][W], mip_valid the layout's, uv [n][2], lod empty or [n]");
+        std::vector<float> out(n * 3);
+        if (weight) weight->resize(n);
+        if (n == 0) return out;
+        mi_ctx* ctx = nullptr;
+        mi_check(mi_ctx_create(device, &ctx));
+        const int rc = mi_lightmap_sample_bc6h(ctx, width, height, image.data(), valid.empty() ? nullptr : valid.data(), levels,
+                                               mips.empty() ? nullptr : mips.data(), mip_valid.empty() ? nullptr : mip_valid.data(), (uint32_t)n,
+                                               uv.data(), lod.empty() ? nullptr : lod.data(), nearest ? MI_LS_NEAREST : 0u, out.data(),
+                                               weight ? weight->data() : nullptr);
+        const std::string err = rc == MI_OK ? "" : mi_last_error();
+        mi_ctx_destroy(ctx);
+        if (rc != MI_OK) throw std::runtime_error("mi_rt: " + err);
+        return out;
+    }
+
 private:
     static uint32_t f32_bits(float x) { uint32_t u; std::memcpy(&u, &x, 4); return u; }
     static float bits_f32(uint32_t u) { float x; std::memcpy(&x, &u, 4); return x; }
@@ -717,6 +813,99 @@ private:
         mi_ctx_destroy(ctx);
         if (rc != MI_OK) throw std::runtime_error("mi_rt: " + err);
         return out;
+    }
+
+    // BC6H, the one mode: the integer pieces of the decoder and the encoder (include/mi_rt.h "BC6H lightmaps")
+    static int64_t bc6h_weight(uint32_t i) { static const int W[16] = { 0, 4, 9, 13, 17, 21, 26, 30, 34, 38, 43, 47, 51, 55, 60, 64 }; return W[i]; }
+    static int64_t bc6h_unq(int64_t q) { return q == 0 ? 0 : q == 1023 ? 0xFFFF : ((q << 16) + 0x8000) >> 10; }
+    static int64_t bc6h_interp(int64_t a, int64_t b, int64_t w) { return (((a * (64 - w) + b * w + 32) >> 6) * 31) >> 6; }
+    static int64_t bc6h_field(uint64_t lo, uint64_t hi, int bit) { return (int64_t)(((lo >> bit) | (hi << (64 - bit))) & 1023u); }
+    static int64_t bc6h_to_c(int64_t h) { return (64 * h + 30) / 31; }
+    // the field whose unquantised value is nearest to c (clamped to 0 .. 65535), the lower field on a tie
+    static int64_t bc6h_quant(int64_t c) {
+        c = std::min<int64_t>(std::max<int64_t>(c, 0), 65535);
+        const int64_t q0 = std::min<int64_t>(std::max<int64_t>((c - 1) >> 6, 0), 1023);
+        int64_t best = std::max<int64_t>(q0 - 1, 0), bd = std::llabs(bc6h_unq(best) - c);
+        for (int64_t step = 0; step < 2; step++) {
+            const int64_t q = std::min<int64_t>(q0 + step, 1023), d = std::llabs(bc6h_unq(q) - c);
+            if (d < bd) { best = q; bd = d; }
+        }
+        return best;
+    }
+    static int64_t bc6h_floor_div(int64_t a, int64_t b) { return a / b - ((a % b != 0 && (a < 0) != (b < 0)) ? 1 : 0); }
+    // every texel's index for the fields f: the least squared distance to its target, the lowest index on a tie; returns the error summed
+    // over the texels that take part
+    static int64_t bc6h_assign(const int64_t (&target)[16][3], const bool (&part)[16], const int64_t (&f)[2][3], int (&idx)[16]) {
+        int64_t err = 0;
+        for (int t = 0; t < 16; t++) {
+            int64_t be = -1;
+            for (uint32_t i = 0; i < 16; i++) {
+                int64_t e = 0;
+                for (int k = 0; k < 3; k++) { const int64_t d = target[t][k] - bc6h_interp(bc6h_unq(f[0][k]), bc6h_unq(f[1][k]), bc6h_weight(i)); e += d * d; }
+                if (be < 0 || e < be) { be = e; idx[t] = (int)i; }
+            }
+            if (part[t]) err += be;
+        }
+        return err;
+    }
+    static void bc6h_encode_block(const int64_t (&h)[16][3], const bool (&part)[16], uint32_t rounds, uint8_t* out) {
+        std::memset(out, 0, 16);
+        out[0] = 3;
+        int64_t n = 0, sum[3] = { 0, 0, 0 };
+        for (int t = 0; t < 16; t++) if (part[t]) { n++; for (int k = 0; k < 3; k++) sum[k] += h[t][k]; }
+        if (n == 0) return;
+        int fi = -1, fj = -1;
+        int64_t far = -1;
+        for (int i = 0; i < 16; i++)
+            for (int j = i; j < 16; j++) {
+                if (!part[i] || !part[j]) continue;
+                int64_t d = 0;
+                for (int k = 0; k < 3; k++) d += (h[i][k] - h[j][k]) * (h[i][k] - h[j][k]);
+                if (d > far) { far = d; fi = i; fj = j; }
+            }
+        int64_t f[2][3], target[16][3], ct[16][3];
+        for (int k = 0; k < 3; k++) { f[0][k] = bc6h_quant(bc6h_to_c(h[fi][k])); f[1][k] = bc6h_quant(bc6h_to_c(h[fj][k])); }
+        if (f[0][0] == f[1][0] && f[0][1] == f[1][1] && f[0][2] == f[1][2])             // a flat start: the two fields around c where the one is far
+            for (int k = 0; k < 3; k++) {
+                const int64_t c = bc6h_to_c(h[fi][k]);
+                if (std::llabs(bc6h_unq(f[0][k]) - c) > 32) { f[0][k] = c < 96 ? 0 : 1022; f[1][k] = f[0][k] + 1; }
+            }
+        for (int t = 0; t < 16; t++)
+            for (int k = 0; k < 3; k++) { target[t][k] = part[t] ? h[t][k] : sum[k] / n; ct[t][k] = bc6h_to_c(h[t][k]); }
+        int idx[16];
+        int64_t err = bc6h_assign(target, part, f, idx);
+        for (uint32_t r = 0; r < rounds; r++) {
+            int64_t suu = 0, suv = 0, svv = 0, suc[3] = { 0, 0, 0 }, svc[3] = { 0, 0, 0 };
+            for (int t = 0; t < 16; t++) {
+                if (!part[t]) continue;
+                const int64_t v = bc6h_weight((uint32_t)idx[t]), u = 64 - v;
+                suu += u * u; suv += u * v; svv += v * v;
+                for (int k = 0; k < 3; k++) { suc[k] += u * ct[t][k]; svc[k] += v * ct[t][k]; }
+            }
+            const int64_t det = suu * svv - suv * suv;
+            int64_t cf[2][3];
+            for (int k = 0; k < 3; k++) {
+                cf[0][k] = f[0][k]; cf[1][k] = f[1][k];
+                if (det == 0) continue;
+                cf[0][k] = bc6h_quant(bc6h_floor_div(2 * (64 * (svv * suc[k] - suv * svc[k])) + det, 2 * det));
+                cf[1][k] = bc6h_quant(bc6h_floor_div(2 * (64 * (suu * svc[k] - suv * suc[k])) + det, 2 * det));
+            }
+            int cidx[16];
+            const int64_t cerr = bc6h_assign(target, part, cf, cidx);
+            if (cerr < err) {                                                            // kept only if strictly lower
+                err = cerr;
+                std::memcpy(f, cf, sizeof f);
+                std::memcpy(idx, cidx, sizeof idx);
+            }
+        }
+        if (idx[0] >= 8) {
+            for (int k = 0; k < 3; k++) std::swap(f[0][k], f[1][k]);
+            for (int t = 0; t < 16; t++) idx[t] = 15 - idx[t];
+        }
+        uint64_t lo = 3, hi = (uint64_t)f[1][2] >> 9 | (uint64_t)idx[0] << 1;
+        for (int k = 0; k < 6; k++) lo |= (uint64_t)f[k / 3][k % 3] << (5 + 10 * k);       // (the last field's top bit falls off: it is hi's bit 0)
+        for (int t = 1; t < 16; t++) hi |= (uint64_t)idx[t] << (4 * t);
+        for (int i = 0; i < 8; i++) { out[i] = (uint8_t)(lo >> (8 * i)); out[8 + i] = (uint8_t)(hi >> (8 * i)); }
     }
 
     // the texels of levels 1 .. of a chain

@@ -1401,6 +1401,286 @@ def lightmap_sh_sample_packed(packed_chain, format, uv, normals, lod=None, valid
     return E.reshape(shape + (3,)), sw.reshape(shape)
 
 
+# ---- BC6H lightmaps: a block encoder, the decoder, lookups that read blocks (mi_lightmap_bc6h_encode, _decode, mi_lightmap_sample_bc6h) ----
+# BC6H_UF16, 3 channels, ONE block mode: the one-region mode with two 10-bit direct endpoints and 4-bit indices ("mode 11", low five bits
+# 3).  A block is 16 bytes, a little-endian 128-bit integer: bits 0-4 hold 3; six 10-bit fields rw, gw, bw (endpoint 0) and rx, gx, bx
+# (endpoint 1) at bits 5, 15, 25, 35, 45, 55; from bit 65 texel 0's 3-bit index (its top bit is implied 0), then 4 bits for each of texels
+# 1 .. 15; texel t = (y & 3) * 4 + (x & 3).  Everything below is integer arithmetic (int64), so every implementation agrees bit for bit.
+
+def _bc6h_weights():
+    """The 4-bit interpolation weights W[i] (int64 [16]); W[15 - i] = 64 - W[i]"""
+    return np.array((0, 4, 9, 13, 17, 21, 26, 30, 34, 38, 43, 47, 51, 55, 60, 64), np.int64)
+
+
+def lightmap_bc6h_layout(width: int, height: int, levels: int = 0):
+    """The block layout of a BC6H mip chain, no GPU needed (render_plan.cpp bc6h_plan is the same rule): [(BW_l, BH_l, offset_l)] for the
+    levels of lightmap_mip_layout(width, height, levels): BW_l = (W_l + 3) >> 2 and BH_l likewise blocks of 16 bytes, row-major in the
+    level's own row order.  offset_l is where level l starts, in BLOCKS, in the buffer that holds levels 1 .. L - 1 one after the other;
+    level 0 is a buffer of its own and its offset is given as 0.  Raises ValueError as lightmap_mip_layout does."""
+    out, off = [], 0
+    for l, (wl, hl, _) in enumerate(lightmap_mip_layout(width, height, levels)):
+        bw, bh = (wl + 3) >> 2, (hl + 3) >> 2
+        out.append((bw, bh, off))
+        off += bw * bh if l else 0
+    return out
+
+
+def _bc6h_unq(q):
+    """A 10-bit endpoint field unquantised to 16 bits (int64 arrays): 0 gives 0, 1023 gives 0xFFFF, every other q gives 64 q + 32"""
+    return np.where(q == 0, 0, np.where(q == 1023, 0xFFFF, ((q << 16) + 0x8000) >> 10))
+
+
+def _bc6h_palette(fields):
+    """The sixteen colours a block can hold, as binary16 bits: fields [B, 2, 3] int64 (endpoint, channel) to [B, 16, 3] int64"""
+    e = _bc6h_unq(fields)
+    w = _bc6h_weights()[None, :, None]
+    c = (e[:, 0:1, :] * (64 - w) + e[:, 1:2, :] * w + 32) >> 6
+    return (c * 31) >> 6
+
+
+def _bc6h_quant(c):
+    """The 10-bit field whose unquantised value is nearest to c (int64 arrays, clamped to 0 .. 65535 first), the lower field on a tie:
+    the three candidates around (c - 1) >> 6 in ascending order, a later one taken only if strictly nearer"""
+    c = np.clip(c, 0, 65535)
+    q0 = np.clip((c - 1) >> 6, 0, 1023)
+    best = np.maximum(q0 - 1, 0)
+    bd = np.abs(_bc6h_unq(best) - c)
+    for step in (0, 1):
+        q = np.minimum(q0 + step, 1023)
+        d = np.abs(_bc6h_unq(q) - c)
+        take = d < bd
+        best, bd = np.where(take, q, best), np.where(take, d, bd)
+    return best
+
+
+def _bc6h_assign(target, fields):
+    """Every texel's index by exhaustive search: target [B, 16, 3] binary16 bits, fields [B, 2, 3]; the index whose colour has the least
+    squared distance over the three channels, the lowest index on a tie.  Returns (index [B, 16], that distance [B, 16])."""
+    d = target[:, :, None, :] - _bc6h_palette(fields)[:, None, :, :]
+    e = (d * d).sum(axis=-1)
+    idx = e.argmin(axis=-1)                                       # (the first of equal minima)
+    return idx, np.take_along_axis(e, idx[..., None], -1)[..., 0]
+
+
+def _bc6h_blocks_of(plane, bh, bw):
+    """[4 bh, 4 bw, ...] as [bh * bw, 16, ...]: texel t = (y & 3) * 4 + (x & 3) of block (y >> 2) * bw + (x >> 2)"""
+    tail = plane.shape[2:]
+    order = (0, 2, 1, 3) + tuple(range(4, 4 + len(tail)))
+    return plane.reshape((bh, 4, bw, 4) + tail).transpose(order).reshape((bh * bw, 16) + tail)
+
+
+def _bc6h_fit(h, part, rounds):
+    """Steps 3 to 6 of lightmap_bc6h_encode for B blocks: h [B, 16, 3] int64 binary16 bits, part [B, 16] bool.  Returns (fields [B, 2, 3],
+    index [B, 16]) int64."""
+    i64 = np.int64
+    n = part.sum(axis=1)
+    # 4. the farthest pair
+    d = h[:, :, None, :] - h[:, None, :, :]
+    d2 = (d * d).sum(axis=-1)
+    i, j = np.mgrid[0:16, 0:16]
+    both = part[:, :, None] & part[:, None, :] & (i <= j)
+    key = np.where(both, d2 * 256 + (255 - (16 * i + j)), -1)
+    far = key.reshape(-1, 256).argmax(axis=1)
+    at = np.arange(len(h))
+    ends = np.stack([h[at, far // 16], h[at, far % 16]], axis=1)
+    fields = _bc6h_quant((64 * ends + 30) // 31)
+    # 4b. a flat start: a channel whose one field lies more than 32 from its c takes the two fields around c
+    c0 = (64 * ends[:, 0] + 30) // 31
+    flat = (fields[:, 0] == fields[:, 1]).all(axis=1)
+    wide = flat[:, None] & (np.abs(_bc6h_unq(fields[:, 0]) - c0) > 32)
+    below = np.where(c0 < 96, 0, 1022)
+    fields = np.where(wide[:, None, :], np.stack([below, below + 1], axis=1), fields)
+    # 3. the targets and the first indices
+    mean = (h * part[..., None]).sum(axis=1) // np.maximum(n, 1)[:, None]
+    target = np.where(part[..., None], h, mean[:, None, :])
+    idx, e = _bc6h_assign(target, fields)
+    err = (e * part).sum(axis=1)
+    # 5. least-squares refinement
+    w = _bc6h_weights()
+    ct = (64 * h + 30) // 31
+    for _ in range(rounds):
+        u, v = (64 - w[idx]) * part, w[idx] * part
+        suu, suv, svv = (u * u).sum(axis=1)[:, None], (u * v).sum(axis=1)[:, None], (v * v).sum(axis=1)[:, None]
+        suc, svc = (u[..., None] * ct).sum(axis=1), (v[..., None] * ct).sum(axis=1)
+        det = suu * svv - suv * suv
+        na, nb = 64 * (svv * suc - suv * svc), 64 * (suu * svc - suv * suc)
+        two = 2 * np.maximum(det, 1)
+        solved = _bc6h_quant(np.stack([(2 * na + det) // two, (2 * nb + det) // two], axis=1))
+        cand = np.where((det != 0)[:, :, None], solved, fields)
+        cidx, ce = _bc6h_assign(target, cand)
+        cerr = (ce * part).sum(axis=1)
+        better = cerr < err
+        fields = np.where(better[:, None, None], cand, fields)
+        idx, err = np.where(better[:, None], cidx, idx), np.where(better, cerr, err)
+    # 6. the anchor, and the blocks in which nothing takes part
+    swap = idx[:, 0] >= 8
+    fields = np.where(swap[:, None, None], fields[:, ::-1, :], fields)
+    idx = np.where(swap[:, None], 15 - idx, idx)
+    fields, idx = np.where((n == 0)[:, None, None], 0, fields), np.where((n == 0)[:, None], 0, idx)
+    return fields, idx
+
+
+def check_lightmap_bc6h_image(image, valid=None, rounds: int = 2):
+    """Input checking of mi_lightmap_bc6h_encode, no GPU needed: `image` [H, W, 3] with 1 <= W, H <= 32768, `valid` None or [H, W]
+    (0 = the texel takes no part), `rounds` 0 .. 4.  Returns (image f32, valid uint8 or None, rounds), contiguous; raises ValueError."""
+    img = np.asarray(image, np.float32)
+    if img.ndim != 3 or img.shape[2] != 3:
+        raise ValueError(f"image must be [H, W, 3], got {np.shape(image)}")
+    H, W = img.shape[:2]
+    if not (1 <= H <= 32768 and 1 <= W <= 32768):
+        raise ValueError(f"width and height must be in 1 .. 32768, got {W} x {H}")
+    if not (0 <= int(rounds) <= 4):
+        raise ValueError(f"rounds must be in 0 .. 4, got {rounds}")
+    v8 = None
+    if valid is not None:
+        v8 = np.ascontiguousarray(np.asarray(valid) != 0, np.uint8)
+        if v8.shape != (H, W):
+            raise ValueError(f"valid must be [{H}, {W}], got {v8.shape}")
+    return np.ascontiguousarray(img), v8, int(rounds)
+
+
+def lightmap_bc6h_encode(image, valid=None, rounds: int = 2):
+    """Encode an f32 lightmap as BC6H_UF16 blocks on the host (numpy only).  This is the DEFINITION of mi_lightmap_bc6h_encode, which
+    equals it byte for byte.  Arguments as check_lightmap_bc6h_image.  Returns uint8 [BH, BW, 16], BH = ceil(H / 4), BW = ceil(W / 4).
+    All integer (int64) after step 1.
+    1. Per texel and channel: c = min(x, 65504) where x > 0, else 0 (a NaN, a negative, -0.0: 0); h = the round-to-nearest-even binary16
+       bits of c, 0 .. 0x7BFF.
+    2. A texel TAKES PART when it lies inside the image and valid is None or non-zero there.  One that does not never influences a bit,
+       whatever it holds.  A block with no such texel is the word 3 and zeros.
+    3. A texel's error is the squared distance of its h to the block's exact decode, summed over channels; a block's error the sum over
+       the texels that take part.  Given endpoints every texel has the index of least error, the lowest on a tie; a texel that takes no
+       part gets the index that is best for the integer (floor) mean of the h that take part.
+    4. Start: the pair (i <= j) of texels that take part farthest apart in h, the lowest (i, j) on a tie; endpoint 0 from texel i,
+       endpoint 1 from j.  Per channel c = (64 h + 30) // 31, the smallest c with (c * 31) >> 6 == h, and the field whose unquantised
+       value is nearest to c, the lower field on a tie.
+    4b. A flat start: if the two endpoints have the same field in every channel, a channel whose field's unquantised value lies more
+       than 32 from endpoint 0's c takes the two fields around c instead, (0, 1) where c < 96 and (1022, 1023) otherwise, and the
+       indices interpolate.  The unquantised fields are 0, 96, 160, .., 64 q + 32, .., 65440, 65535: only between 0 | 96 and
+       65440 | 65535 can the nearest be more than 32 away.  With it a constant block decodes within 16 units of h.
+    5. `rounds` times: with u = 64 - W[index], v = W[index] and c as in 4 over the texels that take part, Suu, Suv, Svv, Suc, Svc the sums
+       of products and det = Suu Svv - Suv Suv.  Unless det == 0 the endpoints of a channel are a = (2 na + det) // (2 det) with
+       na = 64 (Svv Suc - Suv Svc), and b likewise with nb = 64 (Suu Svc - Suv Suc) (floor division: round half up), clamped to
+       0 .. 65535 and quantised as in 4.  Indices are assigned again and the result is kept ONLY IF the block's error is strictly lower.
+    6. If texel 0's index is 8 or more the endpoints swap and every index i becomes 15 - i (the decode is the same)."""
+    img, v8, rounds = check_lightmap_bc6h_image(image, valid, rounds)
+    i64 = np.int64
+    H, W = img.shape[:2]
+    bh, bw = (H + 3) >> 2, (W + 3) >> 2
+    with np.errstate(all="ignore"):
+        c = np.where(img > 0, np.minimum(img, np.float32(65504.0)), np.float32(0.0))
+        bits = c.astype(np.float16).view(np.uint16)
+    hp = np.zeros((4 * bh, 4 * bw, 3), i64)
+    hp[:H, :W] = bits
+    pp = np.zeros((4 * bh, 4 * bw), bool)
+    pp[:H, :W] = True if v8 is None else v8 != 0
+    h, part = _bc6h_blocks_of(hp, bh, bw), _bc6h_blocks_of(pp, bh, bw)
+    fit = [_bc6h_fit(h[k:k + 4096], part[k:k + 4096], rounds) for k in range(0, len(h), 4096)]       # (in chunks: the search is [B, 16, 16, 3])
+    fields, idx = np.concatenate([f for f, _ in fit]), np.concatenate([x for _, x in fit])
+    f, x = fields.reshape(-1, 6).astype(np.uint64), idx.astype(np.uint64)
+    lo = np.full(len(h), 3, np.uint64) | (f[:, 5] & np.uint64(511)) << np.uint64(55)
+    for k in range(5):
+        lo |= f[:, k] << np.uint64(5 + 10 * k)
+    hi = f[:, 5] >> np.uint64(9) | x[:, 0] << np.uint64(1)
+    for t in range(1, 16):
+        hi |= x[:, t] << np.uint64(4 * t)
+    return np.ascontiguousarray(np.stack([lo, hi], axis=1).astype("<u8").view(np.uint8).reshape(bh, bw, 16))
+
+
+def _check_bc6h_blocks(blocks, width, height):
+    """`blocks` as uint8 [BH, BW, 16] for a level of width x height texels (any array of BH * BW * 16 bytes); raises ValueError"""
+    W, H = int(width), int(height)
+    if not (1 <= W <= 32768 and 1 <= H <= 32768):
+        raise ValueError(f"width and height must be in 1 .. 32768, got {W} x {H}")
+    b = np.ascontiguousarray(blocks)
+    bw, bh = (W + 3) >> 2, (H + 3) >> 2
+    if b.dtype != np.uint8 or b.size != bh * bw * 16:
+        raise ValueError(f"blocks must be uint8 [{bh}, {bw}, 16] for {W} x {H} texels, got {b.dtype} {b.shape}")
+    return b.reshape(bh, bw, 16)
+
+
+def lightmap_bc6h_modes(blocks):
+    """The histogram of the low five bits of BC6H blocks (uint8 [..., 16]): int64 [32].  lightmap_bc6h_decode and the kernels read the
+    blocks counted at [3] and give zeros for all others, so a file is readable here when every block is counted there."""
+    b = np.ascontiguousarray(blocks)
+    if b.dtype != np.uint8 or b.ndim < 1 or b.shape[-1] != 16:
+        raise ValueError(f"blocks must be uint8 [..., 16], got {b.dtype} {b.shape}")
+    return np.bincount((b[..., 0] & 31).reshape(-1), minlength=32).astype(np.int64)
+
+
+def lightmap_bc6h_decode(blocks, width: int, height: int):
+    """Decode BC6H_UF16 blocks on the host (numpy only).  This is the DEFINITION of mi_lightmap_bc6h_decode: uint8 [BH, BW, 16] to f32
+    [height, width, 3].  A block whose low five bits are not 3 (every two-region, delta or reserved mode) decodes to zeros.  Otherwise,
+    with a, b the unquantised fields of a channel (0 gives 0, 1023 gives 0xFFFF, else ((q << 16) + 0x8000) >> 10) and i the texel's index:
+    c = (a (64 - W[i]) + b W[i] + 32) >> 6, h = (c * 31) >> 6, and h read as binary16 bits, widened exactly to f32 (h <= 0x7BFF)."""
+    b = _check_bc6h_blocks(blocks, width, height)
+    bh, bw = b.shape[:2]
+    words = b.reshape(-1, 16).view("<u8").astype(np.uint64)
+    lo, hi = words[:, 0], words[:, 1]
+    f = [(lo >> np.uint64(5 + 10 * k)) & np.uint64(1023) for k in range(5)] + [(lo >> np.uint64(55) | hi << np.uint64(9)) & np.uint64(1023)]
+    fields = np.stack(f, axis=1).astype(np.int64).reshape(-1, 2, 3)
+    idx = np.stack([(hi >> np.uint64(1)) & np.uint64(7)] + [(hi >> np.uint64(4 * t)) & np.uint64(15) for t in range(1, 16)], axis=1).astype(np.int64)
+    h = np.take_along_axis(_bc6h_palette(fields), idx[:, :, None], axis=1)
+    h = np.where(((lo & np.uint64(31)) == 3)[:, None, None], h, 0)
+    texels = h.reshape(bh, bw, 4, 4, 3).transpose(0, 2, 1, 3, 4).reshape(4 * bh, 4 * bw, 3)[:int(height), :int(width)]
+    return np.ascontiguousarray(texels.astype(np.uint16).view(np.float16).astype(np.float32))
+
+
+def lightmap_bc6h_chain(chain, valid_chain=None, rounds: int = 2):
+    """Encode every level of a lightmap_mips chain ([H_l, W_l, 3] f32, level 0 first) with its own mask (valid_chain None: everything takes
+    part; lightmap_mips' second list otherwise; an entry may be None).  Returns the list of uint8 [BH_l, BW_l, 16]."""
+    chain = list(chain) if isinstance(chain, (list, tuple)) else [chain]
+    masks = [None] * len(chain) if valid_chain is None else list(valid_chain)
+    if len(masks) != len(chain):
+        raise ValueError(f"valid_chain must be None or a list of {len(chain)} masks")
+    return [lightmap_bc6h_encode(a, m, rounds) for a, m in zip(chain, masks)]
+
+
+def check_lightmap_bc6h(blocks_chain, width: int, height: int, uv, lod=None, valid_chain=None, flags: int = 0):
+    """Input checking of mi_lightmap_sample_bc6h, no GPU needed.  `blocks_chain` is a list of block arrays as lightmap_bc6h_chain returns
+    them, level 0 first (sizes: lightmap_bc6h_layout(width, height, L)), or one array.  The rest is checked on the decoded levels as
+    check_lightmap_lod checks it, or with lod None as check_lightmap_lookup does (abi.MI_LS_NEAREST allowed; one level alone).  Returns
+    (blocks [L] contiguous uint8 [BH_l, BW_l, 16], what the f32 check returned for the decoded levels); raises ValueError."""
+    chain = list(blocks_chain) if isinstance(blocks_chain, (list, tuple)) else [blocks_chain]
+    if len(chain) == 0:
+        raise ValueError("blocks_chain must hold level 0")
+    layout = lightmap_mip_layout(width, height, len(chain))
+    blocks = [_check_bc6h_blocks(b, wl, hl) for b, (wl, hl, _) in zip(chain, layout)]
+    levels = [lightmap_bc6h_decode(b, wl, hl) for b, (wl, hl, _) in zip(blocks, layout)]
+    if lod is not None:
+        return blocks, check_lightmap_lod(levels, uv, lod, valid_chain, flags)
+    if len(levels) != 1:
+        raise ValueError(f"lod None reads level 0 alone: {len(levels)} levels were given")
+    if isinstance(valid_chain, (list, tuple)):
+        if len(valid_chain) != 1:
+            raise ValueError("lod None reads level 0 alone: valid_chain must be None, one mask or a list of one")
+        valid_chain = valid_chain[0]
+    return blocks, check_lightmap_lookup(levels[0], uv, valid_chain, flags)
+
+
+def lightmap_sample_bc6h(blocks_chain, width: int, height: int, uv, lod=None, valid_chain=None, flags: int = 0):
+    """Read a BC6H lightmap at uv points on the host (numpy only).  This is the DEFINITION of mi_lightmap_sample_bc6h: decode every
+    level, then lightmap_sample_lod — or, with lod None, lightmap_sample of the one level (bilinear or abi.MI_LS_NEAREST).  Arguments as
+    check_lightmap_bc6h.  Returns (out [..., 3] f32, weight [...] f32)."""
+    _, checked = check_lightmap_bc6h(blocks_chain, width, height, uv, lod, valid_chain, flags)
+    if lod is None:
+        img, T, v8, flags, _, shape = checked
+        out, sw = lightmap_sample(img, T, v8, flags)
+    else:
+        levels, masks, T, D, _, shape = checked
+        out, sw = lightmap_sample_lod(levels, T, D, masks, flags)
+    return out.reshape(shape + (3,)), sw.reshape(shape)
+
+
+class Bc6hLightmap:
+    """A plain (irradiance) lightmap stored as BC6H blocks, for Scene.shade_rays_baked and shade_hits_baked: `blocks_chain` as
+    lightmap_bc6h_chain returns it for a lightmap of width x height texels, `valid_chain` its masks or None, `lod` None (level 0 alone:
+    then the chain is one level) or the lod every hit is read at."""
+
+    def __init__(self, blocks_chain, width: int, height: int, valid_chain=None, lod=None):
+        self.blocks_chain = list(blocks_chain) if isinstance(blocks_chain, (list, tuple)) else [blocks_chain]
+        self.width, self.height, self.valid_chain, self.lod = int(width), int(height), valid_chain, lod
+
+
 def lightmap_finish_var(image, m2, samples, points, normals, levels: int = 3, normal_power_log2: int = 5,
                         sigma_plane: float = float("inf"), reach: float = float("inf"), sigma_color: float = 8.0,
                         color_floor: float = 1e-6, dilate: int = 4):
@@ -2100,6 +2380,72 @@ class Context:
         """mi_lightmap_sh_sample_packed_device: the same for packed records and points held on the device.  Queued on `stream`."""
         abi.check(self._lib.mi_lightmap_sh_sample_packed_device(self._h, format, width, height, d_sh, d_valid, levels, d_mips, d_mip_valid,
                                                                 n, d_uv, d_normals, d_lod, flags, d_irradiance, d_weight, stream))
+
+    # ---- BC6H lightmaps: the block encoder, the decoder, the lookup that reads blocks ----
+    def lightmap_bc6h_encode(self, image, valid=None, rounds: int = 2):
+        """mi_lightmap_bc6h_encode: the helper lightmap_bc6h_encode on the GPU, byte for byte: `image` [H, W, 3] f32 (one level) as uint8
+        [BH, BW, 16] blocks; `valid` None or [H, W]; `rounds` 0 .. 4.  No scene is needed."""
+        img, v8, rounds = check_lightmap_bc6h_image(image, valid, rounds)
+        H, W = img.shape[:2]
+        out = np.empty(((H + 3) >> 2, (W + 3) >> 2, 16), np.uint8)
+        abi.check(self._lib.mi_lightmap_bc6h_encode(self._h, W, H, img.ctypes.data, None if v8 is None else v8.ctypes.data, rounds, out.ctypes.data))
+        return out
+
+    def lightmap_bc6h_encode_device(self, width: int, height: int, d_image: int, d_blocks: int, rounds: int = 2, d_valid: Optional[int] = None,
+                                    stream: Optional[int] = None):
+        """mi_lightmap_bc6h_encode_device: the same for a level held on the device (raw pointers: [height, width, 3] f32 in, the 16-byte
+        aligned blocks out, which must not overlap the inputs).  Queued on `stream`, no synchronisation, no scratch."""
+        abi.check(self._lib.mi_lightmap_bc6h_encode_device(self._h, width, height, d_image, d_valid, rounds, d_blocks, stream))
+
+    def lightmap_bc6h_decode(self, blocks, width: int, height: int):
+        """mi_lightmap_bc6h_decode: the helper lightmap_bc6h_decode on the GPU, bit for bit: uint8 [BH, BW, 16] as f32 [height, width, 3]."""
+        b = _check_bc6h_blocks(blocks, width, height)
+        out = np.empty((int(height), int(width), 3), np.float32)
+        abi.check(self._lib.mi_lightmap_bc6h_decode(self._h, int(width), int(height), b.ctypes.data, out.ctypes.data))
+        return out
+
+    def lightmap_bc6h_decode_device(self, width: int, height: int, d_blocks: int, d_image: int, stream: Optional[int] = None):
+        """mi_lightmap_bc6h_decode_device: the same for blocks held on the device (raw pointers).  Queued on `stream`."""
+        abi.check(self._lib.mi_lightmap_bc6h_decode_device(self._h, width, height, d_blocks, d_image, stream))
+
+    def lightmap_bc6h_chain(self, chain, valid_chain=None, rounds: int = 2):
+        """The helper lightmap_bc6h_chain on the GPU: one mi_lightmap_bc6h_encode call per level of a lightmap_mips chain, each with its
+        own mask.  Returns the list of uint8 [BH_l, BW_l, 16]."""
+        chain = list(chain) if isinstance(chain, (list, tuple)) else [chain]
+        masks = [None] * len(chain) if valid_chain is None else list(valid_chain)
+        if len(masks) != len(chain):
+            raise ValueError(f"valid_chain must be None or a list of {len(chain)} masks")
+        return [self.lightmap_bc6h_encode(a, m, rounds) for a, m in zip(chain, masks)]
+
+    def lightmap_sample_bc6h(self, blocks_chain, width: int, height: int, uv, lod=None, valid_chain=None, flags: int = 0):
+        """mi_lightmap_sample_bc6h: the helper lightmap_sample_bc6h on the GPU, bit for bit: BC6H levels (a list as lightmap_bc6h_chain
+        returns it, or one array) of a width x height lightmap read at `uv` [..., 2], trilinearly at `lod`, or with lod None level 0 alone
+        (bilinear or abi.MI_LS_NEAREST).  Returns (out [..., 3] f32, weight [...] f32)."""
+        blocks, checked = check_lightmap_bc6h(blocks_chain, width, height, uv, lod, valid_chain, flags)
+        if lod is None:
+            _, T, v0, flags, _, shape = checked
+            L, mips, mv, D = 1, None, None, None
+        else:
+            _, masks, T, D, _, shape = checked
+            flags, L = 0, len(blocks)
+            v0 = None if masks[0] is None else np.ascontiguousarray(masks[0], np.uint8)
+            mv = None if L < 2 or masks[1] is None else _lmm_pack(masks, np.uint8)
+            mips = _lmm_pack(blocks, np.uint8, (16,))
+        out = np.empty((len(T), 3), np.float32)
+        weight = np.empty(len(T), np.float32)
+        ptr = lambda a: None if a is None else a.ctypes.data
+        abi.check(self._lib.mi_lightmap_sample_bc6h(self._h, int(width), int(height), blocks[0].ctypes.data, ptr(v0), L, ptr(mips), ptr(mv), len(T),
+                                                    T.ctypes.data, ptr(D), flags, out.ctypes.data, weight.ctypes.data))
+        return out.reshape(shape + (3,)), weight.reshape(shape)
+
+    def lightmap_sample_bc6h_device(self, width: int, height: int, d_image_blocks: int, levels: int, d_mip_blocks: Optional[int], n: int,
+                                    d_uv: int, d_lod: Optional[int], d_out: int, d_weight: Optional[int] = None, d_valid: Optional[int] = None,
+                                    d_mip_valid: Optional[int] = None, flags: int = 0, stream: Optional[int] = None):
+        """mi_lightmap_sample_bc6h_device: the same for blocks and points held on the device (raw pointers as
+        lightmap_sample_packed_device, the texels in 16-byte aligned blocks; d_lod None: level 0 alone, levels 1, d_mip_blocks None).
+        Queued on `stream`, no synchronisation, no scratch."""
+        abi.check(self._lib.mi_lightmap_sample_bc6h_device(self._h, width, height, d_image_blocks, d_valid, levels, d_mip_blocks, d_mip_valid, n,
+                                                           d_uv, d_lod, flags, d_out, d_weight, stream))
 
     def last_reduce_psh_ms(self) -> float:
         """Sum of the wf_reduce_psh launch durations (ms) of the last render: entry 7 of mi_last_pipeline_ms after render_points_sh /
@@ -2895,33 +3241,39 @@ class Scene:                         # tracing.rs:213-218
         """Baked lighting for a batch of rays: one ray query and one lightmap lookup per lit object, no path is traced.  `lightmaps` maps
         an index into Scene.objects to (sh [H, W, 9, 3], valid [H, W] or None): that object's finished directional lightmap
         (bake_lightmap(directional=True) + lightmap_finish_sh).  Returns (rgb [n, 3] f32, RayHits): shade_hits_baked of the hits of
-        intersect_rays(resolve=True), the lookups on the GPU (mi_lightmap_sh_sample)."""
+        intersect_rays(resolve=True), the lookups on the GPU (mi_lightmap_sh_sample).  An entry may also be a Bc6hLightmap: a plain
+        irradiance lightmap stored as BC6H blocks, read through mi_lightmap_sample_bc6h."""
         o, d, t_min, t_max = check_rays(origins, dirs, t_min, t_max)
         ctx = Context(device)
         try:
             ctx.upload(self.flatten())
             hits = ctx.intersect_rays(o, d, t_min, t_max, resolve=True)
-            return shade_hits_baked(hits, lightmaps, ctx.lightmap_sh_sample), hits
+            return shade_hits_baked(hits, lightmaps, ctx.lightmap_sh_sample, ctx.lightmap_sample_bc6h), hits
         finally:
             ctx.close()
 
 
-def shade_hits_baked(hits: RayHits, lightmaps, sample=lightmap_sh_sample) -> np.ndarray:
+def shade_hits_baked(hits: RayHits, lightmaps, sample=lightmap_sh_sample, sample_bc6h=lightmap_sample_bc6h) -> np.ndarray:
     """The baked-lighting colour [n, 3] f32 of resolved ray hits: a miss is 0; a hit on an object listed in `lightmaps`
     ({object index: (sh [H, W, 9, 3], valid or None)}) that has texture coordinates is
     emission + (albedo * E) * f32(1 / pi) with E = sample(sh, hit uv, hit normal, valid)[0] — the hit's shading normal, so a normal map
     shows; every other hit is its emission.  All f32, one rounding per operation.  `sample` is lightmap_sh_sample (the definition) or
-    Context.lightmap_sh_sample."""
+    Context.lightmap_sh_sample.  Where an entry of `lightmaps` is a Bc6hLightmap m instead of a pair, E is the plain irradiance
+    sample_bc6h(m.blocks_chain, m.width, m.height, hit uv, m.lod, m.valid_chain)[0] (lightmap_sample_bc6h or Context.lightmap_sample_bc6h)."""
     f32 = np.float32
     obj = np.asarray(hits.object)
     rgb = np.zeros((len(obj), 3), f32)
     hit = obj >= 0
     rgb[hit] = hits.material["emission"][hit]
-    for index, (sh, valid) in lightmaps.items():
+    for index, entry in lightmaps.items():
         at = np.nonzero((obj == int(index)) & hits.has_uv)[0]
         if len(at) == 0:
             continue
-        E, _ = sample(sh, hits.uv[at], hits.normal[at], valid)
+        if isinstance(entry, Bc6hLightmap):
+            E, _ = sample_bc6h(entry.blocks_chain, entry.width, entry.height, hits.uv[at], entry.lod, entry.valid_chain)
+        else:
+            sh, valid = entry
+            E, _ = sample(sh, hits.uv[at], hits.normal[at], valid)
         with np.errstate(all="ignore"):
             rgb[at] = hits.material["emission"][at] + (hits.material["albedo"][at] * E) * f32(0.3183098861837907)
     assert rgb.dtype == np.float32

@@ -214,6 +214,11 @@ typedef struct mi_render_opts {
 /* `format` of mi_lightmap_pack / mi_lightmap_unpack / mi_lightmap_*_packed (below); 0 is reserved for f32 and refused there */
 #define MI_LP_F16 1u                /* `channels` IEEE binary16 per texel, tightly packed (3 or 27 channels) */
 #define MI_LP_RGB9E5 2u             /* one u32 per texel: three 9-bit mantissas and a shared 5-bit exponent (3 channels only) */
+/* BC6H lightmaps (mi_lightmap_bc6h_*, mi_lightmap_sample_bc6h, below) */
+#define MI_BC6H_BLOCK_BYTES 16u     /* one block ... */
+#define MI_BC6H_BLOCK_DIM 4u        /* ... of 4 x 4 texels */
+#define MI_BC6H_MODE 3u             /* the low five bits of the one block mode written and read */
+#define MI_BC6H_MAX_ROUNDS 4u       /* mi_lightmap_bc6h_encode: the most least-squares rounds */
 
 typedef enum mi_variant {
     MI_VARIANT_DEFAULT    = 0,  /* library picks (currently MI_VARIANT_WAVEFRONT)                  */
@@ -975,7 +980,7 @@ int  mi_lightmap_sh_sample_device(mi_ctx* ctx, uint32_t width, uint32_t height, 
  *   A later launch reads the coverage of the last level the one before wrote: with out_coverage == NULL the coverage planes live in a
  *   buffer the context owns, so two such calls on one context must not be in flight at once (pass out_coverage to overlap them).  The
  *   lookups need no scratch.  Indices are 64-bit.
- * Out of scope: block-compressed formats (BC6H), deriving lod from ray footprints, anisotropic filtering, wrap modes other than clamp. */
+ * Out of scope: block-compressed mips are encoded level by level ("BC6H lightmaps" below); deriving lod from ray footprints, anisotropic filtering, wrap modes other than clamp. */
 int  mi_lightmap_mips(mi_ctx* ctx, uint32_t width, uint32_t height, uint32_t channels, const float* image, const uint8_t* valid,
                       uint32_t levels, float* out_mips, uint8_t* out_valid, float* out_coverage);
 int  mi_lightmap_mips_device(mi_ctx* ctx, uint32_t width, uint32_t height, uint32_t channels, const float* image, const uint8_t* valid,
@@ -1028,7 +1033,7 @@ int  mi_lightmap_sh_sample_lod_device(mi_ctx* ctx, uint32_t width, uint32_t heig
  *   output that overlaps an input.  n_texels == 0 / n == 0 is MI_OK and launches nothing.
  * Host forms: HOST pointers, blocking; the arrays pass through the buffer the context owns.  _device forms: DEVICE pointers on ctx's
  *   device, queued on `stream`, no synchronisation, no scratch; mi_last_kernel_ms reports the kernel.
- * Out of scope: block-compressed formats (BC6H), signed shared-exponent formats, packing `valid` or the coverage planes, packed outputs
+ * Out of scope: lossy block compression here (BC6H has calls of its own: "BC6H lightmaps" below), signed shared-exponent formats, packing `valid` or the coverage planes, packed outputs
  *   of bake, finish or mips (pack is a separate call). */
 int  mi_lightmap_pack(mi_ctx* ctx, uint32_t format, uint32_t channels, uint64_t n_texels, const float* texels, void* out_packed);
 int  mi_lightmap_pack_device(mi_ctx* ctx, uint32_t format, uint32_t channels, uint64_t n_texels, const float* texels, void* out_packed,
@@ -1049,6 +1054,72 @@ int  mi_lightmap_sh_sample_packed_device(mi_ctx* ctx, uint32_t format, uint32_t 
                                          const uint8_t* valid, uint32_t levels, const void* mips, const uint8_t* mip_valid, uint32_t n,
                                          const float* uv, const float* normals, const float* lod, uint32_t flags, float* out_irradiance,
                                          float* out_weight, void* stream);
+
+/* ---- BC6H lightmaps: a GPU encoder, a decoder and a lookup that reads blocks (added within ABI version 5: detect by symbol lookup) ----
+ * BC6H_UF16 (unsigned, 3 channels) is the format in which HDR lightmaps reach a renderer: 16 bytes per 4 x 4 texels, one byte a texel.
+ *   It is LOSSY, so it has calls of its own: the MI_LP_* calls above keep their contract ("decodes to f32 exactly") and refuse it.
+ *   lightmap_bc6h_encode, lightmap_bc6h_decode, lightmap_bc6h_layout and lightmap_sample_bc6h (Python) are the definitions.
+ * ONE block mode is written and read: the one-region mode with two 10-bit direct endpoints and 4-bit indices ("mode 11").  A block is a
+ *   little-endian 128-bit integer.  Bits 0-4 hold 3.  Six 10-bit fields follow: rw at bit 5, gw 15, bw 25 (endpoint 0), rx 35, gx 45,
+ *   bx 55 (endpoint 1).  From bit 65 texel 0 has a 3-bit index (its top bit is implied 0), texels 1 .. 15 four bits each; texel
+ *   t = (y & 3) * 4 + (x & 3).
+ * Decode, all integer: unquantise a field q: 0 gives 0, 1023 gives 0xFFFF, else ((q << 16) + 0x8000) >> 10.  With
+ *   W = {0, 4, 9, 13, 17, 21, 26, 30, 34, 38, 43, 47, 51, 55, 60, 64}: c = (a * (64 - W[i]) + b * W[i] + 32) >> 6, h = (c * 31) >> 6,
+ *   and h (at most 0x7BFF) is read as binary16 bits and widened exactly to f32.  A block whose low five bits are not 3 decodes to
+ *   sixteen zero texels: other encoders' two-region and delta modes, the other one-region widths and the reserved modes are NOT read
+ *   (lightmap_bc6h_modes counts the low five bits of a file's blocks, so a caller can tell).
+ * Layout: a level of w x h texels is ceil(w / 4) x ceil(h / 4) blocks, row-major in the image's own row order, 16-byte aligned.  A
+ *   chain is level 0 in one buffer and levels 1 .. L - 1 one after the other in a second, the image / mips split of the _lod calls;
+ *   the levels' extents are mi_lightmap_mips' (lightmap_mip_layout), the block counts and offsets lightmap_bc6h_layout's.
+ * mi_lightmap_bc6h_encode: `image` [height][width][3] f32, `valid` NULL or [height][width], `rounds` 0 .. 4; writes the level's blocks.
+ *   One level per call: the caller walks a chain with the layout rule, each level with its own mip_valid.  All integer after step 1:
+ *   1. Per texel and channel: c = min(x, 65504) where x > 0, else 0 (a NaN, a negative, -0.0); h = round-to-nearest-even binary16 bits.
+ *   2. A texel TAKES PART when it lies inside the image and valid is NULL or non-zero there.  One that does not is not read and never
+ *      influences a bit.  A block in which nothing takes part is the word 3 followed by zeros.
+ *   3. A texel's error is the squared distance of its h to the block's exact decode, summed over channels (64-bit sums); a block's
+ *      error the sum over the texels that take part.  Given endpoints every texel has the index of least error, the lowest on a tie; a
+ *      texel that takes no part gets the index best for the integer (floor) mean of the h that take part, so the gutter decodes to
+ *      something a hardware filter can touch.
+ *   4. Start: the pair (i <= j) of texels that take part farthest apart in h (squared distance), the lowest (i, j) on a tie; endpoint 0
+ *      from texel i, endpoint 1 from j.  Per channel c = (64 h + 30) / 31, the smallest c with (c * 31) >> 6 == h, and the field whose
+ *      unquantised value is nearest to c, the lower field on a tie.
+ *   4b. A flat start: if the two endpoints have the same field in every channel, a channel whose field's unquantised value lies more
+ *      than 32 from endpoint 0's c takes the two fields around c instead, (0, 1) where c < 96 and (1022, 1023) otherwise, and the
+ *      indices interpolate.  (The unquantised fields are 0, 96, 160, .., 64 q + 32, .., 65440, 65535: only at the two ends can the
+ *      nearest be more than 32 away.)  With it a constant block decodes within 16 units of h.
+ *   5. `rounds` times: with u = 64 - W[index], v = W[index] over the texels that take part and c as in 4: Suu, Suv, Svv, Suc, Svc the
+ *      sums of products, det = Suu Svv - Suv Suv.  Unless det == 0 a channel's endpoints are a = floor((2 na + det) / (2 det)) with
+ *      na = 64 (Svv Suc - Suv Svc) and b likewise with nb = 64 (Suu Svc - Suv Suc), clamped to 0 .. 65535 and quantised as in 4.
+ *      Indices are assigned again and the result is kept ONLY IF the block's error is strictly lower: the error is monotone in
+ *      `rounds`, and a block that already decodes exactly stays as it is.
+ *   6. If texel 0's index is 8 or more the endpoints swap and every index i becomes 15 - i (W[15 - i] = 64 - W[i]: the same decode).
+ *   (The kernel takes one lane per block; MI_RT_LMB_LANE_PER_BLOCK=0 at context creation selects the kernel that takes a texel per
+ *   lane and a block per 16-lane row: the same bytes, slower.)
+ * mi_lightmap_bc6h_decode: the level's blocks to [height][width][3] f32.
+ * mi_lightmap_sample_bc6h: mi_lightmap_sample_packed's rules word for word, three channels, the texels in blocks: with lod != NULL the
+ *   result is, BIT FOR BIT, mi_lightmap_sample_lod on the decoded levels; with lod == NULL mi_lightmap_sample on the decoded image:
+ *   then `levels` must be 1 and `mip_blocks`, `mip_valid` NULL, and MI_LS_NEAREST is allowed.  Tap order, a tap that takes no part is
+ *   not read (its block is not loaded), clamped indices only, 64-bit indexing, NaN behaviour and out_weight carry over.  `valid` and
+ *   `mip_valid` are per TEXEL, in mi_lightmap_mips' layout, as for the f32 calls.
+ * MI_ERR_INVALID (each with a message, checked before the context, nothing is launched): everything the f32 lookups refuse; rounds
+ *   above 4; a NULL image / blocks / out; in the _device forms blocks that are not 16-byte aligned and an output that overlaps an
+ *   input.  n == 0 is MI_OK and launches nothing.
+ * Host forms: HOST pointers, blocking; the arrays pass through the buffer the context owns.  _device forms: DEVICE pointers on ctx's
+ *   device, queued on `stream`, no synchronisation, no scratch; mi_last_kernel_ms reports the kernel.
+ * Out of scope: every other block mode, the signed format (BC6H_SF16), DDS / KTX containers, and 27-channel SH records, which are
+ *   signed and stay MI_LP_F16. */
+int  mi_lightmap_bc6h_encode(mi_ctx* ctx, uint32_t width, uint32_t height, const float* image, const uint8_t* valid, uint32_t rounds,
+                             void* out_blocks);
+int  mi_lightmap_bc6h_encode_device(mi_ctx* ctx, uint32_t width, uint32_t height, const float* image, const uint8_t* valid, uint32_t rounds,
+                                    void* out_blocks, void* stream);
+int  mi_lightmap_bc6h_decode(mi_ctx* ctx, uint32_t width, uint32_t height, const void* blocks, float* out_image);
+int  mi_lightmap_bc6h_decode_device(mi_ctx* ctx, uint32_t width, uint32_t height, const void* blocks, float* out_image, void* stream);
+int  mi_lightmap_sample_bc6h(mi_ctx* ctx, uint32_t width, uint32_t height, const void* image_blocks, const uint8_t* valid, uint32_t levels,
+                             const void* mip_blocks, const uint8_t* mip_valid, uint32_t n, const float* uv, const float* lod,
+                             uint32_t flags, float* out, float* out_weight);
+int  mi_lightmap_sample_bc6h_device(mi_ctx* ctx, uint32_t width, uint32_t height, const void* image_blocks, const uint8_t* valid,
+                                    uint32_t levels, const void* mip_blocks, const uint8_t* mip_valid, uint32_t n, const float* uv,
+                                    const float* lod, uint32_t flags, float* out, float* out_weight, void* stream);
 
 /* Size and allocate the wavefront pipeline's HBM buffers (path state, sample slots) for
  * this camera with the image shared by `world` ranks, so that the first render does not pay the

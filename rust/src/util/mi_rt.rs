@@ -55,6 +55,10 @@ pub const MI_PV_NORMAL_WEIGHT: u32 = 1;
 pub const MI_LS_NEAREST: u32 = 1;
 pub const MI_LP_F16: u32 = 1;
 pub const MI_LP_RGB9E5: u32 = 2;
+pub const MI_BC6H_BLOCK_BYTES: u32 = 16;
+pub const MI_BC6H_BLOCK_DIM: u32 = 4;
+pub const MI_BC6H_MODE: u32 = 3;
+pub const MI_BC6H_MAX_ROUNDS: u32 = 4;
 // mi_material_kind / mi_object_kind / projection and shading modes (include/mi_rt.h)
 pub const MI_MAT_LAMBERTIAN: i32 = 0; pub const MI_MAT_METAL: i32 = 1; pub const MI_MAT_DIELECTRIC: i32 = 2;
 pub const MI_MAT_PARAMETERIZED: i32 = 3; pub const MI_MAT_ISOTROPIC: i32 = 4;
@@ -275,6 +279,20 @@ extern "C" {
                                                levels: u32, mips: *const c_void, mip_valid: *const u8, n: u32, uv: *const f32,
                                                normals: *const f32, lod: *const f32, flags: u32, out_irradiance: *mut f32,
                                                out_weight: *mut f32, stream: *mut c_void) -> c_int;
+    // BC6H lightmaps: one level per encode / decode call; the lookup reads blocks (lod null = the level-0 lookup)
+    pub fn mi_lightmap_bc6h_encode(ctx: *mut mi_ctx, width: u32, height: u32, image: *const f32, valid: *const u8, rounds: u32,
+                                   out_blocks: *mut c_void) -> c_int;
+    pub fn mi_lightmap_bc6h_encode_device(ctx: *mut mi_ctx, width: u32, height: u32, image: *const f32, valid: *const u8, rounds: u32,
+                                          out_blocks: *mut c_void, stream: *mut c_void) -> c_int;
+    pub fn mi_lightmap_bc6h_decode(ctx: *mut mi_ctx, width: u32, height: u32, blocks: *const c_void, out_image: *mut f32) -> c_int;
+    pub fn mi_lightmap_bc6h_decode_device(ctx: *mut mi_ctx, width: u32, height: u32, blocks: *const c_void, out_image: *mut f32,
+                                          stream: *mut c_void) -> c_int;
+    pub fn mi_lightmap_sample_bc6h(ctx: *mut mi_ctx, width: u32, height: u32, image_blocks: *const c_void, valid: *const u8, levels: u32,
+                                   mip_blocks: *const c_void, mip_valid: *const u8, n: u32, uv: *const f32, lod: *const f32, flags: u32,
+                                   out: *mut f32, out_weight: *mut f32) -> c_int;
+    pub fn mi_lightmap_sample_bc6h_device(ctx: *mut mi_ctx, width: u32, height: u32, image_blocks: *const c_void, valid: *const u8,
+                                          levels: u32, mip_blocks: *const c_void, mip_valid: *const u8, n: u32, uv: *const f32,
+                                          lod: *const f32, flags: u32, out: *mut f32, out_weight: *mut f32, stream: *mut c_void) -> c_int;
     pub fn mi_reserve(ctx: *mut mi_ctx, cam: *const mi_camera_desc, world: i32, max_state_bytes: u64) -> c_int;
     pub fn mi_last_pipeline_ms(ctx: *mut mi_ctx, out8: *mut f32) -> c_int;
     pub fn mi_last_pipeline_counts(ctx: *mut mi_ctx, out8: *mut u64) -> c_int;

@@ -705,6 +705,208 @@ impl Scene {
         (out, weight)
     }
 
+    /// BC6H lightmaps (include/mi_rt.h "BC6H lightmaps").  `encode_lightmap_bc6h` and `decode_lightmap_bc6h` are the format's definitions on
+    /// the host, one level per call, in integer arithmetic alone after the binary16 conversion; the bytes equal mi_lightmap_bc6h_encode's
+    /// and mi_lightmap_bc6h_decode's.  `image` is [height][width][3] f32, `valid` empty (every texel takes part) or [height][width],
+    /// `rounds` 0 .. 4; the result is ceil(height / 4) x ceil(width / 4) blocks of 16 bytes, row-major.
+    pub fn encode_lightmap_bc6h(image: &[f32], valid: &[u8], width: u32, height: u32, rounds: u32) -> Vec<u8> {
+        let (w, h) = (width as usize, height as usize);
+        assert!(width >= 1 && width <= 32768 && height >= 1 && height <= 32768 && image.len() == w * h * 3 && (valid.is_empty() || valid.len() == w * h),
+                "mi_rt: image must be [height][width][3] with 1 .. 32768 texels a side, valid empty or [height][width]");
+        assert!(rounds <= mi_rt::MI_BC6H_MAX_ROUNDS, "mi_rt: rounds must be in 0 .. 4");
+        let (bw, bh) = ((w + 3) >> 2, (h + 3) >> 2);
+        let mut out = Vec::with_capacity(bw * bh * 16);
+        for by in 0..bh {
+            for bx in 0..bw {
+                let mut hb = [[0i64; 3]; 16];
+                let mut part = [false; 16];
+                for t in 0..16 {
+                    let (x, y) = (4 * bx + (t & 3), 4 * by + (t >> 2));
+                    if x >= w || y >= h { continue; }
+                    let q = y * w + x;
+                    if !valid.is_empty() && valid[q] == 0 { continue; }
+                    part[t] = true;
+                    for k in 0..3 {
+                        let v = image[3 * q + k];
+                        hb[t][k] = Self::f16_bits(if v > 0.0 { v.min(65504.0) } else { 0.0 }) as i64;
+                    }
+                }
+                out.extend_from_slice(&Self::bc6h_encode_block(&hb, &part, rounds));
+            }
+        }
+        out
+    }
+
+    /// The exact decode of a level's blocks: [height][width][3] f32; a block whose low five bits are not 3 gives zeros.
+    pub fn decode_lightmap_bc6h(blocks: &[u8], width: u32, height: u32) -> Vec<f32> {
+        let (w, h) = (width as usize, height as usize);
+        let (bw, bh) = ((w + 3) >> 2, (h + 3) >> 2);
+        assert!(width >= 1 && width <= 32768 && height >= 1 && height <= 32768 && blocks.len() == bw * bh * 16,
+                "mi_rt: blocks must be ceil(height / 4) x ceil(width / 4) x 16 bytes");
+        let pow2 = |e: i32| f32::from_bits(((e + 127) as u32) << 23);
+        let mut out = vec![0.0f32; w * h * 3];
+        for y in 0..h {
+            for x in 0..w {
+                let at = ((y >> 2) * bw + (x >> 2)) * 16;
+                let v = u128::from_le_bytes(blocks[at..at + 16].try_into().unwrap());
+                let t = (y & 3) * 4 + (x & 3);
+                let i = (if t == 0 { (v >> 65) & 7 } else { (v >> (64 + 4 * t)) & 15 }) as usize;
+                for k in 0..3 {
+                    let a = Self::bc6h_unq(((v >> (5 + 10 * k)) & 1023) as i64);
+                    let b = Self::bc6h_unq(((v >> (35 + 10 * k)) & 1023) as i64);
+                    let hb = if v & 31 == 3 { Self::bc6h_interp(a, b, Self::BC6H_W[i]) as u32 } else { 0 };
+                    out[3 * (y * w + x) + k] = if hb >> 10 != 0 { f32::from_bits(((hb >> 10) + 112) << 23 | (hb & 1023) << 13) } else { hb as f32 * pow2(-24) };
+                }
+            }
+        }
+        out
+    }
+
+    /// The one rule for block counts and offsets of a BC6H chain: (blocks per row, block rows, offset in blocks) of every level of
+    /// `lightmap_mip_layout`; level 0 is a buffer of its own (offset 0), levels 1 .. lie one after the other in a second one.
+    pub fn lightmap_bc6h_layout(width: u32, height: u32, levels: u32) -> Vec<(u32, u32, usize)> {
+        let mut off = 0usize;
+        Self::lightmap_mip_layout(width, height, levels).iter().enumerate().map(|(l, m)| {
+            let (bw, bh) = ((m.0 + 3) >> 2, (m.1 + 3) >> 2);
+            let at = off;
+            if l > 0 { off += bw as usize * bh as usize; }
+            (bw, bh, if l > 0 { at } else { 0 })
+        }).collect()
+    }
+
+    /// Read a BC6H lightmap at uv points through mi_lightmap_sample_bc6h: `sample_lightmap_packed`'s arguments, three channels, the levels
+    /// as `encode_lightmap_bc6h` made them (level 0 in `image`, levels 1 .. one after the other in `mips`); an empty `lod` reads level 0
+    /// alone.  Equals `sample_lightmap(_lod)` on the decoded texels bit for bit.
+    pub fn sample_lightmap_bc6h(image: &[u8], valid: &[u8], width: u32, height: u32, levels: u32, mips: &[u8], mip_valid: &[u8],
+                                uv: &[[f32; 2]], lod: &[f32], nearest: bool) -> (Vec<[f32; 3]>, Vec<f32>) {
+        let layout = Self::lightmap_bc6h_layout(width, height, levels);
+        let texels = width as usize * height as usize;
+        let made: usize = Self::lightmap_mip_layout(width, height, levels).iter().skip(1).map(|l| l.0 as usize * l.1 as usize).sum();
+        let made_blocks: usize = layout.iter().skip(1).map(|l| l.0 as usize * l.1 as usize).sum();
+        assert!(image.len() == layout[0].0 as usize * layout[0].1 as usize * 16 && (valid.is_empty() || valid.len() == texels), "mi_rt: image (and valid) must hold level 0");
+        assert!(mips.len() == made_blocks * 16 && (mip_valid.is_empty() || mip_valid.len() == made), "mi_rt: mips (and mip_valid) must hold levels 1 .. of the layout");
+        assert!(lod.is_empty() || lod.len() == uv.len(), "mi_rt: lod is empty or holds one value per point");
+        let mut out = vec![[0.0f32; 3]; uv.len()];
+        let mut weight = vec![0.0f32; uv.len()];
+        if uv.is_empty() { return (out, weight); }
+        let or_null = |s: &[u8]| if s.is_empty() { std::ptr::null() } else { s.as_ptr() };
+        let d = if lod.is_empty() { std::ptr::null() } else { lod.as_ptr() };
+        let flags = if nearest { mi_rt::MI_LS_NEAREST } else { 0 };
+        unsafe {
+            let mut ctx = std::ptr::null_mut();
+            assert_eq!(mi_rt::mi_ctx_create(0, &mut ctx), 0, "{}", mi_rt::last_error());
+            let rc = mi_rt::mi_lightmap_sample_bc6h(ctx, width, height, image.as_ptr() as *const std::ffi::c_void, or_null(valid), levels,
+                                                    or_null(mips) as *const std::ffi::c_void, or_null(mip_valid), uv.len() as u32,
+                                                    uv.as_ptr() as *const f32, d, flags, out.as_mut_ptr() as *mut f32, weight.as_mut_ptr());
+            let msg = mi_rt::last_error();
+            mi_rt::mi_ctx_destroy(ctx);
+            assert_eq!(rc, 0, "{}", msg);
+        }
+        (out, weight)
+    }
+
+    const BC6H_W: [i64; 16] = [0, 4, 9, 13, 17, 21, 26, 30, 34, 38, 43, 47, 51, 55, 60, 64];
+    fn bc6h_unq(q: i64) -> i64 { if q == 0 { 0 } else if q == 1023 { 0xFFFF } else { ((q << 16) + 0x8000) >> 10 } }
+    fn bc6h_interp(a: i64, b: i64, w: i64) -> i64 { (((a * (64 - w) + b * w + 32) >> 6) * 31) >> 6 }
+    fn bc6h_to_c(h: i64) -> i64 { (64 * h + 30) / 31 }
+
+    /// The field whose unquantised value is nearest to c (clamped to 0 .. 65535), the lower field on a tie.
+    fn bc6h_quant(c: i64) -> i64 {
+        let c = c.max(0).min(65535);
+        let q0 = ((c - 1) >> 6).max(0).min(1023);
+        let mut best = (q0 - 1).max(0);
+        let mut bd = (Self::bc6h_unq(best) - c).abs();
+        for step in 0..2 {
+            let q = (q0 + step).min(1023);
+            let d = (Self::bc6h_unq(q) - c).abs();
+            if d < bd { best = q; bd = d; }
+        }
+        best
+    }
+
+    /// Every texel's index for the fields f: the least squared distance to its target, the lowest index on a tie; returns the indices
+    /// and the error summed over the texels that take part.
+    fn bc6h_assign(target: &[[i64; 3]; 16], part: &[bool; 16], f: &[[i64; 3]; 2]) -> ([usize; 16], i64) {
+        let mut idx = [0usize; 16];
+        let mut err = 0i64;
+        for t in 0..16 {
+            let mut be = -1i64;
+            for i in 0..16 {
+                let mut e = 0i64;
+                for k in 0..3 {
+                    let d = target[t][k] - Self::bc6h_interp(Self::bc6h_unq(f[0][k]), Self::bc6h_unq(f[1][k]), Self::BC6H_W[i]);
+                    e += d * d;
+                }
+                if be < 0 || e < be { be = e; idx[t] = i; }
+            }
+            if part[t] { err += be; }
+        }
+        (idx, err)
+    }
+
+    fn bc6h_encode_block(h: &[[i64; 3]; 16], part: &[bool; 16], rounds: u32) -> [u8; 16] {
+        let n = part.iter().filter(|&&p| p).count() as i64;
+        if n == 0 { return 3u128.to_le_bytes(); }
+        let mut sum = [0i64; 3];
+        for t in 0..16 { if part[t] { for k in 0..3 { sum[k] += h[t][k]; } } }
+        let (mut fi, mut fj, mut far) = (0usize, 0usize, -1i64);
+        for i in 0..16 {
+            for j in i..16 {
+                if !part[i] || !part[j] { continue; }
+                let d: i64 = (0..3).map(|k| (h[i][k] - h[j][k]) * (h[i][k] - h[j][k])).sum();
+                if d > far { far = d; fi = i; fj = j; }
+            }
+        }
+        let mut f = [[0i64; 3]; 2];
+        let mut target = [[0i64; 3]; 16];
+        let mut ct = [[0i64; 3]; 16];
+        for k in 0..3 {
+            f[0][k] = Self::bc6h_quant(Self::bc6h_to_c(h[fi][k]));
+            f[1][k] = Self::bc6h_quant(Self::bc6h_to_c(h[fj][k]));
+            for t in 0..16 {
+                target[t][k] = if part[t] { h[t][k] } else { sum[k] / n };
+                ct[t][k] = Self::bc6h_to_c(h[t][k]);
+            }
+        }
+        if f[0] == f[1] {
+            for k in 0..3 {                                  // a flat start: the two fields around c where the one is far from it
+                let c = Self::bc6h_to_c(h[fi][k]);
+                if (Self::bc6h_unq(f[0][k]) - c).abs() > 32 { f[0][k] = if c < 96 { 0 } else { 1022 }; f[1][k] = f[0][k] + 1; }
+            }
+        }
+        let (mut idx, mut err) = Self::bc6h_assign(&target, part, &f);
+        for _ in 0..rounds {
+            let (mut suu, mut suv, mut svv) = (0i64, 0i64, 0i64);
+            let (mut suc, mut svc) = ([0i64; 3], [0i64; 3]);
+            for t in 0..16 {
+                if !part[t] { continue; }
+                let v = Self::BC6H_W[idx[t]];
+                let u = 64 - v;
+                suu += u * u; suv += u * v; svv += v * v;
+                for k in 0..3 { suc[k] += u * ct[t][k]; svc[k] += v * ct[t][k]; }
+            }
+            let det = suu * svv - suv * suv;
+            let mut cf = f;
+            if det != 0 {
+                for k in 0..3 {
+                    cf[0][k] = Self::bc6h_quant((2 * (64 * (svv * suc[k] - suv * svc[k])) + det).div_euclid(2 * det));
+                    cf[1][k] = Self::bc6h_quant((2 * (64 * (suu * svc[k] - suv * suc[k])) + det).div_euclid(2 * det));
+                }
+            }
+            let (cidx, cerr) = Self::bc6h_assign(&target, part, &cf);
+            if cerr < err { f = cf; idx = cidx; err = cerr; }
+        }
+        if idx[0] >= 8 {
+            f.swap(0, 1);
+            for t in 0..16 { idx[t] = 15 - idx[t]; }
+        }
+        let mut v = 3u128;
+        for k in 0..6 { v |= (f[k / 3][k % 3] as u128) << (5 + 10 * k); }
+        v |= (idx[0] as u128) << 65;
+        for t in 1..16 { v |= (idx[t] as u128) << (64 + 4 * t); }
+        v.to_le_bytes()
+    }
+
     /// flatten -> context on device 0 -> upload -> `call` -> destroy; panics with the library's message on failure.
     fn with_gpu_scene<F: FnOnce(*mut mi_rt::mi_ctx) -> i32>(&self, call: F) {
         let sb = self.flatten_scene();

@@ -118,6 +118,9 @@ from cs397raytracingsp22_amd import Context, abi, scenes  # noqa: E402
 
 # --mode packed (appended to the notes above): times mi_lightmap_pack_device / mi_lightmap_unpack_device against a device copy of the same
 # bytes, and every packed lookup against its f32 twin on coherent and shuffled uv, with and without lod (packed_rows' docstring).
+# --mode bc6h (appended to the notes above): times mi_lightmap_bc6h_encode_device (rounds 0 and 2) and mi_lightmap_bc6h_decode_device against a
+# device copy of the f32 bytes and against lmp_pack RGB9E5, the BC6H lookup against the f32 and RGB9E5 lookups of the same chain, and reports
+# the relative RMSE of BC6H, RGB9E5 and f16 on a finished cube bake (bc6h_rows' docstring).
 # --mode adaptive (appended to the notes above): times mi_bake_lightmap_adaptive (16 first samples, 2 rounds of 16, the relative target the
 # median of round 0's error over its luminance) on the cube in the one-light box and on the drone, atlas --atlas-sizes[0] squared, against
 # uniform mi_bake_lightmap_moments bakes at the adaptive run's own slots per texel and at first + max_rounds * round_samples; reports every
@@ -1541,6 +1544,185 @@ def packed_rows(ctx, sizes, point_counts, calls, warmup):
     return rows
 
 
+def bc6h_rows(ctx, sizes, point_counts, calls, warmup):
+    """--mode bc6h: BC6H lightmaps on resident tables, HIP events inside the library (mi_last_kernel_ms), `warmup` calls then `calls` timed
+    ones, medians with min - max; `spread` is (max - min) / median of a row.  Inputs per size: packed_rows' seeded random image
+    [size, size, 3] in 0 .. 4 under its chart-and-gutter mask and its full mip chain.  Rows:
+    "lmb_encode_block" (one lane per block, what ships) and "lmb_encode" (one lane per texel, MI_RT_LMB_LANE_PER_BLOCK=0, on a context of
+    its own) of level 0 at rounds 0 and 2 and "lmb_decode", alternating with "lmp_pack rgb9e5" of the same image and with "copy", a
+    device-to-device copy of the f32 bytes an encode reads (`over_copy`, `over_rgb9e5`: ratios of the medians); the blocks of the first
+    64 block rows are checked against lightmap_bc6h_encode, the decoded texels against lightmap_bc6h_decode, bit for bit.
+    Then, per point count and in lookup_rows' two orders, the BC6H lookup against its f32 twin (the f32 kernel on the texels
+    mi_lightmap_bc6h_decode_device made of the same blocks) and against the RGB9E5 lookup of the same chain, with lod (uniform in 0 .. 4)
+    and without; the BC6H and f32 outputs are compared on the device, every point, bit for bit.
+    Quality: the cube of --mode adaptive baked in the Cornell box at 64 x 64 (64 samples), finished, under its own mask: the relative
+    RMSE over valid texels of BC6H at rounds 0, 2 and 4 next to RGB9E5 and f16.  The measured figures are in DESIGN.md section 4,
+    "BC6H lightmaps"."""
+    from dataclasses import replace
+    from cs397raytracingsp22_amd import (Lambertian, Scene, StaticMesh, abi, cgmath, lightmap_bc6h_decode, lightmap_bc6h_encode, lightmap_bc6h_layout,
+                                         lightmap_mip_layout, lightmap_pack, lightmap_unpack, objload)
+    dev = torch.device("cuda:0")
+    RGB, F16 = abi.MI_LP_RGB9E5, abi.MI_LP_F16
+    rows = []
+    knob, before = "MI_RT_LMB_LANE_PER_BLOCK", os.environ.get("MI_RT_LMB_LANE_PER_BLOCK")
+    os.environ[knob] = "0"                                         # read when a context is created: the one-lane-per-texel encoder
+    try:
+        per_texel = Context(0)
+    finally:
+        if before is None:
+            del os.environ[knob]
+        else:
+            os.environ[knob] = before
+
+    def stats(ms):
+        med = float(np.median(ms))
+        return {"ms_median": round(med, 4), "ms_min": round(float(np.min(ms)), 4), "ms_max": round(float(np.max(ms)), 4),
+                "spread": round((float(np.max(ms)) - float(np.min(ms))) / med, 4)}
+
+    def emit(row):
+        rows.append(row)
+        print(json.dumps(row), flush=True)
+
+    for size in sizes:
+        layout, blocks_of = lightmap_mip_layout(size, size), lightmap_bc6h_layout(size, size)
+        L, made, texels = len(layout), sum(w * h for w, h, _ in layout[1:]), size * size
+        nb0, made_blocks = blocks_of[0][0] * blocks_of[0][1], sum(bw * bh for bw, bh, _ in blocks_of[1:])
+        gen = torch.Generator(device=dev)
+        gen.manual_seed(3)
+        yy, xx = torch.meshgrid(torch.arange(size, device=dev), torch.arange(size, device=dev), indexing="ij")
+        valid = ((xx % 64 < 60) & (yy % 64 < 60)).to(torch.uint8).contiguous()
+        del yy, xx
+        img = (torch.rand((size, size, 3), generator=gen, dtype=torch.float32, device=dev) * 4.0).contiguous()
+        mips = torch.empty((made, 3), dtype=torch.float32, device=dev)
+        mv = torch.empty(made, dtype=torch.uint8, device=dev)
+        ctx.lightmap_mips_device(size, size, 3, img.data_ptr(), L, mips.data_ptr(), mv.data_ptr(), None, valid.data_ptr())
+        b0 = torch.empty((nb0, 16), dtype=torch.uint8, device=dev)
+        b1 = torch.empty((nb0, 16), dtype=torch.uint8, device=dev)
+        bm = torch.empty((max(made_blocks, 1), 16), dtype=torch.uint8, device=dev)
+        r0, rm = torch.empty(texels, dtype=torch.int32, device=dev), torch.empty(made, dtype=torch.int32, device=dev)
+        u0, um = torch.empty_like(img), torch.empty_like(mips)
+        src, dst = torch.empty(texels * 12, dtype=torch.uint8, device=dev), torch.empty(texels * 12, dtype=torch.uint8, device=dev)
+        ms = {"lmb_encode_block rounds 0": [], "lmb_encode_block rounds 2": [], "lmb_encode rounds 0": [], "lmb_encode rounds 2": [], "lmb_decode": [],
+              "lmp_pack rgb9e5": [], "copy": []}
+        for it in range(warmup + calls):
+            t = {}
+            for rounds in (0, 2):
+                ctx.lightmap_bc6h_encode_device(size, size, img.data_ptr(), b0.data_ptr(), rounds, valid.data_ptr())
+                torch.cuda.synchronize()
+                t[f"lmb_encode_block rounds {rounds}"] = ctx.last_kernel_ms()
+                per_texel.lightmap_bc6h_encode_device(size, size, img.data_ptr(), b1.data_ptr(), rounds, valid.data_ptr())
+                torch.cuda.synchronize()
+                t[f"lmb_encode rounds {rounds}"] = per_texel.last_kernel_ms()
+            ctx.lightmap_bc6h_decode_device(size, size, b0.data_ptr(), u0.data_ptr())
+            torch.cuda.synchronize()
+            t["lmb_decode"] = ctx.last_kernel_ms()
+            ctx.lightmap_pack_device(RGB, 3, texels, img.data_ptr(), r0.data_ptr())
+            torch.cuda.synchronize()
+            t["lmp_pack rgb9e5"] = ctx.last_kernel_ms()
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            dst.copy_(src)
+            e1.record()
+            torch.cuda.synchronize()
+            t["copy"] = e0.elapsed_time(e1)
+            if it >= warmup:
+                for key, val in t.items():
+                    ms[key].append(val)
+        del src, dst
+        for l in range(1, L):                                      # the chain: one encode call per level, with its own mask
+            (w, h, off), (bw, bh, boff) = layout[l], blocks_of[l]
+            ctx.lightmap_bc6h_encode_device(w, h, mips.data_ptr() + off * 12, bm.data_ptr() + boff * 16, 2, mv.data_ptr() + off)
+            ctx.lightmap_bc6h_decode_device(w, h, bm.data_ptr() + boff * 16, um.data_ptr() + off * 12)
+        ctx.lightmap_pack_device(RGB, 3, made, mips.data_ptr(), rm.data_ptr())
+        torch.cuda.synchronize()
+        head = min(size, 256)                                      # texel rows checked on the host
+        want = lightmap_bc6h_encode(img[:head].cpu().numpy(), valid[:head].cpu().numpy(), 2)
+        got = b0[:want.shape[0] * want.shape[1]].cpu().numpy().reshape(want.shape)
+        same = bool(np.array_equal(got, want) and torch.equal(b0, b1) and np.array_equal(u0[:head].cpu().numpy().view(np.int32), lightmap_bc6h_decode(want, size, head).view(np.int32)))
+        copy, rgb = float(np.median(ms["copy"])), float(np.median(ms["lmp_pack rgb9e5"]))
+        for key in ms:
+            row = dict(mode="bc6h", size=size, query=key, calls=calls, **stats(ms[key]), mtexels_per_s=round(texels / float(np.median(ms[key])) / 1e3, 1))
+            if key.startswith("lmb"):
+                row.update(over_copy=round(float(np.median(ms[key])) / copy, 3), over_rgb9e5=round(float(np.median(ms[key])) / rgb, 3), equals_helper=same)
+            emit(row)
+        if not same:
+            raise SystemExit("ray_query_bench: the blocks differ from lightmap_bc6h_encode / lightmap_bc6h_decode")
+        for n in point_counts:
+            gw = 2 * size
+            if n > gw * gw:
+                raise SystemExit(f"ray_query_bench: {n} points exceed the {gw} x {gw} grid")
+
+            def centres(k):                  # the uv of the points number k of the gw x gw grid, row-major
+                u = ((k % gw).to(torch.float32) + 0.5) / gw
+                v = 1.0 - ((k // gw).to(torch.float32) + 0.5) / gw
+                return torch.stack([u, v], dim=1).contiguous()
+
+            k = torch.arange(n, device=dev, dtype=torch.int64)
+            anywhere = torch.randint(0, gw * gw, (n,), generator=gen, device=dev, dtype=torch.int64)
+            lod = (torch.rand(n, generator=gen, dtype=torch.float32, device=dev) * 4.0).contiguous()
+            w = torch.empty(n, dtype=torch.float32, device=dev)
+            outs = {key: torch.empty((n, 3), dtype=torch.float32, device=dev) for key in ("bc6h", "f32", "rgb9e5")}
+            for order, uv in (("coherent", centres(k)), ("shuffled", centres(anywhere))):
+                for with_lod in (True, False):
+                    d, lv = (lod.data_ptr(), L) if with_lod else (None, 1)
+                    m_b, m_u, m_r, m_v = (bm.data_ptr(), um.data_ptr(), rm.data_ptr(), mv.data_ptr()) if with_lod else (None, None, None, None)
+                    call = {
+                        "bc6h": lambda: ctx.lightmap_sample_bc6h_device(size, size, b0.data_ptr(), lv, m_b, n, uv.data_ptr(), d, outs["bc6h"].data_ptr(),
+                                                                        w.data_ptr(), valid.data_ptr(), m_v),
+                        "rgb9e5": lambda: ctx.lightmap_sample_packed_device(RGB, size, size, 3, r0.data_ptr(), lv, m_r, n, uv.data_ptr(), d,
+                                                                            outs["rgb9e5"].data_ptr(), w.data_ptr(), valid.data_ptr(), m_v),
+                        "f32": (lambda: ctx.lightmap_sample_lod_device(size, size, 3, u0.data_ptr(), L, m_u, n, uv.data_ptr(), d, outs["f32"].data_ptr(),
+                                                                       w.data_ptr(), valid.data_ptr(), m_v)) if with_lod else
+                               (lambda: ctx.lightmap_sample_device(size, size, 3, u0.data_ptr(), n, uv.data_ptr(), outs["f32"].data_ptr(), w.data_ptr(),
+                                                                   valid.data_ptr())),
+                    }
+                    took = {key: [] for key in call}
+                    torch.cuda.synchronize()
+                    for it in range(warmup + calls):
+                        for key, fn in call.items():
+                            fn()
+                            torch.cuda.synchronize()
+                            if it >= warmup:
+                                took[key].append(ctx.last_kernel_ms())
+                    same = bool(torch.equal(outs["bc6h"].view(torch.int32), outs["f32"].view(torch.int32)))
+                    f32_ms = float(np.median(took["f32"]))
+                    for key in call:
+                        row = dict(mode="bc6h", size=size, n_points=n, order=order, lod=with_lod, query=key, calls=calls, **stats(took[key]),
+                                   over_f32=round(float(np.median(took[key])) / f32_ms, 4))
+                        if key == "bc6h":
+                            row.update(equals_f32_twin=same)
+                        emit(row)
+                    if not same:
+                        raise SystemExit("ray_query_bench: a BC6H lookup differs from the f32 lookup of the decoded texels")
+            del k, anywhere, lod, w, outs
+        del img, mips, b0, bm, r0, rm, u0, um
+    # quality: the finished cube bake under its own mask
+    import gzip
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    with gzip.open(os.path.join(root, "tests", "golden", "obj", "cube.obj.gz"), "rt") as fh:
+        cube = objload.load_obj_text(fh.read())[0]
+    xf = cgmath.mul(cgmath.from_translation((0.2, 1.6, -0.3)), cgmath.from_angle_y(25.0), cgmath.from_scale(0.8))
+    box = StaticMesh(cube, Lambertian(albedo=(0.7, 0.7, 0.7)), [None] * 5, xf)
+    sc = Scene(replace(scenes.config4(64, 64, 64, 10).camera, path_depth=6), scenes.cornell_walls() + [box])
+    ctx.upload(sc.flatten())
+    mean = ctx.bake_lightmap_sh(replace(sc.camera, screen_width=64, screen_height=64, aa_sample_count=64), box, jitter=True, offset=1e-3, seed=5)[1]
+    p1, n1, _ = ctx.lightmap_texels(box, 64, 64, rows=1, offset=1e-3)
+    fin, ok = ctx.lightmap_finish(mean, p1[0], n1[0], levels=1, dilate=2)
+    keep = ok != 0
+    ref = fin.astype(np.float64)[keep]
+
+    def rel_rmse(x):
+        return float(np.sqrt(((x.astype(np.float64)[keep] - ref) ** 2).sum() / (ref ** 2).sum()))
+
+    quality = {f"bc6h rounds {r}": rel_rmse(ctx.lightmap_bc6h_decode(ctx.lightmap_bc6h_encode(fin, ok, r), 64, 64)) for r in (0, 2, 4)}
+    quality["rgb9e5"] = rel_rmse(lightmap_unpack(lightmap_pack(fin, RGB), RGB))
+    quality["f16"] = rel_rmse(lightmap_unpack(lightmap_pack(fin, F16), F16))
+    per_texel.close()
+    for key, val in quality.items():
+        emit(dict(mode="bc6h", query="quality", image="cube bake 64 x 64, finished", valid_texels=int(keep.sum()), format=key, rel_rmse=float(f"{val:.4g}")))
+    return rows
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--calls", type=int, default=20, help="timed calls per row (at least 20)")
@@ -1548,7 +1730,7 @@ def main():
     ap.add_argument("--width", type=int, default=1920)
     ap.add_argument("--height", type=int, default=1080)
     ap.add_argument("--configs", default="2,4")
-    ap.add_argument("--mode", choices=("intersect", "occlusion", "render", "hemisphere", "bake", "probes", "atlas", "finish", "volume", "variance", "adaptive", "directional", "lookup", "mips", "packed"), default="intersect",
+    ap.add_argument("--mode", choices=("intersect", "occlusion", "render", "hemisphere", "bake", "probes", "atlas", "finish", "volume", "variance", "adaptive", "directional", "lookup", "mips", "packed", "bc6h"), default="intersect",
                     help="intersect: the closest-hit rows; occlusion: the any-hit query against the visibility form; "
                          "render: ray-table rendering against mi_shade_rays_device; "
                          "hemisphere: hemisphere occlusion against the any-hit query on the identical pre-made rays; "
@@ -1566,7 +1748,8 @@ def main():
                          "and against a copy of the same bytes; "
                          "mips: the lightmap mip chain, five levels per launch against one, against a copy of the nominal bytes, and the "
                          "trilinear lookups against the level-0 lookups on the same points; "
-                         "packed: lmp_pack / lmp_unpack against a copy of the same bytes, and every packed lookup against its f32 twin")
+                         "packed: lmp_pack / lmp_unpack against a copy of the same bytes, and every packed lookup against its f32 twin; "
+                         "bc6h: the BC6H encoder and decoder against a copy and RGB9E5, the BC6H lookup against the f32 and RGB9E5 ones, quality")
     ap.add_argument("--lookup-sizes", default="1024,2048", help="--mode lookup, --mode mips and --mode packed: the square lightmap sizes")
     ap.add_argument("--volume-grids", default="16,32", help="--mode volume: probes per axis")
     ap.add_argument("--volume-points", default=f"{1 << 20},{1 << 22}", help="--mode volume, --mode directional, --mode lookup, --mode mips and --mode packed: point counts")
@@ -1605,6 +1788,9 @@ def main():
         a.configs = ""
     if a.mode == "packed":
         rows += packed_rows(ctx, [int(v) for v in a.lookup_sizes.split(",")], [int(v) for v in a.volume_points.split(",")], a.calls, a.warmup)
+        a.configs = ""
+    if a.mode == "bc6h":
+        rows += bc6h_rows(ctx, [int(v) for v in a.lookup_sizes.split(",")], [int(v) for v in a.volume_points.split(",")], a.calls, a.warmup)
         a.configs = ""
     if a.mode == "adaptive":
         rows += adaptive_rows(ctx, int(a.atlas_sizes.split(",")[0]), a.atlas_bakes)
