@@ -72,12 +72,10 @@ hipError_t launch_lma_merge(const LmaListArgs& a, hipStream_t stream);
 hipError_t launch_wf_reduce_psh(const WfArgs& a, bool first_batch, bool last_batch, hipStream_t stream);
 hipError_t launch_lsh_atrous(const LmfArgs& a, hipStream_t stream);
 hipError_t launch_lsh_eval(const LshEvalArgs& a, hipStream_t stream);
-hipError_t launch_lml_sample(const LmlArgs& a, uint32_t channels, hipStream_t stream);
+hipError_t launch_lookup(const LmlArgs& a, uint32_t format, uint32_t channels, hipStream_t stream);
+hipError_t launch_lookup(const LmlLodArgs& a, uint32_t format, uint32_t channels, hipStream_t stream);
 hipError_t launch_lmm_reduce(const LmmArgs& a, uint32_t channels, hipStream_t stream);
-hipError_t launch_lml_sample_lod(const LmlLodArgs& a, uint32_t channels, hipStream_t stream);
 hipError_t launch_lmp_pack(const LmpArgs& a, uint32_t format, bool unpack, hipStream_t stream);
-hipError_t launch_lmp_sample(const LmlArgs& a, uint32_t format, uint32_t channels, hipStream_t stream);
-hipError_t launch_lmp_sample_lod(const LmlLodArgs& a, uint32_t format, uint32_t channels, hipStream_t stream);
 hipError_t launch_lmb_encode(const LmbArgs& a, bool lane_per_block, hipStream_t stream);
 hipError_t launch_lmb_decode(const LmbArgs& a, hipStream_t stream);
 }  // namespace pt
@@ -1488,41 +1486,56 @@ extern "C" int mi_bake_lightmap_sh(mi_ctx* c, const mi_camera_desc* cam, const m
 // ------------------------------------------------------------------ lightmap post-processing: what the calls below share
 static inline size_t up256(size_t x) { return (x + 255) / 256 * 256; }
 
-// The device forms never work in place: no output may overlap an input.  A null address (an optional plane that is absent) is skipped.
-struct Span { const void* at; size_t bytes; const char* name; };       // (an input needs no name)
-static int check_no_overlap(const char* who, std::initializer_list<Span> outs, std::initializer_list<Span> ins) {
-    for (const Span& o : outs)
-        for (const Span& in : ins) {
-            const uintptr_t a = (uintptr_t)o.at, b = (uintptr_t)in.at;
-            if (a && b && a < b + in.bytes && b < a + o.bytes)
-                return fail(MI_ERR_INVALID, "%s: %s overlaps an input (the passes are never in place)", who, o.name);
-        }
-    return MI_OK;
-}
-
-// The host forms.  A column of the caller's: `bytes` at `host` (nullptr: an optional column that is absent — no space, a null device
-// pointer), uploaded before the body (kIn, kInOut), downloaded after it (kOut, kInOut) or neither (kDevice: the caller fetches what it
-// needs of it before the next staged call).  staged lays the columns out at 256-byte-aligned offsets of the context's ONE staging buffer,
-// in the order given, uploads on c->stream, calls body(dev) — dev[i] = column i's device array — downloads and synchronises.  All uploads
-// precede all downloads, so an output of the caller's may alias one of its inputs; the copies stay outside the body's timed region.
+// A call's buffers are described ONCE, as a list of columns: `bytes` at `at` (nullptr: an optional column that is absent), read by the call
+// (kIn), written by it (kOut), both (kInOut), or scratch that only the host form has to provide (kDevice).  The list serves the host form's
+// staging and the device form's overlap test alike, so a byte count cannot be right in one and wrong in the other.  name: what an overlap
+// refusal calls an output; an output without one is not tested (the finish calls' out_valid never was).
 enum class Stage { kIn, kOut, kInOut, kDevice };
-struct StageColumn { const void* host; size_t bytes; Stage dir; };
+struct StageColumn { const void* at; size_t bytes; Stage dir; const char* name = nullptr; };
+
+// The host forms.  staged lays the columns present out at 256-byte-aligned offsets of the context's ONE staging buffer, in the order given
+// (an absent column takes no space and gets a null device pointer), uploads kIn / kInOut on c->stream, calls body(dev) — dev[i] = column
+// i's device array — downloads kOut / kInOut and synchronises; of a kDevice column the caller fetches what it needs before the next staged
+// call.  All uploads precede all downloads, so an output of the caller's may alias one of its inputs; the copies stay outside the body's
+// timed region.
 template <size_t N, class Body> static int staged(mi_ctx* c, const StageColumn (&cols)[N], Body body) {
     HIP_TRY(hipSetDevice(c->device));
     size_t off[N + 1] = { 0 };
-    for (size_t i = 0; i < N; i++) off[i + 1] = off[i] + (cols[i].host ? up256(cols[i].bytes) : 0);
+    for (size_t i = 0; i < N; i++) off[i + 1] = off[i] + (cols[i].at ? up256(cols[i].bytes) : 0);
     MI_TRY(ensure(&c->d_io, &c->io_bytes, off[N]));
     void* dev[N];
-    for (size_t i = 0; i < N; i++) dev[i] = cols[i].host ? (char*)c->d_io + off[i] : nullptr;
+    for (size_t i = 0; i < N; i++) dev[i] = cols[i].at ? (char*)c->d_io + off[i] : nullptr;
     for (size_t i = 0; i < N; i++) if (dev[i] && (cols[i].dir == Stage::kIn || cols[i].dir == Stage::kInOut))
-        HIP_TRY(hipMemcpyAsync(dev[i], cols[i].host, cols[i].bytes, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipMemcpyAsync(dev[i], cols[i].at, cols[i].bytes, hipMemcpyHostToDevice, c->stream));
     MI_TRY(body(dev));
     for (size_t i = 0; i < N; i++) if (dev[i] && (cols[i].dir == Stage::kOut || cols[i].dir == Stage::kInOut))
-        HIP_TRY(hipMemcpyAsync((void*)cols[i].host, dev[i], cols[i].bytes, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipMemcpyAsync((void*)cols[i].at, dev[i], cols[i].bytes, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return MI_OK;
 }
 
+// Both forms of a call whose arguments are checked.  host: the columns are HOST arrays: body(dev, c->stream) runs staged, the call blocks.
+// Else they are DEVICE arrays and never work in place: a named output that overlaps an input is refused (a null address is skipped), then
+// body(the caller's own pointers — null for a kDevice column —, stream) queues the work.  Between the two sit the only things the families
+// place differently: a NULL context is refused here, AFTER the overlap test (a family that refuses it before tests it before it calls),
+// and `empty` — a call with nothing to launch — returns MI_OK here: after the overlap test, before any device call.
+template <size_t N, class Body>
+static int run_columns(const char* who, mi_ctx* c, bool host, void* stream, const StageColumn (&cols)[N], bool empty, Body body) {
+    if (!host)
+        for (const StageColumn& o : cols) if (o.name && (o.dir == Stage::kOut || o.dir == Stage::kInOut))
+            for (const StageColumn& in : cols) if (in.dir == Stage::kIn) {
+                const uintptr_t a = (uintptr_t)o.at, b = (uintptr_t)in.at;
+                if (a && b && a < b + in.bytes && b < a + o.bytes)
+                    return fail(MI_ERR_INVALID, "%s: %s overlaps an input (the passes are never in place)", who, o.name);
+            }
+    if (!c) return fail(MI_ERR_INVALID, "ctx is NULL");
+    if (empty) return MI_OK;
+    if (host) return staged(c, cols, [&](void* const* dev) -> int { return body(dev, c->stream); });
+    HIP_TRY(hipSetDevice(c->device));
+    void* at[N];
+    for (size_t i = 0; i < N; i++) at[i] = cols[i].dir == Stage::kDevice ? nullptr : (void*)cols[i].at;
+    return body(at, (hipStream_t)stream);
+}
 // ------------------------------------------------------------------ lightmap finishing (edge-aware a-trous filter, gutter dilation)
 // tracing.py lightmap_finish, lightmap_finish_sh and lightmap_finish_var as kernels, one pass per launch, in three forms:
 //   plain     [H][W][3] texels; scratch d_lmf; lmf_mask, lmf_atrous per level, lmf_dilate per pass
@@ -1624,50 +1637,41 @@ static int finish_device(mi_ctx* c, FinishForm form, const FinishArgs& f, const 
     });
 }
 
-// The device-pointer entry of every form.  The refusals in order: the arguments, then — the plain and the SH form — a NULL context and an
-// overlap, or — the variance forms — an overlap and a NULL context.
-static int finish_entry_device(const char* who, FinishForm form, mi_ctx* c, const FinishArgs& f, const FinishVarArgs* fv, void* stream) {
+// The entry of every form (host: see run_columns; out may alias image there: see staged).  The refusals in order: the arguments, then a
+// NULL context — but the variance forms' device calls refuse an overlap first, and a NULL context after it.
+static int finish_entry(const char* who, FinishForm form, mi_ctx* c, const FinishArgs& f, const FinishVarArgs* fv, bool host, void* stream) {
     MI_TRY(fv ? check_lmv_args(who, f, *fv) : check_lmf_args(who, f));
     if (!fv && !c) return fail(MI_ERR_INVALID, "ctx is NULL");
-    const size_t n = (size_t)f.width * f.height, tab = n * 3 * sizeof(float), rec = form == FinishForm::kSh ? n * kShFloats * sizeof(float) : tab;
-    MI_TRY(check_no_overlap(who, { { f.out, rec, form == FinishForm::kSh ? "out_sh" : "out_image" }, { fv ? fv->out_var : nullptr, n * 4, "out_var" } },
-                            { { f.image, rec }, { fv ? fv->m2 : nullptr, tab }, { f.points, tab }, { f.normals, tab }, { fv ? fv->counts : nullptr, n * 4 } }));
-    if (!c) return fail(MI_ERR_INVALID, "ctx is NULL");
-    HIP_TRY(hipSetDevice(c->device));
-    return finish_device(c, form, f, fv, (hipStream_t)stream);
-}
-
-// The host-pointer entry of every form: the arguments, then the context, then the call staged (out may alias image: see staged).
-static int finish_entry_host(const char* who, FinishForm form, mi_ctx* c, const FinishArgs& f, const FinishVarArgs* fv) {
-    MI_TRY(fv ? check_lmv_args(who, f, *fv) : check_lmf_args(who, f));
-    if (!c) return fail(MI_ERR_INVALID, "ctx is NULL");
-    const size_t n = (size_t)f.width * f.height, tab = n * 3 * sizeof(float), rec = form == FinishForm::kSh ? n * kShFloats * sizeof(float) : tab;
+    const bool sh = form == FinishForm::kSh;
+    const size_t n = (size_t)f.width * f.height, tab = n * 3 * sizeof(float), rec = sh ? n * kShFloats * sizeof(float) : tab;
     enum { kImage, kM2, kPoints, kNormals, kCounts, kOut, kOutVar, kOutValid };
     const StageColumn cols[] = { { f.image, rec, Stage::kIn }, { fv ? fv->m2 : nullptr, tab, Stage::kIn }, { f.points, tab, Stage::kIn },
-                                 { f.normals, tab, Stage::kIn }, { fv ? fv->counts : nullptr, n * 4, Stage::kIn }, { f.out, rec, Stage::kOut },
-                                 { fv ? fv->out_var : nullptr, n * 4, Stage::kOut }, { f.out_valid, n, Stage::kOut } };
-    return staged(c, cols, [&](void* const* d) -> int {
+                                 { f.normals, tab, Stage::kIn }, { fv ? fv->counts : nullptr, n * 4, Stage::kIn },
+                                 { f.out, rec, Stage::kOut, sh ? "out_sh" : "out_image" },
+                                 { fv ? fv->out_var : nullptr, n * 4, Stage::kOut, "out_var" },
+                                 { f.out_valid, n, Stage::kOut } };          // (no name: the device forms have never tested out_valid)
+    return run_columns(who, c, host, stream, cols, false, [&](void* const* d, hipStream_t s) -> int {
         FinishArgs df = f;
         df.image = (const float*)d[kImage]; df.points = (const float*)d[kPoints]; df.normals = (const float*)d[kNormals];
         df.out = (float*)d[kOut]; df.out_valid = (uint8_t*)d[kOutValid];
         FinishVarArgs dv{};
         if (fv) { dv = *fv; dv.m2 = (const float*)d[kM2]; dv.counts = (const uint32_t*)d[kCounts]; dv.out_var = (float*)d[kOutVar]; }
-        return finish_device(c, form, df, fv ? &dv : nullptr, c->stream);
+        return finish_device(c, form, df, fv ? &dv : nullptr, s);
     });
 }
 
 extern "C" int mi_lightmap_finish_device(mi_ctx* c, uint32_t width, uint32_t height, const float* image, const float* points,
                                          const float* normals, uint32_t levels, uint32_t normal_power_log2, float sigma_plane, float reach,
                                          float sigma_color, uint32_t dilate, float* out_image, uint8_t* out_valid, void* stream) {
-    return finish_entry_device("mi_lightmap_finish_device", FinishForm::kPlain, c, { width, height, image, points, normals, levels,
-                               normal_power_log2, sigma_plane, reach, sigma_color, dilate, out_image, out_valid }, nullptr, stream);
+    return finish_entry("mi_lightmap_finish_device", FinishForm::kPlain, c, { width, height, image, points, normals, levels,
+                        normal_power_log2, sigma_plane, reach, sigma_color, dilate, out_image, out_valid }, nullptr, false, stream);
 }
 
 extern "C" int mi_lightmap_finish(mi_ctx* c, uint32_t width, uint32_t height, const float* image, const float* points, const float* normals,
                                   uint32_t levels, uint32_t normal_power_log2, float sigma_plane, float reach, float sigma_color,
                                   uint32_t dilate, float* out_image, uint8_t* out_valid) {
-    return finish_entry_host("mi_lightmap_finish", FinishForm::kPlain, c, { width, height, image, points, normals, levels, normal_power_log2,
-                             sigma_plane, reach, sigma_color, dilate, out_image, out_valid }, nullptr);
+    return finish_entry("mi_lightmap_finish", FinishForm::kPlain, c, { width, height, image, points, normals, levels, normal_power_log2,
+                        sigma_plane, reach, sigma_color, dilate, out_image, out_valid }, nullptr, true, nullptr);
 }
 
 // ------------------------------------------------------------------ directional lightmaps: the finish and the evaluation
@@ -1675,15 +1679,15 @@ extern "C" int mi_lightmap_finish(mi_ctx* c, uint32_t width, uint32_t height, co
 extern "C" int mi_lightmap_finish_sh_device(mi_ctx* c, uint32_t width, uint32_t height, const float* sh, const float* points,
                                             const float* normals, uint32_t levels, uint32_t normal_power_log2, float sigma_plane, float reach,
                                             float sigma_color, uint32_t dilate, float* out_sh, uint8_t* out_valid, void* stream) {
-    return finish_entry_device("mi_lightmap_finish_sh_device", FinishForm::kSh, c, { width, height, sh, points, normals, levels,
-                               normal_power_log2, sigma_plane, reach, sigma_color, dilate, out_sh, out_valid }, nullptr, stream);
+    return finish_entry("mi_lightmap_finish_sh_device", FinishForm::kSh, c, { width, height, sh, points, normals, levels,
+                        normal_power_log2, sigma_plane, reach, sigma_color, dilate, out_sh, out_valid }, nullptr, false, stream);
 }
 
 extern "C" int mi_lightmap_finish_sh(mi_ctx* c, uint32_t width, uint32_t height, const float* sh, const float* points, const float* normals,
                                      uint32_t levels, uint32_t normal_power_log2, float sigma_plane, float reach, float sigma_color,
                                      uint32_t dilate, float* out_sh, uint8_t* out_valid) {
-    return finish_entry_host("mi_lightmap_finish_sh", FinishForm::kSh, c, { width, height, sh, points, normals, levels, normal_power_log2,
-                             sigma_plane, reach, sigma_color, dilate, out_sh, out_valid }, nullptr);
+    return finish_entry("mi_lightmap_finish_sh", FinishForm::kSh, c, { width, height, sh, points, normals, levels, normal_power_log2,
+                        sigma_plane, reach, sigma_color, dilate, out_sh, out_valid }, nullptr, true, nullptr);
 }
 
 // tracing.py lightmap_sh_eval as one kernel (lsh_eval): one lane per point.  Checked before the context; n == 0 launches nothing.
@@ -1720,13 +1724,19 @@ extern "C" int mi_lightmap_sh_eval(mi_ctx* c, uint32_t n, const float* sh, const
 }
 
 // ------------------------------------------------------------------ lightmap lookup (a finished lightmap read at uv points)
-// tracing.py lightmap_sample and lightmap_sh_sample as one kernel each (lml_sample<3>, lml_sample<27>, lml_sh_sample): one lane per point,
-// no scratch, no scene.  One argument record serves both calls: channels == 0 is the fused SH form, which reads 27 floats per texel and
-// the normals and writes three per point.  format: 0 = f32 texels, else MI_LP_* (the packed lookups further down enter here) or kLpBc6h
-// (the BC6H lookup, further down still).
+// tracing.py lightmap_sample / lightmap_sh_sample (level 0 alone) and lightmap_sample_lod / lightmap_sh_sample_lod (trilinear over the
+// chain of render_plan.cpp mip_plan) as one kernel per form, format and channel count: one lane per point, no scratch, no scene.  ONE
+// argument record, checker, device body and entry serve all eighteen calls — f32, packed and BC6H texels, both level forms:
+//   format    0 = f32 texels, MI_LP_* (the packed calls further down) or kLpBc6h (the BC6H call, further down still)
+//   channels  3 or 27, or 0: the fused SH form, which reads 27 values per texel and the normals and writes three per point
+//   admits    which level forms the entry point has: mi_lightmap_sample / _sh_sample level 0 alone (levels 1, no mips, no lod), the
+//             _lod calls the chain alone (a NULL lod is a missing argument there), the packed and BC6H calls either: lod == NULL reads
+//             level 0 alone, which then wants levels == 1 and no mips, and allows MI_LS_NEAREST, which the chain form refuses.
+enum class Levels { kZero, kChain, kEither };
 struct LookupArgs {
-    uint32_t width, height, channels; const void* image; const uint8_t* valid; uint32_t n; const float* uv; const float* normals;
-    uint32_t flags; float* out; float* out_weight; uint32_t format = 0;
+    uint32_t format, channels; Levels admits;
+    uint32_t width, height; const void* image; const uint8_t* valid; uint32_t levels; const void* mips; const uint8_t* mip_valid;
+    uint32_t n; const float* uv; const float* normals; const float* lod; uint32_t flags; float* out; float* out_weight;
 };
 // The bytes of one stored texel of `channels` values
 static inline size_t texel_bytes(uint32_t format, size_t channels) {
@@ -1741,87 +1751,118 @@ static inline size_t mips_bytes(uint32_t format, const MipPlan& plan, size_t cha
     return format == kLpBc6h ? (size_t)bc6h_plan(plan).blocks * 16u : (size_t)plan.texels * texel_bytes(format, channels);
 }
 
-// Checked before the context, nothing is launched: the pointers, the size, the channel count, the flags
-static int check_lookup_args(const char* who, const LookupArgs& l) {
+// What every packed call checks of its format, before anything else (sh: the fused form, which reads signed coefficients)
+static int check_packed_format(const char* who, uint32_t format, uint32_t channels, bool sh) {
+    if (format != MI_LP_F16 && format != MI_LP_RGB9E5)
+        return fail(MI_ERR_INVALID, "%s: format %u is not MI_LP_F16 or MI_LP_RGB9E5 (f32 texels take the unpacked calls)", who, format);
+    if (sh && format != MI_LP_F16) return fail(MI_ERR_INVALID, "%s: SH coefficients are signed: only MI_LP_F16 holds them", who);
+    if (!sh && channels != 3 && channels != (uint32_t)kShFloats) return fail(MI_ERR_INVALID, "%s: channels %u is not 3 or 27", who, channels);
+    if (format == MI_LP_RGB9E5 && channels != 3)
+        return fail(MI_ERR_INVALID, "%s: MI_LP_RGB9E5 holds 3 unsigned channels, not %u (SH records pack as MI_LP_F16)", who, channels);
+    return MI_OK;
+}
+
+// Checked before the context, nothing is launched: the alignment of blocks (device pointers only: the host form stages them aligned),
+// the level form, the pointers, the size, the channel count, the levels, the flags.  chain: the form the call takes; plan: its levels
+// (one for the level-0 form, whose levels is 1).
+static int check_lookup_args(const char* who, const LookupArgs& l, bool host, bool chain, MipPlan* plan) {
     const bool sh = l.channels == 0;
-    if (!l.image || !l.uv || !l.out || (sh && !l.normals))
-        return fail(MI_ERR_INVALID, sh ? "%s: sh, uv, normals and out_irradiance are required" : "%s: image, uv and out are required", who);
+    if (l.format == kLpBc6h && !host && (((uintptr_t)l.image | (uintptr_t)l.mips) & 15u))
+        return fail(MI_ERR_INVALID, "%s: the blocks are not 16-byte aligned", who);
+    if (!chain && l.admits == Levels::kEither && (l.levels != 1 || l.mips || l.mip_valid))
+        return fail(MI_ERR_INVALID, "%s: lod == NULL reads level 0 alone: levels must be 1 (not %u) and mips, mip_valid NULL", who, l.levels);
+    if (!l.image || !l.uv || !l.out || (sh && !l.normals) || (chain && !l.lod))
+        return fail(MI_ERR_INVALID, chain ? (sh ? "%s: sh, uv, normals, lod and out_irradiance are required" : "%s: image, uv, lod and out are required")
+                                          : (sh ? "%s: sh, uv, normals and out_irradiance are required" : "%s: image, uv and out are required"), who);
     if (l.width == 0 || l.width > 32768u || l.height == 0 || l.height > 32768u)
         return fail(MI_ERR_INVALID, "%s: width %u / height %u is not in 1 .. 32768", who, l.width, l.height);
     if (!sh && l.channels != 3 && l.channels != (uint32_t)kShFloats) return fail(MI_ERR_INVALID, "%s: channels %u is not 3 or 27", who, l.channels);
+    if (!mip_plan(l.width, l.height, l.levels, kMipFuse, plan))
+        return fail(MI_ERR_INVALID, "%s: levels %u is above the full chain of %u x %u, %u", who, l.levels, l.width, l.height,
+                    mip_full_chain(l.width, l.height));
+    if (plan->levels > 1 && !l.mips) return fail(MI_ERR_INVALID, "%s: mips is required with %u levels", who, plan->levels);
+    if (chain && (l.flags & MI_LS_NEAREST)) return fail(MI_ERR_INVALID, "%s: MI_LS_NEAREST is refused: nearest addressing has no mips", who);
     if (l.flags & ~MI_LS_NEAREST) return fail(MI_ERR_INVALID, "%s: unknown flag bits 0x%x", who, l.flags & ~MI_LS_NEAREST);
     return MI_OK;
 }
 
-static int lookup_device(mi_ctx* c, const LookupArgs& l, hipStream_t stream) {
+// Queue the lookup on `stream`: every pointer is a device pointer
+static int lookup_device(mi_ctx* c, const LookupArgs& l, bool chain, const MipPlan& plan, hipStream_t stream) {
     LmlArgs a{};
     a.image = l.image; a.valid = l.valid; a.uv = l.uv; a.normals = l.normals; a.out = l.out; a.out_weight = l.out_weight;
     a.width = l.width; a.height = l.height; a.n = l.n; a.nearest = l.flags & MI_LS_NEAREST;
+    LmlLodArgs b{};
+    if (chain) {
+        b.image = l.image; b.valid = l.valid; b.mips = l.mips; b.mip_valid = l.mip_valid; b.uv = l.uv; b.lod = l.lod; b.normals = l.normals;
+        b.out = l.out; b.out_weight = l.out_weight; b.levels = plan.levels; b.n = l.n;
+        for (uint32_t k = 0; k < plan.levels; k++) { b.off[k] = plan.level[k].offset; b.lw[k] = plan.level[k].width; b.lh[k] = plan.level[k].height; }
+        if (l.format == kLpBc6h) {
+            const Bc6hPlan blocks = bc6h_plan(plan);
+            for (uint32_t k = 0; k < plan.levels; k++) b.boff[k] = (uint32_t)blocks.level[k].offset;
+        }
+    }
     return timed(c, stream, [&]() -> int {
-        HIP_TRY(l.format ? launch_lmp_sample(a, l.format, l.channels, stream) : launch_lml_sample(a, l.channels, stream));
+        HIP_TRY(chain ? launch_lookup(b, l.format, l.channels, stream) : launch_lookup(a, l.format, l.channels, stream));
         return MI_OK;
     });
 }
 
-// The device-pointer entry: the arguments, the context, the overlaps (the kernels never work in place); n == 0 launches nothing
-static int lookup_entry_device(const char* who, mi_ctx* c, const LookupArgs& l, void* stream) {
-    MI_TRY(check_lookup_args(who, l));
+// The entry of every lookup (host: see run_columns): the arguments, the context, the overlaps; n == 0 launches nothing.  A level-0 call
+// has no mips, mip_valid and lod columns, and the host form stages none for a chain of one level.
+static int lookup_entry(const char* who, mi_ctx* c, const LookupArgs& l, bool host, void* stream) {
+    const bool chain = l.admits == Levels::kChain || (l.admits == Levels::kEither && l.lod);
+    MipPlan plan;
+    MI_TRY(check_lookup_args(who, l, host, chain, &plan));
     if (!c) return fail(MI_ERR_INVALID, "ctx is NULL");
     const size_t texels = (size_t)l.width * l.height, in_c = l.channels ? l.channels : (uint32_t)kShFloats, out_c = l.channels ? l.channels : 3u;
-    MI_TRY(check_no_overlap(who, { { l.out, (size_t)l.n * out_c * sizeof(float), l.channels ? "out" : "out_irradiance" },
-                                   { l.out_weight, (size_t)l.n * sizeof(float), "out_weight" } },
-                            { { l.image, level_bytes(l.format, l.width, l.height, in_c) }, { l.valid, texels }, { l.uv, (size_t)l.n * 2 * sizeof(float) },
-                              { l.normals, (size_t)l.n * 3 * sizeof(float) } }));
-    if (l.n == 0) return MI_OK;
-    HIP_TRY(hipSetDevice(c->device));
-    return lookup_device(c, l, (hipStream_t)stream);
-}
-
-// The host-pointer entry: the arguments, then the context, then the call staged
-static int lookup_entry_host(const char* who, mi_ctx* c, const LookupArgs& l) {
-    MI_TRY(check_lookup_args(who, l));
-    if (!c) return fail(MI_ERR_INVALID, "ctx is NULL");
-    if (l.n == 0) return MI_OK;                // before any device call
-    const size_t texels = (size_t)l.width * l.height, in_c = l.channels ? l.channels : (uint32_t)kShFloats, out_c = l.channels ? l.channels : 3u;
-    enum { kImage, kValid, kUv, kNormals, kOut, kWeight };
+    const bool no_mips = host && plan.levels == 1;
+    enum { kImage, kValid, kMips, kMipValid, kUv, kLod, kNormals, kOut, kWeight };
     const StageColumn cols[] = { { l.image, level_bytes(l.format, l.width, l.height, in_c), Stage::kIn }, { l.valid, texels, Stage::kIn },
-                                 { l.uv, (size_t)l.n * 2 * sizeof(float), Stage::kIn }, { l.normals, (size_t)l.n * 3 * sizeof(float), Stage::kIn },
-                                 { l.out, (size_t)l.n * out_c * sizeof(float), Stage::kOut }, { l.out_weight, (size_t)l.n * sizeof(float), Stage::kOut } };
-    return staged(c, cols, [&](void* const* d) -> int {
+                                 { no_mips ? nullptr : l.mips, mips_bytes(l.format, plan, in_c), Stage::kIn },
+                                 { no_mips ? nullptr : l.mip_valid, (size_t)plan.texels, Stage::kIn },
+                                 { l.uv, (size_t)l.n * 2 * sizeof(float), Stage::kIn }, { l.lod, (size_t)l.n * sizeof(float), Stage::kIn },
+                                 { l.normals, (size_t)l.n * 3 * sizeof(float), Stage::kIn },
+                                 { l.out, (size_t)l.n * out_c * sizeof(float), Stage::kOut, l.channels ? "out" : "out_irradiance" },
+                                 { l.out_weight, (size_t)l.n * sizeof(float), Stage::kOut, "out_weight" } };
+    return run_columns(who, c, host, stream, cols, l.n == 0, [&](void* const* d, hipStream_t s) -> int {
         LookupArgs dl = l;
-        dl.image = d[kImage]; dl.valid = (const uint8_t*)d[kValid]; dl.uv = (const float*)d[kUv];
-        dl.normals = (const float*)d[kNormals]; dl.out = (float*)d[kOut]; dl.out_weight = (float*)d[kWeight];
-        return lookup_device(c, dl, c->stream);
+        dl.image = d[kImage]; dl.valid = (const uint8_t*)d[kValid]; dl.mips = d[kMips]; dl.mip_valid = (const uint8_t*)d[kMipValid];
+        dl.uv = (const float*)d[kUv]; dl.lod = (const float*)d[kLod]; dl.normals = (const float*)d[kNormals];
+        dl.out = (float*)d[kOut]; dl.out_weight = (float*)d[kWeight];
+        return lookup_device(c, dl, chain, plan, s);
     });
 }
 
 extern "C" int mi_lightmap_sample_device(mi_ctx* c, uint32_t width, uint32_t height, uint32_t channels, const float* image, const uint8_t* valid,
                                          uint32_t n, const float* uv, uint32_t flags, float* out, float* out_weight, void* stream) {
     if (channels == 0) return fail(MI_ERR_INVALID, "mi_lightmap_sample_device: channels 0 is not 3 or 27");
-    return lookup_entry_device("mi_lightmap_sample_device", c, { width, height, channels, image, valid, n, uv, nullptr, flags, out, out_weight }, stream);
+    return lookup_entry("mi_lightmap_sample_device", c, { 0, channels, Levels::kZero, width, height, image, valid, 1, nullptr, nullptr, n, uv,
+                        nullptr, nullptr, flags, out, out_weight }, false, stream);
 }
 
 extern "C" int mi_lightmap_sample(mi_ctx* c, uint32_t width, uint32_t height, uint32_t channels, const float* image, const uint8_t* valid,
                                   uint32_t n, const float* uv, uint32_t flags, float* out, float* out_weight) {
     if (channels == 0) return fail(MI_ERR_INVALID, "mi_lightmap_sample: channels 0 is not 3 or 27");
-    return lookup_entry_host("mi_lightmap_sample", c, { width, height, channels, image, valid, n, uv, nullptr, flags, out, out_weight });
+    return lookup_entry("mi_lightmap_sample", c, { 0, channels, Levels::kZero, width, height, image, valid, 1, nullptr, nullptr, n, uv, nullptr,
+                        nullptr, flags, out, out_weight }, true, nullptr);
 }
 
 extern "C" int mi_lightmap_sh_sample_device(mi_ctx* c, uint32_t width, uint32_t height, const float* sh, const uint8_t* valid, uint32_t n,
                                             const float* uv, const float* normals, uint32_t flags, float* out_irradiance, float* out_weight,
                                             void* stream) {
-    return lookup_entry_device("mi_lightmap_sh_sample_device", c, { width, height, 0, sh, valid, n, uv, normals, flags, out_irradiance, out_weight },
-                               stream);
+    return lookup_entry("mi_lightmap_sh_sample_device", c, { 0, 0, Levels::kZero, width, height, sh, valid, 1, nullptr, nullptr, n, uv, normals,
+                        nullptr, flags, out_irradiance, out_weight }, false, stream);
 }
 
 extern "C" int mi_lightmap_sh_sample(mi_ctx* c, uint32_t width, uint32_t height, const float* sh, const uint8_t* valid, uint32_t n,
                                      const float* uv, const float* normals, uint32_t flags, float* out_irradiance, float* out_weight) {
-    return lookup_entry_host("mi_lightmap_sh_sample", c, { width, height, 0, sh, valid, n, uv, normals, flags, out_irradiance, out_weight });
+    return lookup_entry("mi_lightmap_sh_sample", c, { 0, 0, Levels::kZero, width, height, sh, valid, 1, nullptr, nullptr, n, uv, normals, nullptr,
+                        flags, out_irradiance, out_weight }, true, nullptr);
 }
 
 // ------------------------------------------------------------------ lightmap mips (the coverage-aware pyramid and the trilinear lookups)
 // tracing.py lightmap_mips as lmm_reduce<3> / lmm_reduce<27>, launched by render_plan.cpp mip_plan (the layout and which level every
-// launch reads and how many it writes), and lightmap_sample_lod / lightmap_sh_sample_lod as one kernel each, which read the same layout.
+// launch reads and how many it writes); the trilinear lookups are the lookup above in its chain form, which reads the same layout.
 struct MipsArgs {
     uint32_t width, height, channels; const float* image; const uint8_t* valid; uint32_t levels; float* out_mips; uint8_t* out_valid;
     float* out_coverage;
@@ -1857,177 +1898,79 @@ static int mips_device(mi_ctx* c, const MipsArgs& m, const MipPlan& plan, float*
     });
 }
 
-extern "C" int mi_lightmap_mips_device(mi_ctx* c, uint32_t width, uint32_t height, uint32_t channels, const float* image, const uint8_t* valid,
-                                       uint32_t levels, float* out_mips, uint8_t* out_valid, float* out_coverage, void* stream) {
-    const char* who = "mi_lightmap_mips_device";
-    const MipsArgs m{ width, height, channels, image, valid, levels, out_mips, out_valid, out_coverage };
+// The entry (host: see run_columns): the arguments, the context, the overlaps; one level makes nothing.  Without out_coverage the planes
+// still have to exist on the device: the host form stages a column that is neither uploaded nor fetched, the device form uses the
+// context's own buffer (one such call at a time).  The launches are planned anew by the context's tuning once the context is known.
+static int mips_entry(const char* who, mi_ctx* c, const MipsArgs& m, bool host, void* stream) {
     MipPlan plan;
     MI_TRY(check_mips_args(who, m, &plan));
     if (!c) return fail(MI_ERR_INVALID, "ctx is NULL");
-    const size_t texels = (size_t)width * height, made = (size_t)plan.texels;
-    MI_TRY(check_no_overlap(who, { { out_mips, made * channels * sizeof(float), "out_mips" }, { out_valid, made, "out_valid" },
-                                   { out_coverage, made * sizeof(float), "out_coverage" } },
-                            { { image, texels * channels * sizeof(float) }, { valid, texels } }));
-    if (plan.levels == 1) return MI_OK;                // one level: nothing to make
-    HIP_TRY(hipSetDevice(c->device));
-    if (c->tune.lmm_levels_per_launch != kMipFuse) mip_plan(width, height, levels, c->tune.lmm_levels_per_launch, &plan);
-    float* cov = out_coverage;
-    if (!cov) {                                        // the coverage planes in the context's own buffer: one such call at a time
-        MI_TRY(ensure(&c->d_lmm, &c->lmm_bytes, made * sizeof(float)));
-        cov = (float*)c->d_lmm;
-    }
-    return mips_device(c, m, plan, cov, (hipStream_t)stream);
+    const size_t texels = (size_t)m.width * m.height, made = (size_t)plan.texels;
+    enum { kImage, kValid, kMips, kMipValid, kCov, kScratch };
+    static const char kScratchColumn = 0;
+    const StageColumn cols[] = { { m.image, texels * m.channels * sizeof(float), Stage::kIn }, { m.valid, texels, Stage::kIn },
+                                 { m.out_mips, made * m.channels * sizeof(float), Stage::kOut, "out_mips" },
+                                 { m.out_valid, made, Stage::kOut, "out_valid" }, { m.out_coverage, made * sizeof(float), Stage::kOut, "out_coverage" },
+                                 { m.out_coverage ? nullptr : &kScratchColumn, made * sizeof(float), Stage::kDevice } };
+    return run_columns(who, c, host, stream, cols, plan.levels == 1, [&](void* const* d, hipStream_t s) -> int {
+        if (c->tune.lmm_levels_per_launch != kMipFuse) mip_plan(m.width, m.height, m.levels, c->tune.lmm_levels_per_launch, &plan);
+        float* cov = (float*)(d[kCov] ? d[kCov] : d[kScratch]);
+        if (!cov) {
+            MI_TRY(ensure(&c->d_lmm, &c->lmm_bytes, made * sizeof(float)));
+            cov = (float*)c->d_lmm;
+        }
+        MipsArgs dm = m;
+        dm.image = (const float*)d[kImage]; dm.valid = (const uint8_t*)d[kValid]; dm.out_mips = (float*)d[kMips];
+        dm.out_valid = (uint8_t*)d[kMipValid];
+        return mips_device(c, dm, plan, cov, s);
+    });
+}
+
+extern "C" int mi_lightmap_mips_device(mi_ctx* c, uint32_t width, uint32_t height, uint32_t channels, const float* image, const uint8_t* valid,
+                                       uint32_t levels, float* out_mips, uint8_t* out_valid, float* out_coverage, void* stream) {
+    return mips_entry("mi_lightmap_mips_device", c, { width, height, channels, image, valid, levels, out_mips, out_valid, out_coverage }, false, stream);
 }
 
 extern "C" int mi_lightmap_mips(mi_ctx* c, uint32_t width, uint32_t height, uint32_t channels, const float* image, const uint8_t* valid,
                                 uint32_t levels, float* out_mips, uint8_t* out_valid, float* out_coverage) {
-    const char* who = "mi_lightmap_mips";
-    const MipsArgs m{ width, height, channels, image, valid, levels, out_mips, out_valid, out_coverage };
-    MipPlan plan;
-    MI_TRY(check_mips_args(who, m, &plan));
-    if (!c) return fail(MI_ERR_INVALID, "ctx is NULL");
-    if (plan.levels == 1) return MI_OK;                // before any device call
-    if (c->tune.lmm_levels_per_launch != kMipFuse) mip_plan(width, height, levels, c->tune.lmm_levels_per_launch, &plan);
-    const size_t texels = (size_t)width * height, made = (size_t)plan.texels;
-    enum { kImage, kValid, kMips, kMipValid, kCov, kScratch };
-    // without out_coverage the planes still have to exist on the device: a column that is neither uploaded nor fetched
-    static const char kScratchColumn = 0;
-    const StageColumn cols[] = { { image, texels * channels * sizeof(float), Stage::kIn }, { valid, texels, Stage::kIn },
-                                 { out_mips, made * channels * sizeof(float), Stage::kOut }, { out_valid, made, Stage::kOut },
-                                 { out_coverage, made * sizeof(float), Stage::kOut },
-                                 { out_coverage ? nullptr : &kScratchColumn, made * sizeof(float), Stage::kDevice } };
-    return staged(c, cols, [&](void* const* d) -> int {
-        MipsArgs dm = m;
-        dm.image = (const float*)d[kImage]; dm.valid = (const uint8_t*)d[kValid]; dm.out_mips = (float*)d[kMips];
-        dm.out_valid = (uint8_t*)d[kMipValid];
-        return mips_device(c, dm, plan, (float*)(d[kCov] ? d[kCov] : d[kScratch]), c->stream);
-    });
-}
-
-// The trilinear lookups.  One argument record serves both calls: channels == 0 is the fused SH form.
-struct LodArgs {
-    uint32_t width, height, channels; const void* image; const uint8_t* valid; uint32_t levels; const void* mips; const uint8_t* mip_valid;
-    uint32_t n; const float* uv; const float* normals; const float* lod; uint32_t flags; float* out; float* out_weight; uint32_t format = 0;
-};
-
-// Checked before the context, nothing is launched
-static int check_lod_args(const char* who, const LodArgs& l, MipPlan* plan) {
-    const bool sh = l.channels == 0;
-    if (!l.image || !l.uv || !l.lod || !l.out || (sh && !l.normals))
-        return fail(MI_ERR_INVALID, sh ? "%s: sh, uv, normals, lod and out_irradiance are required" : "%s: image, uv, lod and out are required", who);
-    if (l.width == 0 || l.width > 32768u || l.height == 0 || l.height > 32768u)
-        return fail(MI_ERR_INVALID, "%s: width %u / height %u is not in 1 .. 32768", who, l.width, l.height);
-    if (!sh && l.channels != 3 && l.channels != (uint32_t)kShFloats) return fail(MI_ERR_INVALID, "%s: channels %u is not 3 or 27", who, l.channels);
-    if (!mip_plan(l.width, l.height, l.levels, kMipFuse, plan))
-        return fail(MI_ERR_INVALID, "%s: levels %u is above the full chain of %u x %u, %u", who, l.levels, l.width, l.height,
-                    mip_full_chain(l.width, l.height));
-    if (plan->levels > 1 && !l.mips) return fail(MI_ERR_INVALID, "%s: mips is required with %u levels", who, plan->levels);
-    if (l.flags & MI_LS_NEAREST) return fail(MI_ERR_INVALID, "%s: MI_LS_NEAREST is refused: nearest addressing has no mips", who);
-    if (l.flags) return fail(MI_ERR_INVALID, "%s: unknown flag bits 0x%x", who, l.flags);
-    return MI_OK;
-}
-
-static int lod_device(mi_ctx* c, const LodArgs& l, const MipPlan& plan, hipStream_t stream) {
-    LmlLodArgs a{};
-    a.image = l.image; a.valid = l.valid; a.mips = l.mips; a.mip_valid = l.mip_valid; a.uv = l.uv; a.lod = l.lod; a.normals = l.normals;
-    a.out = l.out; a.out_weight = l.out_weight; a.levels = plan.levels; a.n = l.n;
-    for (uint32_t k = 0; k < plan.levels; k++) { a.off[k] = plan.level[k].offset; a.lw[k] = plan.level[k].width; a.lh[k] = plan.level[k].height; }
-    if (l.format == kLpBc6h) {
-        const Bc6hPlan blocks = bc6h_plan(plan);
-        for (uint32_t k = 0; k < plan.levels; k++) a.boff[k] = (uint32_t)blocks.level[k].offset;
-    }
-    return timed(c, stream, [&]() -> int {
-        HIP_TRY(l.format ? launch_lmp_sample_lod(a, l.format, l.channels, stream) : launch_lml_sample_lod(a, l.channels, stream));
-        return MI_OK;
-    });
-}
-
-static int lod_entry_device(const char* who, mi_ctx* c, const LodArgs& l, void* stream) {
-    MipPlan plan;
-    MI_TRY(check_lod_args(who, l, &plan));
-    if (!c) return fail(MI_ERR_INVALID, "ctx is NULL");
-    const size_t texels = (size_t)l.width * l.height, made = (size_t)plan.texels;
-    const size_t in_c = l.channels ? l.channels : (uint32_t)kShFloats, out_c = l.channels ? l.channels : 3u;
-    MI_TRY(check_no_overlap(who, { { l.out, (size_t)l.n * out_c * sizeof(float), l.channels ? "out" : "out_irradiance" },
-                                   { l.out_weight, (size_t)l.n * sizeof(float), "out_weight" } },
-                            { { l.image, level_bytes(l.format, l.width, l.height, in_c) }, { l.valid, texels }, { l.mips, mips_bytes(l.format, plan, in_c) },
-                              { l.mip_valid, made }, { l.uv, (size_t)l.n * 2 * sizeof(float) }, { l.lod, (size_t)l.n * sizeof(float) },
-                              { l.normals, (size_t)l.n * 3 * sizeof(float) } }));
-    if (l.n == 0) return MI_OK;
-    HIP_TRY(hipSetDevice(c->device));
-    return lod_device(c, l, plan, (hipStream_t)stream);
-}
-
-static int lod_entry_host(const char* who, mi_ctx* c, const LodArgs& l) {
-    MipPlan plan;
-    MI_TRY(check_lod_args(who, l, &plan));
-    if (!c) return fail(MI_ERR_INVALID, "ctx is NULL");
-    if (l.n == 0) return MI_OK;                // before any device call
-    const size_t texels = (size_t)l.width * l.height, made = (size_t)plan.texels;
-    const size_t in_c = l.channels ? l.channels : (uint32_t)kShFloats, out_c = l.channels ? l.channels : 3u;
-    const bool chain = plan.levels > 1;
-    enum { kImage, kValid, kMips, kMipValid, kUv, kLod, kNormals, kOut, kWeight };
-    const StageColumn cols[] = { { l.image, level_bytes(l.format, l.width, l.height, in_c), Stage::kIn }, { l.valid, texels, Stage::kIn },
-                                 { chain ? l.mips : nullptr, mips_bytes(l.format, plan, in_c), Stage::kIn },
-                                 { chain ? l.mip_valid : nullptr, made, Stage::kIn },
-                                 { l.uv, (size_t)l.n * 2 * sizeof(float), Stage::kIn }, { l.lod, (size_t)l.n * sizeof(float), Stage::kIn },
-                                 { l.normals, (size_t)l.n * 3 * sizeof(float), Stage::kIn },
-                                 { l.out, (size_t)l.n * out_c * sizeof(float), Stage::kOut }, { l.out_weight, (size_t)l.n * sizeof(float), Stage::kOut } };
-    return staged(c, cols, [&](void* const* d) -> int {
-        LodArgs dl = l;
-        dl.image = d[kImage]; dl.valid = (const uint8_t*)d[kValid]; dl.mips = d[kMips];
-        dl.mip_valid = (const uint8_t*)d[kMipValid]; dl.uv = (const float*)d[kUv]; dl.lod = (const float*)d[kLod];
-        dl.normals = (const float*)d[kNormals]; dl.out = (float*)d[kOut]; dl.out_weight = (float*)d[kWeight];
-        return lod_device(c, dl, plan, c->stream);
-    });
+    return mips_entry("mi_lightmap_mips", c, { width, height, channels, image, valid, levels, out_mips, out_valid, out_coverage }, true, nullptr);
 }
 
 extern "C" int mi_lightmap_sample_lod_device(mi_ctx* c, uint32_t width, uint32_t height, uint32_t channels, const float* image,
                                              const uint8_t* valid, uint32_t levels, const float* mips, const uint8_t* mip_valid, uint32_t n,
                                              const float* uv, const float* lod, uint32_t flags, float* out, float* out_weight, void* stream) {
     if (channels == 0) return fail(MI_ERR_INVALID, "mi_lightmap_sample_lod_device: channels 0 is not 3 or 27");
-    return lod_entry_device("mi_lightmap_sample_lod_device", c, { width, height, channels, image, valid, levels, mips, mip_valid, n, uv, nullptr,
-                            lod, flags, out, out_weight }, stream);
+    return lookup_entry("mi_lightmap_sample_lod_device", c, { 0, channels, Levels::kChain, width, height, image, valid, levels, mips, mip_valid,
+                        n, uv, nullptr, lod, flags, out, out_weight }, false, stream);
 }
 
 extern "C" int mi_lightmap_sample_lod(mi_ctx* c, uint32_t width, uint32_t height, uint32_t channels, const float* image, const uint8_t* valid,
                                       uint32_t levels, const float* mips, const uint8_t* mip_valid, uint32_t n, const float* uv,
                                       const float* lod, uint32_t flags, float* out, float* out_weight) {
     if (channels == 0) return fail(MI_ERR_INVALID, "mi_lightmap_sample_lod: channels 0 is not 3 or 27");
-    return lod_entry_host("mi_lightmap_sample_lod", c, { width, height, channels, image, valid, levels, mips, mip_valid, n, uv, nullptr, lod,
-                          flags, out, out_weight });
+    return lookup_entry("mi_lightmap_sample_lod", c, { 0, channels, Levels::kChain, width, height, image, valid, levels, mips, mip_valid, n, uv,
+                        nullptr, lod, flags, out, out_weight }, true, nullptr);
 }
 
 extern "C" int mi_lightmap_sh_sample_lod_device(mi_ctx* c, uint32_t width, uint32_t height, const float* sh, const uint8_t* valid,
                                                 uint32_t levels, const float* mips, const uint8_t* mip_valid, uint32_t n, const float* uv,
                                                 const float* normals, const float* lod, uint32_t flags, float* out_irradiance,
                                                 float* out_weight, void* stream) {
-    return lod_entry_device("mi_lightmap_sh_sample_lod_device", c, { width, height, 0, sh, valid, levels, mips, mip_valid, n, uv, normals, lod,
-                            flags, out_irradiance, out_weight }, stream);
+    return lookup_entry("mi_lightmap_sh_sample_lod_device", c, { 0, 0, Levels::kChain, width, height, sh, valid, levels, mips, mip_valid, n, uv,
+                        normals, lod, flags, out_irradiance, out_weight }, false, stream);
 }
 
 extern "C" int mi_lightmap_sh_sample_lod(mi_ctx* c, uint32_t width, uint32_t height, const float* sh, const uint8_t* valid, uint32_t levels,
                                          const float* mips, const uint8_t* mip_valid, uint32_t n, const float* uv, const float* normals,
                                          const float* lod, uint32_t flags, float* out_irradiance, float* out_weight) {
-    return lod_entry_host("mi_lightmap_sh_sample_lod", c, { width, height, 0, sh, valid, levels, mips, mip_valid, n, uv, normals, lod, flags,
-                          out_irradiance, out_weight });
+    return lookup_entry("mi_lightmap_sh_sample_lod", c, { 0, 0, Levels::kChain, width, height, sh, valid, levels, mips, mip_valid, n, uv, normals,
+                        lod, flags, out_irradiance, out_weight }, true, nullptr);
 }
 
 // ------------------------------------------------------------------ packed lightmaps (f16 and RGB9E5 storage, lookups that read them)
 // tracing.py lightmap_pack / lightmap_unpack as lmp_pack<F> / lmp_unpack<F>: a count of texels, whatever their layout.  The packed lookups
-// are the lookups above with LookupArgs / LodArgs' format set: the same checks, staging, plan and timing, the lmp_* kernels.
+// are the lookup above with LookupArgs' format set: the same checks, columns, plan and timing, the lmp_* kernels.
 struct PackArgs { uint32_t format, channels; uint64_t n_texels; const void* src; void* dst; bool unpack; };
-
-// What every packed call checks of its format, before anything else (sh: the fused form, which reads signed coefficients)
-static int check_packed_format(const char* who, uint32_t format, uint32_t channels, bool sh) {
-    if (format != MI_LP_F16 && format != MI_LP_RGB9E5)
-        return fail(MI_ERR_INVALID, "%s: format %u is not MI_LP_F16 or MI_LP_RGB9E5 (f32 texels take the unpacked calls)", who, format);
-    if (sh && format != MI_LP_F16) return fail(MI_ERR_INVALID, "%s: SH coefficients are signed: only MI_LP_F16 holds them", who);
-    if (!sh && channels != 3 && channels != (uint32_t)kShFloats) return fail(MI_ERR_INVALID, "%s: channels %u is not 3 or 27", who, channels);
-    if (format == MI_LP_RGB9E5 && channels != 3)
-        return fail(MI_ERR_INVALID, "%s: MI_LP_RGB9E5 holds 3 unsigned channels, not %u (SH records pack as MI_LP_F16)", who, channels);
-    return MI_OK;
-}
 
 static int pack_device(mi_ctx* c, const PackArgs& p, hipStream_t stream) {
     LmpArgs a{};
@@ -2038,25 +1981,19 @@ static int pack_device(mi_ctx* c, const PackArgs& p, hipStream_t stream) {
     });
 }
 
-// host: HOST pointers, staged and blocking; else DEVICE pointers queued on `stream`
+// The entry (host: see run_columns): the arguments, the context, the overlap; no texels launch nothing
 static int pack_entry(const char* who, mi_ctx* c, const PackArgs& p, bool host, void* stream) {
     MI_TRY(check_packed_format(who, p.format, p.channels, false));
     if (!p.src || !p.dst) return fail(MI_ERR_INVALID, p.unpack ? "%s: packed and out_texels are required" : "%s: texels and out_packed are required", who);
     if (p.n_texels > (1ull << 32)) return fail(MI_ERR_INVALID, "%s: n_texels %llu is above 2^32", who, (unsigned long long)p.n_texels);
     if (!c) return fail(MI_ERR_INVALID, "ctx is NULL");
     const size_t f32_bytes = (size_t)p.n_texels * p.channels * sizeof(float), packed_bytes = (size_t)p.n_texels * texel_bytes(p.format, p.channels);
-    const size_t src_bytes = p.unpack ? packed_bytes : f32_bytes, dst_bytes = p.unpack ? f32_bytes : packed_bytes;
-    if (!host) MI_TRY(check_no_overlap(who, { { p.dst, dst_bytes, p.unpack ? "out_texels" : "out_packed" } }, { { p.src, src_bytes } }));
-    if (p.n_texels == 0) return MI_OK;         // before any device call
-    if (!host) {
-        HIP_TRY(hipSetDevice(c->device));
-        return pack_device(c, p, (hipStream_t)stream);
-    }
-    const StageColumn cols[] = { { p.src, src_bytes, Stage::kIn }, { p.dst, dst_bytes, Stage::kOut } };
-    return staged(c, cols, [&](void* const* d) -> int {
+    const StageColumn cols[] = { { p.src, p.unpack ? packed_bytes : f32_bytes, Stage::kIn },
+                                 { p.dst, p.unpack ? f32_bytes : packed_bytes, Stage::kOut, p.unpack ? "out_texels" : "out_packed" } };
+    return run_columns(who, c, host, stream, cols, p.n_texels == 0, [&](void* const* d, hipStream_t s) -> int {
         PackArgs dp = p;
         dp.src = d[0]; dp.dst = d[1];
-        return pack_device(c, dp, c->stream);
+        return pack_device(c, dp, s);
     });
 }
 
@@ -2075,54 +2012,44 @@ extern "C" int mi_lightmap_unpack_device(mi_ctx* c, uint32_t format, uint32_t ch
     return pack_entry("mi_lightmap_unpack_device", c, { format, channels, n_texels, packed, out_texels, true }, false, stream);
 }
 
-// The packed lookups: lod != NULL is the trilinear form over the mip plan; lod == NULL the level-0 form, which has no chain
-static int format_lookup_entry(const char* who, mi_ctx* c, uint32_t format, LodArgs l, bool host, void* stream);
-static int packed_lookup_entry(const char* who, mi_ctx* c, uint32_t format, LodArgs l, bool host, void* stream) {
-    MI_TRY(check_packed_format(who, format, l.channels, l.channels == 0));
-    return format_lookup_entry(who, c, format, l, host, stream);
+// The packed lookups: lod != NULL is the trilinear form over the mip plan; lod == NULL the level-0 form, which has no chain.  The format
+// is the caller's here (0, f32, is refused: f32 texels take the unpacked calls), so it is checked before anything else.
+static int packed_lookup_entry(const char* who, mi_ctx* c, const LookupArgs& l, bool host, void* stream) {
+    MI_TRY(check_packed_format(who, l.format, l.channels, l.channels == 0));
+    return lookup_entry(who, c, l, host, stream);
 }
-// ... for a format already checked: MI_LP_* or kLpBc6h
-static int format_lookup_entry(const char* who, mi_ctx* c, uint32_t format, LodArgs l, bool host, void* stream) {
-    l.format = format;
-    if (l.lod) return host ? lod_entry_host(who, c, l) : lod_entry_device(who, c, l, stream);
-    if (l.levels != 1 || l.mips || l.mip_valid)
-        return fail(MI_ERR_INVALID, "%s: lod == NULL reads level 0 alone: levels must be 1 (not %u) and mips, mip_valid NULL", who, l.levels);
-    LookupArgs k{ l.width, l.height, l.channels, l.image, l.valid, l.n, l.uv, l.normals, l.flags, l.out, l.out_weight, format };
-    return host ? lookup_entry_host(who, c, k) : lookup_entry_device(who, c, k, stream);
-}
-
 extern "C" int mi_lightmap_sample_packed(mi_ctx* c, uint32_t format, uint32_t width, uint32_t height, uint32_t channels, const void* image,
                                          const uint8_t* valid, uint32_t levels, const void* mips, const uint8_t* mip_valid, uint32_t n,
                                          const float* uv, const float* lod, uint32_t flags, float* out, float* out_weight) {
     if (channels == 0) return fail(MI_ERR_INVALID, "mi_lightmap_sample_packed: channels 0 is not 3 or 27");
-    return packed_lookup_entry("mi_lightmap_sample_packed", c, format, { width, height, channels, image, valid, levels, mips, mip_valid, n, uv,
-                               nullptr, lod, flags, out, out_weight }, true, nullptr);
+    return packed_lookup_entry("mi_lightmap_sample_packed", c, { format, channels, Levels::kEither, width, height, image, valid, levels, mips, mip_valid,
+                        n, uv, nullptr, lod, flags, out, out_weight }, true, nullptr);
 }
 extern "C" int mi_lightmap_sample_packed_device(mi_ctx* c, uint32_t format, uint32_t width, uint32_t height, uint32_t channels,
                                                 const void* image, const uint8_t* valid, uint32_t levels, const void* mips,
                                                 const uint8_t* mip_valid, uint32_t n, const float* uv, const float* lod, uint32_t flags,
                                                 float* out, float* out_weight, void* stream) {
     if (channels == 0) return fail(MI_ERR_INVALID, "mi_lightmap_sample_packed_device: channels 0 is not 3 or 27");
-    return packed_lookup_entry("mi_lightmap_sample_packed_device", c, format, { width, height, channels, image, valid, levels, mips, mip_valid,
-                               n, uv, nullptr, lod, flags, out, out_weight }, false, stream);
+    return packed_lookup_entry("mi_lightmap_sample_packed_device", c, { format, channels, Levels::kEither, width, height, image, valid, levels, mips,
+                        mip_valid, n, uv, nullptr, lod, flags, out, out_weight }, false, stream);
 }
 extern "C" int mi_lightmap_sh_sample_packed(mi_ctx* c, uint32_t format, uint32_t width, uint32_t height, const void* sh, const uint8_t* valid,
                                             uint32_t levels, const void* mips, const uint8_t* mip_valid, uint32_t n, const float* uv,
                                             const float* normals, const float* lod, uint32_t flags, float* out_irradiance, float* out_weight) {
-    return packed_lookup_entry("mi_lightmap_sh_sample_packed", c, format, { width, height, 0, sh, valid, levels, mips, mip_valid, n, uv, normals,
-                               lod, flags, out_irradiance, out_weight }, true, nullptr);
+    return packed_lookup_entry("mi_lightmap_sh_sample_packed", c, { format, 0, Levels::kEither, width, height, sh, valid, levels, mips, mip_valid, n, uv,
+                        normals, lod, flags, out_irradiance, out_weight }, true, nullptr);
 }
 extern "C" int mi_lightmap_sh_sample_packed_device(mi_ctx* c, uint32_t format, uint32_t width, uint32_t height, const void* sh,
                                                    const uint8_t* valid, uint32_t levels, const void* mips, const uint8_t* mip_valid,
                                                    uint32_t n, const float* uv, const float* normals, const float* lod, uint32_t flags,
                                                    float* out_irradiance, float* out_weight, void* stream) {
-    return packed_lookup_entry("mi_lightmap_sh_sample_packed_device", c, format, { width, height, 0, sh, valid, levels, mips, mip_valid, n, uv,
-                               normals, lod, flags, out_irradiance, out_weight }, false, stream);
+    return packed_lookup_entry("mi_lightmap_sh_sample_packed_device", c, { format, 0, Levels::kEither, width, height, sh, valid, levels, mips, mip_valid,
+                        n, uv, normals, lod, flags, out_irradiance, out_weight }, false, stream);
 }
 
 // ------------------------------------------------------------------ BC6H lightmaps (a block encoder, the decoder, the lookup that reads blocks)
-// tracing.py lightmap_bc6h_encode / lightmap_bc6h_decode as lmb_encode / lmb_decode, one level per call; the lookup is the lookups above
-// with the format kLpBc6h: the same checks, staging, plan and timing, the lmp_* kernels with the block policy.  BC6H is lossy, so it has
+// tracing.py lightmap_bc6h_encode / lightmap_bc6h_decode as lmb_encode / lmb_decode, one level per call; the lookup is the lookup above
+// with the format kLpBc6h: the same checks, columns, plan and timing, the lmp_* kernels with the block policy.  BC6H is lossy, so it has
 // entry points of its own: the MI_LP_* calls keep refusing every format they refused.
 struct Bc6hArgs { uint32_t width, height; const float* image; const uint8_t* valid; uint32_t rounds; void* blocks; float* out; bool decode; };
 
@@ -2136,7 +2063,8 @@ static int bc6h_device(mi_ctx* c, const Bc6hArgs& b, hipStream_t stream) {
     });
 }
 
-// host: HOST pointers, staged and blocking; else DEVICE pointers queued on `stream`
+// The entry of the coder (host: see run_columns).  Encoding reads image and valid and writes the blocks; decoding reads the blocks and
+// writes out: the columns of the other direction are absent.
 static int bc6h_entry(const char* who, mi_ctx* c, const Bc6hArgs& b, bool host, void* stream) {
     if (!b.blocks || (b.decode ? !b.out : !b.image))
         return fail(MI_ERR_INVALID, b.decode ? "%s: blocks and out_image are required" : "%s: image and out_blocks are required", who);
@@ -2145,26 +2073,15 @@ static int bc6h_entry(const char* who, mi_ctx* c, const Bc6hArgs& b, bool host, 
     if (b.rounds > kBc6hMaxRounds) return fail(MI_ERR_INVALID, "%s: rounds %u is above %u", who, b.rounds, kBc6hMaxRounds);
     if (!host && ((uintptr_t)b.blocks & 15u)) return fail(MI_ERR_INVALID, "%s: the blocks are not 16-byte aligned", who);
     if (!c) return fail(MI_ERR_INVALID, "ctx is NULL");
-    const size_t texels = (size_t)b.width * b.height, f32_bytes = texels * 3 * sizeof(float), block_bytes = level_bytes(kLpBc6h, b.width, b.height, 3);
-    if (!host) {
-        if (b.decode) MI_TRY(check_no_overlap(who, { { b.out, f32_bytes, "out_image" } }, { { b.blocks, block_bytes } }));
-        else MI_TRY(check_no_overlap(who, { { b.blocks, block_bytes, "out_blocks" } }, { { b.image, f32_bytes }, { b.valid, texels } }));
-        HIP_TRY(hipSetDevice(c->device));
-        return bc6h_device(c, b, (hipStream_t)stream);
-    }
-    if (b.decode) {
-        const StageColumn cols[] = { { b.blocks, block_bytes, Stage::kIn }, { b.out, f32_bytes, Stage::kOut } };
-        return staged(c, cols, [&](void* const* d) -> int {
-            Bc6hArgs db = b;
-            db.blocks = d[0]; db.out = (float*)d[1];
-            return bc6h_device(c, db, c->stream);
-        });
-    }
-    const StageColumn cols[] = { { b.image, f32_bytes, Stage::kIn }, { b.valid, texels, Stage::kIn }, { b.blocks, block_bytes, Stage::kOut } };
-    return staged(c, cols, [&](void* const* d) -> int {
+    const size_t texels = (size_t)b.width * b.height, f32_bytes = texels * 3 * sizeof(float);
+    enum { kImage, kValid, kBlocks, kOut };
+    const StageColumn cols[] = { { b.image, f32_bytes, Stage::kIn }, { b.valid, texels, Stage::kIn },
+                                 { b.blocks, level_bytes(kLpBc6h, b.width, b.height, 3), b.decode ? Stage::kIn : Stage::kOut, "out_blocks" },
+                                 { b.out, f32_bytes, Stage::kOut, "out_image" } };
+    return run_columns(who, c, host, stream, cols, false, [&](void* const* d, hipStream_t s) -> int {
         Bc6hArgs db = b;
-        db.image = (const float*)d[0]; db.valid = (const uint8_t*)d[1]; db.blocks = d[2];
-        return bc6h_device(c, db, c->stream);
+        db.image = (const float*)d[kImage]; db.valid = (const uint8_t*)d[kValid]; db.blocks = d[kBlocks]; db.out = (float*)d[kOut];
+        return bc6h_device(c, db, s);
     });
 }
 
@@ -2184,21 +2101,17 @@ extern "C" int mi_lightmap_bc6h_decode_device(mi_ctx* c, uint32_t width, uint32_
 }
 
 // The lookup: mi_lightmap_sample_packed's rules word for word, three channels, the texels in blocks
-static int bc6h_lookup_entry(const char* who, mi_ctx* c, const LodArgs& l, bool host, void* stream) {
-    if (!host && (((uintptr_t)l.image | (uintptr_t)l.mips) & 15u)) return fail(MI_ERR_INVALID, "%s: the blocks are not 16-byte aligned", who);
-    return format_lookup_entry(who, c, kLpBc6h, l, host, stream);
-}
 extern "C" int mi_lightmap_sample_bc6h(mi_ctx* c, uint32_t width, uint32_t height, const void* image_blocks, const uint8_t* valid,
                                        uint32_t levels, const void* mip_blocks, const uint8_t* mip_valid, uint32_t n, const float* uv,
                                        const float* lod, uint32_t flags, float* out, float* out_weight) {
-    return bc6h_lookup_entry("mi_lightmap_sample_bc6h", c, { width, height, 3, image_blocks, valid, levels, mip_blocks, mip_valid, n, uv, nullptr,
-                             lod, flags, out, out_weight }, true, nullptr);
+    return lookup_entry("mi_lightmap_sample_bc6h", c, { kLpBc6h, 3, Levels::kEither, width, height, image_blocks, valid, levels, mip_blocks,
+                        mip_valid, n, uv, nullptr, lod, flags, out, out_weight }, true, nullptr);
 }
 extern "C" int mi_lightmap_sample_bc6h_device(mi_ctx* c, uint32_t width, uint32_t height, const void* image_blocks, const uint8_t* valid,
                                               uint32_t levels, const void* mip_blocks, const uint8_t* mip_valid, uint32_t n, const float* uv,
                                               const float* lod, uint32_t flags, float* out, float* out_weight, void* stream) {
-    return bc6h_lookup_entry("mi_lightmap_sample_bc6h_device", c, { width, height, 3, image_blocks, valid, levels, mip_blocks, mip_valid, n, uv,
-                             nullptr, lod, flags, out, out_weight }, false, stream);
+    return lookup_entry("mi_lightmap_sample_bc6h_device", c, { kLpBc6h, 3, Levels::kEither, width, height, image_blocks, valid, levels,
+                        mip_blocks, mip_valid, n, uv, nullptr, lod, flags, out, out_weight }, false, stream);
 }
 
 // ------------------------------------------------------------------ variance-guided lightmap finishing
@@ -2209,8 +2122,8 @@ extern "C" int mi_lightmap_finish_var_device(mi_ctx* c, uint32_t width, uint32_t
                                              float sigma_plane, float reach, float sigma_color, float color_floor, uint32_t dilate,
                                              float* out_image, float* out_var, uint8_t* out_valid, void* stream) {
     const FinishVarArgs fv = { m2, nullptr, samples, color_floor, out_var };
-    return finish_entry_device("mi_lightmap_finish_var_device", FinishForm::kVar, c, { width, height, image, points, normals, levels,
-                               normal_power_log2, sigma_plane, reach, sigma_color, dilate, out_image, out_valid }, &fv, stream);
+    return finish_entry("mi_lightmap_finish_var_device", FinishForm::kVar, c, { width, height, image, points, normals, levels,
+                        normal_power_log2, sigma_plane, reach, sigma_color, dilate, out_image, out_valid }, &fv, false, stream);
 }
 
 extern "C" int mi_lightmap_finish_var(mi_ctx* c, uint32_t width, uint32_t height, const float* image, const float* m2, uint32_t samples,
@@ -2218,8 +2131,8 @@ extern "C" int mi_lightmap_finish_var(mi_ctx* c, uint32_t width, uint32_t height
                                       float sigma_plane, float reach, float sigma_color, float color_floor, uint32_t dilate,
                                       float* out_image, float* out_var, uint8_t* out_valid) {
     const FinishVarArgs fv = { m2, nullptr, samples, color_floor, out_var };
-    return finish_entry_host("mi_lightmap_finish_var", FinishForm::kVar, c, { width, height, image, points, normals, levels,
-                             normal_power_log2, sigma_plane, reach, sigma_color, dilate, out_image, out_valid }, &fv);
+    return finish_entry("mi_lightmap_finish_var", FinishForm::kVar, c, { width, height, image, points, normals, levels,
+                        normal_power_log2, sigma_plane, reach, sigma_color, dilate, out_image, out_valid }, &fv, true, nullptr);
 }
 
 extern "C" int mi_lightmap_finish_var_counts_device(mi_ctx* c, uint32_t width, uint32_t height, const float* image, const float* m2,
@@ -2229,8 +2142,8 @@ extern "C" int mi_lightmap_finish_var_counts_device(mi_ctx* c, uint32_t width, u
                                                     void* stream) {
     if (!counts) return fail(MI_ERR_INVALID, "mi_lightmap_finish_var_counts_device: counts is required");
     const FinishVarArgs fv = { m2, counts, 2, color_floor, out_var };
-    return finish_entry_device("mi_lightmap_finish_var_counts_device", FinishForm::kVar, c, { width, height, image, points, normals, levels,
-                               normal_power_log2, sigma_plane, reach, sigma_color, dilate, out_image, out_valid }, &fv, stream);
+    return finish_entry("mi_lightmap_finish_var_counts_device", FinishForm::kVar, c, { width, height, image, points, normals, levels,
+                        normal_power_log2, sigma_plane, reach, sigma_color, dilate, out_image, out_valid }, &fv, false, stream);
 }
 
 extern "C" int mi_lightmap_finish_var_counts(mi_ctx* c, uint32_t width, uint32_t height, const float* image, const float* m2,
@@ -2239,8 +2152,8 @@ extern "C" int mi_lightmap_finish_var_counts(mi_ctx* c, uint32_t width, uint32_t
                                              uint32_t dilate, float* out_image, float* out_var, uint8_t* out_valid) {
     if (!counts) return fail(MI_ERR_INVALID, "mi_lightmap_finish_var_counts: counts is required");
     const FinishVarArgs fv = { m2, counts, 2, color_floor, out_var };
-    return finish_entry_host("mi_lightmap_finish_var_counts", FinishForm::kVar, c, { width, height, image, points, normals, levels,
-                             normal_power_log2, sigma_plane, reach, sigma_color, dilate, out_image, out_valid }, &fv);
+    return finish_entry("mi_lightmap_finish_var_counts", FinishForm::kVar, c, { width, height, image, points, normals, levels,
+                        normal_power_log2, sigma_plane, reach, sigma_color, dilate, out_image, out_valid }, &fv, true, nullptr);
 }
 
 // ------------------------------------------------------------------ adaptive lightmap baking (select, gather, merge, the whole bake)

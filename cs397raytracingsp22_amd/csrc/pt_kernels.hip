@@ -5244,13 +5244,6 @@ hipError_t launch_lsh_atrous(const LmfArgs& a, hipStream_t stream) {
     return hipGetLastError();
 }
 hipError_t launch_lsh_eval(const LshEvalArgs& a, hipStream_t stream) { return launch_per_item(lsh_eval, a.n, stream, a); }
-// lightmap lookup: `channels` floats per texel out (3 or 27), or 0: the fused SH form
-hipError_t launch_lml_sample(const LmlArgs& a, uint32_t channels, hipStream_t stream) {
-    if (channels == 0) return launch_per_item(lml_sh_sample, a.n, stream, a);
-    if (channels == 3) return launch_per_item(lml_sample<3>, a.n, stream, a);
-    if (channels == kShFloats) return launch_per_item(lml_sample<kShFloats>, a.n, stream, a);
-    return hipErrorInvalidValue;
-}
 // lightmap mips: one block per 32 x 32 tile of the level read; `channels` 3 or 27
 hipError_t launch_lmm_reduce(const LmmArgs& a, uint32_t channels, hipStream_t stream) {
     const uint32_t tiles_y = (a.src_h + kTile - 1) / kTile;
@@ -5261,39 +5254,11 @@ hipError_t launch_lmm_reduce(const LmmArgs& a, uint32_t channels, hipStream_t st
     else return hipErrorInvalidValue;
     return hipGetLastError();
 }
-// trilinear lightmap lookup: `channels` floats per texel out (3 or 27), or 0: the fused SH form
-hipError_t launch_lml_sample_lod(const LmlLodArgs& a, uint32_t channels, hipStream_t stream) {
-    if (a.levels == 0 || a.levels > kMipMaxLevels) return hipErrorInvalidValue;
-    if (channels == 0) return launch_per_item(lml_sh_sample_lod, a.n, stream, a);
-    if (channels == 3) return launch_per_item(lml_sample_lod<3>, a.n, stream, a);
-    if (channels == kShFloats) return launch_per_item(lml_sample_lod<kShFloats>, a.n, stream, a);
-    return hipErrorInvalidValue;
-}
 // packed lightmaps: `format` MI_LP_*; a.n counts f16 elements or RGB9E5 texels
 hipError_t launch_lmp_pack(const LmpArgs& a, uint32_t format, bool unpack, hipStream_t stream) {
     if ((a.n + kBlock - 1) / kBlock > 0x7fffffffull) return hipErrorInvalidValue;
     if (format == kLpF16) return unpack ? launch_per_item(lmp_unpack<kLpF16>, (a.n + 1) / 2, stream, a) : launch_per_item(lmp_pack<kLpF16>, (a.n + 1) / 2, stream, a);
     if (format == kLpRgb9e5) return unpack ? launch_per_item(lmp_unpack<kLpRgb9e5>, a.n, stream, a) : launch_per_item(lmp_pack<kLpRgb9e5>, a.n, stream, a);
-    return hipErrorInvalidValue;
-}
-// the packed lookups: launch_lml_sample's and launch_lml_sample_lod's forms per format (RGB9E5: 3 channels only)
-hipError_t launch_lmp_sample(const LmlArgs& a, uint32_t format, uint32_t channels, hipStream_t stream) {
-    if (format == kLpBc6h && channels == 3) return launch_per_item(lmp_sample<LmTexBc6h, 3>, a.n, stream, a);
-    if (format == kLpRgb9e5 && channels == 3) return launch_per_item(lmp_sample<LmTexRgb9e5, 3>, a.n, stream, a);
-    if (format != kLpF16) return hipErrorInvalidValue;
-    if (channels == 0) return launch_per_item(lmp_sh_sample<LmTexF16>, a.n, stream, a);
-    if (channels == 3) return launch_per_item(lmp_sample<LmTexF16, 3>, a.n, stream, a);
-    if (channels == kShFloats) return launch_per_item(lmp_sample<LmTexF16, kShFloats>, a.n, stream, a);
-    return hipErrorInvalidValue;
-}
-hipError_t launch_lmp_sample_lod(const LmlLodArgs& a, uint32_t format, uint32_t channels, hipStream_t stream) {
-    if (a.levels == 0 || a.levels > kMipMaxLevels) return hipErrorInvalidValue;
-    if (format == kLpRgb9e5 && channels == 3) return launch_per_item(lmp_sample_lod<LmTexRgb9e5, 3>, a.n, stream, a);
-    if (format == kLpBc6h && channels == 3) return launch_per_item(lmp_sample_lod<LmTexBc6h, 3>, a.n, stream, a);
-    if (format != kLpF16) return hipErrorInvalidValue;
-    if (channels == 0) return launch_per_item(lmp_sh_sample_lod<LmTexF16>, a.n, stream, a);
-    if (channels == 3) return launch_per_item(lmp_sample_lod<LmTexF16, 3>, a.n, stream, a);
-    if (channels == kShFloats) return launch_per_item(lmp_sample_lod<LmTexF16, kShFloats>, a.n, stream, a);
     return hipErrorInvalidValue;
 }
 // BC6H lightmaps: one lane per texel of the padded block grid (encode) or of the image (decode)
@@ -5345,6 +5310,29 @@ template <class Args> static hipError_t launch_form(const void* fn, const Args& 
     void* params[] = { (void*)&args };
     (void)hipLaunchKernel(fn, dim3(n_blocks), dim3(kBlock), params, dyn, stream);
     return hipGetLastError();
+}
+// The lightmap lookups, one lane per point: the kernel at [level form][format][channel form].  format: 0 = f32 texels, else kLp*;
+// channels: 3 or 27 floats per texel out, or 0: the fused SH form.  An empty slot is a form that does not exist: RGB9E5 texels and BC6H
+// blocks hold three unsigned channels.
+static const void* lookup_kernel(bool lod, uint32_t format, uint32_t channels) {
+#define PT_L(S) { { (const void*)&lml_sample##S<3>, (const void*)&lml_sample##S<kShFloats>, (const void*)&lml_sh_sample##S },                              \
+                  { (const void*)&lmp_sample##S<LmTexF16, 3>, (const void*)&lmp_sample##S<LmTexF16, kShFloats>, (const void*)&lmp_sh_sample##S<LmTexF16> }, \
+                  { (const void*)&lmp_sample##S<LmTexRgb9e5, 3>, nullptr, nullptr }, { (const void*)&lmp_sample##S<LmTexBc6h, 3>, nullptr, nullptr } }
+    static const void* const fn[2][4][3] = { PT_L(), PT_L(_lod) };       // [lod][format][0: 3 channels, 1: 27, 2: SH]
+#undef PT_L
+    const int form = channels == 3 ? 0 : channels == kShFloats ? 1 : channels == 0 ? 2 : -1;
+    return format > kLpBc6h || form < 0 ? nullptr : fn[lod][format][form];
+}
+template <class Args> static hipError_t launch_lookup_form(bool lod, const Args& a, uint32_t format, uint32_t channels, hipStream_t stream) {
+    const void* const fn = lookup_kernel(lod, format, channels);
+    return fn ? launch_form(fn, a, (uint32_t)(((size_t)a.n + kBlock - 1) / kBlock), 0, stream) : hipErrorInvalidValue;
+}
+hipError_t launch_lookup(const LmlArgs& a, uint32_t format, uint32_t channels, hipStream_t stream) {
+    return launch_lookup_form(false, a, format, channels, stream);
+}
+hipError_t launch_lookup(const LmlLodArgs& a, uint32_t format, uint32_t channels, hipStream_t stream) {
+    if (a.levels == 0 || a.levels > kMipMaxLevels) return hipErrorInvalidValue;
+    return launch_lookup_form(true, a, format, channels, stream);
 }
 hipError_t launch_megakernel(const K1Args& args, uint32_t n_blocks, bool lds, bool sig, size_t lds_bytes, hipStream_t stream) {
     static const void* const fn[2][2] = { { (const void*)&pt_megakernel<false, false>, (const void*)&pt_megakernel<false, true> },

@@ -1146,14 +1146,6 @@ def check_lightmap_lod(chain, uv, lod, valid_chain=None, flags: int = 0, normals
     return levels, masks, T, D, N, shape
 
 
-def _lod_buffers(levels, masks):
-    """What check_lightmap_lod returned as the buffers the C calls take: (level 0's mask u8 or None, levels 1 .. L - 1 packed
-    [sum W_l H_l, C] f32, their masks packed u8 or None)"""
-    v0 = None if masks[0] is None else np.ascontiguousarray(masks[0], np.uint8)
-    mv = None if len(masks) < 2 or masks[1] is None else _lmm_pack(masks, np.uint8)
-    return v0, _lmm_pack(levels, np.float32, (levels[0].shape[2],)), mv
-
-
 def _lml_axis_lod(t, n0, s, n):
     """One axis of the bilinear form at level l: coordinate t in 0 .. 1, n0 texels at level 0, s = 2^-l (exact), n texels at level l:
     ((i0, i1), (1 - f, f)).  _lml_axis' clamp and index expressions; at l = 0 this is _lml_axis itself."""
@@ -1362,43 +1354,46 @@ def check_lightmap_packed(packed_chain, format, uv, lod=None, valid_chain=None, 
         raise ValueError(f"the levels must be [H, W, 9, 3] or [H, W, 27], got {np.shape(chain[0])}")
     if sh and normals is None:
         raise ValueError("normals are required")
+    return packed, _check_level_form(levels, uv, lod, valid_chain, flags, normals)
+
+
+def _check_level_form(levels, uv, lod, valid_chain, flags, normals=None):
+    """The f32 check of a lookup that has both level forms: with `lod` check_lightmap_lod's of the chain; with lod None
+    check_lightmap_lookup's of level 0, which must then be the one level given"""
     if lod is not None:
-        return packed, check_lightmap_lod(levels, uv, lod, valid_chain, flags, normals)
+        return check_lightmap_lod(levels, uv, lod, valid_chain, flags, normals)
     if len(levels) != 1:
         raise ValueError(f"lod None reads level 0 alone: {len(levels)} levels were given")
     if isinstance(valid_chain, (list, tuple)):
         if len(valid_chain) != 1:
             raise ValueError("lod None reads level 0 alone: valid_chain must be None, one mask or a list of one")
         valid_chain = valid_chain[0]
-    return packed, check_lightmap_lookup(levels[0], uv, valid_chain, flags, normals)
+    return check_lightmap_lookup(levels[0], uv, valid_chain, flags, normals)
+
+
+def _sample_level_form(checked, lod, sh: bool = False):
+    """The definition's result for what _check_level_form returned: the level-0 lookup or the trilinear one, plain or fused SH"""
+    if lod is None:
+        img, T, v8, flags, N, shape = checked
+        out, sw = lightmap_sh_sample(img, T, N, v8, flags) if sh else lightmap_sample(img, T, v8, flags)
+    else:
+        levels, masks, T, D, N, shape = checked                     # (the flags are 0 here: the check refuses every other value)
+        out, sw = lightmap_sh_sample_lod(levels, T, N, D, masks) if sh else lightmap_sample_lod(levels, T, D, masks)
+    return out.reshape(shape + out.shape[-1:]), sw.reshape(shape)
 
 
 def lightmap_sample_packed(packed_chain, format, uv, lod=None, valid_chain=None, flags: int = 0):
     """Read a packed lightmap at uv points on the host (numpy only).  This is the DEFINITION of mi_lightmap_sample_packed: unpack, then
     lightmap_sample_lod — or, with lod None, lightmap_sample of the one level (abi.MI_LS_NEAREST then gives the decoded texel as it
     stands, a -0.0 included).  Arguments as check_lightmap_packed.  Returns (out [..., C] f32, weight [...] f32)."""
-    _, checked = check_lightmap_packed(packed_chain, format, uv, lod, valid_chain, flags)
-    if lod is None:
-        img, T, v8, flags, _, shape = checked
-        out, sw = lightmap_sample(img, T, v8, flags)
-    else:
-        levels, masks, T, D, _, shape = checked
-        out, sw = lightmap_sample_lod(levels, T, D, masks, flags)
-    return out.reshape(shape + out.shape[-1:]), sw.reshape(shape)
+    return _sample_level_form(check_lightmap_packed(packed_chain, format, uv, lod, valid_chain, flags)[1], lod)
 
 
 def lightmap_sh_sample_packed(packed_chain, format, uv, normals, lod=None, valid_chain=None, flags: int = 0):
     """The irradiance of a packed directional lightmap at uv points and their normals on the host (numpy only).  This is the DEFINITION
     of mi_lightmap_sh_sample_packed: unpack (abi.MI_LP_F16 only), then lightmap_sh_sample_lod — or, with lod None, lightmap_sh_sample
     of the one level.  Returns (E [..., 3] f32, weight [...] f32)."""
-    _, checked = check_lightmap_packed(packed_chain, format, uv, lod, valid_chain, flags, normals, sh=True)
-    if lod is None:
-        img, T, v8, flags, N, shape = checked
-        E, sw = lightmap_sh_sample(img, T, N, v8, flags)
-    else:
-        levels, masks, T, D, N, shape = checked
-        E, sw = lightmap_sh_sample_lod(levels, T, N, D, masks, flags)
-    return E.reshape(shape + (3,)), sw.reshape(shape)
+    return _sample_level_form(check_lightmap_packed(packed_chain, format, uv, lod, valid_chain, flags, normals, sh=True)[1], lod, True)
 
 
 # ---- BC6H lightmaps: a block encoder, the decoder, lookups that read blocks (mi_lightmap_bc6h_encode, _decode, mi_lightmap_sample_bc6h) ----
@@ -1646,29 +1641,14 @@ def check_lightmap_bc6h(blocks_chain, width: int, height: int, uv, lod=None, val
     layout = lightmap_mip_layout(width, height, len(chain))
     blocks = [_check_bc6h_blocks(b, wl, hl) for b, (wl, hl, _) in zip(chain, layout)]
     levels = [lightmap_bc6h_decode(b, wl, hl) for b, (wl, hl, _) in zip(blocks, layout)]
-    if lod is not None:
-        return blocks, check_lightmap_lod(levels, uv, lod, valid_chain, flags)
-    if len(levels) != 1:
-        raise ValueError(f"lod None reads level 0 alone: {len(levels)} levels were given")
-    if isinstance(valid_chain, (list, tuple)):
-        if len(valid_chain) != 1:
-            raise ValueError("lod None reads level 0 alone: valid_chain must be None, one mask or a list of one")
-        valid_chain = valid_chain[0]
-    return blocks, check_lightmap_lookup(levels[0], uv, valid_chain, flags)
+    return blocks, _check_level_form(levels, uv, lod, valid_chain, flags)
 
 
 def lightmap_sample_bc6h(blocks_chain, width: int, height: int, uv, lod=None, valid_chain=None, flags: int = 0):
     """Read a BC6H lightmap at uv points on the host (numpy only).  This is the DEFINITION of mi_lightmap_sample_bc6h: decode every
     level, then lightmap_sample_lod — or, with lod None, lightmap_sample of the one level (bilinear or abi.MI_LS_NEAREST).  Arguments as
     check_lightmap_bc6h.  Returns (out [..., 3] f32, weight [...] f32)."""
-    _, checked = check_lightmap_bc6h(blocks_chain, width, height, uv, lod, valid_chain, flags)
-    if lod is None:
-        img, T, v8, flags, _, shape = checked
-        out, sw = lightmap_sample(img, T, v8, flags)
-    else:
-        levels, masks, T, D, _, shape = checked
-        out, sw = lightmap_sample_lod(levels, T, D, masks, flags)
-    return out.reshape(shape + (3,)), sw.reshape(shape)
+    return _sample_level_form(check_lightmap_bc6h(blocks_chain, width, height, uv, lod, valid_chain, flags)[1], lod)
 
 
 class Bc6hLightmap:
@@ -2176,13 +2156,32 @@ class Context:
         """mi_lightmap_sample: the helper lightmap_sample on the GPU, bit for bit: `image` [H, W, 3], [H, W, 27] or [H, W, 9, 3] f32 read
         at `uv` [..., 2], bilinear over the texels `valid` ([H, W], None = all) lets take part, or with abi.MI_LS_NEAREST the reference's
         nearest texel.  Returns (out [..., C] f32, weight [...] f32).  No scene is needed."""
-        img, T, v8, flags, _, shape = check_lightmap_lookup(image, uv, valid, flags)
+        return self._lookup("sample", check_lightmap_lookup(image, uv, valid, flags), None, chain_args=False)
+
+    def _lookup(self, name, checked, lod, sh=False, stored=None, fmt=None, chain_args=True, channels_arg=True):
+        """One host lookup through mi_lightmap_<name>: the buffers, None as NULL, the call, the reshape.  `checked`: what
+        check_lightmap_lookup (lod None: level 0 alone) or check_lightmap_lod returned; `stored`: the levels as the call reads them where
+        they are not the f32 levels checked (packed texels, blocks); `fmt`: the packed calls' format argument; chain_args: the call
+        takes levels, mips, mip_valid and lod (all but the two level-0 calls); channels_arg: a plain call takes a channel count (all
+        but BC6H's)."""
+        if lod is None:
+            img, T, v0, flags, N, shape = checked
+            stored, L, mips, mv, D = stored or [img], 1, None, None, None
+        else:
+            levels, masks, T, D, N, shape = checked
+            stored, img, flags, L = stored or levels, levels[0], 0, len(levels)
+            v0 = None if masks[0] is None else np.ascontiguousarray(masks[0], np.uint8)
+            mv = None if L < 2 or masks[1] is None else _lmm_pack(masks, np.uint8)
+            mips = _lmm_pack(stored, stored[0].dtype, stored[0].shape[2:])
         H, W, ch = img.shape
-        out = np.empty((len(T), ch), np.float32)
+        out = np.empty((len(T), 3 if sh else ch), np.float32)
         weight = np.empty(len(T), np.float32)
-        abi.check(self._lib.mi_lightmap_sample(self._h, W, H, ch, img.ctypes.data, None if v8 is None else v8.ctypes.data, len(T),
-                                               T.ctypes.data, flags, out.ctypes.data, weight.ctypes.data))
-        return out.reshape(shape + (ch,)), weight.reshape(shape)
+        ptr = lambda a: None if a is None else a.ctypes.data
+        args = (() if fmt is None else (fmt,)) + (W, H) + ((ch,) if channels_arg and not sh else ()) + (stored[0].ctypes.data, ptr(v0))
+        args += ((L, ptr(mips), ptr(mv)) if chain_args else ()) + (len(T), T.ctypes.data) + ((N.ctypes.data,) if sh else ())
+        args += ((ptr(D),) if chain_args else ()) + (flags, out.ctypes.data, weight.ctypes.data)
+        abi.check(getattr(self._lib, "mi_lightmap_" + name)(self._h, *args))
+        return out.reshape(shape + out.shape[1:]), weight.reshape(shape)
 
     def lightmap_sample_device(self, width: int, height: int, channels: int, d_image: int, n: int, d_uv: int, d_out: int,
                                d_weight: Optional[int] = None, d_valid: Optional[int] = None, flags: int = 0,
@@ -2199,15 +2198,10 @@ class Context:
         they stand).  Returns (E [..., 3] f32, weight [...] f32).  No scene is needed."""
         if normals is None:
             raise ValueError("normals are required")
-        img, T, v8, flags, N, shape = check_lightmap_lookup(sh, uv, valid, flags, normals)
-        if img.shape[2] != 27:
+        checked = check_lightmap_lookup(sh, uv, valid, flags, normals)
+        if checked[0].shape[2] != 27:
             raise ValueError(f"sh must be [H, W, 9, 3] or [H, W, 27], got {np.shape(sh)}")
-        H, W = img.shape[:2]
-        E = np.empty((len(T), 3), np.float32)
-        weight = np.empty(len(T), np.float32)
-        abi.check(self._lib.mi_lightmap_sh_sample(self._h, W, H, img.ctypes.data, None if v8 is None else v8.ctypes.data, len(T),
-                                                  T.ctypes.data, N.ctypes.data, flags, E.ctypes.data, weight.ctypes.data))
-        return E.reshape(shape + (3,)), weight.reshape(shape)
+        return self._lookup("sh_sample", checked, None, sh=True, chain_args=False)
 
     def lightmap_sh_sample_device(self, width: int, height: int, d_sh: int, n: int, d_uv: int, d_normals: int, d_irradiance: int,
                                   d_weight: Optional[int] = None, d_valid: Optional[int] = None, flags: int = 0,
@@ -2252,15 +2246,7 @@ class Context:
         """mi_lightmap_sample_lod: the helper lightmap_sample_lod on the GPU, bit for bit: the chain lightmap_mips returned (levels and
         masks, per level) read at `uv` [..., 2] and `lod` (a scalar or uv's leading shape), trilinear over the valid texels.  Returns
         (out [..., C] f32, weight [...] f32).  No scene is needed."""
-        levels, masks, T, D, _, shape = check_lightmap_lod(chain, uv, lod, valid_chain, flags)
-        H, W, ch = levels[0].shape
-        v0, mips, mv = _lod_buffers(levels, masks)
-        out = np.empty((len(T), ch), np.float32)
-        weight = np.empty(len(T), np.float32)
-        abi.check(self._lib.mi_lightmap_sample_lod(self._h, W, H, ch, levels[0].ctypes.data, None if v0 is None else v0.ctypes.data,
-                                                   len(levels), mips.ctypes.data, None if mv is None else mv.ctypes.data, len(T),
-                                                   T.ctypes.data, D.ctypes.data, flags, out.ctypes.data, weight.ctypes.data))
-        return out.reshape(shape + (ch,)), weight.reshape(shape)
+        return self._lookup("sample_lod", check_lightmap_lod(chain, uv, lod, valid_chain, flags), lod)
 
     def lightmap_sample_lod_device(self, width: int, height: int, channels: int, d_image: int, levels: int, d_mips: Optional[int], n: int,
                                    d_uv: int, d_lod: int, d_out: int, d_weight: Optional[int] = None, d_valid: Optional[int] = None,
@@ -2276,18 +2262,10 @@ class Context:
         lightmap's mip chain at `uv` [..., 2], the normals [..., 3] there and `lod`.  Returns (E [..., 3] f32, weight [...] f32)."""
         if normals is None:
             raise ValueError("normals are required")
-        levels, masks, T, D, N, shape = check_lightmap_lod(chain, uv, lod, valid_chain, flags, normals)
-        if levels[0].shape[2] != 27:
+        checked = check_lightmap_lod(chain, uv, lod, valid_chain, flags, normals)
+        if checked[0][0].shape[2] != 27:
             raise ValueError(f"the levels must be [H, W, 9, 3] or [H, W, 27], got {np.shape(chain[0])}")
-        H, W = levels[0].shape[:2]
-        v0, mips, mv = _lod_buffers(levels, masks)
-        E = np.empty((len(T), 3), np.float32)
-        weight = np.empty(len(T), np.float32)
-        abi.check(self._lib.mi_lightmap_sh_sample_lod(self._h, W, H, levels[0].ctypes.data, None if v0 is None else v0.ctypes.data,
-                                                      len(levels), mips.ctypes.data, None if mv is None else mv.ctypes.data, len(T),
-                                                      T.ctypes.data, N.ctypes.data, D.ctypes.data, flags, E.ctypes.data,
-                                                      weight.ctypes.data))
-        return E.reshape(shape + (3,)), weight.reshape(shape)
+        return self._lookup("sh_sample_lod", checked, lod, sh=True)
 
     def lightmap_sh_sample_lod_device(self, width: int, height: int, d_sh: int, levels: int, d_mips: Optional[int], n: int, d_uv: int,
                                       d_normals: int, d_lod: int, d_irradiance: int, d_weight: Optional[int] = None,
@@ -2331,31 +2309,12 @@ class Context:
         """mi_lightmap_unpack_device: the same for packed texels held on the device (raw pointers).  Queued on `stream`."""
         abi.check(self._lib.mi_lightmap_unpack_device(self._h, format, channels, n_texels, d_packed, d_texels, stream))
 
-    def _packed_lookup(self, entry, packed, checked, fmt, lod, sh):
-        """One packed lookup through the host form `entry`: `packed`, `checked` as check_lightmap_packed returned them"""
-        if lod is None:
-            img, T, v0, flags, N, shape = checked
-            L, mips, mv, D = 1, None, None, None
-        else:
-            levels, masks, T, D, N, shape = checked
-            img, flags, L = levels[0], 0, len(levels)
-            v0 = None if masks[0] is None else np.ascontiguousarray(masks[0], np.uint8)
-            mv = None if L < 2 or masks[1] is None else _lmm_pack(masks, np.uint8)
-            mips = _lmm_pack(packed, packed[0].dtype, packed[0].shape[2:])
-        H, W, ch = img.shape
-        out = np.empty((len(T), 3 if sh else ch), np.float32)
-        weight = np.empty(len(T), np.float32)
-        ptr = lambda a: None if a is None else a.ctypes.data
-        head = (self._h, fmt, W, H) + (() if sh else (ch,)) + (packed[0].ctypes.data, ptr(v0), L, ptr(mips), ptr(mv), len(T), T.ctypes.data)
-        abi.check(entry(*head, *((N.ctypes.data,) if sh else ()), ptr(D), flags, out.ctypes.data, weight.ctypes.data))
-        return out.reshape(shape + out.shape[1:]), weight.reshape(shape)
-
     def lightmap_sample_packed(self, packed_chain, format, uv, lod=None, valid_chain=None, flags: int = 0):
         """mi_lightmap_sample_packed: the helper lightmap_sample_packed on the GPU, bit for bit: packed levels (a list as lightmap_pack
         returns them per level, or one array) read at `uv` [..., 2], trilinearly at `lod`, or with lod None level 0 alone (bilinear or
         abi.MI_LS_NEAREST).  Returns (out [..., C] f32, weight [...] f32)."""
         packed, checked = check_lightmap_packed(packed_chain, format, uv, lod, valid_chain, flags)
-        return self._packed_lookup(self._lib.mi_lightmap_sample_packed, packed, checked, int(format), lod, False)
+        return self._lookup("sample_packed", checked, lod, stored=packed, fmt=int(format))
 
     def lightmap_sample_packed_device(self, format: int, width: int, height: int, channels: int, d_image: int, levels: int,
                                       d_mips: Optional[int], n: int, d_uv: int, d_lod: Optional[int], d_out: int,
@@ -2371,7 +2330,7 @@ class Context:
         """mi_lightmap_sh_sample_packed: the helper lightmap_sh_sample_packed on the GPU, bit for bit: the irradiance of a directional
         lightmap packed as abi.MI_LP_F16 at `uv`, the normals there and `lod` (None: level 0 alone).  Returns (E [..., 3], weight [...])."""
         packed, checked = check_lightmap_packed(packed_chain, format, uv, lod, valid_chain, flags, normals, sh=True)
-        return self._packed_lookup(self._lib.mi_lightmap_sh_sample_packed, packed, checked, int(format), lod, True)
+        return self._lookup("sh_sample_packed", checked, lod, sh=True, stored=packed, fmt=int(format))
 
     def lightmap_sh_sample_packed_device(self, format: int, width: int, height: int, d_sh: int, levels: int, d_mips: Optional[int], n: int,
                                          d_uv: int, d_normals: int, d_lod: Optional[int], d_irradiance: int,
@@ -2422,21 +2381,7 @@ class Context:
         returns it, or one array) of a width x height lightmap read at `uv` [..., 2], trilinearly at `lod`, or with lod None level 0 alone
         (bilinear or abi.MI_LS_NEAREST).  Returns (out [..., 3] f32, weight [...] f32)."""
         blocks, checked = check_lightmap_bc6h(blocks_chain, width, height, uv, lod, valid_chain, flags)
-        if lod is None:
-            _, T, v0, flags, _, shape = checked
-            L, mips, mv, D = 1, None, None, None
-        else:
-            _, masks, T, D, _, shape = checked
-            flags, L = 0, len(blocks)
-            v0 = None if masks[0] is None else np.ascontiguousarray(masks[0], np.uint8)
-            mv = None if L < 2 or masks[1] is None else _lmm_pack(masks, np.uint8)
-            mips = _lmm_pack(blocks, np.uint8, (16,))
-        out = np.empty((len(T), 3), np.float32)
-        weight = np.empty(len(T), np.float32)
-        ptr = lambda a: None if a is None else a.ctypes.data
-        abi.check(self._lib.mi_lightmap_sample_bc6h(self._h, int(width), int(height), blocks[0].ctypes.data, ptr(v0), L, ptr(mips), ptr(mv), len(T),
-                                                    T.ctypes.data, ptr(D), flags, out.ctypes.data, weight.ctypes.data))
-        return out.reshape(shape + (3,)), weight.reshape(shape)
+        return self._lookup("sample_bc6h", checked, lod, stored=blocks, channels_arg=False)
 
     def lightmap_sample_bc6h_device(self, width: int, height: int, d_image_blocks: int, levels: int, d_mip_blocks: Optional[int], n: int,
                                     d_uv: int, d_lod: Optional[int], d_out: int, d_weight: Optional[int] = None, d_valid: Optional[int] = None,
